@@ -11,8 +11,10 @@ Workload at N=1 (BASELINE.json configs[1], SURVEY.md 8d "Config 2"): one synthet
 E events x cams {0,1} x F=41 frames of 1280x1024 u8, resident in HBM before the timed region.
 A "step" is one pass of the detect path over the whole run.  Steps are software-pipelined (--inflight, default 6:
 host.PipelineRing): the host stages of step k run while the GPU works on step k+1; all K steps of a block start
-and finish inside that block's timed region.  The K-step block (barrier + synchronize on both sides, max over
-ranks) is repeated until --min-seconds have been measured; `ms_per_step` / `value` are the MEDIAN block.
+and finish inside that block's timed region.  The timed region is ONE block of exactly K steps (barrier + synchronize on
+both sides, max over ranks); `ms_per_step` is that block's time over K.  With --min-seconds S > 0 the block is repeated
+until S seconds have been measured and `ms_per_step` / `value` are the MEDIAN block.
+--dump-outputs DIR writes the per-stack results of the last timed step as DIR/<name>.npy (float64).
 
 Also reported (config.microbench): BASELINE configs[2], the fused kernel alone on a 10k-frame slab, store mode and
 trigger-only mode, bound-and-verify and the plain row machine (the dense-regime worst case).
@@ -55,8 +57,9 @@ def parse(argv=None):
     ap.add_argument("--stream-steps", type=int, default=10,
                     help="runs streamed from pinned host memory, two in flight (BASELINE configs[4] on this GPU: PCIe-inclusive "
                          "rate, reported in config only; 0 = skip)")
-    ap.add_argument("--min-seconds", type=float, default=2.0,
-                    help="repeat the timed K-step block until this much time has been measured (0 = one block)")
+    ap.add_argument("--min-seconds", type=float, default=0.0,
+                    help="repeat the timed K-step block until this much time has been measured (0 = one block: exactly "
+                         "--steps timed steps)")
     ap.add_argument("--max-blocks", type=int, default=400)
     ap.add_argument("--micro-frames", type=int, default=10000,
                     help="frames of the configs[2] kernel microbench slab (0 = skip)")
@@ -74,7 +77,14 @@ def parse(argv=None):
     ap.add_argument("--dry", action="store_true",
                     help="no GPU work: every rank only walks the launch / barrier / max-over-ranks / report protocol "
                          "(rehearsal of the multi-rank path on CPU with ABUB_BENCH_BACKEND=gloo)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the results of the last timed step (rank 0's stacks) as DIR/<name>.npy")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.dry:
+        ap.error("--dump-outputs needs the real path (not --dry)")
+    return args
 
 
 def self_launch(args):
@@ -316,6 +326,9 @@ def main():
     if not args.dry:
         for p_ in pipes[:max(1, min(ninfl, args.steps))]:
             assert p_.summary() == fingerprint, "results changed between steps"
+        if args.dump_outputs and rank == 0:
+            # the last timed step ran on pipeline (K - 1) % N; the legs below run more steps on the same pipelines
+            dump_outputs(args.dump_outputs, pipes[(args.steps - 1) % ninfl], ev_ids, C)
     n_trig = sum(1 for r in fingerprint if r[0] == 0)
     n_bub = sum(r[2] for r in fingerprint)
 
@@ -516,6 +529,38 @@ def main():
     if dist:
         dist.barrier()  # all ranks leave together
         dist.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(outdir, pipe, ev_ids, C):
+    """What a caller of the detect path receives for every stack of the run (host.Pipeline.result), as float64 arrays:
+    stacks.npy       [S, 9]  event, cam, staged, trig, status, loc_thres, ok, nbubbles, has_error
+    bubble_desc.npy  [D, 14] stack, bubble, descriptor index, then host.DESC_KEYS (x y w h area radius m00 m10 m01 cx cy)
+    bubble_rates.npy [B, 4]  stack, bubble, dzdt, drdt"""
+    import numpy as np
+
+    from autobub3hs_amd import host
+
+    stacks, descs, rates = [], [], []
+    for s in range(pipe.S):
+        staged, st, bubbles, err = pipe.result(s)
+        stacks.append((ev_ids[s // C], s % C, staged, st["trig"], st["status"], st["loc_thres"], st["ok"], len(bubbles),
+                       bool(err)))
+        for b, bub in enumerate(bubbles):
+            rates.append((s, b, bub["dzdt"], bub["drdt"]))
+            for d, dd in enumerate(bub["desc"]):
+                descs.append((s, b, d) + tuple(dd[k] for k in host.DESC_KEYS))
+    arrays = {"stacks": np.array(stacks, dtype=np.float64).reshape(-1, 9),
+              "bubble_desc": np.array(descs, dtype=np.float64).reshape(-1, 3 + len(host.DESC_KEYS)),
+              "bubble_rates": np.array(rates, dtype=np.float64).reshape(-1, 4)}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (limit {DUMP_LIMIT_BYTES})")
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
 
 
 def png_decode_leg(torch, slab, C, F, W, H):

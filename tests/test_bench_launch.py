@@ -59,3 +59,45 @@ def test_stdout_is_exactly_one_json_line():
     assert p.returncode == 0, p.stderr[-2000:]
     lines = p.stdout.splitlines()
     assert len(lines) == 1 and json.loads(lines[0])["metric"]
+
+
+def test_steps_is_the_number_of_timed_steps():
+    """Without --min-seconds the timed region is one block of exactly --steps steps."""
+    p = _run(["--dry", "--steps", "5", "--warmup", "1"])
+    assert p.returncode == 0, p.stderr[-2000:]
+    out = json.loads(p.stdout.strip().splitlines()[-1])
+    t = out["config"]["timing"]
+    assert out["steps"] == 5 and t["blocks"] == 1 and t["steps_per_block"] == 5
+    assert abs(out["ms_per_step"] - t["timed_seconds"] / 5 * 1e3) < 1e-9
+
+
+def test_dump_outputs_refuses_dry_and_zero_steps():
+    assert _run(["--dry", "--dump-outputs", "x"]).returncode == 2
+    assert _run(["--dry", "--steps", "0"]).returncode == 2
+
+
+def test_dump_outputs_layout(tmp_path):
+    """bench.dump_outputs writes every stack's result (host.Pipeline.result) as float64 arrays."""
+    import numpy as np
+
+    import bench
+    from autobub3hs_amd import host
+
+    class FakePipe:
+        S = 4
+
+        def result(self, s):
+            desc = dict(zip(host.DESC_KEYS, [10.0 * s + k for k in range(len(host.DESC_KEYS))]))
+            bubbles = [{"desc": [desc, desc], "dzdt": 0.5 * s, "drdt": -0.25}] * (s % 2)
+            return s % 3, {"trig": 20 + s, "status": 0, "ok": True, "loc_thres": 7}, bubbles, "" if s else "err"
+
+    bench.dump_outputs(str(tmp_path / "out"), FakePipe(), [5, 9], 2)
+    st = np.load(tmp_path / "out" / "stacks.npy")
+    de = np.load(tmp_path / "out" / "bubble_desc.npy")
+    ra = np.load(tmp_path / "out" / "bubble_rates.npy")
+    assert st.dtype == de.dtype == ra.dtype == np.float64
+    assert st.tolist() == [[5, 0, 0, 20, 0, 7, 1, 0, 1], [5, 1, 1, 21, 0, 7, 1, 1, 0],
+                           [9, 0, 2, 22, 0, 7, 1, 0, 0], [9, 1, 0, 23, 0, 7, 1, 1, 0]]
+    assert de.shape == (4, 3 + len(host.DESC_KEYS)) and de[:, :3].tolist() == [[1, 0, 0], [1, 0, 1], [3, 0, 0], [3, 0, 1]]
+    assert de[2, 3:].tolist() == [30.0 + k for k in range(len(host.DESC_KEYS))]
+    assert ra.tolist() == [[1, 0, 0.5, -0.25], [3, 0, 1.5, -0.25]]

@@ -67,17 +67,22 @@ def test_bmp_decode_matches_pillow():
         assert np.array_equal(got, exp), mode
 
 
-REF = "/root/reference/cam_masks/40l-19"
+# one file of each kind in the reference's sample data (cam_masks/40l-19): an 8-bit grey-palette frame and bellows
+# template (PNG) as its camera software wrote them, and windows of a 1-bit fiducial mask (cam1_mask.bmp, x 1352..1551,
+# y 880..999) and of an 8-bit grey bellows mask with anti-aliased edges (cam1_bellows_mask.bmp, x 1338..1679, y 128..255).
+# The masks are cut down to keep the repository small: header layout and palette are the originals', only the size
+# fields differ, rows are padded to 4 bytes as BMP requires, and each window crosses the mask's edge.
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+SAMPLES = ("sample_40l19_cam1_image30.png", "sample_40l19_cam1_bellows_template.png", "sample_40l19_cam1_mask.bmp",
+           "sample_40l19_cam1_bellows_mask.bmp")
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference sample images are not on this machine")
 def test_reference_sample_frames_and_masks_decode_like_pillow():
-    for name in sorted(os.listdir(REF)):
-        if not name.endswith((".png", ".bmp")):
-            continue
-        data = open(os.path.join(REF, name), "rb").read()
+    for name in SAMPLES:
+        path = os.path.join(GOLDEN, name)
+        data = open(path, "rb").read()
         got = host.imdecode(data, cap=1 << 23)
-        exp = np.array(Image.open(os.path.join(REF, name)).convert("L"))
+        exp = np.array(Image.open(path).convert("L"))
         assert got is not None and got.shape == exp.shape, name
         assert np.array_equal(got, exp), name
 
