@@ -157,7 +157,7 @@ class Run:
 
     def run_batched(self, ncams, outdir, run_number, frame_offset, maskdir="", ngpus=1, nthreads=16, decode_threads=16,
                     batch_mb=0, shard=(0, 1)):
-        """Every event of this run through the batched GPU pipeline (host/pipeline.cpp RunBatched): frames decoded (PNG files: on the GPU, abub_png_decode_dev; ABUB_GPU_DECODE=0: by host threads into pinned
+        """Every event of this run through the batched GPU pipeline (host/runbatch.cpp RunBatched): frames decoded (PNG files: on the GPU, abub_png_decode_dev; ABUB_GPU_DECODE=0: by host threads into pinned
         batches), detect, blocks appended to <outdir>abub3hs_<run>.txt in event order.  -> stats dict."""
         L = lib()
         L.abh_run_batched.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p] + [C.c_int] * 7 + [_dp]

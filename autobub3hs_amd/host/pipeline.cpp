@@ -11,7 +11,6 @@
 //   stacks whose trigger produced no accepted bubble go round again from the next frame.
 #include <algorithm>
 #include <atomic>
-#include <chrono>
 #include <condition_variable>
 #include <deque>
 #include <functional>
@@ -36,20 +35,12 @@
 #include "PICOFormatWriter/PICOFormatWriterV4.hpp"
 #include "devctx.hpp"
 #include "hostlogic.hpp"
-#include "pngwalk.hpp"
-#include "runbatch.hpp"
+#include "pipeline.hpp"
 
 namespace abub {
 extern bool g_quietAnalyzers;
 
 namespace {
-
-#define HIPOK(x)                                                                          \
-    do {                                                                                  \
-        hipError_t e_ = (x);                                                              \
-        if (e_ != hipSuccess)                                                             \
-            throw std::runtime_error(std::string(#x) + ": " + hipGetErrorString(e_));     \
-    } while (0)
 
 struct PlannedImage {
     int kind; // 0 = D(i; ref) (genesis), 1 = post-trigger image of frame i
@@ -166,18 +157,6 @@ struct StackState {
     int trig = 0, status = 0, loc_thres = 3, ok = 1;
 };
 
-} // namespace
-
-// What a batched driver knows about one (event, camera) stack that came from a Parser: the reference's event id,
-// the real frame names in the Parser's order and which of them decoded (host/runbatch: RunBatched)
-struct StackMeta {
-    std::string eventID;
-    std::vector<std::string> names;
-    std::vector<uint8_t> ok;
-};
-
-namespace {
-
 // Persistent worker pool shared by all stack groups: a group that is waiting for the GPU lends its
 // threads to the groups that are in their host stages (no per-call thread creation either).
 class WorkerPool {
@@ -279,11 +258,6 @@ private:
     bool stop = false;
 };
 
-double nowMs()
-{
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
 } // namespace
 
 // One slice of the run with its own stream and scratch: groups run concurrently on host threads, so the
@@ -362,6 +336,33 @@ public:
                 throw std::runtime_error("RunPipeline::setStackMeta: stack longer than the pipeline's frame count");
             metaParser.AddNamedFrames(meta[s].eventID, s % C, meta[s].names);
         }
+    }
+    // event k's cameras of the last run staged into `out` and written: the analyzers are gone, so the track records are
+    // rebuilt from the results (and freed once the block is written)
+    void writeEvent(int k, int eventNumber, OutputWriter &out)
+    {
+        std::vector<std::vector<bubble *>> owned(C);
+        for (int c = 0; c < C; ++c) {
+            StackState &ss = stacks[(size_t)k * C + c];
+            if (!ss.error.empty())
+                std::cout << ss.error << '\n'; // (AnyCamAnalysis prints the exception text, then stages -6)
+            if (ss.staged == 0) {
+                for (BubbleOut &bo : ss.bubbles) {
+                    bubble *bb = new bubble(bo.desc[0]);
+                    for (size_t d = 1; d < bo.desc.size(); ++d) {
+                        bb->lockThisIteration = false;
+                        *bb << bo.desc[d];
+                    }
+                    owned[c].push_back(bb);
+                }
+                out.stageCameraOutput(owned[c], c, ss.trig, eventNumber);
+            } else
+                out.stageCameraOutputError(c, ss.staged, eventNumber);
+        }
+        out.writeCameraOutput();
+        for (auto &l : owned)
+            for (bubble *bb : l)
+                delete bb;
     }
     // trigger-search job of frame i of stack s (FindTriggerFrame's pairing: ref = max(i - off, 0), off = 1 when the model
     // was trained on fewer than 6 frames, AnalyzerUnit.cpp:185-188).  Frames a shorter stack does not have are replaced
@@ -1173,709 +1174,19 @@ private:
     }
 };
 
-// ------------------------------------------------------------------------------------------------------------------
-// RunBatched: a run from a Parser through the batched pipeline (see runbatch.hpp).  Replaces the detect loop of the
-// reference's main program (AutoBubStart3.cpp:338-388): same per-(event, camera) analyses, same output blocks in the
-// same order, but the frames of a whole batch of events are decoded once (the reference decodes a frame up to three
-// times: main loop, look-ahead, localizer), uploaded once and processed with a handful of launches.
-// ------------------------------------------------------------------------------------------------------------------
-int RunBatched(Parser *parser, const std::vector<std::string> &EventList, const std::vector<Trainer *> &Trainers,
-               int numCams, const std::string &out_dir, const std::string &run_number, int frameOffset,
-               const BatchedRunOptions &opt, BatchedRunStats *stats, std::string *why)
+void RunPipelineDelete::operator()(RunPipeline *p) const { delete p; }
+
+RunPipelinePtr newRunPipeline(int device, int W, int H, int F, int E, int C, const int *tss, int nthreads, const char *maskDir)
 {
-    const double tAll = nowMs();
-    auto refuse = [&](const char *msg) {
-        if (why)
-            *why = msg;
-        return 1;
-    };
-    const int C = numCams;
-    if (C <= 0 || (int)Trainers.size() != C)
-        return refuse("one trainer per camera expected");
-    const int W = Trainers[0]->TrainedAvgImage.cols, H = Trainers[0]->TrainedAvgImage.rows;
-    if (W <= 0 || H <= 0)
-        return refuse("untrained model");
-    for (Trainer *t : Trainers)
-        if (t->TrainedAvgImage.cols != W || t->TrainedAvgImage.rows != H || t->TrainedSigmaImage.cols != W ||
-            t->TrainedSigmaImage.rows != H)
-            return refuse("cameras with different image sizes");
-    const size_t P = (size_t)W * H;
-    std::vector<int> mine; // indices into EventList handled by this process
-    for (int i = 0; i < (int)EventList.size(); ++i)
-        if (opt.shardWorld <= 1 || i % opt.shardWorld == opt.shardRank)
-            mine.push_back(i);
-    BatchedRunStats st;
-    st.W = W;
-    st.H = H;
-    st.events = (int)mine.size();
-    if (mine.empty()) {
-        if (stats)
-            *stats = st;
-        return 0;
-    }
-    const int ndec = std::max(1, opt.decodeThreads);
-
-    // ---- frame lists of every (event, camera), in the Parser's (lexicographic) order -------------------------------
-    double t0 = nowMs();
-    std::vector<std::vector<std::vector<std::string>>> lists(mine.size(), std::vector<std::vector<std::string>>(C));
-    {
-        std::atomic<size_t> next{0};
-        std::vector<std::thread> th;
-        for (int t = 0; t < std::min<int>(ndec, (int)mine.size()); ++t)
-            th.emplace_back([&]() {
-                std::unique_ptr<Parser> p(parser->clone());
-                for (;;) {
-                    const size_t k = next.fetch_add(1);
-                    if (k >= mine.size())
-                        break;
-                    for (int c = 0; c < C; ++c)
-                        p->ParseAndSortFramesInFolder(EventList[mine[k]], c, lists[k][c]);
-                }
-            });
-        for (auto &t : th)
-            t.join();
-    }
-    int Fmax = 1;
-    for (auto &ev : lists)
-        for (auto &l : ev)
-            Fmax = std::max(Fmax, (int)l.size());
-    st.list_s = (nowMs() - t0) * 1e-3;
-    if (Fmax > 1024)
-        return refuse("more than 1024 frames in one stack");
-    st.Fmax = Fmax;
-    const size_t perEvent = (size_t)C * Fmax * P;
-    int G = (int)std::max<size_t>(1, std::min<size_t>(opt.batchBytes / perEvent, mine.size()));
-    // A run that would fit a few batches is cut into at least twelve per GPU (of at least four events): decoding batch
-    // b + 1 then overlaps the GPU work of batch b, and the two pinned slabs stay small -- page-locking 2.6 GB takes about
-    // as long as decoding it on 16 cores (measured: 1.0 s of a 2.8 s run of 96 events with batches of 24).
-    {
-        const int ng = std::max(1, opt.ngpus);
-        const int want = std::max(4, (int)((mine.size() + (size_t)12 * ng - 1) / ((size_t)12 * ng)));
-        G = std::max(1, std::min(G, want));
-    }
-    G = std::min(G, 512);
-    // ---- where the frames are decoded --------------------------------------------------------------------------------
-    // On the GPU (abub_png.hip) when the parser hands out the files as they are stored and the first frame is a PNG the
-    // kernels take; a host thread still reads each file and walks its chunks, and decodes the odd frame the GPU path
-    // refuses.  Otherwise host threads decode every frame (GetImageInto) as before.
-    bool devDecode = opt.gpuDecode != 0 && (W & 3) == 0 && W >= 4 && W <= 2048;
-    if (const char *e = getenv("ABUB_GPU_DECODE"))
-        devDecode = devDecode && atoi(e) != 0;
-    if (devDecode) {
-        devDecode = false;
-        for (size_t k = 0; k < lists.size() && !devDecode; ++k)
-            for (int c = 0; c < C && !devDecode; ++c)
-                if (!lists[k][c].empty()) {
-                    std::unique_ptr<Parser> p(parser->clone());
-                    const long long sz = p->GetImageFileSize(EventList[mine[k]], lists[k][c][0]);
-                    if (sz > 0 && sz < ((long long)1 << 30)) {
-                        std::vector<unsigned char> buf((size_t)sz);
-                        PngInfo info;
-                        devDecode = p->ReadImageFile(EventList[mine[k]], lists[k][c][0], buf.data(), buf.size()) == sz &&
-                                    pngWalk(buf.data(), buf.size(), W, H, info);
-                    }
-                    k = lists.size(); // (one probe decides)
-                    break;
-                }
-    }
-    int Ggpu = 0; // device-decode mode: the first Ggpu events of a batch are decoded on the GPU, the others by the host threads
-    if (devDecode) {
-        // The inflate kernel runs four streams per CU at a time (1024 on an MI355X) and a batch takes as long as its longest
-        // stream: batches carry that many frames for the GPU, not one more.
-        int ncu = 256;
-        {
-            int dev0 = opt.firstDevice, v = 0, nd = 0;
-            if (hipGetDeviceCount(&nd) == hipSuccess && nd > 0 &&
-                hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev0 % nd) == hipSuccess && v > 0)
-                ncu = v;
-        }
-        const int perEv = std::max(1, C * Fmax);
-        const int capG = (int)std::max<size_t>(1, opt.batchBytes / perEvent);
-        Ggpu = std::max(1, std::min((4 * ncu) / perEv, std::min(capG, (int)mine.size())));
-        if (const char *e = getenv("ABUB_GPU_DECODE_EVENTS")) // (tests: a small GPU share)
-            Ggpu = std::max(1, std::min(Ggpu, atoi(e)));
-        // The host threads can decode the frames of a few more events per batch while the GPU works (they only READ the
-        // files otherwise): ABUB_HOST_DECODE_EVENTS=n.  Off by default -- measured on a 96-event run (16 threads): 8.1 k
-        // frames/s without, 7.5 k with n = 4, 7.3 k with n = 8: the first batch's host share is not overlapped with
-        // anything, the GPU decode slows by 10 - 15 % beside 16 busy cores, and a run of eight batches never makes that up.
-        int Ghost = 0;
-        if (const char *e = getenv("ABUB_HOST_DECODE_EVENTS"))
-            Ghost = std::max(0, atoi(e));
-        Ghost = std::max(0, std::min(Ghost, std::min(capG, (int)mine.size()) - Ggpu));
-        G = Ggpu + Ghost;
-    }
-    const int nb = ((int)mine.size() + G - 1) / G;
-    int ndev = 0;
-    HIPOK(hipGetDeviceCount(&ndev));
-    if (ndev <= 0)
-        throw std::runtime_error("RunBatched: no GPU");
-    const int ngpus = std::max(1, std::min(opt.ngpus, nb));
-    st.gpus = ngpus;
-    st.batches = nb;
-    st.eventsPerBatch = G;
-
-    std::mutex turnMu;
-    std::condition_variable turnCv;
-    int turn = 0;       // next batch to be written (output is in event order, AutoBubStart3.cpp:380-383)
-    bool failed = false;
-    std::vector<std::string> errors(ngpus);
-    std::mutex statMu;
-
-    struct Decoded {
-        std::vector<StackMeta> meta;
-        double ms = 0;
-        long long ok = 0, bad = 0;
-    };
-    auto decodeBatch = [&](int b, uint8_t *h, Decoded &out, int nthreads) {
-        const double td = nowMs();
-        const int e0 = b * G, nEv = std::min(G, (int)mine.size() - e0);
-        out.meta.assign((size_t)G * C, StackMeta());
-        std::vector<std::pair<int, int>> tasks;
-        for (int k = 0; k < G; ++k)
-            for (int c = 0; c < C; ++c) {
-                StackMeta &m = out.meta[(size_t)k * C + c];
-                if (k < nEv) {
-                    m.eventID = EventList[mine[e0 + k]];
-                    m.names = lists[e0 + k][c];
-                    m.ok.assign(m.names.size(), 0);
-                    for (int f = 0; f < (int)m.names.size(); ++f)
-                        tasks.emplace_back(k * C + c, f);
-                } else
-                    m.eventID = "_pad" + std::to_string(k); // filler of the last batch: no frames -> -9, never written
-            }
-        std::atomic<size_t> next{0};
-        std::atomic<long long> good{0}, bad{0};
-        std::vector<std::thread> th;
-        for (int t = 0; t < std::max(1, std::min<int>(nthreads, (int)tasks.size())); ++t)
-            th.emplace_back([&]() {
-                std::unique_ptr<Parser> p(parser->clone());
-                for (;;) {
-                    const size_t i = next.fetch_add(1);
-                    if (i >= tasks.size())
-                        break;
-                    const int s = tasks[i].first, f = tasks[i].second;
-                    StackMeta &m = out.meta[s];
-                    uint8_t *dst = h + ((size_t)s * Fmax + f) * P;
-                    int rc = -1;
-                    try {
-                        rc = p->GetImageInto(m.eventID, m.names[f], dst, W, H); // decoded in place, no per-frame allocation
-                    } catch (...) {
-                        rc = -1;
-                    }
-                    // (anything but 1 = undecodable, like EventOnDevice; so is a frame of another size)
-                    if (rc != 1) {
-                        // (its slot would otherwise keep the bytes of an earlier batch or half a decode: results never use
-                        // them, but dense garbage costs the trigger search's kernels time that varies from run to run)
-                        std::memset(dst, 0, P);
-                        ++bad;
-                        continue;
-                    }
-                    m.ok[f] = 1;
-                    ++good;
-                }
-            });
-        for (auto &t : th)
-            t.join();
-        out.ok = good;
-        out.bad = bad;
-        out.ms = nowMs() - td;
-    };
-
-    // ---- device-decode mode: a batch's FILES into one pinned buffer, with what the GPU decoder needs to know about each ----
-    struct Encoded {
-        std::vector<StackMeta> meta;
-        uint8_t *h_files = nullptr; // pinned; grown on demand by the reading thread (its worker's device is current there)
-        size_t cap = 0, bytes = 0;
-        uint8_t *d_files = nullptr; // the reading thread uploads them as soon as they are read: the copy runs beside the GPU
-        size_t dcap = 0;            // work of the batch before
-        hipEvent_t uploaded = nullptr;
-        std::vector<abub_png_frame> desc;        // the frames the GPU decodes
-        std::vector<std::pair<int, int>> where;  // (stack, frame) of desc[i]
-        std::vector<uint32_t> fileOff, fileLen;  // of desc[i] inside h_files
-        std::vector<abub_png_seg> segs;
-        std::vector<uint8_t> luts;               // 256 bytes each
-        size_t zbytes = 0;
-        // frames a host thread decoded while reading (files the GPU path does not take): pixels + (stack, frame)
-        std::vector<std::vector<uint8_t>> hostPix;
-        std::vector<std::pair<int, int>> hostWhere;
-        double ms = 0;
-        long long bad = 0, hostGood = 0;
-    };
-    auto readBatch = [&](int b, Encoded &out, uint8_t *h_host, int nthreads, int dev, hipStream_t upStream) {
-        const double td = nowMs();
-        (void)hipSetDevice(dev);
-        const int e0 = b * G, nEv = std::min(G, (int)mine.size() - e0);
-        out.meta.assign((size_t)G * C, StackMeta());
-        struct Task {
-            int s, f;
-            long long size;
-            size_t off;
-            int state; // 0 = for the GPU, 1 = decoded here, 2 = missing / undecodable
-            PngInfo info;
-            std::vector<uint8_t> pix;
-        };
-        std::vector<Task> tasks, hostTasks; // (the files for the GPU are read first: its work can start before the host's is done)
-        std::unique_ptr<Parser> sizer(parser->clone());
-        size_t total = 0;
-        for (int k = 0; k < G; ++k)
-            for (int c = 0; c < C; ++c) {
-                StackMeta &m = out.meta[(size_t)k * C + c];
-                if (k < nEv) {
-                    m.eventID = EventList[mine[e0 + k]];
-                    m.names = lists[e0 + k][c];
-                    m.ok.assign(m.names.size(), 0);
-                    for (int f = 0; f < (int)m.names.size(); ++f) {
-                        Task t;
-                        t.s = k * C + c;
-                        t.f = f;
-                        if (k >= Ggpu) { // the host threads' share of the batch: decoded straight into the pinned slab
-                            t.size = 0;
-                            t.off = 0;
-                            t.state = 3;
-                            hostTasks.push_back(std::move(t));
-                            continue;
-                        }
-                        t.size = sizer->GetImageFileSize(m.eventID, m.names[f]);
-                        t.state = (t.size > 0 && t.size < ((long long)1 << 30)) ? 0 : 2;
-                        t.off = total;
-                        if (t.state == 0)
-                            total += ((size_t)t.size + 15) & ~(size_t)15;
-                        tasks.push_back(std::move(t));
-                    }
-                } else
-                    m.eventID = "_pad" + std::to_string(k);
-            }
-        total += 16;
-        if (total > out.cap) {
-            if (out.h_files)
-                (void)hipHostFree(out.h_files);
-            out.h_files = nullptr;
-            out.cap = total + total / 4;
-            if (hipHostMalloc((void **)&out.h_files, out.cap, hipHostMallocDefault) != hipSuccess) {
-                out.cap = 0;
-                throw std::runtime_error("RunBatched: hipHostMalloc of the file staging buffer failed");
-            }
-        }
-        out.bytes = total;
-        const size_t nGpuTasks = tasks.size();
-        for (Task &t : hostTasks)
-            tasks.push_back(std::move(t));
-        std::atomic<size_t> next{0};
-        std::atomic<long long> hostGood{0}, hostBad{0};
-        std::vector<std::thread> th;
-        for (int t = 0; t < std::max(1, std::min<int>(nthreads, (int)tasks.size())); ++t)
-            th.emplace_back([&]() {
-                std::unique_ptr<Parser> p(parser->clone());
-                for (;;) {
-                    const size_t i = next.fetch_add(1);
-                    if (i >= tasks.size())
-                        break;
-                    Task &t = tasks[i];
-                    if (t.state == 3) {
-                        StackMeta &hm = out.meta[t.s];
-                        uint8_t *hd = h_host + ((size_t)(t.s - Ggpu * C) * Fmax + t.f) * P;
-                        int rc = -1;
-                        try {
-                            rc = p->GetImageInto(hm.eventID, hm.names[t.f], hd, W, H);
-                        } catch (...) {
-                            rc = -1;
-                        }
-                        if (rc != 1) {
-                            std::memset(hd, 0, P);
-                            ++hostBad;
-                        } else {
-                            hm.ok[t.f] = 1;
-                            ++hostGood;
-                        }
-                        continue;
-                    }
-                    if (t.state != 0)
-                        continue;
-                    const StackMeta &m = out.meta[t.s];
-                    uint8_t *dst = out.h_files + t.off;
-                    long long got = -1;
-                    try {
-                        got = p->ReadImageFile(m.eventID, m.names[t.f], dst, (size_t)t.size);
-                    } catch (...) {
-                        got = -1;
-                    }
-                    if (got != t.size) {
-                        t.state = 2;
-                        continue;
-                    }
-                    try {
-                        if (!pngWalk(dst, (size_t)t.size, W, H, t.info)) {
-                            // not a file for the GPU decoder (BMP, 16-bit, colour, interlaced, another size): the host decoder's answer
-                            t.pix.resize(P);
-                            t.state = cv::imdecodeInto(dst, (size_t)t.size, t.pix.data(), W, H) ? 1 : 2;
-                        }
-                    } catch (...) { // (an allocation that fails inside a pool thread must not end the process)
-                        t.state = 2;
-                    }
-                }
-            });
-        for (auto &t : th)
-            t.join();
-        out.desc.clear();
-        out.where.clear();
-        out.fileOff.clear();
-        out.fileLen.clear();
-        out.segs.clear();
-        out.luts.clear();
-        out.hostPix.clear();
-        out.hostWhere.clear();
-        out.bad = hostBad;
-        out.hostGood = hostGood;
-        size_t zoff = 0;
-        for (size_t ti = 0; ti < nGpuTasks; ++ti) {
-            Task &t = tasks[ti];
-            if (t.state == 2) {
-                ++out.bad;
-                continue;
-            }
-            if (t.state == 1) {
-                out.hostPix.push_back(std::move(t.pix));
-                out.hostWhere.emplace_back(t.s, t.f);
-                continue;
-            }
-            abub_png_frame d;
-            d.seg_begin = (uint32_t)out.segs.size();
-            d.seg_count = (uint32_t)t.info.segs.size();
-            d.zoff = (uint32_t)zoff;
-            d.zlen = (uint32_t)t.info.zlen;
-            d.lut = 0xffffffffu;
-            d.reserved = 0;
-            d.dst = ((uint64_t)t.s * Fmax + t.f) * P;
-            if (t.info.palette) { // (the frames of a run share their palette: look for the table among those already kept)
-                size_t nl = out.luts.size() / 256, l = 0;
-                for (; l < nl; ++l)
-                    if (!memcmp(&out.luts[l * 256], t.info.lut, 256))
-                        break;
-                if (l == nl)
-                    out.luts.insert(out.luts.end(), t.info.lut, t.info.lut + 256);
-                d.lut = (uint32_t)l;
-            }
-            for (const abub_png_seg &sg : t.info.segs)
-                out.segs.push_back(abub_png_seg{(uint32_t)(t.off + sg.off), sg.len});
-            zoff += (((size_t)d.zlen + 15) & ~(size_t)15) + 16;
-            out.desc.push_back(d);
-            out.where.emplace_back(t.s, t.f);
-            out.fileOff.push_back((uint32_t)t.off);
-            out.fileLen.push_back((uint32_t)t.size);
-        }
-        out.zbytes = zoff + 16;
-        if (out.bytes >= ((size_t)1 << 32) || out.zbytes >= ((size_t)1 << 32))
-            throw std::runtime_error("RunBatched: a batch of more than 4 GB of files (lower the batch size)");
-        if (!out.desc.empty()) {
-            if (out.bytes > out.dcap) {
-                if (out.d_files)
-                    (void)hipFree(out.d_files);
-                out.d_files = nullptr;
-                out.dcap = out.bytes + out.bytes / 4;
-                if (hipMalloc((void **)&out.d_files, out.dcap) != hipSuccess) {
-                    out.dcap = 0;
-                    throw std::runtime_error("RunBatched: hipMalloc of the uploaded files failed");
-                }
-            }
-            if (!out.uploaded && hipEventCreateWithFlags(&out.uploaded, hipEventDisableTiming) != hipSuccess)
-                throw std::runtime_error("RunBatched: hipEventCreate failed");
-            if (hipMemcpyAsync(out.d_files, out.h_files, out.bytes, hipMemcpyHostToDevice, upStream) != hipSuccess ||
-                hipEventRecord(out.uploaded, upStream) != hipSuccess)
-                throw std::runtime_error("RunBatched: upload of the files failed");
-        }
-        out.ms = nowMs() - td;
-    };
-
-    auto writeBatch = [&](RunPipeline &pipe, int b) {
-        const int e0 = b * G, nEv = std::min(G, (int)mine.size() - e0);
-        for (int k = 0; k < nEv; ++k) {
-            OutputWriter out(out_dir, run_number, frameOffset, C);
-            const int actualEventNumber = atoi(EventList[mine[e0 + k]].c_str());
-            std::vector<std::vector<bubble *>> owned(C);
-            for (int c = 0; c < C; ++c) {
-                StackState &ss = pipe.stacks[(size_t)k * C + c];
-                if (!ss.error.empty())
-                    std::cout << ss.error << '\n'; // (AnyCamAnalysis prints the exception text, then stages -6)
-                if (ss.staged == 0) {
-                    for (BubbleOut &bo : ss.bubbles) { // the analyzers are gone: rebuild the track records
-                        bubble *bb = new bubble(bo.desc[0]);
-                        for (size_t d = 1; d < bo.desc.size(); ++d) {
-                            bb->lockThisIteration = false;
-                            *bb << bo.desc[d];
-                        }
-                        owned[c].push_back(bb);
-                    }
-                    out.stageCameraOutput(owned[c], c, ss.trig, actualEventNumber);
-                } else
-                    out.stageCameraOutputError(c, ss.staged, actualEventNumber);
-            }
-            out.writeCameraOutput();
-            for (auto &l : owned)
-                for (bubble *bb : l)
-                    delete bb;
-        }
-    };
-
-    auto worker = [&](int g) {
-        uint8_t *h_slab[2] = {nullptr, nullptr}, *d_slab[2] = {nullptr, nullptr}, *d_model = nullptr;
-        hipStream_t copyStream = nullptr;
-        // The look-ahead decode thread writes decd[] and reads nthr: both live OUTSIDE the try block, so that they outlive
-        // it on every failure path (the thread is joined below, after the catch).
-        Decoded decd[2];
-        Encoded encd[2]; // device-decode mode
-        // device-decode mode: the uploaded files, the decoder's scratch, its descriptors (grown on demand)
-        uint8_t *d_z = nullptr, *d_raw = nullptr, *d_luts = nullptr;
-        hipStream_t upStream = nullptr;
-        abub_png_frame *d_desc = nullptr;
-        abub_png_seg *d_segs = nullptr;
-        int32_t *d_status = nullptr, *h_status = nullptr;
-        size_t capZ = 0, capRaw = 0, capLuts = 0, capDesc = 0, capSegs = 0, capStatus = 0;
-        const int nthr = std::max(1, ndec / ngpus);
-        std::thread dec;
-        std::exception_ptr decErr[2];
-        try {
-            const int dev = (opt.firstDevice + g) % ndev;
-            HIPOK(hipSetDevice(dev));
-            const size_t slabBytes = (size_t)G * perEvent;
-            const int nslots = g + ngpus < nb ? 2 : 1; // a worker with a single batch needs no second buffer
-            for (int k = 0; k < nslots; ++k) {
-                // (device-decode mode uploads files; only the host threads' share of a batch comes as frames)
-                const size_t pinned = devDecode ? (size_t)(G - Ggpu) * perEvent : slabBytes;
-                if (pinned)
-                    HIPOK(hipHostMalloc((void **)&h_slab[k], pinned, hipHostMallocDefault));
-                HIPOK(hipMalloc((void **)&d_slab[k], slabBytes));
-            }
-            auto grow = [&](void **ptr, size_t &cap, size_t need) {
-                if (need <= cap)
-                    return;
-                if (*ptr)
-                    HIPOK(hipFree(*ptr));
-                *ptr = nullptr;
-                cap = need + need / 4 + 256;
-                HIPOK(hipMalloc(ptr, cap));
-            };
-            if (devDecode) {
-                HIPOK(hipHostMalloc((void **)&h_status, (size_t)G * C * Fmax * sizeof(int32_t) + 64, hipHostMallocDefault));
-                HIPOK(hipStreamCreateWithFlags(&upStream, hipStreamNonBlocking));
-            }
-            HIPOK(hipMalloc((void **)&d_model, 3 * (size_t)C * P)); // mu | sigma | sigma6
-            uint8_t *d_mu = d_model, *d_sigma = d_model + (size_t)C * P, *d_s6 = d_model + 2 * (size_t)C * P;
-            HIPOK(hipStreamCreateWithFlags(&copyStream, hipStreamNonBlocking));
-            std::vector<int> tss(C);
-            for (int c = 0; c < C; ++c) {
-                HIPOK(hipMemcpy(d_mu + (size_t)c * P, Trainers[c]->TrainedAvgImage.data, P, hipMemcpyHostToDevice));
-                HIPOK(hipMemcpy(d_sigma + (size_t)c * P, Trainers[c]->TrainedSigmaImage.data, P, hipMemcpyHostToDevice));
-                tss[c] = Trainers[c]->TrainingSetSize;
-            }
-            check(abub_sigma6_dev(d_sigma, d_s6, (size_t)C * P, copyStream), "abub_sigma6_dev");
-            HIPOK(hipStreamSynchronize(copyStream));
-            const bool trace = getenv("ABUB_INGEST_TRACE") != nullptr;
-            if (trace)
-                fprintf(stderr, "worker %d: buffers and model on the device at %.1f ms\n", g, nowMs() - tAll);
-            RunPipeline pipe(dev, W, H, Fmax, G, C, tss.data(), std::max(1, opt.hostThreads), opt.maskDir.c_str());
-            pipe.d_sigmaRaw = d_sigma;
-            if (trace)
-                fprintf(stderr, "worker %d: pipeline of %d events ready at %.1f ms\n", g, G, nowMs() - tAll);
-            int slot = 0;
-            // (an exception of the look-ahead thread -- a failed allocation, a throwing parser -- is carried over and re-thrown here)
-            auto startDecode = [&](int bb, int sl) {
-                decErr[sl] = nullptr;
-                dec = std::thread([&, bb, sl, dev]() { // (dev by value: it lives inside the try block)
-                    try {
-                        if (devDecode)
-                            readBatch(bb, encd[sl], h_slab[sl], nthr, dev, upStream);
-                        else
-                            decodeBatch(bb, h_slab[sl], decd[sl], nthr);
-                    } catch (...) {
-                        decErr[sl] = std::current_exception();
-                    }
-                });
-            };
-            if (g < nb)
-                startDecode(g, slot);
-            if (devDecode) {
-                // (the decoder's scratch while the first batch's files are being read: sizes from the batch's frame count; the
-                // stream buffer from a guess that regrows if a batch proves it wrong)
-                const size_t nfMax = (size_t)std::max(1, Ggpu) * C * Fmax;
-                grow((void **)&d_raw, capRaw, nfMax * abub_png_raw_stride(W, H));
-                grow((void **)&d_desc, capDesc, nfMax * sizeof(abub_png_frame));
-                grow((void **)&d_status, capStatus, nfMax * sizeof(int32_t));
-                grow((void **)&d_z, capZ, nfMax * (P / 4 * 3));
-                if (trace)
-                    fprintf(stderr, "worker %d: decoder scratch ready at %.1f ms\n", g, nowMs() - tAll);
-            }
-            for (int b = g; b < nb; b += ngpus) {
-                const double tj = nowMs();
-                dec.join();
-                if (trace)
-                    fprintf(stderr, "batch %d: waited %.1f ms for its files at %.1f ms\n", b, nowMs() - tj, nowMs() - tAll);
-                if (decErr[slot])
-                    std::rethrow_exception(decErr[slot]);
-                const int bn = b + ngpus;
-                if (bn < nb)
-                    startDecode(bn, slot ^ 1);
-                const int nEv = std::min(G, (int)mine.size() - b * G);
-                const double tg = nowMs();
-                double dms = 0, pngms = 0;
-                long long good = 0, bad = 0, onGpu = 0, onHost = 0;
-                if (!devDecode) {
-                    HIPOK(hipMemcpyAsync(d_slab[slot], h_slab[slot], (size_t)nEv * perEvent, hipMemcpyHostToDevice, copyStream));
-                    dms = decd[slot].ms;
-                    good = decd[slot].ok;
-                    bad = decd[slot].bad;
-                    onHost = good;
-                    pipe.setStackMeta(std::move(decd[slot].meta));
-                } else {
-                    Encoded &E = encd[slot];
-                    const int nf = (int)E.desc.size();
-                    // frames nobody decodes (missing, undecodable) stay zero: results never use them, but dense garbage would
-                    // cost the trigger search's kernels time that varies from run to run
-                    const int nEvGpu = std::min(nEv, Ggpu);
-                    HIPOK(hipMemsetAsync(d_slab[slot], 0, (size_t)nEvGpu * perEvent, copyStream));
-                    if (nEv > nEvGpu) // the events the host threads decoded
-                        HIPOK(hipMemcpyAsync(d_slab[slot] + (size_t)nEvGpu * perEvent, h_slab[slot], (size_t)(nEv - nEvGpu) * perEvent,
-                                             hipMemcpyHostToDevice, copyStream));
-                    const double tp = nowMs();
-                    std::vector<uint8_t> okGpu((size_t)nf, 0);
-                    if (nf) {
-                        const size_t stride = abub_png_raw_stride(W, H);
-                        grow((void **)&d_z, capZ, E.zbytes);
-                        grow((void **)&d_raw, capRaw, (size_t)nf * stride);
-                        grow((void **)&d_desc, capDesc, (size_t)nf * sizeof(abub_png_frame));
-                        grow((void **)&d_segs, capSegs, E.segs.size() * sizeof(abub_png_seg) + 8);
-                        grow((void **)&d_luts, capLuts, E.luts.size() + 256);
-                        grow((void **)&d_status, capStatus, (size_t)nf * sizeof(int32_t));
-                        HIPOK(hipStreamWaitEvent(copyStream, E.uploaded, 0)); // (the reading thread's upload of the files)
-                        HIPOK(hipMemcpyAsync(d_desc, E.desc.data(), (size_t)nf * sizeof(abub_png_frame), hipMemcpyHostToDevice, copyStream));
-                        HIPOK(hipMemcpyAsync(d_segs, E.segs.data(), E.segs.size() * sizeof(abub_png_seg), hipMemcpyHostToDevice, copyStream));
-                        if (!E.luts.empty())
-                            HIPOK(hipMemcpyAsync(d_luts, E.luts.data(), E.luts.size(), hipMemcpyHostToDevice, copyStream));
-                        check(abub_png_decode_dev(E.d_files, E.bytes, d_desc, nf, d_segs, (int)E.segs.size(), d_luts, (int)(E.luts.size() / 256), W,
-                                                  H, d_z, capZ, d_raw, capRaw, d_slab[slot], (size_t)nEv * perEvent, d_status, copyStream),
-                              "abub_png_decode_dev");
-                        HIPOK(hipMemcpyAsync(h_status, d_status, (size_t)nf * sizeof(int32_t), hipMemcpyDeviceToHost, copyStream));
-                        HIPOK(hipStreamSynchronize(copyStream));
-                        for (int i = 0; i < nf; ++i)
-                            okGpu[i] = h_status[i] == 0;
-                    }
-                    // a frame the kernels refused: the host decoder's answer (the same image, or the same failure)
-                    std::vector<uint8_t> pix;
-                    for (int i = 0; i < nf; ++i) {
-                        StackMeta &m = E.meta[E.where[i].first];
-                        if (okGpu[i]) {
-                            m.ok[E.where[i].second] = 1;
-                            ++onGpu;
-                            continue;
-                        }
-                        pix.resize(P);
-                        if (cv::imdecodeInto(E.h_files + E.fileOff[i], E.fileLen[i], pix.data(), W, H)) {
-                            HIPOK(hipMemcpy(d_slab[slot] + E.desc[i].dst, pix.data(), P, hipMemcpyHostToDevice));
-                            m.ok[E.where[i].second] = 1;
-                            ++onHost;
-                        } else {
-                            HIPOK(hipMemset(d_slab[slot] + E.desc[i].dst, 0, P)); // (a refused frame may be half written)
-                            ++E.bad;
-                        }
-                    }
-                    for (size_t i = 0; i < E.hostPix.size(); ++i) {
-                        const size_t at = ((size_t)E.hostWhere[i].first * Fmax + E.hostWhere[i].second) * P;
-                        HIPOK(hipMemcpy(d_slab[slot] + at, E.hostPix[i].data(), P, hipMemcpyHostToDevice));
-                        E.meta[E.hostWhere[i].first].ok[E.hostWhere[i].second] = 1;
-                        ++onHost;
-                    }
-                    onHost += E.hostGood;
-                    pngms = nowMs() - tp;
-                    if (trace)
-                        fprintf(stderr, "batch %d: %d frames for the GPU (%zu MB of files), %lld decoded by host threads, read + host decode %.1f ms, "
-                                        "upload + GPU decode %.1f ms\n", b, nf, E.bytes >> 20, E.hostGood, E.ms, pngms);
-                    dms = E.ms;
-                    good = onGpu + onHost;
-                    bad = E.bad;
-                    pipe.setStackMeta(std::move(E.meta));
-                }
-                if (const char *tf = getenv("ABUB_TEST_FAIL_BATCH")) // test hook: a batch fails while the next one decodes
-                    if (atoi(tf) == b)
-                        throw std::runtime_error("injected failure of batch " + std::to_string(b) + " (ABUB_TEST_FAIL_BATCH)");
-                pipe.run(d_slab[slot], d_mu, d_s6, copyStream); // waits for the upload first
-                const double gms = nowMs() - tg;
-                double wms = 0;
-                {
-                    std::unique_lock<std::mutex> lock(turnMu);
-                    turnCv.wait(lock, [&] { return turn == b || failed; });
-                    if (failed)
-                        break;
-                    const double tw = nowMs();
-                    writeBatch(pipe, b);
-                    wms = nowMs() - tw;
-                    ++turn;
-                }
-                turnCv.notify_all();
-                {
-                    std::lock_guard<std::mutex> lock(statMu);
-                    st.decode_s += dms * 1e-3;
-                    st.gpu_s += gms * 1e-3;
-                    st.write_s += wms * 1e-3;
-                    st.frames += good;
-                    st.framesFailed += bad;
-                    st.framesGpuDecoded += onGpu;
-                    st.framesHostDecoded += onHost;
-                    st.gpudecode_s += pngms * 1e-3;
-                }
-                slot ^= 1;
-            }
-        } catch (std::exception &e) {
-            errors[g] = e.what();
-            {
-                std::lock_guard<std::mutex> lock(turnMu);
-                failed = true;
-            }
-            turnCv.notify_all();
-        }
-        if (dec.joinable())
-            dec.join();
-        if (copyStream)
-            (void)hipStreamDestroy(copyStream);
-        for (int k = 0; k < 2; ++k) {
-            if (h_slab[k])
-                (void)hipHostFree(h_slab[k]);
-            if (d_slab[k])
-                (void)hipFree(d_slab[k]);
-        }
-        if (d_model)
-            (void)hipFree(d_model);
-        if (upStream) {
-            (void)hipStreamSynchronize(upStream);
-            (void)hipStreamDestroy(upStream);
-        }
-        for (Encoded &E : encd) {
-            if (E.d_files)
-                (void)hipFree(E.d_files);
-            if (E.uploaded)
-                (void)hipEventDestroy(E.uploaded);
-        }
-        for (void *q : {(void *)d_z, (void *)d_raw, (void *)d_luts, (void *)d_desc, (void *)d_segs, (void *)d_status})
-            if (q)
-                (void)hipFree(q);
-        if (h_status)
-            (void)hipHostFree(h_status);
-        for (Encoded &E : encd)
-            if (E.h_files)
-                (void)hipHostFree(E.h_files);
-    };
-    std::vector<std::thread> th;
-    for (int g = 1; g < ngpus; ++g)
-        th.emplace_back(worker, g);
-    worker(0);
-    for (auto &t : th)
-        t.join();
-    for (const std::string &e : errors)
-        if (!e.empty())
-            throw std::runtime_error("RunBatched: " + e);
-    st.total_s = (nowMs() - tAll) * 1e-3;
-    if (stats)
-        *stats = st;
-    return 0;
+    return RunPipelinePtr(new RunPipeline(device, W, H, F, E, C, tss, nthreads, maskDir));
 }
+void setSigmaRaw(RunPipeline &p, const uint8_t *d_sigma) { p.d_sigmaRaw = d_sigma; }
+void setStackMeta(RunPipeline &p, std::vector<StackMeta> &&meta) { p.setStackMeta(std::move(meta)); }
+void run(RunPipeline &p, const uint8_t *d_frames, const uint8_t *d_mu, const uint8_t *d_sigma6, hipStream_t stream)
+{
+    p.run(d_frames, d_mu, d_sigma6, stream);
+}
+void writeEvent(RunPipeline &p, int k, int eventNumber, OutputWriter &out) { p.writeEvent(k, eventNumber, out); }
 
 } // namespace abub
 

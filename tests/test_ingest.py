@@ -225,9 +225,14 @@ def test_batched_run_survives_a_failing_batch(tmp_path, monkeypatch):
 def test_batched_run_with_frames_decoded_on_the_gpu(tmp_path, monkeypatch):
     """The batched run decodes PNG frames on the GPU (abub_png_decode_dev) when the parser hands out the files; host threads
     then only read them.  Same text as with host decode, from a directory, a stored and a deflated archive; a 16-bit PNG, a
-    truncated file, an empty file and a frame of another size among the frames take the host decoder's answer."""
+    truncated file, an empty file and a frame of another size among the frames take the host decoder's answer.  Every frame
+    of event 6 is a 16-bit PNG: a batch of that event alone gives the GPU nothing to decode, and the frames the reading
+    threads decoded must still land after the batch's slab is cleared."""
     W, H, F = 320, 128, 20
-    rd, frames = make_run_dir(str(tmp_path), W=W, H=H, F=F, nev=6, ncams=2)
+    rd, frames = make_run_dir(str(tmp_path), W=W, H=H, F=F, nev=7, ncams=2)
+    for (e, c, name), img in frames.items():
+        if e == 6:
+            Image.fromarray(img.astype(np.uint16) << 8).save(os.path.join(rd, "6", "Images", name))  # 16-bit grey
     d3 = os.path.join(rd, "3", "Images")
     Image.fromarray((frames[(3, 0, "cam0_image37.png")].astype(np.uint16) << 8)).save(os.path.join(d3, "cam0_image37.png"))  # 16-bit grey
     data = open(os.path.join(d3, "cam1_image40.png"), "rb").read()
@@ -239,7 +244,7 @@ def test_batched_run_with_frames_decoded_on_the_gpu(tmp_path, monkeypatch):
     zip_run(rd, zs, zipfile.ZIP_STORED)
     zip_run(rd, zd, zipfile.ZIP_DEFLATED)
 
-    def go(kind, src, tag, gpu):
+    def go(kind, src, tag, gpu, batch_mb=2):
         monkeypatch.setenv("ABUB_GPU_DECODE", "1" if gpu else "0")
         outdir = os.path.join(str(tmp_path), tag)
         os.makedirs(outdir, exist_ok=True)
@@ -247,7 +252,7 @@ def test_batched_run_with_frames_decoded_on_the_gpu(tmp_path, monkeypatch):
         try:
             for c in range(2):
                 assert run.train(c, shape=(H, W))[0] == 0
-            st = run.run_batched(2, outdir + "/", "r", 30, nthreads=4, decode_threads=4, batch_mb=2)
+            st = run.run_batched(2, outdir + "/", "r", 30, nthreads=4, decode_threads=4, batch_mb=batch_mb)
         finally:
             run.close()
         return st, open(os.path.join(outdir, "abub3hs_r.txt")).read()
@@ -257,26 +262,25 @@ def test_batched_run_with_frames_decoded_on_the_gpu(tmp_path, monkeypatch):
     for kind, src, tag in (("raw", rd + "/", "gpu_raw"), ("zip", zs, "gpu_stored"), ("zip", zd, "gpu_deflated")):
         st, text = go(kind, src, tag, True)
         assert text == ref, tag
-        assert st["frames_failed"] == 3 and st["frames_host_decoded"] == 1, (tag, st)  # the 16-bit frame
+        assert st["frames_failed"] == 3 and st["frames_host_decoded"] == 1 + 2 * F, (tag, st)  # the 16-bit frames
         assert st["frames_gpu_decoded"] == 6 * 2 * F - 4, (tag, st)
     assert len(ref.splitlines()) >= 12
     # batches shared between the GPU (the first two events of each) and the host threads (the third)
     monkeypatch.setenv("ABUB_GPU_DECODE_EVENTS", "2")
     monkeypatch.setenv("ABUB_HOST_DECODE_EVENTS", "1")
-    outdir = os.path.join(str(tmp_path), "hybrid")
-    os.makedirs(outdir)
-    monkeypatch.setenv("ABUB_GPU_DECODE", "1")
-    run = host.Run("zip", zs, "Images")
-    try:
-        for c in range(2):
-            assert run.train(c, shape=(H, W))[0] == 0
-        st = run.run_batched(2, outdir + "/", "r", 30, nthreads=4, decode_threads=4, batch_mb=64)
-    finally:
-        run.close()
-    assert open(os.path.join(outdir, "abub3hs_r.txt")).read() == ref
-    assert st["events_per_batch"] == 3 and st["batches"] == 3, st  # (7 event directories: 0..5 and the frame-less 9)
-    assert st["frames_failed"] == 3 and st["frames_gpu_decoded"] + st["frames_host_decoded"] == 6 * 2 * F - 3, st
-    assert st["frames_host_decoded"] >= 2 * 2 * F - 3, st
+    st, text = go("zip", zs, "hybrid", True, batch_mb=64)
+    assert text == ref
+    assert st["events_per_batch"] == 3 and st["batches"] == 3, st  # (8 event directories: 0..6 and the frame-less 9)
+    assert st["frames_failed"] == 3 and st["frames_gpu_decoded"] + st["frames_host_decoded"] == 7 * 2 * F - 3, st
+    assert st["frames_host_decoded"] >= 3 * 2 * F - 3, st
+    # one event per batch: the batch of event 6 has no frame for the GPU, only frames its reading threads decoded
+    monkeypatch.setenv("ABUB_GPU_DECODE_EVENTS", "1")
+    monkeypatch.delenv("ABUB_HOST_DECODE_EVENTS")
+    st, text = go("raw", rd + "/", "gpu_share_on_host", True, batch_mb=64)
+    assert text == ref
+    assert st["events_per_batch"] == 1 and st["batches"] == 8, st
+    assert st["frames_failed"] == 3 and st["frames_host_decoded"] == 1 + 2 * F, st
+    assert st["frames_gpu_decoded"] == 6 * 2 * F - 4, st
 
 
 def test_png_walk_for_the_gpu_decoder():
