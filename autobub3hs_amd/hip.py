@@ -244,3 +244,33 @@ def png_decode(files, W, H, device="cuda:0"):
     st = status.cpu().numpy()[:n].copy()
     st[status_pre != 0] = -1
     return out[:n], st
+
+
+def match_terms(frames, frame_idx, tmpl):
+    """Exact CCORR terms (abub_match_ccorr_batch_dev): frames u8 [N,H,W] (any slab of frames), frame_idx int32 [njobs]
+    (frame of each job), tmpl u8 [th,tw] -> (num, wsum2), each int64 [njobs, H-th+1, W-tw+1] holding the u64 sums."""
+    _need_cuda(frames, frame_idx, tmpl)
+    H, W = frames.shape[-2:]
+    th, tw = tmpl.shape
+    n = frame_idx.numel()
+    num = torch.empty((n, H - th + 1, W - tw + 1), dtype=torch.int64, device=frames.device)
+    w2 = torch.empty_like(num)
+    _lib.check(_lib.lib().abub_match_ccorr_batch_dev(_ptr(frames), W, H, _ptr(frame_idx), n, _ptr(tmpl), tw, th,
+                                                     _ptr(num), _ptr(w2), _stream()), "abub_match_ccorr_batch_dev")
+    return num, w2
+
+
+def match_best(frames, frame_idx, tmpl, scratch=None):
+    """Best template position per job, computed on the device (abub_match_best_batch_dev) -> float32 [njobs, 2] (x, y)."""
+    _need_cuda(frames, frame_idx, tmpl)
+    H, W = frames.shape[-2:]
+    th, tw = tmpl.shape
+    n = frame_idx.numel()
+    need = _lib.lib().abub_match_best_scratch_bytes(W, H, tw, th, n)
+    if scratch is None:
+        scratch = torch.empty(max(need, 1), dtype=torch.uint8, device=frames.device)
+    out = torch.empty((n, 2), dtype=torch.float32, device=frames.device)
+    _lib.check(_lib.lib().abub_match_best_batch_dev(_ptr(frames), W, H, _ptr(frame_idx), n, _ptr(tmpl), tw, th,
+                                                    _ptr(out), _ptr(scratch), scratch.numel(), _stream()),
+               "abub_match_best_batch_dev")
+    return out

@@ -389,6 +389,17 @@ class Pipeline:
                          "s3_bucket_ms", "pairs", "trigger_jobs", "dropin_stacks", "jobs_completed_on_demand"), list(out)),
                     rounds=rounds)
 
+    def bellows_stats(self):
+        """Bellows veto of the last run: stacks vetoed inside the batch, template-match jobs and launches, residual
+        images, wall time of the veto rounds (ms)."""
+        L = lib()
+        L.abh_pipe_bellows.argtypes = [C.c_void_p, _dp]
+        out = (C.c_double * 5)()
+        L.abh_pipe_bellows(self._h, out)
+        v = list(out)
+        return {"vetoed": int(v[0]), "match_jobs": int(v[1]), "match_launches": int(v[2]), "residual_images": int(v[3]),
+                "veto_ms": v[4]}
+
     def result(self, s):
         L = lib()
         o = (C.c_int * 6)()

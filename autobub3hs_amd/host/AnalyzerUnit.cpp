@@ -80,20 +80,7 @@ void AnalyzerUnit::ProcessFrame(cv::Mat &workingFrame, cv::Mat &prevFrame, cv::M
 {
     if (blur_diam != 5)
         throw std::runtime_error("AnalyzerUnit::ProcessFrame: only the 5x5 kernel of the reference is implemented");
-    if (workingFrame.empty() || prevFrame.empty() || workingFrame.rows != prevFrame.rows || workingFrame.cols != prevFrame.cols)
-        throw std::runtime_error("AnalyzerUnit::ProcessFrame: empty or mismatching frames");
-    abub::DeviceContext &dc = abub::DeviceContext::forThread(workingFrame.cols, workingFrame.rows, 2);
-    const uint8_t *fr[2] = {workingFrame.data, prevFrame.data};
-    abub::check(abub_ctx_upload_stack(dc.ctx, fr, 2), "abub_ctx_upload_stack");
-    dc.residentEvent = 0;
-    dc.ensureModel(*TrainedData);
-    diff_frame.create(workingFrame.rows, workingFrame.cols, CV_8U);
-    const bool full = ROI.x == 0 && ROI.y == 0 && ROI.width == workingFrame.cols && ROI.height == workingFrame.rows;
-    if (full)
-        abub::check(abub_ctx_diff_frame(dc.ctx, 0, 1, diff_frame.data, nullptr), "abub_ctx_diff_frame");
-    else
-        abub::check(abub_ctx_diff_frame_roi(dc.ctx, 0, 1, ROI.x, ROI.y, ROI.width, ROI.height, diff_frame.data, nullptr),
-                    "abub_ctx_diff_frame_roi");
+    abub::processFrameOnDevice(*TrainedData, workingFrame, prevFrame, ROI, diff_frame);
 }
 
 // 128-bin entropy and its z-score: compiled but unused upstream (AnalyzerUnit.cpp:386-433).

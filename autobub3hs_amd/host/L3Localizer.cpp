@@ -86,9 +86,7 @@ static void trackResident(abub::EventData &ev, int frame, const cv::Mat &templ, 
 {
     if (templ.cols > ev.W || templ.rows > ev.H)
         throw std::runtime_error("L3Localizer: bellows template larger than the frame");
-    std::vector<unsigned long long> num, w2;
-    ev.matchTerms(frame, templ, num, w2);
-    abub::bestMatchFromTerms(num.data(), w2.data(), ev.W - templ.cols + 1, ev.H - templ.rows + 1, templ, best.x, best.y);
+    best = ev.bestMatch(frame, templ);
 }
 
 // L3Localizer.cpp:215-460, including the bellows-movement veto (:292-390): when every genesis contour lies in the
@@ -161,18 +159,11 @@ void L3Localizer::CalculateInitialBubbleParams(void)
                 auto inside = [&](const cv::Rect &r) { return r.x >= 0 && r.y >= 0 && r.x + r.width <= W && r.y + r.height <= H; };
                 if (!inside(rt) || !inside(rp))
                     throw std::runtime_error("L3Localizer: bellows template position outside the frame");
-                cv::Mat trig_copy = cv::Mat::zeros(H, W, CV_8U), preTrig_copy = cv::Mat::zeros(H, W, CV_8U);
-                for (int r = 0; r < th; ++r) {
-                    std::memcpy(trig_copy.ptr<uchar>(rt.y + r) + rt.x, TemplateImage.ptr<uchar>(r), (size_t)tw);
-                    std::memcpy(preTrig_copy.ptr<uchar>(rp.y + r) + rp.x, TemplateImage.ptr<uchar>(r), (size_t)tw);
-                }
                 cv::Rect diffROI = GetDiffROI(pt, pp, TemplateImage);
                 if (diffROI.width < 0 || diffROI.height < 0 || !inside(diffROI))
                     throw std::runtime_error("L3Localizer: bellows ROI outside the frame");
-                cv::Mat diff_frame;
-                ProcessFrame(trig_copy, preTrig_copy, diff_frame, 5, diffROI); // uses the frame slab: D is recomputed below
-                ev.diffFrame(MatTrigFrame, pre);
-                hist = ev.subtractFromCurrent(diff_frame); // overTheSigma -= diff_frame (:362)
+                // renderings, ROI ProcessFrame, overTheSigma -= diff_frame (:326-362)
+                hist = ev.bellowsResidual(MatTrigFrame, pre, TemplateImage, rt, rp, diffROI);
                 contoursOfCurrentImage(ev, hist, loc_thres, contours);
             }
             largestBoxArea = 0;

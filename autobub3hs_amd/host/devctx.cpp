@@ -7,6 +7,7 @@
 
 #include "AlgorithmTraining/Trainer.hpp"
 #include "ParseFolder/Parser.hpp"
+#include "hostlogic.hpp"
 
 namespace abub {
 
@@ -186,6 +187,57 @@ void EventOnDevice::matchTerms(int i, const cv::Mat &templ, std::vector<unsigned
     wsum2.resize(n);
     check(abub_ctx_match_template(dc.ctx, i, templ.data, templ.cols, templ.rows, num.data(), wsum2.data()),
           "abub_ctx_match_template");
+}
+
+cv::Point2f EventData::bestMatch(int i, const cv::Mat &templ)
+{
+    std::vector<unsigned long long> num, w2;
+    matchTerms(i, templ, num, w2);
+    cv::Point2f best;
+    bestMatchFromTerms(num.data(), w2.data(), W - templ.cols + 1, H - templ.rows + 1, templ, best.x, best.y);
+    return best;
+}
+
+const uint32_t *EventData::bellowsResidual(int trig, int pre, const cv::Mat &templ, cv::Rect rt, cv::Rect rp,
+                                           cv::Rect diffROI)
+{
+    cv::Mat trig_copy = cv::Mat::zeros(H, W, CV_8U), preTrig_copy = cv::Mat::zeros(H, W, CV_8U);
+    for (int r = 0; r < templ.rows; ++r) {
+        std::memcpy(trig_copy.ptr<uchar>(rt.y + r) + rt.x, templ.ptr<uchar>(r), (size_t)templ.cols);
+        std::memcpy(preTrig_copy.ptr<uchar>(rp.y + r) + rp.x, templ.ptr<uchar>(r), (size_t)templ.cols);
+    }
+    cv::Mat diff_frame;
+    processFrameROI(trig_copy, preTrig_copy, diffROI, diff_frame); // uses the frame slab: D is recomputed below
+    diffFrame(trig, pre);
+    return subtractFromCurrent(diff_frame); // overTheSigma -= diff_frame (:362)
+}
+
+void EventData::processFrameROI(cv::Mat &, cv::Mat &, cv::Rect, cv::Mat &)
+{
+    throw std::runtime_error("EventData: ROI ProcessFrame is not available from this provider");
+}
+
+void EventOnDevice::processFrameROI(cv::Mat &cur, cv::Mat &ref, cv::Rect roi, cv::Mat &out)
+{
+    processFrameOnDevice(*model_, cur, ref, roi, out);
+}
+
+void processFrameOnDevice(const Trainer &model, cv::Mat &cur, cv::Mat &ref, cv::Rect roi, cv::Mat &out)
+{
+    if (cur.empty() || ref.empty() || cur.rows != ref.rows || cur.cols != ref.cols)
+        throw std::runtime_error("AnalyzerUnit::ProcessFrame: empty or mismatching frames");
+    DeviceContext &dc = DeviceContext::forThread(cur.cols, cur.rows, 2);
+    const uint8_t *fr[2] = {cur.data, ref.data};
+    check(abub_ctx_upload_stack(dc.ctx, fr, 2), "abub_ctx_upload_stack");
+    dc.residentEvent = 0;
+    dc.ensureModel(model);
+    out.create(cur.rows, cur.cols, CV_8U);
+    const bool full = roi.x == 0 && roi.y == 0 && roi.width == cur.cols && roi.height == cur.rows;
+    if (full)
+        check(abub_ctx_diff_frame(dc.ctx, 0, 1, out.data, nullptr), "abub_ctx_diff_frame");
+    else
+        check(abub_ctx_diff_frame_roi(dc.ctx, 0, 1, roi.x, roi.y, roi.width, roi.height, out.data, nullptr),
+              "abub_ctx_diff_frame_roi");
 }
 
 const uint32_t *EventOnDevice::subtractFromCurrent(const cv::Mat &sub)

@@ -58,7 +58,22 @@ public:
                             std::vector<unsigned long long> &wsum2) = 0;
     // current image = saturate(current image - sub); returns the new histogram
     virtual const uint32_t *subtractFromCurrent(const cv::Mat &sub) = 0;
+
+    // bellows veto, TrackAFeature (L3Localizer.cpp:473-510): best template position in frame i.
+    // Default: matchTerms, normalised on the host (bestMatchFromTerms).
+    virtual cv::Point2f bestMatch(int i, const cv::Mat &templ);
+    // bellows veto, L3Localizer.cpp:326-362: the template rendered at rt (trigger copy) and at rp (pre-trigger copy), the
+    // ROI ProcessFrame of the two renderings subtracted from D(trig; pre), which becomes the current image; returns its
+    // histogram.  Default: host renders, processFrameROI, diffFrame, subtractFromCurrent.
+    virtual const uint32_t *bellowsResidual(int trig, int pre, const cv::Mat &templ, cv::Rect rt, cv::Rect rp,
+                                            cv::Rect diffROI);
+    // AnalyzerUnit::ProcessFrame(cur, ref, out, 5, roi) with this event's model (used by the default bellowsResidual)
+    virtual void processFrameROI(cv::Mat &cur, cv::Mat &ref, cv::Rect roi, cv::Mat &out);
 };
+
+// AnalyzerUnit::ProcessFrame (AnalyzerUnit.cpp:79-97) on two host images with `model`: the pair is staged as a two-frame
+// stack in the thread's context; out = D(cur; ref) on `roi` (the whole frame: the full-frame kernel)
+void processFrameOnDevice(const Trainer &model, cv::Mat &cur, cv::Mat &ref, cv::Rect roi, cv::Mat &out);
 
 // thrown by a provider that cannot serve a request (the batched pipeline re-runs such a stack one at a time)
 struct NeedsDropInPath : public std::runtime_error {
@@ -84,6 +99,7 @@ public:
     void matchTerms(int i, const cv::Mat &templ, std::vector<unsigned long long> &num,
                     std::vector<unsigned long long> &wsum2) override;
     const uint32_t *subtractFromCurrent(const cv::Mat &sub) override;
+    void processFrameROI(cv::Mat &cur, cv::Mat &ref, cv::Rect roi, cv::Mat &out) override;
 
 private:
     DeviceContext &resident();

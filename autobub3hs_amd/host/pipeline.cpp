@@ -43,7 +43,7 @@ extern bool g_quietAnalyzers;
 namespace {
 
 struct PlannedImage {
-    int kind; // 0 = D(i; ref) (genesis), 1 = post-trigger image of frame i
+    int kind; // 0 = D(i; ref) (genesis), 1 = post-trigger image of frame i, 2 = bellows residual of D(i; ref)
     int i, ref;
     int slot; // index into the image / histogram slabs of this round
     int tozero;
@@ -57,6 +57,13 @@ struct PlannedImage {
 // pipeline evaluates that block for the stack and runs the search again (see RunPipeline::runGroup)
 struct NeedMoreFrames : public std::runtime_error {
     NeedMoreFrames() : std::runtime_error("trigger search needs the next block of frames") {}
+};
+
+// thrown by the batched provider when the bellows veto asks for a template match or a residual image that has not been
+// computed yet: the request is recorded, the pipeline serves all of them in a veto round and runs localize again (see
+// RunPipeline::vetoRound).  Both throws come before LocalizeOMatic pushes anything to bubbleRects or BubbleList.
+struct NeedBellows : public std::runtime_error {
+    NeedBellows() : std::runtime_error("bellows veto waits for the batched match / residual") {}
 };
 
 // EventData served from the pipeline's batched results
@@ -78,7 +85,31 @@ public:
     int refOffset = 2;
     const uint32_t *roundHists = nullptr; // [nslots][256] of the current round
     std::vector<PlannedImage> planned;
-    int cur = -1;
+    const PlannedImage *cur = nullptr;
+    // bellows veto memos of the current trigger (cleared when the search moves on): template matches keyed by frame and
+    // template, residual images keyed by (trig, pre, rt, rp); entries with ready == false are requests
+    bool bellowsDropIn = false; // ABUB_PIPE_BELLOWS=dropin: the veto goes through the one-at-a-time path
+    struct MatchMemo {
+        int frame;
+        cv::Mat templ;
+        bool ready;
+        cv::Point2f xy;
+    };
+    struct ResidualMemo {
+        int trig, pre;
+        cv::Rect rt, rp, roi;
+        cv::Mat templ;
+        bool ready;
+        uint32_t hist[256];
+        PlannedImage img;
+    };
+    std::vector<MatchMemo> matches;
+    std::vector<ResidualMemo> residuals; // (cur points into it only until the next request)
+    void clearVeto()
+    {
+        matches.clear();
+        residuals.clear();
+    }
     const uint8_t *ok = nullptr; // per-frame "decoded" flags of a stack that came from disk (NULL: all good)
 
     bool frameOk(int i) const override { return i >= 0 && i < F && (!ok || ok[i]); }
@@ -107,7 +138,7 @@ public:
     {
         for (size_t k = 0; k < planned.size(); ++k)
             if (planned[k].kind == kind && planned[k].i == i && (kind == 1 || planned[k].ref == ref)) {
-                cur = (int)k;
+                cur = &planned[k];
                 return roundHists + (size_t)planned[k].slot * 256;
             }
         throw std::runtime_error("BatchEventData: image was not planned for this round");
@@ -126,11 +157,63 @@ public:
     {
         throw NeedsDropInPath("bellows veto requested in the batched path");
     }
+    static bool same(const cv::Rect &a, const cv::Rect &b)
+    {
+        return a.x == b.x && a.y == b.y && a.width == b.width && a.height == b.height;
+    }
+    MatchMemo *findMatch(int i, const cv::Mat &templ)
+    {
+        for (MatchMemo &m : matches)
+            if (m.frame == i && m.templ.data == templ.data && m.templ.cols == templ.cols && m.templ.rows == templ.rows)
+                return &m;
+        return nullptr;
+    }
+    void requestMatch(int i, const cv::Mat &templ)
+    {
+        if (!findMatch(i, templ))
+            matches.push_back(MatchMemo{i, templ, false, cv::Point2f()});
+    }
+    cv::Point2f bestMatch(int i, const cv::Mat &templ) override
+    {
+        if (bellowsDropIn)
+            throw NeedsDropInPath("bellows veto requested in the batched path");
+        if (MatchMemo *m = findMatch(i, templ))
+            if (m->ready)
+                return m->xy;
+        requestMatch(i, templ);
+        // the veto always locates the template in the genesis pair's two frames: ask for both in one match round
+        for (const PlannedImage &p : planned)
+            if (p.kind == 0 && p.i == i)
+                requestMatch(p.ref, templ);
+        throw NeedBellows();
+    }
+    const uint32_t *bellowsResidual(int trig, int pre, const cv::Mat &templ, cv::Rect rt, cv::Rect rp, cv::Rect roi) override
+    {
+        if (bellowsDropIn)
+            throw NeedsDropInPath("bellows veto requested in the batched path");
+        for (ResidualMemo &r : residuals)
+            if (r.trig == trig && r.pre == pre && same(r.rt, rt) && same(r.rp, rp) && same(r.roi, roi) && r.templ.data == templ.data) {
+                if (!r.ready)
+                    throw NeedBellows();
+                cur = &r.img;
+                return r.hist;
+            }
+        ResidualMemo r{};
+        r.trig = trig;
+        r.pre = pre;
+        r.rt = rt;
+        r.rp = rp;
+        r.roi = roi;
+        r.templ = templ;
+        r.ready = false;
+        residuals.push_back(r);
+        throw NeedBellows();
+    }
     void foreground(int thr, std::vector<uint32_t> &idx) override
     {
-        if (cur < 0 || planned[cur].thr != thr)
+        if (!cur || cur->thr != thr)
             throw std::runtime_error("BatchEventData::foreground: threshold differs from the planned one");
-        const PlannedImage &p = planned[cur];
+        const PlannedImage &p = *cur;
         idx.clear();
         for (uint32_t k = 0; k < p.nfg; ++k)
             if ((int)p.fgv[k] > thr)
@@ -152,6 +235,8 @@ struct StackState {
     bool localize = false;
     bool dropIn = false; // must be re-run through the one-at-a-time path (bellows veto)
     bool needMore = false; // the trigger search stopped at a frame block that is not evaluated yet (data.needBlock)
+    bool needBellows = false; // localize stopped at a bellows-veto request (data.matches / data.residuals)
+    bool vetoed = false;      // a bellows residual was computed for this stack in the batch
     std::string error;
     std::vector<BubbleOut> bubbles;
     int trig = 0, status = 0, loc_thres = 3, ok = 1;
@@ -294,6 +379,28 @@ struct Group {
     abub_job *h_jobs3 = nullptr;
     int32_t *h_thr = nullptr;
     uint32_t pairCap = 0;
+    // bellows veto round (vetoRound): its own buffers, allocated on first use, grown on demand
+    struct Veto {
+        int capJobs = 0;           // match jobs the buffers hold
+        size_t scratchBytes = 0;   // abub_match_best_batch_dev scratch
+        uint32_t *d_fidx = nullptr, *h_fidx = nullptr;
+        float *d_xy = nullptr, *h_xy = nullptr;
+        void *d_scratch = nullptr;
+        int capImg = 0;            // residual images
+        uint8_t *d_rend = nullptr, *h_rend = nullptr; // [2n][P]: trigger copy, pre-trigger copy
+        uint8_t *d_syn = nullptr, *d_img = nullptr;   // [n][P]: ROI ProcessFrame of the renderings, the residual
+        uint32_t *d_rhist = nullptr;                  // [n][256] (ROI ProcessFrame histograms, unused)
+        uint32_t *d_hist = nullptr, *h_hist = nullptr;
+        abub_job *d_jobs = nullptr, *h_jobs = nullptr;
+        int32_t *d_thr = nullptr, *h_thr = nullptr;
+        uint32_t pairCap = 0;
+        uint32_t *d_pairs = nullptr, *d_count = nullptr, *h_count = nullptr, *d_gscratch = nullptr, *d_goff = nullptr,
+                 *h_goff = nullptr, *d_gidx = nullptr, *h_gidx = nullptr;
+        uint8_t *d_gval = nullptr, *h_gval = nullptr;
+        std::vector<std::pair<cv::Mat, uint8_t *>> templates; // device copies of the bellows templates (deviceTemplate)
+    } veto;
+    int vetoed = 0, matchJobs = 0, matchLaunches = 0, residualImages = 0;
+    double vetoMs = 0;
     int nthreads = 1;
     double tms[8] = {0};
     int rounds = 0;
@@ -314,6 +421,8 @@ public:
     long long jobsCompleted = 0;        // ... jobs of the last run that were completed that way
     long long jobsLaunched = 0;         // trigger-search jobs of the last run (F - 1 per stack when nothing is lazy)
     int dropIns = 0;                    // stacks of the last run that went through the one-at-a-time path (bellows veto)
+    bool bellowsDropIn = false;         // ABUB_PIPE_BELLOWS=dropin: every bellows veto takes the one-at-a-time path (A/B)
+    double bellowsStats[5] = {0};       // last run: vetoed stacks, match jobs, match launches, residual images, veto ms
     hipStream_t stage1Stream = nullptr; // all trigger-search launches, in group order (see run())
     int chainStride = 0;                // FindTriggerFrame's frame offset when every camera shares it, else 0
     bool ordered = true;                // localisation kernels queue on stage1Stream too (see batchImages())
@@ -469,6 +578,8 @@ public:
             HIPOK(hipSetDevice(device));
             const char *eg = getenv("ABUB_PIPE_GROUPS");
             ngroups = eg ? atoi(eg) : 1; // >1 overlaps host stages of one group with the GPU work of the next
+            const char *ebw = getenv("ABUB_PIPE_BELLOWS");
+            bellowsDropIn = ebw && std::string(ebw) == "dropin";
             const char *eo = getenv("ABUB_PIPE_ORDERED");
             ordered = eo ? atoi(eo) != 0 : true;
             int prLow = 0, prHigh = 0; // (numerically lower = higher priority)
@@ -684,6 +795,7 @@ public:
         for (auto &t : th)
             t.join();
         std::fill(tms, tms + 8, 0.0);
+        std::fill(bellowsStats, bellowsStats + 5, 0.0);
         rounds = 0;
         lastPairs = 0;
         // stacks the batched providers could not serve (bellows veto): one at a time through the drop-in path
@@ -698,6 +810,11 @@ public:
                 throw std::runtime_error(G.error);
             for (int k = 0; k < 8; ++k)
                 tms[k] = std::max(tms[k], G.tms[k]);
+            bellowsStats[0] += G.vetoed;
+            bellowsStats[1] += G.matchJobs;
+            bellowsStats[2] += G.matchLaunches;
+            bellowsStats[3] += G.residualImages;
+            bellowsStats[4] += G.vetoMs;
             rounds = std::max(rounds, G.rounds);
             lastPairs += G.lastPairs;
         }
@@ -791,6 +908,8 @@ private:
     {
         std::fill(G.tms, G.tms + 8, 0.0);
         G.rounds = 0;
+        G.vetoed = G.matchJobs = G.matchLaunches = G.residualImages = 0;
+        G.vetoMs = 0;
         const int ns = G.s1 - G.s0;
         double t0 = nowMs();
         // ---- stage 1 (already queued by run()) -----------------------------------------------------
@@ -812,6 +931,9 @@ private:
             st_.data.W = W;
             st_.data.H = H;
             st_.data.refOffset = tss[c] < 6 ? 1 : 2;
+            st_.data.bellowsDropIn = bellowsDropIn;
+            st_.data.clearVeto();
+            st_.vetoed = false;
             st_.data.nblocks = (int)blocks.size() - 1;
             for (size_t b = 0; b < blocks.size(); ++b)
                 st_.data.bstart[b] = blocks[b];
@@ -861,6 +983,7 @@ private:
             // ---- stage 4: localize + track -------------------------------------------------------
             double t4 = nowMs();
             pool->parallelFor((int)loc.size(), [&](int k) { localize(stacks[loc[k]]); });
+            vetoRound(G, loc, d_frames, d_sigma6);
             G.tms[3] += nowMs() - t4;
             std::vector<int> next;
             for (int s : pending)
@@ -1005,7 +1128,8 @@ private:
             const int t = A->MatTrigFrame;
             const int off = A->TrainedData->TrainingSetSize < 6 ? 1 : 2;
             st_.data.planned.clear();
-            st_.data.cur = -1;
+            st_.data.cur = nullptr;
+            st_.data.clearVeto(); // a new trigger: new veto keys
             PlannedImage g;
             g.kind = 0;
             g.i = t;
@@ -1139,6 +1263,276 @@ private:
         G.tms[6] += nowMs() - ta; // list D2H (+ thresholds)
     }
 
+    // ---- bellows veto round ----------------------------------------------------------------------------------------
+    // The stacks of `loc` whose localize stopped at a veto request (NeedBellows) are served together on the group's own
+    // stream, one host synchronisation per sub-round: first the template matches (trigger and pre-trigger frames, one
+    // launch per template), then the residual images; after each, localize runs again on those stacks.  The round's
+    // planned images (h_hist3, h_gidx, h_gval) stay untouched: the veto has buffers of its own.
+    void vetoRound(Group &G, const std::vector<int> &loc, const uint8_t *d_frames, const uint8_t *d_sigma6)
+    {
+        const double t0 = nowMs();
+        bool any = false;
+        for (int sub = 0;; ++sub) {
+            std::vector<int> ask;
+            for (int s : loc)
+                if (stacks[s].needBellows)
+                    ask.push_back(s);
+            if (ask.empty())
+                break;
+            any = true;
+            bool served = false;
+            if (sub < 3) {
+                try {
+                    served = vetoMatches(G, ask, d_frames) || vetoResiduals(G, ask, d_frames, d_sigma6);
+                } catch (VetoFallback &) {
+                    // no room for the veto buffers, or a shape the batched matcher refuses: the one-at-a-time path takes
+                    // these stacks, as it took every veto before
+                    for (int s : ask) {
+                        stacks[s].needBellows = false;
+                        stacks[s].dropIn = true;
+                        stacks[s].done = true;
+                    }
+                    break;
+                }
+            }
+            if (!served) {
+                for (int s : ask) {
+                    stacks[s].needBellows = false;
+                    stacks[s].error = "bellows veto: request left unserved by the veto round";
+                    stacks[s].staged = -6;
+                    stacks[s].done = true;
+                }
+                break;
+            }
+            pool->parallelFor((int)ask.size(), [&](int k) { localize(stacks[ask[k]]); });
+        }
+        if (any)
+            G.vetoMs += nowMs() - t0;
+    }
+
+    struct VetoFallback {};
+
+    template <typename T>
+    T *vetoAlloc(size_t n, bool device)
+    {
+        try {
+            return device ? dalloc<T>(n) : halloc<T>(n);
+        } catch (std::exception &) {
+            throw VetoFallback();
+        }
+    }
+
+    // the group's device copy of a bellows template, uploaded once on the group's stream (the only stream that uses it;
+    // the host Mat is the process-wide mask cache's, immutable and kept alive by the entry)
+    const uint8_t *deviceTemplate(Group &G, const cv::Mat &t)
+    {
+        for (auto &e : G.veto.templates)
+            if (e.first.data == t.data && e.first.cols == t.cols && e.first.rows == t.rows)
+                return e.second;
+        uint8_t *d = vetoAlloc<uint8_t>(t.total(), true);
+        HIPOK(hipMemcpyAsync(d, t.data, t.total(), hipMemcpyHostToDevice, G.stream));
+        G.veto.templates.emplace_back(t, d);
+        return d;
+    }
+
+    // every outstanding match request of the asking stacks; false if there is none
+    bool vetoMatches(Group &G, const std::vector<int> &ask, const uint8_t *d_frames)
+    {
+        std::vector<cv::Mat> tpl;
+        std::vector<std::vector<std::pair<int, BatchEventData::MatchMemo *>>> byT;
+        for (int s : ask)
+            for (BatchEventData::MatchMemo &m : stacks[s].data.matches) {
+                if (m.ready)
+                    continue;
+                size_t t = 0;
+                while (t < tpl.size() && !(tpl[t].data == m.templ.data && tpl[t].cols == m.templ.cols && tpl[t].rows == m.templ.rows))
+                    ++t;
+                if (t == tpl.size()) {
+                    tpl.push_back(m.templ);
+                    byT.emplace_back();
+                }
+                byT[t].emplace_back(s, &m);
+            }
+        if (tpl.empty())
+            return false;
+        Group::Veto &V = G.veto;
+        int total = 0;
+        size_t scratch = 0;
+        for (size_t t = 0; t < tpl.size(); ++t) {
+            total += (int)byT[t].size();
+            const size_t need = abub_match_best_scratch_bytes(W, H, tpl[t].cols, tpl[t].rows, (int)byT[t].size());
+            if (need == 0)
+                throw VetoFallback();
+            scratch = std::max(scratch, need);
+        }
+        if (V.capJobs < total) {
+            const int cap = std::max(total, 2 * V.capJobs);
+            V.d_fidx = vetoAlloc<uint32_t>(cap, true);
+            V.h_fidx = vetoAlloc<uint32_t>(cap, false);
+            V.d_xy = vetoAlloc<float>(2 * (size_t)cap, true);
+            V.h_xy = vetoAlloc<float>(2 * (size_t)cap, false);
+            V.capJobs = cap;
+        }
+        if (V.scratchBytes < scratch) {
+            V.d_scratch = vetoAlloc<uint8_t>(scratch, true);
+            V.scratchBytes = scratch;
+        }
+        hipStream_t st = G.stream;
+        int off = 0;
+        for (size_t t = 0; t < tpl.size(); ++t) {
+            const int n = (int)byT[t].size();
+            const uint8_t *dt = deviceTemplate(G, tpl[t]);
+            for (int q = 0; q < n; ++q)
+                V.h_fidx[off + q] = (uint32_t)(byT[t][q].first * F + byT[t][q].second->frame);
+            HIPOK(hipMemcpyAsync(V.d_fidx + off, V.h_fidx + off, (size_t)n * 4, hipMemcpyHostToDevice, st));
+            const int rc = abub_match_best_batch_dev(d_frames, W, H, V.d_fidx + off, n, dt, tpl[t].cols, tpl[t].rows,
+                                                     V.d_xy + 2 * off, V.d_scratch, V.scratchBytes, st);
+            if (rc == ABUB_E_INVALID) // refused before anything was queued (e.g. a frame wider than the matcher takes)
+                throw VetoFallback();
+            check(rc, "bellows veto match");
+            off += n;
+            ++G.matchLaunches;
+        }
+        HIPOK(hipMemcpyAsync(V.h_xy, V.d_xy, (size_t)total * 8, hipMemcpyDeviceToHost, st));
+        HIPOK(hipStreamSynchronize(st));
+        off = 0;
+        for (size_t t = 0; t < tpl.size(); ++t)
+            for (auto &r : byT[t]) {
+                r.second->xy = cv::Point2f(V.h_xy[2 * off], V.h_xy[2 * off + 1]);
+                r.second->ready = true;
+                ++off;
+            }
+        G.matchJobs += total;
+        return true;
+    }
+
+    // every outstanding residual request of the asking stacks; false if there is none
+    bool vetoResiduals(Group &G, const std::vector<int> &ask, const uint8_t *d_frames, const uint8_t *d_sigma6)
+    {
+        std::vector<std::pair<int, BatchEventData::ResidualMemo *>> req;
+        for (int s : ask)
+            for (BatchEventData::ResidualMemo &r : stacks[s].data.residuals)
+                if (!r.ready)
+                    req.emplace_back(s, &r);
+        if (req.empty())
+            return false;
+        Group::Veto &V = G.veto;
+        const int n = (int)req.size();
+        if (V.capImg < n) {
+            const int cap = std::max(n, 2 * V.capImg);
+            V.d_rend = vetoAlloc<uint8_t>(2 * (size_t)cap * P, true);
+            V.h_rend = vetoAlloc<uint8_t>(2 * (size_t)cap * P, false);
+            V.d_syn = vetoAlloc<uint8_t>((size_t)cap * P, true);
+            V.d_img = vetoAlloc<uint8_t>((size_t)cap * P, true);
+            V.d_rhist = vetoAlloc<uint32_t>((size_t)cap * 256, true);
+            V.d_hist = vetoAlloc<uint32_t>((size_t)cap * 256, true);
+            V.h_hist = vetoAlloc<uint32_t>((size_t)cap * 256, false);
+            V.d_jobs = vetoAlloc<abub_job>(cap, true);
+            V.h_jobs = vetoAlloc<abub_job>(cap, false);
+            V.d_thr = vetoAlloc<int32_t>(cap, true);
+            V.h_thr = vetoAlloc<int32_t>(cap, false);
+            V.d_gscratch = vetoAlloc<uint32_t>(2 * (size_t)cap, true);
+            V.d_goff = vetoAlloc<uint32_t>((size_t)cap + 1, true);
+            V.h_goff = vetoAlloc<uint32_t>((size_t)cap + 1, false);
+            V.capImg = cap;
+        }
+        if (!V.d_count) {
+            V.d_count = vetoAlloc<uint32_t>(1, true);
+            V.h_count = vetoAlloc<uint32_t>(1, false);
+        }
+        if (V.pairCap == 0)
+            growVetoLists(V, 1u << 20);
+        hipStream_t st = G.stream;
+        // the two renderings of the template (L3Localizer.cpp:326-334), then everything on the device with no sync between
+        pool->parallelFor(n, [&](int k) {
+            const BatchEventData::ResidualMemo &r = *req[k].second;
+            uint8_t *t = V.h_rend + 2 * (size_t)k * P, *p = t + P;
+            std::memset(t, 0, 2 * P);
+            for (int y = 0; y < r.templ.rows; ++y) {
+                std::memcpy(t + (size_t)(r.rt.y + y) * W + r.rt.x, r.templ.ptr<uchar>(y), (size_t)r.templ.cols);
+                std::memcpy(p + (size_t)(r.rp.y + y) * W + r.rp.x, r.templ.ptr<uchar>(y), (size_t)r.templ.cols);
+            }
+        });
+        HIPOK(hipMemcpyAsync(V.d_rend, V.h_rend, 2 * (size_t)n * P, hipMemcpyHostToDevice, st));
+        for (int k = 0; k < n; ++k) {
+            const int s = req[k].first, c = s % C;
+            const BatchEventData::ResidualMemo &r = *req[k].second;
+            // ROI ProcessFrame(trig copy, pre copy) (:355); the pre copy lies after the trigger copy, as the kernel wants
+            check(abub_diff_roi_dev(V.d_rend + 2 * (size_t)k * P, V.d_rend + (2 * (size_t)k + 1) * P, d_sigma6 + (size_t)c * P, W, H,
+                                    r.roi.x, r.roi.y, r.roi.width, r.roi.height, V.d_syn + (size_t)k * P, V.d_rhist + (size_t)k * 256,
+                                    st),
+                  "bellows veto ROI ProcessFrame");
+            abub_job &j = V.h_jobs[k];
+            j.cur = (uint32_t)(s * F + r.trig);
+            j.ref = (uint32_t)(s * F + r.pre);
+            j.model = (uint32_t)c;
+            j.out = (uint32_t)k;
+            V.h_thr[k] = stacks[s].analyzer->loc_thres; // TOZERO cut of contoursOfCurrentImage
+        }
+        HIPOK(hipMemcpyAsync(V.d_jobs, V.h_jobs, (size_t)n * sizeof(abub_job), hipMemcpyHostToDevice, st));
+        HIPOK(hipMemcpyAsync(V.d_thr, V.h_thr, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        // D(trig; pre) stored, minus the synthetic diff (overTheSigma -= diff_frame, :362)
+        check(abub_diff_hist_dev(d_frames, d_sigma6, V.d_jobs, n, W, H, V.d_hist, V.d_img, 0, st), "bellows veto K2 store");
+        for (int k = 0; k < n; ++k)
+            check(abub_subsat_hist_dev(V.d_img + (size_t)k * P, V.d_syn + (size_t)k * P, W, H, V.d_hist + (size_t)k * 256, st),
+                  "bellows veto subtract");
+        uint32_t cnt = 0;
+        for (int attempt = 0;; ++attempt) {
+            HIPOK(hipMemsetAsync(V.d_count, 0, sizeof(uint32_t), st));
+            check(abub_fg_compact_pairs_dev(V.d_img, n, W, H, V.d_thr, V.d_pairs, V.pairCap, V.d_count, st), "bellows veto K4");
+            check(abub_pairs_group_hist_dev(V.d_pairs, V.d_count, V.pairCap, n, V.d_gscratch, V.d_goff, V.d_gidx, V.d_gval,
+                                            V.d_hist, V.d_thr, st),
+                  "bellows veto group");
+            HIPOK(hipMemcpyAsync(V.h_hist, V.d_hist, (size_t)n * 1024, hipMemcpyDeviceToHost, st));
+            HIPOK(hipMemcpyAsync(V.h_count, V.d_count, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            HIPOK(hipMemcpyAsync(V.h_goff, V.d_goff, (size_t)(n + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            HIPOK(hipStreamSynchronize(st));
+            cnt = *V.h_count;
+            if (cnt <= V.pairCap)
+                break;
+            if (attempt > 0 || cnt > (1u << 30))
+                throw std::runtime_error("RunPipeline: bellows veto foreground list overflow");
+            growVetoLists(V, cnt + cnt / 4 + 1024);
+        }
+        if (cnt) {
+            HIPOK(hipMemcpyAsync(V.h_gidx, V.d_gidx, (size_t)cnt * 4, hipMemcpyDeviceToHost, st));
+            HIPOK(hipMemcpyAsync(V.h_gval, V.d_gval, (size_t)cnt, hipMemcpyDeviceToHost, st));
+            HIPOK(hipStreamSynchronize(st));
+        }
+        for (int k = 0; k < n; ++k) {
+            const int s = req[k].first;
+            BatchEventData::ResidualMemo &r = *req[k].second;
+            std::memcpy(r.hist, V.h_hist + (size_t)k * 256, sizeof(r.hist));
+            PlannedImage &p = r.img;
+            p.kind = 2;
+            p.i = r.trig;
+            p.ref = r.pre;
+            p.slot = k;
+            p.tozero = V.h_thr[k];
+            p.thr = binarizeThresholdFromHist(r.hist, P, p.tozero);
+            p.fg = V.h_gidx + V.h_goff[k];
+            p.fgv = V.h_gval + V.h_goff[k];
+            p.nfg = V.h_goff[k + 1] - V.h_goff[k];
+            r.ready = true;
+            if (!stacks[s].vetoed) {
+                stacks[s].vetoed = true;
+                ++G.vetoed;
+            }
+        }
+        G.residualImages += n;
+        return true;
+    }
+
+    void growVetoLists(Group::Veto &V, uint32_t cap)
+    {
+        V.d_pairs = vetoAlloc<uint32_t>((size_t)cap * 2, true);
+        V.d_gidx = vetoAlloc<uint32_t>(cap, true);
+        V.d_gval = vetoAlloc<uint8_t>(cap, true);
+        V.h_gidx = vetoAlloc<uint32_t>(cap, false);
+        V.h_gval = vetoAlloc<uint8_t>(cap, false);
+        V.pairCap = cap;
+    }
+
     // the old buffers stay on the allocation lists and are released with the pipeline
     void growLists(Group &G, uint32_t cap)
     {
@@ -1153,6 +1547,7 @@ private:
     // AnyCamAnalysis body from LocalizeOMatic on (AutoBubStart3.cpp:94-110)
     void localize(StackState &st_)
     {
+        st_.needBellows = false;
         AnalyzerUnit *A = st_.analyzer.get();
         try {
             A->LocalizeOMatic("");
@@ -1163,6 +1558,8 @@ private:
             }
             st_.staged = A->BubbleList.empty() ? -1 : 0;
             st_.done = !A->BubbleList.empty(); // no accepted bubble: search on from the next frame
+        } catch (NeedBellows &) {
+            st_.needBellows = true; // not done: served by the veto round, then localized again
         } catch (NeedsDropInPath &) {
             st_.dropIn = true;
             st_.done = true;
@@ -1187,6 +1584,7 @@ void run(RunPipeline &p, const uint8_t *d_frames, const uint8_t *d_mu, const uin
     p.run(d_frames, d_mu, d_sigma6, stream);
 }
 void writeEvent(RunPipeline &p, int k, int eventNumber, OutputWriter &out) { p.writeEvent(k, eventNumber, out); }
+int bellowsVetoed(const RunPipeline &p) { return (int)p.bellowsStats[0]; }
 
 } // namespace abub
 
@@ -1266,6 +1664,17 @@ const char *abh_pipe_stack_error(void *p, int s) { return ((abub::RunPipeline *)
 // out[0..11]: stage1 .. stage4, total, stage-3 details (ms), candidate pairs, trigger-search jobs, drop-in stacks,
 // jobs completed on demand of the last run;
 // returns the number of rounds
+int abh_pipe_timing(void *p, double *out);
+
+// out[0..4] of the last run: stacks whose bellows veto ran in the batch, template-match jobs, match launches, residual
+// images, wall time of the veto rounds (ms, summed over the stack groups)
+void abh_pipe_bellows(void *p, double *out)
+{
+    abub::RunPipeline *r = (abub::RunPipeline *)p;
+    for (int k = 0; k < 5; ++k)
+        out[k] = r->bellowsStats[k];
+}
+
 int abh_pipe_timing(void *p, double *out)
 {
     abub::RunPipeline *r = (abub::RunPipeline *)p;

@@ -51,6 +51,8 @@ void setSigmaRaw(RunPipeline &p, const uint8_t *d_sigma);
 void setStackMeta(RunPipeline &p, std::vector<StackMeta> &&meta);
 // the analysis of every stack of d_frames [E][C][F][H][W]; work queued on `stream` (the upload) is waited for first
 void run(RunPipeline &p, const uint8_t *d_frames, const uint8_t *d_mu, const uint8_t *d_sigma6, hipStream_t stream);
+// stacks of the last run whose bellows veto ran inside the batch
+int bellowsVetoed(const RunPipeline &p);
 // event k's cameras of the last run staged into `out` and written as one block
 void writeEvent(RunPipeline &p, int k, int eventNumber, OutputWriter &out);
 

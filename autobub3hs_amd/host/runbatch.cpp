@@ -599,6 +599,7 @@ int RunBatched(Parser *parser, const std::vector<std::string> &EventList, const 
                     st.write_s += wms * 1e-3;
                     st.frames += onGpu + onHost;
                     st.framesFailed += R.bad;
+                    st.bellowsVetoed += bellowsVetoed(*pipe);
                     st.framesGpuDecoded += onGpu;
                     st.framesHostDecoded += onHost;
                     st.gpudecode_s += pngms * 1e-3;

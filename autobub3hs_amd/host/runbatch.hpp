@@ -31,6 +31,7 @@ struct BatchedRunOptions {
 struct BatchedRunStats {
     double list_s = 0, decode_s = 0, gpu_s = 0, write_s = 0, total_s = 0; // decode/gpu: summed over batches (they overlap)
     long long frames = 0, framesFailed = 0;
+    long long bellowsVetoed = 0; // stacks whose bellows-movement veto ran inside the batch (pipeline veto round)
     long long framesGpuDecoded = 0, framesHostDecoded = 0; // of `frames`: by abub_png_decode_dev / by a host thread
     double gpudecode_s = 0;                                // upload of the files + the decode kernels, summed over batches
     int events = 0, batches = 0, eventsPerBatch = 0, W = 0, H = 0, Fmax = 0, gpus = 0;
