@@ -45,6 +45,8 @@ SIGNATURES = {
     "abub_diff_hist_chained_dev": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _vp]),
     "abub_diff_hist_chained_store_dev": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _i, _i, _vp]),
     "abub_k2_set_option": (_i, [C.c_char_p, _i]),
+    "abub_k2_deferred_ok": (_i, [_i, _i]),
+    "abub_k3_set_option": (_i, [C.c_char_p, _i]),
     "abub_k2_pieces_cap": (_sz, [_i, _i, _i]),
     "abub_png_raw_stride": (_sz, [_i, _i]),
     "abub_png_decode_dev": (_i, [_vp, _sz, _vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp]),
@@ -87,6 +89,10 @@ def lib():
             raise RuntimeError(
                 f"{SO} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(there is no CPU fallback for the hot path)")
+        try:  # torch ships its own HIP runtime: load it first, so that the library binds to it instead of a second copy
+            import torch  # noqa: F401
+        except ImportError:
+            pass
         L = C.CDLL(SO)
         for name, (res, args) in SIGNATURES.items():
             fn = getattr(L, name)  # AttributeError if the ABI and the header drift apart

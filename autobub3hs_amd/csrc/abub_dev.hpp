@@ -163,6 +163,13 @@ __device__ __forceinline__ uint32_t compact_reserve(const Compact &cp, uint32_t 
     }
     return base + inc - c;
 }
+// The fused K2 / K3 lists never hold value-0 pixels (the bound scans skip rows they prove zero), so a negative cthr
+// lists like 0; abub_pairs_group_hist_dev counts with the same rule.
+__device__ __forceinline__ int compact_thr(const int32_t *cthr, uint32_t out)
+{
+    const int t = cthr[out];
+    return t < 0 ? 0 : t;
+}
 __device__ __forceinline__ void compact_put(const Compact &cp, uint32_t &pos, uint32_t v, uint32_t idx)
 {
     if ((int)v > cp.thr) {
@@ -175,6 +182,7 @@ __device__ __forceinline__ void compact_put(const Compact &cp, uint32_t &pos, ui
 }
 
 #define K2B_PEND 512 /* suspects per (job, chunk) kept in LDS; also >= the groups of one row (W/4 <= 512) */
+#define K_MAX_CHUNKS 4096 /* largest "chunks" option (chunks per frame) of the K2 / K3 launchers */
 #ifndef K2B_SUB
 #define K2B_SUB 32 /* rows per handed-over piece */
 #endif
@@ -426,7 +434,7 @@ __global__ __launch_bounds__(256) void sus_tail_list(const uint8_t *__restrict__
                     packed = k3_exact_group(frames + (size_t)jb.cur * P, mu + (size_t)jb.model * P,
                                             sigma6 + (size_t)jb.model * P, y, x0, W, H);
                 if (COMPACT)
-                    thr[u] = cthr[jb.out];
+                    thr[u] = compact_thr(cthr, jb.out);
 #pragma unroll
                 for (int q = 0; q < 4; q++) {
                     const uint32_t v = (packed >> (8 * q)) & 0xffu;

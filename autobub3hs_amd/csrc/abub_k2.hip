@@ -260,7 +260,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(K2_WAVES_PER
     cp.count = pcount;
     cp.cap = pcap;
     cp.slot = jb.out + slot_base;
-    cp.thr = COMPACT ? cthr[jb.out] : 255;
+    cp.thr = COMPACT ? compact_thr(cthr, jb.out) : 255;
 
     // Software prefetch PF rows ahead through a ring of PF+1 row buffers.  The loop is unrolled by
     // U = lcm(PF+1, 2) so that ring slots are compile-time registers and neither the ring nor the
@@ -686,7 +686,7 @@ __global__ __launch_bounds__(64) void k2_bound_scan(const uint8_t *__restrict__ 
     cp.count = pcount;
     cp.cap = pcap;
     cp.slot = jb.out + slot_base;
-    cp.thr = COMPACT ? cthr[jb.out] : 255;
+    cp.thr = COMPACT ? compact_thr(cthr, jb.out) : 255;
     k2b_tail<COMPACT>(pend, J.npend, jb, frames, sigma6, W, H, hist, diff, cp, lane);
 }
 
@@ -1029,8 +1029,8 @@ static void launch_k2_rows_pf(const uint8_t *frames, const uint8_t *sigma6, cons
 }
 
 // Tuning knobs of the K2 launchers.  Defaults come from the environment once (ABUB_K2_BOUND, ABUB_K2_CHAIN,
-// ABUB_K2_BUDGET, ABUB_K2_PF); abub_k2_set_option() overrides them at run time (tests and benches switch between
-// the bound-and-verify pass and the plain row machine inside one process).
+// ABUB_K2_BUDGET, ABUB_K2_PF, ..., ABUB_K2_CHUNKS); abub_k2_set_option() overrides them at run time (tests and benches
+// switch between the bound-and-verify pass and the plain row machine inside one process).
 struct K2Options {
     int bound = 1;     // 0: always the full row machine (k2_rows); 1: bound-and-verify (trigger-only AND store mode)
     int chain = -1;    // jobs per wave in the chained scan: 2 or 4 (>= 3 means 4); 0 = never chain; -1 = automatic (4)
@@ -1046,6 +1046,7 @@ struct K2Options {
                        // -1 = automatic (K2C_DEFAULT_WG)
     int sync = -1;     // chained scan: row steps a wave may run ahead of its workgroup's slowest wave (0 = never waits;
                        // -1 = automatic, K2C_DEFAULT_SYNC)
+    int chunks = 0;    // chunks per frame when the caller leaves rows_per_chunk to the launcher (0 = automatic)
     bool loaded = false;
 };
 static K2Options g_k2opt;
@@ -1073,6 +1074,9 @@ static K2Options k2_options()
             g_k2opt.sync = atoi(e);
         if (const char *e = getenv("ABUB_K2_SCANPF"))
             g_k2opt.scanpf = atoi(e);
+        if (const char *e = getenv("ABUB_K2_CHUNKS"))
+            if (atoi(e) >= 0 && atoi(e) <= K_MAX_CHUNKS)
+                g_k2opt.chunks = atoi(e);
         g_k2opt.loaded = true;
     }
     return g_k2opt;
@@ -1102,6 +1106,8 @@ extern "C" int abub_k2_set_option(const char *name, int value)
         g_k2opt.sync = value;
     else if (!strcmp(name, "scanpf"))
         g_k2opt.scanpf = value;
+    else if (!strcmp(name, "chunks") && value >= 0 && value <= K_MAX_CHUNKS)
+        g_k2opt.chunks = value;
     else
         return set_err(ABUB_E_INVALID, "abub_k2_set_option: unknown option or bad value");
     return ABUB_OK;
@@ -1250,6 +1256,8 @@ static int launch_k2_rows(const uint8_t *frames, const uint8_t *sigma6, const ab
 #undef K2R_LAUNCH
         return ABUB_OK;
     }
+    if (ca.df_pieces) // the plain row machine has no handed-over rows to defer; d_incomplete would stay unwritten
+        return set_err(ABUB_E_INVALID, "deferred pieces need the bound-and-verify pass (option \"bound\" on)");
     // prefetch depth 1 won on MI355X: depth 2/3 rings cost a wave of occupancy and ran 10-17 % slower
     // (measured in round 1, see DESIGN.md "Tuning log")
     if (opt.pf == 2)
@@ -1267,13 +1275,9 @@ static int k2_auto_rows(int njobs, int H)
     int nch = 8;
     if ((long long)njobs * nch < 8192)
         nch = (8192 + njobs - 1) / njobs;
-    static int k2chunks = -1;
-    if (k2chunks < 0) {
-        const char *e = getenv("ABUB_K2_CHUNKS"); // tuning knob: chunks per frame (0 = automatic)
-        k2chunks = e ? atoi(e) : 0;
-    }
-    if (k2chunks > 0)
-        nch = k2chunks;
+    const int chunks = k2_options().chunks; // tuning knob: chunks per frame (0 = automatic)
+    if (chunks > 0)
+        nch = chunks;
     nch = (nch + 7) / 8 * 8; // keep chunk id == XCD id
     int R = (H + nch - 1) / nch;
     if (R < 16)
@@ -1370,6 +1374,13 @@ extern "C" size_t abub_k2_pieces_cap(int njobs, int W, int H)
         return 0;
     const int R = k2_auto_rows(njobs, H), nchunks = (H + R - 1) / R;
     return (size_t)njobs * nchunks * (size_t)((R + K2B_SUB - 1) / K2B_SUB);
+}
+
+// whether abub_diff_hist_chained_deferred_dev accepts W x H frames under the current options (the bound-and-verify pass)
+extern "C" int abub_k2_deferred_ok(int W, int H)
+{
+    return W > 0 && H > 0 && H < 65536 && (size_t)H * (size_t)(W / 4) < ((size_t)1 << 32) && pick_ndw(W) != 0 &&
+           k2_options().bound != 0;
 }
 
 extern "C" int abub_diff_hist_chained_deferred_dev(const uint8_t *frames, const uint8_t *sigma6, const abub_job *jobs, int njobs,

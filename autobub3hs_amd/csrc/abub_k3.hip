@@ -238,7 +238,7 @@ __global__ __launch_bounds__(64) void k3_rows(const uint8_t *__restrict__ frames
         cp.count = pcount;
         cp.cap = pcap;
         cp.slot = jb.out + slot_base;
-        cp.thr = cthr ? cthr[jb.out] : 255;
+        cp.thr = cthr ? compact_thr(cthr, jb.out) : 255;
 
         uint32_t raw[2][3][NDW]; // frame, mu, sigma6
 #define K3_LOAD(SL, Y)                                                                        \
@@ -561,44 +561,78 @@ __global__ __launch_bounds__(64) void k3_bound_scan(const uint8_t *__restrict__ 
             cp.count = pcount;
             cp.cap = pcap;
             cp.slot = jb[t].out + slot_base;
-            cp.thr = COMPACT ? cthr[jb[t].out] : 255;
+            cp.thr = COMPACT ? compact_thr(cthr, jb[t].out) : 255;
             k3s_tail<COMPACT>(pend[t], J[t].npend, jb[t], frames, mu, sigma6, W, H, hist, img, cp, lane);
         }
     }
 }
 
-static int k3_scan_enabled()
+// Tuning knobs of the K3 launcher.  Defaults come from the environment once (ABUB_K3_SCAN, ABUB_K3_LIST,
+// ABUB_K3_BUDGET, ABUB_K3_CHUNKS); abub_k3_set_option() overrides them at run time, as abub_k2_set_option() does for K2.
+struct K3Options {
+    int scan = 1;          // 0: the row machine on every row (no zero scan)
+    int list = 1;          // 0: suspects are evaluated by the scanning waves themselves (k3s_tail), 1: sus_tail_list
+    int budget = K3S_PEND; // suspects a (job, chunk) may remember before it hands a piece over (0 .. K3S_PEND)
+    int chunks = 0;        // chunks per frame (0 = automatic)
+    bool loaded = false;
+};
+static K3Options g_k3opt;
+static std::mutex g_k3optMu;
+static K3Options k3_options()
 {
-    static int on = -1;
-    if (on < 0) {
-        const char *e = getenv("ABUB_K3_SCAN"); // 0: the row machine on every row (no zero scan)
-        on = e ? atoi(e) : 1;
+    std::lock_guard<std::mutex> lock(g_k3optMu);
+    if (!g_k3opt.loaded) {
+        if (const char *e = getenv("ABUB_K3_SCAN"))
+            g_k3opt.scan = atoi(e) != 0;
+        if (const char *e = getenv("ABUB_K3_LIST"))
+            g_k3opt.list = atoi(e) != 0;
+        if (const char *e = getenv("ABUB_K3_BUDGET"))
+            if (atoi(e) >= 0 && atoi(e) <= K3S_PEND)
+                g_k3opt.budget = atoi(e);
+        if (const char *e = getenv("ABUB_K3_CHUNKS"))
+            if (atoi(e) >= 0 && atoi(e) <= K_MAX_CHUNKS)
+                g_k3opt.chunks = atoi(e);
+        g_k3opt.loaded = true;
     }
-    return on;
+    return g_k3opt;
+}
+
+extern "C" int abub_k3_set_option(const char *name, int value)
+{
+    if (!name)
+        return set_err(ABUB_E_INVALID, "abub_k3_set_option: null name");
+    (void)k3_options();
+    std::lock_guard<std::mutex> lock(g_k3optMu);
+    if (!strcmp(name, "scan") && (value == 0 || value == 1))
+        g_k3opt.scan = value;
+    else if (!strcmp(name, "list") && (value == 0 || value == 1))
+        g_k3opt.list = value;
+    else if (!strcmp(name, "budget") && value >= 0 && value <= K3S_PEND)
+        g_k3opt.budget = value;
+    else if (!strcmp(name, "chunks") && value >= 0 && value <= K_MAX_CHUNKS)
+        g_k3opt.chunks = value;
+    else
+        return set_err(ABUB_E_INVALID, "abub_k3_set_option: unknown option or bad value");
+    return ABUB_OK;
 }
 
 template <int NDW>
 static int launch_k3_rows(const uint8_t *frames, const uint8_t *mu, const uint8_t *sigma6, const abub_job *jobs,
                           int njobs, int W, int H, int R, int nchunks, uint32_t *hist, uint8_t *img,
-                          const CompactArgs &ca, hipStream_t st)
+                          const CompactArgs &ca, const K3Options &opt, hipStream_t st)
 {
 #define K3R_LAUNCH(ST, GRID, PL, PC)                                                                                 \
     hipLaunchKernelGGL((k3_rows<NDW, ST>), dim3(GRID), dim3(64), 0, st, frames, mu, sigma6, jobs, W, H, R, nchunks,   \
                        hist, img, ca.cthr, ca.pairs, ca.cap, ca.count, ca.slot_base, PL, PC)
-    if (k3_scan_enabled() && H < 65536 && (size_t)H * (size_t)(W / 4) < ((size_t)1 << 32)) {
+    if (opt.scan && H < 65536 && (size_t)H * (size_t)(W / 4) < ((size_t)1 << 32)) {
         constexpr int KF = NDW <= 5 ? 5 : (NDW <= 7 ? 4 : 3); // jobs per scanning wave (register budget)
         const size_t nunits = (size_t)njobs * nchunks;
         const size_t cap = nunits * (size_t)((R + K2B_SUB - 1) / K2B_SUB); // handed-over pieces, worst case
         // the global suspect list (see sus_tail_list): room for 2048 groups per frame on average -- the footprint of a
         // tracked bubble is a few hundred to a thousand groups -- within 64 K .. 16 M entries
-        static int k3list = -1;
-        if (k3list < 0) {
-            const char *e = getenv("ABUB_K3_LIST"); // 0: suspects are evaluated by the scanning waves themselves
-            k3list = e ? atoi(e) : 1;
-        }
         size_t gcap = (size_t)njobs * 2048;
         gcap = gcap < ((size_t)1 << 16) ? ((size_t)1 << 16) : (gcap > ((size_t)1 << 24) ? ((size_t)1 << 24) : gcap);
-        if (!k3list)
+        if (!opt.list)
             gcap = 0;
         const size_t piecesBytes = (cap * sizeof(uint2) + 255) & ~(size_t)255;
         std::unique_lock<std::mutex> hold;
@@ -611,14 +645,7 @@ static int launch_k3_rows(const uint8_t *frames, const uint8_t *mu, const uint8_
         uint2 *glist = gcap ? (uint2 *)(scr + 256 + piecesBytes) : nullptr;
         HIPCHK(hipMemsetAsync(counter, 0, 256, st));
         const dim3 sgrid((unsigned)((size_t)((njobs + KF - 1) / KF) * nchunks));
-        static int k3b = -1;
-        if (k3b < 0) {
-            const char *e = getenv("ABUB_K3_BUDGET"); // suspects a (job, chunk) may remember before it hands a piece over
-            k3b = e ? atoi(e) : K3S_PEND;
-            if (k3b < 0 || k3b > K3S_PEND)
-                k3b = K3S_PEND;
-        }
-        const uint32_t k3budget = (uint32_t)k3b;
+        const uint32_t k3budget = (uint32_t)opt.budget;
 #define K3S_LAUNCH(ST, CO)                                                                                          \
     hipLaunchKernelGGL((k3_bound_scan<NDW, KF, CO>), sgrid, dim3(64), 0, st, frames, mu, sigma6, jobs, njobs, W, H, R,  \
                        nchunks, hist, img, pieces, counter, ca.cthr, ca.pairs, ca.cap, ca.count, ca.slot_base,      \
@@ -696,18 +723,14 @@ static int posttrig_impl(const uint8_t *frames, const uint8_t *mu, const uint8_t
     if (ndw) {
         // waves of the launch = (groups of jobs one wave serves) x chunks: enough of them (>= ~8k, several rounds of the
         // chip's wave slots) that the exact tails of early waves run under the scans of later ones
-        const int kf = k3_scan_enabled() ? (ndw <= 5 ? 5 : (ndw <= 7 ? 4 : 3)) : 1;
+        const K3Options opt = k3_options(); // read once: the chunking below and the launch must agree
+        const int kf = opt.scan ? (ndw <= 5 ? 5 : (ndw <= 7 ? 4 : 3)) : 1;
         const long long ngrp = (njobs + kf - 1) / kf;
         int nch = 8;
         if (ngrp * nch < 8192)
             nch = (int)((8192 + ngrp - 1) / ngrp);
-        static int k3chunks = -1;
-        if (k3chunks < 0) {
-            const char *e = getenv("ABUB_K3_CHUNKS"); // tuning knob: chunks per frame (0 = automatic)
-            k3chunks = e ? atoi(e) : 0;
-        }
-        if (k3chunks > 0)
-            nch = k3chunks;
+        if (opt.chunks > 0)
+            nch = opt.chunks;
         nch = (nch + 7) / 8 * 8;
         int R = (H + nch - 1) / nch;
         if (R < 16)
@@ -715,14 +738,14 @@ static int posttrig_impl(const uint8_t *frames, const uint8_t *mu, const uint8_t
         int nchunks = (H + R - 1) / R;
         int rc3 = ABUB_OK;
         switch (ndw) {
-        case 1: rc3 = launch_k3_rows<1>(frames, mu, sigma6, jobs, njobs, W, H, R, nchunks, hist, img, ca, st); break;
-        case 2: rc3 = launch_k3_rows<2>(frames, mu, sigma6, jobs, njobs, W, H, R, nchunks, hist, img, ca, st); break;
-        case 3: rc3 = launch_k3_rows<3>(frames, mu, sigma6, jobs, njobs, W, H, R, nchunks, hist, img, ca, st); break;
-        case 4: rc3 = launch_k3_rows<4>(frames, mu, sigma6, jobs, njobs, W, H, R, nchunks, hist, img, ca, st); break;
-        case 5: rc3 = launch_k3_rows<5>(frames, mu, sigma6, jobs, njobs, W, H, R, nchunks, hist, img, ca, st); break;
-        case 6: rc3 = launch_k3_rows<6>(frames, mu, sigma6, jobs, njobs, W, H, R, nchunks, hist, img, ca, st); break;
-        case 7: rc3 = launch_k3_rows<7>(frames, mu, sigma6, jobs, njobs, W, H, R, nchunks, hist, img, ca, st); break;
-        default: rc3 = launch_k3_rows<8>(frames, mu, sigma6, jobs, njobs, W, H, R, nchunks, hist, img, ca, st); break;
+        case 1: rc3 = launch_k3_rows<1>(frames, mu, sigma6, jobs, njobs, W, H, R, nchunks, hist, img, ca, opt, st); break;
+        case 2: rc3 = launch_k3_rows<2>(frames, mu, sigma6, jobs, njobs, W, H, R, nchunks, hist, img, ca, opt, st); break;
+        case 3: rc3 = launch_k3_rows<3>(frames, mu, sigma6, jobs, njobs, W, H, R, nchunks, hist, img, ca, opt, st); break;
+        case 4: rc3 = launch_k3_rows<4>(frames, mu, sigma6, jobs, njobs, W, H, R, nchunks, hist, img, ca, opt, st); break;
+        case 5: rc3 = launch_k3_rows<5>(frames, mu, sigma6, jobs, njobs, W, H, R, nchunks, hist, img, ca, opt, st); break;
+        case 6: rc3 = launch_k3_rows<6>(frames, mu, sigma6, jobs, njobs, W, H, R, nchunks, hist, img, ca, opt, st); break;
+        case 7: rc3 = launch_k3_rows<7>(frames, mu, sigma6, jobs, njobs, W, H, R, nchunks, hist, img, ca, opt, st); break;
+        default: rc3 = launch_k3_rows<8>(frames, mu, sigma6, jobs, njobs, W, H, R, nchunks, hist, img, ca, opt, st); break;
         }
         if (rc3 != ABUB_OK)
             return rc3;

@@ -328,10 +328,10 @@ __global__ __launch_bounds__(256) void k4_compact(const uint8_t *__restrict__ im
         for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < nv; q += stride) {
             uint4 w = reinterpret_cast<const uint4 *>(im)[q];
             uint32_t ww[4] = {w.x, w.y, w.z, w.w};
-            // v > t  for any byte?  quick reject: all bytes <= t
+            // quick reject of an all-zero dword: no byte is > t when t >= 0 (t < 0 admits value 0)
 #pragma unroll
             for (int d = 0; d < 4; d++) {
-                if (ww[d] == 0)
+                if (ww[d] == 0 && t >= 0)
                     continue;
 #pragma unroll
                 for (int b = 0; b < 4; b++) {
@@ -394,7 +394,7 @@ __global__ __launch_bounds__(256) void k4_compact_pairs(const uint8_t *__restric
             uint32_t ww[4] = {w.x, w.y, w.z, w.w};
 #pragma unroll
             for (int d = 0; d < 4; d++) {
-                if (ww[d] == 0)
+                if (ww[d] == 0 && t >= 0) // (t < 0 admits value 0)
                     continue;
 #pragma unroll
                 for (int b = 0; b < 4; b++) {
@@ -538,7 +538,8 @@ __global__ __launch_bounds__(256) void k_pairs_scatter(const uint32_t *__restric
 }
 
 // counts per slot straight from the histograms the producing kernels already made: the number of
-// list entries of slot s is the number of its pixels with value > cthr[s]
+// list entries of slot s is the number of its pixels with value > max(cthr[s], 0) (the fused K2 / K3
+// lists never hold value-0 pixels, see compact_thr)
 __global__ __launch_bounds__(64) void k_slot_counts_from_hist(const uint32_t *__restrict__ hist,
                                                               const int32_t *__restrict__ cthr, uint32_t nslots,
                                                               uint32_t *__restrict__ slotcount)
@@ -547,7 +548,7 @@ __global__ __launch_bounds__(64) void k_slot_counts_from_hist(const uint32_t *__
     if (sl >= nslots)
         return;
     const uint32_t *h = hist + (size_t)sl * 256;
-    const int t = cthr[sl];
+    const int t = cthr[sl] < 0 ? 0 : cthr[sl];
     const int l = threadIdx.x;
     uint32_t c = 0;
 #pragma unroll

@@ -98,8 +98,13 @@ def diff_hist_pieces(frames, sigma6_, jobs, W, H, hist, state, want):
 
 
 def k2_set_option(name, value):
-    """Run-time K2 launcher knob ("bound", "chain", "budget", "pf"); results never depend on them."""
+    """Run-time K2 launcher knob ("bound", "chain", "budget", "pf", "chunks", ...); results never depend on them."""
     _lib.check(_lib.lib().abub_k2_set_option(name.encode(), int(value)), "abub_k2_set_option")
+
+
+def k3_set_option(name, value):
+    """Run-time K3 launcher knob ("scan", "list", "budget", "chunks"); results never depend on them."""
+    _lib.check(_lib.lib().abub_k3_set_option(name.encode(), int(value)), "abub_k3_set_option")
 
 
 def bound_counts(stream=None):

@@ -30,6 +30,9 @@ def lib():
     if _lib is None:
         if not os.path.exists(SO):
             raise RuntimeError(f"{SO} is missing: run __graft_entry__.build()")
+        from . import _lib as hiplib
+
+        hiplib.lib()  # the HIP library first, bound to torch's HIP runtime (see _lib.lib)
         L = C.CDLL(SO)
         L.abh_run_new.restype = C.c_void_p
         L.abh_run_free.argtypes = [C.c_void_p]

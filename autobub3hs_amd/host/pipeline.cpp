@@ -520,8 +520,10 @@ public:
         Group::Fetch fe;
         fe.first = first;
         fe.n = n;
-        const size_t pcap = deferPieces ? abub_k2_pieces_cap(nj, W, H) : 0;
-        if (deferPieces && G.fetches[k].size() < 64 && G.pieceUsedB[k] + pcap <= G.pieceCapB[k]) {
+        // deferral is decided per launch: the K2 options (abub_k2_set_option "bound") may change after construction
+        const bool defer = deferPieces && abub_k2_deferred_ok(W, H);
+        const size_t pcap = defer ? abub_k2_pieces_cap(nj, W, H) : 0;
+        if (defer && G.fetches[k].size() < 64 && G.pieceUsedB[k] + pcap <= G.pieceCapB[k]) {
             // the scan alone: dense frames' rows go to this launch's range of the block's piece list, their jobs are flagged
             fe.deferred = true;
             fe.pieceOff = G.pieceUsedB[k];

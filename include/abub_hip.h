@@ -97,7 +97,8 @@ int abub_posttrig_dev(const uint8_t *frames, const uint8_t *mu, const uint8_t *s
 /* K4: binarize (v > thr[k]) + stream-compaction of foreground pixel indices, for nimg images
  * img[k] (the TOZERO + BINARY|OTSU mask of L3Localizer.cpp:252-254,786-787 with
  * thr = max(loc_thres, otsu)).  idx: [nimg][cap] u32 raster indices (unordered); count: [nimg]
- * (true counts, may exceed cap -> caller falls back to abub_fetch). */
+ * (true counts, may exceed cap -> caller falls back to abub_fetch; nothing is written past cap).
+ * Any thr: a negative one lists value-0 pixels too. */
 int abub_fg_compact_dev(const uint8_t *img, int nimg, int W, int H, const int32_t *thr,
                         uint32_t *idx, int cap, uint32_t *count, void *stream);
 
@@ -107,6 +108,7 @@ int abub_fg_compact_dev(const uint8_t *img, int nimg, int W, int H, const int32_
  * (unordered; *count = true total, may exceed cap; count must be zeroed by the caller).  With the
  * list the images need not be materialised (diff / img may be NULL): cthr = the TOZERO threshold is
  * known before the launch, the final Otsu cut is applied to the listed values on the host.
+ * These lists never hold value-0 pixels: a negative cthr lists like cthr = 0 (pixels with value >= 1).
  * Fast path only (abub_fast_path(W) != 0). */
 int abub_fast_path(int W);
 
@@ -152,8 +154,26 @@ int abub_diff_hist_pieces_dev(const uint8_t *frames, const uint8_t *sigma6, cons
  *   "scanpf" rows the chained scan fetches ahead: 1, 2, -1 (default) = 2 where instantiated (trigger-only, W = 1280 class)
  *   "wg"     waves per workgroup of the chained scan = consecutive segments of one chain (1 .. 8; -1 default = 1)
  *   "sync"   row steps a wave of such a workgroup may run ahead of its slowest wave (0 = never waits; -1 default = 0)
- * Results never depend on them. */
+ *   "chunks" chunks per frame where the launcher picks the chunk height itself (rows_per_chunk = 0, the chained, deferred
+ *            and compact forms); 0 (default) = automatic, else 1 .. 4096 (chunks are at least 16 rows high)
+ * Results never depend on them.  abub_k2_pieces_cap() and abub_diff_hist_pieces_dev() recompute the deferred launch's
+ * chunking, so the options must not change between a deferred call and the pieces calls that complete it.
+ * Unknown names and bad values return ABUB_E_INVALID. */
 int abub_k2_set_option(const char *name, int value);
+
+/* 1 when abub_diff_hist_chained_deferred_dev() accepts W x H frames under the current K2 options (fast-path width and
+ * the "bound" option on), else 0.  Callers decide per launch, since the options can change at any time. */
+int abub_k2_deferred_ok(int W, int H);
+
+/* Run-time tuning knobs of the K3 launcher (abub_posttrig_dev / abub_posttrig_compact_dev; defaults from ABUB_K3_SCAN /
+ * _LIST / _BUDGET / _CHUNKS in the environment, read at first use):
+ *   "scan"   1 (default) = zero scan with exact suspect groups, 0 = the row machine on every row
+ *   "list"   1 (default) = suspect groups go to a global list that a second kernel evaluates, 0 = the scanning waves
+ *            evaluate their own
+ *   "budget" suspect groups a (job, chunk) may keep in LDS before it hands a piece of rows over: 0 .. 512 (default 512)
+ *   "chunks" chunks per frame: 0 (default) = automatic, else 1 .. 4096 (chunks are at least 16 rows high)
+ * Results never depend on them.  Unknown names and bad values return ABUB_E_INVALID. */
+int abub_k3_set_option(const char *name, int value);
 
 /* The bound-and-verify form of abub_diff_hist_dev keeps a work list in device scratch memory that the
  * library owns, one buffer per (device, stream), grown on demand.  Call this before destroying a stream that was
@@ -174,21 +194,25 @@ int abub_posttrig_compact_dev(const uint8_t *frames, const uint8_t *mu, const ui
                               uint32_t slot_base, void *stream);
 
 /* Group such a list by slot on the device (counting sort): offsets[s] .. offsets[s+1] delimit slot s
- * in idx_out / val_out (raster index, value); offsets[nslots] = total (<= cap).  `count` is read on the
+ * in idx_out / val_out (raster index, value); offsets[nslots] = total (<= cap).  Only the first min(*count, cap)
+ * entries are read; entries with slot >= nslots are dropped.  `count` is read on the
  * device, no host synchronisation needed between the producing launches and this call. */
 int abub_pairs_group_dev(const uint32_t *pairs, const uint32_t *count, uint32_t cap, int nslots,
                          uint32_t *scratch /* [2*nslots] */, uint32_t *offsets /* [nslots+1] */,
                          uint32_t *idx_out /* [cap] */, uint8_t *val_out /* [cap] */, void *stream);
 
 /* Same, with the per-slot counts taken from the producers' histograms (entries of slot s = pixels of hist[s]
- * with value > cthr[s]) instead of a counting pass over the list; valid when the list did not overflow. */
+ * with value > max(cthr[s], 0), the rule of the fused lists) instead of a counting pass over the list; valid when the
+ * list did not overflow (on overflow nothing is written at or past idx_out[cap] / val_out[cap]).  A K4 list made with
+ * a negative threshold holds value-0 pixels: group it with abub_pairs_group_dev. */
 int abub_pairs_group_hist_dev(const uint32_t *pairs, const uint32_t *count, uint32_t cap, int nslots,
                               uint32_t *scratch, uint32_t *offsets, uint32_t *idx_out, uint8_t *val_out,
                               const uint32_t *hist /* [nslots][256] */, const int32_t *cthr /* [nslots] */,
                               void *stream);
 
 /* K4, batched form: one shared output list for all nimg images, pairs[2*k] = image | value << 24,
- * pairs[2*k+1] = y*W+x (unordered); *count = true total (may exceed cap). */
+ * pairs[2*k+1] = y*W+x (unordered); *count = true total (may exceed cap; nothing is written past cap).
+ * Any thr, as abub_fg_compact_dev. */
 int abub_fg_compact_pairs_dev(const uint8_t *img, int nimg, int W, int H, const int32_t *thr,
                               uint32_t *pairs, uint32_t cap, uint32_t *count, void *stream);
 

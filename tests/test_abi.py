@@ -53,3 +53,18 @@ def test_product_never_imports_oracle():
             if f.endswith((".py", ".hip", ".cpp", ".hpp", ".h")):
                 src = open(os.path.join(dp, f), errors="replace").read()
                 assert "pyoracle" not in src and "abub_oracle" not in src and "liboracle" not in src, f
+
+
+def test_option_setters_refuse_bad_names_and_values():
+    """abub_k2_set_option / abub_k3_set_option validate before anything else (no device needed): unknown and null
+    names and out-of-range values are refused with ABUB_E_INVALID and leave the options as they were."""
+    L = _lib.lib()
+    for setter in (L.abub_k2_set_option, L.abub_k3_set_option):
+        assert setter(None, 1) == -1
+        assert b"null name" in L.abub_last_error()
+        assert setter(b"no_such_option", 1) == -1
+        assert b"unknown option" in L.abub_last_error()
+        assert setter(b"chunks", -1) == -1 and setter(b"chunks", 4097) == -1
+    for name, value in ((b"scan", 2), (b"scan", -1), (b"list", 2), (b"budget", -1), (b"budget", 513), (b"pf", 1)):
+        assert L.abub_k3_set_option(name, value) == -1, name
+    assert L.abub_k2_set_option(b"budget", 0) == -1
