@@ -62,6 +62,10 @@ SIGNATURES = {
     "abub_match_ccorr_batch_dev": (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _vp]),
     "abub_match_best_batch_dev": (_i, [_vp, _i, _i, _vp, _i, _vp, _i, _i, _vp, _vp, _sz, _vp]),
     "abub_match_best_scratch_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "abub_binarize_thr_dev": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp]),
+    "abub_label_blobs_dev": (_i, [_vp, _vp, _vp, C.c_uint32, _i, _i, _i, _vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp,
+                                  C.c_uint32, _vp, _vp, _sz, _vp]),
+    "abub_label_blobs_scratch_bytes": (_sz, [_i, _i, _i, C.c_uint32, _i]),
     "abub_ctx_create": (_i, [C.POINTER(_vp), _i, _i, _i, _i]),
     "abub_ctx_destroy": (None, [_vp]),
     "abub_ctx_train": (_i, [_vp, C.POINTER(_vp), _i, _vp, _vp]),

@@ -171,6 +171,45 @@ def fg_compact(img, thr, cap):
     return idx, cnt
 
 
+
+def binarize_thr(hist, tozero, W, H):
+    """Device Otsu (abub_binarize_thr_dev): hist [n,256] i32, tozero int32 [n] -> thr int32 [n], bit for bit the host's
+    binarizeThresholdFromHist(hist[s], W*H, tozero[s])."""
+    _need_cuda(hist, tozero)
+    n = tozero.numel()
+    thr = torch.empty((n,), dtype=torch.int32, device=hist.device)
+    _lib.check(_lib.lib().abub_binarize_thr_dev(_ptr(hist), _ptr(tozero), n, W, H, _ptr(thr), _stream()),
+               "abub_binarize_thr_dev")
+    return thr
+
+
+def label_blobs(offsets, idx, val, thr, min_box_area, W, H, cap=None, comp=True, in_cap=None):
+    """K4b (abub_label_blobs_dev) on a grouped candidate list: offsets int32 [n+1], idx int32 [>= offsets[n]], val u8,
+    thr / min_box_area int32 [n] -> dict of device tensors kept_off [n+1], kept_idx [cap], ncomp [n], nkept_comp [n],
+    comp_off [n+1], comp [cap, 6] int32 (first, x0, y0, x1, y1, npix) or None, stats [4] (global-path slots, foreground
+    pixels, components, kept components).  cap defaults to the list's length (kept <= candidates)."""
+    _need_cuda(offsets, idx, val, thr, min_box_area)
+    n = thr.numel()
+    dev = idx.device
+    in_cap = int(idx.numel()) if in_cap is None else int(in_cap)
+    cap = max(in_cap, 1) if cap is None else int(cap)
+    L = _lib.lib()
+    need = int(L.abub_label_blobs_scratch_bytes(n, W, H, in_cap, 1 if comp else 0))
+    scratch = torch.empty((max(need, 1),), dtype=torch.uint8, device=dev)
+    out = {"kept_off": torch.empty((n + 1,), dtype=torch.int32, device=dev),
+           "kept_idx": torch.empty((cap,), dtype=torch.int32, device=dev),
+           "ncomp": torch.empty((n,), dtype=torch.int32, device=dev),
+           "nkept_comp": torch.empty((n,), dtype=torch.int32, device=dev),
+           "comp_off": torch.empty((n + 1,), dtype=torch.int32, device=dev),
+           "comp": torch.empty((cap, 6), dtype=torch.int32, device=dev) if comp else None,
+           "stats": torch.empty((4,), dtype=torch.int32, device=dev)}
+    _lib.check(L.abub_label_blobs_dev(_ptr(offsets), _ptr(idx), _ptr(val), in_cap, n, W, H, _ptr(thr), _ptr(min_box_area),
+                                      _ptr(out["kept_off"]), _ptr(out["kept_idx"]), cap, _ptr(out["ncomp"]),
+                                      _ptr(out["nkept_comp"]), _ptr(out["comp_off"]), _ptr(out["comp"]), cap if comp else 0,
+                                      _ptr(out["stats"]), _ptr(scratch), scratch.numel(), _stream()),
+               "abub_label_blobs_dev")
+    return out
+
 # ---- PNG frames decoded on the GPU (abub_png_decode_dev) --------------------------------------------------------
 def png_parse(data, W, H):
     """What the host does per file before the upload: walk the chunks of a PNG, -> (idat segments [(offset, length)],

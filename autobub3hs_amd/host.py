@@ -392,6 +392,27 @@ class Pipeline:
                          "s3_bucket_ms", "pairs", "trigger_jobs", "dropin_stacks", "jobs_completed_on_demand"), list(out)),
                     rounds=rounds)
 
+    def set_option(self, name, value):
+        """Run-time knob of this pipeline object: "blobs" 0 (default, from ABUB_PIPE_BLOBS) or 1 -- label the foreground on
+        the GPU and ship only the pixels of the components the localizer can use.  Results never depend on it."""
+        L = lib()
+        L.abh_pipe_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
+        L.abh_pipe_error.restype = C.c_char_p
+        if L.abh_pipe_set_option(self._h, name.encode(), int(value)) != 0:
+            raise ValueError(L.abh_pipe_error().decode())
+
+    def blob_stats(self):
+        """Blob labelling of the last run (zeros when the "blobs" knob was off), summed over stack groups and rounds."""
+        L = lib()
+        L.abh_pipe_blob_stats.argtypes = [C.c_void_p, _dp]
+        out = (C.c_double * 8)()
+        L.abh_pipe_blob_stats(self._h, out)
+        v = list(out)
+        keys = ("candidates", "foreground", "kept", "components", "kept_components", "large_slots")
+        d = {k: int(x) for k, x in zip(keys, v)}
+        d.update(otsu_ms=v[6], k4b_ms=v[7])
+        return d
+
     def bellows_stats(self):
         """Bellows veto of the last run: stacks vetoed inside the batch, template-match jobs and launches, residual
         images, wall time of the veto rounds (ms)."""

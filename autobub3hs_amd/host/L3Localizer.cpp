@@ -46,12 +46,14 @@ L3Localizer::~L3Localizer()
 static cv::Mat cachedMask(const std::string &path);
 static thread_local abub::ContourFinder t_finder;
 
-static void contoursOfCurrentImage(abub::EventData &ev, const uint32_t *hist, int tozeroThr,
+// minBoxArea: the caller drops every contour whose bounding box has area <= minBoxArea (-1: keeps all), so the provider
+// may leave out components that small (EventData::foregroundKept)
+static void contoursOfCurrentImage(abub::EventData &ev, const uint32_t *hist, int tozeroThr, int minBoxArea,
                                    std::vector<std::vector<cv::Point>> &contours, cv::Mat *debugMask = nullptr)
 {
     const int thr = abub::binarizeThresholdFromHist(hist, (size_t)ev.W * ev.H, tozeroThr);
     std::vector<uint32_t> fg;
-    ev.foreground(thr, fg);
+    ev.foregroundKept(thr, minBoxArea, fg);
     if (debugMask) { // the thresholded image of L3Localizer.cpp:254 (debug write-out only)
         *debugMask = cv::Mat::zeros(ev.H, ev.W, CV_8U);
         for (uint32_t i : fg)
@@ -116,7 +118,7 @@ void L3Localizer::CalculateInitialBubbleParams(void)
         std::cout << "this->loc_thres: " << loc_thres << std::endl;
     }
     std::vector<std::vector<cv::Point>> contours;
-    contoursOfCurrentImage(ev, hist, loc_thres, contours, dbg ? &thresFrame : nullptr);
+    contoursOfCurrentImage(ev, hist, loc_thres, -1, contours, dbg ? &thresFrame : nullptr);
     if (dbg)
         cv::imwrite(peek + "_3_OtsuThresholded.png", thresFrame);
 
@@ -164,7 +166,7 @@ void L3Localizer::CalculateInitialBubbleParams(void)
                     throw std::runtime_error("L3Localizer: bellows ROI outside the frame");
                 // renderings, ROI ProcessFrame, overTheSigma -= diff_frame (:326-362)
                 hist = ev.bellowsResidual(MatTrigFrame, pre, TemplateImage, rt, rp, diffROI);
-                contoursOfCurrentImage(ev, hist, loc_thres, contours);
+                contoursOfCurrentImage(ev, hist, loc_thres, -1, contours);
             }
             largestBoxArea = 0;
             minRect.clear();
@@ -205,12 +207,12 @@ void L3Localizer::CalculatePostTriggerFrameParams(int postTrigFrameNumber)
         throw std::runtime_error("L3Localizer: undecodable post-trigger frame");
     const uint32_t *hist = ev.postTrig(frame);
     std::vector<std::vector<cv::Point>> contours;
-    contoursOfCurrentImage(ev, hist, 3, contours);
+    contoursOfCurrentImage(ev, hist, 3, abub::kTrackMinBoxArea, contours);
 
     std::vector<BubbleImageFrame> sightings;
     for (auto &c : contours) {
         cv::Rect r = abub::boundingRectOf(c);
-        if (r.width * r.height > 10) {
+        if (r.width * r.height > abub::kTrackMinBoxArea) {
             BubbleImageFrame f = describe(c, r, false);
             if (!isInMask(&f.newPosition))
                 continue;

@@ -16,6 +16,9 @@ class Trainer;
 
 namespace abub {
 
+// contours whose bounding box has at most this area are dropped in a tracking frame (L3Localizer.cpp:800-805)
+constexpr int kTrackMinBoxArea = 10;
+
 // Throws std::runtime_error carrying abub_last_error(): AnyCamAnalysis maps exceptions to status -6
 // (reference AutoBubStart3.cpp:114-117).
 void check(int rc, const char *what);
@@ -53,6 +56,10 @@ public:
     virtual const uint32_t *postTrig(int i, cv::Mat *out = nullptr) = 0;
     // foreground (v > thr) raster indices of the current image
     virtual void foreground(int thr, std::vector<uint32_t> &idx) = 0;
+    // foreground raster indices of the current image, of which a provider may leave out the pixels of 8-connected
+    // components whose bounding box has area <= minBoxArea (-1: none left out): the contours such components yield are
+    // dropped by the caller anyway, and they enclose no other component (abub_blobs.hip).  Default: foreground().
+    virtual void foregroundKept(int thr, int minBoxArea, std::vector<uint32_t> &idx) { foreground(thr, idx); }
     // bellows veto: exact correlation terms of frame i against a template ((H-th+1) x (W-tw+1) placements)
     virtual void matchTerms(int i, const cv::Mat &templ, std::vector<unsigned long long> &num,
                             std::vector<unsigned long long> &wsum2) = 0;

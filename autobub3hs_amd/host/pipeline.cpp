@@ -51,6 +51,12 @@ struct PlannedImage {
     const uint32_t *fg = nullptr; // raster indices of the candidate pixels (value > tozero), grouped on the GPU
     const uint8_t *fgv = nullptr; // their values: the Otsu cut is applied on the host
     uint32_t nfg = 0;
+    int minBox = -1; // the localizer drops contours with box area <= minBox (-1: keeps all): kTrackMinBoxArea when tracking
+    // blobs knob: the pixels of the kept components (K4b, abub_blobs.hip) in raster order, labelled on the device with the
+    // device's Otsu threshold (kept == nullptr: served from fg / fgv)
+    const uint32_t *kept = nullptr;
+    uint32_t nkept = 0;
+    bool otsuMismatch = false; // the device's Otsu threshold differs from the host's (parity tripwire)
 };
 
 // thrown by the batched provider when the trigger search asks for a frame whose block has not been evaluated yet: the
@@ -219,6 +225,19 @@ public:
             if ((int)p.fgv[k] > thr)
                 idx.push_back(p.fg[k]);
     }
+    void foregroundKept(int thr, int minBoxArea, std::vector<uint32_t> &idx) override
+    {
+        if (!cur || cur->thr != thr || cur->minBox != minBoxArea)
+            throw std::runtime_error("BatchEventData::foregroundKept: threshold or min box area differs from the planned one");
+        const PlannedImage &p = *cur;
+        if (!p.kept) {
+            foreground(thr, idx);
+            return;
+        }
+        if (p.otsuMismatch)
+            throw std::runtime_error("BatchEventData::foregroundKept: device Otsu threshold differs from the host's");
+        idx.assign(p.kept, p.kept + p.nkept);
+    }
 };
 
 struct BubbleOut {
@@ -379,6 +398,18 @@ struct Group {
     abub_job *h_jobs3 = nullptr;
     int32_t *h_thr = nullptr;
     uint32_t pairCap = 0;
+    // blobs knob: device Otsu + K4b behind the grouping (allocated on first use; kept list and scratch grow with pairCap)
+    struct Blobs {
+        bool ready = false;
+        int32_t *d_otsu = nullptr, *h_otsu = nullptr, *d_minbox = nullptr, *h_minbox = nullptr;
+        uint32_t *d_koff = nullptr, *h_koff = nullptr, *d_kidx = nullptr, *h_kidx = nullptr;
+        uint32_t *d_ncomp = nullptr, *d_nkc = nullptr, *d_coff = nullptr, *d_stats = nullptr, *h_stats = nullptr;
+        void *d_scratch = nullptr;
+        size_t scratchBytes = 0;
+        uint32_t cap = 0; // of d_kidx / h_kidx and the scratch's staging
+        hipEvent_t ev[3] = {nullptr, nullptr, nullptr}; // before Otsu, between, after K4b
+        double stats[8] = {0}; // last run: see abh_pipe_blob_stats
+    } blobs;
     // bellows veto round (vetoRound): its own buffers, allocated on first use, grown on demand
     struct Veto {
         int capJobs = 0;           // match jobs the buffers hold
@@ -423,9 +454,11 @@ public:
     int dropIns = 0;                    // stacks of the last run that went through the one-at-a-time path (bellows veto)
     bool bellowsDropIn = false;         // ABUB_PIPE_BELLOWS=dropin: every bellows veto takes the one-at-a-time path (A/B)
     double bellowsStats[5] = {0};       // last run: vetoed stacks, match jobs, match launches, residual images, veto ms
+    double blobStats[8] = {0};          // last run, blobs knob: see abh_pipe_blob_stats
     hipStream_t stage1Stream = nullptr; // all trigger-search launches, in group order (see run())
     int chainStride = 0;                // FindTriggerFrame's frame offset when every camera shares it, else 0
     bool ordered = true;                // localisation kernels queue on stage1Stream too (see batchImages())
+    int blobs = 0;                      // 1: stage 3 labels blobs on the GPU and ships only the kept pixels (set_option "blobs")
     std::vector<void *> devAllocs, hostAllocs;
     std::mutex allocMu, launchMu;
     std::vector<StackState> stacks;
@@ -584,6 +617,8 @@ public:
             bellowsDropIn = ebw && std::string(ebw) == "dropin";
             const char *eo = getenv("ABUB_PIPE_ORDERED");
             ordered = eo ? atoi(eo) != 0 : true;
+            const char *eb = getenv("ABUB_PIPE_BLOBS");
+            blobs = eb ? atoi(eb) != 0 : 0;
             int prLow = 0, prHigh = 0; // (numerically lower = higher priority)
             HIPOK(hipDeviceGetStreamPriorityRange(&prLow, &prHigh));
             HIPOK(hipStreamCreateWithPriority(&stage1Stream, hipStreamNonBlocking, prLow));
@@ -707,6 +742,9 @@ public:
                 (void)hipEventDestroy(G.kernelsDone);
             if (G.blockDone)
                 (void)hipEventDestroy(G.blockDone);
+            for (hipEvent_t &e : G.blobs.ev)
+                if (e)
+                    (void)hipEventDestroy(e);
         }
         if (stage1Stream) {
             (void)abub_scratch_release(stage1Stream); // the trigger search's work list lives in library scratch
@@ -798,6 +836,7 @@ public:
             t.join();
         std::fill(tms, tms + 8, 0.0);
         std::fill(bellowsStats, bellowsStats + 5, 0.0);
+        std::fill(blobStats, blobStats + 8, 0.0);
         rounds = 0;
         lastPairs = 0;
         // stacks the batched providers could not serve (bellows veto): one at a time through the drop-in path
@@ -817,6 +856,8 @@ public:
             bellowsStats[2] += G.matchLaunches;
             bellowsStats[3] += G.residualImages;
             bellowsStats[4] += G.vetoMs;
+            for (int k = 0; k < 8; ++k)
+                blobStats[k] += G.blobs.stats[k];
             rounds = std::max(rounds, G.rounds);
             lastPairs += G.lastPairs;
         }
@@ -912,6 +953,7 @@ private:
         G.rounds = 0;
         G.vetoed = G.matchJobs = G.matchLaunches = G.residualImages = 0;
         G.vetoMs = 0;
+        std::fill(G.blobs.stats, G.blobs.stats + 8, 0.0);
         const int ns = G.s1 - G.s0;
         double t0 = nowMs();
         // ---- stage 1 (already queued by run()) -----------------------------------------------------
@@ -1139,6 +1181,7 @@ private:
             g.tozero = A->loc_thres;
             g.slot = -1;
             g.thr = 0;
+            g.minBox = -1; // genesis: largestBoxArea / allInBellowsMask need the small contours too
             st_.data.planned.push_back(g);
             const int last = (t < 29) ? NumFramesBubbleTrack : (39 - t);
             for (int k = 1; k <= last; ++k) {
@@ -1151,6 +1194,7 @@ private:
                 p.tozero = 3;
                 p.slot = -1;
                 p.thr = 0;
+                p.minBox = kTrackMinBoxArea;
                 st_.data.planned.push_back(p);
             }
             st_.localize = true;
@@ -1192,12 +1236,20 @@ private:
         }
         const int nimg = nd + np;
         double ta = nowMs();
+        // blobs knob: the device also computes the Otsu thresholds and labels each image's foreground (K4b), and only the
+        // pixels of the components the localizer can use come back (abub_blobs.hip); the knob is read once per batch
+        const bool useBlobs = blobs != 0;
+        Group::Blobs &B = G.blobs;
+        if (useBlobs)
+            initBlobs(G);
         std::vector<PlannedImage *> bySlot((size_t)nimg);
         for (int s : loc) {
             stacks[s].data.roundHists = G.h_hist3;
             for (PlannedImage &p : stacks[s].data.planned) {
                 bySlot[p.slot] = &p;
                 G.h_thr[p.slot] = p.tozero; // candidate cut = TOZERO threshold, known before the launch
+                if (useBlobs)
+                    B.h_minbox[p.slot] = p.minBox;
             }
         }
         uint32_t cnt = 0;
@@ -1231,12 +1283,35 @@ private:
             check(abub_pairs_group_hist_dev(G.d_pairs, G.d_count, G.pairCap, nimg, G.d_gscratch, G.d_goff, G.d_gidx, G.d_gval,
                                             G.d_hist3, G.d_thr, stream),
                   "stage3 group");
+            if (useBlobs) {
+                HIPOK(hipMemcpyAsync(B.d_minbox, B.h_minbox, (size_t)nimg * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+                HIPOK(hipEventRecord(B.ev[0], stream));
+                check(abub_binarize_thr_dev(G.d_hist3, G.d_thr, nimg, W, H, B.d_otsu, stream), "stage3 Otsu");
+                HIPOK(hipEventRecord(B.ev[1], stream));
+                check(abub_label_blobs_dev(G.d_goff, G.d_gidx, G.d_gval, G.pairCap, nimg, W, H, B.d_otsu, B.d_minbox, B.d_koff,
+                                           B.d_kidx, B.cap, B.d_ncomp, B.d_nkc, B.d_coff, nullptr, 0, B.d_stats, B.d_scratch,
+                                           B.scratchBytes, stream),
+                      "stage3 K4b");
+                HIPOK(hipEventRecord(B.ev[2], stream));
+            }
             HIPOK(hipEventRecord(G.kernelsDone, stream));
             HIPOK(hipStreamWaitEvent(back, G.kernelsDone, 0));
             HIPOK(hipMemcpyAsync(G.h_hist3, G.d_hist3, (size_t)nimg * 1024, hipMemcpyDeviceToHost, back));
             HIPOK(hipMemcpyAsync(G.h_count, G.d_count, sizeof(uint32_t), hipMemcpyDeviceToHost, back));
             HIPOK(hipMemcpyAsync(G.h_goff, G.d_goff, (size_t)(nimg + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, back));
+            if (useBlobs) {
+                HIPOK(hipMemcpyAsync(B.h_otsu, B.d_otsu, (size_t)nimg * sizeof(int32_t), hipMemcpyDeviceToHost, back));
+                HIPOK(hipMemcpyAsync(B.h_koff, B.d_koff, (size_t)(nimg + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, back));
+                HIPOK(hipMemcpyAsync(B.h_stats, B.d_stats, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, back));
+            }
             HIPOK(hipStreamSynchronize(back));
+            if (useBlobs) {
+                float m0 = 0, m1 = 0;
+                HIPOK(hipEventElapsedTime(&m0, B.ev[0], B.ev[1]));
+                HIPOK(hipEventElapsedTime(&m1, B.ev[1], B.ev[2]));
+                B.stats[6] += m0;
+                B.stats[7] += m1;
+            }
             G.tms[5] += nowMs() - ta; // launches + kernels + hist/count D2H
             ta = nowMs();
             cnt = *G.h_count;
@@ -1249,7 +1324,17 @@ private:
                 throw std::runtime_error("RunPipeline: foreground list overflow (dense foreground in too many images)");
             growLists(G, cnt + cnt / 4 + 1024);
         }
-        if (cnt) {
+        const uint32_t nkept = useBlobs ? B.h_koff[nimg] : 0;
+        if (useBlobs) {
+            if (nkept > B.cap)
+                throw std::runtime_error("RunPipeline: kept list larger than the candidate list");
+            if (nkept)
+                HIPOK(hipMemcpyAsync(B.h_kidx, B.d_kidx, (size_t)nkept * 4, hipMemcpyDeviceToHost, back));
+            const double add[6] = {(double)cnt, (double)B.h_stats[1], (double)nkept, (double)B.h_stats[2], (double)B.h_stats[3],
+                                   (double)B.h_stats[0]};
+            for (int k = 0; k < 6; ++k)
+                B.stats[k] += add[k];
+        } else if (cnt) {
             HIPOK(hipMemcpyAsync(G.h_gidx, G.d_gidx, (size_t)cnt * 4, hipMemcpyDeviceToHost, back));
             HIPOK(hipMemcpyAsync(G.h_gval, G.d_gval, (size_t)cnt, hipMemcpyDeviceToHost, back));
         }
@@ -1257,9 +1342,20 @@ private:
         pool->parallelFor(nimg, [&](int k) {
             PlannedImage *p = bySlot[k];
             p->thr = binarizeThresholdFromHist(G.h_hist3 + (size_t)k * 256, P, p->tozero);
-            p->fg = G.h_gidx + G.h_goff[k];
-            p->fgv = G.h_gval + G.h_goff[k];
-            p->nfg = G.h_goff[k + 1] - G.h_goff[k];
+            if (useBlobs) {
+                p->fg = nullptr;
+                p->fgv = nullptr;
+                p->nfg = 0;
+                p->kept = B.h_kidx + B.h_koff[k];
+                p->nkept = B.h_koff[k + 1] - B.h_koff[k];
+                p->otsuMismatch = B.h_otsu[k] != p->thr;
+            } else {
+                p->fg = G.h_gidx + G.h_goff[k];
+                p->fgv = G.h_gval + G.h_goff[k];
+                p->nfg = G.h_goff[k + 1] - G.h_goff[k];
+                p->kept = nullptr;
+                p->nkept = 0;
+            }
         });
         HIPOK(hipStreamSynchronize(back));
         G.tms[6] += nowMs() - ta; // list D2H (+ thresholds)
@@ -1512,6 +1608,7 @@ private:
             p.slot = k;
             p.tozero = V.h_thr[k];
             p.thr = binarizeThresholdFromHist(r.hist, P, p.tozero);
+            p.minBox = -1;
             p.fg = V.h_gidx + V.h_goff[k];
             p.fgv = V.h_gval + V.h_goff[k];
             p.nfg = V.h_goff[k + 1] - V.h_goff[k];
@@ -1544,6 +1641,44 @@ private:
         G.d_gval = dalloc<uint8_t>(cap);
         G.h_gidx = halloc<uint32_t>(cap);
         G.h_gval = halloc<uint8_t>(cap);
+        if (G.blobs.ready)
+            growBlobList(G, cap); // kept pixels are a subset of the candidates: the same capacity suffices
+    }
+
+    void growBlobList(Group &G, uint32_t cap)
+    {
+        Group::Blobs &B = G.blobs;
+        const int n3 = (G.s1 - G.s0) * (NumFramesBubbleTrack + 1);
+        B.scratchBytes = abub_label_blobs_scratch_bytes(n3, W, H, cap, 0);
+        if (B.scratchBytes == 0)
+            throw std::runtime_error("RunPipeline: frame size not supported by the blob labelling");
+        B.d_scratch = (void *)dalloc<uint8_t>(B.scratchBytes);
+        B.d_kidx = dalloc<uint32_t>(cap);
+        B.h_kidx = halloc<uint32_t>(cap);
+        B.cap = cap;
+    }
+
+    void initBlobs(Group &G)
+    {
+        Group::Blobs &B = G.blobs;
+        if (B.ready)
+            return;
+        const size_t n3 = (size_t)(G.s1 - G.s0) * (NumFramesBubbleTrack + 1);
+        B.d_otsu = dalloc<int32_t>(n3);
+        B.h_otsu = halloc<int32_t>(n3);
+        B.d_minbox = dalloc<int32_t>(n3);
+        B.h_minbox = halloc<int32_t>(n3);
+        B.d_koff = dalloc<uint32_t>(n3 + 1);
+        B.h_koff = halloc<uint32_t>(n3 + 1);
+        B.d_ncomp = dalloc<uint32_t>(n3);
+        B.d_nkc = dalloc<uint32_t>(n3);
+        B.d_coff = dalloc<uint32_t>(n3 + 1);
+        B.d_stats = dalloc<uint32_t>(4);
+        B.h_stats = halloc<uint32_t>(4);
+        for (hipEvent_t &e : B.ev)
+            HIPOK(hipEventCreate(&e));
+        growBlobList(G, G.pairCap);
+        B.ready = true;
     }
 
     // AnyCamAnalysis body from LocalizeOMatic on (AutoBubStart3.cpp:94-110)
@@ -1675,6 +1810,37 @@ void abh_pipe_bellows(void *p, double *out)
     abub::RunPipeline *r = (abub::RunPipeline *)p;
     for (int k = 0; k < 5; ++k)
         out[k] = r->bellowsStats[k];
+}
+
+// Run-time knobs of one pipeline object: "blobs" (0 = the host applies the Otsu cut to every candidate pixel, 1 = the
+// device labels the foreground and ships only the pixels of the components the localizer can use; default from
+// ABUB_PIPE_BLOBS).  Names and values are checked before the handle: -1 for an unknown name, a bad value or no handle.
+int abh_pipe_set_option(void *p, const char *name, int value)
+{
+    if (!name || std::string(name) != "blobs") {
+        g_pipeErr = std::string("abh_pipe_set_option: unknown option ") + (name ? name : "(null)");
+        return -1;
+    }
+    if (value != 0 && value != 1) {
+        g_pipeErr = "abh_pipe_set_option: blobs takes 0 or 1";
+        return -1;
+    }
+    if (!p) {
+        g_pipeErr = "abh_pipe_set_option: no pipeline";
+        return -1;
+    }
+    ((abub::RunPipeline *)p)->blobs = value;
+    return 0;
+}
+
+// out[0..7] of the last run with the blobs knob on (zeros otherwise), summed over stack groups and rounds: candidate
+// pairs, foreground pixels after the Otsu cut, kept pixels (shipped to the host), components, kept components, slots
+// labelled on the global-memory path, ms of the Otsu launches, ms of the K4b launches
+void abh_pipe_blob_stats(void *p, double *out)
+{
+    abub::RunPipeline *r = (abub::RunPipeline *)p;
+    for (int k = 0; k < 8; ++k)
+        out[k] = r->blobStats[k];
 }
 
 int abh_pipe_timing(void *p, double *out)

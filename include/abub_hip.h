@@ -216,6 +216,36 @@ int abub_pairs_group_hist_dev(const uint32_t *pairs, const uint32_t *count, uint
 int abub_fg_compact_pairs_dev(const uint8_t *img, int nimg, int W, int H, const int32_t *thr,
                               uint32_t *pairs, uint32_t cap, uint32_t *count, void *stream);
 
+/* Otsu threshold per slot on the device, bit for bit host/hostlogic.cpp binarizeThresholdFromHist (the TOZERO + BINARY|OTSU
+ * cut of L3Localizer.cpp:252-254, 786-787): thr[s] = max(tozero[s], Otsu of hist[s] after TOZERO at tozero[s]) over
+ * W*H pixels.  hist: [nslots][256] u32, tozero / thr: [nslots] int32 (device). */
+int abub_binarize_thr_dev(const uint32_t *hist, const int32_t *tozero, int nslots, int W, int H, int32_t *thr, void *stream);
+
+/* One 8-connected component of a slot's foreground: first (smallest) raster index, inclusive bbox, pixel count. */
+typedef struct abub_blob {
+    uint32_t first;
+    int32_t x0, y0, x1, y1;
+    uint32_t npix;
+} abub_blob;
+
+/* K4b: which candidate pixels belong to a blob that can matter, for the contour tracing of L3Localizer.cpp:254-256 and
+ * :787-836 (cv::findContours on the thresholded image; tracking drops contours with box area <= 10, :800-805).
+ * Input: a grouped candidate list (abub_pairs_group_dev / _hist_dev: offsets [nslots+1], idx / val [in_cap]; entries at
+ * or past in_cap are never read), per slot thr (foreground = val > thr[s]) and min_box_area (a component is kept iff
+ * bbox_w * bbox_h > min_box_area; -1 keeps everything).  Output, per slot s:
+ *   kept_idx[kept_off[s] .. kept_off[s+1]) = the raster indices of every pixel of every kept component, increasing;
+ *   ncomp[s] components, nkept_comp[s] of them kept; comp[comp_off[s] .. comp_off[s+1]) their descriptors in order of
+ *   first raster index (comp may be NULL: no descriptors; then scratch sized with with_comp = 0).
+ * Offsets are true counts; nothing is written at or past kept_idx[cap] / comp[comp_cap].  Exact and deterministic.
+ * stats[4] (device, overwritten): slots labelled on the global-memory path, foreground pixels, components, kept components.
+ * scratch: abub_label_blobs_scratch_bytes(nslots, W, H, in_cap, comp != NULL) bytes, 256-byte aligned. */
+int abub_label_blobs_dev(const uint32_t *offsets, const uint32_t *idx, const uint8_t *val, uint32_t in_cap, int nslots, int W,
+                         int H, const int32_t *thr, const int32_t *min_box_area, uint32_t *kept_off, uint32_t *kept_idx,
+                         uint32_t cap, uint32_t *ncomp, uint32_t *nkept_comp, uint32_t *comp_off, abub_blob *comp,
+                         uint32_t comp_cap, uint32_t *stats, void *scratch, size_t scratch_bytes, void *stream);
+/* 0 for impossible shapes */
+size_t abub_label_blobs_scratch_bytes(int nslots, int W, int H, uint32_t in_cap, int with_comp);
+
 /* Raw terms of cv::matchTemplate(CV_TM_CCORR_NORMED) for the bellows veto (L3Localizer::TrackAFeature,
  * L3Localizer.cpp:499-500): for each of the (W-tw+1) x (H-th+1) placements the exact integer sums
  * num = sum(T*I) and wsum2 = sum(I*I) over the window.  Normalisation is host work (double). */
