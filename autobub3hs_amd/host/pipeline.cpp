@@ -34,6 +34,7 @@
 #include "common/CommonParameters.h"
 #include "PICOFormatWriter/PICOFormatWriterV4.hpp"
 #include "devctx.hpp"
+#include "holders.hpp"
 #include "hostlogic.hpp"
 #include "pipeline.hpp"
 
@@ -364,71 +365,147 @@ private:
 
 } // namespace
 
+// The candidate pixels of a batch of images (stage 3, or the veto's residuals): (raster index, value) pairs as the
+// compaction kernels write them, grouped by image on the device, and the host mirrors the localizer reads
+struct CandidateList {
+    uint32_t cap = 0;                   // pairs the lists hold (0 while they are being grown)
+    DeviceArray<uint32_t> pairs;        // [2 cap]
+    DeviceArray<uint32_t> gscratch;     // [2 nimg]
+    Mirror<uint32_t> count, goff, gidx; // pairs found (the kernels count past cap); image k's pairs are [goff[k], goff[k + 1])
+    Mirror<uint8_t> gval;
+    // blobs knob (stage 3): the kept pixels are a subset of the candidates, so the kept list and K4b's scratch follow cap
+    int keptImages = 0, keptW = 0, keptH = 0; // 0 images: no kept list
+    Mirror<uint32_t> kidx;
+    DeviceArray<uint8_t> keptScratch;
+    size_t keptScratchBytes = 0;
+
+    // room for the per-image arrays of `nimg` images
+    void allocate(size_t nimg)
+    {
+        count.allocate(1);
+        gscratch.allocate(2 * nimg);
+        goff.allocate(nimg + 1);
+    }
+    // the old storage is freed: only once the streams that used it have been synchronised
+    void grow(uint32_t c)
+    {
+        cap = 0;
+        pairs.allocate(2 * (size_t)c);
+        gidx.allocate(c);
+        gval.allocate(c);
+        if (keptImages)
+            growKept(c);
+        cap = c;
+    }
+    // from now on the list also has room for the kept pixels of `nimg` images of W x H
+    void keep(int nimg, int W, int H)
+    {
+        keptImages = nimg;
+        keptW = W;
+        keptH = H;
+        growKept(cap);
+    }
+    void growKept(uint32_t c)
+    {
+        keptScratchBytes = abub_label_blobs_scratch_bytes(keptImages, keptW, keptH, c, 0);
+        if (keptScratchBytes == 0)
+            throw std::runtime_error("RunPipeline: frame size not supported by the blob labelling");
+        keptScratch.allocate(keptScratchBytes);
+        kidx.allocate(c);
+    }
+    // the pairs grouped by image (per-image counts from the histograms and TOZERO cuts of the same launches)
+    void group(int nimg, const uint32_t *d_hist, const int32_t *d_thr, hipStream_t s, const char *what)
+    {
+        check(abub_pairs_group_hist_dev(pairs, count.d, cap, nimg, gscratch, goff.d, gidx.d, gval.d, d_hist, d_thr, s), what);
+    }
+    void offsetsToHost(int nimg, hipStream_t s)
+    {
+        count.toHost(1, s);
+        goff.toHost((size_t)nimg + 1, s);
+    }
+    // once the offsets are on the host: true if every pair fitted; else the list grows to what the kernels counted and the
+    // caller redoes its launches (once)
+    bool fits(int attempt, const char *what)
+    {
+        const uint32_t n = *count.h;
+        if (n <= cap)
+            return true;
+        if (attempt > 0 || n > (1u << 30))
+            throw std::runtime_error(std::string("RunPipeline: ") + what);
+        grow(n + n / 4 + 1024);
+        return false;
+    }
+    void pairsToHost(hipStream_t s)
+    {
+        if (const uint32_t n = *count.h) {
+            gidx.toHost(n, s);
+            gval.toHost(n, s);
+        }
+    }
+    // image k's candidates (pointers into the host mirrors: valid until the next grow)
+    void bind(PlannedImage &p, int k) const
+    {
+        p.fg = gidx.h + goff.h[k];
+        p.fgv = gval.h + goff.h[k];
+        p.nfg = goff.h[k + 1] - goff.h[k];
+    }
+};
+
 // One slice of the run with its own stream and scratch: groups run concurrently on host threads, so the
 // GPU work of one group overlaps the host state machines of another (no group waits on another).
 struct Group {
     int s0 = 0, s1 = 0; // stacks [s0, s1)
-    hipStream_t stream = nullptr;
-    hipEvent_t stage1Done = nullptr, kernelsDone = nullptr;
-    // trigger search, per frame block: job lists and histograms (capacity: every stack of the group once)
-    std::vector<abub_job *> d_jobsB, h_jobsB;
-    std::vector<uint32_t *> d_histB, h_histB;
-    std::vector<int> usedB; // stacks already served per block in this run (each stack fetches a block at most once)
-    // deferred pieces, per block: handed-over row ranges of every launch of the block, per-launch counters, per-job
-    // "incomplete" / "wanted" flags
+    Event stage1Done, kernelsDone, blockDone;
+    // trigger search, per frame block k = frames [blocks[k], blocks[k + 1]): job lists and histograms (capacity: every
+    // stack of the group once), and the deferred pieces: handed-over row ranges of every launch of the block, per-launch
+    // counters, per-job "incomplete" / "wanted" flags
     struct Fetch {
         int first = 0, n = 0;   // stacks [first, first + n) of the block's buffers
         size_t pieceOff = 0;    // its range of the block's piece list
         bool deferred = false;
     };
-    std::vector<std::vector<Fetch>> fetches;
-    std::vector<void *> d_piecesB;
-    std::vector<uint32_t *> d_pcountB;
-    std::vector<uint8_t *> d_incB, h_incB, d_wantB, h_wantB;
-    std::vector<size_t> pieceCapB, pieceUsedB;
-    hipEvent_t blockDone = nullptr;
-    abub_job *d_jobs3 = nullptr;
-    uint32_t *d_hist3 = nullptr;
-    uint8_t *d_img = nullptr;
-    int32_t *d_thr = nullptr;
-    uint32_t *d_pairs = nullptr, *d_count = nullptr, *d_gscratch = nullptr, *d_goff = nullptr, *d_gidx = nullptr;
-    uint8_t *d_gval = nullptr;
-    uint32_t *h_hist3 = nullptr, *h_count = nullptr, *h_goff = nullptr, *h_gidx = nullptr;
-    uint8_t *h_gval = nullptr;
-    abub_job *h_jobs3 = nullptr;
-    int32_t *h_thr = nullptr;
-    uint32_t pairCap = 0;
-    // blobs knob: device Otsu + K4b behind the grouping (allocated on first use; kept list and scratch grow with pairCap)
+    struct Block {
+        Mirror<abub_job> jobs;
+        Mirror<uint32_t> hist;
+        DeviceArray<uint64_t> pieces;
+        DeviceArray<uint32_t> pcount; // [64]: one per launch
+        Mirror<uint8_t> inc, want;
+        size_t pieceCap = 0, pieceUsed = 0;
+        int slots = 0; // stacks the buffers hold: every stack of the group once
+        int used = 0;  // stacks already served in this run (each stack fetches a block at most once)
+        std::vector<Fetch> fetches;
+    };
+    std::vector<Block> blocks;
+    Mirror<abub_job> jobs3;
+    Mirror<uint32_t> hist3;
+    DeviceArray<uint8_t> img;
+    Mirror<int32_t> thr;
+    CandidateList list;
+    // blobs knob: device Otsu + K4b behind the grouping (allocated on first use; the kept list is in `list`)
     struct Blobs {
         bool ready = false;
-        int32_t *d_otsu = nullptr, *h_otsu = nullptr, *d_minbox = nullptr, *h_minbox = nullptr;
-        uint32_t *d_koff = nullptr, *h_koff = nullptr, *d_kidx = nullptr, *h_kidx = nullptr;
-        uint32_t *d_ncomp = nullptr, *d_nkc = nullptr, *d_coff = nullptr, *d_stats = nullptr, *h_stats = nullptr;
-        void *d_scratch = nullptr;
-        size_t scratchBytes = 0;
-        uint32_t cap = 0; // of d_kidx / h_kidx and the scratch's staging
-        hipEvent_t ev[3] = {nullptr, nullptr, nullptr}; // before Otsu, between, after K4b
+        Mirror<int32_t> otsu, minbox;
+        Mirror<uint32_t> koff, kstats; // kstats: K4b's counters
+        DeviceArray<uint32_t> ncomp, nkc, coff;
+        Event ev[3]; // before Otsu, between, after K4b
         double stats[8] = {0}; // last run: see abh_pipe_blob_stats
     } blobs;
     // bellows veto round (vetoRound): its own buffers, allocated on first use, grown on demand
     struct Veto {
         int capJobs = 0;           // match jobs the buffers hold
         size_t scratchBytes = 0;   // abub_match_best_batch_dev scratch
-        uint32_t *d_fidx = nullptr, *h_fidx = nullptr;
-        float *d_xy = nullptr, *h_xy = nullptr;
-        void *d_scratch = nullptr;
+        Mirror<uint32_t> fidx;
+        Mirror<float> xy;
+        DeviceArray<uint8_t> scratch;
         int capImg = 0;            // residual images
-        uint8_t *d_rend = nullptr, *h_rend = nullptr; // [2n][P]: trigger copy, pre-trigger copy
-        uint8_t *d_syn = nullptr, *d_img = nullptr;   // [n][P]: ROI ProcessFrame of the renderings, the residual
-        uint32_t *d_rhist = nullptr;                  // [n][256] (ROI ProcessFrame histograms, unused)
-        uint32_t *d_hist = nullptr, *h_hist = nullptr;
-        abub_job *d_jobs = nullptr, *h_jobs = nullptr;
-        int32_t *d_thr = nullptr, *h_thr = nullptr;
-        uint32_t pairCap = 0;
-        uint32_t *d_pairs = nullptr, *d_count = nullptr, *h_count = nullptr, *d_gscratch = nullptr, *d_goff = nullptr,
-                 *h_goff = nullptr, *d_gidx = nullptr, *h_gidx = nullptr;
-        uint8_t *d_gval = nullptr, *h_gval = nullptr;
-        std::vector<std::pair<cv::Mat, uint8_t *>> templates; // device copies of the bellows templates (deviceTemplate)
+        Mirror<uint8_t> rend;      // [2n][P]: trigger copy, pre-trigger copy
+        DeviceArray<uint8_t> syn, img; // [n][P]: ROI ProcessFrame of the renderings, the residual
+        DeviceArray<uint32_t> rhist;   // [n][256] (ROI ProcessFrame histograms, unused)
+        Mirror<uint32_t> hist;
+        Mirror<abub_job> jobs;
+        Mirror<int32_t> thr;
+        CandidateList list;
+        std::vector<std::pair<cv::Mat, DeviceArray<uint8_t>>> templates; // device copies of the bellows templates (deviceTemplate)
     } veto;
     int vetoed = 0, matchJobs = 0, matchLaunches = 0, residualImages = 0;
     double vetoMs = 0;
@@ -437,6 +514,8 @@ struct Group {
     int rounds = 0;
     uint32_t lastPairs = 0;
     std::string error;
+    // declared last, so destroyed first: the holder finishes the stream's work before the buffers above are freed
+    Stream stream;
 };
 
 class RunPipeline {
@@ -445,6 +524,9 @@ public:
     size_t P;
     std::vector<int> tss;
     std::string maskDir;
+    // Declaration order: the streams (stage1Stream, copyStream, each group's last member) come after the buffers their
+    // work uses, so they are destroyed first, and a Stream finishes its work before it goes (see ~RunPipeline)
+    DeviceArray<uint8_t> ownFrames;     // frame slab owned by the pipeline (streamed mode only)
     std::vector<Group> groups;
     std::unique_ptr<WorkerPool> pool;
     std::vector<int> blocks;            // frame blocks of the trigger search: block k = frames [blocks[k], blocks[k + 1])
@@ -455,14 +537,14 @@ public:
     bool bellowsDropIn = false;         // ABUB_PIPE_BELLOWS=dropin: every bellows veto takes the one-at-a-time path (A/B)
     double bellowsStats[5] = {0};       // last run: vetoed stacks, match jobs, match launches, residual images, veto ms
     double blobStats[8] = {0};          // last run, blobs knob: see abh_pipe_blob_stats
-    hipStream_t stage1Stream = nullptr; // all trigger-search launches, in group order (see run())
+    Stream stage1Stream;                // all trigger-search launches, in group order (see run())
     int chainStride = 0;                // FindTriggerFrame's frame offset when every camera shares it, else 0
     bool ordered = true;                // localisation kernels queue on stage1Stream too (see batchImages())
+    int pairCap = 0;                    // ABUB_PIPE_PAIRCAP (0: unset)
     int blobs = 0;                      // 1: stage 3 labels blobs on the GPU and ships only the kept pixels (set_option "blobs")
-    std::vector<void *> devAllocs, hostAllocs;
-    std::mutex allocMu, launchMu;
+    std::mutex launchMu;
     std::vector<StackState> stacks;
-    std::vector<Trainer *> trainers;
+    std::vector<std::unique_ptr<Trainer>> trainers;
     MemParser parser;
     // optional (runs ingested from a Parser): real ids / names / decode flags per stack; a stack may be shorter than F
     std::vector<StackMeta> meta;
@@ -522,51 +604,50 @@ public:
         return j;
     }
     // after the launch of block k has been waited for: the stack at position q of fetch `f` gets its histograms (and flags)
-    void bindBlock(Group &G, StackState &st_, int k, int f, int q)
+    void bindBlock(Group::Block &B, int k, StackState &st_, int f, int q)
     {
-        const Group::Fetch &fe = G.fetches[k][f];
+        const Group::Fetch &fe = B.fetches[f];
         const size_t blen = (size_t)(blocks[k + 1] - blocks[k]), slot = (size_t)fe.first + q;
-        st_.data.bh[k] = G.h_histB[k] + slot * blen * 256;
-        st_.data.inc[k] = fe.deferred ? G.h_incB[k] + slot * blen : nullptr;
+        st_.data.bh[k] = B.hist.h + slot * blen * 256;
+        st_.data.inc[k] = fe.deferred ? B.inc.h + slot * blen : nullptr;
         st_.data.fetchOf[k] = f;
         st_.data.slotOf[k] = q;
     }
     // K2 over block k for the listed stacks (all of them on the same block): jobs -> device, launch, histograms -> host.
     // Returns the first slot (in stacks) of the block's histogram buffer the results go to.
-    int launchBlock(Group &G, int k, const std::vector<int> &list, const uint8_t *d_frames, const uint8_t *d_sigma6,
+    int launchBlock(Group::Block &B, int k, const std::vector<int> &list, const uint8_t *d_frames, const uint8_t *d_sigma6,
                     hipStream_t stream)
     {
         const int a = blocks[k], blen = blocks[k + 1] - blocks[k];
-        const int first = G.usedB[k], n = (int)list.size();
+        const int first = B.used, n = (int)list.size();
         if (blen <= 0 || n == 0)
             return first;
-        if (first + n > G.s1 - G.s0)
+        if (first + n > B.slots)
             throw std::runtime_error("RunPipeline: a frame block was requested twice for one stack");
-        abub_job *hj = G.h_jobsB[k] + (size_t)first * blen;
+        const size_t j0 = (size_t)first * blen;
         for (int q = 0; q < n; ++q)
             for (int i = 0; i < blen; ++i)
-                hj[(size_t)q * blen + i] = triggerJob(list[q], a + i, (uint32_t)((size_t)q * blen + i));
-        abub_job *dj = G.d_jobsB[k] + (size_t)first * blen;
-        uint32_t *dh = G.d_histB[k] + (size_t)first * blen * 256, *hh = G.h_histB[k] + (size_t)first * blen * 256;
+                B.jobs.h[j0 + (size_t)q * blen + i] = triggerJob(list[q], a + i, (uint32_t)((size_t)q * blen + i));
+        abub_job *dj = B.jobs.d + j0;
+        uint32_t *dh = B.hist.d + j0 * 256;
         const int nj = n * blen;
-        HIPOK(hipMemcpyAsync(dj, hj, (size_t)nj * sizeof(abub_job), hipMemcpyHostToDevice, stream));
+        B.jobs.toDevice(nj, stream, j0);
         Group::Fetch fe;
         fe.first = first;
         fe.n = n;
         // deferral is decided per launch: the K2 options (abub_k2_set_option "bound") may change after construction
         const bool defer = deferPieces && abub_k2_deferred_ok(W, H);
         const size_t pcap = defer ? abub_k2_pieces_cap(nj, W, H) : 0;
-        if (defer && G.fetches[k].size() < 64 && G.pieceUsedB[k] + pcap <= G.pieceCapB[k]) {
+        if (defer && B.fetches.size() < 64 && B.pieceUsed + pcap <= B.pieceCap) {
             // the scan alone: dense frames' rows go to this launch's range of the block's piece list, their jobs are flagged
             fe.deferred = true;
-            fe.pieceOff = G.pieceUsedB[k];
-            G.pieceUsedB[k] += pcap;
-            uint8_t *dinc = G.d_incB[k] + (size_t)first * blen, *hinc = G.h_incB[k] + (size_t)first * blen;
+            fe.pieceOff = B.pieceUsed;
+            B.pieceUsed += pcap;
             check(abub_diff_hist_chained_deferred_dev(d_frames, d_sigma6, dj, nj, W, H, dh, blen, chainStride,
-                                                      (uint64_t *)G.d_piecesB[k] + fe.pieceOff, (uint32_t)pcap,
-                                                      G.d_pcountB[k] + G.fetches[k].size(), dinc, stream),
+                                                      B.pieces + fe.pieceOff, (uint32_t)pcap, B.pcount + B.fetches.size(),
+                                                      B.inc.d + j0, stream),
                   "trigger search K2 (deferred pieces)");
-            HIPOK(hipMemcpyAsync(hinc, dinc, (size_t)nj, hipMemcpyDeviceToHost, stream));
+            B.inc.toHost(nj, stream, j0);
         } else {
             // all cameras on the same frame offset: per stack the jobs are a chain (job i refs the cur frame of job i - off)
             // and the scan loads every frame row once for both of its jobs
@@ -574,9 +655,9 @@ public:
                                   : abub_diff_hist_dev(d_frames, d_sigma6, dj, nj, W, H, dh, nullptr, 0, stream),
                   "trigger search K2");
         }
-        HIPOK(hipMemcpyAsync(hh, dh, (size_t)nj * 1024, hipMemcpyDeviceToHost, stream));
-        G.fetches[k].push_back(fe);
-        G.usedB[k] = first + n;
+        B.hist.toHost((size_t)nj * 256, stream, j0 * 256);
+        B.fetches.push_back(fe);
+        B.used = first + n;
         jobsLaunched += nj;
         return first;
     }
@@ -584,195 +665,121 @@ public:
     int rounds = 0;
     uint32_t lastPairs = 0;
 
-    template <typename T>
-    T *dalloc(size_t n)
-    {
-        void *p = nullptr;
-        HIPOK(hipMalloc(&p, n * sizeof(T) + 256));
-        std::lock_guard<std::mutex> lock(allocMu); // group threads may grow their lists concurrently
-        devAllocs.push_back(p);
-        return (T *)p;
-    }
-    template <typename T>
-    T *halloc(size_t n)
-    {
-        void *p = nullptr;
-        HIPOK(hipHostMalloc(&p, n * sizeof(T) + 256, hipHostMallocDefault));
-        std::lock_guard<std::mutex> lock(allocMu);
-        hostAllocs.push_back(p);
-        return (T *)p;
-    }
-
     RunPipeline(int device_, int W_, int H_, int F_, int E_, int C_, const int *tss_, int nthreads_, const char *maskdir)
         : device(device_), W(W_), H(H_), F(F_), E(E_), C(C_), S(E_ * C_), nthreads(nthreads_), P((size_t)W_ * H_),
           tss(tss_, tss_ + C_), maskDir(maskdir ? maskdir : "")
     {
-        try {
-            if (W <= 0 || H <= 0 || F <= 0 || E <= 0 || C <= 0)
-                throw std::runtime_error("RunPipeline: bad geometry");
-            HIPOK(hipSetDevice(device));
-            const char *eg = getenv("ABUB_PIPE_GROUPS");
-            ngroups = eg ? atoi(eg) : 1; // >1 overlaps host stages of one group with the GPU work of the next
-            const char *ebw = getenv("ABUB_PIPE_BELLOWS");
-            bellowsDropIn = ebw && std::string(ebw) == "dropin";
-            const char *eo = getenv("ABUB_PIPE_ORDERED");
-            ordered = eo ? atoi(eo) != 0 : true;
-            const char *eb = getenv("ABUB_PIPE_BLOBS");
-            blobs = eb ? atoi(eb) != 0 : 0;
-            int prLow = 0, prHigh = 0; // (numerically lower = higher priority)
-            HIPOK(hipDeviceGetStreamPriorityRange(&prLow, &prHigh));
-            HIPOK(hipStreamCreateWithPriority(&stage1Stream, hipStreamNonBlocking, prLow));
-            if (ngroups < 1)
-                ngroups = 1;
-            if (ngroups > S)
-                ngroups = S;
-            const int K = NumFramesBubbleTrack + 1;
-            chainStride = tss[0] < 6 ? 1 : 2;
-            for (int c = 1; c < C; ++c)
-                if ((tss[c] < 6 ? 1 : 2) != chainStride)
-                    chainStride = 0;
-            groups.resize(ngroups);
-            pool.reset(new WorkerPool(std::max(0, nthreads - ngroups))); // the group driver threads take part too
-            // Frame blocks of the trigger search.  The reference walks the frames in order and stops at the trigger
-            // (AnalyzerUnit.cpp:191, break at :307); it never differences the frames behind it unless the localizer finds no
-            // bubble and the search goes on (AutoBubStart3.cpp:87-110).  So the histograms are produced block by block: block 0
-            // for every stack up front, later blocks only for the stacks whose search reaches them.  ABUB_PIPE_LAZY=0: one
-            // block (every frame of every stack up front, what round 2 did).
-            {
-                const char *el = getenv("ABUB_PIPE_LAZY");
-                const bool lazy = el ? atoi(el) != 0 : true;
-                const char *e0 = getenv("ABUB_PIPE_BLOCK0"), *e1 = getenv("ABUB_PIPE_BLOCK");
-                // first block: up to the frame the cameras' own trigger puts the bubble at (the middle of the stack) plus the
-                // two look-ahead frames and a margin; then blocks of about a fifth of the stack
-                int first = e0 && atoi(e0) > 0 ? atoi(e0) : F / 2 + 4, step = e1 && atoi(e1) > 0 ? atoi(e1) : std::max(4, F / 5);
-                blocks.clear();
-                blocks.push_back(1);
-                if (lazy && F > 8)
-                    for (int b = std::min(first + 1, F); b < F && (int)blocks.size() < BatchEventData::MAXB; b += step)
-                        blocks.push_back(b);
-                blocks.push_back(std::max(F, 1)); // block k = frames [blocks[k], blocks[k + 1])
-                // Deferred pieces: inside a block the bound scan still covers every frame, but the row machine runs only on the
-                // dense frames a search actually reaches (ABUB_PIPE_DEFER=0: at once, for every frame of the block).
-                const char *ed = getenv("ABUB_PIPE_DEFER");
-                deferPieces = (ed ? atoi(ed) != 0 : true) && chainStride > 0 && abub_fast_path(W) != 0;
-            }
-            const int nB = (int)blocks.size() - 1;
-            for (int g = 0; g < ngroups; ++g) {
-                Group &G = groups[g];
-                G.s0 = (int)((long long)S * g / ngroups);
-                G.s1 = (int)((long long)S * (g + 1) / ngroups);
-                const size_t ns = (size_t)(G.s1 - G.s0), n3 = ns * K;
-                G.nthreads = std::max(1, nthreads / ngroups);
-                const char *ec = getenv("ABUB_PIPE_PAIRCAP"); // initial candidate-list capacity (grows on demand)
-                G.pairCap = ec && atoi(ec) > 0 ? (uint32_t)atoi(ec) : (8u << 20) / ngroups;
-                // the short localisation launches of a finished group must not queue behind the next group's
-                // chip-filling trigger search
-                HIPOK(hipStreamCreateWithPriority(&G.stream, hipStreamNonBlocking, prHigh));
-                HIPOK(hipEventCreateWithFlags(&G.stage1Done, hipEventDisableTiming));
-                HIPOK(hipEventCreateWithFlags(&G.kernelsDone, hipEventDisableTiming));
-                HIPOK(hipEventCreateWithFlags(&G.blockDone, hipEventDisableTiming));
-                G.usedB.assign(nB, 0);
-                for (int k = 0; k < nB; ++k) {
-                    const size_t nj = ns * (size_t)std::max(blocks[k + 1] - blocks[k], 1);
-                    G.d_jobsB.push_back(dalloc<abub_job>(nj));
-                    G.h_jobsB.push_back(halloc<abub_job>(nj));
-                    G.d_histB.push_back(dalloc<uint32_t>(nj * 256));
-                    G.h_histB.push_back(halloc<uint32_t>(nj * 256));
-                    // deferred pieces: at most H / 16 + 8 row ranges per job (chunks are at least 16 rows), 64 launches per block
-                    const size_t pc = deferPieces ? nj * (size_t)(H / 16 + 8) : 1;
-                    G.pieceCapB.push_back(pc);
-                    G.d_piecesB.push_back((void *)dalloc<uint64_t>(pc));
-                    G.d_pcountB.push_back(dalloc<uint32_t>(64));
-                    G.d_incB.push_back(dalloc<uint8_t>(nj));
-                    G.h_incB.push_back(halloc<uint8_t>(nj));
-                    G.d_wantB.push_back(dalloc<uint8_t>(nj));
-                    G.h_wantB.push_back(halloc<uint8_t>(nj));
-                }
-                G.fetches.assign(nB, std::vector<Group::Fetch>());
-                G.pieceUsedB.assign(nB, 0);
-                G.d_jobs3 = dalloc<abub_job>(n3);
-                G.d_hist3 = dalloc<uint32_t>(n3 * 256);
-                G.d_img = dalloc<uint8_t>(abub_fast_path(W) ? 256 : n3 * P); // only the unfused fallback stores images
-                G.d_thr = dalloc<int32_t>(n3);
-                G.d_pairs = dalloc<uint32_t>((size_t)G.pairCap * 2);
-                G.d_count = dalloc<uint32_t>(1);
-                G.d_gscratch = dalloc<uint32_t>(2 * n3);
-                G.d_goff = dalloc<uint32_t>(n3 + 1);
-                G.d_gidx = dalloc<uint32_t>(G.pairCap);
-                G.d_gval = dalloc<uint8_t>(G.pairCap);
-                G.h_hist3 = halloc<uint32_t>(n3 * 256);
-                G.h_count = halloc<uint32_t>(1);
-                G.h_goff = halloc<uint32_t>(n3 + 1);
-                G.h_gidx = halloc<uint32_t>(G.pairCap);
-                G.h_gval = halloc<uint8_t>(G.pairCap);
-                G.h_jobs3 = halloc<abub_job>(n3);
-                G.h_thr = halloc<int32_t>(n3);
-            }
-            // frame names only: the images live in HBM
-            for (int c = 0; c < C; ++c) {
-                Trainer *t = new Trainer(c, {}, "", "cam%d_image%u.png", "", parser.clone(), false);
-                t->TrainingSetSize = tss[c];
-                t->ModelId = 0;
-                trainers.push_back(t);
-            }
-            std::vector<cv::Mat> none((size_t)F);
-            for (int e = 0; e < E; ++e)
-                for (int c = 0; c < C; ++c)
-                    parser.AddFrames(std::to_string(e), c, none, 10000); // 5-digit numbers: lexicographic == numeric
-        } catch (...) { // (e.g. a hipMalloc that fails: give back what was allocated so far)
-            release();
-            throw;
+        if (W <= 0 || H <= 0 || F <= 0 || E <= 0 || C <= 0)
+            throw std::runtime_error("RunPipeline: bad geometry");
+        HIPOK(hipSetDevice(device));
+        const char *eg = getenv("ABUB_PIPE_GROUPS");
+        ngroups = eg ? atoi(eg) : 1; // >1 overlaps host stages of one group with the GPU work of the next
+        const char *ebw = getenv("ABUB_PIPE_BELLOWS");
+        bellowsDropIn = ebw && std::string(ebw) == "dropin";
+        const char *eo = getenv("ABUB_PIPE_ORDERED");
+        ordered = eo ? atoi(eo) != 0 : true;
+        const char *eb = getenv("ABUB_PIPE_BLOBS");
+        blobs = eb ? atoi(eb) != 0 : 0;
+        int prLow = 0, prHigh = 0; // (numerically lower = higher priority)
+        HIPOK(hipDeviceGetStreamPriorityRange(&prLow, &prHigh));
+        stage1Stream.create(prLow);
+        if (ngroups < 1)
+            ngroups = 1;
+        if (ngroups > S)
+            ngroups = S;
+        const int K = NumFramesBubbleTrack + 1;
+        chainStride = tss[0] < 6 ? 1 : 2;
+        for (int c = 1; c < C; ++c)
+            if ((tss[c] < 6 ? 1 : 2) != chainStride)
+                chainStride = 0;
+        groups.resize(ngroups);
+        pool.reset(new WorkerPool(std::max(0, nthreads - ngroups))); // the group driver threads take part too
+        // Frame blocks of the trigger search.  The reference walks the frames in order and stops at the trigger
+        // (AnalyzerUnit.cpp:191, break at :307); it never differences the frames behind it unless the localizer finds no
+        // bubble and the search goes on (AutoBubStart3.cpp:87-110).  So the histograms are produced block by block: block 0
+        // for every stack up front, later blocks only for the stacks whose search reaches them.  ABUB_PIPE_LAZY=0: one
+        // block (every frame of every stack up front, what round 2 did).
+        {
+            const char *el = getenv("ABUB_PIPE_LAZY");
+            const bool lazy = el ? atoi(el) != 0 : true;
+            const char *e0 = getenv("ABUB_PIPE_BLOCK0"), *e1 = getenv("ABUB_PIPE_BLOCK");
+            // first block: up to the frame the cameras' own trigger puts the bubble at (the middle of the stack) plus the
+            // two look-ahead frames and a margin; then blocks of about a fifth of the stack
+            int first = e0 && atoi(e0) > 0 ? atoi(e0) : F / 2 + 4, step = e1 && atoi(e1) > 0 ? atoi(e1) : std::max(4, F / 5);
+            blocks.clear();
+            blocks.push_back(1);
+            if (lazy && F > 8)
+                for (int b = std::min(first + 1, F); b < F && (int)blocks.size() < BatchEventData::MAXB; b += step)
+                    blocks.push_back(b);
+            blocks.push_back(std::max(F, 1)); // block k = frames [blocks[k], blocks[k + 1])
+            // Deferred pieces: inside a block the bound scan still covers every frame, but the row machine runs only on the
+            // dense frames a search actually reaches (ABUB_PIPE_DEFER=0: at once, for every frame of the block).
+            const char *ed = getenv("ABUB_PIPE_DEFER");
+            deferPieces = (ed ? atoi(ed) != 0 : true) && chainStride > 0 && abub_fast_path(W) != 0;
         }
+        const int nB = (int)blocks.size() - 1;
+        // initial capacity of the candidate lists (they grow on demand): ABUB_PIPE_PAIRCAP sets the veto's too
+        const char *ec = getenv("ABUB_PIPE_PAIRCAP");
+        pairCap = ec ? atoi(ec) : 0;
+        for (int g = 0; g < ngroups; ++g) {
+            Group &G = groups[g];
+            G.s0 = (int)((long long)S * g / ngroups);
+            G.s1 = (int)((long long)S * (g + 1) / ngroups);
+            const size_t ns = (size_t)(G.s1 - G.s0), n3 = ns * K;
+            G.nthreads = std::max(1, nthreads / ngroups);
+            // the short localisation launches of a finished group must not queue behind the next group's
+            // chip-filling trigger search
+            G.stream.create(prHigh);
+            G.stage1Done.create(false);
+            G.kernelsDone.create(false);
+            G.blockDone.create(false);
+            G.blocks.resize(nB);
+            for (int k = 0; k < nB; ++k) {
+                Group::Block &B = G.blocks[k];
+                const size_t nj = ns * (size_t)std::max(blocks[k + 1] - blocks[k], 1);
+                B.slots = (int)ns;
+                B.jobs.allocate(nj);
+                B.hist.allocate(nj * 256);
+                // deferred pieces: at most H / 16 + 8 row ranges per job (chunks are at least 16 rows), 64 launches per block
+                B.pieceCap = deferPieces ? nj * (size_t)(H / 16 + 8) : 1;
+                B.pieces.allocate(B.pieceCap);
+                B.pcount.allocate(64);
+                B.inc.allocate(nj);
+                B.want.allocate(nj);
+            }
+            G.jobs3.allocate(n3);
+            G.hist3.allocate(n3 * 256);
+            G.img.allocate(abub_fast_path(W) ? 256 : n3 * P); // only the unfused fallback stores images
+            G.thr.allocate(n3);
+            G.list.allocate(n3);
+            G.list.grow(pairCap > 0 ? (uint32_t)pairCap : (8u << 20) / ngroups);
+        }
+        // frame names only: the images live in HBM
+        for (int c = 0; c < C; ++c) {
+            trainers.emplace_back(new Trainer(c, {}, "", "cam%d_image%u.png", "", parser.clone(), false));
+            trainers.back()->TrainingSetSize = tss[c];
+            trainers.back()->ModelId = 0;
+        }
+        std::vector<cv::Mat> none((size_t)F);
+        for (int e = 0; e < E; ++e)
+            for (int c = 0; c < C; ++c)
+                parser.AddFrames(std::to_string(e), c, none, 10000); // 5-digit numbers: lexicographic == numeric
     }
 
-    ~RunPipeline() { release(); }
-
-    // everything the object owns (also called by the constructor when it fails half-way: a destructor would not run)
-    void release() noexcept
+    // hipSetDevice first, then each stream that owns library scratch gives it back; the members go after the body, the
+    // streams before the buffers their work uses (declaration order)
+    ~RunPipeline()
     {
         (void)hipSetDevice(device);
-        for (Group &G : groups) {
-            if (G.stream) {
-                (void)abub_scratch_release(G.stream);
-                (void)hipStreamDestroy(G.stream);
-            }
-            if (G.stage1Done)
-                (void)hipEventDestroy(G.stage1Done);
-            if (G.kernelsDone)
-                (void)hipEventDestroy(G.kernelsDone);
-            if (G.blockDone)
-                (void)hipEventDestroy(G.blockDone);
-            for (hipEvent_t &e : G.blobs.ev)
-                if (e)
-                    (void)hipEventDestroy(e);
-        }
-        if (stage1Stream) {
-            (void)abub_scratch_release(stage1Stream); // the trigger search's work list lives in library scratch
-            (void)hipStreamDestroy(stage1Stream);
-        }
-        if (copyStream)
-            (void)hipStreamDestroy(copyStream);
-        for (auto &e : copied)
-            (void)hipEventDestroy(e);
-        for (void *p : devAllocs)
-            (void)hipFree(p);
-        for (void *p : hostAllocs)
-            (void)hipHostFree(p);
-        for (Trainer *t : trainers)
-            delete t;
-        groups.clear();
-        copied.clear();
-        devAllocs.clear();
-        hostAllocs.clear();
-        trainers.clear();
-        stage1Stream = copyStream = nullptr;
+        for (Group &G : groups)
+            (void)abub_scratch_release(G.stream.get());
+        (void)abub_scratch_release(stage1Stream.get()); // the trigger search's work list lives in library scratch
     }
 
     // `callerStream`: work already queued there (e.g. the upload of the frames) is waited for first
     const uint8_t *d_sigmaRaw = nullptr; // optional: sigma (not 6*sigma) for stacks that need the drop-in path
-    uint8_t *d_ownFrames = nullptr;      // frame slab owned by the pipeline (streamed mode only)
-    hipStream_t copyStream = nullptr;
-    std::vector<hipEvent_t> copied;
+    Stream copyStream;
+    std::vector<Event> copied;
 
     // Streamed mode (BASELINE configs[4]): the run sits in HOST memory (ideally pinned).  Stack groups are
     // uploaded in order on a copy stream; the trigger search of group g waits only for its own upload, so it
@@ -781,21 +788,20 @@ public:
     void runFromHost(const uint8_t *h_frames, const uint8_t *d_mu, const uint8_t *d_sigma6)
     {
         HIPOK(hipSetDevice(device));
-        if (!d_ownFrames) {
-            d_ownFrames = dalloc<uint8_t>((size_t)S * F * P);
-            HIPOK(hipStreamCreateWithFlags(&copyStream, hipStreamNonBlocking));
+        if (!ownFrames) {
+            ownFrames.allocate((size_t)S * F * P);
             copied.resize(ngroups);
-            for (auto &e : copied)
-                HIPOK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+            for (Event &e : copied)
+                e.create(false);
         }
         for (int g = 0; g < ngroups; ++g) {
             const Group &G = groups[g];
             const size_t off = (size_t)G.s0 * F * P, n = (size_t)(G.s1 - G.s0) * F * P;
-            HIPOK(hipMemcpyAsync(d_ownFrames + off, h_frames + off, n, hipMemcpyHostToDevice, copyStream));
-            HIPOK(hipEventRecord(copied[g], copyStream));
+            HIPOK(hipMemcpyAsync(ownFrames + off, h_frames + off, n, hipMemcpyHostToDevice, copyStream.get()));
+            HIPOK(hipEventRecord(copied[g].get(), copyStream.get()));
         }
         waitCopies = true;
-        run(d_ownFrames, d_mu, d_sigma6, nullptr);
+        run(ownFrames, d_mu, d_sigma6, nullptr);
         waitCopies = false;
     }
     bool waitCopies = false;
@@ -816,17 +822,18 @@ public:
         for (size_t gi = 0; gi < groups.size(); ++gi) {
             Group &G = groups[gi];
             if (waitCopies)
-                HIPOK(hipStreamWaitEvent(stage1Stream, copied[gi], 0));
-            std::fill(G.usedB.begin(), G.usedB.end(), 0);
-            std::fill(G.pieceUsedB.begin(), G.pieceUsedB.end(), 0);
-            for (auto &fv : G.fetches)
-                fv.clear();
+                HIPOK(hipStreamWaitEvent(stage1Stream.get(), copied[gi].get(), 0));
+            for (Group::Block &B : G.blocks) {
+                B.used = 0;
+                B.pieceUsed = 0;
+                B.fetches.clear();
+            }
             std::vector<int> all;
             for (int sI = G.s0; sI < G.s1; ++sI)
                 all.push_back(sI);
             if (F > 1)
-                launchBlock(G, 0, all, d_frames, d_sigma6, stage1Stream); // block 0: every stack, slot == index in the group
-            HIPOK(hipEventRecord(G.stage1Done, stage1Stream));
+                launchBlock(G.blocks[0], 0, all, d_frames, d_sigma6, stage1Stream.get()); // block 0: every stack, slot == index in the group
+            HIPOK(hipEventRecord(G.stage1Done.get(), stage1Stream.get()));
         }
         std::vector<std::thread> th;
         for (int g = 1; g < ngroups; ++g)
@@ -962,7 +969,7 @@ private:
             const int s = G.s0 + k;
             StackState &st_ = stacks[s];
             const int e = s / C, c = s % C;
-            Trainer *t = trainers[c];
+            Trainer *t = trainers[c].get();
             if (meta.empty()) {
                 st_.analyzer.reset(new L3Localizer(std::to_string(e), "", c, true, &t, maskDir, parser.clone()));
                 st_.data.F = F;
@@ -987,10 +994,10 @@ private:
             }
             // block 0 was launched for every stack of the group, in group order (fetch 0, position k)
             if (F > 1)
-                bindBlock(G, st_, 0, 0, k);
+                bindBlock(G.blocks[0], 0, st_, 0, k);
             st_.analyzer->AttachEventData(&st_.data);
         });
-        HIPOK(hipEventSynchronize(G.stage1Done));
+        HIPOK(hipEventSynchronize(G.stage1Done.get()));
         G.tms[0] = nowMs() - t0;
 
         std::vector<int> pending(ns);
@@ -1059,7 +1066,7 @@ private:
     // of frames of a block that is already there (one row-machine launch per launch of the block that holds them).
     void fetchBlocks(Group &G, const std::vector<int> &need, const uint8_t *d_frames, const uint8_t *d_sigma6)
     {
-        hipStream_t stream = ordered ? stage1Stream : G.stream;
+        hipStream_t stream = ordered ? stage1Stream.get() : G.stream.get();
         const int nB = (int)blocks.size() - 1;
         std::vector<std::vector<int>> byBlock((size_t)nB);
         std::vector<std::vector<std::vector<int>>> byFetch((size_t)nB); // [block][fetch] -> stacks that need pieces
@@ -1078,18 +1085,19 @@ private:
         {
             std::lock_guard<std::mutex> lock(launchMu); // (the counters, and one launch sequence at a time per pipeline)
             for (int k = 0; k < nB; ++k) {
+                Group::Block &B = G.blocks[k];
                 if (!byBlock[k].empty()) {
-                    launchBlock(G, k, byBlock[k], d_frames, d_sigma6, stream);
-                    newFetch[k] = (int)G.fetches[k].size() - 1;
+                    launchBlock(B, k, byBlock[k], d_frames, d_sigma6, stream);
+                    newFetch[k] = (int)B.fetches.size() - 1;
                 }
                 const size_t blen = (size_t)(blocks[k + 1] - blocks[k]);
                 for (size_t f = 0; f < byFetch[k].size(); ++f) {
                     if (byFetch[k][f].empty())
                         continue;
                     // complete, for every asking stack, the flagged frames from the one it stopped at to the end of the block
-                    const Group::Fetch &fe = G.fetches[k][f];
+                    const Group::Fetch &fe = B.fetches[f];
                     const size_t nj = (size_t)fe.n * blen, base = (size_t)fe.first * blen;
-                    uint8_t *hw = G.h_wantB[k] + base;
+                    uint8_t *hw = B.want.h + base;
                     std::memset(hw, 0, nj);
                     for (int sI : byFetch[k][f]) {
                         BatchEventData &d = stacks[sI].data;
@@ -1099,25 +1107,24 @@ private:
                                 ++jobsCompleted;
                             }
                     }
-                    HIPOK(hipMemcpyAsync(G.d_wantB[k] + base, hw, nj, hipMemcpyHostToDevice, stream));
-                    check(abub_diff_hist_pieces_dev(d_frames, d_sigma6, G.d_jobsB[k] + base, (int)nj, W, H, G.d_histB[k] + base * 256,
-                                                    (uint64_t *)G.d_piecesB[k] + fe.pieceOff, G.d_pcountB[k] + f, G.d_wantB[k] + base,
-                                                    stream),
+                    B.want.toDevice(nj, stream, base);
+                    check(abub_diff_hist_pieces_dev(d_frames, d_sigma6, B.jobs.d + base, (int)nj, W, H, B.hist.d + base * 256,
+                                                    B.pieces + fe.pieceOff, B.pcount + f, B.want.d + base, stream),
                           "trigger search K2 (pieces)");
                     for (int sI : byFetch[k][f]) {
                         BatchEventData &d = stacks[sI].data;
                         const size_t j0 = (size_t)(d.needFrame - blocks[k]), o = (base + (size_t)d.slotOf[k] * blen + j0) * 256;
-                        HIPOK(hipMemcpyAsync(G.h_histB[k] + o, G.d_histB[k] + o, (blen - j0) * 1024, hipMemcpyDeviceToHost, stream));
+                        B.hist.toHost((blen - j0) * 256, stream, o);
                     }
                 }
             }
-            HIPOK(hipEventRecord(G.blockDone, stream));
+            HIPOK(hipEventRecord(G.blockDone.get(), stream));
         }
-        HIPOK(hipEventSynchronize(G.blockDone));
+        HIPOK(hipEventSynchronize(G.blockDone.get()));
         for (int k = 0; k < nB; ++k) {
             for (size_t q = 0; q < byBlock[k].size(); ++q) {
                 StackState &st_ = stacks[byBlock[k][q]];
-                bindBlock(G, st_, k, newFetch[k], (int)q);
+                bindBlock(G.blocks[k], k, st_, newFetch[k], (int)q);
                 st_.needMore = false;
             }
             const size_t blen = (size_t)(blocks[k + 1] - blocks[k]);
@@ -1212,8 +1219,8 @@ private:
         // group's kernels queue on the one trigger-search stream, so the GPU sees K2(g0) K2(g1) .. S3(g0) S3(g1) ..
         // strictly one kernel at a time -- chip-filling kernels launched on different streams only slow each
         // other down -- while the host stages of group g run under the kernels of group g+1.
-        hipStream_t stream = ordered ? stage1Stream : G.stream;
-        hipStream_t back = G.stream;
+        hipStream_t stream = ordered ? stage1Stream.get() : G.stream.get();
+        hipStream_t back = G.stream.get();
         // slots: all genesis images first (K2), then all post-trigger images (K3), camera-major: consecutive K3 jobs
         // then share their model, which is what lets one scanning wave serve several tracking frames (k3_zero_scan)
         int nd = 0, np = 0;
@@ -1227,7 +1234,7 @@ private:
             const int c = s % C;
             for (PlannedImage &p : stacks[s].data.planned) {
                 p.slot = p.kind == 0 ? di++ : pi++;
-                abub_job &j = G.h_jobs3[p.slot];
+                abub_job &j = G.jobs3.h[p.slot];
                 j.cur = (uint32_t)(s * F + p.i);
                 j.ref = (uint32_t)(s * F + p.ref);
                 j.model = (uint32_t)c;
@@ -1240,119 +1247,109 @@ private:
         // pixels of the components the localizer can use come back (abub_blobs.hip); the knob is read once per batch
         const bool useBlobs = blobs != 0;
         Group::Blobs &B = G.blobs;
+        CandidateList &L = G.list;
         if (useBlobs)
             initBlobs(G);
         std::vector<PlannedImage *> bySlot((size_t)nimg);
         for (int s : loc) {
-            stacks[s].data.roundHists = G.h_hist3;
+            stacks[s].data.roundHists = G.hist3.h;
             for (PlannedImage &p : stacks[s].data.planned) {
                 bySlot[p.slot] = &p;
-                G.h_thr[p.slot] = p.tozero; // candidate cut = TOZERO threshold, known before the launch
+                G.thr.h[p.slot] = p.tozero; // candidate cut = TOZERO threshold, known before the launch
                 if (useBlobs)
-                    B.h_minbox[p.slot] = p.minBox;
+                    B.minbox.h[p.slot] = p.minBox;
             }
         }
-        uint32_t cnt = 0;
         for (int attempt = 0;; ++attempt) {
-            HIPOK(hipMemcpyAsync(G.d_jobs3, G.h_jobs3, (size_t)nimg * sizeof(abub_job), hipMemcpyHostToDevice, stream));
-            HIPOK(hipMemcpyAsync(G.d_thr, G.h_thr, (size_t)nimg * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-            HIPOK(hipMemsetAsync(G.d_count, 0, sizeof(uint32_t), stream));
+            G.jobs3.toDevice(nimg, stream);
+            G.thr.toDevice(nimg, stream);
+            HIPOK(hipMemsetAsync(L.count.d, 0, sizeof(uint32_t), stream));
             const bool fused = abub_fast_path(W) != 0;
             if (fused) {
                 // images are never materialised: histogram + candidate list come out of the same pass
-                check(abub_diff_hist_compact_dev(d_frames, d_sigma6, G.d_jobs3, nd, W, H, G.d_hist3, nullptr, G.d_thr,
-                                                 G.d_pairs, G.pairCap, G.d_count, 0, stream),
+                check(abub_diff_hist_compact_dev(d_frames, d_sigma6, G.jobs3.d, nd, W, H, G.hist3.d, nullptr, G.thr.d, L.pairs,
+                                                 L.cap, L.count.d, 0, stream),
                       "stage3 K2 compact");
                 if (np > 0)
-                    check(abub_posttrig_compact_dev(d_frames, d_mu, d_sigma6, G.d_jobs3 + nd, np, W, H,
-                                                    G.d_hist3 + (size_t)nd * 256, nullptr, G.d_thr + nd, G.d_pairs,
-                                                    G.pairCap, G.d_count, (uint32_t)nd, stream),
+                    check(abub_posttrig_compact_dev(d_frames, d_mu, d_sigma6, G.jobs3.d + nd, np, W, H,
+                                                    G.hist3.d + (size_t)nd * 256, nullptr, G.thr.d + nd, L.pairs, L.cap,
+                                                    L.count.d, (uint32_t)nd, stream),
                           "stage3 K3 compact");
             } else {
-                check(abub_diff_hist_dev(d_frames, d_sigma6, G.d_jobs3, nd, W, H, G.d_hist3, G.d_img, 0, stream),
+                check(abub_diff_hist_dev(d_frames, d_sigma6, G.jobs3.d, nd, W, H, G.hist3.d, G.img, 0, stream),
                       "stage3 K2 store");
                 if (np > 0)
-                    check(abub_posttrig_dev(d_frames, d_mu, d_sigma6, G.d_jobs3 + nd, np, W, H, G.d_hist3 + (size_t)nd * 256,
-                                            G.d_img + (size_t)nd * P, stream),
+                    check(abub_posttrig_dev(d_frames, d_mu, d_sigma6, G.jobs3.d + nd, np, W, H, G.hist3.d + (size_t)nd * 256,
+                                            G.img + (size_t)nd * P, stream),
                           "stage3 K3");
-                check(abub_fg_compact_pairs_dev(G.d_img, nimg, W, H, G.d_thr, G.d_pairs, G.pairCap, G.d_count, stream),
-                      "stage3 K4");
+                check(abub_fg_compact_pairs_dev(G.img, nimg, W, H, G.thr.d, L.pairs, L.cap, L.count.d, stream), "stage3 K4");
             }
             // group the list by image on the device; the host gets contiguous runs and never re-buckets
             // (per-slot counts come from the histograms the same launches produced: no counting pass)
-            check(abub_pairs_group_hist_dev(G.d_pairs, G.d_count, G.pairCap, nimg, G.d_gscratch, G.d_goff, G.d_gidx, G.d_gval,
-                                            G.d_hist3, G.d_thr, stream),
-                  "stage3 group");
+            L.group(nimg, G.hist3.d, G.thr.d, stream, "stage3 group");
             if (useBlobs) {
-                HIPOK(hipMemcpyAsync(B.d_minbox, B.h_minbox, (size_t)nimg * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-                HIPOK(hipEventRecord(B.ev[0], stream));
-                check(abub_binarize_thr_dev(G.d_hist3, G.d_thr, nimg, W, H, B.d_otsu, stream), "stage3 Otsu");
-                HIPOK(hipEventRecord(B.ev[1], stream));
-                check(abub_label_blobs_dev(G.d_goff, G.d_gidx, G.d_gval, G.pairCap, nimg, W, H, B.d_otsu, B.d_minbox, B.d_koff,
-                                           B.d_kidx, B.cap, B.d_ncomp, B.d_nkc, B.d_coff, nullptr, 0, B.d_stats, B.d_scratch,
-                                           B.scratchBytes, stream),
+                B.minbox.toDevice(nimg, stream);
+                HIPOK(hipEventRecord(B.ev[0].get(), stream));
+                check(abub_binarize_thr_dev(G.hist3.d, G.thr.d, nimg, W, H, B.otsu.d, stream), "stage3 Otsu");
+                HIPOK(hipEventRecord(B.ev[1].get(), stream));
+                check(abub_label_blobs_dev(L.goff.d, L.gidx.d, L.gval.d, L.cap, nimg, W, H, B.otsu.d, B.minbox.d, B.koff.d,
+                                           L.kidx.d, L.cap, B.ncomp, B.nkc, B.coff, nullptr, 0, B.kstats.d, L.keptScratch,
+                                           L.keptScratchBytes, stream),
                       "stage3 K4b");
-                HIPOK(hipEventRecord(B.ev[2], stream));
+                HIPOK(hipEventRecord(B.ev[2].get(), stream));
             }
-            HIPOK(hipEventRecord(G.kernelsDone, stream));
-            HIPOK(hipStreamWaitEvent(back, G.kernelsDone, 0));
-            HIPOK(hipMemcpyAsync(G.h_hist3, G.d_hist3, (size_t)nimg * 1024, hipMemcpyDeviceToHost, back));
-            HIPOK(hipMemcpyAsync(G.h_count, G.d_count, sizeof(uint32_t), hipMemcpyDeviceToHost, back));
-            HIPOK(hipMemcpyAsync(G.h_goff, G.d_goff, (size_t)(nimg + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, back));
+            HIPOK(hipEventRecord(G.kernelsDone.get(), stream));
+            HIPOK(hipStreamWaitEvent(back, G.kernelsDone.get(), 0));
+            G.hist3.toHost((size_t)nimg * 256, back);
+            L.offsetsToHost(nimg, back);
             if (useBlobs) {
-                HIPOK(hipMemcpyAsync(B.h_otsu, B.d_otsu, (size_t)nimg * sizeof(int32_t), hipMemcpyDeviceToHost, back));
-                HIPOK(hipMemcpyAsync(B.h_koff, B.d_koff, (size_t)(nimg + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, back));
-                HIPOK(hipMemcpyAsync(B.h_stats, B.d_stats, 4 * sizeof(uint32_t), hipMemcpyDeviceToHost, back));
+                B.otsu.toHost(nimg, back);
+                B.koff.toHost((size_t)nimg + 1, back);
+                B.kstats.toHost(4, back);
             }
             HIPOK(hipStreamSynchronize(back));
             if (useBlobs) {
                 float m0 = 0, m1 = 0;
-                HIPOK(hipEventElapsedTime(&m0, B.ev[0], B.ev[1]));
-                HIPOK(hipEventElapsedTime(&m1, B.ev[1], B.ev[2]));
+                HIPOK(hipEventElapsedTime(&m0, B.ev[0].get(), B.ev[1].get()));
+                HIPOK(hipEventElapsedTime(&m1, B.ev[1].get(), B.ev[2].get()));
                 B.stats[6] += m0;
                 B.stats[7] += m1;
             }
             G.tms[5] += nowMs() - ta; // launches + kernels + hist/count D2H
             ta = nowMs();
-            cnt = *G.h_count;
-            G.lastPairs = cnt;
-            if (cnt <= G.pairCap)
+            G.lastPairs = *L.count.h;
+            // dense foreground (e.g. a flash frame): the kernels kept counting past the capacity, so the needed size is
+            // known -- grow the lists once (the kernels that used them are done: `back` waited for them) and redo the batch
+            if (L.fits(attempt, "foreground list overflow (dense foreground in too many images)"))
                 break;
-            // dense foreground (e.g. a flash frame): the kernels kept counting past the capacity, so the needed
-            // size is known -- grow the lists once and redo the batch
-            if (attempt > 0 || cnt > (1u << 30))
-                throw std::runtime_error("RunPipeline: foreground list overflow (dense foreground in too many images)");
-            growLists(G, cnt + cnt / 4 + 1024);
         }
-        const uint32_t nkept = useBlobs ? B.h_koff[nimg] : 0;
+        const uint32_t cnt = *L.count.h;
+        const uint32_t nkept = useBlobs ? B.koff.h[nimg] : 0;
         if (useBlobs) {
-            if (nkept > B.cap)
+            if (nkept > L.cap)
                 throw std::runtime_error("RunPipeline: kept list larger than the candidate list");
             if (nkept)
-                HIPOK(hipMemcpyAsync(B.h_kidx, B.d_kidx, (size_t)nkept * 4, hipMemcpyDeviceToHost, back));
-            const double add[6] = {(double)cnt, (double)B.h_stats[1], (double)nkept, (double)B.h_stats[2], (double)B.h_stats[3],
-                                   (double)B.h_stats[0]};
+                L.kidx.toHost(nkept, back);
+            const double add[6] = {(double)cnt, (double)B.kstats.h[1], (double)nkept, (double)B.kstats.h[2],
+                                   (double)B.kstats.h[3], (double)B.kstats.h[0]};
             for (int k = 0; k < 6; ++k)
                 B.stats[k] += add[k];
-        } else if (cnt) {
-            HIPOK(hipMemcpyAsync(G.h_gidx, G.d_gidx, (size_t)cnt * 4, hipMemcpyDeviceToHost, back));
-            HIPOK(hipMemcpyAsync(G.h_gval, G.d_gval, (size_t)cnt, hipMemcpyDeviceToHost, back));
-        }
+        } else
+            L.pairsToHost(back);
         // thresholds (TOZERO + Otsu) on the host from the histograms, while the list travels
+        // (pointers into the list: taken after the grow loop, used until the next batch replans every image)
         pool->parallelFor(nimg, [&](int k) {
             PlannedImage *p = bySlot[k];
-            p->thr = binarizeThresholdFromHist(G.h_hist3 + (size_t)k * 256, P, p->tozero);
+            p->thr = binarizeThresholdFromHist(G.hist3.h + (size_t)k * 256, P, p->tozero);
             if (useBlobs) {
                 p->fg = nullptr;
                 p->fgv = nullptr;
                 p->nfg = 0;
-                p->kept = B.h_kidx + B.h_koff[k];
-                p->nkept = B.h_koff[k + 1] - B.h_koff[k];
-                p->otsuMismatch = B.h_otsu[k] != p->thr;
+                p->kept = L.kidx.h + B.koff.h[k];
+                p->nkept = B.koff.h[k + 1] - B.koff.h[k];
+                p->otsuMismatch = B.otsu.h[k] != p->thr;
             } else {
-                p->fg = G.h_gidx + G.h_goff[k];
-                p->fgv = G.h_gval + G.h_goff[k];
-                p->nfg = G.h_goff[k + 1] - G.h_goff[k];
+                L.bind(*p, k);
                 p->kept = nullptr;
                 p->nkept = 0;
             }
@@ -1365,7 +1362,7 @@ private:
     // The stacks of `loc` whose localize stopped at a veto request (NeedBellows) are served together on the group's own
     // stream, one host synchronisation per sub-round: first the template matches (trigger and pre-trigger frames, one
     // launch per template), then the residual images; after each, localize runs again on those stacks.  The round's
-    // planned images (h_hist3, h_gidx, h_gval) stay untouched: the veto has buffers of its own.
+    // planned images (hist3, list) stay untouched: the veto has buffers of its own.
     void vetoRound(Group &G, const std::vector<int> &loc, const uint8_t *d_frames, const uint8_t *d_sigma6)
     {
         const double t0 = nowMs();
@@ -1378,11 +1375,16 @@ private:
             if (ask.empty())
                 break;
             any = true;
-            bool served = false;
+            bool served = false, fallback = false;
             if (sub < 3) {
                 try {
                     served = vetoMatches(G, ask, d_frames) || vetoResiduals(G, ask, d_frames, d_sigma6);
                 } catch (VetoFallback &) {
+                    fallback = true;
+                } catch (AllocError &) {
+                    fallback = true;
+                }
+                if (fallback) {
                     // no room for the veto buffers, or a shape the batched matcher refuses: the one-at-a-time path takes
                     // these stacks, as it took every veto before
                     for (int s : ask) {
@@ -1410,16 +1412,6 @@ private:
 
     struct VetoFallback {};
 
-    template <typename T>
-    T *vetoAlloc(size_t n, bool device)
-    {
-        try {
-            return device ? dalloc<T>(n) : halloc<T>(n);
-        } catch (std::exception &) {
-            throw VetoFallback();
-        }
-    }
-
     // the group's device copy of a bellows template, uploaded once on the group's stream (the only stream that uses it;
     // the host Mat is the process-wide mask cache's, immutable and kept alive by the entry)
     const uint8_t *deviceTemplate(Group &G, const cv::Mat &t)
@@ -1427,10 +1419,11 @@ private:
         for (auto &e : G.veto.templates)
             if (e.first.data == t.data && e.first.cols == t.cols && e.first.rows == t.rows)
                 return e.second;
-        uint8_t *d = vetoAlloc<uint8_t>(t.total(), true);
-        HIPOK(hipMemcpyAsync(d, t.data, t.total(), hipMemcpyHostToDevice, G.stream));
-        G.veto.templates.emplace_back(t, d);
-        return d;
+        DeviceArray<uint8_t> d;
+        d.allocate(t.total());
+        HIPOK(hipMemcpyAsync(d, t.data, t.total(), hipMemcpyHostToDevice, G.stream.get()));
+        G.veto.templates.emplace_back(t, std::move(d));
+        return G.veto.templates.back().second;
     }
 
     // every outstanding match request of the asking stacks; false if there is none
@@ -1463,40 +1456,41 @@ private:
                 throw VetoFallback();
             scratch = std::max(scratch, need);
         }
+        // (the veto's earlier work on the group's stream has been waited for: growing frees the old buffers)
         if (V.capJobs < total) {
             const int cap = std::max(total, 2 * V.capJobs);
-            V.d_fidx = vetoAlloc<uint32_t>(cap, true);
-            V.h_fidx = vetoAlloc<uint32_t>(cap, false);
-            V.d_xy = vetoAlloc<float>(2 * (size_t)cap, true);
-            V.h_xy = vetoAlloc<float>(2 * (size_t)cap, false);
+            V.capJobs = 0;
+            V.fidx.allocate(cap);
+            V.xy.allocate(2 * (size_t)cap);
             V.capJobs = cap;
         }
         if (V.scratchBytes < scratch) {
-            V.d_scratch = vetoAlloc<uint8_t>(scratch, true);
+            V.scratchBytes = 0;
+            V.scratch.allocate(scratch);
             V.scratchBytes = scratch;
         }
-        hipStream_t st = G.stream;
+        hipStream_t st = G.stream.get();
         int off = 0;
         for (size_t t = 0; t < tpl.size(); ++t) {
             const int n = (int)byT[t].size();
             const uint8_t *dt = deviceTemplate(G, tpl[t]);
             for (int q = 0; q < n; ++q)
-                V.h_fidx[off + q] = (uint32_t)(byT[t][q].first * F + byT[t][q].second->frame);
-            HIPOK(hipMemcpyAsync(V.d_fidx + off, V.h_fidx + off, (size_t)n * 4, hipMemcpyHostToDevice, st));
-            const int rc = abub_match_best_batch_dev(d_frames, W, H, V.d_fidx + off, n, dt, tpl[t].cols, tpl[t].rows,
-                                                     V.d_xy + 2 * off, V.d_scratch, V.scratchBytes, st);
+                V.fidx.h[off + q] = (uint32_t)(byT[t][q].first * F + byT[t][q].second->frame);
+            V.fidx.toDevice(n, st, off);
+            const int rc = abub_match_best_batch_dev(d_frames, W, H, V.fidx.d + off, n, dt, tpl[t].cols, tpl[t].rows,
+                                                     V.xy.d + 2 * off, V.scratch, V.scratchBytes, st);
             if (rc == ABUB_E_INVALID) // refused before anything was queued (e.g. a frame wider than the matcher takes)
                 throw VetoFallback();
             check(rc, "bellows veto match");
             off += n;
             ++G.matchLaunches;
         }
-        HIPOK(hipMemcpyAsync(V.h_xy, V.d_xy, (size_t)total * 8, hipMemcpyDeviceToHost, st));
+        V.xy.toHost(2 * (size_t)total, st);
         HIPOK(hipStreamSynchronize(st));
         off = 0;
         for (size_t t = 0; t < tpl.size(); ++t)
             for (auto &r : byT[t]) {
-                r.second->xy = cv::Point2f(V.h_xy[2 * off], V.h_xy[2 * off + 1]);
+                r.second->xy = cv::Point2f(V.xy.h[2 * off], V.xy.h[2 * off + 1]);
                 r.second->ready = true;
                 ++off;
             }
@@ -1515,103 +1509,83 @@ private:
         if (req.empty())
             return false;
         Group::Veto &V = G.veto;
+        CandidateList &L = V.list;
         const int n = (int)req.size();
         if (V.capImg < n) {
             const int cap = std::max(n, 2 * V.capImg);
-            V.d_rend = vetoAlloc<uint8_t>(2 * (size_t)cap * P, true);
-            V.h_rend = vetoAlloc<uint8_t>(2 * (size_t)cap * P, false);
-            V.d_syn = vetoAlloc<uint8_t>((size_t)cap * P, true);
-            V.d_img = vetoAlloc<uint8_t>((size_t)cap * P, true);
-            V.d_rhist = vetoAlloc<uint32_t>((size_t)cap * 256, true);
-            V.d_hist = vetoAlloc<uint32_t>((size_t)cap * 256, true);
-            V.h_hist = vetoAlloc<uint32_t>((size_t)cap * 256, false);
-            V.d_jobs = vetoAlloc<abub_job>(cap, true);
-            V.h_jobs = vetoAlloc<abub_job>(cap, false);
-            V.d_thr = vetoAlloc<int32_t>(cap, true);
-            V.h_thr = vetoAlloc<int32_t>(cap, false);
-            V.d_gscratch = vetoAlloc<uint32_t>(2 * (size_t)cap, true);
-            V.d_goff = vetoAlloc<uint32_t>((size_t)cap + 1, true);
-            V.h_goff = vetoAlloc<uint32_t>((size_t)cap + 1, false);
+            V.capImg = 0;
+            V.rend.allocate(2 * (size_t)cap * P);
+            V.syn.allocate((size_t)cap * P);
+            V.img.allocate((size_t)cap * P);
+            V.rhist.allocate((size_t)cap * 256);
+            V.hist.allocate((size_t)cap * 256);
+            V.jobs.allocate(cap);
+            V.thr.allocate(cap);
+            L.allocate(cap);
             V.capImg = cap;
         }
-        if (!V.d_count) {
-            V.d_count = vetoAlloc<uint32_t>(1, true);
-            V.h_count = vetoAlloc<uint32_t>(1, false);
-        }
-        if (V.pairCap == 0)
-            growVetoLists(V, 1u << 20);
-        hipStream_t st = G.stream;
+        if (L.cap == 0)
+            L.grow(pairCap > 0 ? (uint32_t)pairCap : 1u << 20);
+        hipStream_t st = G.stream.get();
         // the two renderings of the template (L3Localizer.cpp:326-334), then everything on the device with no sync between
         pool->parallelFor(n, [&](int k) {
             const BatchEventData::ResidualMemo &r = *req[k].second;
-            uint8_t *t = V.h_rend + 2 * (size_t)k * P, *p = t + P;
+            uint8_t *t = V.rend.h + 2 * (size_t)k * P, *p = t + P;
             std::memset(t, 0, 2 * P);
             for (int y = 0; y < r.templ.rows; ++y) {
                 std::memcpy(t + (size_t)(r.rt.y + y) * W + r.rt.x, r.templ.ptr<uchar>(y), (size_t)r.templ.cols);
                 std::memcpy(p + (size_t)(r.rp.y + y) * W + r.rp.x, r.templ.ptr<uchar>(y), (size_t)r.templ.cols);
             }
         });
-        HIPOK(hipMemcpyAsync(V.d_rend, V.h_rend, 2 * (size_t)n * P, hipMemcpyHostToDevice, st));
+        V.rend.toDevice(2 * (size_t)n * P, st);
         for (int k = 0; k < n; ++k) {
             const int s = req[k].first, c = s % C;
             const BatchEventData::ResidualMemo &r = *req[k].second;
             // ROI ProcessFrame(trig copy, pre copy) (:355); the pre copy lies after the trigger copy, as the kernel wants
-            check(abub_diff_roi_dev(V.d_rend + 2 * (size_t)k * P, V.d_rend + (2 * (size_t)k + 1) * P, d_sigma6 + (size_t)c * P, W, H,
-                                    r.roi.x, r.roi.y, r.roi.width, r.roi.height, V.d_syn + (size_t)k * P, V.d_rhist + (size_t)k * 256,
+            check(abub_diff_roi_dev(V.rend.d + 2 * (size_t)k * P, V.rend.d + (2 * (size_t)k + 1) * P, d_sigma6 + (size_t)c * P, W, H,
+                                    r.roi.x, r.roi.y, r.roi.width, r.roi.height, V.syn + (size_t)k * P, V.rhist + (size_t)k * 256,
                                     st),
                   "bellows veto ROI ProcessFrame");
-            abub_job &j = V.h_jobs[k];
+            abub_job &j = V.jobs.h[k];
             j.cur = (uint32_t)(s * F + r.trig);
             j.ref = (uint32_t)(s * F + r.pre);
             j.model = (uint32_t)c;
             j.out = (uint32_t)k;
-            V.h_thr[k] = stacks[s].analyzer->loc_thres; // TOZERO cut of contoursOfCurrentImage
+            V.thr.h[k] = stacks[s].analyzer->loc_thres; // TOZERO cut of contoursOfCurrentImage
         }
-        HIPOK(hipMemcpyAsync(V.d_jobs, V.h_jobs, (size_t)n * sizeof(abub_job), hipMemcpyHostToDevice, st));
-        HIPOK(hipMemcpyAsync(V.d_thr, V.h_thr, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, st));
+        V.jobs.toDevice(n, st);
+        V.thr.toDevice(n, st);
         // D(trig; pre) stored, minus the synthetic diff (overTheSigma -= diff_frame, :362)
-        check(abub_diff_hist_dev(d_frames, d_sigma6, V.d_jobs, n, W, H, V.d_hist, V.d_img, 0, st), "bellows veto K2 store");
+        check(abub_diff_hist_dev(d_frames, d_sigma6, V.jobs.d, n, W, H, V.hist.d, V.img, 0, st), "bellows veto K2 store");
         for (int k = 0; k < n; ++k)
-            check(abub_subsat_hist_dev(V.d_img + (size_t)k * P, V.d_syn + (size_t)k * P, W, H, V.d_hist + (size_t)k * 256, st),
+            check(abub_subsat_hist_dev(V.img + (size_t)k * P, V.syn + (size_t)k * P, W, H, V.hist.d + (size_t)k * 256, st),
                   "bellows veto subtract");
-        uint32_t cnt = 0;
         for (int attempt = 0;; ++attempt) {
-            HIPOK(hipMemsetAsync(V.d_count, 0, sizeof(uint32_t), st));
-            check(abub_fg_compact_pairs_dev(V.d_img, n, W, H, V.d_thr, V.d_pairs, V.pairCap, V.d_count, st), "bellows veto K4");
-            check(abub_pairs_group_hist_dev(V.d_pairs, V.d_count, V.pairCap, n, V.d_gscratch, V.d_goff, V.d_gidx, V.d_gval,
-                                            V.d_hist, V.d_thr, st),
-                  "bellows veto group");
-            HIPOK(hipMemcpyAsync(V.h_hist, V.d_hist, (size_t)n * 1024, hipMemcpyDeviceToHost, st));
-            HIPOK(hipMemcpyAsync(V.h_count, V.d_count, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-            HIPOK(hipMemcpyAsync(V.h_goff, V.d_goff, (size_t)(n + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+            HIPOK(hipMemsetAsync(L.count.d, 0, sizeof(uint32_t), st));
+            check(abub_fg_compact_pairs_dev(V.img, n, W, H, V.thr.d, L.pairs, L.cap, L.count.d, st), "bellows veto K4");
+            L.group(n, V.hist.d, V.thr.d, st, "bellows veto group");
+            V.hist.toHost((size_t)n * 256, st);
+            L.offsetsToHost(n, st);
             HIPOK(hipStreamSynchronize(st));
-            cnt = *V.h_count;
-            if (cnt <= V.pairCap)
+            if (L.fits(attempt, "bellows veto foreground list overflow")) // (grows after the sync above: only K4 is redone)
                 break;
-            if (attempt > 0 || cnt > (1u << 30))
-                throw std::runtime_error("RunPipeline: bellows veto foreground list overflow");
-            growVetoLists(V, cnt + cnt / 4 + 1024);
         }
-        if (cnt) {
-            HIPOK(hipMemcpyAsync(V.h_gidx, V.d_gidx, (size_t)cnt * 4, hipMemcpyDeviceToHost, st));
-            HIPOK(hipMemcpyAsync(V.h_gval, V.d_gval, (size_t)cnt, hipMemcpyDeviceToHost, st));
-            HIPOK(hipStreamSynchronize(st));
-        }
+        L.pairsToHost(st);
+        HIPOK(hipStreamSynchronize(st));
         for (int k = 0; k < n; ++k) {
             const int s = req[k].first;
             BatchEventData::ResidualMemo &r = *req[k].second;
-            std::memcpy(r.hist, V.h_hist + (size_t)k * 256, sizeof(r.hist));
+            std::memcpy(r.hist, V.hist.h + (size_t)k * 256, sizeof(r.hist));
             PlannedImage &p = r.img;
             p.kind = 2;
             p.i = r.trig;
             p.ref = r.pre;
             p.slot = k;
-            p.tozero = V.h_thr[k];
+            p.tozero = V.thr.h[k];
             p.thr = binarizeThresholdFromHist(r.hist, P, p.tozero);
             p.minBox = -1;
-            p.fg = V.h_gidx + V.h_goff[k];
-            p.fgv = V.h_gval + V.h_goff[k];
-            p.nfg = V.h_goff[k + 1] - V.h_goff[k];
+            // valid until the veto's next sub-round: a ready memo is read only by the localize that directly follows
+            L.bind(p, k);
             r.ready = true;
             if (!stacks[s].vetoed) {
                 stacks[s].vetoed = true;
@@ -1622,62 +1596,22 @@ private:
         return true;
     }
 
-    void growVetoLists(Group::Veto &V, uint32_t cap)
-    {
-        V.d_pairs = vetoAlloc<uint32_t>((size_t)cap * 2, true);
-        V.d_gidx = vetoAlloc<uint32_t>(cap, true);
-        V.d_gval = vetoAlloc<uint8_t>(cap, true);
-        V.h_gidx = vetoAlloc<uint32_t>(cap, false);
-        V.h_gval = vetoAlloc<uint8_t>(cap, false);
-        V.pairCap = cap;
-    }
-
-    // the old buffers stay on the allocation lists and are released with the pipeline
-    void growLists(Group &G, uint32_t cap)
-    {
-        G.pairCap = cap;
-        G.d_pairs = dalloc<uint32_t>((size_t)cap * 2);
-        G.d_gidx = dalloc<uint32_t>(cap);
-        G.d_gval = dalloc<uint8_t>(cap);
-        G.h_gidx = halloc<uint32_t>(cap);
-        G.h_gval = halloc<uint8_t>(cap);
-        if (G.blobs.ready)
-            growBlobList(G, cap); // kept pixels are a subset of the candidates: the same capacity suffices
-    }
-
-    void growBlobList(Group &G, uint32_t cap)
-    {
-        Group::Blobs &B = G.blobs;
-        const int n3 = (G.s1 - G.s0) * (NumFramesBubbleTrack + 1);
-        B.scratchBytes = abub_label_blobs_scratch_bytes(n3, W, H, cap, 0);
-        if (B.scratchBytes == 0)
-            throw std::runtime_error("RunPipeline: frame size not supported by the blob labelling");
-        B.d_scratch = (void *)dalloc<uint8_t>(B.scratchBytes);
-        B.d_kidx = dalloc<uint32_t>(cap);
-        B.h_kidx = halloc<uint32_t>(cap);
-        B.cap = cap;
-    }
-
     void initBlobs(Group &G)
     {
         Group::Blobs &B = G.blobs;
         if (B.ready)
             return;
         const size_t n3 = (size_t)(G.s1 - G.s0) * (NumFramesBubbleTrack + 1);
-        B.d_otsu = dalloc<int32_t>(n3);
-        B.h_otsu = halloc<int32_t>(n3);
-        B.d_minbox = dalloc<int32_t>(n3);
-        B.h_minbox = halloc<int32_t>(n3);
-        B.d_koff = dalloc<uint32_t>(n3 + 1);
-        B.h_koff = halloc<uint32_t>(n3 + 1);
-        B.d_ncomp = dalloc<uint32_t>(n3);
-        B.d_nkc = dalloc<uint32_t>(n3);
-        B.d_coff = dalloc<uint32_t>(n3 + 1);
-        B.d_stats = dalloc<uint32_t>(4);
-        B.h_stats = halloc<uint32_t>(4);
-        for (hipEvent_t &e : B.ev)
-            HIPOK(hipEventCreate(&e));
-        growBlobList(G, G.pairCap);
+        B.otsu.allocate(n3);
+        B.minbox.allocate(n3);
+        B.koff.allocate(n3 + 1);
+        B.ncomp.allocate(n3);
+        B.nkc.allocate(n3);
+        B.coff.allocate(n3 + 1);
+        B.kstats.allocate(4);
+        for (Event &e : B.ev)
+            e.create(true);
+        G.list.keep((int)n3, W, H);
         B.ready = true;
     }
 

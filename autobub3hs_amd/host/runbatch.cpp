@@ -24,79 +24,13 @@
 #include "ParseFolder/Parser.hpp"
 #include "PICOFormatWriter/PICOFormatWriterV4.hpp"
 #include "devctx.hpp"
+#include "holders.hpp"
 #include "pipeline.hpp"
 #include "pngwalk.hpp"
 #include "runbatch.hpp"
 
 namespace abub {
 namespace {
-
-struct NoCopy {
-    NoCopy() = default;
-    NoCopy(const NoCopy &) = delete;
-    NoCopy &operator=(const NoCopy &) = delete;
-};
-
-// Memory of a worker: HBM, or pinned host memory
-template <bool Pinned>
-class Buffer : NoCopy {
-public:
-    ~Buffer() { release(); }
-    uint8_t *get() const { return p_; }
-    size_t capacity() const { return cap_; }
-    // at least `bytes`; when it has to grow it takes a quarter more, for the batches to come (the contents are not kept)
-    void grow(size_t bytes)
-    {
-        if (bytes > cap_)
-            allocate(bytes + bytes / 4 + 256);
-    }
-    // exactly `bytes`
-    void allocate(size_t bytes)
-    {
-        release();
-        void *q = nullptr;
-        const hipError_t e = Pinned ? hipHostMalloc(&q, bytes, hipHostMallocDefault) : hipMalloc(&q, bytes);
-        if (e != hipSuccess)
-            throw std::runtime_error(std::string(Pinned ? "hipHostMalloc" : "hipMalloc") + " of " + std::to_string(bytes) +
-                                     " bytes: " + hipGetErrorString(e));
-        p_ = (uint8_t *)q;
-        cap_ = bytes;
-    }
-
-private:
-    void release()
-    {
-        if (p_)
-            (void)(Pinned ? hipHostFree(p_) : hipFree(p_));
-        p_ = nullptr;
-        cap_ = 0;
-    }
-    uint8_t *p_ = nullptr;
-    size_t cap_ = 0;
-};
-using DeviceBuffer = Buffer<false>;
-using PinnedBuffer = Buffer<true>;
-
-// A non-blocking stream of the current device, made on first use; its work is finished before it goes
-class Stream : NoCopy {
-public:
-    ~Stream()
-    {
-        if (s_) {
-            (void)hipStreamSynchronize(s_);
-            (void)hipStreamDestroy(s_);
-        }
-    }
-    hipStream_t get()
-    {
-        if (!s_)
-            HIPOK(hipStreamCreateWithFlags(&s_, hipStreamNonBlocking));
-        return s_;
-    }
-
-private:
-    hipStream_t s_ = nullptr;
-};
 
 // fn(parser, i) for every i < n on up to `nthreads` threads, each with its own clone of `parser`.  The first exception is
 // re-thrown once every thread has been joined (the others stop at their next task).

@@ -324,6 +324,17 @@ def test_pipeline_runs_the_veto_in_the_batch(tmp_path, oracle):
 
 
 @pytest.mark.gpu
+def test_pipeline_veto_list_grows_on_overflow(tmp_path, oracle):
+    """ABUB_PIPE_PAIRCAP also seeds the veto's candidate list: the residual's candidates overflow it, the list grows and
+    the veto's K4 is redone -- the same results and veto counts as with the default capacity."""
+    pipe = _run_pipeline(tmp_path, oracle, with_sigma=True, env={"ABUB_PIPE_PAIRCAP": "16"})
+    assert pipe.timing()["dropin_stacks"] == 0
+    st = pipe.bellows_stats()
+    assert st["vetoed"] == 1 and st["match_jobs"] == 2 and st["match_launches"] == 1 and st["residual_images"] == 1, st
+    pipe.close()
+
+
+@pytest.mark.gpu
 def test_pipeline_veto_without_raw_sigma(tmp_path, oracle):
     pipe = _run_pipeline(tmp_path, oracle, with_sigma=False)
     assert pipe.timing()["dropin_stacks"] == 0 and pipe.bellows_stats()["vetoed"] == 1
