@@ -137,6 +137,27 @@ class Run:
             raise RuntimeError(lib().abh_last_error(self._h).decode())
         return st.value, tss.value, mu, sg
 
+    def train_on_gpu(self, ncams, shape=None):
+        """Every camera trained in one pass on the device (abub::TrainOnDevice): per camera (status, tss, mu, sigma), the
+        same as train(cam).  self.train_path is "device", or "host" where TrainOnDevice declined the run; self.train_stats:
+        frames decoded by the GPU decoder / by host threads, decode launches, seconds."""
+        H, W = shape if shape is not None else self._shape
+        L = lib()
+        L.abh_train_device.argtypes = [C.c_void_p, C.c_int, _ip, _ip, _u8p, _u8p, C.c_int, _dp]
+        mu = np.zeros((ncams, H, W), np.uint8)
+        sg = np.zeros((ncams, H, W), np.uint8)
+        st = np.zeros(ncams, np.int32)
+        tss = np.zeros(ncams, np.int32)
+        stats = np.zeros(4, np.float64)
+        rc = L.abh_train_device(self._h, ncams, st.ctypes.data_as(_ip), tss.ctypes.data_as(_ip), mu.ctypes.data_as(_u8p),
+                                sg.ctypes.data_as(_u8p), H * W, stats.ctypes.data_as(_dp))
+        if rc < 0:
+            raise RuntimeError(L.abh_last_error(self._h).decode())
+        self.train_path = "device" if rc == 0 else "host"
+        self.train_stats = {"frames_gpu_decoded": int(stats[0]), "frames_host_decoded": int(stats[1]),
+                            "decode_launches": int(stats[2]), "seconds": float(stats[3])}
+        return [(int(st[c]), int(tss[c]), mu[c], sg[c]) for c in range(ncams)]
+
     def set_model(self, cam, mu, sigma, tss):
         mu = np.ascontiguousarray(mu, dtype=np.uint8)
         sigma = np.ascontiguousarray(sigma, dtype=np.uint8)

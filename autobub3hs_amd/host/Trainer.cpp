@@ -17,6 +17,8 @@
 
 static std::atomic<unsigned long long> g_modelCounter{1};
 
+unsigned long long Trainer::NextModelId() { return g_modelCounter.fetch_add(1); }
+
 Trainer::Trainer(int camera, std::vector<std::string> EventList, std::string EventDir, std::string ImageFormat,
                  std::string ImageFolder, Parser *FileParser, bool debug)
 {
@@ -190,6 +192,6 @@ void Trainer::MakeAvgSigmaImage(bool PerformLBPOnImages)
         return;
     }
     CalculateMeanSigmaImageVector(training, TrainedAvgImage, TrainedSigmaImage);
-    ModelId = g_modelCounter.fetch_add(1);
+    ModelId = NextModelId();
     printf("complete.\n");
 }

@@ -4,15 +4,12 @@
 // (-7 rows if it fails), event loop with ordered output, -5 if the run cannot be read.  boost::program_options and
 // OpenMP are replaced by a small parser and a std::thread pool (ABUB_THREADS, default min(16, cores)).
 #include <algorithm>
-#include <atomic>
-#include <condition_variable>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <iostream>
 #include <sstream>
-#include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
@@ -30,10 +27,15 @@
 static std::string usage()
 {
     return "Usage: abub3hs [-hzme] [-D data_series] [-c cam_mask_dir] [--debug code] -d data_dir -r run_ID -o out_dir\n"
+           "       abub3hs [-hzm] [-D data_series] [-c cam_mask_dir] -d data_dir --runs ID[,ID...] | --run-list FILE -o out_dir\n"
            "Run the AutoBub3hs bubble finding algorithm on a PICO run (MI355X hot path)\n\n"
            "Required arguments:\n"
            "  -d, --data_dir = Dir\t\tpath to the directory in which the run folder/file is stored\n"
            "  -r, --run_id = Str\t\trun ID, formatted as YYYYMMDD_*\n"
+           "  or --runs = ID[,ID...]\truns of one data series processed by this one process (a campaign), each written to\n"
+           "\t\t\t\tits own abub3hs_<run>.txt; the next run trains on the GPU while the current one is detected\n"
+           "  or --run-list = File\t\tthe same with one run ID per line (blank lines and # comments ignored); may be\n"
+           "\t\t\t\tcombined with --runs, the order is kept; not with -r, no run twice\n"
            "  -o, --out_dir = Dir\t\tdirectory to write the output file to\n\n"
            "Optional arguments:\n"
            "  -h, --help\t\t\tgive this help message\n"
@@ -47,12 +49,13 @@ static std::string usage()
            "  --gpus = Int\t\t\tGPUs to spread the event batches over (one worker thread per GPU; default 1)\n"
            "  --gpu-shard = r/N\t\tprocess only the events whose index in the sorted event list is r modulo N;\n"
            "\t\t\t\twrites abub3hs_<run>.part<r>of<N>.txt (N > 1)\n"
-           "  --merge = N\t\t\tassemble abub3hs_<run>.txt in --out_dir from the N part files of a sharded run\n"
+           "  --merge = N\t\t\tassemble abub3hs_<run>.txt in --out_dir from the N part files of a sharded run (of every\n"
+           "\t\t\t\trun of --runs / --run-list)\n"
            "  --per-event\t\t\tone analyzer at a time like the reference's loop (also chosen by -e and --debug);\n"
-           "\t\t\t\tdefault: whole batches of events decoded into pinned memory and analysed together\n";
+           "\t\t\t\tdefault: whole batches of events decoded into pinned memory and analysed together;\n"
+           "\t\t\t\t-e, --debug and --per-event take a single run\n"
+           "Environment: ABUB_TRAIN_ON_GPU=0 trains the runs of a campaign with the host Trainer\n";
 }
-
-static bool eventNameOrderSort(const std::string &a, const std::string &b) { return std::stoi(a) < std::stoi(b); }
 
 // cores this process may use: the affinity mask (taskset, cpuset) AND the cgroup's CPU quota (cpu.max: a container may see
 // 256 cores and be allowed 16 of them) -- the reference's omp_get_max_threads() (AutoBubStart3.cpp:338) sees only the former
@@ -123,11 +126,89 @@ static int mergeParts(const std::string &out_dir, const std::string &run_number,
     return out.good() ? 0 : -1;
 }
 
+// how the different experiments stored their images (AutoBubStart3.cpp:216-245); per run: for 40l-19 the camera count and
+// the frame offset depend on the run ID
+static void runConstants(const std::string &data_series, const std::string &run_number, std::string &imageFormat,
+                         std::string &imageFolder, int &frameOffset, int &numCams)
+{
+    if (data_series == "01l-21" || data_series == "2l-16") {
+        imageFormat = "cam%dimage %u.bmp";
+        imageFolder = "/";
+        frameOffset = 0;
+        numCams = 2;
+    } else if (data_series == "40l-19") {
+        imageFormat = "cam%d_image%u.png";
+        imageFolder = "/Images/";
+        frameOffset = 30;
+        numCams = run_number >= "20200713_7" ? 4 : 2;
+        if (run_number < "20200501_1")
+            frameOffset = 20;
+    } else {
+        imageFormat = "cam%d_image%u.png";
+        imageFolder = "/Images/";
+        frameOffset = 30;
+        numCams = 4;
+    }
+    if (const char *nc = getenv("ABUB_NUM_CAMS")) // synthetic runs with fewer cameras
+        numCams = atoi(nc);
+}
+
+// a run of the command line: its event directory and the series' constants
+static abub::RunSpec runSpec(const std::string &dataLoc, const std::string &data_series, const std::string &run, bool zipped)
+{
+    abub::RunSpec sp;
+    sp.runId = run;
+    sp.eventDir = dataLoc + "/" + run + "/";
+    sp.zipped = zipped;
+    runConstants(data_series, run, sp.imageFormat, sp.imageFolder, sp.frameOffset, sp.numCams);
+    return sp;
+}
+
+// the batched path's options from the command line and the environment
+static abub::BatchedRunOptions batchedOptions(int ngpus, int hostThreads, int decodeThreads, int shardRank, int shardWorld,
+                                              const std::string &mask_dir)
+{
+    abub::BatchedRunOptions bo;
+    bo.ngpus = ngpus;
+    if (const char *d = getenv("ABUB_DEVICE"))
+        bo.firstDevice = atoi(d);
+    bo.hostThreads = hostThreads;
+    bo.decodeThreads = decodeThreads;
+    if (const char *t = getenv("ABUB_DECODE_THREADS"))
+        bo.decodeThreads = std::max(1, atoi(t));
+    if (const char *b = getenv("ABUB_BATCH_MB"))
+        bo.batchBytes = (size_t)std::max(1, atoi(b)) << 20;
+    bo.shardRank = shardRank;
+    bo.shardWorld = shardWorld;
+    bo.maskDir = mask_dir;
+    return bo;
+}
+
+// --run-list FILE: one run ID per line; blank lines and '#' comments are ignored
+static bool readRunList(const std::string &path, std::vector<std::string> &runs)
+{
+    std::ifstream in(path);
+    if (!in)
+        return false;
+    std::string line;
+    while (std::getline(in, line)) {
+        const size_t hash = line.find('#');
+        if (hash != std::string::npos)
+            line.erase(hash);
+        const size_t a = line.find_first_not_of(" \t\r"), b = line.find_last_not_of(" \t\r");
+        if (a != std::string::npos)
+            runs.push_back(line.substr(a, b - a + 1));
+    }
+    return true;
+}
+
 int main(int argc, char **argv)
 {
     std::string dataLoc, run_number, out_dir, mask_dir, data_series;
     int event_user = -1, debug_mode = 0, ngpus = 1, shardRank = 0, shardWorld = 1, mergeN = 0;
     bool zipped = false, mask_check = false, help = argc == 1, perEvent = false;
+    bool haveRun = false, haveList = false; // -r; --runs / --run-list
+    std::vector<std::string> runs;          // of --runs / --run-list, in command-line order
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i], v;
         auto value = [&](std::string &dst) {
@@ -146,8 +227,26 @@ int main(int argc, char **argv)
             mask_check = true;
         else if (is("-d", "--data_dir"))
             value(dataLoc);
-        else if (is("-r", "--run_num") || a == "--run_id")
+        else if (is("-r", "--run_num") || a == "--run_id") {
             value(run_number);
+            haveRun = true;
+        } else if (a == "--runs" || a.rfind("--runs=", 0) == 0) {
+            value(v);
+            haveList = true;
+            for (size_t at = 0; at <= v.size();) {
+                const size_t comma = std::min(v.find(',', at), v.size());
+                if (comma > at)
+                    runs.push_back(v.substr(at, comma - at));
+                at = comma + 1;
+            }
+        } else if (a == "--run-list" || a.rfind("--run-list=", 0) == 0) {
+            value(v);
+            haveList = true;
+            if (!readRunList(v, runs)) {
+                std::cerr << "--run-list: cannot read " << v << std::endl;
+                return -1;
+            }
+        }
         else if (is("-o", "--out_dir"))
             value(out_dir);
         else if (is("-c", "--cam_mask_dir"))
@@ -187,6 +286,52 @@ int main(int argc, char **argv)
         std::cout << usage() << std::endl;
         return 1;
     }
+    if (haveList) {
+        if (haveRun) {
+            std::cerr << "-r cannot be combined with --runs or --run-list" << std::endl;
+            return -1;
+        }
+        if (runs.empty()) {
+            std::cerr << "--runs / --run-list: no run ID given" << std::endl;
+            return -1;
+        }
+        for (size_t i = 0; i < runs.size(); ++i)
+            for (size_t j = 0; j < i; ++j)
+                if (runs[i] == runs[j]) {
+                    std::cerr << "duplicate run ID '" << runs[i] << "' in --runs / --run-list (both would write abub3hs_"
+                              << runs[i] << ".txt)" << std::endl;
+                    return -1;
+                }
+        if (runs.size() > 1) {
+            const char *pe = getenv("ABUB_PER_EVENT"), *bad = event_user >= 0 ? "-e/--event" : debug_mode ? "--debug" : perEvent ? "--per-event"
+                              : pe && atoi(pe) != 0 ? "ABUB_PER_EVENT" : nullptr;
+            if (bad) {
+                std::cerr << bad << " cannot be used with more than one run" << std::endl;
+                return -1;
+            }
+        }
+        if (mergeN > 0) {
+            if (out_dir.empty()) {
+                std::cerr << "--merge needs --out_dir" << std::endl;
+                return -1;
+            }
+            if (out_dir[out_dir.length() - 1] != '/')
+                out_dir += "/";
+            int rc = 0;
+            for (const std::string &r : runs) {
+                const int m = mergeParts(out_dir, r, mergeN);
+                if (m && !rc)
+                    rc = m;
+            }
+            return rc;
+        }
+        // one run with -e / --debug / --per-event: the single-run path
+        const char *pe = getenv("ABUB_PER_EVENT");
+        if (runs.size() == 1 && (event_user >= 0 || debug_mode || perEvent || (pe && atoi(pe) != 0))) {
+            run_number = runs[0];
+            runs.clear();
+        }
+    }
     if (mergeN > 0) {
         if (run_number.empty() || out_dir.empty()) {
             std::cerr << "--merge needs --run_id and --out_dir" << std::endl;
@@ -196,7 +341,7 @@ int main(int argc, char **argv)
             out_dir += "/";
         return mergeParts(out_dir, run_number, mergeN);
     }
-    if (dataLoc.empty() || run_number.empty() || out_dir.empty()) {
+    if (dataLoc.empty() || (run_number.empty() && runs.empty()) || out_dir.empty()) {
         std::cerr << "Insufficient required arguments; use \"autobub3hs -h\" to view required arguments" << std::endl;
         return -1;
     }
@@ -209,33 +354,13 @@ int main(int argc, char **argv)
     else if (!mask_check && mask_dir == "")
         std::cout << "Not performing mask check on this run." << std::endl;
 
-    std::string eventDir = dataLoc + "/" + run_number + "/";
     if (out_dir[out_dir.length() - 1] != '/')
         out_dir += "/";
+    std::string eventDir = dataLoc + "/" + run_number + "/";
 
-    // how the different experiments stored their images (AutoBubStart3.cpp:216-245)
     std::string imageFormat, imageFolder;
     int frameOffset, numCams;
-    if (data_series == "01l-21" || data_series == "2l-16") {
-        imageFormat = "cam%dimage %u.bmp";
-        imageFolder = "/";
-        frameOffset = 0;
-        numCams = 2;
-    } else if (data_series == "40l-19") {
-        imageFormat = "cam%d_image%u.png";
-        imageFolder = "/Images/";
-        frameOffset = 30;
-        numCams = run_number >= "20200713_7" ? 4 : 2;
-        if (run_number < "20200501_1")
-            frameOffset = 20;
-    } else {
-        imageFormat = "cam%d_image%u.png";
-        imageFolder = "/Images/";
-        frameOffset = 30;
-        numCams = 4;
-    }
-    if (const char *nc = getenv("ABUB_NUM_CAMS")) // synthetic runs with fewer cameras
-        numCams = atoi(nc);
+    runConstants(data_series, run_number, imageFormat, imageFolder, frameOffset, numCams);
 
     // Threads.  The reference runs omp_get_max_threads() events at once (AutoBubStart3.cpp:338-342): the per-event loop and
     // the decoders of the batched path take every core this process may use (at most 128); the host stages of the batched
@@ -249,63 +374,40 @@ int main(int argc, char **argv)
     if (shardWorld > 1) // every shard writes its own part file (--merge N assembles the run's file)
         OutputWriter::PartSuffix = ".part" + std::to_string(shardRank) + "of" + std::to_string(shardWorld);
 
-    OutputWriter *header = new OutputWriter(out_dir, run_number, frameOffset, numCams);
-    header->writeHeader();
+    // ---- a campaign: every run of --runs / --run-list in this process (abub::RunCampaign) ------------------------------
+    if (!runs.empty()) {
+        std::vector<abub::RunSpec> specs;
+        for (const std::string &r : runs)
+            specs.push_back(runSpec(dataLoc, data_series, r, zipped));
+        abub::BatchedRunOptions bo = batchedOptions(ngpus, hostThreads, decodeThreads, shardRank, shardWorld, mask_dir);
+        bo.outDir = out_dir;
+        bo.perEventThreads = nthreads;
+        if (const char *t = getenv("ABUB_TRAIN_ON_GPU"))
+            bo.trainOnGpu = atoi(t) != 0;
+        abub::CampaignStats cs;
+        const int rc = abub::RunCampaign(specs, bo, &cs);
+        std::string notRun;
+        for (const std::string &r : cs.notRun)
+            notRun += (notRun.empty() ? "" : ",") + r;
+        printf("campaign: %d runs, %lld frames, %.2f s, %.1f frames/s; training %.2f s (exposed %.2f s); pipelines built %d; "
+               "not run: %s\n",
+               cs.runs, cs.frames, cs.total_s, cs.total_s > 0 ? cs.frames / cs.total_s : 0.0, cs.train_s, cs.trainExposed_s,
+               cs.pipelinesBuilt, notRun.empty() ? "none" : notRun.c_str());
+        return rc;
+    }
 
-    std::vector<std::string> EventList;
-    Parser *FileParser = nullptr;
-    try {
-        if (zipped)
-            FileParser = new ZipParser(eventDir, imageFolder, imageFormat);
-        else
-            FileParser = new RawParser(eventDir, imageFolder, imageFormat);
-        FileParser->GetEventDirLists(EventList);
-    } catch (...) {
-        std::cout << "Failed to read the images from run " << run_number << ". Autobub cannot continue.\n";
-        if (shardRank == 0) { // (one block for the run: it goes into part 0 of a sharded run)
-            for (int icam = 0; icam < numCams; icam++)
-                header->stageCameraOutputError(icam, -5, -1);
-            header->writeCameraOutput();
-        }
-        return -5;
-    }
-    std::sort(EventList.begin(), EventList.end(), eventNameOrderSort);
-
-    printf("**Starting training. AutoBub is in learn mode**\n");
-    std::vector<Trainer *> Trainers;
-    for (int icam = 0; icam < numCams; icam++)
-        Trainers.push_back(new Trainer(icam, EventList, eventDir, imageFormat, imageFolder, FileParser->clone(), debug_mode / 100));
-    {
-        std::vector<std::thread> th; // one thread per camera, like `#pragma omp parallel for` (:304-307)
-        for (int icam = 0; icam < numCams; icam++)
-            th.emplace_back([&, icam]() {
-                try {
-                    Trainers[icam]->MakeAvgSigmaImage(false);
-                } catch (std::exception &e) {
-                    std::cout << e.what() << '\n';
-                    Trainers[icam]->StatusCode = -7;
-                }
-            });
-        for (auto &t : th)
-            t.join();
-    }
-    bool succeeded = true;
-    for (Trainer *t : Trainers)
-        if (t->StatusCode)
-            succeeded = false;
-    if (!succeeded) {
-        std::cout << "Failed to train on images from run " << run_number << ". Autobub cannot continue.\n";
-        for (size_t evi = 0; evi < EventList.size(); evi++) {
-            if (shardWorld > 1 && (int)(evi % (size_t)shardWorld) != shardRank)
-                continue;
-            for (int icam = 0; icam < numCams; icam++)
-                header->stageCameraOutputError(icam, -7, atoi(EventList[evi].c_str()));
-            header->writeCameraOutput();
-        }
-        return -7;
-    }
-    printf("***Training complete. AutoBub is now in detect mode***\n");
-    delete header;
+    // header, event list (-5 rows if the run cannot be read), training (-7 rows if a camera fails): the campaign's steps
+    abub::RunSpec spec = runSpec(dataLoc, data_series, run_number, zipped);
+    abub::BatchedRunOptions po = batchedOptions(ngpus, hostThreads, decodeThreads, shardRank, shardWorld, mask_dir);
+    po.outDir = out_dir;
+    po.trainOnGpu = 0; // (a single run trains through the host Trainer, as the reference does)
+    abub::PreparedRun prep = abub::PrepareRun(spec, po, debug_mode / 100, nullptr, false);
+    abub::CommitRun(spec, po, prep);
+    if (prep.rc)
+        return prep.rc;
+    Parser *FileParser = prep.parser.get();
+    const std::vector<std::string> &EventList = prep.events;
+    const std::vector<Trainer *> &Trainers = prep.trainers;
 
     // ---- batched detect (default): every event of a batch decoded once into pinned memory, one set of launches per
     // batch, output in event order.  The per-event loop below stays for -e / --debug / --per-event and as the
@@ -313,19 +415,7 @@ int main(int argc, char **argv)
     if (const char *e = getenv("ABUB_PER_EVENT"))
         perEvent = perEvent || atoi(e) != 0;
     if (!perEvent && event_user < 0 && debug_mode == 0) {
-        abub::BatchedRunOptions bo;
-        bo.ngpus = ngpus;
-        if (const char *d = getenv("ABUB_DEVICE"))
-            bo.firstDevice = atoi(d);
-        bo.hostThreads = hostThreads;
-        bo.decodeThreads = decodeThreads;
-        if (const char *t = getenv("ABUB_DECODE_THREADS"))
-            bo.decodeThreads = std::max(1, atoi(t));
-        if (const char *b = getenv("ABUB_BATCH_MB"))
-            bo.batchBytes = (size_t)std::max(1, atoi(b)) << 20;
-        bo.shardRank = shardRank;
-        bo.shardWorld = shardWorld;
-        bo.maskDir = mask_dir;
+        abub::BatchedRunOptions bo = batchedOptions(ngpus, hostThreads, decodeThreads, shardRank, shardWorld, mask_dir);
         abub::BatchedRunStats bs;
         std::string why;
         int rc = 1;
@@ -336,71 +426,17 @@ int main(int argc, char **argv)
             return -6;
         }
         if (rc == 0) {
-            printf("batched detect: %d events in %d batches of <= %d on %d GPU(s), %lld frames %dx%d decoded (%lld on the GPU, %lld on "
-                   "host threads; %lld undecodable), %.2f s total (list %.2f, read/decode %.2f, upload+GPU+host stages %.2f of which "
-                   "GPU decode %.2f, write %.2f) = %.1f frames/s ingest-inclusive\n",
-                   bs.events, bs.batches, bs.eventsPerBatch, bs.gpus, bs.frames, bs.W, bs.H, bs.framesGpuDecoded, bs.framesHostDecoded,
-                   bs.framesFailed, bs.total_s, bs.list_s, bs.decode_s, bs.gpu_s, bs.gpudecode_s, bs.write_s,
-                   bs.total_s > 0 ? (bs.frames + bs.framesFailed) / bs.total_s : 0.0);
+            abub::PrintBatchedLine(bs);
             printf("run complete.\n");
-            for (Trainer *t : Trainers)
-                delete t;
-            delete FileParser;
             printf("AutoBub done analyzing this run. Thank you.\n");
             return 0;
         }
         std::cout << "batched detect not used (" << why << "): falling back to the per-event loop" << std::endl;
     }
 
-    // events in parallel, output appended in event order (the `ordered` clause :380-383)
-    std::cout << "Total threads: " << nthreads << std::endl;
-    std::atomic<int> next{0};
-    std::mutex turnMutex;
-    std::condition_variable turnCv;
-    int turn = 0;
-    auto worker = [&]() {
-        for (;;) {
-            const int evi = next.fetch_add(1);
-            if (evi >= (int)EventList.size())
-                break;
-            const bool skip = (event_user >= 0 && evi != event_user) // compares the loop index, like upstream (:350)
-                              || (shardWorld > 1 && evi % shardWorld != shardRank);
-            OutputWriter *out = nullptr;
-            std::vector<AnalyzerUnit *> Analyzers;
-            if (!skip) {
-                out = new OutputWriter(out_dir, run_number, frameOffset, numCams);
-                const std::string imageDir = eventDir + EventList[evi] + "/Images/";
-                const int actualEventNumber = atoi(EventList[evi].c_str());
-                for (int icam = 0; icam < numCams; icam++) {
-                    Analyzers.push_back(new L3Localizer(EventList[evi], imageDir, icam, debug_mode / 100 ? false : true,
-                                                        &Trainers[icam], mask_dir, FileParser->clone()));
-                    abub::AnyCamAnalysis(Analyzers[icam], icam, debug_mode % 10 ? false : true, out, out_dir, actualEventNumber);
-                }
-            }
-            {
-                std::unique_lock<std::mutex> lock(turnMutex);
-                turnCv.wait(lock, [&] { return turn == evi; });
-                if (out)
-                    out->writeCameraOutput();
-                ++turn;
-            }
-            turnCv.notify_all();
-            delete out;
-            for (AnalyzerUnit *A : Analyzers)
-                delete A;
-        }
-    };
-    {
-        std::vector<std::thread> th;
-        for (int t = 0; t < nthreads; ++t)
-            th.emplace_back(worker);
-        for (auto &t : th)
-            t.join();
-    }
+    abub::RunPerEvent(FileParser, EventList, Trainers, numCams, eventDir, out_dir, run_number, frameOffset, mask_dir, nthreads,
+                      event_user, debug_mode, shardRank, shardWorld);
     printf("run complete.\n");
-    for (Trainer *t : Trainers)
-        delete t;
-    delete FileParser;
     printf("AutoBub done analyzing this run. Thank you.\n");
     return 0;
 }

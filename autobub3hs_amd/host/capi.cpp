@@ -19,6 +19,7 @@
 #include "ParseFolder/RawParser.hpp"
 #include "ParseFolder/ZipParser.hpp"
 #include "devctx.hpp"
+#include "devtrain.hpp"
 #include "driver.hpp"
 #include "hostlogic.hpp"
 #include "pngwalk.hpp"
@@ -257,6 +258,55 @@ int abh_train(void *r, int cam, int *status, int *tss, uint8_t *mu_out, uint8_t 
             std::memcpy(sigma_out, t->TrainedSigmaImage.data, t->TrainedSigmaImage.total());
         }
         return 0;
+    } catch (std::exception &e) {
+        run->error = e.what();
+        return -1;
+    }
+}
+
+// Every camera 0..ncams-1 trained in one pass on the device (TrainOnDevice) over every event of the run; per camera c:
+// status[c], tss[c] and, where it trained, its mu / sigma at mu_out + c * cap, sigma_out + c * cap (cap bytes each).  The
+// Run's Trainers are replaced.  Returns 0 (trained on the device), 1 (TrainOnDevice declined the run: the host Trainer
+// trained it), -1 on errors.  stats (may be NULL): [frames decoded by the GPU decoder, by host threads, decode launches,
+// seconds].
+int abh_train_device(void *r, int ncams, int *status, int *tss, uint8_t *mu_out, uint8_t *sigma_out, int cap, double *stats)
+{
+    Run *run = (Run *)r;
+    try {
+        std::vector<std::string> events;
+        run->parser->GetEventDirLists(events);
+        std::sort(events.begin(), events.end(), [](const std::string &a, const std::string &b) { return std::stoi(a) < std::stoi(b); });
+        std::vector<Trainer *> trainers;
+        for (int c = 0; c < ncams; ++c) {
+            delete run->trainers[c];
+            run->trainers[c] = new Trainer(c, events, "", "cam%d_image%u.png", "", run->parser->clone(), false);
+            trainers.push_back(run->trainers[c]);
+        }
+        abub::DeviceTrainOptions to;
+        std::string why;
+        abub::DeviceTrainStats st;
+        const int rc = abub::TrainOnDevice(run->parser, events, trainers, to, &st, &why);
+        if (stats) {
+            stats[0] = (double)st.framesGpuDecoded;
+            stats[1] = (double)st.framesHostDecoded;
+            stats[2] = (double)st.decodeLaunches;
+            stats[3] = st.total_s;
+        }
+        if (rc != 0) {
+            run->error = why;
+            for (Trainer *t : trainers)
+                t->MakeAvgSigmaImage(false);
+        }
+        for (int c = 0; c < ncams; ++c) {
+            Trainer *t = trainers[c];
+            status[c] = t->StatusCode;
+            tss[c] = t->TrainingSetSize;
+            if (t->StatusCode == 0 && mu_out && sigma_out && (int)t->TrainedAvgImage.total() <= cap) {
+                std::memcpy(mu_out + (size_t)c * cap, t->TrainedAvgImage.data, t->TrainedAvgImage.total());
+                std::memcpy(sigma_out + (size_t)c * cap, t->TrainedSigmaImage.data, t->TrainedSigmaImage.total());
+            }
+        }
+        return rc != 0 ? 1 : 0;
     } catch (std::exception &e) {
         run->error = e.what();
         return -1;

@@ -1,0 +1,239 @@
+// framefiles.hpp -- frames read as FILES for the GPU PNG decoder (abub_png_decode_dev), shared by the batched detect path
+// (runbatch.cpp) and device training (devtrain.cpp).  A host thread reads each file and walks its chunks (pngWalk); a
+// file the walk refuses (BMP, 16-bit, colour, interlaced, another size) gets the host decoder's answer at once, and so
+// does a frame the kernel later returns a nonzero status for.  Internal to the host library.
+#ifndef ABUB3HS_FRAMEFILES_HPP
+#define ABUB3HS_FRAMEFILES_HPP
+
+#include <algorithm>
+#include <atomic>
+#include <cstdint>
+#include <cstring>
+#include <exception>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <thread>
+#include <utility>
+#include <vector>
+
+#include "ParseFolder/Parser.hpp"
+#include "abub_hip.h"
+#include "devctx.hpp"
+#include "holders.hpp"
+#include "pipeline.hpp"
+#include "pngwalk.hpp"
+
+namespace abub {
+
+// fn(parser, i) for every i < n on up to `nthreads` threads, each with its own clone of `parser`.  The first exception is
+// re-thrown once every thread has been joined (the others stop at their next task).
+template <class Fn>
+void forEachTask(Parser *parser, int nthreads, size_t n, const Fn &fn)
+{
+    std::atomic<size_t> next{0};
+    std::mutex errMu;
+    std::exception_ptr err;
+    std::vector<std::thread> th;
+    for (int t = 0; t < std::max(1, (int)std::min<size_t>(nthreads, n)); ++t)
+        th.emplace_back([&]() {
+            try {
+                std::unique_ptr<Parser> p(parser->clone());
+                for (size_t i; (i = next.fetch_add(1)) < n;)
+                    fn(*p, i);
+            } catch (...) {
+                std::lock_guard<std::mutex> lock(errMu);
+                if (!err)
+                    err = std::current_exception();
+                next = n;
+            }
+        });
+    for (auto &t : th)
+        t.join();
+    if (err)
+        std::rethrow_exception(err);
+}
+
+// One frame to be read: where it goes is decided by the caller (s, f); `state` says what became of it
+struct FileTask {
+    enum { Gpu = 0, HostDecoded = 1, Bad = 2, Other = 3 }; // Other: not a file task (the caller's own work)
+    int s = 0, f = 0;
+    long long size = 0;
+    size_t off = 0; // in the pinned file buffer
+    int state = Other;
+    bool read = false; // the file's bytes are in the buffer (a Bad frame may still have been read)
+    PngInfo info;
+    std::vector<uint8_t> pix;
+};
+
+// The descriptors of one decode launch, and the frames a reading thread decoded itself
+struct FileDescs {
+    size_t bytes = 0, zbytes = 0;           // of the files; of the decoder's stream buffer
+    std::vector<abub_png_frame> desc;       // the frames the GPU decodes
+    std::vector<std::pair<int, int>> where; // (s, f) of desc[i]
+    std::vector<uint32_t> fileOff, fileLen; // of desc[i] inside the file buffer
+    std::vector<abub_png_seg> segs;
+    std::vector<uint8_t> luts;              // 256 bytes each
+    std::vector<std::vector<uint8_t>> hostPix;
+    std::vector<std::pair<int, int>> hostWhere;
+    long long bad = 0;
+};
+
+// The file's size and its place in the buffer (`total` grows by the file rounded up to 16 bytes); Bad if the parser
+// cannot hand it out
+inline void planFileTask(Parser &sizer, const std::string &ev, const std::string &name, FileTask &t, size_t &total)
+{
+    t.size = sizer.GetImageFileSize(ev, name);
+    t.state = (t.size > 0 && t.size < ((long long)1 << 30)) ? FileTask::Gpu : FileTask::Bad;
+    t.off = total;
+    if (t.state == FileTask::Gpu)
+        total += ((size_t)t.size + 15) & ~(size_t)15;
+}
+
+// On a pool thread: the file into files + t.off, walked for the W x H GPU decoder, else decoded here
+inline void readFileTask(Parser &p, const std::string &ev, const std::string &name, FileTask &t, uint8_t *files, int W, int H)
+{
+    if (t.state != FileTask::Gpu)
+        return;
+    uint8_t *dst = files + t.off;
+    long long got = -1;
+    try {
+        got = p.ReadImageFile(ev, name, dst, (size_t)t.size);
+    } catch (...) {
+        got = -1;
+    }
+    if (got != t.size) {
+        t.state = FileTask::Bad;
+        return;
+    }
+    t.read = true;
+    try {
+        if (!pngWalk(dst, (size_t)t.size, W, H, t.info)) {
+            // not a file for the GPU decoder (BMP, 16-bit, colour, interlaced, another size): the host decoder's answer
+            t.pix.resize((size_t)W * H);
+            t.state = cv::imdecodeInto(dst, (size_t)t.size, t.pix.data(), W, H) ? FileTask::HostDecoded : FileTask::Bad;
+        }
+    } catch (...) { // (an allocation that fails inside a pool thread must not end the batch)
+        t.state = FileTask::Bad;
+    }
+}
+
+// The descriptors of the tasks' Gpu frames, in task order; dstOf(s, f): byte offset of the decoded frame from the output
+// (tasks [first, last); the files of every task are in one buffer of totalFileBytes)
+template <class DstOf>
+void buildFileDescs(FileTask *first, FileTask *last, size_t totalFileBytes, FileDescs &r, const DstOf &dstOf)
+{
+    r.bytes = totalFileBytes + 16;
+    size_t zoff = 0;
+    for (FileTask *tp = first; tp != last; ++tp) {
+        FileTask &t = *tp;
+        if (t.state == FileTask::Other)
+            continue;
+        if (t.state == FileTask::Bad) {
+            ++r.bad;
+            continue;
+        }
+        if (t.state == FileTask::HostDecoded) {
+            r.hostPix.push_back(std::move(t.pix));
+            r.hostWhere.emplace_back(t.s, t.f);
+            continue;
+        }
+        abub_png_frame d;
+        d.seg_begin = (uint32_t)r.segs.size();
+        d.seg_count = (uint32_t)t.info.segs.size();
+        d.zoff = (uint32_t)zoff;
+        d.zlen = (uint32_t)t.info.zlen;
+        d.lut = 0xffffffffu;
+        d.reserved = 0;
+        d.dst = dstOf(t.s, t.f);
+        if (t.info.palette) { // (the frames of a run share their palette: look for the table among those already kept)
+            size_t nl = r.luts.size() / 256, l = 0;
+            for (; l < nl; ++l)
+                if (!memcmp(&r.luts[l * 256], t.info.lut, 256))
+                    break;
+            if (l == nl)
+                r.luts.insert(r.luts.end(), t.info.lut, t.info.lut + 256);
+            d.lut = (uint32_t)l;
+        }
+        for (const abub_png_seg &sg : t.info.segs)
+            r.segs.push_back(abub_png_seg{(uint32_t)(t.off + sg.off), sg.len});
+        zoff += (((size_t)d.zlen + 15) & ~(size_t)15) + 16;
+        r.desc.push_back(d);
+        r.where.emplace_back(t.s, t.f);
+        r.fileOff.push_back((uint32_t)t.off);
+        r.fileLen.push_back((uint32_t)t.size);
+    }
+    r.zbytes = zoff + 16;
+    if (r.bytes >= ((size_t)1 << 32) || r.zbytes >= ((size_t)1 << 32))
+        throw std::runtime_error("a batch of more than 4 GB of files (lower the batch size)");
+}
+
+// The decoder's scratch, kept from one launch to the next
+struct PngScratch {
+    DeviceBuffer z, raw, luts, desc, segs, status;
+    PinnedBuffer h_status;
+};
+
+// One abub_png_decode_dev launch over r's frames into `out` (out_bytes), the statuses copied back into sc.h_status; queued
+// on `stream`, not waited for.  The files are already in d_files.
+inline void launchFileDecode(const FileDescs &r, const uint8_t *d_files, int W, int H, uint8_t *out, size_t out_bytes,
+                             PngScratch &sc, hipStream_t stream)
+{
+    const int nf = (int)r.desc.size();
+    if (!nf)
+        return;
+    sc.z.grow(r.zbytes);
+    sc.raw.grow((size_t)nf * abub_png_raw_stride(W, H));
+    sc.desc.grow((size_t)nf * sizeof(abub_png_frame));
+    sc.segs.grow(r.segs.size() * sizeof(abub_png_seg) + 8);
+    sc.luts.grow(r.luts.size() + 256);
+    sc.status.grow((size_t)nf * sizeof(int32_t));
+    if (sc.h_status.capacity() < (size_t)nf * sizeof(int32_t))
+        sc.h_status.allocate((size_t)nf * sizeof(int32_t) + 64);
+    HIPOK(hipMemcpyAsync(sc.desc.get(), r.desc.data(), (size_t)nf * sizeof(abub_png_frame), hipMemcpyHostToDevice, stream));
+    HIPOK(hipMemcpyAsync(sc.segs.get(), r.segs.data(), r.segs.size() * sizeof(abub_png_seg), hipMemcpyHostToDevice, stream));
+    if (!r.luts.empty())
+        HIPOK(hipMemcpyAsync(sc.luts.get(), r.luts.data(), r.luts.size(), hipMemcpyHostToDevice, stream));
+    check(abub_png_decode_dev(d_files, r.bytes, (const abub_png_frame *)sc.desc.get(), nf, (const abub_png_seg *)sc.segs.get(),
+                              (int)r.segs.size(), sc.luts.get(), (int)(r.luts.size() / 256), W, H, sc.z.get(), sc.z.capacity(),
+                              sc.raw.get(), sc.raw.capacity(), out, out_bytes, (int32_t *)sc.status.get(), stream),
+          "abub_png_decode_dev");
+    HIPOK(hipMemcpyAsync(sc.h_status.get(), sc.status.get(), (size_t)nf * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+}
+
+// After the launch above has been waited for: a frame the kernels refused takes the host decoder's answer (the same image,
+// or the same failure), and the reading threads' own frames are uploaded.  ok(s, f) is called for every frame that is in
+// place; gpuOut(s, f) for those of the kernel; hostOffset(s, f): byte offset of the frame from `out`.
+template <class HostOffset, class Ok>
+void finishFileDecode(FileDescs &r, const uint8_t *h_files, const int32_t *status, uint8_t *out, int W, int H,
+                      hipStream_t stream, const HostOffset &hostOffset, const Ok &ok, long long &onGpu, long long &onHost)
+{
+    const size_t P = (size_t)W * H;
+    std::vector<uint8_t> pix;
+    for (size_t i = 0; i < r.desc.size(); ++i) {
+        uint8_t *dst = out + r.desc[i].dst;
+        if (status[i] == 0) {
+            ok(r.where[i].first, r.where[i].second);
+            ++onGpu;
+            continue;
+        }
+        pix.resize(P);
+        if (cv::imdecodeInto(h_files + r.fileOff[i], r.fileLen[i], pix.data(), W, H)) {
+            HIPOK(hipMemcpy(dst, pix.data(), P, hipMemcpyHostToDevice));
+            ok(r.where[i].first, r.where[i].second);
+            ++onHost;
+        } else {
+            HIPOK(hipMemsetAsync(dst, 0, P, stream)); // (a refused frame may be half written)
+            ++r.bad;
+        }
+    }
+    for (size_t i = 0; i < r.hostPix.size(); ++i) {
+        HIPOK(hipMemcpy(out + hostOffset(r.hostWhere[i].first, r.hostWhere[i].second), r.hostPix[i].data(), P,
+                        hipMemcpyHostToDevice));
+        ok(r.hostWhere[i].first, r.hostWhere[i].second);
+        ++onHost;
+    }
+}
+
+} // namespace abub
+#endif

@@ -1649,6 +1649,20 @@ RunPipelinePtr newRunPipeline(int device, int W, int H, int F, int E, int C, con
     return RunPipelinePtr(new RunPipeline(device, W, H, F, E, C, tss, nthreads, maskDir));
 }
 void setSigmaRaw(RunPipeline &p, const uint8_t *d_sigma) { p.d_sigmaRaw = d_sigma; }
+bool setTrainingSetSizes(RunPipeline &p, const int *tss)
+{
+    int stride = tss[0] < 6 ? 1 : 2; // (as the constructor decides it)
+    for (int c = 1; c < p.C; ++c)
+        if ((tss[c] < 6 ? 1 : 2) != stride)
+            stride = 0;
+    if (stride != p.chainStride)
+        return false;
+    for (int c = 0; c < p.C; ++c) {
+        p.tss[c] = tss[c];
+        p.trainers[c]->TrainingSetSize = tss[c];
+    }
+    return true;
+}
 void setStackMeta(RunPipeline &p, std::vector<StackMeta> &&meta) { p.setStackMeta(std::move(meta)); }
 void run(RunPipeline &p, const uint8_t *d_frames, const uint8_t *d_mu, const uint8_t *d_sigma6, hipStream_t stream)
 {

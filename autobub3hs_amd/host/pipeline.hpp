@@ -45,6 +45,9 @@ using RunPipelinePtr = std::unique_ptr<RunPipeline, RunPipelineDelete>;
 // a pipeline for batches of E events of C cameras, F frames of W x H each, on `device`
 RunPipelinePtr newRunPipeline(int device, int W, int H, int F, int E, int C, const int *tss, int nthreads,
                               const char *maskDir);
+// a new model's training-set sizes (one per camera) for the runs to come; false, and nothing changed, when they would
+// change the trigger search's frame offset the pipeline was built for (a new pipeline is needed then)
+bool setTrainingSetSizes(RunPipeline &p, const int *tss);
 // sigma (not 6 * sigma) of every camera, for the stacks that need the one-at-a-time path
 void setSigmaRaw(RunPipeline &p, const uint8_t *d_sigma);
 // the next run's ids, frame names and decode flags, one entry per stack

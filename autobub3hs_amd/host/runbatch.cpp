@@ -13,6 +13,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <exception>
+#include <future>
+#include <iostream>
 #include <memory>
 #include <mutex>
 #include <stdexcept>
@@ -21,9 +23,15 @@
 #include <vector>
 
 #include "AlgorithmTraining/Trainer.hpp"
+#include "BubbleLocalizer/L3Localizer.hpp"
 #include "ParseFolder/Parser.hpp"
+#include "ParseFolder/RawParser.hpp"
+#include "ParseFolder/ZipParser.hpp"
 #include "PICOFormatWriter/PICOFormatWriterV4.hpp"
 #include "devctx.hpp"
+#include "devtrain.hpp"
+#include "driver.hpp"
+#include "framefiles.hpp"
 #include "holders.hpp"
 #include "pipeline.hpp"
 #include "pngwalk.hpp"
@@ -31,34 +39,6 @@
 
 namespace abub {
 namespace {
-
-// fn(parser, i) for every i < n on up to `nthreads` threads, each with its own clone of `parser`.  The first exception is
-// re-thrown once every thread has been joined (the others stop at their next task).
-template <class Fn>
-void forEachTask(Parser *parser, int nthreads, size_t n, const Fn &fn)
-{
-    std::atomic<size_t> next{0};
-    std::mutex errMu;
-    std::exception_ptr err;
-    std::vector<std::thread> th;
-    for (int t = 0; t < std::max(1, (int)std::min<size_t>(nthreads, n)); ++t)
-        th.emplace_back([&]() {
-            try {
-                std::unique_ptr<Parser> p(parser->clone());
-                for (size_t i; (i = next.fetch_add(1)) < n;)
-                    fn(*p, i);
-            } catch (...) {
-                std::lock_guard<std::mutex> lock(errMu);
-                if (!err)
-                    err = std::current_exception();
-                next = n;
-            }
-        });
-    for (auto &t : th)
-        t.join();
-    if (err)
-        std::rethrow_exception(err);
-}
 
 // Frame f of stack m decoded by the host into its slot (W x H bytes at dst), or the slot zeroed: a frame that does not
 // decode (missing, undecodable, of another size) would otherwise keep the bytes of an earlier batch or half a decode.
@@ -88,25 +68,44 @@ struct Slot {
     std::exception_ptr err;    // of the look-ahead thread that read the batch
     struct Read {
         std::vector<StackMeta> meta;
-        size_t bytes = 0, zbytes = 0;           // of the files; of the decoder's stream buffer
-        std::vector<abub_png_frame> desc;       // the frames the GPU decodes
-        std::vector<std::pair<int, int>> where; // (stack, frame) of desc[i]
-        std::vector<uint32_t> fileOff, fileLen; // of desc[i] inside h_files
-        std::vector<abub_png_seg> segs;
-        std::vector<uint8_t> luts;              // 256 bytes each
-        // frames of the GPU share a reading thread decoded (files the GPU path does not take): pixels + (stack, frame)
-        std::vector<std::vector<uint8_t>> hostPix;
-        std::vector<std::pair<int, int>> hostWhere;
+        FileDescs files;       // the frames the GPU decodes; those of the GPU share a reading thread decoded
         double ms = 0;
-        long long bad = 0, hostGood = 0;
+        long long hostGood = 0;
     } r;
 };
 
-} // namespace
+// A worker's buffers, streams and pipelines, kept from one run to the next (RunCampaign) or for one run (RunBatched).
+// Declaration order: the pipelines go first, then the streams (they finish their work), then the buffers.
+struct WorkerCache {
+    Slot slots[2];
+    DeviceBuffer d_model; // mu | sigma | sigma6
+    PngScratch png;       // the GPU decoder's scratch
+    Stream copyStream, upStream;
+    struct Pipe {
+        std::vector<long long> key;
+        RunPipelinePtr pipe;
+    };
+    std::vector<Pipe> pipes; // the last two shapes (a run of another size does not throw away the campaign's pipeline)
+};
 
-int RunBatched(Parser *parser, const std::vector<std::string> &EventList, const std::vector<Trainer *> &Trainers,
-               int numCams, const std::string &out_dir, const std::string &run_number, int frameOffset,
-               const BatchedRunOptions &opt, BatchedRunStats *stats, std::string *why)
+// the worker caches of a campaign (one per GPU) and how many pipelines they built
+struct Workers {
+    std::vector<std::unique_ptr<WorkerCache>> w;
+    int pipelinesBuilt = 0;
+};
+
+// at least `bytes`, allocated exactly when it has to grow (pinned memory is page-locked, every byte costs)
+template <bool Pinned>
+void fit(Buffer<Pinned> &b, size_t bytes)
+{
+    if (b.capacity() < bytes)
+        b.allocate(bytes);
+}
+
+// RunBatched on the workers `ws` (their buffers and pipelines are reused where they fit, and kept for the next run)
+int runBatchedOn(Workers &ws, Parser *parser, const std::vector<std::string> &EventList, const std::vector<Trainer *> &Trainers,
+                 int numCams, const std::string &out_dir, const std::string &run_number, int frameOffset,
+                 const BatchedRunOptions &opt, BatchedRunStats *stats, std::string *why)
 {
     const double tAll = nowMs();
     auto refuse = [&](const char *msg) {
@@ -223,6 +222,8 @@ int RunBatched(Parser *parser, const std::vector<std::string> &EventList, const 
         throw std::runtime_error("RunBatched: no GPU");
     const int ngpus = std::max(1, std::min(opt.ngpus, nb));
     st.gpus = ngpus;
+    while ((int)ws.w.size() < ngpus)
+        ws.w.emplace_back(new WorkerCache());
     st.batches = nb;
     st.eventsPerBatch = G;
 
@@ -241,15 +242,7 @@ int RunBatched(Parser *parser, const std::vector<std::string> &EventList, const 
         Slot::Read &r = sl.r;
         r = Slot::Read();
         r.meta.assign((size_t)G * C, StackMeta());
-        struct Task {
-            int s, f;
-            long long size = 0;
-            size_t off = 0;
-            int state; // 0 = a file for the GPU, 1 = decoded here, 2 = missing / undecodable, 3 = host share
-            PngInfo info;
-            std::vector<uint8_t> pix;
-        };
-        std::vector<Task> tasks; // (in stack order: the GPU's files are read first, its work can start before the host's is done)
+        std::vector<FileTask> tasks; // (in stack order: the GPU's files are read first, its work can start before the host's is done)
         std::unique_ptr<Parser> sizer(Ggpu ? parser->clone() : nullptr);
         size_t total = 0;
         for (int k = 0; k < G; ++k)
@@ -263,112 +256,45 @@ int RunBatched(Parser *parser, const std::vector<std::string> &EventList, const 
                 m.names = lists[e0 + k][c];
                 m.ok.assign(m.names.size(), 0);
                 for (int f = 0; f < (int)m.names.size(); ++f) {
-                    Task t;
+                    FileTask t;
                     t.s = k * C + c;
                     t.f = f;
-                    t.state = 3;
-                    if (k < Ggpu) {
-                        t.size = sizer->GetImageFileSize(m.eventID, m.names[f]);
-                        t.state = (t.size > 0 && t.size < ((long long)1 << 30)) ? 0 : 2;
-                        t.off = total;
-                        if (t.state == 0)
-                            total += ((size_t)t.size + 15) & ~(size_t)15;
-                    }
+                    if (k < Ggpu)
+                        planFileTask(*sizer, m.eventID, m.names[f], t, total);
                     tasks.push_back(std::move(t));
                 }
             }
-        r.bytes = total + 16;
         if (Ggpu)
-            sl.h_files.grow(r.bytes);
+            sl.h_files.grow(total + 16);
         std::atomic<long long> hostGood{0}, hostBad{0};
         forEachTask(parser, nthreads, tasks.size(), [&](Parser &p, size_t i) {
-            Task &t = tasks[i];
-            if (t.state == 3) { // the host share: straight into the pinned slab
+            FileTask &t = tasks[i];
+            StackMeta &m = r.meta[t.s];
+            if (t.state == FileTask::Other) { // the host share: straight into the pinned slab
                 uint8_t *dst = sl.h_frames.get() + ((size_t)(t.s - Ggpu * C) * Fmax + t.f) * P;
-                ++(decodeFrame(p, r.meta[t.s], t.f, dst, W, H) ? hostGood : hostBad);
+                ++(decodeFrame(p, m, t.f, dst, W, H) ? hostGood : hostBad);
                 return;
             }
-            if (t.state != 0)
-                return;
-            uint8_t *dst = sl.h_files.get() + t.off;
-            long long got = -1;
-            try {
-                got = p.ReadImageFile(r.meta[t.s].eventID, r.meta[t.s].names[t.f], dst, (size_t)t.size);
-            } catch (...) {
-                got = -1;
-            }
-            if (got != t.size) {
-                t.state = 2;
-                return;
-            }
-            try {
-                if (!pngWalk(dst, (size_t)t.size, W, H, t.info)) {
-                    // not a file for the GPU decoder (BMP, 16-bit, colour, interlaced, another size): the host decoder's answer
-                    t.pix.resize(P);
-                    t.state = cv::imdecodeInto(dst, (size_t)t.size, t.pix.data(), W, H) ? 1 : 2;
-                }
-            } catch (...) { // (an allocation that fails inside a pool thread must not end the batch)
-                t.state = 2;
-            }
+            readFileTask(p, m.eventID, m.names[t.f], t, sl.h_files.get(), W, H);
         });
-        r.bad = hostBad;
+        r.files.bad = hostBad;
         r.hostGood = hostGood;
-        size_t zoff = 0;
-        for (Task &t : tasks) {
-            if (t.state == 3)
-                continue;
-            if (t.state == 2) {
-                ++r.bad;
-                continue;
-            }
-            if (t.state == 1) {
-                r.hostPix.push_back(std::move(t.pix));
-                r.hostWhere.emplace_back(t.s, t.f);
-                continue;
-            }
-            abub_png_frame d;
-            d.seg_begin = (uint32_t)r.segs.size();
-            d.seg_count = (uint32_t)t.info.segs.size();
-            d.zoff = (uint32_t)zoff;
-            d.zlen = (uint32_t)t.info.zlen;
-            d.lut = 0xffffffffu;
-            d.reserved = 0;
-            d.dst = ((uint64_t)t.s * Fmax + t.f) * P;
-            if (t.info.palette) { // (the frames of a run share their palette: look for the table among those already kept)
-                size_t nl = r.luts.size() / 256, l = 0;
-                for (; l < nl; ++l)
-                    if (!memcmp(&r.luts[l * 256], t.info.lut, 256))
-                        break;
-                if (l == nl)
-                    r.luts.insert(r.luts.end(), t.info.lut, t.info.lut + 256);
-                d.lut = (uint32_t)l;
-            }
-            for (const abub_png_seg &sg : t.info.segs)
-                r.segs.push_back(abub_png_seg{(uint32_t)(t.off + sg.off), sg.len});
-            zoff += (((size_t)d.zlen + 15) & ~(size_t)15) + 16;
-            r.desc.push_back(d);
-            r.where.emplace_back(t.s, t.f);
-            r.fileOff.push_back((uint32_t)t.off);
-            r.fileLen.push_back((uint32_t)t.size);
-        }
-        r.zbytes = zoff + 16;
-        if (r.bytes >= ((size_t)1 << 32) || r.zbytes >= ((size_t)1 << 32))
-            throw std::runtime_error("RunBatched: a batch of more than 4 GB of files (lower the batch size)");
+        buildFileDescs(tasks.data(), tasks.data() + tasks.size(), total, r.files, [&](int s, int f) { return ((uint64_t)s * Fmax + f) * P; });
         r.ms = nowMs() - td;
-        if (!r.desc.empty()) {
-            sl.d_files.grow(r.bytes);
-            HIPOK(hipMemcpyAsync(sl.d_files.get(), sl.h_files.get(), r.bytes, hipMemcpyHostToDevice, upStream.get()));
+        if (!r.files.desc.empty()) {
+            sl.d_files.grow(r.files.bytes);
+            HIPOK(hipMemcpyAsync(sl.d_files.get(), sl.h_files.get(), r.files.bytes, hipMemcpyHostToDevice, upStream.get()));
             HIPOK(hipStreamSynchronize(upStream.get()));
         }
     };
 
     auto worker = [&](int g) {
-        // Everything the look-ahead thread touches lives outside the try block, and the thread is joined after it on every
-        // path.  (Declaration order: the streams are finished before the buffers they use are freed.)
-        Slot slots[2];
-        DeviceBuffer d_model, d_z, d_raw, d_luts, d_desc, d_segs, d_status; // the model; the GPU decoder's scratch
-        PinnedBuffer h_status;
-        Stream copyStream, upStream;
+        // Everything the look-ahead thread touches lives outside the try block (in the worker's cache), and the thread is
+        // joined after it on every path.
+        WorkerCache &wc = *ws.w[g];
+        Slot *slots = wc.slots;
+        PngScratch &png = wc.png;
+        Stream &copyStream = wc.copyStream, &upStream = wc.upStream;
         const int nthr = std::max(1, ndec / ngpus);
         std::thread dec;
         auto fail = [&](const std::string &msg) {
@@ -385,11 +311,11 @@ int RunBatched(Parser *parser, const std::vector<std::string> &EventList, const 
             const int nslots = g + ngpus < nb ? 2 : 1; // a worker with a single batch needs no second buffer
             for (int k = 0; k < nslots; ++k) {
                 if (G > Ggpu)
-                    slots[k].h_frames.allocate((size_t)(G - Ggpu) * perEvent);
-                slots[k].d_frames.allocate((size_t)G * perEvent);
+                    fit(slots[k].h_frames, (size_t)(G - Ggpu) * perEvent);
+                fit(slots[k].d_frames, (size_t)G * perEvent);
             }
-            d_model.allocate(3 * (size_t)C * P); // mu | sigma | sigma6
-            uint8_t *d_mu = d_model.get(), *d_sigma = d_mu + (size_t)C * P, *d_s6 = d_mu + 2 * (size_t)C * P;
+            fit(wc.d_model, 3 * (size_t)C * P); // mu | sigma | sigma6
+            uint8_t *d_mu = wc.d_model.get(), *d_sigma = d_mu + (size_t)C * P, *d_s6 = d_mu + 2 * (size_t)C * P;
             std::vector<int> tss(C);
             for (int c = 0; c < C; ++c) {
                 HIPOK(hipMemcpy(d_mu + (size_t)c * P, Trainers[c]->TrainedAvgImage.data, P, hipMemcpyHostToDevice));
@@ -401,7 +327,27 @@ int RunBatched(Parser *parser, const std::vector<std::string> &EventList, const 
             const bool trace = getenv("ABUB_INGEST_TRACE") != nullptr;
             if (trace)
                 fprintf(stderr, "worker %d: buffers and model on the device at %.1f ms\n", g, nowMs() - tAll);
-            RunPipelinePtr pipe = newRunPipeline(dev, W, H, Fmax, G, C, tss.data(), std::max(1, opt.hostThreads), opt.maskDir.c_str());
+            // a pipeline of this shape from an earlier run takes the new model's training-set sizes; otherwise one is built
+            RunPipeline *pipe = nullptr;
+            {
+                const std::vector<long long> key = {dev, W, H, Fmax, G, C, std::max(1, opt.hostThreads)};
+                for (size_t i = 0; i < wc.pipes.size() && !pipe; ++i)
+                    if (wc.pipes[i].key == key && setTrainingSetSizes(*wc.pipes[i].pipe, tss.data())) {
+                        std::rotate(wc.pipes.begin(), wc.pipes.begin() + i, wc.pipes.begin() + i + 1); // (most recent first)
+                        pipe = wc.pipes[0].pipe.get();
+                    }
+                if (!pipe) {
+                    if (wc.pipes.size() >= 2)
+                        wc.pipes.pop_back();
+                    WorkerCache::Pipe np;
+                    np.key = key;
+                    np.pipe = newRunPipeline(dev, W, H, Fmax, G, C, tss.data(), std::max(1, opt.hostThreads), opt.maskDir.c_str());
+                    wc.pipes.insert(wc.pipes.begin(), std::move(np));
+                    pipe = wc.pipes[0].pipe.get();
+                    std::lock_guard<std::mutex> lock(statMu);
+                    ++ws.pipelinesBuilt;
+                }
+            }
             setSigmaRaw(*pipe, d_sigma);
             if (trace)
                 fprintf(stderr, "worker %d: pipeline of %d events ready at %.1f ms\n", g, G, nowMs() - tAll);
@@ -423,11 +369,11 @@ int RunBatched(Parser *parser, const std::vector<std::string> &EventList, const 
                 // (the decoder's scratch while the first batch's files are being read: sizes from the batch's frame count; the
                 // stream buffer from a guess that regrows if a batch proves it wrong)
                 const size_t nfMax = (size_t)Ggpu * C * Fmax;
-                d_raw.grow(nfMax * abub_png_raw_stride(W, H));
-                d_desc.grow(nfMax * sizeof(abub_png_frame));
-                d_status.grow(nfMax * sizeof(int32_t));
-                h_status.allocate(nfMax * sizeof(int32_t) + 64);
-                d_z.grow(nfMax * (P / 4 * 3));
+                png.raw.grow(nfMax * abub_png_raw_stride(W, H));
+                png.desc.grow(nfMax * sizeof(abub_png_frame));
+                png.status.grow(nfMax * sizeof(int32_t));
+                fit(png.h_status, nfMax * sizeof(int32_t) + 64);
+                png.z.grow(nfMax * (P / 4 * 3));
                 if (trace)
                     fprintf(stderr, "worker %d: decoder scratch ready at %.1f ms\n", g, nowMs() - tAll);
             }
@@ -445,7 +391,7 @@ int RunBatched(Parser *parser, const std::vector<std::string> &EventList, const 
                     startRead(bn, slot ^ 1);
                 const double tg = nowMs();
                 const int nEv = std::min(G, (int)mine.size() - b * G), nEvGpu = std::min(nEv, Ggpu);
-                const int nf = (int)R.desc.size();
+                const int nf = (int)R.files.desc.size();
                 uint8_t *d_frames = S.d_frames.get();
                 hipStream_t cs = copyStream.get();
                 // the GPU share starts at zero (frames nobody decodes stay so, see decodeFrame); the host share is uploaded
@@ -455,56 +401,17 @@ int RunBatched(Parser *parser, const std::vector<std::string> &EventList, const 
                     HIPOK(hipMemcpyAsync(d_frames + (size_t)nEvGpu * perEvent, S.h_frames.get(), (size_t)(nEv - nEvGpu) * perEvent,
                                          hipMemcpyHostToDevice, cs));
                 const double tp = nowMs();
-                if (nf) {
-                    d_z.grow(R.zbytes);
-                    d_raw.grow((size_t)nf * abub_png_raw_stride(W, H));
-                    d_desc.grow((size_t)nf * sizeof(abub_png_frame));
-                    d_segs.grow(R.segs.size() * sizeof(abub_png_seg) + 8);
-                    d_luts.grow(R.luts.size() + 256);
-                    HIPOK(hipMemcpyAsync(d_desc.get(), R.desc.data(), (size_t)nf * sizeof(abub_png_frame), hipMemcpyHostToDevice, cs));
-                    HIPOK(hipMemcpyAsync(d_segs.get(), R.segs.data(), R.segs.size() * sizeof(abub_png_seg), hipMemcpyHostToDevice, cs));
-                    if (!R.luts.empty())
-                        HIPOK(hipMemcpyAsync(d_luts.get(), R.luts.data(), R.luts.size(), hipMemcpyHostToDevice, cs));
-                    check(abub_png_decode_dev(S.d_files.get(), R.bytes, (const abub_png_frame *)d_desc.get(), nf,
-                                              (const abub_png_seg *)d_segs.get(), (int)R.segs.size(), d_luts.get(),
-                                              (int)(R.luts.size() / 256), W, H, d_z.get(), d_z.capacity(), d_raw.get(),
-                                              d_raw.capacity(), d_frames, (size_t)nEv * perEvent, (int32_t *)d_status.get(), cs),
-                          "abub_png_decode_dev");
-                    HIPOK(hipMemcpyAsync(h_status.get(), d_status.get(), (size_t)nf * sizeof(int32_t), hipMemcpyDeviceToHost, cs));
-                }
+                launchFileDecode(R.files, S.d_files.get(), W, H, d_frames, (size_t)nEv * perEvent, png, cs);
                 // every write below lands after the clear above
                 HIPOK(hipStreamSynchronize(cs));
-                // a frame the kernels refused: the host decoder's answer (the same image, or the same failure)
                 long long onGpu = 0, onHost = R.hostGood;
-                std::vector<uint8_t> pix;
-                for (int i = 0; i < nf; ++i) {
-                    StackMeta &m = R.meta[R.where[i].first];
-                    uint8_t *dst = d_frames + R.desc[i].dst;
-                    if (((const int32_t *)h_status.get())[i] == 0) {
-                        m.ok[R.where[i].second] = 1;
-                        ++onGpu;
-                        continue;
-                    }
-                    pix.resize(P);
-                    if (cv::imdecodeInto(S.h_files.get() + R.fileOff[i], R.fileLen[i], pix.data(), W, H)) {
-                        HIPOK(hipMemcpy(dst, pix.data(), P, hipMemcpyHostToDevice));
-                        m.ok[R.where[i].second] = 1;
-                        ++onHost;
-                    } else {
-                        HIPOK(hipMemsetAsync(dst, 0, P, cs)); // (a refused frame may be half written)
-                        ++R.bad;
-                    }
-                }
-                for (size_t i = 0; i < R.hostPix.size(); ++i) {
-                    const size_t at = ((size_t)R.hostWhere[i].first * Fmax + R.hostWhere[i].second) * P;
-                    HIPOK(hipMemcpy(d_frames + at, R.hostPix[i].data(), P, hipMemcpyHostToDevice));
-                    R.meta[R.hostWhere[i].first].ok[R.hostWhere[i].second] = 1;
-                    ++onHost;
-                }
+                finishFileDecode(R.files, S.h_files.get(), (const int32_t *)png.h_status.get(), d_frames, W, H, cs,
+                                 [&](int s, int f) { return ((size_t)s * Fmax + f) * P; },
+                                 [&](int s, int f) { R.meta[s].ok[f] = 1; }, onGpu, onHost);
                 const double pngms = Ggpu ? nowMs() - tp : 0;
                 if (trace)
                     fprintf(stderr, "batch %d: %d frames for the GPU (%zu MB of files), %lld decoded by host threads, read + host decode %.1f ms, "
-                                    "upload + GPU decode %.1f ms\n", b, nf, R.bytes >> 20, R.hostGood, R.ms, pngms);
+                                    "upload + GPU decode %.1f ms\n", b, nf, R.files.bytes >> 20, R.hostGood, R.ms, pngms);
                 setStackMeta(*pipe, std::move(R.meta));
                 if (const char *tf = getenv("ABUB_TEST_FAIL_BATCH")) // test hook: a batch fails while the next one decodes
                     if (atoi(tf) == b)
@@ -532,7 +439,7 @@ int RunBatched(Parser *parser, const std::vector<std::string> &EventList, const 
                     st.gpu_s += gms * 1e-3;
                     st.write_s += wms * 1e-3;
                     st.frames += onGpu + onHost;
-                    st.framesFailed += R.bad;
+                    st.framesFailed += R.files.bad;
                     st.bellowsVetoed += bellowsVetoed(*pipe);
                     st.framesGpuDecoded += onGpu;
                     st.framesHostDecoded += onHost;
@@ -560,6 +467,267 @@ int RunBatched(Parser *parser, const std::vector<std::string> &EventList, const 
     st.total_s = (nowMs() - tAll) * 1e-3;
     if (stats)
         *stats = st;
+    return 0;
+}
+
+} // namespace
+
+int RunBatched(Parser *parser, const std::vector<std::string> &EventList, const std::vector<Trainer *> &Trainers,
+               int numCams, const std::string &out_dir, const std::string &run_number, int frameOffset,
+               const BatchedRunOptions &opt, BatchedRunStats *stats, std::string *why)
+{
+    Workers ws;
+    return runBatchedOn(ws, parser, EventList, Trainers, numCams, out_dir, run_number, frameOffset, opt, stats, why);
+}
+
+void RunPerEvent(Parser *parser, const std::vector<std::string> &EventList, const std::vector<Trainer *> &Trainers,
+                 int numCams, const std::string &eventDir, const std::string &out_dir, const std::string &run_number,
+                 int frameOffset, const std::string &maskDir, int nthreads, int eventUser, int debugMode, int shardRank,
+                 int shardWorld)
+{
+    // events in parallel, output appended in event order (the `ordered` clause :380-383)
+    std::cout << "Total threads: " << nthreads << std::endl;
+    std::vector<Trainer *> trainers = Trainers; // (L3Localizer takes Trainer **)
+    std::atomic<int> next{0};
+    std::mutex turnMutex;
+    std::condition_variable turnCv;
+    int turn = 0;
+    auto worker = [&]() {
+        for (;;) {
+            const int evi = next.fetch_add(1);
+            if (evi >= (int)EventList.size())
+                break;
+            const bool skip = (eventUser >= 0 && evi != eventUser) // compares the loop index, like upstream (:350)
+                              || (shardWorld > 1 && evi % shardWorld != shardRank);
+            OutputWriter *out = nullptr;
+            std::vector<AnalyzerUnit *> Analyzers;
+            if (!skip) {
+                out = new OutputWriter(out_dir, run_number, frameOffset, numCams);
+                const std::string imageDir = eventDir + EventList[evi] + "/Images/";
+                const int actualEventNumber = atoi(EventList[evi].c_str());
+                for (int icam = 0; icam < numCams; icam++) {
+                    Analyzers.push_back(new L3Localizer(EventList[evi], imageDir, icam, debugMode / 100 ? false : true,
+                                                        &trainers[icam], maskDir, parser->clone()));
+                    AnyCamAnalysis(Analyzers[icam], icam, debugMode % 10 ? false : true, out, out_dir, actualEventNumber);
+                }
+            }
+            {
+                std::unique_lock<std::mutex> lock(turnMutex);
+                turnCv.wait(lock, [&] { return turn == evi; });
+                if (out)
+                    out->writeCameraOutput();
+                ++turn;
+            }
+            turnCv.notify_all();
+            delete out;
+            for (AnalyzerUnit *A : Analyzers)
+                delete A;
+        }
+    };
+    std::vector<std::thread> th;
+    for (int t = 0; t < nthreads; ++t)
+        th.emplace_back(worker);
+    for (auto &t : th)
+        t.join();
+}
+
+PreparedRun::PreparedRun() = default;
+PreparedRun::PreparedRun(PreparedRun &&) = default;
+PreparedRun &PreparedRun::operator=(PreparedRun &&) = default;
+PreparedRun::~PreparedRun() = default;
+
+void PrintBatchedLine(const BatchedRunStats &bs)
+{
+    printf("batched detect: %d events in %d batches of <= %d on %d GPU(s), %lld frames %dx%d decoded (%lld on the GPU, %lld on "
+           "host threads; %lld undecodable), %.2f s total (list %.2f, read/decode %.2f, upload+GPU+host stages %.2f of which "
+           "GPU decode %.2f, write %.2f) = %.1f frames/s ingest-inclusive\n",
+           bs.events, bs.batches, bs.eventsPerBatch, bs.gpus, bs.frames, bs.W, bs.H, bs.framesGpuDecoded, bs.framesHostDecoded,
+           bs.framesFailed, bs.total_s, bs.list_s, bs.decode_s, bs.gpu_s, bs.gpudecode_s, bs.write_s,
+           bs.total_s > 0 ? (bs.frames + bs.framesFailed) / bs.total_s : 0.0);
+}
+
+// (a line for stdout, or held back in pr.log)
+static void say(PreparedRun &pr, bool buffered, const std::string &line)
+{
+    if (buffered)
+        pr.log += line;
+    else {
+        fputs(line.c_str(), stdout);
+        fflush(stdout);
+    }
+}
+
+PreparedRun PrepareRun(const RunSpec &r, const BatchedRunOptions &opt, int trainerDebug, DeviceTrainBuffers *buffers,
+                       bool buffered)
+{
+    PreparedRun pr;
+    const int C = r.numCams;
+    try {
+        if (r.zipped)
+            pr.parser.reset(new ZipParser(r.eventDir, r.imageFolder, r.imageFormat));
+        else
+            pr.parser.reset(new RawParser(r.eventDir, r.imageFolder, r.imageFormat));
+        pr.parser->GetEventDirLists(pr.events);
+    } catch (...) {
+        say(pr, buffered, "Failed to read the images from run " + r.runId + ". Autobub cannot continue.\n");
+        pr.rc = -5;
+        return pr;
+    }
+    std::sort(pr.events.begin(), pr.events.end(), [](const std::string &a, const std::string &b) { return std::stoi(a) < std::stoi(b); });
+
+    say(pr, buffered, "**Starting training. AutoBub is in learn mode**\n");
+    const double t0 = nowMs();
+    for (int icam = 0; icam < C; icam++) {
+        pr.owned.emplace_back(new Trainer(icam, pr.events, r.eventDir, r.imageFormat, r.imageFolder, pr.parser->clone(),
+                                          trainerDebug != 0));
+        pr.trainers.push_back(pr.owned.back().get());
+    }
+    int declined = 1;
+    if (opt.trainOnGpu) {
+        int ndev = 0;
+        HIPOK(hipGetDeviceCount(&ndev));
+        if (ndev <= 0)
+            throw std::runtime_error("TrainOnDevice: no GPU");
+        DeviceTrainOptions to;
+        to.device = opt.firstDevice % ndev;
+        to.threads = std::max(1, opt.decodeThreads / 4); // (the detect of the run before reads with the others)
+        to.capBytes = opt.batchBytes;
+        to.gpuDecode = opt.gpuDecode;
+        to.buffers = buffers;
+        to.log = buffered ? &pr.log : nullptr;
+        std::string why;
+        declined = TrainOnDevice(pr.parser.get(), pr.events, pr.trainers, to, nullptr, &why);
+        if (declined)
+            say(pr, buffered, "device training not used (" + why + "): training on host threads\n");
+    }
+    if (declined) {
+        // (the host Trainer prints its own lines as it goes: they are not held back)
+        pr.hostTrained = true;
+        std::vector<std::thread> th; // one thread per camera, like `#pragma omp parallel for` (:304-307)
+        for (int icam = 0; icam < C; icam++)
+            th.emplace_back([&, icam]() {
+                try {
+                    pr.trainers[icam]->MakeAvgSigmaImage(false);
+                } catch (std::exception &e) {
+                    std::cout << e.what() << '\n';
+                    pr.trainers[icam]->StatusCode = -7;
+                }
+            });
+        for (auto &t : th)
+            t.join();
+    }
+    pr.train_s = (nowMs() - t0) * 1e-3;
+    for (Trainer *t : pr.trainers)
+        if (t->StatusCode)
+            pr.rc = -7;
+    say(pr, buffered, pr.rc ? "Failed to train on images from run " + r.runId + ". Autobub cannot continue.\n"
+                            : std::string("***Training complete. AutoBub is now in detect mode***\n"));
+    return pr;
+}
+
+void CommitRun(const RunSpec &r, const BatchedRunOptions &opt, PreparedRun &pr)
+{
+    if (!pr.log.empty()) {
+        fputs(pr.log.c_str(), stdout);
+        fflush(stdout);
+        pr.log.clear();
+    }
+    const int C = r.numCams;
+    OutputWriter header(opt.outDir, r.runId, r.frameOffset, C);
+    header.writeHeader();
+    if (pr.rc == -5 && opt.shardRank == 0) { // (one block for the run: it goes into part 0 of a sharded run)
+        for (int icam = 0; icam < C; icam++)
+            header.stageCameraOutputError(icam, -5, -1);
+        header.writeCameraOutput();
+    }
+    if (pr.rc == -7)
+        for (size_t evi = 0; evi < pr.events.size(); evi++) {
+            if (opt.shardWorld > 1 && (int)(evi % (size_t)opt.shardWorld) != opt.shardRank)
+                continue;
+            for (int icam = 0; icam < C; icam++)
+                header.stageCameraOutputError(icam, -7, atoi(pr.events[evi].c_str()));
+            header.writeCameraOutput();
+        }
+}
+
+int RunCampaign(const std::vector<RunSpec> &runs, const BatchedRunOptions &opt, CampaignStats *stats)
+{
+    const double tAll = nowMs();
+    CampaignStats cs;
+    cs.status.assign(runs.size(), 0);
+    Workers ws;
+    DeviceTrainBuffers trainBuffers; // (one run is prepared at a time: the next starts once the last one was taken)
+    // run k + 1 is listed and trained while run k is detected: at most one run ahead.  Nothing of it is written, and its
+    // device-training lines are held back, until run k is done.
+    auto prepare = [&](size_t k) {
+        return std::async(std::launch::async, [&, k]() { return PrepareRun(runs[k], opt, 0, &trainBuffers, true); });
+    };
+    std::future<PreparedRun> next;
+    if (!runs.empty())
+        next = prepare(0);
+    size_t k = 0;
+    for (; k < runs.size(); ++k) {
+        const RunSpec &r = runs[k];
+        const double tw = nowMs();
+        PreparedRun pr;
+        try {
+            pr = next.get();
+        } catch (std::exception &e) { // (a HIP failure of device training)
+            std::cout << "training failed: " << e.what() << std::endl;
+            cs.status[k] = -6;
+            ++cs.runs;
+            break;
+        }
+        cs.trainExposed_s += (nowMs() - tw) * 1e-3;
+        ++cs.runs;
+        if (k + 1 < runs.size())
+            next = prepare(k + 1);
+        cs.train_s += pr.train_s;
+        cs.trainedOnHost += pr.hostTrained ? 1 : 0;
+        CommitRun(r, opt, pr);
+        if (pr.rc) {
+            cs.status[k] = pr.rc;
+            continue;
+        }
+        BatchedRunStats bs;
+        std::string why;
+        int rc = 1;
+        try {
+            rc = runBatchedOn(ws, pr.parser.get(), pr.events, pr.trainers, r.numCams, opt.outDir, r.runId, r.frameOffset, opt,
+                              &bs, &why);
+        } catch (std::exception &e) {
+            std::cout << "batched detect failed: " << e.what() << std::endl;
+            cs.status[k] = -6;
+            break;
+        }
+        if (rc == 0) {
+            PrintBatchedLine(bs);
+            cs.frames += bs.frames + bs.framesFailed;
+        } else {
+            std::cout << "batched detect not used (" << why << "): falling back to the per-event loop" << std::endl;
+            RunPerEvent(pr.parser.get(), pr.events, pr.trainers, r.numCams, r.eventDir, opt.outDir, r.runId, r.frameOffset,
+                        opt.maskDir, std::max(1, opt.perEventThreads), -1, 0, opt.shardRank, opt.shardWorld);
+        }
+        printf("run complete.\n");
+        printf("AutoBub done analyzing this run. Thank you.\n");
+    }
+    if (k < runs.size()) { // ended by a failure: the run prepared ahead is neither written nor detected
+        if (next.valid()) {
+            try {
+                next.get();
+            } catch (...) {
+            }
+        }
+        for (size_t j = k + 1; j < runs.size(); ++j)
+            cs.notRun.push_back(runs[j].runId);
+    }
+    cs.pipelinesBuilt = ws.pipelinesBuilt;
+    cs.total_s = (nowMs() - tAll) * 1e-3;
+    if (stats)
+        *stats = cs;
+    for (int st : cs.status)
+        if (st)
+            return st;
     return 0;
 }
 

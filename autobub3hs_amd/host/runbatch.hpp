@@ -10,6 +10,8 @@
 #include <string>
 #include <vector>
 
+#include <memory>
+
 class Parser;
 class Trainer;
 
@@ -26,6 +28,10 @@ struct BatchedRunOptions {
     int gpuDecode = -1;             // PNG frames decoded on the GPU (abub_png_decode_dev): 1 on, 0 off (host threads decode),
                                     // -1 = on where the parser hands out the files and the frames are 8-bit grey / palette
                                     // PNGs of a width the kernels take (ABUB_GPU_DECODE=0/1 overrides)
+    // RunCampaign only
+    std::string outDir;             // where every run's abub3hs_<run>.txt goes (ends with '/')
+    int trainOnGpu = 1;             // 1: TrainOnDevice (the host Trainer where it declines a run); 0: the host Trainer
+    int perEventThreads = 16;       // threads of the per-event loop of a run the batched path declines
 };
 
 struct BatchedRunStats {
@@ -44,6 +50,69 @@ struct BatchedRunStats {
 int RunBatched(Parser *parser, const std::vector<std::string> &EventList, const std::vector<Trainer *> &Trainers,
                int numCams, const std::string &out_dir, const std::string &run_number, int frameOffset,
                const BatchedRunOptions &opt, BatchedRunStats *stats, std::string *why);
+
+// The per-event loop of the reference's main program (AutoBubStart3.cpp:338-388): one analyzer per (event, camera), events on
+// `nthreads` threads, blocks appended to <out_dir>abub3hs_<run_number>.txt in event order.  eventUser >= 0: only the event
+// at that index; debugMode: the CLI's --debug digits.  The CLI's -e / --debug / --per-event path and the fallback of a
+// run that RunBatched declines.
+void RunPerEvent(Parser *parser, const std::vector<std::string> &EventList, const std::vector<Trainer *> &Trainers,
+                 int numCams, const std::string &eventDir, const std::string &out_dir, const std::string &run_number,
+                 int frameOffset, const std::string &maskDir, int nthreads, int eventUser, int debugMode, int shardRank,
+                 int shardWorld);
+
+// The "batched detect: ..." line of a run
+void PrintBatchedLine(const BatchedRunStats &bs);
+
+// One run of a campaign: what the CLI computes from -d / -D and the run ID (AutoBubStart3.cpp:212-245)
+struct RunSpec {
+    std::string runId, eventDir, imageFormat, imageFolder;
+    int frameOffset = 30, numCams = 4;
+    bool zipped = false;
+};
+
+struct DeviceTrainBuffers;
+
+// A run listed and trained, ready for detect; rc = -5 (the run cannot be read) or -7 (a camera did not train)
+struct PreparedRun {
+    std::unique_ptr<Parser> parser;
+    std::vector<std::string> events;
+    std::vector<std::unique_ptr<Trainer>> owned;
+    std::vector<Trainer *> trainers;
+    int rc = 0;
+    double train_s = 0;
+    bool hostTrained = false;
+    std::string log; // stdout lines held back (buffered)
+    PreparedRun();
+    PreparedRun(PreparedRun &&);
+    PreparedRun &operator=(PreparedRun &&);
+    ~PreparedRun();
+};
+
+// The CLI's flow up to detect (AutoBubStart3.cpp:250-307) without writing anything: the event list, then training (the
+// host Trainer, or TrainOnDevice where opt.trainOnGpu; trainerDebug: the Trainers' debug flag).  buffered: the lines for
+// stdout are held in pr.log (the host Trainer's own lines are printed as they come); buffers: kept from run to run.
+PreparedRun PrepareRun(const RunSpec &r, const BatchedRunOptions &opt, int trainerDebug, DeviceTrainBuffers *buffers,
+                       bool buffered);
+// Prints the held-back lines, then writes the run's header into opt.outDir, and its -5 / -7 rows when it failed
+void CommitRun(const RunSpec &r, const BatchedRunOptions &opt, PreparedRun &pr);
+
+struct CampaignStats {
+    int runs = 0;                  // runs that were started (listed, trained, detected or failed)
+    long long frames = 0;          // frames of the batched runs (decoded or not)
+    double total_s = 0;
+    double train_s = 0;            // training, summed over runs
+    double trainExposed_s = 0;     // ... of which the detect loop waited for
+    int pipelinesBuilt = 0;
+    int trainedOnHost = 0;         // runs trained by the host Trainer (ABUB_TRAIN_ON_GPU=0, or TrainOnDevice declined)
+    std::vector<int> status;       // per run: 0, -5, -6, -7 (what a single-run invocation returns)
+    std::vector<std::string> notRun; // runs never started after a GPU failure
+};
+
+// Every run of `runs` in one process, each written to its own abub3hs_<run>.txt in opt.outDir with the bytes a single-run
+// invocation writes.  The workers (one per GPU) keep their buffers, streams and pipelines from one run to the next; while
+// a run is detected, the next one lists its events and trains (on the device, its own stream).  A HIP or IO failure ends
+// the campaign at that run (-6).  Returns the first nonzero status in list order, else 0.
+int RunCampaign(const std::vector<RunSpec> &runs, const BatchedRunOptions &opt, CampaignStats *stats);
 
 } // namespace abub
 #endif

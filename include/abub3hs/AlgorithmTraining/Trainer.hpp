@@ -41,6 +41,8 @@ public:
     // identifies the (mu, sigma) pair so that a GPU context re-uploads it only when it changes;
     // copied by the copy constructor together with the images
     unsigned long long ModelId = 0;
+    // the next ModelId a trained model gets (the one counter of every path that trains, host or device)
+    static unsigned long long NextModelId();
 
     Trainer(int camera, std::vector<std::string> EventList, std::string EventDir, std::string ImageFormat,
             std::string ImageFolder, Parser *FileParser, bool debug = false);
