@@ -16,8 +16,13 @@ both sides, max over ranks); `ms_per_step` is that block's time over K.  With --
 until S seconds have been measured and `ms_per_step` / `value` are the MEDIAN block.
 --dump-outputs DIR writes the per-stack results of the last timed step as DIR/<name>.npy (float64).
 
-Also reported (config.microbench): BASELINE configs[2], the fused kernel alone on a 10k-frame slab, store mode and
-trigger-only mode, bound-and-verify and the plain row machine (the dense-regime worst case).
+A plain run does only that: set up, warm up, time the K steps, dump, print the line.  With --full the run goes on, after
+the timed steps and the dump, through the legs that only the full report needs: latency one step at a time
+(config.latency_one_step_at_a_time_ms), the PCIe-inclusive and decode-inclusive rates (config.pcie_inclusive,
+config.ingest_inclusive, config.png_decode_on_gpu), the K2 pass alone (roofline), BASELINE configs[2] on a 10k-frame slab
+(config.microbench: store mode and trigger-only mode, bound-and-verify and the plain row machine, the dense-regime worst
+case), the CPU oracle on a sample of the stacks (cpu_baseline, also a full-size parity check) and the other data regimes
+(config.regimes).
 """
 import argparse
 import json
@@ -32,6 +37,9 @@ if ROOT not in sys.path:
 
 HBM_PEAK_GBPS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec (6.29 TB/s measured copy ceiling)
 
+# the sizes of the --full legs (0 skips a leg); a plain run runs none of them
+FULL_LEG_SIZES = {"latency_steps": 5, "stream_steps": 10, "ingest_events": 96, "micro_frames": 10000, "regime_steps": 12}
+
 
 def parse(argv=None):
     ap = argparse.ArgumentParser()
@@ -44,36 +52,41 @@ def parse(argv=None):
     ap.add_argument("--width", type=int, default=1280)
     ap.add_argument("--height", type=int, default=1024)
     ap.add_argument("--train-events", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, run every other leg of the report too (latency, PCIe- and decode-inclusive "
+                         "rates, roofline, kernel microbench, CPU baseline, other data regimes); the options marked (--full) "
+                         "size those legs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="(--full) time of the 1-core CPU baseline")
     ap.add_argument("--threads", type=int, default=16, help="host threads of the per-event state machines")
     ap.add_argument("--decode-threads", type=int, default=0,
-                    help="decode threads of the ingestion leg (0 = the cores this process may run on, at most 128)")
+                    help="(--full) decode threads of the ingestion leg (0 = the cores this process may run on, at most 128)")
     ap.add_argument("--inflight", type=int, default=6,
                     help="steps in flight at once (each on its own pipeline object and host thread); measured on one MI355X: "
                          "2 -> 2.46, 3 -> 2.59, 4 -> 2.65, 6 -> 2.76, 8 -> 2.79, 12 -> 2.58 M frames/s")
     ap.add_argument("--pipe-threads", type=int, default=0,
                     help="host threads per pipeline object in flight (0 = --threads, capped so that all ranks of the node together stay near 400)")
-    ap.add_argument("--stream-steps", type=int, default=10,
-                    help="runs streamed from pinned host memory, two in flight (BASELINE configs[4] on this GPU: PCIe-inclusive "
-                         "rate, reported in config only; 0 = skip)")
+    ap.add_argument("--stream-steps", type=int, default=None,
+                    help="(--full, default 10) runs streamed from pinned host memory, two in flight (BASELINE configs[4] on "
+                         "this GPU: PCIe-inclusive rate, reported in config only; 0 = skip)")
     ap.add_argument("--min-seconds", type=float, default=0.0,
                     help="repeat the timed K-step block until this much time has been measured (0 = one block: exactly "
                          "--steps timed steps)")
     ap.add_argument("--max-blocks", type=int, default=400)
-    ap.add_argument("--micro-frames", type=int, default=10000,
-                    help="frames of the configs[2] kernel microbench slab (0 = skip)")
-    ap.add_argument("--regime-steps", type=int, default=12,
-                    help="steps per extra data regime (config.regimes: post_trigger_dense, noisy); 0 = skip")
+    ap.add_argument("--micro-frames", type=int, default=None,
+                    help="(--full, default 10000) frames of the configs[2] kernel microbench slab (0 = skip)")
+    ap.add_argument("--regime-steps", type=int, default=None,
+                    help="(--full, default 12) steps per extra data regime (config.regimes: post_trigger_dense, noisy); 0 = skip")
     ap.add_argument("--no-masks", action="store_true", help="run without fiducial / bellows mask files")
     ap.add_argument("--slabs", type=int, default=0, help="copies of the run in HBM (0 = one per step in flight)")
     ap.add_argument("--regime", default="default", choices=["default", "post_trigger_dense", "noisy"],
                     help="data regime of the MAIN workload (default: BASELINE's quiet-noise run; the others are reported under "
-                         "config.regimes by the default run and can be made the main workload for A/B runs)")
-    ap.add_argument("--ingest-events", type=int, default=96,
-                    help="events of the run written as a PNG zip archive on local disk and detected from there through the "
-                         "batched ingestion path (decode-inclusive rate, config.ingest_inclusive; 0 = skip)")
-    ap.add_argument("--latency-steps", type=int, default=5, help="steps run one at a time for the latency figure (0 = skip)")
+                         "config.regimes by a --full run and can be made the main workload for A/B runs)")
+    ap.add_argument("--ingest-events", type=int, default=None,
+                    help="(--full, default 96) events of the run written as a PNG zip archive on local disk and detected from "
+                         "there through the batched ingestion path (decode-inclusive rate, config.ingest_inclusive; 0 = skip)")
+    ap.add_argument("--latency-steps", type=int, default=None,
+                    help="(--full, default 5) steps run one at a time for the latency figure (0 = skip)")
     ap.add_argument("--dry", action="store_true",
                     help="no GPU work: every rank only walks the launch / barrier / max-over-ranks / report protocol "
                          "(rehearsal of the multi-rank path on CPU with ABUB_BENCH_BACKEND=gloo)")
@@ -84,6 +97,12 @@ def parse(argv=None):
         ap.error("--steps must be at least 1")
     if args.dump_outputs and args.dry:
         ap.error("--dump-outputs needs the real path (not --dry)")
+    asked = [k for k in FULL_LEG_SIZES if getattr(args, k)]
+    if asked and not args.full:
+        ap.error(f"--{asked[0].replace('_', '-')} sizes a leg of --full, which this run does not have")
+    for k, n in FULL_LEG_SIZES.items():
+        if getattr(args, k) is None:
+            setattr(args, k, n if args.full else 0)
     return args
 
 
@@ -387,6 +406,14 @@ def main():
         if rank == 0:
             emit(out)
         if dist:
+            dist.destroy_process_group()
+        return
+    if not args.full:
+        # a plain run ends here: everything below is the rest of the report of a --full run
+        if rank == 0:
+            emit(out)
+        if dist:
+            dist.barrier()
             dist.destroy_process_group()
         return
 

@@ -76,6 +76,21 @@ def test_dump_outputs_refuses_dry_and_zero_steps():
     assert _run(["--dry", "--steps", "0"]).returncode == 2
 
 
+def test_full_legs_run_only_with_full():
+    """A plain run has none of the report's other legs; --full gives each its default size, and an option that sizes one
+    of them is refused without --full rather than dropped."""
+    import bench
+
+    plain = bench.parse([])
+    assert not plain.full and all(getattr(plain, k) == 0 for k in bench.FULL_LEG_SIZES)
+    full = bench.parse(["--full"])
+    assert all(getattr(full, k) == n and n > 0 for k, n in bench.FULL_LEG_SIZES.items())
+    assert bench.parse(["--full", "--latency-steps", "3", "--micro-frames", "0"]).latency_steps == 3
+    assert bench.parse(["--micro-frames", "0", "--regime-steps", "0"]).regime_steps == 0
+    p = _run(["--dry", "--latency-steps", "3"])
+    assert p.returncode == 2 and "--latency-steps" in p.stderr and "--full" in p.stderr
+
+
 def test_dump_outputs_layout(tmp_path):
     """bench.dump_outputs writes every stack's result (host.Pipeline.result) as float64 arrays."""
     import numpy as np

@@ -11,7 +11,7 @@ TAG=$1; shift
 case " $* " in *" --gpus "[2-9]*|*" --gpus="[2-9]*) echo "prof_bench_pmc.sh: profile a single rank (no --gpus N > 1 under rocprofv3)"; exit 2;; esac
 O=$R/gpurun_out/$TAG; mkdir -p $O
 rm -f $O/pmc_*.csv $O/bench_pmc_summary.json   # never summarise the counter files of an earlier collection
-ARGS="--steps 2 --warmup 1 --inflight 1 --micro-frames 0 --no-cpu-baseline --ingest-events 0 --stream-steps 0 --min-seconds 0 --latency-steps 0 --regime-steps 0 $@"
+ARGS="--full --steps 2 --warmup 1 --inflight 1 --micro-frames 0 --no-cpu-baseline --ingest-events 0 --stream-steps 0 --min-seconds 0 --latency-steps 0 --regime-steps 0 $@"
 cd /tmp
 KPAT='k2_|k3_|sus_|k1_|k4_|k_hist|k_pairs|k_slot|k1b|k_sigma|k_fill'
 rm -rf /tmp/bp_trace

@@ -2,7 +2,7 @@
 # end-to-end ingest with GPU decode on / off
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 cd $R; mkdir -p gpurun_out/r03
-B="python bench.py --steps 2 --warmup 1 --micro-frames 0 --no-cpu-baseline --stream-steps 0 --latency-steps 0 --regime-steps 0 --min-seconds 0 --ingest-events 96"
+B="python bench.py --full --steps 2 --warmup 1 --micro-frames 0 --no-cpu-baseline --stream-steps 0 --latency-steps 0 --regime-steps 0 --min-seconds 0 --ingest-events 96"
 for g in 1 0; do
   ABUB_GPU_DECODE=$g timeout -k 10 500 $B > gpurun_out/r03/ingest_gpu$g.json 2> gpurun_out/r03/ingest_gpu$g.err; echo "gpu=$g rc=$?"
   python3 - gpurun_out/r03/ingest_gpu$g.json <<'P'

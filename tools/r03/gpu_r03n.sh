@@ -6,7 +6,7 @@ cd $R
 timeout -k 10 1100 python -m pytest tests -m gpu -x -q > $O/pytest_gpu.log 2>&1; rc=$?
 tail -8 $O/pytest_gpu.log
 [ $rc -ne 0 ] && exit $rc
-( time timeout -k 10 600 python bench.py > $O/bench_default.json 2> $O/bench_default.err ) 2> $O/bench_default.time || { tail -20 $O/bench_default.err; exit 1; }
+( time timeout -k 10 600 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err ) 2> $O/bench_default.time || { tail -20 $O/bench_default.err; exit 1; }
 tail -3 $O/bench_default.time
 python3 - $O/bench_default.json <<'PY'
 import json,sys
