@@ -12,8 +12,62 @@ SO = os.path.join(HERE, "libabub_host.so")
 
 _u8p = C.POINTER(C.c_uint8)
 _u32p = C.POINTER(C.c_uint32)
+_u64p = C.POINTER(C.c_uint64)
 _ip = C.POINTER(C.c_int)
+_fp = C.POINTER(C.c_float)
 _dp = C.POINTER(C.c_double)
+_vp, _i, _s = C.c_void_p, C.c_int, C.c_char_p
+# name -> (restype, argtypes) of every abh_* entry this module calls (host/capi.cpp, host/pipeline.cpp)
+SIGNATURES = {
+    "abh_run_new": (_vp, []),
+    "abh_run_open": (_vp, [_i, _s, _s, _s]),
+    "abh_run_free": (None, [_vp]),
+    "abh_run_events": (_s, [_vp]),
+    "abh_run_frames": (_s, [_vp, _s, _i]),
+    "abh_run_image": (_i, [_vp, _s, _s, _u8p, _i, _ip, _ip]),
+    "abh_run_add_event": (_i, [_vp, _s, _i, _u8p, _i, _i, _i, _u8p]),
+    "abh_train": (_i, [_vp, _i, _ip, _ip, _u8p, _u8p]),
+    "abh_train_device": (_i, [_vp, _i, _ip, _ip, _u8p, _u8p, _i, _dp]),
+    "abh_set_model": (_i, [_vp, _i, _u8p, _u8p, _i, _i, _i]),
+    "abh_probe_frame_stats": (_i, [_vp, _s, _i, _u8p, _i, _i, _i, _dp]),
+    "abh_run_batched": (_i, [_vp, _i, _s, _s, _s] + [_i] * 7 + [_dp]),
+    "abh_analyze": (_i, [_vp, _s, _i, _s]),
+    "abh_last_error": (_s, [_vp]),
+    "abh_run_last": (_vp, [_vp]),
+    "abh_result_state": (None, [_vp, _ip]),
+    "abh_result_error": (_s, [_vp]),
+    "abh_result_ndesc": (_i, [_vp, _i]),
+    "abh_result_desc": (None, [_vp, _i, _i, _dp]),
+    "abh_result_ndz": (_i, [_vp, _i]),
+    "abh_result_dz": (C.c_float, [_vp, _i, _i]),
+    "abh_result_dzdt": (C.c_float, [_vp, _i]),
+    "abh_result_drdt": (C.c_float, [_vp, _i]),
+    "abh_imdecode": (_i, [_u8p, _i, _u8p, _i, _ip, _ip]),
+    "abh_png_walk": (_i, [_u8p, _i, _i, _i, _u32p, _i, _ip, _ip, _u8p]),
+    "abh_imwrite": (_i, [_s, _u8p, _i, _i]),
+    "abh_write_header": (None, [_s, _s, _i, _i]),
+    "abh_event_to_file": (_i, [_vp, _s, _i, _i, _s, _s, _s, _i]),
+    "abh_writer_probe": (None, [_s, _s, _i, _i, _i, _ip, _ip, _ip, _ip, _dp]),
+    "abh_contours": (_i, [_u32p, _i, _i, _i, _ip, _ip, _i, _i]),
+    "abh_binarize_threshold": (_i, [_u32p, _i, _i]),
+    "abh_entropy": (C.c_float, [_u32p, _i, _i]),
+    "abh_blob_stats": (None, [_ip, _i, _dp]),
+    "abh_best_match": (None, [_u64p, _u64p, _i, _i, _u8p, _i, _i, _fp, _fp]),
+    "abh_sig_new": (_vp, []),
+    "abh_sig_free": (None, [_vp]),
+    "abh_sig_eval": (C.c_double, [_vp, _u32p, _i, _i, _i, _ip]),
+    "abh_pipe_new": (_vp, [_i] * 6 + [_ip, _i, _s]),
+    "abh_pipe_free": (None, [_vp]),
+    "abh_pipe_error": (_s, []),
+    "abh_pipe_set_sigma": (None, [_vp, _vp]),
+    "abh_pipe_run": (_i, [_vp] * 5),
+    "abh_pipe_run_host": (_i, [_vp] * 4),
+    "abh_pipe_stack": (_vp, [_vp, _i]),
+    "abh_pipe_timing": (_i, [_vp, _dp]),
+    "abh_pipe_set_option": (_i, [_vp, _s, _i]),
+    "abh_pipe_blob_stats": (None, [_vp, _dp]),
+    "abh_pipe_bellows": (None, [_vp, _dp]),
+}
 _lib = None
 
 
@@ -34,41 +88,39 @@ def lib():
 
         hiplib.lib()  # the HIP library first, bound to torch's HIP runtime (see _lib.lib)
         L = C.CDLL(SO)
-        L.abh_run_new.restype = C.c_void_p
-        L.abh_run_free.argtypes = [C.c_void_p]
-        L.abh_run_add_event.argtypes = [C.c_void_p, C.c_char_p, C.c_int, _u8p, C.c_int, C.c_int, C.c_int, _u8p]
-        L.abh_train.argtypes = [C.c_void_p, C.c_int, _ip, _ip, _u8p, _u8p]
-        L.abh_set_model.argtypes = [C.c_void_p, C.c_int, _u8p, _u8p, C.c_int, C.c_int, C.c_int]
-        L.abh_analyze.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_char_p]
-        for f in ("trig", "status", "loc_thres", "ok", "nbubbles"):
-            getattr(L, "abh_last_" + f).argtypes = [C.c_void_p]
-        L.abh_last_error.argtypes = [C.c_void_p]
-        L.abh_last_error.restype = C.c_char_p
-        L.abh_last_ndesc.argtypes = [C.c_void_p, C.c_int]
-        L.abh_last_desc.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp]
-        L.abh_last_ndz.argtypes = [C.c_void_p, C.c_int]
-        L.abh_last_dz.argtypes = [C.c_void_p, C.c_int, C.c_int]
-        L.abh_last_dz.restype = C.c_float
-        L.abh_last_dzdt.argtypes = [C.c_void_p, C.c_int]
-        L.abh_last_dzdt.restype = C.c_float
-        L.abh_last_drdt.argtypes = [C.c_void_p, C.c_int]
-        L.abh_last_drdt.restype = C.c_float
-        L.abh_write_header.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int]
-        L.abh_event_to_file.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int]
-        L.abh_contours.argtypes = [_u32p, C.c_int, C.c_int, C.c_int, _ip, _ip, C.c_int, C.c_int]
-        L.abh_binarize_threshold.argtypes = [_u32p, C.c_int, C.c_int]
-        L.abh_entropy.argtypes = [_u32p, C.c_int, C.c_int]
-        L.abh_entropy.restype = C.c_float
-        L.abh_blob_stats.argtypes = [_ip, C.c_int, _dp]
-        L.abh_sig_new.restype = C.c_void_p
-        L.abh_sig_free.argtypes = [C.c_void_p]
-        L.abh_sig_eval.argtypes = [C.c_void_p, _u32p, C.c_int, C.c_int, C.c_int, _ip]
-        L.abh_sig_eval.restype = C.c_double
+        for name, (res, args) in SIGNATURES.items():
+            fn = getattr(L, name)  # AttributeError if this table and the library drift apart
+            fn.restype = res
+            fn.argtypes = args
         _lib = L
     return _lib
 
 
 DESC_KEYS = ("x", "y", "w", "h", "area", "radius", "m00", "m10", "m01", "cx", "cy")
+
+
+def _read_result(res, with_dz):
+    """A StackResult (host/stackresult.hpp) handed out by abh_run_last / abh_pipe_stack -> (staged, state, bubbles,
+    error text); a bubble's per-frame dz list only where asked for."""
+    L = lib()
+    o = (C.c_int * 6)()
+    L.abh_result_state(res, o)
+    state = {"trig": o[1], "status": o[2], "ok": bool(o[4]), "loc_thres": o[3]}
+    bubbles = []
+    buf = (C.c_double * len(DESC_KEYS))()
+    for b in range(o[5]):
+        descs = []
+        for d in range(L.abh_result_ndesc(res, b)):
+            L.abh_result_desc(res, b, d, buf)
+            dd = dict(zip(DESC_KEYS, list(buf)))
+            for k in ("x", "y", "w", "h"):
+                dd[k] = int(dd[k])
+            descs.append(dd)
+        bub = {"desc": descs, "dzdt": L.abh_result_dzdt(res, b), "drdt": L.abh_result_drdt(res, b)}
+        if with_dz:
+            bub["dz"] = [L.abh_result_dz(res, b, i) for i in range(L.abh_result_ndz(res, b))]
+        bubbles.append(bub)
+    return o[0], state, bubbles, L.abh_result_error(res).decode()
 
 
 class Run:
@@ -77,13 +129,6 @@ class Run:
 
     def __init__(self, kind=None, run_folder="", image_folder="Images", image_format="cam%d_image%u.png"):
         L = lib()
-        L.abh_run_open.restype = C.c_void_p
-        L.abh_run_open.argtypes = [C.c_int, C.c_char_p, C.c_char_p, C.c_char_p]
-        L.abh_run_events.restype = C.c_char_p
-        L.abh_run_events.argtypes = [C.c_void_p]
-        L.abh_run_frames.restype = C.c_char_p
-        L.abh_run_frames.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
-        L.abh_run_image.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, _u8p, C.c_int, _ip, _ip]
         if kind is None:
             self._h = L.abh_run_new()
         else:
@@ -143,7 +188,6 @@ class Run:
         frames decoded by the GPU decoder / by host threads, decode launches, seconds."""
         H, W = shape if shape is not None else self._shape
         L = lib()
-        L.abh_train_device.argtypes = [C.c_void_p, C.c_int, _ip, _ip, _u8p, _u8p, C.c_int, _dp]
         mu = np.zeros((ncams, H, W), np.uint8)
         sg = np.zeros((ncams, H, W), np.uint8)
         st = np.zeros(ncams, np.int32)
@@ -169,7 +213,6 @@ class Run:
         256-bin significance, through the private AnalyzerUnit members that the reference compiles but never calls
         (AnalyzerUnit.cpp:386-433) -> float64 [n,3]."""
         L = lib()
-        L.abh_probe_frame_stats.argtypes = [C.c_void_p, C.c_char_p, C.c_int, _u8p, C.c_int, C.c_int, C.c_int, _dp]
         imgs = np.ascontiguousarray(imgs, dtype=np.uint8)
         n, H, W = imgs.shape
         out = np.zeros((n, 3), np.float64)
@@ -184,7 +227,6 @@ class Run:
         """Every event of this run through the batched GPU pipeline (host/runbatch.cpp RunBatched): frames decoded (PNG files: on the GPU, abub_png_decode_dev; ABUB_GPU_DECODE=0: by host threads into pinned
         batches), detect, blocks appended to <outdir>abub3hs_<run>.txt in event order.  -> stats dict."""
         L = lib()
-        L.abh_run_batched.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_char_p, C.c_char_p] + [C.c_int] * 7 + [_dp]
         st = (C.c_double * 13)()
         rc = L.abh_run_batched(self._h, ncams, maskdir.encode(), outdir.encode(), run_number.encode(), frame_offset, ngpus,
                                nthreads, decode_threads, batch_mb, shard[0], shard[1], st)
@@ -199,27 +241,11 @@ class Run:
         staged = L.abh_analyze(self._h, str(event).encode(), cam, maskdir.encode())
         if staged == -100:
             raise RuntimeError(L.abh_last_error(self._h).decode())
-        state = {"trig": L.abh_last_trig(self._h), "status": L.abh_last_status(self._h),
-                 "ok": bool(L.abh_last_ok(self._h)), "loc_thres": L.abh_last_loc_thres(self._h)}
-        bubbles = []
-        buf = (C.c_double * 11)()
-        for b in range(L.abh_last_nbubbles(self._h)):
-            descs = []
-            for d in range(L.abh_last_ndesc(self._h, b)):
-                L.abh_last_desc(self._h, b, d, buf)
-                dd = dict(zip(DESC_KEYS, list(buf)))
-                for k in ("x", "y", "w", "h"):
-                    dd[k] = int(dd[k])
-                descs.append(dd)
-            dz = [L.abh_last_dz(self._h, b, i) for i in range(L.abh_last_ndz(self._h, b))]
-            bubbles.append({"desc": descs, "dz": dz, "dzdt": L.abh_last_dzdt(self._h, b),
-                            "drdt": L.abh_last_drdt(self._h, b)})
-        return staged, state, bubbles, L.abh_last_error(self._h).decode()
+        return _read_result(L.abh_run_last(self._h), with_dz=True)
 
 
 def imdecode(data, cap=1 << 22):
     L = lib()
-    L.abh_imdecode.argtypes = [_u8p, C.c_int, _u8p, C.c_int, _ip, _ip]
     src = np.frombuffer(data, np.uint8)
     out = np.empty(cap, np.uint8)
     w, h = C.c_int(), C.c_int()
@@ -233,7 +259,6 @@ def png_walk(data, W, H, cap=4096):
     """host/pngwalk.hpp::pngWalk: None for a file the GPU decoder does not take, else (IDAT segments [(offset, length)],
     palette -> grey table (bytes) or None)"""
     L = lib()
-    L.abh_png_walk.argtypes = [_u8p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint32), C.c_int, _ip, _ip, _u8p]
     src = np.frombuffer(data, np.uint8)
     segs = (C.c_uint32 * (2 * cap))()
     n, pal = C.c_int(), C.c_int()
@@ -246,7 +271,6 @@ def png_walk(data, W, H, cap=4096):
 def imwrite(path, img):
     """cvlite's cv::imwrite (debug image write-out): 8-bit grey PNG, or BMP when the name ends in .bmp."""
     L = lib()
-    L.abh_imwrite.argtypes = [C.c_char_p, _u8p, C.c_int, C.c_int]
     img = np.ascontiguousarray(img, dtype=np.uint8)
     return L.abh_imwrite(path.encode(), img.ctypes.data_as(_u8p), img.shape[1], img.shape[0]) == 0
 
@@ -267,7 +291,6 @@ def event_to_file(run, event, actual_event_number, ncams, outdir, run_number, fr
 def writer_probe(outdir, run_number, frame_offset, event, cams):
     """cams: list of (status, frame0, bubbles) with bubbles = list of descriptor-row lists (11 numbers each)."""
     L = lib()
-    L.abh_writer_probe.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, _ip, _ip, _ip, _ip, _dp]
     n = len(cams)
     status = (C.c_int * n)(*[c[0] for c in cams])
     frame0 = (C.c_int * n)(*[c[1] for c in cams])
@@ -314,14 +337,12 @@ def blob_stats(xy):
 
 def best_match(num, wsum2, tmpl):
     L = lib()
-    u64p = C.POINTER(C.c_uint64)
-    L.abh_best_match.argtypes = [u64p, u64p, C.c_int, C.c_int, _u8p, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     num = np.ascontiguousarray(num, dtype=np.uint64)
     wsum2 = np.ascontiguousarray(wsum2, dtype=np.uint64)
     tmpl = np.ascontiguousarray(tmpl, dtype=np.uint8)
     rh, rw = num.shape
     bx, by = C.c_float(), C.c_float()
-    L.abh_best_match(num.ctypes.data_as(u64p), wsum2.ctypes.data_as(u64p), rw, rh, tmpl.ctypes.data_as(_u8p),
+    L.abh_best_match(num.ctypes.data_as(_u64p), wsum2.ctypes.data_as(_u64p), rw, rh, tmpl.ctypes.data_as(_u8p),
                      tmpl.shape[1], tmpl.shape[0], C.byref(bx), C.byref(by))
     return bx.value, by.value
 
@@ -349,21 +370,6 @@ class Pipeline:
 
     def __init__(self, device, W, H, F, E, ncams, tss, nthreads=16, maskdir=""):
         L = lib()
-        L.abh_pipe_new.restype = C.c_void_p
-        L.abh_pipe_new.argtypes = [C.c_int] * 6 + [_ip, C.c_int, C.c_char_p]
-        L.abh_pipe_free.argtypes = [C.c_void_p]
-        L.abh_pipe_run.argtypes = [C.c_void_p] * 5
-        L.abh_pipe_error.restype = C.c_char_p
-        L.abh_pipe_result.argtypes = [C.c_void_p, C.c_int, _ip]
-        L.abh_pipe_ndesc.argtypes = [C.c_void_p, C.c_int, C.c_int]
-        L.abh_pipe_desc.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp]
-        L.abh_pipe_dzdt.argtypes = [C.c_void_p, C.c_int, C.c_int]
-        L.abh_pipe_dzdt.restype = C.c_float
-        L.abh_pipe_drdt.argtypes = [C.c_void_p, C.c_int, C.c_int]
-        L.abh_pipe_drdt.restype = C.c_float
-        L.abh_pipe_stack_error.argtypes = [C.c_void_p, C.c_int]
-        L.abh_pipe_stack_error.restype = C.c_char_p
-        L.abh_pipe_timing.argtypes = [C.c_void_p, _dp]
         t = (C.c_int * len(tss))(*tss)
         self.S = E * ncams
         self._h = L.abh_pipe_new(device, W, H, F, E, ncams, t, nthreads, maskdir.encode())
@@ -383,7 +389,6 @@ class Pipeline:
 
     def set_sigma(self, sigma):
         """sigma image(s) (not 6 sigma) on the device: needed only by stacks that fall back to the drop-in path."""
-        lib().abh_pipe_set_sigma.argtypes = [C.c_void_p, C.c_void_p]
         lib().abh_pipe_set_sigma(self._h, sigma.data_ptr() if hasattr(sigma, "data_ptr") else int(sigma))
 
     def run(self, frames, mu, sigma6, stream=0, sigma=None):
@@ -391,8 +396,7 @@ class Pipeline:
         bellows veto): device pointers (ints) or torch tensors."""
         p = [x.data_ptr() if hasattr(x, "data_ptr") else int(x) for x in (frames, mu, sigma6)]
         if sigma is not None:
-            lib().abh_pipe_set_sigma.argtypes = [C.c_void_p, C.c_void_p]
-            lib().abh_pipe_set_sigma(self._h, sigma.data_ptr() if hasattr(sigma, "data_ptr") else int(sigma))
+            self.set_sigma(sigma)
         rc = lib().abh_pipe_run(self._h, p[0], p[1], p[2], stream)
         if rc != 0:
             raise RuntimeError("pipeline: " + lib().abh_pipe_error().decode())
@@ -401,8 +405,7 @@ class Pipeline:
         """Streamed mode: `frames_host` is a HOST tensor / pointer ([E][C][F][H][W], pinned for full PCIe rate);
         stack groups are uploaded and processed in a pipeline."""
         L = lib()
-        L.abh_pipe_run_host.argtypes = [C.c_void_p] * 4
-        p = [x.data_ptr() if hasattr(x, "data_ptr") else int(x) for x in (frames_host, mu, sigma6)]
+        p =[x.data_ptr() if hasattr(x, "data_ptr") else int(x) for x in (frames_host, mu, sigma6)]
         if L.abh_pipe_run_host(self._h, p[0], p[1], p[2]) != 0:
             raise RuntimeError("pipeline: " + L.abh_pipe_error().decode())
 
@@ -417,17 +420,13 @@ class Pipeline:
         """Run-time knob of this pipeline object: "blobs" 0 (default, from ABUB_PIPE_BLOBS) or 1 -- label the foreground on
         the GPU and ship only the pixels of the components the localizer can use.  Results never depend on it."""
         L = lib()
-        L.abh_pipe_set_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int]
-        L.abh_pipe_error.restype = C.c_char_p
         if L.abh_pipe_set_option(self._h, name.encode(), int(value)) != 0:
             raise ValueError(L.abh_pipe_error().decode())
 
     def blob_stats(self):
         """Blob labelling of the last run (zeros when the "blobs" knob was off), summed over stack groups and rounds."""
-        L = lib()
-        L.abh_pipe_blob_stats.argtypes = [C.c_void_p, _dp]
         out = (C.c_double * 8)()
-        L.abh_pipe_blob_stats(self._h, out)
+        lib().abh_pipe_blob_stats(self._h, out)
         v = list(out)
         keys = ("candidates", "foreground", "kept", "components", "kept_components", "large_slots")
         d = {k: int(x) for k, x in zip(keys, v)}
@@ -437,31 +436,14 @@ class Pipeline:
     def bellows_stats(self):
         """Bellows veto of the last run: stacks vetoed inside the batch, template-match jobs and launches, residual
         images, wall time of the veto rounds (ms)."""
-        L = lib()
-        L.abh_pipe_bellows.argtypes = [C.c_void_p, _dp]
         out = (C.c_double * 5)()
-        L.abh_pipe_bellows(self._h, out)
+        lib().abh_pipe_bellows(self._h, out)
         v = list(out)
         return {"vetoed": int(v[0]), "match_jobs": int(v[1]), "match_launches": int(v[2]), "residual_images": int(v[3]),
                 "veto_ms": v[4]}
 
     def result(self, s):
-        L = lib()
-        o = (C.c_int * 6)()
-        L.abh_pipe_result(self._h, s, o)
-        state = {"trig": o[1], "status": o[2], "ok": bool(o[4]), "loc_thres": o[3]}
-        bubbles = []
-        buf = (C.c_double * 11)()
-        for b in range(o[5]):
-            descs = []
-            for d in range(L.abh_pipe_ndesc(self._h, s, b)):
-                L.abh_pipe_desc(self._h, s, b, d, buf)
-                dd = dict(zip(DESC_KEYS, list(buf)))
-                for k in ("x", "y", "w", "h"):
-                    dd[k] = int(dd[k])
-                descs.append(dd)
-            bubbles.append({"desc": descs, "dzdt": L.abh_pipe_dzdt(self._h, s, b), "drdt": L.abh_pipe_drdt(self._h, s, b)})
-        return o[0], state, bubbles, L.abh_pipe_stack_error(self._h, s).decode()
+        return _read_result(lib().abh_pipe_stack(self._h, s), with_dz=False)
 
     def summary(self):
         """(staged, trig, nbubbles) for every stack -- cheap fingerprint of a run."""
@@ -469,7 +451,7 @@ class Pipeline:
         o = (C.c_int * 6)()
         out = []
         for s in range(self.S):
-            L.abh_pipe_result(self._h, s, o)
+            L.abh_result_state(L.abh_pipe_stack(self._h, s), o)
             out.append((o[0], o[1], o[5]))
         return out
 

@@ -24,53 +24,17 @@
 #include "hostlogic.hpp"
 #include "pngwalk.hpp"
 #include "runbatch.hpp"
+#include "stackresult.hpp"
 
 namespace {
-
-struct BubbleOut {
-    std::vector<BubbleImageFrame> desc;
-    std::vector<float> dz;
-    float dzdt, drdt;
-};
 
 struct Run {
     Parser *parser = nullptr; // MemParser (tests / synthetic), RawParser or ZipParser
     MemParser *mem = nullptr;
     std::string frames_of_last_query;
     std::map<int, Trainer *> trainers;
-    // last analysis
-    int staged = 0, trig = 0, status = 0, loc_thres = 0, ok = 0;
-    std::vector<BubbleOut> bubbles;
-    std::string error;
+    abub::StackResult last; // last analysis; last.error also carries the text of any other failed call on the run
 };
-
-// AnyCamAnalysis (AutoBubStart3.cpp:87-117): retry until a bubble is found or the search fails.
-int anyCamAnalysis(AnalyzerUnit *A, Run *run)
-{
-    int staged = 0;
-    try {
-        do {
-            A->FindTriggerFrame(true, A->MatTrigFrame + 1);
-            if (A->okToProceed) {
-                A->LocalizeOMatic("");
-                if (A->okToProceed)
-                    staged = A->BubbleList.empty() ? -1 : 0; // stageCameraOutput (PICOFormatWriterV4.cpp:99-110)
-                else {
-                    staged = -8;
-                    break;
-                }
-            } else {
-                staged = A->TriggerFrameIdentificationStatus;
-                break;
-            }
-        } while (A->BubbleList.size() == 0);
-    } catch (std::exception &e) {
-        run->error = e.what();
-        std::cout << e.what() << '\n';
-        staged = -6;
-    }
-    return staged;
-}
 
 } // namespace
 
@@ -105,7 +69,7 @@ int abh_probe_frame_stats(void *r, const char *ev, int cam, const uint8_t *imgs,
             out[3 * k + 2] = abub::AnalyzerProbe::significance(A, m, true);
         }
     } catch (std::exception &e) {
-        run->error = e.what();
+        run->last.error = e.what();
         return -1;
     }
     abub::DeviceContext::releaseThread();
@@ -141,11 +105,8 @@ void *abh_run_open(int kind, const char *runFolder, const char *imageFolder, con
 const char *abh_run_events(void *r)
 {
     Run *run = (Run *)r;
-    std::vector<std::string> ev;
-    run->parser->GetEventDirLists(ev);
-    std::sort(ev.begin(), ev.end(), [](const std::string &a, const std::string &b) { return std::stoi(a) < std::stoi(b); });
     run->frames_of_last_query.clear();
-    for (auto &e : ev)
+    for (auto &e : abub::sortedEvents(*run->parser))
         run->frames_of_last_query += e + "\n";
     return run->frames_of_last_query.c_str();
 }
@@ -244,9 +205,7 @@ int abh_train(void *r, int cam, int *status, int *tss, uint8_t *mu_out, uint8_t 
 {
     Run *run = (Run *)r;
     try {
-        std::vector<std::string> events;
-        run->parser->GetEventDirLists(events);
-        std::sort(events.begin(), events.end(), [](const std::string &a, const std::string &b) { return std::stoi(a) < std::stoi(b); });
+        const std::vector<std::string> events = abub::sortedEvents(*run->parser);
         delete run->trainers[cam];
         Trainer *t = new Trainer(cam, events, "", "cam%d_image%u.png", "", run->parser->clone(), false);
         run->trainers[cam] = t;
@@ -259,7 +218,7 @@ int abh_train(void *r, int cam, int *status, int *tss, uint8_t *mu_out, uint8_t 
         }
         return 0;
     } catch (std::exception &e) {
-        run->error = e.what();
+        run->last.error = e.what();
         return -1;
     }
 }
@@ -273,9 +232,7 @@ int abh_train_device(void *r, int ncams, int *status, int *tss, uint8_t *mu_out,
 {
     Run *run = (Run *)r;
     try {
-        std::vector<std::string> events;
-        run->parser->GetEventDirLists(events);
-        std::sort(events.begin(), events.end(), [](const std::string &a, const std::string &b) { return std::stoi(a) < std::stoi(b); });
+        const std::vector<std::string> events = abub::sortedEvents(*run->parser);
         std::vector<Trainer *> trainers;
         for (int c = 0; c < ncams; ++c) {
             delete run->trainers[c];
@@ -293,7 +250,7 @@ int abh_train_device(void *r, int ncams, int *status, int *tss, uint8_t *mu_out,
             stats[3] = st.total_s;
         }
         if (rc != 0) {
-            run->error = why;
+            run->last.error = why;
             for (Trainer *t : trainers)
                 t->MakeAvgSigmaImage(false);
         }
@@ -308,7 +265,7 @@ int abh_train_device(void *r, int ncams, int *status, int *tss, uint8_t *mu_out,
         }
         return rc != 0 ? 1 : 0;
     } catch (std::exception &e) {
-        run->error = e.what();
+        run->last.error = e.what();
         return -1;
     }
 }
@@ -333,11 +290,11 @@ int abh_set_model(void *r, int cam, const uint8_t *mu, const uint8_t *sigma, int
 int abh_analyze(void *r, const char *ev, int cam, const char *maskdir)
 {
     Run *run = (Run *)r;
-    run->bubbles.clear();
-    run->error.clear();
+    run->last.bubbles.clear();
+    run->last.error.clear();
     auto it = run->trainers.find(cam);
     if (it == run->trainers.end() || !it->second) {
-        run->error = "no trainer for camera";
+        run->last.error = "no trainer for camera";
         return -100;
     }
     Trainer *t = it->second;
@@ -345,24 +302,15 @@ int abh_analyze(void *r, const char *ev, int cam, const char *maskdir)
     try {
         A = new L3Localizer(ev, "", cam, true, &t, maskdir ? maskdir : "", run->parser->clone());
     } catch (std::exception &e) {
-        run->error = e.what();
+        run->last.error = e.what();
         return -100;
     }
-    run->staged = anyCamAnalysis(A, run);
-    run->trig = A->MatTrigFrame;
-    run->status = A->TriggerFrameIdentificationStatus;
-    run->loc_thres = A->loc_thres;
-    run->ok = A->okToProceed;
-    for (bubble *b : A->BubbleList) {
-        BubbleOut o;
-        o.desc = b->KnownDescriptors;
-        o.dz = b->dz;
-        o.dzdt = b->dZdT();
-        o.drdt = b->dRdT();
-        run->bubbles.push_back(o);
-    }
+    run->last.staged = abub::analyzeUntilBubble(A, true, "", run->last.error);
+    if (run->last.staged == -6)
+        std::cout << run->last.error << '\n';
+    run->last.capture(*A);
     delete A;
-    return run->staged;
+    return run->last.staged;
 }
 
 // A whole run (every event of the Run's parser, cameras 0..ncams-1, the Run's trained models) through the batched
@@ -373,14 +321,12 @@ int abh_run_batched(void *r, int ncams, const char *maskdir, const char *outdir,
 {
     Run *run = (Run *)r;
     try {
-        std::vector<std::string> events;
-        run->parser->GetEventDirLists(events);
-        std::sort(events.begin(), events.end(), [](const std::string &a, const std::string &b) { return std::stoi(a) < std::stoi(b); });
+        const std::vector<std::string> events = abub::sortedEvents(*run->parser);
         std::vector<Trainer *> trainers;
         for (int c = 0; c < ncams; ++c) {
             auto it = run->trainers.find(c);
             if (it == run->trainers.end() || !it->second) {
-                run->error = "no trainer for camera";
+                run->last.error = "no trainer for camera";
                 return -1;
             }
             trainers.push_back(it->second);
@@ -398,7 +344,7 @@ int abh_run_batched(void *r, int ncams, const char *maskdir, const char *outdir,
         std::string why;
         const int rc = abub::RunBatched(run->parser, events, trainers, ncams, outdir, run_number, frameOffset, bo, &bs, &why);
         if (rc != 0)
-            run->error = why;
+            run->last.error = why;
         if (statsOut) {
             const double v[13] = {bs.total_s, bs.list_s, bs.decode_s, bs.gpu_s, bs.write_s, (double)bs.frames, (double)bs.framesFailed,
                                   (double)bs.batches, (double)bs.eventsPerBatch, (double)bs.gpus, (double)bs.framesGpuDecoded,
@@ -407,7 +353,7 @@ int abh_run_batched(void *r, int ncams, const char *maskdir, const char *outdir,
         }
         return rc;
     } catch (std::exception &e) {
-        run->error = e.what();
+        run->last.error = e.what();
         return -1;
     }
 }
@@ -448,68 +394,43 @@ void abh_writer_probe(const char *outdir, const char *run_number, int frameOffse
                       const int *status, const int *frame0, const int *nbub, const int *ndesc, const double *desc)
 {
     OutputWriter w(outdir, run_number, frameOffset, ncams);
-    std::vector<std::vector<bubble *>> lists(ncams);
+    abub::StagedBubbles staged;
     int bi = 0, di = 0;
     for (int c = 0; c < ncams; ++c) {
+        abub::StackResult res;
+        res.staged = status[c];
+        res.trig = frame0[c];
         for (int k = 0; k < nbub[c]; ++k, ++bi) {
-            bubble *b = nullptr;
-            for (int d = 0; d < ndesc[bi]; ++d, ++di) {
-                const double *r = desc + 11 * (size_t)di;
-                BubbleImageFrame f;
-                f.newPosition = cv::Rect((int)r[0], (int)r[1], (int)r[2], (int)r[3]);
-                f.ContArea = r[4];
-                f.ContRadius = r[5];
-                f.moments.m00 = r[6];
-                f.moments.m10 = r[7];
-                f.moments.m01 = r[8];
-                f.MassCentres = cv::Point2f((float)r[9], (float)r[10]);
-                if (!b)
-                    b = new bubble(f);
-                else {
-                    b->lockThisIteration = false;
-                    *b << f;
-                }
-            }
-            lists[c].push_back(b);
+            abub::BubbleOut bo{};
+            for (int d = 0; d < ndesc[bi]; ++d, ++di)
+                bo.desc.push_back(abub::descFromRow(desc + abub::kDescRow * (size_t)di));
+            res.bubbles.push_back(bo);
         }
-        if (status[c] == 0)
-            w.stageCameraOutput(lists[c], c, frame0[c], event);
-        else
-            w.stageCameraOutputError(c, status[c], event);
+        staged.stage(w, res, c, event);
     }
     w.writeCameraOutput();
-    for (auto &l : lists)
-        for (bubble *b : l)
-            delete b;
 }
 
-int abh_last_trig(void *r) { return ((Run *)r)->trig; }
-int abh_last_status(void *r) { return ((Run *)r)->status; }
-int abh_last_loc_thres(void *r) { return ((Run *)r)->loc_thres; }
-int abh_last_ok(void *r) { return ((Run *)r)->ok; }
-const char *abh_last_error(void *r) { return ((Run *)r)->error.c_str(); }
-int abh_last_nbubbles(void *r) { return (int)((Run *)r)->bubbles.size(); }
-int abh_last_ndesc(void *r, int b) { return (int)((Run *)r)->bubbles[b].desc.size(); }
-// out: x,y,w,h,area,radius,m00,m10,m01,cx,cy
-void abh_last_desc(void *r, int b, int d, double *out)
+// A StackResult read out: `res` comes from abh_run_last (valid until the run's next call) or abh_pipe_stack (until the
+// pipeline's next run).  state: staged, trig, status, loc_thres, ok, nbubbles
+const void *abh_run_last(void *r) { return &((Run *)r)->last; }
+const char *abh_last_error(void *r) { return ((Run *)r)->last.error.c_str(); }
+void abh_result_state(const void *res, int *out)
 {
-    const BubbleImageFrame &f = ((Run *)r)->bubbles[b].desc[d];
-    out[0] = f.newPosition.x;
-    out[1] = f.newPosition.y;
-    out[2] = f.newPosition.width;
-    out[3] = f.newPosition.height;
-    out[4] = f.ContArea;
-    out[5] = f.ContRadius;
-    out[6] = f.moments.m00;
-    out[7] = f.moments.m10;
-    out[8] = f.moments.m01;
-    out[9] = f.MassCentres.x;
-    out[10] = f.MassCentres.y;
+    const abub::StackResult &r = *(const abub::StackResult *)res;
+    const int v[6] = {r.staged, r.trig, r.status, r.loc_thres, r.ok, (int)r.bubbles.size()};
+    std::memcpy(out, v, sizeof v);
 }
-int abh_last_ndz(void *r, int b) { return (int)((Run *)r)->bubbles[b].dz.size(); }
-float abh_last_dz(void *r, int b, int i) { return ((Run *)r)->bubbles[b].dz[i]; }
-float abh_last_dzdt(void *r, int b) { return ((Run *)r)->bubbles[b].dzdt; }
-float abh_last_drdt(void *r, int b) { return ((Run *)r)->bubbles[b].drdt; }
+const char *abh_result_error(const void *res) { return ((const abub::StackResult *)res)->error.c_str(); }
+int abh_result_ndesc(const void *res, int b) { return (int)((const abub::StackResult *)res)->bubbles[b].desc.size(); }
+void abh_result_desc(const void *res, int b, int d, double *out)
+{
+    abub::descToRow(((const abub::StackResult *)res)->bubbles[b].desc[d], out);
+}
+int abh_result_ndz(const void *res, int b) { return (int)((const abub::StackResult *)res)->bubbles[b].dz.size(); }
+float abh_result_dz(const void *res, int b, int i) { return ((const abub::StackResult *)res)->bubbles[b].dz[i]; }
+float abh_result_dzdt(const void *res, int b) { return ((const abub::StackResult *)res)->bubbles[b].dzdt; }
+float abh_result_drdt(const void *res, int b) { return ((const abub::StackResult *)res)->bubbles[b].drdt; }
 
 // host-logic probes for CPU-side unit tests (no GPU needed)
 int abh_contours(const uint32_t *idx, int n, int W, int H, int *npts_out, int *xy_out, int cap_contours, int cap_pts)

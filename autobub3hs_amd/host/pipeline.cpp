@@ -34,14 +34,30 @@
 #include "common/CommonParameters.h"
 #include "PICOFormatWriter/PICOFormatWriterV4.hpp"
 #include "devctx.hpp"
+#include "driver.hpp"
 #include "holders.hpp"
 #include "hostlogic.hpp"
 #include "pipeline.hpp"
+#include "stackresult.hpp"
 
 namespace abub {
 extern bool g_quietAnalyzers;
 
 namespace {
+
+// FindTriggerFrame's frame offset: frame i is differenced against frame max(i - off, 0), off = 1 when the model was
+// trained on fewer than 6 frames (AnalyzerUnit.cpp:185-188)
+int refOffset(int tss) { return tss < 6 ? 1 : 2; }
+// that offset when every camera shares it, else 0
+int chainStrideOf(const int *tss, int C)
+{
+    for (int c = 1; c < C; ++c)
+        if (refOffset(tss[c]) != refOffset(tss[0]))
+            return 0;
+    return refOffset(tss[0]);
+}
+// the bellows templates are Mats of the process-wide mask cache: the same template is the same buffer
+bool sameTemplate(const cv::Mat &a, const cv::Mat &b) { return a.data == b.data && a.cols == b.cols && a.rows == b.rows; }
 
 struct PlannedImage {
     int kind; // 0 = D(i; ref) (genesis), 1 = post-trigger image of frame i, 2 = bellows residual of D(i; ref)
@@ -171,7 +187,7 @@ public:
     MatchMemo *findMatch(int i, const cv::Mat &templ)
     {
         for (MatchMemo &m : matches)
-            if (m.frame == i && m.templ.data == templ.data && m.templ.cols == templ.cols && m.templ.rows == templ.rows)
+            if (m.frame == i && sameTemplate(m.templ, templ))
                 return &m;
         return nullptr;
     }
@@ -241,25 +257,22 @@ public:
     }
 };
 
-struct BubbleOut {
-    std::vector<BubbleImageFrame> desc;
-    std::vector<float> dz;
-    float dzdt, drdt;
-};
-
-struct StackState {
+// the stack's result (a stack that ends before its first trigger reports the analyzer's initial loc_thres and
+// okToProceed) and its state while the run is on
+struct StackState : StackResult {
+    StackState()
+    {
+        loc_thres = 3;
+        ok = 1;
+    }
     std::unique_ptr<L3Localizer> analyzer;
     BatchEventData data;
-    int staged = 0;
     bool done = false;
     bool localize = false;
     bool dropIn = false; // must be re-run through the one-at-a-time path (bellows veto)
     bool needMore = false; // the trigger search stopped at a frame block that is not evaluated yet (data.needBlock)
     bool needBellows = false; // localize stopped at a bellows-veto request (data.matches / data.residuals)
     bool vetoed = false;      // a bellows residual was computed for this stack in the batch
-    std::string error;
-    std::vector<BubbleOut> bubbles;
-    int trig = 0, status = 0, loc_thres = 3, ok = 1;
 };
 
 // Persistent worker pool shared by all stack groups: a group that is waiting for the GPU lends its
@@ -451,6 +464,55 @@ struct CandidateList {
     }
 };
 
+// Counters of one run: every stack group keeps its own, the pipeline merges them (abh_pipe_timing, abh_pipe_bellows and
+// abh_pipe_blob_stats hand them out)
+struct PipeStats {
+    // host wall time (ms): waiting for stage 1, stages 2 .. 4 summed over the rounds; of stage 3: launches + kernels +
+    // histogram / count D2H, list D2H + thresholds
+    double stage1Ms = 0, stage2Ms = 0, stage3Ms = 0, stage4Ms = 0, s3GpuMs = 0, s3ListMs = 0;
+    int rounds = 0;
+    uint32_t pairs = 0;          // candidate pairs of the last stage-3 batch
+    // kept by the pipeline across its groups (the counters under launchMu, or after the groups have ended), so not merged:
+    double totalMs = 0;          // wall time of the whole run
+    long long jobsLaunched = 0;  // trigger-search jobs (F - 1 per stack when nothing is lazy)
+    long long jobsCompleted = 0; // ... of which the dense rows were evaluated on demand (deferred pieces)
+    int dropIns = 0;             // stacks that went through the one-at-a-time path (bellows veto)
+    // bellows veto inside the batch: stacks, template-match jobs and launches, residual images, wall time of the veto rounds
+    int vetoed = 0, matchJobs = 0, matchLaunches = 0, residualImages = 0;
+    double vetoMs = 0;
+    // blobs knob, summed over the rounds: candidate pairs, foreground pixels after the Otsu cut, kept pixels (shipped to the
+    // host), components, kept components, slots labelled on the global-memory path, ms of the Otsu and of the K4b launches
+    long long blobCandidates = 0, blobForeground = 0, blobKept = 0, blobComponents = 0, blobKeptComponents = 0, blobLargeSlots = 0;
+    double blobOtsuMs = 0, blobK4bMs = 0;
+
+    void reset() { *this = PipeStats(); }
+    // a group's counters into the run's: the groups run side by side, so times and rounds take the maximum, counts add
+    void merge(const PipeStats &g)
+    {
+        stage1Ms = std::max(stage1Ms, g.stage1Ms);
+        stage2Ms = std::max(stage2Ms, g.stage2Ms);
+        stage3Ms = std::max(stage3Ms, g.stage3Ms);
+        stage4Ms = std::max(stage4Ms, g.stage4Ms);
+        s3GpuMs = std::max(s3GpuMs, g.s3GpuMs);
+        s3ListMs = std::max(s3ListMs, g.s3ListMs);
+        rounds = std::max(rounds, g.rounds);
+        pairs += g.pairs;
+        vetoed += g.vetoed;
+        matchJobs += g.matchJobs;
+        matchLaunches += g.matchLaunches;
+        residualImages += g.residualImages;
+        vetoMs += g.vetoMs;
+        blobCandidates += g.blobCandidates;
+        blobForeground += g.blobForeground;
+        blobKept += g.blobKept;
+        blobComponents += g.blobComponents;
+        blobKeptComponents += g.blobKeptComponents;
+        blobLargeSlots += g.blobLargeSlots;
+        blobOtsuMs += g.blobOtsuMs;
+        blobK4bMs += g.blobK4bMs;
+    }
+};
+
 // One slice of the run with its own stream and scratch: groups run concurrently on host threads, so the
 // GPU work of one group overlaps the host state machines of another (no group waits on another).
 struct Group {
@@ -488,7 +550,6 @@ struct Group {
         Mirror<uint32_t> koff, kstats; // kstats: K4b's counters
         DeviceArray<uint32_t> ncomp, nkc, coff;
         Event ev[3]; // before Otsu, between, after K4b
-        double stats[8] = {0}; // last run: see abh_pipe_blob_stats
     } blobs;
     // bellows veto round (vetoRound): its own buffers, allocated on first use, grown on demand
     struct Veto {
@@ -507,12 +568,8 @@ struct Group {
         CandidateList list;
         std::vector<std::pair<cv::Mat, DeviceArray<uint8_t>>> templates; // device copies of the bellows templates (deviceTemplate)
     } veto;
-    int vetoed = 0, matchJobs = 0, matchLaunches = 0, residualImages = 0;
-    double vetoMs = 0;
     int nthreads = 1;
-    double tms[8] = {0};
-    int rounds = 0;
-    uint32_t lastPairs = 0;
+    PipeStats stats; // of the group's part of the last run
     std::string error;
     // declared last, so destroyed first: the holder finishes the stream's work before the buffers above are freed
     Stream stream;
@@ -531,12 +588,8 @@ public:
     std::unique_ptr<WorkerPool> pool;
     std::vector<int> blocks;            // frame blocks of the trigger search: block k = frames [blocks[k], blocks[k + 1])
     bool deferPieces = false;           // trigger search: dense frames' rows are evaluated on demand (see the constructor)
-    long long jobsCompleted = 0;        // ... jobs of the last run that were completed that way
-    long long jobsLaunched = 0;         // trigger-search jobs of the last run (F - 1 per stack when nothing is lazy)
-    int dropIns = 0;                    // stacks of the last run that went through the one-at-a-time path (bellows veto)
     bool bellowsDropIn = false;         // ABUB_PIPE_BELLOWS=dropin: every bellows veto takes the one-at-a-time path (A/B)
-    double bellowsStats[5] = {0};       // last run: vetoed stacks, match jobs, match launches, residual images, veto ms
-    double blobStats[8] = {0};          // last run, blobs knob: see abh_pipe_blob_stats
+    PipeStats stats;                    // the last run's, merged over the groups
     Stream stage1Stream;                // all trigger-search launches, in group order (see run())
     int chainStride = 0;                // FindTriggerFrame's frame offset when every camera shares it, else 0
     bool ordered = true;                // localisation kernels queue on stage1Stream too (see batchImages())
@@ -549,6 +602,12 @@ public:
     // optional (runs ingested from a Parser): real ids / names / decode flags per stack; a stack may be shorter than F
     std::vector<StackMeta> meta;
     MemParser metaParser;
+    const uint8_t *d_sigmaRaw = nullptr; // optional: sigma (not 6*sigma) for stacks that need the drop-in path
+    // streamed mode (runFromHost): the uploads, one event per group, and whether run() waits for them
+    Stream copyStream;
+    std::vector<Event> copied;
+    bool waitCopies = false;
+
     void setStackMeta(std::vector<StackMeta> &&m)
     {
         if ((int)m.size() != S)
@@ -565,35 +624,20 @@ public:
     // rebuilt from the results (and freed once the block is written)
     void writeEvent(int k, int eventNumber, OutputWriter &out)
     {
-        std::vector<std::vector<bubble *>> owned(C);
+        StagedBubbles staged;
         for (int c = 0; c < C; ++c) {
-            StackState &ss = stacks[(size_t)k * C + c];
+            const StackState &ss = stacks[(size_t)k * C + c];
             if (!ss.error.empty())
                 std::cout << ss.error << '\n'; // (AnyCamAnalysis prints the exception text, then stages -6)
-            if (ss.staged == 0) {
-                for (BubbleOut &bo : ss.bubbles) {
-                    bubble *bb = new bubble(bo.desc[0]);
-                    for (size_t d = 1; d < bo.desc.size(); ++d) {
-                        bb->lockThisIteration = false;
-                        *bb << bo.desc[d];
-                    }
-                    owned[c].push_back(bb);
-                }
-                out.stageCameraOutput(owned[c], c, ss.trig, eventNumber);
-            } else
-                out.stageCameraOutputError(c, ss.staged, eventNumber);
+            staged.stage(out, ss, c, eventNumber);
         }
         out.writeCameraOutput();
-        for (auto &l : owned)
-            for (bubble *bb : l)
-                delete bb;
     }
-    // trigger-search job of frame i of stack s (FindTriggerFrame's pairing: ref = max(i - off, 0), off = 1 when the model
-    // was trained on fewer than 6 frames, AnalyzerUnit.cpp:185-188).  Frames a shorter stack does not have are replaced
-    // by its last one on both sides (D = 0: a quiet job that keeps the chain structure the scan relies on).
+    // trigger-search job of frame i of stack s (FindTriggerFrame's pairing, see refOffset).  Frames a shorter stack does not
+    // have are replaced by its last one on both sides (D = 0: a quiet job that keeps the chain structure the scan relies on).
     abub_job triggerJob(int s, int i, uint32_t out) const
     {
-        const int c = s % C, off = tss[c] < 6 ? 1 : 2;
+        const int c = s % C, off = refOffset(tss[c]);
         const int Fs = meta.empty() ? F : (int)meta[s].names.size();
         const int last = std::max(Fs - 1, 0);
         abub_job j;
@@ -658,12 +702,9 @@ public:
         B.hist.toHost((size_t)nj * 256, stream, j0 * 256);
         B.fetches.push_back(fe);
         B.used = first + n;
-        jobsLaunched += nj;
+        stats.jobsLaunched += nj;
         return first;
     }
-    double tms[8] = {0};
-    int rounds = 0;
-    uint32_t lastPairs = 0;
 
     RunPipeline(int device_, int W_, int H_, int F_, int E_, int C_, const int *tss_, int nthreads_, const char *maskdir)
         : device(device_), W(W_), H(H_), F(F_), E(E_), C(C_), S(E_ * C_), nthreads(nthreads_), P((size_t)W_ * H_),
@@ -688,10 +729,7 @@ public:
         if (ngroups > S)
             ngroups = S;
         const int K = NumFramesBubbleTrack + 1;
-        chainStride = tss[0] < 6 ? 1 : 2;
-        for (int c = 1; c < C; ++c)
-            if ((tss[c] < 6 ? 1 : 2) != chainStride)
-                chainStride = 0;
+        chainStride = chainStrideOf(tss.data(), C);
         groups.resize(ngroups);
         pool.reset(new WorkerPool(std::max(0, nthreads - ngroups))); // the group driver threads take part too
         // Frame blocks of the trigger search.  The reference walks the frames in order and stops at the trigger
@@ -776,11 +814,6 @@ public:
         (void)abub_scratch_release(stage1Stream.get()); // the trigger search's work list lives in library scratch
     }
 
-    // `callerStream`: work already queued there (e.g. the upload of the frames) is waited for first
-    const uint8_t *d_sigmaRaw = nullptr; // optional: sigma (not 6*sigma) for stacks that need the drop-in path
-    Stream copyStream;
-    std::vector<Event> copied;
-
     // Streamed mode (BASELINE configs[4]): the run sits in HOST memory (ideally pinned).  Stack groups are
     // uploaded in order on a copy stream; the trigger search of group g waits only for its own upload, so it
     // overlaps the transfer of group g+1 (double buffering in time; the slab itself stays resident for the
@@ -804,8 +837,8 @@ public:
         run(ownFrames, d_mu, d_sigma6, nullptr);
         waitCopies = false;
     }
-    bool waitCopies = false;
 
+    // `callerStream`: work already queued there (e.g. the upload of the frames) is waited for first
     void run(const uint8_t *d_frames, const uint8_t *d_mu, const uint8_t *d_sigma6, hipStream_t callerStream)
     {
         HIPOK(hipSetDevice(device));
@@ -818,7 +851,7 @@ public:
         // Stage 1 of every group goes to ONE stream in group order: the trigger search of group g+1 runs
         // on the GPU while the host threads of group g are in their state machines (two kernels launched on
         // different streams would simply share the chip and finish together, leaving nothing to overlap).
-        jobsLaunched = jobsCompleted = 0;
+        stats.reset();
         for (size_t gi = 0; gi < groups.size(); ++gi) {
             Group &G = groups[gi];
             if (waitCopies)
@@ -841,34 +874,18 @@ public:
         runGroupNoThrow(groups[0], d_frames, d_mu, d_sigma6);
         for (auto &t : th)
             t.join();
-        std::fill(tms, tms + 8, 0.0);
-        std::fill(bellowsStats, bellowsStats + 5, 0.0);
-        std::fill(blobStats, blobStats + 8, 0.0);
-        rounds = 0;
-        lastPairs = 0;
         // stacks the batched providers could not serve (bellows veto): one at a time through the drop-in path
-        dropIns = 0;
         for (int s = 0; s < S; ++s)
             if (stacks[s].dropIn) {
-                ++dropIns;
+                ++stats.dropIns;
                 runDropIn(s, d_frames, d_mu);
             }
         for (Group &G : groups) {
             if (!G.error.empty())
                 throw std::runtime_error(G.error);
-            for (int k = 0; k < 8; ++k)
-                tms[k] = std::max(tms[k], G.tms[k]);
-            bellowsStats[0] += G.vetoed;
-            bellowsStats[1] += G.matchJobs;
-            bellowsStats[2] += G.matchLaunches;
-            bellowsStats[3] += G.residualImages;
-            bellowsStats[4] += G.vetoMs;
-            for (int k = 0; k < 8; ++k)
-                blobStats[k] += G.blobs.stats[k];
-            rounds = std::max(rounds, G.rounds);
-            lastPairs += G.lastPairs;
+            stats.merge(G.stats);
         }
-        tms[4] = nowMs() - t0;
+        stats.totalMs = nowMs() - t0;
     }
 
 private:
@@ -907,35 +924,9 @@ private:
             t.ModelId = 0; // always (re)uploaded
             Trainer *tp = &t;
             L3Localizer A(evName, "", c, true, &tp, maskDir, mp.clone());
-            int staged = 0;
-            do {
-                A.FindTriggerFrame(true, A.MatTrigFrame + 1);
-                if (A.okToProceed) {
-                    A.LocalizeOMatic("");
-                    if (A.okToProceed)
-                        staged = A.BubbleList.empty() ? -1 : 0;
-                    else {
-                        staged = -8;
-                        break;
-                    }
-                } else {
-                    staged = A.TriggerFrameIdentificationStatus;
-                    break;
-                }
-            } while (A.BubbleList.size() == 0);
-            st_.staged = staged;
-            st_.trig = A.MatTrigFrame;
-            st_.status = A.TriggerFrameIdentificationStatus;
-            st_.loc_thres = A.loc_thres;
-            st_.ok = A.okToProceed;
-            for (bubble *b : A.BubbleList) {
-                BubbleOut o;
-                o.desc = b->KnownDescriptors;
-                o.dz = b->dz;
-                o.dzdt = b->dZdT();
-                o.drdt = b->dRdT();
-                st_.bubbles.push_back(std::move(o));
-            }
+            st_.staged = analyzeUntilBubble(&A, true, "", st_.error);
+            if (st_.staged != -6) // (after an exception the stack keeps the state its batched attempt ended with)
+                st_.capture(A);
         } catch (std::exception &ex) {
             st_.error = ex.what();
             st_.staged = -6;
@@ -956,11 +947,7 @@ private:
 
     void runGroup(Group &G, const uint8_t *d_frames, const uint8_t *d_mu, const uint8_t *d_sigma6)
     {
-        std::fill(G.tms, G.tms + 8, 0.0);
-        G.rounds = 0;
-        G.vetoed = G.matchJobs = G.matchLaunches = G.residualImages = 0;
-        G.vetoMs = 0;
-        std::fill(G.blobs.stats, G.blobs.stats + 8, 0.0);
+        G.stats.reset();
         const int ns = G.s1 - G.s0;
         double t0 = nowMs();
         // ---- stage 1 (already queued by run()) -----------------------------------------------------
@@ -981,7 +968,7 @@ private:
             }
             st_.data.W = W;
             st_.data.H = H;
-            st_.data.refOffset = tss[c] < 6 ? 1 : 2;
+            st_.data.refOffset = refOffset(tss[c]);
             st_.data.bellowsDropIn = bellowsDropIn;
             st_.data.clearVeto();
             st_.vetoed = false;
@@ -998,13 +985,13 @@ private:
             st_.analyzer->AttachEventData(&st_.data);
         });
         HIPOK(hipEventSynchronize(G.stage1Done.get()));
-        G.tms[0] = nowMs() - t0;
+        G.stats.stage1Ms = nowMs() - t0;
 
         std::vector<int> pending(ns);
         for (int k = 0; k < ns; ++k)
             pending[k] = G.s0 + k;
         while (!pending.empty()) {
-            ++G.rounds;
+            ++G.stats.rounds;
             // ---- stage 2: trigger search + plan ------------------------------------------------
             // A search that runs into a frame block which has not been evaluated for its stack stops there
             // (NeedMoreFrames); those blocks are evaluated -- one launch per block index -- and the searches run again.
@@ -1021,7 +1008,7 @@ private:
                 fetchBlocks(G, need, d_frames, d_sigma6);
                 todo.swap(need);
             }
-            G.tms[1] += nowMs() - t2;
+            G.stats.stage2Ms += nowMs() - t2;
             // ---- stage 3: batched images, thresholds, foreground ---------------------------------
             double t3 = nowMs();
             std::vector<int> loc;
@@ -1030,12 +1017,12 @@ private:
                     loc.push_back(s);
             if (!loc.empty())
                 batchImages(G, loc, d_frames, d_mu, d_sigma6);
-            G.tms[2] += nowMs() - t3;
+            G.stats.stage3Ms += nowMs() - t3;
             // ---- stage 4: localize + track -------------------------------------------------------
             double t4 = nowMs();
             pool->parallelFor((int)loc.size(), [&](int k) { localize(stacks[loc[k]]); });
             vetoRound(G, loc, d_frames, d_sigma6);
-            G.tms[3] += nowMs() - t4;
+            G.stats.stage4Ms += nowMs() - t4;
             std::vector<int> next;
             for (int s : pending)
                 if (!stacks[s].done)
@@ -1045,19 +1032,7 @@ private:
         // results out, analyzers released
         pool->parallelFor(ns, [&](int k) {
             StackState &st_ = stacks[G.s0 + k];
-            AnalyzerUnit *A = st_.analyzer.get();
-            st_.trig = A->MatTrigFrame;
-            st_.status = A->TriggerFrameIdentificationStatus;
-            st_.loc_thres = A->loc_thres;
-            st_.ok = A->okToProceed;
-            for (bubble *b : A->BubbleList) {
-                BubbleOut o;
-                o.desc = b->KnownDescriptors;
-                o.dz = b->dz;
-                o.dzdt = b->dZdT();
-                o.drdt = b->dRdT();
-                st_.bubbles.push_back(std::move(o));
-            }
+            st_.capture(*st_.analyzer);
             st_.analyzer.reset();
         });
     }
@@ -1104,7 +1079,7 @@ private:
                         for (size_t j = (size_t)(d.needFrame - blocks[k]); j < blen; ++j)
                             if (d.inc[k][j]) {
                                 hw[(size_t)d.slotOf[k] * blen + j] = 1;
-                                ++jobsCompleted;
+                                ++stats.jobsCompleted;
                             }
                     }
                     B.want.toDevice(nj, stream, base);
@@ -1177,7 +1152,7 @@ private:
                 return;
             }
             const int t = A->MatTrigFrame;
-            const int off = A->TrainedData->TrainingSetSize < 6 ? 1 : 2;
+            const int off = refOffset(A->TrainedData->TrainingSetSize);
             st_.data.planned.clear();
             st_.data.cur = nullptr;
             st_.data.clearVeto(); // a new trigger: new veto keys
@@ -1312,12 +1287,12 @@ private:
                 float m0 = 0, m1 = 0;
                 HIPOK(hipEventElapsedTime(&m0, B.ev[0].get(), B.ev[1].get()));
                 HIPOK(hipEventElapsedTime(&m1, B.ev[1].get(), B.ev[2].get()));
-                B.stats[6] += m0;
-                B.stats[7] += m1;
+                G.stats.blobOtsuMs += m0;
+                G.stats.blobK4bMs += m1;
             }
-            G.tms[5] += nowMs() - ta; // launches + kernels + hist/count D2H
+            G.stats.s3GpuMs += nowMs() - ta; // launches + kernels + hist/count D2H
             ta = nowMs();
-            G.lastPairs = *L.count.h;
+            G.stats.pairs = *L.count.h;
             // dense foreground (e.g. a flash frame): the kernels kept counting past the capacity, so the needed size is
             // known -- grow the lists once (the kernels that used them are done: `back` waited for them) and redo the batch
             if (L.fits(attempt, "foreground list overflow (dense foreground in too many images)"))
@@ -1330,10 +1305,12 @@ private:
                 throw std::runtime_error("RunPipeline: kept list larger than the candidate list");
             if (nkept)
                 L.kidx.toHost(nkept, back);
-            const double add[6] = {(double)cnt, (double)B.kstats.h[1], (double)nkept, (double)B.kstats.h[2],
-                                   (double)B.kstats.h[3], (double)B.kstats.h[0]};
-            for (int k = 0; k < 6; ++k)
-                B.stats[k] += add[k];
+            G.stats.blobCandidates += cnt;
+            G.stats.blobForeground += B.kstats.h[1];
+            G.stats.blobKept += nkept;
+            G.stats.blobComponents += B.kstats.h[2];
+            G.stats.blobKeptComponents += B.kstats.h[3];
+            G.stats.blobLargeSlots += B.kstats.h[0];
         } else
             L.pairsToHost(back);
         // thresholds (TOZERO + Otsu) on the host from the histograms, while the list travels
@@ -1355,7 +1332,7 @@ private:
             }
         });
         HIPOK(hipStreamSynchronize(back));
-        G.tms[6] += nowMs() - ta; // list D2H (+ thresholds)
+        G.stats.s3ListMs += nowMs() - ta; // list D2H (+ thresholds)
     }
 
     // ---- bellows veto round ----------------------------------------------------------------------------------------
@@ -1407,7 +1384,7 @@ private:
             pool->parallelFor((int)ask.size(), [&](int k) { localize(stacks[ask[k]]); });
         }
         if (any)
-            G.vetoMs += nowMs() - t0;
+            G.stats.vetoMs += nowMs() - t0;
     }
 
     struct VetoFallback {};
@@ -1417,7 +1394,7 @@ private:
     const uint8_t *deviceTemplate(Group &G, const cv::Mat &t)
     {
         for (auto &e : G.veto.templates)
-            if (e.first.data == t.data && e.first.cols == t.cols && e.first.rows == t.rows)
+            if (sameTemplate(e.first, t))
                 return e.second;
         DeviceArray<uint8_t> d;
         d.allocate(t.total());
@@ -1436,7 +1413,7 @@ private:
                 if (m.ready)
                     continue;
                 size_t t = 0;
-                while (t < tpl.size() && !(tpl[t].data == m.templ.data && tpl[t].cols == m.templ.cols && tpl[t].rows == m.templ.rows))
+                while (t < tpl.size() && !sameTemplate(tpl[t], m.templ))
                     ++t;
                 if (t == tpl.size()) {
                     tpl.push_back(m.templ);
@@ -1483,7 +1460,7 @@ private:
                 throw VetoFallback();
             check(rc, "bellows veto match");
             off += n;
-            ++G.matchLaunches;
+            ++G.stats.matchLaunches;
         }
         V.xy.toHost(2 * (size_t)total, st);
         HIPOK(hipStreamSynchronize(st));
@@ -1494,7 +1471,7 @@ private:
                 r.second->ready = true;
                 ++off;
             }
-        G.matchJobs += total;
+        G.stats.matchJobs += total;
         return true;
     }
 
@@ -1589,10 +1566,10 @@ private:
             r.ready = true;
             if (!stacks[s].vetoed) {
                 stacks[s].vetoed = true;
-                ++G.vetoed;
+                ++G.stats.vetoed;
             }
         }
-        G.residualImages += n;
+        G.stats.residualImages += n;
         return true;
     }
 
@@ -1651,11 +1628,7 @@ RunPipelinePtr newRunPipeline(int device, int W, int H, int F, int E, int C, con
 void setSigmaRaw(RunPipeline &p, const uint8_t *d_sigma) { p.d_sigmaRaw = d_sigma; }
 bool setTrainingSetSizes(RunPipeline &p, const int *tss)
 {
-    int stride = tss[0] < 6 ? 1 : 2; // (as the constructor decides it)
-    for (int c = 1; c < p.C; ++c)
-        if ((tss[c] < 6 ? 1 : 2) != stride)
-            stride = 0;
-    if (stride != p.chainStride)
+    if (chainStrideOf(tss, p.C) != p.chainStride)
         return false;
     for (int c = 0; c < p.C; ++c) {
         p.tss[c] = tss[c];
@@ -1669,7 +1642,7 @@ void run(RunPipeline &p, const uint8_t *d_frames, const uint8_t *d_mu, const uin
     p.run(d_frames, d_mu, d_sigma6, stream);
 }
 void writeEvent(RunPipeline &p, int k, int eventNumber, OutputWriter &out) { p.writeEvent(k, eventNumber, out); }
-int bellowsVetoed(const RunPipeline &p) { return (int)p.bellowsStats[0]; }
+int bellowsVetoed(const RunPipeline &p) { return p.stats.vetoed; }
 
 } // namespace abub
 
@@ -1716,48 +1689,20 @@ int abh_pipe_run_host(void *p, const void *frames_host, const void *mu_dev, cons
     }
 }
 
-// out: staged, trig, status, loc_thres, ok, nbubbles
-void abh_pipe_result(void *p, int s, int *out)
+// stack s of the last run as a StackResult for the abh_result_* readers (capi.cpp)
+const void *abh_pipe_stack(void *p, int s)
 {
-    abub::StackState &st = ((abub::RunPipeline *)p)->stacks[s];
-    out[0] = st.staged;
-    out[1] = st.trig;
-    out[2] = st.status;
-    out[3] = st.loc_thres;
-    out[4] = st.ok;
-    out[5] = (int)st.bubbles.size();
+    const abub::StackResult &res = ((abub::RunPipeline *)p)->stacks[s];
+    return &res;
 }
-int abh_pipe_ndesc(void *p, int s, int b) { return (int)((abub::RunPipeline *)p)->stacks[s].bubbles[b].desc.size(); }
-void abh_pipe_desc(void *p, int s, int b, int d, double *out)
-{
-    const BubbleImageFrame &f = ((abub::RunPipeline *)p)->stacks[s].bubbles[b].desc[d];
-    out[0] = f.newPosition.x;
-    out[1] = f.newPosition.y;
-    out[2] = f.newPosition.width;
-    out[3] = f.newPosition.height;
-    out[4] = f.ContArea;
-    out[5] = f.ContRadius;
-    out[6] = f.moments.m00;
-    out[7] = f.moments.m10;
-    out[8] = f.moments.m01;
-    out[9] = f.MassCentres.x;
-    out[10] = f.MassCentres.y;
-}
-float abh_pipe_dzdt(void *p, int s, int b) { return ((abub::RunPipeline *)p)->stacks[s].bubbles[b].dzdt; }
-float abh_pipe_drdt(void *p, int s, int b) { return ((abub::RunPipeline *)p)->stacks[s].bubbles[b].drdt; }
-const char *abh_pipe_stack_error(void *p, int s) { return ((abub::RunPipeline *)p)->stacks[s].error.c_str(); }
-// out[0..11]: stage1 .. stage4, total, stage-3 details (ms), candidate pairs, trigger-search jobs, drop-in stacks,
-// jobs completed on demand of the last run;
-// returns the number of rounds
-int abh_pipe_timing(void *p, double *out);
 
 // out[0..4] of the last run: stacks whose bellows veto ran in the batch, template-match jobs, match launches, residual
 // images, wall time of the veto rounds (ms, summed over the stack groups)
 void abh_pipe_bellows(void *p, double *out)
 {
-    abub::RunPipeline *r = (abub::RunPipeline *)p;
-    for (int k = 0; k < 5; ++k)
-        out[k] = r->bellowsStats[k];
+    const abub::PipeStats &st = ((abub::RunPipeline *)p)->stats;
+    const double v[5] = {(double)st.vetoed, (double)st.matchJobs, (double)st.matchLaunches, (double)st.residualImages, st.vetoMs};
+    std::memcpy(out, v, sizeof v);
 }
 
 // Run-time knobs of one pipeline object: "blobs" (0 = the host applies the Otsu cut to every candidate pixel, 1 = the
@@ -1786,20 +1731,21 @@ int abh_pipe_set_option(void *p, const char *name, int value)
 // labelled on the global-memory path, ms of the Otsu launches, ms of the K4b launches
 void abh_pipe_blob_stats(void *p, double *out)
 {
-    abub::RunPipeline *r = (abub::RunPipeline *)p;
-    for (int k = 0; k < 8; ++k)
-        out[k] = r->blobStats[k];
+    const abub::PipeStats &st = ((abub::RunPipeline *)p)->stats;
+    const double v[8] = {(double)st.blobCandidates, (double)st.blobForeground, (double)st.blobKept, (double)st.blobComponents,
+                         (double)st.blobKeptComponents, (double)st.blobLargeSlots, st.blobOtsuMs, st.blobK4bMs};
+    std::memcpy(out, v, sizeof v);
 }
 
+// out[0..11] of the last run: stage1 .. stage4, total, stage-3 launches + kernels, stage-3 list transfer, an unused slot
+// (ms), candidate pairs, trigger-search jobs, drop-in stacks, jobs completed on demand; returns the number of rounds
 int abh_pipe_timing(void *p, double *out)
 {
-    abub::RunPipeline *r = (abub::RunPipeline *)p;
-    for (int k = 0; k < 8; ++k)
-        out[k] = r->tms[k];
-    out[8] = r->lastPairs;
-    out[9] = (double)r->jobsLaunched; // trigger-search jobs the run evaluated (S * (F - 1) when nothing is lazy)
-    out[10] = (double)r->dropIns;     // stacks re-run one at a time (bellows veto)
-    out[11] = (double)r->jobsCompleted; // trigger-search jobs whose dense rows were evaluated on demand (deferred pieces)
-    return r->rounds;
+    const abub::PipeStats &st = ((abub::RunPipeline *)p)->stats;
+    const double v[12] = {st.stage1Ms, st.stage2Ms, st.stage3Ms, st.stage4Ms, st.totalMs, st.s3GpuMs, st.s3ListMs,
+                          0.0, // (s3_bucket_ms: the key stays in the reports, nothing writes it)
+                          (double)st.pairs, (double)st.jobsLaunched, (double)st.dropIns, (double)st.jobsCompleted};
+    std::memcpy(out, v, sizeof v);
+    return st.rounds;
 }
 }

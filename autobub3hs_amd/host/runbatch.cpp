@@ -573,7 +573,7 @@ PreparedRun PrepareRun(const RunSpec &r, const BatchedRunOptions &opt, int train
         pr.rc = -5;
         return pr;
     }
-    std::sort(pr.events.begin(), pr.events.end(), [](const std::string &a, const std::string &b) { return std::stoi(a) < std::stoi(b); });
+    sortEvents(pr.events);
 
     say(pr, buffered, "**Starting training. AutoBub is in learn mode**\n");
     const double t0 = nowMs();
