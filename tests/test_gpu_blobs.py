@@ -12,6 +12,7 @@ torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 from autobub3hs_amd import _lib, host, synth  # noqa: E402
+from blobscenes import _assert_same_outputs, _check, _grouped, _launch, _slot_image  # noqa: E402
 
 DEV = "cuda:0"
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -85,102 +86,6 @@ def test_device_otsu_equals_host(W, H):
 
 
 # ---- K4b -----------------------------------------------------------------------------------------------------------------
-
-def _slot_image(rs, W, H, kind):
-    """-> values u8 [H, W]; the candidate list of a slot is every pixel with value > 0"""
-    v = np.zeros((H, W), np.uint8)
-    if kind == "empty":
-        return v
-    if kind == "large":  # >= 200k foreground pixels: the global-memory path
-        m = rs.rand(H, W) < 0.35
-        v[m] = rs.randint(1, 256, m.sum())
-        return v
-    n = rs.randint(1, 1500)
-    ys, xs = rs.randint(0, H, n), rs.randint(0, W, n)
-    v[ys, xs] = rs.randint(1, 256, n)
-    for _ in range(rs.randint(0, 6)):  # a few blobs, some on the edges
-        h, w = rs.randint(1, 12), rs.randint(1, 12)
-        y, x = rs.randint(-3, H), rs.randint(-3, W)
-        y0, y1, x0, x1 = max(y, 0), min(y + h, H), max(x, 0), min(x + w, W)
-        if y1 > y0 and x1 > x0:
-            v[y0:y1, x0:x1] = np.maximum(v[y0:y1, x0:x1], rs.randint(100, 256, (y1 - y0, x1 - x0)).astype(np.uint8))
-    return v
-
-
-def _grouped(imgs, rs):
-    """grouped candidate list as abub_pairs_group_*_dev leave it: per slot contiguous, unordered inside the slot"""
-    offs, idx, val = [0], [], []
-    for v in imgs:
-        i = np.flatnonzero(v.ravel()).astype(np.int64)
-        rs.shuffle(i)
-        idx.append(i)
-        val.append(v.ravel()[i])
-        offs.append(offs[-1] + len(i))
-    idx = np.concatenate(idx) if idx else np.zeros(0, np.int64)
-    val = np.concatenate(val) if val else np.zeros(0, np.uint8)
-    return np.array(offs, np.int64), idx, val
-
-
-def _reference(v, thr, mb):
-    from scipy import ndimage
-
-    m = v > thr
-    lab, n = ndimage.label(m, structure=np.ones((3, 3)))
-    comps = []
-    keep = np.zeros(n + 1, bool)
-    first = ndimage.minimum(np.arange(v.size).reshape(v.shape), lab, np.arange(1, n + 1)) if n else []
-    counts = np.bincount(lab.ravel(), minlength=n + 1)
-    for k, sl in enumerate(ndimage.find_objects(lab), start=1):
-        y0, y1, x0, x1 = sl[0].start, sl[0].stop - 1, sl[1].start, sl[1].stop - 1
-        keep[k] = mb < 0 or (x1 - x0 + 1) * (y1 - y0 + 1) > mb
-        if keep[k]:
-            comps.append((int(first[k - 1]), x0, y0, x1, y1, int(counts[k])))
-    comps.sort()
-    kept = np.flatnonzero(keep[lab].ravel() & m.ravel())
-    return n, comps, kept
-
-
-def _launch(imgs, thr, mb, W, H, rs, **kw):
-    from autobub3hs_amd import hip
-
-    offs, idx, val = _grouped(imgs, rs)
-    t = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a).astype(dt)).to(DEV)  # noqa: E731
-    out = hip.label_blobs(t(offs, np.int32), t(np.concatenate([idx, [0]]), np.int32), t(np.concatenate([val, [0]]), np.uint8),
-                          t(thr, np.int32), t(mb, np.int32), W, H, **kw)
-    return {k: (None if v is None else v.cpu().numpy()) for k, v in out.items()}, offs
-
-
-def _check(imgs, thr, mb, out):
-    n = len(imgs)
-    ko, co = out["kept_off"].astype(np.int64), out["comp_off"].astype(np.int64)
-    fg = ncomp_total = nkept_total = 0
-    for s in range(n):
-        ncomp, comps, kept = _reference(imgs[s], thr[s], mb[s])
-        fg += int((imgs[s] > thr[s]).sum())
-        ncomp_total += ncomp
-        nkept_total += len(comps)
-        assert out["ncomp"][s] == ncomp, (s, out["ncomp"][s], ncomp)
-        assert out["nkept_comp"][s] == len(comps)
-        assert np.array_equal(out["kept_idx"][ko[s]:ko[s + 1]], kept), s
-        assert co[s + 1] - co[s] == len(comps)
-        got = [tuple(int(x) for x in r) for r in out["comp"][co[s]:co[s + 1]]]
-        assert got == comps, (s, got[:5], comps[:5])
-    st = out["stats"]
-    assert (st[1], st[2], st[3]) == (fg, ncomp_total, nkept_total)
-    return st
-
-
-def _assert_same_outputs(out, out2):
-    """two launches wrote the same outputs: every array, but kept_idx and comp only up to their counts (the rest of those
-    buffers is never written: torch.empty)"""
-    for k in out:
-        a, b = out[k], out2[k]
-        if k == "kept_idx":
-            a, b = a[:out["kept_off"][-1]], b[:out2["kept_off"][-1]]
-        elif k == "comp":
-            a, b = a[:out["comp_off"][-1]], b[:out2["comp_off"][-1]]
-        assert np.array_equal(a, b), k
-
 
 @pytest.mark.parametrize("W,H", [(1280, 96), (1280, 1024), (1680, 1050)])
 def test_label_blobs_equals_scipy(W, H):
