@@ -18,7 +18,7 @@ struct abub_ctx {
     uint8_t *d_img;     // [H][W]         current image (last D or post-trigger image)
     uint32_t *d_hist;   // [maxF][256]
     abub_job *d_jobs;   // [maxF]
-    uint32_t *d_idx;    // [idx_cap]
+    uint32_t *d_idx;    // [idx_cap], grown on demand by abub_ctx_foreground
     uint32_t *d_count;
     int32_t *d_thr;
     int idx_cap;
@@ -26,7 +26,7 @@ struct abub_ctx {
     uint32_t *h_hist;   // pinned [maxF][256]
     abub_job *h_job;    // pinned [1]
     uint32_t *h_small;  // pinned [4]
-    uint32_t *h_idx;    // pinned [idx_cap]
+    uint32_t *h_idx;    // pinned [idx_cap], grown with d_idx
     int F;
     int have_model;
 };
@@ -122,13 +122,20 @@ extern "C" void abub_ctx_destroy(abub_ctx *c)
     free(c);
 }
 
+// every frame pointer is checked before the first copy: a refused call leaves the resident stack as it was
+static bool any_null(const uint8_t *const *frames, int n)
+{
+    for (int k = 0; k < n; k++)
+        if (!frames[k])
+            return true;
+    return false;
+}
+
 // stage host frames through pinned memory, one async H2D per frame so that the next host memcpy
 // overlaps the previous transfer
 static int upload_frames(abub_ctx *c, const uint8_t *const *frames, int n, uint8_t *d_dst, uint8_t *h_stage)
 {
     for (int k = 0; k < n; k++) {
-        if (!frames[k])
-            return cfail(ABUB_E_INVALID, "upload_frames: null frame pointer");
         memcpy(h_stage + (size_t)k * c->P, frames[k], c->P);
         CCHK(hipMemcpyAsync(d_dst + (size_t)k * c->P, h_stage + (size_t)k * c->P, c->P,
                             hipMemcpyHostToDevice, c->stream));
@@ -141,16 +148,22 @@ extern "C" int abub_ctx_train(abub_ctx *c, const uint8_t *const *frames, int N, 
 {
     if (!c || !frames || N <= 0 || !mu_out || !sigma_out)
         return cfail(ABUB_E_INVALID, "abub_ctx_train: bad arguments");
+    if (any_null(frames, N))
+        return cfail(ABUB_E_INVALID, "abub_ctx_train: null frame pointer");
     CCHK(hipSetDevice(c->device));
     uint8_t *d_train = nullptr, *h_st = nullptr;
     bool own = N > c->maxF;
+    c->F = 0; // the resident stack is overwritten when N fits the slab; it is given up either way
     if (own) {
         CCHK(hipMalloc((void **)&d_train, c->P * (size_t)N));
-        CCHK(hipHostMalloc((void **)&h_st, c->P * (size_t)N, hipHostMallocDefault));
+        hipError_t e = hipHostMalloc((void **)&h_st, c->P * (size_t)N, hipHostMallocDefault);
+        if (e != hipSuccess) {
+            (void)hipFree(d_train);
+            return cfail(ABUB_E_HIP, "abub_ctx_train: hipHostMalloc", e);
+        }
     } else {
         d_train = c->d_frames;
         h_st = c->h_stage;
-        c->F = 0; // the resident stack is overwritten
     }
     int rc = upload_frames(c, frames, N, d_train, h_st);
     if (rc == ABUB_OK)
@@ -212,7 +225,10 @@ extern "C" int abub_ctx_upload_stack(abub_ctx *c, const uint8_t *const *frames, 
 {
     if (!c || !frames || F <= 0 || F > c->maxF)
         return cfail(ABUB_E_INVALID, "abub_ctx_upload_stack: bad arguments (F > max_frames?)");
+    if (any_null(frames, F))
+        return cfail(ABUB_E_INVALID, "abub_ctx_upload_stack: null frame pointer");
     CCHK(hipSetDevice(c->device));
+    c->F = 0; // a copy that fails half way leaves no stack rather than a mixed one
     CALL(upload_frames(c, frames, F, c->d_frames, c->h_stage));
     c->F = F;
     return ABUB_OK;
@@ -303,12 +319,35 @@ extern "C" int abub_ctx_posttrig(abub_ctx *c, int i, uint8_t *O_out, uint32_t *h
     return finish_image(c, O_out, hist_out);
 }
 
+// the index buffers hold 1 << 16 entries from abub_ctx_create on; a larger request replaces them (new ones first, so
+// that a failed allocation leaves the context usable)
+static int grow_idx(abub_ctx *c, int want)
+{
+    uint32_t *d = nullptr, *h = nullptr;
+    CCHK(hipMalloc((void **)&d, (size_t)want * sizeof(uint32_t)));
+    hipError_t e = hipHostMalloc((void **)&h, (size_t)want * sizeof(uint32_t), hipHostMallocDefault);
+    if (e != hipSuccess) {
+        (void)hipFree(d);
+        return cfail(ABUB_E_HIP, "abub_ctx_foreground: hipHostMalloc", e);
+    }
+    (void)hipStreamSynchronize(c->stream);
+    (void)hipFree(c->d_idx);
+    (void)hipHostFree(c->h_idx);
+    c->d_idx = d;
+    c->h_idx = h;
+    c->idx_cap = want;
+    return ABUB_OK;
+}
+
 extern "C" int abub_ctx_foreground(abub_ctx *c, int thr, uint32_t *idx_out, int cap, int *n)
 {
     if (!c || !idx_out || !n || cap <= 0)
         return cfail(ABUB_E_INVALID, "abub_ctx_foreground: bad arguments");
     CCHK(hipSetDevice(c->device));
-    int dcap = cap < c->idx_cap ? cap : c->idx_cap;
+    // no image has more than W*H foreground pixels: min(cap, W*H) entries serve any cap
+    int dcap = (size_t)cap < c->P ? cap : (int)c->P;
+    if (dcap > c->idx_cap)
+        CALL(grow_idx(c, dcap));
     int32_t *h_thr = reinterpret_cast<int32_t *>(c->h_small);
     *h_thr = thr;
     CCHK(hipMemcpyAsync(c->d_thr, h_thr, sizeof(int32_t), hipMemcpyHostToDevice, c->stream));

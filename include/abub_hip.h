@@ -67,8 +67,9 @@ int abub_fill_stack_jobs_dev(abub_job *jobs, int nstacks, int F, int first, int 
  *   jobs    : njobs entries (device)         hist   : [nslots][256] u32 (device), fully overwritten
  *   diff    : NULL (trigger-only mode, 3*W*H algorithmic bytes/job) or [nslots][H][W] u8
  *             (store mode, 4*W*H bytes/job)
- *   rows_per_chunk: 0 = auto.  Fast register-rolling kernel when W%4==0 and W<=2048, generic
- *   LDS-tile kernel otherwise (same results). */
+ *   rows_per_chunk: 0 = auto.  Fast register-rolling kernel when abub_fast_path(W) != 0: W % 4 == 0 and
+ *   W / 4 = ndw * lanes with ndw <= 8 dwords per lane and lanes <= 64 (so W <= 2048, and e.g. 268 = 4 * 67,
+ *   536 and 2052 are not fast-path widths); generic LDS-tile kernel otherwise (same results). */
 int abub_diff_hist_dev(const uint8_t *frames, const uint8_t *sigma6, const abub_job *jobs, int njobs,
                        int W, int H, uint32_t *hist, uint8_t *diff, int rows_per_chunk, void *stream);
 
@@ -282,17 +283,22 @@ void abub_ctx_destroy(abub_ctx *ctx);
 
 /* Trainer::CalculateMeanSigmaImageVector on N host frames (Trainer.cpp:316); fills host mu/sigma.
  * N is not limited by max_frames: a training set larger than the ctx slab gets a temporary device slab of
- * N frames for the call (the Welford recurrence needs every frame of a pixel in order). */
+ * N frames for the call (the Welford recurrence needs every frame of a pixel in order).
+ * The trained model becomes the context's current model.  The resident frame stack is given up, whatever N is:
+ * the frame calls below are refused until the next abub_ctx_upload_stack.  Every frame pointer is checked
+ * before the first copy (a null one: ABUB_E_INVALID, model and stack untouched). */
 int abub_ctx_train(abub_ctx *ctx, const uint8_t *const *frames, int N, uint8_t *mu_out,
                    uint8_t *sigma_out);
-/* 256-bin histogram of sat(f1 - f0) (training entropy veto, Trainer.cpp:279-280). */
+/* 256-bin histogram of sat(f1 - f0) (training entropy veto, Trainer.cpp:279-280).  Uses the frame slab: the
+ * resident frame stack is given up, as after abub_ctx_train. */
 int abub_ctx_pair_hist(abub_ctx *ctx, const uint8_t *f0, const uint8_t *f1, uint32_t hist[256]);
 
 /* Make (mu, sigma) the context's current model (AnalyzerUnit.cpp:27 deep-copies the Trainer per
  * analyzer; here the model lives once in HBM). */
 int abub_ctx_set_model(abub_ctx *ctx, const uint8_t *mu, const uint8_t *sigma);
 
-/* Upload the frame stack of one (event, camera): F host frame pointers (Parser::GetImage results). */
+/* Upload the frame stack of one (event, camera): F host frame pointers (Parser::GetImage results).
+ * F > max_frames or a null pointer among them: ABUB_E_INVALID, and the previous stack stays as it was. */
 int abub_ctx_upload_stack(abub_ctx *ctx, const uint8_t *const *frames, int F);
 
 /* Histograms of D(frame[i]; frame[max(i-ref_offset,0)]) for i in [first, first+count):
@@ -311,7 +317,8 @@ int abub_ctx_diff_frame_roi(abub_ctx *ctx, int i, int ref, int rx, int ry, int r
 int abub_ctx_posttrig(abub_ctx *ctx, int i, uint8_t *O_out, uint32_t *hist_out);
 
 /* Foreground pixels (v > thr) of the current image as raster indices; *n = true count.
- * Returns ABUB_E_OVERFLOW if *n > cap (idx_out then holds the first cap found). */
+ * Returns ABUB_E_OVERFLOW if *n > cap (idx_out then holds the first cap found).  Any cap: the context's index
+ * buffers grow on demand beyond their initial 65536 entries (up to W*H). */
 int abub_ctx_foreground(abub_ctx *ctx, int thr, uint32_t *idx_out, int cap, int *n);
 
 /* Bellows veto: correlation terms of resident frame i against a host template (see abub_match_ccorr_dev);
