@@ -93,11 +93,14 @@ __device__ __forceinline__ uint32_t widen8_hi(uint32_t w) { return __builtin_amd
 __device__ __forceinline__ uint32_t pack8(uint32_t a, uint32_t b) { return __builtin_amdgcn_perm(b, a, 0x07050301u); }
 
 
-static __global__ __launch_bounds__(64) void k_hist_bin0(uint32_t *hist, uint32_t P, const uint8_t *__restrict__ only = nullptr)
+// One block per slot; with `only` (deferred pieces) one block per JOB: only[] is indexed by job like want[] / incomplete[],
+// the histogram by the job's output slot, and only the jobs whose rows were just completed are finalised.
+static __global__ __launch_bounds__(64) void k_hist_bin0(uint32_t *hist, uint32_t P, const uint8_t *__restrict__ only = nullptr,
+                                                         const abub_job *__restrict__ jobs = nullptr)
 {
-    if (only && !only[blockIdx.x]) // (deferred pieces: only the slots whose rows were just completed)
+    if (only && !only[blockIdx.x])
         return;
-    uint32_t *h = hist + (size_t)blockIdx.x * 256;
+    uint32_t *h = hist + (size_t)(jobs ? jobs[blockIdx.x].out : blockIdx.x) * 256;
     int l = threadIdx.x;
     uint32_t s = h[l + 64] + h[l + 128] + h[l + 192] + (l ? h[l] : 0u);
     for (int o = 32; o > 0; o >>= 1)

@@ -1436,7 +1436,7 @@ extern "C" int abub_diff_hist_pieces_dev(const uint8_t *frames, const uint8_t *s
     }
     HIPCHK(hipGetLastError());
     // bin 0 of the jobs whose rows are complete now (the deferred launch computed it from partial counts)
-    hipLaunchKernelGGL(k_hist_bin0, dim3(njobs), dim3(64), 0, st, hist, (uint32_t)((size_t)W * H), want);
+    hipLaunchKernelGGL(k_hist_bin0, dim3(njobs), dim3(64), 0, st, hist, (uint32_t)((size_t)W * H), want, jobs);
     HIPCHK(hipGetLastError());
     return ABUB_OK;
 }

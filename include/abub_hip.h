@@ -41,6 +41,10 @@ typedef struct {
     uint32_t model; /* index into the [nmodels][H][W] sigma6 / mu slabs         */
     uint32_t out;   /* output slot: hist[out][256] and, if stored, img[out][H][W] */
 } abub_job;
+/* The `out` values of one launch's njobs jobs are a permutation of 0 .. njobs - 1 (the launchers clear and finalise
+ * exactly those slots); a job need not write its own index.  Per-slot arguments (hist, diff / img, cthr, the list slot)
+ * are indexed by `out`; per-job arguments (the jobs themselves, `incomplete` and `want` of the deferred pieces) by the
+ * job's position in the list. */
 
 const char *abub_last_error(void);
 int abub_device_count(void);
@@ -134,7 +138,8 @@ int abub_diff_hist_chained_store_dev(const uint8_t *frames, const uint8_t *sigma
  * caller's `pieces` list (abub_k2_pieces_cap(njobs, W, H) entries of 8 bytes, `*npieces` used) and incomplete[job] (njobs
  * bytes) is set to 1 for every job that has some -- the histograms of exactly those jobs are not final.
  * abub_diff_hist_pieces_dev() then runs the row machine on the pieces of the jobs with want[job] != 0 (njobs bytes) and
- * finalises their histograms; same frames / sigma6 / jobs / njobs / hist as the deferred call.  A job must be completed at
+ * finalises their histograms; same frames / sigma6 / jobs / njobs / hist as the deferred call.  incomplete[] and want[]
+ * are indexed by job (position in `jobs`), the histograms by the job's slot: job j is completed in hist[jobs[j].out].  A job must be completed at
  * most once.  Needs abub_fast_path(W) and the "bound" option on. */
 size_t abub_k2_pieces_cap(int njobs, int W, int H);
 int abub_diff_hist_chained_deferred_dev(const uint8_t *frames, const uint8_t *sigma6, const abub_job *jobs, int njobs, int W,

@@ -7,6 +7,7 @@ torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 from autobub3hs_amd import hip, synth  # noqa: E402
+from scanscenes import PARTIAL_WIDTHS, decision_boundary_stack  # noqa: E402
 
 DEV = "cuda:0"
 
@@ -45,7 +46,7 @@ K2_SHAPES = [
     (64, 1280, 0), (50, 1680, 0), (37, 256, 8), (40, 512, 16), (33, 768, 0), (16, 1024, 8),
     (9, 1536, 0), (21, 2048, 8), (64, 100, 16),      # fast path NDW = 5,7,1,2,3,4,6,8,1(25 lanes)
     (37, 53, 0), (5, 5, 0), (12, 6, 0), (1, 16, 0), (2, 8, 0), (3, 4, 0),  # generic / degenerate
-]
+] + [(37, W, R) for W in PARTIAL_WIDTHS for R in (0, 16)]  # partial waves of NDW = 2, 3, 4, 5, 6, 7, 8
 
 
 @pytest.mark.parametrize("H,W,R", K2_SHAPES)
@@ -105,26 +106,7 @@ def test_k2_chained_scan_decision_boundary_and_saturation(oracle, W, H):
     Histograms and stored D must equal the oracle's for every jobs-per-wave / workgroup setting."""
     rs = np.random.RandomState(W + 7 * H)
     n = 11
-    base = rs.randint(0, 256, (H, W)).astype(np.int64)
-    base[:, : W // 8] = 0            # c, r at the low rail
-    base[:, W // 8: W // 4] = 255    # ... and at the high rail
-    frames = np.repeat(base[None], n, 0)
-    for f in range(n):
-        k = rs.randint(100, 500)
-        ys, xs = rs.randint(0, H, k), rs.randint(0, W, k)
-        frames[f, ys, xs] += rs.choice([-1, 1], k) * rs.randint(1, 7, k)
-        for _ in range(20):  # tight clusters whose masses cross the bound only together
-            y, x = rs.randint(0, H - 1), rs.randint(0, W - 2)
-            frames[f, y, x] += rs.randint(1, 4)
-            frames[f, y + rs.randint(0, 2), x + rs.randint(0, 3)] += rs.randint(1, 4)
-        for (y, x) in [(0, 0), (0, 1), (1, 0), (H - 1, W - 1), (H - 2, W - 1), (H - 1, W - 2), (0, W - 1), (H - 1, 0)]:
-            frames[f, y, x] += rs.randint(-6, 7)
-        if f % 3 == 2:  # large excursions: |c - r| up to 255
-            ys, xs = rs.randint(0, H, 60), rs.randint(0, W, 60)
-            frames[f, ys, xs] = rs.choice([0, 255], 60)
-    frames = np.clip(frames, 0, 255).astype(np.uint8)
-    sigma = np.zeros((2, H, W), np.uint8)
-    sigma[1] = rs.choice([0, 0, 1, 1, 2, 7, 20, 42, 43, 255], (H, W))  # sigma6 = 0 .. 252, 255 (saturated)
+    frames, sigma = decision_boundary_stack(rs, n, H, W)
     f_d = torch.from_numpy(frames).to(DEV)
     s6 = hip.sigma6(torch.from_numpy(sigma).to(DEV))
     for model in (0, 1):

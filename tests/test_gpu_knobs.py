@@ -94,7 +94,7 @@ PF2_SHAPES = [
     (64, 1280, 0), (50, 1680, 0), (37, 256, 8), (40, 512, 16), (33, 768, 0), (16, 1024, 8), (9, 1536, 0), (21, 2048, 8),
     (64, 100, 16),                                      # every fast-path NDW (5, 7, 1, 2, 3, 4, 6, 8, 1 with 25 lanes)
     (17, 1280, 16), (33, 1680, 16), (17, 256, 16), (2, 1024, 16), (1, 512, 0),  # last chunk shorter than the ring
-]
+] + [(37, W, R) for W in (264, 276, 560, 1100, 792, 1400, 1088) for R in (0, 16)]  # partial waves of NDW = 2 .. 8
 
 
 @pytest.mark.parametrize("H,W,R", PF2_SHAPES)
