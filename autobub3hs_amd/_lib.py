@@ -66,6 +66,10 @@ SIGNATURES = {
     "abub_label_blobs_dev": (_i, [_vp, _vp, _vp, C.c_uint32, _i, _i, _i, _vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, _vp, _vp,
                                   C.c_uint32, _vp, _vp, _sz, _vp]),
     "abub_label_blobs_scratch_bytes": (_sz, [_i, _i, _i, C.c_uint32, _i]),
+    "abub_trace_contours_dev": (_i, [_vp, _vp, C.c_uint32, _i, _i, _i, _vp, _vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32,
+                                     _vp, _vp, _sz, _vp]),
+    "abub_trace_contours_scratch_bytes": (_sz, [_i, C.c_uint32]),
+    "abub_trace_contours_limits": (_i, [C.POINTER(_i), C.POINTER(_i)]),
     "abub_ctx_create": (_i, [C.POINTER(_vp), _i, _i, _i, _i]),
     "abub_ctx_destroy": (None, [_vp]),
     "abub_ctx_train": (_i, [_vp, C.POINTER(_vp), _i, _vp, _vp]),

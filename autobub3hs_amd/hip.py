@@ -210,6 +210,41 @@ def label_blobs(offsets, idx, val, thr, min_box_area, W, H, cap=None, comp=True,
                "abub_label_blobs_dev")
     return out
 
+def trace_contours_limits():
+    """(max_pixels, max_chain) of K5: a slot with more kept pixels, or with a border chain of more codes, is declined."""
+    import ctypes as C
+    mp, mc = C.c_int(0), C.c_int(0)
+    _lib.check(_lib.lib().abub_trace_contours_limits(C.byref(mp), C.byref(mc)), "abub_trace_contours_limits")
+    return mp.value, mc.value
+
+
+def trace_contours(kept_off, kept_idx, W, H, cont_cap=None, pts_cap=None, in_cap=None):
+    """K5 (abub_trace_contours_dev) on K4b's kept lists: kept_off int32 [n+1], kept_idx int32 -> dict of device tensors
+    status [n] (0 traced, 1 declined: trace on the host), ncont [n], cont_off [n+1], cont_npts [cont_cap], pt_off [n+1],
+    pts [pts_cap] (x | y << 16), stats [4] (slots traced, slots declined, contours, vertices).  Offsets are true counts;
+    the capacities default to the list's length and four times it."""
+    _need_cuda(kept_off, kept_idx)
+    n = kept_off.numel() - 1
+    dev = kept_idx.device
+    in_cap = int(kept_idx.numel()) if in_cap is None else int(in_cap)
+    cont_cap = max(in_cap, 1) if cont_cap is None else int(cont_cap)
+    pts_cap = max(4 * in_cap, 1) if pts_cap is None else int(pts_cap)
+    L = _lib.lib()
+    need = int(L.abub_trace_contours_scratch_bytes(n, in_cap))
+    scratch = torch.empty((max(need, 1),), dtype=torch.uint8, device=dev)
+    out = {"status": torch.empty((n,), dtype=torch.int32, device=dev),
+           "ncont": torch.empty((n,), dtype=torch.int32, device=dev),
+           "cont_off": torch.empty((n + 1,), dtype=torch.int32, device=dev),
+           "cont_npts": torch.empty((cont_cap,), dtype=torch.int32, device=dev),
+           "pt_off": torch.empty((n + 1,), dtype=torch.int32, device=dev),
+           "pts": torch.empty((pts_cap,), dtype=torch.int32, device=dev),
+           "stats": torch.empty((4,), dtype=torch.int32, device=dev)}
+    _lib.check(L.abub_trace_contours_dev(_ptr(kept_off), _ptr(kept_idx), in_cap, n, W, H, _ptr(out["status"]),
+                                         _ptr(out["ncont"]), _ptr(out["cont_off"]), _ptr(out["cont_npts"]), cont_cap,
+                                         _ptr(out["pt_off"]), _ptr(out["pts"]), pts_cap, _ptr(out["stats"]), _ptr(scratch),
+                                         scratch.numel(), _stream()), "abub_trace_contours_dev")
+    return out
+
 # ---- PNG frames decoded on the GPU (abub_png_decode_dev) --------------------------------------------------------
 def png_parse(data, W, H):
     """What the host does per file before the upload: walk the chunks of a PNG, -> (idat segments [(offset, length)],

@@ -66,6 +66,7 @@ SIGNATURES = {
     "abh_pipe_timing": (_i, [_vp, _dp]),
     "abh_pipe_set_option": (_i, [_vp, _s, _i]),
     "abh_pipe_blob_stats": (None, [_vp, _dp]),
+    "abh_pipe_contour_stats": (None, [_vp, _dp]),
     "abh_pipe_bellows": (None, [_vp, _dp]),
 }
 _lib = None
@@ -418,7 +419,9 @@ class Pipeline:
 
     def set_option(self, name, value):
         """Run-time knob of this pipeline object: "blobs" 0 (default, from ABUB_PIPE_BLOBS) or 1 -- label the foreground on
-        the GPU and ship only the pixels of the components the localizer can use.  Results never depend on it."""
+        the GPU and ship only the pixels of the components the localizer can use; "contours" 0 (default, from
+        ABUB_PIPE_CONTOURS) or 1 -- also trace the contours of those components on the GPU (K5) and ship their vertices,
+        whatever "blobs" says.  Results never depend on them."""
         L = lib()
         if L.abh_pipe_set_option(self._h, name.encode(), int(value)) != 0:
             raise ValueError(L.abh_pipe_error().decode())
@@ -431,6 +434,16 @@ class Pipeline:
         keys = ("candidates", "foreground", "kept", "components", "kept_components", "large_slots")
         d = {k: int(x) for k, x in zip(keys, v)}
         d.update(otsu_ms=v[6], k4b_ms=v[7])
+        return d
+
+    def contour_stats(self):
+        """Contour tracing of the last run (zeros when the "contours" knob was off), summed over stack groups and rounds:
+        slots traced on the device, slots left to the host route, contours, vertices, ms of the K5 launches."""
+        out = (C.c_double * 5)()
+        lib().abh_pipe_contour_stats(self._h, out)
+        v = list(out)
+        d = {k: int(x) for k, x in zip(("traced", "host_route", "contours", "vertices"), v)}
+        d["k5_ms"] = v[4]
         return d
 
     def bellows_stats(self):

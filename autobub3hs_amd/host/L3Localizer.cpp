@@ -52,6 +52,9 @@ static void contoursOfCurrentImage(abub::EventData &ev, const uint32_t *hist, in
                                    std::vector<std::vector<cv::Point>> &contours, cv::Mat *debugMask = nullptr)
 {
     const int thr = abub::binarizeThresholdFromHist(hist, (size_t)ev.W * ev.H, tozeroThr);
+    // a provider that traced the contours on the device hands them over; the debug mask needs the pixels
+    if (!debugMask && ev.contoursKept(thr, minBoxArea, contours))
+        return;
     std::vector<uint32_t> fg;
     ev.foregroundKept(thr, minBoxArea, fg);
     if (debugMask) { // the thresholded image of L3Localizer.cpp:254 (debug write-out only)

@@ -60,6 +60,16 @@ public:
     // components whose bounding box has area <= minBoxArea (-1: none left out): the contours such components yield are
     // dropped by the caller anyway, and they enclose no other component (abub_blobs.hip).  Default: foreground().
     virtual void foregroundKept(int thr, int minBoxArea, std::vector<uint32_t> &idx) { foreground(thr, idx); }
+    // the external contours of the current image's foreground as ContourFinder::find returns them for foregroundKept()'s
+    // pixels, when the provider already has them (traced on the device, abub_contours.hip): true and `out` filled.
+    // false: the caller traces the pixels of foregroundKept() itself.  Default: false.
+    virtual bool contoursKept(int thr, int minBoxArea, std::vector<std::vector<cv::Point>> &out)
+    {
+        (void)thr;
+        (void)minBoxArea;
+        (void)out;
+        return false;
+    }
     // bellows veto: exact correlation terms of frame i against a template ((H-th+1) x (W-tw+1) placements)
     virtual void matchTerms(int i, const cv::Mat &templ, std::vector<unsigned long long> &num,
                             std::vector<unsigned long long> &wsum2) = 0;

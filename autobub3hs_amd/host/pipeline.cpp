@@ -74,6 +74,12 @@ struct PlannedImage {
     const uint32_t *kept = nullptr;
     uint32_t nkept = 0;
     bool otsuMismatch = false; // the device's Otsu threshold differs from the host's (parity tripwire)
+    // contours knob: the contours of the kept pixels traced on the device (K5, abub_contours.hip): contour k has cnp[k]
+    // vertices, one after the other in cpts (x | y << 16).  traced == false: the slot takes the host route from `kept`
+    bool traced = false;
+    bool keptShipped = true; // false: the batch had no declined slot, so its kept pixels stayed on the device
+    const uint32_t *cnp = nullptr, *cpts = nullptr;
+    uint32_t ncont = 0;
 };
 
 // thrown by the batched provider when the trigger search asks for a frame whose block has not been evaluated yet: the
@@ -253,7 +259,28 @@ public:
         }
         if (p.otsuMismatch)
             throw std::runtime_error("BatchEventData::foregroundKept: device Otsu threshold differs from the host's");
+        if (!p.keptShipped)
+            throw std::runtime_error("BatchEventData::foregroundKept: the kept pixels of a traced image stayed on the device");
         idx.assign(p.kept, p.kept + p.nkept);
+    }
+    bool contoursKept(int thr, int minBoxArea, std::vector<std::vector<cv::Point>> &out) override
+    {
+        if (!cur || cur->thr != thr || cur->minBox != minBoxArea)
+            throw std::runtime_error("BatchEventData::contoursKept: threshold or min box area differs from the planned one");
+        const PlannedImage &p = *cur;
+        if (!p.traced)
+            return false;
+        if (p.otsuMismatch)
+            throw std::runtime_error("BatchEventData::contoursKept: device Otsu threshold differs from the host's");
+        out.resize(p.ncont);
+        const uint32_t *q = p.cpts;
+        for (uint32_t k = 0; k < p.ncont; ++k) {
+            std::vector<cv::Point> &c = out[k];
+            c.resize(p.cnp[k]);
+            for (uint32_t v = 0; v < p.cnp[k]; ++v, ++q)
+                c[v] = cv::Point((int)(*q & 0xffffu), (int)(*q >> 16));
+        }
+        return true;
     }
 };
 
@@ -484,6 +511,10 @@ struct PipeStats {
     // host), components, kept components, slots labelled on the global-memory path, ms of the Otsu and of the K4b launches
     long long blobCandidates = 0, blobForeground = 0, blobKept = 0, blobComponents = 0, blobKeptComponents = 0, blobLargeSlots = 0;
     double blobOtsuMs = 0, blobK4bMs = 0;
+    // contours knob, summed over the rounds: slots traced on the device, slots left to the host route, contours, vertices,
+    // ms of the K5 launches
+    long long contTraced = 0, contHost = 0, contContours = 0, contVertices = 0;
+    double contK5Ms = 0;
 
     void reset() { *this = PipeStats(); }
     // a group's counters into the run's: the groups run side by side, so times and rounds take the maximum, counts add
@@ -510,6 +541,11 @@ struct PipeStats {
         blobLargeSlots += g.blobLargeSlots;
         blobOtsuMs += g.blobOtsuMs;
         blobK4bMs += g.blobK4bMs;
+        contTraced += g.contTraced;
+        contHost += g.contHost;
+        contContours += g.contContours;
+        contVertices += g.contVertices;
+        contK5Ms += g.contK5Ms;
     }
 };
 
@@ -551,6 +587,16 @@ struct Group {
         DeviceArray<uint32_t> ncomp, nkc, coff;
         Event ev[3]; // before Otsu, between, after K4b
     } blobs;
+    // contours knob: K5 behind K4b (allocated on first use).  The scratch follows the candidate list's capacity, the
+    // contour and vertex lists have capacities of their own and grow when a batch overflows them
+    struct Contours {
+        bool ready = false;
+        uint32_t inCap = 0, contCap = 0, ptsCap = 0;
+        Mirror<uint32_t> status, ncont, coff, cnpts, poff, pts, cstats;
+        DeviceArray<uint8_t> scratch;
+        size_t scratchBytes = 0;
+        Event ev[2]; // before and after K5
+    } contours;
     // bellows veto round (vetoRound): its own buffers, allocated on first use, grown on demand
     struct Veto {
         int capJobs = 0;           // match jobs the buffers hold
@@ -595,6 +641,7 @@ public:
     bool ordered = true;                // localisation kernels queue on stage1Stream too (see batchImages())
     int pairCap = 0;                    // ABUB_PIPE_PAIRCAP (0: unset)
     int blobs = 0;                      // 1: stage 3 labels blobs on the GPU and ships only the kept pixels (set_option "blobs")
+    int contours = 0;                   // 1: stage 3 also traces the contours on the GPU and ships their vertices (set_option "contours")
     std::mutex launchMu;
     std::vector<StackState> stacks;
     std::vector<std::unique_ptr<Trainer>> trainers;
@@ -721,6 +768,8 @@ public:
         ordered = eo ? atoi(eo) != 0 : true;
         const char *eb = getenv("ABUB_PIPE_BLOBS");
         blobs = eb ? atoi(eb) != 0 : 0;
+        const char *ect = getenv("ABUB_PIPE_CONTOURS");
+        contours = ect ? atoi(ect) != 0 : 0;
         int prLow = 0, prHigh = 0; // (numerically lower = higher priority)
         HIPOK(hipDeviceGetStreamPriorityRange(&prLow, &prHigh));
         stage1Stream.create(prLow);
@@ -1220,11 +1269,16 @@ private:
         double ta = nowMs();
         // blobs knob: the device also computes the Otsu thresholds and labels each image's foreground (K4b), and only the
         // pixels of the components the localizer can use come back (abub_blobs.hip); the knob is read once per batch
-        const bool useBlobs = blobs != 0;
+        // contours knob: K5 then traces each image's contours from K4b's kept list (abub_contours.hip) and the vertices
+        // come back; the kept pixels travel only when a slot was declined.  It implies device Otsu + K4b
+        const bool useContours = contours != 0;
+        const bool useBlobs = blobs != 0 || useContours;
         Group::Blobs &B = G.blobs;
+        Group::Contours &K = G.contours;
         CandidateList &L = G.list;
         if (useBlobs)
             initBlobs(G);
+        bool contoursGrown = false;
         std::vector<PlannedImage *> bySlot((size_t)nimg);
         for (int s : loc) {
             stacks[s].data.roundHists = G.hist3.h;
@@ -1273,6 +1327,15 @@ private:
                       "stage3 K4b");
                 HIPOK(hipEventRecord(B.ev[2].get(), stream));
             }
+            if (useContours) {
+                fitContours(G, nimg); // (the list may have grown: `back` has waited for the kernels that used the old buffers)
+                HIPOK(hipEventRecord(K.ev[0].get(), stream));
+                check(abub_trace_contours_dev(B.koff.d, L.kidx.d, L.cap, nimg, W, H, K.status.d, K.ncont.d, K.coff.d, K.cnpts.d,
+                                              K.contCap, K.poff.d, K.pts.d, K.ptsCap, K.cstats.d, K.scratch, K.scratchBytes,
+                                              stream),
+                      "stage3 K5");
+                HIPOK(hipEventRecord(K.ev[1].get(), stream));
+            }
             HIPOK(hipEventRecord(G.kernelsDone.get(), stream));
             HIPOK(hipStreamWaitEvent(back, G.kernelsDone.get(), 0));
             G.hist3.toHost((size_t)nimg * 256, back);
@@ -1282,7 +1345,18 @@ private:
                 B.koff.toHost((size_t)nimg + 1, back);
                 B.kstats.toHost(4, back);
             }
+            if (useContours) {
+                K.status.toHost(nimg, back);
+                K.coff.toHost((size_t)nimg + 1, back);
+                K.poff.toHost((size_t)nimg + 1, back);
+                K.cstats.toHost(4, back);
+            }
             HIPOK(hipStreamSynchronize(back));
+            if (useContours) {
+                float m = 0;
+                HIPOK(hipEventElapsedTime(&m, K.ev[0].get(), K.ev[1].get()));
+                G.stats.contK5Ms += m;
+            }
             if (useBlobs) {
                 float m0 = 0, m1 = 0;
                 HIPOK(hipEventElapsedTime(&m0, B.ev[0].get(), B.ev[1].get()));
@@ -1295,16 +1369,37 @@ private:
             G.stats.pairs = *L.count.h;
             // dense foreground (e.g. a flash frame): the kernels kept counting past the capacity, so the needed size is
             // known -- grow the lists once (the kernels that used them are done: `back` waited for them) and redo the batch
-            if (L.fits(attempt, "foreground list overflow (dense foreground in too many images)"))
-                break;
+            if (!L.fits(attempt, "foreground list overflow (dense foreground in too many images)"))
+                continue;
+            // more contours or vertices than their lists hold: the kernel kept counting, so the needed sizes are known --
+            // grow them once and redo the batch
+            if (useContours && (K.coff.h[nimg] > K.contCap || K.poff.h[nimg] > K.ptsCap)) {
+                if (contoursGrown)
+                    throw std::runtime_error("RunPipeline: contour list overflow after it was grown");
+                growContours(K, K.coff.h[nimg], K.poff.h[nimg]);
+                contoursGrown = true;
+                continue;
+            }
+            break;
         }
         const uint32_t cnt = *L.count.h;
         const uint32_t nkept = useBlobs ? B.koff.h[nimg] : 0;
         if (useBlobs) {
             if (nkept > L.cap)
                 throw std::runtime_error("RunPipeline: kept list larger than the candidate list");
-            if (nkept)
+            // with the contours knob the pixels travel only when some slot was declined and takes the host route
+            if (nkept && (!useContours || K.cstats.h[1] != 0))
                 L.kidx.toHost(nkept, back);
+            if (useContours) {
+                if (const uint32_t nc = K.coff.h[nimg])
+                    K.cnpts.toHost(nc, back);
+                if (const uint32_t nv = K.poff.h[nimg])
+                    K.pts.toHost(nv, back);
+                G.stats.contTraced += K.cstats.h[0];
+                G.stats.contHost += K.cstats.h[1];
+                G.stats.contContours += K.cstats.h[2];
+                G.stats.contVertices += K.cstats.h[3];
+            }
             G.stats.blobCandidates += cnt;
             G.stats.blobForeground += B.kstats.h[1];
             G.stats.blobKept += nkept;
@@ -1325,10 +1420,19 @@ private:
                 p->kept = L.kidx.h + B.koff.h[k];
                 p->nkept = B.koff.h[k + 1] - B.koff.h[k];
                 p->otsuMismatch = B.otsu.h[k] != p->thr;
+                p->traced = useContours && K.status.h[k] == 0;
+                p->keptShipped = !useContours || K.cstats.h[1] != 0;
+                if (p->traced) {
+                    p->cnp = K.cnpts.h + K.coff.h[k];
+                    p->cpts = K.pts.h + K.poff.h[k];
+                    p->ncont = K.coff.h[k + 1] - K.coff.h[k];
+                }
             } else {
                 L.bind(*p, k);
                 p->kept = nullptr;
                 p->nkept = 0;
+                p->traced = false;
+                p->keptShipped = true;
             }
         });
         HIPOK(hipStreamSynchronize(back));
@@ -1592,6 +1696,47 @@ private:
         B.ready = true;
     }
 
+    // the contour buffers of the group: per-image arrays once, the scratch sized for the candidate list's current capacity,
+    // the contour and vertex lists at a quarter of it to start with (a contour has far fewer vertices than pixels)
+    void fitContours(Group &G, int nimg)
+    {
+        Group::Contours &K = G.contours;
+        if (!K.ready) {
+            const size_t n3 = (size_t)(G.s1 - G.s0) * (NumFramesBubbleTrack + 1);
+            K.status.allocate(n3);
+            K.ncont.allocate(n3);
+            K.coff.allocate(n3 + 1);
+            K.poff.allocate(n3 + 1);
+            K.cstats.allocate(4);
+            for (Event &e : K.ev)
+                e.create(true);
+            K.ready = true;
+        }
+        if (K.inCap != G.list.cap) {
+            K.scratchBytes = abub_trace_contours_scratch_bytes((int)((size_t)(G.s1 - G.s0) * (NumFramesBubbleTrack + 1)), G.list.cap);
+            if (K.scratchBytes == 0 || W > 65535 || H > 65535)
+                throw std::runtime_error("RunPipeline: frame size not supported by the contour tracing");
+            K.scratch.allocate(K.scratchBytes);
+            K.inCap = G.list.cap;
+        }
+        (void)nimg;
+        if (K.contCap == 0)
+            growContours(K, G.list.cap / 4 + 64, G.list.cap / 4 + 64);
+    }
+    void growContours(Group::Contours &K, uint32_t nc, uint32_t nv)
+    {
+        if (nc > K.contCap) {
+            K.contCap = 0;
+            K.cnpts.allocate((size_t)nc + nc / 4 + 64);
+            K.contCap = nc + nc / 4 + 64;
+        }
+        if (nv > K.ptsCap) {
+            K.ptsCap = 0;
+            K.pts.allocate((size_t)nv + nv / 4 + 64);
+            K.ptsCap = nv + nv / 4 + 64;
+        }
+    }
+
     // AnyCamAnalysis body from LocalizeOMatic on (AutoBubStart3.cpp:94-110)
     void localize(StackState &st_)
     {
@@ -1707,23 +1852,35 @@ void abh_pipe_bellows(void *p, double *out)
 
 // Run-time knobs of one pipeline object: "blobs" (0 = the host applies the Otsu cut to every candidate pixel, 1 = the
 // device labels the foreground and ships only the pixels of the components the localizer can use; default from
-// ABUB_PIPE_BLOBS).  Names and values are checked before the handle: -1 for an unknown name, a bad value or no handle.
+// ABUB_PIPE_BLOBS) and "contours" (1 = the device also traces the contours of those components and ships their vertices,
+// whatever "blobs" says; a slot the kernel declines keeps the host route; default from ABUB_PIPE_CONTOURS, else 0).  Names and values are checked before the handle: -1 for an unknown name, a bad value or no handle.
 int abh_pipe_set_option(void *p, const char *name, int value)
 {
-    if (!name || std::string(name) != "blobs") {
+    const std::string opt = name ? name : "";
+    if (opt != "blobs" && opt != "contours") {
         g_pipeErr = std::string("abh_pipe_set_option: unknown option ") + (name ? name : "(null)");
         return -1;
     }
     if (value != 0 && value != 1) {
-        g_pipeErr = "abh_pipe_set_option: blobs takes 0 or 1";
+        g_pipeErr = "abh_pipe_set_option: " + opt + " takes 0 or 1";
         return -1;
     }
     if (!p) {
         g_pipeErr = "abh_pipe_set_option: no pipeline";
         return -1;
     }
-    ((abub::RunPipeline *)p)->blobs = value;
+    (opt == "blobs" ? ((abub::RunPipeline *)p)->blobs : ((abub::RunPipeline *)p)->contours) = value;
     return 0;
+}
+
+// out[0..4] of the last run with the contours knob on (zeros otherwise), summed over stack groups and rounds: slots
+// traced on the device, slots left to the host route, contours, vertices, ms of the K5 launches
+void abh_pipe_contour_stats(void *p, double *out)
+{
+    const abub::PipeStats &st = ((abub::RunPipeline *)p)->stats;
+    const double v[5] = {(double)st.contTraced, (double)st.contHost, (double)st.contContours, (double)st.contVertices,
+                         st.contK5Ms};
+    std::memcpy(out, v, sizeof v);
 }
 
 // out[0..7] of the last run with the blobs knob on (zeros otherwise), summed over stack groups and rounds: candidate

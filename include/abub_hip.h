@@ -252,6 +252,29 @@ int abub_label_blobs_dev(const uint32_t *offsets, const uint32_t *idx, const uin
 /* 0 for impossible shapes */
 size_t abub_label_blobs_scratch_bytes(int nslots, int W, int H, uint32_t in_cap, int with_comp);
 
+/* K5: the contours of each slot of a K4b kept list, traced on the device -- what cv::findContours(RETR_EXTERNAL,
+ * CHAIN_APPROX_TC89_L1) returns for the thresholded image (L3Localizer.cpp:264, 374, 793), bit for bit what
+ * host/hostlogic.cpp ContourFinder::find returns for the slot's kept pixels: the same contours in the same order (the
+ * last discovered first), the same vertices in the order approxChainTC89L1 emits them.
+ * Input: kept_off [nslots+1] / kept_idx of abub_label_blobs_dev (raster indices increasing within a slot; entries at or
+ * past in_cap are never read), for images of W x H (each <= 65535).  Output, per slot s:
+ *   status[s] = 0: traced.  cont_npts[cont_off[s] .. cont_off[s+1]) = the vertex count of each of its ncont[s] contours,
+ *               pts[pt_off[s] .. pt_off[s+1]) = their vertices one after the other, one dword x | y << 16 each.
+ *   status[s] = 1: declined (more than max_pixels kept pixels, or a border chain of more than max_chain codes, see
+ *               abub_trace_contours_limits): ncont[s] = 0, nothing written; trace the slot on the host.
+ * Offsets are true counts; nothing is written at or past cont_npts[cont_cap] / pts[pts_cap].  Exact and deterministic.
+ * stats[4] (device, overwritten): slots traced, slots declined, contours, vertices.
+ * scratch: abub_trace_contours_scratch_bytes(nslots, in_cap) bytes, 256-byte aligned. */
+int abub_trace_contours_dev(const uint32_t *kept_off, const uint32_t *kept_idx, uint32_t in_cap, int nslots, int W, int H,
+                            uint32_t *status, uint32_t *ncont, uint32_t *cont_off, uint32_t *cont_npts, uint32_t cont_cap,
+                            uint32_t *pt_off, uint32_t *pts, uint32_t pts_cap, uint32_t *stats, void *scratch,
+                            size_t scratch_bytes, void *stream);
+/* Scratch of abub_trace_contours_dev (the contour tracing of L3Localizer.cpp:264, 374, 793); 0 for impossible shapes */
+size_t abub_trace_contours_scratch_bytes(int nslots, uint32_t in_cap);
+/* The limits under which abub_trace_contours_dev traces a slot (L3Localizer.cpp:264, 374, 793 stay on the host above
+ * them): kept pixels per slot, Freeman codes per border chain.  Needs no device. */
+int abub_trace_contours_limits(int *max_pixels, int *max_chain);
+
 /* Raw terms of cv::matchTemplate(CV_TM_CCORR_NORMED) for the bellows veto (L3Localizer::TrackAFeature,
  * L3Localizer.cpp:499-500): for each of the (W-tw+1) x (H-th+1) placements the exact integer sums
  * num = sum(T*I) and wsum2 = sum(I*I) over the window.  Normalisation is host work (double). */

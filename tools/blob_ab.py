@@ -1,11 +1,14 @@
-"""Interleaved A/B of the pipeline's "blobs" knob (0 = host applies the Otsu cut to every candidate pixel, 1 = the GPU
-labels the foreground and ships only the kept pixels), on bench.py's synthetic run in each data regime.
+"""Interleaved A/B of the pipeline's "blobs" and "contours" knobs on bench.py's synthetic run in each data regime:
+blobs0 (the host applies the Otsu cut to every candidate pixel and traces the contours), blobs1 (the GPU labels the
+foreground and ships only the kept pixels; the host traces them), contours1 (the GPU also traces the contours, K5, and
+ships their vertices).
 
-One pipeline object per regime; steps alternate blobs = 0 / 1 on it (A B A B ...), each step timed from a device
-synchronise to the end of the run (the pipeline synchronises itself).  Per step: ms, the pipeline's stage timings and,
-for blobs = 1, blob_stats().  Results must not depend on the knob: every step's per-stack summary is compared.
+One pipeline object per regime; steps cycle through the three settings on it (A B C A B C ...), each step timed from a
+device synchronise to the end of the run (the pipeline synchronises itself).  Per step: ms, the pipeline's stage timings
+and, with a knob on, blob_stats() / contour_stats().  Results must not depend on the knobs: every step's per-stack summary
+is compared.  --threads 2 is the host share of one rank of an 8-GPU node.
 
-    python tools/blob_ab.py --steps 10 --out profiles/r04/blobs_ab.json
+    python tools/blob_ab.py --steps 10 --out profiles/r05/contours_ab_t16.json
 """
 import argparse
 import json
@@ -64,9 +67,11 @@ def main():
         pipe.set_sigma(sg_t)
         stream = torch.cuda.current_stream().cuda_stream
         rows, ref = [], None
-        for k in range(2 * (args.warmup + args.steps)):
-            v = k % 2
-            pipe.set_option("blobs", v)
+        settings = (("blobs0", 0, 0), ("blobs1", 1, 0), ("contours1", 0, 1))
+        for k in range(len(settings) * (args.warmup + args.steps)):
+            name, vb, vc = settings[k % len(settings)]
+            pipe.set_option("blobs", vb)
+            pipe.set_option("contours", vc)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             pipe.run(slab, mu_t, s6, stream)
@@ -74,28 +79,34 @@ def main():
             summ = pipe.summary()
             if ref is None:
                 ref = summ
-            assert summ == ref, "results depend on the blobs knob"
-            if k < 2 * args.warmup:
+            assert summ == ref, "results depend on the blobs / contours knobs"
+            if k < len(settings) * args.warmup:
                 continue
             t = pipe.timing()
-            row = {"blobs": v, "ms": ms, "stage3_ms": t["stage3_ms"], "stage4_ms": t["stage4_ms"],
-                   "s3_gpu_ms": t["s3_gpu_ms"], "s3_list_ms": t["s3_list_ms"], "pairs": t["pairs"]}
-            if v:
+            row = {"setting": name, "blobs": vb, "contours": vc, "ms": ms, "stage3_ms": t["stage3_ms"],
+                   "stage4_ms": t["stage4_ms"], "s3_gpu_ms": t["s3_gpu_ms"], "s3_list_ms": t["s3_list_ms"], "pairs": t["pairs"]}
+            if vb or vc:
                 row["blob_stats"] = pipe.blob_stats()
+            if vc:
+                row["contour_stats"] = pipe.contour_stats()
             rows.append(row)
         pipe.close()
         del slab
 
-        def med(key, v):
-            return statistics.median(r[key] for r in rows if r["blobs"] == v)
-
         summary = {}
-        for v in (0, 1):
-            summary["blobs%d" % v] = {k: med(k, v) for k in ("ms", "stage3_ms", "stage4_ms", "s3_gpu_ms", "s3_list_ms")}
-        b = [r["blob_stats"] for r in rows if r["blobs"] == 1]
-        summary["blobs1"].update({k: statistics.median(x[k] for x in b) for k in b[0]})
-        # pixels shipped to the host per step: every candidate pair (5 bytes: index + value) vs the kept indices (4 bytes)
-        summary["shipped_pixels"] = {"blobs0": summary["blobs1"]["candidates"], "blobs1": summary["blobs1"]["kept"]}
+        for name, _, _ in settings:
+            mine = [r for r in rows if r["setting"] == name]
+            summary[name] = {k: statistics.median(r[k] for r in mine)
+                             for k in ("ms", "stage3_ms", "stage4_ms", "s3_gpu_ms", "s3_list_ms")}
+            for key in ("blob_stats", "contour_stats"):
+                b = [r[key] for r in mine if key in r]
+                if b:
+                    summary[name].update({k: statistics.median(x[k] for x in b) for k in b[0]})
+        # what travels to the host per step: every candidate pair (5 bytes: index + value), the kept indices (4 bytes), the
+        # contour vertices (4 bytes) plus the kept indices of the batches with a declined slot
+        summary["shipped"] = {"blobs0_pixels": summary["blobs1"]["candidates"], "blobs1_pixels": summary["blobs1"]["kept"],
+                              "contours1_vertices": summary["contours1"]["vertices"],
+                              "contours1_host_route_slots": summary["contours1"]["host_route"]}
         out["regimes"][regime] = {"summary": summary, "steps": rows}
         print(regime, json.dumps(summary), flush=True)
     if args.out:
