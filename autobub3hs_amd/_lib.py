@@ -16,6 +16,15 @@ class Job(C.Structure):
     _fields_ = [("cur", C.c_uint32), ("ref", C.c_uint32), ("model", C.c_uint32), ("out", C.c_uint32)]
 
 
+class TrigSeg(C.Structure):
+    _fields_ = [("hist", C.c_void_p), ("pending", C.c_void_p), ("first", C.c_int32), ("count", C.c_int32)]
+
+
+class TrigStack(C.Structure):
+    _fields_ = [("seg0", C.c_uint32), ("nseg", C.c_uint32), ("F", C.c_int32), ("start", C.c_int32), ("tss", C.c_int32),
+                ("first_bad", C.c_int32)]
+
+
 def build(force=False):
     """Compile the HIP library for gfx950 (cross-compiles without a GPU)."""
     srcs = [os.path.join(HERE, "csrc", f) for f in os.listdir(os.path.join(HERE, "csrc"))
@@ -70,6 +79,10 @@ SIGNATURES = {
                                      _vp, _vp, _sz, _vp]),
     "abub_trace_contours_scratch_bytes": (_sz, [_i, C.c_uint32]),
     "abub_trace_contours_limits": (_i, [C.POINTER(_i), C.POINTER(_i)]),
+    "abub_trigger_search_dev": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _sz, _vp, _vp, _i, _vp]),
+    "abub_trigger_search_desc_bytes": (_sz, [_i, _i]),
+    "abub_trigger_clear_pending_dev": (_i, [_vp, _vp, _sz, _vp]),
+    "abub_trigger_search_limits": (_i, [C.POINTER(_i), C.POINTER(_i)]),
     "abub_ctx_create": (_i, [C.POINTER(_vp), _i, _i, _i, _i]),
     "abub_ctx_destroy": (None, [_vp]),
     "abub_ctx_train": (_i, [_vp, C.POINTER(_vp), _i, _vp, _vp]),

@@ -245,6 +245,58 @@ def trace_contours(kept_off, kept_idx, W, H, cont_cap=None, pts_cap=None, in_cap
                                          scratch.numel(), _stream()), "abub_trace_contours_dev")
     return out
 
+def trigger_search_limits():
+    """(max_frames, max_segs) of K6: a stack with more frames or more segments keeps the host search."""
+    import ctypes as C
+    mf, ms = C.c_int(0), C.c_int(0)
+    _lib.check(_lib.lib().abub_trigger_search_limits(C.byref(mf), C.byref(ms)), "abub_trigger_search_limits")
+    return mf.value, ms.value
+
+
+TRIG_DONE, TRIG_NEED_FRAMES, TRIG_NEED_FINAL, TRIG_BAD_LOOKAHEAD = 0, 1, 2, 3
+
+
+def trigger_search(stacks, W, H, sig_main=True):
+    """K6 (abub_trigger_search_dev): one trigger search per stack in one launch.  stacks: a list of dicts with F, tss and
+    segs = [(first, hist, pending)] (hist: int32 device tensor [count, 256], pending: uint8 device tensor [count] or
+    None), optionally start (1) and first_bad (F).  -> (list of result dicts with the fields of abub_trig_result,
+    sig_main: float64 tensor [nstacks, max F] filled with NaN where the search evaluated no main-loop frame, or None)."""
+    import ctypes as C
+    import struct
+    n = len(stacks)
+    nseg = sum(len(s["segs"]) for s in stacks)
+    st = (_lib.TrigStack * max(n, 1))()
+    sg = (_lib.TrigSeg * max(nseg, 1))()
+    k = 0
+    dev = None
+    for i, s in enumerate(stacks):
+        st[i].seg0, st[i].nseg, st[i].F, st[i].tss = k, len(s["segs"]), s["F"], s["tss"]
+        st[i].start, st[i].first_bad = s.get("start", 1), s.get("first_bad", s["F"])
+        for first, hist, pending in s["segs"]:
+            _need_cuda(hist, pending)
+            dev = hist.device
+            sg[k].hist, sg[k].pending, sg[k].first, sg[k].count = _ptr(hist), _ptr(pending), first, hist.shape[0]
+            k += 1
+    if dev is None:
+        dev = torch.device("cuda")
+    L = _lib.lib()
+    nbytes = int(L.abub_trigger_search_desc_bytes(n, nseg))
+    desc = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=dev)
+    out = torch.zeros((max(n, 1), 8), dtype=torch.int32, device=dev)
+    pitch = max([s["F"] for s in stacks] + [1])
+    sm = torch.full((max(n, 1), pitch), float("nan"), dtype=torch.float64, device=dev) if sig_main else None
+    _lib.check(L.abub_trigger_search_dev(C.addressof(st), C.addressof(sg), n, nseg, W, H, _ptr(desc), desc.numel(), _ptr(out),
+                                         _ptr(sm), pitch, _stream()), "abub_trigger_search_dev")
+    rows = out.cpu().numpy()  # (synchronises: the host arrays above stay alive until here)
+    names = ("state", "status", "trig", "loc_thres", "need_frame", "evaluated")
+    res = []
+    for i in range(n):
+        r = {k_: int(rows[i, j]) for j, k_ in enumerate(names)}
+        r["sig"] = struct.unpack("<f", struct.pack("<i", int(rows[i, 6])))[0]
+        res.append(r)
+    return res, (sm[:n] if sig_main else None)
+
+
 # ---- PNG frames decoded on the GPU (abub_png_decode_dev) --------------------------------------------------------
 def png_parse(data, W, H):
     """What the host does per file before the upload: walk the chunks of a PNG, -> (idat segments [(offset, length)],

@@ -67,6 +67,8 @@ SIGNATURES = {
     "abh_pipe_set_option": (_i, [_vp, _s, _i]),
     "abh_pipe_blob_stats": (None, [_vp, _dp]),
     "abh_pipe_contour_stats": (None, [_vp, _dp]),
+    "abh_pipe_trigger_stats": (None, [_vp, _dp]),
+    "abh_pipe_trigger_totals": (None, [_dp]),
     "abh_pipe_bellows": (None, [_vp, _dp]),
 }
 _lib = None
@@ -348,6 +350,14 @@ def best_match(num, wsum2, tmpl):
     return bx.value, by.value
 
 
+def trigger_totals():
+    """(stacks searched on the device, stacks on the host route) with the "trigger" knob on, over every pipeline run of
+    this process so far -- Run.run_batched owns its pipelines, so a caller takes the difference around it."""
+    out = (C.c_double * 2)()
+    lib().abh_pipe_trigger_totals(out)
+    return int(out[0]), int(out[1])
+
+
 class Significance:
     def __init__(self, tss):
         self._h = lib().abh_sig_new()
@@ -421,7 +431,9 @@ class Pipeline:
         """Run-time knob of this pipeline object: "blobs" 0 (default, from ABUB_PIPE_BLOBS) or 1 -- label the foreground on
         the GPU and ship only the pixels of the components the localizer can use; "contours" 0 (default, from
         ABUB_PIPE_CONTOURS) or 1 -- also trace the contours of those components on the GPU (K5) and ship their vertices,
-        whatever "blobs" says.  Results never depend on them."""
+        whatever "blobs" says; "trigger" 0 (default, from ABUB_PIPE_TRIGGER) or 1 -- run the trigger search of every
+        stack inside the kernel's limits on the GPU (K6) from the histograms that are already there, instead of
+        FindTriggerFrame on host threads; read at the start of a run.  Results never depend on them."""
         L = lib()
         if L.abh_pipe_set_option(self._h, name.encode(), int(value)) != 0:
             raise ValueError(L.abh_pipe_error().decode())
@@ -444,6 +456,17 @@ class Pipeline:
         v = list(out)
         d = {k: int(x) for k, x in zip(("traced", "host_route", "contours", "vertices"), v)}
         d["k5_ms"] = v[4]
+        return d
+
+    def trigger_stats(self):
+        """Device trigger search of the last run (zeros when the "trigger" knob was off), summed over stack groups and
+        rounds: stacks searched on the device, stacks on the host route (beyond the kernel's limits), search launches,
+        NEED_FRAMES answers, NEED_FINAL answers, ms of the K6 launches."""
+        out = (C.c_double * 6)()
+        lib().abh_pipe_trigger_stats(self._h, out)
+        v = list(out)
+        d = {k: int(x) for k, x in zip(("device", "host_route", "launches", "need_frames", "need_final"), v)}
+        d["k6_ms"] = v[5]
         return d
 
     def bellows_stats(self):

@@ -42,6 +42,9 @@
 
 namespace abub {
 extern bool g_quietAnalyzers;
+// trigger knob, summed over every pipeline run of the process (a batched run owns its pipelines; abh_pipe_trigger_totals):
+// stacks searched on the device, stacks on the host route
+static std::atomic<long long> g_trigTotals[2];
 
 namespace {
 
@@ -299,6 +302,12 @@ struct StackState : StackResult {
     bool dropIn = false; // must be re-run through the one-at-a-time path (bellows veto)
     bool needMore = false; // the trigger search stopped at a frame block that is not evaluated yet (data.needBlock)
     bool needBellows = false; // localize stopped at a bellows-veto request (data.matches / data.residuals)
+    // trigger knob: the device search's answer for the analyzer's current state (trigReady: not consumed yet), and where
+    // this stack's histograms (and deferred flags) of each bound block lie in device memory
+    bool trigReady = false;
+    abub_trig_result trigRes{};
+    const uint32_t *dbh[BatchEventData::MAXB] = {nullptr};
+    const uint8_t *dinc[BatchEventData::MAXB] = {nullptr};
     bool vetoed = false;      // a bellows residual was computed for this stack in the batch
 };
 
@@ -515,6 +524,10 @@ struct PipeStats {
     // ms of the K5 launches
     long long contTraced = 0, contHost = 0, contContours = 0, contVertices = 0;
     double contK5Ms = 0;
+    // trigger knob: stacks searched on the device, stacks on the host route, NEED_FRAMES and NEED_FINAL answers, ms of the
+    // K6 launches (per group, merged); search launches (kept by the pipeline, like jobsLaunched)
+    long long trigDevStacks = 0, trigHostStacks = 0, trigNeedFrames = 0, trigNeedFinal = 0, trigLaunches = 0;
+    double trigK6Ms = 0;
 
     void reset() { *this = PipeStats(); }
     // a group's counters into the run's: the groups run side by side, so times and rounds take the maximum, counts add
@@ -546,6 +559,11 @@ struct PipeStats {
         contContours += g.contContours;
         contVertices += g.contVertices;
         contK5Ms += g.contK5Ms;
+        trigDevStacks += g.trigDevStacks;
+        trigHostStacks += g.trigHostStacks;
+        trigNeedFrames += g.trigNeedFrames;
+        trigNeedFinal += g.trigNeedFinal;
+        trigK6Ms += g.trigK6Ms;
     }
 };
 
@@ -597,6 +615,19 @@ struct Group {
         size_t scratchBytes = 0;
         Event ev[2]; // before and after K5
     } contours;
+    // trigger knob: K6 (abub_trigger.hip) on the blocks' device histograms (allocated on first use): descriptors of one
+    // launch (pinned, copied by the launcher), its results, the stacks it serves in launch order.  One launch at a time:
+    // every launch is waited for (stage1Done / blockDone) and collected before the next one is filled in.
+    struct Trigger {
+        bool ready = false, inflight = false;
+        PinnedArray<abub_trig_stack> st;
+        PinnedArray<abub_trig_seg> sg;
+        DeviceArray<uint8_t> desc;
+        size_t descBytes = 0;
+        Mirror<abub_trig_result> res;
+        std::vector<int> list;
+        Event ev[2]; // before and after the launch
+    } trig;
     // bellows veto round (vetoRound): its own buffers, allocated on first use, grown on demand
     struct Veto {
         int capJobs = 0;           // match jobs the buffers hold
@@ -642,6 +673,9 @@ public:
     int pairCap = 0;                    // ABUB_PIPE_PAIRCAP (0: unset)
     int blobs = 0;                      // 1: stage 3 labels blobs on the GPU and ships only the kept pixels (set_option "blobs")
     int contours = 0;                   // 1: stage 3 also traces the contours on the GPU and ships their vertices (set_option "contours")
+    int trigger = 0;                    // 1: the trigger search runs on the GPU (K6) for every stack inside its limits (set_option "trigger")
+    bool trigOn = false;                // `trigger` as read at the start of the current run
+    int trigMaxF = 0;                   // abub_trigger_search_limits: a longer stack keeps the host search
     std::mutex launchMu;
     std::vector<StackState> stacks;
     std::vector<std::unique_ptr<Trainer>> trainers;
@@ -703,6 +737,91 @@ public:
         st_.data.inc[k] = fe.deferred ? B.inc.h + slot * blen : nullptr;
         st_.data.fetchOf[k] = f;
         st_.data.slotOf[k] = q;
+    }
+    // the same for the device search, at launch time: where the stack's histograms and deferred flags of block k lie in HBM
+    void bindBlockDevice(Group::Block &B, int k, StackState &st_, int f, int q)
+    {
+        const Group::Fetch &fe = B.fetches[f];
+        const size_t blen = (size_t)(blocks[k + 1] - blocks[k]), slot = (size_t)fe.first + q;
+        st_.dbh[k] = B.hist.d + slot * blen * 256;
+        st_.dinc[k] = fe.deferred ? B.inc.d + slot * blen : nullptr;
+    }
+    int stackFrames(int s) const { return meta.empty() ? F : (int)meta[s].names.size(); }
+    // trigger knob: does stack s keep the host search (decided before the first search, from the kernel's static limits)
+    bool trigHostRoute(int s) const { return stackFrames(s) > trigMaxF; }
+    // One K6 launch for the listed stacks, each from its analyzer's current state (retry: behind the last trigger), on the
+    // blocks bound for it so far; the results come back with the next event the group waits for (collectSearch).
+    void launchSearch(Group &G, const std::vector<int> &list, hipStream_t stream)
+    {
+        Group::Trigger &T = G.trig;
+        if (list.empty())
+            return;
+        if (T.inflight)
+            throw std::runtime_error("RunPipeline: a trigger search was launched before the previous one was collected");
+        const size_t ns = (size_t)(G.s1 - G.s0), nsg = ns * BatchEventData::MAXB;
+        if (!T.ready) {
+            T.st.allocate(ns);
+            T.sg.allocate(nsg);
+            T.descBytes = abub_trigger_search_desc_bytes((int)ns, (int)nsg);
+            T.desc.allocate(T.descBytes);
+            T.res.allocate(ns);
+            T.ev[0].create(true);
+            T.ev[1].create(true);
+            T.ready = true;
+        }
+        const int nB = (int)blocks.size() - 1;
+        uint32_t nseg = 0;
+        for (size_t q = 0; q < list.size(); ++q) {
+            const int s = list[q];
+            const StackState &st_ = stacks[s];
+            abub_trig_stack &d = T.st[q];
+            const int Fs = stackFrames(s);
+            d.seg0 = nseg;
+            d.F = Fs;
+            d.start = (st_.analyzer ? st_.analyzer->MatTrigFrame : 0) + 1;
+            d.tss = tss[s % C];
+            d.first_bad = Fs;
+            if (!meta.empty())
+                for (int i = 0; i < Fs; ++i)
+                    if (!meta[s].ok[i]) {
+                        d.first_bad = i;
+                        break;
+                    }
+            for (int k = 0; k < nB; ++k)
+                if (st_.dbh[k] && blocks[k + 1] > blocks[k]) {
+                    abub_trig_seg &g = T.sg[nseg++];
+                    g.hist = st_.dbh[k];
+                    g.pending = st_.dinc[k];
+                    g.first = blocks[k];
+                    g.count = blocks[k + 1] - blocks[k];
+                }
+            d.nseg = nseg - d.seg0;
+        }
+        HIPOK(hipEventRecord(T.ev[0].get(), stream));
+        check(abub_trigger_search_dev(T.st, T.sg, (int)list.size(), (int)nseg, W, H, T.desc, T.descBytes, T.res.d, nullptr, 0,
+                                      stream),
+              "trigger search K6");
+        HIPOK(hipEventRecord(T.ev[1].get(), stream));
+        T.res.toHost(list.size(), stream);
+        T.list = list;
+        T.inflight = true;
+        ++stats.trigLaunches;
+    }
+    // after the event behind the launch has been waited for: every served stack gets its answer
+    void collectSearch(Group &G)
+    {
+        Group::Trigger &T = G.trig;
+        if (!T.inflight)
+            return;
+        for (size_t q = 0; q < T.list.size(); ++q) {
+            StackState &st_ = stacks[T.list[q]];
+            st_.trigRes = T.res.h[q];
+            st_.trigReady = true;
+        }
+        float ms = 0;
+        HIPOK(hipEventElapsedTime(&ms, T.ev[0].get(), T.ev[1].get()));
+        G.stats.trigK6Ms += ms;
+        T.inflight = false;
     }
     // K2 over block k for the listed stacks (all of them on the same block): jobs -> device, launch, histograms -> host.
     // Returns the first slot (in stacks) of the block's histogram buffer the results go to.
@@ -770,6 +889,12 @@ public:
         blobs = eb ? atoi(eb) != 0 : 0;
         const char *ect = getenv("ABUB_PIPE_CONTOURS");
         contours = ect ? atoi(ect) != 0 : 0;
+        const char *etr = getenv("ABUB_PIPE_TRIGGER");
+        trigger = etr ? atoi(etr) != 0 : 0;
+        int trigMaxSegs = 0;
+        check(abub_trigger_search_limits(&trigMaxF, &trigMaxSegs), "abub_trigger_search_limits");
+        if (trigMaxSegs < BatchEventData::MAXB)
+            trigMaxF = 0; // (cannot happen: the kernel's segment limit is MAXB) -- every stack keeps the host search
         int prLow = 0, prHigh = 0; // (numerically lower = higher priority)
         HIPOK(hipDeviceGetStreamPriorityRange(&prLow, &prHigh));
         stage1Stream.create(prLow);
@@ -897,6 +1022,7 @@ public:
         double t0 = nowMs();
         stacks.clear();
         stacks.resize(S);
+        trigOn = trigger != 0; // read once per run
         // Stage 1 of every group goes to ONE stream in group order: the trigger search of group g+1 runs
         // on the GPU while the host threads of group g are in their state machines (two kernels launched on
         // different streams would simply share the chip and finish together, leaving nothing to overlap).
@@ -915,6 +1041,19 @@ public:
                 all.push_back(sI);
             if (F > 1)
                 launchBlock(G.blocks[0], 0, all, d_frames, d_sigma6, stage1Stream.get()); // block 0: every stack, slot == index in the group
+            if (trigOn) {
+                // the first search of every stack right behind the K2 that produces its input: the decisions arrive with
+                // stage1Done
+                G.trig.inflight = false;
+                std::vector<int> dev;
+                for (int sI : all)
+                    if (!trigHostRoute(sI)) {
+                        if (F > 1)
+                            bindBlockDevice(G.blocks[0], 0, stacks[sI], 0, sI - G.s0);
+                        dev.push_back(sI);
+                    }
+                launchSearch(G, dev, stage1Stream.get());
+            }
             HIPOK(hipEventRecord(G.stage1Done.get(), stage1Stream.get()));
         }
         std::vector<std::thread> th;
@@ -934,6 +1073,8 @@ public:
                 throw std::runtime_error(G.error);
             stats.merge(G.stats);
         }
+        g_trigTotals[0] += stats.trigDevStacks;
+        g_trigTotals[1] += stats.trigHostStacks;
         stats.totalMs = nowMs() - t0;
     }
 
@@ -1039,6 +1180,9 @@ private:
         std::vector<int> pending(ns);
         for (int k = 0; k < ns; ++k)
             pending[k] = G.s0 + k;
+        if (trigOn)
+            for (int sI : pending)
+                ++(trigHostRoute(sI) ? G.stats.trigHostStacks : G.stats.trigDevStacks);
         while (!pending.empty()) {
             ++G.stats.rounds;
             // ---- stage 2: trigger search + plan ------------------------------------------------
@@ -1047,11 +1191,33 @@ private:
             double t2 = nowMs();
             std::vector<int> todo(pending);
             while (!todo.empty()) {
+                if (trigOn) {
+                    // the answers that came with the event just waited for; stacks without one (retry rounds: the
+                    // search goes on behind a trigger that gave no bubble) get a launch of their own
+                    collectSearch(G);
+                    std::vector<int> ask;
+                    for (int sI : todo)
+                        if (!trigHostRoute(sI) && !stacks[sI].trigReady)
+                            ask.push_back(sI);
+                    if (!ask.empty()) {
+                        {
+                            std::lock_guard<std::mutex> lock(launchMu);
+                            hipStream_t stream = ordered ? stage1Stream.get() : G.stream.get();
+                            launchSearch(G, ask, stream);
+                            HIPOK(hipEventRecord(G.blockDone.get(), stream));
+                        }
+                        HIPOK(hipEventSynchronize(G.blockDone.get()));
+                        collectSearch(G);
+                    }
+                }
                 pool->parallelFor((int)todo.size(), [&](int k) { triggerAndPlan(stacks[todo[k]]); });
                 std::vector<int> need;
-                for (int sI : todo)
+                for (int sI : todo) {
+                    if (trigOn && !trigHostRoute(sI) && stacks[sI].needMore)
+                        ++(stacks[sI].data.needPieces ? G.stats.trigNeedFinal : G.stats.trigNeedFrames);
                     if (stacks[sI].needMore)
                         need.push_back(sI);
+                }
                 if (need.empty())
                     break;
                 fetchBlocks(G, need, d_frames, d_sigma6);
@@ -1113,6 +1279,9 @@ private:
                 if (!byBlock[k].empty()) {
                     launchBlock(B, k, byBlock[k], d_frames, d_sigma6, stream);
                     newFetch[k] = (int)B.fetches.size() - 1;
+                    if (trigOn)
+                        for (size_t q = 0; q < byBlock[k].size(); ++q)
+                            bindBlockDevice(B, k, stacks[byBlock[k][q]], newFetch[k], (int)q);
                 }
                 const size_t blen = (size_t)(blocks[k + 1] - blocks[k]);
                 for (size_t f = 0; f < byFetch[k].size(); ++f) {
@@ -1140,7 +1309,18 @@ private:
                         const size_t j0 = (size_t)(d.needFrame - blocks[k]), o = (base + (size_t)d.slotOf[k] * blen + j0) * 256;
                         B.hist.toHost((blen - j0) * 256, stream, o);
                     }
+                    // final now on the device too (the host mirror of the flags is cleared below): one launch per fetch
+                    if (trigOn)
+                        check(abub_trigger_clear_pending_dev(B.inc.d + base, B.want.d + base, nj, stream), "trigger search flags");
                 }
+            }
+            if (trigOn) {
+                // the searches that asked go on right behind the launches that produce what they asked for
+                std::vector<int> dev;
+                for (int sI : need)
+                    if (!trigHostRoute(sI))
+                        dev.push_back(sI);
+                launchSearch(G, dev, stream);
             }
             HIPOK(hipEventRecord(G.blockDone.get(), stream));
         }
@@ -1162,6 +1342,48 @@ private:
         }
     }
 
+    // trigger knob: what FindTriggerFrame(true, MatTrigFrame + 1) would have left in the analyzer, from the device search's
+    // answer (K6, abub_trigger.hip).  false: the search needs frames (needMore is set as NeedMoreFrames would have set it;
+    // nothing to roll back).  A look-ahead frame that cannot be decoded throws what the host search throws.
+    bool applySearch(StackState &st_)
+    {
+        AnalyzerUnit *A = st_.analyzer.get();
+        BatchEventData &d = st_.data;
+        const abub_trig_result r = st_.trigRes;
+        st_.trigReady = false;
+        if (r.state == ABUB_TRIG_NEED_FRAMES || r.state == ABUB_TRIG_NEED_FINAL) {
+            int k = 0;
+            while (k + 1 < d.nblocks && r.need_frame >= d.bstart[k + 1])
+                ++k;
+            d.needBlock = k;
+            d.needPieces = r.state == ABUB_TRIG_NEED_FINAL;
+            d.needFrame = r.need_frame;
+            if (d.needPieces ? !d.inc[k] : d.bh[k] != nullptr)
+                throw std::runtime_error("RunPipeline: the device trigger search asked for a frame that is there");
+            st_.needMore = true;
+            return false;
+        }
+        if (r.state == ABUB_TRIG_BAD_LOOKAHEAD)
+            throw std::runtime_error("AnalyzerUnit::FindTriggerFrame: undecodable look-ahead frame");
+        if (r.state != ABUB_TRIG_DONE)
+            throw std::runtime_error("RunPipeline: unknown answer of the device trigger search");
+        const int s = (int)(&st_ - stacks.data());
+        if (r.status == -9 && d.F >= 5 && !meta.empty()) { // the line FindTriggerFrame prints for the frame it stopped at
+            const int i = A->MatTrigFrame + 1 + r.evaluated;
+            if (i >= 0 && i < (int)meta[s].names.size())
+                std::cout << "Image " << meta[s].names[i] << " is corrupted/empty of camera " << s % C << " for the event "
+                          << meta[s].eventID << "." << std::endl;
+        }
+        A->TriggerFrameIdentificationStatus = r.status;
+        if (r.loc_thres >= 0)
+            A->loc_thres = r.loc_thres;
+        if (r.status == 0)
+            A->MatTrigFrame = r.trig;
+        else
+            A->okToProceed = false;
+        return true;
+    }
+
     // AnyCamAnalysis body up to LocalizeOMatic (AutoBubStart3.cpp:87-107)
     void triggerAndPlan(StackState &st_)
     {
@@ -1177,7 +1399,13 @@ private:
             const int trig0 = A->MatTrigFrame, loc0 = A->loc_thres, status0 = A->TriggerFrameIdentificationStatus;
             const bool ok0 = A->okToProceed;
             try {
-                A->FindTriggerFrame(true, A->MatTrigFrame + 1);
+                if (trigOn && !trigHostRoute((int)(&st_ - stacks.data()))) {
+                    if (!st_.trigReady)
+                        throw std::runtime_error("RunPipeline: no answer of the device trigger search for this stack");
+                    if (!applySearch(st_))
+                        return;
+                } else
+                    A->FindTriggerFrame(true, A->MatTrigFrame + 1);
             } catch (NeedMoreFrames &) {
                 for (int b = 0; havePix && b < 256 && A->pix_counts.size() == 256; ++b)
                     A->pix_counts[b].resize(pixSize[b]);
@@ -1853,11 +2081,13 @@ void abh_pipe_bellows(void *p, double *out)
 // Run-time knobs of one pipeline object: "blobs" (0 = the host applies the Otsu cut to every candidate pixel, 1 = the
 // device labels the foreground and ships only the pixels of the components the localizer can use; default from
 // ABUB_PIPE_BLOBS) and "contours" (1 = the device also traces the contours of those components and ships their vertices,
-// whatever "blobs" says; a slot the kernel declines keeps the host route; default from ABUB_PIPE_CONTOURS, else 0).  Names and values are checked before the handle: -1 for an unknown name, a bad value or no handle.
+// whatever "blobs" says; a slot the kernel declines keeps the host route; default from ABUB_PIPE_CONTOURS, else 0) and
+// "trigger" (1 = stage 2's trigger search runs on the device, K6, for every stack inside abub_trigger_search_limits; the
+// host search stays for the others; read at the start of a run; default from ABUB_PIPE_TRIGGER, else 0).  Names and values are checked before the handle: -1 for an unknown name, a bad value or no handle.
 int abh_pipe_set_option(void *p, const char *name, int value)
 {
     const std::string opt = name ? name : "";
-    if (opt != "blobs" && opt != "contours") {
+    if (opt != "blobs" && opt != "contours" && opt != "trigger") {
         g_pipeErr = std::string("abh_pipe_set_option: unknown option ") + (name ? name : "(null)");
         return -1;
     }
@@ -1869,8 +2099,28 @@ int abh_pipe_set_option(void *p, const char *name, int value)
         g_pipeErr = "abh_pipe_set_option: no pipeline";
         return -1;
     }
-    (opt == "blobs" ? ((abub::RunPipeline *)p)->blobs : ((abub::RunPipeline *)p)->contours) = value;
+    abub::RunPipeline *rp = (abub::RunPipeline *)p;
+    (opt == "blobs" ? rp->blobs : opt == "contours" ? rp->contours : rp->trigger) = value;
     return 0;
+}
+
+// out[0..5] of the last run with the trigger knob on (zeros otherwise), summed over stack groups and rounds: stacks
+// searched on the device, stacks on the host route (beyond abub_trigger_search_limits), search launches, NEED_FRAMES
+// answers, NEED_FINAL answers, ms of the K6 launches
+void abh_pipe_trigger_stats(void *p, double *out)
+{
+    const abub::PipeStats &st = ((abub::RunPipeline *)p)->stats;
+    const double v[6] = {(double)st.trigDevStacks, (double)st.trigHostStacks, (double)st.trigLaunches, (double)st.trigNeedFrames,
+                         (double)st.trigNeedFinal, st.trigK6Ms};
+    std::memcpy(out, v, sizeof v);
+}
+
+// out[0..1]: the first two numbers of abh_pipe_trigger_stats summed over every pipeline run of this process so far (the
+// pipelines of a batched run are its own: a caller takes the difference around it)
+void abh_pipe_trigger_totals(double *out)
+{
+    out[0] = (double)abub::g_trigTotals[0].load();
+    out[1] = (double)abub::g_trigTotals[1].load();
 }
 
 // out[0..4] of the last run with the contours knob on (zeros otherwise), summed over stack groups and rounds: slots

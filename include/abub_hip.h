@@ -275,6 +275,58 @@ size_t abub_trace_contours_scratch_bytes(int nslots, uint32_t in_cap);
  * them): kept pixels per slot, Freeman codes per border chain.  Needs no device. */
 int abub_trace_contours_limits(int *max_pixels, int *max_chain);
 
+/* K6: AnalyzerUnit::FindTriggerFrame with calculateSignificanceFrame and CalcMean / CalcStdDev (AnalyzerUnit.cpp:119-324,
+ * 435-504, 514-532) on finished 256-bin histograms that are already in device memory: one decision per stack, bit for bit
+ * what host/AnalyzerUnit.cpp FindTriggerFrame makes of the same histograms (host/hostlogic.cpp significanceFromHist).
+ * The histograms of a stack come in segments (the frame blocks of a lazy search); frame 0 has none. */
+typedef struct abub_trig_seg {      /* frames [first, first + count) of one stack */
+    const uint32_t *hist;           /* device: histogram of frame i at (i - first) * 256 */
+    const uint8_t *pending;         /* device or NULL: pending[i - first] != 0 => that histogram is not final */
+    int32_t first, count;
+} abub_trig_seg;
+typedef struct abub_trig_stack {
+    uint32_t seg0, nseg;            /* its segments in the segment array, ascending, not overlapping */
+    int32_t F;                      /* CameraFrames.size() of this stack */
+    int32_t start;                  /* startframe (values < 1 mean 1) */
+    int32_t tss;                    /* TrainingSetSize */
+    int32_t first_bad;              /* smallest frame index with frameOk == false, or F */
+} abub_trig_stack;
+#define ABUB_TRIG_DONE 0            /* the search ran to its end: status / trig / loc_thres are the analyzer's new state */
+#define ABUB_TRIG_NEED_FRAMES 1     /* no segment covers frame need_frame */
+#define ABUB_TRIG_NEED_FINAL 2      /* a segment covers frame need_frame, but its pending flag is set */
+#define ABUB_TRIG_BAD_LOOKAHEAD 3   /* a look-ahead frame is >= first_bad (the host search throws there) */
+typedef struct abub_trig_result {
+    int32_t state;                  /* ABUB_TRIG_* */
+    int32_t status, trig;           /* TriggerFrameIdentificationStatus (0, -3, -9), MatTrigFrame (valid when status == 0, else 0) */
+    int32_t loc_thres;              /* of the last store = true evaluation; -1: none ran, keep the old value */
+    int32_t need_frame;             /* NEED_*: the first frame the search touched and could not read; else 0 */
+    int32_t evaluated;              /* main-loop frames evaluated (statistics) */
+    float sig;                      /* singleEntropy of the last main-loop frame */
+    int32_t reserved;
+} abub_trig_result;
+/* One search per stack (AnalyzerUnit.cpp:119-324, 435-504, 514-532), all in one launch.  stacks[nstacks] and segs[nsegs] are HOST arrays: they are checked here, before
+ * anything is launched (a stack beyond abub_trigger_search_limits, overlapping segments: ABUB_E_INVALID), then copied to
+ * `desc` on the stream -- device memory of abub_trigger_search_desc_bytes(nstacks, nsegs) bytes, 256-byte aligned; keep the
+ * host arrays unchanged until the stream has passed the call.  out[nstacks] (device).  The search reports the first frame
+ * the host search would have touched and cannot be read, counting the frames before `start` (its history) as touched
+ * first: state NEED_FRAMES / NEED_FINAL with need_frame, every other field then as in a fresh record (status -3, trig 0,
+ * loc_thres -1, evaluated 0, sig 0).  A frame behind a missing one never influences anything.  n < 5 gives DONE, -9.
+ * sig_main: NULL, or device [nstacks][sig_pitch] doubles (sig_pitch >= every F): entry [s][i] receives the significance
+ * of every main-loop frame i the search of stack s evaluated, when its state is DONE or BAD_LOOKAHEAD; other entries,
+ * and the whole row of a search that needs frames, are left alone. */
+int abub_trigger_search_dev(const abub_trig_stack *stacks, const abub_trig_seg *segs, int nstacks, int nsegs, int W, int H,
+                            void *desc, size_t desc_bytes, abub_trig_result *out, double *sig_main, int sig_pitch,
+                            void *stream);
+/* pending[j] = 0 for every j < n with done[j] != 0 (device arrays): the deferred flags of the jobs that
+ * abub_diff_hist_pieces_dev has just completed (its `want`), so that the next search (AnalyzerUnit.cpp:119-324, 435-504,
+ * 514-532) reads their histograms; queue it on the stream of that launch. */
+int abub_trigger_clear_pending_dev(uint8_t *pending, const uint8_t *done, size_t n, void *stream);
+/* Descriptor scratch of abub_trigger_search_dev (AnalyzerUnit.cpp:119-324, 435-504, 514-532); 0 for nstacks <= 0 */
+size_t abub_trigger_search_desc_bytes(int nstacks, int nsegs);
+/* The static limits of abub_trigger_search_dev (AnalyzerUnit.cpp:119-324, 435-504, 514-532 stay on the host above them):
+ * frames per stack (F), segments per stack.  Needs no device. */
+int abub_trigger_search_limits(int *max_frames, int *max_segs);
+
 /* Raw terms of cv::matchTemplate(CV_TM_CCORR_NORMED) for the bellows veto (L3Localizer::TrackAFeature,
  * L3Localizer.cpp:499-500): for each of the (W-tw+1) x (H-th+1) placements the exact integer sums
  * num = sum(T*I) and wsum2 = sum(I*I) over the window.  Normalisation is host work (double). */
