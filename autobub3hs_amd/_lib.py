@@ -25,6 +25,25 @@ class TrigStack(C.Structure):
                 ("first_bad", C.c_int32)]
 
 
+class ContourDesc(C.Structure):
+    _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("w", C.c_int32), ("h", C.c_int32), ("area", C.c_double),
+                ("radius", C.c_double), ("m00", C.c_double), ("m10", C.c_double), ("m01", C.c_double), ("cx", C.c_float),
+                ("cy", C.c_float), ("gx", C.c_float), ("gy", C.c_float), ("npts", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class LocMask(C.Structure):
+    _fields_ = [("fid", C.c_void_p), ("bel", C.c_void_p), ("fw", C.c_int32), ("fh", C.c_int32), ("bw", C.c_int32),
+                ("bh", C.c_int32)]
+
+
+LOC_MAXTRACK = 10
+
+
+class LocStack(C.Structure):
+    _fields_ = [("cam", C.c_int32), ("genesis", C.c_int32), ("ntrack", C.c_int32), ("bad", C.c_int32),
+                ("track", C.c_int32 * LOC_MAXTRACK), ("reserved", C.c_int32 * 2)]
+
+
 def build(force=False):
     """Compile the HIP library for gfx950 (cross-compiles without a GPU)."""
     srcs = [os.path.join(HERE, "csrc", f) for f in os.listdir(os.path.join(HERE, "csrc"))
@@ -83,6 +102,11 @@ SIGNATURES = {
     "abub_trigger_search_desc_bytes": (_sz, [_i, _i]),
     "abub_trigger_clear_pending_dev": (_i, [_vp, _vp, _sz, _vp]),
     "abub_trigger_search_limits": (_i, [C.POINTER(_i), C.POINTER(_i)]),
+    "abub_describe_contours_dev": (_i, [_vp, _vp, _vp, C.c_uint32, _vp, _vp, C.c_uint32, _i, _vp, C.c_uint32, _vp]),
+    "abub_localize_stacks_dev": (_i, [_vp, _i, _vp, _i, _vp, _vp, _i, _vp, C.c_uint32, _vp, _sz, _vp, _vp, C.c_uint32, _vp,
+                                      C.c_uint32, _vp, _vp]),
+    "abub_localize_scratch_bytes": (_sz, [_i, _i]),
+    "abub_localize_limits": (_i, [C.POINTER(_i), C.POINTER(_i)]),
     "abub_ctx_create": (_i, [C.POINTER(_vp), _i, _i, _i, _i]),
     "abub_ctx_destroy": (None, [_vp]),
     "abub_ctx_train": (_i, [_vp, C.POINTER(_vp), _i, _vp, _vp]),

@@ -405,3 +405,103 @@ def match_best(frames, frame_idx, tmpl, scratch=None):
                                                     _ptr(out), _ptr(scratch), scratch.numel(), _stream()),
                "abub_match_best_batch_dev")
     return out
+
+
+# ---- K7: descriptors and the localizer's decisions on K5's polygons (abub_localize.hip) -------------------------
+LOC_DONE, LOC_LIMIT, LOC_SLOT, LOC_BAD_FRAME, LOC_BELLOWS, LOC_INCOMPLETE = 0, 1, 2, 3, 4, 5
+
+
+def localize_limits():
+    """(max_contours, max_bubbles) of K7b: a stack with more contours in a slot, or more bubbles, keeps the host route."""
+    import ctypes as C
+    mc, mb = C.c_int(0), C.c_int(0)
+    _lib.check(_lib.lib().abub_localize_limits(C.byref(mc), C.byref(mb)), "abub_localize_limits")
+    return mc.value, mb.value
+
+
+def desc_dtype():
+    """numpy dtype of one abub_contour_desc record"""
+    import numpy as np
+    return np.dtype([("x", "<i4"), ("y", "<i4"), ("w", "<i4"), ("h", "<i4"), ("area", "<f8"), ("radius", "<f8"), ("m00", "<f8"),
+                     ("m10", "<f8"), ("m01", "<f8"), ("cx", "<f4"), ("cy", "<f4"), ("gx", "<f4"), ("gy", "<f4"), ("npts", "<u4"),
+                     ("reserved", "<u4")])
+
+
+def describe_contours(tc, cont_cap=None, pts_cap=None, desc_cap=None):
+    """K7a (abub_describe_contours_dev) on the dict trace_contours() returned -> uint8 device tensor [desc_cap, 80], one
+    abub_contour_desc per contour of the list (desc_records() reads it on the host).  The capacities default to the sizes
+    of the list's tensors."""
+    status, cont_off, npts, pt_off, pts = tc["status"], tc["cont_off"], tc["cont_npts"], tc["pt_off"], tc["pts"]
+    _need_cuda(status, cont_off, npts, pt_off, pts)
+    n = status.numel()
+    cont_cap = int(npts.numel()) if cont_cap is None else int(cont_cap)
+    pts_cap = int(pts.numel()) if pts_cap is None else int(pts_cap)
+    desc_cap = cont_cap if desc_cap is None else int(desc_cap)
+    desc = torch.zeros((max(desc_cap, 1), 80), dtype=torch.uint8, device=status.device)
+    _lib.check(_lib.lib().abub_describe_contours_dev(_ptr(status), _ptr(cont_off), _ptr(npts), cont_cap, _ptr(pt_off), _ptr(pts),
+                                                     pts_cap, n, _ptr(desc), desc_cap, _stream()), "abub_describe_contours_dev")
+    return desc
+
+
+def desc_records(desc, n=None):
+    """the records of describe_contours() as a numpy structured array (desc_dtype)"""
+    a = desc.cpu().numpy().reshape(-1).view(desc_dtype())
+    return a if n is None else a[:n]
+
+
+def localize_stacks(stacks, masks, slot_status, cont_off, desc, ndesc=None, rect_cap=None, track_cap=None, guard=0):
+    """K7b (abub_localize_stacks_dev): the localizer's decisions per stack in one launch.  stacks: a list of dicts with cam,
+    genesis (slot) and track (slots in frame order), optionally bad; masks: per camera (fiducial, bellows), each a uint8
+    device tensor [h, w] or None; slot_status / cont_off: of trace_contours(); desc: of describe_contours().
+    -> (list of dicts with status, nrects, nbubbles, rects (list of (x, y, w, h), None when the list was too small) and
+    bubbles (per bubble the record indices of its descriptors, None when the list was too small), totals (rects, track
+    dwords) that the launch would have needed, (rects, tracks) as numpy arrays with `guard` more entries than the
+    capacities, filled with -1 before the launch)."""
+    import ctypes as C
+    _need_cuda(slot_status, cont_off, desc)
+    n, nc = len(stacks), len(masks)
+    st = (_lib.LocStack * max(n, 1))()
+    mk = (_lib.LocMask * max(nc, 1))()
+    for i, s in enumerate(stacks):
+        st[i].cam, st[i].genesis, st[i].ntrack, st[i].bad = s["cam"], s["genesis"], len(s["track"]), int(s.get("bad", 0))
+        for k, t in enumerate(s["track"][:_lib.LOC_MAXTRACK]):
+            st[i].track[k] = t
+    for c, (fid, bel) in enumerate(masks):
+        _need_cuda(fid, bel)
+        mk[c].fid, mk[c].bel = _ptr(fid), _ptr(bel)
+        mk[c].fh, mk[c].fw = (fid.shape if fid is not None else (0, 0))
+        mk[c].bh, mk[c].bw = (bel.shape if bel is not None else (0, 0))
+    dev = desc.device
+    L = _lib.lib()
+    ndesc = int(desc.shape[0]) if ndesc is None else int(ndesc)
+    mc, mb = localize_limits()
+    rect_cap = max(n * mc, 1) if rect_cap is None else int(rect_cap)
+    track_cap = max(n * mb * (_lib.LOC_MAXTRACK + 2), 1) if track_cap is None else int(track_cap)
+    scratch = torch.empty((max(int(L.abub_localize_scratch_bytes(n, nc)), 1),), dtype=torch.uint8, device=dev)
+    out = torch.zeros((max(n, 1), 8), dtype=torch.int32, device=dev)
+    rects = torch.full((rect_cap + guard, 4), -1, dtype=torch.int32, device=dev)
+    tracks = torch.full((track_cap + guard,), -1, dtype=torch.int32, device=dev)
+    totals = torch.zeros((2,), dtype=torch.int32, device=dev)
+    _lib.check(L.abub_localize_stacks_dev(C.addressof(st), n, C.addressof(mk), nc, _ptr(slot_status), _ptr(cont_off),
+                                          slot_status.numel(), _ptr(desc), ndesc, _ptr(scratch), scratch.numel(), _ptr(out),
+                                          _ptr(rects), rect_cap, _ptr(tracks), track_cap, _ptr(totals), _stream()),
+               "abub_localize_stacks_dev")
+    rows = out.cpu().numpy()  # (synchronises: the host arrays above stay alive until here)
+    R, T, tot = rects.cpu().numpy(), tracks.cpu().numpy(), [int(v) for v in totals.cpu().numpy()]
+    res = []
+    for i in range(n):
+        status, nrects, roff, nbub, ntr, toff = (int(v) for v in rows[i, :6])
+        r = {"status": status, "nrects": nrects, "nbubbles": nbub, "rects": None, "bubbles": None,
+             "rect_off": roff, "track_off": toff, "ntrack": ntr}
+        if status == 0:
+            if roff + nrects <= rect_cap:
+                r["rects"] = [tuple(int(v) for v in R[roff + k]) for k in range(nrects)]
+            if toff + ntr <= track_cap:
+                o, bub = toff, []
+                for _ in range(nbub):
+                    m = int(T[o])
+                    bub.append([int(v) for v in T[o + 1:o + 1 + m]])
+                    o += 1 + m
+                r["bubbles"] = bub
+        res.append(r)
+    return res, tot, (R, T)

@@ -68,7 +68,9 @@ SIGNATURES = {
     "abh_pipe_blob_stats": (None, [_vp, _dp]),
     "abh_pipe_contour_stats": (None, [_vp, _dp]),
     "abh_pipe_trigger_stats": (None, [_vp, _dp]),
+    "abh_pipe_localize_stats": (None, [_vp, _dp]),
     "abh_pipe_trigger_totals": (None, [_dp]),
+    "abh_pipe_localize_totals": (None, [_dp]),
     "abh_pipe_bellows": (None, [_vp, _dp]),
 }
 _lib = None
@@ -350,6 +352,14 @@ def best_match(num, wsum2, tmpl):
     return bx.value, by.value
 
 
+def localize_totals():
+    """(stacks localised on the device, stacks on the host route) with the "localize" knob on, over every pipeline run of
+    this process so far -- see trigger_totals()."""
+    out = (C.c_double * 2)()
+    lib().abh_pipe_localize_totals(out)
+    return int(out[0]), int(out[1])
+
+
 def trigger_totals():
     """(stacks searched on the device, stacks on the host route) with the "trigger" knob on, over every pipeline run of
     this process so far -- Run.run_batched owns its pipelines, so a caller takes the difference around it."""
@@ -433,7 +443,9 @@ class Pipeline:
         ABUB_PIPE_CONTOURS) or 1 -- also trace the contours of those components on the GPU (K5) and ship their vertices,
         whatever "blobs" says; "trigger" 0 (default, from ABUB_PIPE_TRIGGER) or 1 -- run the trigger search of every
         stack inside the kernel's limits on the GPU (K6) from the histograms that are already there, instead of
-        FindTriggerFrame on host threads; read at the start of a run.  Results never depend on them."""
+        FindTriggerFrame on host threads; read at the start of a run; "localize" 0 (default, from ABUB_PIPE_LOCALIZE) or 1
+        -- also describe the contours and run the localizer's decisions per stack on the GPU (K7), whatever "contours"
+        and "blobs" say; a stack the kernels decline keeps the host route.  Results never depend on them."""
         L = lib()
         if L.abh_pipe_set_option(self._h, name.encode(), int(value)) != 0:
             raise ValueError(L.abh_pipe_error().decode())
@@ -456,6 +468,24 @@ class Pipeline:
         v = list(out)
         d = {k: int(x) for k, x in zip(("traced", "host_route", "contours", "vertices"), v)}
         d["k5_ms"] = v[4]
+        return d
+
+    def localize_stats(self):
+        """Device localizer of the last run (zeros when the "localize" knob was off), summed over stack groups and rounds:
+        stacks localised on the device; stacks on the host route (host_route, and by reason: over a limit, with a declined
+        slot or an undecodable frame, with every genesis contour in the bellows mask, other: an Otsu mismatch); bubbles and
+        descriptors of the device's tracks; ms of the K7 launches; list_bytes: what stage 3 copied to the host of the kept-pixel,
+        contour, vertex, record, box and track lists (counted with the "contours" knob alone, too); regrows: batches redone
+        because the record list, or the box and track lists, had to grow."""
+        out = (C.c_double * 10)()
+        lib().abh_pipe_localize_stats(self._h, out)
+        v = list(out)
+        keys = ("device", "host_limits", "host_slot", "host_bellows", "host_other", "bubbles", "descriptors")
+        d = {k: int(x) for k, x in zip(keys, v)}
+        d["host_route"] = d["host_limits"] + d["host_slot"] + d["host_bellows"] + d["host_other"]
+        d["k7_ms"] = v[7]
+        d["list_bytes"] = int(v[8])
+        d["regrows"] = int(v[9])
         return d
 
     def trigger_stats(self):

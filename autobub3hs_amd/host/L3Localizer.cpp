@@ -263,6 +263,22 @@ void L3Localizer::LocalizeOMatic(std::string)
     presentationFrame = triggerFrame.clone();
     ComparisonFrame = ev.hostFrame(0);
 
+    // a provider that ran the localizer's decisions on the device hands over the finished tracks; the bubbles are rebuilt
+    // from their descriptors the way StagedBubbles::stage rebuilds them.  A debug analyzer (!nonStopMode) does not ask:
+    // its write-outs and the presentationFrame rectangles come from the host's own pass over the contours
+    std::vector<std::vector<BubbleImageFrame>> tracks;
+    if (nonStopMode && ev.localized(MatTrigFrame, bubbleRects, tracks)) {
+        for (const std::vector<BubbleImageFrame> &t : tracks) {
+            bubble *b = new bubble(t[0]);
+            for (size_t d = 1; d < t.size(); ++d) {
+                b->lockThisIteration = false;
+                *b << t[d];
+            }
+            BubbleList.push_back(b);
+        }
+        return;
+    }
+
     CalculateInitialBubbleParams();
 
     const int last = (MatTrigFrame < 29) ? NumFramesBubbleTrack : (39 - MatTrigFrame);
@@ -274,7 +290,8 @@ void L3Localizer::LocalizeOMatic(std::string)
 }
 
 // mask files are immutable during a run: decode each once per process instead of once per analyzer
-static cv::Mat cachedMask(const std::string &path)
+static cv::Mat cachedMask(const std::string &path) { return abub::cachedMaskImage(path); }
+cv::Mat abub::cachedMaskImage(const std::string &path)
 {
     static std::mutex mu;
     static std::map<std::string, cv::Mat> cache;

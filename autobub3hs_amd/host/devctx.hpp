@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "abub_hip.h"
+#include "bubble/bubble.hpp"
 #include "cvlite.hpp"
 
 class Parser;
@@ -70,6 +71,16 @@ public:
         (void)out;
         return false;
     }
+    // a finished localisation of trigger frame `trig`, when the provider has one (decided on the device, abub_localize.hip):
+    // true, the boxes of L3Localizer::bubbleRects appended to `rects` and per bubble its descriptors in sighting order (the
+    // genesis first) in `tracks`.  false: LocalizeOMatic runs as it always has.  Default: false.
+    virtual bool localized(int trig, std::vector<cv::Rect> &rects, std::vector<std::vector<BubbleImageFrame>> &tracks)
+    {
+        (void)trig;
+        (void)rects;
+        (void)tracks;
+        return false;
+    }
     // bellows veto: exact correlation terms of frame i against a template ((H-th+1) x (W-tw+1) placements)
     virtual void matchTerms(int i, const cv::Mat &templ, std::vector<unsigned long long> &num,
                             std::vector<unsigned long long> &wsum2) = 0;
@@ -87,6 +98,10 @@ public:
     // AnalyzerUnit::ProcessFrame(cur, ref, out, 5, roi) with this event's model (used by the default bellowsResidual)
     virtual void processFrameROI(cv::Mat &cur, cv::Mat &ref, cv::Rect roi, cv::Mat &out);
 };
+
+// the mask image L3Localizer::isInMask reads from `path` (cam<N>_mask.bmp, cam<N>_bellows_mask.bmp), decoded once per
+// process; empty when the file is missing or not loadable
+cv::Mat cachedMaskImage(const std::string &path);
 
 // AnalyzerUnit::ProcessFrame (AnalyzerUnit.cpp:79-97) on two host images with `model`: the pair is staged as a two-frame
 // stack in the thread's context; out = D(cur; ref) on `roi` (the whole frame: the full-frame kernel)

@@ -45,6 +45,8 @@ extern bool g_quietAnalyzers;
 // trigger knob, summed over every pipeline run of the process (a batched run owns its pipelines; abh_pipe_trigger_totals):
 // stacks searched on the device, stacks on the host route
 static std::atomic<long long> g_trigTotals[2];
+// localize knob, likewise (abh_pipe_localize_totals): stacks localised on the device, stacks on the host route
+static std::atomic<long long> g_locTotals[2];
 
 namespace {
 
@@ -83,6 +85,7 @@ struct PlannedImage {
     bool keptShipped = true; // false: the batch had no declined slot, so its kept pixels stayed on the device
     const uint32_t *cnp = nullptr, *cpts = nullptr;
     uint32_t ncont = 0;
+    bool vertsShipped = true; // false (localize knob): every stack of the batch was localised on the device, the vertices stayed there
 };
 
 // thrown by the batched provider when the trigger search asks for a frame whose block has not been evaluated yet: the
@@ -275,6 +278,8 @@ public:
             return false;
         if (p.otsuMismatch)
             throw std::runtime_error("BatchEventData::contoursKept: device Otsu threshold differs from the host's");
+        if (!p.vertsShipped)
+            throw std::runtime_error("BatchEventData::contoursKept: the vertices of a localised batch stayed on the device");
         out.resize(p.ncont);
         const uint32_t *q = p.cpts;
         for (uint32_t k = 0; k < p.ncont; ++k) {
@@ -282,6 +287,41 @@ public:
             c.resize(p.cnp[k]);
             for (uint32_t v = 0; v < p.cnp[k]; ++v, ++q)
                 c[v] = cv::Point((int)(*q & 0xffffu), (int)(*q >> 16));
+        }
+        return true;
+    }
+    // localize knob: the finished localisation of the planned trigger (K7, abub_localize.hip) in the round's lists; valid
+    // from batchImages() until the search plans the next trigger
+    bool locReady = false;
+    int locTrig = -1;
+    abub_loc_result locRes{};
+    const int32_t *locRects = nullptr;
+    const uint32_t *locTracks = nullptr;
+    const abub_contour_desc *locDesc = nullptr;
+    bool localized(int trig, std::vector<cv::Rect> &rects, std::vector<std::vector<BubbleImageFrame>> &tracks) override
+    {
+        if (!locReady || trig != locTrig)
+            return false;
+        const int32_t *r = locRects + 4 * (size_t)locRes.rect_off;
+        for (uint32_t k = 0; k < locRes.nrects; ++k, r += 4)
+            rects.push_back(cv::Rect(r[0], r[1], r[2], r[3]));
+        const uint32_t *t = locTracks + locRes.track_off;
+        tracks.resize(locRes.nbubbles);
+        for (uint32_t b = 0; b < locRes.nbubbles; ++b) {
+            const uint32_t n = *t++;
+            for (uint32_t j = 0; j < n; ++j) {
+                const abub_contour_desc &d = locDesc[*t++];
+                BubbleImageFrame f;
+                f.ContArea = d.area;
+                f.newPosition = cv::Rect(d.x, d.y, d.w, d.h);
+                f.moments = cv::Moments();
+                f.moments.m00 = d.m00;
+                f.moments.m10 = d.m10;
+                f.moments.m01 = d.m01;
+                f.ContRadius = d.radius;
+                f.MassCentres = j == 0 ? cv::Point2f(d.gx, d.gy) : cv::Point2f(d.cx, d.cy); // genesis / tracking form
+                tracks[b].push_back(f);
+            }
         }
         return true;
     }
@@ -528,6 +568,13 @@ struct PipeStats {
     // K6 launches (per group, merged); search launches (kept by the pipeline, like jobsLaunched)
     long long trigDevStacks = 0, trigHostStacks = 0, trigNeedFrames = 0, trigNeedFinal = 0, trigLaunches = 0;
     double trigK6Ms = 0;
+    // localize knob, summed over the rounds: stacks localised on the device, stacks on the host route by reason (over a
+    // limit; a declined slot or an undecodable frame; every genesis contour in the bellows mask; an Otsu mismatch),
+    // bubbles and descriptors of the device's tracks, ms of the K7 launches
+    long long locDevice = 0, locHostLimit = 0, locHostSlot = 0, locHostBellows = 0, locHostOther = 0, locBubbles = 0, locDescs = 0;
+    double locK7Ms = 0;
+    long long locRegrows = 0; // batches redone because the record list, or the box / track lists, were too small
+    long long listBytes = 0; // contours / localize knobs: bytes of the kept-pixel, contour, vertex, record, box and track lists copied to the host
 
     void reset() { *this = PipeStats(); }
     // a group's counters into the run's: the groups run side by side, so times and rounds take the maximum, counts add
@@ -564,6 +611,16 @@ struct PipeStats {
         trigNeedFrames += g.trigNeedFrames;
         trigNeedFinal += g.trigNeedFinal;
         trigK6Ms += g.trigK6Ms;
+        locDevice += g.locDevice;
+        locHostLimit += g.locHostLimit;
+        locHostSlot += g.locHostSlot;
+        locHostBellows += g.locHostBellows;
+        locHostOther += g.locHostOther;
+        locBubbles += g.locBubbles;
+        locDescs += g.locDescs;
+        locK7Ms += g.locK7Ms;
+        locRegrows += g.locRegrows;
+        listBytes += g.listBytes;
     }
 };
 
@@ -628,6 +685,21 @@ struct Group {
         std::vector<int> list;
         Event ev[2]; // before and after the launch
     } trig;
+    // localize knob: K7 behind K5 (allocated on first use): the records of the round's contours, the stack descriptors of
+    // one launch (pinned, copied by the launcher), the per-stack results and the box / track lists, which grow when a
+    // batch overflows them
+    struct Localize {
+        bool ready = false;
+        uint32_t descCap = 0, rectCap = 0, trackCap = 0;
+        Mirror<abub_contour_desc> desc;
+        PinnedArray<abub_loc_stack> st;
+        DeviceArray<uint8_t> scratch;
+        size_t scratchBytes = 0;
+        Mirror<abub_loc_result> res;
+        Mirror<int32_t> rects;
+        Mirror<uint32_t> tracks, totals;
+        Event ev[2]; // before K7a and after K7b
+    } loc;
     // bellows veto round (vetoRound): its own buffers, allocated on first use, grown on demand
     struct Veto {
         int capJobs = 0;           // match jobs the buffers hold
@@ -671,9 +743,15 @@ public:
     int chainStride = 0;                // FindTriggerFrame's frame offset when every camera shares it, else 0
     bool ordered = true;                // localisation kernels queue on stage1Stream too (see batchImages())
     int pairCap = 0;                    // ABUB_PIPE_PAIRCAP (0: unset)
+    int locCap = 0;                     // ABUB_PIPE_LOCCAP (0: unset)
     int blobs = 0;                      // 1: stage 3 labels blobs on the GPU and ships only the kept pixels (set_option "blobs")
     int contours = 0;                   // 1: stage 3 also traces the contours on the GPU and ships their vertices (set_option "contours")
     int trigger = 0;                    // 1: the trigger search runs on the GPU (K6) for every stack inside its limits (set_option "trigger")
+    int localizeDev = 0;                // 1: stage 3 also describes the contours and runs the localizer's decisions on the GPU (K7; set_option "localize")
+    std::mutex maskMu;                  // the cameras' masks on the device, uploaded once per pipeline (deviceMasks)
+    bool masksReady = false;
+    std::vector<DeviceArray<uint8_t>> maskBuf;
+    std::vector<abub_loc_mask> locMasks;
     bool trigOn = false;                // `trigger` as read at the start of the current run
     int trigMaxF = 0;                   // abub_trigger_search_limits: a longer stack keeps the host search
     std::mutex launchMu;
@@ -891,6 +969,8 @@ public:
         contours = ect ? atoi(ect) != 0 : 0;
         const char *etr = getenv("ABUB_PIPE_TRIGGER");
         trigger = etr ? atoi(etr) != 0 : 0;
+        const char *elo = getenv("ABUB_PIPE_LOCALIZE");
+        localizeDev = elo ? atoi(elo) != 0 : 0;
         int trigMaxSegs = 0;
         check(abub_trigger_search_limits(&trigMaxF, &trigMaxSegs), "abub_trigger_search_limits");
         if (trigMaxSegs < BatchEventData::MAXB)
@@ -933,6 +1013,9 @@ public:
         // initial capacity of the candidate lists (they grow on demand): ABUB_PIPE_PAIRCAP sets the veto's too
         const char *ec = getenv("ABUB_PIPE_PAIRCAP");
         pairCap = ec ? atoi(ec) : 0;
+        // ... and of the record, box and track lists of the localize knob: ABUB_PIPE_LOCCAP entries each
+        const char *elc = getenv("ABUB_PIPE_LOCCAP");
+        locCap = elc ? atoi(elc) : 0;
         for (int g = 0; g < ngroups; ++g) {
             Group &G = groups[g];
             G.s0 = (int)((long long)S * g / ngroups);
@@ -1075,6 +1158,8 @@ public:
         }
         g_trigTotals[0] += stats.trigDevStacks;
         g_trigTotals[1] += stats.trigHostStacks;
+        g_locTotals[0] += stats.locDevice;
+        g_locTotals[1] += stats.locHostLimit + stats.locHostSlot + stats.locHostBellows + stats.locHostOther;
         stats.totalMs = nowMs() - t0;
     }
 
@@ -1432,6 +1517,7 @@ private:
             const int off = refOffset(A->TrainedData->TrainingSetSize);
             st_.data.planned.clear();
             st_.data.cur = nullptr;
+            st_.data.locReady = false;
             st_.data.clearVeto(); // a new trigger: new veto keys
             PlannedImage g;
             g.kind = 0;
@@ -1499,8 +1585,14 @@ private:
         // pixels of the components the localizer can use come back (abub_blobs.hip); the knob is read once per batch
         // contours knob: K5 then traces each image's contours from K4b's kept list (abub_contours.hip) and the vertices
         // come back; the kept pixels travel only when a slot was declined.  It implies device Otsu + K4b
-        const bool useContours = contours != 0;
+        // localize knob: K7 then describes every contour and runs the localizer's decisions per stack (abub_localize.hip);
+        // the finished tracks come back, the vertices only when some stack was declined.  It implies the contours knob
+        const bool useLocalize = localizeDev != 0;
+        const bool useContours = contours != 0 || useLocalize;
         const bool useBlobs = blobs != 0 || useContours;
+        Group::Localize &Z = G.loc;
+        bool recordsGrown = false, tracksGrown = false;
+        const int nloc = (int)loc.size();
         Group::Blobs &B = G.blobs;
         Group::Contours &K = G.contours;
         CandidateList &L = G.list;
@@ -1564,6 +1656,37 @@ private:
                       "stage3 K5");
                 HIPOK(hipEventRecord(K.ev[1].get(), stream));
             }
+            if (useLocalize) {
+                fitLocalize(G);
+                for (int k = 0; k < nloc; ++k) {
+                    const StackState &ss = stacks[loc[k]];
+                    abub_loc_stack &d = Z.st[k];
+                    d = abub_loc_stack{};
+                    d.cam = loc[k] % C;
+                    d.bad = !ss.data.frameOk(0);
+                    int nt = 0;
+                    for (const PlannedImage &p : ss.data.planned) {
+                        if (!ss.data.frameOk(p.i) || (p.kind == 0 && !ss.data.frameOk(p.ref)))
+                            d.bad = 1;
+                        if (p.kind == 0)
+                            d.genesis = p.slot;
+                        else if (nt < ABUB_LOC_MAXTRACK)
+                            d.track[nt++] = p.slot; // (planned in frame order)
+                        else
+                            throw std::runtime_error("RunPipeline: more tracking frames planned than ABUB_LOC_MAXTRACK");
+                    }
+                    d.ntrack = nt;
+                }
+                HIPOK(hipEventRecord(Z.ev[0].get(), stream));
+                check(abub_describe_contours_dev(K.status.d, K.coff.d, K.cnpts.d, K.contCap, K.poff.d, K.pts.d, K.ptsCap, nimg,
+                                                 Z.desc.d, Z.descCap, stream),
+                      "stage3 K7a");
+                check(abub_localize_stacks_dev(Z.st, nloc, locMasks.data(), C, K.status.d, K.coff.d, nimg, Z.desc.d,
+                                               std::min(Z.descCap, K.contCap), Z.scratch, Z.scratchBytes, Z.res.d, Z.rects.d,
+                                               Z.rectCap, Z.tracks.d, Z.trackCap, Z.totals.d, stream),
+                      "stage3 K7b");
+                HIPOK(hipEventRecord(Z.ev[1].get(), stream));
+            }
             HIPOK(hipEventRecord(G.kernelsDone.get(), stream));
             HIPOK(hipStreamWaitEvent(back, G.kernelsDone.get(), 0));
             G.hist3.toHost((size_t)nimg * 256, back);
@@ -1579,7 +1702,16 @@ private:
                 K.poff.toHost((size_t)nimg + 1, back);
                 K.cstats.toHost(4, back);
             }
+            if (useLocalize) {
+                Z.res.toHost((size_t)nloc, back);
+                Z.totals.toHost(2, back);
+            }
             HIPOK(hipStreamSynchronize(back));
+            if (useLocalize) {
+                float m = 0;
+                HIPOK(hipEventElapsedTime(&m, Z.ev[0].get(), Z.ev[1].get()));
+                G.stats.locK7Ms += m;
+            }
             if (useContours) {
                 float m = 0;
                 HIPOK(hipEventElapsedTime(&m, K.ev[0].get(), K.ev[1].get()));
@@ -1608,21 +1740,60 @@ private:
                 contoursGrown = true;
                 continue;
             }
+            // ... and the same for the lists of the localize knob, in two steps.  K7b declines (INCOMPLETE) every stack
+            // with records beyond the record list, and a declined stack reserves no boxes or tracks: while the records do
+            // not fit the two totals are lower bounds, so the record list grows first, from K5's true count, ...
+            if (useLocalize && K.coff.h[nimg] > Z.descCap) {
+                if (recordsGrown)
+                    throw std::runtime_error("RunPipeline: localizer record list overflow after it was grown");
+                growLocalize(Z, K.coff.h[nimg], 0, 0);
+                recordsGrown = true;
+                ++G.stats.locRegrows;
+                continue;
+            }
+            // ... and the boxes and tracks once every stack was looked at: now the totals are true counts
+            if (useLocalize && (Z.totals.h[0] > Z.rectCap || Z.totals.h[1] > Z.trackCap)) {
+                if (tracksGrown)
+                    throw std::runtime_error("RunPipeline: localizer box / track list overflow after it was grown");
+                growLocalize(Z, 0, Z.totals.h[0], Z.totals.h[1]);
+                tracksGrown = true;
+                ++G.stats.locRegrows;
+                continue;
+            }
             break;
         }
         const uint32_t cnt = *L.count.h;
         const uint32_t nkept = useBlobs ? B.koff.h[nimg] : 0;
+        // localize knob: the vertices travel only when some stack was declined and takes the host route
+        bool shipVerts = !useLocalize;
+        for (int k = 0; useLocalize && k < nloc; ++k)
+            shipVerts = shipVerts || Z.res.h[k].status != ABUB_LOC_DONE;
         if (useBlobs) {
             if (nkept > L.cap)
                 throw std::runtime_error("RunPipeline: kept list larger than the candidate list");
             // with the contours knob the pixels travel only when some slot was declined and takes the host route
-            if (nkept && (!useContours || K.cstats.h[1] != 0))
+            if (nkept && (!useContours || K.cstats.h[1] != 0)) {
                 L.kidx.toHost(nkept, back);
+                G.stats.listBytes += useContours ? 4ll * nkept : 0;
+            }
             if (useContours) {
-                if (const uint32_t nc = K.coff.h[nimg])
-                    K.cnpts.toHost(nc, back);
-                if (const uint32_t nv = K.poff.h[nimg])
-                    K.pts.toHost(nv, back);
+                if (shipVerts) {
+                    if (const uint32_t nc = K.coff.h[nimg])
+                        K.cnpts.toHost(nc, back);
+                    if (const uint32_t nv = K.poff.h[nimg])
+                        K.pts.toHost(nv, back);
+                    G.stats.listBytes += 4ll * K.coff.h[nimg] + 4ll * K.poff.h[nimg];
+                }
+                if (useLocalize) {
+                    if (const uint32_t nc = K.coff.h[nimg])
+                        Z.desc.toHost(nc, back);
+                    if (Z.totals.h[0])
+                        Z.rects.toHost(4 * (size_t)Z.totals.h[0], back);
+                    if (Z.totals.h[1])
+                        Z.tracks.toHost(Z.totals.h[1], back);
+                    G.stats.listBytes += (long long)sizeof(abub_contour_desc) * K.coff.h[nimg] + 16ll * Z.totals.h[0] +
+                                         4ll * Z.totals.h[1] + (long long)sizeof(abub_loc_result) * nloc;
+                }
                 G.stats.contTraced += K.cstats.h[0];
                 G.stats.contHost += K.cstats.h[1];
                 G.stats.contContours += K.cstats.h[2];
@@ -1650,6 +1821,7 @@ private:
                 p->otsuMismatch = B.otsu.h[k] != p->thr;
                 p->traced = useContours && K.status.h[k] == 0;
                 p->keptShipped = !useContours || K.cstats.h[1] != 0;
+                p->vertsShipped = shipVerts;
                 if (p->traced) {
                     p->cnp = K.cnpts.h + K.coff.h[k];
                     p->cpts = K.pts.h + K.poff.h[k];
@@ -1661,9 +1833,36 @@ private:
                 p->nkept = 0;
                 p->traced = false;
                 p->keptShipped = true;
+                p->vertsShipped = true;
             }
         });
         HIPOK(hipStreamSynchronize(back));
+        // localize knob: a stack the kernels finished, and whose thresholds the host confirms, skips stage 4's arithmetic
+        for (int k = 0; useLocalize && k < nloc; ++k) {
+            BatchEventData &d = stacks[loc[k]].data;
+            const abub_loc_result &r = Z.res.h[k];
+            bool mismatch = false;
+            for (const PlannedImage &p : d.planned)
+                mismatch = mismatch || p.otsuMismatch;
+            d.locReady = r.status == ABUB_LOC_DONE && !mismatch;
+            if (d.locReady) {
+                d.locTrig = d.planned[0].i;
+                d.locRes = r;
+                d.locRects = Z.rects.h;
+                d.locTracks = Z.tracks.h;
+                d.locDesc = Z.desc.h;
+                ++G.stats.locDevice;
+                G.stats.locBubbles += r.nbubbles;
+                G.stats.locDescs += r.ntrack - r.nbubbles;
+            } else if (r.status == ABUB_LOC_LIMIT)
+                ++G.stats.locHostLimit;
+            else if (r.status == ABUB_LOC_SLOT || r.status == ABUB_LOC_BAD_FRAME)
+                ++G.stats.locHostSlot;
+            else if (r.status == ABUB_LOC_BELLOWS)
+                ++G.stats.locHostBellows;
+            else
+                ++G.stats.locHostOther;
+        }
         G.stats.s3ListMs += nowMs() - ta; // list D2H (+ thresholds)
     }
 
@@ -1965,6 +2164,75 @@ private:
         }
     }
 
+    // the localize buffers of the group: per-stack arrays once, the record, box and track lists at a modest size to start
+    // with (they grow like the contour lists); the cameras' masks once per pipeline
+    void fitLocalize(Group &G)
+    {
+        Group::Localize &Z = G.loc;
+        deviceMasks();
+        if (Z.ready)
+            return;
+        const size_t ns = (size_t)(G.s1 - G.s0);
+        Z.st.allocate(ns);
+        Z.scratchBytes = abub_localize_scratch_bytes((int)ns, C);
+        Z.scratch.allocate(Z.scratchBytes);
+        Z.res.allocate(ns);
+        Z.totals.allocate(2);
+        for (Event &e : Z.ev)
+            e.create(true);
+        if (locCap > 0) { // (exactly: the lists are meant to overflow)
+            Z.desc.allocate((size_t)locCap);
+            Z.rects.allocate(4 * (size_t)locCap);
+            Z.tracks.allocate((size_t)locCap);
+            Z.descCap = Z.rectCap = Z.trackCap = (uint32_t)locCap;
+        } else
+            growLocalize(Z, (uint32_t)(64 * ns), (uint32_t)(8 * ns), (uint32_t)(16 * ns));
+        Z.ready = true;
+    }
+    void growLocalize(Group::Localize &Z, uint32_t nd, uint32_t nr, uint32_t nt)
+    {
+        if (nd > Z.descCap) {
+            Z.descCap = 0;
+            Z.desc.allocate((size_t)nd + nd / 4 + 64);
+            Z.descCap = nd + nd / 4 + 64;
+        }
+        if (nr > Z.rectCap) {
+            Z.rectCap = 0;
+            Z.rects.allocate(4 * ((size_t)nr + nr / 4 + 64));
+            Z.rectCap = nr + nr / 4 + 64;
+        }
+        if (nt > Z.trackCap) {
+            Z.trackCap = 0;
+            Z.tracks.allocate((size_t)nt + nt / 4 + 64);
+            Z.trackCap = nt + nt / 4 + 64;
+        }
+    }
+    // cam<N>_mask.bmp and cam<N>_bellows_mask.bmp of every camera as L3Localizer::isInMask reads them, decoded through the
+    // process-wide mask cache and uploaded once per pipeline; no mask dir, or a file that is not loadable: no mask
+    void deviceMasks()
+    {
+        std::lock_guard<std::mutex> lock(maskMu);
+        if (masksReady)
+            return;
+        locMasks.assign((size_t)C, abub_loc_mask{});
+        maskBuf.clear();
+        maskBuf.resize(2 * (size_t)C);
+        for (int c = 0; c < C && !maskDir.empty(); ++c)
+            for (int b = 0; b < 2; ++b) {
+                const cv::Mat m = cachedMaskImage(maskDir + "/cam" + std::to_string(c) + (b ? "_bellows_mask.bmp" : "_mask.bmp"));
+                if (m.empty())
+                    continue;
+                DeviceArray<uint8_t> &buf = maskBuf[2 * (size_t)c + b];
+                buf.allocate((size_t)m.cols * m.rows);
+                HIPOK(hipMemcpy((uint8_t *)buf, m.data, (size_t)m.cols * m.rows, hipMemcpyHostToDevice)); // (a Mat is continuous)
+                abub_loc_mask &k = locMasks[(size_t)c];
+                (b ? k.bel : k.fid) = buf;
+                (b ? k.bw : k.fw) = m.cols;
+                (b ? k.bh : k.fh) = m.rows;
+            }
+        masksReady = true;
+    }
+
     // AnyCamAnalysis body from LocalizeOMatic on (AutoBubStart3.cpp:94-110)
     void localize(StackState &st_)
     {
@@ -2083,11 +2351,13 @@ void abh_pipe_bellows(void *p, double *out)
 // ABUB_PIPE_BLOBS) and "contours" (1 = the device also traces the contours of those components and ships their vertices,
 // whatever "blobs" says; a slot the kernel declines keeps the host route; default from ABUB_PIPE_CONTOURS, else 0) and
 // "trigger" (1 = stage 2's trigger search runs on the device, K6, for every stack inside abub_trigger_search_limits; the
-// host search stays for the others; read at the start of a run; default from ABUB_PIPE_TRIGGER, else 0).  Names and values are checked before the handle: -1 for an unknown name, a bad value or no handle.
+// host search stays for the others; read at the start of a run; default from ABUB_PIPE_TRIGGER, else 0) and "localize" (1 =
+// stage 3 also describes the contours and runs the localizer's decisions per stack on the device, K7, whatever "contours"
+// and "blobs" say; a stack the kernels decline keeps the host route; default from ABUB_PIPE_LOCALIZE, else 0).  Names and values are checked before the handle: -1 for an unknown name, a bad value or no handle.
 int abh_pipe_set_option(void *p, const char *name, int value)
 {
     const std::string opt = name ? name : "";
-    if (opt != "blobs" && opt != "contours" && opt != "trigger") {
+    if (opt != "blobs" && opt != "contours" && opt != "trigger" && opt != "localize") {
         g_pipeErr = std::string("abh_pipe_set_option: unknown option ") + (name ? name : "(null)");
         return -1;
     }
@@ -2100,7 +2370,7 @@ int abh_pipe_set_option(void *p, const char *name, int value)
         return -1;
     }
     abub::RunPipeline *rp = (abub::RunPipeline *)p;
-    (opt == "blobs" ? rp->blobs : opt == "contours" ? rp->contours : rp->trigger) = value;
+    (opt == "blobs" ? rp->blobs : opt == "contours" ? rp->contours : opt == "trigger" ? rp->trigger : rp->localizeDev) = value;
     return 0;
 }
 
@@ -2121,6 +2391,28 @@ void abh_pipe_trigger_totals(double *out)
 {
     out[0] = (double)abub::g_trigTotals[0].load();
     out[1] = (double)abub::g_trigTotals[1].load();
+}
+
+// out[0..1]: stacks localised on the device and stacks on the host route with the localize knob on, summed over every
+// pipeline run of this process so far (see abh_pipe_trigger_totals)
+void abh_pipe_localize_totals(double *out)
+{
+    out[0] = (double)abub::g_locTotals[0].load();
+    out[1] = (double)abub::g_locTotals[1].load();
+}
+
+// out[0..9] of the last run with the localize knob on (zeros otherwise), summed over stack groups and rounds: stacks
+// localised on the device; stacks on the host route: over a limit, with a declined slot or an undecodable frame, with every
+// genesis contour in the bellows mask, for another reason (Otsu mismatch); bubbles and descriptors of the device's tracks;
+// ms of the K7 launches; bytes of the kept-pixel, contour, vertex, record, box and track lists stage 3 copied to the host
+// (counted with the contours knob alone, too); batches redone because the record list or the box / track lists had to grow
+void abh_pipe_localize_stats(void *p, double *out)
+{
+    const abub::PipeStats &st = ((abub::RunPipeline *)p)->stats;
+    const double v[10] = {(double)st.locDevice, (double)st.locHostLimit, (double)st.locHostSlot, (double)st.locHostBellows,
+                         (double)st.locHostOther, (double)st.locBubbles, (double)st.locDescs, st.locK7Ms,
+                          (double)st.listBytes, (double)st.locRegrows};
+    std::memcpy(out, v, sizeof v);
 }
 
 // out[0..4] of the last run with the contours knob on (zeros otherwise), summed over stack groups and rounds: slots

@@ -327,6 +327,77 @@ size_t abub_trigger_search_desc_bytes(int nstacks, int nsegs);
  * frames per stack (F), segments per stack.  Needs no device. */
 int abub_trigger_search_limits(int *max_frames, int *max_segs);
 
+/* ---- K7: the localizer's arithmetic and decisions on K5's polygons (abub_localize.hip) ---------------------------------- */
+/* One record per contour of abub_trace_contours_dev, in the order of its contour list: the columns of a descriptor row
+ * (box, ContArea, ContRadius, m00, m10, m01, centroid) with the centroid in both forms the localizer uses. */
+typedef struct abub_contour_desc {
+    int32_t x, y, w, h;          /* cv::boundingRect */
+    double area, radius;         /* fabs(cv::contourArea), sqrt(area / 3.14159) */
+    double m00, m10, m01;        /* cv::moments of the polygon */
+    float cx, cy;                /* tracking form: (float)(m10 / m00), NaN when m00 == 0 */
+    float gx, gy;                /* genesis form: the vertex mean instead when m00 > 0 is false */
+    uint32_t npts, reserved;
+} abub_contour_desc;
+/* K7a: describes every contour of a traced contour list (boundingRect, contourArea, moments and the centroid of
+ * L3Localizer.cpp:401-418 and :808-823), bit for bit host/hostlogic.cpp boundingRectOf / contourAreaOf / momentsOf and
+ * host/L3Localizer.cpp describe.  Input as abub_trace_contours_dev left it: status, cont_off [nslots+1], cont_npts,
+ * pt_off [nslots+1], pts (x | y << 16); cont_cap / pts_cap: the capacities those lists were traced with.
+ * desc[k] receives contour k for every k < min(cont_off[nslots], cont_cap, desc_cap) whose vertices lie below pts_cap;
+ * nothing is written past desc_cap (the caller sees the true count in cont_off[nslots]). */
+int abub_describe_contours_dev(const uint32_t *status, const uint32_t *cont_off, const uint32_t *cont_npts, uint32_t cont_cap,
+                               const uint32_t *pt_off, const uint32_t *pts, uint32_t pts_cap, int nslots,
+                               abub_contour_desc *desc, uint32_t desc_cap, void *stream);
+
+typedef struct abub_loc_mask { /* the masks of one camera: device images of 8-bit pixels, rows of `w` bytes */
+    const uint8_t *fid;        /* cam<N>_mask.bmp, or NULL: no mask dir / not loadable */
+    const uint8_t *bel;        /* cam<N>_bellows_mask.bmp, or NULL */
+    int32_t fw, fh, bw, bh;
+} abub_loc_mask;
+#define ABUB_LOC_MAXTRACK 10 /* NumFramesBubbleTrack */
+typedef struct abub_loc_stack {
+    int32_t cam;                       /* index into masks[] */
+    int32_t genesis;                   /* slot of the genesis image */
+    int32_t ntrack;                    /* tracking slots, in frame order (the caller applied L3Localizer.cpp:947-955) */
+    int32_t bad;                       /* != 0: the stack holds an undecodable frame */
+    int32_t track[ABUB_LOC_MAXTRACK];
+    int32_t reserved[2];
+} abub_loc_stack;
+/* status of a stack after abub_localize_stacks_dev: 0 = localised, otherwise the host route takes it */
+#define ABUB_LOC_DONE 0
+#define ABUB_LOC_LIMIT 1       /* a slot over the contour limit, or more bubbles than the bubble limit */
+#define ABUB_LOC_SLOT 2        /* a slot abub_trace_contours_dev declined (status 1) */
+#define ABUB_LOC_BAD_FRAME 3   /* abub_loc_stack.bad */
+#define ABUB_LOC_BELLOWS 4     /* every genesis contour lies in the bellows mask: the veto (L3Localizer.cpp:292-390) */
+#define ABUB_LOC_INCOMPLETE 5  /* a slot's records lie beyond ndesc (the contour lists overflowed: redo the batch) */
+typedef struct abub_loc_result {
+    int32_t status;
+    uint32_t nrects, rect_off;   /* bubbleRects: rects[4 * rect_off ..] = x, y, w, h of each, in order */
+    uint32_t nbubbles;
+    uint32_t ntrack, track_off;  /* tracks[track_off ..]: per bubble its descriptor count n, then n record indices (into
+                                    desc[]) in sighting order, the genesis first; ntrack = nbubbles + all the counts */
+    uint32_t reserved[2];
+} abub_loc_result;
+/* K7b: CalculateInitialBubbleParams and CalculatePostTriggerFrameParams with isInMask (L3Localizer.cpp:215-460, 764-869,
+ * 971-1012) per stack on the records of abub_describe_contours_dev, one launch for all stacks.  stacks[nstacks] and
+ * masks[ncams] are HOST arrays, checked here (a camera or slot index out of range, ntrack beyond ABUB_LOC_MAXTRACK:
+ * ABUB_E_INVALID) and copied to `scratch` on the stream -- device memory of abub_localize_scratch_bytes(nstacks, ncams)
+ * bytes, 256-byte aligned; keep them unchanged until the stream has passed the call.  slot_status / cont_off: of
+ * abub_trace_contours_dev; desc[ndesc]: the records.  out[nstacks] (device) is written for every stack.  A stack with
+ * status 0 reserves its part of `rects` (rect_cap boxes of 4 int32) and `tracks` (track_cap dwords); totals[2] (device,
+ * zeroed here) count every reservation: a stack whose part would end beyond a capacity writes nothing there, so
+ * totals[0] > rect_cap or totals[1] > track_cap asks for larger lists and another launch.  When several reasons decline
+ * a stack the status is the first of BAD_FRAME, SLOT, INCOMPLETE, LIMIT, BELLOWS. */
+int abub_localize_stacks_dev(const abub_loc_stack *stacks, int nstacks, const abub_loc_mask *masks, int ncams,
+                             const uint32_t *slot_status, const uint32_t *cont_off, int nslots,
+                             const abub_contour_desc *desc, uint32_t ndesc, void *scratch, size_t scratch_bytes,
+                             abub_loc_result *out, int32_t *rects, uint32_t rect_cap, uint32_t *tracks, uint32_t track_cap,
+                             uint32_t *totals, void *stream);
+/* Descriptor scratch of abub_localize_stacks_dev (L3Localizer.cpp:215-460, 764-869, 971-1012); 0 for nstacks <= 0 */
+size_t abub_localize_scratch_bytes(int nstacks, int ncams);
+/* The static limits of abub_localize_stacks_dev (L3Localizer.cpp:215-460, 764-869, 971-1012 stay on the host above them):
+ * contours per slot, bubbles per stack.  Needs no device. */
+int abub_localize_limits(int *max_contours, int *max_bubbles);
+
 /* Raw terms of cv::matchTemplate(CV_TM_CCORR_NORMED) for the bellows veto (L3Localizer::TrackAFeature,
  * L3Localizer.cpp:499-500): for each of the (W-tw+1) x (H-th+1) placements the exact integer sums
  * num = sum(T*I) and wsum2 = sum(I*I) over the window.  Normalisation is host work (double). */
