@@ -98,6 +98,56 @@ struct Mirror {
     }
 };
 
+// The part of a GrowList that does not depend on its element type: its capacity in entries and how it grows.  The contents
+// are not kept and the old storage is freed first, so a list grows only once the streams that used it have been synchronised
+class Growable {
+public:
+    size_t cap() const { return cap_; } // (0 while the list is being grown, and after a failed allocation)
+    void seed(size_t n) // exactly n entries
+    {
+        cap_ = 0;
+        allocateEntries(n);
+        cap_ = n;
+    }
+    // at least n entries; when it has to grow it takes a quarter more and its slack, for the batches to come
+    void reserve(size_t n)
+    {
+        if (n > cap_)
+            seed(n + n / 4 + slack_);
+    }
+    // The redo rule of a batch whose kernels count past the capacity: true if `needed` entries fit; else the list grows and
+    // the caller redoes the batch -- once: a list that overflows again in the same batch, or past its limit, throws
+    bool fit(size_t needed, const char *message)
+    {
+        if (needed <= cap_)
+            return true;
+        if (grown_ || needed > limit_)
+            throw std::runtime_error(message);
+        reserve(needed);
+        grown_ = true;
+        return false;
+    }
+    void newBatch() { grown_ = false; }
+
+protected:
+    Growable(size_t slack, size_t limit) : slack_(slack), limit_(limit) {}
+
+private:
+    virtual void allocateEntries(size_t n) = 0;
+    size_t cap_ = 0, slack_, limit_;
+    bool grown_ = false;
+};
+
+// A Mirror that knows its capacity in entries of `per` elements each (the boxes of the localize knob: 4)
+template <class T>
+struct GrowList final : Mirror<T>, Growable {
+    explicit GrowList(size_t slack, size_t per = 1, size_t limit = SIZE_MAX) : Growable(slack, limit), per_(per) {}
+
+private:
+    void allocateEntries(size_t n) override { Mirror<T>::allocate(per_ * n); }
+    size_t per_;
+};
+
 // A non-blocking stream of the current device; its work is finished before it goes
 class Stream {
 public:
@@ -142,6 +192,13 @@ public:
         HIPOK(hipEventCreateWithFlags(&ev_, timing ? hipEventDefault : hipEventDisableTiming));
     }
     hipEvent_t get() const { return ev_; }
+    // ms between `start` and this one, both recorded with timing and both reached
+    float msSince(const Event &start) const
+    {
+        float ms = 0;
+        HIPOK(hipEventElapsedTime(&ms, start.ev_, ev_));
+        return ms;
+    }
 
 private:
     void reset()

@@ -23,6 +23,7 @@
 #include <stdexcept>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include <hip/hip_runtime_api.h>
@@ -457,17 +458,21 @@ private:
 // The candidate pixels of a batch of images (stage 3, or the veto's residuals): (raster index, value) pairs as the
 // compaction kernels write them, grouped by image on the device, and the host mirrors the localizer reads
 struct CandidateList {
-    uint32_t cap = 0;                   // pairs the lists hold (0 while they are being grown)
-    DeviceArray<uint32_t> pairs;        // [2 cap]
-    DeviceArray<uint32_t> gscratch;     // [2 nimg]
-    Mirror<uint32_t> count, goff, gidx; // pairs found (the kernels count past cap); image k's pairs are [goff[k], goff[k + 1])
+    // gidx carries the capacity in pairs, cap(): it is the list that is seeded, grows (slack 1024, at most 2^30 pairs) and
+    // is checked for overflow; the other arrays follow it at the start of the next batch (start())
+    GrowList<uint32_t> gidx{1024, 1, 1u << 30};
     Mirror<uint8_t> gval;
-    // blobs knob (stage 3): the kept pixels are a subset of the candidates, so the kept list and K4b's scratch follow cap
-    int keptImages = 0, keptW = 0, keptH = 0; // 0 images: no kept list
+    DeviceArray<uint32_t> pairs;    // [2 cap]
+    size_t followed = 0;            // the capacity pairs and gval were made for
+    DeviceArray<uint32_t> gscratch; // [2 nimg]
+    Mirror<uint32_t> count, goff;   // pairs found (the kernels count past cap); image k's pairs are [goff[k], goff[k + 1])
+    // blobs knob (stage 3): the kept pixels are a subset of the candidates, so the kept list and K4b's scratch follow cap too
+    int keptImages = 0, keptW = 0, keptH = 0; // images of W x H the kept list has room for from the next start() on (0: none)
     Mirror<uint32_t> kidx;
     DeviceArray<uint8_t> keptScratch;
-    size_t keptScratchBytes = 0;
+    size_t keptScratchBytes = 0, keptFollowed = 0;
 
+    uint32_t cap() const { return (uint32_t)gidx.cap(); }
     // room for the per-image arrays of `nimg` images
     void allocate(size_t nimg)
     {
@@ -475,54 +480,34 @@ struct CandidateList {
         gscratch.allocate(2 * nimg);
         goff.allocate(nimg + 1);
     }
-    // the old storage is freed: only once the streams that used it have been synchronised
-    void grow(uint32_t c)
+    // before the launches of a batch: the arrays that follow the capacity are made for it (the streams that used the old
+    // ones have been synchronised: gidx has grown, or the kept list is new), the count is zeroed
+    void start(hipStream_t s)
     {
-        cap = 0;
-        pairs.allocate(2 * (size_t)c);
-        gidx.allocate(c);
-        gval.allocate(c);
-        if (keptImages)
-            growKept(c);
-        cap = c;
-    }
-    // from now on the list also has room for the kept pixels of `nimg` images of W x H
-    void keep(int nimg, int W, int H)
-    {
-        keptImages = nimg;
-        keptW = W;
-        keptH = H;
-        growKept(cap);
-    }
-    void growKept(uint32_t c)
-    {
-        keptScratchBytes = abub_label_blobs_scratch_bytes(keptImages, keptW, keptH, c, 0);
-        if (keptScratchBytes == 0)
-            throw std::runtime_error("RunPipeline: frame size not supported by the blob labelling");
-        keptScratch.allocate(keptScratchBytes);
-        kidx.allocate(c);
+        if (followed != gidx.cap()) {
+            pairs.allocate(2 * gidx.cap());
+            gval.allocate(gidx.cap());
+            followed = gidx.cap();
+        }
+        if (keptImages && keptFollowed != gidx.cap()) {
+            keptScratchBytes = abub_label_blobs_scratch_bytes(keptImages, keptW, keptH, cap(), 0);
+            if (keptScratchBytes == 0)
+                throw std::runtime_error("RunPipeline: frame size not supported by the blob labelling");
+            keptScratch.allocate(keptScratchBytes);
+            kidx.allocate(gidx.cap());
+            keptFollowed = gidx.cap();
+        }
+        HIPOK(hipMemsetAsync(count.d, 0, sizeof(uint32_t), s));
     }
     // the pairs grouped by image (per-image counts from the histograms and TOZERO cuts of the same launches)
     void group(int nimg, const uint32_t *d_hist, const int32_t *d_thr, hipStream_t s, const char *what)
     {
-        check(abub_pairs_group_hist_dev(pairs, count.d, cap, nimg, gscratch, goff.d, gidx.d, gval.d, d_hist, d_thr, s), what);
+        check(abub_pairs_group_hist_dev(pairs, count.d, cap(), nimg, gscratch, goff.d, gidx.d, gval.d, d_hist, d_thr, s), what);
     }
     void offsetsToHost(int nimg, hipStream_t s)
     {
         count.toHost(1, s);
         goff.toHost((size_t)nimg + 1, s);
-    }
-    // once the offsets are on the host: true if every pair fitted; else the list grows to what the kernels counted and the
-    // caller redoes its launches (once)
-    bool fits(int attempt, const char *what)
-    {
-        const uint32_t n = *count.h;
-        if (n <= cap)
-            return true;
-        if (attempt > 0 || n > (1u << 30))
-            throw std::runtime_error(std::string("RunPipeline: ") + what);
-        grow(n + n / 4 + 1024);
-        return false;
     }
     void pairsToHost(hipStream_t s)
     {
@@ -540,87 +525,108 @@ struct CandidateList {
     }
 };
 
-// Counters of one run: every stack group keeps its own, the pipeline merges them (abh_pipe_timing, abh_pipe_bellows and
-// abh_pipe_blob_stats hand them out)
+// One overflow check of a batch: the kernels counted `needed` entries for `list`.  Rows of the same step grow together;
+// locRegrow: counts as a regrow of the localize knob's lists (PipeStats)
+struct Fit {
+    Growable *list;
+    size_t needed;
+    const char *message;
+    int step;
+    bool locRegrow;
+};
+// The checks of a batch in the order of `rows`, once its counts are on the host and its kernels are done: the lists of the
+// first step that does not fit grow (Growable::fit; attempt 0 starts the batch) and the caller redoes the batch -> the
+// first row that grew, nullptr when everything fitted
+static const Fit *fitLists(const Fit *rows, size_t n, int attempt)
+{
+    for (size_t k = 0; attempt == 0 && k < n; ++k)
+        rows[k].list->newBatch();
+    const Fit *grew = nullptr;
+    for (size_t k = 0; k < n && (!grew || rows[k].step == grew->step); ++k)
+        if (!rows[k].list->fit(rows[k].needed, rows[k].message) && !grew)
+            grew = &rows[k];
+    return grew;
+}
+
+// The counters a getter (abh_pipe_*_stats, abh_pipe_bellows, abh_pipe_timing) hands out are one struct of doubles in the
+// getter's slot order -- a count stays exact in a double far beyond any run's -- so each counter is declared, and named,
+// once: the struct is copied out as it stands, and two of them add slot by slot
+template <class T>
+void copySlots(const T &s, double *out)
+{
+    static_assert(std::is_trivially_copyable<T>::value && sizeof(T) % sizeof(double) == 0, "a struct of doubles");
+    std::memcpy(out, &s, sizeof s);
+}
+template <class T>
+void addSlots(T &a, const T &b)
+{
+    double x[sizeof(T) / sizeof(double)], y[sizeof(T) / sizeof(double)];
+    copySlots(a, x);
+    copySlots(b, y);
+    for (size_t k = 0; k < sizeof(T) / sizeof(double); ++k)
+        x[k] += y[k];
+    std::memcpy(&a, x, sizeof a);
+}
+
+// Counters of one run: every stack group keeps its own, the pipeline merges them.  The groups run side by side, so the
+// times and rounds of the stage timers take the maximum; counts, and the kernel ms of the knobs, add up over groups and rounds
 struct PipeStats {
-    // host wall time (ms): waiting for stage 1, stages 2 .. 4 summed over the rounds; of stage 3: launches + kernels +
-    // histogram / count D2H, list D2H + thresholds
-    double stage1Ms = 0, stage2Ms = 0, stage3Ms = 0, stage4Ms = 0, s3GpuMs = 0, s3ListMs = 0;
-    int rounds = 0;
-    uint32_t pairs = 0;          // candidate pairs of the last stage-3 batch
-    // kept by the pipeline across its groups (the counters under launchMu, or after the groups have ended), so not merged:
-    double totalMs = 0;          // wall time of the whole run
-    long long jobsLaunched = 0;  // trigger-search jobs (F - 1 per stack when nothing is lazy)
-    long long jobsCompleted = 0; // ... of which the dense rows were evaluated on demand (deferred pieces)
-    int dropIns = 0;             // stacks that went through the one-at-a-time path (bellows veto)
-    // bellows veto inside the batch: stacks, template-match jobs and launches, residual images, wall time of the veto rounds
-    int vetoed = 0, matchJobs = 0, matchLaunches = 0, residualImages = 0;
-    double vetoMs = 0;
-    // blobs knob, summed over the rounds: candidate pairs, foreground pixels after the Otsu cut, kept pixels (shipped to the
-    // host), components, kept components, slots labelled on the global-memory path, ms of the Otsu and of the K4b launches
-    long long blobCandidates = 0, blobForeground = 0, blobKept = 0, blobComponents = 0, blobKeptComponents = 0, blobLargeSlots = 0;
-    double blobOtsuMs = 0, blobK4bMs = 0;
-    // contours knob, summed over the rounds: slots traced on the device, slots left to the host route, contours, vertices,
-    // ms of the K5 launches
-    long long contTraced = 0, contHost = 0, contContours = 0, contVertices = 0;
-    double contK5Ms = 0;
-    // trigger knob: stacks searched on the device, stacks on the host route, NEED_FRAMES and NEED_FINAL answers, ms of the
-    // K6 launches (per group, merged); search launches (kept by the pipeline, like jobsLaunched)
-    long long trigDevStacks = 0, trigHostStacks = 0, trigNeedFrames = 0, trigNeedFinal = 0, trigLaunches = 0;
-    double trigK6Ms = 0;
-    // localize knob, summed over the rounds: stacks localised on the device, stacks on the host route by reason (over a
-    // limit; a declined slot or an undecodable frame; every genesis contour in the bellows mask; an Otsu mismatch),
-    // bubbles and descriptors of the device's tracks, ms of the K7 launches
-    long long locDevice = 0, locHostLimit = 0, locHostSlot = 0, locHostBellows = 0, locHostOther = 0, locBubbles = 0, locDescs = 0;
-    double locK7Ms = 0;
-    long long locRegrows = 0; // batches redone because the record list, or the box / track lists, were too small
-    long long listBytes = 0; // contours / localize knobs: bytes of the kept-pixel, contour, vertex, record, box and track lists copied to the host
+    // abh_pipe_timing: host wall time (ms) waiting for stage 1, of stages 2 .. 4 summed over the rounds, of the whole run;
+    // of stage 3: launches + kernels + histogram / count D2H, list D2H + thresholds, an unused slot (the key s3_bucket_ms
+    // stays in the reports); candidate pairs of the last stage-3 batch; trigger-search jobs (F - 1 per stack when nothing is
+    // lazy); stacks on the one-at-a-time path (bellows veto); jobs whose dense rows were evaluated on demand
+    struct Timing {
+        double stage1Ms = 0, stage2Ms = 0, stage3Ms = 0, stage4Ms = 0, totalMs = 0, s3GpuMs = 0, s3ListMs = 0, s3BucketMs = 0;
+        double pairs = 0, jobsLaunched = 0, dropIns = 0, jobsCompleted = 0;
+        // (totalMs and the last three are kept by the pipeline across its groups, under launchMu or after the groups ended)
+        void add(const Timing &g)
+        {
+            for (double Timing::*t : {&Timing::stage1Ms, &Timing::stage2Ms, &Timing::stage3Ms, &Timing::stage4Ms,
+                                      &Timing::s3GpuMs, &Timing::s3ListMs})
+                this->*t = std::max(this->*t, g.*t);
+            pairs += g.pairs;
+        }
+    } timing;
+    int rounds = 0; // what abh_pipe_timing returns
+    // abh_pipe_bellows, the veto inside the batch: stacks, template-match jobs and launches, residual images, ms of its rounds
+    struct Bellows {
+        double vetoed = 0, matchJobs = 0, matchLaunches = 0, residualImages = 0, vetoMs = 0;
+    } bellows;
+    // abh_pipe_blob_stats: candidate pairs, foreground pixels after the Otsu cut, kept pixels (shipped to the host),
+    // components, kept components, slots labelled on the global-memory path, ms of the Otsu and of the K4b launches
+    struct Blobs {
+        double candidates = 0, foreground = 0, kept = 0, components = 0, keptComponents = 0, largeSlots = 0, otsuMs = 0, k4bMs = 0;
+    } blobs;
+    // abh_pipe_contour_stats: slots traced on the device, slots left to the host route, contours, vertices, ms of K5
+    struct Contours {
+        double traced = 0, host = 0, contours = 0, vertices = 0, k5Ms = 0;
+    } contours;
+    // abh_pipe_trigger_stats: stacks searched on the device, stacks on the host route, search launches (kept by the
+    // pipeline, like jobsLaunched: a group's are 0), NEED_FRAMES and NEED_FINAL answers, ms of the K6 launches
+    struct Trigger {
+        double devStacks = 0, hostStacks = 0, launches = 0, needFrames = 0, needFinal = 0, k6Ms = 0;
+    } trigger;
+    // abh_pipe_localize_stats, summed over the rounds: stacks localised on the device, stacks on the host route by reason
+    // (over a limit; a declined slot or an undecodable frame; every genesis contour in the bellows mask; an Otsu mismatch),
+    // bubbles and descriptors of the device's tracks, ms of the K7 launches; bytes of the kept-pixel, contour, vertex, record,
+    // box and track lists copied to the host (with the contours knob alone, too); batches redone to grow the knob's lists
+    struct Localize {
+        double device = 0, hostLimit = 0, hostSlot = 0, hostBellows = 0, hostOther = 0, bubbles = 0, descs = 0, k7Ms = 0;
+        double listBytes = 0, regrows = 0;
+        double hostRoute() const { return hostLimit + hostSlot + hostBellows + hostOther; }
+    } loc;
 
     void reset() { *this = PipeStats(); }
-    // a group's counters into the run's: the groups run side by side, so times and rounds take the maximum, counts add
+    // a group's counters into the run's
     void merge(const PipeStats &g)
     {
-        stage1Ms = std::max(stage1Ms, g.stage1Ms);
-        stage2Ms = std::max(stage2Ms, g.stage2Ms);
-        stage3Ms = std::max(stage3Ms, g.stage3Ms);
-        stage4Ms = std::max(stage4Ms, g.stage4Ms);
-        s3GpuMs = std::max(s3GpuMs, g.s3GpuMs);
-        s3ListMs = std::max(s3ListMs, g.s3ListMs);
+        timing.add(g.timing);
         rounds = std::max(rounds, g.rounds);
-        pairs += g.pairs;
-        vetoed += g.vetoed;
-        matchJobs += g.matchJobs;
-        matchLaunches += g.matchLaunches;
-        residualImages += g.residualImages;
-        vetoMs += g.vetoMs;
-        blobCandidates += g.blobCandidates;
-        blobForeground += g.blobForeground;
-        blobKept += g.blobKept;
-        blobComponents += g.blobComponents;
-        blobKeptComponents += g.blobKeptComponents;
-        blobLargeSlots += g.blobLargeSlots;
-        blobOtsuMs += g.blobOtsuMs;
-        blobK4bMs += g.blobK4bMs;
-        contTraced += g.contTraced;
-        contHost += g.contHost;
-        contContours += g.contContours;
-        contVertices += g.contVertices;
-        contK5Ms += g.contK5Ms;
-        trigDevStacks += g.trigDevStacks;
-        trigHostStacks += g.trigHostStacks;
-        trigNeedFrames += g.trigNeedFrames;
-        trigNeedFinal += g.trigNeedFinal;
-        trigK6Ms += g.trigK6Ms;
-        locDevice += g.locDevice;
-        locHostLimit += g.locHostLimit;
-        locHostSlot += g.locHostSlot;
-        locHostBellows += g.locHostBellows;
-        locHostOther += g.locHostOther;
-        locBubbles += g.locBubbles;
-        locDescs += g.locDescs;
-        locK7Ms += g.locK7Ms;
-        locRegrows += g.locRegrows;
-        listBytes += g.listBytes;
+        addSlots(bellows, g.bellows);
+        addSlots(blobs, g.blobs);
+        addSlots(contours, g.contours);
+        addSlots(trigger, g.trigger);
+        addSlots(loc, g.loc);
     }
 };
 
@@ -628,6 +634,7 @@ struct PipeStats {
 // GPU work of one group overlaps the host state machines of another (no group waits on another).
 struct Group {
     int s0 = 0, s1 = 0; // stacks [s0, s1)
+    size_t ns = 0, n3 = 0; // their number, and the image slots of a stage-3 batch: NumFramesBubbleTrack + 1 per stack
     Event stage1Done, kernelsDone, blockDone;
     // trigger search, per frame block k = frames [blocks[k], blocks[k + 1]): job lists and histograms (capacity: every
     // stack of the group once), and the deferred pieces: handed-over row ranges of every launch of the block, per-launch
@@ -654,29 +661,173 @@ struct Group {
     DeviceArray<uint8_t> img;
     Mirror<int32_t> thr;
     CandidateList list;
-    // blobs knob: device Otsu + K4b behind the grouping (allocated on first use; the kept list is in `list`)
+    // The opt-in knobs of stage 3: each stage allocates nothing before its first use (which makes its last event last: that
+    // event says the stage is there), and has one function per phase of batchImages, which calls them in this order:
+    // launch, countsToHost, addTimings, (the overflow checks,) listsToHost, bind
+    // blobs knob: the device also computes the Otsu thresholds and labels each image's foreground (K4b, abub_blobs.hip)
+    // behind the grouping, and only the pixels of the components the localizer can use come back (the kept list is in `list`)
     struct Blobs {
-        bool ready = false;
+        bool shipKept = true; // of the batch: its kept pixels travel (listsToHost)
         Mirror<int32_t> otsu, minbox;
         Mirror<uint32_t> koff, kstats; // kstats: K4b's counters
         DeviceArray<uint32_t> ncomp, nkc, coff;
         Event ev[3]; // before Otsu, between, after K4b
+        void firstUse(size_t n3, CandidateList &L, int W, int H)
+        {
+            if (ev[2].get())
+                return;
+            otsu.allocate(n3);
+            minbox.allocate(n3);
+            koff.allocate(n3 + 1);
+            ncomp.allocate(n3);
+            nkc.allocate(n3);
+            coff.allocate(n3 + 1);
+            kstats.allocate(4);
+            L.keptImages = (int)n3;
+            L.keptW = W;
+            L.keptH = H;
+            for (Event &e : ev)
+                e.create(true);
+        }
+        void launch(const CandidateList &L, const std::vector<PlannedImage *> &bySlot, const uint32_t *d_hist, const int32_t *d_thr,
+                    int W, int H, hipStream_t stream)
+        {
+            const int nimg = (int)bySlot.size();
+            for (int k = 0; k < nimg; ++k)
+                minbox.h[k] = bySlot[k]->minBox;
+            minbox.toDevice(nimg, stream);
+            HIPOK(hipEventRecord(ev[0].get(), stream));
+            check(abub_binarize_thr_dev(d_hist, d_thr, nimg, W, H, otsu.d, stream), "stage3 Otsu");
+            HIPOK(hipEventRecord(ev[1].get(), stream));
+            check(abub_label_blobs_dev(L.goff.d, L.gidx.d, L.gval.d, L.cap(), nimg, W, H, otsu.d, minbox.d, koff.d, L.kidx.d,
+                                       L.cap(), ncomp, nkc, coff, nullptr, 0, kstats.d, L.keptScratch, L.keptScratchBytes, stream),
+                  "stage3 K4b");
+            HIPOK(hipEventRecord(ev[2].get(), stream));
+        }
+        void countsToHost(int nimg, hipStream_t back)
+        {
+            otsu.toHost(nimg, back);
+            koff.toHost((size_t)nimg + 1, back);
+            kstats.toHost(4, back);
+        }
+        void addTimings(PipeStats &stats)
+        {
+            stats.blobs.otsuMs += ev[1].msSince(ev[0]);
+            stats.blobs.k4bMs += ev[2].msSince(ev[1]);
+        }
+        // `traced`: K5's counters (nullptr: contours knob off): then the kept pixels travel only when a slot was declined
+        void listsToHost(hipStream_t back, const CandidateList &L, int nimg, const uint32_t *traced, PipeStats &stats)
+        {
+            const uint32_t nkept = koff.h[nimg];
+            if (nkept > L.cap())
+                throw std::runtime_error("RunPipeline: kept list larger than the candidate list");
+            shipKept = !traced || traced[1] != 0;
+            if (nkept && shipKept) {
+                L.kidx.toHost(nkept, back);
+                stats.loc.listBytes += traced ? 4.0 * nkept : 0;
+            }
+            stats.blobs.candidates += *L.count.h;
+            stats.blobs.foreground += kstats.h[1];
+            stats.blobs.kept += nkept;
+            stats.blobs.components += kstats.h[2];
+            stats.blobs.keptComponents += kstats.h[3];
+            stats.blobs.largeSlots += kstats.h[0];
+        }
+        // image k's kept pixels, after the host's threshold p.thr (pointers into the host mirrors, like CandidateList::bind)
+        void bind(PlannedImage &p, int k, const CandidateList &L) const
+        {
+            p.kept = L.kidx.h + koff.h[k];
+            p.nkept = koff.h[k + 1] - koff.h[k];
+            p.otsuMismatch = otsu.h[k] != p.thr;
+            p.keptShipped = shipKept;
+        }
     } blobs;
-    // contours knob: K5 behind K4b (allocated on first use).  The scratch follows the candidate list's capacity, the
-    // contour and vertex lists have capacities of their own and grow when a batch overflows them
+    // contours knob: K5 (abub_contours.hip) then traces each image's contours from K4b's kept list and the vertices come
+    // back.  The scratch follows the candidate list's capacity, the contour and vertex lists have capacities of their own
     struct Contours {
-        bool ready = false;
-        uint32_t inCap = 0, contCap = 0, ptsCap = 0;
-        Mirror<uint32_t> status, ncont, coff, cnpts, poff, pts, cstats;
+        bool shipVerts = true; // of the batch: its vertices travel (listsToHost)
+        size_t inCap = 0;      // the candidate capacity the scratch was made for
+        Mirror<uint32_t> status, ncont, coff, poff, cstats;
+        GrowList<uint32_t> cnpts{64}, pts{64}; // vertices per contour; vertices
         DeviceArray<uint8_t> scratch;
         size_t scratchBytes = 0;
         Event ev[2]; // before and after K5
+        // the per-image arrays once, the scratch for the candidate list's capacity, which may just have grown (`back` has waited
+        // for the kernels that used the old one), the two lists at a quarter of it to start with (few pixels are vertices)
+        void fit(size_t n3, const CandidateList &L, int W, int H)
+        {
+            if (!ev[1].get()) {
+                status.allocate(n3);
+                ncont.allocate(n3);
+                coff.allocate(n3 + 1);
+                poff.allocate(n3 + 1);
+                cstats.allocate(4);
+                for (Event &e : ev)
+                    e.create(true);
+            }
+            if (inCap != L.cap()) {
+                scratchBytes = abub_trace_contours_scratch_bytes((int)n3, L.cap());
+                if (scratchBytes == 0 || W > 65535 || H > 65535)
+                    throw std::runtime_error("RunPipeline: frame size not supported by the contour tracing");
+                scratch.allocate(scratchBytes);
+                inCap = L.cap();
+            }
+            if (cnpts.cap() == 0) {
+                cnpts.reserve(L.cap() / 4 + 64);
+                pts.reserve(L.cap() / 4 + 64);
+            }
+        }
+        void launch(size_t n3, const CandidateList &L, const uint32_t *d_koff, int nimg, int W, int H, hipStream_t stream)
+        {
+            fit(n3, L, W, H);
+            HIPOK(hipEventRecord(ev[0].get(), stream));
+            check(abub_trace_contours_dev(d_koff, L.kidx.d, L.cap(), nimg, W, H, status.d, ncont.d, coff.d, cnpts.d,
+                                          (uint32_t)cnpts.cap(), poff.d, pts.d, (uint32_t)pts.cap(), cstats.d, scratch,
+                                          scratchBytes, stream),
+                  "stage3 K5");
+            HIPOK(hipEventRecord(ev[1].get(), stream));
+        }
+        void countsToHost(int nimg, hipStream_t back)
+        {
+            status.toHost(nimg, back);
+            coff.toHost((size_t)nimg + 1, back);
+            poff.toHost((size_t)nimg + 1, back);
+            cstats.toHost(4, back);
+        }
+        void addTimings(PipeStats &stats) { stats.contours.k5Ms += ev[1].msSince(ev[0]); }
+        // `ship`: with the localize knob the vertices travel only when some stack was declined and takes the host route
+        void listsToHost(hipStream_t back, int nimg, bool ship, PipeStats &stats)
+        {
+            shipVerts = ship;
+            if (shipVerts) {
+                if (const uint32_t nc = coff.h[nimg])
+                    cnpts.toHost(nc, back);
+                if (const uint32_t nv = poff.h[nimg])
+                    pts.toHost(nv, back);
+                stats.loc.listBytes += 4.0 * coff.h[nimg] + 4.0 * poff.h[nimg];
+            }
+            stats.contours.traced += cstats.h[0];
+            stats.contours.host += cstats.h[1];
+            stats.contours.contours += cstats.h[2];
+            stats.contours.vertices += cstats.h[3];
+        }
+        // image k's contours, unless the kernel declined the slot
+        void bind(PlannedImage &p, int k) const
+        {
+            p.traced = status.h[k] == 0;
+            p.vertsShipped = shipVerts;
+            if (p.traced) {
+                p.cnp = cnpts.h + coff.h[k];
+                p.cpts = pts.h + poff.h[k];
+                p.ncont = coff.h[k + 1] - coff.h[k];
+            }
+        }
     } contours;
-    // trigger knob: K6 (abub_trigger.hip) on the blocks' device histograms (allocated on first use): descriptors of one
-    // launch (pinned, copied by the launcher), its results, the stacks it serves in launch order.  One launch at a time:
-    // every launch is waited for (stage1Done / blockDone) and collected before the next one is filled in.
+    // trigger knob: K6 (abub_trigger.hip) on the blocks' device histograms: descriptors of one launch (pinned, copied by
+    // the launcher), its results, the stacks it serves in launch order.  One launch at a time: every launch is waited for
+    // (stage1Done / blockDone) and collected before the next one is filled in.
     struct Trigger {
-        bool ready = false, inflight = false;
+        bool inflight = false;
         PinnedArray<abub_trig_stack> st;
         PinnedArray<abub_trig_seg> sg;
         DeviceArray<uint8_t> desc;
@@ -684,21 +835,131 @@ struct Group {
         Mirror<abub_trig_result> res;
         std::vector<int> list;
         Event ev[2]; // before and after the launch
+        void firstUse(size_t ns)
+        {
+            if (ev[1].get())
+                return;
+            const size_t nsg = ns * BatchEventData::MAXB;
+            st.allocate(ns);
+            sg.allocate(nsg);
+            descBytes = abub_trigger_search_desc_bytes((int)ns, (int)nsg);
+            desc.allocate(descBytes);
+            res.allocate(ns);
+            ev[0].create(true);
+            ev[1].create(true);
+        }
     } trig;
-    // localize knob: K7 behind K5 (allocated on first use): the records of the round's contours, the stack descriptors of
-    // one launch (pinned, copied by the launcher), the per-stack results and the box / track lists, which grow when a
-    // batch overflows them
+    // localize knob: K7 (abub_localize.hip) then describes every contour (the records) and runs the localizer's decisions per
+    // stack (descriptors: pinned, copied by the launcher); the per-stack results, boxes and tracks come back
     struct Localize {
-        bool ready = false;
-        uint32_t descCap = 0, rectCap = 0, trackCap = 0;
-        Mirror<abub_contour_desc> desc;
+        GrowList<abub_contour_desc> desc{64};
+        GrowList<int32_t> rects{64, 4}; // x, y, w, h
+        GrowList<uint32_t> tracks{64};
         PinnedArray<abub_loc_stack> st;
         DeviceArray<uint8_t> scratch;
         size_t scratchBytes = 0;
         Mirror<abub_loc_result> res;
-        Mirror<int32_t> rects;
-        Mirror<uint32_t> tracks, totals;
+        Mirror<uint32_t> totals; // boxes and track entries of the batch
         Event ev[2]; // before K7a and after K7b
+        // the per-stack arrays; the three lists at a modest size to start with, or exactly `locCap` entries each (to overflow)
+        void firstUse(size_t ns, int C, int locCap)
+        {
+            if (ev[1].get())
+                return;
+            st.allocate(ns);
+            scratchBytes = abub_localize_scratch_bytes((int)ns, C);
+            scratch.allocate(scratchBytes);
+            res.allocate(ns);
+            totals.allocate(2);
+            locCap > 0 ? desc.seed((size_t)locCap) : desc.reserve(64 * ns);
+            locCap > 0 ? rects.seed((size_t)locCap) : rects.reserve(8 * ns);
+            locCap > 0 ? tracks.seed((size_t)locCap) : tracks.reserve(16 * ns);
+            for (Event &e : ev)
+                e.create(true);
+        }
+        // the descriptors of the stacks of `loc` from their planned images, then K7a over the contours K5 traced and K7b
+        void launch(size_t ns, int C, int locCap, const abub_loc_mask *masks, const Contours &K,
+                    const std::vector<StackState> &stacks, const std::vector<int> &loc, int nimg, hipStream_t stream)
+        {
+            firstUse(ns, C, locCap);
+            const int nloc = (int)loc.size();
+            for (int k = 0; k < nloc; ++k) {
+                const StackState &ss = stacks[loc[k]];
+                abub_loc_stack &d = st[k];
+                d = abub_loc_stack{};
+                d.cam = loc[k] % C;
+                d.bad = !ss.data.frameOk(0);
+                int nt = 0;
+                for (const PlannedImage &p : ss.data.planned) {
+                    if (!ss.data.frameOk(p.i) || (p.kind == 0 && !ss.data.frameOk(p.ref)))
+                        d.bad = 1;
+                    if (p.kind == 0)
+                        d.genesis = p.slot;
+                    else if (nt < ABUB_LOC_MAXTRACK)
+                        d.track[nt++] = p.slot; // (planned in frame order)
+                    else
+                        throw std::runtime_error("RunPipeline: more tracking frames planned than ABUB_LOC_MAXTRACK");
+                }
+                d.ntrack = nt;
+            }
+            HIPOK(hipEventRecord(ev[0].get(), stream));
+            check(abub_describe_contours_dev(K.status.d, K.coff.d, K.cnpts.d, (uint32_t)K.cnpts.cap(), K.poff.d, K.pts.d,
+                                             (uint32_t)K.pts.cap(), nimg, desc.d, (uint32_t)desc.cap(), stream),
+                  "stage3 K7a");
+            check(abub_localize_stacks_dev(st, nloc, masks, C, K.status.d, K.coff.d, nimg, desc.d,
+                                           (uint32_t)std::min(desc.cap(), K.cnpts.cap()), scratch, scratchBytes, res.d, rects.d,
+                                           (uint32_t)rects.cap(), tracks.d, (uint32_t)tracks.cap(), totals.d, stream),
+                  "stage3 K7b");
+            HIPOK(hipEventRecord(ev[1].get(), stream));
+        }
+        void countsToHost(int nloc, hipStream_t back)
+        {
+            res.toHost((size_t)nloc, back);
+            totals.toHost(2, back);
+        }
+        void addTimings(PipeStats &stats) { stats.loc.k7Ms += ev[1].msSince(ev[0]); }
+        // some stack of the batch was declined and takes the host route
+        bool declined(int nloc) const
+        {
+            return std::any_of(res.h + 0, res.h + nloc, [](const abub_loc_result &r) { return r.status != ABUB_LOC_DONE; });
+        }
+        // the records of the batch's `nc` contours, its boxes and its tracks
+        void listsToHost(hipStream_t back, uint32_t nc, int nloc, PipeStats &stats)
+        {
+            if (nc)
+                desc.toHost(nc, back);
+            if (totals.h[0])
+                rects.toHost(4 * (size_t)totals.h[0], back);
+            if (totals.h[1])
+                tracks.toHost(totals.h[1], back);
+            stats.loc.listBytes += (double)sizeof(abub_contour_desc) * nc + 16.0 * totals.h[0] + 4.0 * totals.h[1] +
+                                   (double)sizeof(abub_loc_result) * nloc;
+        }
+        // stack k: one the kernels finished, and whose thresholds the host confirms, skips stage 4's arithmetic; the others
+        // are counted by the reason they take the host route for
+        void bind(BatchEventData &d, int k, PipeStats &stats) const
+        {
+            const abub_loc_result &r = res.h[k];
+            d.locReady = r.status == ABUB_LOC_DONE &&
+                         std::none_of(d.planned.begin(), d.planned.end(), [](const PlannedImage &p) { return p.otsuMismatch; });
+            if (d.locReady) {
+                d.locTrig = d.planned[0].i;
+                d.locRes = r;
+                d.locRects = rects.h;
+                d.locTracks = tracks.h;
+                d.locDesc = desc.h;
+                ++stats.loc.device;
+                stats.loc.bubbles += r.nbubbles;
+                stats.loc.descs += r.ntrack - r.nbubbles;
+            } else if (r.status == ABUB_LOC_LIMIT)
+                ++stats.loc.hostLimit;
+            else if (r.status == ABUB_LOC_SLOT || r.status == ABUB_LOC_BAD_FRAME)
+                ++stats.loc.hostSlot;
+            else if (r.status == ABUB_LOC_BELLOWS)
+                ++stats.loc.hostBellows;
+            else
+                ++stats.loc.hostOther;
+        }
     } loc;
     // bellows veto round (vetoRound): its own buffers, allocated on first use, grown on demand
     struct Veto {
@@ -724,8 +985,24 @@ struct Group {
     Stream stream;
 };
 
+// an integer from the environment (atoi of the variable's text), `unset` when the variable is not there
+static int envInt(const char *name, int unset)
+{
+    const char *e = getenv(name);
+    return e ? atoi(e) : unset;
+}
+
+// An opt-in knob of a pipeline object (0 or 1): abh_pipe_set_option's name for it, the environment variable a new pipeline
+// takes it from (unset: 0), the member that holds it
+class RunPipeline;
+struct Knob {
+    const char *name, *env;
+    int RunPipeline::*value;
+};
+
 class RunPipeline {
 public:
+    static const Knob knobs[4];
     int device, W, H, F, E, C, S, nthreads, ngroups;
     size_t P;
     std::vector<int> tss;
@@ -744,10 +1021,7 @@ public:
     bool ordered = true;                // localisation kernels queue on stage1Stream too (see batchImages())
     int pairCap = 0;                    // ABUB_PIPE_PAIRCAP (0: unset)
     int locCap = 0;                     // ABUB_PIPE_LOCCAP (0: unset)
-    int blobs = 0;                      // 1: stage 3 labels blobs on the GPU and ships only the kept pixels (set_option "blobs")
-    int contours = 0;                   // 1: stage 3 also traces the contours on the GPU and ships their vertices (set_option "contours")
-    int trigger = 0;                    // 1: the trigger search runs on the GPU (K6) for every stack inside its limits (set_option "trigger")
-    int localizeDev = 0;                // 1: stage 3 also describes the contours and runs the localizer's decisions on the GPU (K7; set_option "localize")
+    int blobs = 0, contours = 0, trigger = 0, localizeDev = 0; // the knobs (see `knobs` and abh_pipe_set_option)
     std::mutex maskMu;                  // the cameras' masks on the device, uploaded once per pipeline (deviceMasks)
     bool masksReady = false;
     std::vector<DeviceArray<uint8_t>> maskBuf;
@@ -836,17 +1110,7 @@ public:
             return;
         if (T.inflight)
             throw std::runtime_error("RunPipeline: a trigger search was launched before the previous one was collected");
-        const size_t ns = (size_t)(G.s1 - G.s0), nsg = ns * BatchEventData::MAXB;
-        if (!T.ready) {
-            T.st.allocate(ns);
-            T.sg.allocate(nsg);
-            T.descBytes = abub_trigger_search_desc_bytes((int)ns, (int)nsg);
-            T.desc.allocate(T.descBytes);
-            T.res.allocate(ns);
-            T.ev[0].create(true);
-            T.ev[1].create(true);
-            T.ready = true;
-        }
+        T.firstUse(G.ns);
         const int nB = (int)blocks.size() - 1;
         uint32_t nseg = 0;
         for (size_t q = 0; q < list.size(); ++q) {
@@ -883,7 +1147,7 @@ public:
         T.res.toHost(list.size(), stream);
         T.list = list;
         T.inflight = true;
-        ++stats.trigLaunches;
+        ++stats.trigger.launches;
     }
     // after the event behind the launch has been waited for: every served stack gets its answer
     void collectSearch(Group &G)
@@ -896,9 +1160,7 @@ public:
             st_.trigRes = T.res.h[q];
             st_.trigReady = true;
         }
-        float ms = 0;
-        HIPOK(hipEventElapsedTime(&ms, T.ev[0].get(), T.ev[1].get()));
-        G.stats.trigK6Ms += ms;
+        G.stats.trigger.k6Ms += T.ev[1].msSince(T.ev[0]);
         T.inflight = false;
     }
     // K2 over block k for the listed stacks (all of them on the same block): jobs -> device, launch, histograms -> host.
@@ -946,7 +1208,7 @@ public:
         B.hist.toHost((size_t)nj * 256, stream, j0 * 256);
         B.fetches.push_back(fe);
         B.used = first + n;
-        stats.jobsLaunched += nj;
+        stats.timing.jobsLaunched += nj;
         return first;
     }
 
@@ -957,20 +1219,12 @@ public:
         if (W <= 0 || H <= 0 || F <= 0 || E <= 0 || C <= 0)
             throw std::runtime_error("RunPipeline: bad geometry");
         HIPOK(hipSetDevice(device));
-        const char *eg = getenv("ABUB_PIPE_GROUPS");
-        ngroups = eg ? atoi(eg) : 1; // >1 overlaps host stages of one group with the GPU work of the next
+        ngroups = envInt("ABUB_PIPE_GROUPS", 1); // >1 overlaps host stages of one group with the GPU work of the next
         const char *ebw = getenv("ABUB_PIPE_BELLOWS");
         bellowsDropIn = ebw && std::string(ebw) == "dropin";
-        const char *eo = getenv("ABUB_PIPE_ORDERED");
-        ordered = eo ? atoi(eo) != 0 : true;
-        const char *eb = getenv("ABUB_PIPE_BLOBS");
-        blobs = eb ? atoi(eb) != 0 : 0;
-        const char *ect = getenv("ABUB_PIPE_CONTOURS");
-        contours = ect ? atoi(ect) != 0 : 0;
-        const char *etr = getenv("ABUB_PIPE_TRIGGER");
-        trigger = etr ? atoi(etr) != 0 : 0;
-        const char *elo = getenv("ABUB_PIPE_LOCALIZE");
-        localizeDev = elo ? atoi(elo) != 0 : 0;
+        ordered = envInt("ABUB_PIPE_ORDERED", 1) != 0;
+        for (const Knob &k : knobs)
+            this->*k.value = envInt(k.env, 0) != 0;
         int trigMaxSegs = 0;
         check(abub_trigger_search_limits(&trigMaxF, &trigMaxSegs), "abub_trigger_search_limits");
         if (trigMaxSegs < BatchEventData::MAXB)
@@ -992,12 +1246,11 @@ public:
         // for every stack up front, later blocks only for the stacks whose search reaches them.  ABUB_PIPE_LAZY=0: one
         // block (every frame of every stack up front, what round 2 did).
         {
-            const char *el = getenv("ABUB_PIPE_LAZY");
-            const bool lazy = el ? atoi(el) != 0 : true;
-            const char *e0 = getenv("ABUB_PIPE_BLOCK0"), *e1 = getenv("ABUB_PIPE_BLOCK");
+            const bool lazy = envInt("ABUB_PIPE_LAZY", 1) != 0;
             // first block: up to the frame the cameras' own trigger puts the bubble at (the middle of the stack) plus the
-            // two look-ahead frames and a margin; then blocks of about a fifth of the stack
-            int first = e0 && atoi(e0) > 0 ? atoi(e0) : F / 2 + 4, step = e1 && atoi(e1) > 0 ? atoi(e1) : std::max(4, F / 5);
+            // two look-ahead frames and a margin; then blocks of about a fifth of the stack (a value > 0 overrides either)
+            const int e0 = envInt("ABUB_PIPE_BLOCK0", 0), e1 = envInt("ABUB_PIPE_BLOCK", 0);
+            int first = e0 > 0 ? e0 : F / 2 + 4, step = e1 > 0 ? e1 : std::max(4, F / 5);
             blocks.clear();
             blocks.push_back(1);
             if (lazy && F > 8)
@@ -1006,21 +1259,18 @@ public:
             blocks.push_back(std::max(F, 1)); // block k = frames [blocks[k], blocks[k + 1])
             // Deferred pieces: inside a block the bound scan still covers every frame, but the row machine runs only on the
             // dense frames a search actually reaches (ABUB_PIPE_DEFER=0: at once, for every frame of the block).
-            const char *ed = getenv("ABUB_PIPE_DEFER");
-            deferPieces = (ed ? atoi(ed) != 0 : true) && chainStride > 0 && abub_fast_path(W) != 0;
+            deferPieces = envInt("ABUB_PIPE_DEFER", 1) != 0 && chainStride > 0 && abub_fast_path(W) != 0;
         }
         const int nB = (int)blocks.size() - 1;
         // initial capacity of the candidate lists (they grow on demand): ABUB_PIPE_PAIRCAP sets the veto's too
-        const char *ec = getenv("ABUB_PIPE_PAIRCAP");
-        pairCap = ec ? atoi(ec) : 0;
+        pairCap = envInt("ABUB_PIPE_PAIRCAP", 0);
         // ... and of the record, box and track lists of the localize knob: ABUB_PIPE_LOCCAP entries each
-        const char *elc = getenv("ABUB_PIPE_LOCCAP");
-        locCap = elc ? atoi(elc) : 0;
+        locCap = envInt("ABUB_PIPE_LOCCAP", 0);
         for (int g = 0; g < ngroups; ++g) {
             Group &G = groups[g];
             G.s0 = (int)((long long)S * g / ngroups);
             G.s1 = (int)((long long)S * (g + 1) / ngroups);
-            const size_t ns = (size_t)(G.s1 - G.s0), n3 = ns * K;
+            const size_t ns = G.ns = (size_t)(G.s1 - G.s0), n3 = G.n3 = ns * K;
             G.nthreads = std::max(1, nthreads / ngroups);
             // the short localisation launches of a finished group must not queue behind the next group's
             // chip-filling trigger search
@@ -1047,7 +1297,7 @@ public:
             G.img.allocate(abub_fast_path(W) ? 256 : n3 * P); // only the unfused fallback stores images
             G.thr.allocate(n3);
             G.list.allocate(n3);
-            G.list.grow(pairCap > 0 ? (uint32_t)pairCap : (8u << 20) / ngroups);
+            G.list.gidx.seed(pairCap > 0 ? (uint32_t)pairCap : (8u << 20) / ngroups);
         }
         // frame names only: the images live in HBM
         for (int c = 0; c < C; ++c) {
@@ -1148,7 +1398,7 @@ public:
         // stacks the batched providers could not serve (bellows veto): one at a time through the drop-in path
         for (int s = 0; s < S; ++s)
             if (stacks[s].dropIn) {
-                ++stats.dropIns;
+                ++stats.timing.dropIns;
                 runDropIn(s, d_frames, d_mu);
             }
         for (Group &G : groups) {
@@ -1156,11 +1406,11 @@ public:
                 throw std::runtime_error(G.error);
             stats.merge(G.stats);
         }
-        g_trigTotals[0] += stats.trigDevStacks;
-        g_trigTotals[1] += stats.trigHostStacks;
-        g_locTotals[0] += stats.locDevice;
-        g_locTotals[1] += stats.locHostLimit + stats.locHostSlot + stats.locHostBellows + stats.locHostOther;
-        stats.totalMs = nowMs() - t0;
+        g_trigTotals[0] += (long long)stats.trigger.devStacks;
+        g_trigTotals[1] += (long long)stats.trigger.hostStacks;
+        g_locTotals[0] += (long long)stats.loc.device;
+        g_locTotals[1] += (long long)stats.loc.hostRoute();
+        stats.timing.totalMs = nowMs() - t0;
     }
 
 private:
@@ -1260,14 +1510,14 @@ private:
             st_.analyzer->AttachEventData(&st_.data);
         });
         HIPOK(hipEventSynchronize(G.stage1Done.get()));
-        G.stats.stage1Ms = nowMs() - t0;
+        G.stats.timing.stage1Ms = nowMs() - t0;
 
         std::vector<int> pending(ns);
         for (int k = 0; k < ns; ++k)
             pending[k] = G.s0 + k;
         if (trigOn)
             for (int sI : pending)
-                ++(trigHostRoute(sI) ? G.stats.trigHostStacks : G.stats.trigDevStacks);
+                ++(trigHostRoute(sI) ? G.stats.trigger.hostStacks : G.stats.trigger.devStacks);
         while (!pending.empty()) {
             ++G.stats.rounds;
             // ---- stage 2: trigger search + plan ------------------------------------------------
@@ -1299,7 +1549,7 @@ private:
                 std::vector<int> need;
                 for (int sI : todo) {
                     if (trigOn && !trigHostRoute(sI) && stacks[sI].needMore)
-                        ++(stacks[sI].data.needPieces ? G.stats.trigNeedFinal : G.stats.trigNeedFrames);
+                        ++(stacks[sI].data.needPieces ? G.stats.trigger.needFinal : G.stats.trigger.needFrames);
                     if (stacks[sI].needMore)
                         need.push_back(sI);
                 }
@@ -1308,7 +1558,7 @@ private:
                 fetchBlocks(G, need, d_frames, d_sigma6);
                 todo.swap(need);
             }
-            G.stats.stage2Ms += nowMs() - t2;
+            G.stats.timing.stage2Ms += nowMs() - t2;
             // ---- stage 3: batched images, thresholds, foreground ---------------------------------
             double t3 = nowMs();
             std::vector<int> loc;
@@ -1317,12 +1567,12 @@ private:
                     loc.push_back(s);
             if (!loc.empty())
                 batchImages(G, loc, d_frames, d_mu, d_sigma6);
-            G.stats.stage3Ms += nowMs() - t3;
+            G.stats.timing.stage3Ms += nowMs() - t3;
             // ---- stage 4: localize + track -------------------------------------------------------
             double t4 = nowMs();
             pool->parallelFor((int)loc.size(), [&](int k) { localize(stacks[loc[k]]); });
             vetoRound(G, loc, d_frames, d_sigma6);
-            G.stats.stage4Ms += nowMs() - t4;
+            G.stats.timing.stage4Ms += nowMs() - t4;
             std::vector<int> next;
             for (int s : pending)
                 if (!stacks[s].done)
@@ -1382,7 +1632,7 @@ private:
                         for (size_t j = (size_t)(d.needFrame - blocks[k]); j < blen; ++j)
                             if (d.inc[k][j]) {
                                 hw[(size_t)d.slotOf[k] * blen + j] = 1;
-                                ++stats.jobsCompleted;
+                                ++stats.timing.jobsCompleted;
                             }
                     }
                     B.want.toDevice(nj, stream, base);
@@ -1579,49 +1829,36 @@ private:
                 j.out = (uint32_t)(p.kind == 0 ? p.slot : p.slot - nd);
             }
         }
-        const int nimg = nd + np;
+        const int nimg = nd + np, nloc = (int)loc.size();
         double ta = nowMs();
-        // blobs knob: the device also computes the Otsu thresholds and labels each image's foreground (K4b), and only the
-        // pixels of the components the localizer can use come back (abub_blobs.hip); the knob is read once per batch
-        // contours knob: K5 then traces each image's contours from K4b's kept list (abub_contours.hip) and the vertices
-        // come back; the kept pixels travel only when a slot was declined.  It implies device Otsu + K4b
-        // localize knob: K7 then describes every contour and runs the localizer's decisions per stack (abub_localize.hip);
-        // the finished tracks come back, the vertices only when some stack was declined.  It implies the contours knob
-        const bool useLocalize = localizeDev != 0;
-        const bool useContours = contours != 0 || useLocalize;
-        const bool useBlobs = blobs != 0 || useContours;
-        Group::Localize &Z = G.loc;
-        bool recordsGrown = false, tracksGrown = false;
-        const int nloc = (int)loc.size();
+        // the knobs, read once per batch (Group has their stages): localize implies contours, which implies blobs
+        const bool useLocalize = localizeDev != 0, useContours = contours != 0 || useLocalize, useBlobs = blobs != 0 || useContours;
         Group::Blobs &B = G.blobs;
         Group::Contours &K = G.contours;
+        Group::Localize &Z = G.loc;
         CandidateList &L = G.list;
-        if (useBlobs)
-            initBlobs(G);
-        bool contoursGrown = false;
         std::vector<PlannedImage *> bySlot((size_t)nimg);
         for (int s : loc) {
             stacks[s].data.roundHists = G.hist3.h;
             for (PlannedImage &p : stacks[s].data.planned) {
                 bySlot[p.slot] = &p;
                 G.thr.h[p.slot] = p.tozero; // candidate cut = TOZERO threshold, known before the launch
-                if (useBlobs)
-                    B.minbox.h[p.slot] = p.minBox;
             }
         }
+        if (useBlobs)
+            B.firstUse(G.n3, L, W, H); // (before the candidate list starts its batch: it makes room for the kept pixels)
         for (int attempt = 0;; ++attempt) {
             G.jobs3.toDevice(nimg, stream);
             G.thr.toDevice(nimg, stream);
-            HIPOK(hipMemsetAsync(L.count.d, 0, sizeof(uint32_t), stream));
-            const bool fused = abub_fast_path(W) != 0;
-            if (fused) {
+            L.start(stream);
+            if (abub_fast_path(W)) {
                 // images are never materialised: histogram + candidate list come out of the same pass
                 check(abub_diff_hist_compact_dev(d_frames, d_sigma6, G.jobs3.d, nd, W, H, G.hist3.d, nullptr, G.thr.d, L.pairs,
-                                                 L.cap, L.count.d, 0, stream),
+                                                 L.cap(), L.count.d, 0, stream),
                       "stage3 K2 compact");
                 if (np > 0)
                     check(abub_posttrig_compact_dev(d_frames, d_mu, d_sigma6, G.jobs3.d + nd, np, W, H,
-                                                    G.hist3.d + (size_t)nd * 256, nullptr, G.thr.d + nd, L.pairs, L.cap,
+                                                    G.hist3.d + (size_t)nd * 256, nullptr, G.thr.d + nd, L.pairs, L.cap(),
                                                     L.count.d, (uint32_t)nd, stream),
                           "stage3 K3 compact");
             } else {
@@ -1631,239 +1868,82 @@ private:
                     check(abub_posttrig_dev(d_frames, d_mu, d_sigma6, G.jobs3.d + nd, np, W, H, G.hist3.d + (size_t)nd * 256,
                                             G.img + (size_t)nd * P, stream),
                           "stage3 K3");
-                check(abub_fg_compact_pairs_dev(G.img, nimg, W, H, G.thr.d, L.pairs, L.cap, L.count.d, stream), "stage3 K4");
+                check(abub_fg_compact_pairs_dev(G.img, nimg, W, H, G.thr.d, L.pairs, L.cap(), L.count.d, stream), "stage3 K4");
             }
             // group the list by image on the device; the host gets contiguous runs and never re-buckets
             // (per-slot counts come from the histograms the same launches produced: no counting pass)
             L.group(nimg, G.hist3.d, G.thr.d, stream, "stage3 group");
-            if (useBlobs) {
-                B.minbox.toDevice(nimg, stream);
-                HIPOK(hipEventRecord(B.ev[0].get(), stream));
-                check(abub_binarize_thr_dev(G.hist3.d, G.thr.d, nimg, W, H, B.otsu.d, stream), "stage3 Otsu");
-                HIPOK(hipEventRecord(B.ev[1].get(), stream));
-                check(abub_label_blobs_dev(L.goff.d, L.gidx.d, L.gval.d, L.cap, nimg, W, H, B.otsu.d, B.minbox.d, B.koff.d,
-                                           L.kidx.d, L.cap, B.ncomp, B.nkc, B.coff, nullptr, 0, B.kstats.d, L.keptScratch,
-                                           L.keptScratchBytes, stream),
-                      "stage3 K4b");
-                HIPOK(hipEventRecord(B.ev[2].get(), stream));
-            }
-            if (useContours) {
-                fitContours(G, nimg); // (the list may have grown: `back` has waited for the kernels that used the old buffers)
-                HIPOK(hipEventRecord(K.ev[0].get(), stream));
-                check(abub_trace_contours_dev(B.koff.d, L.kidx.d, L.cap, nimg, W, H, K.status.d, K.ncont.d, K.coff.d, K.cnpts.d,
-                                              K.contCap, K.poff.d, K.pts.d, K.ptsCap, K.cstats.d, K.scratch, K.scratchBytes,
-                                              stream),
-                      "stage3 K5");
-                HIPOK(hipEventRecord(K.ev[1].get(), stream));
-            }
-            if (useLocalize) {
-                fitLocalize(G);
-                for (int k = 0; k < nloc; ++k) {
-                    const StackState &ss = stacks[loc[k]];
-                    abub_loc_stack &d = Z.st[k];
-                    d = abub_loc_stack{};
-                    d.cam = loc[k] % C;
-                    d.bad = !ss.data.frameOk(0);
-                    int nt = 0;
-                    for (const PlannedImage &p : ss.data.planned) {
-                        if (!ss.data.frameOk(p.i) || (p.kind == 0 && !ss.data.frameOk(p.ref)))
-                            d.bad = 1;
-                        if (p.kind == 0)
-                            d.genesis = p.slot;
-                        else if (nt < ABUB_LOC_MAXTRACK)
-                            d.track[nt++] = p.slot; // (planned in frame order)
-                        else
-                            throw std::runtime_error("RunPipeline: more tracking frames planned than ABUB_LOC_MAXTRACK");
-                    }
-                    d.ntrack = nt;
-                }
-                HIPOK(hipEventRecord(Z.ev[0].get(), stream));
-                check(abub_describe_contours_dev(K.status.d, K.coff.d, K.cnpts.d, K.contCap, K.poff.d, K.pts.d, K.ptsCap, nimg,
-                                                 Z.desc.d, Z.descCap, stream),
-                      "stage3 K7a");
-                check(abub_localize_stacks_dev(Z.st, nloc, locMasks.data(), C, K.status.d, K.coff.d, nimg, Z.desc.d,
-                                               std::min(Z.descCap, K.contCap), Z.scratch, Z.scratchBytes, Z.res.d, Z.rects.d,
-                                               Z.rectCap, Z.tracks.d, Z.trackCap, Z.totals.d, stream),
-                      "stage3 K7b");
-                HIPOK(hipEventRecord(Z.ev[1].get(), stream));
-            }
+            if (useBlobs)
+                B.launch(L, bySlot, G.hist3.d, G.thr.d, W, H, stream);
+            if (useContours)
+                K.launch(G.n3, L, B.koff.d, nimg, W, H, stream);
+            if (useLocalize)
+                Z.launch(G.ns, C, locCap, deviceMasks(), K, stacks, loc, nimg, stream);
             HIPOK(hipEventRecord(G.kernelsDone.get(), stream));
             HIPOK(hipStreamWaitEvent(back, G.kernelsDone.get(), 0));
             G.hist3.toHost((size_t)nimg * 256, back);
             L.offsetsToHost(nimg, back);
-            if (useBlobs) {
-                B.otsu.toHost(nimg, back);
-                B.koff.toHost((size_t)nimg + 1, back);
-                B.kstats.toHost(4, back);
-            }
-            if (useContours) {
-                K.status.toHost(nimg, back);
-                K.coff.toHost((size_t)nimg + 1, back);
-                K.poff.toHost((size_t)nimg + 1, back);
-                K.cstats.toHost(4, back);
-            }
-            if (useLocalize) {
-                Z.res.toHost((size_t)nloc, back);
-                Z.totals.toHost(2, back);
-            }
+            if (useBlobs)
+                B.countsToHost(nimg, back);
+            if (useContours)
+                K.countsToHost(nimg, back);
+            if (useLocalize)
+                Z.countsToHost(nloc, back);
             HIPOK(hipStreamSynchronize(back));
-            if (useLocalize) {
-                float m = 0;
-                HIPOK(hipEventElapsedTime(&m, Z.ev[0].get(), Z.ev[1].get()));
-                G.stats.locK7Ms += m;
-            }
-            if (useContours) {
-                float m = 0;
-                HIPOK(hipEventElapsedTime(&m, K.ev[0].get(), K.ev[1].get()));
-                G.stats.contK5Ms += m;
-            }
-            if (useBlobs) {
-                float m0 = 0, m1 = 0;
-                HIPOK(hipEventElapsedTime(&m0, B.ev[0].get(), B.ev[1].get()));
-                HIPOK(hipEventElapsedTime(&m1, B.ev[1].get(), B.ev[2].get()));
-                G.stats.blobOtsuMs += m0;
-                G.stats.blobK4bMs += m1;
-            }
-            G.stats.s3GpuMs += nowMs() - ta; // launches + kernels + hist/count D2H
+            if (useBlobs)
+                B.addTimings(G.stats);
+            if (useContours)
+                K.addTimings(G.stats);
+            if (useLocalize)
+                Z.addTimings(G.stats);
+            G.stats.timing.s3GpuMs += nowMs() - ta; // launches + kernels + hist/count D2H
             ta = nowMs();
-            G.stats.pairs = *L.count.h;
-            // dense foreground (e.g. a flash frame): the kernels kept counting past the capacity, so the needed size is
-            // known -- grow the lists once (the kernels that used them are done: `back` waited for them) and redo the batch
-            if (!L.fits(attempt, "foreground list overflow (dense foreground in too many images)"))
-                continue;
-            // more contours or vertices than their lists hold: the kernel kept counting, so the needed sizes are known --
-            // grow them once and redo the batch
-            if (useContours && (K.coff.h[nimg] > K.contCap || K.poff.h[nimg] > K.ptsCap)) {
-                if (contoursGrown)
-                    throw std::runtime_error("RunPipeline: contour list overflow after it was grown");
-                growContours(K, K.coff.h[nimg], K.poff.h[nimg]);
-                contoursGrown = true;
-                continue;
-            }
-            // ... and the same for the lists of the localize knob, in two steps.  K7b declines (INCOMPLETE) every stack
-            // with records beyond the record list, and a declined stack reserves no boxes or tracks: while the records do
-            // not fit the two totals are lower bounds, so the record list grows first, from K5's true count, ...
-            if (useLocalize && K.coff.h[nimg] > Z.descCap) {
-                if (recordsGrown)
-                    throw std::runtime_error("RunPipeline: localizer record list overflow after it was grown");
-                growLocalize(Z, K.coff.h[nimg], 0, 0);
-                recordsGrown = true;
-                ++G.stats.locRegrows;
-                continue;
-            }
-            // ... and the boxes and tracks once every stack was looked at: now the totals are true counts
-            if (useLocalize && (Z.totals.h[0] > Z.rectCap || Z.totals.h[1] > Z.trackCap)) {
-                if (tracksGrown)
-                    throw std::runtime_error("RunPipeline: localizer box / track list overflow after it was grown");
-                growLocalize(Z, 0, Z.totals.h[0], Z.totals.h[1]);
-                tracksGrown = true;
-                ++G.stats.locRegrows;
-                continue;
-            }
-            break;
+            G.stats.timing.pairs = *L.count.h;
+            // Needed vs. capacity: the kernels keep counting past a list's capacity, so the needed size is known (0: the
+            // list's knob is off).  The lists of the first step that does not fit grow, once (the kernels that used them are
+            // done: `back` waited for them), and the batch is redone: 1, dense foreground (e.g. a flash frame); 2, contours
+            // and vertices; 3, the records, from K5's true count -- before step 4, because K7b declines (INCOMPLETE) every
+            // stack with records beyond the record list and a declined stack reserves no boxes or tracks, so while the records
+            // do not fit the two totals are lower bounds; 4, the boxes and tracks, from totals that are true counts now
+            const uint32_t nc = useContours ? K.coff.h[nimg] : 0, nv = nc ? K.poff.h[nimg] : 0;
+            const uint32_t *total = useLocalize ? (const uint32_t *)Z.totals.h : nullptr;
+            const Fit rows[] = {
+                {&L.gidx, *L.count.h, "RunPipeline: foreground list overflow (dense foreground in too many images)", 1, false},
+                {&K.cnpts, nc, "RunPipeline: contour list overflow after it was grown", 2, false},
+                {&K.pts, nv, "RunPipeline: contour list overflow after it was grown", 2, false},
+                {&Z.desc, total ? nc : 0, "RunPipeline: localizer record list overflow after it was grown", 3, true},
+                {&Z.rects, total ? total[0] : 0, "RunPipeline: localizer box / track list overflow after it was grown", 4, true},
+                {&Z.tracks, total ? total[1] : 0, "RunPipeline: localizer box / track list overflow after it was grown", 4, true}};
+            const Fit *grew = fitLists(rows, sizeof rows / sizeof *rows, attempt);
+            if (!grew)
+                break;
+            G.stats.loc.regrows += grew->locRegrow;
         }
-        const uint32_t cnt = *L.count.h;
-        const uint32_t nkept = useBlobs ? B.koff.h[nimg] : 0;
-        // localize knob: the vertices travel only when some stack was declined and takes the host route
-        bool shipVerts = !useLocalize;
-        for (int k = 0; useLocalize && k < nloc; ++k)
-            shipVerts = shipVerts || Z.res.h[k].status != ABUB_LOC_DONE;
-        if (useBlobs) {
-            if (nkept > L.cap)
-                throw std::runtime_error("RunPipeline: kept list larger than the candidate list");
-            // with the contours knob the pixels travel only when some slot was declined and takes the host route
-            if (nkept && (!useContours || K.cstats.h[1] != 0)) {
-                L.kidx.toHost(nkept, back);
-                G.stats.listBytes += useContours ? 4ll * nkept : 0;
-            }
-            if (useContours) {
-                if (shipVerts) {
-                    if (const uint32_t nc = K.coff.h[nimg])
-                        K.cnpts.toHost(nc, back);
-                    if (const uint32_t nv = K.poff.h[nimg])
-                        K.pts.toHost(nv, back);
-                    G.stats.listBytes += 4ll * K.coff.h[nimg] + 4ll * K.poff.h[nimg];
-                }
-                if (useLocalize) {
-                    if (const uint32_t nc = K.coff.h[nimg])
-                        Z.desc.toHost(nc, back);
-                    if (Z.totals.h[0])
-                        Z.rects.toHost(4 * (size_t)Z.totals.h[0], back);
-                    if (Z.totals.h[1])
-                        Z.tracks.toHost(Z.totals.h[1], back);
-                    G.stats.listBytes += (long long)sizeof(abub_contour_desc) * K.coff.h[nimg] + 16ll * Z.totals.h[0] +
-                                         4ll * Z.totals.h[1] + (long long)sizeof(abub_loc_result) * nloc;
-                }
-                G.stats.contTraced += K.cstats.h[0];
-                G.stats.contHost += K.cstats.h[1];
-                G.stats.contContours += K.cstats.h[2];
-                G.stats.contVertices += K.cstats.h[3];
-            }
-            G.stats.blobCandidates += cnt;
-            G.stats.blobForeground += B.kstats.h[1];
-            G.stats.blobKept += nkept;
-            G.stats.blobComponents += B.kstats.h[2];
-            G.stats.blobKeptComponents += B.kstats.h[3];
-            G.stats.blobLargeSlots += B.kstats.h[0];
-        } else
+        // The lists travel; with the blobs knob the kept pixels in place of the candidates
+        if (useBlobs)
+            B.listsToHost(back, L, nimg, useContours ? (const uint32_t *)K.cstats.h : nullptr, G.stats);
+        else
             L.pairsToHost(back);
-        // thresholds (TOZERO + Otsu) on the host from the histograms, while the list travels
-        // (pointers into the list: taken after the grow loop, used until the next batch replans every image)
+        if (useContours)
+            K.listsToHost(back, nimg, !useLocalize || Z.declined(nloc), G.stats);
+        if (useLocalize)
+            Z.listsToHost(back, K.coff.h[nimg], nloc, G.stats);
+        // thresholds (TOZERO + Otsu) on the host from the histograms, while the lists travel (pointers into the lists: taken
+        // after the grow loop, used until the next batch replans every image; what a knob that is off would bind is default)
         pool->parallelFor(nimg, [&](int k) {
-            PlannedImage *p = bySlot[k];
-            p->thr = binarizeThresholdFromHist(G.hist3.h + (size_t)k * 256, P, p->tozero);
-            if (useBlobs) {
-                p->fg = nullptr;
-                p->fgv = nullptr;
-                p->nfg = 0;
-                p->kept = L.kidx.h + B.koff.h[k];
-                p->nkept = B.koff.h[k + 1] - B.koff.h[k];
-                p->otsuMismatch = B.otsu.h[k] != p->thr;
-                p->traced = useContours && K.status.h[k] == 0;
-                p->keptShipped = !useContours || K.cstats.h[1] != 0;
-                p->vertsShipped = shipVerts;
-                if (p->traced) {
-                    p->cnp = K.cnpts.h + K.coff.h[k];
-                    p->cpts = K.pts.h + K.poff.h[k];
-                    p->ncont = K.coff.h[k + 1] - K.coff.h[k];
-                }
-            } else {
-                L.bind(*p, k);
-                p->kept = nullptr;
-                p->nkept = 0;
-                p->traced = false;
-                p->keptShipped = true;
-                p->vertsShipped = true;
-            }
+            PlannedImage &p = *bySlot[k];
+            p.thr = binarizeThresholdFromHist(G.hist3.h + (size_t)k * 256, P, p.tozero);
+            if (useBlobs)
+                B.bind(p, k, L);
+            else
+                L.bind(p, k);
+            if (useContours)
+                K.bind(p, k);
         });
         HIPOK(hipStreamSynchronize(back));
-        // localize knob: a stack the kernels finished, and whose thresholds the host confirms, skips stage 4's arithmetic
-        for (int k = 0; useLocalize && k < nloc; ++k) {
-            BatchEventData &d = stacks[loc[k]].data;
-            const abub_loc_result &r = Z.res.h[k];
-            bool mismatch = false;
-            for (const PlannedImage &p : d.planned)
-                mismatch = mismatch || p.otsuMismatch;
-            d.locReady = r.status == ABUB_LOC_DONE && !mismatch;
-            if (d.locReady) {
-                d.locTrig = d.planned[0].i;
-                d.locRes = r;
-                d.locRects = Z.rects.h;
-                d.locTracks = Z.tracks.h;
-                d.locDesc = Z.desc.h;
-                ++G.stats.locDevice;
-                G.stats.locBubbles += r.nbubbles;
-                G.stats.locDescs += r.ntrack - r.nbubbles;
-            } else if (r.status == ABUB_LOC_LIMIT)
-                ++G.stats.locHostLimit;
-            else if (r.status == ABUB_LOC_SLOT || r.status == ABUB_LOC_BAD_FRAME)
-                ++G.stats.locHostSlot;
-            else if (r.status == ABUB_LOC_BELLOWS)
-                ++G.stats.locHostBellows;
-            else
-                ++G.stats.locHostOther;
-        }
-        G.stats.s3ListMs += nowMs() - ta; // list D2H (+ thresholds)
+        for (int k = 0; useLocalize && k < nloc; ++k)
+            Z.bind(stacks[loc[k]].data, k, G.stats);
+        G.stats.timing.s3ListMs += nowMs() - ta; // list D2H (+ thresholds)
     }
 
     // ---- bellows veto round ----------------------------------------------------------------------------------------
@@ -1915,7 +1995,7 @@ private:
             pool->parallelFor((int)ask.size(), [&](int k) { localize(stacks[ask[k]]); });
         }
         if (any)
-            G.stats.vetoMs += nowMs() - t0;
+            G.stats.bellows.vetoMs += nowMs() - t0;
     }
 
     struct VetoFallback {};
@@ -1991,7 +2071,7 @@ private:
                 throw VetoFallback();
             check(rc, "bellows veto match");
             off += n;
-            ++G.stats.matchLaunches;
+            ++G.stats.bellows.matchLaunches;
         }
         V.xy.toHost(2 * (size_t)total, st);
         HIPOK(hipStreamSynchronize(st));
@@ -2002,7 +2082,7 @@ private:
                 r.second->ready = true;
                 ++off;
             }
-        G.stats.matchJobs += total;
+        G.stats.bellows.matchJobs += total;
         return true;
     }
 
@@ -2032,8 +2112,8 @@ private:
             L.allocate(cap);
             V.capImg = cap;
         }
-        if (L.cap == 0)
-            L.grow(pairCap > 0 ? (uint32_t)pairCap : 1u << 20);
+        if (L.cap() == 0)
+            L.gidx.seed(pairCap > 0 ? (uint32_t)pairCap : 1u << 20);
         hipStream_t st = G.stream.get();
         // the two renderings of the template (L3Localizer.cpp:326-334), then everything on the device with no sync between
         pool->parallelFor(n, [&](int k) {
@@ -2069,13 +2149,14 @@ private:
             check(abub_subsat_hist_dev(V.img + (size_t)k * P, V.syn + (size_t)k * P, W, H, V.hist.d + (size_t)k * 256, st),
                   "bellows veto subtract");
         for (int attempt = 0;; ++attempt) {
-            HIPOK(hipMemsetAsync(L.count.d, 0, sizeof(uint32_t), st));
-            check(abub_fg_compact_pairs_dev(V.img, n, W, H, V.thr.d, L.pairs, L.cap, L.count.d, st), "bellows veto K4");
+            L.start(st);
+            check(abub_fg_compact_pairs_dev(V.img, n, W, H, V.thr.d, L.pairs, L.cap(), L.count.d, st), "bellows veto K4");
             L.group(n, V.hist.d, V.thr.d, st, "bellows veto group");
             V.hist.toHost((size_t)n * 256, st);
             L.offsetsToHost(n, st);
             HIPOK(hipStreamSynchronize(st));
-            if (L.fits(attempt, "bellows veto foreground list overflow")) // (grows after the sync above: only K4 is redone)
+            const Fit row = {&L.gidx, *L.count.h, "RunPipeline: bellows veto foreground list overflow", 1, false};
+            if (!fitLists(&row, 1, attempt)) // (grows after the sync above: only K4 is redone)
                 break;
         }
         L.pairsToHost(st);
@@ -2097,123 +2178,21 @@ private:
             r.ready = true;
             if (!stacks[s].vetoed) {
                 stacks[s].vetoed = true;
-                ++G.stats.vetoed;
+                ++G.stats.bellows.vetoed;
             }
         }
-        G.stats.residualImages += n;
+        G.stats.bellows.residualImages += n;
         return true;
     }
 
-    void initBlobs(Group &G)
-    {
-        Group::Blobs &B = G.blobs;
-        if (B.ready)
-            return;
-        const size_t n3 = (size_t)(G.s1 - G.s0) * (NumFramesBubbleTrack + 1);
-        B.otsu.allocate(n3);
-        B.minbox.allocate(n3);
-        B.koff.allocate(n3 + 1);
-        B.ncomp.allocate(n3);
-        B.nkc.allocate(n3);
-        B.coff.allocate(n3 + 1);
-        B.kstats.allocate(4);
-        for (Event &e : B.ev)
-            e.create(true);
-        G.list.keep((int)n3, W, H);
-        B.ready = true;
-    }
-
-    // the contour buffers of the group: per-image arrays once, the scratch sized for the candidate list's current capacity,
-    // the contour and vertex lists at a quarter of it to start with (a contour has far fewer vertices than pixels)
-    void fitContours(Group &G, int nimg)
-    {
-        Group::Contours &K = G.contours;
-        if (!K.ready) {
-            const size_t n3 = (size_t)(G.s1 - G.s0) * (NumFramesBubbleTrack + 1);
-            K.status.allocate(n3);
-            K.ncont.allocate(n3);
-            K.coff.allocate(n3 + 1);
-            K.poff.allocate(n3 + 1);
-            K.cstats.allocate(4);
-            for (Event &e : K.ev)
-                e.create(true);
-            K.ready = true;
-        }
-        if (K.inCap != G.list.cap) {
-            K.scratchBytes = abub_trace_contours_scratch_bytes((int)((size_t)(G.s1 - G.s0) * (NumFramesBubbleTrack + 1)), G.list.cap);
-            if (K.scratchBytes == 0 || W > 65535 || H > 65535)
-                throw std::runtime_error("RunPipeline: frame size not supported by the contour tracing");
-            K.scratch.allocate(K.scratchBytes);
-            K.inCap = G.list.cap;
-        }
-        (void)nimg;
-        if (K.contCap == 0)
-            growContours(K, G.list.cap / 4 + 64, G.list.cap / 4 + 64);
-    }
-    void growContours(Group::Contours &K, uint32_t nc, uint32_t nv)
-    {
-        if (nc > K.contCap) {
-            K.contCap = 0;
-            K.cnpts.allocate((size_t)nc + nc / 4 + 64);
-            K.contCap = nc + nc / 4 + 64;
-        }
-        if (nv > K.ptsCap) {
-            K.ptsCap = 0;
-            K.pts.allocate((size_t)nv + nv / 4 + 64);
-            K.ptsCap = nv + nv / 4 + 64;
-        }
-    }
-
-    // the localize buffers of the group: per-stack arrays once, the record, box and track lists at a modest size to start
-    // with (they grow like the contour lists); the cameras' masks once per pipeline
-    void fitLocalize(Group &G)
-    {
-        Group::Localize &Z = G.loc;
-        deviceMasks();
-        if (Z.ready)
-            return;
-        const size_t ns = (size_t)(G.s1 - G.s0);
-        Z.st.allocate(ns);
-        Z.scratchBytes = abub_localize_scratch_bytes((int)ns, C);
-        Z.scratch.allocate(Z.scratchBytes);
-        Z.res.allocate(ns);
-        Z.totals.allocate(2);
-        for (Event &e : Z.ev)
-            e.create(true);
-        if (locCap > 0) { // (exactly: the lists are meant to overflow)
-            Z.desc.allocate((size_t)locCap);
-            Z.rects.allocate(4 * (size_t)locCap);
-            Z.tracks.allocate((size_t)locCap);
-            Z.descCap = Z.rectCap = Z.trackCap = (uint32_t)locCap;
-        } else
-            growLocalize(Z, (uint32_t)(64 * ns), (uint32_t)(8 * ns), (uint32_t)(16 * ns));
-        Z.ready = true;
-    }
-    void growLocalize(Group::Localize &Z, uint32_t nd, uint32_t nr, uint32_t nt)
-    {
-        if (nd > Z.descCap) {
-            Z.descCap = 0;
-            Z.desc.allocate((size_t)nd + nd / 4 + 64);
-            Z.descCap = nd + nd / 4 + 64;
-        }
-        if (nr > Z.rectCap) {
-            Z.rectCap = 0;
-            Z.rects.allocate(4 * ((size_t)nr + nr / 4 + 64));
-            Z.rectCap = nr + nr / 4 + 64;
-        }
-        if (nt > Z.trackCap) {
-            Z.trackCap = 0;
-            Z.tracks.allocate((size_t)nt + nt / 4 + 64);
-            Z.trackCap = nt + nt / 4 + 64;
-        }
-    }
     // cam<N>_mask.bmp and cam<N>_bellows_mask.bmp of every camera as L3Localizer::isInMask reads them, decoded through the
-    // process-wide mask cache and uploaded once per pipeline; no mask dir, or a file that is not loadable: no mask
-    void deviceMasks()
+    // process-wide mask cache and uploaded once per pipeline (one entry per camera comes back); no mask dir, or a file that
+    // is not loadable: no mask
+    const abub_loc_mask *deviceMasks()
     {
         std::lock_guard<std::mutex> lock(maskMu);
         if (masksReady)
-            return;
+            return locMasks.data();
         locMasks.assign((size_t)C, abub_loc_mask{});
         maskBuf.clear();
         maskBuf.resize(2 * (size_t)C);
@@ -2231,6 +2210,7 @@ private:
                 (b ? k.bh : k.fh) = m.rows;
             }
         masksReady = true;
+        return locMasks.data();
     }
 
     // AnyCamAnalysis body from LocalizeOMatic on (AutoBubStart3.cpp:94-110)
@@ -2260,6 +2240,11 @@ private:
     }
 };
 
+const Knob RunPipeline::knobs[4] = {{"blobs", "ABUB_PIPE_BLOBS", &RunPipeline::blobs},
+                                    {"contours", "ABUB_PIPE_CONTOURS", &RunPipeline::contours},
+                                    {"trigger", "ABUB_PIPE_TRIGGER", &RunPipeline::trigger},
+                                    {"localize", "ABUB_PIPE_LOCALIZE", &RunPipeline::localizeDev}};
+
 void RunPipelineDelete::operator()(RunPipeline *p) const { delete p; }
 
 RunPipelinePtr newRunPipeline(int device, int W, int H, int F, int E, int C, const int *tss, int nthreads, const char *maskDir)
@@ -2283,7 +2268,7 @@ void run(RunPipeline &p, const uint8_t *d_frames, const uint8_t *d_mu, const uin
     p.run(d_frames, d_mu, d_sigma6, stream);
 }
 void writeEvent(RunPipeline &p, int k, int eventNumber, OutputWriter &out) { p.writeEvent(k, eventNumber, out); }
-int bellowsVetoed(const RunPipeline &p) { return p.stats.vetoed; }
+int bellowsVetoed(const RunPipeline &p) { return (int)p.stats.bellows.vetoed; }
 
 } // namespace abub
 
@@ -2337,27 +2322,55 @@ const void *abh_pipe_stack(void *p, int s)
     return &res;
 }
 
-// out[0..4] of the last run: stacks whose bellows veto ran in the batch, template-match jobs, match launches, residual
-// images, wall time of the veto rounds (ms, summed over the stack groups)
-void abh_pipe_bellows(void *p, double *out)
+// The counters of the last run, one getter per struct of PipeStats: the struct has the getter's slots in their order and
+// says what each counts (summed over stack groups and rounds; a knob's are zeros when the knob was off).  out[0..4],
+// [0..5], [0..9], [0..4], [0..7], and [0..11] with the number of rounds as the return value
+static const abub::PipeStats &statsOf(void *p) { return ((abub::RunPipeline *)p)->stats; }
+void abh_pipe_bellows(void *p, double *out) { abub::copySlots(statsOf(p).bellows, out); }
+void abh_pipe_trigger_stats(void *p, double *out) { abub::copySlots(statsOf(p).trigger, out); }
+void abh_pipe_localize_stats(void *p, double *out) { abub::copySlots(statsOf(p).loc, out); }
+void abh_pipe_contour_stats(void *p, double *out) { abub::copySlots(statsOf(p).contours, out); }
+void abh_pipe_blob_stats(void *p, double *out) { abub::copySlots(statsOf(p).blobs, out); }
+int abh_pipe_timing(void *p, double *out)
 {
-    const abub::PipeStats &st = ((abub::RunPipeline *)p)->stats;
-    const double v[5] = {(double)st.vetoed, (double)st.matchJobs, (double)st.matchLaunches, (double)st.residualImages, st.vetoMs};
-    std::memcpy(out, v, sizeof v);
+    abub::copySlots(statsOf(p).timing, out);
+    return statsOf(p).rounds;
 }
 
-// Run-time knobs of one pipeline object: "blobs" (0 = the host applies the Otsu cut to every candidate pixel, 1 = the
-// device labels the foreground and ships only the pixels of the components the localizer can use; default from
-// ABUB_PIPE_BLOBS) and "contours" (1 = the device also traces the contours of those components and ships their vertices,
-// whatever "blobs" says; a slot the kernel declines keeps the host route; default from ABUB_PIPE_CONTOURS, else 0) and
-// "trigger" (1 = stage 2's trigger search runs on the device, K6, for every stack inside abub_trigger_search_limits; the
-// host search stays for the others; read at the start of a run; default from ABUB_PIPE_TRIGGER, else 0) and "localize" (1 =
-// stage 3 also describes the contours and runs the localizer's decisions per stack on the device, K7, whatever "contours"
-// and "blobs" say; a stack the kernels decline keeps the host route; default from ABUB_PIPE_LOCALIZE, else 0).  Names and values are checked before the handle: -1 for an unknown name, a bad value or no handle.
+// out[0..1]: the first two numbers of abh_pipe_trigger_stats summed over every pipeline run of this process so far (the
+// pipelines of a batched run are its own: a caller takes the difference around it)
+void abh_pipe_trigger_totals(double *out)
+{
+    out[0] = (double)abub::g_trigTotals[0].load();
+    out[1] = (double)abub::g_trigTotals[1].load();
+}
+
+// ... and the same for abh_pipe_localize_stats: stacks localised on the device, stacks on the host route
+void abh_pipe_localize_totals(double *out)
+{
+    out[0] = (double)abub::g_locTotals[0].load();
+    out[1] = (double)abub::g_locTotals[1].load();
+}
+
+// Run-time knobs of one pipeline object, each 0 or 1 (RunPipeline::knobs has the names, and the environment variables
+// that give a new pipeline its values, else 0).  Results never depend on them.
+//  - "blobs": 0 = the host applies the Otsu cut to every candidate pixel; 1 = the device labels the foreground and ships
+//    only the pixels of the components the localizer can use.
+//  - "contours": 1 = the device also traces the contours of those components (K5) and ships their vertices, whatever
+//    "blobs" says; a slot the kernel declines keeps the host route.
+//  - "trigger": 1 = stage 2's trigger search runs on the device (K6) for every stack inside abub_trigger_search_limits;
+//    the host search stays for the others.  Read at the start of a run.
+//  - "localize": 1 = stage 3 also describes the contours and runs the localizer's decisions per stack on the device (K7),
+//    whatever "contours" and "blobs" say; a stack the kernels decline keeps the host route.
+// Checked in this order, -1 for each: an unknown name, a value other than 0 or 1, no handle.
 int abh_pipe_set_option(void *p, const char *name, int value)
 {
     const std::string opt = name ? name : "";
-    if (opt != "blobs" && opt != "contours" && opt != "trigger" && opt != "localize") {
+    const abub::Knob *knob = nullptr;
+    for (const abub::Knob &k : abub::RunPipeline::knobs)
+        if (opt == k.name)
+            knob = &k;
+    if (!knob) {
         g_pipeErr = std::string("abh_pipe_set_option: unknown option ") + (name ? name : "(null)");
         return -1;
     }
@@ -2369,82 +2382,7 @@ int abh_pipe_set_option(void *p, const char *name, int value)
         g_pipeErr = "abh_pipe_set_option: no pipeline";
         return -1;
     }
-    abub::RunPipeline *rp = (abub::RunPipeline *)p;
-    (opt == "blobs" ? rp->blobs : opt == "contours" ? rp->contours : opt == "trigger" ? rp->trigger : rp->localizeDev) = value;
+    ((abub::RunPipeline *)p)->*knob->value = value;
     return 0;
-}
-
-// out[0..5] of the last run with the trigger knob on (zeros otherwise), summed over stack groups and rounds: stacks
-// searched on the device, stacks on the host route (beyond abub_trigger_search_limits), search launches, NEED_FRAMES
-// answers, NEED_FINAL answers, ms of the K6 launches
-void abh_pipe_trigger_stats(void *p, double *out)
-{
-    const abub::PipeStats &st = ((abub::RunPipeline *)p)->stats;
-    const double v[6] = {(double)st.trigDevStacks, (double)st.trigHostStacks, (double)st.trigLaunches, (double)st.trigNeedFrames,
-                         (double)st.trigNeedFinal, st.trigK6Ms};
-    std::memcpy(out, v, sizeof v);
-}
-
-// out[0..1]: the first two numbers of abh_pipe_trigger_stats summed over every pipeline run of this process so far (the
-// pipelines of a batched run are its own: a caller takes the difference around it)
-void abh_pipe_trigger_totals(double *out)
-{
-    out[0] = (double)abub::g_trigTotals[0].load();
-    out[1] = (double)abub::g_trigTotals[1].load();
-}
-
-// out[0..1]: stacks localised on the device and stacks on the host route with the localize knob on, summed over every
-// pipeline run of this process so far (see abh_pipe_trigger_totals)
-void abh_pipe_localize_totals(double *out)
-{
-    out[0] = (double)abub::g_locTotals[0].load();
-    out[1] = (double)abub::g_locTotals[1].load();
-}
-
-// out[0..9] of the last run with the localize knob on (zeros otherwise), summed over stack groups and rounds: stacks
-// localised on the device; stacks on the host route: over a limit, with a declined slot or an undecodable frame, with every
-// genesis contour in the bellows mask, for another reason (Otsu mismatch); bubbles and descriptors of the device's tracks;
-// ms of the K7 launches; bytes of the kept-pixel, contour, vertex, record, box and track lists stage 3 copied to the host
-// (counted with the contours knob alone, too); batches redone because the record list or the box / track lists had to grow
-void abh_pipe_localize_stats(void *p, double *out)
-{
-    const abub::PipeStats &st = ((abub::RunPipeline *)p)->stats;
-    const double v[10] = {(double)st.locDevice, (double)st.locHostLimit, (double)st.locHostSlot, (double)st.locHostBellows,
-                         (double)st.locHostOther, (double)st.locBubbles, (double)st.locDescs, st.locK7Ms,
-                          (double)st.listBytes, (double)st.locRegrows};
-    std::memcpy(out, v, sizeof v);
-}
-
-// out[0..4] of the last run with the contours knob on (zeros otherwise), summed over stack groups and rounds: slots
-// traced on the device, slots left to the host route, contours, vertices, ms of the K5 launches
-void abh_pipe_contour_stats(void *p, double *out)
-{
-    const abub::PipeStats &st = ((abub::RunPipeline *)p)->stats;
-    const double v[5] = {(double)st.contTraced, (double)st.contHost, (double)st.contContours, (double)st.contVertices,
-                         st.contK5Ms};
-    std::memcpy(out, v, sizeof v);
-}
-
-// out[0..7] of the last run with the blobs knob on (zeros otherwise), summed over stack groups and rounds: candidate
-// pairs, foreground pixels after the Otsu cut, kept pixels (shipped to the host), components, kept components, slots
-// labelled on the global-memory path, ms of the Otsu launches, ms of the K4b launches
-void abh_pipe_blob_stats(void *p, double *out)
-{
-    const abub::PipeStats &st = ((abub::RunPipeline *)p)->stats;
-    const double v[8] = {(double)st.blobCandidates, (double)st.blobForeground, (double)st.blobKept, (double)st.blobComponents,
-                         (double)st.blobKeptComponents, (double)st.blobLargeSlots, st.blobOtsuMs, st.blobK4bMs};
-    std::memcpy(out, v, sizeof v);
-}
-
-// out[0..11] of the last run: stage1 .. stage4, total, stage-3 launches + kernels, stage-3 list transfer, an unused slot
-// (ms), candidate pairs, trigger-search jobs, drop-in stacks, jobs completed on demand; returns the number of rounds
-int abh_pipe_timing(void *p, double *out)
-{
-    const abub::PipeStats &st = ((abub::RunPipeline *)p)->stats;
-    const double v[12] = {st.stage1Ms, st.stage2Ms, st.stage3Ms, st.stage4Ms, st.totalMs, st.s3GpuMs, st.s3ListMs,
-                          0.0, // (s3_bucket_ms: the key stays in the reports, nothing writes it)
-                          (double)st.pairs, (double)st.jobsLaunched, (double)st.dropIns, (double)st.jobsCompleted};
-    std::memcpy(out, v, sizeof v);
-    return st.rounds;
 }
 }

@@ -204,6 +204,52 @@ def test_pipeline_localize_lists_regrow(oracle, monkeypatch, paircap):
     _against_oracle(oracle, small, slab, models, tss, what="lists regrow")
 
 
+@pytest.mark.parametrize("paircap,loccap", [(None, None), ("64", "1")])
+@pytest.mark.parametrize("groups", [None, "2"])
+def test_pipeline_knob_ladder_on_one_object(oracle, monkeypatch, groups, paircap, loccap):
+    """One Pipeline object through localize, contours, blobs, nothing, localize + trigger, nothing: the first batch makes
+    every stage's buffers at once (with the small capacities, while every list is growing) and the later settings reuse
+    them.  Every run gives the same per-stack results, the oracle's; the stats of a stage that did not run are zero."""
+    W, H, E, C_ = 1280, 96, 6, 2
+    slab, models, tss = ls.regime_run(oracle, "post_trigger_dense")
+    d_slab, d_mu, d_s6 = _device(slab, models)
+    st_ = torch.cuda.current_stream().cuda_stream
+    env = {"ABUB_PIPE_GROUPS": groups, "ABUB_PIPE_PAIRCAP": paircap, "ABUB_PIPE_LOCCAP": loccap}
+    for k, v in env.items():
+        if v:
+            monkeypatch.setenv(k, v)
+    pipe = host.Pipeline(0, W, H, F, E, C_, tss, nthreads=4)
+    for k, v in env.items():
+        if v:
+            monkeypatch.delenv(k)
+    ladder = [{"localize": 1}, {"contours": 1}, {"blobs": 1}, {}, {"localize": 1, "trigger": 1}, {}]
+    res, regrows = [], []
+    for on in ladder:
+        for name in ("blobs", "contours", "trigger", "localize"):
+            pipe.set_option(name, on.get(name, 0))
+        pipe.run(d_slab, d_mu, d_s6, st_)
+        res.append([pipe.result(s) for s in range(E * C_)])
+        lst = pipe.localize_stats()
+        regrows.append(lst["regrows"])
+        # a stage runs when its knob, or one that implies it, is on: localize -> contours -> blobs
+        ran = {"localize": "localize" in on, "trigger": "trigger" in on}
+        ran["contours"] = ran["localize"] or "contours" in on
+        ran["blobs"] = ran["contours"] or "blobs" in on
+        stats = {"localize": {k: v for k, v in lst.items() if k != "list_bytes"}, "trigger": pipe.trigger_stats(),
+                 "contours": pipe.contour_stats(), "blobs": pipe.blob_stats()}
+        for name, st in stats.items():
+            if not ran[name]:
+                assert all(v == 0 for v in st.values()), (on, name, st)
+        if ran["localize"]:
+            assert lst["device"] > 0 and lst["host_route"] == 0, (on, lst)
+    pipe.close()
+    for r in res[1:]:
+        assert repr(r) == repr(res[0])
+    if loccap:
+        assert regrows[0] >= 2 and regrows[4] == 0, regrows
+    _against_oracle(oracle, res[0], slab, models, tss, what="knob ladder")
+
+
 def test_pipeline_localize_with_trigger(oracle):
     W, H, E, C_ = 1280, 96, 6, 2
     slab, models, tss = ls.regime_run(oracle, "default", seed=740)
