@@ -377,6 +377,27 @@ def png_decode(files, W, H, device="cuda:0"):
     return out[:n], st
 
 
+def abf_decode(files, descs, W, H, out, status=None):
+    """abub_abf_decode_dev: files u8 [files_bytes] (packed "ABF1" files as they are on disk, anywhere in the buffer), descs
+    int64 [n, 3] of (offset of the file, its length, byte offset of its decoded frame in `out`), out u8 (any shape, written
+    in place) -> status i32 [n] on the device (0 = decoded, else ABUB_ABF_E_*)."""
+    import numpy as np
+    _need_cuda(files, out)
+    d = np.asarray(descs, dtype=np.int64).reshape(-1, 3)
+    n = len(d)
+    rec = np.zeros((max(n, 1), 4), dtype=np.uint32)
+    rec[:n, 0] = d[:, 0] & 0xFFFFFFFF
+    rec[:n, 1] = d[:, 1] & 0xFFFFFFFF
+    rec[:n, 2] = d[:, 2] & 0xFFFFFFFF
+    rec[:n, 3] = d[:, 2] >> 32
+    d_desc = torch.from_numpy(rec.view(np.int32).copy()).to(files.device)
+    if status is None:
+        status = torch.full((max(n, 1),), 99, dtype=torch.int32, device=files.device)
+    _lib.check(_lib.lib().abub_abf_decode_dev(_ptr(files), files.numel(), _ptr(d_desc), n, W, H, _ptr(out), out.numel(),
+                                              _ptr(status), _stream()), "abub_abf_decode_dev")
+    return status[:n]
+
+
 def match_terms(frames, frame_idx, tmpl):
     """Exact CCORR terms (abub_match_ccorr_batch_dev): frames u8 [N,H,W] (any slab of frames), frame_idx int32 [njobs]
     (frame of each job), tmpl u8 [th,tw] -> (num, wsum2), each int64 [njobs, H-th+1, W-tw+1] holding the u64 sums."""

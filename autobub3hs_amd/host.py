@@ -43,6 +43,9 @@ SIGNATURES = {
     "abh_result_dzdt": (C.c_float, [_vp, _i]),
     "abh_result_drdt": (C.c_float, [_vp, _i]),
     "abh_imdecode": (_i, [_u8p, _i, _u8p, _i, _ip, _ip]),
+    "abh_abf_encode": (C.c_longlong, [_u8p, _i, _i, _u8p, C.c_longlong]),
+    "abh_abf_decode": (_i, [_u8p, C.c_longlong, _u8p, _i, _i]),
+    "abh_run_repack": (_i, [_vp, _s, _i, _i, _dp]),
     "abh_png_walk": (_i, [_u8p, _i, _i, _i, _u32p, _i, _ip, _ip, _u8p]),
     "abh_imwrite": (_i, [_s, _u8p, _i, _i]),
     "abh_write_header": (None, [_s, _s, _i, _i]),
@@ -190,21 +193,23 @@ class Run:
     def train_on_gpu(self, ncams, shape=None):
         """Every camera trained in one pass on the device (abub::TrainOnDevice): per camera (status, tss, mu, sigma), the
         same as train(cam).  self.train_path is "device", or "host" where TrainOnDevice declined the run; self.train_stats:
-        frames decoded by the GPU decoder / by host threads, decode launches, seconds."""
+        frames decoded by the GPU decoders / by host threads, decode launches, seconds, and of the first the packed frames
+        (frames_gpu_unpacked, abub_abf_decode_dev)."""
         H, W = shape if shape is not None else self._shape
         L = lib()
         mu = np.zeros((ncams, H, W), np.uint8)
         sg = np.zeros((ncams, H, W), np.uint8)
         st = np.zeros(ncams, np.int32)
         tss = np.zeros(ncams, np.int32)
-        stats = np.zeros(4, np.float64)
+        stats = np.zeros(5, np.float64)
         rc = L.abh_train_device(self._h, ncams, st.ctypes.data_as(_ip), tss.ctypes.data_as(_ip), mu.ctypes.data_as(_u8p),
                                 sg.ctypes.data_as(_u8p), H * W, stats.ctypes.data_as(_dp))
         if rc < 0:
             raise RuntimeError(L.abh_last_error(self._h).decode())
         self.train_path = "device" if rc == 0 else "host"
         self.train_stats = {"frames_gpu_decoded": int(stats[0]), "frames_host_decoded": int(stats[1]),
-                            "decode_launches": int(stats[2]), "seconds": float(stats[3])}
+                            "decode_launches": int(stats[2]), "seconds": float(stats[3]),
+                            "frames_gpu_unpacked": int(stats[4])}
         return [(int(st[c]), int(tss[c]), mu[c], sg[c]) for c in range(ncams)]
 
     def set_model(self, cam, mu, sigma, tss):
@@ -229,17 +234,29 @@ class Run:
 
     def run_batched(self, ncams, outdir, run_number, frame_offset, maskdir="", ngpus=1, nthreads=16, decode_threads=16,
                     batch_mb=0, shard=(0, 1)):
-        """Every event of this run through the batched GPU pipeline (host/runbatch.cpp RunBatched): frames decoded (PNG files: on the GPU, abub_png_decode_dev; ABUB_GPU_DECODE=0: by host threads into pinned
+        """Every event of this run through the batched GPU pipeline (host/runbatch.cpp RunBatched): frames decoded (PNG and packed files: on the GPU, abub_png_decode_dev / abub_abf_decode_dev; ABUB_GPU_DECODE=0: by host threads into pinned
         batches), detect, blocks appended to <outdir>abub3hs_<run>.txt in event order.  -> stats dict."""
         L = lib()
-        st = (C.c_double * 13)()
+        st = (C.c_double * 14)()
         rc = L.abh_run_batched(self._h, ncams, maskdir.encode(), outdir.encode(), run_number.encode(), frame_offset, ngpus,
                                nthreads, decode_threads, batch_mb, shard[0], shard[1], st)
         if rc != 0:
             raise RuntimeError(f"abh_run_batched rc={rc}: " + L.abh_last_error(self._h).decode())
         keys = ("total_s", "list_s", "decode_s", "gpu_s", "write_s", "frames", "frames_failed", "batches",
-                "events_per_batch", "gpus", "frames_gpu_decoded", "frames_host_decoded", "gpudecode_s")
+                "events_per_batch", "gpus", "frames_gpu_decoded", "frames_host_decoded", "gpudecode_s", "frames_gpu_unpacked")
         return dict(zip(keys, list(st)))
+
+    def repack(self, outdir, nthreads=16, ncams=4):
+        """abub3hs --repack of this run (opened from a directory or an archive): every frame of cameras 0 .. ncams-1
+        written in the packed format (abf_encode) to <outdir>/<event>/<image folder>/<same name>; `outdir` is the new run
+        folder, its last component the run ID.  Files that do not decode are copied as they are.  No GPU.  -> stats dict;
+        raises if anything could not be written."""
+        L = lib()
+        st = (C.c_double * 6)()
+        rc = L.abh_run_repack(self._h, outdir.encode(), ncams, nthreads, st)
+        if rc != 0:
+            raise RuntimeError(f"abh_run_repack rc={rc}: " + L.abh_last_error(self._h).decode())
+        return dict(zip(("packed", "copied", "failed", "bytes_in", "bytes_out", "seconds"), list(st)))
 
     def analyze(self, event, cam, maskdir=""):
         L = lib()
@@ -258,6 +275,29 @@ def imdecode(data, cap=1 << 22):
     if rc != 0:
         return None
     return out[: w.value * h.value].reshape(h.value, w.value).copy()
+
+
+def abf_encode(img):
+    """cv::abfEncode (host/abf.cpp): an 8-bit grey image [H, W] -> the bytes of its packed file ("ABF1", DESIGN section 3, "Packed frames")."""
+    L = lib()
+    img = np.ascontiguousarray(img, dtype=np.uint8)
+    H, W = img.shape
+    cap = 64 + 8 * H + H * ((W + 63) // 64) + W * H
+    out = np.empty(cap, np.uint8)
+    n = L.abh_abf_encode(img.ctypes.data_as(_u8p), W, H, out.ctypes.data_as(_u8p), cap)
+    if n < 0 or n > cap:
+        raise ValueError(f"abf_encode: a {W} x {H} image cannot be packed")
+    return out[:n].tobytes()
+
+
+def abf_decode(data, W, H):
+    """cv::abfDecodeStatus: the bytes of a packed file -> (status, image [H, W]); status 0 = decoded, else the code the GPU
+    decoder gives the same file (ABUB_ABF_E_*); the image of a refused file may be half written."""
+    L = lib()
+    src = np.frombuffer(bytes(data) or b"\0", np.uint8)
+    out = np.zeros((H, W), np.uint8)
+    rc = L.abh_abf_decode(src.ctypes.data_as(_u8p), len(data), out.ctypes.data_as(_u8p), W, H)
+    return rc, out
 
 
 def png_walk(data, W, H, cap=4096):

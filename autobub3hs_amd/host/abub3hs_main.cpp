@@ -9,6 +9,7 @@
 #include <cstring>
 #include <fstream>
 #include <iostream>
+#include <memory>
 #include <sstream>
 #include <string>
 #include <thread>
@@ -28,6 +29,7 @@ static std::string usage()
 {
     return "Usage: abub3hs [-hzme] [-D data_series] [-c cam_mask_dir] [--debug code] -d data_dir -r run_ID -o out_dir\n"
            "       abub3hs [-hzm] [-D data_series] [-c cam_mask_dir] -d data_dir --runs ID[,ID...] | --run-list FILE -o out_dir\n"
+           "       abub3hs [-z] [-D data_series] -d data_dir -r run_ID --repack out_data_dir\n"
            "Run the AutoBub3hs bubble finding algorithm on a PICO run (MI355X hot path)\n\n"
            "Required arguments:\n"
            "  -d, --data_dir = Dir\t\tpath to the directory in which the run folder/file is stored\n"
@@ -54,6 +56,10 @@ static std::string usage()
            "  --per-event\t\t\tone analyzer at a time like the reference's loop (also chosen by -e and --debug);\n"
            "\t\t\t\tdefault: whole batches of events decoded into pinned memory and analysed together;\n"
            "\t\t\t\t-e, --debug and --per-event take a single run\n"
+           "  --repack = Dir\t\twrite the run to Dir/<run_ID>/ with every frame in the packed format the GPU decodes\n"
+           "\t\t\t\twithout an inflate (24x the PNG decode; file names stay; files that do not decode are copied); no GPU, no analysis,\n"
+           "\t\t\t\tno -o; not with -e, --merge, --runs / --run-list, --gpu-shard, and not into the\n"
+           "\t\t\t\tdata_dir it reads.  Analyse it with -d Dir\n"
            "Environment: ABUB_TRAIN_ON_GPU=0 trains the runs of a campaign with the host Trainer\n";
 }
 
@@ -204,7 +210,8 @@ static bool readRunList(const std::string &path, std::vector<std::string> &runs)
 
 int main(int argc, char **argv)
 {
-    std::string dataLoc, run_number, out_dir, mask_dir, data_series;
+    std::string dataLoc, run_number, out_dir, mask_dir, data_series, repackDir;
+    bool haveShard = false, haveRepack = false;
     int event_user = -1, debug_mode = 0, ngpus = 1, shardRank = 0, shardWorld = 1, mergeN = 0;
     bool zipped = false, mask_check = false, help = argc == 1, perEvent = false;
     bool haveRun = false, haveList = false; // -r; --runs / --run-list
@@ -264,6 +271,7 @@ int main(int argc, char **argv)
             ngpus = std::max(1, atoi(v.c_str()));
         } else if (a.rfind("--gpu-shard", 0) == 0) {
             value(v);
+            haveShard = true;
             if (sscanf(v.c_str(), "%d/%d", &shardRank, &shardWorld) != 2 || shardWorld < 1 || shardRank < 0 || shardRank >= shardWorld) {
                 std::cerr << "--gpu-shard expects r/N with 0 <= r < N" << std::endl;
                 return -1;
@@ -275,6 +283,9 @@ int main(int argc, char **argv)
                 std::cerr << "--merge expects the number of shards" << std::endl;
                 return -1;
             }
+        } else if (a == "--repack" || a.rfind("--repack=", 0) == 0) {
+            value(repackDir);
+            haveRepack = true;
         } else if (a == "--per-event") {
             perEvent = true;
         } else {
@@ -285,6 +296,51 @@ int main(int argc, char **argv)
     if (help) {
         std::cout << usage() << std::endl;
         return 1;
+    }
+    if (haveRepack) {
+        // ---- --repack: the run rewritten with packed frames (abub::RepackRun); nothing else happens -----------------------
+        const char *bad = mergeN > 0 ? "--merge" : haveList ? "--runs / --run-list" : haveShard ? "--gpu-shard"
+                          : event_user >= 0 ? "-e/--event" : nullptr;
+        if (bad) {
+            std::cerr << "--repack cannot be combined with " << bad << std::endl;
+            return -1;
+        }
+        if (dataLoc.empty() || run_number.empty() || repackDir.empty()) {
+            std::cerr << "--repack needs --data_dir, --run_id and the directory to write to" << std::endl;
+            return -1;
+        }
+        const abub::RunSpec sp = runSpec(dataLoc, data_series, run_number, zipped);
+        std::unique_ptr<Parser> parser;
+        try {
+            if (zipped)
+                parser.reset(new ZipParser(sp.eventDir, sp.imageFolder, sp.imageFormat));
+            else
+                parser.reset(new RawParser(sp.eventDir, sp.imageFolder, sp.imageFormat));
+        } catch (...) {
+            std::cerr << "Failed to read the images from run " << run_number << "." << std::endl;
+            return -5;
+        }
+        int threads = std::min(usableCores(), 128);
+        if (const char *t = getenv("ABUB_THREADS"))
+            threads = std::max(1, atoi(t));
+        abub::RepackStats rs;
+        int rc = 1;
+        try {
+            rc = abub::RepackRun(parser.get(), zipped ? std::string() : sp.eventDir,
+                                 zipped ? std::string() : sp.eventDir + run_number + ".txt",
+                                 repackDir + "/" + run_number, sp.imageFolder, sp.numCams, threads, &rs);
+        } catch (std::exception &e) {
+            std::cerr << "repack failed: " << e.what() << std::endl;
+            return -6;
+        } catch (...) { // (the parsers throw their status codes)
+            std::cerr << "Failed to read the images from run " << run_number << "." << std::endl;
+            return -5;
+        }
+        printf("repack: %d events, %lld frames packed (%lld -> %lld bytes), %lld copied as they are, %lld not written, %.2f s, "
+               "%.1f frames/s\n",
+               rs.events, rs.packed, rs.bytesIn, rs.bytesOut, rs.copied, rs.failed, rs.total_s,
+               rs.total_s > 0 ? (rs.packed + rs.copied) / rs.total_s : 0.0);
+        return rc;
     }
     if (haveList) {
         if (haveRun) {

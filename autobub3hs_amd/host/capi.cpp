@@ -30,6 +30,8 @@ namespace {
 
 struct Run {
     Parser *parser = nullptr; // MemParser (tests / synthetic), RawParser or ZipParser
+    int kind = -1;            // of abh_run_open
+    std::string runFolder, imageFolder;
     MemParser *mem = nullptr;
     std::string frames_of_last_query;
     std::map<int, Trainer *> trainers;
@@ -93,6 +95,9 @@ void *abh_run_open(int kind, const char *runFolder, const char *imageFolder, con
             r->parser = new RawParser(runFolder, imageFolder, imageFormat);
         else
             r->parser = new ZipParser(runFolder, imageFolder, imageFormat);
+        r->kind = kind;
+        r->runFolder = runFolder;
+        r->imageFolder = imageFolder;
         return r;
     } catch (int code) {
         return nullptr;
@@ -142,6 +147,54 @@ int abh_imdecode(const uint8_t *data, int n, uint8_t *out, int cap, int *w, int 
     if ((int)m.total() <= cap)
         std::memcpy(out, m.data, m.total());
     return 0;
+}
+
+// the packed frame format (host/abf.cpp): abh_abf_encode returns the file's size (written when cap suffices), -1 on errors;
+// abh_abf_decode the code of cv::abfDecodeStatus (0 = decoded into out, W * H bytes)
+long long abh_abf_encode(const uint8_t *img, int W, int H, uint8_t *out, long long cap)
+{
+    std::vector<uchar> v;
+    if (!cv::abfEncode(img, W, H, v))
+        return -1;
+    if ((long long)v.size() <= cap)
+        std::memcpy(out, v.data(), v.size());
+    return (long long)v.size();
+}
+int abh_abf_decode(const uint8_t *data, long long n, uint8_t *out, int W, int H)
+{
+    return cv::abfDecodeStatus(data, (size_t)n, out, W, H);
+}
+// abub::RepackRun of a run opened with abh_run_open into the directory `dstRunDir` (its last component is the new run ID);
+// stats (may be NULL): [frames packed, copied as they are, not written, bytes of the packed frames' sources, of the packed
+// files, seconds].  Returns RepackRun's code, -1 on errors.
+int abh_run_repack(void *r, const char *dstRunDir, int ncams, int nthreads, double *stats)
+{
+    Run *run = (Run *)r;
+    try {
+        if (run->kind < 0) {
+            run->last.error = "repack: not a run opened from a directory or an archive";
+            return -1;
+        }
+        std::string src; // the event file of a directory run: <run>/<runID>.txt
+        if (run->kind == 0) {
+            std::string folder = run->runFolder;
+            while (folder.size() > 1 && folder.back() == '/')
+                folder.pop_back();
+            const size_t slash = folder.find_last_of('/');
+            src = folder + "/" + (slash == std::string::npos ? folder : folder.substr(slash + 1)) + ".txt";
+        }
+        abub::RepackStats st;
+        const int rc = abub::RepackRun(run->parser, run->kind == 0 ? run->runFolder : std::string(), src, dstRunDir, run->imageFolder, ncams, std::max(1, nthreads), &st);
+        if (stats) {
+            const double v[6] = {(double)st.packed, (double)st.copied, (double)st.failed, (double)st.bytesIn, (double)st.bytesOut,
+                                 st.total_s};
+            std::memcpy(stats, v, sizeof v);
+        }
+        return rc;
+    } catch (std::exception &e) {
+        run->last.error = e.what();
+        return -1;
+    }
 }
 
 // cv::imwrite of the debug write-out (PNG, or BMP by extension)
@@ -227,7 +280,7 @@ int abh_train(void *r, int cam, int *status, int *tss, uint8_t *mu_out, uint8_t 
 // status[c], tss[c] and, where it trained, its mu / sigma at mu_out + c * cap, sigma_out + c * cap (cap bytes each).  The
 // Run's Trainers are replaced.  Returns 0 (trained on the device), 1 (TrainOnDevice declined the run: the host Trainer
 // trained it), -1 on errors.  stats (may be NULL): [frames decoded by the GPU decoder, by host threads, decode launches,
-// seconds].
+// seconds, packed frames decoded by the GPU decoder (they count in the first, too)].
 int abh_train_device(void *r, int ncams, int *status, int *tss, uint8_t *mu_out, uint8_t *sigma_out, int cap, double *stats)
 {
     Run *run = (Run *)r;
@@ -248,6 +301,7 @@ int abh_train_device(void *r, int ncams, int *status, int *tss, uint8_t *mu_out,
             stats[1] = (double)st.framesHostDecoded;
             stats[2] = (double)st.decodeLaunches;
             stats[3] = st.total_s;
+            stats[4] = (double)st.framesGpuUnpacked;
         }
         if (rc != 0) {
             run->last.error = why;
@@ -315,7 +369,7 @@ int abh_analyze(void *r, const char *ev, int cam, const char *maskdir)
 
 // A whole run (every event of the Run's parser, cameras 0..ncams-1, the Run's trained models) through the batched
 // pipeline into <outdir>abub3hs_<run>.txt; stats: [total_s, list_s, decode_s, gpu_s, write_s, frames, failed,
-// batches, events_per_batch, gpus, frames decoded on the GPU, on host threads, gpudecode_s].  Returns 0, 1 when the batched path declines the run, -1 on errors.
+// batches, events_per_batch, gpus, frames decoded on the GPU, on host threads, gpudecode_s, packed frames decoded on the GPU].  Returns 0, 1 when the batched path declines the run, -1 on errors.
 int abh_run_batched(void *r, int ncams, const char *maskdir, const char *outdir, const char *run_number, int frameOffset,
                     int ngpus, int nthreads, int decodeThreads, int batchMB, int shardRank, int shardWorld, double *statsOut)
 {
@@ -346,9 +400,9 @@ int abh_run_batched(void *r, int ncams, const char *maskdir, const char *outdir,
         if (rc != 0)
             run->last.error = why;
         if (statsOut) {
-            const double v[13] = {bs.total_s, bs.list_s, bs.decode_s, bs.gpu_s, bs.write_s, (double)bs.frames, (double)bs.framesFailed,
+            const double v[14] = {bs.total_s, bs.list_s, bs.decode_s, bs.gpu_s, bs.write_s, (double)bs.frames, (double)bs.framesFailed,
                                   (double)bs.batches, (double)bs.eventsPerBatch, (double)bs.gpus, (double)bs.framesGpuDecoded,
-                                  (double)bs.framesHostDecoded, bs.gpudecode_s};
+                                  (double)bs.framesHostDecoded, bs.gpudecode_s, (double)bs.framesGpuUnpacked};
             std::memcpy(statsOut, v, sizeof v);
         }
         return rc;

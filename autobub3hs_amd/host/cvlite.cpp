@@ -345,6 +345,8 @@ bool imdecodeInto(const uchar *data, size_t size, uchar *dst, int W, int H)
         PixelSink sink = {fixedSink, &f};
         return decodePNGTo(data, size, sink);
     }
+    if (size >= 4 && !std::memcmp(data, "ABF1", 4))
+        return abfDecodeInto(data, size, dst, W, H);
     const Mat m = imdecode(data, size, 0); // (BMP: small files, decoded the ordinary way)
     if (m.empty() || m.cols != W || m.rows != H)
         return false;
@@ -358,6 +360,12 @@ Mat imdecode(const uchar *data, size_t size, int)
         return decodePNG(data, size);
     if (size >= 2 && data[0] == 'B' && data[1] == 'M')
         return decodeBMP(data, size);
+    int w = 0, h = 0;
+    if (abfProbe(data, size, &w, &h)) { // the packed frame format (abf.cpp)
+        Mat m(h, w, CV_8U);
+        if (abfDecodeInto(data, size, m.data, w, h))
+            return m;
+    }
     return Mat();
 }
 

@@ -101,7 +101,7 @@ int TrainOnDevice(Parser *parser, const std::vector<std::string> &EventList, std
                       std::to_string(opt.capBytes >> 20) + " MB");
 
     // ---- read / walk / decode ------------------------------------------------------------------------------------------
-    // GPU decode where the parser hands out the files and the width is one the kernels take; other frames are decoded by
+    // GPU decode where the parser hands out the files and the width is one the PNG kernels take (packed frames too); other frames are decoded by
     // the reading threads (GetImage, as the host path does)
     bool devDecode = W > 0 && opt.gpuDecode != 0 && (W & 3) == 0 && W >= 4 && W <= 2048;
     if (const char *e = getenv("ABUB_GPU_DECODE"))
@@ -181,18 +181,19 @@ int TrainOnDevice(Parser *parser, const std::vector<std::string> &EventList, std
         const size_t perLaunch = (size_t)4 * ncu;
         for (size_t i0 = 0; i0 < tasks.size();) {
             size_t i1 = i0, ngpu = 0;
-            for (; i1 < tasks.size() && (ngpu < perLaunch || tasks[i1].state != FileTask::Gpu); ++i1)
-                ngpu += tasks[i1].state == FileTask::Gpu;
+            for (; i1 < tasks.size() && (ngpu < perLaunch || !tasks[i1].onGpu()); ++i1)
+                ngpu += tasks[i1].onGpu();
             FileDescs fd;
             buildFileDescs(tasks.data() + i0, tasks.data() + i1, total, fd, [&](int s, int) { return (uint64_t)s * P; });
-            if (!fd.desc.empty()) {
+            if (fd.gpuFrames()) {
                 launchFileDecode(fd, B.files.get(), W, H, B.slab.get(), slab, B.png, cs);
                 ++st.decodeLaunches;
             }
             HIPOK(hipStreamSynchronize(cs));
-            finishFileDecode(fd, h_files.get(), (const int32_t *)B.png.h_status.get(), B.slab.get(), W, H, cs,
+            finishFileDecode(fd, h_files.get(), B.png, B.slab.get(), W, H, cs,
                              [&](int s, int) { return (size_t)s * P; }, [&](int s, int) { good[s] = 1; }, st.framesGpuDecoded,
                              st.framesHostDecoded);
+            st.framesGpuUnpacked += fd.unpacked;
             i0 = i1;
         }
         HIPOK(hipStreamSynchronize(cs));

@@ -1,6 +1,6 @@
 // devtrain.hpp -- the background models of every camera of a run trained in one pass on the device: the same frames, skip
 // rules, entropy veto and float Welford recurrence as Trainer::MakeAvgSigmaImage (Trainer.cpp, the reference's
-// AlgorithmTraining/Trainer.cpp:221-331), with the training frames decoded by abub_png_decode_dev into one slab, the veto
+// AlgorithmTraining/Trainer.cpp:221-331), with the training frames decoded by abub_png_decode_dev / abub_abf_decode_dev into one slab, the veto
 // histograms of every (camera, event) pair from one abub_pair_hist_dev launch and one abub_train_dev per camera.
 #ifndef ABUB3HS_DEVTRAIN_HPP
 #define ABUB3HS_DEVTRAIN_HPP
@@ -37,6 +37,7 @@ struct DeviceTrainOptions {
 struct DeviceTrainStats {
     double total_s = 0;
     long long frames = 0, framesGpuDecoded = 0, framesHostDecoded = 0;
+    long long framesGpuUnpacked = 0; // of framesGpuDecoded: packed frames, by abub_abf_decode_dev
     size_t slabBytes = 0;
     int decodeLaunches = 0;
 };

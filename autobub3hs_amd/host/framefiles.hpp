@@ -1,7 +1,8 @@
-// framefiles.hpp -- frames read as FILES for the GPU PNG decoder (abub_png_decode_dev), shared by the batched detect path
-// (runbatch.cpp) and device training (devtrain.cpp).  A host thread reads each file and walks its chunks (pngWalk); a
-// file the walk refuses (BMP, 16-bit, colour, interlaced, another size) gets the host decoder's answer at once, and so
-// does a frame the kernel later returns a nonzero status for.  Internal to the host library.
+// framefiles.hpp -- frames read as FILES for the GPU decoders (abub_png_decode_dev, abub_abf_decode_dev), shared by the
+// batched detect path (runbatch.cpp) and device training (devtrain.cpp).  A host thread reads each file; a packed frame
+// ("ABF1") whose header is valid for W x H goes to the packed decoder as it is, a PNG has its chunks walked (pngWalk); a
+// file neither takes (BMP, 16-bit, colour, interlaced, another size) gets the host decoder's answer at once, and so
+// does a frame a kernel later returns a nonzero status for.  Internal to the host library.
 #ifndef ABUB3HS_FRAMEFILES_HPP
 #define ABUB3HS_FRAMEFILES_HPP
 
@@ -56,7 +57,10 @@ void forEachTask(Parser *parser, int nthreads, size_t n, const Fn &fn)
 
 // One frame to be read: where it goes is decided by the caller (s, f); `state` says what became of it
 struct FileTask {
-    enum { Gpu = 0, HostDecoded = 1, Bad = 2, Other = 3 }; // Other: not a file task (the caller's own work)
+    // Gpu: planned for / taken by the PNG decoder, GpuPacked: taken by the packed decoder; Other: not a file task (the
+    // caller's own work)
+    enum { Gpu = 0, HostDecoded = 1, Bad = 2, Other = 3, GpuPacked = 4 };
+    bool onGpu() const { return state == Gpu || state == GpuPacked; }
     int s = 0, f = 0;
     long long size = 0;
     size_t off = 0; // in the pinned file buffer
@@ -69,11 +73,15 @@ struct FileTask {
 // The descriptors of one decode launch, and the frames a reading thread decoded itself
 struct FileDescs {
     size_t bytes = 0, zbytes = 0;           // of the files; of the decoder's stream buffer
-    std::vector<abub_png_frame> desc;       // the frames the GPU decodes
+    std::vector<abub_png_frame> desc;       // the PNG frames the GPU decodes
     std::vector<std::pair<int, int>> where; // (s, f) of desc[i]
     std::vector<uint32_t> fileOff, fileLen; // of desc[i] inside the file buffer
     std::vector<abub_png_seg> segs;
     std::vector<uint8_t> luts;              // 256 bytes each
+    std::vector<abub_abf_frame> abf;        // the packed frames the GPU decodes (file offset, length, destination)
+    std::vector<std::pair<int, int>> abfWhere;
+    long long unpacked = 0;                 // of them, decoded by the kernel (finishFileDecode)
+    size_t gpuFrames() const { return desc.size() + abf.size(); }
     std::vector<std::vector<uint8_t>> hostPix;
     std::vector<std::pair<int, int>> hostWhere;
     long long bad = 0;
@@ -88,6 +96,13 @@ inline void planFileTask(Parser &sizer, const std::string &ev, const std::string
     t.off = total;
     if (t.state == FileTask::Gpu)
         total += ((size_t)t.size + 15) & ~(size_t)15;
+}
+
+// a packed frame ("ABF1") whose header is valid for W x H: one for abub_abf_decode_dev
+inline bool packedFrameOf(const uint8_t *data, size_t size, int W, int H)
+{
+    int w = 0, h = 0;
+    return cv::abfProbe(data, size, &w, &h) && w == W && h == H;
 }
 
 // On a pool thread: the file into files + t.off, walked for the W x H GPU decoder, else decoded here
@@ -108,6 +123,10 @@ inline void readFileTask(Parser &p, const std::string &ev, const std::string &na
     }
     t.read = true;
     try {
+        if (packedFrameOf(dst, (size_t)t.size, W, H)) {
+            t.state = FileTask::GpuPacked; // (the file goes up as it is; the kernel checks the rest)
+            return;
+        }
         if (!pngWalk(dst, (size_t)t.size, W, H, t.info)) {
             // not a file for the GPU decoder (BMP, 16-bit, colour, interlaced, another size): the host decoder's answer
             t.pix.resize((size_t)W * H);
@@ -136,6 +155,11 @@ void buildFileDescs(FileTask *first, FileTask *last, size_t totalFileBytes, File
         if (t.state == FileTask::HostDecoded) {
             r.hostPix.push_back(std::move(t.pix));
             r.hostWhere.emplace_back(t.s, t.f);
+            continue;
+        }
+        if (t.state == FileTask::GpuPacked) {
+            r.abf.push_back(abub_abf_frame{(uint32_t)t.off, (uint32_t)t.size, dstOf(t.s, t.f)});
+            r.abfWhere.emplace_back(t.s, t.f);
             continue;
         }
         abub_png_frame d;
@@ -168,16 +192,45 @@ void buildFileDescs(FileTask *first, FileTask *last, size_t totalFileBytes, File
         throw std::runtime_error("a batch of more than 4 GB of files (lower the batch size)");
 }
 
-// The decoder's scratch, kept from one launch to the next
+// The decoders' scratch, kept from one launch to the next
 struct PngScratch {
     DeviceBuffer z, raw, luts, desc, segs, status;
     PinnedBuffer h_status;
+    DeviceBuffer abfDesc, abfStatus; // the packed decoder needs no more than its descriptors and statuses
+    PinnedBuffer h_abfStatus;
 };
 
-// One abub_png_decode_dev launch over r's frames into `out` (out_bytes), the statuses copied back into sc.h_status; queued
-// on `stream`, not waited for.  The files are already in d_files.
+// One abub_abf_decode_dev launch over r's packed frames, as launchPngDecode below
+inline void launchAbfDecode(const FileDescs &r, const uint8_t *d_files, int W, int H, uint8_t *out, size_t out_bytes,
+                            PngScratch &sc, hipStream_t stream)
+{
+    const int nf = (int)r.abf.size();
+    if (!nf)
+        return;
+    sc.abfDesc.grow((size_t)nf * sizeof(abub_abf_frame));
+    sc.abfStatus.grow((size_t)nf * sizeof(int32_t));
+    if (sc.h_abfStatus.capacity() < (size_t)nf * sizeof(int32_t))
+        sc.h_abfStatus.allocate((size_t)nf * sizeof(int32_t) + 64);
+    HIPOK(hipMemcpyAsync(sc.abfDesc.get(), r.abf.data(), (size_t)nf * sizeof(abub_abf_frame), hipMemcpyHostToDevice, stream));
+    check(abub_abf_decode_dev(d_files, r.bytes, (const abub_abf_frame *)sc.abfDesc.get(), nf, W, H, out, out_bytes,
+                              (int32_t *)sc.abfStatus.get(), stream),
+          "abub_abf_decode_dev");
+    HIPOK(hipMemcpyAsync(sc.h_abfStatus.get(), sc.abfStatus.get(), (size_t)nf * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+}
+
+// One launch of each decoder that has frames in r, into `out` (out_bytes), the statuses copied back into sc.h_status /
+// sc.h_abfStatus; both queued on `stream` (so both stay behind whatever the caller queued there before, the clear of the
+// batch's slab for one), not waited for.  The files are already in d_files.
+inline void launchPngDecode(const FileDescs &r, const uint8_t *d_files, int W, int H, uint8_t *out, size_t out_bytes,
+                            PngScratch &sc, hipStream_t stream);
 inline void launchFileDecode(const FileDescs &r, const uint8_t *d_files, int W, int H, uint8_t *out, size_t out_bytes,
                              PngScratch &sc, hipStream_t stream)
+{
+    launchPngDecode(r, d_files, W, H, out, out_bytes, sc, stream);
+    launchAbfDecode(r, d_files, W, H, out, out_bytes, sc, stream);
+}
+inline void launchPngDecode(const FileDescs &r, const uint8_t *d_files, int W, int H, uint8_t *out, size_t out_bytes,
+                            PngScratch &sc, hipStream_t stream)
 {
     const int nf = (int)r.desc.size();
     if (!nf)
@@ -201,32 +254,40 @@ inline void launchFileDecode(const FileDescs &r, const uint8_t *d_files, int W, 
     HIPOK(hipMemcpyAsync(sc.h_status.get(), sc.status.get(), (size_t)nf * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
 }
 
-// After the launch above has been waited for: a frame the kernels refused takes the host decoder's answer (the same image,
-// or the same failure), and the reading threads' own frames are uploaded.  ok(s, f) is called for every frame that is in
-// place; gpuOut(s, f) for those of the kernel; hostOffset(s, f): byte offset of the frame from `out`.
+// After the launches above have been waited for: a frame the kernels refused takes the host decoder's answer (the same
+// image, or the same failure), and the reading threads' own frames are uploaded.  ok(s, f) is called for every frame that
+// is in place; hostOffset(s, f): byte offset of the frame from `out`.  Packed frames the kernel decoded count in onGpu
+// and in r.unpacked.
 template <class HostOffset, class Ok>
-void finishFileDecode(FileDescs &r, const uint8_t *h_files, const int32_t *status, uint8_t *out, int W, int H,
+void finishFileDecode(FileDescs &r, const uint8_t *h_files, const PngScratch &sc, uint8_t *out, int W, int H,
                       hipStream_t stream, const HostOffset &hostOffset, const Ok &ok, long long &onGpu, long long &onHost)
 {
     const size_t P = (size_t)W * H;
     std::vector<uint8_t> pix;
-    for (size_t i = 0; i < r.desc.size(); ++i) {
-        uint8_t *dst = out + r.desc[i].dst;
-        if (status[i] == 0) {
-            ok(r.where[i].first, r.where[i].second);
+    // frame (s, f) of file [off, off + len) whose decoder answered `status`
+    auto settle = [&](int32_t status, std::pair<int, int> w, uint64_t dstOff, uint32_t off, uint32_t len) {
+        uint8_t *dst = out + dstOff;
+        if (status == 0) {
+            ok(w.first, w.second);
             ++onGpu;
-            continue;
+            return true;
         }
         pix.resize(P);
-        if (cv::imdecodeInto(h_files + r.fileOff[i], r.fileLen[i], pix.data(), W, H)) {
+        if (cv::imdecodeInto(h_files + off, len, pix.data(), W, H)) {
             HIPOK(hipMemcpy(dst, pix.data(), P, hipMemcpyHostToDevice));
-            ok(r.where[i].first, r.where[i].second);
+            ok(w.first, w.second);
             ++onHost;
         } else {
             HIPOK(hipMemsetAsync(dst, 0, P, stream)); // (a refused frame may be half written)
             ++r.bad;
         }
-    }
+        return false;
+    };
+    const int32_t *status = (const int32_t *)sc.h_status.get(), *abfStatus = (const int32_t *)sc.h_abfStatus.get();
+    for (size_t i = 0; i < r.desc.size(); ++i)
+        settle(status[i], r.where[i], r.desc[i].dst, r.fileOff[i], r.fileLen[i]);
+    for (size_t i = 0; i < r.abf.size(); ++i)
+        r.unpacked += settle(abfStatus[i], r.abfWhere[i], r.abf[i].dst, r.abf[i].off, r.abf[i].len);
     for (size_t i = 0; i < r.hostPix.size(); ++i) {
         HIPOK(hipMemcpy(out + hostOffset(r.hostWhere[i].first, r.hostWhere[i].second), r.hostPix[i].data(), P,
                         hipMemcpyHostToDevice));

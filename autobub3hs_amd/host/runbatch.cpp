@@ -166,9 +166,10 @@ int runBatchedOn(Workers &ws, Parser *parser, const std::vector<std::string> &Ev
     }
     G = std::min(G, 512);
     // ---- where the frames are decoded --------------------------------------------------------------------------------
-    // On the GPU (abub_png.hip) when the parser hands out the files as they are stored and the first frame is a PNG the
-    // kernels take; a host thread still reads each file and walks its chunks, and decodes the odd frame the GPU path
-    // refuses.  Otherwise host threads decode every frame (GetImageInto).
+    // On the GPU (abub_png.hip, abub_abf.hip) when the parser hands out the files as they are stored and the first frame is
+    // a PNG the kernels take or a packed frame; a host thread still reads each file, walks a PNG's chunks, and decodes the
+    // odd frame the GPU path refuses.  Otherwise host threads decode every frame (GetImageInto).  The width gate is the
+    // PNG kernels': it holds for packed frames too, although abub_abf_decode_dev takes any width.
     bool devDecode = opt.gpuDecode != 0 && (W & 3) == 0 && W >= 4 && W <= 2048;
     if (const char *e = getenv("ABUB_GPU_DECODE"))
         devDecode = devDecode && atoi(e) != 0;
@@ -183,7 +184,7 @@ int runBatchedOn(Workers &ws, Parser *parser, const std::vector<std::string> &Ev
                         std::vector<unsigned char> buf((size_t)sz);
                         PngInfo info;
                         devDecode = p->ReadImageFile(EventList[mine[k]], lists[k][c][0], buf.data(), buf.size()) == sz &&
-                                    pngWalk(buf.data(), buf.size(), W, H, info);
+                                    (pngWalk(buf.data(), buf.size(), W, H, info) || packedFrameOf(buf.data(), buf.size(), W, H));
                     }
                     k = lists.size(); // (one probe decides)
                     break;
@@ -281,7 +282,7 @@ int runBatchedOn(Workers &ws, Parser *parser, const std::vector<std::string> &Ev
         r.hostGood = hostGood;
         buildFileDescs(tasks.data(), tasks.data() + tasks.size(), total, r.files, [&](int s, int f) { return ((uint64_t)s * Fmax + f) * P; });
         r.ms = nowMs() - td;
-        if (!r.files.desc.empty()) {
+        if (r.files.gpuFrames()) {
             sl.d_files.grow(r.files.bytes);
             HIPOK(hipMemcpyAsync(sl.d_files.get(), sl.h_files.get(), r.files.bytes, hipMemcpyHostToDevice, upStream.get()));
             HIPOK(hipStreamSynchronize(upStream.get()));
@@ -391,7 +392,7 @@ int runBatchedOn(Workers &ws, Parser *parser, const std::vector<std::string> &Ev
                     startRead(bn, slot ^ 1);
                 const double tg = nowMs();
                 const int nEv = std::min(G, (int)mine.size() - b * G), nEvGpu = std::min(nEv, Ggpu);
-                const int nf = (int)R.files.desc.size();
+                const int nf = (int)R.files.gpuFrames();
                 uint8_t *d_frames = S.d_frames.get();
                 hipStream_t cs = copyStream.get();
                 // the GPU share starts at zero (frames nobody decodes stay so, see decodeFrame); the host share is uploaded
@@ -405,7 +406,7 @@ int runBatchedOn(Workers &ws, Parser *parser, const std::vector<std::string> &Ev
                 // every write below lands after the clear above
                 HIPOK(hipStreamSynchronize(cs));
                 long long onGpu = 0, onHost = R.hostGood;
-                finishFileDecode(R.files, S.h_files.get(), (const int32_t *)png.h_status.get(), d_frames, W, H, cs,
+                finishFileDecode(R.files, S.h_files.get(), png, d_frames, W, H, cs,
                                  [&](int s, int f) { return ((size_t)s * Fmax + f) * P; },
                                  [&](int s, int f) { R.meta[s].ok[f] = 1; }, onGpu, onHost);
                 const double pngms = Ggpu ? nowMs() - tp : 0;
@@ -443,6 +444,7 @@ int runBatchedOn(Workers &ws, Parser *parser, const std::vector<std::string> &Ev
                     st.bellowsVetoed += bellowsVetoed(*pipe);
                     st.framesGpuDecoded += onGpu;
                     st.framesHostDecoded += onHost;
+                    st.framesGpuUnpacked += R.files.unpacked;
                     st.gpudecode_s += pngms * 1e-3;
                 }
                 slot ^= 1;

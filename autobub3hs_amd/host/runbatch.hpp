@@ -38,7 +38,8 @@ struct BatchedRunStats {
     double list_s = 0, decode_s = 0, gpu_s = 0, write_s = 0, total_s = 0; // decode/gpu: summed over batches (they overlap)
     long long frames = 0, framesFailed = 0;
     long long bellowsVetoed = 0; // stacks whose bellows-movement veto ran inside the batch (pipeline veto round)
-    long long framesGpuDecoded = 0, framesHostDecoded = 0; // of `frames`: by abub_png_decode_dev / by a host thread
+    long long framesGpuDecoded = 0, framesHostDecoded = 0; // of `frames`: by the GPU decoders / by a host thread
+    long long framesGpuUnpacked = 0;                       // of framesGpuDecoded: packed frames, by abub_abf_decode_dev
     double gpudecode_s = 0;                                // upload of the files + the decode kernels, summed over batches
     int events = 0, batches = 0, eventsPerBatch = 0, W = 0, H = 0, Fmax = 0, gpus = 0;
 };
@@ -71,6 +72,21 @@ struct RunSpec {
 };
 
 struct DeviceTrainBuffers;
+
+struct RepackStats {
+    int events = 0;
+    long long packed = 0, copied = 0, failed = 0; // frames written in the packed format / copied as they are / not written
+    long long bytesIn = 0, bytesOut = 0;          // of the packed frames: the source files, the packed files
+    double total_s = 0;
+};
+// abub3hs --repack: every frame of every event and camera 0 .. numCams-1 that `parser` lists, written in the packed format
+// (cv::abfEncode) to <dstRunDir>/<event>/<imageFolder>/<same name> on `nthreads` threads.  A source file that does not
+// decode is copied byte for byte.  Every event gets its directory, frames or not.  The run's event file
+// <dstRunDir>/<its last component>.txt takes the bytes of srcRunFile where that can be read, else one line per event
+// that parser->GetRunFileInfo lists.  No GPU.  Returns 0, or 1 if anything could not be written; throws, before anything
+// is written, when dstRunDir is srcRunDir (the directory the parser reads; empty for an archive).
+int RepackRun(Parser *parser, const std::string &srcRunDir, const std::string &srcRunFile, const std::string &dstRunDir,
+              const std::string &imageFolder, int numCams, int nthreads, RepackStats *stats);
 
 // A run listed and trained, ready for detect; rc = -5 (the run cannot be read) or -7 (a camera did not train)
 struct PreparedRun {

@@ -150,6 +150,14 @@ Mat imdecode(const uchar *data, size_t size, int flags = IMREAD_GRAYSCALE);
 // (not in OpenCV) decodes an 8-bit grey view of the image straight into `dst` (W * H bytes); false when the data is not a
 // W x H image; no per-call heap allocation for PNG (thread-local scratch)
 bool imdecodeInto(const uchar *data, size_t size, uchar *dst, int W, int H);
+// (not in OpenCV) the packed frame format "ABF1" (host/abf.cpp, DESIGN section 3, "Packed frames"): lossless, every row and every 64-pixel block
+// decodable on its own, decoded on the GPU by abub_abf_decode_dev.  imread / imdecode / imdecodeInto recognise it by its
+// magic.  abfEncode: canonical (same pixels, same bytes); false for sizes the header cannot express.  abfProbe: the size
+// a self-consistent header states.  abfDecodeStatus: 0, or the ABUB_ABF_E_* code the GPU decoder gives the same file.
+bool abfEncode(const uchar *pixels, int W, int H, std::vector<uchar> &out);
+bool abfDecodeInto(const uchar *data, size_t size, uchar *dst, int W, int H);
+int abfDecodeStatus(const uchar *data, size_t size, uchar *dst, int W, int H);
+bool abfProbe(const uchar *data, size_t size, int *W, int *H);
 // debug write-out (AnalyzerUnit.cpp:237,354-365; L3Localizer.cpp:236-257,448): 8-bit grey PNG, or 8-bit palettised BMP
 // when the name ends in .bmp; false when the file cannot be written (like cv::imwrite into a missing directory)
 bool imwrite(const std::string &path, const Mat &img);

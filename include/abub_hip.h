@@ -532,6 +532,30 @@ int abub_png_decode_dev(const uint8_t *files, size_t files_bytes, const abub_png
                         uint8_t *zbuf, size_t zbuf_bytes, uint8_t *rawbuf, size_t rawbuf_bytes, uint8_t *out,
                         size_t out_bytes, int32_t *status, void *stream);
 
+/* ---- packed frames ("ABF1") decoded on the GPU (abub_abf.hip) ---------------------------------------------------
+ * The frame format of repacked runs (abub3hs --repack; layout and rules: DESIGN section 3, "Packed frames"; host codec: cv::abfEncode /
+ * cv::abfDecodeInto).  Lossless, about the size of the PNG, every row and every 64-pixel block decodable on its own:
+ * the decode needs no more than one read of the file and one write of the frame (the design goal; what the kernel
+ * reaches: DESIGN).  The caller uploads the FILES as they are on disk;
+ * the kernel trusts nothing in them: every offset is checked against the file's stated length, and that against
+ * files_bytes, before it is used; nothing is read outside `files`, nothing written outside a frame's own W*H bytes. */
+typedef struct abub_abf_frame {
+    uint32_t off, len; /* the file in `files` (no alignment rule) */
+    uint64_t dst;      /* byte offset of the decoded W*H frame from `out` (no alignment rule) */
+} abub_abf_frame;
+/* status[frame] after abub_abf_decode_dev: 0 = decoded.  1-3 are found identically by every wave of the frame and win;
+ * of 4-6 (found per row) the largest wins.  A refused frame may be half written. */
+#define ABUB_ABF_E_DESC 1   /* descriptor outside files_bytes / out_bytes */
+#define ABUB_ABF_E_HEADER 2 /* magic, W, H, nblk */
+#define ABUB_ABF_E_SIZE 3   /* len != computed file size */
+#define ABUB_ABF_E_WIDTH 4  /* a width above 8 */
+#define ABUB_ABF_E_ROWS 5   /* row offsets inconsistent */
+#define ABUB_ABF_E_CHECK 6  /* a row check differs */
+/* One launch per batch; every pointer is a device pointer; W, H in [1, 65535]; status[nframes] is written for every
+ * frame.  Null pointers, nframes < 0 and W or H out of range: ABUB_E_INVALID before anything touches the device. */
+int abub_abf_decode_dev(const uint8_t *files, size_t files_bytes, const abub_abf_frame *frames, int nframes, int W, int H,
+                        uint8_t *out, size_t out_bytes, int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
