@@ -398,6 +398,33 @@ def abf_decode(files, descs, W, H, out, status=None):
     return status[:n]
 
 
+def abf_encode(pixels, src, W, H, out=None, scratch=None, out_cap=None):
+    """abub_abf_encode_dev: pixels u8 (any shape; frames of W * H bytes anywhere in it), src: byte offset of each frame
+    (any alignment), out u8 (None: nframes * abub_abf_file_bound(W, H), rounded up to 16 per file; out_cap: the kernels may
+    write only that many bytes of it, default all) ->
+    (files int64 [n, 3] of (off, len, status) on the host, total, out).  File f is out[off:off + len], the bytes
+    host.abf_encode gives the frame; status: 0, ABUB_ABF_ENC_E_SRC = 1, ABUB_ABF_ENC_E_CAP = 2 (total stays true)."""
+    import numpy as np
+    _need_cuda(pixels, out, scratch)
+    L = _lib.lib()
+    offs = np.asarray(src, dtype=np.int64).reshape(-1)
+    n = len(offs)
+    dev = pixels.device
+    d_src = torch.from_numpy(np.concatenate([offs, np.zeros(1, np.int64)])).to(dev)
+    if out is None:
+        out = torch.empty((max(n, 1) * ((int(L.abub_abf_file_bound(W, H)) + 15) & ~15),), dtype=torch.uint8, device=dev)
+    need = int(L.abub_abf_encode_scratch_bytes(n, W, H))
+    if scratch is None:
+        scratch = torch.empty((max(need, 16),), dtype=torch.uint8, device=dev)
+    d_files = torch.zeros((max(n, 1), 2), dtype=torch.int64, device=dev)
+    d_total = torch.zeros((1,), dtype=torch.int64, device=dev)
+    _lib.check(L.abub_abf_encode_dev(_ptr(pixels), pixels.numel(), _ptr(d_src), n, W, H, _ptr(out), out.numel() if out_cap is None else min(int(out_cap), out.numel()),
+                                     _ptr(d_files), _ptr(d_total), _ptr(scratch), scratch.numel(), _stream()), "abub_abf_encode_dev")
+    rec = d_files.cpu().numpy()[:n]
+    files = np.stack([rec[:, 0], rec[:, 1] & 0xFFFFFFFF, rec[:, 1] >> 32], axis=1) if n else np.zeros((0, 3), np.int64)
+    return files, int(d_total.item()), out
+
+
 def match_terms(frames, frame_idx, tmpl):
     """Exact CCORR terms (abub_match_ccorr_batch_dev): frames u8 [N,H,W] (any slab of frames), frame_idx int32 [njobs]
     (frame of each job), tmpl u8 [th,tw] -> (num, wsum2), each int64 [njobs, H-th+1, W-tw+1] holding the u64 sums."""

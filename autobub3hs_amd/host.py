@@ -46,6 +46,7 @@ SIGNATURES = {
     "abh_abf_encode": (C.c_longlong, [_u8p, _i, _i, _u8p, C.c_longlong]),
     "abh_abf_decode": (_i, [_u8p, C.c_longlong, _u8p, _i, _i]),
     "abh_run_repack": (_i, [_vp, _s, _i, _i, _dp]),
+    "abh_run_repack_dev": (_i, [_vp, _s, _i, _i, _i, _dp]),
     "abh_png_walk": (_i, [_u8p, _i, _i, _i, _u32p, _i, _ip, _ip, _u8p]),
     "abh_imwrite": (_i, [_s, _u8p, _i, _i]),
     "abh_write_header": (None, [_s, _s, _i, _i]),
@@ -246,17 +247,25 @@ class Run:
                 "events_per_batch", "gpus", "frames_gpu_decoded", "frames_host_decoded", "gpudecode_s", "frames_gpu_unpacked")
         return dict(zip(keys, list(st)))
 
-    def repack(self, outdir, nthreads=16, ncams=4):
+    def repack(self, outdir, nthreads=16, ncams=4, device=None):
         """abub3hs --repack of this run (opened from a directory or an archive): every frame of cameras 0 .. ncams-1
         written in the packed format (abf_encode) to <outdir>/<event>/<image folder>/<same name>; `outdir` is the new run
-        folder, its last component the run ID.  Files that do not decode are copied as they are.  No GPU.  -> stats dict;
-        raises if anything could not be written."""
+        folder, its last component the run ID.  Files that do not decode are copied as they are.  device=None: no GPU.
+        device=N (--repack-gpu): the same files, the frames decoded and packed on that GPU (abub_abf_encode_dev); raises
+        when there is no such device.  -> stats dict; raises if anything could not be written."""
         L = lib()
-        st = (C.c_double * 6)()
-        rc = L.abh_run_repack(self._h, outdir.encode(), ncams, nthreads, st)
+        keys = ("packed", "copied", "failed", "bytes_in", "bytes_out", "seconds")
+        if device is None:
+            st = (C.c_double * 6)()
+            rc = L.abh_run_repack(self._h, outdir.encode(), ncams, nthreads, st)
+        else:
+            keys += ("frames_gpu_encoded", "frames_gpu_png_decoded", "frames_gpu_unpacked", "frames_host_decoded",
+                     "frames_host_route", "batches", "read_s", "decode_s", "encode_s", "copy_s", "write_s", "device")
+            st = (C.c_double * 18)()
+            rc = L.abh_run_repack_dev(self._h, outdir.encode(), ncams, nthreads, int(device), st)
         if rc != 0:
             raise RuntimeError(f"abh_run_repack rc={rc}: " + L.abh_last_error(self._h).decode())
-        return dict(zip(("packed", "copied", "failed", "bytes_in", "bytes_out", "seconds"), list(st)))
+        return dict(zip(keys, list(st)))
 
     def analyze(self, event, cam, maskdir=""):
         L = lib()

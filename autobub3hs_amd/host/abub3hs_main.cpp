@@ -29,7 +29,7 @@ static std::string usage()
 {
     return "Usage: abub3hs [-hzme] [-D data_series] [-c cam_mask_dir] [--debug code] -d data_dir -r run_ID -o out_dir\n"
            "       abub3hs [-hzm] [-D data_series] [-c cam_mask_dir] -d data_dir --runs ID[,ID...] | --run-list FILE -o out_dir\n"
-           "       abub3hs [-z] [-D data_series] -d data_dir -r run_ID --repack out_data_dir\n"
+           "       abub3hs [-z] [-D data_series] -d data_dir -r run_ID --repack out_data_dir [--repack-gpu]\n"
            "Run the AutoBub3hs bubble finding algorithm on a PICO run (MI355X hot path)\n\n"
            "Required arguments:\n"
            "  -d, --data_dir = Dir\t\tpath to the directory in which the run folder/file is stored\n"
@@ -60,6 +60,8 @@ static std::string usage()
            "\t\t\t\twithout an inflate (24x the PNG decode; file names stay; files that do not decode are copied); no GPU, no analysis,\n"
            "\t\t\t\tno -o; not with -e, --merge, --runs / --run-list, --gpu-shard, and not into the\n"
            "\t\t\t\tdata_dir it reads.  Analyse it with -d Dir\n"
+           "  --repack-gpu\t\t\twith --repack: decode and pack the frames on GPU 0 (the same files, byte for byte; what the\n"
+           "\t\t\t\tGPU decoders do not take is packed by host threads); an error when there is no HIP device\n"
            "Environment: ABUB_TRAIN_ON_GPU=0 trains the runs of a campaign with the host Trainer\n";
 }
 
@@ -211,7 +213,7 @@ static bool readRunList(const std::string &path, std::vector<std::string> &runs)
 int main(int argc, char **argv)
 {
     std::string dataLoc, run_number, out_dir, mask_dir, data_series, repackDir;
-    bool haveShard = false, haveRepack = false;
+    bool haveShard = false, haveRepack = false, repackGpu = false;
     int event_user = -1, debug_mode = 0, ngpus = 1, shardRank = 0, shardWorld = 1, mergeN = 0;
     bool zipped = false, mask_check = false, help = argc == 1, perEvent = false;
     bool haveRun = false, haveList = false; // -r; --runs / --run-list
@@ -286,6 +288,8 @@ int main(int argc, char **argv)
         } else if (a == "--repack" || a.rfind("--repack=", 0) == 0) {
             value(repackDir);
             haveRepack = true;
+        } else if (a == "--repack-gpu") {
+            repackGpu = true;
         } else if (a == "--per-event") {
             perEvent = true;
         } else {
@@ -296,6 +300,10 @@ int main(int argc, char **argv)
     if (help) {
         std::cout << usage() << std::endl;
         return 1;
+    }
+    if (repackGpu && !haveRepack) {
+        std::cerr << "--repack-gpu is valid only together with --repack" << std::endl;
+        return -1;
     }
     if (haveRepack) {
         // ---- --repack: the run rewritten with packed frames (abub::RepackRun); nothing else happens -----------------------
@@ -326,9 +334,12 @@ int main(int argc, char **argv)
         abub::RepackStats rs;
         int rc = 1;
         try {
-            rc = abub::RepackRun(parser.get(), zipped ? std::string() : sp.eventDir,
-                                 zipped ? std::string() : sp.eventDir + run_number + ".txt",
-                                 repackDir + "/" + run_number, sp.imageFolder, sp.numCams, threads, &rs);
+            const std::string srcDir = zipped ? std::string() : sp.eventDir;
+            const std::string srcFile = zipped ? std::string() : sp.eventDir + run_number + ".txt";
+            rc = repackGpu ? abub::RepackRunDevice(parser.get(), srcDir, srcFile, repackDir + "/" + run_number, sp.imageFolder,
+                                                   sp.numCams, threads, 0, &rs)
+                           : abub::RepackRun(parser.get(), srcDir, srcFile, repackDir + "/" + run_number, sp.imageFolder,
+                                             sp.numCams, threads, &rs);
         } catch (std::exception &e) {
             std::cerr << "repack failed: " << e.what() << std::endl;
             return -6;
@@ -340,6 +351,18 @@ int main(int argc, char **argv)
                "%.1f frames/s\n",
                rs.events, rs.packed, rs.bytesIn, rs.bytesOut, rs.copied, rs.failed, rs.total_s,
                rs.total_s > 0 ? (rs.packed + rs.copied) / rs.total_s : 0.0);
+        if (repackGpu) {
+            if (rs.device < 0)
+                printf("repack-gpu: 0 frames encoded on the GPU, %lld took the host route (no frame of a width the GPU decoders "
+                       "take)\n",
+                       rs.framesHostRoute);
+            else
+                printf("repack-gpu: %lld frames encoded on GPU %d (%lld decoded by the PNG kernel, %lld by the packed kernel, "
+                       "%lld by a host thread), %lld took the host route, %d batches; read %.2f s, upload + decode %.2f s, "
+                       "encode %.2f s, copy back %.2f s, write %.2f s\n",
+                       rs.framesGpuEncoded, rs.device, rs.framesGpuPngDecoded, rs.framesGpuUnpacked, rs.framesHostDecoded,
+                       rs.framesHostRoute, rs.batches, rs.read_s, rs.decode_s, rs.encode_s, rs.copy_s, rs.write_s);
+        }
         return rc;
     }
     if (haveList) {

@@ -166,8 +166,11 @@ int abh_abf_decode(const uint8_t *data, long long n, uint8_t *out, int W, int H)
 }
 // abub::RepackRun of a run opened with abh_run_open into the directory `dstRunDir` (its last component is the new run ID);
 // stats (may be NULL): [frames packed, copied as they are, not written, bytes of the packed frames' sources, of the packed
-// files, seconds].  Returns RepackRun's code, -1 on errors.
-int abh_run_repack(void *r, const char *dstRunDir, int ncams, int nthreads, double *stats)
+// files, seconds].  Returns RepackRun's code, -1 on errors.  abh_run_repack_dev: abub::RepackRunDevice on `device`, no
+// fall-back when there is no such device; its stats go on with [frames encoded on the GPU, of them decoded by the PNG
+// kernel, by the packed kernel, by a host thread, frames that took the host route, batches, seconds of the legs read,
+// upload + decode, encode, copy back, write, the device (-1: the whole run took the host route)] (18 values).
+static int runRepack(void *r, const char *dstRunDir, int ncams, int nthreads, int device, bool onDevice, double *stats)
 {
     Run *run = (Run *)r;
     try {
@@ -184,17 +187,30 @@ int abh_run_repack(void *r, const char *dstRunDir, int ncams, int nthreads, doub
             src = folder + "/" + (slash == std::string::npos ? folder : folder.substr(slash + 1)) + ".txt";
         }
         abub::RepackStats st;
-        const int rc = abub::RepackRun(run->parser, run->kind == 0 ? run->runFolder : std::string(), src, dstRunDir, run->imageFolder, ncams, std::max(1, nthreads), &st);
+        const std::string srcDir = run->kind == 0 ? run->runFolder : std::string();
+        const int rc = onDevice ? abub::RepackRunDevice(run->parser, srcDir, src, dstRunDir, run->imageFolder, ncams,
+                                                        std::max(1, nthreads), device, &st)
+                                : abub::RepackRun(run->parser, srcDir, src, dstRunDir, run->imageFolder, ncams, std::max(1, nthreads), &st);
         if (stats) {
-            const double v[6] = {(double)st.packed, (double)st.copied, (double)st.failed, (double)st.bytesIn, (double)st.bytesOut,
-                                 st.total_s};
-            std::memcpy(stats, v, sizeof v);
+            const double v[18] = {(double)st.packed, (double)st.copied, (double)st.failed, (double)st.bytesIn, (double)st.bytesOut,
+                                  st.total_s, (double)st.framesGpuEncoded, (double)st.framesGpuPngDecoded,
+                                  (double)st.framesGpuUnpacked, (double)st.framesHostDecoded, (double)st.framesHostRoute,
+                                  (double)st.batches, st.read_s, st.decode_s, st.encode_s, st.copy_s, st.write_s, (double)st.device};
+            std::memcpy(stats, v, (onDevice ? 18 : 6) * sizeof(double));
         }
         return rc;
     } catch (std::exception &e) {
         run->last.error = e.what();
         return -1;
     }
+}
+int abh_run_repack(void *r, const char *dstRunDir, int ncams, int nthreads, double *stats)
+{
+    return runRepack(r, dstRunDir, ncams, nthreads, -1, false, stats);
+}
+int abh_run_repack_dev(void *r, const char *dstRunDir, int ncams, int nthreads, int device, double *stats)
+{
+    return runRepack(r, dstRunDir, ncams, nthreads, device, true, stats);
 }
 
 // cv::imwrite of the debug write-out (PNG, or BMP by extension)

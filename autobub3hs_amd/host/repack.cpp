@@ -1,9 +1,15 @@
 // repack.cpp -- a run rewritten with its frames in the packed format (cv::abfEncode, DESIGN section 3, "Packed frames"): abub3hs --repack.
-// Host only: no GPU, no analysis.  Everything is read through the Parser interface, so a directory and a zip archive
-// repack alike; the result is always a directory.
+// No analysis.  Everything is read through the Parser interface, so a directory and a zip archive repack alike; the result
+// is always a directory.  RepackRun is host only (cv::imdecode + cv::abfEncode on the pool's threads); RepackRunDevice
+// (--repack-gpu) decodes the frames of the run's size with the GPU decoders and encodes them with abub_abf_encode_dev, and
+// writes the same bytes.  What both share -- the refusal to write into the run being read, the directory layout, the run's
+// event file, what becomes of a single file on a host thread, the exit status -- is one copy.
+#include <algorithm>
 #include <cerrno>
 #include <cstdio>
+#include <cstring>
 #include <fstream>
+#include <memory>
 #include <mutex>
 #include <sstream>
 #include <stdexcept>
@@ -46,14 +52,59 @@ std::string trimSlashes(std::string s)
     return s;
 }
 
-} // namespace
+// what became of one frame
+struct Outcome {
+    bool ok = false, packed = false;
+    long long in = 0, out = 0; // of a packed frame: the source file's bytes, the packed file's
+};
 
-int RepackRun(Parser *parser, const std::string &srcRunDir, const std::string &srcRunFile, const std::string &dstRunDir_,
-              const std::string &imageFolder, int numCams, int nthreads, RepackStats *stats)
+// The bytes of a source file on a host thread: decoded at whatever size the file has and packed, or, where they do not
+// decode, copied as they are (the file stays undecodable)
+Outcome packBytes(const unsigned char *data, size_t size, const std::string &path)
 {
-    const double t0 = nowMs();
-    RepackStats st;
-    const std::string dstRunDir = trimSlashes(dstRunDir_);
+    static thread_local std::vector<unsigned char> packed;
+    Outcome o;
+    const cv::Mat m = size ? cv::imdecode(data, size, 0) : cv::Mat();
+    o.packed = !m.empty() && cv::abfEncode(m.data, m.cols, m.rows, packed);
+    o.ok = o.packed ? writeFile(path, packed.data(), packed.size()) : writeFile(path, data, size);
+    o.in = (long long)size;
+    o.out = (long long)packed.size();
+    return o;
+}
+
+// One frame read through the parser and packed on this thread
+Outcome hostFrame(Parser &p, const std::string &ev, const std::string &name, const std::string &path)
+{
+    static thread_local std::vector<unsigned char> file;
+    const long long size = p.GetImageFileSize(ev, name);
+    if (size < 0 || size >= ((long long)1 << 30))
+        return Outcome();
+    file.resize((size_t)size);
+    if (size && p.ReadImageFile(ev, name, file.data(), file.size()) != size)
+        return Outcome();
+    return packBytes(file.data(), file.size(), path);
+}
+
+struct Task {
+    size_t ev;
+    std::string name;
+};
+
+// The part of a repack that is not its frames
+struct Plan {
+    std::string dstRunDir;
+    std::vector<std::string> events, dirs; // dirs[e]: where the frames of events[e] go
+    std::vector<Task> tasks;               // every frame, in event, camera and frame order
+    bool failed = false;                   // a directory or the event file could not be written
+    std::string pathOf(const Task &t) const { return dirs[t.ev] + "/" + t.name; }
+};
+
+Plan planRun(Parser *parser, const std::string &srcRunDir, const std::string &srcRunFile, const std::string &dstRunDir_,
+             const std::string &imageFolder, int numCams)
+{
+    Plan pl;
+    pl.dstRunDir = trimSlashes(dstRunDir_);
+    const std::string &dstRunDir = pl.dstRunDir;
     {
         // the files keep their names: written into the source run they would replace the frames they are read from
         struct stat a, b;
@@ -61,30 +112,25 @@ int RepackRun(Parser *parser, const std::string &srcRunDir, const std::string &s
             a.st_ino == b.st_ino)
             throw std::runtime_error("repack: " + dstRunDir + " is the run that is being read");
     }
-    std::vector<std::string> events = sortedEvents(*parser);
-    struct Task {
-        size_t ev;
-        std::string name;
-    };
-    std::vector<Task> tasks;
-    std::vector<std::string> dirs(events.size());
-    bool failed = false;
+    pl.events = sortedEvents(*parser);
+    const std::vector<std::string> &events = pl.events;
+    pl.dirs.resize(events.size());
     for (size_t e = 0; e < events.size(); ++e) {
-        dirs[e] = trimSlashes(dstRunDir + "/" + events[e] + "/" + imageFolder);
-        for (size_t at; (at = dirs[e].find("//")) != std::string::npos;)
-            dirs[e].erase(at, 1);
-        if (!makeDirs(dirs[e])) {
-            failed = true;
+        std::string &dir = pl.dirs[e];
+        dir = trimSlashes(dstRunDir + "/" + events[e] + "/" + imageFolder);
+        for (size_t at; (at = dir.find("//")) != std::string::npos;)
+            dir.erase(at, 1);
+        if (!makeDirs(dir)) {
+            pl.failed = true;
             continue;
         }
         for (int c = 0; c < numCams; ++c) {
             std::vector<std::string> names;
             parser->ParseAndSortFramesInFolder(events[e], c, names);
             for (std::string &n : names)
-                tasks.push_back(Task{e, std::move(n)});
+                pl.tasks.push_back(Task{e, std::move(n)});
         }
     }
-    st.events = (int)events.size();
 
     // ---- the run's event file: the source's bytes where there is such a file, else one line per listed event ------------
     if (makeDirs(dstRunDir)) {
@@ -102,42 +148,249 @@ int RepackRun(Parser *parser, const std::string &srcRunDir, const std::string &s
         }
         const std::string s = text.str();
         if (!s.empty() && !writeFile(dstRunDir + "/" + runId + ".txt", (const unsigned char *)s.data(), s.size()))
-            failed = true;
+            pl.failed = true;
     } else
-        failed = true;
+        pl.failed = true;
+    return pl;
+}
 
+// The frames' outcomes summed into the stats, from any thread
+struct Tally {
+    RepackStats &st;
     std::mutex mu;
-    forEachTask(parser, nthreads, tasks.size(), [&](Parser &p, size_t i) {
-        const Task &t = tasks[i];
-        static thread_local std::vector<unsigned char> file, packed;
-        const long long size = p.GetImageFileSize(events[t.ev], t.name);
-        bool ok = size >= 0 && size < ((long long)1 << 30);
-        bool isPacked = false;
-        if (ok) {
-            file.resize((size_t)size);
-            ok = !size || p.ReadImageFile(events[t.ev], t.name, file.data(), file.size()) == size;
-        }
-        if (ok) {
-            const cv::Mat m = size ? cv::imdecode(file.data(), file.size(), 0) : cv::Mat();
-            isPacked = !m.empty() && cv::abfEncode(m.data, m.cols, m.rows, packed);
-            // a file that does not decode is copied as it is: it stays undecodable
-            const std::vector<unsigned char> &outv = isPacked ? packed : file;
-            ok = writeFile(dirs[t.ev] + "/" + t.name, outv.data(), outv.size());
-        }
+    void add(const Outcome &o, bool onGpu = false)
+    {
         std::lock_guard<std::mutex> lock(mu);
-        if (!ok)
+        if (onGpu)
+            ++st.framesGpuEncoded;
+        else
+            ++st.framesHostRoute;
+        if (!o.ok)
             ++st.failed;
-        else if (isPacked) {
+        else if (o.packed) {
             ++st.packed;
-            st.bytesIn += size;
-            st.bytesOut += (long long)packed.size();
+            st.bytesIn += o.in;
+            st.bytesOut += o.out;
         } else
             ++st.copied;
+    }
+};
+
+void hostFrames(Parser *parser, const Plan &pl, int nthreads, Tally &tally)
+{
+    forEachTask(parser, nthreads, pl.tasks.size(), [&](Parser &p, size_t i) {
+        const Task &t = pl.tasks[i];
+        tally.add(hostFrame(p, pl.events[t.ev], t.name, pl.pathOf(t)));
     });
+}
+
+// The size of the first frame that decodes; false if none does
+bool firstFrameSize(Parser *parser, const Plan &pl, int &W, int &H)
+{
+    std::unique_ptr<Parser> p(parser->clone());
+    for (const Task &t : pl.tasks) {
+        cv::Mat m;
+        try {
+            if (p->GetImage(pl.events[t.ev], t.name, m) != -1 && !m.empty()) {
+                W = m.cols;
+                H = m.rows;
+                return true;
+            }
+        } catch (...) {
+        }
+    }
+    return false;
+}
+
+// The device route: the frames in batches of at most 4 per CU.  Per batch: the pool reads the files into a pinned buffer
+// (and packs, on the spot, what is no file for the GPU decoders: a frame it had to decode itself, a frame of another size,
+// a file that does not decode); upload; both decoders into a slab; abub_abf_encode_dev over the frames that are in place;
+// files and total copied back; one copy of `total` bytes into pinned memory; the pool writes the files.
+void deviceFrames(Parser *parser, const Plan &pl, int nthreads, int device, int W, int H, Tally &tally)
+{
+    RepackStats &st = tally.st;
+    HIPOK(hipSetDevice(device));
+    int ncu = 256, v = 0;
+    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && v > 0)
+        ncu = v;
+    const size_t perBatch = (size_t)4 * ncu, P = (size_t)W * H;
+    PinnedBuffer h_files, h_meta;
+    DeviceBuffer d_files, slab, d_meta, scratch;
+    PngScratch png;
+    GrowList<uint8_t> out(4096, 1, SIZE_MAX); // the packed files of a batch, on the device and in pinned memory
+    Stream stream;
+    hipStream_t cs = stream.get();
+    std::unique_ptr<Parser> sizer(parser->clone());
+
+    for (size_t i0 = 0; i0 < pl.tasks.size(); i0 += perBatch) {
+        const size_t n = std::min(perBatch, pl.tasks.size() - i0);
+        // ---- read -------------------------------------------------------------------------------------------------------
+        double t0 = nowMs();
+        std::vector<FileTask> ft(n);
+        size_t total = 0;
+        for (size_t i = 0; i < n; ++i) {
+            const Task &t = pl.tasks[i0 + i];
+            ft[i].s = (int)i;
+            planFileTask(*sizer, pl.events[t.ev], t.name, ft[i], total);
+        }
+        h_files.grow(total + 16);
+        forEachTask(parser, nthreads, n, [&](Parser &p, size_t i) {
+            const Task &t = pl.tasks[i0 + i];
+            FileTask &f = ft[i];
+            const std::string &ev = pl.events[t.ev];
+            readFileTask(p, ev, t.name, f, h_files.get(), W, H);
+            if (f.onGpu())
+                return;
+            if (f.state == FileTask::HostDecoded) { // (16-bit, colour, BMP: this thread decoded it at W x H)
+                static thread_local std::vector<unsigned char> packed;
+                Outcome o;
+                o.packed = cv::abfEncode(f.pix.data(), W, H, packed);
+                o.ok = o.packed && writeFile(pl.pathOf(t), packed.data(), packed.size());
+                o.in = f.size;
+                o.out = (long long)packed.size();
+                tally.add(o);
+            } else if (f.read) // another size, or a file that does not decode
+                tally.add(packBytes(h_files.get() + f.off, (size_t)f.size, pl.pathOf(t)));
+            else               // a file the parser does not hand out in one piece
+                tally.add(hostFrame(p, ev, t.name, pl.pathOf(t)));
+            f.pix = std::vector<uint8_t>();
+            f.state = FileTask::Other;
+        });
+        st.read_s += (nowMs() - t0) * 1e-3;
+
+        // ---- upload and decode ------------------------------------------------------------------------------------------
+        t0 = nowMs();
+        FileDescs fd;
+        buildFileDescs(ft.data(), ft.data() + n, total, fd, [&](int s, int) { return (uint64_t)s * P; });
+        std::vector<uint8_t> good(n, 0);
+        std::vector<uint64_t> src;
+        std::vector<size_t> slot;
+        if (fd.gpuFrames()) {
+            slab.grow(n * P);
+            d_files.grow(total + 16);
+            HIPOK(hipMemcpyAsync(d_files.get(), h_files.get(), total + 16, hipMemcpyHostToDevice, cs));
+            launchFileDecode(fd, d_files.get(), W, H, slab.get(), n * P, png, cs);
+            HIPOK(hipStreamSynchronize(cs));
+            long long onGpu = 0, onHost = 0;
+            finishFileDecode(fd, h_files.get(), png, slab.get(), W, H, cs, [&](int s, int) { return (size_t)s * P; },
+                             [&](int s, int) { good[s] = 1; }, onGpu, onHost);
+            st.framesGpuUnpacked += fd.unpacked;
+            st.framesGpuPngDecoded += onGpu - fd.unpacked;
+            st.framesHostDecoded += onHost;
+            for (size_t i = 0; i < n; ++i)
+                if (good[i]) {
+                    src.push_back((uint64_t)i * P);
+                    slot.push_back(i);
+                }
+        }
+        HIPOK(hipStreamSynchronize(cs));
+        st.decode_s += (nowMs() - t0) * 1e-3;
+
+        // ---- encode: [src][files][total] in one buffer; redone once when the files outgrow `out` ---------------------------
+        t0 = nowMs();
+        const size_t ng = src.size();
+        const abub_abf_file *files = nullptr;
+        uint64_t bytes = 0;
+        if (ng) {
+            const size_t metaBytes = ng * (sizeof(uint64_t) + sizeof(abub_abf_file)) + sizeof(uint64_t);
+            h_meta.grow(metaBytes);
+            d_meta.grow(metaBytes);
+            scratch.grow(abub_abf_encode_scratch_bytes((int)ng, W, H));
+            std::memcpy(h_meta.get(), src.data(), ng * sizeof(uint64_t));
+            HIPOK(hipMemcpyAsync(d_meta.get(), h_meta.get(), ng * sizeof(uint64_t), hipMemcpyHostToDevice, cs));
+            abub_abf_file *d_rec = (abub_abf_file *)(d_meta.get() + ng * sizeof(uint64_t));
+            uint64_t *d_total = (uint64_t *)(d_rec + ng);
+            files = (const abub_abf_file *)(h_meta.get() + ng * sizeof(uint64_t));
+            out.newBatch();
+            out.reserve(total + 64 * ng); // (a packed frame is about the size of its PNG)
+            for (;;) {
+                check(abub_abf_encode_dev(slab.get(), n * P, (const uint64_t *)d_meta.get(), (int)ng, W, H, out.d, out.cap(), d_rec,
+                                          d_total, scratch.get(), scratch.capacity(), cs),
+                      "abub_abf_encode_dev");
+                HIPOK(hipMemcpyAsync(h_meta.get() + ng * sizeof(uint64_t), d_rec, ng * sizeof(abub_abf_file) + sizeof(uint64_t),
+                                     hipMemcpyDeviceToHost, cs));
+                HIPOK(hipStreamSynchronize(cs));
+                std::memcpy(&bytes, files + ng, sizeof bytes);
+                if (out.fit((size_t)bytes, "repack: the packed files of a batch outgrew their buffer twice"))
+                    break;
+            }
+            st.encode_s += (nowMs() - t0) * 1e-3;
+            // ---- copy back --------------------------------------------------------------------------------------------------
+            t0 = nowMs();
+            out.toHost((size_t)bytes, cs);
+            HIPOK(hipStreamSynchronize(cs));
+            st.copy_s += (nowMs() - t0) * 1e-3;
+        }
+
+        // ---- write: the packed files, and on the host route what the decoders left (a PNG that is damaged behind its header) -
+        t0 = nowMs();
+        std::vector<size_t> fileOf(n, SIZE_MAX);
+        for (size_t g = 0; g < ng; ++g)
+            fileOf[slot[g]] = g;
+        forEachTask(parser, nthreads, n, [&](Parser &, size_t i) {
+            const Task &t = pl.tasks[i0 + i];
+            if (ft[i].state == FileTask::Other)
+                return; // (written by the thread that read it)
+            if (fileOf[i] == SIZE_MAX) {
+                tally.add(packBytes(h_files.get() + ft[i].off, (size_t)ft[i].size, pl.pathOf(t)));
+                return;
+            }
+            const abub_abf_file &r = files[fileOf[i]];
+            Outcome o;
+            o.packed = true;
+            o.ok = r.status == 0 && writeFile(pl.pathOf(t), out.h + r.off, r.len);
+            o.in = ft[i].size;
+            o.out = r.len;
+            tally.add(o, true);
+        });
+        st.write_s += (nowMs() - t0) * 1e-3;
+        ++st.batches;
+    }
+}
+
+int repackRun(Parser *parser, const std::string &srcRunDir, const std::string &srcRunFile, const std::string &dstRunDir,
+              const std::string &imageFolder, int numCams, int nthreads, int device, RepackStats *stats)
+{
+    const double t0 = nowMs();
+    RepackStats st;
+    if (device >= 0) { // (before anything is written)
+        int count = 0;
+        if (hipGetDeviceCount(&count) != hipSuccess || device >= count)
+            throw std::runtime_error("repack: no such HIP device: " + std::to_string(device) + " (" + std::to_string(std::max(count, 0)) +
+                                     " found); without --repack-gpu the run is repacked on the host");
+    }
+    const Plan pl = planRun(parser, srcRunDir, srcRunFile, dstRunDir, imageFolder, numCams);
+    st.events = (int)pl.events.size();
+    Tally tally{st, {}};
+    int W = 0, H = 0;
+    // the decoders' width gate (runbatch.cpp): a run outside it takes the host route whole
+    if (device >= 0 && firstFrameSize(parser, pl, W, H) && (W & 3) == 0 && W >= 4 && W <= 2048) {
+        st.device = device;
+        st.W = W;
+        st.H = H;
+        deviceFrames(parser, pl, nthreads, device, W, H, tally);
+    } else
+        hostFrames(parser, pl, nthreads, tally);
     st.total_s = (nowMs() - t0) * 1e-3;
     if (stats)
         *stats = st;
-    return failed || st.failed ? 1 : 0;
+    return pl.failed || st.failed ? 1 : 0;
+}
+
+} // namespace
+
+int RepackRun(Parser *parser, const std::string &srcRunDir, const std::string &srcRunFile, const std::string &dstRunDir,
+              const std::string &imageFolder, int numCams, int nthreads, RepackStats *stats)
+{
+    return repackRun(parser, srcRunDir, srcRunFile, dstRunDir, imageFolder, numCams, nthreads, -1, stats);
+}
+
+int RepackRunDevice(Parser *parser, const std::string &srcRunDir, const std::string &srcRunFile, const std::string &dstRunDir,
+                    const std::string &imageFolder, int numCams, int nthreads, int device, RepackStats *stats)
+{
+    if (device < 0)
+        throw std::runtime_error("repack: no such HIP device: " + std::to_string(device));
+    return repackRun(parser, srcRunDir, srcRunFile, dstRunDir, imageFolder, numCams, nthreads, device, stats);
 }
 
 } // namespace abub

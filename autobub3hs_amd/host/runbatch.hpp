@@ -78,6 +78,14 @@ struct RepackStats {
     long long packed = 0, copied = 0, failed = 0; // frames written in the packed format / copied as they are / not written
     long long bytesIn = 0, bytesOut = 0;          // of the packed frames: the source files, the packed files
     double total_s = 0;
+    // Of all frames (packed + copied + failed): framesGpuEncoded were packed by abub_abf_encode_dev, framesHostRoute by a
+    // host thread (or copied, or not written) -- every frame of RepackRun, and of a run outside the decoders' width gate.
+    // Of framesGpuEncoded: decoded by abub_png_decode_dev, by abub_abf_decode_dev, or by a host thread after a kernel
+    // refused the file.
+    long long framesGpuEncoded = 0, framesHostRoute = 0;
+    long long framesGpuPngDecoded = 0, framesGpuUnpacked = 0, framesHostDecoded = 0;
+    int device = -1, W = 0, H = 0, batches = 0;   // of the device route (device -1: it was not taken)
+    double read_s = 0, decode_s = 0, encode_s = 0, copy_s = 0, write_s = 0; // its legs, summed over the batches
 };
 // abub3hs --repack: every frame of every event and camera 0 .. numCams-1 that `parser` lists, written in the packed format
 // (cv::abfEncode) to <dstRunDir>/<event>/<imageFolder>/<same name> on `nthreads` threads.  A source file that does not
@@ -87,6 +95,14 @@ struct RepackStats {
 // is written, when dstRunDir is srcRunDir (the directory the parser reads; empty for an archive).
 int RepackRun(Parser *parser, const std::string &srcRunDir, const std::string &srcRunFile, const std::string &dstRunDir,
               const std::string &imageFolder, int numCams, int nthreads, RepackStats *stats);
+// abub3hs --repack --repack-gpu: the same files, byte for byte, with the frames of the run's size (that of the first frame
+// that decodes) decoded by the GPU decoders and packed by abub_abf_encode_dev on `device`, in batches of at most 4 frames
+// per CU; the pool's threads read and write the files, and pack on the spot what the decoders do not take (a frame the
+// thread had to decode itself, a frame of another size; a file that does not decode is copied).  A run whose width the
+// decoders do not take ((W & 3) == 0, 4 <= W <= 2048) goes the host route whole.  Throws, before anything is written,
+// when there is no such device: there is no silent fall-back to the host route.
+int RepackRunDevice(Parser *parser, const std::string &srcRunDir, const std::string &srcRunFile, const std::string &dstRunDir,
+                    const std::string &imageFolder, int numCams, int nthreads, int device, RepackStats *stats);
 
 // A run listed and trained, ready for detect; rc = -5 (the run cannot be read) or -7 (a camera did not train)
 struct PreparedRun {

@@ -556,6 +556,35 @@ typedef struct abub_abf_frame {
 int abub_abf_decode_dev(const uint8_t *files, size_t files_bytes, const abub_abf_frame *frames, int nframes, int W, int H,
                         uint8_t *out, size_t out_bytes, int32_t *status, void *stream);
 
+/* ---- packed frames ("ABF1") encoded on the GPU (abub_abf_enc.hip) -------------------------------------------------
+ * What cv::abfEncode does on a host thread, for a batch of resident frames: file f is exactly the bytes
+ * cv::abfEncode(pixels + src[f], W, H) writes (the host encoder is canonical: smallest width per block, zero padding
+ * bits, zero table padding).  The files lie in `out` in frame order, each at a multiple of 16: off[0] = 0,
+ * off[f + 1] = align16(off[f] + len[f]); nothing is written between them, nothing at or behind out + out_cap.
+ * *total = off + len of the last file, a true count whatever out_cap is: a caller whose buffer was too small grows it
+ * and encodes the batch again.  Four launches on `stream` (measure, place rows, place files, write: DESIGN), no host
+ * synchronisation. */
+/* the largest file of a W x H frame: 32 + 8 * H + pad4(H * ceil(W / 64)) + W * H (every block 8 bits wide);
+ * 0 if W or H is outside [1, 65535] or the value is >= 2^32 */
+size_t abub_abf_file_bound(int W, int H);
+/* bytes of `scratch` a launch over nframes frames needs; 0 for arguments abub_abf_encode_dev refuses */
+size_t abub_abf_encode_scratch_bytes(int nframes, int W, int H);
+typedef struct abub_abf_file {
+    uint64_t off;   /* of the file from `out` */
+    uint32_t len;   /* its length */
+    int32_t status; /* 0 = written */
+} abub_abf_file;
+#define ABUB_ABF_ENC_E_SRC 1 /* src + W*H > pixels_bytes: nothing read, len = 0, takes no room */
+#define ABUB_ABF_ENC_E_CAP 2 /* off + len > out_cap: off and len are true, none of the file's bytes is written */
+/* pixels: frames of W*H bytes anywhere in a buffer of pixels_bytes (the slab the decoders wrote, for one); src[nframes]:
+ * byte offset of each frame from `pixels`, any alignment; files[nframes] and *total are written for every launch with
+ * nframes > 0.  src, files, total and scratch are device memory, 8-byte aligned.  Null pointers, nframes < 0, W or H
+ * outside [1, 65535], abub_abf_file_bound(W, H) == 0, a scratch smaller than abub_abf_encode_scratch_bytes or misaligned:
+ * ABUB_E_INVALID before anything touches the device.  nframes == 0: ABUB_OK, nothing is touched. */
+int abub_abf_encode_dev(const uint8_t *pixels, size_t pixels_bytes, const uint64_t *src, int nframes, int W, int H,
+                        uint8_t *out, size_t out_cap, abub_abf_file *files, uint64_t *total, void *scratch,
+                        size_t scratch_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
