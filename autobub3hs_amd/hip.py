@@ -425,6 +425,26 @@ def abf_encode(pixels, src, W, H, out=None, scratch=None, out_cap=None):
     return files, int(d_total.item()), out
 
 
+def frames_compare(a, b, pairs, frame_bytes, a_bytes=None, b_bytes=None, results=None):
+    """abub_frames_compare_dev: a, b u8 (any shape, may be the same tensor; frames of frame_bytes bytes anywhere in them),
+    pairs: [n, 2] byte offsets of the two frames of each pair (any alignment); a_bytes / b_bytes: the sizes the kernel is
+    told (default: the tensors'); results: int32 device tensor of at least 4 * n elements, written in place (None: a new
+    one) -> int64 [n, 4] on the host: (status, ndiff, first, max_abs); status 0 or ABUB_CMP_E_RANGE = 1, first
+    0xffffffff when ndiff == 0."""
+    import numpy as np
+    _need_cuda(a, b, results)
+    offs = np.asarray(pairs, dtype=np.int64).reshape(-1, 2)
+    n = len(offs)
+    dev = a.device
+    d_pairs = torch.from_numpy(np.concatenate([offs, np.zeros((1, 2), np.int64)])).to(dev)
+    if results is None:
+        results = torch.empty((max(n, 1) * 4,), dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().abub_frames_compare_dev(_ptr(a), a.numel() if a_bytes is None else int(a_bytes), _ptr(b),
+                                                  b.numel() if b_bytes is None else int(b_bytes), _ptr(d_pairs), n,
+                                                  int(frame_bytes), _ptr(results), _stream()), "abub_frames_compare_dev")
+    return results.reshape(-1)[:4 * n].cpu().numpy().view(np.uint32).astype(np.int64).reshape(n, 4)
+
+
 def match_terms(frames, frame_idx, tmpl):
     """Exact CCORR terms (abub_match_ccorr_batch_dev): frames u8 [N,H,W] (any slab of frames), frame_idx int32 [njobs]
     (frame of each job), tmpl u8 [th,tw] -> (num, wsum2), each int64 [njobs, H-th+1, W-tw+1] holding the u64 sums."""

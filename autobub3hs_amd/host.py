@@ -47,6 +47,9 @@ SIGNATURES = {
     "abh_abf_decode": (_i, [_u8p, C.c_longlong, _u8p, _i, _i]),
     "abh_run_repack": (_i, [_vp, _s, _i, _i, _dp]),
     "abh_run_repack_dev": (_i, [_vp, _s, _i, _i, _i, _dp]),
+    "abh_run_verify": (_i, [_vp, _vp, _i, _i, _dp, C.c_char_p, _i]),
+    "abh_run_verify_dev": (_i, [_vp, _vp, _i, _i, _i, _dp, C.c_char_p, _i]),
+    "abh_run_verify_report": (_s, [_vp]),
     "abh_png_walk": (_i, [_u8p, _i, _i, _i, _u32p, _i, _ip, _ip, _u8p]),
     "abh_imwrite": (_i, [_s, _u8p, _i, _i]),
     "abh_write_header": (None, [_s, _s, _i, _i]),
@@ -266,6 +269,44 @@ class Run:
         if rc != 0:
             raise RuntimeError(f"abh_run_repack rc={rc}: " + L.abh_last_error(self._h).decode())
         return dict(zip(keys, list(st)))
+
+    def verify(self, other, nthreads=16, ncams=4, device=None):
+        """abub3hs --verify-repack: is the run `other` (another Run opened from a directory or an archive) pixel for pixel
+        this one?  Every frame this run lists for cameras 0 .. ncams-1 gets one verdict: same (identical pixels, the other
+        file is a packed frame), same_not_packed, copied (this file does not decode, the other has its bytes), and the
+        failures differ, missing, undecodable; a frame or an event only `other` lists is extra, a failure too.
+        device=None: host threads (cv::imdecode + memcmp).  device=N (--verify-gpu): the same answer, the frames decoded on
+        both sides and compared (abub_frames_compare_dev) on that GPU; raises when there is no such device.
+        -> dict: rc (0 = verified, 1 = something failed), the counters, event_file ("same", "differs", "missing", "not
+        compared"), the device route's counters and legs (device -1: it was not taken), and findings: every failure and
+        every same_not_packed frame in task order, then the extras and the event file, each a dict of event, name, verdict,
+        ndiff, x, y, max_abs (and w, h, other_w, other_h where the sizes differ)."""
+        L = lib()
+        st = (C.c_double * 25)()
+        cap = 1 << 16
+        buf = C.create_string_buffer(cap)
+        if device is None:
+            rc = L.abh_run_verify(self._h, other._h, ncams, nthreads, st, buf, cap)
+        else:
+            rc = L.abh_run_verify_dev(self._h, other._h, ncams, nthreads, int(device), st, buf, cap)
+        if rc not in (0, 1):
+            raise RuntimeError(f"abh_run_verify rc={rc}: " + L.abh_last_error(self._h).decode())
+        text = buf.value if st[11] < cap else L.abh_run_verify_report(self._h)
+        keys = ("events", "frames", "same", "same_not_packed", "copied", "differ", "missing", "undecodable", "extra")
+        res = {"rc": rc, **{k: int(v) for k, v in zip(keys, list(st))}}
+        res["event_file"] = ("same", "differs", "missing", "not compared")[int(st[9])]
+        res["seconds"] = st[10]
+        keys = ("frames_kernel", "frames_host_route", "src_gpu_png_decoded", "src_gpu_unpacked", "src_host_decoded",
+                "other_gpu_png_decoded", "other_gpu_unpacked", "other_host_decoded", "batches")
+        res.update({k: int(v) for k, v in zip(keys, list(st)[12:21])})
+        res.update(read_s=st[21], decode_s=st[22], compare_s=st[23], device=int(st[24]))
+        cols = ("ndiff", "x", "y", "max_abs", "w", "h", "other_w", "other_h")
+        res["findings"] = []
+        for line in text.decode().split("\n"):
+            if line:
+                f = line.split("\t")
+                res["findings"].append(dict(event=f[0], name=f[1], verdict=f[2], **{k: int(v) for k, v in zip(cols, f[3:])}))
+        return res
 
     def analyze(self, event, cam, maskdir=""):
         L = lib()

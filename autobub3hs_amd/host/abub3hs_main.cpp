@@ -30,6 +30,7 @@ static std::string usage()
     return "Usage: abub3hs [-hzme] [-D data_series] [-c cam_mask_dir] [--debug code] -d data_dir -r run_ID -o out_dir\n"
            "       abub3hs [-hzm] [-D data_series] [-c cam_mask_dir] -d data_dir --runs ID[,ID...] | --run-list FILE -o out_dir\n"
            "       abub3hs [-z] [-D data_series] -d data_dir -r run_ID --repack out_data_dir [--repack-gpu]\n"
+           "       abub3hs [-z] [-D data_series] -d data_dir -r run_ID --verify-repack other_data_dir [--verify-gpu]\n"
            "Run the AutoBub3hs bubble finding algorithm on a PICO run (MI355X hot path)\n\n"
            "Required arguments:\n"
            "  -d, --data_dir = Dir\t\tpath to the directory in which the run folder/file is stored\n"
@@ -62,6 +63,13 @@ static std::string usage()
            "\t\t\t\tdata_dir it reads.  Analyse it with -d Dir\n"
            "  --repack-gpu\t\t\twith --repack: decode and pack the frames on GPU 0 (the same files, byte for byte; what the\n"
            "\t\t\t\tGPU decoders do not take is packed by host threads); an error when there is no HIP device\n"
+           "  --verify-repack = Dir\t\tcompare the run with its copy Dir/<run_ID>/ (what --repack Dir wrote), frame by frame: every\n"
+           "\t\t\t\tframe decoded on both sides and compared pixel for pixel, missing and extra frames and events,\n"
+           "\t\t\t\tthe event file; one line per finding (the first 20) and a summary; exit status 0 = verified,\n"
+           "\t\t\t\t1 = something failed; no analysis, no -o; not with -e, --merge, --runs / --run-list, --gpu-shard;\n"
+           "\t\t\t\twith --repack Dir (the same Dir): repack first, then verify\n"
+           "  --verify-gpu\t\t\twith --verify-repack: decode both sides and compare them on GPU 0 (the same findings and\n"
+           "\t\t\t\tcounters); an error when there is no HIP device\n"
            "Environment: ABUB_TRAIN_ON_GPU=0 trains the runs of a campaign with the host Trainer\n";
 }
 
@@ -212,8 +220,8 @@ static bool readRunList(const std::string &path, std::vector<std::string> &runs)
 
 int main(int argc, char **argv)
 {
-    std::string dataLoc, run_number, out_dir, mask_dir, data_series, repackDir;
-    bool haveShard = false, haveRepack = false, repackGpu = false;
+    std::string dataLoc, run_number, out_dir, mask_dir, data_series, repackDir, verifyDir;
+    bool haveShard = false, haveRepack = false, repackGpu = false, haveVerify = false, verifyGpu = false;
     int event_user = -1, debug_mode = 0, ngpus = 1, shardRank = 0, shardWorld = 1, mergeN = 0;
     bool zipped = false, mask_check = false, help = argc == 1, perEvent = false;
     bool haveRun = false, haveList = false; // -r; --runs / --run-list
@@ -290,6 +298,11 @@ int main(int argc, char **argv)
             haveRepack = true;
         } else if (a == "--repack-gpu") {
             repackGpu = true;
+        } else if (a == "--verify-repack" || a.rfind("--verify-repack=", 0) == 0) {
+            value(verifyDir);
+            haveVerify = true;
+        } else if (a == "--verify-gpu") {
+            verifyGpu = true;
         } else if (a == "--per-event") {
             perEvent = true;
         } else {
@@ -305,32 +318,57 @@ int main(int argc, char **argv)
         std::cerr << "--repack-gpu is valid only together with --repack" << std::endl;
         return -1;
     }
-    if (haveRepack) {
-        // ---- --repack: the run rewritten with packed frames (abub::RepackRun); nothing else happens -----------------------
+    if (verifyGpu && !haveVerify) {
+        std::cerr << "--verify-gpu is valid only together with --verify-repack" << std::endl;
+        return -1;
+    }
+    if (haveRepack || haveVerify) {
+        // ---- --repack: the run rewritten with packed frames (abub::RepackRun); --verify-repack: the run compared with such
+        // a copy (abub::VerifyRun); with both, one after the other; nothing else happens ---------------------------------------
         const char *bad = mergeN > 0 ? "--merge" : haveList ? "--runs / --run-list" : haveShard ? "--gpu-shard"
                           : event_user >= 0 ? "-e/--event" : nullptr;
         if (bad) {
-            std::cerr << "--repack cannot be combined with " << bad << std::endl;
+            std::cerr << (haveRepack ? "--repack" : "--verify-repack") << " cannot be combined with " << bad << std::endl;
             return -1;
         }
-        if (dataLoc.empty() || run_number.empty() || repackDir.empty()) {
+        if (haveRepack && (dataLoc.empty() || run_number.empty() || repackDir.empty())) {
             std::cerr << "--repack needs --data_dir, --run_id and the directory to write to" << std::endl;
             return -1;
         }
-        const abub::RunSpec sp = runSpec(dataLoc, data_series, run_number, zipped);
+        if (haveVerify && (dataLoc.empty() || run_number.empty() || verifyDir.empty())) {
+            std::cerr << "--verify-repack needs --data_dir, --run_id and the directory of the copy" << std::endl;
+            return -1;
+        }
+        if (haveRepack && haveVerify && repackDir != verifyDir) {
+            std::cerr << "--repack and --verify-repack together must name the same directory" << std::endl;
+            return -1;
+        }
+    }
+    // the run of a RunSpec through its parser; null (and the -5 message) when it cannot be read
+    auto openRun = [&](const abub::RunSpec &sp) {
         std::unique_ptr<Parser> parser;
         try {
-            if (zipped)
+            if (sp.zipped)
                 parser.reset(new ZipParser(sp.eventDir, sp.imageFolder, sp.imageFormat));
             else
                 parser.reset(new RawParser(sp.eventDir, sp.imageFolder, sp.imageFormat));
         } catch (...) {
             std::cerr << "Failed to read the images from run " << run_number << "." << std::endl;
-            return -5;
         }
+        return parser;
+    };
+    auto poolThreads = [&]() {
         int threads = std::min(usableCores(), 128);
         if (const char *t = getenv("ABUB_THREADS"))
             threads = std::max(1, atoi(t));
+        return threads;
+    };
+    if (haveRepack) {
+        const abub::RunSpec sp = runSpec(dataLoc, data_series, run_number, zipped);
+        const std::unique_ptr<Parser> parser = openRun(sp);
+        if (!parser)
+            return -5;
+        const int threads = poolThreads();
         abub::RepackStats rs;
         int rc = 1;
         try {
@@ -362,6 +400,51 @@ int main(int argc, char **argv)
                        "encode %.2f s, copy back %.2f s, write %.2f s\n",
                        rs.framesGpuEncoded, rs.device, rs.framesGpuPngDecoded, rs.framesGpuUnpacked, rs.framesHostDecoded,
                        rs.framesHostRoute, rs.batches, rs.read_s, rs.decode_s, rs.encode_s, rs.copy_s, rs.write_s);
+        }
+        if (!haveVerify || rc != 0)
+            return rc;
+    }
+    if (haveVerify) {
+        const abub::RunSpec sp = runSpec(dataLoc, data_series, run_number, zipped);
+        const abub::RunSpec other = runSpec(verifyDir, data_series, run_number, false);
+        const std::unique_ptr<Parser> parser = openRun(sp), copy = parser ? openRun(other) : nullptr;
+        if (!parser || !copy)
+            return -5;
+        abub::VerifyStats vs;
+        std::vector<abub::VerifyFinding> findings;
+        int rc = 1;
+        try {
+            const std::string srcFile = zipped ? std::string() : sp.eventDir + run_number + ".txt";
+            const std::string otherFile = other.eventDir + run_number + ".txt";
+            rc = verifyGpu ? abub::VerifyRunDevice(parser.get(), copy.get(), srcFile, otherFile, sp.numCams, poolThreads(), 0, &vs, &findings)
+                           : abub::VerifyRun(parser.get(), copy.get(), srcFile, otherFile, sp.numCams, poolThreads(), &vs, &findings);
+        } catch (std::exception &e) {
+            std::cerr << "verify failed: " << e.what() << std::endl;
+            return -6;
+        } catch (...) { // (the parsers throw their status codes)
+            std::cerr << "Failed to read the images from run " << run_number << "." << std::endl;
+            return -5;
+        }
+        const size_t shown = std::min<size_t>(findings.size(), 20);
+        for (size_t i = 0; i < shown; ++i)
+            printf("verify: %s\n", findings[i].text().c_str());
+        if (findings.size() > shown)
+            printf("... and %zu more\n", findings.size() - shown);
+        printf("verify: %d events, %lld frames: %lld same, %lld same but not packed, %lld copied, %lld differ, %lld missing, "
+               "%lld undecodable, %lld extra; event file %s; %.2f s, %.1f frames/s\n",
+               vs.events, vs.frames, vs.same, vs.sameNotPacked, vs.copied, vs.differ, vs.missing, vs.undecodable, vs.extra,
+               vs.eventFileName(), vs.total_s, vs.total_s > 0 ? vs.frames / vs.total_s : 0.0);
+        if (verifyGpu) {
+            if (vs.device < 0)
+                printf("verify-gpu: 0 frames compared on the GPU, %lld took the host route (no frame of a width the GPU decoders "
+                       "take)\n",
+                       vs.framesHostRoute);
+            else
+                printf("verify-gpu: %lld frames compared on GPU %d (the source's decoded: %lld by the PNG kernel, %lld by the packed "
+                       "kernel, %lld by a host thread; the copy's: %lld, %lld, %lld), %lld took the host route, %d batches; read %.2f s, "
+                       "upload + decode %.2f s, compare %.2f s\n",
+                       vs.framesKernel, vs.device, vs.srcGpuPngDecoded, vs.srcGpuUnpacked, vs.srcHostDecoded, vs.otherGpuPngDecoded,
+                       vs.otherGpuUnpacked, vs.otherHostDecoded, vs.framesHostRoute, vs.batches, vs.read_s, vs.decode_s, vs.compare_s);
         }
         return rc;
     }

@@ -170,6 +170,17 @@ int abh_abf_decode(const uint8_t *data, long long n, uint8_t *out, int W, int H)
 // fall-back when there is no such device; its stats go on with [frames encoded on the GPU, of them decoded by the PNG
 // kernel, by the packed kernel, by a host thread, frames that took the host route, batches, seconds of the legs read,
 // upload + decode, encode, copy back, write, the device (-1: the whole run took the host route)] (18 values).
+// the event file of a directory run: <run>/<runID>.txt; empty for an archive
+static std::string eventFileOf(const Run &run)
+{
+    if (run.kind != 0)
+        return std::string();
+    std::string folder = run.runFolder;
+    while (folder.size() > 1 && folder.back() == '/')
+        folder.pop_back();
+    const size_t slash = folder.find_last_of('/');
+    return folder + "/" + (slash == std::string::npos ? folder : folder.substr(slash + 1)) + ".txt";
+}
 static int runRepack(void *r, const char *dstRunDir, int ncams, int nthreads, int device, bool onDevice, double *stats)
 {
     Run *run = (Run *)r;
@@ -178,14 +189,7 @@ static int runRepack(void *r, const char *dstRunDir, int ncams, int nthreads, in
             run->last.error = "repack: not a run opened from a directory or an archive";
             return -1;
         }
-        std::string src; // the event file of a directory run: <run>/<runID>.txt
-        if (run->kind == 0) {
-            std::string folder = run->runFolder;
-            while (folder.size() > 1 && folder.back() == '/')
-                folder.pop_back();
-            const size_t slash = folder.find_last_of('/');
-            src = folder + "/" + (slash == std::string::npos ? folder : folder.substr(slash + 1)) + ".txt";
-        }
+        const std::string src = eventFileOf(*run);
         abub::RepackStats st;
         const std::string srcDir = run->kind == 0 ? run->runFolder : std::string();
         const int rc = onDevice ? abub::RepackRunDevice(run->parser, srcDir, src, dstRunDir, run->imageFolder, ncams,
@@ -211,6 +215,71 @@ int abh_run_repack(void *r, const char *dstRunDir, int ncams, int nthreads, doub
 int abh_run_repack_dev(void *r, const char *dstRunDir, int ncams, int nthreads, int device, double *stats)
 {
     return runRepack(r, dstRunDir, ncams, nthreads, device, true, stats);
+}
+
+// abub::VerifyRun of two runs opened with abh_run_open: is `other` pixel for pixel the run `src`?  stats (may be NULL, 25
+// values): [events, frames, same, same but not packed, copied, differ, missing, undecodable, extra, the event file (0 same,
+// 1 differs, 2 missing, 3 not compared), seconds, the report's length; of the device route: frames compared by the kernel,
+// frames that took the host route, the source's frames decoded by the PNG kernel, by the packed kernel, by a host thread,
+// the other run's likewise, batches, seconds of the legs read, upload + decode, compare, the device (-1: it was not
+// taken)].  report (may be NULL): one line per finding, "event\tname\tverdict\tndiff\tx\ty\tmax_abs\tw\th\tother_w\tother_h\n",
+// cut at report_cap - 1 characters; the whole text stays with `src` for abh_run_verify_report.  Returns VerifyRun's code, -1
+// on errors.  abh_run_verify_dev: abub::VerifyRunDevice on `device`, no fall-back when there is no such device.
+static int runVerify(void *a, void *b, int ncams, int nthreads, int device, bool onDevice, double *stats, char *report, int report_cap)
+{
+    Run *run = (Run *)a, *other = (Run *)b;
+    try {
+        if (!other || run->kind < 0 || other->kind < 0) {
+            run->last.error = "verify: not two runs opened from a directory or an archive";
+            return -1;
+        }
+        abub::VerifyStats st;
+        std::vector<abub::VerifyFinding> findings;
+        const int rc = onDevice ? abub::VerifyRunDevice(run->parser, other->parser, eventFileOf(*run), eventFileOf(*other), ncams,
+                                                        std::max(1, nthreads), device, &st, &findings)
+                                : abub::VerifyRun(run->parser, other->parser, eventFileOf(*run), eventFileOf(*other), ncams,
+                                                  std::max(1, nthreads), &st, &findings);
+        std::string &text = run->frames_of_last_query;
+        text.clear();
+        for (const abub::VerifyFinding &f : findings)
+            text += f.event + "\t" + f.name + "\t" + f.verdictName() + "\t" + std::to_string(f.ndiff) + "\t" + std::to_string(f.x) + "\t" +
+                    std::to_string(f.y) + "\t" + std::to_string(f.maxAbs) + "\t" + std::to_string(f.w) + "\t" + std::to_string(f.h) + "\t" +
+                    std::to_string(f.otherW) + "\t" + std::to_string(f.otherH) + "\n";
+        if (report && report_cap > 0) {
+            const size_t n = std::min(text.size(), (size_t)report_cap - 1);
+            std::memcpy(report, text.data(), n);
+            report[n] = 0;
+        }
+        if (stats) {
+            const double v[25] = {(double)st.events, (double)st.frames, (double)st.same, (double)st.sameNotPacked, (double)st.copied,
+                                  (double)st.differ, (double)st.missing, (double)st.undecodable, (double)st.extra, (double)st.eventFile,
+                                  st.total_s, (double)text.size(), (double)st.framesKernel, (double)st.framesHostRoute,
+                                  (double)st.srcGpuPngDecoded, (double)st.srcGpuUnpacked, (double)st.srcHostDecoded,
+                                  (double)st.otherGpuPngDecoded, (double)st.otherGpuUnpacked, (double)st.otherHostDecoded,
+                                  (double)st.batches, st.read_s, st.decode_s, st.compare_s, (double)st.device};
+            std::memcpy(stats, v, sizeof v);
+        }
+        return rc;
+    } catch (std::exception &e) {
+        run->last.error = e.what();
+        return -1;
+    } catch (...) { // (the parsers throw their status codes)
+        run->last.error = "verify: a run could not be read";
+        return -1;
+    }
+}
+int abh_run_verify(void *src, void *other, int ncams, int nthreads, double *stats, char *report, int report_cap)
+{
+    return runVerify(src, other, ncams, nthreads, -1, false, stats, report, report_cap);
+}
+int abh_run_verify_dev(void *src, void *other, int ncams, int nthreads, int device, double *stats, char *report, int report_cap)
+{
+    return runVerify(src, other, ncams, nthreads, device, true, stats, report, report_cap);
+}
+// the whole report of the last abh_run_verify[_dev] on `src` (valid until the next query on it)
+const char *abh_run_verify_report(void *src)
+{
+    return ((Run *)src)->frames_of_last_query.c_str();
 }
 
 // cv::imwrite of the debug write-out (PNG, or BMP by extension)

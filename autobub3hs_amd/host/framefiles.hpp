@@ -27,10 +27,10 @@
 
 namespace abub {
 
-// fn(parser, i) for every i < n on up to `nthreads` threads, each with its own clone of `parser`.  The first exception is
-// re-thrown once every thread has been joined (the others stop at their next task).
-template <class Fn>
-void forEachTask(Parser *parser, int nthreads, size_t n, const Fn &fn)
+// fn(state, i) for every i < n on up to `nthreads` threads, each with a state of its own from make().  The first exception
+// is re-thrown once every thread has been joined (the others stop at their next task).
+template <class Make, class Fn>
+void forEachTaskWith(int nthreads, size_t n, const Make &make, const Fn &fn)
 {
     std::atomic<size_t> next{0};
     std::mutex errMu;
@@ -39,9 +39,9 @@ void forEachTask(Parser *parser, int nthreads, size_t n, const Fn &fn)
     for (int t = 0; t < std::max(1, (int)std::min<size_t>(nthreads, n)); ++t)
         th.emplace_back([&]() {
             try {
-                std::unique_ptr<Parser> p(parser->clone());
+                auto state = make();
                 for (size_t i; (i = next.fetch_add(1)) < n;)
-                    fn(*p, i);
+                    fn(state, i);
             } catch (...) {
                 std::lock_guard<std::mutex> lock(errMu);
                 if (!err)
@@ -53,6 +53,15 @@ void forEachTask(Parser *parser, int nthreads, size_t n, const Fn &fn)
         t.join();
     if (err)
         std::rethrow_exception(err);
+}
+
+// fn(parser, i) for every i < n, each thread with its own clone of `parser`
+template <class Fn>
+void forEachTask(Parser *parser, int nthreads, size_t n, const Fn &fn)
+{
+    forEachTaskWith(
+        nthreads, n, [&]() { return std::unique_ptr<Parser>(parser->clone()); },
+        [&](std::unique_ptr<Parser> &p, size_t i) { fn(*p, i); });
 }
 
 // One frame to be read: where it goes is decided by the caller (s, f); `state` says what became of it

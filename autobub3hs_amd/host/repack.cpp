@@ -19,6 +19,7 @@
 #include "driver.hpp"
 #include "framefiles.hpp"
 #include "runbatch.hpp"
+#include "runframes.hpp"
 
 namespace abub {
 
@@ -43,13 +44,6 @@ bool writeFile(const std::string &path, const unsigned char *data, size_t n)
         return false;
     const bool ok = fwrite(data, 1, n, f) == n;
     return fclose(f) == 0 && ok;
-}
-
-std::string trimSlashes(std::string s)
-{
-    while (s.size() > 1 && s.back() == '/')
-        s.pop_back();
-    return s;
 }
 
 // what became of one frame
@@ -85,10 +79,7 @@ Outcome hostFrame(Parser &p, const std::string &ev, const std::string &name, con
     return packBytes(file.data(), file.size(), path);
 }
 
-struct Task {
-    size_t ev;
-    std::string name;
-};
+using Task = FrameTask;
 
 // The part of a repack that is not its frames
 struct Plan {
@@ -124,12 +115,7 @@ Plan planRun(Parser *parser, const std::string &srcRunDir, const std::string &sr
             pl.failed = true;
             continue;
         }
-        for (int c = 0; c < numCams; ++c) {
-            std::vector<std::string> names;
-            parser->ParseAndSortFramesInFolder(events[e], c, names);
-            for (std::string &n : names)
-                pl.tasks.push_back(Task{e, std::move(n)});
-        }
+        appendEventFrames(*parser, events[e], e, numCams, pl.tasks);
     }
 
     // ---- the run's event file: the source's bytes where there is such a file, else one line per listed event ------------
@@ -184,24 +170,6 @@ void hostFrames(Parser *parser, const Plan &pl, int nthreads, Tally &tally)
     });
 }
 
-// The size of the first frame that decodes; false if none does
-bool firstFrameSize(Parser *parser, const Plan &pl, int &W, int &H)
-{
-    std::unique_ptr<Parser> p(parser->clone());
-    for (const Task &t : pl.tasks) {
-        cv::Mat m;
-        try {
-            if (p->GetImage(pl.events[t.ev], t.name, m) != -1 && !m.empty()) {
-                W = m.cols;
-                H = m.rows;
-                return true;
-            }
-        } catch (...) {
-        }
-    }
-    return false;
-}
-
 // The device route: the frames in batches of at most 4 per CU.  Per batch: the pool reads the files into a pinned buffer
 // (and packs, on the spot, what is no file for the GPU decoders: a frame it had to decode itself, a frame of another size,
 // a file that does not decode); upload; both decoders into a slab; abub_abf_encode_dev over the frames that are in place;
@@ -210,10 +178,7 @@ void deviceFrames(Parser *parser, const Plan &pl, int nthreads, int device, int 
 {
     RepackStats &st = tally.st;
     HIPOK(hipSetDevice(device));
-    int ncu = 256, v = 0;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && v > 0)
-        ncu = v;
-    const size_t perBatch = (size_t)4 * ncu, P = (size_t)W * H;
+    const size_t perBatch = framesPerBatch(device), P = (size_t)W * H;
     PinnedBuffer h_files, h_meta;
     DeviceBuffer d_files, slab, d_meta, scratch;
     PngScratch png;
@@ -353,18 +318,13 @@ int repackRun(Parser *parser, const std::string &srcRunDir, const std::string &s
 {
     const double t0 = nowMs();
     RepackStats st;
-    if (device >= 0) { // (before anything is written)
-        int count = 0;
-        if (hipGetDeviceCount(&count) != hipSuccess || device >= count)
-            throw std::runtime_error("repack: no such HIP device: " + std::to_string(device) + " (" + std::to_string(std::max(count, 0)) +
-                                     " found); without --repack-gpu the run is repacked on the host");
-    }
+    if (device >= 0) // (before anything is written)
+        requireDevice(device, "repack", "; without --repack-gpu the run is repacked on the host");
     const Plan pl = planRun(parser, srcRunDir, srcRunFile, dstRunDir, imageFolder, numCams);
     st.events = (int)pl.events.size();
     Tally tally{st, {}};
     int W = 0, H = 0;
-    // the decoders' width gate (runbatch.cpp): a run outside it takes the host route whole
-    if (device >= 0 && firstFrameSize(parser, pl, W, H) && (W & 3) == 0 && W >= 4 && W <= 2048) {
+    if (device >= 0 && firstFrameSize(parser, pl.events, pl.tasks, W, H) && decodersTakeWidth(W)) {
         st.device = device;
         st.W = W;
         st.H = H;

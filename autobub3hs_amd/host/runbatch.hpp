@@ -104,6 +104,56 @@ int RepackRun(Parser *parser, const std::string &srcRunDir, const std::string &s
 int RepackRunDevice(Parser *parser, const std::string &srcRunDir, const std::string &srcRunFile, const std::string &dstRunDir,
                     const std::string &imageFolder, int numCams, int nthreads, int device, RepackStats *stats);
 
+// What verify says about one frame, an extra frame or event, or the event file
+struct VerifyFinding {
+    enum Verdict { Same, SameNotPacked, Copied, Differ, Missing, Undecodable, Extra, EventFileDiffers, EventFileMissing };
+    int verdict = Same;
+    std::string event, name; // name: the frame's file; empty for an extra event; the event file's name
+    long long ndiff = 0;     // Differ with equal sizes: pixels that differ, the first of them in raster order, max |a - b|
+    int x = -1, y = -1, maxAbs = 0;
+    int w = 0, h = 0, otherW = 0, otherH = 0; // Differ with different sizes: the source's, the other run's (else 0)
+    bool failure() const { return verdict != Same && verdict != SameNotPacked && verdict != Copied; }
+    const char *verdictName() const; // "same", "same_not_packed", "copied", "differ", "missing", "undecodable", "extra",
+                                     // "event_file_differs", "event_file_missing"
+    std::string text() const;        // "3/cam1_image41.png: differ: 37 pixels, first at (x=12, y=3), max |a-b| = 5"
+};
+struct VerifyStats {
+    enum EventFile { FileSame = 0, FileDiffers = 1, FileMissing = 2, FileNotCompared = 3 };
+    int events = 0;          // of the source
+    long long frames = 0;    // of the source: same + sameNotPacked + copied + differ + missing + undecodable
+    long long same = 0, sameNotPacked = 0, copied = 0, differ = 0, missing = 0, undecodable = 0, extra = 0;
+    int eventFile = FileNotCompared;
+    double total_s = 0;
+    // Of the device route (device -1: it was not taken).  Of `frames`: framesKernel were compared by
+    // abub_frames_compare_dev, framesHostRoute by a host thread.  Of the frames the decoders were given, per side: by
+    // abub_png_decode_dev, by abub_abf_decode_dev, or by a host thread (a file the kernels do not take or refused).
+    long long framesKernel = 0, framesHostRoute = 0;
+    long long srcGpuPngDecoded = 0, srcGpuUnpacked = 0, srcHostDecoded = 0;
+    long long otherGpuPngDecoded = 0, otherGpuUnpacked = 0, otherHostDecoded = 0;
+    int device = -1, W = 0, H = 0, batches = 0;
+    double read_s = 0, decode_s = 0, compare_s = 0; // its legs, summed over the batches
+    const char *eventFileName() const;              // "same", "differs", "missing", "not compared"
+};
+// abub3hs --verify-repack: is the run `other` reads, pixel for pixel, the run `src` reads?  The source is the authority:
+// every frame it lists for cameras 0 .. numCams-1 gets one verdict, in event, camera and frame order, on `nthreads`
+// threads; both files are decoded by the host decoder (cv::imdecode) and compared with memcmp.  same: identical pixels
+// and the other file is a packed frame; same_not_packed: identical pixels, another format; copied: the source does not
+// decode and the other file has its bytes; differ, missing, undecodable: failures.  A frame or an event only the other
+// run lists is `extra`, a failure.  The event files srcRunFile and otherRunFile are compared byte for byte (not compared
+// when one of the names is empty or the source's cannot be read).  `findings` (may be NULL) gets every failure and every
+// same_not_packed frame in task order, then the extras, then the event file if it fails.  No GPU.  Returns 0 if nothing
+// failed, else 1.
+int VerifyRun(Parser *src, Parser *other, const std::string &srcRunFile, const std::string &otherRunFile, int numCams, int nthreads,
+              VerifyStats *stats, std::vector<VerifyFinding> *findings);
+// abub3hs --verify-repack --verify-gpu: the same verdicts, findings and counters.  The frames of the run's size (that of
+// the source's first frame that decodes) are decoded on both sides by the GPU decoders on `device`, in batches of at most
+// 4 frames per CU (ABUB_VERIFY_BATCH=n: of n), and compared by abub_frames_compare_dev; every other frame (a file that does
+// not decode, another size, a file the parser does not hand out) gets its verdict from a host thread as in VerifyRun.  A
+// run whose width the decoders do not take, or without a frame that decodes, goes the host route whole.  Throws, before
+// anything else, when there is no such device: there is no silent fall-back to the host route.
+int VerifyRunDevice(Parser *src, Parser *other, const std::string &srcRunFile, const std::string &otherRunFile, int numCams,
+                    int nthreads, int device, VerifyStats *stats, std::vector<VerifyFinding> *findings);
+
 // A run listed and trained, ready for detect; rc = -5 (the run cannot be read) or -7 (a camera did not train)
 struct PreparedRun {
     std::unique_ptr<Parser> parser;

@@ -585,6 +585,29 @@ int abub_abf_encode_dev(const uint8_t *pixels, size_t pixels_bytes, const uint64
                         uint8_t *out, size_t out_cap, abub_abf_file *files, uint64_t *total, void *scratch,
                         size_t scratch_bytes, void *stream);
 
+/* ---- resident frames compared byte for byte (abub_compare.hip) ------------------------------------------------------
+ * What memcmp of two decoded frames, and a byte loop behind it, does on a host thread, for a batch of resident frames:
+ * results[p] says how many of the frame_bytes bytes at a + pairs[p].a and b + pairs[p].b differ, where the first one is
+ * and how far apart the two sides get.  The check of a repacked run against its source (abub3hs --verify-repack
+ * --verify-gpu; verdicts and mapping: DESIGN section 3, "Verifying a repacked run").  Two launches on `stream` (the
+ * records' initial state, then pairs x 16 KiB tiles), no host synchronisation, no allocation; a tile without a
+ * difference issues no atomic, and the three atomics of one with a difference commute: the records are deterministic. */
+typedef struct abub_cmp_pair { uint64_t a, b; } abub_cmp_pair;   /* byte offsets of the two frames from `a` and `b`; no alignment rule */
+typedef struct abub_cmp_result {
+    uint32_t status;  /* 0, or ABUB_CMP_E_RANGE */
+    uint32_t ndiff;   /* bytes that differ */
+    uint32_t first;   /* lowest index of a differing byte; 0xffffffff when ndiff == 0 */
+    uint32_t max_abs; /* largest |a[i] - b[i]|; 0 when ndiff == 0 */
+} abub_cmp_result;
+#define ABUB_CMP_E_RANGE 1 /* a + frame_bytes > a_bytes or b + frame_bytes > b_bytes: nothing of the pair is read; ndiff 0, first 0xffffffff, max_abs 0 */
+/* Every pointer is a device pointer; pairs and results are 8-byte aligned; a and b may be the same buffer; frame_bytes in
+ * [1, 2^32 - 2].  results[npairs] is written in full by every call with npairs > 0, whatever it held before.  Frames
+ * whose addresses are congruent mod 16 are read 16 bytes at a time; any other combination is as exact, and slower.  Null
+ * pointers, npairs < 0, frame_bytes out of range or a misaligned pairs / results: ABUB_E_INVALID before anything touches
+ * the device.  npairs == 0: ABUB_OK, nothing is touched. */
+int abub_frames_compare_dev(const uint8_t *a, size_t a_bytes, const uint8_t *b, size_t b_bytes, const abub_cmp_pair *pairs,
+                            int npairs, size_t frame_bytes, abub_cmp_result *results, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
