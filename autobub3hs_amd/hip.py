@@ -425,6 +425,30 @@ def abf_encode(pixels, src, W, H, out=None, scratch=None, out_cap=None):
     return files, int(d_total.item()), out
 
 
+def png_encode(pixels, src, W, H, out=None, scratch=None, out_cap=None):
+    """abub_png_encode_dev: the arguments and results of abf_encode; file f is out[off:off + len], the canonical Huffman-only
+    PNG host.png_huff_encode gives the frame (out=None: nframes * abub_png_file_bound(W, H), rounded up to 16 per file)."""
+    import numpy as np
+    _need_cuda(pixels, out, scratch)
+    L = _lib.lib()
+    offs = np.asarray(src, dtype=np.int64).reshape(-1)
+    n = len(offs)
+    dev = pixels.device
+    d_src = torch.from_numpy(np.concatenate([offs, np.zeros(1, np.int64)])).to(dev)
+    if out is None:
+        out = torch.empty((max(n, 1) * ((int(L.abub_png_file_bound(W, H)) + 15) & ~15),), dtype=torch.uint8, device=dev)
+    need = int(L.abub_png_encode_scratch_bytes(n, W, H))
+    if scratch is None:
+        scratch = torch.empty((max(need, 16),), dtype=torch.uint8, device=dev)
+    d_files = torch.zeros((max(n, 1), 2), dtype=torch.int64, device=dev)
+    d_total = torch.zeros((1,), dtype=torch.int64, device=dev)
+    _lib.check(L.abub_png_encode_dev(_ptr(pixels), pixels.numel(), _ptr(d_src), n, W, H, _ptr(out), out.numel() if out_cap is None else min(int(out_cap), out.numel()),
+                                     _ptr(d_files), _ptr(d_total), _ptr(scratch), scratch.numel(), _stream()), "abub_png_encode_dev")
+    rec = d_files.cpu().numpy()[:n]
+    files = np.stack([rec[:, 0], rec[:, 1] & 0xFFFFFFFF, rec[:, 1] >> 32], axis=1) if n else np.zeros((0, 3), np.int64)
+    return files, int(d_total.item()), out
+
+
 def frames_compare(a, b, pairs, frame_bytes, a_bytes=None, b_bytes=None, results=None):
     """abub_frames_compare_dev: a, b u8 (any shape, may be the same tensor; frames of frame_bytes bytes anywhere in them),
     pairs: [n, 2] byte offsets of the two frames of each pair (any alignment); a_bytes / b_bytes: the sizes the kernel is

@@ -47,6 +47,11 @@ SIGNATURES = {
     "abh_abf_decode": (_i, [_u8p, C.c_longlong, _u8p, _i, _i]),
     "abh_run_repack": (_i, [_vp, _s, _i, _i, _dp]),
     "abh_run_repack_dev": (_i, [_vp, _s, _i, _i, _i, _dp]),
+    "abh_png_huff_encode": (C.c_longlong, [_u8p, _i, _i, _u8p, C.c_longlong]),
+    "abh_png_huff_bound": (C.c_longlong, [_i, _i]),
+    "abh_png_huff_lengths": (_i, [C.POINTER(C.c_uint64), _i, _i, _u8p]),
+    "abh_run_unpack": (_i, [_vp, _s, _i, _i, _dp]),
+    "abh_run_unpack_dev": (_i, [_vp, _s, _i, _i, _i, _dp]),
     "abh_run_verify": (_i, [_vp, _vp, _i, _i, _dp, C.c_char_p, _i]),
     "abh_run_verify_dev": (_i, [_vp, _vp, _i, _i, _i, _dp, C.c_char_p, _i]),
     "abh_run_verify_report": (_s, [_vp]),
@@ -270,6 +275,26 @@ class Run:
             raise RuntimeError(f"abh_run_repack rc={rc}: " + L.abh_last_error(self._h).decode())
         return dict(zip(keys, list(st)))
 
+    def unpack(self, outdir, nthreads=16, ncams=4, device=None):
+        """abub3hs --unpack of this run (opened from a directory or an archive; packed, PNG, BMP or mixed): the way back
+        from repack.  Every frame of cameras 0 .. ncams-1 written as a canonical Huffman-only PNG (png_huff_encode) to
+        <outdir>/<event>/<image folder>/<same name>; layout, event file and refusals as repack.  device=None: no GPU.
+        device=N (--unpack-gpu): the same files, the frames decoded and encoded on that GPU (abub_png_encode_dev); raises
+        when there is no such device.  -> the stats dict of repack ("packed": PNG files written)."""
+        L = lib()
+        keys = ("packed", "copied", "failed", "bytes_in", "bytes_out", "seconds")
+        if device is None:
+            st = (C.c_double * 6)()
+            rc = L.abh_run_unpack(self._h, outdir.encode(), ncams, nthreads, st)
+        else:
+            keys += ("frames_gpu_encoded", "frames_gpu_png_decoded", "frames_gpu_unpacked", "frames_host_decoded",
+                     "frames_host_route", "batches", "read_s", "decode_s", "encode_s", "copy_s", "write_s", "device")
+            st = (C.c_double * 18)()
+            rc = L.abh_run_unpack_dev(self._h, outdir.encode(), ncams, nthreads, int(device), st)
+        if rc != 0:
+            raise RuntimeError(f"abh_run_unpack rc={rc}: " + L.abh_last_error(self._h).decode())
+        return dict(zip(keys, list(st)))
+
     def verify(self, other, nthreads=16, ncams=4, device=None):
         """abub3hs --verify-repack: is the run `other` (another Run opened from a directory or an archive) pixel for pixel
         this one?  Every frame this run lists for cameras 0 .. ncams-1 gets one verdict: same (identical pixels, the other
@@ -338,6 +363,32 @@ def abf_encode(img):
     if n < 0 or n > cap:
         raise ValueError(f"abf_encode: a {W} x {H} image cannot be packed")
     return out[:n].tobytes()
+
+
+def png_huff_encode(img):
+    """cv::pngHuffEncode (host/pnghuff.cpp): an 8-bit grey image [H, W] -> the bytes of its canonical Huffman-only PNG
+    ("Unpacking a run")."""
+    L = lib()
+    img = np.ascontiguousarray(img, dtype=np.uint8)
+    H, W = img.shape
+    cap = int(L.abh_png_huff_bound(W, H))
+    if cap <= 0:
+        raise ValueError(f"png_huff_encode: a {W} x {H} image cannot be written")
+    out = np.empty(cap, np.uint8)
+    n = L.abh_png_huff_encode(img.ctypes.data_as(_u8p), W, H, out.ctypes.data_as(_u8p), cap)
+    if n < 0 or n > cap:
+        raise ValueError(f"png_huff_encode: a {W} x {H} image cannot be written")
+    return out[:n].tobytes()
+
+
+def png_huff_lengths(counts, limit):
+    """cv::pngHuffLengths: the format's length-limited code lengths of `counts` -> (lengths u8 [n], depth of the unlimited tree)"""
+    c = np.ascontiguousarray(counts, dtype=np.uint64)
+    out = np.zeros(len(c), np.uint8)
+    depth = lib().abh_png_huff_lengths(c.ctypes.data_as(C.POINTER(C.c_uint64)), len(c), limit, out.ctypes.data_as(_u8p))
+    if depth < 0:
+        raise ValueError("png_huff_lengths: bad arguments")
+    return out, depth
 
 
 def abf_decode(data, W, H):

@@ -30,6 +30,7 @@ static std::string usage()
     return "Usage: abub3hs [-hzme] [-D data_series] [-c cam_mask_dir] [--debug code] -d data_dir -r run_ID -o out_dir\n"
            "       abub3hs [-hzm] [-D data_series] [-c cam_mask_dir] -d data_dir --runs ID[,ID...] | --run-list FILE -o out_dir\n"
            "       abub3hs [-z] [-D data_series] -d data_dir -r run_ID --repack out_data_dir [--repack-gpu]\n"
+           "       abub3hs [-z] [-D data_series] -d data_dir -r run_ID --unpack out_data_dir [--unpack-gpu]\n"
            "       abub3hs [-z] [-D data_series] -d data_dir -r run_ID --verify-repack other_data_dir [--verify-gpu]\n"
            "Run the AutoBub3hs bubble finding algorithm on a PICO run (MI355X hot path)\n\n"
            "Required arguments:\n"
@@ -63,14 +64,21 @@ static std::string usage()
            "\t\t\t\tdata_dir it reads.  Analyse it with -d Dir\n"
            "  --repack-gpu\t\t\twith --repack: decode and pack the frames on GPU 0 (the same files, byte for byte; what the\n"
            "\t\t\t\tGPU decoders do not take is packed by host threads); an error when there is no HIP device\n"
+           "  --unpack = Dir\t\tthe way back from --repack: write the run (packed, PNG, BMP or mixed) to Dir/<run_ID>/ with every\n"
+           "\t\t\t\tframe as an ordinary 8-bit grey PNG under its own name (Sub filter, one Huffman-only deflate block:\n"
+           "\t\t\t\tthe same pixels give the same bytes); everything else as --repack; not together with --repack\n"
+           "  --unpack-gpu\t\t\twith --unpack: decode the frames and write the PNG files on GPU 0 (the same files, byte for byte);\n"
+           "\t\t\t\tan error when there is no HIP device\n"
            "  --verify-repack = Dir\t\tcompare the run with its copy Dir/<run_ID>/ (what --repack Dir wrote), frame by frame: every\n"
            "\t\t\t\tframe decoded on both sides and compared pixel for pixel, missing and extra frames and events,\n"
            "\t\t\t\tthe event file; one line per finding (the first 20) and a summary; exit status 0 = verified,\n"
            "\t\t\t\t1 = something failed; no analysis, no -o; not with -e, --merge, --runs / --run-list, --gpu-shard;\n"
-           "\t\t\t\twith --repack Dir (the same Dir): repack first, then verify\n"
+           "\t\t\t\twith --repack Dir or --unpack Dir (the same Dir): repack or unpack first, then verify\n"
            "  --verify-gpu\t\t\twith --verify-repack: decode both sides and compare them on GPU 0 (the same findings and\n"
            "\t\t\t\tcounters); an error when there is no HIP device\n"
-           "Environment: ABUB_TRAIN_ON_GPU=0 trains the runs of a campaign with the host Trainer\n";
+           "Environment: ABUB_TRAIN_ON_GPU=0 trains the runs of a campaign with the host Trainer\n"
+           "             ABUB_REPACK_BATCH=n (a test knob) lowers the frames per batch of --repack-gpu and --unpack-gpu to n; the files\n"
+           "             are the same\n";
 }
 
 // cores this process may use: the affinity mask (taskset, cpuset) AND the cgroup's CPU quota (cpu.max: a container may see
@@ -221,6 +229,7 @@ static bool readRunList(const std::string &path, std::vector<std::string> &runs)
 int main(int argc, char **argv)
 {
     std::string dataLoc, run_number, out_dir, mask_dir, data_series, repackDir, verifyDir;
+    bool haveUnpack = false, unpackGpu = false; // (--unpack takes --repack's route with another frame format)
     bool haveShard = false, haveRepack = false, repackGpu = false, haveVerify = false, verifyGpu = false;
     int event_user = -1, debug_mode = 0, ngpus = 1, shardRank = 0, shardWorld = 1, mergeN = 0;
     bool zipped = false, mask_check = false, help = argc == 1, perEvent = false;
@@ -294,10 +303,23 @@ int main(int argc, char **argv)
                 return -1;
             }
         } else if (a == "--repack" || a.rfind("--repack=", 0) == 0) {
+            if (haveUnpack) {
+                std::cerr << "--unpack cannot be combined with --repack" << std::endl;
+                return -1;
+            }
             value(repackDir);
             haveRepack = true;
         } else if (a == "--repack-gpu") {
             repackGpu = true;
+        } else if (a == "--unpack" || a.rfind("--unpack=", 0) == 0) {
+            if (haveRepack && !haveUnpack) {
+                std::cerr << "--unpack cannot be combined with --repack" << std::endl;
+                return -1;
+            }
+            value(repackDir);
+            haveRepack = haveUnpack = true;
+        } else if (a == "--unpack-gpu") {
+            unpackGpu = true;
         } else if (a == "--verify-repack" || a.rfind("--verify-repack=", 0) == 0) {
             value(verifyDir);
             haveVerify = true;
@@ -314,6 +336,16 @@ int main(int argc, char **argv)
         std::cout << usage() << std::endl;
         return 1;
     }
+    if (unpackGpu && !haveUnpack) {
+        std::cerr << "--unpack-gpu is valid only together with --unpack" << std::endl;
+        return -1;
+    }
+    if (repackGpu && haveUnpack) {
+        std::cerr << "--repack-gpu is valid only together with --repack" << std::endl;
+        return -1;
+    }
+    const char *const rewrite = haveUnpack ? "unpack" : "repack"; // the flag and the word in the messages
+    repackGpu = repackGpu || unpackGpu;
     if (repackGpu && !haveRepack) {
         std::cerr << "--repack-gpu is valid only together with --repack" << std::endl;
         return -1;
@@ -328,11 +360,11 @@ int main(int argc, char **argv)
         const char *bad = mergeN > 0 ? "--merge" : haveList ? "--runs / --run-list" : haveShard ? "--gpu-shard"
                           : event_user >= 0 ? "-e/--event" : nullptr;
         if (bad) {
-            std::cerr << (haveRepack ? "--repack" : "--verify-repack") << " cannot be combined with " << bad << std::endl;
+            std::cerr << (haveUnpack ? "--unpack" : haveRepack ? "--repack" : "--verify-repack") << " cannot be combined with " << bad << std::endl;
             return -1;
         }
         if (haveRepack && (dataLoc.empty() || run_number.empty() || repackDir.empty())) {
-            std::cerr << "--repack needs --data_dir, --run_id and the directory to write to" << std::endl;
+            std::cerr << "--" << rewrite << " needs --data_dir, --run_id and the directory to write to" << std::endl;
             return -1;
         }
         if (haveVerify && (dataLoc.empty() || run_number.empty() || verifyDir.empty())) {
@@ -340,7 +372,7 @@ int main(int argc, char **argv)
             return -1;
         }
         if (haveRepack && haveVerify && repackDir != verifyDir) {
-            std::cerr << "--repack and --verify-repack together must name the same directory" << std::endl;
+            std::cerr << "--" << rewrite << " and --verify-repack together must name the same directory" << std::endl;
             return -1;
         }
     }
@@ -374,31 +406,32 @@ int main(int argc, char **argv)
         try {
             const std::string srcDir = zipped ? std::string() : sp.eventDir;
             const std::string srcFile = zipped ? std::string() : sp.eventDir + run_number + ".txt";
-            rc = repackGpu ? abub::RepackRunDevice(parser.get(), srcDir, srcFile, repackDir + "/" + run_number, sp.imageFolder,
-                                                   sp.numCams, threads, 0, &rs)
-                           : abub::RepackRun(parser.get(), srcDir, srcFile, repackDir + "/" + run_number, sp.imageFolder,
-                                             sp.numCams, threads, &rs);
+            const std::string dst = repackDir + "/" + run_number;
+            rc = repackGpu ? (haveUnpack ? abub::UnpackRunDevice : abub::RepackRunDevice)(parser.get(), srcDir, srcFile, dst,
+                                                                                          sp.imageFolder, sp.numCams, threads, 0, &rs)
+                           : (haveUnpack ? abub::UnpackRun : abub::RepackRun)(parser.get(), srcDir, srcFile, dst, sp.imageFolder,
+                                                                              sp.numCams, threads, &rs);
         } catch (std::exception &e) {
-            std::cerr << "repack failed: " << e.what() << std::endl;
+            std::cerr << rewrite << " failed: " << e.what() << std::endl;
             return -6;
         } catch (...) { // (the parsers throw their status codes)
             std::cerr << "Failed to read the images from run " << run_number << "." << std::endl;
             return -5;
         }
-        printf("repack: %d events, %lld frames packed (%lld -> %lld bytes), %lld copied as they are, %lld not written, %.2f s, "
+        printf("%s: %d events, %lld frames %s (%lld -> %lld bytes), %lld copied as they are, %lld not written, %.2f s, "
                "%.1f frames/s\n",
-               rs.events, rs.packed, rs.bytesIn, rs.bytesOut, rs.copied, rs.failed, rs.total_s,
+               rewrite, rs.events, rs.packed, haveUnpack ? "written as PNG" : "packed", rs.bytesIn, rs.bytesOut, rs.copied, rs.failed, rs.total_s,
                rs.total_s > 0 ? (rs.packed + rs.copied) / rs.total_s : 0.0);
         if (repackGpu) {
             if (rs.device < 0)
-                printf("repack-gpu: 0 frames encoded on the GPU, %lld took the host route (no frame of a width the GPU decoders "
+                printf("%s-gpu: 0 frames encoded on the GPU, %lld took the host route (no frame of a width the GPU decoders "
                        "take)\n",
-                       rs.framesHostRoute);
+                       rewrite, rs.framesHostRoute);
             else
-                printf("repack-gpu: %lld frames encoded on GPU %d (%lld decoded by the PNG kernel, %lld by the packed kernel, "
+                printf("%s-gpu: %lld frames encoded on GPU %d (%lld decoded by the PNG kernel, %lld by the packed kernel, "
                        "%lld by a host thread), %lld took the host route, %d batches; read %.2f s, upload + decode %.2f s, "
                        "encode %.2f s, copy back %.2f s, write %.2f s\n",
-                       rs.framesGpuEncoded, rs.device, rs.framesGpuPngDecoded, rs.framesGpuUnpacked, rs.framesHostDecoded,
+                       rewrite, rs.framesGpuEncoded, rs.device, rs.framesGpuPngDecoded, rs.framesGpuUnpacked, rs.framesHostDecoded,
                        rs.framesHostRoute, rs.batches, rs.read_s, rs.decode_s, rs.encode_s, rs.copy_s, rs.write_s);
         }
         if (!haveVerify || rc != 0)

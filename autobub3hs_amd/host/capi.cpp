@@ -164,12 +164,31 @@ int abh_abf_decode(const uint8_t *data, long long n, uint8_t *out, int W, int H)
 {
     return cv::abfDecodeStatus(data, (size_t)n, out, W, H);
 }
+// the canonical Huffman-only PNG (host/pnghuff.cpp): abh_png_huff_encode returns the file's size (written when cap suffices),
+// -1 on errors; abh_png_huff_bound cv::pngHuffFileBound; abh_png_huff_lengths cv::pngHuffLengths (the depth of the
+// unlimited tree, -1 on bad arguments)
+long long abh_png_huff_encode(const uint8_t *img, int W, int H, uint8_t *out, long long cap)
+{
+    std::vector<uchar> v;
+    if (!cv::pngHuffEncode(img, W, H, v))
+        return -1;
+    if ((long long)v.size() <= cap)
+        std::memcpy(out, v.data(), v.size());
+    return (long long)v.size();
+}
+long long abh_png_huff_bound(int W, int H) { return (long long)cv::pngHuffFileBound(W, H); }
+int abh_png_huff_lengths(const uint64_t *counts, int n, int limit, uint8_t *lengths)
+{
+    return cv::pngHuffLengths(counts, n, limit, lengths);
+}
 // abub::RepackRun of a run opened with abh_run_open into the directory `dstRunDir` (its last component is the new run ID);
 // stats (may be NULL): [frames packed, copied as they are, not written, bytes of the packed frames' sources, of the packed
 // files, seconds].  Returns RepackRun's code, -1 on errors.  abh_run_repack_dev: abub::RepackRunDevice on `device`, no
 // fall-back when there is no such device; its stats go on with [frames encoded on the GPU, of them decoded by the PNG
 // kernel, by the packed kernel, by a host thread, frames that took the host route, batches, seconds of the legs read,
 // upload + decode, encode, copy back, write, the device (-1: the whole run took the host route)] (18 values).
+// abh_run_unpack / abh_run_unpack_dev: abub::UnpackRun / abub::UnpackRunDevice, the same arguments and stats (packed: frames
+// written as canonical Huffman-only PNG files).
 // the event file of a directory run: <run>/<runID>.txt; empty for an archive
 static std::string eventFileOf(const Run &run)
 {
@@ -181,20 +200,23 @@ static std::string eventFileOf(const Run &run)
     const size_t slash = folder.find_last_of('/');
     return folder + "/" + (slash == std::string::npos ? folder : folder.substr(slash + 1)) + ".txt";
 }
-static int runRepack(void *r, const char *dstRunDir, int ncams, int nthreads, int device, bool onDevice, double *stats)
+static int runRepack(void *r, const char *dstRunDir, int ncams, int nthreads, int device, bool onDevice, double *stats,
+                     bool unpack = false)
 {
     Run *run = (Run *)r;
     try {
         if (run->kind < 0) {
-            run->last.error = "repack: not a run opened from a directory or an archive";
+            run->last.error = std::string(unpack ? "unpack" : "repack") + ": not a run opened from a directory or an archive";
             return -1;
         }
         const std::string src = eventFileOf(*run);
         abub::RepackStats st;
         const std::string srcDir = run->kind == 0 ? run->runFolder : std::string();
-        const int rc = onDevice ? abub::RepackRunDevice(run->parser, srcDir, src, dstRunDir, run->imageFolder, ncams,
-                                                        std::max(1, nthreads), device, &st)
-                                : abub::RepackRun(run->parser, srcDir, src, dstRunDir, run->imageFolder, ncams, std::max(1, nthreads), &st);
+        const int threads = std::max(1, nthreads);
+        const int rc = onDevice ? (unpack ? abub::UnpackRunDevice : abub::RepackRunDevice)(run->parser, srcDir, src, dstRunDir,
+                                                                                         run->imageFolder, ncams, threads, device, &st)
+                                : (unpack ? abub::UnpackRun : abub::RepackRun)(run->parser, srcDir, src, dstRunDir, run->imageFolder,
+                                                                               ncams, threads, &st);
         if (stats) {
             const double v[18] = {(double)st.packed, (double)st.copied, (double)st.failed, (double)st.bytesIn, (double)st.bytesOut,
                                   st.total_s, (double)st.framesGpuEncoded, (double)st.framesGpuPngDecoded,
@@ -215,6 +237,14 @@ int abh_run_repack(void *r, const char *dstRunDir, int ncams, int nthreads, doub
 int abh_run_repack_dev(void *r, const char *dstRunDir, int ncams, int nthreads, int device, double *stats)
 {
     return runRepack(r, dstRunDir, ncams, nthreads, device, true, stats);
+}
+int abh_run_unpack(void *r, const char *dstRunDir, int ncams, int nthreads, double *stats)
+{
+    return runRepack(r, dstRunDir, ncams, nthreads, -1, false, stats, true);
+}
+int abh_run_unpack_dev(void *r, const char *dstRunDir, int ncams, int nthreads, int device, double *stats)
+{
+    return runRepack(r, dstRunDir, ncams, nthreads, device, true, stats, true);
 }
 
 // abub::VerifyRun of two runs opened with abh_run_open: is `other` pixel for pixel the run `src`?  stats (may be NULL, 25

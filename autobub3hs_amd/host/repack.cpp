@@ -4,9 +4,12 @@
 // (--repack-gpu) decodes the frames of the run's size with the GPU decoders and encodes them with abub_abf_encode_dev, and
 // writes the same bytes.  What both share -- the refusal to write into the run being read, the directory layout, the run's
 // event file, what becomes of a single file on a host thread, the exit status -- is one copy.
+// UnpackRun / UnpackRunDevice (abub3hs --unpack [--unpack-gpu]) are the same two routes with another codec: every frame
+// becomes a canonical Huffman-only PNG (cv::pngHuffEncode / abub_png_encode_dev; DESIGN section 3, "Unpacking a run").
 #include <algorithm>
 #include <cerrno>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <memory>
@@ -46,6 +49,23 @@ bool writeFile(const std::string &path, const unsigned char *data, size_t n)
     return fclose(f) == 0 && ok;
 }
 
+// The frame format a run is rewritten in: what differs between --repack and --unpack
+struct Codec {
+    const char *what;                                                         // "repack" / "unpack", in messages
+    bool (*encode)(const uchar *pixels, int W, int H, std::vector<uchar> &out); // on a host thread
+    int (*encodeDev)(const uint8_t *, size_t, const uint64_t *, int, int, int, uint8_t *, size_t, abub_abf_file *, uint64_t *, void *,
+                     size_t, void *);
+    size_t (*scratchBytes)(int nframes, int W, int H);
+    const char *devName, *noDevice, *outgrew; // the device entry's name; what requireDevice adds to its message; the
+                                              // message when a batch's files do not fit their regrown buffer
+};
+const Codec kPacked = {"repack", cv::abfEncode, abub_abf_encode_dev, abub_abf_encode_scratch_bytes, "abub_abf_encode_dev",
+                       "; without --repack-gpu the run is repacked on the host",
+                       "repack: the packed files of a batch outgrew their buffer twice"};
+const Codec kPng = {"unpack", cv::pngHuffEncode, abub_png_encode_dev, abub_png_encode_scratch_bytes, "abub_png_encode_dev",
+                    "; without --unpack-gpu the run is unpacked on the host",
+                    "unpack: the PNG files of a batch outgrew their buffer twice"};
+
 // what became of one frame
 struct Outcome {
     bool ok = false, packed = false;
@@ -54,12 +74,12 @@ struct Outcome {
 
 // The bytes of a source file on a host thread: decoded at whatever size the file has and packed, or, where they do not
 // decode, copied as they are (the file stays undecodable)
-Outcome packBytes(const unsigned char *data, size_t size, const std::string &path)
+Outcome packBytes(const Codec &codec, const unsigned char *data, size_t size, const std::string &path)
 {
     static thread_local std::vector<unsigned char> packed;
     Outcome o;
     const cv::Mat m = size ? cv::imdecode(data, size, 0) : cv::Mat();
-    o.packed = !m.empty() && cv::abfEncode(m.data, m.cols, m.rows, packed);
+    o.packed = !m.empty() && codec.encode(m.data, m.cols, m.rows, packed);
     o.ok = o.packed ? writeFile(path, packed.data(), packed.size()) : writeFile(path, data, size);
     o.in = (long long)size;
     o.out = (long long)packed.size();
@@ -67,7 +87,7 @@ Outcome packBytes(const unsigned char *data, size_t size, const std::string &pat
 }
 
 // One frame read through the parser and packed on this thread
-Outcome hostFrame(Parser &p, const std::string &ev, const std::string &name, const std::string &path)
+Outcome hostFrame(const Codec &codec, Parser &p, const std::string &ev, const std::string &name, const std::string &path)
 {
     static thread_local std::vector<unsigned char> file;
     const long long size = p.GetImageFileSize(ev, name);
@@ -76,7 +96,7 @@ Outcome hostFrame(Parser &p, const std::string &ev, const std::string &name, con
     file.resize((size_t)size);
     if (size && p.ReadImageFile(ev, name, file.data(), file.size()) != size)
         return Outcome();
-    return packBytes(file.data(), file.size(), path);
+    return packBytes(codec, file.data(), file.size(), path);
 }
 
 using Task = FrameTask;
@@ -90,7 +110,7 @@ struct Plan {
     std::string pathOf(const Task &t) const { return dirs[t.ev] + "/" + t.name; }
 };
 
-Plan planRun(Parser *parser, const std::string &srcRunDir, const std::string &srcRunFile, const std::string &dstRunDir_,
+Plan planRun(const Codec &codec, Parser *parser, const std::string &srcRunDir, const std::string &srcRunFile, const std::string &dstRunDir_,
              const std::string &imageFolder, int numCams)
 {
     Plan pl;
@@ -101,7 +121,7 @@ Plan planRun(Parser *parser, const std::string &srcRunDir, const std::string &sr
         struct stat a, b;
         if (!srcRunDir.empty() && stat(srcRunDir.c_str(), &a) == 0 && stat(dstRunDir.c_str(), &b) == 0 && a.st_dev == b.st_dev &&
             a.st_ino == b.st_ino)
-            throw std::runtime_error("repack: " + dstRunDir + " is the run that is being read");
+            throw std::runtime_error(std::string(codec.what) + ": " + dstRunDir + " is the run that is being read");
     }
     pl.events = sortedEvents(*parser);
     const std::vector<std::string> &events = pl.events;
@@ -162,23 +182,29 @@ struct Tally {
     }
 };
 
-void hostFrames(Parser *parser, const Plan &pl, int nthreads, Tally &tally)
+void hostFrames(const Codec &codec, Parser *parser, const Plan &pl, int nthreads, Tally &tally)
 {
     forEachTask(parser, nthreads, pl.tasks.size(), [&](Parser &p, size_t i) {
         const Task &t = pl.tasks[i];
-        tally.add(hostFrame(p, pl.events[t.ev], t.name, pl.pathOf(t)));
+        tally.add(hostFrame(codec, p, pl.events[t.ev], t.name, pl.pathOf(t)));
     });
 }
 
-// The device route: the frames in batches of at most 4 per CU.  Per batch: the pool reads the files into a pinned buffer
+// The device route: the frames in batches of at most 4 per CU (ABUB_REPACK_BATCH=n, a test knob: of at most n, never more).  Per batch: the pool reads the files into a pinned buffer
 // (and packs, on the spot, what is no file for the GPU decoders: a frame it had to decode itself, a frame of another size,
-// a file that does not decode); upload; both decoders into a slab; abub_abf_encode_dev over the frames that are in place;
+// a file that does not decode); upload; both decoders into a slab; the codec's device encoder over the frames that are in place;
 // files and total copied back; one copy of `total` bytes into pinned memory; the pool writes the files.
-void deviceFrames(Parser *parser, const Plan &pl, int nthreads, int device, int W, int H, Tally &tally)
+void deviceFrames(const Codec &codec, Parser *parser, const Plan &pl, int nthreads, int device, int W, int H, Tally &tally)
 {
     RepackStats &st = tally.st;
     HIPOK(hipSetDevice(device));
-    const size_t perBatch = framesPerBatch(device), P = (size_t)W * H;
+    size_t perBatch = framesPerBatch(device);
+    if (const char *e = getenv("ABUB_REPACK_BATCH")) { // (a test knob: several batches of a small run; it can only lower the size)
+        const long v = atol(e);
+        if (v > 0)
+            perBatch = std::min(perBatch, (size_t)v);
+    }
+    const size_t P = (size_t)W * H;
     PinnedBuffer h_files, h_meta;
     DeviceBuffer d_files, slab, d_meta, scratch;
     PngScratch png;
@@ -209,15 +235,15 @@ void deviceFrames(Parser *parser, const Plan &pl, int nthreads, int device, int 
             if (f.state == FileTask::HostDecoded) { // (16-bit, colour, BMP: this thread decoded it at W x H)
                 static thread_local std::vector<unsigned char> packed;
                 Outcome o;
-                o.packed = cv::abfEncode(f.pix.data(), W, H, packed);
+                o.packed = codec.encode(f.pix.data(), W, H, packed);
                 o.ok = o.packed && writeFile(pl.pathOf(t), packed.data(), packed.size());
                 o.in = f.size;
                 o.out = (long long)packed.size();
                 tally.add(o);
             } else if (f.read) // another size, or a file that does not decode
-                tally.add(packBytes(h_files.get() + f.off, (size_t)f.size, pl.pathOf(t)));
+                tally.add(packBytes(codec, h_files.get() + f.off, (size_t)f.size, pl.pathOf(t)));
             else               // a file the parser does not hand out in one piece
-                tally.add(hostFrame(p, ev, t.name, pl.pathOf(t)));
+                tally.add(hostFrame(codec, p, ev, t.name, pl.pathOf(t)));
             f.pix = std::vector<uint8_t>();
             f.state = FileTask::Other;
         });
@@ -260,7 +286,7 @@ void deviceFrames(Parser *parser, const Plan &pl, int nthreads, int device, int 
             const size_t metaBytes = ng * (sizeof(uint64_t) + sizeof(abub_abf_file)) + sizeof(uint64_t);
             h_meta.grow(metaBytes);
             d_meta.grow(metaBytes);
-            scratch.grow(abub_abf_encode_scratch_bytes((int)ng, W, H));
+            scratch.grow(codec.scratchBytes((int)ng, W, H));
             std::memcpy(h_meta.get(), src.data(), ng * sizeof(uint64_t));
             HIPOK(hipMemcpyAsync(d_meta.get(), h_meta.get(), ng * sizeof(uint64_t), hipMemcpyHostToDevice, cs));
             abub_abf_file *d_rec = (abub_abf_file *)(d_meta.get() + ng * sizeof(uint64_t));
@@ -269,14 +295,14 @@ void deviceFrames(Parser *parser, const Plan &pl, int nthreads, int device, int 
             out.newBatch();
             out.reserve(total + 64 * ng); // (a packed frame is about the size of its PNG)
             for (;;) {
-                check(abub_abf_encode_dev(slab.get(), n * P, (const uint64_t *)d_meta.get(), (int)ng, W, H, out.d, out.cap(), d_rec,
-                                          d_total, scratch.get(), scratch.capacity(), cs),
-                      "abub_abf_encode_dev");
+                check(codec.encodeDev(slab.get(), n * P, (const uint64_t *)d_meta.get(), (int)ng, W, H, out.d, out.cap(), d_rec,
+                                      d_total, scratch.get(), scratch.capacity(), cs),
+                      codec.devName);
                 HIPOK(hipMemcpyAsync(h_meta.get() + ng * sizeof(uint64_t), d_rec, ng * sizeof(abub_abf_file) + sizeof(uint64_t),
                                      hipMemcpyDeviceToHost, cs));
                 HIPOK(hipStreamSynchronize(cs));
                 std::memcpy(&bytes, files + ng, sizeof bytes);
-                if (out.fit((size_t)bytes, "repack: the packed files of a batch outgrew their buffer twice"))
+                if (out.fit((size_t)bytes, codec.outgrew))
                     break;
             }
             st.encode_s += (nowMs() - t0) * 1e-3;
@@ -297,7 +323,7 @@ void deviceFrames(Parser *parser, const Plan &pl, int nthreads, int device, int 
             if (ft[i].state == FileTask::Other)
                 return; // (written by the thread that read it)
             if (fileOf[i] == SIZE_MAX) {
-                tally.add(packBytes(h_files.get() + ft[i].off, (size_t)ft[i].size, pl.pathOf(t)));
+                tally.add(packBytes(codec, h_files.get() + ft[i].off, (size_t)ft[i].size, pl.pathOf(t)));
                 return;
             }
             const abub_abf_file &r = files[fileOf[i]];
@@ -313,14 +339,14 @@ void deviceFrames(Parser *parser, const Plan &pl, int nthreads, int device, int 
     }
 }
 
-int repackRun(Parser *parser, const std::string &srcRunDir, const std::string &srcRunFile, const std::string &dstRunDir,
+int repackRun(const Codec &codec, Parser *parser, const std::string &srcRunDir, const std::string &srcRunFile, const std::string &dstRunDir,
               const std::string &imageFolder, int numCams, int nthreads, int device, RepackStats *stats)
 {
     const double t0 = nowMs();
     RepackStats st;
     if (device >= 0) // (before anything is written)
-        requireDevice(device, "repack", "; without --repack-gpu the run is repacked on the host");
-    const Plan pl = planRun(parser, srcRunDir, srcRunFile, dstRunDir, imageFolder, numCams);
+        requireDevice(device, codec.what, codec.noDevice);
+    const Plan pl = planRun(codec, parser, srcRunDir, srcRunFile, dstRunDir, imageFolder, numCams);
     st.events = (int)pl.events.size();
     Tally tally{st, {}};
     int W = 0, H = 0;
@@ -328,9 +354,9 @@ int repackRun(Parser *parser, const std::string &srcRunDir, const std::string &s
         st.device = device;
         st.W = W;
         st.H = H;
-        deviceFrames(parser, pl, nthreads, device, W, H, tally);
+        deviceFrames(codec, parser, pl, nthreads, device, W, H, tally);
     } else
-        hostFrames(parser, pl, nthreads, tally);
+        hostFrames(codec, parser, pl, nthreads, tally);
     st.total_s = (nowMs() - t0) * 1e-3;
     if (stats)
         *stats = st;
@@ -342,7 +368,7 @@ int repackRun(Parser *parser, const std::string &srcRunDir, const std::string &s
 int RepackRun(Parser *parser, const std::string &srcRunDir, const std::string &srcRunFile, const std::string &dstRunDir,
               const std::string &imageFolder, int numCams, int nthreads, RepackStats *stats)
 {
-    return repackRun(parser, srcRunDir, srcRunFile, dstRunDir, imageFolder, numCams, nthreads, -1, stats);
+    return repackRun(kPacked, parser, srcRunDir, srcRunFile, dstRunDir, imageFolder, numCams, nthreads, -1, stats);
 }
 
 int RepackRunDevice(Parser *parser, const std::string &srcRunDir, const std::string &srcRunFile, const std::string &dstRunDir,
@@ -350,7 +376,21 @@ int RepackRunDevice(Parser *parser, const std::string &srcRunDir, const std::str
 {
     if (device < 0)
         throw std::runtime_error("repack: no such HIP device: " + std::to_string(device));
-    return repackRun(parser, srcRunDir, srcRunFile, dstRunDir, imageFolder, numCams, nthreads, device, stats);
+    return repackRun(kPacked, parser, srcRunDir, srcRunFile, dstRunDir, imageFolder, numCams, nthreads, device, stats);
+}
+
+int UnpackRun(Parser *parser, const std::string &srcRunDir, const std::string &srcRunFile, const std::string &dstRunDir,
+              const std::string &imageFolder, int numCams, int nthreads, RepackStats *stats)
+{
+    return repackRun(kPng, parser, srcRunDir, srcRunFile, dstRunDir, imageFolder, numCams, nthreads, -1, stats);
+}
+
+int UnpackRunDevice(Parser *parser, const std::string &srcRunDir, const std::string &srcRunFile, const std::string &dstRunDir,
+                    const std::string &imageFolder, int numCams, int nthreads, int device, RepackStats *stats)
+{
+    if (device < 0)
+        throw std::runtime_error("unpack: no such HIP device: " + std::to_string(device));
+    return repackRun(kPng, parser, srcRunDir, srcRunFile, dstRunDir, imageFolder, numCams, nthreads, device, stats);
 }
 
 } // namespace abub

@@ -97,11 +97,20 @@ int RepackRun(Parser *parser, const std::string &srcRunDir, const std::string &s
               const std::string &imageFolder, int numCams, int nthreads, RepackStats *stats);
 // abub3hs --repack --repack-gpu: the same files, byte for byte, with the frames of the run's size (that of the first frame
 // that decodes) decoded by the GPU decoders and packed by abub_abf_encode_dev on `device`, in batches of at most 4 frames
-// per CU; the pool's threads read and write the files, and pack on the spot what the decoders do not take (a frame the
+// per CU (ABUB_REPACK_BATCH=n, a test knob: of at most n); the pool's threads read and write the files, and pack on the spot what the decoders do not take (a frame the
 // thread had to decode itself, a frame of another size; a file that does not decode is copied).  A run whose width the
 // decoders do not take ((W & 3) == 0, 4 <= W <= 2048) goes the host route whole.  Throws, before anything is written,
 // when there is no such device: there is no silent fall-back to the host route.
 int RepackRunDevice(Parser *parser, const std::string &srcRunDir, const std::string &srcRunFile, const std::string &dstRunDir,
+                    const std::string &imageFolder, int numCams, int nthreads, int device, RepackStats *stats);
+// abub3hs --unpack [--unpack-gpu]: the way back.  RepackRun / RepackRunDevice with another frame format: every frame is
+// written as a canonical Huffman-only PNG (cv::pngHuffEncode; on the device abub_png_encode_dev, the same bytes) under its
+// own name, so that anything that reads PNG reads the run again; the source may be packed, PNG, BMP or mixed.  Layout,
+// event file, refusals, return value and stats as there (packed / bytesOut count the PNG files written,
+// framesGpuEncoded those abub_png_encode_dev wrote).
+int UnpackRun(Parser *parser, const std::string &srcRunDir, const std::string &srcRunFile, const std::string &dstRunDir,
+              const std::string &imageFolder, int numCams, int nthreads, RepackStats *stats);
+int UnpackRunDevice(Parser *parser, const std::string &srcRunDir, const std::string &srcRunFile, const std::string &dstRunDir,
                     const std::string &imageFolder, int numCams, int nthreads, int device, RepackStats *stats);
 
 // What verify says about one frame, an extra frame or event, or the event file

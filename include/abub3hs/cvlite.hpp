@@ -158,6 +158,15 @@ bool abfEncode(const uchar *pixels, int W, int H, std::vector<uchar> &out);
 bool abfDecodeInto(const uchar *data, size_t size, uchar *dst, int W, int H);
 int abfDecodeStatus(const uchar *data, size_t size, uchar *dst, int W, int H);
 bool abfProbe(const uchar *data, size_t size, int *W, int *H);
+// (not in OpenCV) the canonical Huffman-only PNG (host/pnghuff.cpp, DESIGN section 3, "Unpacking a run"): an ordinary 8-bit grey PNG
+// whose every byte is fixed by rule -- Sub filter on every row, one dynamic-Huffman deflate block of literals, no LZ77 --
+// so that the GPU encoder abub_png_encode_dev writes the same file.  pngHuffEncode: false for sizes outside [1, 65535] or
+// whose file may reach 4 GB.  pngHuffFileBound: the longest file of a W x H frame (15 bits per symbol, the longest
+// header), 0 where pngHuffEncode refuses.  pngHuffLengths: the format's length-limited code lengths of n <= 288 counts
+// (at least two of them nonzero); returns the depth of the unlimited tree, -1 on bad arguments.
+bool pngHuffEncode(const uchar *pixels, int W, int H, std::vector<uchar> &out);
+size_t pngHuffFileBound(int W, int H);
+int pngHuffLengths(const uint64_t *counts, int n, int limit, uchar *lengths);
 // debug write-out (AnalyzerUnit.cpp:237,354-365; L3Localizer.cpp:236-257,448): 8-bit grey PNG, or 8-bit palettised BMP
 // when the name ends in .bmp; false when the file cannot be written (like cv::imwrite into a missing directory)
 bool imwrite(const std::string &path, const Mat &img);

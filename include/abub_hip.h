@@ -585,6 +585,28 @@ int abub_abf_encode_dev(const uint8_t *pixels, size_t pixels_bytes, const uint64
                         uint8_t *out, size_t out_cap, abub_abf_file *files, uint64_t *total, void *scratch,
                         size_t scratch_bytes, void *stream);
 
+/* ---- canonical Huffman-only PNG files written on the GPU (abub_png_enc.hip) ------------------------------------------
+ * What cv::pngHuffEncode does on a host thread, for a batch of resident frames (abub3hs --unpack --unpack-gpu; the format's
+ * rules, the launches and the limits: DESIGN section 3, "Unpacking a run"): file f is exactly the bytes
+ * cv::pngHuffEncode(pixels + src[f], W, H) writes -- an ordinary 8-bit grey PNG with the Sub filter on every row and one
+ * dynamic-Huffman deflate block of literals.  The conventions are those of abub_abf_encode_dev, and its record type and
+ * status codes are reused: the files lie in `out` in frame order, each at a multiple of 16; nothing is written between
+ * them, nothing at or behind out + out_cap; *total is a true count whatever out_cap is; ABUB_ABF_ENC_E_SRC takes no room,
+ * ABUB_ABF_ENC_E_CAP writes none of the file's bytes.  Every byte of `out` is stored once with a plain store (a byte that
+ * two rows share is written by the row its first bit lies in); `out` is not cleared and not read before it is written.
+ * A memset and eight launches on `stream`, no host synchronisation, no allocation. */
+/* the longest file of a W x H frame: 63 + ceil((1880 + 15 * (H * (W + 1) + 1)) / 8) (15 bits per symbol, the longest
+ * header, the container); 0 if W or H is outside [1, 65535] or the value is >= 2^32 */
+size_t abub_png_file_bound(int W, int H);
+/* bytes of `scratch` a launch over nframes frames needs; 0 for arguments abub_png_encode_dev refuses */
+size_t abub_png_encode_scratch_bytes(int nframes, int W, int H);
+/* Arguments as for abub_abf_encode_dev.  Null pointers, nframes < 0, W or H outside [1, 65535], abub_png_file_bound(W, H)
+ * == 0, a scratch smaller than abub_png_encode_scratch_bytes or misaligned: ABUB_E_INVALID before anything touches the
+ * device.  nframes == 0: ABUB_OK, nothing is touched. */
+int abub_png_encode_dev(const uint8_t *pixels, size_t pixels_bytes, const uint64_t *src, int nframes, int W, int H,
+                        uint8_t *out, size_t out_cap, abub_abf_file *files, uint64_t *total, void *scratch,
+                        size_t scratch_bytes, void *stream);
+
 /* ---- resident frames compared byte for byte (abub_compare.hip) ------------------------------------------------------
  * What memcmp of two decoded frames, and a byte loop behind it, does on a host thread, for a batch of resident frames:
  * results[p] says how many of the frame_bytes bytes at a + pairs[p].a and b + pairs[p].b differ, where the first one is
