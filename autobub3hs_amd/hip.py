@@ -398,6 +398,65 @@ def abf_decode(files, descs, W, H, out, status=None):
     return status[:n]
 
 
+# ---- BMP frames decoded on the GPU (abub_bmp_decode_dev) ----------------------------------------------------------
+def bmp_parse(data, W, H):
+    """What the host does per file before the upload (host/bmpwalk.hpp::bmpWalk restated): the header of a BMP -> dict of
+    data_off, stride, bpp, top_down, identity and lut (bytes, 256: index -> grey; the identity for 24 / 32 bit) for a file
+    the host decoder (decodeBMP, host/cvlite.cpp) reads as a W x H image, or None for anything else."""
+    import struct
+    size = len(data)
+    if size < 54 or data[:2] != b"BM":
+        return None
+    data_off, hdr, w, h = struct.unpack_from("<IIii", data, 10)
+    bpp, comp = struct.unpack_from("<HI", data, 28)
+    ncol, = struct.unpack_from("<I", data, 46)
+    if hdr < 40:
+        return None
+    top_down = h < 0
+    h = abs(h)
+    if w <= 0 or h <= 0 or (comp != 0 and not (comp == 3 and bpp == 32)) or bpp not in (1, 4, 8, 24, 32):
+        return None
+    if w != W or h != H:
+        return None
+    stride = (w * bpp + 31) // 32 * 4
+    if data_off + stride * h > size:
+        return None
+    lut = list(range(256))
+    if bpp <= 8:
+        if ncol == 0:
+            ncol = 1 << bpp
+        po = (14 + hdr) & 0xFFFFFFFF
+        for i in range(min(ncol, 256)):
+            if po + 4 * i + 3 >= size:
+                break
+            b, g, r = data[po + 4 * i], data[po + 4 * i + 1], data[po + 4 * i + 2]
+            lut[i] = ((b * 1868 + g * 9617 + r * 4899 + 8192) >> 14) & 255
+    return dict(data_off=data_off, stride=stride, bpp=bpp, top_down=top_down, identity=lut == list(range(256)), lut=bytes(lut))
+
+
+def bmp_decode(files, descs, luts, W, H, out, status=None):
+    """abub_bmp_decode_dev: files u8 [files_bytes] (BMP files as they are on disk, anywhere in the buffer), descs: rows of
+    (off, len, data_off, stride, bpp, flags, lut, dst) as abub_bmp_frame (lut 0xffffffff: none), luts u8 [nluts * 256] or
+    None, out u8 (any shape, written in place) -> status i32 [n] on the device (0 = decoded, else ABUB_BMP_E_DESC)."""
+    import numpy as np
+    _need_cuda(files, out, luts)
+    d = np.asarray(descs, dtype=np.int64).reshape(-1, 8)
+    n = len(d)
+    rec = np.zeros((max(n, 1), 8), dtype=np.uint32)
+    rec[:n, 0:4] = d[:, 0:4] & 0xFFFFFFFF
+    rec[:n, 4] = (d[:, 4] & 0xFFFF) | ((d[:, 5] & 0xFFFF) << 16)
+    rec[:n, 5] = d[:, 6] & 0xFFFFFFFF
+    rec[:n, 6] = d[:, 7] & 0xFFFFFFFF
+    rec[:n, 7] = d[:, 7] >> 32
+    d_desc = torch.from_numpy(rec.view(np.int32).copy()).to(files.device)
+    if status is None:
+        status = torch.full((max(n, 1),), 99, dtype=torch.int32, device=files.device)
+    nluts = 0 if luts is None else luts.numel() // 256
+    _lib.check(_lib.lib().abub_bmp_decode_dev(_ptr(files), files.numel(), _ptr(d_desc), n, _ptr(luts), nluts, W, H, _ptr(out),
+                                              out.numel(), _ptr(status), _stream()), "abub_bmp_decode_dev")
+    return status[:n]
+
+
 def abf_encode(pixels, src, W, H, out=None, scratch=None, out_cap=None):
     """abub_abf_encode_dev: pixels u8 (any shape; frames of W * H bytes anywhere in it), src: byte offset of each frame
     (any alignment), out u8 (None: nframes * abub_abf_file_bound(W, H), rounded up to 16 per file; out_cap: the kernels may

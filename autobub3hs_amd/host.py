@@ -56,6 +56,7 @@ SIGNATURES = {
     "abh_run_verify_dev": (_i, [_vp, _vp, _i, _i, _i, _dp, C.c_char_p, _i]),
     "abh_run_verify_report": (_s, [_vp]),
     "abh_png_walk": (_i, [_u8p, _i, _i, _i, _u32p, _i, _ip, _ip, _u8p]),
+    "abh_bmp_walk": (_i, [_u8p, _i, _i, _i, _u32p, _u8p]),
     "abh_imwrite": (_i, [_s, _u8p, _i, _i]),
     "abh_write_header": (None, [_s, _s, _i, _i]),
     "abh_event_to_file": (_i, [_vp, _s, _i, _i, _s, _s, _s, _i]),
@@ -203,14 +204,14 @@ class Run:
         """Every camera trained in one pass on the device (abub::TrainOnDevice): per camera (status, tss, mu, sigma), the
         same as train(cam).  self.train_path is "device", or "host" where TrainOnDevice declined the run; self.train_stats:
         frames decoded by the GPU decoders / by host threads, decode launches, seconds, and of the first the packed frames
-        (frames_gpu_unpacked, abub_abf_decode_dev)."""
+        (frames_gpu_unpacked, abub_abf_decode_dev) and the BMP frames (frames_gpu_bmp, abub_bmp_decode_dev)."""
         H, W = shape if shape is not None else self._shape
         L = lib()
         mu = np.zeros((ncams, H, W), np.uint8)
         sg = np.zeros((ncams, H, W), np.uint8)
         st = np.zeros(ncams, np.int32)
         tss = np.zeros(ncams, np.int32)
-        stats = np.zeros(5, np.float64)
+        stats = np.zeros(6, np.float64)
         rc = L.abh_train_device(self._h, ncams, st.ctypes.data_as(_ip), tss.ctypes.data_as(_ip), mu.ctypes.data_as(_u8p),
                                 sg.ctypes.data_as(_u8p), H * W, stats.ctypes.data_as(_dp))
         if rc < 0:
@@ -218,7 +219,7 @@ class Run:
         self.train_path = "device" if rc == 0 else "host"
         self.train_stats = {"frames_gpu_decoded": int(stats[0]), "frames_host_decoded": int(stats[1]),
                             "decode_launches": int(stats[2]), "seconds": float(stats[3]),
-                            "frames_gpu_unpacked": int(stats[4])}
+                            "frames_gpu_unpacked": int(stats[4]), "frames_gpu_bmp": int(stats[5])}
         return [(int(st[c]), int(tss[c]), mu[c], sg[c]) for c in range(ncams)]
 
     def set_model(self, cam, mu, sigma, tss):
@@ -243,16 +244,17 @@ class Run:
 
     def run_batched(self, ncams, outdir, run_number, frame_offset, maskdir="", ngpus=1, nthreads=16, decode_threads=16,
                     batch_mb=0, shard=(0, 1)):
-        """Every event of this run through the batched GPU pipeline (host/runbatch.cpp RunBatched): frames decoded (PNG and packed files: on the GPU, abub_png_decode_dev / abub_abf_decode_dev; ABUB_GPU_DECODE=0: by host threads into pinned
+        """Every event of this run through the batched GPU pipeline (host/runbatch.cpp RunBatched): frames decoded (PNG, packed and BMP files: on the GPU, abub_png_decode_dev / abub_abf_decode_dev / abub_bmp_decode_dev with ABUB_GPU_BMP=1, else BMP files by host threads; ABUB_GPU_DECODE=0: by host threads into pinned
         batches), detect, blocks appended to <outdir>abub3hs_<run>.txt in event order.  -> stats dict."""
         L = lib()
-        st = (C.c_double * 14)()
+        st = (C.c_double * 15)()
         rc = L.abh_run_batched(self._h, ncams, maskdir.encode(), outdir.encode(), run_number.encode(), frame_offset, ngpus,
                                nthreads, decode_threads, batch_mb, shard[0], shard[1], st)
         if rc != 0:
             raise RuntimeError(f"abh_run_batched rc={rc}: " + L.abh_last_error(self._h).decode())
         keys = ("total_s", "list_s", "decode_s", "gpu_s", "write_s", "frames", "frames_failed", "batches",
-                "events_per_batch", "gpus", "frames_gpu_decoded", "frames_host_decoded", "gpudecode_s", "frames_gpu_unpacked")
+                "events_per_batch", "gpus", "frames_gpu_decoded", "frames_host_decoded", "gpudecode_s", "frames_gpu_unpacked",
+                "frames_gpu_bmp")
         return dict(zip(keys, list(st)))
 
     def repack(self, outdir, nthreads=16, ncams=4, device=None):
@@ -268,8 +270,9 @@ class Run:
             rc = L.abh_run_repack(self._h, outdir.encode(), ncams, nthreads, st)
         else:
             keys += ("frames_gpu_encoded", "frames_gpu_png_decoded", "frames_gpu_unpacked", "frames_host_decoded",
-                     "frames_host_route", "batches", "read_s", "decode_s", "encode_s", "copy_s", "write_s", "device")
-            st = (C.c_double * 18)()
+                     "frames_host_route", "batches", "read_s", "decode_s", "encode_s", "copy_s", "write_s", "device",
+                     "frames_gpu_bmp_decoded")
+            st = (C.c_double * 19)()
             rc = L.abh_run_repack_dev(self._h, outdir.encode(), ncams, nthreads, int(device), st)
         if rc != 0:
             raise RuntimeError(f"abh_run_repack rc={rc}: " + L.abh_last_error(self._h).decode())
@@ -288,8 +291,9 @@ class Run:
             rc = L.abh_run_unpack(self._h, outdir.encode(), ncams, nthreads, st)
         else:
             keys += ("frames_gpu_encoded", "frames_gpu_png_decoded", "frames_gpu_unpacked", "frames_host_decoded",
-                     "frames_host_route", "batches", "read_s", "decode_s", "encode_s", "copy_s", "write_s", "device")
-            st = (C.c_double * 18)()
+                     "frames_host_route", "batches", "read_s", "decode_s", "encode_s", "copy_s", "write_s", "device",
+                     "frames_gpu_bmp_decoded")
+            st = (C.c_double * 19)()
             rc = L.abh_run_unpack_dev(self._h, outdir.encode(), ncams, nthreads, int(device), st)
         if rc != 0:
             raise RuntimeError(f"abh_run_unpack rc={rc}: " + L.abh_last_error(self._h).decode())
@@ -303,11 +307,12 @@ class Run:
         device=None: host threads (cv::imdecode + memcmp).  device=N (--verify-gpu): the same answer, the frames decoded on
         both sides and compared (abub_frames_compare_dev) on that GPU; raises when there is no such device.
         -> dict: rc (0 = verified, 1 = something failed), the counters, event_file ("same", "differs", "missing", "not
-        compared"), the device route's counters and legs (device -1: it was not taken), and findings: every failure and
+        compared"), the device route's counters and legs (device -1: it was not taken; src_gpu_bmp_decoded /
+        other_gpu_bmp_decoded: frames of each side decoded by abub_bmp_decode_dev), and findings: every failure and
         every same_not_packed frame in task order, then the extras and the event file, each a dict of event, name, verdict,
         ndiff, x, y, max_abs (and w, h, other_w, other_h where the sizes differ)."""
         L = lib()
-        st = (C.c_double * 25)()
+        st = (C.c_double * 27)()
         cap = 1 << 16
         buf = C.create_string_buffer(cap)
         if device is None:
@@ -325,6 +330,7 @@ class Run:
                 "other_gpu_png_decoded", "other_gpu_unpacked", "other_host_decoded", "batches")
         res.update({k: int(v) for k, v in zip(keys, list(st)[12:21])})
         res.update(read_s=st[21], decode_s=st[22], compare_s=st[23], device=int(st[24]))
+        res.update(src_gpu_bmp_decoded=int(st[25]), other_gpu_bmp_decoded=int(st[26]))
         cols = ("ndiff", "x", "y", "max_abs", "w", "h", "other_w", "other_h")
         res["findings"] = []
         for line in text.decode().split("\n"):
@@ -412,6 +418,18 @@ def png_walk(data, W, H, cap=4096):
     if not L.abh_png_walk(src.ctypes.data_as(_u8p), len(src), W, H, segs, cap, C.byref(n), C.byref(pal), lut.ctypes.data_as(_u8p)):
         return None
     return [(segs[2 * i], segs[2 * i + 1]) for i in range(min(n.value, cap))], (lut.tobytes() if pal.value else None)
+
+
+def bmp_walk(data, W, H):
+    """host/bmpwalk.hpp::bmpWalk: None for a file the host decoder does not read as a W x H BMP, else the dict of
+    hip.bmp_parse (data_off, stride, bpp, top_down, identity, lut)."""
+    L = lib()
+    src = np.frombuffer(bytes(data) or b"\0", np.uint8)
+    f = (C.c_uint32 * 5)()
+    lut = np.zeros(256, np.uint8)
+    if not L.abh_bmp_walk(src.ctypes.data_as(_u8p), len(data), W, H, f, lut.ctypes.data_as(_u8p)):
+        return None
+    return dict(data_off=int(f[0]), stride=int(f[1]), bpp=int(f[2]), top_down=bool(f[3]), identity=bool(f[4]), lut=lut.tobytes())
 
 
 def imwrite(path, img):

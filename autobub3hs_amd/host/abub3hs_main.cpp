@@ -78,7 +78,10 @@ static std::string usage()
            "\t\t\t\tcounters); an error when there is no HIP device\n"
            "Environment: ABUB_TRAIN_ON_GPU=0 trains the runs of a campaign with the host Trainer\n"
            "             ABUB_REPACK_BATCH=n (a test knob) lowers the frames per batch of --repack-gpu and --unpack-gpu to n; the files\n"
-           "             are the same\n";
+           "             are the same\n"
+           "             ABUB_GPU_BMP=1 decodes BMP frames on the GPU in every device reading route (the batched run, training on the\n"
+           "             GPU, --repack-gpu, --unpack-gpu, --verify-gpu); ABUB_GPU_BMP=0, the default, leaves them to host threads;\n"
+           "             results are the same\n";
 }
 
 // cores this process may use: the affinity mask (taskset, cpuset) AND the cgroup's CPU quota (cpu.max: a container may see
@@ -433,6 +436,8 @@ int main(int argc, char **argv)
                        "encode %.2f s, copy back %.2f s, write %.2f s\n",
                        rewrite, rs.framesGpuEncoded, rs.device, rs.framesGpuPngDecoded, rs.framesGpuUnpacked, rs.framesHostDecoded,
                        rs.framesHostRoute, rs.batches, rs.read_s, rs.decode_s, rs.encode_s, rs.copy_s, rs.write_s);
+            if (rs.framesGpuBmpDecoded)
+                printf("%s-gpu: %lld frames decoded by the BMP kernel\n", rewrite, rs.framesGpuBmpDecoded);
         }
         if (!haveVerify || rc != 0)
             return rc;
@@ -478,6 +483,9 @@ int main(int argc, char **argv)
                        "upload + decode %.2f s, compare %.2f s\n",
                        vs.framesKernel, vs.device, vs.srcGpuPngDecoded, vs.srcGpuUnpacked, vs.srcHostDecoded, vs.otherGpuPngDecoded,
                        vs.otherGpuUnpacked, vs.otherHostDecoded, vs.framesHostRoute, vs.batches, vs.read_s, vs.decode_s, vs.compare_s);
+            if (vs.srcGpuBmpDecoded || vs.otherGpuBmpDecoded)
+                printf("verify-gpu: %lld frames decoded by the BMP kernel (the source's %lld, the copy's %lld)\n",
+                       vs.srcGpuBmpDecoded + vs.otherGpuBmpDecoded, vs.srcGpuBmpDecoded, vs.otherGpuBmpDecoded);
         }
         return rc;
     }

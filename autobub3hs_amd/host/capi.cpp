@@ -22,6 +22,7 @@
 #include "devtrain.hpp"
 #include "driver.hpp"
 #include "hostlogic.hpp"
+#include "bmpwalk.hpp"
 #include "pngwalk.hpp"
 #include "runbatch.hpp"
 #include "stackresult.hpp"
@@ -186,7 +187,8 @@ int abh_png_huff_lengths(const uint64_t *counts, int n, int limit, uint8_t *leng
 // files, seconds].  Returns RepackRun's code, -1 on errors.  abh_run_repack_dev: abub::RepackRunDevice on `device`, no
 // fall-back when there is no such device; its stats go on with [frames encoded on the GPU, of them decoded by the PNG
 // kernel, by the packed kernel, by a host thread, frames that took the host route, batches, seconds of the legs read,
-// upload + decode, encode, copy back, write, the device (-1: the whole run took the host route)] (18 values).
+// upload + decode, encode, copy back, write, the device (-1: the whole run took the host route), of the encoded frames
+// those decoded by the BMP kernel] (19 values).
 // abh_run_unpack / abh_run_unpack_dev: abub::UnpackRun / abub::UnpackRunDevice, the same arguments and stats (packed: frames
 // written as canonical Huffman-only PNG files).
 // the event file of a directory run: <run>/<runID>.txt; empty for an archive
@@ -218,11 +220,12 @@ static int runRepack(void *r, const char *dstRunDir, int ncams, int nthreads, in
                                 : (unpack ? abub::UnpackRun : abub::RepackRun)(run->parser, srcDir, src, dstRunDir, run->imageFolder,
                                                                                ncams, threads, &st);
         if (stats) {
-            const double v[18] = {(double)st.packed, (double)st.copied, (double)st.failed, (double)st.bytesIn, (double)st.bytesOut,
+            const double v[19] = {(double)st.packed, (double)st.copied, (double)st.failed, (double)st.bytesIn, (double)st.bytesOut,
                                   st.total_s, (double)st.framesGpuEncoded, (double)st.framesGpuPngDecoded,
                                   (double)st.framesGpuUnpacked, (double)st.framesHostDecoded, (double)st.framesHostRoute,
-                                  (double)st.batches, st.read_s, st.decode_s, st.encode_s, st.copy_s, st.write_s, (double)st.device};
-            std::memcpy(stats, v, (onDevice ? 18 : 6) * sizeof(double));
+                                  (double)st.batches, st.read_s, st.decode_s, st.encode_s, st.copy_s, st.write_s, (double)st.device,
+                                  (double)st.framesGpuBmpDecoded};
+            std::memcpy(stats, v, (onDevice ? 19 : 6) * sizeof(double));
         }
         return rc;
     } catch (std::exception &e) {
@@ -247,12 +250,12 @@ int abh_run_unpack_dev(void *r, const char *dstRunDir, int ncams, int nthreads, 
     return runRepack(r, dstRunDir, ncams, nthreads, device, true, stats, true);
 }
 
-// abub::VerifyRun of two runs opened with abh_run_open: is `other` pixel for pixel the run `src`?  stats (may be NULL, 25
+// abub::VerifyRun of two runs opened with abh_run_open: is `other` pixel for pixel the run `src`?  stats (may be NULL, 27
 // values): [events, frames, same, same but not packed, copied, differ, missing, undecodable, extra, the event file (0 same,
 // 1 differs, 2 missing, 3 not compared), seconds, the report's length; of the device route: frames compared by the kernel,
 // frames that took the host route, the source's frames decoded by the PNG kernel, by the packed kernel, by a host thread,
 // the other run's likewise, batches, seconds of the legs read, upload + decode, compare, the device (-1: it was not
-// taken)].  report (may be NULL): one line per finding, "event\tname\tverdict\tndiff\tx\ty\tmax_abs\tw\th\tother_w\tother_h\n",
+// taken), the source's and the other run's frames decoded by the BMP kernel].  report (may be NULL): one line per finding, "event\tname\tverdict\tndiff\tx\ty\tmax_abs\tw\th\tother_w\tother_h\n",
 // cut at report_cap - 1 characters; the whole text stays with `src` for abh_run_verify_report.  Returns VerifyRun's code, -1
 // on errors.  abh_run_verify_dev: abub::VerifyRunDevice on `device`, no fall-back when there is no such device.
 static int runVerify(void *a, void *b, int ncams, int nthreads, int device, bool onDevice, double *stats, char *report, int report_cap)
@@ -281,12 +284,13 @@ static int runVerify(void *a, void *b, int ncams, int nthreads, int device, bool
             report[n] = 0;
         }
         if (stats) {
-            const double v[25] = {(double)st.events, (double)st.frames, (double)st.same, (double)st.sameNotPacked, (double)st.copied,
+            const double v[27] = {(double)st.events, (double)st.frames, (double)st.same, (double)st.sameNotPacked, (double)st.copied,
                                   (double)st.differ, (double)st.missing, (double)st.undecodable, (double)st.extra, (double)st.eventFile,
                                   st.total_s, (double)text.size(), (double)st.framesKernel, (double)st.framesHostRoute,
                                   (double)st.srcGpuPngDecoded, (double)st.srcGpuUnpacked, (double)st.srcHostDecoded,
                                   (double)st.otherGpuPngDecoded, (double)st.otherGpuUnpacked, (double)st.otherHostDecoded,
-                                  (double)st.batches, st.read_s, st.decode_s, st.compare_s, (double)st.device};
+                                  (double)st.batches, st.read_s, st.decode_s, st.compare_s, (double)st.device,
+                                  (double)st.srcGpuBmpDecoded, (double)st.otherGpuBmpDecoded};
             std::memcpy(stats, v, sizeof v);
         }
         return rc;
@@ -310,6 +314,22 @@ int abh_run_verify_dev(void *src, void *other, int ncams, int nthreads, int devi
 const char *abh_run_verify_report(void *src)
 {
     return ((Run *)src)->frames_of_last_query.c_str();
+}
+
+// bmpWalk (host/bmpwalk.hpp: what the reading threads learn about a BMP before the GPU decodes it): 1 = a file decodeBMP
+// reads as a W x H image (fields_out: data_off, stride, bpp, top-down, the table is the identity; lut_out[256]), 0 = not
+int abh_bmp_walk(const uint8_t *data, int n, int W, int H, uint32_t *fields_out, uint8_t *lut_out)
+{
+    abub::BmpInfo info;
+    if (n < 0 || !abub::bmpWalk(data, (size_t)n, W, H, info))
+        return 0;
+    fields_out[0] = info.dataOff;
+    fields_out[1] = info.stride;
+    fields_out[2] = (uint32_t)info.bpp;
+    fields_out[3] = info.topDown ? 1 : 0;
+    fields_out[4] = info.identity ? 1 : 0;
+    std::memcpy(lut_out, info.lut, 256);
+    return 1;
 }
 
 // cv::imwrite of the debug write-out (PNG, or BMP by extension)
@@ -395,7 +415,7 @@ int abh_train(void *r, int cam, int *status, int *tss, uint8_t *mu_out, uint8_t 
 // status[c], tss[c] and, where it trained, its mu / sigma at mu_out + c * cap, sigma_out + c * cap (cap bytes each).  The
 // Run's Trainers are replaced.  Returns 0 (trained on the device), 1 (TrainOnDevice declined the run: the host Trainer
 // trained it), -1 on errors.  stats (may be NULL): [frames decoded by the GPU decoder, by host threads, decode launches,
-// seconds, packed frames decoded by the GPU decoder (they count in the first, too)].
+// seconds, packed frames decoded by the GPU decoder (they count in the first, too), BMP frames likewise].
 int abh_train_device(void *r, int ncams, int *status, int *tss, uint8_t *mu_out, uint8_t *sigma_out, int cap, double *stats)
 {
     Run *run = (Run *)r;
@@ -417,6 +437,7 @@ int abh_train_device(void *r, int ncams, int *status, int *tss, uint8_t *mu_out,
             stats[2] = (double)st.decodeLaunches;
             stats[3] = st.total_s;
             stats[4] = (double)st.framesGpuUnpacked;
+            stats[5] = (double)st.framesGpuBmp;
         }
         if (rc != 0) {
             run->last.error = why;
@@ -484,7 +505,7 @@ int abh_analyze(void *r, const char *ev, int cam, const char *maskdir)
 
 // A whole run (every event of the Run's parser, cameras 0..ncams-1, the Run's trained models) through the batched
 // pipeline into <outdir>abub3hs_<run>.txt; stats: [total_s, list_s, decode_s, gpu_s, write_s, frames, failed,
-// batches, events_per_batch, gpus, frames decoded on the GPU, on host threads, gpudecode_s, packed frames decoded on the GPU].  Returns 0, 1 when the batched path declines the run, -1 on errors.
+// batches, events_per_batch, gpus, frames decoded on the GPU, on host threads, gpudecode_s, packed frames decoded on the GPU, BMP frames decoded on the GPU].  Returns 0, 1 when the batched path declines the run, -1 on errors.
 int abh_run_batched(void *r, int ncams, const char *maskdir, const char *outdir, const char *run_number, int frameOffset,
                     int ngpus, int nthreads, int decodeThreads, int batchMB, int shardRank, int shardWorld, double *statsOut)
 {
@@ -515,9 +536,9 @@ int abh_run_batched(void *r, int ncams, const char *maskdir, const char *outdir,
         if (rc != 0)
             run->last.error = why;
         if (statsOut) {
-            const double v[14] = {bs.total_s, bs.list_s, bs.decode_s, bs.gpu_s, bs.write_s, (double)bs.frames, (double)bs.framesFailed,
+            const double v[15] = {bs.total_s, bs.list_s, bs.decode_s, bs.gpu_s, bs.write_s, (double)bs.frames, (double)bs.framesFailed,
                                   (double)bs.batches, (double)bs.eventsPerBatch, (double)bs.gpus, (double)bs.framesGpuDecoded,
-                                  (double)bs.framesHostDecoded, bs.gpudecode_s, (double)bs.framesGpuUnpacked};
+                                  (double)bs.framesHostDecoded, bs.gpudecode_s, (double)bs.framesGpuUnpacked, (double)bs.framesGpuBmp};
             std::memcpy(statsOut, v, sizeof v);
         }
         return rc;

@@ -194,6 +194,7 @@ int TrainOnDevice(Parser *parser, const std::vector<std::string> &EventList, std
                              [&](int s, int) { return (size_t)s * P; }, [&](int s, int) { good[s] = 1; }, st.framesGpuDecoded,
                              st.framesHostDecoded);
             st.framesGpuUnpacked += fd.unpacked;
+            st.framesGpuBmp += fd.bmpDecoded;
             i0 = i1;
         }
         HIPOK(hipStreamSynchronize(cs));

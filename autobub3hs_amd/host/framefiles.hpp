@@ -1,14 +1,17 @@
-// framefiles.hpp -- frames read as FILES for the GPU decoders (abub_png_decode_dev, abub_abf_decode_dev), shared by the
-// batched detect path (runbatch.cpp) and device training (devtrain.cpp).  A host thread reads each file; a packed frame
-// ("ABF1") whose header is valid for W x H goes to the packed decoder as it is, a PNG has its chunks walked (pngWalk); a
-// file neither takes (BMP, 16-bit, colour, interlaced, another size) gets the host decoder's answer at once, and so
-// does a frame a kernel later returns a nonzero status for.  Internal to the host library.
+// framefiles.hpp -- frames read as FILES for the GPU decoders (abub_png_decode_dev, abub_abf_decode_dev,
+// abub_bmp_decode_dev), shared by the batched detect path (runbatch.cpp), device training (devtrain.cpp) and the device
+// routes of repack, unpack and verify.  A host thread reads each file; a packed frame ("ABF1") whose header is valid for
+// W x H goes to the packed decoder as it is, a PNG has its chunks walked (pngWalk), a BMP its header (bmpWalk, with
+// ABUB_GPU_BMP=1; by default BMP files stay with the reading thread); a file none of them takes
+// (16-bit, colour or interlaced PNG, compressed BMP, another size) gets the host decoder's answer at once, and so does a
+// frame a kernel later returns a nonzero status for.  Internal to the host library.
 #ifndef ABUB3HS_FRAMEFILES_HPP
 #define ABUB3HS_FRAMEFILES_HPP
 
 #include <algorithm>
 #include <atomic>
 #include <cstdint>
+#include <cstdlib>
 #include <cstring>
 #include <exception>
 #include <memory>
@@ -20,6 +23,7 @@
 
 #include "ParseFolder/Parser.hpp"
 #include "abub_hip.h"
+#include "bmpwalk.hpp"
 #include "devctx.hpp"
 #include "holders.hpp"
 #include "pipeline.hpp"
@@ -66,18 +70,21 @@ void forEachTask(Parser *parser, int nthreads, size_t n, const Fn &fn)
 
 // One frame to be read: where it goes is decided by the caller (s, f); `state` says what became of it
 struct FileTask {
-    // Gpu: planned for / taken by the PNG decoder, GpuPacked: taken by the packed decoder; Other: not a file task (the
-    // caller's own work)
-    enum { Gpu = 0, HostDecoded = 1, Bad = 2, Other = 3, GpuPacked = 4 };
-    bool onGpu() const { return state == Gpu || state == GpuPacked; }
+    // Gpu: planned for / taken by the PNG decoder, GpuPacked: taken by the packed decoder, GpuBmp: by the BMP decoder;
+    // Other: not a file task (the caller's own work)
+    enum { Gpu = 0, HostDecoded = 1, Bad = 2, Other = 3, GpuPacked = 4, GpuBmp = 5 };
+    bool onGpu() const { return state == Gpu || state == GpuPacked || state == GpuBmp; }
     int s = 0, f = 0;
     long long size = 0;
     size_t off = 0; // in the pinned file buffer
     int state = Other;
     bool read = false; // the file's bytes are in the buffer (a Bad frame may still have been read)
     PngInfo info;
+    BmpInfo bmp;
     std::vector<uint8_t> pix;
 };
+
+static_assert(sizeof(abub_bmp_frame) == 32, "abub_bmp_frame is the 32 bytes include/abub_hip.h states");
 
 // The descriptors of one decode launch, and the frames a reading thread decoded itself
 struct FileDescs {
@@ -90,7 +97,11 @@ struct FileDescs {
     std::vector<abub_abf_frame> abf;        // the packed frames the GPU decodes (file offset, length, destination)
     std::vector<std::pair<int, int>> abfWhere;
     long long unpacked = 0;                 // of them, decoded by the kernel (finishFileDecode)
-    size_t gpuFrames() const { return desc.size() + abf.size(); }
+    std::vector<abub_bmp_frame> bmp;        // the BMP frames the GPU decodes
+    std::vector<std::pair<int, int>> bmpWhere;
+    std::vector<uint8_t> bmpLuts;           // 256 bytes each
+    long long bmpDecoded = 0;               // of them, decoded by the kernel (finishFileDecode)
+    size_t gpuFrames() const { return desc.size() + abf.size() + bmp.size(); }
     std::vector<std::vector<uint8_t>> hostPix;
     std::vector<std::pair<int, int>> hostWhere;
     long long bad = 0;
@@ -112,6 +123,15 @@ inline bool packedFrameOf(const uint8_t *data, size_t size, int W, int H)
 {
     int w = 0, h = 0;
     return cv::abfProbe(data, size, &w, &h) && w == W && h == H;
+}
+
+// ABUB_GPU_BMP=1: BMP files go to the GPU decoder.  Off by default (BMP files stay with the reading threads, RunBatched's
+// probe does not accept them): results are the same, but the batched run of a BMP directory measured slower with it
+// than without ("BMP frames on the GPU").
+inline bool gpuBmpEnabled()
+{
+    const char *e = getenv("ABUB_GPU_BMP");
+    return e && atoi(e) != 0;
 }
 
 // On a pool thread: the file into files + t.off, walked for the W x H GPU decoder, else decoded here
@@ -136,11 +156,15 @@ inline void readFileTask(Parser &p, const std::string &ev, const std::string &na
             t.state = FileTask::GpuPacked; // (the file goes up as it is; the kernel checks the rest)
             return;
         }
-        if (!pngWalk(dst, (size_t)t.size, W, H, t.info)) {
-            // not a file for the GPU decoder (BMP, 16-bit, colour, interlaced, another size): the host decoder's answer
-            t.pix.resize((size_t)W * H);
-            t.state = cv::imdecodeInto(dst, (size_t)t.size, t.pix.data(), W, H) ? FileTask::HostDecoded : FileTask::Bad;
+        if (pngWalk(dst, (size_t)t.size, W, H, t.info))
+            return;
+        if (gpuBmpEnabled() && bmpWalk(dst, (size_t)t.size, W, H, t.bmp)) {
+            t.state = FileTask::GpuBmp;
+            return;
         }
+        // not a file for the GPU decoders (16-bit, colour, interlaced, another size): the host decoder's answer
+        t.pix.resize((size_t)W * H);
+        t.state = cv::imdecodeInto(dst, (size_t)t.size, t.pix.data(), W, H) ? FileTask::HostDecoded : FileTask::Bad;
     } catch (...) { // (an allocation that fails inside a pool thread must not end the batch)
         t.state = FileTask::Bad;
     }
@@ -169,6 +193,29 @@ void buildFileDescs(FileTask *first, FileTask *last, size_t totalFileBytes, File
         if (t.state == FileTask::GpuPacked) {
             r.abf.push_back(abub_abf_frame{(uint32_t)t.off, (uint32_t)t.size, dstOf(t.s, t.f)});
             r.abfWhere.emplace_back(t.s, t.f);
+            continue;
+        }
+        if (t.state == FileTask::GpuBmp) {
+            abub_bmp_frame b;
+            b.off = (uint32_t)t.off;
+            b.len = (uint32_t)t.size;
+            b.data_off = t.bmp.dataOff;
+            b.stride = t.bmp.stride;
+            b.bpp = (uint16_t)t.bmp.bpp;
+            b.flags = t.bmp.topDown ? 1 : 0;
+            b.lut = 0xffffffffu;
+            b.dst = dstOf(t.s, t.f);
+            if (t.bmp.bpp <= 8 && !t.bmp.identity) { // (as the PNG tables below: the frames of a run share one)
+                size_t nl = r.bmpLuts.size() / 256, l = 0;
+                for (; l < nl; ++l)
+                    if (!memcmp(&r.bmpLuts[l * 256], t.bmp.lut, 256))
+                        break;
+                if (l == nl)
+                    r.bmpLuts.insert(r.bmpLuts.end(), t.bmp.lut, t.bmp.lut + 256);
+                b.lut = (uint32_t)l;
+            }
+            r.bmp.push_back(b);
+            r.bmpWhere.emplace_back(t.s, t.f);
             continue;
         }
         abub_png_frame d;
@@ -207,6 +254,8 @@ struct PngScratch {
     PinnedBuffer h_status;
     DeviceBuffer abfDesc, abfStatus; // the packed decoder needs no more than its descriptors and statuses
     PinnedBuffer h_abfStatus;
+    DeviceBuffer bmpDesc, bmpLuts, bmpStatus; // the BMP decoder: descriptors, tables, statuses
+    PinnedBuffer h_bmpStatus;
 };
 
 // One abub_abf_decode_dev launch over r's packed frames, as launchPngDecode below
@@ -227,9 +276,30 @@ inline void launchAbfDecode(const FileDescs &r, const uint8_t *d_files, int W, i
     HIPOK(hipMemcpyAsync(sc.h_abfStatus.get(), sc.abfStatus.get(), (size_t)nf * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
 }
 
+// One abub_bmp_decode_dev launch over r's BMP frames, likewise
+inline void launchBmpDecode(const FileDescs &r, const uint8_t *d_files, int W, int H, uint8_t *out, size_t out_bytes,
+                            PngScratch &sc, hipStream_t stream)
+{
+    const int nf = (int)r.bmp.size();
+    if (!nf)
+        return;
+    sc.bmpDesc.grow((size_t)nf * sizeof(abub_bmp_frame));
+    sc.bmpStatus.grow((size_t)nf * sizeof(int32_t));
+    sc.bmpLuts.grow(r.bmpLuts.size() + 256);
+    if (sc.h_bmpStatus.capacity() < (size_t)nf * sizeof(int32_t))
+        sc.h_bmpStatus.allocate((size_t)nf * sizeof(int32_t) + 64);
+    HIPOK(hipMemcpyAsync(sc.bmpDesc.get(), r.bmp.data(), (size_t)nf * sizeof(abub_bmp_frame), hipMemcpyHostToDevice, stream));
+    if (!r.bmpLuts.empty())
+        HIPOK(hipMemcpyAsync(sc.bmpLuts.get(), r.bmpLuts.data(), r.bmpLuts.size(), hipMemcpyHostToDevice, stream));
+    check(abub_bmp_decode_dev(d_files, r.bytes, (const abub_bmp_frame *)sc.bmpDesc.get(), nf, sc.bmpLuts.get(),
+                              (int)(r.bmpLuts.size() / 256), W, H, out, out_bytes, (int32_t *)sc.bmpStatus.get(), stream),
+          "abub_bmp_decode_dev");
+    HIPOK(hipMemcpyAsync(sc.h_bmpStatus.get(), sc.bmpStatus.get(), (size_t)nf * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+}
+
 // One launch of each decoder that has frames in r, into `out` (out_bytes), the statuses copied back into sc.h_status /
-// sc.h_abfStatus; both queued on `stream` (so both stay behind whatever the caller queued there before, the clear of the
-// batch's slab for one), not waited for.  The files are already in d_files.
+// sc.h_abfStatus / sc.h_bmpStatus; all queued on `stream` (so they stay behind whatever the caller queued there before, the
+// clear of the batch's slab for one), not waited for.  The files are already in d_files.
 inline void launchPngDecode(const FileDescs &r, const uint8_t *d_files, int W, int H, uint8_t *out, size_t out_bytes,
                             PngScratch &sc, hipStream_t stream);
 inline void launchFileDecode(const FileDescs &r, const uint8_t *d_files, int W, int H, uint8_t *out, size_t out_bytes,
@@ -237,6 +307,7 @@ inline void launchFileDecode(const FileDescs &r, const uint8_t *d_files, int W, 
 {
     launchPngDecode(r, d_files, W, H, out, out_bytes, sc, stream);
     launchAbfDecode(r, d_files, W, H, out, out_bytes, sc, stream);
+    launchBmpDecode(r, d_files, W, H, out, out_bytes, sc, stream);
 }
 inline void launchPngDecode(const FileDescs &r, const uint8_t *d_files, int W, int H, uint8_t *out, size_t out_bytes,
                             PngScratch &sc, hipStream_t stream)
@@ -266,7 +337,7 @@ inline void launchPngDecode(const FileDescs &r, const uint8_t *d_files, int W, i
 // After the launches above have been waited for: a frame the kernels refused takes the host decoder's answer (the same
 // image, or the same failure), and the reading threads' own frames are uploaded.  ok(s, f) is called for every frame that
 // is in place; hostOffset(s, f): byte offset of the frame from `out`.  Packed frames the kernel decoded count in onGpu
-// and in r.unpacked.
+// and in r.unpacked, BMP frames the kernel decoded in onGpu and in r.bmpDecoded.
 template <class HostOffset, class Ok>
 void finishFileDecode(FileDescs &r, const uint8_t *h_files, const PngScratch &sc, uint8_t *out, int W, int H,
                       hipStream_t stream, const HostOffset &hostOffset, const Ok &ok, long long &onGpu, long long &onHost)
@@ -293,10 +364,13 @@ void finishFileDecode(FileDescs &r, const uint8_t *h_files, const PngScratch &sc
         return false;
     };
     const int32_t *status = (const int32_t *)sc.h_status.get(), *abfStatus = (const int32_t *)sc.h_abfStatus.get();
+    const int32_t *bmpStatus = (const int32_t *)sc.h_bmpStatus.get();
     for (size_t i = 0; i < r.desc.size(); ++i)
         settle(status[i], r.where[i], r.desc[i].dst, r.fileOff[i], r.fileLen[i]);
     for (size_t i = 0; i < r.abf.size(); ++i)
         r.unpacked += settle(abfStatus[i], r.abfWhere[i], r.abf[i].dst, r.abf[i].off, r.abf[i].len);
+    for (size_t i = 0; i < r.bmp.size(); ++i)
+        r.bmpDecoded += settle(bmpStatus[i], r.bmpWhere[i], r.bmp[i].dst, r.bmp[i].off, r.bmp[i].len);
     for (size_t i = 0; i < r.hostPix.size(); ++i) {
         HIPOK(hipMemcpy(out + hostOffset(r.hostWhere[i].first, r.hostWhere[i].second), r.hostPix[i].data(), P,
                         hipMemcpyHostToDevice));

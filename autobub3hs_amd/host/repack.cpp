@@ -266,7 +266,8 @@ void deviceFrames(const Codec &codec, Parser *parser, const Plan &pl, int nthrea
             finishFileDecode(fd, h_files.get(), png, slab.get(), W, H, cs, [&](int s, int) { return (size_t)s * P; },
                              [&](int s, int) { good[s] = 1; }, onGpu, onHost);
             st.framesGpuUnpacked += fd.unpacked;
-            st.framesGpuPngDecoded += onGpu - fd.unpacked;
+            st.framesGpuBmpDecoded += fd.bmpDecoded;
+            st.framesGpuPngDecoded += onGpu - fd.unpacked - fd.bmpDecoded;
             st.framesHostDecoded += onHost;
             for (size_t i = 0; i < n; ++i)
                 if (good[i]) {

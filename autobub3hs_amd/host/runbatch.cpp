@@ -166,9 +166,10 @@ int runBatchedOn(Workers &ws, Parser *parser, const std::vector<std::string> &Ev
     }
     G = std::min(G, 512);
     // ---- where the frames are decoded --------------------------------------------------------------------------------
-    // On the GPU (abub_png.hip, abub_abf.hip) when the parser hands out the files as they are stored and the first frame is
-    // a PNG the kernels take or a packed frame; a host thread still reads each file, walks a PNG's chunks, and decodes the
-    // odd frame the GPU path refuses.  Otherwise host threads decode every frame (GetImageInto).  The width gate is the
+    // On the GPU (abub_png.hip, abub_abf.hip, abub_bmp.hip) when the parser hands out the files as they are stored and the
+    // first frame is a PNG the kernels take, a packed frame or, with ABUB_GPU_BMP=1, a BMP the host decoder reads; a host
+    // thread still reads each file, walks a PNG's chunks or a BMP's header, and decodes the odd frame the GPU path refuses.
+    // Otherwise host threads decode every frame (GetImageInto).  The width gate is the
     // PNG kernels': it holds for packed frames too, although abub_abf_decode_dev takes any width.
     bool devDecode = opt.gpuDecode != 0 && (W & 3) == 0 && W >= 4 && W <= 2048;
     if (const char *e = getenv("ABUB_GPU_DECODE"))
@@ -183,8 +184,10 @@ int runBatchedOn(Workers &ws, Parser *parser, const std::vector<std::string> &Ev
                     if (sz > 0 && sz < ((long long)1 << 30)) {
                         std::vector<unsigned char> buf((size_t)sz);
                         PngInfo info;
+                        BmpInfo bmp;
                         devDecode = p->ReadImageFile(EventList[mine[k]], lists[k][c][0], buf.data(), buf.size()) == sz &&
-                                    (pngWalk(buf.data(), buf.size(), W, H, info) || packedFrameOf(buf.data(), buf.size(), W, H));
+                                    (pngWalk(buf.data(), buf.size(), W, H, info) || packedFrameOf(buf.data(), buf.size(), W, H) ||
+                                     (gpuBmpEnabled() && bmpWalk(buf.data(), buf.size(), W, H, bmp)));
                     }
                     k = lists.size(); // (one probe decides)
                     break;
@@ -445,6 +448,7 @@ int runBatchedOn(Workers &ws, Parser *parser, const std::vector<std::string> &Ev
                     st.framesGpuDecoded += onGpu;
                     st.framesHostDecoded += onHost;
                     st.framesGpuUnpacked += R.files.unpacked;
+                    st.framesGpuBmp += R.files.bmpDecoded;
                     st.gpudecode_s += pngms * 1e-3;
                 }
                 slot ^= 1;

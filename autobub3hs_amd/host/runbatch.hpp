@@ -40,6 +40,7 @@ struct BatchedRunStats {
     long long bellowsVetoed = 0; // stacks whose bellows-movement veto ran inside the batch (pipeline veto round)
     long long framesGpuDecoded = 0, framesHostDecoded = 0; // of `frames`: by the GPU decoders / by a host thread
     long long framesGpuUnpacked = 0;                       // of framesGpuDecoded: packed frames, by abub_abf_decode_dev
+    long long framesGpuBmp = 0;                            // of framesGpuDecoded: BMP frames, by abub_bmp_decode_dev
     double gpudecode_s = 0;                                // upload of the files + the decode kernels, summed over batches
     int events = 0, batches = 0, eventsPerBatch = 0, W = 0, H = 0, Fmax = 0, gpus = 0;
 };
@@ -80,10 +81,10 @@ struct RepackStats {
     double total_s = 0;
     // Of all frames (packed + copied + failed): framesGpuEncoded were packed by abub_abf_encode_dev, framesHostRoute by a
     // host thread (or copied, or not written) -- every frame of RepackRun, and of a run outside the decoders' width gate.
-    // Of framesGpuEncoded: decoded by abub_png_decode_dev, by abub_abf_decode_dev, or by a host thread after a kernel
-    // refused the file.
+    // Of framesGpuEncoded: decoded by abub_png_decode_dev, by abub_abf_decode_dev, by abub_bmp_decode_dev, or by a host
+    // thread after a kernel refused the file.
     long long framesGpuEncoded = 0, framesHostRoute = 0;
-    long long framesGpuPngDecoded = 0, framesGpuUnpacked = 0, framesHostDecoded = 0;
+    long long framesGpuPngDecoded = 0, framesGpuUnpacked = 0, framesHostDecoded = 0, framesGpuBmpDecoded = 0;
     int device = -1, W = 0, H = 0, batches = 0;   // of the device route (device -1: it was not taken)
     double read_s = 0, decode_s = 0, encode_s = 0, copy_s = 0, write_s = 0; // its legs, summed over the batches
 };
@@ -135,10 +136,12 @@ struct VerifyStats {
     double total_s = 0;
     // Of the device route (device -1: it was not taken).  Of `frames`: framesKernel were compared by
     // abub_frames_compare_dev, framesHostRoute by a host thread.  Of the frames the decoders were given, per side: by
-    // abub_png_decode_dev, by abub_abf_decode_dev, or by a host thread (a file the kernels do not take or refused).
+    // abub_png_decode_dev, by abub_abf_decode_dev, by abub_bmp_decode_dev, or by a host thread (a file the kernels do not
+    // take or refused).
     long long framesKernel = 0, framesHostRoute = 0;
     long long srcGpuPngDecoded = 0, srcGpuUnpacked = 0, srcHostDecoded = 0;
     long long otherGpuPngDecoded = 0, otherGpuUnpacked = 0, otherHostDecoded = 0;
+    long long srcGpuBmpDecoded = 0, otherGpuBmpDecoded = 0;
     int device = -1, W = 0, H = 0, batches = 0;
     double read_s = 0, decode_s = 0, compare_s = 0; // its legs, summed over the batches
     const char *eventFileName() const;              // "same", "differs", "missing", "not compared"

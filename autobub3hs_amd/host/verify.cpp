@@ -226,7 +226,7 @@ struct Side {
     size_t total = 0;
     FileDescs fd;
     std::vector<uint8_t> good;
-    long long gpuPng = 0, gpuUnpacked = 0, hostDecoded = 0;
+    long long gpuPng = 0, gpuUnpacked = 0, gpuBmp = 0, hostDecoded = 0;
 
     void upload(size_t n, size_t stride, hipStream_t cs)
     {
@@ -250,7 +250,8 @@ struct Side {
         finishFileDecode(fd, h_files.get(), png, slab.get(), W, H, cs, [&](int s, int) { return (size_t)s * stride; },
                          [&](int s, int) { good[s] = 1; }, onGpu, onHost);
         gpuUnpacked += fd.unpacked;
-        gpuPng += onGpu - fd.unpacked;
+        gpuBmp += fd.bmpDecoded;
+        gpuPng += onGpu - fd.unpacked - fd.bmpDecoded;
         hostDecoded += onHost;
     }
 };
@@ -380,6 +381,8 @@ void deviceFrames(Parser *src, Parser *other, const Plan &pl, int nthreads, int 
     st.otherGpuPngDecoded = O.gpuPng;
     st.otherGpuUnpacked = O.gpuUnpacked;
     st.otherHostDecoded = O.hostDecoded;
+    st.srcGpuBmpDecoded = S.gpuBmp;
+    st.otherGpuBmpDecoded = O.gpuBmp;
 }
 
 // 0 .. 3 of VerifyStats::EventFile

@@ -556,6 +556,34 @@ typedef struct abub_abf_frame {
 int abub_abf_decode_dev(const uint8_t *files, size_t files_bytes, const abub_abf_frame *frames, int nframes, int W, int H,
                         uint8_t *out, size_t out_bytes, int32_t *status, void *stream);
 
+/* ---- BMP frames decoded on the GPU (abub_bmp.hip) -------------------------------------------------------------------
+ * Replaces the cv::imread / cv::imdecode of a BMP frame (RawParser.cpp:34-47, ZipParser.cpp:186-239) for the series whose
+ * cameras wrote BMP; host definition: decodeBMP (host/cvlite.cpp), bit for bit.  The caller uploads the FILES as they are
+ * on disk and walks each header on the host (host/bmpwalk.hpp); the kernel never reads a header and believes the descriptor
+ * alone, which every wave of a frame checks against the stated sizes before it reads a pixel: off + len <= files_bytes,
+ * data_off + stride * H <= len, stride >= ceil(W * bpp / 8), bpp one of the five, lut == 0xffffffff or < nluts,
+ * dst + W * H <= out_bytes.  A frame that fails one gets ABUB_BMP_E_DESC and not one byte of `out`; nothing is read
+ * outside `files`, nothing written outside a frame's own W*H bytes.  Output row y is stored row (top-down ? y : H-1-y);
+ * 8, 4 (high nibble first) and 1 bit (bit 7 first) pixels go through the frame's table (or stay the index), 24 and 32 bit
+ * pixels are (b*1868 + g*9617 + r*4899 + 8192) >> 14 of bytes 0, 1, 2. */
+typedef struct abub_bmp_frame {
+    uint32_t off, len;   /* the file inside `files` */
+    uint32_t data_off;   /* of the pixel array inside the file */
+    uint32_t stride;     /* bytes from one stored row to the next */
+    uint16_t bpp, flags; /* 1 | 4 | 8 | 24 | 32; bit 0: top-down */
+    uint32_t lut;        /* index of a 256-byte table, 0xffffffff = none (identity / no palette) */
+    uint64_t dst;        /* byte offset of the W*H frame in `out` (no alignment rule) */
+} abub_bmp_frame;        /* 32 bytes */
+/* status[frame] after abub_bmp_decode_dev: 0 = decoded */
+#define ABUB_BMP_E_DESC 1 /* descriptor outside the stated sizes, or not a shape the kernel takes */
+/* One launch per batch; every pointer is a device pointer; luts[nluts][256] may be null only when nluts == 0; W, H in
+ * [1, 65535]; status[nframes] is written for every frame.  Null pointers, negative counts and W or H out of range:
+ * ABUB_E_INVALID before anything touches the device; nframes == 0: ABUB_OK, nothing touched.  No host synchronisation,
+ * no allocation. */
+int abub_bmp_decode_dev(const uint8_t *files, size_t files_bytes, const abub_bmp_frame *frames, int nframes,
+                        const uint8_t *luts, int nluts, int W, int H, uint8_t *out, size_t out_bytes, int32_t *status,
+                        void *stream);
+
 /* ---- packed frames ("ABF1") encoded on the GPU (abub_abf_enc.hip) -------------------------------------------------
  * What cv::abfEncode does on a host thread, for a batch of resident frames: file f is exactly the bytes
  * cv::abfEncode(pixels + src[f], W, H) writes (the host encoder is canonical: smallest width per block, zero padding
