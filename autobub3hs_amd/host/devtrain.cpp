@@ -103,15 +103,21 @@ int TrainOnDevice(Parser *parser, const std::vector<std::string> &EventList, std
     // ---- read / walk / decode ------------------------------------------------------------------------------------------
     // GPU decode where the parser hands out the files and the width is one the PNG kernels take (packed frames too); other frames are decoded by
     // the reading threads (GetImage, as the host path does)
-    bool devDecode = W > 0 && opt.gpuDecode != 0 && (W & 3) == 0 && W >= 4 && W <= 2048;
-    if (const char *e = getenv("ABUB_GPU_DECODE"))
-        devDecode = devDecode && atoi(e) != 0;
-    std::vector<FileTask> tasks;
-    std::vector<uint8_t> good(nslots, 0), otherSize(nslots, 0);
+    const bool devDecode = gpuDecodeWanted(opt.gpuDecode, W);
+    DeviceTrainBuffers own;
+    DeviceTrainBuffers &B = opt.buffers ? *opt.buffers : own;
+    FileBatch &batch = B.batch;
+    std::vector<FileTask> &tasks = batch.ft;
+    const std::vector<uint8_t> &good = batch.good;
+    std::vector<uint8_t> otherSize(nslots, 0);
     std::vector<std::string> frameError(nslots);
-    size_t total = 0;
+    size_t &total = batch.total;
+    tasks.clear();
+    total = 0;
+    std::fill(batch.decodedBy, batch.decodedBy + NGpuCodecs, 0);
+    batch.hostDecoded = 0;
     if (W) {
-        std::unique_ptr<Parser> sizer(parser->clone());
+        batch.sizer.reset(parser->clone());
         for (int c = 0; c < C; ++c) {
             if (!camError[c].empty())
                 continue;
@@ -121,16 +127,14 @@ int TrainOnDevice(Parser *parser, const std::vector<std::string> &EventList, std
                         FileTask t;
                         t.s = (c * E + e) * Q + q;
                         if (devDecode)
-                            planFileTask(*sizer, EventList[e], *n, t, total);
+                            planFileTask(*batch.sizer, EventList[e], *n, t, total);
                         if (!devDecode || t.state == FileTask::Bad)
                             t.state = FileTask::Other; // decoded by GetImage below (a parser that has no files to hand out)
                         tasks.push_back(std::move(t));
                     }
         }
     }
-    DeviceTrainBuffers own;
-    DeviceTrainBuffers &B = opt.buffers ? *opt.buffers : own;
-    PinnedBuffer &h_files = B.h_files;
+    PinnedBuffer &h_files = batch.h_files;
     if (total)
         h_files.grow(total + 16);
     forEachTask(parser, nthr, tasks.size(), [&](Parser &p, size_t i) {
@@ -168,33 +172,22 @@ int TrainOnDevice(Parser *parser, const std::vector<std::string> &EventList, std
     if (W) {
         HIPOK(hipSetDevice(opt.device));
         hipStream_t cs = B.stream.get();
-        B.slab.grow(slab);
-        HIPOK(hipMemsetAsync(B.slab.get(), 0, slab, cs)); // (frames nobody decodes stay zero)
-        if (total) {
-            B.files.grow(total + 16);
-            HIPOK(hipMemcpyAsync(B.files.get(), h_files.get(), total + 16, hipMemcpyHostToDevice, cs));
-        }
+        batch.reset(nslots, slab);
+        HIPOK(hipMemsetAsync(batch.slab.get(), 0, slab, cs)); // (frames nobody decodes stay zero)
+        batch.upload(cs);
         // decode launches of at most 4 frames per CU, as RunBatched's batches: the decoder's scratch stays bounded
-        int ncu = 256, v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, opt.device) == hipSuccess && v > 0)
-            ncu = v;
-        const size_t perLaunch = (size_t)4 * ncu;
+        const size_t perLaunch = framesPerBatch(opt.device);
         for (size_t i0 = 0; i0 < tasks.size();) {
             size_t i1 = i0, ngpu = 0;
             for (; i1 < tasks.size() && (ngpu < perLaunch || !tasks[i1].onGpu()); ++i1)
                 ngpu += tasks[i1].onGpu();
-            FileDescs fd;
-            buildFileDescs(tasks.data() + i0, tasks.data() + i1, total, fd, [&](int s, int) { return (uint64_t)s * P; });
-            if (fd.gpuFrames()) {
-                launchFileDecode(fd, B.files.get(), W, H, B.slab.get(), slab, B.png, cs);
-                ++st.decodeLaunches;
-            }
+            st.decodeLaunches += batch.launch(i0, i1, W, H, [&](int s, int) { return (uint64_t)s * P; }, cs);
             HIPOK(hipStreamSynchronize(cs));
-            finishFileDecode(fd, h_files.get(), B.png, B.slab.get(), W, H, cs,
-                             [&](int s, int) { return (size_t)s * P; }, [&](int s, int) { good[s] = 1; }, st.framesGpuDecoded,
-                             st.framesHostDecoded);
-            st.framesGpuUnpacked += fd.unpacked;
-            st.framesGpuBmp += fd.bmpDecoded;
+            batch.finish(W, H, cs);
+            st.framesGpuDecoded = std::accumulate(batch.decodedBy, batch.decodedBy + NGpuCodecs, 0LL);
+            st.framesGpuUnpacked = batch.decodedBy[GpuPacked];
+            st.framesGpuBmp = batch.decodedBy[GpuBmp];
+            st.framesHostDecoded = batch.hostDecoded;
             i0 = i1;
         }
         HIPOK(hipStreamSynchronize(cs));
@@ -219,7 +212,7 @@ int TrainOnDevice(Parser *parser, const std::vector<std::string> &EventList, std
             HIPOK(hipMemcpyAsync(B.pairs.get(), pairs.data(), pairs.size() * sizeof(abub_job), hipMemcpyHostToDevice, cs));
             for (size_t k0 = 0; k0 < pairs.size(); k0 += 65535) {
                 const int n = (int)std::min<size_t>(65535, pairs.size() - k0);
-                check(abub_pair_hist_dev(B.slab.get(), (const abub_job *)B.pairs.get() + k0, n, W, H,
+                check(abub_pair_hist_dev(batch.slab.get(), (const abub_job *)B.pairs.get() + k0, n, W, H,
                                          (uint32_t *)B.hist.get() + k0 * 256, cs),
                       "abub_pair_hist_dev");
             }
@@ -282,7 +275,7 @@ int TrainOnDevice(Parser *parser, const std::vector<std::string> &EventList, std
                 continue;
             }
             HIPOK(hipMemcpyAsync(B.idx.get(), kept.data(), kept.size() * sizeof(uint32_t), hipMemcpyHostToDevice, cs));
-            check(abub_train_dev(B.slab.get(), (const uint32_t *)B.idx.get(), (int)kept.size(), W, H, B.mu.get(),
+            check(abub_train_dev(batch.slab.get(), (const uint32_t *)B.idx.get(), (int)kept.size(), W, H, B.mu.get(),
                                  B.sigma.get(), cs),
                   "abub_train_dev");
             T.TrainedAvgImage.create(H, W, CV_8U);

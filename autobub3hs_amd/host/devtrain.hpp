@@ -19,9 +19,8 @@ namespace abub {
 // What TrainOnDevice allocates, kept by a caller that trains run after run (RunCampaign): the pinned file buffer is
 // page-locked once, not per run.  Declaration order: the stream finishes its work before the buffers go.
 struct DeviceTrainBuffers {
-    PinnedBuffer h_files;
-    DeviceBuffer slab, files, pairs, hist, idx, mu, sigma;
-    PngScratch png;
+    FileBatch batch; // the training frames' files, the decoders' scratch, the slab
+    DeviceBuffer pairs, hist, idx, mu, sigma;
     Stream stream;
 };
 

@@ -205,31 +205,32 @@ void deviceFrames(const Codec &codec, Parser *parser, const Plan &pl, int nthrea
             perBatch = std::min(perBatch, (size_t)v);
     }
     const size_t P = (size_t)W * H;
-    PinnedBuffer h_files, h_meta;
-    DeviceBuffer d_files, slab, d_meta, scratch;
-    PngScratch png;
+    FileBatch B; // the batch's files, the decoders' scratch, the slab of decoded frames (frame i at i * P)
+    std::vector<FileTask> &ft = B.ft;
+    PinnedBuffer h_meta;
+    DeviceBuffer d_meta, scratch;
     GrowList<uint8_t> out(4096, 1, SIZE_MAX); // the packed files of a batch, on the device and in pinned memory
     Stream stream;
     hipStream_t cs = stream.get();
-    std::unique_ptr<Parser> sizer(parser->clone());
+    B.sizer.reset(parser->clone());
 
     for (size_t i0 = 0; i0 < pl.tasks.size(); i0 += perBatch) {
         const size_t n = std::min(perBatch, pl.tasks.size() - i0);
         // ---- read -------------------------------------------------------------------------------------------------------
         double t0 = nowMs();
-        std::vector<FileTask> ft(n);
-        size_t total = 0;
+        ft.assign(n, FileTask());
+        B.total = 0;
         for (size_t i = 0; i < n; ++i) {
             const Task &t = pl.tasks[i0 + i];
             ft[i].s = (int)i;
-            planFileTask(*sizer, pl.events[t.ev], t.name, ft[i], total);
+            planFileTask(*B.sizer, pl.events[t.ev], t.name, ft[i], B.total);
         }
-        h_files.grow(total + 16);
+        B.h_files.grow(B.total + 16);
         forEachTask(parser, nthreads, n, [&](Parser &p, size_t i) {
             const Task &t = pl.tasks[i0 + i];
             FileTask &f = ft[i];
             const std::string &ev = pl.events[t.ev];
-            readFileTask(p, ev, t.name, f, h_files.get(), W, H);
+            readFileTask(p, ev, t.name, f, B.h_files.get(), W, H);
             if (f.onGpu())
                 return;
             if (f.state == FileTask::HostDecoded) { // (16-bit, colour, BMP: this thread decoded it at W x H)
@@ -241,7 +242,7 @@ void deviceFrames(const Codec &codec, Parser *parser, const Plan &pl, int nthrea
                 o.out = (long long)packed.size();
                 tally.add(o);
             } else if (f.read) // another size, or a file that does not decode
-                tally.add(packBytes(codec, h_files.get() + f.off, (size_t)f.size, pl.pathOf(t)));
+                tally.add(packBytes(codec, B.h_files.get() + f.off, (size_t)f.size, pl.pathOf(t)));
             else               // a file the parser does not hand out in one piece
                 tally.add(hostFrame(codec, p, ev, t.name, pl.pathOf(t)));
             f.pix = std::vector<uint8_t>();
@@ -251,26 +252,19 @@ void deviceFrames(const Codec &codec, Parser *parser, const Plan &pl, int nthrea
 
         // ---- upload and decode ------------------------------------------------------------------------------------------
         t0 = nowMs();
-        FileDescs fd;
-        buildFileDescs(ft.data(), ft.data() + n, total, fd, [&](int s, int) { return (uint64_t)s * P; });
-        std::vector<uint8_t> good(n, 0);
         std::vector<uint64_t> src;
         std::vector<size_t> slot;
-        if (fd.gpuFrames()) {
-            slab.grow(n * P);
-            d_files.grow(total + 16);
-            HIPOK(hipMemcpyAsync(d_files.get(), h_files.get(), total + 16, hipMemcpyHostToDevice, cs));
-            launchFileDecode(fd, d_files.get(), W, H, slab.get(), n * P, png, cs);
+        B.reset(n, n * P);
+        B.upload(cs);
+        if (B.launch(0, n, W, H, [&](int s, int) { return (uint64_t)s * P; }, cs)) {
             HIPOK(hipStreamSynchronize(cs));
-            long long onGpu = 0, onHost = 0;
-            finishFileDecode(fd, h_files.get(), png, slab.get(), W, H, cs, [&](int s, int) { return (size_t)s * P; },
-                             [&](int s, int) { good[s] = 1; }, onGpu, onHost);
-            st.framesGpuUnpacked += fd.unpacked;
-            st.framesGpuBmpDecoded += fd.bmpDecoded;
-            st.framesGpuPngDecoded += onGpu - fd.unpacked - fd.bmpDecoded;
-            st.framesHostDecoded += onHost;
+            B.finish(W, H, cs);
+            st.framesGpuPngDecoded = B.decodedBy[GpuPng];
+            st.framesGpuUnpacked = B.decodedBy[GpuPacked];
+            st.framesGpuBmpDecoded = B.decodedBy[GpuBmp];
+            st.framesHostDecoded = B.hostDecoded;
             for (size_t i = 0; i < n; ++i)
-                if (good[i]) {
+                if (B.good[i]) {
                     src.push_back((uint64_t)i * P);
                     slot.push_back(i);
                 }
@@ -294,9 +288,9 @@ void deviceFrames(const Codec &codec, Parser *parser, const Plan &pl, int nthrea
             uint64_t *d_total = (uint64_t *)(d_rec + ng);
             files = (const abub_abf_file *)(h_meta.get() + ng * sizeof(uint64_t));
             out.newBatch();
-            out.reserve(total + 64 * ng); // (a packed frame is about the size of its PNG)
+            out.reserve(B.total + 64 * ng); // (a packed frame is about the size of its PNG)
             for (;;) {
-                check(codec.encodeDev(slab.get(), n * P, (const uint64_t *)d_meta.get(), (int)ng, W, H, out.d, out.cap(), d_rec,
+                check(codec.encodeDev(B.slab.get(), n * P, (const uint64_t *)d_meta.get(), (int)ng, W, H, out.d, out.cap(), d_rec,
                                       d_total, scratch.get(), scratch.capacity(), cs),
                       codec.devName);
                 HIPOK(hipMemcpyAsync(h_meta.get() + ng * sizeof(uint64_t), d_rec, ng * sizeof(abub_abf_file) + sizeof(uint64_t),
@@ -324,7 +318,7 @@ void deviceFrames(const Codec &codec, Parser *parser, const Plan &pl, int nthrea
             if (ft[i].state == FileTask::Other)
                 return; // (written by the thread that read it)
             if (fileOf[i] == SIZE_MAX) {
-                tally.add(packBytes(codec, h_files.get() + ft[i].off, (size_t)ft[i].size, pl.pathOf(t)));
+                tally.add(packBytes(codec, B.h_files.get() + ft[i].off, (size_t)ft[i].size, pl.pathOf(t)));
                 return;
             }
             const abub_abf_file &r = files[fileOf[i]];

@@ -79,7 +79,7 @@ struct Slot {
 struct WorkerCache {
     Slot slots[2];
     DeviceBuffer d_model; // mu | sigma | sigma6
-    PngScratch png;       // the GPU decoder's scratch
+    DecodeScratch scratch; // the GPU decoders' scratch
     Stream copyStream, upStream;
     struct Pipe {
         std::vector<long long> key;
@@ -171,9 +171,7 @@ int runBatchedOn(Workers &ws, Parser *parser, const std::vector<std::string> &Ev
     // thread still reads each file, walks a PNG's chunks or a BMP's header, and decodes the odd frame the GPU path refuses.
     // Otherwise host threads decode every frame (GetImageInto).  The width gate is the
     // PNG kernels': it holds for packed frames too, although abub_abf_decode_dev takes any width.
-    bool devDecode = opt.gpuDecode != 0 && (W & 3) == 0 && W >= 4 && W <= 2048;
-    if (const char *e = getenv("ABUB_GPU_DECODE"))
-        devDecode = devDecode && atoi(e) != 0;
+    bool devDecode = gpuDecodeWanted(opt.gpuDecode, W);
     if (devDecode) {
         devDecode = false;
         for (size_t k = 0; k < lists.size() && !devDecode; ++k)
@@ -183,11 +181,9 @@ int runBatchedOn(Workers &ws, Parser *parser, const std::vector<std::string> &Ev
                     const long long sz = p->GetImageFileSize(EventList[mine[k]], lists[k][c][0]);
                     if (sz > 0 && sz < ((long long)1 << 30)) {
                         std::vector<unsigned char> buf((size_t)sz);
-                        PngInfo info;
-                        BmpInfo bmp;
+                        FileTask probe;
                         devDecode = p->ReadImageFile(EventList[mine[k]], lists[k][c][0], buf.data(), buf.size()) == sz &&
-                                    (pngWalk(buf.data(), buf.size(), W, H, info) || packedFrameOf(buf.data(), buf.size(), W, H) ||
-                                     (gpuBmpEnabled() && bmpWalk(buf.data(), buf.size(), W, H, bmp)));
+                                    gpuCodecOf(buf.data(), buf.size(), W, H, probe);
                     }
                     k = lists.size(); // (one probe decides)
                     break;
@@ -195,18 +191,12 @@ int runBatchedOn(Workers &ws, Parser *parser, const std::vector<std::string> &Ev
     }
     int Ggpu = 0; // the first Ggpu events of a batch are decoded on the GPU, the others by the host threads
     if (devDecode) {
-        // The inflate kernel runs four streams per CU at a time (1024 on an MI355X) and a batch takes as long as its longest
-        // stream: batches carry that many frames for the GPU, not one more.
-        int ncu = 256;
-        {
-            int dev0 = opt.firstDevice, v = 0, nd = 0;
-            if (hipGetDeviceCount(&nd) == hipSuccess && nd > 0 &&
-                hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev0 % nd) == hipSuccess && v > 0)
-                ncu = v;
-        }
+        // batches carry framesPerBatch frames for the GPU (1024 on an MI355X), not one more
+        int nd = 0;
+        const int perBatch = (int)framesPerBatch(hipGetDeviceCount(&nd) == hipSuccess && nd > 0 ? opt.firstDevice % nd : 0);
         const int perEv = std::max(1, C * Fmax);
         const int capG = (int)std::max<size_t>(1, opt.batchBytes / perEvent);
-        Ggpu = std::max(1, std::min((4 * ncu) / perEv, std::min(capG, (int)mine.size())));
+        Ggpu = std::max(1, std::min(perBatch / perEv, std::min(capG, (int)mine.size())));
         if (const char *e = getenv("ABUB_GPU_DECODE_EVENTS")) // (tests: a small GPU share)
             Ggpu = std::max(1, std::min(Ggpu, atoi(e)));
         // The host threads can decode the frames of a few more events per batch while the GPU works (they only READ the
@@ -297,7 +287,7 @@ int runBatchedOn(Workers &ws, Parser *parser, const std::vector<std::string> &Ev
         // joined after it on every path.
         WorkerCache &wc = *ws.w[g];
         Slot *slots = wc.slots;
-        PngScratch &png = wc.png;
+        DecodeScratch &scratch = wc.scratch;
         Stream &copyStream = wc.copyStream, &upStream = wc.upStream;
         const int nthr = std::max(1, ndec / ngpus);
         std::thread dec;
@@ -373,11 +363,11 @@ int runBatchedOn(Workers &ws, Parser *parser, const std::vector<std::string> &Ev
                 // (the decoder's scratch while the first batch's files are being read: sizes from the batch's frame count; the
                 // stream buffer from a guess that regrows if a batch proves it wrong)
                 const size_t nfMax = (size_t)Ggpu * C * Fmax;
-                png.raw.grow(nfMax * abub_png_raw_stride(W, H));
-                png.desc.grow(nfMax * sizeof(abub_png_frame));
-                png.status.grow(nfMax * sizeof(int32_t));
-                fit(png.h_status, nfMax * sizeof(int32_t) + 64);
-                png.z.grow(nfMax * (P / 4 * 3));
+                scratch.raw.grow(nfMax * abub_png_raw_stride(W, H));
+                scratch.lane[GpuPng].desc.grow(nfMax * sizeof(abub_png_frame));
+                scratch.lane[GpuPng].status.grow(nfMax * sizeof(int32_t));
+                fit(scratch.lane[GpuPng].h_status, nfMax * sizeof(int32_t) + 64);
+                scratch.z.grow(nfMax * (P / 4 * 3));
                 if (trace)
                     fprintf(stderr, "worker %d: decoder scratch ready at %.1f ms\n", g, nowMs() - tAll);
             }
@@ -405,13 +395,12 @@ int runBatchedOn(Workers &ws, Parser *parser, const std::vector<std::string> &Ev
                     HIPOK(hipMemcpyAsync(d_frames + (size_t)nEvGpu * perEvent, S.h_frames.get(), (size_t)(nEv - nEvGpu) * perEvent,
                                          hipMemcpyHostToDevice, cs));
                 const double tp = nowMs();
-                launchFileDecode(R.files, S.d_files.get(), W, H, d_frames, (size_t)nEv * perEvent, png, cs);
+                launchFileDecode(R.files, S.d_files.get(), W, H, d_frames, (size_t)nEv * perEvent, scratch, cs);
                 // every write below lands after the clear above
                 HIPOK(hipStreamSynchronize(cs));
-                long long onGpu = 0, onHost = R.hostGood;
-                finishFileDecode(R.files, S.h_files.get(), png, d_frames, W, H, cs,
-                                 [&](int s, int f) { return ((size_t)s * Fmax + f) * P; },
-                                 [&](int s, int f) { R.meta[s].ok[f] = 1; }, onGpu, onHost);
+                long long onHost = R.hostGood;
+                finishFileDecode(R.files, S.h_files.get(), scratch, d_frames, W, H, cs, [&](int s, int f) { R.meta[s].ok[f] = 1; }, onHost);
+                const long long onGpu = R.files.decoded();
                 const double pngms = Ggpu ? nowMs() - tp : 0;
                 if (trace)
                     fprintf(stderr, "batch %d: %d frames for the GPU (%zu MB of files), %lld decoded by host threads, read + host decode %.1f ms, "
@@ -447,8 +436,8 @@ int runBatchedOn(Workers &ws, Parser *parser, const std::vector<std::string> &Ev
                     st.bellowsVetoed += bellowsVetoed(*pipe);
                     st.framesGpuDecoded += onGpu;
                     st.framesHostDecoded += onHost;
-                    st.framesGpuUnpacked += R.files.unpacked;
-                    st.framesGpuBmp += R.files.bmpDecoded;
+                    st.framesGpuUnpacked += R.files.decodedBy[GpuPacked];
+                    st.framesGpuBmp += R.files.decodedBy[GpuBmp];
                     st.gpudecode_s += pngms * 1e-3;
                 }
                 slot ^= 1;

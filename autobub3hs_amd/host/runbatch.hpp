@@ -100,7 +100,7 @@ int RepackRun(Parser *parser, const std::string &srcRunDir, const std::string &s
 // that decodes) decoded by the GPU decoders and packed by abub_abf_encode_dev on `device`, in batches of at most 4 frames
 // per CU (ABUB_REPACK_BATCH=n, a test knob: of at most n); the pool's threads read and write the files, and pack on the spot what the decoders do not take (a frame the
 // thread had to decode itself, a frame of another size; a file that does not decode is copied).  A run whose width the
-// decoders do not take ((W & 3) == 0, 4 <= W <= 2048) goes the host route whole.  Throws, before anything is written,
+// decoders do not take (a multiple of 4 from 4 to 2048) goes the host route whole.  Throws, before anything is written,
 // when there is no such device: there is no silent fall-back to the host route.
 int RepackRunDevice(Parser *parser, const std::string &srcRunDir, const std::string &srcRunFile, const std::string &dstRunDir,
                     const std::string &imageFolder, int numCams, int nthreads, int device, RepackStats *stats);

@@ -1,6 +1,6 @@
 // runframes.hpp -- a run as the list of its frames, for the tools that visit every frame without analysing any: repack
-// (repack.cpp) and verify (verify.cpp).  The list, the size the GPU decoders are set up for, their width gate, the device
-// check and the batch size of the device routes are one copy here.  Internal to the host library.
+// (repack.cpp) and verify (verify.cpp).  The list, the size the GPU decoders are set up for and the device check are one
+// copy here (the decoders' width gate and the batch size: framefiles.hpp).  Internal to the host library.
 #ifndef ABUB3HS_RUNFRAMES_HPP
 #define ABUB3HS_RUNFRAMES_HPP
 
@@ -58,9 +58,6 @@ inline bool firstFrameSize(Parser *parser, const std::vector<std::string> &event
     return false;
 }
 
-// the GPU decoders' width gate (runbatch.cpp): a run outside it takes the host route whole
-inline bool decodersTakeWidth(int W) { return (W & 3) == 0 && W >= 4 && W <= 2048; }
-
 // Throws "<who>: no such HIP device: ..." when there is no device `device`; `hint` says what the caller does without one
 inline void requireDevice(int device, const std::string &who, const std::string &hint)
 {
@@ -68,15 +65,6 @@ inline void requireDevice(int device, const std::string &who, const std::string 
     if (device < 0 || hipGetDeviceCount(&count) != hipSuccess || device >= count)
         throw std::runtime_error(who + ": no such HIP device: " + std::to_string(device) + " (" + std::to_string(std::max(count, 0)) +
                                  " found)" + hint);
-}
-
-// frames per batch of a device route: at most 4 per CU
-inline size_t framesPerBatch(int device)
-{
-    int ncu = 256, v = 0;
-    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && v > 0)
-        ncu = v;
-    return (size_t)4 * ncu;
 }
 
 } // namespace abub

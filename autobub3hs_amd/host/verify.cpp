@@ -216,46 +216,6 @@ void hostFrames(Parser *src, Parser *other, const Plan &pl, int nthreads, std::v
     forEachPair(src, other, nthreads, pl.tasks.size(), [&](Clones &c, size_t i) { verdicts[i] = verifyFrame(c, pl, i); });
 }
 
-// One side of a batch on the device: the files, the decoders' scratch, the slab of decoded frames
-struct Side {
-    PinnedBuffer h_files;
-    DeviceBuffer d_files, slab;
-    PngScratch png;
-    std::unique_ptr<Parser> sizer;
-    std::vector<FileTask> ft;
-    size_t total = 0;
-    FileDescs fd;
-    std::vector<uint8_t> good;
-    long long gpuPng = 0, gpuUnpacked = 0, gpuBmp = 0, hostDecoded = 0;
-
-    void upload(size_t n, size_t stride, hipStream_t cs)
-    {
-        fd = FileDescs();
-        good.assign(n, 0);
-        buildFileDescs(ft.data(), ft.data() + n, total, fd, [&](int s, int) { return (uint64_t)s * stride; });
-        slab.grow(n * stride);
-        if (!fd.gpuFrames())
-            return;
-        d_files.grow(total + 16);
-        HIPOK(hipMemcpyAsync(d_files.get(), h_files.get(), total + 16, hipMemcpyHostToDevice, cs));
-    }
-    void launch(size_t n, size_t stride, int W, int H, hipStream_t cs)
-    {
-        if (fd.gpuFrames())
-            launchFileDecode(fd, d_files.get(), W, H, slab.get(), n * stride, png, cs);
-    }
-    void finish(size_t stride, int W, int H, hipStream_t cs) // (after the stream has been waited for)
-    {
-        long long onGpu = 0, onHost = 0;
-        finishFileDecode(fd, h_files.get(), png, slab.get(), W, H, cs, [&](int s, int) { return (size_t)s * stride; },
-                         [&](int s, int) { good[s] = 1; }, onGpu, onHost);
-        gpuUnpacked += fd.unpacked;
-        gpuBmp += fd.bmpDecoded;
-        gpuPng += onGpu - fd.unpacked - fd.bmpDecoded;
-        hostDecoded += onHost;
-    }
-};
-
 // The device route: the frames in batches.  Per batch and side: the pool reads the files into a pinned buffer (a frame
 // that is no file for the decoders on either side gets its verdict on the spot, from verifyFrame); upload; both decoders
 // into the side's slab, frame i at i * align16(W * H); then one abub_frames_compare_dev launch over the frames that are in
@@ -269,7 +229,7 @@ void deviceFrames(Parser *src, Parser *other, const Plan &pl, int nthreads, int 
         if (atoi(e) > 0)
             perBatch = (size_t)atoi(e);
     const size_t P = (size_t)W * H, stride = (P + 15) & ~(size_t)15;
-    Side S, O;
+    FileBatch S, O; // the two sides of a batch: the files, the decoders' scratch, the slab of decoded frames
     S.sizer.reset(src->clone());
     O.sizer.reset(other->clone());
     PinnedBuffer h_meta;
@@ -282,9 +242,10 @@ void deviceFrames(Parser *src, Parser *other, const Plan &pl, int nthreads, int 
         // ---- read -------------------------------------------------------------------------------------------------------
         double t0 = nowMs();
         std::vector<uint8_t> done(n, 0); // the frame has its verdict
-        for (Side *side : {&S, &O}) {
+        for (FileBatch *side : {&S, &O}) {
             side->ft.assign(n, FileTask());
             side->total = 0;
+            side->reset(n, n * stride);
         }
         for (size_t i = 0; i < n; ++i) {
             const FrameTask &t = pl.tasks[i0 + i];
@@ -300,7 +261,7 @@ void deviceFrames(Parser *src, Parser *other, const Plan &pl, int nthreads, int 
         forEachPair(src, other, nthreads, n, [&](Clones &c, size_t i) {
             const FrameTask &t = pl.tasks[i0 + i];
             FileTask &fs = S.ft[i], &fo = O.ft[i];
-            if (fs.state == FileTask::Gpu && fo.state == FileTask::Gpu) {
+            if (fs.state == FileTask::Planned && fo.state == FileTask::Planned) {
                 readFileTask(*c.src, pl.events[t.ev], t.name, fs, S.h_files.get(), W, H);
                 if (fs.state != FileTask::Bad)
                     readFileTask(*c.other, pl.events[t.ev], t.name, fo, O.h_files.get(), W, H);
@@ -317,13 +278,22 @@ void deviceFrames(Parser *src, Parser *other, const Plan &pl, int nthreads, int 
 
         // ---- upload and decode ------------------------------------------------------------------------------------------
         t0 = nowMs();
-        S.upload(n, stride, cs);
-        O.upload(n, stride, cs);
-        S.launch(n, stride, W, H, cs);
-        O.launch(n, stride, W, H, cs);
+        const auto dstOf = [&](int s, int) { return (uint64_t)s * stride; };
+        S.upload(cs);
+        O.upload(cs);
+        S.launch(0, n, W, H, dstOf, cs);
+        O.launch(0, n, W, H, dstOf, cs);
         HIPOK(hipStreamSynchronize(cs));
-        S.finish(stride, W, H, cs);
-        O.finish(stride, W, H, cs);
+        S.finish(W, H, cs);
+        O.finish(W, H, cs);
+        st.srcGpuPngDecoded = S.decodedBy[GpuPng];
+        st.srcGpuUnpacked = S.decodedBy[GpuPacked];
+        st.srcGpuBmpDecoded = S.decodedBy[GpuBmp];
+        st.srcHostDecoded = S.hostDecoded;
+        st.otherGpuPngDecoded = O.decodedBy[GpuPng];
+        st.otherGpuUnpacked = O.decodedBy[GpuPacked];
+        st.otherGpuBmpDecoded = O.decodedBy[GpuBmp];
+        st.otherHostDecoded = O.hostDecoded;
         HIPOK(hipStreamSynchronize(cs));
         st.decode_s += (nowMs() - t0) * 1e-3;
 
@@ -375,14 +345,6 @@ void deviceFrames(Parser *src, Parser *other, const Plan &pl, int nthreads, int 
         st.read_s += (nowMs() - t0) * 1e-3;
         ++st.batches;
     }
-    st.srcGpuPngDecoded = S.gpuPng;
-    st.srcGpuUnpacked = S.gpuUnpacked;
-    st.srcHostDecoded = S.hostDecoded;
-    st.otherGpuPngDecoded = O.gpuPng;
-    st.otherGpuUnpacked = O.gpuUnpacked;
-    st.otherHostDecoded = O.hostDecoded;
-    st.srcGpuBmpDecoded = S.gpuBmp;
-    st.otherGpuBmpDecoded = O.gpuBmp;
 }
 
 // 0 .. 3 of VerifyStats::EventFile
