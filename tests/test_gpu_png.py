@@ -118,6 +118,44 @@ def test_every_filter_and_block_type(W, H):
         assert np.array_equal(got[k], want[k]), k
 
 
+def width_class_images(rs, W, H):
+    """images() and three more: all 255 (Average sees left + up = 510), two levels 0 / 1 (Paeth's ties pa == pb and pb == pc on
+    most pixels), and one whose last lane's columns differ from the rest of the row (the unfilter kernel gives each lane
+    4 * NDW bytes, NDW = ceil(W / 256): the last W % (4 * NDW) columns, or the whole last lane where that is 0)"""
+    ims = images(rs, W, H)
+    ims["all 255"] = np.full((H, W), 255, dtype=np.uint8)
+    ims["two levels"] = rs.randint(0, 2, (H, W)).astype(np.uint8)
+    per_lane = 4 * ((W + 255) // 256)
+    tail = rs.randint(0, 4, (H, W)).astype(np.uint8)
+    tail[:, W - (W % per_lane or per_lane):] = rs.randint(128, 256, (H, W % per_lane or per_lane))
+    ims["last lane differs"] = tail
+    return ims
+
+
+@pytest.mark.parametrize("W", [260, 772, 1024, 1028, 1284, 1536, 1544, 1796, 2044])
+def test_unfilter_width_classes_with_a_partly_filled_last_lane(W):
+    """Every k_png_unfilter<NDW>, NDW = 2 and 4 .. 8, at a width whose last lane holds fewer than 4 * NDW bytes, and NDW = 4
+    and 6 evenly filled (1024, 1536); H = 5, so a row starts at each of the four misalignments of the raw buffer.  Every
+    filter on every row, row 0 included; the reference is the image that went into filter_rows."""
+    H = 5
+    rs = np.random.RandomState(W)
+    files, want = [], []
+    for name, img in width_class_images(rs, W, H).items():
+        for ft in (0, 1, 2, 3, 4, "mixed"):
+            filters = rs.randint(0, 5, H) if ft == "mixed" else np.full(H, ft)
+            files.append(make_png(img, filters, 6, idat=[1 << 16, 100][len(files) % 2])[0])
+            want.append(img)
+    if W in (260, 1796):
+        pal = rs.randint(0, 256, 3 * 256).astype(np.uint8).tobytes()
+        img = rs.randint(0, 256, (H, W)).astype(np.uint8)
+        files.append(make_png(img, np.array([4, 3, 1, 2, 0]), 6, palette=pal)[0])
+        want.append(expect_grey(img, pal))
+    got, st = run(files, W, H)
+    assert (st == 0).all(), st
+    for k in range(len(files)):
+        assert np.array_equal(got[k], want[k]), k
+
+
 def test_palette_images():
     rs = np.random.RandomState(5)
     W, H = 320, 100

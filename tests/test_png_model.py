@@ -47,3 +47,25 @@ def test_model_refuses_what_zlib_refuses():
             assert got is None, trial
         else:
             assert got == want, trial
+
+
+def test_model_agrees_with_zlib_on_crafted_streams():
+    """the hand-written streams of test_png_crafted_streams (what no compressor emits): the model returns zlib's bytes where
+    zlib accepts and refuses where zlib refuses.  The model checks the expected size at the end of the stream as the kernel
+    does, so the case that inflates to one byte too few (J-) is inside its contract and is not excluded."""
+    from test_png_crafted_streams import crafted_cases, stream_of, zlib_verdict
+    for c in crafted_cases():
+        z = stream_of(c.png)
+        ok, raw = zlib_verdict(z, c.W, c.H)
+        assert ok == c.accepts, c.name
+        try:
+            got = model.inflate_wave(z, c.H * (c.W + 1))
+        except model.Corrupt:
+            got = None
+        assert got == (raw if ok else None), c.name
+
+
+def test_model_has_the_kernel_s_table_sizes():
+    src = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "autobub3hs_amd", "csrc", "abub_png.hip")).read()
+    assert f"LIT_ROOT = {model.LIT_ROOT}, DIST_ROOT = {model.DIST_ROOT};" in src
+    assert f"PNG_SHORT = {model.SHORT};" in src

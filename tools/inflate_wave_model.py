@@ -20,7 +20,7 @@ import numpy as np
 
 NW = 64
 LIT_ROOT = 10
-DIST_ROOT = 9
+DIST_ROOT = 8
 K_LIT, K_LEN, K_EOB, K_LONG, K_BAD = 0, 1, 2, 3, 4
 SHORT = 8  # matches up to this length are copied by their own lane
 
@@ -226,7 +226,7 @@ def inflate_wave(z, expect, stats=None):
             ll, dl = L[:hlit], L[hlit:]
             if ll[256] == 0:
                 raise Corrupt("no end-of-block code")
-        lt = Canon(ll, LIT_ROOT, lit_kind, False if btype == 2 else False)
+        lt = Canon(ll, LIT_ROOT, lit_kind, True)  # (zlib: a lone 1-bit code may be incomplete, e.g. a block of nothing but its end)
         dt = Canon(dl, DIST_ROOT, dist_kind, True)
         # ---- the token loop --------------------------------------------------------------------------------
         s = 0  # chain start inside the window
@@ -337,6 +337,8 @@ def inflate_wave(z, expect, stats=None):
         raise Corrupt("truncated (no checksum)")
     want = struct.unpack(">I", bytes(zb[ip >> 3:(ip >> 3) + 4]))[0]
     res = bytes(out[:op])
+    if op != expect:
+        raise Corrupt("too little output")
     if zlib.adler32(res) != want:
         raise Corrupt("adler32")
     return res
