@@ -80,6 +80,8 @@ SIGNATURES = {
     "abub_png_decode_dev": (_i, [_vp, _sz, _vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp]),
     "abub_abf_decode_dev": (_i, [_vp, _sz, _vp, _i, _i, _i, _vp, _sz, _vp, _vp]),
     "abub_bmp_decode_dev": (_i, [_vp, _sz, _vp, _i, _vp, _i, _i, _i, _vp, _sz, _vp, _vp]),
+    "abub_unzip_dev": (_i, [_vp, _sz, _vp, _i, _vp, _sz, _vp, _vp]),
+    "abub_crc32_dev": (_i, [_vp, _sz, _vp, _i, _vp, _vp, _vp]),
     "abub_abf_file_bound": (_sz, [_i, _i]),
     "abub_abf_encode_scratch_bytes": (_sz, [_i, _i, _i]),
     "abub_abf_encode_dev": (_i, [_vp, _sz, _vp, _i, _i, _i, _vp, _sz, _vp, _vp, _vp, _sz, _vp]),

@@ -20,6 +20,10 @@
 // Every access is bounds-checked against the sizes the caller states: the input is file content.  A frame the kernels
 // refuse (status != 0) is left to the caller, which decodes it on the host (the result is the same image or the same
 // failure: both follow RFC 1950/1951 and the PNG specification).
+//
+// The same inflate serves the zip layer of a deflated archive (abub_unzip_dev): k_zip_inflate is k_png_inflate's body in raw
+// mode (RFC 1951: no header, no trailer, read in place, one output length per entry), k_zip_crc checks the CRC-32 the
+// archive's central directory states for every inflated entry.
 #include "abub_dev.hpp"
 #include <stddef.h>
 
@@ -325,6 +329,8 @@ struct Parser {
     uint32_t nbits;    // its length in bits
     uint32_t in_hi;    // the input ring holds the stream's bytes [in_hi - 512, in_hi)
     uint32_t pf;       // bytes [in_hi + 4 * lane, + 4), requested ahead
+    bool raw;          // a raw deflate stream (RFC 1951: a zip entry) read in place: no header, no trailer, and the bytes
+                       // behind it are somebody else's (read as zeros); a constant of the kernel's instantiation
 };
 struct Writer {
     const uint8_t *z;  // (stored blocks are copied from the stream)
@@ -334,6 +340,7 @@ struct Writer {
     uint32_t fp;       // flushed up to here (multiple of 16)
     uint32_t a1, a2;   // Adler-32 of the flushed bytes
     bool far;          // this lane saw a distance that reaches before the output's first byte (checked at every flush)
+    bool raw_mode;     // no Adler-32 to compare at the end (Parser::raw)
 };
 
 __device__ __forceinline__ uint32_t png_load4(const Parser &P, uint32_t off)
@@ -341,6 +348,8 @@ __device__ __forceinline__ uint32_t png_load4(const Parser &P, uint32_t off)
     uint32_t v = 0;
     if (off + 4 <= P.zpad)
         v = *(const uint32_t *)(P.z + off);
+    if (P.raw && off + 4 > P.zlen) // (the PNG route's gather kernel has put zeros there)
+        v = off >= P.zlen ? 0u : v & (0xffffffffu >> (8 * (off + 4 - P.zlen)));
     return v;
 }
 __device__ __forceinline__ void png_refill(Parser &P, InflateLds &L, int lane)
@@ -620,6 +629,8 @@ __device__ __forceinline__ int png_apply_end(Writer &S, InflateLds &L, uint32_t 
         return ABUB_PNG_E_DISTANCE;
     if (S.op != S.rawLen)
         return ABUB_PNG_E_TOOLITTLE;
+    if (S.raw_mode)
+        return 0;
     return adler == ((S.a2 << 16) | S.a1) ? 0 : ABUB_PNG_E_ADLER;
 }
 
@@ -806,12 +817,12 @@ __device__ __forceinline__ int png_block_tables(Parser &P, InflateLds &L, uint32
 template <bool TWO>
 __device__ __forceinline__ int png_parse(Parser &P, InflateLds &L, Sink<TWO> &sink, int lane)
 {
-    uint32_t ip = 16;
+    uint32_t ip = P.raw ? 0 : 16;
     png_in_start(P, L, 0, lane);
     png_ensure(P, L, 0, lane);
-    if (P.zlen < 6 || P.zlen >= (1u << 28))
+    if (P.zlen < (P.raw ? 1u : 6u) || P.zlen >= (1u << 28))
         return ABUB_PNG_E_TRUNCATED;
-    {
+    if (!P.raw) {
         const uint32_t h = rfl(png_bits32(L, 0));
         const uint32_t cmf = h & 255, flg = (h >> 8) & 255;
         if ((cmf & 15) != 8 || (cmf >> 4) > 7 || ((cmf << 8) | flg) % 31 || (flg & 0x20))
@@ -852,10 +863,16 @@ __device__ __forceinline__ int png_parse(Parser &P, InflateLds &L, Sink<TWO> &si
         }
         {
             const int rc = png_block_tables(P, L, ip, btype, lane);
+            // (a raw stream cut inside a block's header: what the zeros behind it make of the header is not the finding)
+            if (rc && P.raw && ip + 14 > P.nbits)
+                return ABUB_PNG_E_TRUNCATED;
             if (rc)
                 return rc;
         }
         // ---- tokens ----
+        // an invalid code at bit position `at`; in a raw stream one that the zeros behind the stream's end may have made (a
+        // length and distance pair takes up to 48 bits) is a stream cut short
+        auto bad_code = [&](uint32_t at) { return (P.raw && at + 48 > P.nbits) ? ABUB_PNG_E_TRUNCATED : ABUB_PNG_E_CODE; };
         uint32_t s = 0; // first real token start inside the two windows
         for (;;) {
             png_ensure(P, L, ip, lane);
@@ -949,14 +966,14 @@ __device__ __forceinline__ int png_parse(Parser &P, InflateLds &L, Sink<TWO> &si
                     if (stop0) {
                         const uint32_t j = (uint32_t)__builtin_ctzll(stop0);
                         if (rdl(kind[0], j) == T_BAD)
-                            return ABUB_PNG_E_CODE;
+                            return bad_code(ip + j);
                         valid[0] &= (1ull << j) - 1; // (the end-of-block token itself carries no bytes)
                         valid[1] = 0;
                         p = j + rdl(nb[0], j);
                     } else {
                         const uint32_t j = (uint32_t)__builtin_ctzll(stop1);
                         if (rdl(kind[1], j) == T_BAD)
-                            return ABUB_PNG_E_CODE;
+                            return bad_code(ip + 64 + j);
                         valid[1] &= (1ull << j) - 1;
                         p = 64 + j + rdl(nb[1], j);
                     }
@@ -980,6 +997,8 @@ __device__ __forceinline__ int png_parse(Parser &P, InflateLds &L, Sink<TWO> &si
                 break;
         }
     }
+    if (P.raw) // whatever follows the final block is not the stream's
+        return sink.put(REC_END, 0);
     // the trailer: Adler-32 of the output, big-endian, at the next byte boundary
     ip = (ip + 7) & ~7u;
     if (ip + 32 > P.nbits)
@@ -989,44 +1008,34 @@ __device__ __forceinline__ int png_parse(Parser &P, InflateLds &L, Sink<TWO> &si
     return sink.put(REC_END, adler);
 }
 
-template <bool TWO>
-__global__ __launch_bounds__(TWO ? 128 : 64) void k_png_inflate(const uint8_t *__restrict__ zbuf, const abub_png_frame *__restrict__ frames,
-                                                                  uint32_t rawLen, uint64_t rawStride, uint8_t *__restrict__ rawbuf,
-                                                                  int32_t *__restrict__ status, int dbg)
+// one stream: `z` (zlen bytes of it; readable up to zlen rounded up to 16) -> exactly rawLen bytes at `raw`, *status
+template <bool TWO, bool RAW>
+__device__ __forceinline__ void png_inflate_stream(InflateLds &L, const uint8_t *z, uint32_t zlen, uint8_t *raw, uint32_t rawLen,
+                                                   int32_t *status, int dbg)
 {
-    __shared__ InflateLds L;
-    const int f = blockIdx.x, lane = threadIdx.x & 63;
+    const int lane = threadIdx.x & 63;
     const uint32_t wave = rfl(threadIdx.x >> 6);
-    if (TWO) {
-        if (threadIdx.x == 0) {
-            L.q_head = 0;
-            L.q_tail = 0;
-            L.q_abort = 0;
-        }
-        __syncthreads();
-    }
-    if (status[f] != 0) // (refused by the gather kernel; the same for the whole workgroup)
-        return;
-    const abub_png_frame fr = frames[f];
     Writer W;
-    W.z = zbuf + fr.zoff;
-    W.raw = rawbuf + (uint64_t)f * rawStride;
+    W.z = z;
+    W.raw = raw;
     W.rawLen = rawLen;
     W.op = W.op_r = W.fp = 0;
     W.a1 = 1;
     W.a2 = 0;
     W.far = false;
+    W.raw_mode = RAW;
     if (!TWO || wave == 0) {
         Parser P;
-        P.z = zbuf + fr.zoff;
-        P.zlen = fr.zlen;
-        P.zpad = (fr.zlen + 15) & ~15u;
-        P.nbits = fr.zlen * 8;
+        P.z = z;
+        P.zlen = zlen;
+        P.zpad = (zlen + 15) & ~15u;
+        P.nbits = zlen * 8;
+        P.raw = RAW;
         Sink<TWO> sink = {L, &W, 0, 0, lane, dbg};
         int rc = png_parse<TWO>(P, L, sink, lane);
         if (!TWO) {
             if (lane == 0)
-                status[f] = rc;
+                *status = rc;
         } else if (rc > 0)
             (void)sink.put(REC_ERROR, (uint32_t)rc); // (rc == -1: the writing wave has set the status and gone)
         return;
@@ -1077,8 +1086,159 @@ __global__ __launch_bounds__(TWO ? 128 : 64) void k_png_inflate(const uint8_t *_
             break;
     }
     if (lane == 0) {
-        status[f] = (dbg == 5 && rc == 0) ? -(int)(latN ? latSum / latN : 0) - 1000000 * (int)min(latN / 1000u, 2000u) : rc;
+        *status = (dbg == 5 && rc == 0) ? -(int)(latN ? latSum / latN : 0) - 1000000 * (int)min(latN / 1000u, 2000u) : rc;
         q_st(&L.q_abort, 1u);
+    }
+}
+
+template <bool TWO>
+__global__ __launch_bounds__(TWO ? 128 : 64) void k_png_inflate(const uint8_t *__restrict__ zbuf, const abub_png_frame *__restrict__ frames,
+                                                                  uint32_t rawLen, uint64_t rawStride, uint8_t *__restrict__ rawbuf,
+                                                                  int32_t *__restrict__ status, int dbg)
+{
+    __shared__ InflateLds L;
+    const int f = blockIdx.x;
+    if (TWO) {
+        if (threadIdx.x == 0) {
+            L.q_head = 0;
+            L.q_tail = 0;
+            L.q_abort = 0;
+        }
+        __syncthreads();
+    }
+    if (status[f] != 0) // (refused by the gather kernel; the same for the whole workgroup)
+        return;
+    const abub_png_frame fr = frames[f];
+    png_inflate_stream<TWO, false>(L, zbuf + fr.zoff, fr.zlen, rawbuf + (uint64_t)f * rawStride, rawLen, status + f, dbg);
+}
+
+// ---- zip entries: raw deflate streams read in place, one output length per entry (abub_unzip_dev) ------------------------
+__device__ __forceinline__ uint64_t zip_align16(uint64_t v) { return (v + 15) & ~15ull; }
+__device__ __forceinline__ bool zip_desc_bad(const abub_zip_entry &en, uint64_t comp_bytes, uint64_t out_bytes)
+{
+    return (en.off & 15) || en.clen >= (1u << 28) || en.ulen >= (1u << 28) ||
+           (uint64_t)en.off + zip_align16(en.clen) + 16 > comp_bytes || (en.dst & 15) || en.dst > out_bytes ||
+           zip_align16(en.ulen) > out_bytes - en.dst;
+}
+template <bool TWO>
+__global__ __launch_bounds__(TWO ? 128 : 64) void k_zip_inflate(const uint8_t *__restrict__ comp, uint64_t comp_bytes,
+                                                                  const abub_zip_entry *__restrict__ entries, uint8_t *__restrict__ out,
+                                                                  uint64_t out_bytes, int32_t *__restrict__ status)
+{
+    __shared__ InflateLds L;
+    const int e = blockIdx.x;
+    if (TWO) {
+        if (threadIdx.x == 0) {
+            L.q_head = 0;
+            L.q_tail = 0;
+            L.q_abort = 0;
+        }
+        __syncthreads();
+    }
+    const abub_zip_entry en = entries[e];
+    if (zip_desc_bad(en, comp_bytes, out_bytes)) { // (uniform: every thread read the same descriptor)
+        if (threadIdx.x == 0)
+            status[e] = ABUB_ZIP_E_DESC;
+        return;
+    }
+    png_inflate_stream<TWO, true>(L, comp + en.off, en.clen, out + en.dst, en.ulen, status + e, 0);
+}
+
+// ---- CRC-32 (the zip / IEEE one, reflected, polynomial 0xEDB88320) of every inflated entry ---------------------------------
+// One workgroup per entry.  The entry is cut into 256 contiguous pieces (a multiple of 16 bytes, 64 at least), thread t takes
+// the register of piece t with slice-by-4 tables in LDS (thread 0 starts from 0xFFFFFFFF: the pre-conditioning, once), moves
+// it over the bytes behind its piece -- a multiplication by x^(8 * tail) mod P, built from the x^(8 * 2^k) by 32-step
+// carry-less multiplications -- and the registers are summed (xor); the post-conditioning is applied once.
+constexpr uint32_t CRC_POLY = 0xEDB88320u;
+constexpr uint32_t crc_mul(uint32_t a, uint32_t b) // a * b mod P (bit 31 is x^0)
+{
+    uint32_t p = 0;
+    for (int i = 0; i < 32; ++i) {
+        if (a & (0x80000000u >> i))
+            p ^= b;
+        b = (b >> 1) ^ ((b & 1) ? CRC_POLY : 0u);
+    }
+    return p;
+}
+struct CrcTables {
+    uint32_t t[4][256];
+    uint32_t pw[28]; // x^(8 * 2^k) mod P
+};
+constexpr CrcTables crc_make_tables()
+{
+    CrcTables T{};
+    for (uint32_t i = 0; i < 256; ++i) {
+        uint32_t c = i;
+        for (int k = 0; k < 8; ++k)
+            c = (c >> 1) ^ ((c & 1) ? CRC_POLY : 0u);
+        T.t[0][i] = c;
+    }
+    for (int s = 1; s < 4; ++s)
+        for (uint32_t i = 0; i < 256; ++i)
+            T.t[s][i] = (T.t[s - 1][i] >> 8) ^ T.t[0][T.t[s - 1][i] & 255];
+    T.pw[0] = 0x00800000u; // x^8
+    for (int k = 1; k < 28; ++k)
+        T.pw[k] = crc_mul(T.pw[k - 1], T.pw[k - 1]);
+    return T;
+}
+__device__ const CrcTables crc_tables = crc_make_tables();
+
+template <bool ALONE> // ALONE: abub_crc32_dev (every descriptor checked here, the CRCs written out); else behind k_zip_inflate
+__global__ __launch_bounds__(256) void k_zip_crc(const uint8_t *__restrict__ out, uint64_t out_bytes,
+                                                 const abub_zip_entry *__restrict__ entries, int32_t *__restrict__ status,
+                                                 uint32_t *__restrict__ crc_out)
+{
+    __shared__ uint32_t tab[4][256];
+    __shared__ uint32_t acc;
+    const int e = blockIdx.x, tid = threadIdx.x;
+    const abub_zip_entry en = entries[e];
+    if (ALONE) {
+        const bool bad = (en.dst & 15) || en.ulen >= (1u << 28) || en.dst > out_bytes || zip_align16(en.ulen) > out_bytes - en.dst;
+        if (tid == 0)
+            status[e] = bad ? ABUB_ZIP_E_DESC : 0;
+        if (bad)
+            return;
+    } else if (status[e] != 0) // (refused by the inflate; the same for the whole workgroup)
+        return;
+#pragma unroll
+    for (int s = 0; s < 4; ++s)
+        tab[s][tid] = crc_tables.t[s][tid];
+    if (tid == 0)
+        acc = 0;
+    __syncthreads();
+    const uint32_t n = en.ulen;
+    const uint8_t *p = out + en.dst;
+    const uint32_t chunk = max((((n + 255) >> 8) + 15) & ~15u, 64u); // 256 * chunk < 2^29
+    const uint32_t lo = min(n, (uint32_t)tid * chunk), hi = min(n, lo + chunk);
+    uint32_t r = tid == 0 ? 0xffffffffu : 0u;
+    auto word = [&](uint32_t w) {
+        r ^= w;
+        r = tab[3][r & 255] ^ tab[2][(r >> 8) & 255] ^ tab[1][(r >> 16) & 255] ^ tab[0][r >> 24];
+    };
+    uint32_t k = lo;
+    for (; k + 16 <= hi; k += 16) {
+        const uint4 v = *(const uint4 *)(p + k);
+        word(v.x);
+        word(v.y);
+        word(v.z);
+        word(v.w);
+    }
+    for (; k < hi; ++k)
+        r = tab[0][(r ^ p[k]) & 255] ^ (r >> 8);
+    if (r) {
+        const uint32_t tail = n - hi;
+        for (int b = 0; b < 28; ++b)
+            if ((tail >> b) & 1)
+                r = crc_mul(r, crc_tables.pw[b]);
+        atomicXor(&acc, r);
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const uint32_t crc = acc ^ 0xffffffffu;
+        if (ALONE)
+            crc_out[e] = crc;
+        else if (crc != en.crc)
+            status[e] = ABUB_ZIP_E_CRC;
     }
 }
 
@@ -1282,6 +1442,40 @@ extern "C" int abub_png_decode_dev(const uint8_t *files, size_t files_bytes, con
     default: UNF(8); break;
     }
 #undef UNF
+    HIPCHK(hipGetLastError());
+    return ABUB_OK;
+}
+
+extern "C" int abub_unzip_dev(const uint8_t *comp, size_t comp_bytes, const abub_zip_entry *entries, int nentries, uint8_t *out,
+                              size_t out_bytes, int32_t *status, void *stream)
+{
+    if (!comp || !entries || !out || !status || nentries < 0)
+        return set_err(ABUB_E_INVALID, "abub_unzip_dev: null pointer or negative count");
+    if (nentries == 0)
+        return ABUB_OK;
+    if (((uintptr_t)comp & 15) || ((uintptr_t)out & 15) || ((uintptr_t)entries & 7))
+        return set_err(ABUB_E_INVALID, "abub_unzip_dev: comp / out 16-byte, entries 8-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    static const bool oneWave = [] { const char *e = getenv("ABUB_PNG_WAVES"); return e && atoi(e) == 1; }();
+    if (oneWave)
+        k_zip_inflate<false><<<nentries, 64, 0, st>>>(comp, (uint64_t)comp_bytes, entries, out, (uint64_t)out_bytes, status);
+    else
+        k_zip_inflate<true><<<nentries, 128, 0, st>>>(comp, (uint64_t)comp_bytes, entries, out, (uint64_t)out_bytes, status);
+    k_zip_crc<false><<<nentries, 256, 0, st>>>(out, (uint64_t)out_bytes, entries, status, nullptr);
+    HIPCHK(hipGetLastError());
+    return ABUB_OK;
+}
+
+extern "C" int abub_crc32_dev(const uint8_t *buf, size_t buf_bytes, const abub_zip_entry *entries, int nentries, uint32_t *crc,
+                              int32_t *status, void *stream)
+{
+    if (!buf || !entries || !crc || !status || nentries < 0)
+        return set_err(ABUB_E_INVALID, "abub_crc32_dev: null pointer or negative count");
+    if (nentries == 0)
+        return ABUB_OK;
+    if (((uintptr_t)buf & 15) || ((uintptr_t)entries & 7))
+        return set_err(ABUB_E_INVALID, "abub_crc32_dev: buf 16-byte, entries 8-byte aligned");
+    k_zip_crc<true><<<nentries, 256, 0, (hipStream_t)stream>>>(buf, (uint64_t)buf_bytes, entries, status, crc);
     HIPCHK(hipGetLastError());
     return ABUB_OK;
 }

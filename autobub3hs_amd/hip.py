@@ -457,6 +457,43 @@ def bmp_decode(files, descs, luts, W, H, out, status=None):
     return status[:n]
 
 
+# ---- deflated zip entries inflated on the GPU (abub_unzip_dev) --------------------------------------------------------
+def _zip_entries(entries, device):
+    import numpy as np
+    d = np.asarray(entries, dtype=np.int64).reshape(-1, 5)
+    n = len(d)
+    rec = np.zeros((max(n, 1), 6), dtype=np.uint32)
+    rec[:n, 0:4] = d[:, 0:4] & 0xFFFFFFFF
+    rec[:n, 4] = d[:, 4] & 0xFFFFFFFF
+    rec[:n, 5] = d[:, 4] >> 32
+    return n, torch.from_numpy(rec.view(np.int32).copy()).to(device)
+
+
+def unzip(comp, entries, out, status=None):
+    """abub_unzip_dev: comp u8 [comp_bytes] (raw deflate streams as they lie in an archive), entries: rows of
+    (off, clen, ulen, crc, dst) as abub_zip_entry, out u8 (written in place) -> status i32 [n] on the device (0 = inflated,
+    exactly ulen bytes with that CRC-32; else ABUB_ZIP_E_DESC = 1, a deflate status with the number of its ABUB_PNG_E_*, or
+    ABUB_ZIP_E_CRC = 16)."""
+    _need_cuda(comp, out)
+    n, d_ent = _zip_entries(entries, comp.device)
+    if status is None:
+        status = torch.full((max(n, 1),), 99, dtype=torch.int32, device=comp.device)
+    _lib.check(_lib.lib().abub_unzip_dev(_ptr(comp), comp.numel(), _ptr(d_ent), n, _ptr(out), out.numel(), _ptr(status), _stream()),
+               "abub_unzip_dev")
+    return status[:n]
+
+
+def crc32(buf, entries):
+    """abub_crc32_dev (the CRC kernel of abub_unzip_dev alone): entries as for unzip (only ulen and dst are looked at) ->
+    (crc int64 [n] on the host, what zlib.crc32 gives the ulen bytes at buf + dst; status i32 [n] on the host)."""
+    _need_cuda(buf)
+    n, d_ent = _zip_entries(entries, buf.device)
+    crc = torch.zeros((max(n, 1),), dtype=torch.int32, device=buf.device)
+    status = torch.full((max(n, 1),), 99, dtype=torch.int32, device=buf.device)
+    _lib.check(_lib.lib().abub_crc32_dev(_ptr(buf), buf.numel(), _ptr(d_ent), n, _ptr(crc), _ptr(status), _stream()), "abub_crc32_dev")
+    return (crc[:n].cpu().to(torch.int64) & 0xFFFFFFFF), status[:n].cpu()
+
+
 def abf_encode(pixels, src, W, H, out=None, scratch=None, out_cap=None):
     """abub_abf_encode_dev: pixels u8 (any shape; frames of W * H bytes anywhere in it), src: byte offset of each frame
     (any alignment), out u8 (None: nframes * abub_abf_file_bound(W, H), rounded up to 16 per file; out_cap: the kernels may

@@ -25,6 +25,8 @@ SIGNATURES = {
     "abh_run_events": (_s, [_vp]),
     "abh_run_frames": (_s, [_vp, _s, _i]),
     "abh_run_image": (_i, [_vp, _s, _s, _u8p, _i, _ip, _ip]),
+    "abh_run_entry_info": (_i, [_vp, _s, _s, _dp]),
+    "abh_run_entry_raw": (C.c_longlong, [_vp, _s, _s, _u8p, C.c_longlong]),
     "abh_run_add_event": (_i, [_vp, _s, _i, _u8p, _i, _i, _i, _u8p]),
     "abh_train": (_i, [_vp, _i, _ip, _ip, _u8p, _u8p]),
     "abh_train_device": (_i, [_vp, _i, _ip, _ip, _u8p, _u8p, _i, _dp]),
@@ -161,6 +163,24 @@ class Run:
     def frames(self, event, cam):
         return [f for f in lib().abh_run_frames(self._h, str(event).encode(), cam).decode().split("\n") if f]
 
+    def entry_info(self, event, frame):
+        """The archive entry behind a frame (Parser::GetImageEntryInfo): dict of method (0 stored, 8 deflated),
+        compress_size, file_size and crc as the archive's central directory states them, or None where there is none to
+        describe (a directory run, a run in memory, no such frame, an encrypted entry)."""
+        out = (C.c_double * 4)()
+        if not lib().abh_run_entry_info(self._h, str(event).encode(), frame.encode(), out):
+            return None
+        return dict(method=int(out[0]), compress_size=int(out[1]), file_size=int(out[2]), crc=int(out[3]))
+
+    def entry_raw(self, event, frame):
+        """The entry's compressed bytes as they lie in the archive (Parser::ReadImageEntryRaw), or None."""
+        info = self.entry_info(event, frame)
+        if info is None:
+            return None
+        buf = np.zeros(max(1, info["compress_size"]), np.uint8)
+        n = lib().abh_run_entry_raw(self._h, str(event).encode(), frame.encode(), buf.ctypes.data_as(_u8p), info["compress_size"])
+        return None if n < 0 else buf[:n].tobytes()
+
     def image(self, event, frame, cap=1 << 22):
         buf = np.empty(cap, np.uint8)
         w, h = C.c_int(), C.c_int()
@@ -204,14 +224,15 @@ class Run:
         """Every camera trained in one pass on the device (abub::TrainOnDevice): per camera (status, tss, mu, sigma), the
         same as train(cam).  self.train_path is "device", or "host" where TrainOnDevice declined the run; self.train_stats:
         frames decoded by the GPU decoders / by host threads, decode launches, seconds, and of the first the packed frames
-        (frames_gpu_unpacked, abub_abf_decode_dev) and the BMP frames (frames_gpu_bmp, abub_bmp_decode_dev)."""
+        (frames_gpu_unpacked, abub_abf_decode_dev) and the BMP frames (frames_gpu_bmp, abub_bmp_decode_dev); frames_gpu_unzipped:
+        deflated archive entries whose zip layer the GPU inflated (abub_unzip_dev, ABUB_GPU_UNZIP=1)."""
         H, W = shape if shape is not None else self._shape
         L = lib()
         mu = np.zeros((ncams, H, W), np.uint8)
         sg = np.zeros((ncams, H, W), np.uint8)
         st = np.zeros(ncams, np.int32)
         tss = np.zeros(ncams, np.int32)
-        stats = np.zeros(6, np.float64)
+        stats = np.zeros(7, np.float64)
         rc = L.abh_train_device(self._h, ncams, st.ctypes.data_as(_ip), tss.ctypes.data_as(_ip), mu.ctypes.data_as(_u8p),
                                 sg.ctypes.data_as(_u8p), H * W, stats.ctypes.data_as(_dp))
         if rc < 0:
@@ -219,7 +240,8 @@ class Run:
         self.train_path = "device" if rc == 0 else "host"
         self.train_stats = {"frames_gpu_decoded": int(stats[0]), "frames_host_decoded": int(stats[1]),
                             "decode_launches": int(stats[2]), "seconds": float(stats[3]),
-                            "frames_gpu_unpacked": int(stats[4]), "frames_gpu_bmp": int(stats[5])}
+                            "frames_gpu_unpacked": int(stats[4]), "frames_gpu_bmp": int(stats[5]),
+                            "frames_gpu_unzipped": int(stats[6])}
         return [(int(st[c]), int(tss[c]), mu[c], sg[c]) for c in range(ncams)]
 
     def set_model(self, cam, mu, sigma, tss):
@@ -245,16 +267,17 @@ class Run:
     def run_batched(self, ncams, outdir, run_number, frame_offset, maskdir="", ngpus=1, nthreads=16, decode_threads=16,
                     batch_mb=0, shard=(0, 1)):
         """Every event of this run through the batched GPU pipeline (host/runbatch.cpp RunBatched): frames decoded (PNG, packed and BMP files: on the GPU, abub_png_decode_dev / abub_abf_decode_dev / abub_bmp_decode_dev with ABUB_GPU_BMP=1, else BMP files by host threads; ABUB_GPU_DECODE=0: by host threads into pinned
-        batches), detect, blocks appended to <outdir>abub3hs_<run>.txt in event order.  -> stats dict."""
+        batches), detect, blocks appended to <outdir>abub3hs_<run>.txt in event order.  With ABUB_GPU_UNZIP=1 the zip layer of
+        a deflated archive's entries is inflated on the GPU too (abub_unzip_dev; frames_gpu_unzipped counts them).  -> stats dict."""
         L = lib()
-        st = (C.c_double * 15)()
+        st = (C.c_double * 17)()
         rc = L.abh_run_batched(self._h, ncams, maskdir.encode(), outdir.encode(), run_number.encode(), frame_offset, ngpus,
                                nthreads, decode_threads, batch_mb, shard[0], shard[1], st)
         if rc != 0:
             raise RuntimeError(f"abh_run_batched rc={rc}: " + L.abh_last_error(self._h).decode())
         keys = ("total_s", "list_s", "decode_s", "gpu_s", "write_s", "frames", "frames_failed", "batches",
                 "events_per_batch", "gpus", "frames_gpu_decoded", "frames_host_decoded", "gpudecode_s", "frames_gpu_unpacked",
-                "frames_gpu_bmp")
+                "frames_gpu_bmp", "frames_gpu_unzipped", "unzip_s")
         return dict(zip(keys, list(st)))
 
     def repack(self, outdir, nthreads=16, ncams=4, device=None):
@@ -271,8 +294,8 @@ class Run:
         else:
             keys += ("frames_gpu_encoded", "frames_gpu_png_decoded", "frames_gpu_unpacked", "frames_host_decoded",
                      "frames_host_route", "batches", "read_s", "decode_s", "encode_s", "copy_s", "write_s", "device",
-                     "frames_gpu_bmp_decoded")
-            st = (C.c_double * 19)()
+                     "frames_gpu_bmp_decoded", "frames_gpu_unzipped")
+            st = (C.c_double * 20)()
             rc = L.abh_run_repack_dev(self._h, outdir.encode(), ncams, nthreads, int(device), st)
         if rc != 0:
             raise RuntimeError(f"abh_run_repack rc={rc}: " + L.abh_last_error(self._h).decode())
@@ -292,8 +315,8 @@ class Run:
         else:
             keys += ("frames_gpu_encoded", "frames_gpu_png_decoded", "frames_gpu_unpacked", "frames_host_decoded",
                      "frames_host_route", "batches", "read_s", "decode_s", "encode_s", "copy_s", "write_s", "device",
-                     "frames_gpu_bmp_decoded")
-            st = (C.c_double * 19)()
+                     "frames_gpu_bmp_decoded", "frames_gpu_unzipped")
+            st = (C.c_double * 20)()
             rc = L.abh_run_unpack_dev(self._h, outdir.encode(), ncams, nthreads, int(device), st)
         if rc != 0:
             raise RuntimeError(f"abh_run_unpack rc={rc}: " + L.abh_last_error(self._h).decode())
@@ -312,7 +335,7 @@ class Run:
         every same_not_packed frame in task order, then the extras and the event file, each a dict of event, name, verdict,
         ndiff, x, y, max_abs (and w, h, other_w, other_h where the sizes differ)."""
         L = lib()
-        st = (C.c_double * 27)()
+        st = (C.c_double * 29)()
         cap = 1 << 16
         buf = C.create_string_buffer(cap)
         if device is None:
@@ -331,6 +354,7 @@ class Run:
         res.update({k: int(v) for k, v in zip(keys, list(st)[12:21])})
         res.update(read_s=st[21], decode_s=st[22], compare_s=st[23], device=int(st[24]))
         res.update(src_gpu_bmp_decoded=int(st[25]), other_gpu_bmp_decoded=int(st[26]))
+        res.update(src_gpu_unzipped=int(st[27]), other_gpu_unzipped=int(st[28]), frames_gpu_unzipped=int(st[27]) + int(st[28]))
         cols = ("ndiff", "x", "y", "max_abs", "w", "h", "other_w", "other_h")
         res["findings"] = []
         for line in text.decode().split("\n"):

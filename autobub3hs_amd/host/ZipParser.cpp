@@ -107,7 +107,9 @@ void ZipParser::BuildFileList()
         if (o + 46 > cd.size() || rd32(&cd[o]) != 0x02014b50u)
             throw -10;
         Entry e;
+        e.flags = rd16(&cd[o + 8]);
         e.method = rd16(&cd[o + 10]);
+        e.crc32 = rd32(&cd[o + 16]);
         e.compressedSize = rd32(&cd[o + 20]);
         e.uncompressedSize = rd32(&cd[o + 24]);
         const size_t nameLen = rd16(&cd[o + 28]), extraLen = rd16(&cd[o + 30]), commentLen = rd16(&cd[o + 32]);
@@ -262,6 +264,46 @@ long long ZipParser::ReadImageFile(std::string EventID, std::string FrameName, u
         return -1;
     memcpy(dst, data.data(), data.size());
     return (long long)data.size();
+}
+
+bool ZipParser::GetImageEntryInfo(std::string EventID, std::string FrameName, EntryInfo &info)
+{
+    BuildFileList();
+    auto ev = index->ImageLocs.find(EventID);
+    if (ev == index->ImageLocs.end())
+        return false;
+    auto fr = ev->second.find(FrameName);
+    if (fr == ev->second.end())
+        return false;
+    const Entry &e = index->entries[fr->second];
+    if (e.flags & 1)
+        return false;
+    info.method = e.method;
+    info.compressedSize = e.compressedSize;
+    info.uncompressedSize = e.uncompressedSize;
+    info.crc32 = e.crc32;
+    return true;
+}
+
+long long ZipParser::ReadImageEntryRaw(std::string EventID, std::string FrameName, unsigned char *dst, size_t cap)
+{
+    BuildFileList();
+    auto ev = index->ImageLocs.find(EventID);
+    if (ev == index->ImageLocs.end())
+        return -1;
+    auto fr = ev->second.find(FrameName);
+    if (fr == ev->second.end())
+        return -1;
+    const Entry &e = index->entries[fr->second];
+    if ((e.flags & 1) || e.compressedSize > cap)
+        return -1;
+    unsigned char lh[30];
+    if (!preadAll(fp, e.localHeaderOffset, lh, 30) || rd32(lh) != 0x04034b50u)
+        return -1;
+    const uint64_t dataOff = e.localHeaderOffset + 30 + rd16(lh + 26) + rd16(lh + 28);
+    if (e.compressedSize && !preadAll(fp, dataOff, dst, e.compressedSize))
+        return -1;
+    return (long long)e.compressedSize;
 }
 
 void ZipParser::GetFileLists(const char *, std::vector<std::string> &, const char *) {} // empty upstream too (:241-244)

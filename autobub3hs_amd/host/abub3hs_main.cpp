@@ -438,6 +438,8 @@ int main(int argc, char **argv)
                        rs.framesHostRoute, rs.batches, rs.read_s, rs.decode_s, rs.encode_s, rs.copy_s, rs.write_s);
             if (rs.framesGpuBmpDecoded)
                 printf("%s-gpu: %lld frames decoded by the BMP kernel\n", rewrite, rs.framesGpuBmpDecoded);
+            if (rs.framesGpuUnzipped)
+                printf("%s-gpu: %lld archive entries inflated on the GPU\n", rewrite, rs.framesGpuUnzipped);
         }
         if (!haveVerify || rc != 0)
             return rc;
@@ -596,6 +598,9 @@ int main(int argc, char **argv)
                "not run: %s\n",
                cs.runs, cs.frames, cs.total_s, cs.total_s > 0 ? cs.frames / cs.total_s : 0.0, cs.train_s, cs.trainExposed_s,
                cs.pipelinesBuilt, notRun.empty() ? "none" : notRun.c_str());
+        if (cs.framesGpuUnzipped || cs.trainGpuUnzipped)
+            printf("campaign: %lld archive entries inflated on the GPU for the detect, %lld for the training\n", cs.framesGpuUnzipped,
+                   cs.trainGpuUnzipped);
         return rc;
     }
 

@@ -138,6 +138,32 @@ int abh_run_image(void *r, const char *ev, const char *frame, uint8_t *out, int 
         std::memcpy(out, m.data, m.total());
     return rc;
 }
+// the archive entry behind a frame (Parser::GetImageEntryInfo / ReadImageEntryRaw): info_out = [method, compressed size,
+// uncompressed size, CRC-32], returns 1, or 0 where the parser has no entry to describe; abh_run_entry_raw: the entry's
+// compressed bytes as they lie in the archive, returns their count or -1
+int abh_run_entry_info(void *r, const char *ev, const char *frame, double *info_out)
+{
+    Parser::EntryInfo e;
+    try {
+        if (!((Run *)r)->parser->GetImageEntryInfo(ev, frame, e))
+            return 0;
+    } catch (...) {
+        return 0;
+    }
+    info_out[0] = e.method;
+    info_out[1] = (double)e.compressedSize;
+    info_out[2] = (double)e.uncompressedSize;
+    info_out[3] = (double)e.crc32;
+    return 1;
+}
+long long abh_run_entry_raw(void *r, const char *ev, const char *frame, uint8_t *out, long long cap)
+{
+    try {
+        return ((Run *)r)->parser->ReadImageEntryRaw(ev, frame, out, (size_t)std::max(0LL, cap));
+    } catch (...) {
+        return -1;
+    }
+}
 int abh_imdecode(const uint8_t *data, int n, uint8_t *out, int cap, int *w, int *h)
 {
     cv::Mat m = cv::imdecode(data, (size_t)n, 0);
@@ -188,7 +214,7 @@ int abh_png_huff_lengths(const uint64_t *counts, int n, int limit, uint8_t *leng
 // fall-back when there is no such device; its stats go on with [frames encoded on the GPU, of them decoded by the PNG
 // kernel, by the packed kernel, by a host thread, frames that took the host route, batches, seconds of the legs read,
 // upload + decode, encode, copy back, write, the device (-1: the whole run took the host route), of the encoded frames
-// those decoded by the BMP kernel] (19 values).
+// those decoded by the BMP kernel, archive entries inflated by abub_unzip_dev (ABUB_GPU_UNZIP=1)] (20 values).
 // abh_run_unpack / abh_run_unpack_dev: abub::UnpackRun / abub::UnpackRunDevice, the same arguments and stats (packed: frames
 // written as canonical Huffman-only PNG files).
 // the event file of a directory run: <run>/<runID>.txt; empty for an archive
@@ -220,12 +246,12 @@ static int runRepack(void *r, const char *dstRunDir, int ncams, int nthreads, in
                                 : (unpack ? abub::UnpackRun : abub::RepackRun)(run->parser, srcDir, src, dstRunDir, run->imageFolder,
                                                                                ncams, threads, &st);
         if (stats) {
-            const double v[19] = {(double)st.packed, (double)st.copied, (double)st.failed, (double)st.bytesIn, (double)st.bytesOut,
+            const double v[20] = {(double)st.packed, (double)st.copied, (double)st.failed, (double)st.bytesIn, (double)st.bytesOut,
                                   st.total_s, (double)st.framesGpuEncoded, (double)st.framesGpuPngDecoded,
                                   (double)st.framesGpuUnpacked, (double)st.framesHostDecoded, (double)st.framesHostRoute,
                                   (double)st.batches, st.read_s, st.decode_s, st.encode_s, st.copy_s, st.write_s, (double)st.device,
-                                  (double)st.framesGpuBmpDecoded};
-            std::memcpy(stats, v, (onDevice ? 19 : 6) * sizeof(double));
+                                  (double)st.framesGpuBmpDecoded, (double)st.framesGpuUnzipped};
+            std::memcpy(stats, v, (onDevice ? 20 : 6) * sizeof(double));
         }
         return rc;
     } catch (std::exception &e) {
@@ -250,8 +276,8 @@ int abh_run_unpack_dev(void *r, const char *dstRunDir, int ncams, int nthreads, 
     return runRepack(r, dstRunDir, ncams, nthreads, device, true, stats, true);
 }
 
-// abub::VerifyRun of two runs opened with abh_run_open: is `other` pixel for pixel the run `src`?  stats (may be NULL, 27
-// values): [events, frames, same, same but not packed, copied, differ, missing, undecodable, extra, the event file (0 same,
+// abub::VerifyRun of two runs opened with abh_run_open: is `other` pixel for pixel the run `src`?  stats (may be NULL, 29
+// values; the last two: the source's and the other run's archive entries inflated by abub_unzip_dev, ABUB_GPU_UNZIP=1): [events, frames, same, same but not packed, copied, differ, missing, undecodable, extra, the event file (0 same,
 // 1 differs, 2 missing, 3 not compared), seconds, the report's length; of the device route: frames compared by the kernel,
 // frames that took the host route, the source's frames decoded by the PNG kernel, by the packed kernel, by a host thread,
 // the other run's likewise, batches, seconds of the legs read, upload + decode, compare, the device (-1: it was not
@@ -284,13 +310,14 @@ static int runVerify(void *a, void *b, int ncams, int nthreads, int device, bool
             report[n] = 0;
         }
         if (stats) {
-            const double v[27] = {(double)st.events, (double)st.frames, (double)st.same, (double)st.sameNotPacked, (double)st.copied,
+            const double v[29] = {(double)st.events, (double)st.frames, (double)st.same, (double)st.sameNotPacked, (double)st.copied,
                                   (double)st.differ, (double)st.missing, (double)st.undecodable, (double)st.extra, (double)st.eventFile,
                                   st.total_s, (double)text.size(), (double)st.framesKernel, (double)st.framesHostRoute,
                                   (double)st.srcGpuPngDecoded, (double)st.srcGpuUnpacked, (double)st.srcHostDecoded,
                                   (double)st.otherGpuPngDecoded, (double)st.otherGpuUnpacked, (double)st.otherHostDecoded,
                                   (double)st.batches, st.read_s, st.decode_s, st.compare_s, (double)st.device,
-                                  (double)st.srcGpuBmpDecoded, (double)st.otherGpuBmpDecoded};
+                                  (double)st.srcGpuBmpDecoded, (double)st.otherGpuBmpDecoded, (double)st.srcGpuUnzipped,
+                                  (double)st.otherGpuUnzipped};
             std::memcpy(stats, v, sizeof v);
         }
         return rc;
@@ -438,6 +465,7 @@ int abh_train_device(void *r, int ncams, int *status, int *tss, uint8_t *mu_out,
             stats[3] = st.total_s;
             stats[4] = (double)st.framesGpuUnpacked;
             stats[5] = (double)st.framesGpuBmp;
+            stats[6] = (double)st.framesGpuUnzipped;
         }
         if (rc != 0) {
             run->last.error = why;
@@ -536,9 +564,10 @@ int abh_run_batched(void *r, int ncams, const char *maskdir, const char *outdir,
         if (rc != 0)
             run->last.error = why;
         if (statsOut) {
-            const double v[15] = {bs.total_s, bs.list_s, bs.decode_s, bs.gpu_s, bs.write_s, (double)bs.frames, (double)bs.framesFailed,
+            const double v[17] = {bs.total_s, bs.list_s, bs.decode_s, bs.gpu_s, bs.write_s, (double)bs.frames, (double)bs.framesFailed,
                                   (double)bs.batches, (double)bs.eventsPerBatch, (double)bs.gpus, (double)bs.framesGpuDecoded,
-                                  (double)bs.framesHostDecoded, bs.gpudecode_s, (double)bs.framesGpuUnpacked, (double)bs.framesGpuBmp};
+                                  (double)bs.framesHostDecoded, bs.gpudecode_s, (double)bs.framesGpuUnpacked, (double)bs.framesGpuBmp,
+                                  (double)bs.framesGpuUnzipped, bs.unzip_s};
             std::memcpy(statsOut, v, sizeof v);
         }
         return rc;

@@ -116,6 +116,7 @@ int TrainOnDevice(Parser *parser, const std::vector<std::string> &EventList, std
     total = 0;
     std::fill(batch.decodedBy, batch.decodedBy + NGpuCodecs, 0);
     batch.hostDecoded = 0;
+    batch.unzip.begin();
     if (W) {
         batch.sizer.reset(parser->clone());
         for (int c = 0; c < C; ++c) {
@@ -126,8 +127,10 @@ int TrainOnDevice(Parser *parser, const std::vector<std::string> &EventList, std
                     if (const std::string *n = nameOf(c, e, q)) {
                         FileTask t;
                         t.s = (c * E + e) * Q + q;
-                        if (devDecode)
+                        if (devDecode) {
                             planFileTask(*batch.sizer, EventList[e], *n, t, total);
+                            batch.unzip.plan(*batch.sizer, EventList[e], *n, t);
+                        }
                         if (!devDecode || t.state == FileTask::Bad)
                             t.state = FileTask::Other; // decoded by GetImage below (a parser that has no files to hand out)
                         tasks.push_back(std::move(t));
@@ -137,12 +140,13 @@ int TrainOnDevice(Parser *parser, const std::vector<std::string> &EventList, std
     PinnedBuffer &h_files = batch.h_files;
     if (total)
         h_files.grow(total + 16);
-    forEachTask(parser, nthr, tasks.size(), [&](Parser &p, size_t i) {
+    batch.unzip.ready();
+    const auto readOne = [&](Parser &p, size_t i) {
         FileTask &t = tasks[i];
         const int c = t.s / (E * Q), e = t.s / Q % E, q = t.s % Q;
         const std::string &n = *nameOf(c, e, q);
         if (t.state != FileTask::Other) {
-            readFileTask(p, EventList[e], n, t, h_files.get(), W, H);
+            readFileTask(p, EventList[e], n, t, h_files.get(), W, H, batch.unzip.comp());
             if (t.state == FileTask::Bad && t.read) { // refused at W x H: a frame of another size is not a corrupt one
                 cv::Mat m = cv::imdecode(h_files.get() + t.off, (size_t)t.size, 0);
                 otherSize[t.s] = !m.empty() && (m.cols != W || m.rows != H);
@@ -164,7 +168,12 @@ int TrainOnDevice(Parser *parser, const std::vector<std::string> &EventList, std
         } catch (...) {
             frameError[t.s] = "unknown exception";
         }
-    });
+    };
+    forEachTask(parser, nthr, tasks.size(), readOne);
+    if (batch.unzip.comp()) {
+        HIPOK(hipSetDevice(opt.device));
+        batch.inflate(parser, nthr, B.stream.get(), readOne);
+    }
 
     DeviceTrainStats st;
     st.slabBytes = slab;
@@ -187,6 +196,7 @@ int TrainOnDevice(Parser *parser, const std::vector<std::string> &EventList, std
             st.framesGpuDecoded = std::accumulate(batch.decodedBy, batch.decodedBy + NGpuCodecs, 0LL);
             st.framesGpuUnpacked = batch.decodedBy[GpuPacked];
             st.framesGpuBmp = batch.decodedBy[GpuBmp];
+            st.framesGpuUnzipped = batch.unzip.unzipped;
             st.framesHostDecoded = batch.hostDecoded;
             i0 = i1;
         }

@@ -38,6 +38,7 @@ struct DeviceTrainStats {
     long long frames = 0, framesGpuDecoded = 0, framesHostDecoded = 0;
     long long framesGpuUnpacked = 0; // of framesGpuDecoded: packed frames, by abub_abf_decode_dev
     long long framesGpuBmp = 0;      // of framesGpuDecoded: BMP frames, by abub_bmp_decode_dev
+    long long framesGpuUnzipped = 0; // ABUB_GPU_UNZIP=1: archive entries whose zip layer abub_unzip_dev inflated
     size_t slabBytes = 0;
     int decodeLaunches = 0;
 };

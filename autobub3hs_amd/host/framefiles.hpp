@@ -8,7 +8,9 @@
 // frames, its descriptors, its status buffers and its count are indexed by it, and launch and finish loop over the lanes.
 // FileBatch is the unit "one set of files on the device, decoded into one slab" of device training, repack, unpack and
 // verify; RunBatched keeps its own slots (its upload runs on the look-ahead thread) and uses the lanes.  The decoders'
-// width gate, the batch size and the ABUB_GPU_DECODE override are one copy here.  Internal to the host library.
+// width gate, the batch size and the ABUB_GPU_DECODE override are one copy here.  With ABUB_GPU_UNZIP=1 the zip layer of a
+// deflated archive entry is inflated on the device between the read and the walk (GpuUnzip, abub_unzip_dev).  Internal to the
+// host library.
 #ifndef ABUB3HS_FRAMEFILES_HPP
 #define ABUB3HS_FRAMEFILES_HPP
 
@@ -108,11 +110,19 @@ struct FileTask {
     int state = Other;
     GpuCodec codec = GpuPng;
     bool read = false; // the file's bytes are in the buffer (a Bad frame may still have been read)
+    // ABUB_GPU_UNZIP=1, an archive entry of method 8 (GpuUnzip below).  ZipPlanned: its compressed bytes are to be read to
+    // `coff` of the compressed buffer; ZipRead: they are there, the file waits for the device's inflate (state stays Planned);
+    // ZipInflated: the kernel has put the file at `off` of the file buffer, what follows a read is still to do
+    enum { ZipNone = 0, ZipPlanned = 1, ZipRead = 2, ZipInflated = 3 };
+    int zip = ZipNone;
+    size_t coff = 0;
+    uint32_t clen = 0, crc = 0;
     PngInfo info;
     BmpInfo bmp;
     std::vector<uint8_t> pix;
 };
 
+static_assert(sizeof(abub_zip_entry) == 24, "abub_zip_entry is the 24 bytes include/abub_hip.h states");
 static_assert(sizeof(abub_bmp_frame) == 32, "abub_bmp_frame is the 32 bytes include/abub_hip.h states");
 
 // Where one frame of a batch is and where it goes
@@ -198,18 +208,34 @@ inline bool gpuCodecOf(const uint8_t *data, size_t size, int W, int H, FileTask 
     return true;
 }
 
-// On a pool thread: the file into files + t.off, walked for the W x H GPU decoder, else decoded here
-inline void readFileTask(Parser &p, const std::string &ev, const std::string &name, FileTask &t, uint8_t *files, int W, int H)
+// On a pool thread: the file into files + t.off, walked for the W x H GPU decoder, else decoded here.  A task planned for
+// the device's inflate (t.zip, `comp` = the compressed buffer) only has its compressed bytes read and stays Planned; the
+// same call once more after GpuUnzip::run does the rest (the file is in place: ZipInflated) or all of it (ZipNone).
+inline void readFileTask(Parser &p, const std::string &ev, const std::string &name, FileTask &t, uint8_t *files, int W, int H,
+                         uint8_t *comp = nullptr)
 {
-    if (t.state != FileTask::Planned)
+    if (t.state != FileTask::Planned || t.zip == FileTask::ZipRead)
         return;
     uint8_t *dst = files + t.off;
     long long got = -1;
-    try {
-        got = p.ReadImageFile(ev, name, dst, (size_t)t.size);
-    } catch (...) {
-        got = -1;
+    if (t.zip == FileTask::ZipPlanned) {
+        try {
+            got = comp ? p.ReadImageEntryRaw(ev, name, comp + t.coff, t.clen) : -1;
+        } catch (...) {
+            got = -1;
+        }
+        t.zip = got == (long long)t.clen ? FileTask::ZipRead : FileTask::ZipNone;
+        if (t.zip == FileTask::ZipRead)
+            return;
     }
+    if (t.zip == FileTask::ZipInflated)
+        got = t.size;
+    else
+        try {
+            got = p.ReadImageFile(ev, name, dst, (size_t)t.size);
+        } catch (...) {
+            got = -1;
+        }
     if (got != t.size) {
         t.state = FileTask::Bad;
         return;
@@ -227,6 +253,111 @@ inline void readFileTask(Parser &p, const std::string &ev, const std::string &na
         t.state = FileTask::Bad;
     }
 }
+
+// ABUB_GPU_UNZIP=1: the zip layer of deflated archive entries is inflated on the GPU (abub_unzip_dev).  Off by default.
+inline bool gpuUnzipEnabled()
+{
+    const char *e = getenv("ABUB_GPU_UNZIP");
+    return e && atoi(e) != 0;
+}
+
+// The inflate of a batch's deflated archive entries on the device, between the pool's read and the walk of the files:
+// begin(), plan() behind every planFileTask, ready(), the pool (readFileTask with comp()), then run(): the compressed bytes
+// go up, abub_unzip_dev inflates every entry to its file's place in d_files, the files come back into the pinned file buffer
+// (pngWalk needs the chunk headers, the fallback decoder the file), and `readOne` -- the caller's pool function -- runs once
+// more over those tasks.  An entry the kernel refuses, for any status, is read by the host as ever (ReadImageFile).
+struct GpuUnzip {
+    PinnedBuffer h_comp, h_status;
+    DeviceBuffer d_comp, d_ent, d_status;
+    size_t compTotal = 0;
+    long long unzipped = 0; // entries the kernel inflated with status 0
+    double device_s = 0;    // wall time of inflate(): the upload of the compressed bytes, the kernels, the copy back, the wait
+    bool on = false;
+    std::vector<size_t> idx;
+    std::vector<abub_zip_entry> ent;
+
+    void begin()
+    {
+        on = gpuUnzipEnabled();
+        compTotal = 0;
+        unzipped = 0;
+        device_s = 0;
+    }
+    // t has been planned (planFileTask): is its entry one for the kernel?
+    void plan(Parser &sizer, const std::string &ev, const std::string &name, FileTask &t)
+    {
+        Parser::EntryInfo e;
+        if (!on || t.state != FileTask::Planned || !sizer.GetImageEntryInfo(ev, name, e) || e.method != 8 ||
+            e.compressedSize >= (1ull << 28) || e.uncompressedSize >= (1ull << 28) || (long long)e.uncompressedSize != t.size ||
+            compTotal >= ((size_t)1 << 32) - ((size_t)1 << 29))
+            return;
+        t.zip = FileTask::ZipPlanned;
+        t.coff = compTotal;
+        t.clen = (uint32_t)e.compressedSize;
+        t.crc = e.crc32;
+        compTotal += (((size_t)t.clen + 15) & ~(size_t)15) + 16;
+    }
+    void ready()
+    {
+        if (compTotal)
+            h_comp.grow(compTotal + 16);
+    }
+    uint8_t *comp() const { return compTotal ? h_comp.get() : nullptr; }
+
+    // tasks first[0 .. n), their files in h_files / d_files (total bytes planned); queued on `stream` and waited for
+    template <class Fn>
+    void run(FileTask *first, size_t n, uint8_t *h_files, DeviceBuffer &d_files, size_t total, hipStream_t stream, Parser *parser,
+             int nthreads, const Fn &readOne)
+    {
+        if (inflate(first, n, h_files, d_files, total, stream))
+            forEachTask(parser, nthreads, idx.size(), [&](Parser &p, size_t k) { readOne(p, idx[k]); });
+    }
+    // the device's part alone: afterwards `idx` holds the tasks whose read is to be finished (false: none)
+    bool inflate(FileTask *first, size_t n, uint8_t *h_files, DeviceBuffer &d_files, size_t total, hipStream_t stream)
+    {
+        idx.clear();
+        ent.clear();
+        for (size_t i = 0; i < n; ++i)
+            if (first[i].zip == FileTask::ZipRead) {
+                const FileTask &t = first[i];
+                idx.push_back(i);
+                ent.push_back(abub_zip_entry{(uint32_t)t.coff, t.clen, (uint32_t)t.size, t.crc, (uint64_t)t.off});
+            }
+        if (idx.empty())
+            return false;
+        const double t0 = nowMs();
+        const size_t ne = ent.size();
+        d_comp.grow(compTotal + 16);
+        d_files.grow(total + 16);
+        d_ent.grow(ne * sizeof(abub_zip_entry));
+        d_status.grow(ne * sizeof(int32_t));
+        if (h_status.capacity() < ne * sizeof(int32_t))
+            h_status.allocate(ne * sizeof(int32_t) + 64);
+        HIPOK(hipMemcpyAsync(d_comp.get(), h_comp.get(), compTotal, hipMemcpyHostToDevice, stream));
+        HIPOK(hipMemcpyAsync(d_ent.get(), ent.data(), ne * sizeof(abub_zip_entry), hipMemcpyHostToDevice, stream));
+        check(abub_unzip_dev(d_comp.get(), compTotal, (const abub_zip_entry *)d_ent.get(), (int)ne, d_files.get(), total + 16,
+                             (int32_t *)d_status.get(), stream),
+              "abub_unzip_dev");
+        HIPOK(hipMemcpyAsync(h_status.get(), d_status.get(), ne * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+        // the files back, one copy per run of entries whose files lie next to each other (a file between two of them that is
+        // not this stage's is in h_files only); a refused entry's bytes too: the host's read overwrites them
+        for (size_t k = 0; k < ne;) {
+            const uint64_t from = ent[k].dst;
+            uint64_t upto = from + ent[k].ulen;
+            for (++k; k < ne && ent[k].dst == ((upto + 15) & ~(uint64_t)15); ++k)
+                upto = ent[k].dst + ent[k].ulen;
+            HIPOK(hipMemcpyAsync(h_files + from, d_files.get() + from, upto - from, hipMemcpyDeviceToHost, stream));
+        }
+        HIPOK(hipStreamSynchronize(stream));
+        const int32_t *status = (const int32_t *)h_status.get();
+        for (size_t k = 0; k < ne; ++k) {
+            first[idx[k]].zip = status[k] == 0 ? FileTask::ZipInflated : FileTask::ZipNone;
+            unzipped += status[k] == 0;
+        }
+        device_s += (nowMs() - t0) * 1e-3;
+        return true;
+    }
+};
 
 // The descriptors of the tasks' frames, in task order; dstOf(s, f): byte offset of the decoded frame from the output
 // (tasks [first, last); the files of every task are in one buffer of totalFileBytes)
@@ -388,7 +519,14 @@ struct FileBatch {
     FileDescs fd;
     std::vector<uint8_t> good;
     long long decodedBy[NGpuCodecs] = {}, hostDecoded = 0;
+    GpuUnzip unzip; // ABUB_GPU_UNZIP=1: begin / plan / ready around the planning, comp() for the pool, then inflate()
 
+    // after the pool has read ft into h_files: the deflated archive entries inflated on the device (GpuUnzip::run)
+    template <class Fn>
+    void inflate(Parser *parser, int nthreads, hipStream_t cs, const Fn &readOne)
+    {
+        unzip.run(ft.data(), ft.size(), h_files.get(), d_files, total, cs, parser, nthreads, readOne);
+    }
     // a slab of `bytes` for frames 0 .. nslots-1, none of them in place yet (its contents are the caller's to clear)
     void reset(size_t nslots, size_t bytes)
     {

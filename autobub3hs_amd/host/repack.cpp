@@ -220,18 +220,21 @@ void deviceFrames(const Codec &codec, Parser *parser, const Plan &pl, int nthrea
         double t0 = nowMs();
         ft.assign(n, FileTask());
         B.total = 0;
+        B.unzip.begin();
         for (size_t i = 0; i < n; ++i) {
             const Task &t = pl.tasks[i0 + i];
             ft[i].s = (int)i;
             planFileTask(*B.sizer, pl.events[t.ev], t.name, ft[i], B.total);
+            B.unzip.plan(*B.sizer, pl.events[t.ev], t.name, ft[i]);
         }
         B.h_files.grow(B.total + 16);
-        forEachTask(parser, nthreads, n, [&](Parser &p, size_t i) {
+        B.unzip.ready();
+        const auto readOne = [&](Parser &p, size_t i) {
             const Task &t = pl.tasks[i0 + i];
             FileTask &f = ft[i];
             const std::string &ev = pl.events[t.ev];
-            readFileTask(p, ev, t.name, f, B.h_files.get(), W, H);
-            if (f.onGpu())
+            readFileTask(p, ev, t.name, f, B.h_files.get(), W, H, B.unzip.comp());
+            if (f.onGpu() || f.zip == FileTask::ZipRead) // (ZipRead: once more after the device's inflate)
                 return;
             if (f.state == FileTask::HostDecoded) { // (16-bit, colour, BMP: this thread decoded it at W x H)
                 static thread_local std::vector<unsigned char> packed;
@@ -247,7 +250,10 @@ void deviceFrames(const Codec &codec, Parser *parser, const Plan &pl, int nthrea
                 tally.add(hostFrame(codec, p, ev, t.name, pl.pathOf(t)));
             f.pix = std::vector<uint8_t>();
             f.state = FileTask::Other;
-        });
+        };
+        forEachTask(parser, nthreads, n, readOne);
+        B.inflate(parser, nthreads, cs, readOne);
+        st.framesGpuUnzipped += B.unzip.unzipped;
         st.read_s += (nowMs() - t0) * 1e-3;
 
         // ---- upload and decode ------------------------------------------------------------------------------------------

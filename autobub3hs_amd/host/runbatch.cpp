@@ -65,12 +65,15 @@ struct Slot {
     DeviceBuffer d_frames;     // the whole batch, [G][C][Fmax][H][W]
     PinnedBuffer h_files;      // the GPU share's files, each at a 16-byte boundary ...
     DeviceBuffer d_files;      // ... uploaded by the reading thread: the copy runs beside the GPU work of the batch before
+    GpuUnzip unzip;            // ABUB_GPU_UNZIP=1: the deflated archive entries of the batch, inflated on the reading thread's stream
     std::exception_ptr err;    // of the look-ahead thread that read the batch
     struct Read {
         std::vector<StackMeta> meta;
         FileDescs files;       // the frames the GPU decodes; those of the GPU share a reading thread decoded
         double ms = 0;
         long long hostGood = 0;
+        long long unzipped = 0; // archive entries abub_unzip_dev inflated
+        double unzip_s = 0;     // ... and what the device's part of that took (GpuUnzip::device_s)
     } r;
 };
 
@@ -239,6 +242,7 @@ int runBatchedOn(Workers &ws, Parser *parser, const std::vector<std::string> &Ev
         std::vector<FileTask> tasks; // (in stack order: the GPU's files are read first, its work can start before the host's is done)
         std::unique_ptr<Parser> sizer(Ggpu ? parser->clone() : nullptr);
         size_t total = 0;
+        sl.unzip.begin();
         for (int k = 0; k < G; ++k)
             for (int c = 0; c < C; ++c) {
                 StackMeta &m = r.meta[(size_t)k * C + c];
@@ -253,15 +257,18 @@ int runBatchedOn(Workers &ws, Parser *parser, const std::vector<std::string> &Ev
                     FileTask t;
                     t.s = k * C + c;
                     t.f = f;
-                    if (k < Ggpu)
+                    if (k < Ggpu) {
                         planFileTask(*sizer, m.eventID, m.names[f], t, total);
+                        sl.unzip.plan(*sizer, m.eventID, m.names[f], t);
+                    }
                     tasks.push_back(std::move(t));
                 }
             }
         if (Ggpu)
             sl.h_files.grow(total + 16);
+        sl.unzip.ready();
         std::atomic<long long> hostGood{0}, hostBad{0};
-        forEachTask(parser, nthreads, tasks.size(), [&](Parser &p, size_t i) {
+        const auto readOne = [&](Parser &p, size_t i) {
             FileTask &t = tasks[i];
             StackMeta &m = r.meta[t.s];
             if (t.state == FileTask::Other) { // the host share: straight into the pinned slab
@@ -269,8 +276,12 @@ int runBatchedOn(Workers &ws, Parser *parser, const std::vector<std::string> &Ev
                 ++(decodeFrame(p, m, t.f, dst, W, H) ? hostGood : hostBad);
                 return;
             }
-            readFileTask(p, m.eventID, m.names[t.f], t, sl.h_files.get(), W, H);
-        });
+            readFileTask(p, m.eventID, m.names[t.f], t, sl.h_files.get(), W, H, sl.unzip.comp());
+        };
+        forEachTask(parser, nthreads, tasks.size(), readOne);
+        sl.unzip.run(tasks.data(), tasks.size(), sl.h_files.get(), sl.d_files, total, upStream.get(), parser, nthreads, readOne);
+        r.unzipped = sl.unzip.unzipped;
+        r.unzip_s = sl.unzip.device_s;
         r.files.bad = hostBad;
         r.hostGood = hostGood;
         buildFileDescs(tasks.data(), tasks.data() + tasks.size(), total, r.files, [&](int s, int f) { return ((uint64_t)s * Fmax + f) * P; });
@@ -438,6 +449,8 @@ int runBatchedOn(Workers &ws, Parser *parser, const std::vector<std::string> &Ev
                     st.framesHostDecoded += onHost;
                     st.framesGpuUnpacked += R.files.decodedBy[GpuPacked];
                     st.framesGpuBmp += R.files.decodedBy[GpuBmp];
+                    st.framesGpuUnzipped += R.unzipped;
+                    st.unzip_s += R.unzip_s;
                     st.gpudecode_s += pngms * 1e-3;
                 }
                 slot ^= 1;
@@ -591,7 +604,9 @@ PreparedRun PrepareRun(const RunSpec &r, const BatchedRunOptions &opt, int train
         to.buffers = buffers;
         to.log = buffered ? &pr.log : nullptr;
         std::string why;
-        declined = TrainOnDevice(pr.parser.get(), pr.events, pr.trainers, to, nullptr, &why);
+        DeviceTrainStats ts;
+        declined = TrainOnDevice(pr.parser.get(), pr.events, pr.trainers, to, &ts, &why);
+        pr.trainGpuUnzipped = ts.framesGpuUnzipped;
         if (declined)
             say(pr, buffered, "device training not used (" + why + "): training on host threads\n");
     }
@@ -679,6 +694,7 @@ int RunCampaign(const std::vector<RunSpec> &runs, const BatchedRunOptions &opt, 
             next = prepare(k + 1);
         cs.train_s += pr.train_s;
         cs.trainedOnHost += pr.hostTrained ? 1 : 0;
+        cs.trainGpuUnzipped += pr.trainGpuUnzipped;
         CommitRun(r, opt, pr);
         if (pr.rc) {
             cs.status[k] = pr.rc;
@@ -698,6 +714,7 @@ int RunCampaign(const std::vector<RunSpec> &runs, const BatchedRunOptions &opt, 
         if (rc == 0) {
             PrintBatchedLine(bs);
             cs.frames += bs.frames + bs.framesFailed;
+            cs.framesGpuUnzipped += bs.framesGpuUnzipped;
         } else {
             std::cout << "batched detect not used (" << why << "): falling back to the per-event loop" << std::endl;
             RunPerEvent(pr.parser.get(), pr.events, pr.trainers, r.numCams, r.eventDir, opt.outDir, r.runId, r.frameOffset,

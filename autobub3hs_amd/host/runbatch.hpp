@@ -41,6 +41,8 @@ struct BatchedRunStats {
     long long framesGpuDecoded = 0, framesHostDecoded = 0; // of `frames`: by the GPU decoders / by a host thread
     long long framesGpuUnpacked = 0;                       // of framesGpuDecoded: packed frames, by abub_abf_decode_dev
     long long framesGpuBmp = 0;                            // of framesGpuDecoded: BMP frames, by abub_bmp_decode_dev
+    long long framesGpuUnzipped = 0;                       // ABUB_GPU_UNZIP=1: archive entries whose zip layer abub_unzip_dev inflated
+    double unzip_s = 0;                                    // ... of decode_s: upload of the compressed bytes, kernels, copy back, wait
     double gpudecode_s = 0;                                // upload of the files + the decode kernels, summed over batches
     int events = 0, batches = 0, eventsPerBatch = 0, W = 0, H = 0, Fmax = 0, gpus = 0;
 };
@@ -85,6 +87,7 @@ struct RepackStats {
     // thread after a kernel refused the file.
     long long framesGpuEncoded = 0, framesHostRoute = 0;
     long long framesGpuPngDecoded = 0, framesGpuUnpacked = 0, framesHostDecoded = 0, framesGpuBmpDecoded = 0;
+    long long framesGpuUnzipped = 0; // ABUB_GPU_UNZIP=1: archive entries whose zip layer abub_unzip_dev inflated
     int device = -1, W = 0, H = 0, batches = 0;   // of the device route (device -1: it was not taken)
     double read_s = 0, decode_s = 0, encode_s = 0, copy_s = 0, write_s = 0; // its legs, summed over the batches
 };
@@ -142,6 +145,7 @@ struct VerifyStats {
     long long srcGpuPngDecoded = 0, srcGpuUnpacked = 0, srcHostDecoded = 0;
     long long otherGpuPngDecoded = 0, otherGpuUnpacked = 0, otherHostDecoded = 0;
     long long srcGpuBmpDecoded = 0, otherGpuBmpDecoded = 0;
+    long long srcGpuUnzipped = 0, otherGpuUnzipped = 0; // ABUB_GPU_UNZIP=1: archive entries of each side abub_unzip_dev inflated
     int device = -1, W = 0, H = 0, batches = 0;
     double read_s = 0, decode_s = 0, compare_s = 0; // its legs, summed over the batches
     const char *eventFileName() const;              // "same", "differs", "missing", "not compared"
@@ -175,6 +179,7 @@ struct PreparedRun {
     int rc = 0;
     double train_s = 0;
     bool hostTrained = false;
+    long long trainGpuUnzipped = 0; // ABUB_GPU_UNZIP=1: archive entries abub_unzip_dev inflated for the device training
     std::string log; // stdout lines held back (buffered)
     PreparedRun();
     PreparedRun(PreparedRun &&);
@@ -197,6 +202,7 @@ struct CampaignStats {
     double train_s = 0;            // training, summed over runs
     double trainExposed_s = 0;     // ... of which the detect loop waited for
     int pipelinesBuilt = 0;
+    long long framesGpuUnzipped = 0, trainGpuUnzipped = 0; // ABUB_GPU_UNZIP=1: archive entries inflated by abub_unzip_dev, detect / training
     int trainedOnHost = 0;         // runs trained by the host Trainer (ABUB_TRAIN_ON_GPU=0, or TrainOnDevice declined)
     std::vector<int> status;       // per run: 0, -5, -6, -7 (what a single-run invocation returns)
     std::vector<std::string> notRun; // runs never started after a GPU failure

@@ -236,6 +236,7 @@ void deviceFrames(Parser *src, Parser *other, const Plan &pl, int nthreads, int 
     DeviceBuffer d_meta;
     Stream stream;
     hipStream_t cs = stream.get();
+    long long srcUnzipped = 0, otherUnzipped = 0;
 
     for (size_t i0 = 0; i0 < pl.tasks.size(); i0 += perBatch) {
         const size_t n = std::min(perBatch, pl.tasks.size() - i0);
@@ -245,27 +246,36 @@ void deviceFrames(Parser *src, Parser *other, const Plan &pl, int nthreads, int 
         for (FileBatch *side : {&S, &O}) {
             side->ft.assign(n, FileTask());
             side->total = 0;
+            side->unzip.begin();
             side->reset(n, n * stride);
         }
         for (size_t i = 0; i < n; ++i) {
             const FrameTask &t = pl.tasks[i0 + i];
             S.ft[i].s = O.ft[i].s = (int)i;
             planFileTask(*S.sizer, pl.events[t.ev], t.name, S.ft[i], S.total);
-            if (pl.listed[t.ev].count(t.name))
+            S.unzip.plan(*S.sizer, pl.events[t.ev], t.name, S.ft[i]);
+            if (pl.listed[t.ev].count(t.name)) {
                 planFileTask(*O.sizer, pl.events[t.ev], t.name, O.ft[i], O.total);
-            else
+                O.unzip.plan(*O.sizer, pl.events[t.ev], t.name, O.ft[i]);
+            } else
                 O.ft[i].state = FileTask::Bad;
         }
         S.h_files.grow(S.total + 16);
         O.h_files.grow(O.total + 16);
-        forEachPair(src, other, nthreads, n, [&](Clones &c, size_t i) {
+        S.unzip.ready();
+        O.unzip.ready();
+        std::vector<uint8_t> again(n, 0); // a side waits for the device's inflate of its archive entry (ABUB_GPU_UNZIP=1)
+        const auto readPair = [&](Clones &c, size_t i) {
             const FrameTask &t = pl.tasks[i0 + i];
             FileTask &fs = S.ft[i], &fo = O.ft[i];
-            if (fs.state == FileTask::Planned && fo.state == FileTask::Planned) {
-                readFileTask(*c.src, pl.events[t.ev], t.name, fs, S.h_files.get(), W, H);
+            if ((fs.state == FileTask::Planned && fo.state == FileTask::Planned) || again[i]) {
+                readFileTask(*c.src, pl.events[t.ev], t.name, fs, S.h_files.get(), W, H, S.unzip.comp());
                 if (fs.state != FileTask::Bad)
-                    readFileTask(*c.other, pl.events[t.ev], t.name, fo, O.h_files.get(), W, H);
+                    readFileTask(*c.other, pl.events[t.ev], t.name, fo, O.h_files.get(), W, H, O.unzip.comp());
             }
+            again[i] = fs.zip == FileTask::ZipRead || fo.zip == FileTask::ZipRead;
+            if (again[i])
+                return;
             const bool sOk = fs.onGpu() || fs.state == FileTask::HostDecoded, oOk = fo.onGpu() || fo.state == FileTask::HostDecoded;
             if (sOk && oOk)
                 return;
@@ -273,7 +283,21 @@ void deviceFrames(Parser *src, Parser *other, const Plan &pl, int nthreads, int 
             done[i] = 1;
             fs.pix = fo.pix = std::vector<uint8_t>();
             fs.state = fo.state = FileTask::Other;
-        });
+        };
+        forEachPair(src, other, nthreads, n, readPair);
+        const bool sz = S.unzip.inflate(S.ft.data(), n, S.h_files.get(), S.d_files, S.total, cs);
+        const bool oz = O.unzip.inflate(O.ft.data(), n, O.h_files.get(), O.d_files, O.total, cs);
+        if (sz || oz) {
+            std::vector<size_t> idx;
+            for (size_t i = 0; i < n; ++i)
+                if (again[i])
+                    idx.push_back(i);
+            forEachPair(src, other, nthreads, idx.size(), [&](Clones &c, size_t k) { readPair(c, idx[k]); });
+        }
+        srcUnzipped += S.unzip.unzipped;
+        otherUnzipped += O.unzip.unzipped;
+        st.srcGpuUnzipped = srcUnzipped;
+        st.otherGpuUnzipped = otherUnzipped;
         st.read_s += (nowMs() - t0) * 1e-3;
 
         // ---- upload and decode ------------------------------------------------------------------------------------------

@@ -37,6 +37,17 @@ public:
     // caller then uses GetImageInto); ReadImageFile: the bytes into dst (room for cap), returns their count or -1.
     virtual long long GetImageFileSize(std::string EventID, std::string FrameName);
     virtual long long ReadImageFile(std::string EventID, std::string FrameName, unsigned char *dst, size_t cap);
+    // not in the reference either: the frame's archive ENTRY, for the inflate on the GPU (abub_unzip_dev).  GetImageEntryInfo:
+    // the entry's method (0 stored, 8 deflated, ...), sizes and CRC-32 as the archive's directory states them; false = not
+    // available (no archive behind this parser, no such frame, an encrypted entry).  ReadImageEntryRaw: the entry's
+    // COMPRESSED bytes as they lie in the archive into dst (room for cap), returns their count or -1.
+    struct EntryInfo {
+        int method = -1;
+        unsigned long long compressedSize = 0, uncompressedSize = 0;
+        unsigned int crc32 = 0;
+    };
+    virtual bool GetImageEntryInfo(std::string EventID, std::string FrameName, EntryInfo &info);
+    virtual long long ReadImageEntryRaw(std::string EventID, std::string FrameName, unsigned char *dst, size_t cap);
     virtual void GetEventDirLists(std::vector<std::string> &EventList) = 0;
     virtual void GetFileLists(const char *EventFolder, std::vector<std::string> &FileList, const char *camera_out_name) = 0;
     // frame names of camera `camera` in event `EventID`, sorted lexicographically (RawParser.cpp:155)

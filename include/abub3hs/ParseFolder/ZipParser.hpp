@@ -17,6 +17,8 @@ public:
         std::string name;
         uint64_t localHeaderOffset, compressedSize, uncompressedSize;
         int method; // 0 stored, 8 deflate
+        uint32_t crc32; // of the uncompressed bytes, as the central directory states it
+        uint16_t flags; // general purpose bits (bit 0: encrypted)
     };
     struct Index {
         std::vector<Entry> entries;                                          // archive order
@@ -37,6 +39,8 @@ public:
     int GetImageInto(std::string EventID, std::string FrameName, unsigned char *dst, int W, int H) override;
     long long GetImageFileSize(std::string EventID, std::string FrameName) override;
     long long ReadImageFile(std::string EventID, std::string FrameName, unsigned char *dst, size_t cap) override;
+    bool GetImageEntryInfo(std::string EventID, std::string FrameName, EntryInfo &info) override;
+    long long ReadImageEntryRaw(std::string EventID, std::string FrameName, unsigned char *dst, size_t cap) override;
     void GetEventDirLists(std::vector<std::string> &EventList) override;
     void GetFileLists(const char *EventFolder, std::vector<std::string> &FileList, const char *camera_out_name) override;
     void ParseAndSortFramesInFolder(std::string EventID, int camera, std::vector<std::string> &Contents) override;

@@ -584,6 +584,44 @@ int abub_bmp_decode_dev(const uint8_t *files, size_t files_bytes, const abub_bmp
                         const uint8_t *luts, int nluts, int W, int H, uint8_t *out, size_t out_bytes, int32_t *status,
                         void *stream);
 
+/* ---- deflated zip entries inflated on the GPU (abub_png.hip) ---------------------------------------------------------
+ * Replaces, for batches of archive entries of method 8, the zlib inflate of ZipParser::readEntry (host/ZipParser.cpp) that
+ * ZipParser::ReadImageFile runs on the reading thread.  A zip entry is a RAW deflate stream (RFC 1951): no header, no
+ * trailer; its output length and CRC-32 come from the archive's central directory and differ from entry to entry.  The
+ * caller uploads the COMPRESSED bytes as they lie in the archive; the inflate is k_png_inflate's (same device functions,
+ * the raw mode a template parameter: the stream starts at bit 0 and is read in place, no Adler-32), a second kernel takes
+ * the CRC-32 of every inflated entry.  Every descriptor is checked against comp_bytes and out_bytes before a byte is read:
+ * a bad one gets ABUB_ZIP_E_DESC and not one byte of `out`; nothing is read outside `comp`, nothing written outside
+ * [dst, dst + align16(ulen)) of an entry.  Acceptance is ZipParser::readEntry's (zlib's Z_FINISH on a raw stream): status 0
+ * iff the stream reaches its final block's end having produced exactly ulen bytes -- input behind that point is ignored,
+ * ulen == 0 with an empty final block is accepted -- and their CRC-32 is `crc`.  A refused entry (positive status) may be
+ * partly or wholly written inside its own range; the caller inflates it on the host.  clen or ulen >= 2^28:
+ * ABUB_ZIP_E_DESC. */
+typedef struct abub_zip_entry {
+    uint32_t off, clen;  /* the raw deflate stream in `comp`: off a multiple of 16; clen rounded up to 16, plus 16, readable */
+    uint32_t ulen, crc;  /* exactly ulen bytes are expected; their CRC-32 (the zip / IEEE one) */
+    uint64_t dst;        /* byte offset of the inflated file from `out`: a multiple of 16, room for ulen rounded up to 16 */
+} abub_zip_entry;        /* 24 bytes */
+/* status[entry] after abub_unzip_dev: 0 = inflated and checked.  The deflate findings keep the numbers of
+ * ABUB_PNG_E_TRUNCATED ... ABUB_PNG_E_TOOLITTLE and ABUB_PNG_E_INTERNAL (TOOMUCH / TOOLITTLE: more / fewer than ulen bytes;
+ * a stream cut short is ABUB_PNG_E_TRUNCATED whatever the bytes behind it in `comp` are: they are read as zeros.  Near the
+ * stream's end ABUB_PNG_E_TRUNCATED can stand for either: an invalid code that starts inside the last 48 bits, or a block
+ * header error inside the last 14, is reported as TRUNCATED although the stream may be complete and wrong -- the kernel does
+ * not tell a code the missing bits would have completed from one they made). */
+#define ABUB_ZIP_E_DESC 1 /* descriptor outside comp_bytes / out_bytes, misaligned, or a length of 2^28 and more */
+#define ABUB_ZIP_E_CRC 16 /* exactly ulen bytes came out, but their CRC-32 is not `crc` */
+/* Two launches on `stream` (inflate: one workgroup of two waves per entry, 40 KiB of LDS; ABUB_PNG_WAVES=1: one wave; then
+ * the CRC-32: one workgroup per entry); every pointer is a device pointer, comp and out 16-byte aligned; status[nentries]
+ * is written for every entry.  Null pointers, nentries < 0 or a misaligned buffer: ABUB_E_INVALID before anything touches
+ * the device; nentries == 0: ABUB_OK, nothing touched.  No host synchronisation, no allocation. */
+int abub_unzip_dev(const uint8_t *comp, size_t comp_bytes, const abub_zip_entry *entries, int nentries,
+                   uint8_t *out, size_t out_bytes, int32_t *status, void *stream);
+/* The CRC kernel alone: crc[e] = CRC-32 (zlib.crc32) of the ulen bytes at buf + dst of entry e (off, clen and crc are not
+ * looked at); status[e] = 0, or ABUB_ZIP_E_DESC (dst not a multiple of 16, dst + align16(ulen) > buf_bytes, ulen >= 2^28:
+ * nothing read, crc[e] untouched).  Arguments as for abub_unzip_dev. */
+int abub_crc32_dev(const uint8_t *buf, size_t buf_bytes, const abub_zip_entry *entries, int nentries, uint32_t *crc,
+                   int32_t *status, void *stream);
+
 /* ---- packed frames ("ABF1") encoded on the GPU (abub_abf_enc.hip) -------------------------------------------------
  * What cv::abfEncode does on a host thread, for a batch of resident frames: file f is exactly the bytes
  * cv::abfEncode(pixels + src[f], W, H) writes (the host encoder is canonical: smallest width per block, zero padding
