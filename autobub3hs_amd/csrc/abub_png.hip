@@ -17,6 +17,9 @@
 //   k_png_unfilter  one wave per frame, lanes along x, rows in order (filter types None / Sub / Up in a few ops per
 //                   byte; Average and Paeth rows are a serial recurrence along x and take a lane-by-lane pass),
 //                   palette -> grey through the frame's 256-entry table, rows written coalesced into the frame slab.
+// abub_png_decode_typed_dev (ABUB_GPU_PNG_TYPES=1) also takes the other non-interlaced PNG types -- 16-bit, RGB(A), grey+alpha,
+// 1/2/4-bit -- by abub_png_frame.kind: the inflate sizes each frame by its kind, k_png_unfilter_typed unfilters such a frame
+// at its own filter distance and converts it to the 8-bit grey cv::imdecode(..., 0) gives.
 // Every access is bounds-checked against the sizes the caller states: the input is file content.  A frame the kernels
 // refuse (status != 0) is left to the caller, which decodes it on the host (the result is the same image or the same
 // failure: both follow RFC 1950/1951 and the PNG specification).
@@ -26,6 +29,8 @@
 // archive's central directory states for every inflated entry.
 #include "abub_dev.hpp"
 #include <stddef.h>
+#include <algorithm>
+#include <string>
 
 namespace {
 
@@ -1091,10 +1096,33 @@ __device__ __forceinline__ void png_inflate_stream(InflateLds &L, const uint8_t 
     }
 }
 
+// The typed kinds (abub_png_frame.kind = colour type | bit depth << 8; 0 = an 8-bit image, one byte per pixel): the bytes of
+// a scanline and the filter distance.  false for a kind outside the table.
+__host__ __device__ inline bool png_kind_row(uint32_t kind, int W, uint32_t &rowBytes, uint32_t &bpp)
+{
+    const uint32_t ctype = kind & 255, depth = kind >> 8;
+    uint32_t samples = 1;
+    bool ok = kind == 0;
+    if (ctype == 0)
+        ok |= depth == 1 || depth == 2 || depth == 4 || depth == 16;
+    else if (ctype == 3)
+        ok = depth == 1 || depth == 2 || depth == 4;
+    else if (ctype == 2 || ctype == 4 || ctype == 6) {
+        ok = depth == 8 || depth == 16;
+        samples = ctype == 2 ? 3 : ctype == 4 ? 2 : 4;
+    }
+    const uint32_t bits = kind ? samples * depth : 8;
+    rowBytes = ok ? ((uint32_t)W * bits + 7) / 8 : 0;
+    bpp = bits >= 8 ? bits / 8 : 1;
+    return ok;
+}
+
+// typedW != 0 (abub_png_decode_typed_dev): a frame's expected size follows from its kind, H x (row bytes + 1), and has to fit
+// rawStride; else every frame's is rawLen
 template <bool TWO>
 __global__ __launch_bounds__(TWO ? 128 : 64) void k_png_inflate(const uint8_t *__restrict__ zbuf, const abub_png_frame *__restrict__ frames,
                                                                   uint32_t rawLen, uint64_t rawStride, uint8_t *__restrict__ rawbuf,
-                                                                  int32_t *__restrict__ status, int dbg)
+                                                                  int32_t *__restrict__ status, int dbg, int typedW, int typedH)
 {
     __shared__ InflateLds L;
     const int f = blockIdx.x;
@@ -1109,6 +1137,17 @@ __global__ __launch_bounds__(TWO ? 128 : 64) void k_png_inflate(const uint8_t *_
     if (status[f] != 0) // (refused by the gather kernel; the same for the whole workgroup)
         return;
     const abub_png_frame fr = frames[f];
+    if (typedW) {
+        uint32_t rowBytes, bpp;
+        const bool known = png_kind_row(fr.kind, typedW, rowBytes, bpp);
+        const uint64_t len = (uint64_t)typedH * ((uint64_t)rowBytes + 1);
+        if (!known || len >= (1ull << 31) || ((len + 15) & ~15ull) + 16 > rawStride) { // (uniform: one descriptor per workgroup)
+            if (threadIdx.x == 0)
+                status[f] = ABUB_PNG_E_DESC;
+            return;
+        }
+        rawLen = (uint32_t)len;
+    }
     png_inflate_stream<TWO, false>(L, zbuf + fr.zoff, fr.zlen, rawbuf + (uint64_t)f * rawStride, rawLen, status + f, dbg);
 }
 
@@ -1253,7 +1292,8 @@ __device__ __forceinline__ int paeth(int a, int b, int c)
     return (pa <= pb && pa <= pc) ? a : (pb <= pc ? b : c);
 }
 
-template <int NDW>
+// TYPED (abub_png_decode_typed_dev): the frames of another kind than 0 are k_png_unfilter_typed's
+template <int NDW, bool TYPED>
 __global__ __launch_bounds__(64) void k_png_unfilter(const uint8_t *__restrict__ rawbuf, uint64_t rawStride,
                                                      const abub_png_frame *__restrict__ frames, const uint8_t *__restrict__ luts,
                                                      uint32_t nluts, int W, int H, uint8_t *__restrict__ out, uint64_t out_bytes,
@@ -1264,6 +1304,8 @@ __global__ __launch_bounds__(64) void k_png_unfilter(const uint8_t *__restrict__
     if (status[f] != 0)
         return;
     const abub_png_frame fr = frames[f];
+    if (TYPED && fr.kind != 0)
+        return;
     const bool pal = fr.lut != 0xffffffffu;
     if (fr.dst + (uint64_t)W * H > out_bytes || (fr.dst & 3) || (pal && fr.lut >= nluts)) {
         if (lane == 0)
@@ -1392,6 +1434,171 @@ __global__ __launch_bounds__(64) void k_png_unfilter(const uint8_t *__restrict__
         status[f] = ABUB_PNG_E_FILTER;
 }
 
+// ---- typed frames: unfilter at the kind's filter distance, then 8-bit grey as cv::imdecode(..., 0) gives it ---------------
+// One wave per frame, rows in order, three rows in LDS: the filtered row as it lies in the raw buffer, the unfiltered row
+// above and the unfiltered row being made.  A lane owns `chunk` whole units of a row (a unit is the filter distance: BPP
+// bytes, one pixel; below 8 bits per pixel one byte), so a filter's reach to the left never splits a unit between two lanes.
+// None and Up are dword-wise over the row.  Sub is a prefix sum per byte position of the unit: the lane's totals, a wave scan
+// of them, then the lane's bytes from its carry.  Average and Paeth are a serial recurrence along x: in round r every lane
+// from r on works its units from the last unit of the lane to its left as that stands; lane r's input is final in round r
+// (lane 0 has none), so after the rounds of all lanes that own units the row is final.  The only cross-lane traffic is LDS
+// inside the wave, in program order: nothing waits for anything.
+// The sums, averages and Paeth predictors of one row type over this lane's units [u0, u1); nobody writes in / prev meanwhile
+template <int BPP>
+__device__ __forceinline__ void png_unfilter_units(uint32_t ft, const uint8_t *__restrict__ in, const uint8_t *__restrict__ prev,
+                                                   uint8_t *cur, int u0, int u1, int nl, int lane)
+{
+    if (ft == 1) {
+        uint32_t tot[BPP], acc[BPP];
+#pragma unroll
+        for (int k = 0; k < BPP; ++k)
+            tot[k] = 0;
+        for (int u = u0; u < u1; ++u)
+#pragma unroll
+            for (int k = 0; k < BPP; ++k)
+                tot[k] += in[u * BPP + k];
+        // (a lane's total stays below 2^16, the wave's below 2^22)
+#pragma unroll
+        for (int k = 0; k < BPP; ++k)
+            acc[k] = wave_incl_scan(tot[k]) - tot[k];
+        for (int u = u0; u < u1; ++u)
+#pragma unroll
+            for (int k = 0; k < BPP; ++k) {
+                acc[k] += in[u * BPP + k];
+                cur[u * BPP + k] = (uint8_t)acc[k];
+            }
+        return;
+    }
+    const bool mine = u0 < u1, hasLeft = mine && u0 > 0;
+    int c0[BPP];
+#pragma unroll
+    for (int k = 0; k < BPP; ++k)
+        c0[k] = hasLeft ? (int)prev[(u0 - 1) * BPP + k] : 0;
+    for (int round = 0; round < nl; ++round) {
+        int a[BPP], c[BPP];
+#pragma unroll
+        for (int k = 0; k < BPP; ++k) {
+            a[k] = hasLeft ? (int)cur[(u0 - 1) * BPP + k] : 0;
+            c[k] = c0[k];
+        }
+        wave_sync(); // (every lane has read its left neighbour's unit of the last round before anybody writes this round's)
+        if (mine && lane >= round)
+            for (int u = u0; u < u1; ++u)
+#pragma unroll
+                for (int k = 0; k < BPP; ++k) {
+                    const int up = (int)prev[u * BPP + k];
+                    const int x = (int)in[u * BPP + k];
+                    const int pred = ft == 3 ? ((a[k] + up) >> 1) : paeth(a[k], up, c[k]);
+                    a[k] = (x + pred) & 255;
+                    c[k] = up;
+                    cur[u * BPP + k] = (uint8_t)a[k];
+                }
+        wave_sync();
+    }
+}
+
+// ldsRow: the launch's dynamic LDS holds three rows of ldsRow + 8 bytes (in dwords) and the 256-byte table
+__global__ __launch_bounds__(64) void k_png_unfilter_typed(const uint8_t *__restrict__ rawbuf, uint64_t rawStride,
+                                                           const abub_png_frame *__restrict__ frames, const uint8_t *__restrict__ luts,
+                                                           uint32_t nluts, int W, int H, uint8_t *__restrict__ out, uint64_t out_bytes,
+                                                           int32_t *__restrict__ status, uint32_t ldsRow)
+{
+    extern __shared__ uint32_t typed_lds[];
+    const int f = blockIdx.x, lane = threadIdx.x;
+    const abub_png_frame fr = frames[f];
+    if (fr.kind == 0 || status[f] != 0) // (kind 0: k_png_unfilter's frame)
+        return;
+    const uint32_t ctype = fr.kind & 255, depth = fr.kind >> 8;
+    uint32_t rowBytes, bpp;
+    const bool known = png_kind_row(fr.kind, W, rowBytes, bpp);
+    const bool pal = ctype == 3;
+    if (!known || rowBytes > ldsRow || (uint64_t)H * ((uint64_t)rowBytes + 1) + 16 > rawStride || (fr.dst & 3) || fr.dst > out_bytes ||
+        (uint64_t)W * H > out_bytes - fr.dst || (pal && fr.lut >= nluts)) { // (uniform: one descriptor per workgroup)
+        if (lane == 0)
+            status[f] = ABUB_PNG_E_DESC;
+        return;
+    }
+    const uint32_t rowDw = (ldsRow + 11) >> 2;
+    uint32_t *const in32 = typed_lds;
+    uint32_t *prev32 = typed_lds + rowDw, *cur32 = typed_lds + 2 * rowDw;
+    uint8_t *const lut = (uint8_t *)(typed_lds + 3 * rowDw);
+    for (uint32_t i = lane; i < 3 * rowDw; i += 64) // (the row above row 0 is zeros)
+        typed_lds[i] = 0;
+    if (pal)
+        for (int i = lane; i < 256; i += 64)
+            lut[i] = luts[(uint64_t)fr.lut * 256 + i];
+    wave_sync();
+    const uint8_t *raw = rawbuf + (uint64_t)f * rawStride; // 16-byte aligned; row y at y * (rowBytes + 1), its filter type first
+    uint8_t *dst = out + fr.dst;
+    const int nunits = (int)(rowBytes / bpp); // (rowBytes is a multiple of bpp: bpp > 1 only from 8 bits per sample on)
+    const int chunk = (nunits + 63) / 64;
+    const int nl = (nunits + chunk - 1) / chunk;
+    const int u0 = min(lane * chunk, nunits), u1 = min(u0 + chunk, nunits);
+    const uint32_t ndw = (rowBytes + 3) >> 2;
+    const uint32_t maxv = (1u << (depth < 8 ? depth : 8)) - 1, scale = 255u / maxv;
+    const uint32_t perLg = depth == 1 ? 3 : depth == 2 ? 2 : depth == 4 ? 1 : 0, per = 1u << perLg; // pixels per byte below 8 bits
+    const uint32_t k16 = depth / 8; // RGB: bytes from one sample's (high) byte to the next's
+    int bad = 0;
+    for (int y = 0; y < H; ++y) {
+        const uint64_t rb = (uint64_t)y * ((uint64_t)rowBytes + 1);
+        const uint32_t ft = rfl((uint32_t)raw[rb]);
+        const uint32_t mis = (uint32_t)((rb + 1) & 3);
+        // the dwords that hold the row's bytes (up to 3 bytes of the next row or of the padding behind the last one ride along)
+        const uint32_t *src = (const uint32_t *)(raw + ((rb + 1) & ~3ull));
+        for (uint32_t i = lane; i < (mis + rowBytes + 3) >> 2; i += 64)
+            in32[i] = src[i];
+        wave_sync();
+        if (ft == 0 || ft == 2) {
+            for (uint32_t i = lane; i < ndw; i += 64) {
+                const uint32_t v = mis ? __builtin_amdgcn_alignbyte(in32[i + 1], in32[i], mis) : in32[i];
+                cur32[i] = ft == 2 ? add4(v, prev32[i]) : v;
+            }
+        } else if (ft == 1 || ft == 3 || ft == 4) {
+            const uint8_t *in = (const uint8_t *)in32 + mis;
+            const uint8_t *prev = (const uint8_t *)prev32;
+            uint8_t *cur = (uint8_t *)cur32;
+            switch (bpp) {
+            case 1: png_unfilter_units<1>(ft, in, prev, cur, u0, u1, nl, lane); break;
+            case 2: png_unfilter_units<2>(ft, in, prev, cur, u0, u1, nl, lane); break;
+            case 3: png_unfilter_units<3>(ft, in, prev, cur, u0, u1, nl, lane); break;
+            case 4: png_unfilter_units<4>(ft, in, prev, cur, u0, u1, nl, lane); break;
+            case 6: png_unfilter_units<6>(ft, in, prev, cur, u0, u1, nl, lane); break;
+            default: png_unfilter_units<8>(ft, in, prev, cur, u0, u1, nl, lane); break;
+            }
+        } else {
+            bad = 1;
+            break;
+        }
+        wave_sync();
+        // the finished row -> W grey bytes, four pixels per lane and store
+        const uint8_t *row = (const uint8_t *)cur32;
+        uint32_t *drow = (uint32_t *)(dst + (uint64_t)y * W);
+        for (int x4 = lane; x4 < W / 4; x4 += 64) {
+            uint32_t v = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const uint32_t x = 4 * (uint32_t)x4 + j;
+                uint32_t g;
+                if (depth < 8) { // MSB first within a byte; the padding bits of the last byte belong to no pixel
+                    const uint32_t s = (row[x >> perLg] >> ((per - 1 - (x & (per - 1))) * depth)) & maxv;
+                    g = pal ? (uint32_t)lut[s] : s * scale;
+                } else if (ctype == 0 || ctype == 4)
+                    g = row[x * bpp];
+                else
+                    g = ((uint32_t)row[x * bpp] * 9797 + (uint32_t)row[x * bpp + k16] * 19234 + (uint32_t)row[x * bpp + 2 * k16] * 3737 + 16384) >> 15;
+                v |= g << (8 * j);
+            }
+            drow[x4] = v;
+        }
+        wave_sync(); // (the row has been read: the next one may overwrite the row above it)
+        uint32_t *t = prev32;
+        prev32 = cur32;
+        cur32 = t;
+    }
+    if (bad && lane == 0)
+        status[f] = ABUB_PNG_E_FILTER;
+}
+
 } // namespace
 
 extern "C" size_t abub_png_raw_stride(int W, int H)
@@ -1401,36 +1608,58 @@ extern "C" size_t abub_png_raw_stride(int W, int H)
     return (((size_t)H * ((size_t)W + 1) + 15) & ~(size_t)15) + 16;
 }
 
-extern "C" int abub_png_decode_dev(const uint8_t *files, size_t files_bytes, const abub_png_frame *frames, int nframes,
-                                   const abub_png_seg *segs, int nsegs, const uint8_t *luts, int nluts, int W, int H,
-                                   uint8_t *zbuf, size_t zbuf_bytes, uint8_t *rawbuf, size_t rawbuf_bytes, uint8_t *out,
-                                   size_t out_bytes, int32_t *status, void *stream)
+extern "C" size_t abub_png_raw_stride_kind(int W, int H, uint32_t kind)
 {
+    uint32_t rowBytes, bpp;
+    if (W <= 0 || H <= 0 || !png_kind_row(kind, W, rowBytes, bpp))
+        return 0;
+    return (((size_t)H * ((size_t)rowBytes + 1) + 15) & ~(size_t)15) + 16;
+}
+
+// Both entries.  typed = false: every frame is an 8-bit one whatever its descriptor's kind says, `stride` is
+// abub_png_raw_stride(W, H): the launches of abub_png_decode_dev as they always were.  typed = true: the inflate sizes every
+// frame by its kind, k_png_unfilter leaves the frames of another kind than 0 to k_png_unfilter_typed.
+static int png_decode_launch(bool typed, const uint8_t *files, size_t files_bytes, const abub_png_frame *frames, int nframes,
+                             const abub_png_seg *segs, int nsegs, const uint8_t *luts, int nluts, int W, int H, uint8_t *zbuf,
+                             size_t zbuf_bytes, uint8_t *rawbuf, size_t rawbuf_bytes, size_t stride, uint8_t *out, size_t out_bytes,
+                             int32_t *status, void *stream)
+{
+    const std::string who = typed ? "abub_png_decode_typed_dev" : "abub_png_decode_dev";
     if (nframes == 0)
         return ABUB_OK;
     if (!files || !frames || !zbuf || !rawbuf || !out || !status || nframes < 0 || nsegs < 0 || nluts < 0 || (nsegs && !segs) ||
         (nluts && !luts))
-        return set_err(ABUB_E_INVALID, "abub_png_decode_dev: null pointer or negative count");
+        return set_err(ABUB_E_INVALID, (who + ": null pointer or negative count").c_str());
     if (W < 4 || (W & 3) || W > 2048 || H < 1 || (size_t)H * ((size_t)W + 1) >= ((size_t)1 << 31))
-        return set_err(ABUB_E_INVALID, "abub_png_decode_dev: width must be a multiple of 4 in [4, 2048]");
+        return set_err(ABUB_E_INVALID, (who + ": width must be a multiple of 4 in [4, 2048]").c_str());
     if (((uintptr_t)files & 3) || ((uintptr_t)zbuf & 15) || ((uintptr_t)rawbuf & 15) || ((uintptr_t)out & 3))
-        return set_err(ABUB_E_INVALID, "abub_png_decode_dev: files / out 4-byte, zbuf / rawbuf 16-byte aligned");
-    const size_t stride = abub_png_raw_stride(W, H);
-    if ((size_t)nframes * stride > rawbuf_bytes)
-        return set_err(ABUB_E_INVALID, "abub_png_decode_dev: rawbuf smaller than nframes * abub_png_raw_stride(W, H)");
+        return set_err(ABUB_E_INVALID, (who + ": files / out 4-byte, zbuf / rawbuf 16-byte aligned").c_str());
+    if (typed && (stride < 32 || (stride & 15)))
+        return set_err(ABUB_E_INVALID, (who + ": raw_stride must be a multiple of 16, 32 at least").c_str());
+    if (stride > rawbuf_bytes / (size_t)nframes)
+        return set_err(ABUB_E_INVALID, (who + (typed ? ": rawbuf smaller than nframes * raw_stride"
+                                                     : ": rawbuf smaller than nframes * abub_png_raw_stride(W, H)")).c_str());
     hipStream_t st = (hipStream_t)stream;
     k_png_gather<<<nframes, 256, 0, st>>>(files, (uint64_t)files_bytes, frames, segs, (uint32_t)nsegs, zbuf, (uint64_t)zbuf_bytes, status);
     // ABUB_PNG_WAVES=1: one wave parses and writes a stream; default: a parsing and a writing wave per stream
     static const bool oneWave = [] { const char *e = getenv("ABUB_PNG_WAVES"); return e && atoi(e) == 1; }();
     static const int dbg = [] { const char *e = getenv("ABUB_PNG_DEBUG"); return e ? atoi(e) : 0; }(); // (measurement only)
+    const uint32_t rawLen = (uint32_t)((size_t)H * ((size_t)W + 1));
+    const int typedW = typed ? W : 0, typedH = typed ? H : 0;
     if ((oneWave || dbg) && dbg != 5)
-        k_png_inflate<false><<<nframes, 64, 0, st>>>(zbuf, frames, (uint32_t)((size_t)H * ((size_t)W + 1)), (uint64_t)stride, rawbuf, status, dbg);
+        k_png_inflate<false><<<nframes, 64, 0, st>>>(zbuf, frames, rawLen, (uint64_t)stride, rawbuf, status, dbg, typedW, typedH);
     else
-        k_png_inflate<true><<<nframes, 128, 0, st>>>(zbuf, frames, (uint32_t)((size_t)H * ((size_t)W + 1)), (uint64_t)stride, rawbuf, status, dbg);
+        k_png_inflate<true><<<nframes, 128, 0, st>>>(zbuf, frames, rawLen, (uint64_t)stride, rawbuf, status, dbg, typedW, typedH);
     const int ndw = (W + 255) / 256;
 #define UNF(N)                                                                                                             \
-    k_png_unfilter<N><<<nframes, 64, 0, st>>>(rawbuf, (uint64_t)stride, frames, luts, (uint32_t)nluts, W, H, out,         \
-                                              (uint64_t)out_bytes, status)
+    do {                                                                                                                   \
+        if (typed)                                                                                                         \
+            k_png_unfilter<N, true><<<nframes, 64, 0, st>>>(rawbuf, (uint64_t)stride, frames, luts, (uint32_t)nluts, W, H, \
+                                                            out, (uint64_t)out_bytes, status);                             \
+        else                                                                                                               \
+            k_png_unfilter<N, false><<<nframes, 64, 0, st>>>(rawbuf, (uint64_t)stride, frames, luts, (uint32_t)nluts, W,   \
+                                                             H, out, (uint64_t)out_bytes, status);                         \
+    } while (0)
     switch (ndw) {
     case 1: UNF(1); break;
     case 2: UNF(2); break;
@@ -1442,8 +1671,34 @@ extern "C" int abub_png_decode_dev(const uint8_t *files, size_t files_bytes, con
     default: UNF(8); break;
     }
 #undef UNF
+    if (typed) {
+        // the widest row a frame of this launch can have: the widest kind's (8 bytes per pixel), and what fits raw_stride
+        const size_t fits = (stride - 16) / (size_t)H;
+        const uint32_t ldsRow = (uint32_t)std::min<size_t>((size_t)8 * W, fits ? fits - 1 : 0);
+        const size_t lds = (size_t)3 * ((ldsRow + 11) >> 2) * 4 + 256; // <= 49,432 bytes (W = 2048)
+        k_png_unfilter_typed<<<nframes, 64, lds, st>>>(rawbuf, (uint64_t)stride, frames, luts, (uint32_t)nluts, W, H, out,
+                                                       (uint64_t)out_bytes, status, ldsRow);
+    }
     HIPCHK(hipGetLastError());
     return ABUB_OK;
+}
+
+extern "C" int abub_png_decode_dev(const uint8_t *files, size_t files_bytes, const abub_png_frame *frames, int nframes,
+                                   const abub_png_seg *segs, int nsegs, const uint8_t *luts, int nluts, int W, int H,
+                                   uint8_t *zbuf, size_t zbuf_bytes, uint8_t *rawbuf, size_t rawbuf_bytes, uint8_t *out,
+                                   size_t out_bytes, int32_t *status, void *stream)
+{
+    return png_decode_launch(false, files, files_bytes, frames, nframes, segs, nsegs, luts, nluts, W, H, zbuf, zbuf_bytes, rawbuf,
+                             rawbuf_bytes, abub_png_raw_stride(W, H), out, out_bytes, status, stream);
+}
+
+extern "C" int abub_png_decode_typed_dev(const uint8_t *files, size_t files_bytes, const abub_png_frame *frames, int nframes,
+                                         const abub_png_seg *segs, int nsegs, const uint8_t *luts, int nluts, int W, int H,
+                                         uint8_t *zbuf, size_t zbuf_bytes, uint8_t *rawbuf, size_t rawbuf_bytes, size_t raw_stride,
+                                         uint8_t *out, size_t out_bytes, int32_t *status, void *stream)
+{
+    return png_decode_launch(true, files, files_bytes, frames, nframes, segs, nsegs, luts, nluts, W, H, zbuf, zbuf_bytes, rawbuf,
+                             rawbuf_bytes, raw_stride, out, out_bytes, status, stream);
 }
 
 extern "C" int abub_unzip_dev(const uint8_t *comp, size_t comp_bytes, const abub_zip_entry *entries, int nentries, uint8_t *out,

@@ -298,10 +298,23 @@ def trigger_search(stacks, W, H, sig_main=True):
 
 
 # ---- PNG frames decoded on the GPU (abub_png_decode_dev) --------------------------------------------------------
-def png_parse(data, W, H):
+PNG_SAMPLES = {0: 1, 2: 3, 3: 1, 4: 2, 6: 4}
+
+
+def png_kind(ctype, depth):
+    """abub_png_frame.kind of a PNG's colour type and bit depth: 0 for the two 8-bit kinds of abub_png_decode_dev, colour
+    type | depth << 8 for the 13 typed kinds of abub_png_decode_typed_dev, None for what no decoder here reads."""
+    if depth == 8 and ctype in (0, 3):
+        return 0
+    ok = {0: (1, 2, 4, 16), 3: (1, 2, 4), 2: (8, 16), 4: (8, 16), 6: (8, 16)}
+    return ctype | depth << 8 if depth in ok.get(ctype, ()) else None
+
+
+def png_parse(data, W, H, types=False):
     """What the host does per file before the upload: walk the chunks of a PNG, -> (idat segments [(offset, length)],
     palette->grey table (bytes, 256) or None) for an 8-bit grey / 8-bit palette image of W x H without interlace, or None
-    for anything the GPU path does not take (the caller decodes such a file on the host)."""
+    for anything the GPU path does not take (the caller decodes such a file on the host).  types=True: the typed walk
+    (host.png_walk_typed restated) -> (segments, table or None, kind) for every non-interlaced type the host decoder reads."""
     import struct
     if len(data) < 33 or data[:8] != b"\x89PNG\r\n\x1a\n":
         return None
@@ -320,40 +333,57 @@ def png_parse(data, W, H):
         elif typ == b"IEND":
             end = True
         o += 12 + ln
-    if hdr is None or not segs or hdr[0] != W or hdr[1] != H or hdr[2] != 8 or hdr[3] not in (0, 3) or hdr[6] != 0:
+    if hdr is None or not segs or hdr[0] != W or hdr[1] != H or hdr[6] != 0:
+        return None
+    kind = png_kind(hdr[3], hdr[2])
+    if kind is None or (kind != 0 and not types):
+        return None
+    if kind and H * ((W * PNG_SAMPLES[hdr[3]] * hdr[2] + 7) // 8 + 1) >= 1 << 31:
         return None
     lut = None
     if hdr[3] == 3:
         n = min(len(pal or b"") // 3, 256)
         lut = bytes(((pal[3 * i] * 9797 + pal[3 * i + 1] * 19234 + pal[3 * i + 2] * 3737 + 16384) >> 15) & 255 if i < n else 0
                     for i in range(256))
-    return segs, lut
+    return (segs, lut, kind) if types else (segs, lut)
 
 
-def png_decode(files, W, H, device="cuda:0"):
+def png_decode(files, W, H, device="cuda:0", types=False, kinds=None, dsts=None, out=None, out_bytes=None):
     """files: list of bytes objects (PNG files) -> (frames u8 [n, H, W] on the device, status i32 [n] on the host).  A file
-    png_parse() refuses gets status -1 and a frame left untouched (zeros)."""
+    png_parse() refuses gets status -1 and a frame left untouched (zeros).  types=True: the typed walk and
+    abub_png_decode_typed_dev, the raw stride that of the widest kind among the files.  For tests of the descriptor checks
+    (types=True): kinds[i] / dsts[i], where not None, replace the kind the walk found / the frame's byte offset in `out`;
+    out: a u8 device tensor to decode into instead of a new one (returned as it is), out_bytes: how many of its bytes the
+    kernels are told of (what lies behind them must stay as it is)."""
     import numpy as np
     n = len(files)
     frames_np = np.zeros((max(n, 1), 8), dtype=np.uint32)
     segs, luts, blob, zoff = [], [], bytearray(), 0
     status_pre = np.zeros(n, dtype=np.int32)
     P = W * H
+    L = _lib.lib()
+    stride = int(L.abub_png_raw_stride(W, H))
     for i, data in enumerate(files):
-        parsed = png_parse(data, W, H)
+        parsed = png_parse(data, W, H, types)
         base = len(blob)
+        dst = i * P if dsts is None or dsts[i] is None else int(dsts[i])
         if parsed is None:
             status_pre[i] = -1
             frames_np[i] = (len(segs), 0, zoff, 0, 0xFFFFFFFF, 0, (i * P) & 0xFFFFFFFF, (i * P) >> 32)
             zoff += 16
             continue
-        sg, lut = parsed
+        sg, lut = parsed[:2]
+        kind = parsed[2] if types else 0
+        if types and kinds is not None and kinds[i] is not None:
+            kind = int(kinds[i])
+        if types:
+            stride = max(stride, int(L.abub_png_raw_stride_kind(W, H, kind)))
         zlen = sum(l for _, l in sg)
         li = 0xFFFFFFFF
         if lut is not None:
             li = len(luts)
             luts.append(lut)
-        frames_np[i] = (len(segs), len(sg), zoff, zlen, li, 0, (i * P) & 0xFFFFFFFF, (i * P) >> 32)
+        frames_np[i] = (len(segs), len(sg), zoff, zlen, li, kind, dst & 0xFFFFFFFF, dst >> 32)
         segs += [(base + o, l) for o, l in sg]
         blob += data
         blob += b"\0" * ((-len(blob)) % 4)
@@ -364,17 +394,27 @@ def png_decode(files, W, H, device="cuda:0"):
     d_frames = torch.from_numpy(frames_np.view(np.int32).copy()).to(dev)
     d_segs = torch.tensor(segs if segs else [(0, 0)], dtype=torch.int64).to(torch.int32).to(dev) if True else None
     d_luts = torch.frombuffer(bytearray(b"".join(luts) if luts else bytes(256)), dtype=torch.uint8).to(dev)
-    stride = int(_lib.lib().abub_png_raw_stride(W, H))
     d_z = torch.empty((max(zoff, 16),), dtype=torch.uint8, device=dev)
     d_raw = torch.empty((max(n, 1) * stride,), dtype=torch.uint8, device=dev)
-    out = torch.zeros((max(n, 1), H, W), dtype=torch.uint8, device=dev)
+    given = out is not None
+    if given:
+        _need_cuda(out)
+    else:
+        out = torch.zeros((max(n, 1), H, W), dtype=torch.uint8, device=dev)
     status = torch.full((max(n, 1),), 99, dtype=torch.int32, device=dev)
-    _lib.check(_lib.lib().abub_png_decode_dev(_ptr(d_files), d_files.numel(), _ptr(d_frames), n, _ptr(d_segs), len(segs),
-                                              _ptr(d_luts), len(luts), W, H, _ptr(d_z), d_z.numel(), _ptr(d_raw), d_raw.numel(),
-                                              _ptr(out), out.numel(), _ptr(status), _stream()), "abub_png_decode_dev")
+    nout = out.numel() if out_bytes is None else min(int(out_bytes), out.numel())
+    if types:
+        _lib.check(L.abub_png_decode_typed_dev(_ptr(d_files), d_files.numel(), _ptr(d_frames), n, _ptr(d_segs), len(segs),
+                                               _ptr(d_luts), len(luts), W, H, _ptr(d_z), d_z.numel(), _ptr(d_raw), d_raw.numel(),
+                                               stride, _ptr(out), nout, _ptr(status), _stream()),
+                   "abub_png_decode_typed_dev")
+    else:
+        _lib.check(L.abub_png_decode_dev(_ptr(d_files), d_files.numel(), _ptr(d_frames), n, _ptr(d_segs), len(segs),
+                                         _ptr(d_luts), len(luts), W, H, _ptr(d_z), d_z.numel(), _ptr(d_raw), d_raw.numel(),
+                                         _ptr(out), nout, _ptr(status), _stream()), "abub_png_decode_dev")
     st = status.cpu().numpy()[:n].copy()
     st[status_pre != 0] = -1
-    return out[:n], st
+    return (out if given else out[:n]), st
 
 
 def abf_decode(files, descs, W, H, out, status=None):

@@ -58,6 +58,7 @@ SIGNATURES = {
     "abh_run_verify_dev": (_i, [_vp, _vp, _i, _i, _i, _dp, C.c_char_p, _i]),
     "abh_run_verify_report": (_s, [_vp]),
     "abh_png_walk": (_i, [_u8p, _i, _i, _i, _u32p, _i, _ip, _ip, _u8p]),
+    "abh_png_walk_typed": (_i, [_u8p, _i, _i, _i, _u32p, _i, _ip, _ip, _u8p, _u32p]),
     "abh_bmp_walk": (_i, [_u8p, _i, _i, _i, _u32p, _u8p]),
     "abh_imwrite": (_i, [_s, _u8p, _i, _i]),
     "abh_write_header": (None, [_s, _s, _i, _i]),
@@ -442,6 +443,22 @@ def png_walk(data, W, H, cap=4096):
     if not L.abh_png_walk(src.ctypes.data_as(_u8p), len(src), W, H, segs, cap, C.byref(n), C.byref(pal), lut.ctypes.data_as(_u8p)):
         return None
     return [(segs[2 * i], segs[2 * i + 1]) for i in range(min(n.value, cap))], (lut.tobytes() if pal.value else None)
+
+
+def png_walk_typed(data, W, H, cap=4096):
+    """pngWalk with typed = true (what ABUB_GPU_PNG_TYPES=1 sends to the GPU decoder): None for a file it does not take, else
+    (IDAT segments, palette -> grey table (bytes) or None, kind) with kind = 0 for an 8-bit grey / palette file, else
+    colour type | bit depth << 8 (abub_png_frame.kind)"""
+    L = lib()
+    src = np.frombuffer(data, np.uint8)
+    segs = (C.c_uint32 * (2 * cap))()
+    n, pal, kind = C.c_int(), C.c_int(), C.c_uint32()
+    lut = np.zeros(256, np.uint8)
+    if not L.abh_png_walk_typed(src.ctypes.data_as(_u8p), len(src), W, H, segs, cap, C.byref(n), C.byref(pal),
+                                lut.ctypes.data_as(_u8p), C.byref(kind)):
+        return None
+    return ([(segs[2 * i], segs[2 * i + 1]) for i in range(min(n.value, cap))], (lut.tobytes() if pal.value else None),
+            int(kind.value))
 
 
 def bmp_walk(data, W, H):

@@ -81,7 +81,10 @@ static std::string usage()
            "             are the same\n"
            "             ABUB_GPU_BMP=1 decodes BMP frames on the GPU in every device reading route (the batched run, training on the\n"
            "             GPU, --repack-gpu, --unpack-gpu, --verify-gpu); ABUB_GPU_BMP=0, the default, leaves them to host threads;\n"
-           "             results are the same\n";
+           "             results are the same\n"
+           "             ABUB_GPU_PNG_TYPES=1 also decodes 16-bit, RGB(A), grey+alpha and 1/2/4-bit PNG frames on the GPU in those\n"
+           "             routes (interlaced files stay with the host); unset or 0, the default, leaves them to host threads; results\n"
+           "             are the same\n";
 }
 
 // cores this process may use: the affinity mask (taskset, cpuset) AND the cgroup's CPU quota (cpu.max: a container may see

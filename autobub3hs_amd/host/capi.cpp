@@ -379,6 +379,26 @@ int abh_png_walk(const uint8_t *data, int n, int W, int H, uint32_t *segs_out, i
     return 1;
 }
 
+// pngWalk with typed = true (ABUB_GPU_PNG_TYPES=1): also the other PNG types the host decoder reads; *kind = 0 for an 8-bit
+// grey / palette file, else colour type | bit depth << 8; the table also for a palette below 8 bits
+int abh_png_walk_typed(const uint8_t *data, int n, int W, int H, uint32_t *segs_out, int cap, int *nsegs, int *palette, uint8_t *lut_out,
+                       uint32_t *kind)
+{
+    abub::PngInfo info;
+    if (!abub::pngWalk(data, (size_t)n, W, H, info, true))
+        return 0;
+    *nsegs = (int)info.segs.size();
+    for (int i = 0; i < (int)info.segs.size() && i < cap; ++i) {
+        segs_out[2 * i] = info.segs[i].off;
+        segs_out[2 * i + 1] = info.segs[i].len;
+    }
+    *palette = info.palette ? 1 : 0;
+    if (info.palette)
+        std::memcpy(lut_out, info.lut, 256);
+    *kind = info.kind;
+    return 1;
+}
+
 int abh_imwrite(const char *path, const uint8_t *img, int W, int H)
 {
     cv::Mat m(H, W, CV_8U);

@@ -3,7 +3,8 @@
 // routes of repack, unpack and verify.  A host thread reads each file; a packed frame ("ABF1") whose header is valid for
 // W x H goes to the packed decoder as it is, a PNG has its chunks walked (pngWalk), a BMP its header (bmpWalk, with
 // ABUB_GPU_BMP=1; by default BMP files stay with the reading thread); a file none of them takes
-// (16-bit, colour or interlaced PNG, compressed BMP, another size) gets the host decoder's answer at once, and so does a
+// (16-bit, colour or interlaced PNG -- with ABUB_GPU_PNG_TYPES=1 only the interlaced ones --, compressed BMP, another size)
+// gets the host decoder's answer at once, and so does a
 // frame a kernel later returns a nonzero status for.  Each decoder is one lane (GpuCodec) of a batch: the placement of its
 // frames, its descriptors, its status buffers and its count are indexed by it, and launch and finish loop over the lanes.
 // FileBatch is the unit "one set of files on the device, decoded into one slab" of device training, repack, unpack and
@@ -194,12 +195,21 @@ inline bool gpuBmpEnabled()
     return e && atoi(e) != 0;
 }
 
+// ABUB_GPU_PNG_TYPES=1: the PNG lane also takes 16-bit, colour, grey+alpha and sub-byte files (every non-interlaced type
+// the host decoder reads; abub_png_decode_typed_dev).  Off by default: such files stay with the reading threads (DESIGN
+// section 3, "PNG types on the GPU").
+inline bool gpuPngTypesEnabled()
+{
+    const char *e = getenv("ABUB_GPU_PNG_TYPES");
+    return e && atoi(e) != 0;
+}
+
 // Does a GPU decoder take the W x H file?  Which one, and what its walk found, into t
 inline bool gpuCodecOf(const uint8_t *data, size_t size, int W, int H, FileTask &t)
 {
     if (packedFrameOf(data, size, W, H)) // (the file goes up as it is; the kernel checks the rest)
         t.codec = GpuPacked;
-    else if (pngWalk(data, size, W, H, t.info))
+    else if (pngWalk(data, size, W, H, t.info, gpuPngTypesEnabled()))
         t.codec = GpuPng;
     else if (gpuBmpEnabled() && bmpWalk(data, size, W, H, t.bmp))
         t.codec = GpuBmp;
@@ -399,7 +409,7 @@ void buildFileDescs(FileTask *first, FileTask *last, size_t totalFileBytes, File
             d.zoff = (uint32_t)zoff;
             d.zlen = (uint32_t)t.info.zlen;
             d.lut = t.info.palette ? r.intern(GpuPng, t.info.lut) : 0xffffffffu;
-            d.reserved = 0;
+            d.kind = t.info.kind;
             d.dst = at.dst;
             for (const abub_png_seg &sg : t.info.segs)
                 r.segs.push_back(abub_png_seg{(uint32_t)(t.off + sg.off), sg.len});
@@ -447,14 +457,29 @@ inline void launchFileDecode(const FileDescs &r, const uint8_t *d_files, int W, 
             HIPOK(hipMemcpyAsync(l.luts.get(), luts.data(), luts.size(), hipMemcpyHostToDevice, stream));
         int32_t *status = (int32_t *)l.status.get();
         if (c == GpuPng) {
+            // typed frames (ABUB_GPU_PNG_TYPES=1) among them: every frame gets the raw bytes of the widest kind present
+            bool typed = false;
+            size_t stride = abub_png_raw_stride(W, H);
+            for (const abub_png_frame &d : r.png)
+                if (d.kind) {
+                    typed = true;
+                    stride = std::max(stride, abub_png_raw_stride_kind(W, H, d.kind));
+                }
             sc.z.grow(r.zbytes);
-            sc.raw.grow((size_t)nf * abub_png_raw_stride(W, H));
+            sc.raw.grow((size_t)nf * stride);
             sc.segs.grow(r.segs.size() * sizeof(abub_png_seg) + 8);
             HIPOK(hipMemcpyAsync(sc.segs.get(), r.segs.data(), r.segs.size() * sizeof(abub_png_seg), hipMemcpyHostToDevice, stream));
-            check(abub_png_decode_dev(d_files, r.bytes, (const abub_png_frame *)l.desc.get(), nf, (const abub_png_seg *)sc.segs.get(),
-                                      (int)r.segs.size(), l.luts.get(), (int)(luts.size() / 256), W, H, sc.z.get(), sc.z.capacity(),
-                                      sc.raw.get(), sc.raw.capacity(), out, out_bytes, status, stream),
-                  "abub_png_decode_dev");
+            if (typed)
+                check(abub_png_decode_typed_dev(d_files, r.bytes, (const abub_png_frame *)l.desc.get(), nf,
+                                                (const abub_png_seg *)sc.segs.get(), (int)r.segs.size(), l.luts.get(),
+                                                (int)(luts.size() / 256), W, H, sc.z.get(), sc.z.capacity(), sc.raw.get(),
+                                                sc.raw.capacity(), stride, out, out_bytes, status, stream),
+                      "abub_png_decode_typed_dev");
+            else
+                check(abub_png_decode_dev(d_files, r.bytes, (const abub_png_frame *)l.desc.get(), nf, (const abub_png_seg *)sc.segs.get(),
+                                          (int)r.segs.size(), l.luts.get(), (int)(luts.size() / 256), W, H, sc.z.get(), sc.z.capacity(),
+                                          sc.raw.get(), sc.raw.capacity(), out, out_bytes, status, stream),
+                      "abub_png_decode_dev");
         } else if (c == GpuPacked)
             check(abub_abf_decode_dev(d_files, r.bytes, (const abub_abf_frame *)l.desc.get(), nf, W, H, out, out_bytes, status, stream),
                   "abub_abf_decode_dev");

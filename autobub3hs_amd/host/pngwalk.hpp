@@ -15,13 +15,17 @@ namespace abub {
 // What a host thread finds out about a PNG file before its bytes go to the GPU decoder: the IDAT chunks and, for a
 // palette image, the palette -> grey table (the same rounding as cv::imdecode's, cvlite.cpp).  false = not an 8-bit grey
 // or palette image of W x H without interlace (or not a PNG at all): such a file is decoded on the host.
+// typed (ABUB_GPU_PNG_TYPES=1, abub_png_decode_typed_dev): every non-interlaced W x H file the host decoder reads (cvlite.cpp,
+// decodePNGTo) is accepted -- grey at 1, 2, 4, 8, 16 bits, palette at 1, 2, 4, 8, grey+alpha, RGB and RGBA at 8 and 16 -- and
+// `kind` says which: 0 for the two 8-bit ones, else colour type | bit depth << 8 (abub_png_frame.kind).
 struct PngInfo {
     std::vector<abub_png_seg> segs; // offsets relative to the file's first byte
     bool palette = false;
-    uint8_t lut[256];
+    uint8_t lut[256];               // palette images: entries past the palette are 0, as the host decoder has them
     uint64_t zlen = 0;
+    uint32_t kind = 0;
 };
-inline bool pngWalk(const uint8_t *buf, size_t size, int W, int H, PngInfo &out)
+inline bool pngWalk(const uint8_t *buf, size_t size, int W, int H, PngInfo &out, bool typed = false)
 {
     static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
     if (size < 8 + 25 || memcmp(buf, sig, 8) != 0)
@@ -30,6 +34,7 @@ inline bool pngWalk(const uint8_t *buf, size_t size, int W, int H, PngInfo &out)
     out.segs.clear();
     out.palette = false;
     out.zlen = 0;
+    out.kind = 0;
     uint8_t pal[256][3];
     int npal = 0;
     bool haveHdr = false, end = false;
@@ -57,9 +62,19 @@ inline bool pngWalk(const uint8_t *buf, size_t size, int W, int H, PngInfo &out)
             end = true;
         o += 12 + (size_t)len;
     }
-    if (!haveHdr || (int)w != W || (int)h != H || depth != 8 || (ctype != 0 && ctype != 3) || interlace != 0 || out.segs.empty() ||
-        out.zlen >= ((uint64_t)1 << 28) || size >= ((size_t)1 << 31))
+    if (!haveHdr || (int)w != W || (int)h != H || interlace != 0 || out.segs.empty() || out.zlen >= ((uint64_t)1 << 28) ||
+        size >= ((size_t)1 << 31))
         return false;
+    if (depth != 8 || (ctype != 0 && ctype != 3)) {
+        // the combinations of decodePNGTo, and the size of the inflated scanlines inside the kernels' 32-bit arithmetic
+        const bool low = depth == 1 || depth == 2 || depth == 4;
+        const bool known = ctype == 0 ? (low || depth == 16) : ctype == 3 ? low : (ctype == 2 || ctype == 4 || ctype == 6) && (depth == 8 || depth == 16);
+        const uint64_t samples = ctype == 2 ? 3 : ctype == 4 ? 2 : ctype == 6 ? 4 : 1;
+        const uint64_t rowBytes = ((uint64_t)w * samples * depth + 7) / 8;
+        if (!typed || !known || (uint64_t)h * (rowBytes + 1) >= ((uint64_t)1 << 31))
+            return false;
+        out.kind = ctype | (depth << 8);
+    }
     if (ctype == 3) {
         out.palette = true;
         for (int v = 0; v < 256; ++v)

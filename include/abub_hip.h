@@ -490,7 +490,8 @@ int abub_ctx_fetch_image(abub_ctx *ctx, uint8_t *out);
  * frame: where its IDAT chunks lie, where its zlib stream may be assembled, where the decoded frame goes.  Handles
  * 8-bit grey and 8-bit palette images without interlace, any filter type, any deflate block type; a frame the kernels
  * refuse gets a positive status (below) and is left as it is -- the caller decodes such a frame on the host.
- * All pointers are device pointers; nothing here reads host memory. */
+ * abub_png_decode_typed_dev also takes the other non-interlaced PNG types (abub_png_frame.kind) and gives their 8-bit grey
+ * value as cv::imdecode(..., 0) does.  All pointers are device pointers; nothing here reads host memory. */
 typedef struct abub_png_seg {
     uint32_t off; /* byte offset of an IDAT chunk's DATA in `files` */
     uint32_t len; /* its length */
@@ -503,7 +504,10 @@ typedef struct abub_png_frame {
     uint32_t zlen;      /* sum of the segment lengths */
     uint32_t lut;       /* palette images: index of the frame's 256-byte palette-index -> grey table in `luts`;
                            0xffffffff for grey images */
-    uint32_t reserved;
+    uint32_t kind;      /* 0: an 8-bit image, grey or palette by `lut` (abub_png_decode_dev reads nothing else here).
+                           abub_png_decode_typed_dev: colour type | bit depth << 8 of one of the 13 typed kinds --
+                           grey (0) at 1, 2, 4, 16 bits, palette (3) at 1, 2, 4 (`lut`: the table, its entries past the
+                           palette 0), grey+alpha (4), RGB (2) and RGBA (6) at 8 and 16; `lut` is ignored elsewhere */
     uint64_t dst;       /* byte offset of the decoded W*H frame from `out` (a multiple of 4) */
 } abub_png_frame;
 /* status[frame] after abub_png_decode_dev: 0 = decoded */
@@ -517,7 +521,7 @@ typedef struct abub_png_frame {
 #define ABUB_PNG_E_NOEOB 8      /* no end-of-block code */
 #define ABUB_PNG_E_CODE 9       /* invalid literal/length or distance code in the data */
 #define ABUB_PNG_E_DISTANCE 10  /* distance reaches before the start of the output */
-#define ABUB_PNG_E_TOOMUCH 11   /* more than H*(W+1) bytes */
+#define ABUB_PNG_E_TOOMUCH 11   /* more than H*(W+1) bytes (a typed frame: more than H*(its row bytes + 1)) */
 #define ABUB_PNG_E_TOOLITTLE 12 /* fewer */
 #define ABUB_PNG_E_ADLER 13     /* Adler-32 of the output differs from the trailer */
 #define ABUB_PNG_E_FILTER 14    /* filter type above 4 */
@@ -531,6 +535,18 @@ int abub_png_decode_dev(const uint8_t *files, size_t files_bytes, const abub_png
                         const abub_png_seg *segs, int nsegs, const uint8_t *luts, int nluts, int W, int H,
                         uint8_t *zbuf, size_t zbuf_bytes, uint8_t *rawbuf, size_t rawbuf_bytes, uint8_t *out,
                         size_t out_bytes, int32_t *status, void *stream);
+/* Typed frames.  Bytes of `rawbuf` a frame of `kind` takes: H * (ceil(W * samples * depth / 8) + 1), rounded up to 16, plus
+ * 16; 0 for a kind outside the table.  Kind 0 gives abub_png_raw_stride(W, H). */
+size_t abub_png_raw_stride_kind(int W, int H, uint32_t kind);
+/* abub_png_decode_dev with abub_png_frame.kind honoured.  raw_stride: the bytes of `rawbuf` every frame of the launch
+ * gets, a multiple of 16 (the largest abub_png_raw_stride_kind among the launch's frames; rawbuf >= nframes * raw_stride).
+ * A frame of kind 0 goes through the kernels of abub_png_decode_dev; the others are unfiltered at their own filter
+ * distance and converted to grey by a kernel of their own.  ABUB_PNG_E_DESC also for a kind outside the table and for a
+ * frame whose scanlines do not fit raw_stride; TOOMUCH / TOOLITTLE are relative to the frame's own size. */
+int abub_png_decode_typed_dev(const uint8_t *files, size_t files_bytes, const abub_png_frame *frames, int nframes,
+                              const abub_png_seg *segs, int nsegs, const uint8_t *luts, int nluts, int W, int H,
+                              uint8_t *zbuf, size_t zbuf_bytes, uint8_t *rawbuf, size_t rawbuf_bytes, size_t raw_stride,
+                              uint8_t *out, size_t out_bytes, int32_t *status, void *stream);
 
 /* ---- packed frames ("ABF1") decoded on the GPU (abub_abf.hip) ---------------------------------------------------
  * The frame format of repacked runs (abub3hs --repack; layout and rules: DESIGN section 3, "Packed frames"; host codec: cv::abfEncode /
