@@ -14,6 +14,7 @@
 #include <condition_variable>
 #include <deque>
 #include <functional>
+#include <map>
 #include <mutex>
 #include <cstdio>
 #include <cstdlib>
@@ -66,11 +67,18 @@ int chainStrideOf(const int *tss, int C)
 bool sameTemplate(const cv::Mat &a, const cv::Mat &b) { return a.data == b.data && a.cols == b.cols && a.rows == b.rows; }
 
 struct PlannedImage {
-    int kind; // 0 = D(i; ref) (genesis), 1 = post-trigger image of frame i, 2 = bellows residual of D(i; ref)
-    int i, ref;
-    int slot; // index into the image / histogram slabs of this round
-    int tozero;
-    int thr;
+    int kind = 0; // 0 = D(i; ref) (genesis), 1 = post-trigger image of frame i, 2 = bellows residual of D(i; ref)
+    int i = 0, ref = 0;
+    int slot = -1; // index into the image / histogram slabs of this round
+    int tozero = 0;
+    int thr = 0;
+    // an image that waits for its batch: no slot, no Otsu threshold yet
+    static PlannedImage make(int kind, int i, int ref, int tozero, int minBox)
+    {
+        PlannedImage p;
+        p.kind = kind, p.i = i, p.ref = ref, p.tozero = tozero, p.minBox = minBox;
+        return p;
+    }
     const uint32_t *fg = nullptr; // raster indices of the candidate pixels (value > tozero), grouped on the GPU
     const uint8_t *fgv = nullptr; // their values: the Otsu cut is applied on the host
     uint32_t nfg = 0;
@@ -105,20 +113,44 @@ struct NeedBellows : public std::runtime_error {
 // EventData served from the pipeline's batched results
 class BatchEventData : public EventData {
 public:
-    // The trigger search's histograms arrive in blocks of frames: block k covers frames [bstart[k], bstart[k + 1]) and
-    // bh[k] points at its histograms once that block has been evaluated for this stack (frame i at (i - bstart[k]) * 256).
+    // The trigger search's histograms arrive in blocks of frames: block k covers frames [bstart[k], bstart[k + 1]).
+    // ref[k] is this stack's part of block k, bound when launch `fetch` of the block is queued for it (Group::Search::Block::
+    // bind): its first job in the block's buffers, frame i's histogram at hist + (i - bstart[k]) * 256, and inc (deferred
+    // launches only): per frame, 1 while the histogram is not final -- its dense rows were handed over by the bound scan and
+    // the row machine has not run on them yet (deferred pieces); cleared when they are completed.  histDev / incDev: the same in
+    // device memory, what the device search reads from the launch on.  The host search reads hist / inc only once the block
+    // has `arrived`: the launch has been waited for
+    struct BlockRef {
+        int fetch = -1;
+        bool arrived = false;
+        size_t job = 0;
+        const uint32_t *hist = nullptr, *histDev = nullptr;
+        uint8_t *inc = nullptr;
+        const uint8_t *incDev = nullptr;
+        bool launched() const { return fetch >= 0; }
+        bool deferred() const { return inc != nullptr; }
+    };
     static constexpr int MAXB = 32;
     int nblocks = 0;
     int bstart[MAXB + 1] = {0};
-    const uint32_t *bh[MAXB] = {nullptr};
-    // inc[k] (optional): per frame of block k, 1 while the frame's histogram is not final -- its dense rows were handed over
-    // by the bound scan and the row machine has not run on them yet (deferred pieces); cleared when they are completed
-    uint8_t *inc[MAXB] = {nullptr};
-    int fetchOf[MAXB] = {0}, slotOf[MAXB] = {0}; // which launch of block k served this stack, and its position in it
-    int needBlock = -1;    // set when diffHist() throws NeedMoreFrames ...
-    bool needPieces = false; // ... true: block needBlock is there, but frame needFrame (and later ones) must be completed
-    int needFrame = 0;
-    int refOffset = 2;
+    BlockRef ref[MAXB];
+    int blockOf(int frame) const
+    {
+        int k = 0;
+        while (k + 1 < nblocks && frame >= bstart[k + 1])
+            ++k;
+        return k;
+    }
+    // What a search that stopped asks for (the host's diffHist, or the device's answer): block `block` for this stack, or
+    // (pieces) that block is there, but frame `frame` and the later ones must be completed.  block < 0: nothing
+    struct Need {
+        int block = -1, frame = 0;
+        bool pieces = false;
+    } need;
+    bool asked() const { return need.block >= 0; }
+    void request(int block, int frame, bool pieces) { need = Need{block, frame, pieces}; }
+    void clearNeed() { need = Need(); }
+    int tss = 0, refOffset = 2; // the camera's training set size and FindTriggerFrame's frame offset for it
     const uint32_t *roundHists = nullptr; // [nslots][256] of the current round
     std::vector<PlannedImage> planned;
     const PlannedImage *cur = nullptr;
@@ -149,26 +181,26 @@ public:
     const uint8_t *ok = nullptr; // per-frame "decoded" flags of a stack that came from disk (NULL: all good)
 
     bool frameOk(int i) const override { return i >= 0 && i < F && (!ok || ok[i]); }
+    // the first frame that was not decoded (F: none)
+    int firstBad() const
+    {
+        int i = 0;
+        while (i < F && frameOk(i))
+            ++i;
+        return i;
+    }
     cv::Mat hostFrame(int) const override { return cv::Mat(); }
     const uint32_t *diffHist(int i, int off) override
     {
         if (off != refOffset || i < 1 || i >= F)
             throw std::runtime_error("BatchEventData::diffHist: unplanned request");
-        int k = 0;
-        while (k + 1 < nblocks && i >= bstart[k + 1])
-            ++k;
-        if (!bh[k]) {
-            needBlock = k;
-            needPieces = false;
+        const int k = blockOf(i);
+        const BlockRef &b = ref[k];
+        if (!b.arrived || (b.inc && b.inc[i - bstart[k]])) {
+            request(k, i, b.arrived);
             throw NeedMoreFrames();
         }
-        if (inc[k] && inc[k][i - bstart[k]]) {
-            needBlock = k;
-            needPieces = true;
-            needFrame = i;
-            throw NeedMoreFrames();
-        }
-        return bh[k] + (size_t)(i - bstart[k]) * 256;
+        return b.hist + (size_t)(i - bstart[k]) * 256;
     }
     const uint32_t *find(int kind, int i, int ref)
     {
@@ -341,14 +373,11 @@ struct StackState : StackResult {
     bool done = false;
     bool localize = false;
     bool dropIn = false; // must be re-run through the one-at-a-time path (bellows veto)
-    bool needMore = false; // the trigger search stopped at a frame block that is not evaluated yet (data.needBlock)
+    // (the trigger search stopped at frames that are not evaluated yet: data.asked())
     bool needBellows = false; // localize stopped at a bellows-veto request (data.matches / data.residuals)
-    // trigger knob: the device search's answer for the analyzer's current state (trigReady: not consumed yet), and where
-    // this stack's histograms (and deferred flags) of each bound block lie in device memory
+    // trigger knob: the device search's answer for the analyzer's current state (trigReady: not consumed yet)
     bool trigReady = false;
     abub_trig_result trigRes{};
-    const uint32_t *dbh[BatchEventData::MAXB] = {nullptr};
-    const uint8_t *dinc[BatchEventData::MAXB] = {nullptr};
     bool vetoed = false;      // a bellows residual was computed for this stack in the batch
 };
 
@@ -636,26 +665,268 @@ struct Group {
     int s0 = 0, s1 = 0; // stacks [s0, s1)
     size_t ns = 0, n3 = 0; // their number, and the image slots of a stage-3 batch: NumFramesBubbleTrack + 1 per stack
     Event stage1Done, kernelsDone, blockDone;
-    // trigger search, per frame block k = frames [blocks[k], blocks[k + 1]): job lists and histograms (capacity: every
-    // stack of the group once), and the deferred pieces: handed-over row ranges of every launch of the block, per-launch
-    // counters, per-job "incomplete" / "wanted" flags
-    struct Fetch {
-        int first = 0, n = 0;   // stacks [first, first + n) of the block's buffers
-        size_t pieceOff = 0;    // its range of the block's piece list
-        bool deferred = false;
-    };
-    struct Block {
-        Mirror<abub_job> jobs;
-        Mirror<uint32_t> hist;
-        DeviceArray<uint64_t> pieces;
-        DeviceArray<uint32_t> pcount; // [64]: one per launch
-        Mirror<uint8_t> inc, want;
-        size_t pieceCap = 0, pieceUsed = 0;
-        int slots = 0; // stacks the buffers hold: every stack of the group once
-        int used = 0;  // stacks already served in this run (each stack fetches a block at most once)
-        std::vector<Fetch> fetches;
-    };
-    std::vector<Block> blocks;
+    // The trigger search (stages 1 and 2) of the group's stacks: the frame blocks' buffers, their launches (K2), the deferred
+    // pieces and the device search (K6).  The launching functions take `run`, the pipeline's own counters (jobsLaunched,
+    // jobsCompleted, trigger.launches are kept across the groups): the caller holds the pipeline's launchMu, or no group
+    // thread runs yet.  Everything else here belongs to the group's thread.
+    struct Search {
+        using BlockRef = BatchEventData::BlockRef;
+        // what the pipeline's constructor fixes: geometry, the frame offset every camera shares (else 0), whether dense
+        // frames' rows are evaluated on demand, and the frame blocks: block k = frames [starts[k], starts[k + 1])
+        struct Setup {
+            int W = 0, H = 0, F = 0, C = 0, chainStride = 0;
+            bool deferPieces = false;
+            std::vector<int> starts;
+            int nblocks() const { return (int)starts.size() - 1; }
+        };
+        struct Fetch {
+            int first = 0, n = 0;   // stacks [first, first + n) of the block's buffers
+            size_t pieceOff = 0;    // its range of the block's piece list
+            bool deferred = false;
+        };
+        // per frame block: job lists and histograms (capacity: every stack of the group once), and the deferred pieces:
+        // handed-over row ranges of every launch of the block, per-launch counters, per-job "incomplete" / "wanted" flags
+        struct Block {
+            int first = 0, len = 0; // frames [first, first + len)
+            Mirror<abub_job> jobs;
+            Mirror<uint32_t> hist;
+            DeviceArray<uint64_t> pieces;
+            DeviceArray<uint32_t> pcount; // [64]: one per launch
+            Mirror<uint8_t> inc, want;
+            size_t pieceCap = 0, pieceUsed = 0;
+            int used = 0; // stacks already served in this run (each stack fetches a block at most once: `ns` at the most)
+            std::vector<Fetch> fetches;
+            // where the stack at position q of launch f lies in the block's buffers (the only place that works it out)
+            BlockRef bind(int f, int q) const
+            {
+                const Fetch &fe = fetches[f];
+                BlockRef r;
+                r.fetch = f;
+                r.job = (size_t)(fe.first + q) * len;
+                r.hist = hist.h + r.job * 256;
+                r.histDev = hist.d + r.job * 256;
+                if (fe.deferred)
+                    r.inc = inc.h + r.job, r.incDev = inc.d + r.job;
+                return r;
+            }
+        };
+        Setup cfg;
+        size_t ns = 0; // stacks of the group: every per-job buffer of a block holds each of them once
+        std::vector<Block> blocks;
+        // trigger knob: K6 (abub_trigger.hip) on the blocks' device histograms: descriptors of one launch (pinned, copied by
+        // the launcher), its results, the stacks it serves in launch order.  One launch at a time: every launch is waited for
+        // (stage1Done / blockDone) and collected before the next one is filled in.
+        struct Trigger {
+            bool inflight = false;
+            PinnedArray<abub_trig_stack> st;
+            PinnedArray<abub_trig_seg> sg;
+            DeviceArray<uint8_t> desc;
+            size_t descBytes = 0;
+            Mirror<abub_trig_result> res;
+            std::vector<int> list;
+            Event ev[2]; // before and after the launch
+            void firstUse(size_t ns)
+            {
+                if (ev[1].get())
+                    return;
+                const size_t nsg = ns * BatchEventData::MAXB;
+                st.allocate(ns);
+                sg.allocate(nsg);
+                descBytes = abub_trigger_search_desc_bytes((int)ns, (int)nsg);
+                desc.allocate(descBytes);
+                res.allocate(ns);
+                ev[0].create(true);
+                ev[1].create(true);
+            }
+        } trig;
+
+        void allocate(const Setup &setup, size_t nstacks)
+        {
+            cfg = setup;
+            ns = nstacks;
+            blocks.resize((size_t)cfg.nblocks());
+            for (int k = 0; k < cfg.nblocks(); ++k) {
+                Block &B = blocks[k];
+                B.first = cfg.starts[k];
+                B.len = cfg.starts[k + 1] - cfg.starts[k];
+                const size_t nj = ns * (size_t)std::max(B.len, 1);
+                B.jobs.allocate(nj);
+                B.hist.allocate(nj * 256);
+                // deferred pieces: at most H / 16 + 8 row ranges per job (chunks are at least 16 rows), 64 launches per block
+                B.pieceCap = cfg.deferPieces ? nj * (size_t)(cfg.H / 16 + 8) : 1;
+                B.pieces.allocate(B.pieceCap);
+                B.pcount.allocate(64);
+                B.inc.allocate(nj);
+                B.want.allocate(nj);
+            }
+        }
+        // a new run: no block has served a stack, no search is under way
+        void beginRun()
+        {
+            for (Block &B : blocks) {
+                B.used = 0;
+                B.pieceUsed = 0;
+                B.fetches.clear();
+            }
+            trig.inflight = false;
+        }
+        // trigger-search job of frame i of stack s (FindTriggerFrame's pairing, see refOffset).  Frames a shorter stack does
+        // not have are replaced by its last one on both sides (D = 0: a quiet job that keeps the chain structure the scan
+        // relies on).
+        abub_job triggerJob(int s, const BatchEventData &d, int i, uint32_t out) const
+        {
+            const int last = std::max(d.F - 1, 0);
+            abub_job j;
+            j.cur = (uint32_t)(s * cfg.F + std::min(i, last));
+            j.ref = (uint32_t)(s * cfg.F + std::min(std::max(i - d.refOffset, 0), last));
+            j.model = (uint32_t)(s % cfg.C);
+            j.out = out;
+            return j;
+        }
+        // K2 over block k for the listed stacks, which are bound to the launch: jobs -> device, launch, histograms -> host
+        void launchBlock(int k, const std::vector<int> &list, std::vector<StackState> &stacks, const uint8_t *d_frames,
+                         const uint8_t *d_sigma6, hipStream_t stream, PipeStats &run)
+        {
+            Block &B = blocks[k];
+            const int W = cfg.W, H = cfg.H, blen = B.len, first = B.used, n = (int)list.size();
+            if (blen <= 0 || n == 0)
+                return;
+            if (first + n > (int)ns)
+                throw std::runtime_error("RunPipeline: a frame block was requested twice for one stack");
+            const size_t j0 = (size_t)first * blen;
+            for (int q = 0; q < n; ++q)
+                for (int i = 0; i < blen; ++i)
+                    B.jobs.h[j0 + (size_t)q * blen + i] =
+                        triggerJob(list[q], stacks[list[q]].data, B.first + i, (uint32_t)((size_t)q * blen + i));
+            abub_job *dj = B.jobs.d + j0;
+            uint32_t *dh = B.hist.d + j0 * 256;
+            const int nj = n * blen;
+            B.jobs.toDevice(nj, stream, j0);
+            Fetch fe;
+            fe.first = first;
+            fe.n = n;
+            // deferral is decided per launch: the K2 options (abub_k2_set_option "bound") may change after construction
+            const bool defer = cfg.deferPieces && abub_k2_deferred_ok(W, H);
+            const size_t pcap = defer ? abub_k2_pieces_cap(nj, W, H) : 0;
+            if (defer && B.fetches.size() < 64 && B.pieceUsed + pcap <= B.pieceCap) {
+                // the scan alone: dense frames' rows go to this launch's range of the block's piece list, their jobs are flagged
+                fe.deferred = true;
+                fe.pieceOff = B.pieceUsed;
+                B.pieceUsed += pcap;
+                check(abub_diff_hist_chained_deferred_dev(d_frames, d_sigma6, dj, nj, W, H, dh, blen, cfg.chainStride,
+                                                          B.pieces + fe.pieceOff, (uint32_t)pcap, B.pcount + B.fetches.size(),
+                                                          B.inc.d + j0, stream),
+                      "trigger search K2 (deferred pieces)");
+                B.inc.toHost(nj, stream, j0);
+            } else {
+                // all cameras on the same frame offset: per stack the jobs are a chain (job i refs the cur frame of job i - off)
+                // and the scan loads every frame row once for both of its jobs
+                check(cfg.chainStride > 0
+                          ? abub_diff_hist_chained_dev(d_frames, d_sigma6, dj, nj, W, H, dh, blen, cfg.chainStride, stream)
+                          : abub_diff_hist_dev(d_frames, d_sigma6, dj, nj, W, H, dh, nullptr, 0, stream),
+                      "trigger search K2");
+            }
+            B.hist.toHost((size_t)nj * 256, stream, j0 * 256);
+            B.fetches.push_back(fe);
+            B.used = first + n;
+            for (int q = 0; q < n; ++q)
+                stacks[list[q]].data.ref[k] = B.bind((int)B.fetches.size() - 1, q);
+            run.timing.jobsLaunched += nj;
+        }
+        // The row machine on launch f of block k: for every asking stack (all served by that launch), the flagged frames from
+        // the one it stopped at to the end of the block.  clearOnDevice (trigger knob): they are final on the device too, where
+        // K6 reads the flags (the host mirror of the flags is cleared by served())
+        void completePieces(int k, int f, const std::vector<int> &askers, const std::vector<StackState> &stacks,
+                            const uint8_t *d_frames, const uint8_t *d_sigma6, bool clearOnDevice, hipStream_t stream, PipeStats &run)
+        {
+            Block &B = blocks[k];
+            const Fetch &fe = B.fetches[f];
+            const size_t blen = (size_t)B.len, nj = (size_t)fe.n * blen, base = (size_t)fe.first * blen;
+            std::memset(B.want.h + base, 0, nj);
+            for (int sI : askers) {
+                const BatchEventData &d = stacks[sI].data;
+                for (size_t j = (size_t)(d.need.frame - B.first); j < blen; ++j)
+                    if (d.ref[k].inc[j]) {
+                        B.want.h[d.ref[k].job + j] = 1;
+                        ++run.timing.jobsCompleted;
+                    }
+            }
+            B.want.toDevice(nj, stream, base);
+            check(abub_diff_hist_pieces_dev(d_frames, d_sigma6, B.jobs.d + base, (int)nj, cfg.W, cfg.H, B.hist.d + base * 256,
+                                            B.pieces + fe.pieceOff, B.pcount + f, B.want.d + base, stream),
+                  "trigger search K2 (pieces)");
+            for (int sI : askers) {
+                const BatchEventData &d = stacks[sI].data;
+                const size_t j0 = (size_t)(d.need.frame - B.first);
+                B.hist.toHost((blen - j0) * 256, stream, (d.ref[k].job + j0) * 256);
+            }
+            if (clearOnDevice) // one launch per fetch
+                check(abub_trigger_clear_pending_dev(B.inc.d + base, B.want.d + base, nj, stream), "trigger search flags");
+        }
+        // after the launches that serve the stack's request have been waited for: its block has arrived, or its frames are final
+        void served(BatchEventData &d) const
+        {
+            BlockRef &r = d.ref[d.need.block];
+            const Block &B = blocks[d.need.block];
+            if (d.need.pieces)
+                std::fill(r.inc + (d.need.frame - B.first), r.inc + B.len, (uint8_t)0);
+            r.arrived = true;
+            d.clearNeed();
+        }
+        // One K6 launch for the listed stacks, each from its analyzer's current state (retry: behind the last trigger), on
+        // every block launched for it so far; the results come back with the next event the group waits for (collectSearch).
+        void launchSearch(const std::vector<int> &list, const std::vector<StackState> &stacks, hipStream_t stream, PipeStats &run)
+        {
+            Trigger &T = trig;
+            if (list.empty())
+                return;
+            if (T.inflight)
+                throw std::runtime_error("RunPipeline: a trigger search was launched before the previous one was collected");
+            T.firstUse(ns);
+            uint32_t nseg = 0;
+            for (size_t q = 0; q < list.size(); ++q) {
+                const StackState &st_ = stacks[list[q]];
+                abub_trig_stack &d = T.st[q];
+                d.seg0 = nseg;
+                d.F = st_.data.F;
+                d.start = (st_.analyzer ? st_.analyzer->MatTrigFrame : 0) + 1;
+                d.tss = st_.data.tss;
+                d.first_bad = st_.data.firstBad();
+                for (int k = 0; k < cfg.nblocks(); ++k)
+                    if (st_.data.ref[k].launched()) {
+                        abub_trig_seg &g = T.sg[nseg++];
+                        g.hist = st_.data.ref[k].histDev;
+                        g.pending = st_.data.ref[k].incDev;
+                        g.first = blocks[k].first;
+                        g.count = blocks[k].len;
+                    }
+                d.nseg = nseg - d.seg0;
+            }
+            HIPOK(hipEventRecord(T.ev[0].get(), stream));
+            check(abub_trigger_search_dev(T.st, T.sg, (int)list.size(), (int)nseg, cfg.W, cfg.H, T.desc, T.descBytes, T.res.d,
+                                          nullptr, 0, stream),
+                  "trigger search K6");
+            HIPOK(hipEventRecord(T.ev[1].get(), stream));
+            T.res.toHost(list.size(), stream);
+            T.list = list;
+            T.inflight = true;
+            ++run.trigger.launches;
+        }
+        // after the event behind the launch has been waited for: every served stack gets its answer
+        void collectSearch(std::vector<StackState> &stacks, PipeStats &groupStats)
+        {
+            Trigger &T = trig;
+            if (!T.inflight)
+                return;
+            for (size_t q = 0; q < T.list.size(); ++q) {
+                StackState &st_ = stacks[T.list[q]];
+                st_.trigRes = T.res.h[q];
+                st_.trigReady = true;
+            }
+            groupStats.trigger.k6Ms += T.ev[1].msSince(T.ev[0]);
+            T.inflight = false;
+        }
+    } search;
     Mirror<abub_job> jobs3;
     Mirror<uint32_t> hist3;
     DeviceArray<uint8_t> img;
@@ -823,32 +1094,6 @@ struct Group {
             }
         }
     } contours;
-    // trigger knob: K6 (abub_trigger.hip) on the blocks' device histograms: descriptors of one launch (pinned, copied by
-    // the launcher), its results, the stacks it serves in launch order.  One launch at a time: every launch is waited for
-    // (stage1Done / blockDone) and collected before the next one is filled in.
-    struct Trigger {
-        bool inflight = false;
-        PinnedArray<abub_trig_stack> st;
-        PinnedArray<abub_trig_seg> sg;
-        DeviceArray<uint8_t> desc;
-        size_t descBytes = 0;
-        Mirror<abub_trig_result> res;
-        std::vector<int> list;
-        Event ev[2]; // before and after the launch
-        void firstUse(size_t ns)
-        {
-            if (ev[1].get())
-                return;
-            const size_t nsg = ns * BatchEventData::MAXB;
-            st.allocate(ns);
-            sg.allocate(nsg);
-            descBytes = abub_trigger_search_desc_bytes((int)ns, (int)nsg);
-            desc.allocate(descBytes);
-            res.allocate(ns);
-            ev[0].create(true);
-            ev[1].create(true);
-        }
-    } trig;
     // localize knob: K7 (abub_localize.hip) then describes every contour (the records) and runs the localizer's decisions per
     // stack (descriptors: pinned, copied by the launcher); the per-stack results, boxes and tracks come back
     struct Localize {
@@ -1012,13 +1257,11 @@ public:
     DeviceArray<uint8_t> ownFrames;     // frame slab owned by the pipeline (streamed mode only)
     std::vector<Group> groups;
     std::unique_ptr<WorkerPool> pool;
-    std::vector<int> blocks;            // frame blocks of the trigger search: block k = frames [blocks[k], blocks[k + 1])
-    bool deferPieces = false;           // trigger search: dense frames' rows are evaluated on demand (see the constructor)
+    Group::Search::Setup search;        // the trigger search's constants (see the constructor): every group has a copy
     bool bellowsDropIn = false;         // ABUB_PIPE_BELLOWS=dropin: every bellows veto takes the one-at-a-time path (A/B)
     PipeStats stats;                    // the last run's, merged over the groups
     Stream stage1Stream;                // all trigger-search launches, in group order (see run())
-    int chainStride = 0;                // FindTriggerFrame's frame offset when every camera shares it, else 0
-    bool ordered = true;                // localisation kernels queue on stage1Stream too (see batchImages())
+    bool ordered = true;                // a group's later kernels queue on stage1Stream too (see kernelStream())
     int pairCap = 0;                    // ABUB_PIPE_PAIRCAP (0: unset)
     int locCap = 0;                     // ABUB_PIPE_LOCCAP (0: unset)
     int blobs = 0, contours = 0, trigger = 0, localizeDev = 0; // the knobs (see `knobs` and abh_pipe_set_option)
@@ -1066,151 +1309,20 @@ public:
         }
         out.writeCameraOutput();
     }
-    // trigger-search job of frame i of stack s (FindTriggerFrame's pairing, see refOffset).  Frames a shorter stack does not
-    // have are replaced by its last one on both sides (D = 0: a quiet job that keeps the chain structure the scan relies on).
-    abub_job triggerJob(int s, int i, uint32_t out) const
-    {
-        const int c = s % C, off = refOffset(tss[c]);
-        const int Fs = meta.empty() ? F : (int)meta[s].names.size();
-        const int last = std::max(Fs - 1, 0);
-        abub_job j;
-        j.cur = (uint32_t)(s * F + std::min(i, last));
-        j.ref = (uint32_t)(s * F + std::min(std::max(i - off, 0), last));
-        j.model = (uint32_t)c;
-        j.out = out;
-        return j;
-    }
-    // after the launch of block k has been waited for: the stack at position q of fetch `f` gets its histograms (and flags)
-    void bindBlock(Group::Block &B, int k, StackState &st_, int f, int q)
-    {
-        const Group::Fetch &fe = B.fetches[f];
-        const size_t blen = (size_t)(blocks[k + 1] - blocks[k]), slot = (size_t)fe.first + q;
-        st_.data.bh[k] = B.hist.h + slot * blen * 256;
-        st_.data.inc[k] = fe.deferred ? B.inc.h + slot * blen : nullptr;
-        st_.data.fetchOf[k] = f;
-        st_.data.slotOf[k] = q;
-    }
-    // the same for the device search, at launch time: where the stack's histograms and deferred flags of block k lie in HBM
-    void bindBlockDevice(Group::Block &B, int k, StackState &st_, int f, int q)
-    {
-        const Group::Fetch &fe = B.fetches[f];
-        const size_t blen = (size_t)(blocks[k + 1] - blocks[k]), slot = (size_t)fe.first + q;
-        st_.dbh[k] = B.hist.d + slot * blen * 256;
-        st_.dinc[k] = fe.deferred ? B.inc.d + slot * blen : nullptr;
-    }
     int stackFrames(int s) const { return meta.empty() ? F : (int)meta[s].names.size(); }
-    // trigger knob: does stack s keep the host search (decided before the first search, from the kernel's static limits)
-    bool trigHostRoute(int s) const { return stackFrames(s) > trigMaxF; }
-    // One K6 launch for the listed stacks, each from its analyzer's current state (retry: behind the last trigger), on the
-    // blocks bound for it so far; the results come back with the next event the group waits for (collectSearch).
-    void launchSearch(Group &G, const std::vector<int> &list, hipStream_t stream)
+    // trigger knob: is stack s searched on the device in this run (decided before the first search, from the kernel's static
+    // limits; the host search stays for the others), and the stacks of a list that are
+    bool devRoute(int s) const { return trigOn && stackFrames(s) <= trigMaxF; }
+    std::vector<int> devRoute(std::vector<int> list) const
     {
-        Group::Trigger &T = G.trig;
-        if (list.empty())
-            return;
-        if (T.inflight)
-            throw std::runtime_error("RunPipeline: a trigger search was launched before the previous one was collected");
-        T.firstUse(G.ns);
-        const int nB = (int)blocks.size() - 1;
-        uint32_t nseg = 0;
-        for (size_t q = 0; q < list.size(); ++q) {
-            const int s = list[q];
-            const StackState &st_ = stacks[s];
-            abub_trig_stack &d = T.st[q];
-            const int Fs = stackFrames(s);
-            d.seg0 = nseg;
-            d.F = Fs;
-            d.start = (st_.analyzer ? st_.analyzer->MatTrigFrame : 0) + 1;
-            d.tss = tss[s % C];
-            d.first_bad = Fs;
-            if (!meta.empty())
-                for (int i = 0; i < Fs; ++i)
-                    if (!meta[s].ok[i]) {
-                        d.first_bad = i;
-                        break;
-                    }
-            for (int k = 0; k < nB; ++k)
-                if (st_.dbh[k] && blocks[k + 1] > blocks[k]) {
-                    abub_trig_seg &g = T.sg[nseg++];
-                    g.hist = st_.dbh[k];
-                    g.pending = st_.dinc[k];
-                    g.first = blocks[k];
-                    g.count = blocks[k + 1] - blocks[k];
-                }
-            d.nseg = nseg - d.seg0;
-        }
-        HIPOK(hipEventRecord(T.ev[0].get(), stream));
-        check(abub_trigger_search_dev(T.st, T.sg, (int)list.size(), (int)nseg, W, H, T.desc, T.descBytes, T.res.d, nullptr, 0,
-                                      stream),
-              "trigger search K6");
-        HIPOK(hipEventRecord(T.ev[1].get(), stream));
-        T.res.toHost(list.size(), stream);
-        T.list = list;
-        T.inflight = true;
-        ++stats.trigger.launches;
+        list.erase(std::remove_if(list.begin(), list.end(), [this](int s) { return !devRoute(s); }), list.end());
+        return list;
     }
-    // after the event behind the launch has been waited for: every served stack gets its answer
-    void collectSearch(Group &G)
-    {
-        Group::Trigger &T = G.trig;
-        if (!T.inflight)
-            return;
-        for (size_t q = 0; q < T.list.size(); ++q) {
-            StackState &st_ = stacks[T.list[q]];
-            st_.trigRes = T.res.h[q];
-            st_.trigReady = true;
-        }
-        G.stats.trigger.k6Ms += T.ev[1].msSince(T.ev[0]);
-        T.inflight = false;
-    }
-    // K2 over block k for the listed stacks (all of them on the same block): jobs -> device, launch, histograms -> host.
-    // Returns the first slot (in stacks) of the block's histogram buffer the results go to.
-    int launchBlock(Group::Block &B, int k, const std::vector<int> &list, const uint8_t *d_frames, const uint8_t *d_sigma6,
-                    hipStream_t stream)
-    {
-        const int a = blocks[k], blen = blocks[k + 1] - blocks[k];
-        const int first = B.used, n = (int)list.size();
-        if (blen <= 0 || n == 0)
-            return first;
-        if (first + n > B.slots)
-            throw std::runtime_error("RunPipeline: a frame block was requested twice for one stack");
-        const size_t j0 = (size_t)first * blen;
-        for (int q = 0; q < n; ++q)
-            for (int i = 0; i < blen; ++i)
-                B.jobs.h[j0 + (size_t)q * blen + i] = triggerJob(list[q], a + i, (uint32_t)((size_t)q * blen + i));
-        abub_job *dj = B.jobs.d + j0;
-        uint32_t *dh = B.hist.d + j0 * 256;
-        const int nj = n * blen;
-        B.jobs.toDevice(nj, stream, j0);
-        Group::Fetch fe;
-        fe.first = first;
-        fe.n = n;
-        // deferral is decided per launch: the K2 options (abub_k2_set_option "bound") may change after construction
-        const bool defer = deferPieces && abub_k2_deferred_ok(W, H);
-        const size_t pcap = defer ? abub_k2_pieces_cap(nj, W, H) : 0;
-        if (defer && B.fetches.size() < 64 && B.pieceUsed + pcap <= B.pieceCap) {
-            // the scan alone: dense frames' rows go to this launch's range of the block's piece list, their jobs are flagged
-            fe.deferred = true;
-            fe.pieceOff = B.pieceUsed;
-            B.pieceUsed += pcap;
-            check(abub_diff_hist_chained_deferred_dev(d_frames, d_sigma6, dj, nj, W, H, dh, blen, chainStride,
-                                                      B.pieces + fe.pieceOff, (uint32_t)pcap, B.pcount + B.fetches.size(),
-                                                      B.inc.d + j0, stream),
-                  "trigger search K2 (deferred pieces)");
-            B.inc.toHost(nj, stream, j0);
-        } else {
-            // all cameras on the same frame offset: per stack the jobs are a chain (job i refs the cur frame of job i - off)
-            // and the scan loads every frame row once for both of its jobs
-            check(chainStride > 0 ? abub_diff_hist_chained_dev(d_frames, d_sigma6, dj, nj, W, H, dh, blen, chainStride, stream)
-                                  : abub_diff_hist_dev(d_frames, d_sigma6, dj, nj, W, H, dh, nullptr, 0, stream),
-                  "trigger search K2");
-        }
-        B.hist.toHost((size_t)nj * 256, stream, j0 * 256);
-        B.fetches.push_back(fe);
-        B.used = first + n;
-        stats.timing.jobsLaunched += nj;
-        return first;
-    }
+    // Where a group's kernels behind stage 1 go (their results come back on the group's own stream).  Ordered mode (default):
+    // every group's kernels queue on the one trigger-search stream, so the GPU sees K2(g0) K2(g1) .. S3(g0) S3(g1) .. strictly
+    // one kernel at a time -- chip-filling kernels launched on different streams only slow each other down -- while the host
+    // stages of group g run under the kernels of group g+1.
+    hipStream_t kernelStream(Group &G) { return ordered ? stage1Stream.get() : G.stream.get(); }
 
     RunPipeline(int device_, int W_, int H_, int F_, int E_, int C_, const int *tss_, int nthreads_, const char *maskdir)
         : device(device_), W(W_), H(H_), F(F_), E(E_), C(C_), S(E_ * C_), nthreads(nthreads_), P((size_t)W_ * H_),
@@ -1237,7 +1349,8 @@ public:
         if (ngroups > S)
             ngroups = S;
         const int K = NumFramesBubbleTrack + 1;
-        chainStride = chainStrideOf(tss.data(), C);
+        search.W = W, search.H = H, search.F = F, search.C = C;
+        search.chainStride = chainStrideOf(tss.data(), C);
         groups.resize(ngroups);
         pool.reset(new WorkerPool(std::max(0, nthreads - ngroups))); // the group driver threads take part too
         // Frame blocks of the trigger search.  The reference walks the frames in order and stops at the trigger
@@ -1251,7 +1364,7 @@ public:
             // two look-ahead frames and a margin; then blocks of about a fifth of the stack (a value > 0 overrides either)
             const int e0 = envInt("ABUB_PIPE_BLOCK0", 0), e1 = envInt("ABUB_PIPE_BLOCK", 0);
             int first = e0 > 0 ? e0 : F / 2 + 4, step = e1 > 0 ? e1 : std::max(4, F / 5);
-            blocks.clear();
+            std::vector<int> &blocks = search.starts;
             blocks.push_back(1);
             if (lazy && F > 8)
                 for (int b = std::min(first + 1, F); b < F && (int)blocks.size() < BatchEventData::MAXB; b += step)
@@ -1259,9 +1372,8 @@ public:
             blocks.push_back(std::max(F, 1)); // block k = frames [blocks[k], blocks[k + 1])
             // Deferred pieces: inside a block the bound scan still covers every frame, but the row machine runs only on the
             // dense frames a search actually reaches (ABUB_PIPE_DEFER=0: at once, for every frame of the block).
-            deferPieces = envInt("ABUB_PIPE_DEFER", 1) != 0 && chainStride > 0 && abub_fast_path(W) != 0;
+            search.deferPieces = envInt("ABUB_PIPE_DEFER", 1) != 0 && search.chainStride > 0 && abub_fast_path(W) != 0;
         }
-        const int nB = (int)blocks.size() - 1;
         // initial capacity of the candidate lists (they grow on demand): ABUB_PIPE_PAIRCAP sets the veto's too
         pairCap = envInt("ABUB_PIPE_PAIRCAP", 0);
         // ... and of the record, box and track lists of the localize knob: ABUB_PIPE_LOCCAP entries each
@@ -1278,20 +1390,7 @@ public:
             G.stage1Done.create(false);
             G.kernelsDone.create(false);
             G.blockDone.create(false);
-            G.blocks.resize(nB);
-            for (int k = 0; k < nB; ++k) {
-                Group::Block &B = G.blocks[k];
-                const size_t nj = ns * (size_t)std::max(blocks[k + 1] - blocks[k], 1);
-                B.slots = (int)ns;
-                B.jobs.allocate(nj);
-                B.hist.allocate(nj * 256);
-                // deferred pieces: at most H / 16 + 8 row ranges per job (chunks are at least 16 rows), 64 launches per block
-                B.pieceCap = deferPieces ? nj * (size_t)(H / 16 + 8) : 1;
-                B.pieces.allocate(B.pieceCap);
-                B.pcount.allocate(64);
-                B.inc.allocate(nj);
-                B.want.allocate(nj);
-            }
+            G.search.allocate(search, ns);
             G.jobs3.allocate(n3);
             G.hist3.allocate(n3 * 256);
             G.img.allocate(abub_fast_path(W) ? 256 : n3 * P); // only the unfused fallback stores images
@@ -1356,6 +1455,19 @@ public:
         stacks.clear();
         stacks.resize(S);
         trigOn = trigger != 0; // read once per run
+        // what the providers of the fresh stacks serve from (the analyzers are built by the groups, while stage 1 runs)
+        for (int s = 0; s < S; ++s) {
+            BatchEventData &d = stacks[s].data;
+            d.W = W;
+            d.H = H;
+            d.F = stackFrames(s);
+            d.ok = meta.empty() ? nullptr : meta[s].ok.data();
+            d.tss = tss[s % C];
+            d.refOffset = refOffset(d.tss);
+            d.bellowsDropIn = bellowsDropIn;
+            d.nblocks = search.nblocks();
+            std::copy(search.starts.begin(), search.starts.end(), d.bstart);
+        }
         // Stage 1 of every group goes to ONE stream in group order: the trigger search of group g+1 runs
         // on the GPU while the host threads of group g are in their state machines (two kernels launched on
         // different streams would simply share the chip and finish together, leaving nothing to overlap).
@@ -1364,29 +1476,14 @@ public:
             Group &G = groups[gi];
             if (waitCopies)
                 HIPOK(hipStreamWaitEvent(stage1Stream.get(), copied[gi].get(), 0));
-            for (Group::Block &B : G.blocks) {
-                B.used = 0;
-                B.pieceUsed = 0;
-                B.fetches.clear();
-            }
+            G.search.beginRun();
             std::vector<int> all;
             for (int sI = G.s0; sI < G.s1; ++sI)
                 all.push_back(sI);
-            if (F > 1)
-                launchBlock(G.blocks[0], 0, all, d_frames, d_sigma6, stage1Stream.get()); // block 0: every stack, slot == index in the group
-            if (trigOn) {
-                // the first search of every stack right behind the K2 that produces its input: the decisions arrive with
-                // stage1Done
-                G.trig.inflight = false;
-                std::vector<int> dev;
-                for (int sI : all)
-                    if (!trigHostRoute(sI)) {
-                        if (F > 1)
-                            bindBlockDevice(G.blocks[0], 0, stacks[sI], 0, sI - G.s0);
-                        dev.push_back(sI);
-                    }
-                launchSearch(G, dev, stage1Stream.get());
-            }
+            // block 0: every stack, in group order (nothing to launch for one-frame stacks); trigger knob: the first search
+            // of every stack right behind the K2 that produces its input: the decisions arrive with stage1Done
+            G.search.launchBlock(0, all, stacks, d_frames, d_sigma6, stage1Stream.get(), stats);
+            G.search.launchSearch(devRoute(all), stacks, stage1Stream.get(), stats);
             HIPOK(hipEventRecord(G.stage1Done.get(), stage1Stream.get()));
         }
         std::vector<std::thread> th;
@@ -1426,7 +1523,7 @@ private:
         }
         const int e = s / C, c = s % C;
         try {
-            const int Fs = meta.empty() ? F : (int)meta[s].names.size();
+            const int Fs = stackFrames(s);
             std::vector<cv::Mat> frames((size_t)Fs);
             for (int i = 0; i < Fs; ++i) {
                 if (!meta.empty() && !meta[s].ok[i])
@@ -1482,42 +1579,23 @@ private:
             StackState &st_ = stacks[s];
             const int e = s / C, c = s % C;
             Trainer *t = trainers[c].get();
-            if (meta.empty()) {
-                st_.analyzer.reset(new L3Localizer(std::to_string(e), "", c, true, &t, maskDir, parser.clone()));
-                st_.data.F = F;
-                st_.data.ok = nullptr;
-            } else {
-                st_.analyzer.reset(new L3Localizer(meta[s].eventID, "", c, true, &t, maskDir, metaParser.clone()));
-                st_.data.F = (int)meta[s].names.size();
-                st_.data.ok = meta[s].ok.data();
-            }
-            st_.data.W = W;
-            st_.data.H = H;
-            st_.data.refOffset = refOffset(tss[c]);
-            st_.data.bellowsDropIn = bellowsDropIn;
-            st_.data.clearVeto();
-            st_.vetoed = false;
-            st_.data.nblocks = (int)blocks.size() - 1;
-            for (size_t b = 0; b < blocks.size(); ++b)
-                st_.data.bstart[b] = blocks[b];
-            for (int b = 0; b < st_.data.nblocks; ++b) {
-                st_.data.bh[b] = nullptr;
-                st_.data.inc[b] = nullptr;
-            }
-            // block 0 was launched for every stack of the group, in group order (fetch 0, position k)
-            if (F > 1)
-                bindBlock(G.blocks[0], 0, st_, 0, k);
+            st_.analyzer.reset(new L3Localizer(meta.empty() ? std::to_string(e) : meta[s].eventID, "", c, true, &t, maskDir,
+                                               (meta.empty() ? parser : metaParser).clone()));
             st_.analyzer->AttachEventData(&st_.data);
         });
         HIPOK(hipEventSynchronize(G.stage1Done.get()));
         G.stats.timing.stage1Ms = nowMs() - t0;
 
+        // block 0, and with the trigger knob the first answers, came with stage1Done
         std::vector<int> pending(ns);
-        for (int k = 0; k < ns; ++k)
+        for (int k = 0; k < ns; ++k) {
             pending[k] = G.s0 + k;
-        if (trigOn)
-            for (int sI : pending)
-                ++(trigHostRoute(sI) ? G.stats.trigger.hostStacks : G.stats.trigger.devStacks);
+            BatchEventData::BlockRef &r = stacks[pending[k]].data.ref[0];
+            r.arrived = r.launched();
+        }
+        G.search.collectSearch(stacks, G.stats);
+        G.stats.trigger.devStacks = (double)devRoute(pending).size();
+        G.stats.trigger.hostStacks = trigOn ? ns - G.stats.trigger.devStacks : 0;
         while (!pending.empty()) {
             ++G.stats.rounds;
             // ---- stage 2: trigger search + plan ------------------------------------------------
@@ -1526,36 +1604,27 @@ private:
             double t2 = nowMs();
             std::vector<int> todo(pending);
             while (!todo.empty()) {
-                if (trigOn) {
-                    // the answers that came with the event just waited for; stacks without one (retry rounds: the
-                    // search goes on behind a trigger that gave no bubble) get a launch of their own
-                    collectSearch(G);
-                    std::vector<int> ask;
-                    for (int sI : todo)
-                        if (!trigHostRoute(sI) && !stacks[sI].trigReady)
-                            ask.push_back(sI);
-                    if (!ask.empty()) {
-                        {
-                            std::lock_guard<std::mutex> lock(launchMu);
-                            hipStream_t stream = ordered ? stage1Stream.get() : G.stream.get();
-                            launchSearch(G, ask, stream);
-                            HIPOK(hipEventRecord(G.blockDone.get(), stream));
-                        }
-                        HIPOK(hipEventSynchronize(G.blockDone.get()));
-                        collectSearch(G);
-                    }
-                }
+                // trigger knob: the stacks without an answer from the event last waited for (retry rounds: the search goes
+                // on behind a trigger that gave no bubble) get a launch of their own
+                std::vector<int> ask;
+                for (int sI : devRoute(todo))
+                    if (!stacks[sI].trigReady)
+                        ask.push_back(sI);
+                if (!ask.empty())
+                    fetchBlocks(G, {}, ask, d_frames, d_sigma6);
                 pool->parallelFor((int)todo.size(), [&](int k) { triggerAndPlan(stacks[todo[k]]); });
                 std::vector<int> need;
                 for (int sI : todo) {
-                    if (trigOn && !trigHostRoute(sI) && stacks[sI].needMore)
-                        ++(stacks[sI].data.needPieces ? G.stats.trigger.needFinal : G.stats.trigger.needFrames);
-                    if (stacks[sI].needMore)
-                        need.push_back(sI);
+                    const BatchEventData &d = stacks[sI].data;
+                    if (!d.asked())
+                        continue;
+                    need.push_back(sI);
+                    if (devRoute(sI))
+                        ++(d.need.pieces ? G.stats.trigger.needFinal : G.stats.trigger.needFrames);
                 }
                 if (need.empty())
                     break;
-                fetchBlocks(G, need, d_frames, d_sigma6);
+                fetchBlocks(G, need, devRoute(need), d_frames, d_sigma6);
                 todo.swap(need);
             }
             G.stats.timing.stage2Ms += nowMs() - t2;
@@ -1588,98 +1657,38 @@ private:
     }
 
     // What the stopped searches asked for: the next frame block of a stack (one launch per block index), or the dense rows
-    // of frames of a block that is already there (one row-machine launch per launch of the block that holds them).
-    void fetchBlocks(Group &G, const std::vector<int> &need, const uint8_t *d_frames, const uint8_t *d_sigma6)
+    // of frames of a block that is already there (one row-machine launch per launch of the block that holds them); then one
+    // device search for the stacks of `ask`.  Returns when all of it is on the host: blocks arrived, answers collected.
+    void fetchBlocks(Group &G, const std::vector<int> &need, const std::vector<int> &ask, const uint8_t *d_frames,
+                     const uint8_t *d_sigma6)
     {
-        hipStream_t stream = ordered ? stage1Stream.get() : G.stream.get();
-        const int nB = (int)blocks.size() - 1;
-        std::vector<std::vector<int>> byBlock((size_t)nB);
-        std::vector<std::vector<std::vector<int>>> byFetch((size_t)nB); // [block][fetch] -> stacks that need pieces
+        hipStream_t stream = kernelStream(G);
+        // (block, its launch that holds the pieces; -1: the block itself) -> the stacks that ask for it, block by block
+        std::map<std::pair<int, int>, std::vector<int>> asked;
         for (int sI : need) {
             const BatchEventData &d = stacks[sI].data;
-            if (!d.needPieces)
-                byBlock[(size_t)d.needBlock].push_back(sI);
-            else {
-                auto &v = byFetch[(size_t)d.needBlock];
-                if (v.size() <= (size_t)d.fetchOf[d.needBlock])
-                    v.resize((size_t)d.fetchOf[d.needBlock] + 1);
-                v[(size_t)d.fetchOf[d.needBlock]].push_back(sI);
-            }
+            asked[{d.need.block, d.need.pieces ? d.ref[d.need.block].fetch : -1}].push_back(sI);
         }
-        std::vector<int> newFetch((size_t)nB, -1);
         {
             std::lock_guard<std::mutex> lock(launchMu); // (the counters, and one launch sequence at a time per pipeline)
-            for (int k = 0; k < nB; ++k) {
-                Group::Block &B = G.blocks[k];
-                if (!byBlock[k].empty()) {
-                    launchBlock(B, k, byBlock[k], d_frames, d_sigma6, stream);
-                    newFetch[k] = (int)B.fetches.size() - 1;
-                    if (trigOn)
-                        for (size_t q = 0; q < byBlock[k].size(); ++q)
-                            bindBlockDevice(B, k, stacks[byBlock[k][q]], newFetch[k], (int)q);
-                }
-                const size_t blen = (size_t)(blocks[k + 1] - blocks[k]);
-                for (size_t f = 0; f < byFetch[k].size(); ++f) {
-                    if (byFetch[k][f].empty())
-                        continue;
-                    // complete, for every asking stack, the flagged frames from the one it stopped at to the end of the block
-                    const Group::Fetch &fe = B.fetches[f];
-                    const size_t nj = (size_t)fe.n * blen, base = (size_t)fe.first * blen;
-                    uint8_t *hw = B.want.h + base;
-                    std::memset(hw, 0, nj);
-                    for (int sI : byFetch[k][f]) {
-                        BatchEventData &d = stacks[sI].data;
-                        for (size_t j = (size_t)(d.needFrame - blocks[k]); j < blen; ++j)
-                            if (d.inc[k][j]) {
-                                hw[(size_t)d.slotOf[k] * blen + j] = 1;
-                                ++stats.timing.jobsCompleted;
-                            }
-                    }
-                    B.want.toDevice(nj, stream, base);
-                    check(abub_diff_hist_pieces_dev(d_frames, d_sigma6, B.jobs.d + base, (int)nj, W, H, B.hist.d + base * 256,
-                                                    B.pieces + fe.pieceOff, B.pcount + f, B.want.d + base, stream),
-                          "trigger search K2 (pieces)");
-                    for (int sI : byFetch[k][f]) {
-                        BatchEventData &d = stacks[sI].data;
-                        const size_t j0 = (size_t)(d.needFrame - blocks[k]), o = (base + (size_t)d.slotOf[k] * blen + j0) * 256;
-                        B.hist.toHost((blen - j0) * 256, stream, o);
-                    }
-                    // final now on the device too (the host mirror of the flags is cleared below): one launch per fetch
-                    if (trigOn)
-                        check(abub_trigger_clear_pending_dev(B.inc.d + base, B.want.d + base, nj, stream), "trigger search flags");
-                }
-            }
-            if (trigOn) {
-                // the searches that asked go on right behind the launches that produce what they asked for
-                std::vector<int> dev;
-                for (int sI : need)
-                    if (!trigHostRoute(sI))
-                        dev.push_back(sI);
-                launchSearch(G, dev, stream);
-            }
+            for (const auto &a : asked)
+                if (a.first.second < 0)
+                    G.search.launchBlock(a.first.first, a.second, stacks, d_frames, d_sigma6, stream, stats);
+                else
+                    G.search.completePieces(a.first.first, a.first.second, a.second, stacks, d_frames, d_sigma6, trigOn, stream, stats);
+            // the searches that asked go on right behind the launches that produce what they asked for
+            G.search.launchSearch(ask, stacks, stream, stats);
             HIPOK(hipEventRecord(G.blockDone.get(), stream));
         }
         HIPOK(hipEventSynchronize(G.blockDone.get()));
-        for (int k = 0; k < nB; ++k) {
-            for (size_t q = 0; q < byBlock[k].size(); ++q) {
-                StackState &st_ = stacks[byBlock[k][q]];
-                bindBlock(G.blocks[k], k, st_, newFetch[k], (int)q);
-                st_.needMore = false;
-            }
-            const size_t blen = (size_t)(blocks[k + 1] - blocks[k]);
-            for (auto &v : byFetch[k])
-                for (int sI : v) {
-                    StackState &st_ = stacks[sI];
-                    for (size_t j = (size_t)(st_.data.needFrame - blocks[k]); j < blen; ++j)
-                        st_.data.inc[k][j] = 0; // final now
-                    st_.needMore = false;
-                }
-        }
+        for (int sI : need)
+            G.search.served(stacks[sI].data);
+        G.search.collectSearch(stacks, G.stats);
     }
 
     // trigger knob: what FindTriggerFrame(true, MatTrigFrame + 1) would have left in the analyzer, from the device search's
-    // answer (K6, abub_trigger.hip).  false: the search needs frames (needMore is set as NeedMoreFrames would have set it;
-    // nothing to roll back).  A look-ahead frame that cannot be decoded throws what the host search throws.
+    // answer (K6, abub_trigger.hip).  false: the search needs frames (the request is recorded as diffHist would have recorded
+    // it; nothing to roll back).  A look-ahead frame that cannot be decoded throws what the host search throws.
     bool applySearch(StackState &st_)
     {
         AnalyzerUnit *A = st_.analyzer.get();
@@ -1687,15 +1696,11 @@ private:
         const abub_trig_result r = st_.trigRes;
         st_.trigReady = false;
         if (r.state == ABUB_TRIG_NEED_FRAMES || r.state == ABUB_TRIG_NEED_FINAL) {
-            int k = 0;
-            while (k + 1 < d.nblocks && r.need_frame >= d.bstart[k + 1])
-                ++k;
-            d.needBlock = k;
-            d.needPieces = r.state == ABUB_TRIG_NEED_FINAL;
-            d.needFrame = r.need_frame;
-            if (d.needPieces ? !d.inc[k] : d.bh[k] != nullptr)
+            const int k = d.blockOf(r.need_frame);
+            const bool pieces = r.state == ABUB_TRIG_NEED_FINAL;
+            if (pieces ? !d.ref[k].deferred() : d.ref[k].launched())
                 throw std::runtime_error("RunPipeline: the device trigger search asked for a frame that is there");
-            st_.needMore = true;
+            d.request(k, r.need_frame, pieces);
             return false;
         }
         if (r.state == ABUB_TRIG_BAD_LOOKAHEAD)
@@ -1719,80 +1724,61 @@ private:
         return true;
     }
 
-    // AnyCamAnalysis body up to LocalizeOMatic (AutoBubStart3.cpp:87-107)
+    // What the host search may change in the analyzer before it runs out of evaluated frames (it only ever appends to
+    // pix_counts), taken before the search; restore() puts it back
+    struct AnalyzerSnapshot {
+        size_t pixSize[256];
+        bool havePix, ok;
+        int trig, loc, status;
+        explicit AnalyzerSnapshot(const AnalyzerUnit &A)
+            : havePix(A.pix_counts.size() == 256), ok(A.okToProceed), trig(A.MatTrigFrame), loc(A.loc_thres),
+              status(A.TriggerFrameIdentificationStatus)
+        {
+            for (int b = 0; havePix && b < 256; ++b)
+                pixSize[b] = A.pix_counts[b].size();
+        }
+        void restore(AnalyzerUnit &A) const
+        {
+            for (int b = 0; havePix && b < 256 && A.pix_counts.size() == 256; ++b)
+                A.pix_counts[b].resize(pixSize[b]);
+            A.MatTrigFrame = trig;
+            A.loc_thres = loc;
+            A.TriggerFrameIdentificationStatus = status;
+            A.okToProceed = ok;
+        }
+    };
+
+    // AnyCamAnalysis body up to LocalizeOMatic (AutoBubStart3.cpp:87-107): the search on its route, then the plan.  A search
+    // that stopped at frames that are not there leaves its request in st_.data (asked()) and the analyzer as it was
     void triggerAndPlan(StackState &st_)
     {
         st_.localize = false;
-        st_.needMore = false;
+        st_.data.clearNeed();
         AnalyzerUnit *A = st_.analyzer.get();
         try {
-            // what the search may change before it runs out of evaluated frames (it only ever appends to pix_counts)
-            size_t pixSize[256];
-            const bool havePix = A->pix_counts.size() == 256;
-            for (int b = 0; havePix && b < 256; ++b)
-                pixSize[b] = A->pix_counts[b].size();
-            const int trig0 = A->MatTrigFrame, loc0 = A->loc_thres, status0 = A->TriggerFrameIdentificationStatus;
-            const bool ok0 = A->okToProceed;
-            try {
-                if (trigOn && !trigHostRoute((int)(&st_ - stacks.data()))) {
-                    if (!st_.trigReady)
-                        throw std::runtime_error("RunPipeline: no answer of the device trigger search for this stack");
-                    if (!applySearch(st_))
-                        return;
-                } else
+            if (devRoute((int)(&st_ - stacks.data()))) {
+                if (!st_.trigReady)
+                    throw std::runtime_error("RunPipeline: no answer of the device trigger search for this stack");
+                if (!applySearch(st_))
+                    return;
+            } else {
+                const AnalyzerSnapshot before(*A);
+                try {
                     A->FindTriggerFrame(true, A->MatTrigFrame + 1);
-            } catch (NeedMoreFrames &) {
-                for (int b = 0; havePix && b < 256 && A->pix_counts.size() == 256; ++b)
-                    A->pix_counts[b].resize(pixSize[b]);
-                A->MatTrigFrame = trig0;
-                A->loc_thres = loc0;
-                A->TriggerFrameIdentificationStatus = status0;
-                A->okToProceed = ok0;
-                st_.needMore = true;
-                return;
+                } catch (NeedMoreFrames &) {
+                    before.restore(*A);
+                    return;
+                }
             }
             if (!A->okToProceed) {
                 st_.staged = A->TriggerFrameIdentificationStatus;
                 st_.done = true;
-                return;
-            }
-            const int F = st_.data.F;       // this stack's frame count (<= the pipeline's)
-            if (F <= 5) { // LocalizeOMatic refuses (L3Localizer.cpp:889) -> -8
+            } else if (st_.data.F <= 5) { // LocalizeOMatic refuses (L3Localizer.cpp:889) -> -8
                 A->LocalizeOMatic("");
                 st_.staged = -8;
                 st_.done = true;
-                return;
-            }
-            const int t = A->MatTrigFrame;
-            const int off = refOffset(A->TrainedData->TrainingSetSize);
-            st_.data.planned.clear();
-            st_.data.cur = nullptr;
-            st_.data.locReady = false;
-            st_.data.clearVeto(); // a new trigger: new veto keys
-            PlannedImage g;
-            g.kind = 0;
-            g.i = t;
-            g.ref = std::max(t - off, 0);
-            g.tozero = A->loc_thres;
-            g.slot = -1;
-            g.thr = 0;
-            g.minBox = -1; // genesis: largestBoxArea / allInBellowsMask need the small contours too
-            st_.data.planned.push_back(g);
-            const int last = (t < 29) ? NumFramesBubbleTrack : (39 - t);
-            for (int k = 1; k <= last; ++k) {
-                if (t + k >= F)
-                    break;
-                PlannedImage p;
-                p.kind = 1;
-                p.i = t + k;
-                p.ref = 0;
-                p.tozero = 3;
-                p.slot = -1;
-                p.thr = 0;
-                p.minBox = kTrackMinBoxArea;
-                st_.data.planned.push_back(p);
-            }
-            st_.localize = true;
+            } else
+                planImages(st_);
         } catch (std::exception &e) {
             st_.error = e.what();
             st_.staged = -6;
@@ -1800,14 +1786,30 @@ private:
         }
     }
 
+    // the images stage 3 makes for the trigger the search found: the genesis pair and the tracking frames behind it
+    void planImages(StackState &st_)
+    {
+        const AnalyzerUnit *A = st_.analyzer.get();
+        BatchEventData &d = st_.data;
+        const int t = A->MatTrigFrame;
+        d.planned.clear();
+        d.cur = nullptr;
+        d.locReady = false;
+        d.clearVeto(); // a new trigger: new veto keys
+        // genesis: largestBoxArea / allInBellowsMask need the small contours too
+        d.planned.push_back(
+            PlannedImage::make(0, t, std::max(t - refOffset(A->TrainedData->TrainingSetSize), 0), A->loc_thres, -1));
+        const int last = (t < 29) ? NumFramesBubbleTrack : (39 - t);
+        for (int k = 1; k <= last && t + k < d.F; ++k) // (this stack's frame count: <= the pipeline's)
+            d.planned.push_back(PlannedImage::make(1, t + k, 0, 3, kTrackMinBoxArea));
+        st_.localize = true;
+    }
+
     void batchImages(Group &G, const std::vector<int> &loc, const uint8_t *d_frames, const uint8_t *d_mu,
                      const uint8_t *d_sigma6)
     {
-        // Kernels go to `stream`, results come back on the group's own stream.  Ordered mode (default): every
-        // group's kernels queue on the one trigger-search stream, so the GPU sees K2(g0) K2(g1) .. S3(g0) S3(g1) ..
-        // strictly one kernel at a time -- chip-filling kernels launched on different streams only slow each
-        // other down -- while the host stages of group g run under the kernels of group g+1.
-        hipStream_t stream = ordered ? stage1Stream.get() : G.stream.get();
+        // Kernels go to `stream`, results come back on the group's own stream
+        hipStream_t stream = kernelStream(G);
         hipStream_t back = G.stream.get();
         // slots: all genesis images first (K2), then all post-trigger images (K3), camera-major: consecutive K3 jobs
         // then share their model, which is what lets one scanning wave serve several tracking frames (k3_zero_scan)
@@ -2165,14 +2167,9 @@ private:
             const int s = req[k].first;
             BatchEventData::ResidualMemo &r = *req[k].second;
             std::memcpy(r.hist, V.hist.h + (size_t)k * 256, sizeof(r.hist));
-            PlannedImage &p = r.img;
-            p.kind = 2;
-            p.i = r.trig;
-            p.ref = r.pre;
+            PlannedImage &p = r.img = PlannedImage::make(2, r.trig, r.pre, V.thr.h[k], -1);
             p.slot = k;
-            p.tozero = V.thr.h[k];
             p.thr = binarizeThresholdFromHist(r.hist, P, p.tozero);
-            p.minBox = -1;
             // valid until the veto's next sub-round: a ready memo is read only by the localize that directly follows
             L.bind(p, k);
             r.ready = true;
@@ -2254,7 +2251,7 @@ RunPipelinePtr newRunPipeline(int device, int W, int H, int F, int E, int C, con
 void setSigmaRaw(RunPipeline &p, const uint8_t *d_sigma) { p.d_sigmaRaw = d_sigma; }
 bool setTrainingSetSizes(RunPipeline &p, const int *tss)
 {
-    if (chainStrideOf(tss, p.C) != p.chainStride)
+    if (chainStrideOf(tss, p.C) != p.search.chainStride)
         return false;
     for (int c = 0; c < p.C; ++c) {
         p.tss[c] = tss[c];

@@ -142,6 +142,26 @@ def test_pipeline_trigger_small_blocks_and_no_deferral(oracle, monkeypatch, env)
     pipe.close()
 
 
+@pytest.mark.parametrize("ordered", ["1", "0"])
+def test_pipeline_trigger_ordered_and_unordered_groups(oracle, monkeypatch, ordered):
+    """three groups on small blocks: with ABUB_PIPE_ORDERED=0 a group's later blocks, searches and localisation kernels go
+    to the group's own stream, not to the one trigger-search stream"""
+    W, H, F, E, C_ = 1280, 96, 41, 6, 2
+    slab, models, tss = _regime_run(oracle, "post_trigger_dense", seed=720)
+    d_slab, d_mu, d_s6 = _device(slab, models)
+    env = {"ABUB_PIPE_ORDERED": ordered, "ABUB_PIPE_GROUPS": "3", "ABUB_PIPE_BLOCK0": "12", "ABUB_PIPE_BLOCK": "4"}
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    pipe = host.Pipeline(0, W, H, F, E, C_, tss, nthreads=4)
+    for k in env:
+        monkeypatch.delenv(k)
+    st_ = torch.cuda.current_stream().cuda_stream
+    res, st = _both_settings(pipe, lambda: pipe.run(d_slab, d_mu, d_s6, st_), E * C_)
+    _against_oracle(oracle, res, slab, models, tss, str(env))
+    assert st["need_frames"] > 0, st
+    pipe.close()
+
+
 def test_pipeline_trigger_env_seed_and_contours(oracle, monkeypatch):
     """ABUB_PIPE_TRIGGER=1 seeds the knob; trigger = 1 together with contours = 1"""
     W, H, F, E, C_ = 1280, 96, 41, 6, 2
