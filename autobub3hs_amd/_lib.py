@@ -80,6 +80,8 @@ SIGNATURES = {
     "abub_png_decode_dev": (_i, [_vp, _sz, _vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _sz, _vp, _sz, _vp, _sz, _vp, _vp]),
     "abub_png_raw_stride_kind": (_sz, [_i, _i, C.c_uint32]),
     "abub_png_decode_typed_dev": (_i, [_vp, _sz, _vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _vp, _vp]),
+    "abub_png_raw_stride_adam7": (_sz, [_i, _i, C.c_uint32]),
+    "abub_png_decode_adam7_dev": (_i, [_vp, _sz, _vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _sz, _vp, _sz, _sz, _vp, _sz, _vp, _vp]),
     "abub_abf_decode_dev": (_i, [_vp, _sz, _vp, _i, _i, _i, _vp, _sz, _vp, _vp]),
     "abub_bmp_decode_dev": (_i, [_vp, _sz, _vp, _i, _vp, _i, _i, _i, _vp, _sz, _vp, _vp]),
     "abub_unzip_dev": (_i, [_vp, _sz, _vp, _i, _vp, _sz, _vp, _vp]),

@@ -20,6 +20,9 @@
 // abub_png_decode_typed_dev (ABUB_GPU_PNG_TYPES=1) also takes the other non-interlaced PNG types -- 16-bit, RGB(A), grey+alpha,
 // 1/2/4-bit -- by abub_png_frame.kind: the inflate sizes each frame by its kind, k_png_unfilter_typed unfilters such a frame
 // at its own filter distance and converts it to the 8-bit grey cv::imdecode(..., 0) gives.
+// abub_png_decode_adam7_dev (ABUB_GPU_PNG_ADAM7=1) also takes Adam7-interlaced files of all these kinds (ABUB_PNG_KIND_ADAM7 in
+// abub_png_frame.kind): the inflate sizes such a frame by the scanlines of its passes, k_png_unfilter_adam7 runs one wave per
+// (frame, pass) and stores every pixel at its place in the frame.
 // Every access is bounds-checked against the sizes the caller states: the input is file content.  A frame the kernels
 // refuse (status != 0) is left to the caller, which decodes it on the host (the result is the same image or the same
 // failure: both follow RFC 1950/1951 and the PNG specification).
@@ -1117,12 +1120,48 @@ __host__ __device__ inline bool png_kind_row(uint32_t kind, int W, uint32_t &row
     return ok;
 }
 
+// Adam7 (abub_png_decode_adam7_dev; ABUB_PNG_KIND_ADAM7 in abub_png_frame.kind): pass p = 0 .. 6 of a W x H image holds the
+// pixels (y0 + r * dy, x0 + c * dx), pw x ph of them (none: the pass is not in the stream).  Its scanlines are rows of pw
+// pixels, each pass filtered on its own.
+struct Adam7Pass {
+    uint32_t x0, y0, dx, dy, pw, ph;
+};
+__host__ __device__ inline Adam7Pass png_adam7_pass(int p, uint32_t W, uint32_t H)
+{
+    Adam7Pass a; // (one hexadecimal digit per pass, pass 0 the lowest)
+    a.x0 = (0x0102040u >> (4 * p)) & 15;
+    a.y0 = (0x1020400u >> (4 * p)) & 15;
+    a.dx = (0x1224488u >> (4 * p)) & 15;
+    a.dy = (0x2244888u >> (4 * p)) & 15;
+    a.pw = W > a.x0 ? (W - a.x0 + a.dx - 1) / a.dx : 0;
+    a.ph = H > a.y0 ? (H - a.y0 + a.dy - 1) / a.dy : 0;
+    return a;
+}
+// bytes of the inflated stream in front of pass `upto` at `bits` per pixel (upto = 7: the whole stream)
+__host__ __device__ inline uint64_t png_adam7_offset(int upto, uint32_t W, uint32_t H, uint32_t bits)
+{
+    uint64_t n = 0;
+    for (int p = 0; p < upto; ++p) {
+        const Adam7Pass a = png_adam7_pass(p, W, H);
+        if (a.pw && a.ph)
+            n += (uint64_t)a.ph * (((uint64_t)a.pw * bits + 7) / 8 + 1);
+    }
+    return n;
+}
+// bits per pixel of a kind of the table, from its scanline at width 8 (a whole number of bytes for every kind)
+__host__ __device__ inline uint32_t png_kind_bits(uint32_t kind)
+{
+    uint32_t rowBytes, bpp;
+    return png_kind_row(kind, 8, rowBytes, bpp) ? rowBytes : 0;
+}
+
 // typedW != 0 (abub_png_decode_typed_dev): a frame's expected size follows from its kind, H x (row bytes + 1), and has to fit
-// rawStride; else every frame's is rawLen
+// rawStride; else every frame's is rawLen.  adam7 (abub_png_decode_adam7_dev, with typedW): a frame whose kind carries
+// ABUB_PNG_KIND_ADAM7 has the size of its passes' scanlines instead.
 template <bool TWO>
 __global__ __launch_bounds__(TWO ? 128 : 64) void k_png_inflate(const uint8_t *__restrict__ zbuf, const abub_png_frame *__restrict__ frames,
                                                                   uint32_t rawLen, uint64_t rawStride, uint8_t *__restrict__ rawbuf,
-                                                                  int32_t *__restrict__ status, int dbg, int typedW, int typedH)
+                                                                  int32_t *__restrict__ status, int dbg, int typedW, int typedH, int adam7)
 {
     __shared__ InflateLds L;
     const int f = blockIdx.x;
@@ -1139,8 +1178,11 @@ __global__ __launch_bounds__(TWO ? 128 : 64) void k_png_inflate(const uint8_t *_
     const abub_png_frame fr = frames[f];
     if (typedW) {
         uint32_t rowBytes, bpp;
-        const bool known = png_kind_row(fr.kind, typedW, rowBytes, bpp);
-        const uint64_t len = (uint64_t)typedH * ((uint64_t)rowBytes + 1);
+        const bool a7 = adam7 && (fr.kind & ABUB_PNG_KIND_ADAM7);
+        const uint32_t kind = a7 ? fr.kind & ~ABUB_PNG_KIND_ADAM7 : fr.kind;
+        const bool known = png_kind_row(kind, typedW, rowBytes, bpp);
+        const uint64_t len = a7 ? png_adam7_offset(7, (uint32_t)typedW, (uint32_t)typedH, png_kind_bits(kind))
+                                : (uint64_t)typedH * ((uint64_t)rowBytes + 1);
         if (!known || len >= (1ull << 31) || ((len + 15) & ~15ull) + 16 > rawStride) { // (uniform: one descriptor per workgroup)
             if (threadIdx.x == 0)
                 status[f] = ABUB_PNG_E_DESC;
@@ -1497,6 +1539,103 @@ __device__ __forceinline__ void png_unfilter_units(uint32_t ft, const uint8_t *_
     }
 }
 
+// How one wave works the rows of an image (a frame, or one Adam7 pass of it): rows of rowBytes bytes at filter distance bpp
+struct PngRowPlan {
+    uint32_t rowBytes, bpp, ndw; // ndw: the dwords that hold a row
+    int u0, u1, nl;              // this lane's units [u0, u1); the lanes that own units
+};
+__device__ __forceinline__ PngRowPlan png_row_plan(uint32_t rowBytes, uint32_t bpp, int lane)
+{
+    PngRowPlan P;
+    P.rowBytes = rowBytes;
+    P.bpp = bpp;
+    P.ndw = (rowBytes + 3) >> 2;
+    const int nunits = (int)(rowBytes / bpp); // (rowBytes is a multiple of bpp: bpp > 1 only from 8 bits per sample on)
+    const int chunk = (nunits + 63) / 64;
+    P.nl = chunk ? (nunits + chunk - 1) / chunk : 0;
+    P.u0 = min(lane * chunk, nunits);
+    P.u1 = min(P.u0 + chunk, nunits);
+    return P;
+}
+// The row machine of k_png_unfilter_typed and k_png_unfilter_adam7: the scanline at raw + rb (its filter type first; raw is
+// 16-byte aligned) is copied into in32 from the dwords that hold it, and cur32 becomes the unfiltered row, prev32 being the one
+// above (zeros above the first row of an image or of a pass).  false: a filter type above 4.
+__device__ __forceinline__ bool png_unfilter_row(const uint8_t *__restrict__ raw, uint64_t rb, const PngRowPlan &P, uint32_t *in32,
+                                                 const uint32_t *prev32, uint32_t *cur32, int lane)
+{
+    const uint32_t ft = rfl((uint32_t)raw[rb]);
+    const uint32_t mis = (uint32_t)((rb + 1) & 3);
+    // the dwords that hold the row's bytes (up to 3 bytes of the next row or of the padding behind the last one ride along)
+    const uint32_t *src = (const uint32_t *)(raw + ((rb + 1) & ~3ull));
+    for (uint32_t i = lane; i < (mis + P.rowBytes + 3) >> 2; i += 64)
+        in32[i] = src[i];
+    wave_sync();
+    if (ft == 0 || ft == 2) {
+        for (uint32_t i = lane; i < P.ndw; i += 64) {
+            const uint32_t v = mis ? __builtin_amdgcn_alignbyte(in32[i + 1], in32[i], mis) : in32[i];
+            cur32[i] = ft == 2 ? add4(v, prev32[i]) : v;
+        }
+    } else if (ft == 1 || ft == 3 || ft == 4) {
+        const uint8_t *in = (const uint8_t *)in32 + mis;
+        const uint8_t *prev = (const uint8_t *)prev32;
+        uint8_t *cur = (uint8_t *)cur32;
+        switch (P.bpp) {
+        case 1: png_unfilter_units<1>(ft, in, prev, cur, P.u0, P.u1, P.nl, lane); break;
+        case 2: png_unfilter_units<2>(ft, in, prev, cur, P.u0, P.u1, P.nl, lane); break;
+        case 3: png_unfilter_units<3>(ft, in, prev, cur, P.u0, P.u1, P.nl, lane); break;
+        case 4: png_unfilter_units<4>(ft, in, prev, cur, P.u0, P.u1, P.nl, lane); break;
+        case 6: png_unfilter_units<6>(ft, in, prev, cur, P.u0, P.u1, P.nl, lane); break;
+        default: png_unfilter_units<8>(ft, in, prev, cur, P.u0, P.u1, P.nl, lane); break;
+        }
+    } else
+        return false;
+    wave_sync();
+    return true;
+}
+
+// The 8-bit grey of pixel x of an unfiltered row, as cv::imdecode(..., 0) gives it
+struct PngGrey {
+    uint32_t ctype, depth, bpp;
+    uint32_t maxv, scale, perLg, per; // below 8 bits: the largest sample, 255 / it, pixels per byte (and its logarithm)
+    uint32_t k16;                     // RGB: bytes from one sample's (high) byte to the next's
+    bool pal;                         // the sample (below 8 bits) or the byte (8 bits: an Adam7 frame of kind 0) goes through `lut`
+};
+__device__ __forceinline__ PngGrey png_grey_rule(uint32_t ctype, uint32_t depth, uint32_t bpp, bool pal)
+{
+    PngGrey G;
+    G.ctype = ctype;
+    G.depth = depth;
+    G.bpp = bpp;
+    G.maxv = (1u << (depth < 8 ? depth : 8)) - 1;
+    G.scale = 255u / G.maxv;
+    G.perLg = depth == 1 ? 3 : depth == 2 ? 2 : depth == 4 ? 1 : 0;
+    G.per = 1u << G.perLg;
+    G.k16 = depth / 8;
+    G.pal = pal;
+    return G;
+}
+__device__ __forceinline__ uint32_t png_grey_at(const PngGrey &G, const uint8_t *row, const uint8_t *lut, uint32_t x)
+{
+    if (G.depth < 8) { // MSB first within a byte; the padding bits of the last byte belong to no pixel
+        const uint32_t s = (row[x >> G.perLg] >> ((G.per - 1 - (x & (G.per - 1))) * G.depth)) & G.maxv;
+        return G.pal ? (uint32_t)lut[s] : s * G.scale;
+    }
+    if (G.ctype == 0 || G.ctype == 4)
+        return G.pal ? (uint32_t)lut[row[x]] : (uint32_t)row[x * G.bpp];
+    return ((uint32_t)row[x * G.bpp] * 9797 + (uint32_t)row[x * G.bpp + G.k16] * 19234 + (uint32_t)row[x * G.bpp + 2 * G.k16] * 3737 + 16384) >> 15;
+}
+// a finished row of W pixels (a multiple of 4) -> W grey bytes at drow (4-byte aligned), four pixels per lane and store
+__device__ __forceinline__ void png_store_row(const PngGrey &G, const uint8_t *row, const uint8_t *lut, uint32_t *drow, int W, int lane)
+{
+    for (int x4 = lane; x4 < W / 4; x4 += 64) {
+        uint32_t v = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            v |= png_grey_at(G, row, lut, 4 * (uint32_t)x4 + j) << (8 * j);
+        drow[x4] = v;
+    }
+}
+
 // ldsRow: the launch's dynamic LDS holds three rows of ldsRow + 8 bytes (in dwords) and the 256-byte table
 __global__ __launch_bounds__(64) void k_png_unfilter_typed(const uint8_t *__restrict__ rawbuf, uint64_t rawStride,
                                                            const abub_png_frame *__restrict__ frames, const uint8_t *__restrict__ luts,
@@ -1506,7 +1645,8 @@ __global__ __launch_bounds__(64) void k_png_unfilter_typed(const uint8_t *__rest
     extern __shared__ uint32_t typed_lds[];
     const int f = blockIdx.x, lane = threadIdx.x;
     const abub_png_frame fr = frames[f];
-    if (fr.kind == 0 || status[f] != 0) // (kind 0: k_png_unfilter's frame)
+    // (kind 0: k_png_unfilter's frame; an Adam7 frame: k_png_unfilter_adam7's, or refused by the inflate of a typed launch)
+    if (fr.kind == 0 || (fr.kind & ABUB_PNG_KIND_ADAM7) || status[f] != 0)
         return;
     const uint32_t ctype = fr.kind & 255, depth = fr.kind >> 8;
     uint32_t rowBytes, bpp;
@@ -1530,66 +1670,15 @@ __global__ __launch_bounds__(64) void k_png_unfilter_typed(const uint8_t *__rest
     wave_sync();
     const uint8_t *raw = rawbuf + (uint64_t)f * rawStride; // 16-byte aligned; row y at y * (rowBytes + 1), its filter type first
     uint8_t *dst = out + fr.dst;
-    const int nunits = (int)(rowBytes / bpp); // (rowBytes is a multiple of bpp: bpp > 1 only from 8 bits per sample on)
-    const int chunk = (nunits + 63) / 64;
-    const int nl = (nunits + chunk - 1) / chunk;
-    const int u0 = min(lane * chunk, nunits), u1 = min(u0 + chunk, nunits);
-    const uint32_t ndw = (rowBytes + 3) >> 2;
-    const uint32_t maxv = (1u << (depth < 8 ? depth : 8)) - 1, scale = 255u / maxv;
-    const uint32_t perLg = depth == 1 ? 3 : depth == 2 ? 2 : depth == 4 ? 1 : 0, per = 1u << perLg; // pixels per byte below 8 bits
-    const uint32_t k16 = depth / 8; // RGB: bytes from one sample's (high) byte to the next's
+    const PngRowPlan P = png_row_plan(rowBytes, bpp, lane);
+    const PngGrey G = png_grey_rule(ctype, depth, bpp, pal);
     int bad = 0;
     for (int y = 0; y < H; ++y) {
-        const uint64_t rb = (uint64_t)y * ((uint64_t)rowBytes + 1);
-        const uint32_t ft = rfl((uint32_t)raw[rb]);
-        const uint32_t mis = (uint32_t)((rb + 1) & 3);
-        // the dwords that hold the row's bytes (up to 3 bytes of the next row or of the padding behind the last one ride along)
-        const uint32_t *src = (const uint32_t *)(raw + ((rb + 1) & ~3ull));
-        for (uint32_t i = lane; i < (mis + rowBytes + 3) >> 2; i += 64)
-            in32[i] = src[i];
-        wave_sync();
-        if (ft == 0 || ft == 2) {
-            for (uint32_t i = lane; i < ndw; i += 64) {
-                const uint32_t v = mis ? __builtin_amdgcn_alignbyte(in32[i + 1], in32[i], mis) : in32[i];
-                cur32[i] = ft == 2 ? add4(v, prev32[i]) : v;
-            }
-        } else if (ft == 1 || ft == 3 || ft == 4) {
-            const uint8_t *in = (const uint8_t *)in32 + mis;
-            const uint8_t *prev = (const uint8_t *)prev32;
-            uint8_t *cur = (uint8_t *)cur32;
-            switch (bpp) {
-            case 1: png_unfilter_units<1>(ft, in, prev, cur, u0, u1, nl, lane); break;
-            case 2: png_unfilter_units<2>(ft, in, prev, cur, u0, u1, nl, lane); break;
-            case 3: png_unfilter_units<3>(ft, in, prev, cur, u0, u1, nl, lane); break;
-            case 4: png_unfilter_units<4>(ft, in, prev, cur, u0, u1, nl, lane); break;
-            case 6: png_unfilter_units<6>(ft, in, prev, cur, u0, u1, nl, lane); break;
-            default: png_unfilter_units<8>(ft, in, prev, cur, u0, u1, nl, lane); break;
-            }
-        } else {
+        if (!png_unfilter_row(raw, (uint64_t)y * ((uint64_t)rowBytes + 1), P, in32, prev32, cur32, lane)) {
             bad = 1;
             break;
         }
-        wave_sync();
-        // the finished row -> W grey bytes, four pixels per lane and store
-        const uint8_t *row = (const uint8_t *)cur32;
-        uint32_t *drow = (uint32_t *)(dst + (uint64_t)y * W);
-        for (int x4 = lane; x4 < W / 4; x4 += 64) {
-            uint32_t v = 0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const uint32_t x = 4 * (uint32_t)x4 + j;
-                uint32_t g;
-                if (depth < 8) { // MSB first within a byte; the padding bits of the last byte belong to no pixel
-                    const uint32_t s = (row[x >> perLg] >> ((per - 1 - (x & (per - 1))) * depth)) & maxv;
-                    g = pal ? (uint32_t)lut[s] : s * scale;
-                } else if (ctype == 0 || ctype == 4)
-                    g = row[x * bpp];
-                else
-                    g = ((uint32_t)row[x * bpp] * 9797 + (uint32_t)row[x * bpp + k16] * 19234 + (uint32_t)row[x * bpp + 2 * k16] * 3737 + 16384) >> 15;
-                v |= g << (8 * j);
-            }
-            drow[x4] = v;
-        }
+        png_store_row(G, (const uint8_t *)cur32, lut, (uint32_t *)(dst + (uint64_t)y * W), W, lane);
         wave_sync(); // (the row has been read: the next one may overwrite the row above it)
         uint32_t *t = prev32;
         prev32 = cur32;
@@ -1597,6 +1686,81 @@ __global__ __launch_bounds__(64) void k_png_unfilter_typed(const uint8_t *__rest
     }
     if (bad && lane == 0)
         status[f] = ABUB_PNG_E_FILTER;
+}
+
+// ---- Adam7 frames: one wave per (frame, pass) -------------------------------------------------------------------------------
+// Workgroup 7 * f + p is pass p of frame f.  The passes share nothing: where a pass begins in the frame's raw bytes and its
+// pw, ph and row bytes follow from W, H and the kind; a pass without pixels returns.  The wave walks its pass's rows in order
+// with the row machine above (the row above the first row of a pass is zeros), converts with the kind's rule -- a lane per pass
+// pixel, the sub-byte extraction indexed by the pass column -- and stores every pixel as a BYTE at its place in the frame:
+// the neighbours of a pixel inside its dword belong to other waves, so no pass but the last (dx = 1: it owns whole image rows,
+// and stores dwords) writes or read-modify-writes a dword.  Every pixel of the frame belongs to exactly one pass: nothing is
+// cleared, nothing waits for another workgroup.  Up to seven waves may report for one frame: the status is written by atomicMax.
+// ldsRow as for k_png_unfilter_typed (the last pass's row is the frame's full row).
+__global__ __launch_bounds__(64) void k_png_unfilter_adam7(const uint8_t *__restrict__ rawbuf, uint64_t rawStride,
+                                                           const abub_png_frame *__restrict__ frames, const uint8_t *__restrict__ luts,
+                                                           uint32_t nluts, int W, int H, uint8_t *__restrict__ out, uint64_t out_bytes,
+                                                           int32_t *status, uint32_t ldsRow)
+{
+    extern __shared__ uint32_t adam7_lds[];
+    const int f = blockIdx.x / 7, p = blockIdx.x % 7, lane = threadIdx.x;
+    const abub_png_frame fr = frames[f];
+    // (not an Adam7 frame: the other unfilter kernels'; a nonzero status: refused by the inflate, or by a pass that ran earlier)
+    if (!(fr.kind & ABUB_PNG_KIND_ADAM7) || rfl((uint32_t)__hip_atomic_load(&status[f], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) != 0)
+        return;
+    const uint32_t kind = fr.kind & ~ABUB_PNG_KIND_ADAM7;
+    uint32_t rowBytes, bpp; // of the full row
+    const bool known = png_kind_row(kind, W, rowBytes, bpp);
+    const uint32_t bits = png_kind_bits(kind);
+    // kind 0: 8-bit grey, or 8-bit palette by `lut`
+    const uint32_t ctype = kind ? kind & 255 : 0, depth = kind ? kind >> 8 : 8;
+    const bool pal = kind ? ctype == 3 : fr.lut != 0xffffffffu;
+    if (!known || rowBytes > ldsRow || png_adam7_offset(7, (uint32_t)W, (uint32_t)H, bits) + 16 > rawStride || (fr.dst & 3) ||
+        fr.dst > out_bytes || (uint64_t)W * H > out_bytes - fr.dst || (pal && fr.lut >= nluts)) { // (uniform, and the same in all 7 passes)
+        if (lane == 0)
+            atomicMax(&status[f], (int32_t)ABUB_PNG_E_DESC);
+        return;
+    }
+    const Adam7Pass a = png_adam7_pass(p, (uint32_t)W, (uint32_t)H);
+    if (!a.pw || !a.ph)
+        return;
+    const uint32_t rowDw = (ldsRow + 11) >> 2;
+    uint32_t *const in32 = adam7_lds;
+    uint32_t *prev32 = adam7_lds + rowDw, *cur32 = adam7_lds + 2 * rowDw;
+    uint8_t *const lut = (uint8_t *)(adam7_lds + 3 * rowDw);
+    for (uint32_t i = lane; i < 3 * rowDw; i += 64) // (the row above a pass's first row is zeros)
+        adam7_lds[i] = 0;
+    if (pal)
+        for (int i = lane; i < 256; i += 64)
+            lut[i] = luts[(uint64_t)fr.lut * 256 + i];
+    wave_sync();
+    // 16-byte aligned; row r of the pass at base + r * (rbp + 1), its filter type first
+    const uint8_t *raw = rawbuf + (uint64_t)f * rawStride;
+    const uint64_t base = png_adam7_offset(p, (uint32_t)W, (uint32_t)H, bits);
+    const uint32_t rbp = (a.pw * bits + 7) / 8; // <= rowBytes
+    uint8_t *dst = out + fr.dst;
+    const PngRowPlan P = png_row_plan(rbp, bpp, lane);
+    const PngGrey G = png_grey_rule(ctype, depth, bpp, pal);
+    int bad = 0;
+    for (uint32_t r = 0; r < a.ph; ++r) {
+        if (!png_unfilter_row(raw, base + (uint64_t)r * ((uint64_t)rbp + 1), P, in32, prev32, cur32, lane)) {
+            bad = 1;
+            break;
+        }
+        const uint8_t *row = (const uint8_t *)cur32;
+        uint8_t *drow = dst + (uint64_t)(a.y0 + r * a.dy) * W + a.x0; // (y0 + r * dy < H and x0 + c * dx < W for c < pw)
+        if (a.dx == 1) // (x0 = 0, pw = W: a whole row of the image, 4-byte aligned as dst and W are)
+            png_store_row(G, row, lut, (uint32_t *)drow, W, lane);
+        else
+            for (uint32_t c = lane; c < a.pw; c += 64)
+                drow[c * a.dx] = (uint8_t)png_grey_at(G, row, lut, c);
+        wave_sync(); // (the row has been read: the next one may overwrite the row above it)
+        uint32_t *t = prev32;
+        prev32 = cur32;
+        cur32 = t;
+    }
+    if (bad && lane == 0)
+        atomicMax(&status[f], (int32_t)ABUB_PNG_E_FILTER);
 }
 
 } // namespace
@@ -1616,15 +1780,28 @@ extern "C" size_t abub_png_raw_stride_kind(int W, int H, uint32_t kind)
     return (((size_t)H * ((size_t)rowBytes + 1) + 15) & ~(size_t)15) + 16;
 }
 
-// Both entries.  typed = false: every frame is an 8-bit one whatever its descriptor's kind says, `stride` is
-// abub_png_raw_stride(W, H): the launches of abub_png_decode_dev as they always were.  typed = true: the inflate sizes every
-// frame by its kind, k_png_unfilter leaves the frames of another kind than 0 to k_png_unfilter_typed.
-static int png_decode_launch(bool typed, const uint8_t *files, size_t files_bytes, const abub_png_frame *frames, int nframes,
+extern "C" size_t abub_png_raw_stride_adam7(int W, int H, uint32_t kind)
+{
+    if (!(kind & ABUB_PNG_KIND_ADAM7))
+        return abub_png_raw_stride_kind(W, H, kind);
+    const uint32_t bits = png_kind_bits(kind & ~ABUB_PNG_KIND_ADAM7);
+    if (W <= 0 || H <= 0 || !bits)
+        return 0;
+    return (((size_t)png_adam7_offset(7, (uint32_t)W, (uint32_t)H, bits) + 15) & ~(size_t)15) + 16;
+}
+
+// The three entries.  PngPlain: every frame is an 8-bit one whatever its descriptor's kind says, `stride` is
+// abub_png_raw_stride(W, H): the launches of abub_png_decode_dev as they always were.  PngTyped: the inflate sizes every
+// frame by its kind, k_png_unfilter leaves the frames of another kind than 0 to k_png_unfilter_typed.  PngAdam7: a typed
+// launch in which the inflate sizes a frame with ABUB_PNG_KIND_ADAM7 by its passes, and k_png_unfilter_adam7 takes those frames.
+enum PngMode { PngPlain = 0, PngTyped = 1, PngAdam7 = 2 };
+static int png_decode_launch(PngMode mode, const uint8_t *files, size_t files_bytes, const abub_png_frame *frames, int nframes,
                              const abub_png_seg *segs, int nsegs, const uint8_t *luts, int nluts, int W, int H, uint8_t *zbuf,
                              size_t zbuf_bytes, uint8_t *rawbuf, size_t rawbuf_bytes, size_t stride, uint8_t *out, size_t out_bytes,
                              int32_t *status, void *stream)
 {
-    const std::string who = typed ? "abub_png_decode_typed_dev" : "abub_png_decode_dev";
+    const bool typed = mode != PngPlain;
+    const std::string who = mode == PngAdam7 ? "abub_png_decode_adam7_dev" : typed ? "abub_png_decode_typed_dev" : "abub_png_decode_dev";
     if (nframes == 0)
         return ABUB_OK;
     if (!files || !frames || !zbuf || !rawbuf || !out || !status || nframes < 0 || nsegs < 0 || nluts < 0 || (nsegs && !segs) ||
@@ -1645,11 +1822,11 @@ static int png_decode_launch(bool typed, const uint8_t *files, size_t files_byte
     static const bool oneWave = [] { const char *e = getenv("ABUB_PNG_WAVES"); return e && atoi(e) == 1; }();
     static const int dbg = [] { const char *e = getenv("ABUB_PNG_DEBUG"); return e ? atoi(e) : 0; }(); // (measurement only)
     const uint32_t rawLen = (uint32_t)((size_t)H * ((size_t)W + 1));
-    const int typedW = typed ? W : 0, typedH = typed ? H : 0;
+    const int typedW = typed ? W : 0, typedH = typed ? H : 0, adam7 = mode == PngAdam7;
     if ((oneWave || dbg) && dbg != 5)
-        k_png_inflate<false><<<nframes, 64, 0, st>>>(zbuf, frames, rawLen, (uint64_t)stride, rawbuf, status, dbg, typedW, typedH);
+        k_png_inflate<false><<<nframes, 64, 0, st>>>(zbuf, frames, rawLen, (uint64_t)stride, rawbuf, status, dbg, typedW, typedH, adam7);
     else
-        k_png_inflate<true><<<nframes, 128, 0, st>>>(zbuf, frames, rawLen, (uint64_t)stride, rawbuf, status, dbg, typedW, typedH);
+        k_png_inflate<true><<<nframes, 128, 0, st>>>(zbuf, frames, rawLen, (uint64_t)stride, rawbuf, status, dbg, typedW, typedH, adam7);
     const int ndw = (W + 255) / 256;
 #define UNF(N)                                                                                                             \
     do {                                                                                                                   \
@@ -1673,11 +1850,15 @@ static int png_decode_launch(bool typed, const uint8_t *files, size_t files_byte
 #undef UNF
     if (typed) {
         // the widest row a frame of this launch can have: the widest kind's (8 bytes per pixel), and what fits raw_stride
-        const size_t fits = (stride - 16) / (size_t)H;
+        // (an Adam7 launch: a row and its filter type are inside the passes' bytes, which are inside raw_stride - 16)
+        const size_t fits = adam7 ? stride - 16 : (stride - 16) / (size_t)H;
         const uint32_t ldsRow = (uint32_t)std::min<size_t>((size_t)8 * W, fits ? fits - 1 : 0);
         const size_t lds = (size_t)3 * ((ldsRow + 11) >> 2) * 4 + 256; // <= 49,432 bytes (W = 2048)
         k_png_unfilter_typed<<<nframes, 64, lds, st>>>(rawbuf, (uint64_t)stride, frames, luts, (uint32_t)nluts, W, H, out,
                                                        (uint64_t)out_bytes, status, ldsRow);
+        if (adam7)
+            k_png_unfilter_adam7<<<7 * nframes, 64, lds, st>>>(rawbuf, (uint64_t)stride, frames, luts, (uint32_t)nluts, W, H, out,
+                                                               (uint64_t)out_bytes, status, ldsRow);
     }
     HIPCHK(hipGetLastError());
     return ABUB_OK;
@@ -1688,7 +1869,7 @@ extern "C" int abub_png_decode_dev(const uint8_t *files, size_t files_bytes, con
                                    uint8_t *zbuf, size_t zbuf_bytes, uint8_t *rawbuf, size_t rawbuf_bytes, uint8_t *out,
                                    size_t out_bytes, int32_t *status, void *stream)
 {
-    return png_decode_launch(false, files, files_bytes, frames, nframes, segs, nsegs, luts, nluts, W, H, zbuf, zbuf_bytes, rawbuf,
+    return png_decode_launch(PngPlain, files, files_bytes, frames, nframes, segs, nsegs, luts, nluts, W, H, zbuf, zbuf_bytes, rawbuf,
                              rawbuf_bytes, abub_png_raw_stride(W, H), out, out_bytes, status, stream);
 }
 
@@ -1697,7 +1878,16 @@ extern "C" int abub_png_decode_typed_dev(const uint8_t *files, size_t files_byte
                                          uint8_t *zbuf, size_t zbuf_bytes, uint8_t *rawbuf, size_t rawbuf_bytes, size_t raw_stride,
                                          uint8_t *out, size_t out_bytes, int32_t *status, void *stream)
 {
-    return png_decode_launch(true, files, files_bytes, frames, nframes, segs, nsegs, luts, nluts, W, H, zbuf, zbuf_bytes, rawbuf,
+    return png_decode_launch(PngTyped, files, files_bytes, frames, nframes, segs, nsegs, luts, nluts, W, H, zbuf, zbuf_bytes, rawbuf,
+                             rawbuf_bytes, raw_stride, out, out_bytes, status, stream);
+}
+
+extern "C" int abub_png_decode_adam7_dev(const uint8_t *files, size_t files_bytes, const abub_png_frame *frames, int nframes,
+                                         const abub_png_seg *segs, int nsegs, const uint8_t *luts, int nluts, int W, int H,
+                                         uint8_t *zbuf, size_t zbuf_bytes, uint8_t *rawbuf, size_t rawbuf_bytes, size_t raw_stride,
+                                         uint8_t *out, size_t out_bytes, int32_t *status, void *stream)
+{
+    return png_decode_launch(PngAdam7, files, files_bytes, frames, nframes, segs, nsegs, luts, nluts, W, H, zbuf, zbuf_bytes, rawbuf,
                              rawbuf_bytes, raw_stride, out, out_bytes, status, stream);
 }
 

@@ -310,11 +310,28 @@ def png_kind(ctype, depth):
     return ctype | depth << 8 if depth in ok.get(ctype, ()) else None
 
 
-def png_parse(data, W, H, types=False):
+PNG_KIND_ADAM7 = 1 << 16  # ABUB_PNG_KIND_ADAM7
+_ADAM7 = ((0, 0, 8, 8), (4, 0, 8, 8), (0, 4, 4, 8), (2, 0, 4, 4), (0, 2, 2, 4), (1, 0, 2, 2), (0, 1, 1, 2))  # x0, y0, dx, dy
+
+
+def png_adam7_bytes(W, H, bits):
+    """Bytes of the inflated stream of an Adam7-interlaced W x H image of `bits` per pixel: the scanlines (filter type + row)
+    of the passes that have pixels."""
+    n = 0
+    for x0, y0, dx, dy in _ADAM7:
+        pw, ph = max(0, -(-(W - x0) // dx)), max(0, -(-(H - y0) // dy))
+        if pw and ph:
+            n += ph * ((pw * bits + 7) // 8 + 1)
+    return n
+
+
+def png_parse(data, W, H, types=False, adam7=False):
     """What the host does per file before the upload: walk the chunks of a PNG, -> (idat segments [(offset, length)],
     palette->grey table (bytes, 256) or None) for an 8-bit grey / 8-bit palette image of W x H without interlace, or None
     for anything the GPU path does not take (the caller decodes such a file on the host).  types=True: the typed walk
-    (host.png_walk_typed restated) -> (segments, table or None, kind) for every non-interlaced type the host decoder reads."""
+    (host.png_walk_typed restated) -> (segments, table or None, kind) for every non-interlaced type the host decoder reads.
+    adam7=True (host.png_walk_adam7 restated, types as its `typed`): an Adam7-interlaced file of a kind the walk takes anyway
+    is accepted too, -> (segments, table or None, kind) with PNG_KIND_ADAM7 set in the kind of such a file."""
     import struct
     if len(data) < 33 or data[:8] != b"\x89PNG\r\n\x1a\n":
         return None
@@ -333,28 +350,35 @@ def png_parse(data, W, H, types=False):
         elif typ == b"IEND":
             end = True
         o += 12 + ln
-    if hdr is None or not segs or hdr[0] != W or hdr[1] != H or hdr[6] != 0:
+    if hdr is None or not segs or hdr[0] != W or hdr[1] != H or not (hdr[6] == 0 or (adam7 and hdr[6] == 1)):
         return None
     kind = png_kind(hdr[3], hdr[2])
     if kind is None or (kind != 0 and not types):
         return None
-    if kind and H * ((W * PNG_SAMPLES[hdr[3]] * hdr[2] + 7) // 8 + 1) >= 1 << 31:
+    if hdr[6]:
+        if png_adam7_bytes(W, H, PNG_SAMPLES[hdr[3]] * hdr[2]) >= 1 << 31:
+            return None
+        kind |= PNG_KIND_ADAM7
+    elif kind and H * ((W * PNG_SAMPLES[hdr[3]] * hdr[2] + 7) // 8 + 1) >= 1 << 31:
         return None
     lut = None
     if hdr[3] == 3:
         n = min(len(pal or b"") // 3, 256)
         lut = bytes(((pal[3 * i] * 9797 + pal[3 * i + 1] * 19234 + pal[3 * i + 2] * 3737 + 16384) >> 15) & 255 if i < n else 0
                     for i in range(256))
-    return (segs, lut, kind) if types else (segs, lut)
+    return (segs, lut, kind) if types or adam7 else (segs, lut)
 
 
-def png_decode(files, W, H, device="cuda:0", types=False, kinds=None, dsts=None, out=None, out_bytes=None):
+def png_decode(files, W, H, device="cuda:0", types=False, kinds=None, dsts=None, out=None, out_bytes=None, adam7=False,
+               raw_stride=None):
     """files: list of bytes objects (PNG files) -> (frames u8 [n, H, W] on the device, status i32 [n] on the host).  A file
     png_parse() refuses gets status -1 and a frame left untouched (zeros).  types=True: the typed walk and
     abub_png_decode_typed_dev, the raw stride that of the widest kind among the files.  For tests of the descriptor checks
     (types=True): kinds[i] / dsts[i], where not None, replace the kind the walk found / the frame's byte offset in `out`;
     out: a u8 device tensor to decode into instead of a new one (returned as it is), out_bytes: how many of its bytes the
-    kernels are told of (what lies behind them must stay as it is)."""
+    kernels are told of (what lies behind them must stay as it is).  adam7=True: the walk with adam7 (types as its `typed`)
+    and abub_png_decode_adam7_dev, the raw stride the largest abub_png_raw_stride_adam7 among the files -- or raw_stride, for
+    tests of the stride check; kinds / dsts as with types=True."""
     import numpy as np
     n = len(files)
     frames_np = np.zeros((max(n, 1), 8), dtype=np.uint32)
@@ -364,7 +388,7 @@ def png_decode(files, W, H, device="cuda:0", types=False, kinds=None, dsts=None,
     L = _lib.lib()
     stride = int(L.abub_png_raw_stride(W, H))
     for i, data in enumerate(files):
-        parsed = png_parse(data, W, H, types)
+        parsed = png_parse(data, W, H, types, adam7)
         base = len(blob)
         dst = i * P if dsts is None or dsts[i] is None else int(dsts[i])
         if parsed is None:
@@ -373,10 +397,12 @@ def png_decode(files, W, H, device="cuda:0", types=False, kinds=None, dsts=None,
             zoff += 16
             continue
         sg, lut = parsed[:2]
-        kind = parsed[2] if types else 0
-        if types and kinds is not None and kinds[i] is not None:
+        kind = parsed[2] if types or adam7 else 0
+        if (types or adam7) and kinds is not None and kinds[i] is not None:
             kind = int(kinds[i])
-        if types:
+        if adam7:
+            stride = max(stride, int(L.abub_png_raw_stride_adam7(W, H, kind)))
+        elif types:
             stride = max(stride, int(L.abub_png_raw_stride_kind(W, H, kind)))
         zlen = sum(l for _, l in sg)
         li = 0xFFFFFFFF
@@ -389,6 +415,8 @@ def png_decode(files, W, H, device="cuda:0", types=False, kinds=None, dsts=None,
         blob += b"\0" * ((-len(blob)) % 4)
         zoff += ((zlen + 15) & ~15) + 16
     blob += b"\0" * 8
+    if adam7 and raw_stride is not None:
+        stride = int(raw_stride)
     dev = torch.device(device)
     d_files = torch.frombuffer(bytearray(blob), dtype=torch.uint8).to(dev)
     d_frames = torch.from_numpy(frames_np.view(np.int32).copy()).to(dev)
@@ -403,7 +431,12 @@ def png_decode(files, W, H, device="cuda:0", types=False, kinds=None, dsts=None,
         out = torch.zeros((max(n, 1), H, W), dtype=torch.uint8, device=dev)
     status = torch.full((max(n, 1),), 99, dtype=torch.int32, device=dev)
     nout = out.numel() if out_bytes is None else min(int(out_bytes), out.numel())
-    if types:
+    if adam7:
+        _lib.check(L.abub_png_decode_adam7_dev(_ptr(d_files), d_files.numel(), _ptr(d_frames), n, _ptr(d_segs), len(segs),
+                                               _ptr(d_luts), len(luts), W, H, _ptr(d_z), d_z.numel(), _ptr(d_raw), d_raw.numel(),
+                                               stride, _ptr(out), nout, _ptr(status), _stream()),
+                   "abub_png_decode_adam7_dev")
+    elif types:
         _lib.check(L.abub_png_decode_typed_dev(_ptr(d_files), d_files.numel(), _ptr(d_frames), n, _ptr(d_segs), len(segs),
                                                _ptr(d_luts), len(luts), W, H, _ptr(d_z), d_z.numel(), _ptr(d_raw), d_raw.numel(),
                                                stride, _ptr(out), nout, _ptr(status), _stream()),

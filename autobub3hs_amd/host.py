@@ -59,6 +59,7 @@ SIGNATURES = {
     "abh_run_verify_report": (_s, [_vp]),
     "abh_png_walk": (_i, [_u8p, _i, _i, _i, _u32p, _i, _ip, _ip, _u8p]),
     "abh_png_walk_typed": (_i, [_u8p, _i, _i, _i, _u32p, _i, _ip, _ip, _u8p, _u32p]),
+    "abh_png_walk_adam7": (_i, [_u8p, _i, _i, _i, _i, _u32p, _i, _ip, _ip, _u8p, _u32p]),
     "abh_bmp_walk": (_i, [_u8p, _i, _i, _i, _u32p, _u8p]),
     "abh_imwrite": (_i, [_s, _u8p, _i, _i]),
     "abh_write_header": (None, [_s, _s, _i, _i]),
@@ -455,6 +456,22 @@ def png_walk_typed(data, W, H, cap=4096):
     n, pal, kind = C.c_int(), C.c_int(), C.c_uint32()
     lut = np.zeros(256, np.uint8)
     if not L.abh_png_walk_typed(src.ctypes.data_as(_u8p), len(src), W, H, segs, cap, C.byref(n), C.byref(pal),
+                                lut.ctypes.data_as(_u8p), C.byref(kind)):
+        return None
+    return ([(segs[2 * i], segs[2 * i + 1]) for i in range(min(n.value, cap))], (lut.tobytes() if pal.value else None),
+            int(kind.value))
+
+
+def png_walk_adam7(data, W, H, typed=False, cap=4096):
+    """pngWalk with adam7 = true (what ABUB_GPU_PNG_ADAM7=1 sends to the GPU decoder; typed: ABUB_GPU_PNG_TYPES=1 as well):
+    as png_walk_typed, and an Adam7-interlaced file of a kind the walk takes anyway is accepted, its kind with bit 16
+    (ABUB_PNG_KIND_ADAM7) set"""
+    L = lib()
+    src = np.frombuffer(data, np.uint8)
+    segs = (C.c_uint32 * (2 * cap))()
+    n, pal, kind = C.c_int(), C.c_int(), C.c_uint32()
+    lut = np.zeros(256, np.uint8)
+    if not L.abh_png_walk_adam7(src.ctypes.data_as(_u8p), len(src), W, H, 1 if typed else 0, segs, cap, C.byref(n), C.byref(pal),
                                 lut.ctypes.data_as(_u8p), C.byref(kind)):
         return None
     return ([(segs[2 * i], segs[2 * i + 1]) for i in range(min(n.value, cap))], (lut.tobytes() if pal.value else None),

@@ -84,7 +84,10 @@ static std::string usage()
            "             results are the same\n"
            "             ABUB_GPU_PNG_TYPES=1 also decodes 16-bit, RGB(A), grey+alpha and 1/2/4-bit PNG frames on the GPU in those\n"
            "             routes (interlaced files stay with the host); unset or 0, the default, leaves them to host threads; results\n"
-           "             are the same\n";
+           "             are the same\n"
+           "             ABUB_GPU_PNG_ADAM7=1 also decodes Adam7-interlaced PNG frames on the GPU in those routes: 8-bit grey and palette\n"
+           "             files, with ABUB_GPU_PNG_TYPES=1 the other types too; unset or 0, the default, leaves them to host threads,\n"
+           "             which read interlaced files of every type; results are the same\n";
 }
 
 // cores this process may use: the affinity mask (taskset, cpuset) AND the cgroup's CPU quota (cpu.max: a container may see

@@ -379,13 +379,27 @@ int abh_png_walk(const uint8_t *data, int n, int W, int H, uint32_t *segs_out, i
     return 1;
 }
 
+static int pngWalkOut(const uint8_t *data, int n, int W, int H, bool typed, bool adam7, uint32_t *segs_out, int cap, int *nsegs,
+                      int *palette, uint8_t *lut_out, uint32_t *kind);
 // pngWalk with typed = true (ABUB_GPU_PNG_TYPES=1): also the other PNG types the host decoder reads; *kind = 0 for an 8-bit
 // grey / palette file, else colour type | bit depth << 8; the table also for a palette below 8 bits
 int abh_png_walk_typed(const uint8_t *data, int n, int W, int H, uint32_t *segs_out, int cap, int *nsegs, int *palette, uint8_t *lut_out,
                        uint32_t *kind)
 {
+    return pngWalkOut(data, n, W, H, true, false, segs_out, cap, nsegs, palette, lut_out, kind);
+}
+// pngWalk with adam7 = true (ABUB_GPU_PNG_ADAM7=1) and typed as given: also Adam7-interlaced files of the kinds the walk takes
+// anyway; *kind has ABUB_PNG_KIND_ADAM7 set for such a file
+int abh_png_walk_adam7(const uint8_t *data, int n, int W, int H, int typed, uint32_t *segs_out, int cap, int *nsegs, int *palette,
+                       uint8_t *lut_out, uint32_t *kind)
+{
+    return pngWalkOut(data, n, W, H, typed != 0, true, segs_out, cap, nsegs, palette, lut_out, kind);
+}
+static int pngWalkOut(const uint8_t *data, int n, int W, int H, bool typed, bool adam7, uint32_t *segs_out, int cap, int *nsegs,
+                      int *palette, uint8_t *lut_out, uint32_t *kind)
+{
     abub::PngInfo info;
-    if (!abub::pngWalk(data, (size_t)n, W, H, info, true))
+    if (!abub::pngWalk(data, (size_t)n, W, H, info, typed, adam7))
         return 0;
     *nsegs = (int)info.segs.size();
     for (int i = 0; i < (int)info.segs.size() && i < cap; ++i) {

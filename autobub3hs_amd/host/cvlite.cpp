@@ -16,6 +16,8 @@
 #include <dlfcn.h>
 #include <zlib.h>
 
+#include "pngwalk.hpp" // (the Adam7 geometry)
+
 namespace cv {
 
 // Optional fast path for the inflate of PNG / zip payloads: libdeflate (2-3x zlib's speed), when the system has the
@@ -132,7 +134,7 @@ static Mat decodeBMP(const uchar *buf, size_t size)
 }
 
 // ---------------------------------------------------------------------------------------------
-// PNG (non-interlaced)
+// PNG (non-interlaced and Adam7-interlaced)
 // ---------------------------------------------------------------------------------------------
 static inline int paeth(int a, int b, int c)
 {
@@ -147,9 +149,99 @@ struct PixelSink {
     void *ctx;
 };
 
+// One scanline unfiltered: `src` (rowBytes filtered bytes behind the filter type `ft`) -> rowOut; `up` is the unfiltered row
+// above (zeros for the first row of an image or of an interlace pass), bpp the filter distance.  false: a filter type above 4.
+// The filter type is constant along a row: one tight loop per type.
+static inline bool unfilterRow(int ft, const uchar *src, const uchar *up, uchar *rowOut, size_t rowBytes, size_t bpp)
+{
+    switch (ft) {
+    case 0:
+        std::memcpy(rowOut, src, rowBytes);
+        break;
+    case 1:
+        for (size_t i = 0; i < bpp && i < rowBytes; ++i)
+            rowOut[i] = src[i];
+        for (size_t i = bpp; i < rowBytes; ++i)
+            rowOut[i] = (uchar)(src[i] + rowOut[i - bpp]);
+        break;
+    case 2:
+        for (size_t i = 0; i < rowBytes; ++i)
+            rowOut[i] = (uchar)(src[i] + up[i]);
+        break;
+    case 3:
+        for (size_t i = 0; i < bpp && i < rowBytes; ++i)
+            rowOut[i] = (uchar)(src[i] + (up[i] >> 1));
+        for (size_t i = bpp; i < rowBytes; ++i)
+            rowOut[i] = (uchar)(src[i] + ((rowOut[i - bpp] + up[i]) >> 1));
+        break;
+    case 4:
+        for (size_t i = 0; i < bpp && i < rowBytes; ++i)
+            rowOut[i] = (uchar)(src[i] + up[i]); // paeth(0, b, 0) = b
+        if (bpp == 1) { // the common case, with a and c carried in registers
+            int a = rowBytes ? rowOut[0] : 0, c = rowBytes ? up[0] : 0;
+            for (size_t i = 1; i < rowBytes; ++i) {
+                const int b = up[i];
+                a = (uchar)(src[i] + paeth(a, b, c));
+                rowOut[i] = (uchar)a;
+                c = b;
+            }
+        } else {
+            for (size_t i = bpp; i < rowBytes; ++i)
+                rowOut[i] = (uchar)(src[i] + paeth(rowOut[i - bpp], up[i], up[i - bpp]));
+        }
+        break;
+    default:
+        return false;
+    }
+    return true;
+}
+
+// What the conversion of an unfiltered scanline to 8-bit grey needs to know about the image
+struct PngGrey {
+    unsigned ctype, depth;
+    int channels, npal;
+    const uchar (*pal)[3];
+    const uchar *lut; // 8-bit grey / palette: one table look-up per pixel
+};
+// The first n pixels of the unfiltered scanline `cur` -> dst[0], dst[step], ... (step 1: a row of the image; an interlace
+// pass writes every step-th pixel of its rows)
+static inline void greyRow(const PngGrey &g, const uchar *cur, unsigned n, uchar *dst, size_t step)
+{
+    const unsigned ctype = g.ctype, depth = g.depth;
+    if ((ctype == 0 || ctype == 3) && depth == 8) { // 8-bit palette (or grey through the identity table)
+        for (unsigned x = 0; x < n; ++x)
+            dst[x * step] = g.lut[cur[x]];
+        return;
+    }
+    for (unsigned x = 0; x < n; ++x) {
+        uchar &d = dst[x * step];
+        if (ctype == 0 || ctype == 3) {
+            unsigned v;
+            if (depth == 16)
+                v = cur[2 * x]; // high byte (16 -> 8 bit strip)
+            else {
+                const unsigned per = 8 / depth, shift = (per - 1 - (x % per)) * depth;
+                v = (cur[x / per] >> shift) & ((1u << depth) - 1);
+                if (ctype == 0)
+                    v = v * 255u / ((1u << depth) - 1); // expand_gray_1_2_4_to_8
+            }
+            if (ctype == 3) {
+                d = (int)v < g.npal ? png_rgb2grey(g.pal[v][0], g.pal[v][1], g.pal[v][2]) : 0;
+            } else
+                d = (uchar)v;
+        } else if (ctype == 4) {
+            d = depth == 8 ? cur[2 * x] : cur[4 * x];
+        } else { // RGB / RGBA
+            const size_t st = (size_t)g.channels * (depth / 8), k = depth / 8;
+            d = png_rgb2grey(cur[x * st], cur[x * st + k], cur[x * st + 2 * k]);
+        }
+    }
+}
+
 // PNG -> 8-bit grey.  The two large temporaries (concatenated IDAT data, inflated scanlines) are thread-local and keep
 // their capacity: a decode thread of the batched ingestion path allocates nothing per frame (per-frame megabyte
 // allocations -- mmap / munmap / page faults under one mm lock -- are what kept 128 decode threads at the rate of 16).
+// An Adam7-interlaced file is seven small images, each filtered on its own (a pass without pixels is not in the stream).
 static bool decodePNGTo(const uchar *buf, size_t size, PixelSink sink)
 {
     static const uchar sig[8] = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a};
@@ -192,7 +284,7 @@ static bool decodePNGTo(const uchar *buf, size_t size, PixelSink sink)
         }
         o += 12 + (size_t)len;
     }
-    if (!haveHdr || w == 0 || h == 0 || interlace != 0 || idat.empty())
+    if (!haveHdr || w == 0 || h == 0 || interlace > 1 || idat.empty())
         return false;
     int channels;
     switch (ctype) {
@@ -212,9 +304,11 @@ static bool decodePNGTo(const uchar *buf, size_t size, PixelSink sink)
     const size_t bitsPerPixel = (size_t)channels * depth;
     const size_t rowBytes = ((size_t)w * bitsPerPixel + 7) / 8;
     const size_t bpp = bitsPerPixel >= 8 ? bitsPerPixel / 8 : 1; // filter distance
-    if (raw.size() < (rowBytes + 1) * (size_t)h)
-        raw.resize((rowBytes + 1) * (size_t)h);
-    if (!inflateZlibStream(idat.data(), idat.size(), raw.data(), (rowBytes + 1) * (size_t)h))
+    // the inflated stream: h scanlines, or the scanlines of the passes that have pixels
+    const size_t rawLen = interlace ? (size_t)abub::pngAdam7Bytes(w, h, bitsPerPixel) : (rowBytes + 1) * (size_t)h;
+    if (raw.size() < rawLen)
+        raw.resize(rawLen);
+    if (!inflateZlibStream(idat.data(), idat.size(), raw.data(), rawLen))
         return false;
     uchar *const base = sink.get(sink.ctx, w, h);
     if (!base)
@@ -223,89 +317,36 @@ static bool decodePNGTo(const uchar *buf, size_t size, PixelSink sink)
     uchar lut[256];
     for (int v = 0; v < 256; ++v)
         lut[v] = ctype == 3 ? (v < npal ? png_rgb2grey(pal[v][0], pal[v][1], pal[v][2]) : 0) : (uchar)v;
-    const bool direct8 = ctype == 0 && depth == 8; // rows can be unfiltered straight into the output image
+    const PngGrey grey = {ctype, depth, channels, npal, pal, lut};
     std::vector<uchar> prev(rowBytes, 0), cur(rowBytes);
     std::vector<uchar> zero(rowBytes, 0);
+    if (interlace) {
+        const uchar *src = raw.data();
+        for (int p = 0; p < 7; ++p) {
+            const abub::Adam7Pass a = abub::adam7Pass(p, w, h);
+            if (!a.pw || !a.ph)
+                continue;
+            const size_t rb = (size_t)((a.pw * bitsPerPixel + 7) / 8);
+            for (size_t r = 0; r < a.ph; ++r, src += rb + 1) {
+                if (!unfilterRow(src[0], src + 1, r == 0 ? zero.data() : prev.data(), cur.data(), rb, bpp))
+                    return false;
+                greyRow(grey, cur.data(), (unsigned)a.pw, base + (size_t)(a.y0 + r * a.dy) * w + a.x0, (size_t)a.dx);
+                prev.swap(cur);
+            }
+        }
+        return true;
+    }
+    const bool direct8 = ctype == 0 && depth == 8; // rows can be unfiltered straight into the output image
     for (unsigned y = 0; y < h; ++y) {
         const uchar *src = raw.data() + (rowBytes + 1) * (size_t)y;
-        const int ft = src[0];
-        ++src;
-        // the filter type is constant along a row: one tight loop per type (the row above is `up`, zeros for row 0)
+        // (the row above is `up`, zeros for row 0)
         uchar *rowOut = direct8 ? (base + (size_t)y * w) : cur.data();
         const uchar *up = y == 0 ? zero.data() : (direct8 ? (base + (size_t)(y - 1) * w) : prev.data());
-        switch (ft) {
-        case 0:
-            std::memcpy(rowOut, src, rowBytes);
-            break;
-        case 1:
-            for (size_t i = 0; i < bpp && i < rowBytes; ++i)
-                rowOut[i] = src[i];
-            for (size_t i = bpp; i < rowBytes; ++i)
-                rowOut[i] = (uchar)(src[i] + rowOut[i - bpp]);
-            break;
-        case 2:
-            for (size_t i = 0; i < rowBytes; ++i)
-                rowOut[i] = (uchar)(src[i] + up[i]);
-            break;
-        case 3:
-            for (size_t i = 0; i < bpp && i < rowBytes; ++i)
-                rowOut[i] = (uchar)(src[i] + (up[i] >> 1));
-            for (size_t i = bpp; i < rowBytes; ++i)
-                rowOut[i] = (uchar)(src[i] + ((rowOut[i - bpp] + up[i]) >> 1));
-            break;
-        case 4:
-            for (size_t i = 0; i < bpp && i < rowBytes; ++i)
-                rowOut[i] = (uchar)(src[i] + up[i]); // paeth(0, b, 0) = b
-            if (bpp == 1) { // the common case, with a and c carried in registers
-                int a = rowBytes ? rowOut[0] : 0, c = rowBytes ? up[0] : 0;
-                for (size_t i = 1; i < rowBytes; ++i) {
-                    const int b = up[i];
-                    a = (uchar)(src[i] + paeth(a, b, c));
-                    rowOut[i] = (uchar)a;
-                    c = b;
-                }
-            } else {
-                for (size_t i = bpp; i < rowBytes; ++i)
-                    rowOut[i] = (uchar)(src[i] + paeth(rowOut[i - bpp], up[i], up[i - bpp]));
-            }
-            break;
-        default:
+        if (!unfilterRow(src[0], src + 1, up, rowOut, rowBytes, bpp))
             return false;
-        }
         if (direct8)
             continue;
-        if ((ctype == 0 || ctype == 3) && depth == 8) { // 8-bit palette (or grey through the identity table)
-            uchar *d8 = (base + (size_t)y * w);
-            for (unsigned x = 0; x < w; ++x)
-                d8[x] = lut[cur[x]];
-            prev.swap(cur);
-            continue;
-        }
-        uchar *dst = (base + (size_t)y * w);
-        for (unsigned x = 0; x < w; ++x) {
-            if (ctype == 0 || ctype == 3) {
-                unsigned v;
-                if (depth == 8)
-                    v = cur[x];
-                else if (depth == 16)
-                    v = cur[2 * x]; // high byte (16 -> 8 bit strip)
-                else {
-                    const unsigned per = 8 / depth, shift = (per - 1 - (x % per)) * depth;
-                    v = (cur[x / per] >> shift) & ((1u << depth) - 1);
-                    if (ctype == 0)
-                        v = v * 255u / ((1u << depth) - 1); // expand_gray_1_2_4_to_8
-                }
-                if (ctype == 3) {
-                    dst[x] = (int)v < npal ? png_rgb2grey(pal[v][0], pal[v][1], pal[v][2]) : 0;
-                } else
-                    dst[x] = (uchar)v;
-            } else if (ctype == 4) {
-                dst[x] = depth == 8 ? cur[2 * x] : cur[4 * x];
-            } else { // RGB / RGBA
-                const size_t step = (size_t)channels * (depth / 8), k = depth / 8;
-                dst[x] = png_rgb2grey(cur[x * step], cur[x * step + k], cur[x * step + 2 * k]);
-            }
-        }
+        greyRow(grey, cur.data(), w, base + (size_t)y * w, 1);
         prev.swap(cur);
     }
     return true;

@@ -3,7 +3,7 @@
 // routes of repack, unpack and verify.  A host thread reads each file; a packed frame ("ABF1") whose header is valid for
 // W x H goes to the packed decoder as it is, a PNG has its chunks walked (pngWalk), a BMP its header (bmpWalk, with
 // ABUB_GPU_BMP=1; by default BMP files stay with the reading thread); a file none of them takes
-// (16-bit, colour or interlaced PNG -- with ABUB_GPU_PNG_TYPES=1 only the interlaced ones --, compressed BMP, another size)
+// (16-bit, colour or interlaced PNG -- ABUB_GPU_PNG_TYPES=1 and ABUB_GPU_PNG_ADAM7=1 take those too --, compressed BMP, another size)
 // gets the host decoder's answer at once, and so does a
 // frame a kernel later returns a nonzero status for.  Each decoder is one lane (GpuCodec) of a batch: the placement of its
 // frames, its descriptors, its status buffers and its count are indexed by it, and launch and finish loop over the lanes.
@@ -204,12 +204,21 @@ inline bool gpuPngTypesEnabled()
     return e && atoi(e) != 0;
 }
 
+// ABUB_GPU_PNG_ADAM7=1: the PNG lane also takes Adam7-interlaced files of the kinds it takes anyway (8-bit grey / palette; with
+// ABUB_GPU_PNG_TYPES=1 the 13 others too; abub_png_decode_adam7_dev).  Off by default: an interlaced file stays with the reading
+// threads, whose decoder reads it ("Interlaced PNG").
+inline bool gpuPngAdam7Enabled()
+{
+    const char *e = getenv("ABUB_GPU_PNG_ADAM7");
+    return e && atoi(e) != 0;
+}
+
 // Does a GPU decoder take the W x H file?  Which one, and what its walk found, into t
 inline bool gpuCodecOf(const uint8_t *data, size_t size, int W, int H, FileTask &t)
 {
     if (packedFrameOf(data, size, W, H)) // (the file goes up as it is; the kernel checks the rest)
         t.codec = GpuPacked;
-    else if (pngWalk(data, size, W, H, t.info, gpuPngTypesEnabled()))
+    else if (pngWalk(data, size, W, H, t.info, gpuPngTypesEnabled(), gpuPngAdam7Enabled()))
         t.codec = GpuPng;
     else if (gpuBmpEnabled() && bmpWalk(data, size, W, H, t.bmp))
         t.codec = GpuBmp;
@@ -457,19 +466,27 @@ inline void launchFileDecode(const FileDescs &r, const uint8_t *d_files, int W, 
             HIPOK(hipMemcpyAsync(l.luts.get(), luts.data(), luts.size(), hipMemcpyHostToDevice, stream));
         int32_t *status = (int32_t *)l.status.get();
         if (c == GpuPng) {
-            // typed frames (ABUB_GPU_PNG_TYPES=1) among them: every frame gets the raw bytes of the widest kind present
-            bool typed = false;
+            // typed frames (ABUB_GPU_PNG_TYPES=1) or interlaced ones (ABUB_GPU_PNG_ADAM7=1) among them: every frame gets the
+            // raw bytes of the largest kind present
+            bool typed = false, adam7 = false;
             size_t stride = abub_png_raw_stride(W, H);
             for (const abub_png_frame &d : r.png)
                 if (d.kind) {
                     typed = true;
-                    stride = std::max(stride, abub_png_raw_stride_kind(W, H, d.kind));
+                    adam7 |= (d.kind & ABUB_PNG_KIND_ADAM7) != 0;
+                    stride = std::max(stride, abub_png_raw_stride_adam7(W, H, d.kind));
                 }
             sc.z.grow(r.zbytes);
             sc.raw.grow((size_t)nf * stride);
             sc.segs.grow(r.segs.size() * sizeof(abub_png_seg) + 8);
             HIPOK(hipMemcpyAsync(sc.segs.get(), r.segs.data(), r.segs.size() * sizeof(abub_png_seg), hipMemcpyHostToDevice, stream));
-            if (typed)
+            if (adam7)
+                check(abub_png_decode_adam7_dev(d_files, r.bytes, (const abub_png_frame *)l.desc.get(), nf,
+                                                (const abub_png_seg *)sc.segs.get(), (int)r.segs.size(), l.luts.get(),
+                                                (int)(luts.size() / 256), W, H, sc.z.get(), sc.z.capacity(), sc.raw.get(),
+                                                sc.raw.capacity(), stride, out, out_bytes, status, stream),
+                      "abub_png_decode_adam7_dev");
+            else if (typed)
                 check(abub_png_decode_typed_dev(d_files, r.bytes, (const abub_png_frame *)l.desc.get(), nf,
                                                 (const abub_png_seg *)sc.segs.get(), (int)r.segs.size(), l.luts.get(),
                                                 (int)(luts.size() / 256), W, H, sc.z.get(), sc.z.capacity(), sc.raw.get(),

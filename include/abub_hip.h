@@ -491,7 +491,12 @@ int abub_ctx_fetch_image(abub_ctx *ctx, uint8_t *out);
  * 8-bit grey and 8-bit palette images without interlace, any filter type, any deflate block type; a frame the kernels
  * refuse gets a positive status (below) and is left as it is -- the caller decodes such a frame on the host.
  * abub_png_decode_typed_dev also takes the other non-interlaced PNG types (abub_png_frame.kind) and gives their 8-bit grey
- * value as cv::imdecode(..., 0) does.  All pointers are device pointers; nothing here reads host memory. */
+ * value as cv::imdecode(..., 0) does.  abub_png_decode_adam7_dev (ABUB_GPU_PNG_ADAM7=1, off by default) also takes
+ * Adam7-interlaced files of all 15 kinds (ABUB_PNG_KIND_ADAM7 in abub_png_frame.kind): the inflated stream is the scanlines of
+ * the passes that have pixels, each pass filtered on its own; k_png_unfilter_adam7 runs one wave per (frame, pass) and stores
+ * every pixel once, at its place in the frame.  The host decoder (cv::imdecode, cvlite.cpp) reads the same files and is the
+ * definition (tests/test_png_adam7.py, tests/test_gpu_adam7.py, tests/test_gpu_adam7_routes.py).  The width limit is that of
+ * the other entries.  All pointers are device pointers; nothing here reads host memory. */
 typedef struct abub_png_seg {
     uint32_t off; /* byte offset of an IDAT chunk's DATA in `files` */
     uint32_t len; /* its length */
@@ -507,9 +512,12 @@ typedef struct abub_png_frame {
     uint32_t kind;      /* 0: an 8-bit image, grey or palette by `lut` (abub_png_decode_dev reads nothing else here).
                            abub_png_decode_typed_dev: colour type | bit depth << 8 of one of the 13 typed kinds --
                            grey (0) at 1, 2, 4, 16 bits, palette (3) at 1, 2, 4 (`lut`: the table, its entries past the
-                           palette 0), grey+alpha (4), RGB (2) and RGBA (6) at 8 and 16; `lut` is ignored elsewhere */
+                           palette 0), grey+alpha (4), RGB (2) and RGBA (6) at 8 and 16; `lut` is ignored elsewhere.
+                           abub_png_decode_adam7_dev: any of these 15 values, with ABUB_PNG_KIND_ADAM7 or-ed in for an
+                           Adam7-interlaced file (kind 0 with the flag: 8-bit grey, or 8-bit palette by `lut`) */
     uint64_t dst;       /* byte offset of the decoded W*H frame from `out` (a multiple of 4) */
 } abub_png_frame;
+#define ABUB_PNG_KIND_ADAM7 (1u << 16) /* abub_png_frame.kind: the file is Adam7-interlaced (abub_png_decode_adam7_dev only) */
 /* status[frame] after abub_png_decode_dev: 0 = decoded */
 #define ABUB_PNG_E_DESC 1       /* descriptor out of the stated buffer sizes */
 #define ABUB_PNG_E_HEADER 2     /* zlib header (RFC 1950) */
@@ -521,7 +529,8 @@ typedef struct abub_png_frame {
 #define ABUB_PNG_E_NOEOB 8      /* no end-of-block code */
 #define ABUB_PNG_E_CODE 9       /* invalid literal/length or distance code in the data */
 #define ABUB_PNG_E_DISTANCE 10  /* distance reaches before the start of the output */
-#define ABUB_PNG_E_TOOMUCH 11   /* more than H*(W+1) bytes (a typed frame: more than H*(its row bytes + 1)) */
+#define ABUB_PNG_E_TOOMUCH 11   /* more than H*(W+1) bytes (a typed frame: more than H*(its row bytes + 1); an Adam7 frame:
+                                   more than the scanlines of its passes) */
 #define ABUB_PNG_E_TOOLITTLE 12 /* fewer */
 #define ABUB_PNG_E_ADLER 13     /* Adler-32 of the output differs from the trailer */
 #define ABUB_PNG_E_FILTER 14    /* filter type above 4 */
@@ -544,6 +553,22 @@ size_t abub_png_raw_stride_kind(int W, int H, uint32_t kind);
  * distance and converted to grey by a kernel of their own.  ABUB_PNG_E_DESC also for a kind outside the table and for a
  * frame whose scanlines do not fit raw_stride; TOOMUCH / TOOLITTLE are relative to the frame's own size. */
 int abub_png_decode_typed_dev(const uint8_t *files, size_t files_bytes, const abub_png_frame *frames, int nframes,
+                              const abub_png_seg *segs, int nsegs, const uint8_t *luts, int nluts, int W, int H,
+                              uint8_t *zbuf, size_t zbuf_bytes, uint8_t *rawbuf, size_t rawbuf_bytes, size_t raw_stride,
+                              uint8_t *out, size_t out_bytes, int32_t *status, void *stream);
+/* Adam7 frames.  Bytes of `rawbuf` a frame of `kind` takes.  With ABUB_PNG_KIND_ADAM7 set: the scanlines of the seven passes,
+ * sum over the passes with pixels of ph * (ceil(pw * samples * depth / 8) + 1) (pass p: origin (x0, y0), step (dx, dy), pw =
+ * ceil((W - x0) / dx) or 0, ph likewise), rounded up to 16, plus 16.  Without it: abub_png_raw_stride_kind(W, H, kind).  0 for
+ * a kind outside the table. */
+size_t abub_png_raw_stride_adam7(int W, int H, uint32_t kind);
+/* abub_png_decode_typed_dev with ABUB_PNG_KIND_ADAM7 honoured (in the two other entries a kind with that bit is what it always
+ * was: ignored by abub_png_decode_dev, ABUB_PNG_E_DESC in abub_png_decode_typed_dev).  raw_stride: the largest
+ * abub_png_raw_stride_adam7 among the launch's frames.  Frames without the flag go through the kernels of a typed launch.  A
+ * flagged frame is inflated to the size of its passes (TOOMUCH / TOOLITTLE are relative to it) and unfiltered, converted and
+ * stored by k_png_unfilter_adam7, one wave per pass; every pixel of the frame is written exactly once, so a decoded frame needs
+ * no clearing, and a refused one (any positive status; ABUB_PNG_E_FILTER from any pass) may be partly written.
+ * ABUB_PNG_E_DESC as in a typed launch, the frame's passes in place of its scanlines. */
+int abub_png_decode_adam7_dev(const uint8_t *files, size_t files_bytes, const abub_png_frame *frames, int nframes,
                               const abub_png_seg *segs, int nsegs, const uint8_t *luts, int nluts, int W, int H,
                               uint8_t *zbuf, size_t zbuf_bytes, uint8_t *rawbuf, size_t rawbuf_bytes, size_t raw_stride,
                               uint8_t *out, size_t out_bytes, int32_t *status, void *stream);
