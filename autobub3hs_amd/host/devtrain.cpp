@@ -111,44 +111,29 @@ int TrainOnDevice(Parser *parser, const std::vector<std::string> &EventList, std
     const std::vector<uint8_t> &good = batch.good;
     std::vector<uint8_t> otherSize(nslots, 0);
     std::vector<std::string> frameError(nslots);
-    size_t &total = batch.total;
-    tasks.clear();
-    total = 0;
     std::fill(batch.decodedBy, batch.decodedBy + NGpuCodecs, 0);
     batch.hostDecoded = 0;
-    batch.unzip.begin();
+    batch.begin();
     if (W) {
         batch.sizer.reset(parser->clone());
-        for (int c = 0; c < C; ++c) {
-            if (!camError[c].empty())
-                continue;
-            for (int e = 0; e < E; ++e)
+        for (int c = 0; c < C; ++c)
+            for (int e = 0; e < E && camError[c].empty(); ++e)
                 for (int q = 0; q < Q; ++q)
                     if (const std::string *n = nameOf(c, e, q)) {
-                        FileTask t;
-                        t.s = (c * E + e) * Q + q;
-                        if (devDecode) {
-                            planFileTask(*batch.sizer, EventList[e], *n, t, total);
-                            batch.unzip.plan(*batch.sizer, EventList[e], *n, t);
-                        }
-                        if (!devDecode || t.state == FileTask::Bad)
+                        FileTask &t = batch.plan((c * E + e) * Q + q, 0, EventList[e], *n, devDecode);
+                        if (t.state == FileTask::Bad)
                             t.state = FileTask::Other; // decoded by GetImage below (a parser that has no files to hand out)
-                        tasks.push_back(std::move(t));
                     }
-        }
     }
-    PinnedBuffer &h_files = batch.h_files;
-    if (total)
-        h_files.grow(total + 16);
-    batch.unzip.ready();
+    batch.ready();
     const auto readOne = [&](Parser &p, size_t i) {
         FileTask &t = tasks[i];
         const int c = t.s / (E * Q), e = t.s / Q % E, q = t.s % Q;
         const std::string &n = *nameOf(c, e, q);
         if (t.state != FileTask::Other) {
-            readFileTask(p, EventList[e], n, t, h_files.get(), W, H, batch.unzip.comp());
+            batch.read(p, i, EventList[e], n, W, H);
             if (t.state == FileTask::Bad && t.read) { // refused at W x H: a frame of another size is not a corrupt one
-                cv::Mat m = cv::imdecode(h_files.get() + t.off, (size_t)t.size, 0);
+                cv::Mat m = cv::imdecode(batch.h_files.get() + t.off, (size_t)t.size, 0);
                 otherSize[t.s] = !m.empty() && (m.cols != W || m.rows != H);
             }
             return;
@@ -170,10 +155,6 @@ int TrainOnDevice(Parser *parser, const std::vector<std::string> &EventList, std
         }
     };
     forEachTask(parser, nthr, tasks.size(), readOne);
-    if (batch.unzip.comp()) {
-        HIPOK(hipSetDevice(opt.device));
-        batch.inflate(parser, nthr, B.stream.get(), readOne);
-    }
 
     DeviceTrainStats st;
     st.slabBytes = slab;
@@ -181,6 +162,7 @@ int TrainOnDevice(Parser *parser, const std::vector<std::string> &EventList, std
     if (W) {
         HIPOK(hipSetDevice(opt.device));
         hipStream_t cs = B.stream.get();
+        batch.inflate(parser, nthr, cs, readOne);
         batch.reset(nslots, slab);
         HIPOK(hipMemsetAsync(batch.slab.get(), 0, slab, cs)); // (frames nobody decodes stay zero)
         batch.upload(cs);

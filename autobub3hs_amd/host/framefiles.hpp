@@ -7,11 +7,21 @@
 // gets the host decoder's answer at once, and so does a
 // frame a kernel later returns a nonzero status for.  Each decoder is one lane (GpuCodec) of a batch: the placement of its
 // frames, its descriptors, its status buffers and its count are indexed by it, and launch and finish loop over the lanes.
-// FileBatch is the unit "one set of files on the device, decoded into one slab" of device training, repack, unpack and
-// verify; RunBatched keeps its own slots (its upload runs on the look-ahead thread) and uses the lanes.  The decoders'
-// width gate, the batch size and the ABUB_GPU_DECODE override are one copy here.  With ABUB_GPU_UNZIP=1 the zip layer of a
-// deflated archive entry is inflated on the device between the read and the walk (GpuUnzip, abub_unzip_dev).  Internal to the
-// host library.
+// The decoders' width gate, the batch size and the ABUB_GPU_DECODE override are one copy here.  With ABUB_GPU_UNZIP=1 the
+// zip layer of a deflated archive entry is inflated on the device between the read and the walk (GpuUnzip, abub_unzip_dev).
+//
+// FileBatch is the one way a route reads files for the decoders, and the protocol is its calls, in this order:
+//   begin()              no tasks; the opt-in knobs (DecodeKnobs) are read from the environment, once per batch
+//   plan(s, f, ...)      appends a task: the file's size and place, and its place in the inflate stage; a task the route does
+//                        not want read stays Other (its own work) or is set Bad
+//   ready()              the pinned buffers
+//   read(parser, i, ...) inside the route's pool function, which then deals with what came out (OnGpu, HostDecoded, Bad);
+//                        false: the task waits for the inflate, the pool function returns and is called for it once more
+//   inflate(..., fn)     the device's inflate, then the pool function `fn` once more over pending() (verify, whose pool
+//                        runs over pairs, calls inflateOnDevice on both sides and makes that round itself)
+//   upload; launch, finish   over all tasks or per range of them, into the batch's own slab; or describe, launchInto, finishInto
+//                        with the caller's output and scratch (RunBatched: two slots share a scratch and own their frames)
+// Internal to the host library.
 #ifndef ABUB3HS_FRAMEFILES_HPP
 #define ABUB3HS_FRAMEFILES_HPP
 
@@ -32,6 +42,7 @@
 #include "ParseFolder/Parser.hpp"
 #include "abub_hip.h"
 #include "bmpwalk.hpp"
+#include "decodeknobs.hpp"
 #include "devctx.hpp"
 #include "holders.hpp"
 #include "pipeline.hpp"
@@ -101,7 +112,7 @@ inline size_t framesPerBatch(int device)
 
 // One frame to be read: where it goes is decided by the caller (s, f); `state` says what became of it
 struct FileTask {
-    // Planned: to be read (planFileTask); OnGpu: read and taken by the decoder `codec`; Other: not a file task (the
+    // Planned: to be read (FileBatch::plan); OnGpu: read and taken by the decoder `codec`; Other: not a file task (the
     // caller's own work)
     enum { Planned = 0, HostDecoded = 1, Bad = 2, Other = 3, OnGpu = 4 };
     bool onGpu() const { return state == OnGpu; }
@@ -168,17 +179,6 @@ struct FileDescs {
     }
 };
 
-// The file's size and its place in the buffer (`total` grows by the file rounded up to 16 bytes); Bad if the parser
-// cannot hand it out
-inline void planFileTask(Parser &sizer, const std::string &ev, const std::string &name, FileTask &t, size_t &total)
-{
-    t.size = sizer.GetImageFileSize(ev, name);
-    t.state = (t.size > 0 && t.size < ((long long)1 << 30)) ? FileTask::Planned : FileTask::Bad;
-    t.off = total;
-    if (t.state == FileTask::Planned)
-        total += ((size_t)t.size + 15) & ~(size_t)15;
-}
-
 // a packed frame ("ABF1") whose header is valid for W x H: one for abub_abf_decode_dev
 inline bool packedFrameOf(const uint8_t *data, size_t size, int W, int H)
 {
@@ -186,127 +186,43 @@ inline bool packedFrameOf(const uint8_t *data, size_t size, int W, int H)
     return cv::abfProbe(data, size, &w, &h) && w == W && h == H;
 }
 
-// ABUB_GPU_BMP=1: BMP files go to the GPU decoder.  Off by default (BMP files stay with the reading threads, RunBatched's
-// probe does not accept them): results are the same, but the batched run of a BMP directory measured slower with it
-// than without ("BMP frames on the GPU").
-inline bool gpuBmpEnabled()
-{
-    const char *e = getenv("ABUB_GPU_BMP");
-    return e && atoi(e) != 0;
-}
-
-// ABUB_GPU_PNG_TYPES=1: the PNG lane also takes 16-bit, colour, grey+alpha and sub-byte files (every non-interlaced type
-// the host decoder reads; abub_png_decode_typed_dev).  Off by default: such files stay with the reading threads (DESIGN
-// section 3, "PNG types on the GPU").
-inline bool gpuPngTypesEnabled()
-{
-    const char *e = getenv("ABUB_GPU_PNG_TYPES");
-    return e && atoi(e) != 0;
-}
-
-// ABUB_GPU_PNG_ADAM7=1: the PNG lane also takes Adam7-interlaced files of the kinds it takes anyway (8-bit grey / palette; with
-// ABUB_GPU_PNG_TYPES=1 the 13 others too; abub_png_decode_adam7_dev).  Off by default: an interlaced file stays with the reading
-// threads, whose decoder reads it ("Interlaced PNG").
-inline bool gpuPngAdam7Enabled()
-{
-    const char *e = getenv("ABUB_GPU_PNG_ADAM7");
-    return e && atoi(e) != 0;
-}
-
 // Does a GPU decoder take the W x H file?  Which one, and what its walk found, into t
-inline bool gpuCodecOf(const uint8_t *data, size_t size, int W, int H, FileTask &t)
+inline bool gpuCodecOf(const uint8_t *data, size_t size, int W, int H, FileTask &t, const DecodeKnobs &knobs)
 {
     if (packedFrameOf(data, size, W, H)) // (the file goes up as it is; the kernel checks the rest)
         t.codec = GpuPacked;
-    else if (pngWalk(data, size, W, H, t.info, gpuPngTypesEnabled(), gpuPngAdam7Enabled()))
+    else if (pngWalk(data, size, W, H, t.info, knobs.pngTypes, knobs.pngAdam7))
         t.codec = GpuPng;
-    else if (gpuBmpEnabled() && bmpWalk(data, size, W, H, t.bmp))
+    else if (knobs.bmp && bmpWalk(data, size, W, H, t.bmp))
         t.codec = GpuBmp;
     else
         return false;
     return true;
 }
 
-// On a pool thread: the file into files + t.off, walked for the W x H GPU decoder, else decoded here.  A task planned for
-// the device's inflate (t.zip, `comp` = the compressed buffer) only has its compressed bytes read and stays Planned; the
-// same call once more after GpuUnzip::run does the rest (the file is in place: ZipInflated) or all of it (ZipNone).
-inline void readFileTask(Parser &p, const std::string &ev, const std::string &name, FileTask &t, uint8_t *files, int W, int H,
-                         uint8_t *comp = nullptr)
-{
-    if (t.state != FileTask::Planned || t.zip == FileTask::ZipRead)
-        return;
-    uint8_t *dst = files + t.off;
-    long long got = -1;
-    if (t.zip == FileTask::ZipPlanned) {
-        try {
-            got = comp ? p.ReadImageEntryRaw(ev, name, comp + t.coff, t.clen) : -1;
-        } catch (...) {
-            got = -1;
-        }
-        t.zip = got == (long long)t.clen ? FileTask::ZipRead : FileTask::ZipNone;
-        if (t.zip == FileTask::ZipRead)
-            return;
-    }
-    if (t.zip == FileTask::ZipInflated)
-        got = t.size;
-    else
-        try {
-            got = p.ReadImageFile(ev, name, dst, (size_t)t.size);
-        } catch (...) {
-            got = -1;
-        }
-    if (got != t.size) {
-        t.state = FileTask::Bad;
-        return;
-    }
-    t.read = true;
-    try {
-        if (gpuCodecOf(dst, (size_t)t.size, W, H, t)) {
-            t.state = FileTask::OnGpu;
-            return;
-        }
-        // not a file for the GPU decoders (16-bit, colour, interlaced, another size): the host decoder's answer
-        t.pix.resize((size_t)W * H);
-        t.state = cv::imdecodeInto(dst, (size_t)t.size, t.pix.data(), W, H) ? FileTask::HostDecoded : FileTask::Bad;
-    } catch (...) { // (an allocation that fails inside a pool thread must not end the batch)
-        t.state = FileTask::Bad;
-    }
-}
-
-// ABUB_GPU_UNZIP=1: the zip layer of deflated archive entries is inflated on the GPU (abub_unzip_dev).  Off by default.
-inline bool gpuUnzipEnabled()
-{
-    const char *e = getenv("ABUB_GPU_UNZIP");
-    return e && atoi(e) != 0;
-}
-
-// The inflate of a batch's deflated archive entries on the device, between the pool's read and the walk of the files:
-// begin(), plan() behind every planFileTask, ready(), the pool (readFileTask with comp()), then run(): the compressed bytes
-// go up, abub_unzip_dev inflates every entry to its file's place in d_files, the files come back into the pinned file buffer
-// (pngWalk needs the chunk headers, the fallback decoder the file), and `readOne` -- the caller's pool function -- runs once
-// more over those tasks.  An entry the kernel refuses, for any status, is read by the host as ever (ReadImageFile).
+// The inflate of a batch's deflated archive entries on the device (ABUB_GPU_UNZIP=1), between the pool's read and the walk
+// of the files; FileBatch drives it.  An entry of method 8 gets a place in the pinned buffer of compressed bytes when its
+// task is planned, the pool reads those bytes instead of the file, and inflate() sends them up: abub_unzip_dev inflates every
+// entry to its file's place in d_files, and the files come back into the pinned file buffer (pngWalk needs the chunk
+// headers, the fallback decoder the file).  An entry the kernel refuses, for any status, is read by the host as ever
+// (ReadImageFile).
 struct GpuUnzip {
+    long long unzipped = 0; // entries the kernel inflated with status 0, since the batch began
+    double device_s = 0;    // wall time of inflate(): the upload of the compressed bytes, the kernels, the copy back, the wait
+
+private:
+    friend struct FileBatch;
     PinnedBuffer h_comp, h_status;
     DeviceBuffer d_comp, d_ent, d_status;
     size_t compTotal = 0;
-    long long unzipped = 0; // entries the kernel inflated with status 0
-    double device_s = 0;    // wall time of inflate(): the upload of the compressed bytes, the kernels, the copy back, the wait
-    bool on = false;
     std::vector<size_t> idx;
     std::vector<abub_zip_entry> ent;
 
-    void begin()
-    {
-        on = gpuUnzipEnabled();
-        compTotal = 0;
-        unzipped = 0;
-        device_s = 0;
-    }
-    // t has been planned (planFileTask): is its entry one for the kernel?
+    // t has been planned: is its entry one for the kernel?
     void plan(Parser &sizer, const std::string &ev, const std::string &name, FileTask &t)
     {
         Parser::EntryInfo e;
-        if (!on || t.state != FileTask::Planned || !sizer.GetImageEntryInfo(ev, name, e) || e.method != 8 ||
+        if (t.state != FileTask::Planned || !sizer.GetImageEntryInfo(ev, name, e) || e.method != 8 ||
             e.compressedSize >= (1ull << 28) || e.uncompressedSize >= (1ull << 28) || (long long)e.uncompressedSize != t.size ||
             compTotal >= ((size_t)1 << 32) - ((size_t)1 << 29))
             return;
@@ -316,22 +232,8 @@ struct GpuUnzip {
         t.crc = e.crc32;
         compTotal += (((size_t)t.clen + 15) & ~(size_t)15) + 16;
     }
-    void ready()
-    {
-        if (compTotal)
-            h_comp.grow(compTotal + 16);
-    }
-    uint8_t *comp() const { return compTotal ? h_comp.get() : nullptr; }
-
-    // tasks first[0 .. n), their files in h_files / d_files (total bytes planned); queued on `stream` and waited for
-    template <class Fn>
-    void run(FileTask *first, size_t n, uint8_t *h_files, DeviceBuffer &d_files, size_t total, hipStream_t stream, Parser *parser,
-             int nthreads, const Fn &readOne)
-    {
-        if (inflate(first, n, h_files, d_files, total, stream))
-            forEachTask(parser, nthreads, idx.size(), [&](Parser &p, size_t k) { readOne(p, idx[k]); });
-    }
-    // the device's part alone: afterwards `idx` holds the tasks whose read is to be finished (false: none)
+    // tasks first[0 .. n), their files in h_files / d_files (total bytes planned); queued on `stream` and waited for.
+    // Afterwards `idx` holds the tasks whose read is to be finished (false: none)
     bool inflate(FileTask *first, size_t n, uint8_t *h_files, DeviceBuffer &d_files, size_t total, hipStream_t stream)
     {
         idx.clear();
@@ -480,18 +382,12 @@ inline void launchFileDecode(const FileDescs &r, const uint8_t *d_files, int W, 
             sc.raw.grow((size_t)nf * stride);
             sc.segs.grow(r.segs.size() * sizeof(abub_png_seg) + 8);
             HIPOK(hipMemcpyAsync(sc.segs.get(), r.segs.data(), r.segs.size() * sizeof(abub_png_seg), hipMemcpyHostToDevice, stream));
-            if (adam7)
-                check(abub_png_decode_adam7_dev(d_files, r.bytes, (const abub_png_frame *)l.desc.get(), nf,
-                                                (const abub_png_seg *)sc.segs.get(), (int)r.segs.size(), l.luts.get(),
-                                                (int)(luts.size() / 256), W, H, sc.z.get(), sc.z.capacity(), sc.raw.get(),
-                                                sc.raw.capacity(), stride, out, out_bytes, status, stream),
-                      "abub_png_decode_adam7_dev");
-            else if (typed)
-                check(abub_png_decode_typed_dev(d_files, r.bytes, (const abub_png_frame *)l.desc.get(), nf,
-                                                (const abub_png_seg *)sc.segs.get(), (int)r.segs.size(), l.luts.get(),
-                                                (int)(luts.size() / 256), W, H, sc.z.get(), sc.z.capacity(), sc.raw.get(),
-                                                sc.raw.capacity(), stride, out, out_bytes, status, stream),
-                      "abub_png_decode_typed_dev");
+            if (typed)
+                check((adam7 ? abub_png_decode_adam7_dev : abub_png_decode_typed_dev)(
+                          d_files, r.bytes, (const abub_png_frame *)l.desc.get(), nf, (const abub_png_seg *)sc.segs.get(),
+                          (int)r.segs.size(), l.luts.get(), (int)(luts.size() / 256), W, H, sc.z.get(), sc.z.capacity(), sc.raw.get(),
+                          sc.raw.capacity(), stride, out, out_bytes, status, stream),
+                      adam7 ? "abub_png_decode_adam7_dev" : "abub_png_decode_typed_dev");
             else
                 check(abub_png_decode_dev(d_files, r.bytes, (const abub_png_frame *)l.desc.get(), nf, (const abub_png_seg *)sc.segs.get(),
                                           (int)r.segs.size(), l.luts.get(), (int)(luts.size() / 256), W, H, sc.z.get(), sc.z.capacity(),
@@ -547,10 +443,10 @@ void finishFileDecode(FileDescs &r, const uint8_t *h_files, const DecodeScratch 
     }
 }
 
-// One set of files on the device, decoded into one slab: the unit of the device routes that wait for their own upload
-// (device training, repack and unpack, each side of verify).  The caller plans ft[i] (planFileTask with `sizer`, `total`)
-// and has its pool read them into h_files (readFileTask); then reset, upload, and launch + finish once over all tasks or
-// once per range of them; good[s] says whether frame s is in place, `decodedBy` / `hostDecoded` sum over the finishes.
+// One set of files read for the GPU decoders and decoded on the device: the only way a route reads them (the protocol is
+// at the top of this file).  `sizer` is the caller's to set, a clone of the parser the files are read through.  good[s] says
+// whether frame s is in place in the batch's own slab; `decodedBy` / `hostDecoded` sum over the finishes and are the
+// caller's to zero.
 struct FileBatch {
     PinnedBuffer h_files;
     DeviceBuffer d_files, slab;
@@ -561,13 +457,102 @@ struct FileBatch {
     FileDescs fd;
     std::vector<uint8_t> good;
     long long decodedBy[NGpuCodecs] = {}, hostDecoded = 0;
-    GpuUnzip unzip; // ABUB_GPU_UNZIP=1: begin / plan / ready around the planning, comp() for the pool, then inflate()
+    DecodeKnobs knobs;
+    GpuUnzip unzip; // what the inflate stage counted (unzipped, device_s); the stage itself is driven from here
 
-    // after the pool has read ft into h_files: the deflated archive entries inflated on the device (GpuUnzip::run)
+    // no tasks yet; the knobs are read here, once per batch
+    void begin()
+    {
+        knobs = DecodeKnobs::fromEnv();
+        ft.clear();
+        total = 0;
+        fd = FileDescs();
+        unzip.compTotal = 0;
+        unzip.unzipped = 0;
+        unzip.device_s = 0;
+    }
+    // The next task, frame (s, f).  Wanted: its file gets its size and its place in the buffer (`total` grows by the file
+    // rounded up to 16 bytes; Bad if the parser cannot hand it out) and, where it is a deflated archive entry and the knob is
+    // on, a place in the inflate stage.  Not wanted: it stays Other, the caller's own work.  (The reference holds until the
+    // next call.)
+    FileTask &plan(int s, int f, const std::string &ev, const std::string &name, bool wanted = true)
+    {
+        ft.emplace_back();
+        FileTask &t = ft.back();
+        t.s = s;
+        t.f = f;
+        if (!wanted)
+            return t;
+        t.size = sizer->GetImageFileSize(ev, name);
+        t.state = (t.size > 0 && t.size < ((long long)1 << 30)) ? FileTask::Planned : FileTask::Bad;
+        t.off = total;
+        if (t.state == FileTask::Planned)
+            total += ((size_t)t.size + 15) & ~(size_t)15;
+        if (knobs.unzip)
+            unzip.plan(*sizer, ev, name, t);
+        return t;
+    }
+    // every task is planned: the buffers the pool reads into
+    void ready()
+    {
+        if (total)
+            h_files.grow(total + 16);
+        if (unzip.compTotal)
+            unzip.h_comp.grow(unzip.compTotal + 16);
+    }
+    // On a pool thread: task i's file into h_files + its offset, walked for the W x H GPU decoders, else decoded here.  A task
+    // planned for the device's inflate only has its compressed bytes read and stays Planned: false, it is to be read once more
+    // after the inflate, which does the rest (the file is in place: ZipInflated) or all of it (ZipNone).
+    bool read(Parser &p, size_t i, const std::string &ev, const std::string &name, int W, int H)
+    {
+        FileTask &t = ft[i];
+        if (t.state != FileTask::Planned)
+            return true;
+        uint8_t *dst = h_files.get() + t.off;
+        long long got = -1;
+        if (t.zip == FileTask::ZipPlanned) {
+            try {
+                got = p.ReadImageEntryRaw(ev, name, unzip.h_comp.get() + t.coff, t.clen);
+            } catch (...) {
+                got = -1;
+            }
+            t.zip = got == (long long)t.clen ? FileTask::ZipRead : FileTask::ZipNone;
+        }
+        if (t.zip == FileTask::ZipRead)
+            return false;
+        if (t.zip == FileTask::ZipInflated)
+            got = t.size;
+        else
+            try {
+                got = p.ReadImageFile(ev, name, dst, (size_t)t.size);
+            } catch (...) {
+                got = -1;
+            }
+        t.read = got == t.size;
+        try {
+            if (!t.read)
+                t.state = FileTask::Bad;
+            else if (gpuCodecOf(dst, (size_t)t.size, W, H, t, knobs))
+                t.state = FileTask::OnGpu;
+            else { // not a file for the GPU decoders (16-bit, colour, interlaced, another size): the host decoder's answer
+                t.pix.resize((size_t)W * H);
+                t.state = cv::imdecodeInto(dst, (size_t)t.size, t.pix.data(), W, H) ? FileTask::HostDecoded : FileTask::Bad;
+            }
+        } catch (...) { // (an allocation that fails inside a pool thread must not end the batch)
+            t.state = FileTask::Bad;
+        }
+        return true;
+    }
+    // After the pool: the waiting tasks' entries inflated on the device, queued on `cs` and waited for; false if none waited
+    bool inflateOnDevice(hipStream_t cs) { return unzip.inflate(ft.data(), ft.size(), h_files.get(), d_files, total, cs); }
+    // the tasks that waited for the last inflateOnDevice, in ascending order: each is to be read once more
+    const std::vector<size_t> &pending() const { return unzip.idx; }
+    // inflateOnDevice, then `readOne` -- the caller's pool function -- once more over the pending tasks
     template <class Fn>
     void inflate(Parser *parser, int nthreads, hipStream_t cs, const Fn &readOne)
     {
-        unzip.run(ft.data(), ft.size(), h_files.get(), d_files, total, cs, parser, nthreads, readOne);
+        if (inflateOnDevice(cs))
+            forEachTask(parser, nthreads, pending().size(), [&](Parser &p, size_t k) { readOne(p, pending()[k]); });
     }
     // a slab of `bytes` for frames 0 .. nslots-1, none of them in place yet (its contents are the caller's to clear)
     void reset(size_t nslots, size_t bytes)
@@ -576,31 +561,50 @@ struct FileBatch {
         slab.grow(bytes);
         slabBytes = bytes;
     }
-    // the files to the device, if a decoder took any
-    void upload(hipStream_t cs)
+    // the files to the device, if a decoder took any (false: none did, nothing was queued)
+    bool upload(hipStream_t cs)
     {
         if (std::none_of(ft.begin(), ft.end(), [](const FileTask &t) { return t.onGpu(); }))
-            return;
+            return false;
         d_files.grow(total + 16);
         HIPOK(hipMemcpyAsync(d_files.get(), h_files.get(), total + 16, hipMemcpyHostToDevice, cs));
+        return true;
     }
-    // the decoders over tasks [i0, i1), frame (s, f) to dstOf(s, f) in the slab; false if none of them is for a decoder
+    // fd: the descriptors of tasks [i0, i1), frame (s, f) to byte dstOf(s, f) of the output
     template <class DstOf>
-    bool launch(size_t i0, size_t i1, int W, int H, const DstOf &dstOf, hipStream_t cs)
+    void describe(size_t i0, size_t i1, const DstOf &dstOf)
     {
         fd = FileDescs();
         buildFileDescs(ft.data() + i0, ft.data() + i1, total, fd, dstOf);
+    }
+    // the decoders over the described tasks into `out` (out_bytes) with the scratch `sc`, queued on `cs`; false if none of
+    // the tasks is for a decoder
+    bool launchInto(int W, int H, uint8_t *out, size_t out_bytes, DecodeScratch &sc, hipStream_t cs)
+    {
         if (!fd.gpuFrames())
             return false;
-        launchFileDecode(fd, d_files.get(), W, H, slab.get(), slabBytes, scratch, cs);
+        launchFileDecode(fd, d_files.get(), W, H, out, out_bytes, sc, cs);
         return true;
     }
-    // after the stream has been waited for
-    void finish(int W, int H, hipStream_t cs)
+    // after the stream has been waited for: the refused frames and the reading threads' own into `out`; ok(s, f) for every
+    // frame that is in place
+    template <class Ok>
+    void finishInto(int W, int H, uint8_t *out, const DecodeScratch &sc, hipStream_t cs, const Ok &ok)
     {
-        finishFileDecode(fd, h_files.get(), scratch, slab.get(), W, H, cs, [&](int s, int) { good[s] = 1; }, hostDecoded);
+        finishFileDecode(fd, h_files.get(), sc, out, W, H, cs, ok, hostDecoded);
         for (int c = 0; c < NGpuCodecs; ++c)
             decodedBy[c] += fd.decodedBy[c];
+    }
+    // the same two into the batch's own slab with its own scratch, over tasks [i0, i1)
+    template <class DstOf>
+    bool launch(size_t i0, size_t i1, int W, int H, const DstOf &dstOf, hipStream_t cs)
+    {
+        describe(i0, i1, dstOf);
+        return launchInto(W, H, slab.get(), slabBytes, scratch, cs);
+    }
+    void finish(int W, int H, hipStream_t cs)
+    {
+        finishInto(W, H, slab.get(), scratch, cs, [&](int s, int) { good[s] = 1; });
     }
 };
 

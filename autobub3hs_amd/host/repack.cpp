@@ -218,23 +218,15 @@ void deviceFrames(const Codec &codec, Parser *parser, const Plan &pl, int nthrea
         const size_t n = std::min(perBatch, pl.tasks.size() - i0);
         // ---- read -------------------------------------------------------------------------------------------------------
         double t0 = nowMs();
-        ft.assign(n, FileTask());
-        B.total = 0;
-        B.unzip.begin();
-        for (size_t i = 0; i < n; ++i) {
-            const Task &t = pl.tasks[i0 + i];
-            ft[i].s = (int)i;
-            planFileTask(*B.sizer, pl.events[t.ev], t.name, ft[i], B.total);
-            B.unzip.plan(*B.sizer, pl.events[t.ev], t.name, ft[i]);
-        }
-        B.h_files.grow(B.total + 16);
-        B.unzip.ready();
+        B.begin();
+        for (size_t i = 0; i < n; ++i)
+            B.plan((int)i, 0, pl.events[pl.tasks[i0 + i].ev], pl.tasks[i0 + i].name);
+        B.ready();
         const auto readOne = [&](Parser &p, size_t i) {
             const Task &t = pl.tasks[i0 + i];
             FileTask &f = ft[i];
             const std::string &ev = pl.events[t.ev];
-            readFileTask(p, ev, t.name, f, B.h_files.get(), W, H, B.unzip.comp());
-            if (f.onGpu() || f.zip == FileTask::ZipRead) // (ZipRead: once more after the device's inflate)
+            if (!B.read(p, i, ev, t.name, W, H) || f.onGpu()) // (not read yet: once more after the device's inflate)
                 return;
             if (f.state == FileTask::HostDecoded) { // (16-bit, colour, BMP: this thread decoded it at W x H)
                 static thread_local std::vector<unsigned char> packed;

@@ -63,13 +63,11 @@ bool decodeFrame(Parser &p, StackMeta &m, int f, uint8_t *dst, int W, int H)
 struct Slot {
     PinnedBuffer h_frames;     // the host share's frames
     DeviceBuffer d_frames;     // the whole batch, [G][C][Fmax][H][W]
-    PinnedBuffer h_files;      // the GPU share's files, each at a 16-byte boundary ...
-    DeviceBuffer d_files;      // ... uploaded by the reading thread: the copy runs beside the GPU work of the batch before
-    GpuUnzip unzip;            // ABUB_GPU_UNZIP=1: the deflated archive entries of the batch, inflated on the reading thread's stream
+    FileBatch batch;           // the GPU share's files, read, inflated and uploaded by the reading thread (the copy runs beside
+                               // the GPU work of the batch before), and their descriptors (fd); its slab and scratch stay empty
     std::exception_ptr err;    // of the look-ahead thread that read the batch
     struct Read {
         std::vector<StackMeta> meta;
-        FileDescs files;       // the frames the GPU decodes; those of the GPU share a reading thread decoded
         double ms = 0;
         long long hostGood = 0;
         long long unzipped = 0; // archive entries abub_unzip_dev inflated
@@ -186,7 +184,7 @@ int runBatchedOn(Workers &ws, Parser *parser, const std::vector<std::string> &Ev
                         std::vector<unsigned char> buf((size_t)sz);
                         FileTask probe;
                         devDecode = p->ReadImageFile(EventList[mine[k]], lists[k][c][0], buf.data(), buf.size()) == sz &&
-                                    gpuCodecOf(buf.data(), buf.size(), W, H, probe);
+                                    gpuCodecOf(buf.data(), buf.size(), W, H, probe, DecodeKnobs::fromEnv());
                     }
                     k = lists.size(); // (one probe decides)
                     break;
@@ -239,10 +237,11 @@ int runBatchedOn(Workers &ws, Parser *parser, const std::vector<std::string> &Ev
         Slot::Read &r = sl.r;
         r = Slot::Read();
         r.meta.assign((size_t)G * C, StackMeta());
-        std::vector<FileTask> tasks; // (in stack order: the GPU's files are read first, its work can start before the host's is done)
-        std::unique_ptr<Parser> sizer(Ggpu ? parser->clone() : nullptr);
-        size_t total = 0;
-        sl.unzip.begin();
+        FileBatch &B = sl.batch; // (tasks in stack order: the GPU's files are read first, its work can start before the host's is done)
+        B.sizer.reset(Ggpu ? parser->clone() : nullptr);
+        std::fill(B.decodedBy, B.decodedBy + NGpuCodecs, 0);
+        B.hostDecoded = 0;
+        B.begin();
         for (int k = 0; k < G; ++k)
             for (int c = 0; c < C; ++c) {
                 StackMeta &m = r.meta[(size_t)k * C + c];
@@ -253,44 +252,31 @@ int runBatchedOn(Workers &ws, Parser *parser, const std::vector<std::string> &Ev
                 m.eventID = EventList[mine[e0 + k]];
                 m.names = lists[e0 + k][c];
                 m.ok.assign(m.names.size(), 0);
-                for (int f = 0; f < (int)m.names.size(); ++f) {
-                    FileTask t;
-                    t.s = k * C + c;
-                    t.f = f;
-                    if (k < Ggpu) {
-                        planFileTask(*sizer, m.eventID, m.names[f], t, total);
-                        sl.unzip.plan(*sizer, m.eventID, m.names[f], t);
-                    }
-                    tasks.push_back(std::move(t));
-                }
+                for (int f = 0; f < (int)m.names.size(); ++f) // (the host share's tasks stay Other)
+                    B.plan(k * C + c, f, m.eventID, m.names[f], k < Ggpu);
             }
-        if (Ggpu)
-            sl.h_files.grow(total + 16);
-        sl.unzip.ready();
+        B.ready();
         std::atomic<long long> hostGood{0}, hostBad{0};
         const auto readOne = [&](Parser &p, size_t i) {
-            FileTask &t = tasks[i];
+            const FileTask &t = B.ft[i];
             StackMeta &m = r.meta[t.s];
             if (t.state == FileTask::Other) { // the host share: straight into the pinned slab
                 uint8_t *dst = sl.h_frames.get() + ((size_t)(t.s - Ggpu * C) * Fmax + t.f) * P;
                 ++(decodeFrame(p, m, t.f, dst, W, H) ? hostGood : hostBad);
                 return;
             }
-            readFileTask(p, m.eventID, m.names[t.f], t, sl.h_files.get(), W, H, sl.unzip.comp());
+            B.read(p, i, m.eventID, m.names[t.f], W, H); // (what a decoder does not take is uploaded by the worker, FileBatch::finishInto)
         };
-        forEachTask(parser, nthreads, tasks.size(), readOne);
-        sl.unzip.run(tasks.data(), tasks.size(), sl.h_files.get(), sl.d_files, total, upStream.get(), parser, nthreads, readOne);
-        r.unzipped = sl.unzip.unzipped;
-        r.unzip_s = sl.unzip.device_s;
-        r.files.bad = hostBad;
+        forEachTask(parser, nthreads, B.ft.size(), readOne);
+        B.inflate(parser, nthreads, upStream.get(), readOne);
+        r.unzipped = B.unzip.unzipped;
+        r.unzip_s = B.unzip.device_s;
+        B.describe(0, B.ft.size(), [&](int s, int f) { return ((uint64_t)s * Fmax + f) * P; });
+        B.fd.bad += hostBad;
         r.hostGood = hostGood;
-        buildFileDescs(tasks.data(), tasks.data() + tasks.size(), total, r.files, [&](int s, int f) { return ((uint64_t)s * Fmax + f) * P; });
         r.ms = nowMs() - td;
-        if (r.files.gpuFrames()) {
-            sl.d_files.grow(r.files.bytes);
-            HIPOK(hipMemcpyAsync(sl.d_files.get(), sl.h_files.get(), r.files.bytes, hipMemcpyHostToDevice, upStream.get()));
+        if (B.upload(upStream.get()))
             HIPOK(hipStreamSynchronize(upStream.get()));
-        }
     };
 
     auto worker = [&](int g) {
@@ -396,7 +382,8 @@ int runBatchedOn(Workers &ws, Parser *parser, const std::vector<std::string> &Ev
                     startRead(bn, slot ^ 1);
                 const double tg = nowMs();
                 const int nEv = std::min(G, (int)mine.size() - b * G), nEvGpu = std::min(nEv, Ggpu);
-                const int nf = (int)R.files.gpuFrames();
+                FileBatch &B = S.batch;
+                const int nf = (int)B.fd.gpuFrames();
                 uint8_t *d_frames = S.d_frames.get();
                 hipStream_t cs = copyStream.get();
                 // the GPU share starts at zero (frames nobody decodes stay so, see decodeFrame); the host share is uploaded
@@ -406,16 +393,15 @@ int runBatchedOn(Workers &ws, Parser *parser, const std::vector<std::string> &Ev
                     HIPOK(hipMemcpyAsync(d_frames + (size_t)nEvGpu * perEvent, S.h_frames.get(), (size_t)(nEv - nEvGpu) * perEvent,
                                          hipMemcpyHostToDevice, cs));
                 const double tp = nowMs();
-                launchFileDecode(R.files, S.d_files.get(), W, H, d_frames, (size_t)nEv * perEvent, scratch, cs);
-                // every write below lands after the clear above
+                B.launchInto(W, H, d_frames, (size_t)nEv * perEvent, scratch, cs);
+                // every write below lands after the clear above (waited for whether a decoder was launched or not)
                 HIPOK(hipStreamSynchronize(cs));
-                long long onHost = R.hostGood;
-                finishFileDecode(R.files, S.h_files.get(), scratch, d_frames, W, H, cs, [&](int s, int f) { R.meta[s].ok[f] = 1; }, onHost);
-                const long long onGpu = R.files.decoded();
+                B.finishInto(W, H, d_frames, scratch, cs, [&](int s, int f) { R.meta[s].ok[f] = 1; });
+                const long long onHost = R.hostGood + B.hostDecoded, onGpu = B.fd.decoded();
                 const double pngms = Ggpu ? nowMs() - tp : 0;
                 if (trace)
                     fprintf(stderr, "batch %d: %d frames for the GPU (%zu MB of files), %lld decoded by host threads, read + host decode %.1f ms, "
-                                    "upload + GPU decode %.1f ms\n", b, nf, R.files.bytes >> 20, R.hostGood, R.ms, pngms);
+                                    "upload + GPU decode %.1f ms\n", b, nf, B.fd.bytes >> 20, R.hostGood, R.ms, pngms);
                 setStackMeta(*pipe, std::move(R.meta));
                 if (const char *tf = getenv("ABUB_TEST_FAIL_BATCH")) // test hook: a batch fails while the next one decodes
                     if (atoi(tf) == b)
@@ -443,12 +429,12 @@ int runBatchedOn(Workers &ws, Parser *parser, const std::vector<std::string> &Ev
                     st.gpu_s += gms * 1e-3;
                     st.write_s += wms * 1e-3;
                     st.frames += onGpu + onHost;
-                    st.framesFailed += R.files.bad;
+                    st.framesFailed += B.fd.bad;
                     st.bellowsVetoed += bellowsVetoed(*pipe);
                     st.framesGpuDecoded += onGpu;
                     st.framesHostDecoded += onHost;
-                    st.framesGpuUnpacked += R.files.decodedBy[GpuPacked];
-                    st.framesGpuBmp += R.files.decodedBy[GpuBmp];
+                    st.framesGpuUnpacked += B.fd.decodedBy[GpuPacked];
+                    st.framesGpuBmp += B.fd.decodedBy[GpuBmp];
                     st.framesGpuUnzipped += R.unzipped;
                     st.unzip_s += R.unzip_s;
                     st.gpudecode_s += pngms * 1e-3;

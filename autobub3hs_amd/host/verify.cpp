@@ -10,6 +10,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <iterator>
 #include <memory>
 #include <set>
 #include <sstream>
@@ -244,38 +245,31 @@ void deviceFrames(Parser *src, Parser *other, const Plan &pl, int nthreads, int 
         double t0 = nowMs();
         std::vector<uint8_t> done(n, 0); // the frame has its verdict
         for (FileBatch *side : {&S, &O}) {
-            side->ft.assign(n, FileTask());
-            side->total = 0;
-            side->unzip.begin();
+            side->begin();
             side->reset(n, n * stride);
         }
         for (size_t i = 0; i < n; ++i) {
             const FrameTask &t = pl.tasks[i0 + i];
-            S.ft[i].s = O.ft[i].s = (int)i;
-            planFileTask(*S.sizer, pl.events[t.ev], t.name, S.ft[i], S.total);
-            S.unzip.plan(*S.sizer, pl.events[t.ev], t.name, S.ft[i]);
-            if (pl.listed[t.ev].count(t.name)) {
-                planFileTask(*O.sizer, pl.events[t.ev], t.name, O.ft[i], O.total);
-                O.unzip.plan(*O.sizer, pl.events[t.ev], t.name, O.ft[i]);
-            } else
-                O.ft[i].state = FileTask::Bad;
+            S.plan((int)i, 0, pl.events[t.ev], t.name);
+            if (!pl.listed[t.ev].count(t.name))
+                O.plan((int)i, 0, pl.events[t.ev], t.name, false).state = FileTask::Bad;
+            else
+                O.plan((int)i, 0, pl.events[t.ev], t.name);
         }
-        S.h_files.grow(S.total + 16);
-        O.h_files.grow(O.total + 16);
-        S.unzip.ready();
-        O.unzip.ready();
-        std::vector<uint8_t> again(n, 0); // a side waits for the device's inflate of its archive entry (ABUB_GPU_UNZIP=1)
-        const auto readPair = [&](Clones &c, size_t i) {
+        S.ready();
+        O.ready();
+        // A pair is read when both its files are there to be read, the source first, and once more (`second`) when a side of it
+        // waited for the device's inflate of its archive entry (ABUB_GPU_UNZIP=1); it is final only when neither side waits
+        const auto readPair = [&](Clones &c, size_t i, bool second) {
             const FrameTask &t = pl.tasks[i0 + i];
             FileTask &fs = S.ft[i], &fo = O.ft[i];
-            if ((fs.state == FileTask::Planned && fo.state == FileTask::Planned) || again[i]) {
-                readFileTask(*c.src, pl.events[t.ev], t.name, fs, S.h_files.get(), W, H, S.unzip.comp());
+            if (second || (fs.state == FileTask::Planned && fo.state == FileTask::Planned)) {
+                bool settled = S.read(*c.src, i, pl.events[t.ev], t.name, W, H);
                 if (fs.state != FileTask::Bad)
-                    readFileTask(*c.other, pl.events[t.ev], t.name, fo, O.h_files.get(), W, H, O.unzip.comp());
+                    settled = O.read(*c.other, i, pl.events[t.ev], t.name, W, H) && settled;
+                if (!settled)
+                    return;
             }
-            again[i] = fs.zip == FileTask::ZipRead || fo.zip == FileTask::ZipRead;
-            if (again[i])
-                return;
             const bool sOk = fs.onGpu() || fs.state == FileTask::HostDecoded, oOk = fo.onGpu() || fo.state == FileTask::HostDecoded;
             if (sOk && oOk)
                 return;
@@ -284,16 +278,13 @@ void deviceFrames(Parser *src, Parser *other, const Plan &pl, int nthreads, int 
             fs.pix = fo.pix = std::vector<uint8_t>();
             fs.state = fo.state = FileTask::Other;
         };
-        forEachPair(src, other, nthreads, n, readPair);
-        const bool sz = S.unzip.inflate(S.ft.data(), n, S.h_files.get(), S.d_files, S.total, cs);
-        const bool oz = O.unzip.inflate(O.ft.data(), n, O.h_files.get(), O.d_files, O.total, cs);
-        if (sz || oz) {
-            std::vector<size_t> idx;
-            for (size_t i = 0; i < n; ++i)
-                if (again[i])
-                    idx.push_back(i);
-            forEachPair(src, other, nthreads, idx.size(), [&](Clones &c, size_t k) { readPair(c, idx[k]); });
-        }
+        forEachPair(src, other, nthreads, n, [&](Clones &c, size_t i) { readPair(c, i, false); });
+        S.inflateOnDevice(cs);
+        O.inflateOnDevice(cs);
+        std::vector<size_t> waited; // the pairs a side of which waited
+        std::set_union(S.pending().begin(), S.pending().end(), O.pending().begin(), O.pending().end(), std::back_inserter(waited));
+        if (!waited.empty())
+            forEachPair(src, other, nthreads, waited.size(), [&](Clones &c, size_t k) { readPair(c, waited[k], true); });
         srcUnzipped += S.unzip.unzipped;
         otherUnzipped += O.unzip.unzipped;
         st.srcGpuUnzipped = srcUnzipped;

@@ -254,6 +254,59 @@ def test_verify_gpu_with_a_deflated_archive_as_the_source(archives, tmp_path, mo
             assert voff[k] == von[k], (k, voff[k], von[k])
 
 
+def test_verify_gpu_when_only_one_side_waits_for_the_inflate(tmp_path, monkeypatch):
+    """A deflated archive verified against a plain directory in batches of three: only the source side of a pair waits for
+    the device's inflate, so the second reading round meets pairs whose other side is already final -- read and on its way
+    to a decoder, or read and refused (a frame of another size).  A frame the directory lacks is never read on either side
+    (its archive entry is stored, so that every deflated entry is one the kernel inflates).  Verdicts and findings are the
+    host route's."""
+    w, h, nev, nf = 64, 16, 2, 4
+    missing, resized, changed = (0, 1), (1, 0), (1, 2)  # (event, frame): tasks 1, 4 and 6 of batches [0-2], [3-5], [6-7]
+    r = np.random.RandomState(18)
+    other_root = str(tmp_path / "dir" / RUN_ID)
+    listing = "".join(f"{RUN_ID} {e} a b c d e f g h i\n" for e in range(nev)).encode()
+    entries = [(RUN_ID + "/", b"", 0, None, None), (f"{RUN_ID}/{RUN_ID}.txt", listing, 8, None, None)]
+    deflated = 0
+    for e in range(nev):
+        entries += [(f"{RUN_ID}/{e}/", b"", 0, None, None), (f"{RUN_ID}/{e}/Images/", b"", 0, None, None)]
+        os.makedirs(os.path.join(other_root, str(e), "Images"))
+        for k in range(nf):
+            img = np.sort(r.randint(0, 256, (h, w)), axis=1).astype(np.uint8)
+            method = 0 if (e, k) == missing else 8
+            deflated += method == 8
+            entries.append((f"{RUN_ID}/{e}/Images/{name_of(0, k)}", png_bytes(img), method, None, None))
+            if (e, k) == missing:
+                continue
+            if (e, k) == resized:
+                img = img[:, :w - 4]
+            elif (e, k) == changed:
+                img = img.copy()
+                img[5, 9] ^= 0x10
+            open(os.path.join(other_root, str(e), "Images", name_of(0, k)), "wb").write(png_bytes(img))
+    open(os.path.join(other_root, RUN_ID + ".txt"), "wb").write(listing)
+    zc.write_zip(str(tmp_path / "src.zip"), entries)
+    monkeypatch.setenv("ABUB_VERIFY_BATCH", "3")
+    monkeypatch.delenv("ABUB_GPU_DECODE", raising=False)
+    monkeypatch.delenv("ABUB_GPU_UNZIP", raising=False)
+    src = host.Run("zip", str(tmp_path / "src.zip"), "Images", FORMAT)
+    other = host.Run("raw", other_root + "/", "Images", FORMAT)
+    try:
+        vh = src.verify(other, nthreads=4, ncams=1)
+        monkeypatch.setenv("ABUB_GPU_UNZIP", "1")
+        von = src.verify(other, nthreads=4, ncams=1, device=0)
+    finally:
+        other.close()
+        src.close()
+    for k in ("rc", "events", "frames", "same", "same_not_packed", "copied", "differ", "missing", "undecodable", "extra", "event_file",
+              "findings"):
+        assert vh[k] == von[k], (k, vh[k], von[k])
+    assert (von["rc"], von["frames"], von["missing"], von["differ"], von["same_not_packed"]) == (1, nev * nf, 1, 2, nev * nf - 3), von
+    assert [(f["event"], f["name"]) for f in von["findings"] if f["verdict"] in ("missing", "differ")] == [
+        (str(e), name_of(0, k)) for e, k in (missing, resized, changed)], von["findings"]
+    assert von["device"] == 0 and von["batches"] == 3, von
+    assert von["src_gpu_unzipped"] == deflated == nev * nf - 1 and von["other_gpu_unzipped"] == 0, von
+
+
 def test_campaign_of_two_deflated_archives(tmp_path):
     """abub3hs --runs A,B -z (abub::RunCampaign): one FileBatch with its GpuUnzip is kept from run to run for the device
     training, and run B is trained on a thread and stream of its own while run A's batches pass through the look-ahead
