@@ -44,6 +44,11 @@ class LocStack(C.Structure):
                 ("track", C.c_int32 * LOC_MAXTRACK), ("reserved", C.c_int32 * 2)]
 
 
+class PeekItem(C.Structure):
+    _fields_ = [("diff", C.c_uint64), ("frame", C.c_uint64), ("thr_out", C.c_uint64), ("pres_out", C.c_uint64),
+                ("thr", C.c_int32), ("rect_begin", C.c_int32), ("rect_count", C.c_int32), ("reserved", C.c_int32)]
+
+
 def build(force=False):
     """Compile the HIP library for gfx950 (cross-compiles without a GPU)."""
     srcs = [os.path.join(HERE, "csrc", f) for f in os.listdir(os.path.join(HERE, "csrc"))
@@ -93,6 +98,7 @@ SIGNATURES = {
     "abub_png_encode_scratch_bytes": (_sz, [_i, _i, _i]),
     "abub_png_encode_dev": (_i, [_vp, _sz, _vp, _i, _i, _i, _vp, _sz, _vp, _vp, _vp, _sz, _vp]),
     "abub_frames_compare_dev": (_i, [_vp, _sz, _vp, _sz, _vp, _i, _sz, _vp, _vp]),
+    "abub_peek_planes_dev": (_i, [_vp, _sz, _vp, _sz, _vp, _i, _vp, _i, _i, _i, _vp, _sz, _vp, _vp]),
     "abub_diff_hist_chained_deferred_dev": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, C.c_uint32, _vp, _vp, _vp]),
     "abub_diff_hist_pieces_dev": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "abub_diff_hist_compact_dev": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, C.c_uint32, _vp, C.c_uint32, _vp]),

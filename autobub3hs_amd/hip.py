@@ -638,6 +638,43 @@ def frames_compare(a, b, pairs, frame_bytes, a_bytes=None, b_bytes=None, results
     return results.reshape(-1)[:4 * n].cpu().numpy().view(np.uint32).astype(np.int64).reshape(n, 4)
 
 
+def peek_items(rows):
+    """rows of (diff, frame, thr_out, pres_out, thr, rect_begin, rect_count) -> the abub_peek_item records as a uint8 host
+    array (48 bytes each)."""
+    import numpy as np
+    dt = np.dtype([("diff", "<u8"), ("frame", "<u8"), ("thr_out", "<u8"), ("pres_out", "<u8"), ("thr", "<i4"),
+                   ("rect_begin", "<i4"), ("rect_count", "<i4"), ("reserved", "<i4")])
+    rec = np.zeros(len(rows), dtype=dt)
+    for k, r in enumerate(rows):
+        rec[k] = tuple(int(v) for v in r) + (0,)
+    return rec.view(np.uint8).reshape(-1)
+
+
+def peek_planes(diff, frames, items, rects, W, H, out, diff_bytes=None, frames_bytes=None, out_bytes=None):
+    """abub_peek_planes_dev: diff, frames u8 (any shape; D planes and frames of W * H bytes anywhere in them), items: rows of
+    (diff, frame, thr_out, pres_out, thr, rect_begin, rect_count) with byte offsets into diff / frames / out (thr_out and
+    pres_out multiples of 16), rects: [m, 4] of (x, y, w, h); out u8, written in place: per item the thresholded plane
+    (255 where D > thr) at thr_out and the trigger frame with its rectangles drawn at pres_out.  *_bytes: the sizes the
+    kernel is told (default: the tensors').  -> int32 [n] on the host: 0, or ABUB_PEEK_E_SRC = 1, _DST = 2, _RECT = 3 (then
+    not a byte of the item's planes is written)."""
+    import numpy as np
+    _need_cuda(diff, frames, out)
+    dev = out.device
+    rows = list(items)
+    n = len(rows)
+    rc = np.asarray(rects, dtype=np.int64).reshape(-1, 4).astype(np.int32)
+    m = len(rc)
+    d_items = torch.from_numpy(np.concatenate([peek_items(rows), np.zeros(48, np.uint8)])).to(dev)
+    d_rects = torch.from_numpy(np.concatenate([rc, np.zeros((1, 4), np.int32)])).to(dev)
+    status = torch.full((max(n, 1),), 99, dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().abub_peek_planes_dev(_ptr(diff), diff.numel() if diff_bytes is None else int(diff_bytes), _ptr(frames),
+                                               frames.numel() if frames_bytes is None else int(frames_bytes), _ptr(d_items), n,
+                                               _ptr(d_rects), m, W, H, _ptr(out),
+                                               out.numel() if out_bytes is None else int(out_bytes), _ptr(status), _stream()),
+               "abub_peek_planes_dev")
+    return status[:n].cpu().numpy()
+
+
 def match_terms(frames, frame_idx, tmpl):
     """Exact CCORR terms (abub_match_ccorr_batch_dev): frames u8 [N,H,W] (any slab of frames), frame_idx int32 [njobs]
     (frame of each job), tmpl u8 [th,tw] -> (num, wsum2), each int64 [njobs, H-th+1, W-tw+1] holding the u64 sums."""

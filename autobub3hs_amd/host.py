@@ -33,6 +33,9 @@ SIGNATURES = {
     "abh_set_model": (_i, [_vp, _i, _u8p, _u8p, _i, _i, _i]),
     "abh_probe_frame_stats": (_i, [_vp, _s, _i, _u8p, _i, _i, _i, _dp]),
     "abh_run_batched": (_i, [_vp, _i, _s, _s, _s] + [_i] * 7 + [_dp]),
+    "abh_run_batched_peek": (_i, [_vp, _i, _s, _s, _s] + [_i] * 7 + [_dp, _s, _dp]),
+    "abh_peek_planes_host": (None, [_u8p, _u8p, _i, _i, _i, _ip, _i, _u8p, _u8p]),
+    "abh_result_rects": (_i, [_vp, _ip, _i]),
     "abh_analyze": (_i, [_vp, _s, _i, _s]),
     "abh_last_error": (_s, [_vp]),
     "abh_run_last": (_vp, [_vp]),
@@ -143,6 +146,27 @@ def _read_result(res, with_dz):
             bub["dz"] = [L.abh_result_dz(res, b, i) for i in range(L.abh_result_ndz(res, b))]
         bubbles.append(bub)
     return o[0], state, bubbles, L.abh_result_error(res).decode()
+
+
+def _read_rects(res):
+    """StackResult::rects: the boxes (x, y, w, h) of the analyzer's last localizer round, those of _4_BubbleDetected."""
+    L = lib()
+    n = L.abh_result_rects(res, None, 0)
+    buf = (C.c_int * (4 * max(n, 1)))()
+    L.abh_result_rects(res, buf, n)
+    return [tuple(buf[4 * i:4 * i + 4]) for i in range(n)]
+
+
+def peek_planes_host(D, trig, cut, rects):
+    """The host route's two DebugPeek planes (host/peek.cpp peekPlanesHost, the definition of abub_peek_planes_dev):
+    D, trig u8 [H, W] -> (255 where D > cut, trig with cv::rectangle of every (x, y, w, h) drawn)."""
+    D, trig = np.ascontiguousarray(D, np.uint8), np.ascontiguousarray(trig, np.uint8)
+    H, W = D.shape
+    rc = np.ascontiguousarray(np.asarray(rects, np.int64).reshape(-1, 4).astype(np.int32))
+    thr, pres = np.empty((H, W), np.uint8), np.empty((H, W), np.uint8)
+    lib().abh_peek_planes_host(D.ctypes.data_as(_u8p), trig.ctypes.data_as(_u8p), W, H, int(cut), rc.ctypes.data_as(_ip), len(rc),
+                               thr.ctypes.data_as(_u8p), pres.ctypes.data_as(_u8p))
+    return thr, pres
 
 
 class Run:
@@ -267,20 +291,29 @@ class Run:
         return out
 
     def run_batched(self, ncams, outdir, run_number, frame_offset, maskdir="", ngpus=1, nthreads=16, decode_threads=16,
-                    batch_mb=0, shard=(0, 1)):
+                    batch_mb=0, shard=(0, 1), peek_dir=None):
         """Every event of this run through the batched GPU pipeline (host/runbatch.cpp RunBatched): frames decoded (PNG, packed and BMP files: on the GPU, abub_png_decode_dev / abub_abf_decode_dev / abub_bmp_decode_dev with ABUB_GPU_BMP=1, else BMP files by host threads; ABUB_GPU_DECODE=0: by host threads into pinned
         batches), detect, blocks appended to <outdir>abub3hs_<run>.txt in event order.  With ABUB_GPU_UNZIP=1 the zip layer of
-        a deflated archive's entries is inflated on the GPU too (abub_unzip_dev; frames_gpu_unzipped counts them).  -> stats dict."""
+        a deflated archive's entries is inflated on the GPU too (abub_unzip_dev; frames_gpu_unzipped counts them).
+        peek_dir (abub3hs --peek): the six DebugPeek images of every accepted (event, camera) written to
+        <peek_dir>/<run_number>/ by a post-pass per batch, on the GPU (abub_peek_planes_dev, abub_png_encode_dev) or, with
+        ABUB_PEEK_GPU=0, on host threads: the same files; the stats then have peek_stacks, peek_files, peek_bytes, peek_gpu
+        and peek_s.  -> stats dict."""
         L = lib()
         st = (C.c_double * 17)()
-        rc = L.abh_run_batched(self._h, ncams, maskdir.encode(), outdir.encode(), run_number.encode(), frame_offset, ngpus,
-                               nthreads, decode_threads, batch_mb, shard[0], shard[1], st)
+        pk = (C.c_double * 5)()
+        rc = L.abh_run_batched_peek(self._h, ncams, maskdir.encode(), outdir.encode(), run_number.encode(), frame_offset, ngpus,
+                                    nthreads, decode_threads, batch_mb, shard[0], shard[1], st,
+                                    None if peek_dir is None else str(peek_dir).encode(), pk)
         if rc != 0:
             raise RuntimeError(f"abh_run_batched rc={rc}: " + L.abh_last_error(self._h).decode())
         keys = ("total_s", "list_s", "decode_s", "gpu_s", "write_s", "frames", "frames_failed", "batches",
                 "events_per_batch", "gpus", "frames_gpu_decoded", "frames_host_decoded", "gpudecode_s", "frames_gpu_unpacked",
                 "frames_gpu_bmp", "frames_gpu_unzipped", "unzip_s")
-        return dict(zip(keys, list(st)))
+        out = dict(zip(keys, list(st)))
+        if peek_dir is not None:
+            out.update(zip(("peek_stacks", "peek_files", "peek_bytes", "peek_gpu", "peek_s"), list(pk)))
+        return out
 
     def repack(self, outdir, nthreads=16, ncams=4, device=None):
         """abub3hs --repack of this run (opened from a directory or an archive): every frame of cameras 0 .. ncams-1
@@ -727,6 +760,10 @@ class Pipeline:
 
     def result(self, s):
         return _read_result(lib().abh_pipe_stack(self._h, s), with_dz=False)
+
+    def rects(self, s):
+        """the boxes (x, y, w, h) of stack s's last localizer round (StackResult::rects)"""
+        return _read_rects(lib().abh_pipe_stack(self._h, s))
 
     def summary(self):
         """(staged, trig, nbubbles) for every stack -- cheap fingerprint of a run."""

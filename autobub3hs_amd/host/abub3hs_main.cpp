@@ -58,6 +58,9 @@ static std::string usage()
            "  --per-event\t\t\tone analyzer at a time like the reference's loop (also chosen by -e and --debug);\n"
            "\t\t\t\tdefault: whole batches of events decoded into pinned memory and analysed together;\n"
            "\t\t\t\t-e, --debug and --per-event take a single run\n"
+           "  --peek = Dir\t\t\twith the batched path: write the six DebugPeek images of every accepted (event, camera) to\n"
+           "\t\t\t\tDir/<run_ID>/ev<event>_cam<c>_*.png, formed and encoded on the GPU (ABUB_PEEK_GPU=0: on host\n"
+           "\t\t\t\tthreads, the same files); not with -e, --debug, --per-event, --merge, --repack, --unpack, --verify-repack\n"
            "  --repack = Dir\t\twrite the run to Dir/<run_ID>/ with every frame in the packed format the GPU decodes\n"
            "\t\t\t\twithout an inflate (24x the PNG decode; file names stay; files that do not decode are copied); no GPU, no analysis,\n"
            "\t\t\t\tno -o; not with -e, --merge, --runs / --run-list, --gpu-shard, and not into the\n"
@@ -244,6 +247,8 @@ int main(int argc, char **argv)
     bool zipped = false, mask_check = false, help = argc == 1, perEvent = false;
     bool haveRun = false, haveList = false; // -r; --runs / --run-list
     std::vector<std::string> runs;          // of --runs / --run-list, in command-line order
+    std::string peekDir;                    // --peek DIR: the DebugPeek images of the batched path (BatchedRunOptions::peekDir)
+    bool havePeek = false;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i], v;
         auto value = [&](std::string &dst) {
@@ -336,6 +341,9 @@ int main(int argc, char **argv)
             verifyGpu = true;
         } else if (a == "--per-event") {
             perEvent = true;
+        } else if (a == "--peek" || a.rfind("--peek=", 0) == 0) {
+            value(peekDir);
+            havePeek = true;
         } else {
             std::cerr << "unrecognised option '" << a << "'" << std::endl;
             return -1;
@@ -344,6 +352,19 @@ int main(int argc, char **argv)
     if (help) {
         std::cout << usage() << std::endl;
         return 1;
+    }
+    if (havePeek) {
+        // --peek belongs to the batched path: the per-event loop has its own write-out (--debug), the other modes detect nothing
+        const char *bad = event_user >= 0 ? "-e/--event" : debug_mode ? "--debug" : perEvent ? "--per-event" : mergeN > 0 ? "--merge"
+                          : haveUnpack ? "--unpack" : haveRepack ? "--repack" : haveVerify ? "--verify-repack" : nullptr;
+        if (bad) {
+            std::cerr << "--peek cannot be combined with " << bad << std::endl;
+            return -1;
+        }
+        if (peekDir.empty()) {
+            std::cerr << "--peek needs the directory to write to" << std::endl;
+            return -1;
+        }
     }
     if (unpackGpu && !haveUnpack) {
         std::cerr << "--unpack-gpu is valid only together with --unpack" << std::endl;
@@ -592,6 +613,7 @@ int main(int argc, char **argv)
             specs.push_back(runSpec(dataLoc, data_series, r, zipped));
         abub::BatchedRunOptions bo = batchedOptions(ngpus, hostThreads, decodeThreads, shardRank, shardWorld, mask_dir);
         bo.outDir = out_dir;
+        bo.peekDir = peekDir;
         bo.perEventThreads = nthreads;
         if (const char *t = getenv("ABUB_TRAIN_ON_GPU"))
             bo.trainOnGpu = atoi(t) != 0;
@@ -630,6 +652,7 @@ int main(int argc, char **argv)
         perEvent = perEvent || atoi(e) != 0;
     if (!perEvent && event_user < 0 && debug_mode == 0) {
         abub::BatchedRunOptions bo = batchedOptions(ngpus, hostThreads, decodeThreads, shardRank, shardWorld, mask_dir);
+        bo.peekDir = peekDir;
         abub::BatchedRunStats bs;
         std::string why;
         int rc = 1;
@@ -647,6 +670,8 @@ int main(int argc, char **argv)
         }
         std::cout << "batched detect not used (" << why << "): falling back to the per-event loop" << std::endl;
     }
+    if (havePeek) // (ABUB_PER_EVENT=1, or a run the batched path declined)
+        std::cout << "peek: no peek images were written (the per-event loop ran; --debug is its write-out)" << std::endl;
 
     abub::RunPerEvent(FileParser, EventList, Trainers, numCams, eventDir, out_dir, run_number, frameOffset, mask_dir, nthreads,
                       event_user, debug_mode, shardRank, shardWorld);

@@ -22,6 +22,7 @@
 #include "devtrain.hpp"
 #include "driver.hpp"
 #include "hostlogic.hpp"
+#include "peek.hpp"
 #include "bmpwalk.hpp"
 #include "pngwalk.hpp"
 #include "runbatch.hpp"
@@ -557,10 +558,11 @@ int abh_analyze(void *r, const char *ev, int cam, const char *maskdir)
         run->last.error = e.what();
         return -100;
     }
-    run->last.staged = abub::analyzeUntilBubble(A, true, "", run->last.error);
+    size_t rectsBegin = 0;
+    run->last.staged = abub::analyzeUntilBubble(A, true, "", run->last.error, &rectsBegin);
     if (run->last.staged == -6)
         std::cout << run->last.error << '\n';
-    run->last.capture(*A);
+    run->last.capture(*A, rectsBegin);
     delete A;
     return run->last.staged;
 }
@@ -568,8 +570,10 @@ int abh_analyze(void *r, const char *ev, int cam, const char *maskdir)
 // A whole run (every event of the Run's parser, cameras 0..ncams-1, the Run's trained models) through the batched
 // pipeline into <outdir>abub3hs_<run>.txt; stats: [total_s, list_s, decode_s, gpu_s, write_s, frames, failed,
 // batches, events_per_batch, gpus, frames decoded on the GPU, on host threads, gpudecode_s, packed frames decoded on the GPU, BMP frames decoded on the GPU].  Returns 0, 1 when the batched path declines the run, -1 on errors.
-int abh_run_batched(void *r, int ncams, const char *maskdir, const char *outdir, const char *run_number, int frameOffset,
-                    int ngpus, int nthreads, int decodeThreads, int batchMB, int shardRank, int shardWorld, double *statsOut)
+// peekDir (may be NULL): BatchedRunOptions::peekDir; peekOut (may be NULL): [stacks, files, bytes, 1 = GPU route, seconds].
+int abh_run_batched_peek(void *r, int ncams, const char *maskdir, const char *outdir, const char *run_number, int frameOffset,
+                         int ngpus, int nthreads, int decodeThreads, int batchMB, int shardRank, int shardWorld, double *statsOut,
+                         const char *peekDir, double *peekOut)
 {
     Run *run = (Run *)r;
     try {
@@ -592,6 +596,7 @@ int abh_run_batched(void *r, int ncams, const char *maskdir, const char *outdir,
         bo.shardRank = shardRank;
         bo.shardWorld = std::max(1, shardWorld);
         bo.maskDir = maskdir ? maskdir : "";
+        bo.peekDir = peekDir ? peekDir : "";
         abub::BatchedRunStats bs;
         std::string why;
         const int rc = abub::RunBatched(run->parser, events, trainers, ncams, outdir, run_number, frameOffset, bo, &bs, &why);
@@ -604,11 +609,31 @@ int abh_run_batched(void *r, int ncams, const char *maskdir, const char *outdir,
                                   (double)bs.framesGpuUnzipped, bs.unzip_s};
             std::memcpy(statsOut, v, sizeof v);
         }
+        if (peekOut) {
+            const double v[5] = {(double)bs.peekStacks, (double)bs.peekFiles, (double)bs.peekBytes, (double)bs.peekGpu, bs.peek_s};
+            std::memcpy(peekOut, v, sizeof v);
+        }
         return rc;
     } catch (std::exception &e) {
         run->last.error = e.what();
         return -1;
     }
+}
+int abh_run_batched(void *r, int ncams, const char *maskdir, const char *outdir, const char *run_number, int frameOffset,
+                    int ngpus, int nthreads, int decodeThreads, int batchMB, int shardRank, int shardWorld, double *statsOut)
+{
+    return abh_run_batched_peek(r, ncams, maskdir, outdir, run_number, frameOffset, ngpus, nthreads, decodeThreads, batchMB, shardRank,
+                                shardWorld, statsOut, nullptr, nullptr);
+}
+
+// the host route's two peek planes (peek.hpp: peekPlanesHost); rects: nrects rows of x, y, w, h
+void abh_peek_planes_host(const uint8_t *D, const uint8_t *trig, int W, int H, int cut, const int *rects, int nrects, uint8_t *thr,
+                          uint8_t *pres)
+{
+    std::vector<cv::Rect> rs;
+    for (int i = 0; i < nrects; ++i)
+        rs.push_back(cv::Rect(rects[4 * i], rects[4 * i + 1], rects[4 * i + 2], rects[4 * i + 3]));
+    abub::peekPlanesHost(D, trig, W, H, cut, rs, thr, pres);
 }
 
 // reference main(): header once per run (AutoBubStart3.cpp:250-251)
@@ -673,6 +698,18 @@ void abh_result_state(const void *res, int *out)
     const abub::StackResult &r = *(const abub::StackResult *)res;
     const int v[6] = {r.staged, r.trig, r.status, r.loc_thres, r.ok, (int)r.bubbles.size()};
     std::memcpy(out, v, sizeof v);
+}
+// the rectangles of the result (StackResult::rects) as rows of x, y, w, h: at most cap rows are written, the count returned
+int abh_result_rects(const void *res, int *out, int cap)
+{
+    const abub::StackResult &r = *(const abub::StackResult *)res;
+    for (int i = 0; i < (int)r.rects.size() && i < cap; ++i) {
+        out[4 * i] = r.rects[i].x;
+        out[4 * i + 1] = r.rects[i].y;
+        out[4 * i + 2] = r.rects[i].width;
+        out[4 * i + 3] = r.rects[i].height;
+    }
+    return (int)r.rects.size();
 }
 const char *abh_result_error(const void *res) { return ((const abub::StackResult *)res)->error.c_str(); }
 int abh_result_ndesc(const void *res, int b) { return (int)((const abub::StackResult *)res)->bubbles[b].desc.size(); }

@@ -32,14 +32,18 @@ inline std::vector<std::string> sortedEvents(Parser &parser)
 
 // Runs FindTriggerFrame / LocalizeOMatic until a bubble is found or the search fails (:87-117).  Returns the status to
 // stage for the camera: 0 (A->BubbleList holds the bubbles), the trigger status (-3, -9) when FindTriggerFrame refuses,
-// -8 when LocalizeOMatic does, -6 on an exception, whose text goes to `error`.
-inline int analyzeUntilBubble(AnalyzerUnit *A, bool nonStopPref, const std::string &out_dir, std::string &error)
+// -8 when LocalizeOMatic does, -6 on an exception, whose text goes to `error`.  rectsBegin (may be NULL): how many
+// bubbleRects A held before its last LocalizeOMatic round.
+inline int analyzeUntilBubble(AnalyzerUnit *A, bool nonStopPref, const std::string &out_dir, std::string &error,
+                              size_t *rectsBegin = nullptr)
 {
     try {
         do {
             A->FindTriggerFrame(nonStopPref, A->MatTrigFrame + 1);
             if (!A->okToProceed)
                 return A->TriggerFrameIdentificationStatus;
+            if (rectsBegin)
+                *rectsBegin = A->bubbleRects.size();
             A->LocalizeOMatic(out_dir);
             if (!A->okToProceed)
                 return -8;

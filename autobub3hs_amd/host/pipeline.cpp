@@ -379,6 +379,7 @@ struct StackState : StackResult {
     bool trigReady = false;
     abub_trig_result trigRes{};
     bool vetoed = false;      // a bellows residual was computed for this stack in the batch
+    size_t rectsBegin = 0;    // the analyzer's bubbleRects before its last LocalizeOMatic round
 };
 
 // Persistent worker pool shared by all stack groups: a group that is waiting for the GPU lends its
@@ -1546,9 +1547,10 @@ private:
             t.ModelId = 0; // always (re)uploaded
             Trainer *tp = &t;
             L3Localizer A(evName, "", c, true, &tp, maskDir, mp.clone());
-            st_.staged = analyzeUntilBubble(&A, true, "", st_.error);
+            size_t rectsBegin = 0;
+            st_.staged = analyzeUntilBubble(&A, true, "", st_.error, &rectsBegin);
             if (st_.staged != -6) // (after an exception the stack keeps the state its batched attempt ended with)
-                st_.capture(A);
+                st_.capture(A, rectsBegin);
         } catch (std::exception &ex) {
             st_.error = ex.what();
             st_.staged = -6;
@@ -1582,6 +1584,7 @@ private:
             st_.analyzer.reset(new L3Localizer(meta.empty() ? std::to_string(e) : meta[s].eventID, "", c, true, &t, maskDir,
                                                (meta.empty() ? parser : metaParser).clone()));
             st_.analyzer->AttachEventData(&st_.data);
+            st_.rectsBegin = 0;
         });
         HIPOK(hipEventSynchronize(G.stage1Done.get()));
         G.stats.timing.stage1Ms = nowMs() - t0;
@@ -1651,7 +1654,7 @@ private:
         // results out, analyzers released
         pool->parallelFor(ns, [&](int k) {
             StackState &st_ = stacks[G.s0 + k];
-            st_.capture(*st_.analyzer);
+            st_.capture(*st_.analyzer, st_.rectsBegin);
             st_.analyzer.reset();
         });
     }
@@ -2216,6 +2219,7 @@ private:
         st_.needBellows = false;
         AnalyzerUnit *A = st_.analyzer.get();
         try {
+            st_.rectsBegin = A->bubbleRects.size(); // (a round the veto serves throws before it pushes any)
             A->LocalizeOMatic("");
             if (!A->okToProceed) {
                 st_.staged = -8;
@@ -2266,6 +2270,8 @@ void run(RunPipeline &p, const uint8_t *d_frames, const uint8_t *d_mu, const uin
 }
 void writeEvent(RunPipeline &p, int k, int eventNumber, OutputWriter &out) { p.writeEvent(k, eventNumber, out); }
 int bellowsVetoed(const RunPipeline &p) { return (int)p.stats.bellows.vetoed; }
+const StackResult &stackResult(const RunPipeline &p, int s) { return p.stacks[s]; }
+const std::string &stackEventID(const RunPipeline &p, int s) { return p.meta[s].eventID; }
 
 } // namespace abub
 

@@ -56,6 +56,10 @@ void setStackMeta(RunPipeline &p, std::vector<StackMeta> &&meta);
 void run(RunPipeline &p, const uint8_t *d_frames, const uint8_t *d_mu, const uint8_t *d_sigma6, hipStream_t stream);
 // stacks of the last run whose bellows veto ran inside the batch
 int bellowsVetoed(const RunPipeline &p);
+// stack s = event * C + camera of the last run: its result, and the event id setStackMeta gave it
+struct StackResult;
+const StackResult &stackResult(const RunPipeline &p, int s);
+const std::string &stackEventID(const RunPipeline &p, int s);
 // event k's cameras of the last run staged into `out` and written as one block
 void writeEvent(RunPipeline &p, int k, int eventNumber, OutputWriter &out);
 

@@ -33,8 +33,10 @@
 #include "driver.hpp"
 #include "framefiles.hpp"
 #include "holders.hpp"
+#include "peek.hpp"
 #include "pipeline.hpp"
 #include "pngwalk.hpp"
+#include "stackresult.hpp"
 #include "runbatch.hpp"
 
 namespace abub {
@@ -211,6 +213,19 @@ int runBatchedOn(Workers &ws, Parser *parser, const std::vector<std::string> &Ev
         G = Ggpu + Ghost;
     }
     const int nb = ((int)mine.size() + G - 1) / G;
+    // --peek: where the images go and which route forms them
+    const bool peekOn = !opt.peekDir.empty();
+    const std::string peekRunDir = opt.peekDir + (opt.peekDir.empty() || opt.peekDir.back() == '/' ? "" : "/") + run_number + "/";
+    bool peekGpu = opt.peekGpu != 0;
+    int peekMaxStacks = opt.peekMaxStacks;
+    if (peekOn) {
+        if (const char *e = getenv("ABUB_PEEK_GPU"))
+            if (opt.peekGpu < 0)
+                peekGpu = atoi(e) != 0;
+        if (const char *e = getenv("ABUB_PEEK_BATCH"))
+            peekMaxStacks = std::max(1, atoi(e));
+        st.peekGpu = peekGpu ? 1 : 0;
+    }
     int ndev = 0;
     HIPOK(hipGetDeviceCount(&ndev));
     if (ndev <= 0)
@@ -407,6 +422,29 @@ int runBatchedOn(Workers &ws, Parser *parser, const std::vector<std::string> &Ev
                     if (atoi(tf) == b)
                         throw std::runtime_error("injected failure of batch " + std::to_string(b) + " (ABUB_TEST_FAIL_BATCH)");
                 run(*pipe, d_frames, d_mu, d_s6, cs);
+                // ---- the DebugPeek images of the batch's accepted stacks, while its frames are still resident -------------------
+                PeekStats ps;
+                double pms = 0;
+                if (peekOn) {
+                    const double tk = nowMs();
+                    std::vector<PeekStack> accepted;
+                    for (int s = 0; s < nEv * C; ++s) {
+                        const StackResult &res = stackResult(*pipe, s);
+                        if (res.staged != 0 || res.bubbles.empty())
+                            continue;
+                        PeekStack ks;
+                        ks.eventID = stackEventID(*pipe, s);
+                        ks.cam = s % C;
+                        ks.trigFrame = (uint32_t)(s * Fmax + res.trig);
+                        ks.preFrame = (uint32_t)(s * Fmax + peekPreFrame(res.trig, tss[s % C]));
+                        ks.loc_thres = res.loc_thres;
+                        ks.rects = res.rects;
+                        accepted.push_back(std::move(ks));
+                    }
+                    writePeekImages(W, H, C, d_frames, (size_t)nEv * perEvent, d_mu, d_s6, accepted, peekRunDir, peekGpu,
+                                    std::max<size_t>(opt.batchBytes / 8, (size_t)64 << 20), peekMaxStacks, nthr, cs, ps);
+                    pms = nowMs() - tk;
+                }
                 const double gms = nowMs() - tg;
                 double wms = 0;
                 {
@@ -438,6 +476,11 @@ int runBatchedOn(Workers &ws, Parser *parser, const std::vector<std::string> &Ev
                     st.framesGpuUnzipped += R.unzipped;
                     st.unzip_s += R.unzip_s;
                     st.gpudecode_s += pngms * 1e-3;
+                    st.peekStacks += ps.stacks;
+                    st.peekFiles += ps.files;
+                    st.peekBytes += ps.bytes;
+                    st.peekSubBatches += ps.subBatches;
+                    st.peek_s += pms * 1e-3;
                 }
                 slot ^= 1;
             }
@@ -538,6 +581,8 @@ void PrintBatchedLine(const BatchedRunStats &bs)
            bs.events, bs.batches, bs.eventsPerBatch, bs.gpus, bs.frames, bs.W, bs.H, bs.framesGpuDecoded, bs.framesHostDecoded,
            bs.framesFailed, bs.total_s, bs.list_s, bs.decode_s, bs.gpu_s, bs.gpudecode_s, bs.write_s,
            bs.total_s > 0 ? (bs.frames + bs.framesFailed) / bs.total_s : 0.0);
+    if (bs.peekGpu >= 0)
+        printf("peek: %lld stacks, %lld files, %lld bytes, %s\n", bs.peekStacks, bs.peekFiles, bs.peekBytes, bs.peekGpu ? "gpu" : "host");
 }
 
 // (a line for stdout, or held back in pr.log)

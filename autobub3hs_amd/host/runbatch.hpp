@@ -32,6 +32,13 @@ struct BatchedRunOptions {
     std::string outDir;             // where every run's abub3hs_<run>.txt goes (ends with '/')
     int trainOnGpu = 1;             // 1: TrainOnDevice (the host Trainer where it declines a run); 0: the host Trainer
     int perEventThreads = 16;       // threads of the per-event loop of a run the batched path declines
+    // abub3hs --peek DIR: the six DebugPeek images of every accepted stack (staged 0, at least one bubble) written to
+    // <peekDir>/<run_number>/ by a post-pass per batch (peek.hpp); empty = off: no launch, no copy, no file
+    std::string peekDir;
+    int peekGpu = -1;               // 1: abub_peek_planes_dev + abub_png_encode_dev; 0: the host route, which is the definition;
+                                    // -1: 1 unless ABUB_PEEK_GPU=0
+    int peekMaxStacks = 0;          // stacks per sub-batch of the post-pass at most (0: what batchBytes / 8 allows;
+                                    // ABUB_PEEK_BATCH=n, a test knob, overrides)
 };
 
 struct BatchedRunStats {
@@ -45,6 +52,9 @@ struct BatchedRunStats {
     double unzip_s = 0;                                    // ... of decode_s: upload of the compressed bytes, kernels, copy back, wait
     double gpudecode_s = 0;                                // upload of the files + the decode kernels, summed over batches
     int events = 0, batches = 0, eventsPerBatch = 0, W = 0, H = 0, Fmax = 0, gpus = 0;
+    long long peekStacks = 0, peekFiles = 0, peekBytes = 0; // peekDir: accepted stacks, files written, their bytes
+    int peekGpu = -1, peekSubBatches = 0;                   // ... the route taken (-1: off, 0: host, 1: GPU), sub-batches of the post-pass
+    double peek_s = 0;                                      // ... of gpu_s: the post-pass
 };
 
 // Detects every event of `EventList` (already in output order) with the trained `Trainers` (one per camera) and

@@ -4,6 +4,8 @@
 #ifndef ABUB3HS_STACKRESULT_HPP
 #define ABUB3HS_STACKRESULT_HPP
 
+#include <algorithm>
+#include <cstddef>
 #include <memory>
 #include <string>
 #include <vector>
@@ -53,10 +55,13 @@ struct StackResult {
     int trig = 0, status = 0, loc_thres = 0, ok = 0; // the analyzer's MatTrigFrame, TriggerFrameIdentificationStatus, ...
     std::vector<BubbleOut> bubbles;
     std::string error; // the exception text behind a -6
+    std::vector<cv::Rect> rects; // the analyzer's bubbleRects of its last LocalizeOMatic round (the boxes of _4_BubbleDetected)
 
     // the analyzer's state and the track record of every bubble (`staged` and `error` belong to whoever drove it)
-    void capture(AnalyzerUnit &A)
+    // rectsBegin: how many bubbleRects the analyzer held before that round (the list is never cleared between retries)
+    void capture(AnalyzerUnit &A, size_t rectsBegin = 0)
     {
+        rects.assign(A.bubbleRects.begin() + (std::ptrdiff_t)std::min(rectsBegin, A.bubbleRects.size()), A.bubbleRects.end());
         trig = A.MatTrigFrame;
         status = A.TriggerFrameIdentificationStatus;
         loc_thres = A.loc_thres;

@@ -737,6 +737,43 @@ typedef struct abub_cmp_result {
 int abub_frames_compare_dev(const uint8_t *a, size_t a_bytes, const uint8_t *b, size_t b_bytes, const abub_cmp_pair *pairs,
                             int npairs, size_t frame_bytes, abub_cmp_result *results, void *stream);
 
+/* ---- the two DebugPeek planes of a batch of resident frames (abub_peek.hip) ------------------------------------------
+ * What L3Localizer::CalculateInitialBubbleParams builds on the analyzer's thread for its debug write-out (reference
+ * L3Localizer.cpp:252-257, 397, 448; DESIGN section 3, "The peek planes"), for a batch of items.  Per item two W x H u8
+ * planes are written into `out`:
+ *   the thresholded image  out[thr_out + i] = diff[diff + i] > thr ? 255 : 0 -- the mask contoursOfCurrentImage hands back
+ *                          from foregroundKept(thr, -1), written as _3_OtsuThresholded;
+ *   the presentation frame the W * H bytes at frames + frame, then cv::rectangle (host/cvlite.cpp) of every rectangle
+ *                          rects[rect_begin .. rect_begin + rect_count): 255 on the rows y and y + h - 1 and the columns x
+ *                          and x + w - 1, each clipped to the frame; w <= 0 or h <= 0 draws nothing; rectangles may
+ *                          overlap and may lie partly or wholly outside the frame; written as _4_BubbleDetected.
+ * The planes lie at multiples of 16, where abub_png_encode_dev takes them through src[].  A copy launch, then (nrects > 0)
+ * a draw launch on `stream`; no flags, no atomics, no host synchronisation, no allocation.  A source whose address is a
+ * multiple of 16 is read 16 bytes at a time; any other is as exact, and slower. */
+typedef struct abub_peek_item {
+    uint64_t diff;      /* byte offset of D from `diff`, any alignment */
+    uint64_t frame;     /* byte offset of the trigger frame from `frames`, any alignment */
+    uint64_t thr_out;   /* byte offset of the thresholded plane from `out`, a multiple of 16 */
+    uint64_t pres_out;  /* byte offset of the presentation plane from `out`, a multiple of 16 */
+    int32_t thr;        /* any value: below 0 the whole plane is 255, from 255 on it is 0 */
+    int32_t rect_begin; /* the item's rectangles in `rects` */
+    int32_t rect_count;
+    int32_t reserved;
+} abub_peek_item;
+typedef struct abub_peek_rect { int32_t x, y, w, h; } abub_peek_rect;
+#define ABUB_PEEK_E_SRC 1  /* diff + W*H > diff_bytes or frame + W*H > frames_bytes */
+#define ABUB_PEEK_E_DST 2  /* a plane not at a multiple of 16, running past out_bytes, or the two planes overlapping */
+#define ABUB_PEEK_E_RECT 3 /* rect_begin < 0, rect_count < 0 or rect_begin + rect_count > nrects */
+/* Every pointer is a device pointer; items is 8-byte, rects and status 4-byte, out 16-byte aligned; `out` overlaps neither
+ * `diff` nor `frames`, which may be the same buffer; planes of different items do not overlap.  status[nitems] is written
+ * for every item: 0, or the first ABUB_PEEK_E_* that applies in the order above -- then nothing of the item is read and
+ * not one byte of its planes is written.  Nothing is written outside the two planes of an item.  rects may be null when
+ * nrects == 0.  Null pointers, negative counts, W or H outside [1, 65535] or a misaligned buffer: ABUB_E_INVALID before
+ * anything touches the device.  nitems == 0: ABUB_OK, nothing is touched. */
+int abub_peek_planes_dev(const uint8_t *diff, size_t diff_bytes, const uint8_t *frames, size_t frames_bytes,
+                         const abub_peek_item *items, int nitems, const abub_peek_rect *rects, int nrects, int W, int H,
+                         uint8_t *out, size_t out_bytes, int32_t *status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
