@@ -8,7 +8,7 @@
 // workgroup ever waits for another one inside a launch.
 //   measure      one wave per row: the blocks' widths, the row's size and its check -> scratch
 //   place rows   one workgroup per frame: row sizes -> row offsets, the frame's payload and file length
-//   place files  one workgroup: file lengths -> off, status, *total
+//   place files  one workgroup: file lengths -> off, status, *total (k_enc_place_files, abub_enc.hpp: shared with the PNG encoder)
 //   write        one wave per row: table entry, widths, blocks; the waves of row 0 also the header and the table padding
 // Every output byte is written once by one lane, so nothing is cleared beforehand and no atomics are needed.  The string
 // bytes of a block are gathered: lane i + 1 collects the residuals that reach into string byte i with ds_bpermute (at most
@@ -18,65 +18,21 @@
 // written only when off + len <= out_cap (E_CAP otherwise); within it every store lies below len: the widths come from
 // measure (<= 8 by construction, clamped again where they are read), and the row offsets are sums of the sizes those widths
 // give.  Every loop bound is a function of W, H and nframes.
-#include "abub_dev.hpp"
-#include <stddef.h>
+#include "abub_enc.hpp"
 
 namespace {
 
 #define ABFE_WAVES 4         /* waves per block, a row each at a time */
 #define ABFE_ROWS_PER_WAVE 8 /* rows a wave handles, where the frame has that many */
-#define ABFE_SCAN 256        /* threads of the two place kernels */
 
 __device__ __forceinline__ uint32_t abfe_block_bytes(int n, uint32_t b) { return 1u + (((uint32_t)(n - 1) * b + 7u) >> 3); }
-__device__ __forceinline__ uint32_t abfe_wave_sum(uint32_t v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1)
-        v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ bool abfe_src_ok(uint64_t s, uint64_t pixels_bytes, uint64_t P)
-{
-    return s <= pixels_bytes && pixels_bytes - s >= P;
-}
-
 // pixel `lane` of the block at `blk` (n pixels) and its zigzagged difference to the left neighbour (0 for lane 0 and the
 // lanes behind the block)
 __device__ __forceinline__ void abfe_load_block(const uint8_t *__restrict__ blk, int n, int lane, uint32_t &p, uint32_t &z)
 {
     p = lane < n ? (uint32_t)blk[lane] : 0u;
-    uint32_t prev = __builtin_amdgcn_update_dpp(0u, p, DPP_WAVE_SHR1, 0xf, 0xf, false);
-    // (the shift stays a v_mov_b32_dpp of its own: folded into the subtraction -- v_subrev_u32_dpp with p as both operands --
-    // the difference came out negated on gfx950)
-    asm volatile("" : "+v"(prev));
-    const int32_t s = (int32_t)(int8_t)(uint8_t)(p - prev);
+    const int32_t s = (int32_t)(int8_t)(uint8_t)(p - enc_left_neighbour(p));
     z = (lane >= 1 && lane < n) ? (uint32_t)((s << 1) ^ (s >> 7)) & 0xffu : 0u;
-}
-
-// inclusive scan over the ABFE_SCAN threads of a block (sh: one word per wave); every thread calls it
-template <class T>
-__device__ __forceinline__ T abfe_block_scan(T v, T *sh, T &blockTotal)
-{
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const T t = __shfl_up(v, o);
-        if (lane >= o)
-            v += t;
-    }
-    __syncthreads(); // (sh may still be read by the round before)
-    if (lane == 63)
-        sh[wv] = v;
-    __syncthreads();
-    T before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < ABFE_SCAN / 64; ++w) {
-        const T t = sh[w];
-        before += w < wv ? t : (T)0;
-        all += t;
-    }
-    blockTotal = all;
-    return v + before;
 }
 
 // rows[f * H + y] = (size of row y, its check); widths[(f * H + y) * nblk + k] = bit width of block k
@@ -87,7 +43,7 @@ __global__ __launch_bounds__(64 * ABFE_WAVES) void k_abf_enc_measure(const uint8
     const uint32_t f = blockIdx.x;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const uint64_t P = (uint64_t)W * (uint64_t)H, s = src[f];
-    if (!abfe_src_ok(s, pixels_bytes, P))
+    if (!enc_src_ok(s, pixels_bytes, P))
         return; // (nobody reads this frame's scratch)
     const uint8_t *img = pixels + s;
     const uint32_t nblk = ((uint32_t)W + 63u) >> 6;
@@ -116,20 +72,20 @@ __global__ __launch_bounds__(64 * ABFE_WAVES) void k_abf_enc_measure(const uint8
             if (lane < nb)
                 fw[(uint64_t)y * nblk + k0 + lane] = (uint8_t)mine;
         }
-        acc = abfe_wave_sum(acc);
+        acc = enc_wave_sum(acc);
         if (lane == 0)
             frows[y] = make_uint2(rsize, acc);
     }
 }
 
 // rows[f * H + y].x: size -> offset of the row in the payload; flen[f] = the file's length (0 for a frame that is not read)
-__global__ __launch_bounds__(ABFE_SCAN) void k_abf_enc_place_rows(uint64_t pixels_bytes, const uint64_t *__restrict__ src, int W,
+__global__ __launch_bounds__(ENC_SCAN) void k_abf_enc_place_rows(uint64_t pixels_bytes, const uint64_t *__restrict__ src, int W,
                                                                    int H, uint2 *__restrict__ rows, uint32_t *__restrict__ flen)
 {
-    __shared__ uint32_t sh[ABFE_SCAN / 64];
+    __shared__ uint32_t sh[ENC_SCAN / 64];
     const uint32_t f = blockIdx.x;
     const uint64_t P = (uint64_t)W * (uint64_t)H;
-    if (!abfe_src_ok(src[f], pixels_bytes, P)) { // (the same answer in every thread)
+    if (!enc_src_ok(src[f], pixels_bytes, P)) { // (the same answer in every thread)
         if (threadIdx.x == 0)
             flen[f] = 0;
         return;
@@ -137,46 +93,17 @@ __global__ __launch_bounds__(ABFE_SCAN) void k_abf_enc_place_rows(uint64_t pixel
     const uint32_t nblk = ((uint32_t)W + 63u) >> 6;
     uint2 *frows = rows + (uint64_t)f * (uint32_t)H;
     uint32_t base = 0; // (a file is shorter than 2^32 bytes: abub_abf_file_bound)
-    for (int y0 = 0; y0 < H; y0 += ABFE_SCAN) {
+    for (int y0 = 0; y0 < H; y0 += ENC_SCAN) {
         const int y = y0 + (int)threadIdx.x;
         const uint32_t size = y < H ? frows[y].x : 0u;
         uint32_t all;
-        const uint32_t incl = abfe_block_scan(size, sh, all);
+        const uint32_t incl = enc_block_scan(size, sh, all);
         if (y < H)
             frows[y].x = base + incl - size;
         base += all;
     }
     if (threadIdx.x == 0)
         flen[f] = 32u + 8u * (uint32_t)H + (((uint32_t)H * nblk + 3u) & ~3u) + base;
-}
-
-// files[f] = {off, len, status} with off[0] = 0, off[f + 1] = align16(off[f] + len[f]); *total = the end of the last file
-__global__ __launch_bounds__(ABFE_SCAN) void k_abf_enc_place_files(uint64_t pixels_bytes, const uint64_t *__restrict__ src,
-                                                                    int nframes, int W, int H, const uint32_t *__restrict__ flen,
-                                                                    uint64_t out_cap, abub_abf_file *__restrict__ files,
-                                                                    uint64_t *__restrict__ total)
-{
-    __shared__ unsigned long long sh[ABFE_SCAN / 64];
-    const uint64_t P = (uint64_t)W * (uint64_t)H;
-    unsigned long long base = 0;
-    for (int f0 = 0; f0 < nframes; f0 += ABFE_SCAN) {
-        const int f = f0 + (int)threadIdx.x;
-        const uint32_t len = f < nframes ? flen[f] : 0u;
-        const unsigned long long room = ((unsigned long long)len + 15ull) & ~15ull;
-        unsigned long long all;
-        const unsigned long long incl = abfe_block_scan(room, sh, all);
-        if (f < nframes) {
-            const uint64_t off = base + incl - room;
-            abub_abf_file r;
-            r.off = off;
-            r.len = len;
-            r.status = !abfe_src_ok(src[f], pixels_bytes, P) ? ABUB_ABF_ENC_E_SRC : off + len > out_cap ? ABUB_ABF_ENC_E_CAP : 0;
-            files[f] = r;
-            if (f == nframes - 1)
-                *total = off + len;
-        }
-        base += all;
-    }
 }
 
 // ceil(32768 / b) for b = 1 .. 8, 16 bits each: t / b == (t * r) >> 15 for t <= 504 (the error t * (r - 32768 / b) / 32768
@@ -267,8 +194,6 @@ __global__ __launch_bounds__(64 * ABFE_WAVES) void k_abf_enc_write(const uint8_t
     }
 }
 
-inline size_t align16z(size_t v) { return (v + 15) & ~(size_t)15; }
-
 } // namespace
 
 extern "C" size_t abub_abf_file_bound(int W, int H)
@@ -293,16 +218,9 @@ extern "C" int abub_abf_encode_dev(const uint8_t *pixels, size_t pixels_bytes, c
                                    uint8_t *out, size_t out_cap, abub_abf_file *files, uint64_t *total, void *scratch,
                                    size_t scratch_bytes, void *stream)
 {
-    if (!pixels || !src || !out || !files || !total || !scratch || nframes < 0)
-        return set_err(ABUB_E_INVALID, "abub_abf_encode_dev: null pointer or negative count");
-    if (W < 1 || W > 65535 || H < 1 || H > 65535)
-        return set_err(ABUB_E_INVALID, "abub_abf_encode_dev: width and height must be in [1, 65535]");
-    if (!abub_abf_file_bound(W, H))
-        return set_err(ABUB_E_INVALID, "abub_abf_encode_dev: a W x H frame whose file may reach 4 GB");
-    if (scratch_bytes < abub_abf_encode_scratch_bytes(nframes, W, H))
-        return set_err(ABUB_E_INVALID, "abub_abf_encode_dev: scratch smaller than abub_abf_encode_scratch_bytes");
-    if (((uintptr_t)scratch | (uintptr_t)src | (uintptr_t)files | (uintptr_t)total) & 7)
-        return set_err(ABUB_E_INVALID, "abub_abf_encode_dev: src, files, total and scratch must be 8-byte aligned");
+    if (const int e = enc_check_args("abub_abf_encode", abub_abf_file_bound, abub_abf_encode_scratch_bytes, pixels, src, nframes, W, H, out,
+                                     files, total, scratch, scratch_bytes))
+        return e;
     if (nframes == 0)
         return ABUB_OK;
     hipStream_t st = (hipStream_t)stream;
@@ -315,9 +233,10 @@ extern "C" int abub_abf_encode_dev(const uint8_t *pixels, size_t pixels_bytes, c
     const dim3 grid((unsigned)nframes, (unsigned)((H + perBlock - 1) / perBlock));
     k_abf_enc_measure<<<grid, 64 * ABFE_WAVES, 0, st>>>(pixels, (uint64_t)pixels_bytes, src, W, H, rows, widths);
     HIPCHK(hipGetLastError());
-    k_abf_enc_place_rows<<<(unsigned)nframes, ABFE_SCAN, 0, st>>>((uint64_t)pixels_bytes, src, W, H, rows, flen);
+    k_abf_enc_place_rows<<<(unsigned)nframes, ENC_SCAN, 0, st>>>((uint64_t)pixels_bytes, src, W, H, rows, flen);
     HIPCHK(hipGetLastError());
-    k_abf_enc_place_files<<<1, ABFE_SCAN, 0, st>>>((uint64_t)pixels_bytes, src, nframes, W, H, flen, (uint64_t)out_cap, files, total);
+    k_enc_place_files<<<1, ENC_SCAN, 0, st>>>((uint64_t)pixels_bytes, src, nframes, (uint64_t)W * (uint64_t)H, flen, (uint32_t)sizeof *flen,
+                                               (uint64_t)out_cap, files, total);
     HIPCHK(hipGetLastError());
     k_abf_enc_write<<<grid, 64 * ABFE_WAVES, 0, st>>>(pixels, src, W, H, rows, widths, files, out);
     HIPCHK(hipGetLastError());

@@ -12,7 +12,7 @@
 //   codes        one wave per frame: code lengths (limit 15), canonical codes, the code-length code (limit 7), the header bits
 //   measure      one wave per row: the sum of its symbols' lengths
 //   place rows   one workgroup per frame: row bit counts -> 64-bit bit offsets behind the header; file length; Adler-32
-//   place files  one workgroup: file lengths -> off, status, *total
+//   place files  one workgroup: file lengths -> off, status, *total (k_enc_place_files, abub_enc.hpp: the ABF encoder's)
 //   write        one wave per row: the bits; row 0 also the container's head and the header bits, the last row the tail
 //   crc          one lane per 1 KiB segment of "IDAT" + data, table driven (the table is built in LDS)
 //   fold         one lane per frame: crc = mulmod(crc, x^(8 len)) ^ crc_seg over the segments in order
@@ -26,15 +26,13 @@
 // it every store of the deflate data is checked against the byte count place rows derived (the lengths are clamped to 15
 // where they are read, so the counts bound the positions whatever the scratch holds).  Every loop bound is a function of
 // W, H and nframes, or a constant.
-#include "abub_dev.hpp"
-#include <stddef.h>
+#include "abub_enc.hpp"
 
 namespace {
 
 #define PNGE_WAVES 4          /* waves per block of histogram and measure, a row each at a time */
 #define PNGE_ROWS_PER_WAVE 8  /* rows a wave handles, where the frame has that many */
 #define PNGE_WRITE_ROWS 8     /* rows a (one wave) block of write handles */
-#define PNGE_SCAN 256         /* threads of the two place kernels */
 #define PNGE_SEG 1024u        /* bytes per CRC segment */
 #define PNGE_TAB 260          /* words per frame of the histogram and of the code table (257 used; [257] = header bits) */
 #define PNGE_HDR_WORDS 60     /* 3 + 14 + 57 + 258 * 7 = 1880 header bits at the most */
@@ -54,27 +52,13 @@ struct PngeFrame {
     uint64_t nbytes; // of the deflate block
 };
 
-__device__ __forceinline__ uint32_t pnge_wave_sum(uint32_t v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1)
-        v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ bool pnge_src_ok(uint64_t s, uint64_t pixels_bytes, uint64_t P)
-{
-    return s <= pixels_bytes && pixels_bytes - s >= P;
-}
-
 // symbol c0 + lane of a row (W + 1 symbols: the filter byte 1, the first pixel, the differences to the left neighbour)
 __device__ __forceinline__ uint32_t pnge_row_symbol(const uint8_t *__restrict__ row, int W, int c0, int lane, bool &valid)
 {
     const int c = c0 + lane;
     valid = c <= W;
     const uint32_t q = (c >= 1 && c <= W) ? (uint32_t)row[c - 1] : 0u;
-    uint32_t prev = __builtin_amdgcn_update_dpp(0u, q, DPP_WAVE_SHR1, 0xf, 0xf, false);
-    // (the shift stays a v_mov_b32_dpp of its own: folded into the subtraction the difference came out negated on gfx950)
-    asm volatile("" : "+v"(prev));
+    uint32_t prev = enc_left_neighbour(q);
     if (lane == 0)
         prev = (c >= 2 && c <= W) ? (uint32_t)row[c - 2] : 0u;
     return c == 0 ? 1u : (q - prev) & 0xffu;
@@ -91,32 +75,6 @@ __device__ __forceinline__ uint32_t pnge_symbol_at(const uint8_t *__restrict__ i
     return c == 1 ? (uint32_t)row[0] : ((uint32_t)row[c - 1] - (uint32_t)row[c - 2]) & 0xffu;
 }
 
-// inclusive scan over the PNGE_SCAN threads of a block (sh: one word per wave); every thread calls it
-template <class T>
-__device__ __forceinline__ T pnge_block_scan(T v, T *sh, T &blockTotal)
-{
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const T t = __shfl_up(v, o);
-        if (lane >= o)
-            v += t;
-    }
-    __syncthreads(); // (sh may still be read by the round before)
-    if (lane == 63)
-        sh[wv] = v;
-    __syncthreads();
-    T before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < PNGE_SCAN / 64; ++w) {
-        const T t = sh[w];
-        before += w < wv ? t : (T)0;
-        all += t;
-    }
-    blockTotal = all;
-    return v + before;
-}
-
 __global__ __launch_bounds__(64 * PNGE_WAVES) void k_png_enc_hist(const uint8_t *__restrict__ pixels, uint64_t pixels_bytes,
                                                                   const uint64_t *__restrict__ src, int W, int H,
                                                                   uint32_t *__restrict__ hist, PngeRow *__restrict__ rows)
@@ -125,7 +83,7 @@ __global__ __launch_bounds__(64 * PNGE_WAVES) void k_png_enc_hist(const uint8_t 
     const uint32_t f = blockIdx.x;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const uint64_t P = (uint64_t)W * (uint64_t)H, s = src[f];
-    if (!pnge_src_ok(s, pixels_bytes, P))
+    if (!enc_src_ok(s, pixels_bytes, P))
         return; // (the same in every thread; nobody reads this frame's scratch)
     for (int b = threadIdx.x; b < 257; b += 64 * PNGE_WAVES)
         sh[b] = 0;
@@ -145,8 +103,8 @@ __global__ __launch_bounds__(64 * PNGE_WAVES) void k_png_enc_hist(const uint8_t 
                 B = (B + ((n - (uint32_t)(c0 + lane)) % PNGE_MOD) * d) % PNGE_MOD;
             }
         }
-        A = pnge_wave_sum(A % PNGE_MOD);
-        B = pnge_wave_sum(B);
+        A = enc_wave_sum(A % PNGE_MOD);
+        B = enc_wave_sum(B);
         if (lane == 0) {
             frows[y].A = A % PNGE_MOD;
             frows[y].B = B % PNGE_MOD;
@@ -261,7 +219,7 @@ __global__ __launch_bounds__(64) void k_png_enc_codes(uint64_t pixels_bytes, con
     __shared__ uint8_t len[258], cllen[19];
     const uint32_t f = blockIdx.x;
     const int lane = threadIdx.x;
-    if (!pnge_src_ok(src[f], pixels_bytes, (uint64_t)W * (uint64_t)H))
+    if (!enc_src_ok(src[f], pixels_bytes, (uint64_t)W * (uint64_t)H))
         return;
     for (int s = lane; s < 257; s += 64)
         cnt[s] = s == 256 ? 1u : hist[(uint64_t)f * PNGE_TAB + s];
@@ -322,7 +280,7 @@ __global__ __launch_bounds__(64 * PNGE_WAVES) void k_png_enc_measure(const uint8
     const uint32_t f = blockIdx.x;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const uint64_t P = (uint64_t)W * (uint64_t)H, s = src[f];
-    if (!pnge_src_ok(s, pixels_bytes, P))
+    if (!enc_src_ok(s, pixels_bytes, P))
         return;
     for (int b = threadIdx.x; b < 257; b += 64 * PNGE_WAVES)
         len[b] = (uint8_t)min(codes[(uint64_t)f * PNGE_TAB + b] >> 16, 15u);
@@ -337,21 +295,21 @@ __global__ __launch_bounds__(64 * PNGE_WAVES) void k_png_enc_measure(const uint8
             const uint32_t d = pnge_row_symbol(row, W, c0, lane, valid);
             bits += valid ? (uint32_t)len[d] : 0u;
         }
-        bits = pnge_wave_sum(bits);
+        bits = enc_wave_sum(bits);
         if (lane == 0)
             frows[y].bit = bits;
     }
 }
 
 // rows[f * H + y].bit: count -> offset; info[f] = file length, Adler-32, bytes of the deflate block
-__global__ __launch_bounds__(PNGE_SCAN) void k_png_enc_place_rows(uint64_t pixels_bytes, const uint64_t *__restrict__ src, int W,
+__global__ __launch_bounds__(ENC_SCAN) void k_png_enc_place_rows(uint64_t pixels_bytes, const uint64_t *__restrict__ src, int W,
                                                                    int H, const uint32_t *__restrict__ codes,
                                                                    PngeRow *__restrict__ rows, PngeFrame *__restrict__ info)
 {
-    __shared__ unsigned long long sh64[PNGE_SCAN / 64];
-    __shared__ uint32_t sh32[PNGE_SCAN / 64];
+    __shared__ unsigned long long sh64[ENC_SCAN / 64];
+    __shared__ uint32_t sh32[ENC_SCAN / 64];
     const uint32_t f = blockIdx.x;
-    if (!pnge_src_ok(src[f], pixels_bytes, (uint64_t)W * (uint64_t)H)) { // (the same answer in every thread)
+    if (!enc_src_ok(src[f], pixels_bytes, (uint64_t)W * (uint64_t)H)) { // (the same answer in every thread)
         if (threadIdx.x == 0) {
             PngeFrame z;
             z.flen = 0;
@@ -366,7 +324,7 @@ __global__ __launch_bounds__(PNGE_SCAN) void k_png_enc_place_rows(uint64_t pixel
     const uint32_t nmod = ((uint32_t)W + 1u) % PNGE_MOD;
     unsigned long long base = min(tab[257], 32u * PNGE_HDR_WORDS); // the rows start behind the header bits
     uint32_t a = 1, b = 0;                                          // Adler-32 in front of the rows of this round
-    for (int y0 = 0; y0 < H; y0 += PNGE_SCAN) {
+    for (int y0 = 0; y0 < H; y0 += ENC_SCAN) {
         const int y = y0 + (int)threadIdx.x;
         PngeRow r;
         r.bit = 0;
@@ -374,16 +332,16 @@ __global__ __launch_bounds__(PNGE_SCAN) void k_png_enc_place_rows(uint64_t pixel
         if (y < H)
             r = frows[y];
         unsigned long long all;
-        const unsigned long long incl = pnge_block_scan((unsigned long long)r.bit, sh64, all);
+        const unsigned long long incl = enc_block_scan((unsigned long long)r.bit, sh64, all);
         if (y < H)
             frows[y].bit = base + incl - r.bit;
         base += all;
         // a row of n bytes takes (a, b) to (a + A, b + n a + B): a in front of each row by a scan, b by a sum
         uint32_t allA, allT;
-        const uint32_t inclA = pnge_block_scan(r.A, sh32, allA); // (256 values below 65521)
+        const uint32_t inclA = enc_block_scan(r.A, sh32, allA); // (256 values below 65521)
         const uint32_t a0 = (a + inclA - r.A) % PNGE_MOD;
         const uint32_t term = y < H ? (uint32_t)(((unsigned long long)nmod * a0 + r.B) % PNGE_MOD) : 0u;
-        pnge_block_scan(term, sh32, allT);
+        enc_block_scan(term, sh32, allT);
         a = (a + allA) % PNGE_MOD;
         b = (b + allT) % PNGE_MOD;
     }
@@ -394,35 +352,6 @@ __global__ __launch_bounds__(PNGE_SCAN) void k_png_enc_place_rows(uint64_t pixel
         z.flen = (uint32_t)(PNGE_FIXED + z.nbytes); // (below 2^32: abub_png_file_bound)
         z.adler = b << 16 | a;
         info[f] = z;
-    }
-}
-
-// files[f] = {off, len, status} with off[0] = 0, off[f + 1] = align16(off[f] + len[f]); *total = the end of the last file
-__global__ __launch_bounds__(PNGE_SCAN) void k_png_enc_place_files(uint64_t pixels_bytes, const uint64_t *__restrict__ src,
-                                                                    int nframes, int W, int H, const PngeFrame *__restrict__ info,
-                                                                    uint64_t out_cap, abub_abf_file *__restrict__ files,
-                                                                    uint64_t *__restrict__ total)
-{
-    __shared__ unsigned long long sh[PNGE_SCAN / 64];
-    const uint64_t P = (uint64_t)W * (uint64_t)H;
-    unsigned long long base = 0;
-    for (int f0 = 0; f0 < nframes; f0 += PNGE_SCAN) {
-        const int f = f0 + (int)threadIdx.x;
-        const uint32_t len = f < nframes ? info[f].flen : 0u;
-        const unsigned long long room = ((unsigned long long)len + 15ull) & ~15ull;
-        unsigned long long all;
-        const unsigned long long incl = pnge_block_scan(room, sh, all);
-        if (f < nframes) {
-            const uint64_t off = base + incl - room;
-            abub_abf_file r;
-            r.off = off;
-            r.len = len;
-            r.status = !pnge_src_ok(src[f], pixels_bytes, P) ? ABUB_ABF_ENC_E_SRC : off + len > out_cap ? ABUB_ABF_ENC_E_CAP : 0;
-            files[f] = r;
-            if (f == nframes - 1)
-                *total = off + len;
-        }
-        base += all;
     }
 }
 
@@ -664,7 +593,6 @@ __global__ __launch_bounds__(64) void k_png_enc_fold(int nframes, const PngeFram
     p[3] = (uint8_t)crc;
 }
 
-inline size_t align16z(size_t v) { return (v + 15) & ~(size_t)15; }
 inline size_t pnge_nseg_max(int W, int H) { return (abub_png_file_bound(W, H) - (PNGE_FIXED - 10u) + PNGE_SEG - 1u) / PNGE_SEG; }
 
 // CRC-32 of a few bytes on the host (IHDR's depends on W and H only)
@@ -703,16 +631,9 @@ extern "C" int abub_png_encode_dev(const uint8_t *pixels, size_t pixels_bytes, c
                                    uint8_t *out, size_t out_cap, abub_abf_file *files, uint64_t *total, void *scratch,
                                    size_t scratch_bytes, void *stream)
 {
-    if (!pixels || !src || !out || !files || !total || !scratch || nframes < 0)
-        return set_err(ABUB_E_INVALID, "abub_png_encode_dev: null pointer or negative count");
-    if (W < 1 || W > 65535 || H < 1 || H > 65535)
-        return set_err(ABUB_E_INVALID, "abub_png_encode_dev: width and height must be in [1, 65535]");
-    if (!abub_png_file_bound(W, H))
-        return set_err(ABUB_E_INVALID, "abub_png_encode_dev: a W x H frame whose file may reach 4 GB");
-    if (scratch_bytes < abub_png_encode_scratch_bytes(nframes, W, H))
-        return set_err(ABUB_E_INVALID, "abub_png_encode_dev: scratch smaller than abub_png_encode_scratch_bytes");
-    if (((uintptr_t)scratch | (uintptr_t)src | (uintptr_t)files | (uintptr_t)total) & 7)
-        return set_err(ABUB_E_INVALID, "abub_png_encode_dev: src, files, total and scratch must be 8-byte aligned");
+    if (const int e = enc_check_args("abub_png_encode", abub_png_file_bound, abub_png_encode_scratch_bytes, pixels, src, nframes, W, H, out,
+                                     files, total, scratch, scratch_bytes))
+        return e;
     if (nframes == 0)
         return ABUB_OK;
     hipStream_t st = (hipStream_t)stream;
@@ -743,9 +664,10 @@ extern "C" int abub_png_encode_dev(const uint8_t *pixels, size_t pixels_bytes, c
     HIPCHK(hipGetLastError());
     k_png_enc_measure<<<grid, 64 * PNGE_WAVES, 0, st>>>(pixels, (uint64_t)pixels_bytes, src, W, H, codes, rows);
     HIPCHK(hipGetLastError());
-    k_png_enc_place_rows<<<(unsigned)nframes, PNGE_SCAN, 0, st>>>((uint64_t)pixels_bytes, src, W, H, codes, rows, info);
+    k_png_enc_place_rows<<<(unsigned)nframes, ENC_SCAN, 0, st>>>((uint64_t)pixels_bytes, src, W, H, codes, rows, info);
     HIPCHK(hipGetLastError());
-    k_png_enc_place_files<<<1, PNGE_SCAN, 0, st>>>((uint64_t)pixels_bytes, src, nframes, W, H, info, (uint64_t)out_cap, files, total);
+    k_enc_place_files<<<1, ENC_SCAN, 0, st>>>((uint64_t)pixels_bytes, src, nframes, (uint64_t)W * (uint64_t)H, &info->flen,
+                                               (uint32_t)sizeof(PngeFrame), (uint64_t)out_cap, files, total);
     HIPCHK(hipGetLastError());
     const dim3 wgrid((unsigned)nframes, (unsigned)((H + PNGE_WRITE_ROWS - 1) / PNGE_WRITE_ROWS));
     k_png_enc_write<<<wgrid, 64, 0, st>>>(pixels, src, W, H, rows, info, codes, hdr, files, crcIhdr, out);

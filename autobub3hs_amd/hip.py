@@ -567,55 +567,43 @@ def crc32(buf, entries):
     return (crc[:n].cpu().to(torch.int64) & 0xFFFFFFFF), status[:n].cpu()
 
 
+def _encode(entry_name, bound_name, scratch_name, pixels, src, W, H, out, scratch, out_cap):
+    """one call of an encoder's entry: what abf_encode and png_encode share (their arguments and results)"""
+    import numpy as np
+    _need_cuda(pixels, out, scratch)
+    L = _lib.lib()
+    offs = np.asarray(src, dtype=np.int64).reshape(-1)
+    n = len(offs)
+    dev = pixels.device
+    d_src = torch.from_numpy(np.concatenate([offs, np.zeros(1, np.int64)])).to(dev)
+    if out is None:
+        out = torch.empty((max(n, 1) * ((int(getattr(L, bound_name)(W, H)) + 15) & ~15),), dtype=torch.uint8, device=dev)
+    need = int(getattr(L, scratch_name)(n, W, H))
+    if scratch is None:
+        scratch = torch.empty((max(need, 16),), dtype=torch.uint8, device=dev)
+    d_files = torch.zeros((max(n, 1), 2), dtype=torch.int64, device=dev)
+    d_total = torch.zeros((1,), dtype=torch.int64, device=dev)
+    cap = out.numel() if out_cap is None else min(int(out_cap), out.numel())
+    _lib.check(getattr(L, entry_name)(_ptr(pixels), pixels.numel(), _ptr(d_src), n, W, H, _ptr(out), cap, _ptr(d_files), _ptr(d_total),
+                                      _ptr(scratch), scratch.numel(), _stream()), entry_name)
+    rec = d_files.cpu().numpy()[:n]
+    files = np.stack([rec[:, 0], rec[:, 1] & 0xFFFFFFFF, rec[:, 1] >> 32], axis=1) if n else np.zeros((0, 3), np.int64)
+    return files, int(d_total.item()), out
+
+
 def abf_encode(pixels, src, W, H, out=None, scratch=None, out_cap=None):
     """abub_abf_encode_dev: pixels u8 (any shape; frames of W * H bytes anywhere in it), src: byte offset of each frame
     (any alignment), out u8 (None: nframes * abub_abf_file_bound(W, H), rounded up to 16 per file; out_cap: the kernels may
     write only that many bytes of it, default all) ->
     (files int64 [n, 3] of (off, len, status) on the host, total, out).  File f is out[off:off + len], the bytes
     host.abf_encode gives the frame; status: 0, ABUB_ABF_ENC_E_SRC = 1, ABUB_ABF_ENC_E_CAP = 2 (total stays true)."""
-    import numpy as np
-    _need_cuda(pixels, out, scratch)
-    L = _lib.lib()
-    offs = np.asarray(src, dtype=np.int64).reshape(-1)
-    n = len(offs)
-    dev = pixels.device
-    d_src = torch.from_numpy(np.concatenate([offs, np.zeros(1, np.int64)])).to(dev)
-    if out is None:
-        out = torch.empty((max(n, 1) * ((int(L.abub_abf_file_bound(W, H)) + 15) & ~15),), dtype=torch.uint8, device=dev)
-    need = int(L.abub_abf_encode_scratch_bytes(n, W, H))
-    if scratch is None:
-        scratch = torch.empty((max(need, 16),), dtype=torch.uint8, device=dev)
-    d_files = torch.zeros((max(n, 1), 2), dtype=torch.int64, device=dev)
-    d_total = torch.zeros((1,), dtype=torch.int64, device=dev)
-    _lib.check(L.abub_abf_encode_dev(_ptr(pixels), pixels.numel(), _ptr(d_src), n, W, H, _ptr(out), out.numel() if out_cap is None else min(int(out_cap), out.numel()),
-                                     _ptr(d_files), _ptr(d_total), _ptr(scratch), scratch.numel(), _stream()), "abub_abf_encode_dev")
-    rec = d_files.cpu().numpy()[:n]
-    files = np.stack([rec[:, 0], rec[:, 1] & 0xFFFFFFFF, rec[:, 1] >> 32], axis=1) if n else np.zeros((0, 3), np.int64)
-    return files, int(d_total.item()), out
+    return _encode("abub_abf_encode_dev", "abub_abf_file_bound", "abub_abf_encode_scratch_bytes", pixels, src, W, H, out, scratch, out_cap)
 
 
 def png_encode(pixels, src, W, H, out=None, scratch=None, out_cap=None):
     """abub_png_encode_dev: the arguments and results of abf_encode; file f is out[off:off + len], the canonical Huffman-only
     PNG host.png_huff_encode gives the frame (out=None: nframes * abub_png_file_bound(W, H), rounded up to 16 per file)."""
-    import numpy as np
-    _need_cuda(pixels, out, scratch)
-    L = _lib.lib()
-    offs = np.asarray(src, dtype=np.int64).reshape(-1)
-    n = len(offs)
-    dev = pixels.device
-    d_src = torch.from_numpy(np.concatenate([offs, np.zeros(1, np.int64)])).to(dev)
-    if out is None:
-        out = torch.empty((max(n, 1) * ((int(L.abub_png_file_bound(W, H)) + 15) & ~15),), dtype=torch.uint8, device=dev)
-    need = int(L.abub_png_encode_scratch_bytes(n, W, H))
-    if scratch is None:
-        scratch = torch.empty((max(need, 16),), dtype=torch.uint8, device=dev)
-    d_files = torch.zeros((max(n, 1), 2), dtype=torch.int64, device=dev)
-    d_total = torch.zeros((1,), dtype=torch.int64, device=dev)
-    _lib.check(L.abub_png_encode_dev(_ptr(pixels), pixels.numel(), _ptr(d_src), n, W, H, _ptr(out), out.numel() if out_cap is None else min(int(out_cap), out.numel()),
-                                     _ptr(d_files), _ptr(d_total), _ptr(scratch), scratch.numel(), _stream()), "abub_png_encode_dev")
-    rec = d_files.cpu().numpy()[:n]
-    files = np.stack([rec[:, 0], rec[:, 1] & 0xFFFFFFFF, rec[:, 1] >> 32], axis=1) if n else np.zeros((0, 3), np.int64)
-    return files, int(d_total.item()), out
+    return _encode("abub_png_encode_dev", "abub_png_file_bound", "abub_png_encode_scratch_bytes", pixels, src, W, H, out, scratch, out_cap)
 
 
 def frames_compare(a, b, pairs, frame_bytes, a_bytes=None, b_bytes=None, results=None):

@@ -1,23 +1,23 @@
 // peek.cpp -- writePeekImages (peek.hpp): the six DebugPeek images of the accepted stacks of a resident batch.  What
 // L3Localizer::CalculateInitialBubbleParams writes on the analyzer's thread with cv::imwrite (L3Localizer.cpp:222-257, 397,
 // 448), for a whole batch: one store-mode K2 launch for D(trig, pre) and its histogram, the Otsu cut on the host, then
-// either abub_peek_planes_dev + abub_png_encode_dev (files come back finished) or, as the definition, host threads that form
-// the planes from frames copied back and encode with cv::pngHuffEncode.  Both routes write the same bytes.
-#include <sys/stat.h>
-
+// either abub_peek_planes_dev + the PNG encoder through EncodeBatch (encodebatch.hpp; files come back finished) or, as the
+// definition, host threads that form the planes from frames copied back and encode with cv::pngHuffEncode.  Both routes
+// write the same bytes.
 #include <algorithm>
 #include <atomic>
 #include <cerrno>
-#include <cstdio>
 #include <cstring>
 #include <stdexcept>
 
 #include "abub_hip.h"
 #include "devctx.hpp"
+#include "encodebatch.hpp"
 #include "framefiles.hpp"
 #include "holders.hpp"
 #include "hostlogic.hpp"
 #include "peek.hpp"
+#include "runframes.hpp"
 
 namespace abub {
 
@@ -41,24 +41,18 @@ const char *const kSuffix[6] = {"000_AvgImage", "00_PreTrigFrame", "0_TrigFrame"
 
 size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
 
-void makeDirs(const std::string &dir)
+void makeDirsOrThrow(const std::string &dir)
 {
-    for (size_t at = 1; at <= dir.size(); ++at)
-        if (at == dir.size() || dir[at] == '/') {
-            const std::string part = dir.substr(0, at);
-            if (mkdir(part.c_str(), 0777) != 0 && errno != EEXIST)
-                throw std::runtime_error("peek: cannot create " + part + ": " + strerror(errno));
-        }
+    std::string part;
+    if (!makeDirs(dir, &part))
+        throw std::runtime_error("peek: cannot create " + part + ": " + strerror(errno));
 }
 
 void writeBytes(const std::string &path, const uint8_t *p, size_t n)
 {
-    FILE *f = fopen(path.c_str(), "wb");
-    if (!f)
-        throw std::runtime_error("peek: cannot write " + path + ": " + strerror(errno));
-    const bool ok = fwrite(p, 1, n, f) == n;
-    if (fclose(f) != 0 || !ok)
-        throw std::runtime_error("peek: short write of " + path);
+    bool opened;
+    if (!writeFile(path, p, n, &opened))
+        throw std::runtime_error(opened ? "peek: short write of " + path : "peek: cannot write " + path + ": " + strerror(errno));
 }
 
 std::string fileOf(const std::string &dir, const PeekStack &s, int which)
@@ -66,56 +60,28 @@ std::string fileOf(const std::string &dir, const PeekStack &s, int which)
     return dir + "ev" + s.eventID + "_cam" + std::to_string(s.cam) + "_" + kSuffix[which] + ".png";
 }
 
-// A batch of files from abub_png_encode_dev, back on the host: file f is h.get() + rec[f].off, rec[f].len bytes
-struct Encoded {
-    PinnedBuffer h;
-    std::vector<abub_abf_file> rec;
-};
-
 // The device buffers of the post-pass, kept over the sub-batches of a call
 struct PeekBuffers {
     DeviceBuffer work;    // [n] D planes, then [n][2] peek planes, each at a multiple of 16
-    DeviceBuffer meta;    // jobs | hist | items | rects | status, or src | records | total of an encode
-    DeviceBuffer out, scratch;
+    DeviceBuffer meta;    // jobs | hist | items | rects | status
     PinnedBuffer h_meta;
 };
 
-// pixels + src[f] for every f through abub_png_encode_dev; the output grows once to the true count when it was too small
-void encode(PeekBuffers &b, const uint8_t *pixels, size_t pixelsBytes, const std::vector<uint64_t> &src, int W, int H, hipStream_t cs,
-            Encoded &e)
+// the PNG encoder with peek's own words for a batch that outgrows its regrown buffer
+const Codec kPeekPng = [] {
+    Codec c = kPng;
+    c.outgrew = "peek: the encoded files outgrew their regrown buffer";
+    return c;
+}();
+
+// pixels + src[f] for every f as PNG files in e (a first guess at their room: half a byte per pixel); a refused frame throws
+void encode(EncodeBatch &e, const uint8_t *pixels, size_t pixelsBytes, const std::vector<uint64_t> &src, int W, int H, hipStream_t cs)
 {
-    const size_t n = src.size();
-    const size_t metaBytes = n * (sizeof(uint64_t) + sizeof(abub_abf_file)) + sizeof(uint64_t);
-    b.meta.grow(metaBytes);
-    b.h_meta.grow(metaBytes);
-    b.scratch.grow(abub_png_encode_scratch_bytes((int)n, W, H));
-    b.out.grow(n * align16((size_t)W * H / 2 + 1024)); // (a first guess: half a byte per pixel)
-    std::memcpy(b.h_meta.get(), src.data(), n * sizeof(uint64_t));
-    HIPOK(hipMemcpyAsync(b.meta.get(), b.h_meta.get(), n * sizeof(uint64_t), hipMemcpyHostToDevice, cs));
-    abub_abf_file *d_rec = (abub_abf_file *)(b.meta.get() + n * sizeof(uint64_t));
-    uint64_t total = 0;
-    for (int attempt = 0;; ++attempt) {
-        check(abub_png_encode_dev(pixels, pixelsBytes, (const uint64_t *)b.meta.get(), (int)n, W, H, b.out.get(), b.out.capacity(), d_rec,
-                                  (uint64_t *)(d_rec + n), b.scratch.get(), b.scratch.capacity(), cs),
-              "abub_png_encode_dev");
-        HIPOK(hipMemcpyAsync(b.h_meta.get() + n * sizeof(uint64_t), d_rec, n * sizeof(abub_abf_file) + sizeof(uint64_t),
-                             hipMemcpyDeviceToHost, cs));
-        HIPOK(hipStreamSynchronize(cs));
-        std::memcpy(&total, b.h_meta.get() + n * (sizeof(uint64_t) + sizeof(abub_abf_file)), sizeof total);
-        if (total <= b.out.capacity())
-            break;
-        if (attempt)
-            throw std::runtime_error("peek: the encoded files outgrew their regrown buffer");
-        b.out.allocate((size_t)total + 256);
-    }
-    e.rec.resize(n);
-    std::memcpy(e.rec.data(), b.h_meta.get() + n * sizeof(uint64_t), n * sizeof(abub_abf_file));
-    for (const abub_abf_file &r : e.rec)
-        if (r.status != 0)
-            throw std::runtime_error("peek: abub_png_encode_dev refused a plane (status " + std::to_string(r.status) + ")");
-    e.h.grow((size_t)total + 16);
-    HIPOK(hipMemcpyAsync(e.h.get(), b.out.get(), (size_t)total, hipMemcpyDeviceToHost, cs));
-    HIPOK(hipStreamSynchronize(cs));
+    double encode_s = 0, copy_s = 0; // (not reported)
+    e.run(kPeekPng, pixels, pixelsBytes, src, W, H, src.size() * align16((size_t)W * H / 2 + 1024), cs, encode_s, copy_s);
+    for (size_t f = 0; f < e.count(); ++f)
+        if (e.file(f).status != 0)
+            throw std::runtime_error("peek: abub_png_encode_dev refused a plane (status " + std::to_string(e.file(f).status) + ")");
 }
 
 } // namespace
@@ -127,7 +93,7 @@ void writePeekImages(int W, int H, int C, const uint8_t *d_frames, size_t frames
     if (stacks.empty())
         return;
     const size_t P = (size_t)W * H, P16 = align16(P);
-    makeDirs(dir);
+    makeDirsOrThrow(dir);
     // per stack on the device: D and two planes, their files (at most abub_png_file_bound each, five of them) and the
     // encoder's scratch; the sub-batch takes what the budget allows
     const size_t perStack = 3 * P16 + 5 * align16(abub_png_file_bound(W, H)) + abub_png_encode_scratch_bytes(5, W, H) + 2048;
@@ -136,6 +102,7 @@ void writePeekImages(int W, int H, int C, const uint8_t *d_frames, size_t frames
         sub = std::min<size_t>(sub, (size_t)maxStacks);
     sub = std::min(sub, stacks.size());
     PeekBuffers b;
+    EncodeBatch encF, encW; // the files that are alive at once: a sub-batch's frames and its planes
     std::atomic<long long> files{0}, bytes{0};
     auto put = [&](const std::string &path, const uint8_t *p, size_t n) {
         writeBytes(path, p, n);
@@ -149,10 +116,10 @@ void writePeekImages(int W, int H, int C, const uint8_t *d_frames, size_t frames
         std::vector<uint64_t> src;
         for (int c = 0; c < C; ++c)
             src.push_back((uint64_t)c * P);
-        Encoded e;
-        encode(b, d_mu, (size_t)C * P, src, W, H, cs, e);
+        EncodeBatch encMu; // (its files are copied: one per camera, written once per stack)
+        encode(encMu, d_mu, (size_t)C * P, src, W, H, cs);
         for (int c = 0; c < C; ++c)
-            muPng[c].assign(e.h.get() + e.rec[c].off, e.h.get() + e.rec[c].off + e.rec[c].len);
+            muPng[c].assign(encMu.file(c).data, encMu.file(c).data + encMu.file(c).len);
     } else {
         std::vector<uint8_t> mu((size_t)C * P);
         HIPOK(hipMemcpyAsync(mu.data(), d_mu, mu.size(), hipMemcpyDeviceToHost, cs));
@@ -225,7 +192,7 @@ void writePeekImages(int W, int H, int C, const uint8_t *d_frames, size_t frames
             for (size_t k = 0; k < n; ++k)
                 if (status[k] != 0)
                     throw std::runtime_error("peek: abub_peek_planes_dev refused an item (status " + std::to_string(status[k]) + ")");
-            // the frames where they lie; D and the planes in the work slab (the meta buffer is free again: encode reuses it)
+            // the frames where they lie; D and the planes in the work slab
             std::vector<uint64_t> srcF, srcW;
             for (size_t k = 0; k < n; ++k) {
                 srcF.push_back((uint64_t)S[k].preFrame * P);
@@ -234,17 +201,16 @@ void writePeekImages(int W, int H, int C, const uint8_t *d_frames, size_t frames
                 srcW.push_back(planesAt + 2 * k * P16);
                 srcW.push_back(planesAt + (2 * k + 1) * P16);
             }
-            Encoded eF, eW;
-            encode(b, d_frames, framesBytes, srcF, W, H, cs, eF);
-            encode(b, b.work.get(), b.work.capacity(), srcW, W, H, cs, eW);
+            encode(encF, d_frames, framesBytes, srcF, W, H, cs);
+            encode(encW, b.work.get(), b.work.capacity(), srcW, W, H, cs);
             forEachTaskWith(
                 nthreads, n, []() { return 0; },
                 [&](int &, size_t k) {
                     put(fileOf(dir, S[k], 0), muPng[S[k].cam].data(), muPng[S[k].cam].size());
                     for (int j = 0; j < 2; ++j)
-                        put(fileOf(dir, S[k], 1 + j), eF.h.get() + eF.rec[2 * k + j].off, eF.rec[2 * k + j].len);
+                        put(fileOf(dir, S[k], 1 + j), encF.file(2 * k + j).data, encF.file(2 * k + j).len);
                     for (int j = 0; j < 3; ++j)
-                        put(fileOf(dir, S[k], 3 + j), eW.h.get() + eW.rec[3 * k + j].off, eW.rec[3 * k + j].len);
+                        put(fileOf(dir, S[k], 3 + j), encW.file(3 * k + j).data, encW.file(3 * k + j).len);
                 });
         } else {
             // ---- the definition: D and the two frames back, planes and files on host threads ----------------------------

@@ -7,7 +7,6 @@
 // UnpackRun / UnpackRunDevice (abub3hs --unpack [--unpack-gpu]) are the same two routes with another codec: every frame
 // becomes a canonical Huffman-only PNG (cv::pngHuffEncode / abub_png_encode_dev; DESIGN section 3, "Unpacking a run").
 #include <algorithm>
-#include <cerrno>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -20,6 +19,7 @@
 #include <sys/stat.h>
 
 #include "driver.hpp"
+#include "encodebatch.hpp"
 #include "framefiles.hpp"
 #include "runbatch.hpp"
 #include "runframes.hpp"
@@ -27,44 +27,6 @@
 namespace abub {
 
 namespace {
-
-bool makeDirs(const std::string &path)
-{
-    for (size_t at = 1; at <= path.size(); ++at)
-        if (at == path.size() || path[at] == '/') {
-            const std::string part = path.substr(0, at);
-            if (mkdir(part.c_str(), 0777) != 0 && errno != EEXIST)
-                return false;
-        }
-    struct stat sb;
-    return stat(path.c_str(), &sb) == 0 && S_ISDIR(sb.st_mode);
-}
-
-bool writeFile(const std::string &path, const unsigned char *data, size_t n)
-{
-    FILE *f = fopen(path.c_str(), "wb");
-    if (!f)
-        return false;
-    const bool ok = fwrite(data, 1, n, f) == n;
-    return fclose(f) == 0 && ok;
-}
-
-// The frame format a run is rewritten in: what differs between --repack and --unpack
-struct Codec {
-    const char *what;                                                         // "repack" / "unpack", in messages
-    bool (*encode)(const uchar *pixels, int W, int H, std::vector<uchar> &out); // on a host thread
-    int (*encodeDev)(const uint8_t *, size_t, const uint64_t *, int, int, int, uint8_t *, size_t, abub_abf_file *, uint64_t *, void *,
-                     size_t, void *);
-    size_t (*scratchBytes)(int nframes, int W, int H);
-    const char *devName, *noDevice, *outgrew; // the device entry's name; what requireDevice adds to its message; the
-                                              // message when a batch's files do not fit their regrown buffer
-};
-const Codec kPacked = {"repack", cv::abfEncode, abub_abf_encode_dev, abub_abf_encode_scratch_bytes, "abub_abf_encode_dev",
-                       "; without --repack-gpu the run is repacked on the host",
-                       "repack: the packed files of a batch outgrew their buffer twice"};
-const Codec kPng = {"unpack", cv::pngHuffEncode, abub_png_encode_dev, abub_png_encode_scratch_bytes, "abub_png_encode_dev",
-                    "; without --unpack-gpu the run is unpacked on the host",
-                    "unpack: the PNG files of a batch outgrew their buffer twice"};
 
 // what became of one frame
 struct Outcome {
@@ -192,8 +154,8 @@ void hostFrames(const Codec &codec, Parser *parser, const Plan &pl, int nthreads
 
 // The device route: the frames in batches of at most 4 per CU (ABUB_REPACK_BATCH=n, a test knob: of at most n, never more).  Per batch: the pool reads the files into a pinned buffer
 // (and packs, on the spot, what is no file for the GPU decoders: a frame it had to decode itself, a frame of another size,
-// a file that does not decode); upload; both decoders into a slab; the codec's device encoder over the frames that are in place;
-// files and total copied back; one copy of `total` bytes into pinned memory; the pool writes the files.
+// a file that does not decode); upload; both decoders into a slab; the codec's device encoder over the frames that are in place
+// (EncodeBatch, encodebatch.hpp: its files come back in pinned memory); the pool writes the files.
 void deviceFrames(const Codec &codec, Parser *parser, const Plan &pl, int nthreads, int device, int W, int H, Tally &tally)
 {
     RepackStats &st = tally.st;
@@ -207,9 +169,7 @@ void deviceFrames(const Codec &codec, Parser *parser, const Plan &pl, int nthrea
     const size_t P = (size_t)W * H;
     FileBatch B; // the batch's files, the decoders' scratch, the slab of decoded frames (frame i at i * P)
     std::vector<FileTask> &ft = B.ft;
-    PinnedBuffer h_meta;
-    DeviceBuffer d_meta, scratch;
-    GrowList<uint8_t> out(4096, 1, SIZE_MAX); // the packed files of a batch, on the device and in pinned memory
+    EncodeBatch enc; // the packed files of a batch
     Stream stream;
     hipStream_t cs = stream.get();
     B.sizer.reset(parser->clone());
@@ -270,41 +230,9 @@ void deviceFrames(const Codec &codec, Parser *parser, const Plan &pl, int nthrea
         HIPOK(hipStreamSynchronize(cs));
         st.decode_s += (nowMs() - t0) * 1e-3;
 
-        // ---- encode: [src][files][total] in one buffer; redone once when the files outgrow `out` ---------------------------
-        t0 = nowMs();
+        // ---- encode and copy back (a packed frame is about the size of its PNG) ----------------------------------------------
         const size_t ng = src.size();
-        const abub_abf_file *files = nullptr;
-        uint64_t bytes = 0;
-        if (ng) {
-            const size_t metaBytes = ng * (sizeof(uint64_t) + sizeof(abub_abf_file)) + sizeof(uint64_t);
-            h_meta.grow(metaBytes);
-            d_meta.grow(metaBytes);
-            scratch.grow(codec.scratchBytes((int)ng, W, H));
-            std::memcpy(h_meta.get(), src.data(), ng * sizeof(uint64_t));
-            HIPOK(hipMemcpyAsync(d_meta.get(), h_meta.get(), ng * sizeof(uint64_t), hipMemcpyHostToDevice, cs));
-            abub_abf_file *d_rec = (abub_abf_file *)(d_meta.get() + ng * sizeof(uint64_t));
-            uint64_t *d_total = (uint64_t *)(d_rec + ng);
-            files = (const abub_abf_file *)(h_meta.get() + ng * sizeof(uint64_t));
-            out.newBatch();
-            out.reserve(B.total + 64 * ng); // (a packed frame is about the size of its PNG)
-            for (;;) {
-                check(codec.encodeDev(B.slab.get(), n * P, (const uint64_t *)d_meta.get(), (int)ng, W, H, out.d, out.cap(), d_rec,
-                                      d_total, scratch.get(), scratch.capacity(), cs),
-                      codec.devName);
-                HIPOK(hipMemcpyAsync(h_meta.get() + ng * sizeof(uint64_t), d_rec, ng * sizeof(abub_abf_file) + sizeof(uint64_t),
-                                     hipMemcpyDeviceToHost, cs));
-                HIPOK(hipStreamSynchronize(cs));
-                std::memcpy(&bytes, files + ng, sizeof bytes);
-                if (out.fit((size_t)bytes, codec.outgrew))
-                    break;
-            }
-            st.encode_s += (nowMs() - t0) * 1e-3;
-            // ---- copy back --------------------------------------------------------------------------------------------------
-            t0 = nowMs();
-            out.toHost((size_t)bytes, cs);
-            HIPOK(hipStreamSynchronize(cs));
-            st.copy_s += (nowMs() - t0) * 1e-3;
-        }
+        enc.run(codec, B.slab.get(), n * P, src, W, H, B.total + 64 * ng, cs, st.encode_s, st.copy_s);
 
         // ---- write: the packed files, and on the host route what the decoders left (a PNG that is damaged behind its header) -
         t0 = nowMs();
@@ -319,10 +247,10 @@ void deviceFrames(const Codec &codec, Parser *parser, const Plan &pl, int nthrea
                 tally.add(packBytes(codec, B.h_files.get() + ft[i].off, (size_t)ft[i].size, pl.pathOf(t)));
                 return;
             }
-            const abub_abf_file &r = files[fileOf[i]];
+            const EncodeBatch::File r = enc.file(fileOf[i]);
             Outcome o;
             o.packed = true;
-            o.ok = r.status == 0 && writeFile(pl.pathOf(t), out.h + r.off, r.len);
+            o.ok = r.status == 0 && writeFile(pl.pathOf(t), r.data, r.len);
             o.in = ft[i].size;
             o.out = r.len;
             tally.add(o, true);

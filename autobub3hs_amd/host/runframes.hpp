@@ -1,14 +1,19 @@
 // runframes.hpp -- a run as the list of its frames, for the tools that visit every frame without analysing any: repack
 // (repack.cpp) and verify (verify.cpp).  The list, the size the GPU decoders are set up for and the device check are one
-// copy here (the decoders' width gate and the batch size: framefiles.hpp).  Internal to the host library.
+// copy here (the decoders' width gate and the batch size: framefiles.hpp), and so are the two helpers with which repack and
+// the peek images (peek.cpp) put files on disk.  Internal to the host library.
 #ifndef ABUB3HS_RUNFRAMES_HPP
 #define ABUB3HS_RUNFRAMES_HPP
 
 #include <algorithm>
+#include <cerrno>
+#include <cstdio>
 #include <memory>
 #include <stdexcept>
 #include <string>
 #include <vector>
+
+#include <sys/stat.h>
 
 #include <hip/hip_runtime_api.h>
 
@@ -21,6 +26,38 @@ inline std::string trimSlashes(std::string s)
     while (s.size() > 1 && s.back() == '/')
         s.pop_back();
     return s;
+}
+
+// The directory `path` and those above it, made where they are missing.  false: *failed cannot be made or is no directory
+// (errno says why)
+inline bool makeDirs(const std::string &path, std::string *failed = nullptr)
+{
+    std::string part;
+    for (size_t at = 1; at <= path.size(); ++at)
+        if (at == path.size() || path[at] == '/') {
+            part = path.substr(0, at);
+            if (mkdir(part.c_str(), 0777) != 0 && errno != EEXIST)
+                break;
+            part = path;
+        }
+    struct stat sb;
+    if (part == path && stat(path.c_str(), &sb) == 0 && S_ISDIR(sb.st_mode))
+        return true;
+    if (failed)
+        *failed = part;
+    return false;
+}
+
+// The n bytes at `data` as the file `path`.  false: it cannot be opened (*opened says whether it was), or not all of it was written
+inline bool writeFile(const std::string &path, const unsigned char *data, size_t n, bool *opened = nullptr)
+{
+    FILE *f = fopen(path.c_str(), "wb");
+    if (opened)
+        *opened = f != nullptr;
+    if (!f)
+        return false;
+    const bool ok = fwrite(data, 1, n, f) == n;
+    return fclose(f) == 0 && ok;
 }
 
 // One frame of a run: the index of its event in the run's sorted event list, and its file name

@@ -2,6 +2,7 @@
 restatement of the format (tests/abfref.py), bit for bit; its capacity and source errors; the scan across many files; the
 round trip through abub_abf_decode_dev on the device; and abub3hs --repack --repack-gpu / Run.repack(device=0) against the
 host repack, file by file."""
+import functools
 import os
 import subprocess
 import zipfile
@@ -12,18 +13,18 @@ import torch
 from PIL import Image
 
 import abfref
+import enclayout
 from autobub3hs_amd import _lib, hip, host, synth
+from enclayout import CANARY, DEV, E_CAP, E_SRC, align16, check_layout, expected_layout, scatter, tree
 from test_abf_format import all_contents, make_run_dir, zip_run
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-CANARY = 0xA5
-DEV = "cuda:0"
 SHAPES = [(1, 1), (2, 1), (63, 2), (64, 3), (65, 3), (127, 2), (128, 9), (129, 9), (257, 9), (1280, 9), (2050, 2), (4100, 1)]  # W x H
-E_SRC, E_CAP = 1, 2
 RUN_ID = "20200925_1"
+encode = functools.partial(enclayout.encode, hip.abf_encode)
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -56,58 +57,6 @@ def ladder(W, H):
             n = min(64, W - 64 * k)
             img[y, 64 * k:64 * k + n] = blk[:n]
     return img
-
-
-def align16(v):
-    return (v + 15) & ~15
-
-
-def scatter(imgs, rs):
-    """the frames at scattered, unaligned offsets of a random buffer, not in order -> (buffer, offsets)"""
-    P = imgs[0].size
-    order = rs.permutation(len(imgs))
-    offs = np.zeros(len(imgs), np.int64)
-    at = 3
-    for slot in order:
-        at += int(rs.randint(1, 40))
-        offs[slot] = at
-        at += P
-    buf = rs.randint(0, 256, at + 11).astype(np.uint8)
-    for o, img in zip(offs, imgs):
-        buf[o:o + P] = img.reshape(-1)
-    return buf, offs
-
-
-def encode(buf, offs, W, H, out_bytes, out_cap=None, out=None, scratch=None):
-    """one launch; canaries all over `out` and in front of and behind it -> (files, total, out bytes on the host)"""
-    pixels = torch.from_numpy(buf).to(DEV)
-    whole = torch.full((out_bytes + 512,), CANARY, dtype=torch.uint8, device=DEV) if out is None else out
-    files, total, _ = hip.abf_encode(pixels, offs, W, H, out=whole[256:256 + out_bytes], out_cap=out_cap, scratch=scratch)
-    torch.cuda.synchronize()
-    host_out = whole.cpu().numpy()
-    assert (host_out[:256] == CANARY).all() and (host_out[256 + out_bytes:] == CANARY).all(), "written outside out"
-    return files, total, host_out[256:256 + out_bytes]
-
-
-def expected_layout(lens):
-    offs, at = [], 0
-    for n in lens:
-        offs.append(at)
-        at = align16(at + n)
-    return offs, (offs[-1] + lens[-1] if lens else 0)
-
-
-def check_layout(files, total, out, want, written):
-    """want[f]: the bytes of file f (b"" for a frame that takes no room); written[f]: whether they must be in `out`.  Every
-    byte outside the written files is still the canary."""
-    offs, end = expected_layout([len(w) for w in want])
-    assert list(files[:, 0]) == offs and list(files[:, 1]) == [len(w) for w in want] and total == end
-    free = np.ones(len(out), bool)
-    for o, w, there in zip(offs, want, written):
-        if there:
-            assert out[o:o + len(w)].tobytes() == w
-            free[o:o + len(w)] = False
-    assert (out[free] == CANARY).all(), "written outside the files"
 
 
 @pytest.mark.parametrize("W,H", SHAPES)
@@ -201,14 +150,6 @@ def test_round_trip_on_the_device(sources):
     assert (st.cpu().numpy() == 0).all()
     assert torch.equal(back, frames)
     assert out[int(files[3, 0]):int(files[3, 0] + files[3, 1])].cpu().numpy().tobytes() == host.abf_encode(imgs[3])
-
-
-def tree(root):
-    out = {}
-    for dp, _, fs in os.walk(root):
-        for f in fs:
-            out[os.path.relpath(os.path.join(dp, f), root)] = open(os.path.join(dp, f), "rb").read()
-    return out
 
 
 def test_repack_gpu_writes_the_trees_of_the_host_repack(tmp_path):

@@ -3,6 +3,7 @@ the numpy restatement of the format (tests/pnghuffref.py), byte for byte, at the
 that share a byte, block ends, both length limits); its capacity and source errors; the scan across many files; the round
 trip through abub_png_decode_dev on the device; and abub3hs --unpack --unpack-gpu / Run.unpack(device=0) against the host
 unpack, file by file."""
+import functools
 import os
 import subprocess
 import zipfile
@@ -12,8 +13,10 @@ import pytest
 import torch
 from PIL import Image
 
+import enclayout
 import pnghuffref as ref
 from autobub3hs_amd import _lib, hip, host, synth
+from enclayout import CANARY, DEV, E_CAP, E_SRC, align16, check_layout, expected_layout, scatter, tree
 from test_abf_format import make_packed_run, zip_run
 
 pytestmark = pytest.mark.gpu
@@ -21,10 +24,8 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 EXE = os.path.join(ROOT, "autobub3hs_amd", "abub3hs")
-CANARY = 0xA5
-DEV = "cuda:0"
-E_SRC, E_CAP = 1, 2
 RUN_ID = "20200925_1"
+encode = functools.partial(enclayout.encode, hip.png_encode)
 NAMES = ["w1_ones", "w1_sevens", "w2_ones", "3x5", "7x65", "63x3", "64x3", "65x3", "127x3", "128x3", "129x3", "1280x8", "1680x6",
          "160x96", "limit15", "limit7"]
 
@@ -45,62 +46,6 @@ def cases():
     imgs["limit7"] = ref.limit7_case()
     assert sorted(imgs) == sorted(NAMES)
     return imgs
-
-
-def align16(v):
-    return (v + 15) & ~15
-
-
-def scatter(imgs, rs):
-    """the frames at scattered, unaligned offsets of a random buffer, not in order -> (buffer, offsets)"""
-    P = imgs[0].size
-    order = rs.permutation(len(imgs))
-    offs = np.zeros(len(imgs), np.int64)
-    at = 3
-    for slot in order:
-        at += int(rs.randint(1, 40))
-        offs[slot] = at
-        at += P
-    buf = rs.randint(0, 256, at + 11).astype(np.uint8)
-    for o, img in zip(offs, imgs):
-        buf[o:o + P] = img.reshape(-1)
-    return buf, offs
-
-
-def encode(buf, offs, W, H, out_bytes, out_cap=None, out=None, scratch=None):
-    """one call; canaries all over `out` and in front of and behind it -> (files, total, out bytes on the host)"""
-    pixels = torch.from_numpy(buf).to(DEV)
-    whole = torch.full((out_bytes + 512,), CANARY, dtype=torch.uint8, device=DEV) if out is None else out
-    files, total, _ = hip.png_encode(pixels, offs, W, H, out=whole[256:256 + out_bytes], out_cap=out_cap, scratch=scratch)
-    torch.cuda.synchronize()
-    host_out = whole.cpu().numpy()
-    assert (host_out[:256] == CANARY).all() and (host_out[256 + out_bytes:] == CANARY).all(), "written outside out"
-    return files, total, host_out[256:256 + out_bytes]
-
-
-def expected_layout(lens):
-    offs, at = [], 0
-    for n in lens:
-        offs.append(at)
-        at = align16(at + n)
-    return offs, (offs[-1] + lens[-1] if lens else 0)
-
-
-def check_layout(files, total, out, want, written):
-    """want[f]: the bytes of file f (b"" for a frame that takes no room); written[f]: whether they must be in `out`.  Every
-    byte outside the written files is still the canary."""
-    offs, end = expected_layout([len(w) for w in want])
-    assert list(files[:, 0]) == offs and list(files[:, 1]) == [len(w) for w in want] and total == end
-    free = np.ones(len(out), bool)
-    for f, (o, w, there) in enumerate(zip(offs, want, written)):
-        if there:
-            got = out[o:o + len(w)].tobytes()
-            if got != w:
-                first = next(i for i in range(len(w)) if got[i] != w[i])
-                raise AssertionError(f"file {f}: {sum(a != b for a, b in zip(got, w))} of {len(w)} bytes differ, the first at {first}: "
-                                     f"{got[first:first + 8].hex()} for {w[first:first + 8].hex()}")
-            free[o:o + len(w)] = False
-    assert (out[free] == CANARY).all(), "written outside the files"
 
 
 @pytest.mark.parametrize("name", NAMES)
@@ -215,14 +160,6 @@ def test_round_trip_of_the_length_limited_codes(cases, name):
     torch.cuda.synchronize()
     assert list(st) == [0, 0], st
     assert torch.equal(back, frames)
-
-
-def tree(root):
-    out = {}
-    for dp, _, fs in os.walk(root):
-        for f in fs:
-            out[os.path.relpath(os.path.join(dp, f), root)] = open(os.path.join(dp, f), "rb").read()
-    return out
 
 
 def test_unpack_gpu_writes_the_trees_of_the_host_unpack(tmp_path):
