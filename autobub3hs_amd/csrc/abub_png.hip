@@ -31,6 +31,7 @@
 // mode (RFC 1951: no header, no trailer, read in place, one output length per entry), k_zip_crc checks the CRC-32 the
 // archive's central directory states for every inflated entry.
 #include "abub_dev.hpp"
+#include "abub_crc.hpp"
 #include <stddef.h>
 #include <algorithm>
 #include <string>
@@ -1230,39 +1231,7 @@ __global__ __launch_bounds__(TWO ? 128 : 64) void k_zip_inflate(const uint8_t *_
 // the register of piece t with slice-by-4 tables in LDS (thread 0 starts from 0xFFFFFFFF: the pre-conditioning, once), moves
 // it over the bytes behind its piece -- a multiplication by x^(8 * tail) mod P, built from the x^(8 * 2^k) by 32-step
 // carry-less multiplications -- and the registers are summed (xor); the post-conditioning is applied once.
-constexpr uint32_t CRC_POLY = 0xEDB88320u;
-constexpr uint32_t crc_mul(uint32_t a, uint32_t b) // a * b mod P (bit 31 is x^0)
-{
-    uint32_t p = 0;
-    for (int i = 0; i < 32; ++i) {
-        if (a & (0x80000000u >> i))
-            p ^= b;
-        b = (b >> 1) ^ ((b & 1) ? CRC_POLY : 0u);
-    }
-    return p;
-}
-struct CrcTables {
-    uint32_t t[4][256];
-    uint32_t pw[28]; // x^(8 * 2^k) mod P
-};
-constexpr CrcTables crc_make_tables()
-{
-    CrcTables T{};
-    for (uint32_t i = 0; i < 256; ++i) {
-        uint32_t c = i;
-        for (int k = 0; k < 8; ++k)
-            c = (c >> 1) ^ ((c & 1) ? CRC_POLY : 0u);
-        T.t[0][i] = c;
-    }
-    for (int s = 1; s < 4; ++s)
-        for (uint32_t i = 0; i < 256; ++i)
-            T.t[s][i] = (T.t[s - 1][i] >> 8) ^ T.t[0][T.t[s - 1][i] & 255];
-    T.pw[0] = 0x00800000u; // x^8
-    for (int k = 1; k < 28; ++k)
-        T.pw[k] = crc_mul(T.pw[k - 1], T.pw[k - 1]);
-    return T;
-}
-__device__ const CrcTables crc_tables = crc_make_tables();
+// (the tables, crc_mul and the powers: abub_crc.hpp, shared with the archive packer)
 
 template <bool ALONE> // ALONE: abub_crc32_dev (every descriptor checked here, the CRCs written out); else behind k_zip_inflate
 __global__ __launch_bounds__(256) void k_zip_crc(const uint8_t *__restrict__ out, uint64_t out_bytes,

@@ -567,6 +567,32 @@ def crc32(buf, entries):
     return (crc[:n].cpu().to(torch.int64) & 0xFFFFFFFF), status[:n].cpu()
 
 
+def zip_pack(buf, items, names, seg, crc=None, status=None, buf_bytes=None, names_bytes=None, seg_bytes=None):
+    """abub_zip_pack_dev: buf u8 (resident files), items: rows of (src, dst, len, name, name_len, extra_len) as
+    abub_zip_item, names u8 (the entries' names), seg u8 (written in place: per item its local header, name, padding field
+    and data at dst, nothing else) -> (crc int64 [n] on the host, what zlib.crc32 gives the len bytes at buf + src;
+    status i32 [n] on the host: 0, or ABUB_ZIP_E_DESC = 1 and nothing of the item written).  crc / status: i32 device
+    tensors to reuse; *_bytes: what the kernels may touch of a buffer, default all of it."""
+    import numpy as np
+    _need_cuda(buf, names, seg, crc, status)
+    d = np.asarray(items, dtype=np.int64).reshape(-1, 6)
+    n = len(d)
+    rec = np.zeros((max(n, 1),), dtype=np.dtype([("src", "<u8"), ("dst", "<u8"), ("len", "<u4"), ("name", "<u4"),
+                                                  ("name_len", "<u2"), ("extra_len", "<u2"), ("reserved", "<u4")]))
+    for k, col in enumerate(("src", "dst", "len", "name", "name_len", "extra_len")):
+        rec[col][:n] = d[:, k].astype(np.uint64)
+    d_items = torch.from_numpy(rec.view(np.int64).copy()).to(buf.device)
+    if crc is None:
+        crc = torch.full((max(n, 1),), 0x5A5A5A5A, dtype=torch.int32, device=buf.device)
+    if status is None:
+        status = torch.full((max(n, 1),), 99, dtype=torch.int32, device=buf.device)
+    _lib.check(_lib.lib().abub_zip_pack_dev(_ptr(buf), buf.numel() if buf_bytes is None else int(buf_bytes), _ptr(d_items), n,
+                                            _ptr(names), names.numel() if names_bytes is None else int(names_bytes), _ptr(seg),
+                                            seg.numel() if seg_bytes is None else int(seg_bytes), _ptr(crc), _ptr(status), _stream()),
+               "abub_zip_pack_dev")
+    return (crc[:n].cpu().to(torch.int64) & 0xFFFFFFFF), status[:n].cpu()
+
+
 def _encode(entry_name, bound_name, scratch_name, pixels, src, W, H, out, scratch, out_cap):
     """one call of an encoder's entry: what abf_encode and png_encode share (their arguments and results)"""
     import numpy as np

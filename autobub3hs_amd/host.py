@@ -60,6 +60,10 @@ SIGNATURES = {
     "abh_run_verify": (_i, [_vp, _vp, _i, _i, _dp, C.c_char_p, _i]),
     "abh_run_verify_dev": (_i, [_vp, _vp, _i, _i, _i, _dp, C.c_char_p, _i]),
     "abh_run_verify_report": (_s, [_vp]),
+    "abh_run_repack_archive": (_i, [_vp, _s, _i, _i, _i, _i, _dp]),
+    "abh_run_verify_archive": (_i, [_vp, _vp, _i, _i, _i, _dp, C.c_char_p, _i]),
+    "abh_zip_write": (_i, [_s, _i, _u8p, _u32p, _u8p, _u64p]),
+    "abh_zip_error": (_s, []),
     "abh_png_walk": (_i, [_u8p, _i, _i, _i, _u32p, _i, _ip, _ip, _u8p]),
     "abh_png_walk_typed": (_i, [_u8p, _i, _i, _i, _u32p, _i, _ip, _ip, _u8p, _u32p]),
     "abh_png_walk_adam7": (_i, [_u8p, _i, _i, _i, _i, _u32p, _i, _ip, _ip, _u8p, _u32p]),
@@ -315,12 +319,35 @@ class Run:
             out.update(zip(("peek_stacks", "peek_files", "peek_bytes", "peek_gpu", "peek_s"), list(pk)))
         return out
 
-    def repack(self, outdir, nthreads=16, ncams=4, device=None):
+    _REPACK_DEV_KEYS = ("frames_gpu_encoded", "frames_gpu_png_decoded", "frames_gpu_unpacked", "frames_host_decoded",
+                        "frames_host_route", "batches", "read_s", "decode_s", "encode_s", "copy_s", "write_s", "device",
+                        "frames_gpu_bmp_decoded", "frames_gpu_unzipped")
+
+    def _rewrite_archive(self, what, outdir, nthreads, ncams, device, unpack):
+        """--archive of repack / unpack: the copy is the one file <outdir>.zip"""
+        L = lib()
+        st = (C.c_double * 23)()
+        rc = L.abh_run_repack_archive(self._h, outdir.encode(), ncams, nthreads, -1 if device is None else int(device), unpack, st)
+        if rc != 0:
+            raise RuntimeError(f"abh_run_{what} rc={rc}: " + L.abh_last_error(self._h).decode())
+        keys = ("packed", "copied", "failed", "bytes_in", "bytes_out", "seconds")
+        out = dict(zip(keys, list(st)))
+        if device is not None:
+            out.update(zip(self._REPACK_DEV_KEYS, list(st)[6:20]))
+            out["pack_s"] = st[22]
+        out.update(archive_bytes=int(st[20]), archive_entries=int(st[21]))
+        return out
+
+    def repack(self, outdir, nthreads=16, ncams=4, device=None, archive=False):
         """abub3hs --repack of this run (opened from a directory or an archive): every frame of cameras 0 .. ncams-1
         written in the packed format (abf_encode) to <outdir>/<event>/<image folder>/<same name>; `outdir` is the new run
         folder, its last component the run ID.  Files that do not decode are copied as they are.  device=None: no GPU.
         device=N (--repack-gpu): the same files, the frames decoded and packed on that GPU (abub_abf_encode_dev); raises
-        when there is no such device.  -> stats dict; raises if anything could not be written."""
+        when there is no such device.  archive=True (--archive): the copy is the one zip archive <outdir>.zip with the same
+        files as stored entries ("A run as one archive"); the stats gain archive_bytes and
+        archive_entries, with a device pack_s.  -> stats dict; raises if anything could not be written."""
+        if archive:
+            return self._rewrite_archive("repack", outdir, nthreads, ncams, device, 0)
         L = lib()
         keys = ("packed", "copied", "failed", "bytes_in", "bytes_out", "seconds")
         if device is None:
@@ -336,12 +363,15 @@ class Run:
             raise RuntimeError(f"abh_run_repack rc={rc}: " + L.abh_last_error(self._h).decode())
         return dict(zip(keys, list(st)))
 
-    def unpack(self, outdir, nthreads=16, ncams=4, device=None):
+    def unpack(self, outdir, nthreads=16, ncams=4, device=None, archive=False):
         """abub3hs --unpack of this run (opened from a directory or an archive; packed, PNG, BMP or mixed): the way back
         from repack.  Every frame of cameras 0 .. ncams-1 written as a canonical Huffman-only PNG (png_huff_encode) to
         <outdir>/<event>/<image folder>/<same name>; layout, event file and refusals as repack.  device=None: no GPU.
         device=N (--unpack-gpu): the same files, the frames decoded and encoded on that GPU (abub_png_encode_dev); raises
-        when there is no such device.  -> the stats dict of repack ("packed": PNG files written)."""
+        when there is no such device.  archive=True: as for repack.  -> the stats dict of repack ("packed": PNG files
+        written)."""
+        if archive:
+            return self._rewrite_archive("unpack", outdir, nthreads, ncams, device, 1)
         L = lib()
         keys = ("packed", "copied", "failed", "bytes_in", "bytes_out", "seconds")
         if device is None:
@@ -357,7 +387,7 @@ class Run:
             raise RuntimeError(f"abh_run_unpack rc={rc}: " + L.abh_last_error(self._h).decode())
         return dict(zip(keys, list(st)))
 
-    def verify(self, other, nthreads=16, ncams=4, device=None):
+    def verify(self, other, nthreads=16, ncams=4, device=None, archive=False):
         """abub3hs --verify-repack: is the run `other` (another Run opened from a directory or an archive) pixel for pixel
         this one?  Every frame this run lists for cameras 0 .. ncams-1 gets one verdict: same (identical pixels, the other
         file is a packed frame), same_not_packed, copied (this file does not decode, the other has its bytes), and the
@@ -368,12 +398,16 @@ class Run:
         compared"), the device route's counters and legs (device -1: it was not taken; src_gpu_bmp_decoded /
         other_gpu_bmp_decoded: frames of each side decoded by abub_bmp_decode_dev), and findings: every failure and
         every same_not_packed frame in task order, then the extras and the event file, each a dict of event, name, verdict,
-        ndiff, x, y, max_abs (and w, h, other_w, other_h where the sizes differ)."""
+        ndiff, x, y, max_abs (and w, h, other_w, other_h where the sizes differ).  archive=True (--archive): `other` is
+        opened from the archive repack(archive=True) wrote, and the event file is compared as bytes with its <run>.txt
+        entry."""
         L = lib()
         st = (C.c_double * 29)()
         cap = 1 << 16
         buf = C.create_string_buffer(cap)
-        if device is None:
+        if archive:
+            rc = L.abh_run_verify_archive(self._h, other._h, ncams, nthreads, -1 if device is None else int(device), st, buf, cap)
+        elif device is None:
             rc = L.abh_run_verify(self._h, other._h, ncams, nthreads, st, buf, cap)
         else:
             rc = L.abh_run_verify_dev(self._h, other._h, ncams, nthreads, int(device), st, buf, cap)
@@ -404,6 +438,21 @@ class Run:
         if staged == -100:
             raise RuntimeError(L.abh_last_error(self._h).decode())
         return _read_result(L.abh_run_last(self._h), with_dz=True)
+
+
+def zip_write(path, entries):
+    """The host writer of the canonical archive (host/zipwrite.cpp) alone: entries, a list of (name, bytes), written to
+    `path` in that order; raises where it cannot be written (and leaves no file)."""
+    L = lib()
+    n = len(entries)
+    names = b"".join(name.encode() if isinstance(name, str) else name for name, _ in entries)
+    data = b"".join(d for _, d in entries)
+    name_len = (C.c_uint32 * max(n, 1))(*[len(name.encode() if isinstance(name, str) else name) for name, _ in entries])
+    lens = (C.c_uint64 * max(n, 1))(*[len(d) for _, d in entries])
+    nb = (C.c_uint8 * max(len(names), 1)).from_buffer_copy(names or b"\0")
+    db = (C.c_uint8 * max(len(data), 1)).from_buffer_copy(data or b"\0")
+    if L.abh_zip_write(str(path).encode(), n, nb, name_len, db, lens) != 0:
+        raise RuntimeError("abh_zip_write: " + L.abh_zip_error().decode())
 
 
 def imdecode(data, cap=1 << 22):

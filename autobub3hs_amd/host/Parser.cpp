@@ -12,6 +12,7 @@ long long Parser::GetImageFileSize(std::string, std::string) { return -1; }
 long long Parser::ReadImageFile(std::string, std::string, unsigned char *, size_t) { return -1; }
 bool Parser::GetImageEntryInfo(std::string, std::string, EntryInfo &) { return false; }
 long long Parser::ReadImageEntryRaw(std::string, std::string, unsigned char *, size_t) { return -1; }
+bool Parser::GetRunFileBytes(std::string &) { return false; }
 
 // keep only the events the run file knows about (reference ParseFolder/Parser.cpp:14-26)
 void Parser::VerifyEventList(std::vector<std::string> &EventList)

@@ -345,3 +345,13 @@ void ZipParser::GetRunFileInfo(std::vector<std::string> &EventListFromFile)
     while (ifs >> skip >> eventNum >> skip >> skip >> skip >> skip >> skip >> skip >> skip >> skip >> skip)
         EventListFromFile.push_back(std::to_string(eventNum));
 }
+
+bool ZipParser::GetRunFileBytes(std::string &bytes)
+{
+    BuildFileList();
+    std::vector<unsigned char> data;
+    if (index->runFileLoc < 0 || !readEntry(index->runFileLoc, data))
+        return false;
+    bytes.assign(data.begin(), data.end());
+    return true;
+}

@@ -24,14 +24,15 @@
 #include "ParseFolder/ZipParser.hpp"
 #include "driver.hpp"
 #include "runbatch.hpp"
+#include "zipwrite.hpp"
 
 static std::string usage()
 {
     return "Usage: abub3hs [-hzme] [-D data_series] [-c cam_mask_dir] [--debug code] -d data_dir -r run_ID -o out_dir\n"
            "       abub3hs [-hzm] [-D data_series] [-c cam_mask_dir] -d data_dir --runs ID[,ID...] | --run-list FILE -o out_dir\n"
-           "       abub3hs [-z] [-D data_series] -d data_dir -r run_ID --repack out_data_dir [--repack-gpu]\n"
-           "       abub3hs [-z] [-D data_series] -d data_dir -r run_ID --unpack out_data_dir [--unpack-gpu]\n"
-           "       abub3hs [-z] [-D data_series] -d data_dir -r run_ID --verify-repack other_data_dir [--verify-gpu]\n"
+           "       abub3hs [-z] [-D data_series] -d data_dir -r run_ID --repack out_data_dir [--repack-gpu] [--archive]\n"
+           "       abub3hs [-z] [-D data_series] -d data_dir -r run_ID --unpack out_data_dir [--unpack-gpu] [--archive]\n"
+           "       abub3hs [-z] [-D data_series] -d data_dir -r run_ID --verify-repack other_data_dir [--verify-gpu] [--archive]\n"
            "Run the AutoBub3hs bubble finding algorithm on a PICO run (MI355X hot path)\n\n"
            "Required arguments:\n"
            "  -d, --data_dir = Dir\t\tpath to the directory in which the run folder/file is stored\n"
@@ -79,6 +80,11 @@ static std::string usage()
            "\t\t\t\twith --repack Dir or --unpack Dir (the same Dir): repack or unpack first, then verify\n"
            "  --verify-gpu\t\t\twith --verify-repack: decode both sides and compare them on GPU 0 (the same findings and\n"
            "\t\t\t\tcounters); an error when there is no HIP device\n"
+           "  --archive\t\t\twith --repack, --unpack or --verify-repack: the copy is the one file Dir/<run_ID>.zip instead of\n"
+           "\t\t\t\tthe tree Dir/<run_ID>/: a zip archive of stored entries with the same files, every byte fixed by\n"
+           "\t\t\t\trule (the data of each entry at a multiple of 16; zip64 where it is needed), written as .zip.part\n"
+           "\t\t\t\tand renamed when it is complete; with the -gpu flags the entries are formed on the GPU and a batch\n"
+           "\t\t\t\tis one write.  Analyse it with -z -d Dir\n"
            "Environment: ABUB_TRAIN_ON_GPU=0 trains the runs of a campaign with the host Trainer\n"
            "             ABUB_REPACK_BATCH=n (a test knob) lowers the frames per batch of --repack-gpu and --unpack-gpu to n; the files\n"
            "             are the same\n"
@@ -249,6 +255,7 @@ int main(int argc, char **argv)
     std::vector<std::string> runs;          // of --runs / --run-list, in command-line order
     std::string peekDir;                    // --peek DIR: the DebugPeek images of the batched path (BatchedRunOptions::peekDir)
     bool havePeek = false;
+    bool archive = false; // --archive: the copy of --repack / --unpack / --verify-repack is Dir/<run_ID>.zip
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i], v;
         auto value = [&](std::string &dst) {
@@ -339,6 +346,8 @@ int main(int argc, char **argv)
             haveVerify = true;
         } else if (a == "--verify-gpu") {
             verifyGpu = true;
+        } else if (a == "--archive") {
+            archive = true;
         } else if (a == "--per-event") {
             perEvent = true;
         } else if (a == "--peek" || a.rfind("--peek=", 0) == 0) {
@@ -382,6 +391,10 @@ int main(int argc, char **argv)
     }
     if (verifyGpu && !haveVerify) {
         std::cerr << "--verify-gpu is valid only together with --verify-repack" << std::endl;
+        return -1;
+    }
+    if (archive && !haveRepack && !haveVerify) {
+        std::cerr << "--archive is valid only together with --repack, --unpack or --verify-repack" << std::endl;
         return -1;
     }
     if (haveRepack || haveVerify) {
@@ -437,10 +450,11 @@ int main(int argc, char **argv)
             const std::string srcDir = zipped ? std::string() : sp.eventDir;
             const std::string srcFile = zipped ? std::string() : sp.eventDir + run_number + ".txt";
             const std::string dst = repackDir + "/" + run_number;
+            const abub::ArchiveTarget target{archive, zipped ? abub::zipPathOf(sp.eventDir) : std::string()};
             rc = repackGpu ? (haveUnpack ? abub::UnpackRunDevice : abub::RepackRunDevice)(parser.get(), srcDir, srcFile, dst,
-                                                                                          sp.imageFolder, sp.numCams, threads, 0, &rs)
+                                                                                          sp.imageFolder, sp.numCams, threads, 0, &rs, target)
                            : (haveUnpack ? abub::UnpackRun : abub::RepackRun)(parser.get(), srcDir, srcFile, dst, sp.imageFolder,
-                                                                              sp.numCams, threads, &rs);
+                                                                              sp.numCams, threads, &rs, target);
         } catch (std::exception &e) {
             std::cerr << rewrite << " failed: " << e.what() << std::endl;
             return -6;
@@ -452,6 +466,9 @@ int main(int argc, char **argv)
                "%.1f frames/s\n",
                rewrite, rs.events, rs.packed, haveUnpack ? "written as PNG" : "packed", rs.bytesIn, rs.bytesOut, rs.copied, rs.failed, rs.total_s,
                rs.total_s > 0 ? (rs.packed + rs.copied) / rs.total_s : 0.0);
+        if (archive)
+            printf("%s: archive %s/%s.zip: %lld bytes, %lld entries\n", rewrite, repackDir.c_str(), run_number.c_str(), rs.archiveBytes,
+                   rs.archiveEntries);
         if (repackGpu) {
             if (rs.device < 0)
                 printf("%s-gpu: 0 frames encoded on the GPU, %lld took the host route (no frame of a width the GPU decoders "
@@ -467,13 +484,15 @@ int main(int argc, char **argv)
                 printf("%s-gpu: %lld frames decoded by the BMP kernel\n", rewrite, rs.framesGpuBmpDecoded);
             if (rs.framesGpuUnzipped)
                 printf("%s-gpu: %lld archive entries inflated on the GPU\n", rewrite, rs.framesGpuUnzipped);
+            if (archive && rs.device >= 0)
+                printf("%s-gpu: archive entries formed on GPU %d: pack %.2f s\n", rewrite, rs.device, rs.pack_s);
         }
         if (!haveVerify || rc != 0)
             return rc;
     }
     if (haveVerify) {
         const abub::RunSpec sp = runSpec(dataLoc, data_series, run_number, zipped);
-        const abub::RunSpec other = runSpec(verifyDir, data_series, run_number, false);
+        const abub::RunSpec other = runSpec(verifyDir, data_series, run_number, archive); // (--archive: Dir/<run_ID>.zip)
         const std::unique_ptr<Parser> parser = openRun(sp), copy = parser ? openRun(other) : nullptr;
         if (!parser || !copy)
             return -5;
@@ -483,8 +502,8 @@ int main(int argc, char **argv)
         try {
             const std::string srcFile = zipped ? std::string() : sp.eventDir + run_number + ".txt";
             const std::string otherFile = other.eventDir + run_number + ".txt";
-            rc = verifyGpu ? abub::VerifyRunDevice(parser.get(), copy.get(), srcFile, otherFile, sp.numCams, poolThreads(), 0, &vs, &findings)
-                           : abub::VerifyRun(parser.get(), copy.get(), srcFile, otherFile, sp.numCams, poolThreads(), &vs, &findings);
+            rc = verifyGpu ? abub::VerifyRunDevice(parser.get(), copy.get(), srcFile, otherFile, sp.numCams, poolThreads(), 0, &vs, &findings, archive)
+                           : abub::VerifyRun(parser.get(), copy.get(), srcFile, otherFile, sp.numCams, poolThreads(), &vs, &findings, archive);
         } catch (std::exception &e) {
             std::cerr << "verify failed: " << e.what() << std::endl;
             return -6;

@@ -26,6 +26,7 @@
 #include "bmpwalk.hpp"
 #include "pngwalk.hpp"
 #include "runbatch.hpp"
+#include "zipwrite.hpp"
 #include "stackresult.hpp"
 
 namespace {
@@ -230,7 +231,7 @@ static std::string eventFileOf(const Run &run)
     return folder + "/" + (slash == std::string::npos ? folder : folder.substr(slash + 1)) + ".txt";
 }
 static int runRepack(void *r, const char *dstRunDir, int ncams, int nthreads, int device, bool onDevice, double *stats,
-                     bool unpack = false)
+                     bool unpack = false, bool archive = false)
 {
     Run *run = (Run *)r;
     try {
@@ -242,17 +243,24 @@ static int runRepack(void *r, const char *dstRunDir, int ncams, int nthreads, in
         abub::RepackStats st;
         const std::string srcDir = run->kind == 0 ? run->runFolder : std::string();
         const int threads = std::max(1, nthreads);
+        const abub::ArchiveTarget target{archive, run->kind == 0 ? std::string() : abub::zipPathOf(run->runFolder)};
         const int rc = onDevice ? (unpack ? abub::UnpackRunDevice : abub::RepackRunDevice)(run->parser, srcDir, src, dstRunDir,
-                                                                                         run->imageFolder, ncams, threads, device, &st)
+                                                                                         run->imageFolder, ncams, threads, device, &st,
+                                                                                         target)
                                 : (unpack ? abub::UnpackRun : abub::RepackRun)(run->parser, srcDir, src, dstRunDir, run->imageFolder,
-                                                                               ncams, threads, &st);
+                                                                               ncams, threads, &st, target);
         if (stats) {
             const double v[20] = {(double)st.packed, (double)st.copied, (double)st.failed, (double)st.bytesIn, (double)st.bytesOut,
                                   st.total_s, (double)st.framesGpuEncoded, (double)st.framesGpuPngDecoded,
                                   (double)st.framesGpuUnpacked, (double)st.framesHostDecoded, (double)st.framesHostRoute,
                                   (double)st.batches, st.read_s, st.decode_s, st.encode_s, st.copy_s, st.write_s, (double)st.device,
                                   (double)st.framesGpuBmpDecoded, (double)st.framesGpuUnzipped};
-            std::memcpy(stats, v, (onDevice ? 20 : 6) * sizeof(double));
+            std::memcpy(stats, v, (onDevice || archive ? 20 : 6) * sizeof(double));
+            if (archive) {
+                stats[20] = (double)st.archiveBytes;
+                stats[21] = (double)st.archiveEntries;
+                stats[22] = st.pack_s;
+            }
         }
         return rc;
     } catch (std::exception &e) {
@@ -276,6 +284,34 @@ int abh_run_unpack_dev(void *r, const char *dstRunDir, int ncams, int nthreads, 
 {
     return runRepack(r, dstRunDir, ncams, nthreads, device, true, stats, true);
 }
+// --archive: the four entries above with the copy written as the one archive <dstRunDir>.zip (host/zipwrite.hpp).  device < 0:
+// the host route; unpack != 0: abh_run_unpack's codec.  stats (may be NULL): the 20 values of abh_run_repack_dev (those of
+// the device route 0 on the host route, the device -1), then [the archive's bytes, its entries, seconds of abub_zip_pack_dev]
+// (23 values).
+int abh_run_repack_archive(void *r, const char *dstRunDir, int ncams, int nthreads, int device, int unpack, double *stats)
+{
+    return runRepack(r, dstRunDir, ncams, nthreads, device, device >= 0, stats, unpack != 0, true);
+}
+// The host writer of the canonical archive alone: n entries (entry i: name_len[i] bytes of `names`, len[i] bytes of `data`,
+// both laid end to end) written to `path` through <path>.part.  Returns 0, or -1 (abh_zip_error() says why; no file is left)
+static thread_local std::string zipError;
+int abh_zip_write(const char *path, int n, const uint8_t *names, const uint32_t *name_len, const uint8_t *data, const uint64_t *len)
+{
+    try {
+        abub::ZipWriter zw(path);
+        for (int i = 0; i < n; ++i) {
+            zw.add(std::string((const char *)names, name_len[i]), data, (size_t)len[i]);
+            names += name_len[i];
+            data += len[i];
+        }
+        zw.finish();
+        return 0;
+    } catch (std::exception &e) {
+        zipError = e.what();
+        return -1;
+    }
+}
+const char *abh_zip_error() { return zipError.c_str(); }
 
 // abub::VerifyRun of two runs opened with abh_run_open: is `other` pixel for pixel the run `src`?  stats (may be NULL, 29
 // values; the last two: the source's and the other run's archive entries inflated by abub_unzip_dev, ABUB_GPU_UNZIP=1): [events, frames, same, same but not packed, copied, differ, missing, undecodable, extra, the event file (0 same,
@@ -285,7 +321,8 @@ int abh_run_unpack_dev(void *r, const char *dstRunDir, int ncams, int nthreads, 
 // taken), the source's and the other run's frames decoded by the BMP kernel].  report (may be NULL): one line per finding, "event\tname\tverdict\tndiff\tx\ty\tmax_abs\tw\th\tother_w\tother_h\n",
 // cut at report_cap - 1 characters; the whole text stays with `src` for abh_run_verify_report.  Returns VerifyRun's code, -1
 // on errors.  abh_run_verify_dev: abub::VerifyRunDevice on `device`, no fall-back when there is no such device.
-static int runVerify(void *a, void *b, int ncams, int nthreads, int device, bool onDevice, double *stats, char *report, int report_cap)
+static int runVerify(void *a, void *b, int ncams, int nthreads, int device, bool onDevice, double *stats, char *report, int report_cap,
+                     bool otherIsArchive = false)
 {
     Run *run = (Run *)a, *other = (Run *)b;
     try {
@@ -296,9 +333,9 @@ static int runVerify(void *a, void *b, int ncams, int nthreads, int device, bool
         abub::VerifyStats st;
         std::vector<abub::VerifyFinding> findings;
         const int rc = onDevice ? abub::VerifyRunDevice(run->parser, other->parser, eventFileOf(*run), eventFileOf(*other), ncams,
-                                                        std::max(1, nthreads), device, &st, &findings)
+                                                        std::max(1, nthreads), device, &st, &findings, otherIsArchive)
                                 : abub::VerifyRun(run->parser, other->parser, eventFileOf(*run), eventFileOf(*other), ncams,
-                                                  std::max(1, nthreads), &st, &findings);
+                                                  std::max(1, nthreads), &st, &findings, otherIsArchive);
         std::string &text = run->frames_of_last_query;
         text.clear();
         for (const abub::VerifyFinding &f : findings)
@@ -337,6 +374,12 @@ int abh_run_verify(void *src, void *other, int ncams, int nthreads, double *stat
 int abh_run_verify_dev(void *src, void *other, int ncams, int nthreads, int device, double *stats, char *report, int report_cap)
 {
     return runVerify(src, other, ncams, nthreads, device, true, stats, report, report_cap);
+}
+// --archive: `other` is a run opened from the archive that --repack --archive wrote; the event file is compared as bytes (the
+// archive's <run>.txt entry against the source's file or entry).  device < 0: the host route
+int abh_run_verify_archive(void *src, void *other, int ncams, int nthreads, int device, double *stats, char *report, int report_cap)
+{
+    return runVerify(src, other, ncams, nthreads, device, device >= 0, stats, report, report_cap, true);
 }
 // the whole report of the last abh_run_verify[_dev] on `src` (valid until the next query on it)
 const char *abh_run_verify_report(void *src)

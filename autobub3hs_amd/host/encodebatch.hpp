@@ -49,16 +49,18 @@ struct EncodeBatch {
         return File{r.status, h_out.get() + r.off, r.len};
     }
 
-    // The frames of W x H at pixels + src[f] (pixelsBytes: what may be read there) into files.  The meta buffer is
-    // [src | records | total]; the files go into `out`, at least `firstReserve` bytes of it, and when they outgrow it the
-    // list grows to the true total and the call is redone, once (Growable::fit; codec.outgrew is thrown after that).  Queued
-    // on `cs` and waited for.  The time up to the records' return, with every allocation, is added to encode_s, that of the
-    // files' copy to copy_s.
-    void run(const Codec &codec, const uint8_t *pixels, size_t pixelsBytes, const std::vector<uint64_t> &src, int W, int H,
-             size_t firstReserve, hipStream_t cs, double &encode_s, double &copy_s)
+    // The frames of W x H at pixels + src[f] (pixelsBytes: what may be read there) into files that stay ON THE DEVICE: file f
+    // is record(f).len bytes at deviceFiles() + record(f).off (a multiple of 16), of deviceBytes() in all, until the next
+    // call; only the records come back.  The meta buffer is [src | records | total]; the files go into `out`, at least
+    // `firstReserve` bytes of it, and when they outgrow it the list grows to the true total and the call is redone, once
+    // (Growable::fit; codec.outgrew is thrown after that).  Queued on `cs` and waited for.  The time, with every allocation,
+    // is added to encode_s.
+    void encode(const Codec &codec, const uint8_t *pixels, size_t pixelsBytes, const std::vector<uint64_t> &src, int W, int H,
+                size_t firstReserve, hipStream_t cs, double &encode_s)
     {
-        double t0 = nowMs();
+        const double t0 = nowMs();
         const size_t n = n_ = src.size();
+        bytes_ = 0;
         if (!n)
             return;
         const size_t metaBytes = n * (sizeof(uint64_t) + sizeof(abub_abf_file)) + sizeof(uint64_t);
@@ -80,10 +82,30 @@ struct EncodeBatch {
             HIPOK(hipStreamSynchronize(cs));
             std::memcpy(&bytes, records() + n, sizeof bytes);
         } while (!out.fit((size_t)bytes, codec.outgrew));
-        h_out.grow((size_t)bytes);
+        bytes_ = (size_t)bytes;
+        encode_s += (nowMs() - t0) * 1e-3;
+    }
+    struct Record {
+        int32_t status;
+        uint64_t off;
+        uint32_t len;
+    };
+    Record record(size_t f) const { return Record{records()[f].status, records()[f].off, records()[f].len}; }
+    const uint8_t *deviceFiles() const { return out.d.get(); }
+    size_t deviceBytes() const { return bytes_; }
+
+    // encode(), then the files to the host (file(f)); the time of their copy is added to copy_s
+    void run(const Codec &codec, const uint8_t *pixels, size_t pixelsBytes, const std::vector<uint64_t> &src, int W, int H,
+             size_t firstReserve, hipStream_t cs, double &encode_s, double &copy_s)
+    {
+        encode(codec, pixels, pixelsBytes, src, W, H, firstReserve, cs, encode_s);
+        if (!n_)
+            return;
+        double t0 = nowMs();
+        h_out.grow(bytes_); // (an allocation: encode_s, as ever)
         encode_s += (nowMs() - t0) * 1e-3;
         t0 = nowMs();
-        HIPOK(hipMemcpyAsync(h_out.get(), out.d.get(), (size_t)bytes, hipMemcpyDeviceToHost, cs));
+        HIPOK(hipMemcpyAsync(h_out.get(), out.d.get(), bytes_, hipMemcpyDeviceToHost, cs));
         HIPOK(hipStreamSynchronize(cs));
         copy_s += (nowMs() - t0) * 1e-3;
     }
@@ -102,7 +124,7 @@ private:
     } out;
     PinnedBuffer h_meta, h_out; // (h_out: the files on the host, as many bytes as a call wrote)
     DeviceBuffer d_meta, scratch;
-    size_t n_ = 0;
+    size_t n_ = 0, bytes_ = 0;
 };
 
 } // namespace abub

@@ -100,6 +100,17 @@ struct RepackStats {
     long long framesGpuUnzipped = 0; // ABUB_GPU_UNZIP=1: archive entries whose zip layer abub_unzip_dev inflated
     int device = -1, W = 0, H = 0, batches = 0;   // of the device route (device -1: it was not taken)
     double read_s = 0, decode_s = 0, encode_s = 0, copy_s = 0, write_s = 0; // its legs, summed over the batches
+    // --archive: the archive's size and entry count; of the device route, the time of abub_zip_pack_dev (its launches and the
+    // wait for them; the segment's copy to the host is copy_s, the host's own entries and the write are write_s)
+    long long archiveBytes = 0, archiveEntries = 0;
+    double pack_s = 0;
+};
+// --archive: the copy is the one file <dstRunDir>.zip (the canonical archive of zipwrite.hpp, DESIGN section 3, "A run as one
+// archive") instead of the tree <dstRunDir>/.  srcArchive: the archive the parser reads, empty for a directory run; it is
+// refused as the target like the source directory is
+struct ArchiveTarget {
+    bool on = false;
+    std::string srcArchive;
 };
 // abub3hs --repack: every frame of every event and camera 0 .. numCams-1 that `parser` lists, written in the packed format
 // (cv::abfEncode) to <dstRunDir>/<event>/<imageFolder>/<same name> on `nthreads` threads.  A source file that does not
@@ -108,7 +119,8 @@ struct RepackStats {
 // that parser->GetRunFileInfo lists.  No GPU.  Returns 0, or 1 if anything could not be written; throws, before anything
 // is written, when dstRunDir is srcRunDir (the directory the parser reads; empty for an archive).
 int RepackRun(Parser *parser, const std::string &srcRunDir, const std::string &srcRunFile, const std::string &dstRunDir,
-              const std::string &imageFolder, int numCams, int nthreads, RepackStats *stats);
+              const std::string &imageFolder, int numCams, int nthreads, RepackStats *stats,
+              const ArchiveTarget &archive = ArchiveTarget());
 // abub3hs --repack --repack-gpu: the same files, byte for byte, with the frames of the run's size (that of the first frame
 // that decodes) decoded by the GPU decoders and packed by abub_abf_encode_dev on `device`, in batches of at most 4 frames
 // per CU (ABUB_REPACK_BATCH=n, a test knob: of at most n); the pool's threads read and write the files, and pack on the spot what the decoders do not take (a frame the
@@ -116,16 +128,19 @@ int RepackRun(Parser *parser, const std::string &srcRunDir, const std::string &s
 // decoders do not take (a multiple of 4 from 4 to 2048) goes the host route whole.  Throws, before anything is written,
 // when there is no such device: there is no silent fall-back to the host route.
 int RepackRunDevice(Parser *parser, const std::string &srcRunDir, const std::string &srcRunFile, const std::string &dstRunDir,
-                    const std::string &imageFolder, int numCams, int nthreads, int device, RepackStats *stats);
+                    const std::string &imageFolder, int numCams, int nthreads, int device, RepackStats *stats,
+                    const ArchiveTarget &archive = ArchiveTarget());
 // abub3hs --unpack [--unpack-gpu]: the way back.  RepackRun / RepackRunDevice with another frame format: every frame is
 // written as a canonical Huffman-only PNG (cv::pngHuffEncode; on the device abub_png_encode_dev, the same bytes) under its
 // own name, so that anything that reads PNG reads the run again; the source may be packed, PNG, BMP or mixed.  Layout,
 // event file, refusals, return value and stats as there (packed / bytesOut count the PNG files written,
 // framesGpuEncoded those abub_png_encode_dev wrote).
 int UnpackRun(Parser *parser, const std::string &srcRunDir, const std::string &srcRunFile, const std::string &dstRunDir,
-              const std::string &imageFolder, int numCams, int nthreads, RepackStats *stats);
+              const std::string &imageFolder, int numCams, int nthreads, RepackStats *stats,
+              const ArchiveTarget &archive = ArchiveTarget());
 int UnpackRunDevice(Parser *parser, const std::string &srcRunDir, const std::string &srcRunFile, const std::string &dstRunDir,
-                    const std::string &imageFolder, int numCams, int nthreads, int device, RepackStats *stats);
+                    const std::string &imageFolder, int numCams, int nthreads, int device, RepackStats *stats,
+                    const ArchiveTarget &archive = ArchiveTarget());
 
 // What verify says about one frame, an extra frame or event, or the event file
 struct VerifyFinding {
@@ -169,8 +184,11 @@ struct VerifyStats {
 // when one of the names is empty or the source's cannot be read).  `findings` (may be NULL) gets every failure and every
 // same_not_packed frame in task order, then the extras, then the event file if it fails.  No GPU.  Returns 0 if nothing
 // failed, else 1.
+// otherIsArchive (--archive): the copy is an archive, and the event file is compared as bytes: the copy's side is what
+// other->GetRunFileBytes hands out (missing where it has none), the source's its file srcRunFile or, for a zipped source,
+// what src->GetRunFileBytes hands out (not compared where there is neither); otherRunFile only names the finding.
 int VerifyRun(Parser *src, Parser *other, const std::string &srcRunFile, const std::string &otherRunFile, int numCams, int nthreads,
-              VerifyStats *stats, std::vector<VerifyFinding> *findings);
+              VerifyStats *stats, std::vector<VerifyFinding> *findings, bool otherIsArchive = false);
 // abub3hs --verify-repack --verify-gpu: the same verdicts, findings and counters.  The frames of the run's size (that of
 // the source's first frame that decodes) are decoded on both sides by the GPU decoders on `device`, in batches of at most
 // 4 frames per CU (ABUB_VERIFY_BATCH=n: of n), and compared by abub_frames_compare_dev; every other frame (a file that does
@@ -178,7 +196,7 @@ int VerifyRun(Parser *src, Parser *other, const std::string &srcRunFile, const s
 // run whose width the decoders do not take, or without a frame that decodes, goes the host route whole.  Throws, before
 // anything else, when there is no such device: there is no silent fall-back to the host route.
 int VerifyRunDevice(Parser *src, Parser *other, const std::string &srcRunFile, const std::string &otherRunFile, int numCams,
-                    int nthreads, int device, VerifyStats *stats, std::vector<VerifyFinding> *findings);
+                    int nthreads, int device, VerifyStats *stats, std::vector<VerifyFinding> *findings, bool otherIsArchive = false);
 
 // A run listed and trained, ready for detect; rc = -5 (the run cannot be read) or -7 (a camera did not train)
 struct PreparedRun {

@@ -378,8 +378,25 @@ int compareEventFiles(const std::string &srcRunFile, const std::string &otherRun
     return sa.str() == sb.str() ? VerifyStats::FileSame : VerifyStats::FileDiffers;
 }
 
+// The same where the copy is an archive: its side is the bytes of its <run>.txt entry, the source's side its file or, for a
+// zipped source, its own entry
+int compareEventFileBytes(Parser *src, Parser *other, const std::string &srcRunFile)
+{
+    std::string a, b;
+    std::ifstream in(srcRunFile, std::ios::binary);
+    if (!srcRunFile.empty() && in) {
+        std::ostringstream sa;
+        sa << in.rdbuf();
+        a = sa.str();
+    } else if (!src->GetRunFileBytes(a))
+        return VerifyStats::FileNotCompared; // (repack then wrote a file of its own making)
+    if (!other->GetRunFileBytes(b))
+        return VerifyStats::FileMissing;
+    return a == b ? VerifyStats::FileSame : VerifyStats::FileDiffers;
+}
+
 int verifyRun(Parser *src, Parser *other, const std::string &srcRunFile, const std::string &otherRunFile, int numCams, int nthreads,
-              int device, VerifyStats *stats, std::vector<VerifyFinding> *findings)
+              int device, VerifyStats *stats, std::vector<VerifyFinding> *findings, bool otherIsArchive)
 {
     const double t0 = nowMs();
     VerifyStats st;
@@ -428,7 +445,7 @@ int verifyRun(Parser *src, Parser *other, const std::string &srcRunFile, const s
     }
     st.extra = (long long)pl.extras.size();
     found.insert(found.end(), pl.extras.begin(), pl.extras.end());
-    st.eventFile = compareEventFiles(srcRunFile, otherRunFile);
+    st.eventFile = otherIsArchive ? compareEventFileBytes(src, other, srcRunFile) : compareEventFiles(srcRunFile, otherRunFile);
     if (st.eventFile == VerifyStats::FileDiffers || st.eventFile == VerifyStats::FileMissing) {
         VerifyFinding f;
         f.verdict = st.eventFile == VerifyStats::FileDiffers ? VerifyFinding::EventFileDiffers : VerifyFinding::EventFileMissing;
@@ -450,17 +467,17 @@ int verifyRun(Parser *src, Parser *other, const std::string &srcRunFile, const s
 } // namespace
 
 int VerifyRun(Parser *src, Parser *other, const std::string &srcRunFile, const std::string &otherRunFile, int numCams, int nthreads,
-              VerifyStats *stats, std::vector<VerifyFinding> *findings)
+              VerifyStats *stats, std::vector<VerifyFinding> *findings, bool otherIsArchive)
 {
-    return verifyRun(src, other, srcRunFile, otherRunFile, numCams, nthreads, -1, stats, findings);
+    return verifyRun(src, other, srcRunFile, otherRunFile, numCams, nthreads, -1, stats, findings, otherIsArchive);
 }
 
 int VerifyRunDevice(Parser *src, Parser *other, const std::string &srcRunFile, const std::string &otherRunFile, int numCams,
-                    int nthreads, int device, VerifyStats *stats, std::vector<VerifyFinding> *findings)
+                    int nthreads, int device, VerifyStats *stats, std::vector<VerifyFinding> *findings, bool otherIsArchive)
 {
     if (device < 0)
         throw std::runtime_error("verify: no such HIP device: " + std::to_string(device));
-    return verifyRun(src, other, srcRunFile, otherRunFile, numCams, nthreads, device, stats, findings);
+    return verifyRun(src, other, srcRunFile, otherRunFile, numCams, nthreads, device, stats, findings, otherIsArchive);
 }
 
 } // namespace abub

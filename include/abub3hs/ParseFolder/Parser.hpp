@@ -54,6 +54,9 @@ public:
     virtual void ParseAndSortFramesInFolder(std::string EventID, int camera, std::vector<std::string> &Contents) = 0;
 
     virtual void GetRunFileInfo(std::vector<std::string> &info) = 0;
+    // not in the reference: the bytes of the run's event file where the parser itself holds it (an archive's <run>.txt
+    // entry); false = it does not (a directory run's event file is a file the caller opens), or it cannot be read
+    virtual bool GetRunFileBytes(std::string &bytes);
     void VerifyEventList(std::vector<std::string> &EventList);
 };
 

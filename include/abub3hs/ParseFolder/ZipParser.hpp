@@ -45,6 +45,7 @@ public:
     void GetFileLists(const char *EventFolder, std::vector<std::string> &FileList, const char *camera_out_name) override;
     void ParseAndSortFramesInFolder(std::string EventID, int camera, std::vector<std::string> &Contents) override;
     void GetRunFileInfo(std::vector<std::string> &EventListFromFile) override;
+    bool GetRunFileBytes(std::string &bytes) override;
 
 private:
     void BuildFileList();

@@ -714,6 +714,38 @@ int abub_png_encode_dev(const uint8_t *pixels, size_t pixels_bytes, const uint64
                         uint8_t *out, size_t out_cap, abub_abf_file *files, uint64_t *total, void *scratch,
                         size_t scratch_bytes, void *stream);
 
+/* ---- resident files packed into a segment of a zip archive (abub_zip_pack.hip) ----------------------------------------
+ * The files a GPU encoder left in device memory become stored entries of the canonical archive of abub3hs --archive
+ * ("A run as one archive"; the host writer host/zipwrite.cpp is the definition).  Per item the call
+ * writes exactly [dst, dst + 30 + name_len + extra_len + len) of `seg`: the local header with the CRC-32 in it (signature
+ * 0x04034b50, version 20, flags 0, method 0, time 0, date 0x0021, crc, len, len, name_len, extra_len), the name, the
+ * padding field (u16 0x4241, u16 extra_len - 4, zeros; none when extra_len is 0) and the len bytes from buf + src.  It
+ * writes crc[i] (zlib.crc32 of those bytes) and status[i] = 0.  Nothing else of `seg` is touched and `seg` is never read;
+ * the gaps between the items are the host's.  Two items may name the same src; their dst ranges must not overlap.
+ * An item is refused with status[i] = ABUB_ZIP_E_DESC, crc[i] = 0 and not one byte of `seg` written when: src is no
+ * multiple of 16 or [src, src + len) leaves buf_bytes; len is 2^32 - 1; [name, name + name_len) leaves names_bytes;
+ * extra_len is 1, 2 or 3; [dst, dst + 30 + name_len + extra_len + len) leaves seg_bytes; or len > 0 and
+ * dst + 30 + name_len + extra_len is no multiple of 16 (an item of length 0 has no data to align).
+ * ABUB_ZIP_PACK_TILE bytes of a file are one tile: the second launch runs over (item, tile), loads every source byte once
+ * with 16-byte loads for both its store and its CRC, and adds the tile's CRC register, moved over the bytes behind the
+ * tile by a carry-less multiplication with x^(8 * bytes), into crc[i] (xor is commutative: the result does not depend on
+ * the order).  Three launches on `stream` (check the descriptors and clear crc; the tiles; condition the CRCs and write
+ * the headers): every dependence between workgroups is a launch boundary.  Every pointer is a device pointer, buf and seg
+ * 16-byte aligned, items 8-byte, crc and status 4-byte.  Null pointers, nitems < 0 or a misaligned pointer: ABUB_E_INVALID
+ * before anything touches the device; nitems == 0: ABUB_OK, nothing touched.  No host synchronisation, no allocation. */
+#define ABUB_ZIP_PACK_TILE 65536
+typedef struct abub_zip_item {
+    uint64_t src;        /* the file's bytes at buf + src, a multiple of 16 */
+    uint64_t dst;        /* its local header at seg + dst; dst + 30 + name_len + extra_len is a multiple of 16 */
+    uint32_t len;        /* < 2^32 - 1 */
+    uint32_t name;       /* the name at names + name */
+    uint16_t name_len, extra_len;
+    uint32_t reserved;
+} abub_zip_item;         /* 32 bytes */
+int abub_zip_pack_dev(const uint8_t *buf, size_t buf_bytes, const abub_zip_item *items, int nitems,
+                      const uint8_t *names, size_t names_bytes, uint8_t *seg, size_t seg_bytes,
+                      uint32_t *crc, int32_t *status, void *stream);
+
 /* ---- resident frames compared byte for byte (abub_compare.hip) ------------------------------------------------------
  * What memcmp of two decoded frames, and a byte loop behind it, does on a host thread, for a batch of resident frames:
  * results[p] says how many of the frame_bytes bytes at a + pairs[p].a and b + pairs[p].b differ, where the first one is
