@@ -652,6 +652,36 @@ def frames_compare(a, b, pairs, frame_bytes, a_bytes=None, b_bytes=None, results
     return results.reshape(-1)[:4 * n].cpu().numpy().view(np.uint32).astype(np.int64).reshape(n, 4)
 
 
+STAT_NONE = 0xFFFFFFFFFFFFFFFF  # abub_stat_job.ref / .model: no reference frame / no model
+STAT_COLUMNS = ("status", "min", "max", "n_zero", "n_sat", "n_out", "n_moved", "flags", "sum", "sumsq", "sum_out", "sum_moved")
+
+
+def frame_stats(frames, jobs, frame_bytes, mu=None, sigma6=None, frames_bytes=None, model_bytes=None, results=None):
+    """abub_frame_stats_dev: frames u8 (any shape; frames of frame_bytes bytes anywhere in it), jobs: [n, 3] byte offsets
+    (cur, ref, model) of each job's frame and reference frame in `frames` and of its model in mu / sigma6 (u8, the same
+    size; any alignment; STAT_NONE or a negative number: no reference frame / no model; mu=None: no job has a model);
+    frames_bytes / model_bytes: the sizes the kernel is told (default: the tensors'); results: uint8 device tensor of at
+    least 64 * n bytes, 8-byte aligned, written in place (None: a new one) -> uint64 [n, 12] on the host, the columns of
+    STAT_COLUMNS; status 0 or ABUB_STAT_E_RANGE = 1, flags bit 0: n_out / sum_out valid, bit 1: n_moved / sum_moved valid."""
+    import numpy as np
+    _need_cuda(frames, mu, sigma6, results)
+    offs = np.array([[STAT_NONE if int(v) < 0 else int(v) for v in row] for row in jobs], dtype=np.uint64).reshape(-1, 3)
+    n = len(offs)
+    dev = frames.device
+    d_jobs = torch.from_numpy(np.concatenate([offs, np.zeros((1, 3), np.uint64)]).view(np.int64)).to(dev)
+    if results is None:
+        results = torch.empty((max(n, 1) * 64,), dtype=torch.uint8, device=dev)
+    if model_bytes is None:
+        model_bytes = 0 if mu is None else min(mu.numel(), sigma6.numel())
+    _lib.check(_lib.lib().abub_frame_stats_dev(_ptr(frames), frames.numel() if frames_bytes is None else int(frames_bytes),
+                                               None if mu is None else _ptr(mu), None if sigma6 is None else _ptr(sigma6),
+                                               int(model_bytes), _ptr(d_jobs), n, int(frame_bytes), _ptr(results), _stream()),
+               "abub_frame_stats_dev")
+    raw = results.reshape(-1)[:64 * n].cpu().numpy()
+    return np.concatenate([raw.view(np.uint32).reshape(n, 16)[:, :8].astype(np.uint64), raw.view(np.uint64).reshape(n, 8)[:, 4:]],
+                          axis=1)
+
+
 def peek_items(rows):
     """rows of (diff, frame, thr_out, pres_out, thr, rect_begin, rect_count) -> the abub_peek_item records as a uint8 host
     array (48 bytes each)."""

@@ -62,6 +62,10 @@ SIGNATURES = {
     "abh_run_verify_report": (_s, [_vp]),
     "abh_run_repack_archive": (_i, [_vp, _s, _i, _i, _i, _i, _dp]),
     "abh_run_verify_archive": (_i, [_vp, _vp, _i, _i, _i, _dp, C.c_char_p, _i]),
+    "abh_run_survey": (_i, [_vp, _s, _i, _i, _dp, C.c_char_p, _i]),
+    "abh_run_survey_dev": (_i, [_vp, _s, _i, _i, _i, _dp, C.c_char_p, _i]),
+    "abh_run_survey_report": (_s, [_vp]),
+    "abh_frame_stats_host": (None, [_u8p, _u8p, _u8p, _u8p, C.c_uint64, _u64p]),
     "abh_zip_write": (_i, [_s, _i, _u8p, _u32p, _u8p, _u64p]),
     "abh_zip_error": (_s, []),
     "abh_png_walk": (_i, [_u8p, _i, _i, _i, _u32p, _i, _ip, _ip, _u8p]),
@@ -432,12 +436,56 @@ class Run:
                 res["findings"].append(dict(event=f[0], name=f[1], verdict=f[2], **{k: int(v) for k, v in zip(cols, f[3:])}))
         return res
 
+    _SURVEY_KEYS = ("events", "frames", "ok", "undecodable", "missing", "other_size", "frames_kernel", "frames_host_route",
+                    "gpu_png_decoded", "gpu_unpacked", "gpu_bmp_decoded", "host_decoded", "reread", "frames_gpu_unzipped", "device",
+                    "W", "H", "batches", "model_cams")
+
+    def survey(self, path=None, nthreads=16, ncams=4, device=None):
+        """abub3hs --survey of this run (opened from a directory or an archive): the run is listed and trained as for
+        detect, then every frame of cameras 0 .. ncams-1 is measured without analysing any; the report (DESIGN section 3,
+        "Surveying a run") is written to `path` (None: it is not written).  device=None: host threads (cv::imdecode and
+        byte loops, the definition).  device=N (--survey-gpu): the same report, byte for byte, the frames decoded and
+        measured (abub_frame_stats_dev) on that GPU; raises when there is no such device.
+        -> (stats dict: rc (0, or 1 if a frame is not ok), the counters of the states, frames_kernel / frames_host_route,
+        the decoder lanes' counts, batches, device (-1: its route was not taken), W, H, model_cams and the legs read_s,
+        decode_s, stats_s, seconds; the report's text)."""
+        L = lib()
+        st = (C.c_double * 24)()
+        cap = 1 << 16
+        buf = C.create_string_buffer(cap)
+        to = None if path is None else str(path).encode()
+        if device is None:
+            rc = L.abh_run_survey(self._h, to, ncams, nthreads, st, buf, cap)
+        else:
+            rc = L.abh_run_survey_dev(self._h, to, ncams, nthreads, int(device), st, buf, cap)
+        if rc not in (0, 1):
+            raise RuntimeError(f"abh_run_survey rc={rc}: " + L.abh_last_error(self._h).decode())
+        text = buf.value if st[23] < cap else L.abh_run_survey_report(self._h)
+        res = {"rc": rc, **{k: int(v) for k, v in zip(self._SURVEY_KEYS, list(st))}}
+        res.update(read_s=st[19], decode_s=st[20], stats_s=st[21], seconds=st[22])
+        return res, text.decode()
+
     def analyze(self, event, cam, maskdir=""):
         L = lib()
         staged = L.abh_analyze(self._h, str(event).encode(), cam, maskdir.encode())
         if staged == -100:
             raise RuntimeError(L.abh_last_error(self._h).decode())
         return _read_result(L.abh_run_last(self._h), with_dz=True)
+
+
+FRAME_STATS_KEYS = ("min", "max", "n_zero", "n_sat", "n_out", "n_moved", "flags", "sum", "sumsq", "sum_out", "sum_moved")
+
+
+def frame_stats_host(cur, ref=None, mu=None, sigma6=None):
+    """abub::frameStatsHost (host/survey.cpp), the definition of abub_frame_stats_dev: cur u8 (any shape), ref / mu / sigma6
+    of its size or None (sigma6 = min(6 sigma, 255) goes with mu) -> dict of FRAME_STATS_KEYS; flags bit 0: n_out / sum_out
+    are valid (there is a model), bit 1: n_moved / sum_moved are (a model and a reference frame)."""
+    arrs = [None if a is None else np.ascontiguousarray(a, dtype=np.uint8).reshape(-1) for a in (cur, ref, mu, sigma6)]
+    n = arrs[0].size
+    assert all(a is None or a.size == n for a in arrs) and (arrs[2] is None) == (arrs[3] is None)
+    out = np.zeros(11, np.uint64)
+    lib().abh_frame_stats_host(*[None if a is None else a.ctypes.data_as(_u8p) for a in arrs], n, out.ctypes.data_as(_u64p))
+    return dict(zip(FRAME_STATS_KEYS, (int(v) for v in out)))
 
 
 def zip_write(path, entries):

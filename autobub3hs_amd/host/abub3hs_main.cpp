@@ -33,6 +33,7 @@ static std::string usage()
            "       abub3hs [-z] [-D data_series] -d data_dir -r run_ID --repack out_data_dir [--repack-gpu] [--archive]\n"
            "       abub3hs [-z] [-D data_series] -d data_dir -r run_ID --unpack out_data_dir [--unpack-gpu] [--archive]\n"
            "       abub3hs [-z] [-D data_series] -d data_dir -r run_ID --verify-repack other_data_dir [--verify-gpu] [--archive]\n"
+           "       abub3hs [-z] [-D data_series] -d data_dir -r run_ID --survey FILE [--survey-gpu]\n"
            "Run the AutoBub3hs bubble finding algorithm on a PICO run (MI355X hot path)\n\n"
            "Required arguments:\n"
            "  -d, --data_dir = Dir\t\tpath to the directory in which the run folder/file is stored\n"
@@ -85,6 +86,14 @@ static std::string usage()
            "\t\t\t\trule (the data of each entry at a multiple of 16; zip64 where it is needed), written as .zip.part\n"
            "\t\t\t\tand renamed when it is complete; with the -gpu flags the entries are formed on the GPU and a batch\n"
            "\t\t\t\tis one write.  Analyse it with -z -d Dir\n"
+           "  --survey = File\t\tmeasure every frame of the run without analysing any and write the report to File: per camera\n"
+           "\t\t\t\tthe model (pixels with sigma = 0, with 6 sigma >= 255), per frame its state (ok, undecodable,\n"
+           "\t\t\t\tmissing, other_size), grey-level range, sum, sum of squares, black and saturated pixels, and count\n"
+           "\t\t\t\tand sum of what the model and the frame two before leave above 6 sigma; a `run` line with the\n"
+           "\t\t\t\ttotals; exit status 0, or 1 if a frame is not ok; no -o; not with -e, --debug, --per-event, --merge,\n"
+           "\t\t\t\t--repack, --unpack, --verify-repack, --peek, --runs / --run-list, --gpu-shard\n"
+           "  --survey-gpu\t\t\twith --survey: decode the frames and measure them on GPU 0 (the same report, byte for byte); an\n"
+           "\t\t\t\terror when there is no HIP device\n"
            "Environment: ABUB_TRAIN_ON_GPU=0 trains the runs of a campaign with the host Trainer\n"
            "             ABUB_REPACK_BATCH=n (a test knob) lowers the frames per batch of --repack-gpu and --unpack-gpu to n; the files\n"
            "             are the same\n"
@@ -256,6 +265,8 @@ int main(int argc, char **argv)
     std::string peekDir;                    // --peek DIR: the DebugPeek images of the batched path (BatchedRunOptions::peekDir)
     bool havePeek = false;
     bool archive = false; // --archive: the copy of --repack / --unpack / --verify-repack is Dir/<run_ID>.zip
+    std::string surveyFile; // --survey FILE: the run measured frame by frame (abub::SurveyRun), nothing else
+    bool haveSurvey = false, surveyGpu = false;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i], v;
         auto value = [&](std::string &dst) {
@@ -348,6 +359,11 @@ int main(int argc, char **argv)
             verifyGpu = true;
         } else if (a == "--archive") {
             archive = true;
+        } else if (a == "--survey" || a.rfind("--survey=", 0) == 0) {
+            value(surveyFile);
+            haveSurvey = true;
+        } else if (a == "--survey-gpu") {
+            surveyGpu = true;
         } else if (a == "--per-event") {
             perEvent = true;
         } else if (a == "--peek" || a.rfind("--peek=", 0) == 0) {
@@ -372,6 +388,23 @@ int main(int argc, char **argv)
         }
         if (peekDir.empty()) {
             std::cerr << "--peek needs the directory to write to" << std::endl;
+            return -1;
+        }
+    }
+    if (surveyGpu && !haveSurvey) {
+        std::cerr << "--survey-gpu is valid only together with --survey" << std::endl;
+        return -1;
+    }
+    if (haveSurvey) {
+        const char *bad = haveUnpack ? "--unpack" : haveRepack ? "--repack" : haveVerify ? "--verify-repack" : mergeN > 0 ? "--merge"
+                          : debug_mode ? "--debug" : perEvent ? "--per-event" : event_user >= 0 ? "-e/--event" : havePeek ? "--peek"
+                          : haveList ? "--runs / --run-list" : haveShard ? "--gpu-shard" : nullptr;
+        if (bad) {
+            std::cerr << "--survey cannot be combined with " << bad << std::endl;
+            return -1;
+        }
+        if (dataLoc.empty() || run_number.empty() || surveyFile.empty()) {
+            std::cerr << "--survey needs --data_dir, --run_id and the file to write the report to" << std::endl;
             return -1;
         }
     }
@@ -534,6 +567,48 @@ int main(int argc, char **argv)
             if (vs.srcGpuBmpDecoded || vs.otherGpuBmpDecoded)
                 printf("verify-gpu: %lld frames decoded by the BMP kernel (the source's %lld, the copy's %lld)\n",
                        vs.srcGpuBmpDecoded + vs.otherGpuBmpDecoded, vs.srcGpuBmpDecoded, vs.otherGpuBmpDecoded);
+        }
+        return rc;
+    }
+    if (haveSurvey) {
+        // ---- --survey: the run listed and trained as for detect (abub::PrepareRun), then measured; nothing else happens --------
+        const abub::RunSpec sp = runSpec(dataLoc, data_series, run_number, zipped);
+        abub::BatchedRunOptions po;
+        po.trainOnGpu = 0; // (a single run trains through the host Trainer, as the reference does)
+        abub::SurveyStats ss;
+        int rc = 1;
+        try {
+            abub::PreparedRun prep = abub::PrepareRun(sp, po, 0, nullptr, false);
+            if (prep.rc == -5)
+                return -5;
+            if (prep.rc)
+                printf("survey: a camera did not train: the report has no model columns for it\n");
+            rc = surveyGpu ? abub::SurveyRunDevice(prep.parser.get(), prep.trainers, sp.numCams, sp.imageFormat, surveyFile, poolThreads(), 0,
+                                                   &ss, nullptr)
+                           : abub::SurveyRun(prep.parser.get(), prep.trainers, sp.numCams, sp.imageFormat, surveyFile, poolThreads(), &ss,
+                                             nullptr);
+        } catch (std::exception &e) {
+            std::cerr << "survey failed: " << e.what() << std::endl;
+            return -6;
+        } catch (...) { // (the parsers throw their status codes)
+            std::cerr << "Failed to read the images from run " << run_number << "." << std::endl;
+            return -5;
+        }
+        printf("survey: %d events, %lld frames %dx%d: %lld ok, %lld undecodable, %lld missing, %lld of another size; %d cameras with a "
+               "model; %.2f s, %.1f frames/s\n",
+               ss.events, ss.frames, ss.W, ss.H, ss.ok, ss.undecodable, ss.missing, ss.otherSize, ss.modelCams, ss.total_s,
+               ss.total_s > 0 ? ss.frames / ss.total_s : 0.0);
+        if (surveyGpu) {
+            if (ss.device < 0)
+                printf("survey-gpu: 0 frames measured on the GPU, %lld took the host route (no frame of a width the GPU decoders "
+                       "take)\n",
+                       ss.framesHostRoute);
+            else
+                printf("survey-gpu: %lld frames measured on GPU %d (decoded: %lld by the PNG kernel, %lld by the packed kernel, %lld by "
+                       "the BMP kernel, %lld by a host thread; %lld read again, %lld archive entries inflated on the GPU), %lld took the "
+                       "host route, %d batches; read %.2f s, upload + decode %.2f s, measure %.2f s\n",
+                       ss.framesKernel, ss.device, ss.gpuPngDecoded, ss.gpuUnpacked, ss.gpuBmpDecoded, ss.hostDecoded, ss.reread,
+                       ss.gpuUnzipped, ss.framesHostRoute, ss.batches, ss.read_s, ss.decode_s, ss.stats_s);
         }
         return rc;
     }

@@ -34,7 +34,7 @@ namespace {
 struct Run {
     Parser *parser = nullptr; // MemParser (tests / synthetic), RawParser or ZipParser
     int kind = -1;            // of abh_run_open
-    std::string runFolder, imageFolder;
+    std::string runFolder, imageFolder, imageFormat;
     MemParser *mem = nullptr;
     std::string frames_of_last_query;
     std::map<int, Trainer *> trainers;
@@ -101,6 +101,7 @@ void *abh_run_open(int kind, const char *runFolder, const char *imageFolder, con
         r->kind = kind;
         r->runFolder = runFolder;
         r->imageFolder = imageFolder;
+        r->imageFormat = imageFormat;
         return r;
     } catch (int code) {
         return nullptr;
@@ -385,6 +386,90 @@ int abh_run_verify_archive(void *src, void *other, int ncams, int nthreads, int 
 const char *abh_run_verify_report(void *src)
 {
     return ((Run *)src)->frames_of_last_query.c_str();
+}
+
+// abub::SurveyRun of a run opened with abh_run_open (abub3hs --survey): the run is listed and trained the way the CLI does it
+// (abub::PrepareRun, the host Trainer; a camera that does not train has no model), then every frame is measured.  path (may
+// be NULL or empty): where the report is written.  stats (may be NULL, 24 values): [events, frames, ok, undecodable, missing,
+// other size, frames measured by the kernel, frames that took the host route, frames decoded by the PNG kernel, by the
+// packed kernel, by the BMP kernel, by a host thread for the slab, reference frames read again, archive entries inflated on
+// the GPU, the device (-1: its route was not taken), W, H, batches, cameras with a model, seconds of the legs read, upload +
+// decode, measure, seconds in all, the report's length].  report (may be NULL): the report's text, cut at report_cap - 1
+// characters; the whole text stays with the run for abh_run_survey_report.  Returns SurveyRun's code (0, or 1 if a frame is
+// not ok), -5 if the run cannot be read, -1 on errors.  abh_run_survey_dev: abub::SurveyRunDevice on `device`, no fall-back
+// when there is no such device.
+static int runSurvey(void *r, const char *path, int ncams, int nthreads, int device, bool onDevice, double *stats, char *report,
+                     int report_cap)
+{
+    Run *run = (Run *)r;
+    try {
+        if (run->kind < 0) {
+            run->last.error = "survey: not a run opened from a directory or an archive";
+            return -1;
+        }
+        abub::RunSpec sp;
+        sp.eventDir = run->runFolder;
+        sp.imageFolder = run->imageFolder;
+        sp.imageFormat = run->imageFormat;
+        sp.numCams = ncams;
+        sp.zipped = run->kind == 1;
+        abub::BatchedRunOptions bo;
+        bo.trainOnGpu = 0;
+        abub::PreparedRun pr = abub::PrepareRun(sp, bo, 0, nullptr, true);
+        if (pr.rc == -5)
+            return -5;
+        abub::SurveyStats st;
+        std::vector<abub::SurveyRow> rows;
+        std::vector<abub::SurveyModel> models;
+        const std::string to = path ? path : "";
+        const int rc = onDevice ? abub::SurveyRunDevice(pr.parser.get(), pr.trainers, ncams, sp.imageFormat, to, std::max(1, nthreads),
+                                                        device, &st, &rows, &models)
+                                : abub::SurveyRun(pr.parser.get(), pr.trainers, ncams, sp.imageFormat, to, std::max(1, nthreads), &st,
+                                                  &rows, &models);
+        std::string &text = run->frames_of_last_query;
+        text = abub::SurveyReport(models, rows);
+        if (report && report_cap > 0) {
+            const size_t n = std::min(text.size(), (size_t)report_cap - 1);
+            std::memcpy(report, text.data(), n);
+            report[n] = 0;
+        }
+        if (stats) {
+            const double v[24] = {(double)st.events, (double)st.frames, (double)st.ok, (double)st.undecodable, (double)st.missing,
+                                  (double)st.otherSize, (double)st.framesKernel, (double)st.framesHostRoute, (double)st.gpuPngDecoded,
+                                  (double)st.gpuUnpacked, (double)st.gpuBmpDecoded, (double)st.hostDecoded, (double)st.reread,
+                                  (double)st.gpuUnzipped, (double)st.device, (double)st.W, (double)st.H, (double)st.batches,
+                                  (double)st.modelCams, st.read_s, st.decode_s, st.stats_s, st.total_s, (double)text.size()};
+            std::memcpy(stats, v, sizeof v);
+        }
+        return rc;
+    } catch (std::exception &e) {
+        run->last.error = e.what();
+        return -1;
+    } catch (...) { // (the parsers throw their status codes)
+        run->last.error = "survey: the run could not be read";
+        return -1;
+    }
+}
+int abh_run_survey(void *r, const char *path, int ncams, int nthreads, double *stats, char *report, int report_cap)
+{
+    return runSurvey(r, path, ncams, nthreads, -1, false, stats, report, report_cap);
+}
+int abh_run_survey_dev(void *r, const char *path, int ncams, int nthreads, int device, double *stats, char *report, int report_cap)
+{
+    return runSurvey(r, path, ncams, nthreads, device, true, stats, report, report_cap);
+}
+// the whole report of the last abh_run_survey[_dev] on the run (valid until the next query on it)
+const char *abh_run_survey_report(void *r)
+{
+    return ((Run *)r)->frames_of_last_query.c_str();
+}
+// abub::frameStatsHost on raw buffers of n bytes (ref, mu may be NULL; sigma6 = min(6 sigma, 255) goes with mu): out[11] =
+// [min, max, n_zero, n_sat, n_out, n_moved, flags, sum, sumsq, sum_out, sum_moved]
+void abh_frame_stats_host(const uint8_t *cur, const uint8_t *ref, const uint8_t *mu, const uint8_t *sigma6, uint64_t n, uint64_t *out)
+{
+    const abub::FrameStats s = abub::frameStatsHost(cur, ref, mu, sigma6, (size_t)n);
+    const uint64_t v[11] = {s.min, s.max, s.nZero, s.nSat, s.nOut, s.nMoved, s.flags, s.sum, s.sumsq, s.sumOut, s.sumMoved};
+    std::memcpy(out, v, sizeof v);
 }
 
 // bmpWalk (host/bmpwalk.hpp: what the reading threads learn about a BMP before the GPU decodes it): 1 = a file decodeBMP

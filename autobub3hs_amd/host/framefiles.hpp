@@ -1,6 +1,6 @@
 // framefiles.hpp -- frames read as FILES for the GPU decoders (abub_png_decode_dev, abub_abf_decode_dev,
 // abub_bmp_decode_dev), shared by the batched detect path (runbatch.cpp), device training (devtrain.cpp) and the device
-// routes of repack, unpack and verify.  A host thread reads each file; a packed frame ("ABF1") whose header is valid for
+// routes of repack, unpack, verify and survey.  A host thread reads each file; a packed frame ("ABF1") whose header is valid for
 // W x H goes to the packed decoder as it is, a PNG has its chunks walked (pngWalk), a BMP its header (bmpWalk, with
 // ABUB_GPU_BMP=1; by default BMP files stay with the reading thread); a file none of them takes
 // (16-bit, colour or interlaced PNG -- ABUB_GPU_PNG_TYPES=1 and ABUB_GPU_PNG_ADAM7=1 take those too --, compressed BMP, another size)

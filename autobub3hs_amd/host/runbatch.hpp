@@ -7,6 +7,7 @@
 #define ABUB3HS_RUNBATCH_HPP
 
 #include <cstddef>
+#include <cstdint>
 #include <string>
 #include <vector>
 
@@ -197,6 +198,73 @@ int VerifyRun(Parser *src, Parser *other, const std::string &srcRunFile, const s
 // anything else, when there is no such device: there is no silent fall-back to the host route.
 int VerifyRunDevice(Parser *src, Parser *other, const std::string &srcRunFile, const std::string &otherRunFile, int numCams,
                     int nthreads, int device, VerifyStats *stats, std::vector<VerifyFinding> *findings, bool otherIsArchive = false);
+
+// The record of one frame (abub_stat_result without its status; include/abub_hip.h): flags bit 0 says that nOut / sumOut
+// are valid, bit 1 that nMoved / sumMoved are
+struct FrameStats {
+    uint32_t min = 0, max = 0, nZero = 0, nSat = 0, nOut = 0, nMoved = 0, flags = 0;
+    uint64_t sum = 0, sumsq = 0, sumOut = 0, sumMoved = 0;
+};
+// The definition of abub_frame_stats_dev: over the n pixels p of `cur` the range, sum, sum of squares, pixels == 0 and
+// == 255; with mu != NULL (sigma6 = min(6 sigma, 255) beside it) count and sum of sat(|p - mu| - sigma6); with mu and ref
+// count and sum of sat(|p - ref| - sigma6).  Plain byte loops, the one copy: both survey routes and the tests use it.
+FrameStats frameStatsHost(const unsigned char *cur, const unsigned char *ref, const unsigned char *mu, const unsigned char *sigma6,
+                          size_t n);
+
+// One row of a survey: a frame the run lists, or one it should list (missing)
+struct SurveyRow {
+    enum State { Ok = 0, Undecodable = 1, Missing = 2, OtherSize = 3 };
+    size_t ev = 0;           // index into the run's sorted event list
+    std::string event, name;
+    int cam = 0, frame = 0;  // frame: its place in its (event, camera) stack, missing frames counted
+    int state = Ok, w = 0, h = 0; // w, h: of Ok and OtherSize rows
+    FrameStats s;            // Ok: all of it, as far as its flags say; OtherSize: the raw columns
+    bool onKernel = false;
+    const char *stateName() const; // "ok", "undecodable", "missing", "other_size"
+};
+// What the report says of one camera's model
+struct SurveyModel {
+    bool trained = false;
+    int trainingSetSize = 0, sigmaMax = 0;
+    long long pixels = 0, sigmaZero = 0, sigma6Sat = 0; // pixels with sigma == 0; with 6 sigma >= 255
+    double muMean = 0;
+};
+struct SurveyStats {
+    int events = 0;
+    long long frames = 0; // rows: ok + undecodable + missing + otherSize
+    long long ok = 0, undecodable = 0, missing = 0, otherSize = 0;
+    // Of `frames`: framesKernel got their record from abub_frame_stats_dev, framesHostRoute from a host thread (or have
+    // none).  Of the device route (device -1: it was not taken): the frames each decoder lane decoded, those a host thread
+    // decoded for the slab, reference frames read again because their batch was over, archive entries inflated on the GPU
+    long long framesKernel = 0, framesHostRoute = 0;
+    long long gpuPngDecoded = 0, gpuUnpacked = 0, gpuBmpDecoded = 0, hostDecoded = 0, reread = 0, gpuUnzipped = 0;
+    int device = -1, W = 0, H = 0, batches = 0, modelCams = 0;
+    double read_s = 0, decode_s = 0, stats_s = 0, total_s = 0;
+};
+// The report's text ("Surveying a run"): "# abub3hs survey 1", one `model` line per camera, the table's
+// header and one tab-separated row per frame, the `run` line.  Both routes write it through this one function.
+std::string SurveyReport(const std::vector<SurveyModel> &models, const std::vector<SurveyRow> &rows);
+// abub3hs --survey FILE: every frame that `parser` lists for cameras 0 .. numCams-1 measured, no analysis: one row per
+// frame in event, camera and frame order, cv::imdecode and frameStatsHost on `nthreads` threads.  A frame number (read
+// from the name through imageFormat) that some stack of the run has and a stack with frames lacks is a `missing` row of
+// that stack.  Frame i of a stack is measured against frame max(i - 2, 0) of it (the trigger search's pairing) and against
+// the model of its camera: trainers[cam] where it is there, trained (StatusCode 0) and of the run's size (that of the first
+// frame that decodes); without it the model columns are invalid, and the moved columns also where the reference frame is
+// not ok.  The report goes to reportPath (empty: it is not written).  No GPU.  Returns 0, or 1 if any frame is not ok;
+// throws where the report cannot be written.
+int SurveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCams, const std::string &imageFormat,
+              const std::string &reportPath, int nthreads, SurveyStats *stats, std::vector<SurveyRow> *rows,
+              std::vector<SurveyModel> *models = nullptr);
+// abub3hs --survey FILE --survey-gpu: the same rows and the same report, byte for byte.  The frames are read through the
+// FileBatch protocol (framefiles.hpp) in batches of at most 4 frames per CU (ABUB_SURVEY_BATCH=n: of n), decoded into the
+// batch's slab, and measured by one abub_frame_stats_dev launch per batch.  A batch that begins inside a stack reads again
+// the at most two frames of the batch before that its first jobs refer to (they take slots of their own: the number of
+// batches is ceil(rows / batch size) exactly).  A frame that is not in place in the slab (no decoder reads it, another
+// size) gets its row from the host route's per-frame function.  A run whose width the decoders do not take, or without a
+// frame that decodes, goes the host route whole.  Throws, before anything else, when there is no such device.
+int SurveyRunDevice(Parser *parser, const std::vector<Trainer *> &trainers, int numCams, const std::string &imageFormat,
+                    const std::string &reportPath, int nthreads, int device, SurveyStats *stats, std::vector<SurveyRow> *rows,
+                    std::vector<SurveyModel> *models = nullptr);
 
 // A run listed and trained, ready for detect; rc = -5 (the run cannot be read) or -7 (a camera did not train)
 struct PreparedRun {

@@ -1,7 +1,8 @@
 // runframes.hpp -- a run as the list of its frames, for the tools that visit every frame without analysing any: repack
-// (repack.cpp) and verify (verify.cpp).  The list, the size the GPU decoders are set up for and the device check are one
-// copy here (the decoders' width gate and the batch size: framefiles.hpp), and so are the two helpers with which repack and
-// the peek images (peek.cpp) put files on disk.  Internal to the host library.
+// (repack.cpp), verify (verify.cpp) and survey (survey.cpp).  The list, the size the GPU decoders are set up for, the read
+// of a whole file and the device check are one copy here (the decoders' width gate and the batch size: framefiles.hpp),
+// and so are the two helpers with which repack and the peek images (peek.cpp) put files on disk.  Internal to the host
+// library.
 #ifndef ABUB3HS_RUNFRAMES_HPP
 #define ABUB3HS_RUNFRAMES_HPP
 
@@ -74,6 +75,23 @@ inline void appendEventFrames(Parser &parser, const std::string &ev, size_t e, i
         parser.ParseAndSortFramesInFolder(ev, c, names);
         for (std::string &n : names)
             tasks.push_back(FrameTask{e, std::move(n)});
+    }
+}
+
+// A file through its parser; one that cannot be read counts as empty
+inline void readWhole(Parser &p, const std::string &ev, const std::string &name, std::vector<unsigned char> &file)
+{
+    file.clear();
+    long long size = -1;
+    try {
+        size = p.GetImageFileSize(ev, name);
+        if (size <= 0 || size >= ((long long)1 << 30))
+            return;
+        file.resize((size_t)size);
+        if (p.ReadImageFile(ev, name, file.data(), file.size()) != size)
+            file.clear();
+    } catch (...) {
+        file.clear();
     }
 }
 

@@ -129,23 +129,6 @@ Verdict verifyBytes(const unsigned char *s, size_t sn, const unsigned char *o, s
     return v;
 }
 
-// a file through its parser; one that cannot be read counts as empty
-void readWhole(Parser &p, const std::string &ev, const std::string &name, std::vector<unsigned char> &file)
-{
-    file.clear();
-    long long size = -1;
-    try {
-        size = p.GetImageFileSize(ev, name);
-        if (size <= 0 || size >= ((long long)1 << 30))
-            return;
-        file.resize((size_t)size);
-        if (p.ReadImageFile(ev, name, file.data(), file.size()) != size)
-            file.clear();
-    } catch (...) {
-        file.clear();
-    }
-}
-
 // Each thread's clones of the two parsers
 struct Clones {
     std::unique_ptr<Parser> src, other;

@@ -769,6 +769,40 @@ typedef struct abub_cmp_result {
 int abub_frames_compare_dev(const uint8_t *a, size_t a_bytes, const uint8_t *b, size_t b_bytes, const abub_cmp_pair *pairs,
                             int npairs, size_t frame_bytes, abub_cmp_result *results, void *stream);
 
+/* ---- per-frame statistics of resident frames (abub_stats.hip) -------------------------------------------------------
+ * What a survey of a run (abub3hs --survey; record, pairing and report: DESIGN section 3, "Surveying a run") wants to know
+ * of every frame without analysing any, for a batch of resident frames: results[j] holds, over the frame_bytes pixels p at
+ * frames + jobs[j].cur, the grey-level range, sum and sum of squares and the counts of black (0) and saturated (255)
+ * pixels; with m and s the bytes of `mu` and `sigma6` at jobs[j].model (sigma6 = min(6 sigma, 255), abub_sigma6_dev; a
+ * sigma that truncates to 0, reference Trainer.cpp:191-195, gives s = 0) the count and sum of sat(|p - m| - s), the
+ * post-trigger image before its box filter (reference L3Localizer.cpp:779-787); and with r the bytes at frames +
+ * jobs[j].ref the count and sum of sat(|p - r| - s), pos + neg of ProcessFrame before the blur (reference
+ * AnalyzerUnit.cpp:341-351).  Every value is an exact integer: two launches on `stream` (the records' initial state, then
+ * jobs x 16 KiB tiles, each block summing its tile on chip and issuing one atomic of each kind: u32 add / min / max and
+ * u64 add, all of which commute), no host synchronisation, no allocation. */
+typedef struct abub_stat_job { uint64_t cur, ref, model; } abub_stat_job;
+   /* byte offsets: cur/ref into `frames`, model into `mu` and `sigma6`; no alignment rule;
+      ref == UINT64_MAX: no reference frame; model == UINT64_MAX or mu == NULL: no model */
+typedef struct abub_stat_result {   /* 64 bytes */
+    uint32_t status;                /* 0, ABUB_STAT_E_RANGE */
+    uint32_t min, max, n_zero, n_sat;          /* pixels == 0, == 255 */
+    uint32_t n_out, n_moved, flags;            /* flags: bit0 model columns valid, bit1 ref columns valid */
+    uint64_t sum, sumsq, sum_out, sum_moved;
+} abub_stat_result;
+#define ABUB_STAT_E_RANGE 1 /* a stream the job names runs past its buffer: nothing of the job is read; every other field 0 */
+#define ABUB_STAT_F_MODEL 1u /* n_out / sum_out are valid: the job names a model */
+#define ABUB_STAT_F_REF 2u   /* n_moved / sum_moved are valid: the job names a model and a reference frame */
+/* Every pointer is a device pointer; jobs and results are 8-byte aligned; frame_bytes in [1, 2^32 - 2].  mu == NULL: no
+ * job has a model (sigma6 is then not looked at); else sigma6 must not be NULL.  A column whose inputs are absent is 0 and
+ * its flag bit is clear; a reference frame without a model is checked for its range and not read.  results[njobs] is
+ * written in full by every call with njobs > 0, whatever it held before.  Streams whose addresses are congruent mod 16
+ * are read 16 bytes at a time, mod 4 four at a time, else byte by byte: as exact, and slower.  Null pointers, njobs < 0,
+ * frame_bytes out of range or a misaligned jobs / results: ABUB_E_INVALID before anything touches the device.
+ * njobs == 0: ABUB_OK, nothing is touched. */
+int abub_frame_stats_dev(const uint8_t *frames, size_t frames_bytes, const uint8_t *mu, const uint8_t *sigma6,
+                         size_t model_bytes, const abub_stat_job *jobs, int njobs, size_t frame_bytes,
+                         abub_stat_result *results, void *stream);
+
 /* ---- the two DebugPeek planes of a batch of resident frames (abub_peek.hip) ------------------------------------------
  * What L3Localizer::CalculateInitialBubbleParams builds on the analyzer's thread for its debug write-out (reference
  * L3Localizer.cpp:252-257, 397, 448; DESIGN section 3, "The peek planes"), for a batch of items.  Per item two W x H u8
