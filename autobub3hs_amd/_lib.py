@@ -49,6 +49,10 @@ class PeekItem(C.Structure):
                 ("thr", C.c_int32), ("rect_begin", C.c_int32), ("rect_count", C.c_int32), ("reserved", C.c_int32)]
 
 
+class ActJob(C.Structure):  # abub_act_job
+    _fields_ = [("cur", C.c_uint64), ("ref", C.c_uint64)]
+
+
 def build(force=False):
     """Compile the HIP library for gfx950 (cross-compiles without a GPU)."""
     srcs = [os.path.join(HERE, "csrc", f) for f in os.listdir(os.path.join(HERE, "csrc"))
@@ -100,6 +104,7 @@ SIGNATURES = {
     "abub_zip_pack_dev": (_i, [_vp, _sz, _vp, _i, _vp, _sz, _vp, _sz, _vp, _vp, _vp]),
     "abub_frames_compare_dev": (_i, [_vp, _sz, _vp, _sz, _vp, _i, _sz, _vp, _vp]),
     "abub_frame_stats_dev": (_i, [_vp, _sz, _vp, _vp, _sz, _vp, _i, _sz, _vp, _vp]),
+    "abub_pixel_activity_dev": (_i, [_vp, _sz, _vp, _vp, _vp, _i, _sz, _vp, _sz, _vp, _vp]),
     "abub_peek_planes_dev": (_i, [_vp, _sz, _vp, _sz, _vp, _i, _vp, _i, _i, _i, _vp, _sz, _vp, _vp]),
     "abub_diff_hist_chained_deferred_dev": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, C.c_uint32, _vp, _vp, _vp]),
     "abub_diff_hist_pieces_dev": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),

@@ -24,6 +24,7 @@
 // job every load lies in [0, frame_bytes) of its stream: unit i at head + i * U with i < nunits = (frame_bytes - head) / U,
 // head and tail bytes by their own index.  Only results[j] is written, j < njobs.
 #include "abub_dev.hpp"
+#include <algorithm>
 #include <stddef.h>
 
 namespace {
@@ -344,5 +345,300 @@ extern "C" int abub_frame_stats_dev(const uint8_t *frames, size_t frames_bytes, 
     k_stat<<<grid, ST_THREADS, 0, st>>>(frames, (uint64_t)frames_bytes, mu, sigma6, (uint64_t)model_bytes, jobs, njobs,
                                         (uint32_t)frame_bytes, results);
     HIPCHK(hipGetLastError());
+    return ABUB_OK;
+}
+
+// ---- per-pixel activity planes: abub_pixel_activity_dev ("Surveying a run per pixel") ------------------
+// The sum across the frames of a camera that the per-frame records form across the pixels of a frame (host/survey.cpp
+// activityAddHost, the definition): six u32 planes, += per job: p == 0, p == 255, and with a model count and sum of
+// sat(|p - m| - s), with a reference frame too count and sum of sat(|p - r| - s).
+//
+// A thread owns AC_PX = 8 consecutive pixels for the whole call and walks the jobs in list order with its 6 x 8 sums in
+// registers; mu and sigma6 of its pixels are loaded once.  Every plane word has one owner, so nothing is atomic and the
+// planes are read and written once per call.  The jobs go in groups of AC_UNR: the loads of the next group (one 8-byte load
+// of the frame and one of the reference frame per job) are issued before the arithmetic of the current one.  Inside a group
+// the clamped differences stay u16 pairs (widen / v_pk_sub_i16 / v_pk_max_i16 / v_pk_sub_u16 clamp, as k_stat forms them;
+// a lane <= AC_UNR * 255) and are taken apart into the u32 sums once per group.  Planes 0 and 1 count the bytes that are NOT
+// 0 / 255 (min(x, 1) of the widened byte and of its complement) and are turned round at the end with the number of jobs read.
+//
+// Pixels: with `head` = the bytes in front of the first multiple of 8 of the anchor stream (mu, without a model the frames'
+// base), thread t of k_act<8> owns [head + 8 t, head + 8 t + 8), t < nunits = (frame_bytes - head) / 8; the head bytes and
+// the tail bytes behind the last unit (at most 7 each) are single pixels of k_act<1>, one thread each.  A unit of a stream
+// is read by one 8-byte load where its address is a multiple of 8, by two 4-byte loads where of 4, else byte by byte; the
+// address's low bits are those of (base + offset + head), the same in every thread, so that choice is a scalar branch.
+//
+// Bounds.  A job is read only if cur, and ref where it is not UINT64_MAX, lie inside `frames` (st_in_range: no overflow);
+// otherwise it adds nothing, and thread 0 of block 0 stores ABUB_ACT_E_RANGE to *status (the entry clears it on the stream
+// first).  That is decided from the job record alone, before any add, alike in every thread.  Every load of a stream is at
+// pixel index < frame_bytes; the only stores are planes[k * plane_stride + i], k < 6, i < frame_bytes, and *status.
+namespace {
+
+#define AC_THREADS 256
+#define AC_PX 8  /* pixels a thread of the wide kernel owns: one 8-byte load per stream and job */
+#define AC_UNR 4 /* jobs whose loads a thread has in flight */
+
+template <int PX>
+struct ActUnit; // PX consecutive bytes of a stream, as PX / 4 dwords (PX = 1: the byte in the low bits of one)
+template <>
+struct ActUnit<8> {
+    static constexpr int NPK = 4; // u16 pairs
+    uint32_t w[2];
+    static __device__ __forceinline__ ActUnit load(const uint8_t *p, uint32_t low)
+    {
+        ActUnit u;
+        if ((low & 7u) == 0u) {
+            const uint2 v = *reinterpret_cast<const uint2 *>(p);
+            u.w[0] = v.x, u.w[1] = v.y;
+        } else if ((low & 3u) == 0u) {
+            u.w[0] = reinterpret_cast<const uint32_t *>(p)[0];
+            u.w[1] = reinterpret_cast<const uint32_t *>(p)[1];
+        } else {
+            u.w[0] = (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24;
+            u.w[1] = (uint32_t)p[4] | (uint32_t)p[5] << 8 | (uint32_t)p[6] << 16 | (uint32_t)p[7] << 24;
+        }
+        return u;
+    }
+    // the u16 pairs of the unit: pair k holds pixels 2 k (low lane) and 2 k + 1
+    __device__ __forceinline__ uint32_t pair(int k) const { return k & 1 ? widen_hi(w[k >> 1]) : widen_lo(w[k >> 1]); }
+    __device__ __forceinline__ ActUnit inverted() const
+    {
+        ActUnit u;
+        u.w[0] = ~w[0], u.w[1] = ~w[1];
+        return u;
+    }
+};
+template <>
+struct ActUnit<1> {
+    static constexpr int NPK = 1;
+    uint32_t w[1];
+    static __device__ __forceinline__ ActUnit load(const uint8_t *p, uint32_t)
+    {
+        ActUnit u;
+        u.w[0] = *p;
+        return u;
+    }
+    __device__ __forceinline__ uint32_t pair(int) const { return w[0]; } // (the high lane stays 0 throughout)
+    __device__ __forceinline__ ActUnit inverted() const
+    {
+        ActUnit u;
+        u.w[0] = w[0] ^ 0xffu;
+        return u;
+    }
+};
+
+// what a group of AC_UNR jobs is: per job whether it is read and whether it has a reference frame, and their offsets
+struct ActGroup {
+    uint64_t cur[AC_UNR], ref[AC_UNR];
+    bool ok[AC_UNR], has_ref[AC_UNR];
+    bool bad; // a job of the group names a stream that runs past `frames`
+};
+template <bool MODEL>
+__device__ __forceinline__ ActGroup act_group(const abub_act_job *__restrict__ jobs, int njobs, int j0, uint64_t frames_bytes,
+                                              uint64_t frame_bytes)
+{
+    ActGroup g;
+    g.bad = false;
+#pragma unroll
+    for (int u = 0; u < AC_UNR; ++u) {
+        g.ok[u] = g.has_ref[u] = false;
+        g.cur[u] = g.ref[u] = 0;
+        if (j0 + u >= njobs)
+            continue;
+        const abub_act_job jb = jobs[j0 + u];
+        const bool ref = jb.ref != ST_NONE;
+        if (!st_in_range(jb.cur, frames_bytes, frame_bytes) || (ref && !st_in_range(jb.ref, frames_bytes, frame_bytes))) {
+            g.bad = true;
+            continue;
+        }
+        g.ok[u] = true;
+        g.has_ref[u] = MODEL && ref;
+        g.cur[u] = jb.cur;
+        g.ref[u] = g.has_ref[u] ? jb.ref : jb.cur;
+    }
+    return g;
+}
+
+// `at`: this thread's first pixel, whose low three bits are those of `head` in every thread of the wide kernel.  The loads
+// of every job of the group that is read
+template <int PX>
+__device__ __forceinline__ void act_loads(const ActGroup &g, const uint8_t *frames, uint64_t at, uint32_t head, ActUnit<PX> *c,
+                                          ActUnit<PX> *r)
+{
+    const uint32_t base = (uint32_t)(uintptr_t)frames + head;
+#pragma unroll
+    for (int u = 0; u < AC_UNR; ++u)
+        if (g.ok[u])
+            c[u] = ActUnit<PX>::load(frames + g.cur[u] + at, base + (uint32_t)g.cur[u]);
+#pragma unroll
+    for (int u = 0; u < AC_UNR; ++u)
+        if (g.has_ref[u])
+            r[u] = ActUnit<PX>::load(frames + g.ref[u] + at, base + (uint32_t)g.ref[u]);
+}
+
+// Grid: x over the threads' units.  PX = 8: unit t is the pixels [head + 8 t, + 8), t < count.  PX = 1: unit t is the
+// pixel t for t < head, else body_end + (t - head): the head and tail bytes, count of them in all
+template <int PX, bool MODEL>
+__global__ __launch_bounds__(AC_THREADS) void k_act(const uint8_t *frames, uint64_t frames_bytes, const uint8_t *mu,
+                                                    const uint8_t *sigma6, const abub_act_job *__restrict__ jobs, int njobs,
+                                                    uint64_t frame_bytes, uint32_t head, uint64_t body_end, uint64_t count,
+                                                    uint32_t *planes, uint64_t plane_stride, uint32_t *status)
+{
+    typedef ActUnit<PX> Unit;
+    constexpr int NPK = Unit::NPK;
+    const uint64_t t = (uint64_t)blockIdx.x * AC_THREADS + threadIdx.x;
+    const bool mine = t < count;
+    // (a thread past the end works on unit 0's addresses and stores nothing: every load stays in bounds)
+    const uint64_t unit = mine ? t : 0;
+    const uint64_t at = PX == 1 ? (unit < head ? unit : body_end + (unit - head)) : (uint64_t)head + unit * PX;
+
+    uint32_t mp[NPK], sp[NPK]; // mu and sigma6 of the unit as u16 pairs
+    if (MODEL) {
+        const Unit m = Unit::load(mu + at, (uint32_t)(uintptr_t)mu + head);
+        const Unit s = Unit::load(sigma6 + at, (uint32_t)(uintptr_t)sigma6 + head);
+#pragma unroll
+        for (int k = 0; k < NPK; ++k)
+            mp[k] = m.pair(k), sp[k] = s.pair(k);
+    }
+    // sums per pixel: [plane][pixel]; planes 0 and 1 hold the jobs in which the pixel was NOT 0 / 255 until the end
+    uint32_t acc[6][2 * NPK];
+#pragma unroll
+    for (int k = 0; k < 6; ++k)
+#pragma unroll
+        for (int i = 0; i < 2 * NPK; ++i)
+            acc[k][i] = 0;
+    uint32_t n_read = 0, bad = 0; // jobs read; a job was refused (the same in every thread)
+
+    Unit c[AC_UNR], r[AC_UNR], cn[AC_UNR], rn[AC_UNR];
+#pragma unroll
+    for (int u = 0; u < AC_UNR; ++u)
+        c[u] = r[u] = cn[u] = rn[u] = Unit();
+    ActGroup g = act_group<MODEL>(jobs, njobs, 0, frames_bytes, frame_bytes);
+    act_loads<PX>(g, frames, at, head, c, r);
+    for (int64_t j0 = 0; j0 < njobs; j0 += AC_UNR) {
+        ActGroup gn = g;
+        if (j0 + AC_UNR < njobs) { // the next group's loads, before this group's arithmetic
+            gn = act_group<MODEL>(jobs, njobs, (int)(j0 + AC_UNR), frames_bytes, frame_bytes);
+            act_loads<PX>(gn, frames, at, head, cn, rn);
+        }
+        bad |= g.bad;
+        uint32_t pk[6][NPK]; // the group's sums as u16 pairs (a lane <= AC_UNR * 255)
+#pragma unroll
+        for (int k = 0; k < 6; ++k)
+#pragma unroll
+            for (int i = 0; i < NPK; ++i)
+                pk[k][i] = 0;
+#pragma unroll
+        for (int u = 0; u < AC_UNR; ++u) {
+            if (!g.ok[u])
+                continue;
+            ++n_read;
+            const Unit inv = c[u].inverted();
+#pragma unroll
+            for (int i = 0; i < NPK; ++i) {
+                const uint32_t p = c[u].pair(i);
+                pk[0][i] += st_pk_min1(p);
+                pk[1][i] += st_pk_min1(inv.pair(i));
+                if (MODEL) {
+                    const uint32_t o = pk_subsat(pk_absdiff(p, mp[i]), sp[i]);
+                    pk[2][i] += st_pk_min1(o);
+                    pk[3][i] += o;
+                }
+            }
+            if (MODEL && g.has_ref[u]) {
+#pragma unroll
+                for (int i = 0; i < NPK; ++i) {
+                    const uint32_t o = pk_subsat(pk_absdiff(c[u].pair(i), r[u].pair(i)), sp[i]);
+                    pk[4][i] += st_pk_min1(o);
+                    pk[5][i] += o;
+                }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 6; ++k)
+#pragma unroll
+            for (int i = 0; i < NPK; ++i) {
+                acc[k][2 * i] += pk[k][i] & 0xffffu;
+                acc[k][2 * i + 1] += pk[k][i] >> 16;
+            }
+        g = gn;
+#pragma unroll
+        for (int u = 0; u < AC_UNR; ++u)
+            c[u] = cn[u], r[u] = rn[u];
+    }
+    if (bad && t == 0)
+        *status = (uint32_t)ABUB_ACT_E_RANGE;
+    if (!mine || n_read == 0)
+        return;
+#pragma unroll
+    for (int k = 0; k < (MODEL ? 6 : 2); ++k) {
+        uint32_t *row = planes + (uint64_t)k * plane_stride + at;
+        if constexpr (PX == 8) {
+            if ((head & 3u) == 0u) { // (planes is 16-byte aligned, plane_stride a multiple of 4: so is this address)
+                st_u32x4 *q = reinterpret_cast<st_u32x4 *>(row);
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    st_u32x4 v = q[h];
+                    const uint32_t a0 = acc[k][4 * h], a1 = acc[k][4 * h + 1], a2 = acc[k][4 * h + 2], a3 = acc[k][4 * h + 3];
+                    v.x += k < 2 ? n_read - a0 : a0;
+                    v.y += k < 2 ? n_read - a1 : a1;
+                    v.z += k < 2 ? n_read - a2 : a2;
+                    v.w += k < 2 ? n_read - a3 : a3;
+                    q[h] = v;
+                }
+                continue;
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < PX; ++i)
+            row[i] += k < 2 ? n_read - acc[k][i] : acc[k][i];
+    }
+}
+
+template <int PX>
+int act_launch(bool model, unsigned blocks, hipStream_t st, const uint8_t *frames, uint64_t frames_bytes, const uint8_t *mu,
+               const uint8_t *sigma6, const abub_act_job *jobs, int njobs, uint64_t frame_bytes, uint32_t head, uint64_t body_end,
+               uint64_t count, uint32_t *planes, uint64_t plane_stride, uint32_t *status)
+{
+    if (model)
+        k_act<PX, true><<<blocks, AC_THREADS, 0, st>>>(frames, frames_bytes, mu, sigma6, jobs, njobs, frame_bytes, head, body_end, count,
+                                                       planes, plane_stride, status);
+    else
+        k_act<PX, false><<<blocks, AC_THREADS, 0, st>>>(frames, frames_bytes, mu, sigma6, jobs, njobs, frame_bytes, head, body_end, count,
+                                                        planes, plane_stride, status);
+    HIPCHK(hipGetLastError());
+    return ABUB_OK;
+}
+
+} // namespace
+
+extern "C" int abub_pixel_activity_dev(const uint8_t *frames, size_t frames_bytes, const uint8_t *mu, const uint8_t *sigma6,
+                                       const abub_act_job *jobs, int njobs, size_t frame_bytes, uint32_t *planes,
+                                       size_t plane_stride, uint32_t *status, void *stream)
+{
+    if (!frames || !jobs || !planes || !status || njobs < 0 || (mu == nullptr) != (sigma6 == nullptr))
+        return set_err(ABUB_E_INVALID, "abub_pixel_activity_dev: null pointer, negative count, or one of mu and sigma6 without the other");
+    if (frame_bytes < 1 || frame_bytes > (size_t)0xfffffffeu)
+        return set_err(ABUB_E_INVALID, "abub_pixel_activity_dev: frame_bytes must be in [1, 2^32 - 2]");
+    if (plane_stride < frame_bytes || (plane_stride & 3) || ((uintptr_t)planes & 15))
+        return set_err(ABUB_E_INVALID,
+                       "abub_pixel_activity_dev: plane_stride must be a multiple of 4 and >= frame_bytes, planes 16-byte aligned");
+    if (((uintptr_t)jobs & 7) || ((uintptr_t)status & 3))
+        return set_err(ABUB_E_INVALID, "abub_pixel_activity_dev: jobs must be 8-byte aligned, status 4-byte aligned");
+    if (njobs == 0)
+        return ABUB_OK;
+    hipStream_t st = (hipStream_t)stream;
+    HIPCHK(hipMemsetAsync(status, 0, sizeof(uint32_t), st));
+    const uintptr_t anchor = (uintptr_t)(mu ? mu : frames);
+    const uint32_t head = (uint32_t)std::min<uint64_t>((8u - (anchor & 7u)) & 7u, frame_bytes);
+    const uint64_t nunits = (frame_bytes - head) / AC_PX, body_end = head + nunits * AC_PX, edge = head + (frame_bytes - body_end);
+    if (nunits) {
+        const int rc = act_launch<AC_PX>(mu != nullptr, (unsigned)((nunits + AC_THREADS - 1) / AC_THREADS), st, frames, frames_bytes, mu,
+                                         sigma6, jobs, njobs, frame_bytes, head, body_end, nunits, planes, plane_stride, status);
+        if (rc != ABUB_OK)
+            return rc;
+    }
+    if (edge) // (at most 14 single pixels)
+        return act_launch<1>(mu != nullptr, 1u, st, frames, frames_bytes, mu, sigma6, jobs, njobs, frame_bytes, head, body_end, edge,
+                             planes, plane_stride, status);
     return ABUB_OK;
 }

@@ -682,6 +682,33 @@ def frame_stats(frames, jobs, frame_bytes, mu=None, sigma6=None, frames_bytes=No
                           axis=1)
 
 
+ACT_PLANES = ("n_zero", "n_sat", "n_out", "sum_out", "n_moved", "sum_moved")
+ACT_E_RANGE = 1
+ACT_PIXELS_PER_THREAD = 8  # AC_PX of csrc/abub_stats.hip: the run of pixels a thread owns
+
+
+def pixel_activity(frames, jobs, frame_bytes, planes, mu=None, sigma6=None, plane_stride=None, frames_bytes=None):
+    """abub_pixel_activity_dev, one camera's jobs: frames u8 (any shape; frames of frame_bytes bytes anywhere in it), jobs:
+    [n, 2] byte offsets (cur, ref) into `frames` (STAT_NONE or a negative number: no reference frame), mu / sigma6: the
+    camera's model (u8 tensors or views, any alignment) or both None; planes: uint32 device tensor, 16-byte aligned, of at
+    least 5 * plane_stride + frame_bytes words (plane_stride: default its size / 6), ADDED to in place.
+    -> the status word: 0, or ACT_E_RANGE if a job named a stream that runs past frames_bytes (default: the tensor's
+    size) and was left out."""
+    import numpy as np
+    _need_cuda(frames, mu, sigma6, planes)
+    offs = np.array([[STAT_NONE if int(v) < 0 else int(v) for v in row] for row in jobs], dtype=np.uint64).reshape(-1, 2)
+    n = len(offs)
+    dev = frames.device
+    d_jobs = torch.from_numpy(np.concatenate([offs, np.zeros((1, 2), np.uint64)]).view(np.int64)).to(dev)
+    status = torch.full((1,), 0x5A5A5A5A, dtype=torch.int32, device=dev)
+    if plane_stride is None:
+        plane_stride = planes.numel() // 6
+    _lib.check(_lib.lib().abub_pixel_activity_dev(_ptr(frames), frames.numel() if frames_bytes is None else int(frames_bytes),
+                                                  _ptr(mu), _ptr(sigma6), _ptr(d_jobs), n, int(frame_bytes), _ptr(planes),
+                                                  int(plane_stride), _ptr(status), _stream()), "abub_pixel_activity_dev")
+    return int(status.item()) if n else 0
+
+
 def peek_items(rows):
     """rows of (diff, frame, thr_out, pres_out, thr, rect_begin, rect_count) -> the abub_peek_item records as a uint8 host
     array (48 bytes each)."""

@@ -65,6 +65,9 @@ SIGNATURES = {
     "abh_run_survey": (_i, [_vp, _s, _i, _i, _dp, C.c_char_p, _i]),
     "abh_run_survey_dev": (_i, [_vp, _s, _i, _i, _i, _dp, C.c_char_p, _i]),
     "abh_run_survey_report": (_s, [_vp]),
+    "abh_run_survey_planes": (_i, [_vp, _s, _s, _i, _i, _dp, _dp, C.c_char_p, _i]),
+    "abh_run_survey_planes_dev": (_i, [_vp, _s, _s, _i, _i, _i, _dp, _dp, C.c_char_p, _i]),
+    "abh_activity_add_host": (None, [C.POINTER(C.c_uint32), _u8p, _u8p, _u8p, _u8p, C.c_uint64]),
     "abh_frame_stats_host": (None, [_u8p, _u8p, _u8p, _u8p, C.c_uint64, _u64p]),
     "abh_zip_write": (_i, [_s, _i, _u8p, _u32p, _u8p, _u64p]),
     "abh_zip_error": (_s, []),
@@ -440,7 +443,7 @@ class Run:
                     "gpu_png_decoded", "gpu_unpacked", "gpu_bmp_decoded", "host_decoded", "reread", "frames_gpu_unzipped", "device",
                     "W", "H", "batches", "model_cams")
 
-    def survey(self, path=None, nthreads=16, ncams=4, device=None):
+    def survey(self, path=None, nthreads=16, ncams=4, device=None, planes=None):
         """abub3hs --survey of this run (opened from a directory or an archive): the run is listed and trained as for
         detect, then every frame of cameras 0 .. ncams-1 is measured without analysing any; the report (DESIGN section 3,
         "Surveying a run") is written to `path` (None: it is not written).  device=None: host threads (cv::imdecode and
@@ -448,13 +451,24 @@ class Run:
         measured (abub_frame_stats_dev) on that GPU; raises when there is no such device.
         -> (stats dict: rc (0, or 1 if a frame is not ok), the counters of the states, frames_kernel / frames_host_route,
         the decoder lanes' counts, batches, device (-1: its route was not taken), W, H, model_cams and the legs read_s,
-        decode_s, stats_s, seconds; the report's text)."""
+        decode_s, stats_s, seconds; the report's text).
+        planes (--survey-planes): the directory (the CLI's DIR/<run_ID>) that gets the per-pixel activity planes (DESIGN
+        section 3, "Surveying a run per pixel"): cam<c>_activity.npy, cam<c>_moved.png, activity.txt, the same bytes on
+        both routes; the stats then also have plane_rows_kernel / plane_rows_host and the legs activity_s, planes_copy_s,
+        planes_write_s.  The report does not change."""
         L = lib()
         st = (C.c_double * 24)()
+        pst = (C.c_double * 5)()
         cap = 1 << 16
         buf = C.create_string_buffer(cap)
         to = None if path is None else str(path).encode()
-        if device is None:
+        if planes is not None:
+            pd = str(planes).encode()
+            if device is None:
+                rc = L.abh_run_survey_planes(self._h, to, pd, ncams, nthreads, st, pst, buf, cap)
+            else:
+                rc = L.abh_run_survey_planes_dev(self._h, to, pd, ncams, nthreads, int(device), st, pst, buf, cap)
+        elif device is None:
             rc = L.abh_run_survey(self._h, to, ncams, nthreads, st, buf, cap)
         else:
             rc = L.abh_run_survey_dev(self._h, to, ncams, nthreads, int(device), st, buf, cap)
@@ -463,6 +477,9 @@ class Run:
         text = buf.value if st[23] < cap else L.abh_run_survey_report(self._h)
         res = {"rc": rc, **{k: int(v) for k, v in zip(self._SURVEY_KEYS, list(st))}}
         res.update(read_s=st[19], decode_s=st[20], stats_s=st[21], seconds=st[22])
+        if planes is not None:
+            res.update(plane_rows_kernel=int(pst[0]), plane_rows_host=int(pst[1]), activity_s=pst[2], planes_copy_s=pst[3],
+                       planes_write_s=pst[4])
         return res, text.decode()
 
     def analyze(self, event, cam, maskdir=""):
@@ -486,6 +503,18 @@ def frame_stats_host(cur, ref=None, mu=None, sigma6=None):
     out = np.zeros(11, np.uint64)
     lib().abh_frame_stats_host(*[None if a is None else a.ctypes.data_as(_u8p) for a in arrs], n, out.ctypes.data_as(_u64p))
     return dict(zip(FRAME_STATS_KEYS, (int(v) for v in out)))
+
+
+def activity_add_host(planes, cur, ref=None, mu=None, sigma6=None):
+    """abub::activityAddHost (host/survey.cpp), the definition of abub_pixel_activity_dev: one frame `cur` (u8, n pixels)
+    ADDED in place to planes (uint32, contiguous, 6 * n words: n_zero, n_sat, n_out, sum_out, n_moved, sum_moved); ref / mu /
+    sigma6 of cur's size or None (sigma6 goes with mu)."""
+    arrs = [None if a is None else np.ascontiguousarray(a, dtype=np.uint8).reshape(-1) for a in (cur, ref, mu, sigma6)]
+    n = arrs[0].size
+    assert all(a is None or a.size == n for a in arrs) and (arrs[2] is None) == (arrs[3] is None)
+    assert planes.dtype == np.uint32 and planes.flags["C_CONTIGUOUS"] and planes.size == 6 * n
+    lib().abh_activity_add_host(planes.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                *[None if a is None else a.ctypes.data_as(_u8p) for a in arrs], n)
 
 
 def zip_write(path, entries):

@@ -33,7 +33,7 @@ static std::string usage()
            "       abub3hs [-z] [-D data_series] -d data_dir -r run_ID --repack out_data_dir [--repack-gpu] [--archive]\n"
            "       abub3hs [-z] [-D data_series] -d data_dir -r run_ID --unpack out_data_dir [--unpack-gpu] [--archive]\n"
            "       abub3hs [-z] [-D data_series] -d data_dir -r run_ID --verify-repack other_data_dir [--verify-gpu] [--archive]\n"
-           "       abub3hs [-z] [-D data_series] -d data_dir -r run_ID --survey FILE [--survey-gpu]\n"
+           "       abub3hs [-z] [-D data_series] -d data_dir -r run_ID --survey FILE [--survey-gpu] [--survey-planes DIR]\n"
            "Run the AutoBub3hs bubble finding algorithm on a PICO run (MI355X hot path)\n\n"
            "Required arguments:\n"
            "  -d, --data_dir = Dir\t\tpath to the directory in which the run folder/file is stored\n"
@@ -94,6 +94,12 @@ static std::string usage()
            "\t\t\t\t--repack, --unpack, --verify-repack, --peek, --runs / --run-list, --gpu-shard\n"
            "  --survey-gpu\t\t\twith --survey: decode the frames and measure them on GPU 0 (the same report, byte for byte); an\n"
            "\t\t\t\terror when there is no HIP device\n"
+           "  --survey-planes = Dir\t\twith --survey: also sum the frames per pixel and camera and write Dir/<run_ID>/: per camera\n"
+           "\t\t\t\tcam<c>_activity.npy, six u32 planes [6, H, W] (frames in which the pixel was 0, was 255, count and\n"
+           "\t\t\t\tsum of what the model leaves above 6 sigma, count and sum of what the frame two before leaves),\n"
+           "\t\t\t\tcam<c>_moved.png (the share of frames in which the pixel moved, 255 = all) and activity.txt (the\n"
+           "\t\t\t\tdenominators, dead / stuck / ever-moved pixel counts and the 16 hottest pixels); the same bytes\n"
+           "\t\t\t\twith --survey-gpu; the report does not change\n"
            "Environment: ABUB_TRAIN_ON_GPU=0 trains the runs of a campaign with the host Trainer\n"
            "             ABUB_REPACK_BATCH=n (a test knob) lowers the frames per batch of --repack-gpu and --unpack-gpu to n; the files\n"
            "             are the same\n"
@@ -267,6 +273,8 @@ int main(int argc, char **argv)
     bool archive = false; // --archive: the copy of --repack / --unpack / --verify-repack is Dir/<run_ID>.zip
     std::string surveyFile; // --survey FILE: the run measured frame by frame (abub::SurveyRun), nothing else
     bool haveSurvey = false, surveyGpu = false;
+    std::string surveyPlanesDir; // --survey-planes DIR: the survey's per-pixel planes go to DIR/<run_ID>/
+    bool haveSurveyPlanes = false;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i], v;
         auto value = [&](std::string &dst) {
@@ -364,6 +372,9 @@ int main(int argc, char **argv)
             haveSurvey = true;
         } else if (a == "--survey-gpu") {
             surveyGpu = true;
+        } else if (a == "--survey-planes" || a.rfind("--survey-planes=", 0) == 0) {
+            value(surveyPlanesDir);
+            haveSurveyPlanes = true;
         } else if (a == "--per-event") {
             perEvent = true;
         } else if (a == "--peek" || a.rfind("--peek=", 0) == 0) {
@@ -395,6 +406,10 @@ int main(int argc, char **argv)
         std::cerr << "--survey-gpu is valid only together with --survey" << std::endl;
         return -1;
     }
+    if (haveSurveyPlanes && !haveSurvey) {
+        std::cerr << "--survey-planes is valid only together with --survey" << std::endl;
+        return -1;
+    }
     if (haveSurvey) {
         const char *bad = haveUnpack ? "--unpack" : haveRepack ? "--repack" : haveVerify ? "--verify-repack" : mergeN > 0 ? "--merge"
                           : debug_mode ? "--debug" : perEvent ? "--per-event" : event_user >= 0 ? "-e/--event" : havePeek ? "--peek"
@@ -405,6 +420,10 @@ int main(int argc, char **argv)
         }
         if (dataLoc.empty() || run_number.empty() || surveyFile.empty()) {
             std::cerr << "--survey needs --data_dir, --run_id and the file to write the report to" << std::endl;
+            return -1;
+        }
+        if (haveSurveyPlanes && surveyPlanesDir.empty()) {
+            std::cerr << "--survey-planes needs the directory to write to" << std::endl;
             return -1;
         }
     }
@@ -576,6 +595,11 @@ int main(int argc, char **argv)
         abub::BatchedRunOptions po;
         po.trainOnGpu = 0; // (a single run trains through the host Trainer, as the reference does)
         abub::SurveyStats ss;
+        abub::SurveyPlanes planes;
+        if (haveSurveyPlanes) {
+            planes.dir = surveyPlanesDir + "/" + run_number;
+            planes.srcRunDir = zipped ? std::string() : sp.eventDir;
+        }
         int rc = 1;
         try {
             abub::PreparedRun prep = abub::PrepareRun(sp, po, 0, nullptr, false);
@@ -584,9 +608,9 @@ int main(int argc, char **argv)
             if (prep.rc)
                 printf("survey: a camera did not train: the report has no model columns for it\n");
             rc = surveyGpu ? abub::SurveyRunDevice(prep.parser.get(), prep.trainers, sp.numCams, sp.imageFormat, surveyFile, poolThreads(), 0,
-                                                   &ss, nullptr)
+                                                   &ss, nullptr, nullptr, planes)
                            : abub::SurveyRun(prep.parser.get(), prep.trainers, sp.numCams, sp.imageFormat, surveyFile, poolThreads(), &ss,
-                                             nullptr);
+                                             nullptr, nullptr, planes);
         } catch (std::exception &e) {
             std::cerr << "survey failed: " << e.what() << std::endl;
             return -6;
@@ -610,6 +634,10 @@ int main(int argc, char **argv)
                        ss.framesKernel, ss.device, ss.gpuPngDecoded, ss.gpuUnpacked, ss.gpuBmpDecoded, ss.hostDecoded, ss.reread,
                        ss.gpuUnzipped, ss.framesHostRoute, ss.batches, ss.read_s, ss.decode_s, ss.stats_s);
         }
+        if (haveSurveyPlanes)
+            printf("survey-planes: %s: %lld rows added on the GPU, %lld on the host; activity launches %.3f s, copy back %.3f s, files "
+                   "%.3f s\n",
+                   planes.dir.c_str(), ss.planeRowsKernel, ss.planeRowsHost, ss.activity_s, ss.planes_copy_s, ss.planes_write_s);
         return rc;
     }
     if (haveList) {

@@ -398,8 +398,11 @@ const char *abh_run_verify_report(void *src)
 // characters; the whole text stays with the run for abh_run_survey_report.  Returns SurveyRun's code (0, or 1 if a frame is
 // not ok), -5 if the run cannot be read, -1 on errors.  abh_run_survey_dev: abub::SurveyRunDevice on `device`, no fall-back
 // when there is no such device.
+// abh_run_survey_planes[_dev]: the same with the per-pixel planes written to planes_dir (abub::SurveyPlanes::dir, the CLI's
+// DIR/<run_ID>; NULL or empty: none) and plane_stats (may be NULL, 5 values): [rows added to the planes by
+// abub_pixel_activity_dev, rows added by a host thread, seconds of the activity launches, of the copy back, of the files].
 static int runSurvey(void *r, const char *path, int ncams, int nthreads, int device, bool onDevice, double *stats, char *report,
-                     int report_cap)
+                     int report_cap, const char *planes_dir = nullptr, double *plane_stats = nullptr)
 {
     Run *run = (Run *)r;
     try {
@@ -422,10 +425,17 @@ static int runSurvey(void *r, const char *path, int ncams, int nthreads, int dev
         std::vector<abub::SurveyRow> rows;
         std::vector<abub::SurveyModel> models;
         const std::string to = path ? path : "";
+        abub::SurveyPlanes planes;
+        planes.dir = planes_dir ? planes_dir : "";
+        planes.srcRunDir = run->kind == 0 ? run->runFolder : std::string();
         const int rc = onDevice ? abub::SurveyRunDevice(pr.parser.get(), pr.trainers, ncams, sp.imageFormat, to, std::max(1, nthreads),
-                                                        device, &st, &rows, &models)
+                                                        device, &st, &rows, &models, planes)
                                 : abub::SurveyRun(pr.parser.get(), pr.trainers, ncams, sp.imageFormat, to, std::max(1, nthreads), &st,
-                                                  &rows, &models);
+                                                  &rows, &models, planes);
+        if (plane_stats) {
+            const double v[5] = {(double)st.planeRowsKernel, (double)st.planeRowsHost, st.activity_s, st.planes_copy_s, st.planes_write_s};
+            std::memcpy(plane_stats, v, sizeof v);
+        }
         std::string &text = run->frames_of_last_query;
         text = abub::SurveyReport(models, rows);
         if (report && report_cap > 0) {
@@ -458,6 +468,16 @@ int abh_run_survey_dev(void *r, const char *path, int ncams, int nthreads, int d
 {
     return runSurvey(r, path, ncams, nthreads, device, true, stats, report, report_cap);
 }
+int abh_run_survey_planes(void *r, const char *path, const char *planes_dir, int ncams, int nthreads, double *stats, double *plane_stats,
+                          char *report, int report_cap)
+{
+    return runSurvey(r, path, ncams, nthreads, -1, false, stats, report, report_cap, planes_dir, plane_stats);
+}
+int abh_run_survey_planes_dev(void *r, const char *path, const char *planes_dir, int ncams, int nthreads, int device, double *stats,
+                              double *plane_stats, char *report, int report_cap)
+{
+    return runSurvey(r, path, ncams, nthreads, device, true, stats, report, report_cap, planes_dir, plane_stats);
+}
 // the whole report of the last abh_run_survey[_dev] on the run (valid until the next query on it)
 const char *abh_run_survey_report(void *r)
 {
@@ -470,6 +490,12 @@ void abh_frame_stats_host(const uint8_t *cur, const uint8_t *ref, const uint8_t 
     const abub::FrameStats s = abub::frameStatsHost(cur, ref, mu, sigma6, (size_t)n);
     const uint64_t v[11] = {s.min, s.max, s.nZero, s.nSat, s.nOut, s.nMoved, s.flags, s.sum, s.sumsq, s.sumOut, s.sumMoved};
     std::memcpy(out, v, sizeof v);
+}
+
+// abub::activityAddHost on raw buffers: one frame of n bytes ADDED to planes[6 * n] (ref, mu may be NULL; sigma6 goes with mu)
+void abh_activity_add_host(uint32_t *planes, const uint8_t *cur, const uint8_t *ref, const uint8_t *mu, const uint8_t *sigma6, uint64_t n)
+{
+    abub::activityAddHost(planes, cur, ref, mu, sigma6, (size_t)n);
 }
 
 // bmpWalk (host/bmpwalk.hpp: what the reading threads learn about a BMP before the GPU decodes it): 1 = a file decodeBMP

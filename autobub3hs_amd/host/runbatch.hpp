@@ -210,6 +210,13 @@ struct FrameStats {
 // count and sum of sat(|p - ref| - sigma6).  Plain byte loops, the one copy: both survey routes and the tests use it.
 FrameStats frameStatsHost(const unsigned char *cur, const unsigned char *ref, const unsigned char *mu, const unsigned char *sigma6,
                           size_t n);
+// The definition of abub_pixel_activity_dev, the per-pixel terms of frameStatsHost summed over frames instead: one frame
+// ADDED to the six u32 planes planes[k * n + i] (0 n_zero, 1 n_sat, 2 n_out, 3 sum_out, 4 n_moved, 5 sum_moved; DESIGN
+// section 3, "Surveying a run per pixel").  mu == NULL: planes 2 to 5 are not touched; ref == NULL: planes 4 and 5 are not.
+// Plain byte loops; the adds are relaxed atomics, so the rows of a camera may be added from many threads.  The one copy:
+// the host route, the device route's host share and the tests use it.
+void activityAddHost(uint32_t *planes, const unsigned char *cur, const unsigned char *ref, const unsigned char *mu,
+                     const unsigned char *sigma6, size_t n);
 
 // One row of a survey: a frame the run lists, or one it should list (missing)
 struct SurveyRow {
@@ -240,6 +247,18 @@ struct SurveyStats {
     long long gpuPngDecoded = 0, gpuUnpacked = 0, gpuBmpDecoded = 0, hostDecoded = 0, reread = 0, gpuUnzipped = 0;
     int device = -1, W = 0, H = 0, batches = 0, modelCams = 0;
     double read_s = 0, decode_s = 0, stats_s = 0, total_s = 0;
+    // With a planes directory: the rows abub_pixel_activity_dev added to the planes and those a host thread added (on the
+    // device route: the rows whose file no GPU decoder reads, decoded by a reading thread, and the rows not in place); the
+    // seconds of the activity launches, of the planes' copy back and of writing the files
+    long long planeRowsKernel = 0, planeRowsHost = 0;
+    double activity_s = 0, planes_copy_s = 0, planes_write_s = 0;
+};
+// Where a survey writes its per-pixel activity planes (abub3hs --survey-planes; DESIGN section 3, "Surveying a run per
+// pixel"): the directory `dir` (the CLI's DIR/<run_ID>; empty: no planes) gets cam<c>_activity.npy (u32 [6, H, W]) for
+// every camera with a listed row, cam<c>_moved.png for those with a model, and activity.txt.  srcRunDir (empty: an
+// archive) is the directory the run is read from; it is refused as `dir`.
+struct SurveyPlanes {
+    std::string dir, srcRunDir;
 };
 // The report's text ("Surveying a run"): "# abub3hs survey 1", one `model` line per camera, the table's
 // header and one tab-separated row per frame, the `run` line.  Both routes write it through this one function.
@@ -252,9 +271,10 @@ std::string SurveyReport(const std::vector<SurveyModel> &models, const std::vect
 // frame that decodes); without it the model columns are invalid, and the moved columns also where the reference frame is
 // not ok.  The report goes to reportPath (empty: it is not written).  No GPU.  Returns 0, or 1 if any frame is not ok;
 // throws where the report cannot be written.
+// With planes.dir the rows are also summed per pixel and camera and the planes' files are written (both routes: the same bytes).
 int SurveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCams, const std::string &imageFormat,
               const std::string &reportPath, int nthreads, SurveyStats *stats, std::vector<SurveyRow> *rows,
-              std::vector<SurveyModel> *models = nullptr);
+              std::vector<SurveyModel> *models = nullptr, const SurveyPlanes &planes = SurveyPlanes());
 // abub3hs --survey FILE --survey-gpu: the same rows and the same report, byte for byte.  The frames are read through the
 // FileBatch protocol (framefiles.hpp) in batches of at most 4 frames per CU (ABUB_SURVEY_BATCH=n: of n), decoded into the
 // batch's slab, and measured by one abub_frame_stats_dev launch per batch.  A batch that begins inside a stack reads again
@@ -264,7 +284,7 @@ int SurveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCam
 // frame that decodes, goes the host route whole.  Throws, before anything else, when there is no such device.
 int SurveyRunDevice(Parser *parser, const std::vector<Trainer *> &trainers, int numCams, const std::string &imageFormat,
                     const std::string &reportPath, int nthreads, int device, SurveyStats *stats, std::vector<SurveyRow> *rows,
-                    std::vector<SurveyModel> *models = nullptr);
+                    std::vector<SurveyModel> *models = nullptr, const SurveyPlanes &planes = SurveyPlanes());
 
 // A run listed and trained, ready for detect; rc = -5 (the run cannot be read) or -7 (a camera did not train)
 struct PreparedRun {

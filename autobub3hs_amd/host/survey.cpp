@@ -5,14 +5,20 @@
 // abub_frame_stats_dev launch per batch; what is not in place in the slab gets its row from the host route's per-frame
 // function, of which there is one copy.  Both routes fill one row per frame and share everything behind that: the list of
 // the rows, the models, the counters, the report's text, the exit status.
+// With a planes directory (--survey-planes; DESIGN section 3, "Surveying a run per pixel") the ok rows are also summed per
+// pixel and camera: activityAddHost is the definition, a host thread adds its row into the camera's one set of planes with
+// relaxed atomic adds, the device route adds the rows in place in the slab with abub_pixel_activity_dev and keeps its planes
+// on the device until the end; the result is their sum, and one writer puts the files on disk for both routes.
 #include <algorithm>
 #include <cinttypes>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <atomic>
 #include <map>
 #include <memory>
+#include <mutex>
 #include <set>
 #include <stdexcept>
 
@@ -21,6 +27,8 @@
 #include "framefiles.hpp"
 #include "runbatch.hpp"
 #include "runframes.hpp"
+
+#include <sys/stat.h>
 
 namespace abub {
 
@@ -55,6 +63,31 @@ FrameStats frameStatsHost(const unsigned char *cur, const unsigned char *ref, co
         }
     }
     return s;
+}
+
+void activityAddHost(uint32_t *planes, const unsigned char *cur, const unsigned char *ref, const unsigned char *mu,
+                     const unsigned char *sigma6, size_t n)
+{
+    const auto add = [&](int k, size_t i, uint32_t v) {
+        if (v)
+            __atomic_fetch_add(planes + (size_t)k * n + i, v, __ATOMIC_RELAXED);
+    };
+    for (size_t i = 0; i < n; ++i) {
+        const int p = cur[i];
+        add(0, i, p == 0);
+        add(1, i, p == 255);
+        if (!mu)
+            continue;
+        const int lim = sigma6[i];
+        const int out = std::max(std::abs(p - (int)mu[i]) - lim, 0);
+        add(2, i, out > 0);
+        add(3, i, (uint32_t)out);
+        if (!ref)
+            continue;
+        const int moved = std::max(std::abs(p - (int)ref[i]) - lim, 0);
+        add(4, i, moved > 0);
+        add(5, i, (uint32_t)moved);
+    }
 }
 
 const char *SurveyRow::stateName() const
@@ -132,8 +165,25 @@ std::string SurveyReport(const std::vector<SurveyModel> &models, const std::vect
 
 namespace {
 
+// The per-pixel planes of a survey on the host: per camera six u32 planes of P words, there only once a host thread has a
+// row of the camera to add (the device route keeps its own on the device and adds these at the end)
+struct HostPlanes {
+    size_t P = 0;
+    std::vector<std::vector<uint32_t>> cam;
+    std::unique_ptr<std::once_flag[]> once;
+    std::atomic<long long> rows{0};
+    HostPlanes(size_t cams, size_t pixels) : P(pixels), cam(cams), once(new std::once_flag[cams]) {}
+    void add(int c, const uint8_t *cur, const uint8_t *ref, const uint8_t *mu, const uint8_t *sigma6)
+    {
+        std::call_once(once[c], [&] { cam[c].assign(6 * P, 0u); });
+        activityAddHost(cam[c].data(), cur, ref, mu, sigma6, P);
+        ++rows;
+    }
+};
+
 // The part of a survey that is not its frames' pixels
 struct Plan {
+    HostPlanes *planes = nullptr;   // with a planes directory: where surveyFrame adds its ok rows
     std::vector<std::string> events;
     std::vector<SurveyRow> rows;    // in event, camera and frame order
     std::vector<size_t> ref;        // ref[i]: the row frame i is measured against (frame max(i - 2, 0) of its stack)
@@ -286,6 +336,8 @@ void surveyFrame(Parser &p, const Plan &pl, size_t i, SurveyRow &row)
     }
     const uint8_t *r = ri == i ? cur.data : ref.empty() ? nullptr : ref.data;
     row.s = frameStatsHost(cur.data, r, mu, mu ? pl.sigma6[row.cam].data() : nullptr, n);
+    if (pl.planes)
+        pl.planes->add(row.cam, cur.data, r, mu, mu ? pl.sigma6[row.cam].data() : nullptr);
 }
 
 void hostFrames(Parser *parser, Plan &pl, int nthreads)
@@ -313,8 +365,12 @@ FrameStats fromRecord(const abub_stat_result &r)
 // The device route: the rows in batches.  Per batch: the reference frames of its first rows that lie in front of it take
 // the first slots (they are read again), then the rows; the pool reads the files into a pinned buffer; upload; the decoders
 // into the slab, slot s at s * align16(W * H); one abub_frame_stats_dev launch over the rows that are in place, and the
-// records back in one copy.  A row that is not in place goes to surveyFrame.
-void deviceFrames(Parser *parser, Plan &pl, int nthreads, int device, SurveyStats &st)
+// records back in one copy.  A row that is not in place goes to surveyFrame.  With pl.planes the rows in place are also
+// added to the per-pixel planes on the device, [camera][6][stride] u32 cleared once: behind the batch's statistics launch one
+// abub_pixel_activity_dev call per camera that has rows in place, its jobs behind the records in the same meta buffer; they
+// come back in one copy at the end, into devPlanes.  A row in place whose file no GPU decoder reads was decoded by a reading
+// thread; its pixels are on the host, and it is added to the host planes there, not by the kernel.
+void deviceFrames(Parser *parser, Plan &pl, int nthreads, int device, SurveyStats &st, std::vector<uint32_t> &devPlanes)
 {
     HIPOK(hipSetDevice(device));
     size_t perBatch = framesPerBatch(device);
@@ -337,6 +393,12 @@ void deviceFrames(Parser *parser, Plan &pl, int nthreads, int device, SurveyStat
             HIPOK(hipMemcpyAsync(d_model.get() + c * stride, pl.mu[c], P, hipMemcpyHostToDevice, cs));
             HIPOK(hipMemcpyAsync(d_model.get() + (C + c) * stride, pl.sigma6[c].data(), P, hipMemcpyHostToDevice, cs));
         }
+    const bool wantPlanes = pl.planes != nullptr;
+    DeviceBuffer d_planes;
+    if (wantPlanes) {
+        d_planes.allocate(C * 6 * stride * sizeof(uint32_t));
+        HIPOK(hipMemsetAsync(d_planes.get(), 0, C * 6 * stride * sizeof(uint32_t), cs));
+    }
     HIPOK(hipStreamSynchronize(cs));
 
     for (size_t i0 = 0; i0 < pl.rows.size(); i0 += perBatch) {
@@ -387,7 +449,9 @@ void deviceFrames(Parser *parser, Plan &pl, int nthreads, int device, SurveyStat
                 slot.push_back(s);
         const size_t nj = slot.size();
         if (nj) {
-            const size_t metaBytes = nj * (sizeof(abub_stat_job) + sizeof(abub_stat_result));
+            // [stat jobs][records]; with planes behind them [activity jobs, camera by camera][one status word per camera]
+            const size_t statBytes = nj * (sizeof(abub_stat_job) + sizeof(abub_stat_result));
+            const size_t metaBytes = statBytes + (wantPlanes ? nj * sizeof(abub_act_job) + C * sizeof(uint32_t) : 0);
             h_meta.grow(metaBytes);
             d_meta.grow(metaBytes);
             abub_stat_job *jobs = (abub_stat_job *)h_meta.get();
@@ -413,6 +477,76 @@ void deviceFrames(Parser *parser, Plan &pl, int nthreads, int device, SurveyStat
                   "abub_frame_stats_dev");
             HIPOK(hipMemcpyAsync(h_meta.get() + nj * sizeof(abub_stat_job), d_res, nj * sizeof(abub_stat_result), hipMemcpyDeviceToHost, cs));
             HIPOK(hipStreamSynchronize(cs));
+            if (wantPlanes) {
+                st.stats_s += (nowMs() - t0) * 1e-3;
+                t0 = nowMs();
+                // A frame that no GPU decoder reads was decoded by a reading thread, and its pixels are still on the host
+                // (B.fd.hostPix): its row is the device route's host share and is added there; every other row is a job
+                std::vector<int> hostOf(slots, -1);
+                for (size_t q = 0; q < B.fd.host.size(); ++q)
+                    if (B.fd.hostPix[q].size() == P)
+                        hostOf[(size_t)B.fd.host[q].s] = (int)q;
+                std::vector<size_t> onHost;
+                abub_act_job *aj = (abub_act_job *)(h_meta.get() + statBytes);
+                std::vector<size_t> first(C + 1, 0), at(C);
+                for (size_t g = 0; g < nj; ++g)
+                    if (hostOf[slot[g]] >= 0)
+                        onHost.push_back(g);
+                    else
+                        ++first[(size_t)pl.rows[rowOf(slot[g])].cam + 1];
+                for (size_t c = 0; c < C; ++c)
+                    at[c] = first[c + 1] += first[c];
+                for (size_t g = nj; g-- > 0;) // (backwards: a camera's jobs keep the order of the rows)
+                    if (hostOf[slot[g]] < 0)
+                        aj[--at[(size_t)pl.rows[rowOf(slot[g])].cam]] = abub_act_job{jobs[g].cur, jobs[g].ref};
+                HIPOK(hipMemcpyAsync(d_meta.get() + statBytes, aj, nj * sizeof(abub_act_job), hipMemcpyHostToDevice, cs));
+                const size_t statusAt = statBytes + nj * sizeof(abub_act_job);
+                for (size_t c = 0; c < C; ++c) {
+                    ((uint32_t *)(h_meta.get() + statusAt))[c] = 0;
+                    if (first[c + 1] == first[c])
+                        continue;
+                    check(abub_pixel_activity_dev(B.slab.get(), slots * stride, pl.mu[c] ? d_model.get() + c * stride : nullptr,
+                                                  pl.mu[c] ? d_model.get() + (C + c) * stride : nullptr,
+                                                  (const abub_act_job *)(d_meta.get() + statBytes) + first[c], (int)(first[c + 1] - first[c]),
+                                                  P, (uint32_t *)d_planes.get() + c * 6 * stride, stride,
+                                                  (uint32_t *)(d_meta.get() + statusAt) + c, cs),
+                          "abub_pixel_activity_dev");
+                    HIPOK(hipMemcpyAsync(h_meta.get() + statusAt + c * sizeof(uint32_t), d_meta.get() + statusAt + c * sizeof(uint32_t),
+                                         sizeof(uint32_t), hipMemcpyDeviceToHost, cs));
+                }
+                HIPOK(hipStreamSynchronize(cs));
+                for (size_t c = 0; c < C; ++c)
+                    if (((const uint32_t *)(h_meta.get() + statusAt))[c] != 0)
+                        throw std::runtime_error("survey: abub_pixel_activity_dev refused a frame of its own slab");
+                st.planeRowsKernel += (long long)first[C];
+                // the host share: the reference frame from the host where it was decoded there too, else back from the slab
+                std::atomic<int> copyFailed{0};
+                forEachTask(parser, nthreads, onHost.size(), [&](Parser &, size_t q) {
+                    static thread_local std::vector<uint8_t> back;
+                    const size_t g = onHost[q];
+                    const int cam = pl.rows[rowOf(slot[g])].cam;
+                    const uint8_t *mu = pl.mu[cam], *ref = nullptr;
+                    if (mu && jobs[g].ref != UINT64_MAX) {
+                        const size_t rs = (size_t)(jobs[g].ref / stride);
+                        if (hostOf[rs] >= 0)
+                            ref = B.fd.hostPix[(size_t)hostOf[rs]].data();
+                        else {
+                            back.resize(P);
+                            if (hipSetDevice(device) != hipSuccess ||
+                                hipMemcpy(back.data(), B.slab.get() + jobs[g].ref, P, hipMemcpyDeviceToHost) != hipSuccess) {
+                                copyFailed = 1;
+                                return;
+                            }
+                            ref = back.data();
+                        }
+                    }
+                    pl.planes->add(cam, B.fd.hostPix[(size_t)hostOf[slot[g]]].data(), ref, mu, mu ? pl.sigma6[cam].data() : nullptr);
+                });
+                if (copyFailed)
+                    throw std::runtime_error("survey: a reference frame could not be copied back from the slab");
+                st.activity_s += (nowMs() - t0) * 1e-3;
+                t0 = nowMs();
+            }
             for (size_t g = 0; g < nj; ++g) {
                 if (res[g].status != 0)
                     throw std::runtime_error("survey: abub_frame_stats_dev refused a frame of its own slab");
@@ -436,17 +570,143 @@ void deviceFrames(Parser *parser, Plan &pl, int nthreads, int device, SurveyStat
         st.read_s += (nowMs() - t0) * 1e-3;
         ++st.batches;
     }
+    if (wantPlanes) {
+        const double t0 = nowMs();
+        devPlanes.resize(C * 6 * stride);
+        HIPOK(hipMemcpyAsync(devPlanes.data(), d_planes.get(), devPlanes.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, cs));
+        HIPOK(hipStreamSynchronize(cs));
+        st.planes_copy_s += (nowMs() - t0) * 1e-3;
+    }
+}
+
+// The files of the per-pixel planes, one writer for both routes ("Surveying a run per pixel"): per camera
+// with a listed row the sum of the host's planes and the device's (dev: [camera][6][stride], or empty) as
+// cam<c>_activity.npy, with a model cam<c>_moved.png, and the cameras' lines of activity.txt
+void writePlanes(const std::string &dir, const Plan &pl, const HostPlanes &hp, const std::vector<uint32_t> &dev)
+{
+    std::string failed;
+    if (!makeDirs(dir, &failed))
+        throw std::runtime_error("survey: cannot make the directory " + failed);
+    const size_t P = (size_t)pl.W * pl.H, stride = (P + 15) & ~(size_t)15;
+    std::string text = "# abub3hs activity 1\n";
+    char buf[512];
+    for (size_t c = 0; c < pl.mu.size(); ++c) {
+        bool listed = false;
+        unsigned long long frames = 0, framesModel = 0, framesMoved = 0;
+        for (size_t i = 0; i < pl.rows.size(); ++i) {
+            const SurveyRow &r = pl.rows[i];
+            if ((size_t)r.cam != c)
+                continue;
+            listed = listed || pl.listed[i];
+            if (r.state != SurveyRow::Ok)
+                continue;
+            ++frames;
+            framesModel += (r.s.flags & ABUB_STAT_F_MODEL) != 0;
+            framesMoved += (r.s.flags & ABUB_STAT_F_REF) != 0;
+        }
+        if (!listed)
+            continue;
+        std::vector<uint32_t> v(6 * P, 0u);
+        if (!hp.cam[c].empty())
+            v = hp.cam[c];
+        if (!dev.empty())
+            for (size_t k = 0; k < 6; ++k)
+                for (size_t i = 0; i < P; ++i)
+                    v[k * P + i] += dev[(c * 6 + k) * stride + i];
+        const uint32_t *nZero = v.data(), *nSat = nZero + P, *nOut = nSat + P, *sumOut = nOut + P, *nMoved = sumOut + P,
+                       *sumMoved = nMoved + P;
+
+        // ---- cam<c>_activity.npy: NumPy format 1.0, the data at a multiple of 64 --------------------------------------------
+        snprintf(buf, sizeof buf, "{'descr': '<u4', 'fortran_order': False, 'shape': (6, %d, %d), }", pl.H, pl.W);
+        std::string head = buf;
+        head.resize((10 + head.size() + 1 + 63) / 64 * 64 - 10 - 1, ' ');
+        head += '\n';
+        std::string file("\x93NUMPY\x01\x00", 8);
+        file += (char)(head.size() & 0xff);
+        file += (char)(head.size() >> 8);
+        file += head;
+        file.append((const char *)v.data(), v.size() * sizeof(uint32_t));
+        const std::string stem = dir + "/cam" + std::to_string(c);
+        if (!writeFile(stem + "_activity.npy", (const unsigned char *)file.data(), file.size()))
+            throw std::runtime_error("survey: cannot write " + stem + "_activity.npy");
+
+        // ---- cam<c>_moved.png: the share of the counted rows in which the pixel moved, 255 = all of them --------------------
+        if (pl.mu[c]) {
+            cv::Mat img(pl.H, pl.W, CV_8U);
+            for (size_t i = 0; i < P; ++i)
+                img.data[i] = (uint8_t)(framesMoved ? (255ull * nMoved[i] + framesMoved - 1) / framesMoved : 0);
+            if (!cv::imwrite(stem + "_moved.png", img))
+                throw std::runtime_error("survey: cannot write " + stem + "_moved.png");
+        }
+
+        // ---- activity.txt -----------------------------------------------------------------------------------------------------
+        snprintf(buf, sizeof buf, "cam %zu w %d h %d frames %llu frames_model %llu frames_moved %llu\n", c, pl.W, pl.H, frames, framesModel,
+                 framesMoved);
+        text += buf;
+        unsigned long long dead = 0, stuck = 0, everOut = 0, everMoved = 0, moved10 = 0, moved50 = 0;
+        std::vector<uint32_t> hot;
+        for (size_t i = 0; i < P; ++i) {
+            dead += frames && nZero[i] == frames;
+            stuck += frames && nSat[i] == frames;
+            everOut += nOut[i] > 0;
+            everMoved += nMoved[i] > 0;
+            moved10 += framesMoved && 10ull * nMoved[i] >= framesMoved;
+            moved50 += framesMoved && 2ull * nMoved[i] >= framesMoved;
+            if (nMoved[i] > 0)
+                hot.push_back((uint32_t)i);
+        }
+        snprintf(buf, sizeof buf, "cam %zu dead %llu stuck_sat %llu ever_out %llu ever_moved %llu moved_10pct %llu moved_50pct %llu\n", c,
+                 dead, stuck, everOut, everMoved, moved10, moved50);
+        text += buf;
+        const size_t nhot = std::min<size_t>(hot.size(), 16);
+        std::partial_sort(hot.begin(), hot.begin() + nhot, hot.end(), [&](uint32_t a, uint32_t b) {
+            if (nMoved[a] != nMoved[b])
+                return nMoved[a] > nMoved[b];
+            if (sumMoved[a] != sumMoved[b])
+                return sumMoved[a] > sumMoved[b];
+            return a < b;
+        });
+        for (size_t k = 0; k < nhot; ++k) {
+            const uint32_t i = hot[k];
+            snprintf(buf, sizeof buf, "hot %zu %zu %u %u %u %u %u %u %u %u\n", c, k + 1, i % (uint32_t)pl.W, i / (uint32_t)pl.W, nMoved[i],
+                     sumMoved[i], nOut[i], sumOut[i], pl.mu[c][i], pl.sigma6[c][i]);
+            text += buf;
+        }
+    }
+    if (!writeFile(dir + "/activity.txt", (const unsigned char *)text.data(), text.size()))
+        throw std::runtime_error("survey: cannot write " + dir + "/activity.txt");
+}
+
+bool sameDirectory(const std::string &path, const std::string &other)
+{
+    struct stat a, b;
+    return !path.empty() && !other.empty() && stat(path.c_str(), &a) == 0 && stat(other.c_str(), &b) == 0 && a.st_dev == b.st_dev &&
+           a.st_ino == b.st_ino;
 }
 
 int surveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCams, const std::string &format,
               const std::string &reportPath, int nthreads, int device, SurveyStats *stats, std::vector<SurveyRow> *rows,
-              std::vector<SurveyModel> *models)
+              std::vector<SurveyModel> *models, const SurveyPlanes &planes)
 {
     const double t0 = nowMs();
     SurveyStats st;
     if (device >= 0) // (before anything else)
         requireDevice(device, "survey", "; without --survey-gpu the run is surveyed on the host");
+    const std::string planesDir = trimSlashes(planes.dir);
+    // (the planes' files have names of their own, but a run directory is not the place for what was derived from it)
+    if (!planesDir.empty() && sameDirectory(trimSlashes(planes.srcRunDir), planesDir))
+        throw std::runtime_error("survey: " + planesDir + " is the run that is being read");
     Plan pl = planRun(parser, trainers, numCams, format);
+    std::unique_ptr<HostPlanes> hostPlanes;
+    std::vector<uint32_t> devPlanes;
+    if (!planesDir.empty()) {
+        std::vector<size_t> perCam((size_t)numCams, 0);
+        for (const SurveyRow &r : pl.rows)
+            if (++perCam[(size_t)r.cam] > 16777215) // (255 * 2^24 < 2^32: a u32 plane cannot overflow below that)
+                throw std::runtime_error("survey: camera " + std::to_string(r.cam) + " has more than 16777215 frames: its planes could overflow");
+        hostPlanes.reset(new HostPlanes((size_t)numCams, (size_t)pl.W * pl.H));
+        pl.planes = hostPlanes.get();
+    }
     st.events = (int)pl.events.size();
     st.W = pl.W;
     st.H = pl.H;
@@ -454,7 +714,7 @@ int surveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCam
         st.modelCams += m.trained;
     if (device >= 0 && pl.W > 0 && decodersTakeWidth(pl.W)) {
         st.device = device;
-        deviceFrames(parser, pl, nthreads, device, st);
+        deviceFrames(parser, pl, nthreads, device, st, devPlanes);
     } else
         hostFrames(parser, pl, nthreads);
     for (const SurveyRow &r : pl.rows) {
@@ -467,6 +727,12 @@ int surveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCam
         const std::string text = SurveyReport(pl.models, pl.rows);
         if (!writeFile(reportPath, (const unsigned char *)text.data(), text.size()))
             throw std::runtime_error("survey: cannot write " + reportPath);
+    }
+    if (hostPlanes) {
+        const double t1 = nowMs();
+        st.planeRowsHost = hostPlanes->rows;
+        writePlanes(planesDir, pl, *hostPlanes, devPlanes);
+        st.planes_write_s = (nowMs() - t1) * 1e-3;
     }
     st.total_s = (nowMs() - t0) * 1e-3;
     const int rc = st.ok == st.frames ? 0 : 1;
@@ -483,18 +749,18 @@ int surveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCam
 
 int SurveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCams, const std::string &imageFormat,
               const std::string &reportPath, int nthreads, SurveyStats *stats, std::vector<SurveyRow> *rows,
-              std::vector<SurveyModel> *models)
+              std::vector<SurveyModel> *models, const SurveyPlanes &planes)
 {
-    return surveyRun(parser, trainers, numCams, imageFormat, reportPath, nthreads, -1, stats, rows, models);
+    return surveyRun(parser, trainers, numCams, imageFormat, reportPath, nthreads, -1, stats, rows, models, planes);
 }
 
 int SurveyRunDevice(Parser *parser, const std::vector<Trainer *> &trainers, int numCams, const std::string &imageFormat,
                     const std::string &reportPath, int nthreads, int device, SurveyStats *stats, std::vector<SurveyRow> *rows,
-                    std::vector<SurveyModel> *models)
+                    std::vector<SurveyModel> *models, const SurveyPlanes &planes)
 {
     if (device < 0)
         throw std::runtime_error("survey: no such HIP device: " + std::to_string(device));
-    return surveyRun(parser, trainers, numCams, imageFormat, reportPath, nthreads, device, stats, rows, models);
+    return surveyRun(parser, trainers, numCams, imageFormat, reportPath, nthreads, device, stats, rows, models, planes);
 }
 
 } // namespace abub

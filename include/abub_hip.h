@@ -803,6 +803,32 @@ int abub_frame_stats_dev(const uint8_t *frames, size_t frames_bytes, const uint8
                          size_t model_bytes, const abub_stat_job *jobs, int njobs, size_t frame_bytes,
                          abub_stat_result *results, void *stream);
 
+/* ---- per-pixel activity planes of resident frames (abub_stats.hip) ---------------------------------------------------
+ * The per-pixel view of a survey (abub3hs --survey --survey-planes; DESIGN section 3, "Surveying a run per pixel"): the
+ * terms abub_frame_stats_dev sums over the pixels of a frame, summed over the frames of ONE camera instead.  With p the
+ * pixel of the frame at frames + jobs[j].cur, m and s the bytes of `mu` and `sigma6` at that pixel and r the pixel of the
+ * frame at frames + jobs[j].ref, every job ADDS to the six u32 planes at planes + k * plane_stride, k = 0 .. 5:
+ *   0 n_zero: p == 0        2 n_out:   sat(|p - m| - s) > 0      4 n_moved:   sat(|p - r| - s) > 0
+ *   1 n_sat:  p == 255      3 sum_out: sat(|p - m| - s)          5 sum_moved: sat(|p - r| - s)
+ * The call adds and never overwrites: the caller clears the planes once, and a run is a sequence of calls.  mu == NULL
+ * (then sigma6 == NULL too): planes 2 to 5 are not touched.  ref == UINT64_MAX: the job adds nothing to planes 4 and 5.
+ * A job whose cur, or whose ref where it is not UINT64_MAX, runs past frames_bytes adds nothing at all and makes *status
+ * ABUB_ACT_E_RANGE; the other jobs are added.  *status is cleared by the call, on `stream`.  A thread owns 8 consecutive
+ * pixels for the whole call, so every plane word has one owner and nothing is atomic: the planes are bit-identical
+ * whatever the order of the jobs and however they are split over calls.  A memset and at most two launches on `stream`,
+ * no host synchronisation, no allocation.  A caller adds at most 16,777,215 jobs into one set of planes (255 * 2^24 <
+ * 2^32).  Only planes[k * plane_stride + i], k < 6, i < frame_bytes, and *status are written. */
+typedef struct abub_act_job { uint64_t cur, ref; } abub_act_job;   /* byte offsets into frames; ref == UINT64_MAX: none */
+#define ABUB_ACT_E_RANGE 1
+/* Every pointer is a device pointer; mu and sigma6 are ONE camera's planes, or both NULL; jobs is 8-byte aligned, status
+ * 4-byte aligned, planes 16-byte aligned and plane_stride a multiple of 4 and >= frame_bytes; frame_bytes in
+ * [1, 2^32 - 2].  Streams whose addresses are multiples of 8 after the same head bytes are read 8 bytes at a time, of 4
+ * four at a time, else byte by byte: as exact, and slower.  Anything else: ABUB_E_INVALID before anything touches the
+ * device.  njobs == 0: ABUB_OK, nothing is touched. */
+int abub_pixel_activity_dev(const uint8_t *frames, size_t frames_bytes, const uint8_t *mu, const uint8_t *sigma6,
+                            const abub_act_job *jobs, int njobs, size_t frame_bytes, uint32_t *planes, size_t plane_stride,
+                            uint32_t *status, void *stream);
+
 /* ---- the two DebugPeek planes of a batch of resident frames (abub_peek.hip) ------------------------------------------
  * What L3Localizer::CalculateInitialBubbleParams builds on the analyzer's thread for its debug write-out (reference
  * L3Localizer.cpp:252-257, 397, 448; DESIGN section 3, "The peek planes"), for a batch of items.  Per item two W x H u8
