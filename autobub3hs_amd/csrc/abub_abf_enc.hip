@@ -43,7 +43,7 @@ __global__ __launch_bounds__(64 * ABFE_WAVES) void k_abf_enc_measure(const uint8
     const uint32_t f = blockIdx.x;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const uint64_t P = (uint64_t)W * (uint64_t)H, s = src[f];
-    if (!enc_src_ok(s, pixels_bytes, P))
+    if (!frame_in_range(s, pixels_bytes, P))
         return; // (nobody reads this frame's scratch)
     const uint8_t *img = pixels + s;
     const uint32_t nblk = ((uint32_t)W + 63u) >> 6;
@@ -72,7 +72,7 @@ __global__ __launch_bounds__(64 * ABFE_WAVES) void k_abf_enc_measure(const uint8
             if (lane < nb)
                 fw[(uint64_t)y * nblk + k0 + lane] = (uint8_t)mine;
         }
-        acc = enc_wave_sum(acc);
+        acc = wave_sum(acc);
         if (lane == 0)
             frows[y] = make_uint2(rsize, acc);
     }
@@ -85,7 +85,7 @@ __global__ __launch_bounds__(ENC_SCAN) void k_abf_enc_place_rows(uint64_t pixels
     __shared__ uint32_t sh[ENC_SCAN / 64];
     const uint32_t f = blockIdx.x;
     const uint64_t P = (uint64_t)W * (uint64_t)H;
-    if (!enc_src_ok(src[f], pixels_bytes, P)) { // (the same answer in every thread)
+    if (!frame_in_range(src[f], pixels_bytes, P)) { // (the same answer in every thread)
         if (threadIdx.x == 0)
             flen[f] = 0;
         return;

@@ -1,30 +1,17 @@
-// abub_enc.hpp -- what the two GPU encoders (abub_abf_enc.hip, abub_png_enc.hip) share: the source check, the sums and scans of
-// their place kernels, the load of a pixel's left neighbour, the kernel that places the files of a batch, and the argument
-// check of their entries.  Included by those two translation units only.
+// abub_enc.hpp -- what the two GPU encoders (abub_abf_enc.hip, abub_png_enc.hip) share: the scan of their place kernels, the load
+// of a pixel's left neighbour, the kernel that places the files of a batch, and the argument check of their entries.  The source
+// check (a frame of P bytes at s lies inside the pixels: frame_in_range, found alike by every kernel of an entry) and the wave
+// sum come from abub_frames.hpp.  Included by those two translation units only.
 #ifndef ABUB_ENC_HPP
 #define ABUB_ENC_HPP
 
-#include "abub_dev.hpp"
-#include <stddef.h>
+#include "abub_frames.hpp"
 
 namespace {
 
 #define ENC_SCAN 256 /* threads of the place kernels */
 
 inline size_t align16z(size_t v) { return (v + 15) & ~(size_t)15; }
-
-__device__ __forceinline__ uint32_t enc_wave_sum(uint32_t v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1)
-        v += __shfl_xor(v, o);
-    return v;
-}
-// a frame of P bytes at s lies inside the pixels (found alike by every kernel of an entry)
-__device__ __forceinline__ bool enc_src_ok(uint64_t s, uint64_t pixels_bytes, uint64_t P)
-{
-    return s <= pixels_bytes && pixels_bytes - s >= P;
-}
 
 // v of the lane to the left (0 in lane 0)
 __device__ __forceinline__ uint32_t enc_left_neighbour(uint32_t v)
@@ -82,7 +69,7 @@ __global__ __launch_bounds__(ENC_SCAN) void k_enc_place_files(uint64_t pixels_by
             abub_abf_file r;
             r.off = off;
             r.len = len;
-            r.status = !enc_src_ok(src[f], pixels_bytes, P) ? ABUB_ABF_ENC_E_SRC : off + len > out_cap ? ABUB_ABF_ENC_E_CAP : 0;
+            r.status = !frame_in_range(src[f], pixels_bytes, P) ? ABUB_ABF_ENC_E_SRC : off + len > out_cap ? ABUB_ABF_ENC_E_CAP : 0;
             files[f] = r;
             if (f == nframes - 1)
                 *total = off + len;

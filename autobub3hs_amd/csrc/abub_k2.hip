@@ -4,7 +4,7 @@
 //                                  for handed-over rows)
 //   k2_sad_chain / k2_bound_scan   bound-and-verify: proves rows of D zero from a bound, lists the rest
 //   k2_generic                     same arithmetic, any size / ROI, LDS tile (also the ROI overload)
-#include "abub_dev.hpp"
+#include "abub_scan.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // K2 fast: register-rolling rows.

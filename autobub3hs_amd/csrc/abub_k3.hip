@@ -1,6 +1,6 @@
 // abub_k3.hip -- K3: post-trigger image O = blur3x3(sat(|f - mu| - 6 sigma)) + 256-bin histogram (L3Localizer.cpp:779-787)
 // for gfx950 and its stateless C-ABI launchers (include/abub_hip.h).
-#include "abub_dev.hpp"
+#include "abub_scan.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // K3 generic: O = max(0,|f-mu| - 6 sigma), 3x3 box (S+4)/9, histogram.  32x8 tile + 1-pixel halo.

@@ -5,7 +5,7 @@
 //       k_pairs_*                      counting-sort grouping of the shared candidate list by image
 //       k_match_ccorr, k_subsat_hist   bellows veto (TrackAFeature terms, image subtraction)
 //   k_sigma6, k_fill_stack_jobs, error messages, device info, per-stream scratch of the bound-and-verify passes
-#include "abub_dev.hpp"
+#include "abub_scan.hpp"
 
 // ------------------------------------------------------------------------------------------------
 // error plumbing

@@ -5,7 +5,7 @@
 //
 // Two launches; the only dependence between workgroups is the boundary between them.
 //   k_peek_copy  grid = items x contiguous 16 KiB tiles of the plane; a block of four waves owns a tile of both planes.  A
-//                lane issues PEEK_UNR loads of D and PEEK_UNR loads of the frame before it uses any, compares the D bytes
+//                lane issues FR_UNR loads of D and FR_UNR loads of the frame before it uses any, compares the D bytes
 //                four to a dword and stores 16 bytes of each plane.  Block (tile 0) of an item writes its status.
 //   k_peek_draw  grid = items x PEEK_DRAW_BLOCKS; a block takes every PEEK_DRAW_BLOCKS-th rectangle of its item and its
 //                threads store 255 along the clipped perimeter, a byte each.  Every rectangle pixel stores the same value,
@@ -15,32 +15,25 @@
 // P mod 16 bytes of a plane is a 16-byte store.  A source is read 16 bytes at a time where its address is a multiple of
 // 16, 4 where a multiple of 4, else byte by byte; D and the frame choose independently.
 //
-// Bounds.  peek_item_ok is evaluated alike by every block of both kernels.  It admits an item only when both sources lie
-// in their buffers, both planes are multiples of 16 that lie in [0, out_bytes) and do not overlap each other, and its
-// rectangle range lies in [0, nrects].  For an admitted item a load touches bytes [0, P) of its source (unit i < P / 16 at
-// 16 i, the tail by its own index), a copy store bytes [0, P) of its plane, and a draw store index y * W + x with
-// 0 <= x < W and 0 <= y < H of the presentation plane.  Nothing of a refused item is read or written but status[item].
-#include "abub_dev.hpp"
-#include <stddef.h>
+// Bounds.  peek_item_status is evaluated alike by every block of both kernels.  It admits an item only when both sources
+// lie in their buffers, both planes are multiples of 16 that lie in [0, out_bytes) and do not overlap each other, and its
+// rectangle range lies in [0, nrects].  For an admitted item the copy walks [0, P) as abub_frames.hpp describes, with
+// 16-byte units and no head: a load touches bytes [0, P) of its source and a store the same bytes of its plane; a draw
+// store has index y * W + x with 0 <= x < W and 0 <= y < H of the presentation plane.  Nothing of a refused item is read
+// or written but status[item].
+#include "abub_frames.hpp"
 
 namespace {
 
-#define PEEK_THREADS 256     /* four waves per tile */
-#define PEEK_UNR 4           /* 16-byte units of each plane a lane has in flight */
-#define PEEK_TILE 16384u     /* bytes of a plane per block: PEEK_THREADS * PEEK_UNR * 16 */
-#define PEEK_DRAW_BLOCKS 4   /* blocks that share an item's rectangles */
-
-typedef uint32_t peek_u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ bool peek_in_range(uint64_t off, uint64_t bytes, uint64_t P) { return off <= bytes && bytes - off >= P; }
+#define PEEK_DRAW_BLOCKS 4 /* blocks that share an item's rectangles */
 
 // 0, or the ABUB_PEEK_E_* code that keeps the item from being touched
 __device__ __forceinline__ int peek_item_status(const abub_peek_item &it, uint64_t diff_bytes, uint64_t frames_bytes, uint64_t out_bytes,
                                                 int nrects, uint64_t P)
 {
-    if (!peek_in_range(it.diff, diff_bytes, P) || !peek_in_range(it.frame, frames_bytes, P))
+    if (!frame_in_range(it.diff, diff_bytes, P) || !frame_in_range(it.frame, frames_bytes, P))
         return ABUB_PEEK_E_SRC;
-    if (((it.thr_out | it.pres_out) & 15u) || !peek_in_range(it.thr_out, out_bytes, P) || !peek_in_range(it.pres_out, out_bytes, P))
+    if (((it.thr_out | it.pres_out) & 15u) || !frame_in_range(it.thr_out, out_bytes, P) || !frame_in_range(it.pres_out, out_bytes, P))
         return ABUB_PEEK_E_DST;
     if ((it.thr_out > it.pres_out ? it.thr_out - it.pres_out : it.pres_out - it.thr_out) < P)
         return ABUB_PEEK_E_DST; // (the two planes overlap)
@@ -51,20 +44,20 @@ __device__ __forceinline__ int peek_item_status(const abub_peek_item &it, uint64
 
 // 16 bytes from p + 16 i, by the widest loads MODE allows: 16 (p a multiple of 16), 4 (of 4), 1
 template <int MODE>
-__device__ __forceinline__ peek_u32x4 peek_load(const uint8_t *p, uint32_t i)
+__device__ __forceinline__ u32x4 peek_load(const uint8_t *p, uint32_t i)
 {
     if constexpr (MODE == 16)
-        return reinterpret_cast<const peek_u32x4 *>(p)[i];
+        return reinterpret_cast<const u32x4 *>(p)[i];
     else if constexpr (MODE == 4) {
         const uint32_t *q = reinterpret_cast<const uint32_t *>(p) + (size_t)i * 4;
-        return peek_u32x4{q[0], q[1], q[2], q[3]};
+        return u32x4{q[0], q[1], q[2], q[3]};
     } else {
         const uint8_t *q = p + (size_t)i * 16;
         uint32_t w[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k)
             w[k] = (uint32_t)q[4 * k] | (uint32_t)q[4 * k + 1] << 8 | (uint32_t)q[4 * k + 2] << 16 | (uint32_t)q[4 * k + 3] << 24;
-        return peek_u32x4{w[0], w[1], w[2], w[3]};
+        return u32x4{w[0], w[1], w[2], w[3]};
     }
 }
 
@@ -89,33 +82,33 @@ struct PeekCut {
         const uint32_t m = ((xh & nch) | (same & gel)) >> 7;                          // 0 or 1 per byte
         return (((m << 8) - m) | all) & keep;
     }
-    __device__ __forceinline__ peek_u32x4 operator()(peek_u32x4 v) const
+    __device__ __forceinline__ u32x4 operator()(u32x4 v) const
     {
-        return peek_u32x4{(*this)(v.x), (*this)(v.y), (*this)(v.z), (*this)(v.w)};
+        return u32x4{(*this)(v.x), (*this)(v.y), (*this)(v.z), (*this)(v.w)};
     }
 };
 
-// PEEK_THREADS * PEEK_UNR units from `base` on; FULL: all of them lie below `end` (no guard needed)
+// One step of both planes: FR_THREADS * FR_UNR units from `base` on; MD, MF: the load widths of D and of the frame
 template <int MD, int MF, bool FULL>
-__device__ __forceinline__ void peek_step(const uint8_t *d, const uint8_t *f, peek_u32x4 *ot, peek_u32x4 *op, uint32_t base, uint32_t end,
+__device__ __forceinline__ void peek_step(const uint8_t *d, const uint8_t *f, u32x4 *ot, u32x4 *op, uint32_t base, uint32_t end,
                                           const PeekCut &cut)
 {
-    peek_u32x4 vd[PEEK_UNR], vf[PEEK_UNR];
+    u32x4 vd[FR_UNR], vf[FR_UNR];
 #pragma unroll
-    for (int u = 0; u < PEEK_UNR; ++u) {
-        const uint32_t i = base + (uint32_t)u * PEEK_THREADS + threadIdx.x;
+    for (int u = 0; u < FR_UNR; ++u) {
+        const uint32_t i = base + (uint32_t)u * FR_THREADS + threadIdx.x;
         if (FULL || i < end)
             vd[u] = peek_load<MD>(d, i);
     }
 #pragma unroll
-    for (int u = 0; u < PEEK_UNR; ++u) {
-        const uint32_t i = base + (uint32_t)u * PEEK_THREADS + threadIdx.x;
+    for (int u = 0; u < FR_UNR; ++u) {
+        const uint32_t i = base + (uint32_t)u * FR_THREADS + threadIdx.x;
         if (FULL || i < end)
             vf[u] = peek_load<MF>(f, i);
     }
 #pragma unroll
-    for (int u = 0; u < PEEK_UNR; ++u) {
-        const uint32_t i = base + (uint32_t)u * PEEK_THREADS + threadIdx.x;
+    for (int u = 0; u < FR_UNR; ++u) {
+        const uint32_t i = base + (uint32_t)u * FR_THREADS + threadIdx.x;
         if (FULL || i < end) {
             ot[i] = cut(vd[u]);
             op[i] = vf[u];
@@ -123,19 +116,21 @@ __device__ __forceinline__ void peek_step(const uint8_t *d, const uint8_t *f, pe
     }
 }
 
+// Tile `tile` of an item's two planes: this kernel's own copy of frame_walk, 16-byte units and no head (through the shared
+// walk it measured up to 1.4 % slower than before, profiles/r22/frames_ab.json)
 template <int MD, int MF>
 __device__ __forceinline__ void peek_tile(const uint8_t *d, const uint8_t *f, uint8_t *ot, uint8_t *op, uint32_t P, uint32_t tile,
                                           const PeekCut &cut)
 {
-    constexpr uint32_t PER_TILE = PEEK_TILE / 16u, STEP = PEEK_THREADS * PEEK_UNR;
+    constexpr uint32_t PER_TILE = FR_TILE / 16u, STEP = FR_THREADS * FR_UNR;
     const uint32_t nunits = P / 16u, tail = P - nunits * 16u;
     // (tile < 2^18 and PER_TILE = 2^10: the products stay below 2^32)
     const uint32_t first = tile * PER_TILE, end = min(nunits, first + PER_TILE);
     if (first < end) {
         if (end - first >= STEP) // (the same in every thread of the block; PER_TILE == STEP)
-            peek_step<MD, MF, true>(d, f, reinterpret_cast<peek_u32x4 *>(ot), reinterpret_cast<peek_u32x4 *>(op), first, end, cut);
+            peek_step<MD, MF, true>(d, f, reinterpret_cast<u32x4 *>(ot), reinterpret_cast<u32x4 *>(op), first, end, cut);
         else
-            peek_step<MD, MF, false>(d, f, reinterpret_cast<peek_u32x4 *>(ot), reinterpret_cast<peek_u32x4 *>(op), first, end, cut);
+            peek_step<MD, MF, false>(d, f, reinterpret_cast<u32x4 *>(ot), reinterpret_cast<u32x4 *>(op), first, end, cut);
     }
     if (tile == 0 && threadIdx.x < tail) { // the last P mod 16 bytes, one per lane
         const uint32_t at = nunits * 16u + threadIdx.x;
@@ -144,20 +139,20 @@ __device__ __forceinline__ void peek_tile(const uint8_t *d, const uint8_t *f, ui
     }
 }
 
-template <int MD>
-__device__ __forceinline__ void peek_tile_f(const uint8_t *d, const uint8_t *f, uint8_t *ot, uint8_t *op, uint32_t P, uint32_t tile,
-                                            const PeekCut &cut)
+// body(mode) with the width a source at p is read in, as a std::integral_constant: 16, 4 or 1
+template <class Body>
+__device__ __forceinline__ void peek_mode(const uint8_t *p, Body body)
 {
-    const uint32_t lf = (uint32_t)(uintptr_t)f;
-    if ((lf & 15u) == 0u)
-        peek_tile<MD, 16>(d, f, ot, op, P, tile, cut);
-    else if ((lf & 3u) == 0u)
-        peek_tile<MD, 4>(d, f, ot, op, P, tile, cut);
+    const uint32_t low = (uint32_t)(uintptr_t)p;
+    if ((low & 15u) == 0u)
+        body(std::integral_constant<int, 16>());
+    else if ((low & 3u) == 0u)
+        body(std::integral_constant<int, 4>());
     else
-        peek_tile<MD, 1>(d, f, ot, op, P, tile, cut);
+        body(std::integral_constant<int, 1>());
 }
 
-__global__ __launch_bounds__(PEEK_THREADS) void k_peek_copy(const uint8_t *diff, uint64_t diff_bytes, const uint8_t *frames,
+__global__ __launch_bounds__(FR_THREADS) void k_peek_copy(const uint8_t *diff, uint64_t diff_bytes, const uint8_t *frames,
                                                             uint64_t frames_bytes, const abub_peek_item *__restrict__ items, int nitems,
                                                             int nrects, uint32_t P, uint8_t *out, uint64_t out_bytes,
                                                             int32_t *__restrict__ status)
@@ -172,18 +167,12 @@ __global__ __launch_bounds__(PEEK_THREADS) void k_peek_copy(const uint8_t *diff,
         const uint8_t *d = diff + it.diff, *f = frames + it.frame;
         uint8_t *ot = out + it.thr_out, *op = out + it.pres_out;
         const PeekCut cut(it.thr);
-        const uint32_t ld = (uint32_t)(uintptr_t)d;
-        if ((ld & 15u) == 0u)
-            peek_tile_f<16>(d, f, ot, op, P, blockIdx.x, cut);
-        else if ((ld & 3u) == 0u)
-            peek_tile_f<4>(d, f, ot, op, P, blockIdx.x, cut);
-        else
-            peek_tile_f<1>(d, f, ot, op, P, blockIdx.x, cut);
+        peek_mode(d, [&](auto md) { peek_mode(f, [&](auto mf) { peek_tile<md, mf>(d, f, ot, op, P, blockIdx.x, cut); }); });
     }
 }
 
 // cv::rectangle of host/cvlite.cpp, thickness 1: rows y and y + h - 1, columns x and x + w - 1, each clipped to the frame
-__global__ __launch_bounds__(PEEK_THREADS) void k_peek_draw(uint64_t diff_bytes, uint64_t frames_bytes, const abub_peek_item *__restrict__ items,
+__global__ __launch_bounds__(FR_THREADS) void k_peek_draw(uint64_t diff_bytes, uint64_t frames_bytes, const abub_peek_item *__restrict__ items,
                                                             int nitems, const abub_peek_rect *__restrict__ rects, int nrects, int W, int H,
                                                             uint8_t *out, uint64_t out_bytes)
 {
@@ -204,13 +193,13 @@ __global__ __launch_bounds__(PEEK_THREADS) void k_peek_draw(uint64_t diff_bytes,
                 continue; // (wholly outside: no row and no column of it meets the frame)
             const uint32_t nx = (uint32_t)(cx1 - cx0 + 1), ny = (uint32_t)(cy1 - cy0 + 1); // (<= 65535 each)
             const bool top = y0 >= 0 && y0 < H, bottom = y1 >= 0 && y1 < H, left = x0 >= 0 && x0 < W, right = x1 >= 0 && x1 < W;
-            for (uint32_t i = threadIdx.x; i < nx; i += PEEK_THREADS) {
+            for (uint32_t i = threadIdx.x; i < nx; i += FR_THREADS) {
                 if (top)
                     op[(uint32_t)y0 * (uint32_t)W + (uint32_t)cx0 + i] = 255;
                 if (bottom)
                     op[(uint32_t)y1 * (uint32_t)W + (uint32_t)cx0 + i] = 255;
             }
-            for (uint32_t i = threadIdx.x; i < ny; i += PEEK_THREADS) {
+            for (uint32_t i = threadIdx.x; i < ny; i += FR_THREADS) {
                 if (left)
                     op[((uint32_t)cy0 + i) * (uint32_t)W + (uint32_t)x0] = 255;
                 if (right)
@@ -236,12 +225,12 @@ extern "C" int abub_peek_planes_dev(const uint8_t *diff, size_t diff_bytes, cons
         return ABUB_OK;
     hipStream_t st = (hipStream_t)stream;
     const uint32_t P = (uint32_t)W * (uint32_t)H; // (<= 65535^2 < 2^32)
-    const unsigned gy = (unsigned)(nitems < 65535 ? nitems : 65535);
-    k_peek_copy<<<dim3((P + PEEK_TILE - 1) / PEEK_TILE, gy), PEEK_THREADS, 0, st>>>(
+    const dim3 grid = frame_grid(P, nitems);
+    k_peek_copy<<<grid, FR_THREADS, 0, st>>>(
         diff, (uint64_t)diff_bytes, frames, (uint64_t)frames_bytes, items, nitems, nrects, P, out, (uint64_t)out_bytes, status);
     HIPCHK(hipGetLastError());
     if (nrects > 0) { // (an item cannot name a rectangle of an empty list: its rect_count is 0, or it is refused)
-        k_peek_draw<<<dim3(PEEK_DRAW_BLOCKS, gy), PEEK_THREADS, 0, st>>>((uint64_t)diff_bytes, (uint64_t)frames_bytes, items, nitems, rects,
+        k_peek_draw<<<dim3(PEEK_DRAW_BLOCKS, grid.y), FR_THREADS, 0, st>>>((uint64_t)diff_bytes, (uint64_t)frames_bytes, items, nitems, rects,
                                                                          nrects, W, H, out, (uint64_t)out_bytes);
         HIPCHK(hipGetLastError());
     }

@@ -83,7 +83,7 @@ __global__ __launch_bounds__(64 * PNGE_WAVES) void k_png_enc_hist(const uint8_t 
     const uint32_t f = blockIdx.x;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const uint64_t P = (uint64_t)W * (uint64_t)H, s = src[f];
-    if (!enc_src_ok(s, pixels_bytes, P))
+    if (!frame_in_range(s, pixels_bytes, P))
         return; // (the same in every thread; nobody reads this frame's scratch)
     for (int b = threadIdx.x; b < 257; b += 64 * PNGE_WAVES)
         sh[b] = 0;
@@ -103,8 +103,8 @@ __global__ __launch_bounds__(64 * PNGE_WAVES) void k_png_enc_hist(const uint8_t 
                 B = (B + ((n - (uint32_t)(c0 + lane)) % PNGE_MOD) * d) % PNGE_MOD;
             }
         }
-        A = enc_wave_sum(A % PNGE_MOD);
-        B = enc_wave_sum(B);
+        A = wave_sum(A % PNGE_MOD);
+        B = wave_sum(B);
         if (lane == 0) {
             frows[y].A = A % PNGE_MOD;
             frows[y].B = B % PNGE_MOD;
@@ -219,7 +219,7 @@ __global__ __launch_bounds__(64) void k_png_enc_codes(uint64_t pixels_bytes, con
     __shared__ uint8_t len[258], cllen[19];
     const uint32_t f = blockIdx.x;
     const int lane = threadIdx.x;
-    if (!enc_src_ok(src[f], pixels_bytes, (uint64_t)W * (uint64_t)H))
+    if (!frame_in_range(src[f], pixels_bytes, (uint64_t)W * (uint64_t)H))
         return;
     for (int s = lane; s < 257; s += 64)
         cnt[s] = s == 256 ? 1u : hist[(uint64_t)f * PNGE_TAB + s];
@@ -280,7 +280,7 @@ __global__ __launch_bounds__(64 * PNGE_WAVES) void k_png_enc_measure(const uint8
     const uint32_t f = blockIdx.x;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const uint64_t P = (uint64_t)W * (uint64_t)H, s = src[f];
-    if (!enc_src_ok(s, pixels_bytes, P))
+    if (!frame_in_range(s, pixels_bytes, P))
         return;
     for (int b = threadIdx.x; b < 257; b += 64 * PNGE_WAVES)
         len[b] = (uint8_t)min(codes[(uint64_t)f * PNGE_TAB + b] >> 16, 15u);
@@ -295,7 +295,7 @@ __global__ __launch_bounds__(64 * PNGE_WAVES) void k_png_enc_measure(const uint8
             const uint32_t d = pnge_row_symbol(row, W, c0, lane, valid);
             bits += valid ? (uint32_t)len[d] : 0u;
         }
-        bits = enc_wave_sum(bits);
+        bits = wave_sum(bits);
         if (lane == 0)
             frows[y].bit = bits;
     }
@@ -309,7 +309,7 @@ __global__ __launch_bounds__(ENC_SCAN) void k_png_enc_place_rows(uint64_t pixels
     __shared__ unsigned long long sh64[ENC_SCAN / 64];
     __shared__ uint32_t sh32[ENC_SCAN / 64];
     const uint32_t f = blockIdx.x;
-    if (!enc_src_ok(src[f], pixels_bytes, (uint64_t)W * (uint64_t)H)) { // (the same answer in every thread)
+    if (!frame_in_range(src[f], pixels_bytes, (uint64_t)W * (uint64_t)H)) { // (the same answer in every thread)
         if (threadIdx.x == 0) {
             PngeFrame z;
             z.flen = 0;
