@@ -1,5 +1,6 @@
 // abub_stats.hip -- per-frame statistics of resident frames: abub_frame_stats_dev (include/abub_hip.h, DESIGN section 3,
-// "Surveying a run").  What a byte loop over a decoded frame does on a host thread (host/survey.cpp frameStatsHost, the
+// "Surveying a run"); below it the per-pixel planes (abub_pixel_activity_dev) and the shift search (abub_frame_shift_dev),
+// each under a header of its own.  What a byte loop over a decoded frame does on a host thread (host/survey.cpp frameStatsHost, the
 // definition): per job the grey-level range, sum, sum of squares, black and saturated pixels of the frame, and against a
 // model (mu, sigma6) and a reference frame the count and sum of sat(|p - m| - s) and of sat(|p - r| - s).
 //
@@ -543,5 +544,222 @@ extern "C" int abub_pixel_activity_dev(const uint8_t *frames, size_t frames_byte
     if (edge) // (at most 14 single pixels)
         return act_launch<1>(mu != nullptr, 1u, st, frames, frames_bytes, mu, sigma6, jobs, njobs, frame_bytes, head, body_end, edge,
                              planes, plane_stride, status);
+    return ABUB_OK;
+}
+
+// ---- per-frame shift search: abub_frame_shift_dev ("Surveying a run for movement") ----------------------
+// The SAD between a frame p and its model plane m (mu) at every integer displacement within a radius R (host/survey.cpp
+// frameShiftHost, the definition): with the interior I = [R, W - R) x [R, H - R),
+//   sad[(dy + R) * (2 R + 1) + (dx + R)] = sum over (x, y) in I of |p(x + dx, y + dy) - m(x, y)|,    -R <= dx, dy <= R.
+//
+// The grid is jobs x tiles of the interior, SH_TW = 256 pixels by SH_TH = 64 rows; a block of four waves owns a tile.  It
+// reads the tile of the frame with its halo of R pixels on every side from memory once, into LDS, in rows of dwords (row r,
+// dword c: the four pixels from (x0 - R + 4 c, y0 - R + r) on, in memory order).  Lane l owns the four pixels from
+// x0 + 4 l on of the tile's rows w, w + 4, ... (w: its wave) and holds their mu dwords in registers for the whole tile.  Per
+// dy (a loop that is not unrolled) it has 2 R + 1 u32 sums in registers: of every row it owns it reads the ceil((2 R + 4) / 4)
+// dwords of LDS row + dy that lie under its pixels at all dx, forms the byte-shifted dword of each dx with v_alignbyte_b32
+// and adds v_sad_u8 of it against mu.  Pixels of a dword beyond the interior's right edge are cleared in both operands; a
+// block whose 256 columns all lie inside takes a path without the masks, and there, from R = 2 on, four consecutive dx at a
+// time are one v_qsad_pk_u16_u8 of two neighbouring dwords against mu, into four u16 sums that are taken apart once per dy
+// (a lane adds at most 16 rows * 4 * 255 = 16320 into a u16: whether the instruction wraps or saturates never shows).  The sums of a dy are added over the wave
+// with shuffles and kept in LDS per wave; at the end thread t adds the four waves' values of displacement t and issues one u64
+// atomic add into the job's surface (an add of 0 is left out).  A tile has at most 256 * 64 pixels, and 16384 * 255 < 2^32:
+// every partial sum of a block fits u32.  Integer adds commute, so a surface does not depend on the order the blocks
+// arrive in, and no workgroup waits for another.  k_shift_init writes the status and clears the surface first.
+//
+// A stream's dword at any byte index is formed from the two aligned dwords around it (one where the address is a multiple
+// of 4) where both lie inside the frame, else from single bytes; a byte beyond the frame's end reads as 0 and only ever
+// meets a cleared mu byte or a row that is not summed.
+//
+// Bounds.  A job is read only if cur + W * H <= frames_bytes and model + W * H <= model_bytes; otherwise E_RANGE, found
+// alike by k_shift_init and by every block of k_shift.  Within a job every load of sh_load4 lies in [0, W * H) of its
+// stream (the test is on the index itself).  LDS: row r < rows + 2 R <= SH_TH + 2 R, dword c < SH_TW / 4 + ND - 1, the
+// array's bounds; a lane reads dwords l .. l + ND - 1 of rows it was given.  Stores: status[j] and sad[j * N + t], j < njobs,
+// t < N = (2 R + 1)^2.
+namespace {
+
+#define SH_TW 256u /* interior pixels of a tile across: one dword per lane */
+#define SH_TH 64u  /* rows of a tile: 16 per wave */
+#define SH_ROWS (SH_TH / (FR_THREADS / 64))
+
+__device__ __forceinline__ bool sh_job_ok(const abub_shift_job &jb, uint64_t frames_bytes, uint64_t model_bytes, uint64_t P)
+{
+    return frame_in_range(jb.cur, frames_bytes, P) && frame_in_range(jb.model, model_bytes, P);
+}
+
+// the four bytes from index i on of a stream of P bytes, in memory order; bytes at P and beyond read as 0
+__device__ __forceinline__ uint32_t sh_load4(const uint8_t *s, uint64_t i, uint64_t P)
+{
+    const uint32_t mis = (uint32_t)((uintptr_t)(s + i) & 3u);
+    if (mis == 0u && i + 4u <= P)
+        return *reinterpret_cast<const uint32_t *>(s + i);
+    if (i >= mis && i - mis + 8u <= P) {
+        const uint32_t *a = reinterpret_cast<const uint32_t *>(s + (i - mis));
+        return __builtin_amdgcn_alignbyte(a[1], a[0], mis);
+    }
+    uint32_t v = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < 4u; ++k)
+        if (i + k < P)
+            v |= (uint32_t)s[i + k] << (8u * k);
+    return v;
+}
+
+__global__ __launch_bounds__(FR_THREADS) void k_shift_init(uint64_t frames_bytes, uint64_t model_bytes,
+                                                           const abub_shift_job *__restrict__ jobs, int njobs, uint64_t P, uint32_t N,
+                                                           uint32_t *__restrict__ status, uint64_t *__restrict__ sad)
+{
+    const uint64_t t = (uint64_t)blockIdx.x * FR_THREADS + threadIdx.x;
+    if (t >= (uint64_t)njobs * N)
+        return;
+    sad[t] = 0;
+    if (t % N == 0u) {
+        const uint64_t j = t / N;
+        status[j] = sh_job_ok(jobs[j], frames_bytes, model_bytes, P) ? 0u : (uint32_t)ABUB_SHIFT_E_RANGE;
+    }
+}
+
+template <int R, bool FULL, bool QSAD = false>
+__device__ __forceinline__ void sh_tile(const uint32_t *tile, const uint32_t (&m)[SH_ROWS], uint32_t mask, uint32_t rows,
+                                        uint32_t (*part)[(2 * R + 1) * (2 * R + 1)])
+{
+    constexpr int D = 2 * R + 1, ND = (2 * R + 4 + 3) / 4, RS = SH_TW / 4 + ND - 1;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+#pragma unroll 1
+    for (int dy = 0; dy < D; ++dy) {
+        uint32_t acc[D];
+#pragma unroll
+        for (int o = 0; o < D; ++o)
+            acc[o] = 0;
+        // QSAD: the displacements 4 g .. 4 g + 3 of a group g whose upper dword the lane has read, as four u16 sums of one
+        // v_qsad_pk_u16_u8 (a lane adds at most SH_ROWS * 4 * 255 = 16320 into each: no carry, no saturation)
+        constexpr int NQ = QSAD ? ND - 1 : 0;
+        uint64_t qacc[NQ ? NQ : 1] = {};
+#pragma unroll
+        for (uint32_t r = 0; r < SH_ROWS; ++r) {
+            const uint32_t row = r * (FR_THREADS / 64) + wave; // (the same in every lane of the wave)
+            if (row >= rows)
+                break;
+            const uint32_t *src = tile + (row + (uint32_t)dy) * RS + lane;
+            uint32_t d[ND];
+#pragma unroll
+            for (int k = 0; k < ND; ++k)
+                d[k] = src[k];
+#pragma unroll
+            for (int g = 0; g < NQ; ++g)
+                qacc[g] = __builtin_amdgcn_qsad_pk_u16_u8((uint64_t)d[g] | (uint64_t)d[g + 1] << 32, m[r], qacc[g]);
+#pragma unroll
+            for (int o = 4 * NQ; o < D; ++o) {
+                uint32_t a = d[o >> 2]; // the four pixels at dx = o - R: bytes o .. o + 3 of what the lane read
+                if (o & 3)
+                    a = __builtin_amdgcn_alignbyte(d[(o + 3) >> 2], a, (uint32_t)(o & 3));
+                if (!FULL)
+                    a &= mask;
+                acc[o] = __builtin_amdgcn_sad_u8(a, m[r], acc[o]);
+            }
+        }
+#pragma unroll
+        for (int o = 0; o < 4 * NQ && o < D; ++o)
+            acc[o] = (uint32_t)(qacc[o >> 2] >> (16 * (o & 3))) & 0xffffu;
+#pragma unroll
+        for (int s = 32; s > 0; s >>= 1)
+#pragma unroll
+            for (int o = 0; o < D; ++o)
+                acc[o] += (uint32_t)__shfl_xor(acc[o], s);
+        if (lane == 0u) {
+#pragma unroll
+            for (int o = 0; o < D; ++o)
+                part[wave][dy * D + o] = acc[o];
+        }
+    }
+}
+
+template <int R>
+__global__ __launch_bounds__(FR_THREADS) void k_shift(const uint8_t *frames, uint64_t frames_bytes, const uint8_t *mu, uint64_t model_bytes,
+                                                      const abub_shift_job *__restrict__ jobs, int njobs, uint32_t W, uint32_t H,
+                                                      uint32_t tiles_x, uint64_t *__restrict__ sad)
+{
+    constexpr int D = 2 * R + 1, N = D * D, ND = (2 * R + 4 + 3) / 4, RS = SH_TW / 4 + ND - 1;
+    __shared__ uint32_t tile[(SH_TH + 2 * R) * RS];
+    __shared__ uint32_t part[FR_THREADS / 64][N];
+    const uint64_t P = (uint64_t)W * H;
+    // the tile: interior pixels [x0, x0 + cols) x [y0, y0 + rows), cols and rows at least 1 by the grid's shape
+    const uint32_t x0 = (uint32_t)R + (blockIdx.x % tiles_x) * SH_TW, y0 = (uint32_t)R + (blockIdx.x / tiles_x) * SH_TH;
+    const uint32_t cols = min(SH_TW, W - (uint32_t)R - x0), rows = min(SH_TH, H - (uint32_t)R - y0);
+    const uint32_t ndw = (cols + 2u * R + 3u) / 4u; // dwords of a tile row that hold a pixel some lane uses: <= RS
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    // which of the lane's four pixels lie in the interior
+    const uint32_t left = 4u * lane < cols ? min(4u, cols - 4u * lane) : 0u;
+    const uint32_t mask = left == 4u ? 0xffffffffu : (1u << (8u * left)) - 1u;
+    for (uint32_t j = blockIdx.y; j < (uint32_t)njobs; j += gridDim.y) {
+        const abub_shift_job jb = jobs[j];
+        if (!sh_job_ok(jb, frames_bytes, model_bytes, P))
+            continue; // (the same in every thread of every block of the job)
+        const uint8_t *p = frames + jb.cur, *q = mu + jb.model;
+        for (uint32_t i = threadIdx.x; i < (rows + 2u * R) * RS; i += FR_THREADS) {
+            const uint32_t r = i / RS, c = i % RS;
+            tile[i] = c < ndw ? sh_load4(p, (uint64_t)(y0 - R + r) * W + (x0 - R) + 4u * c, P) : 0u;
+        }
+        uint32_t m[SH_ROWS];
+#pragma unroll
+        for (uint32_t r = 0; r < SH_ROWS; ++r) {
+            const uint32_t row = r * (FR_THREADS / 64) + wave;
+            m[r] = row < rows && left ? sh_load4(q, (uint64_t)(y0 + row) * W + x0 + 4u * lane, P) & mask : 0u;
+        }
+        __syncthreads();
+        if (cols == SH_TW)
+            sh_tile<R, true, R >= 2>(tile, m, mask, rows, part); // (the quad form measured 2 to 3 % faster from R = 2 on, 1 % slower at 1)
+        else
+            sh_tile<R, false>(tile, m, mask, rows, part);
+        __syncthreads();
+        for (uint32_t t = threadIdx.x; t < (uint32_t)N; t += FR_THREADS) {
+            uint32_t v = part[0][t];
+#pragma unroll
+            for (int w = 1; w < FR_THREADS / 64; ++w)
+                v += part[w][t];
+            if (v)
+                atomicAdd((unsigned long long *)(sad + (uint64_t)j * N + t), (unsigned long long)v);
+        }
+        __syncthreads(); // (tile and part are written again for the block's next job)
+    }
+}
+
+template <int R>
+void shift_launch(dim3 grid, hipStream_t st, const uint8_t *frames, uint64_t frames_bytes, const uint8_t *mu, uint64_t model_bytes,
+                  const abub_shift_job *jobs, int njobs, uint32_t W, uint32_t H, uint32_t tiles_x, uint64_t *sad)
+{
+    k_shift<R><<<grid, FR_THREADS, 0, st>>>(frames, frames_bytes, mu, model_bytes, jobs, njobs, W, H, tiles_x, sad);
+}
+
+} // namespace
+
+extern "C" int abub_frame_shift_dev(const uint8_t *frames, size_t frames_bytes, const uint8_t *mu, size_t model_bytes,
+                                    const abub_shift_job *jobs, int njobs, int W, int H, int R, uint32_t *status, uint64_t *sad,
+                                    void *stream)
+{
+    if (!frames || !mu || !jobs || !status || !sad || njobs < 0)
+        return set_err(ABUB_E_INVALID, "abub_frame_shift_dev: null pointer or negative count");
+    if (R < 1 || R > 8)
+        return set_err(ABUB_E_INVALID, "abub_frame_shift_dev: R must be in [1, 8]");
+    if (W < 2 * R + 1 || W > 65535 || H < 2 * R + 1 || H > 65535)
+        return set_err(ABUB_E_INVALID, "abub_frame_shift_dev: W and H must be in [2 R + 1, 65535]");
+    if (!frame_lists_aligned(jobs, sad) || ((uintptr_t)status & 3))
+        return set_err(ABUB_E_INVALID, "abub_frame_shift_dev: jobs and sad must be 8-byte aligned, status 4-byte aligned");
+    if (njobs == 0)
+        return ABUB_OK;
+    hipStream_t st = (hipStream_t)stream;
+    const uint64_t P = (uint64_t)W * (uint64_t)H;
+    const uint32_t N = (uint32_t)((2 * R + 1) * (2 * R + 1));
+    k_shift_init<<<(unsigned)(((uint64_t)njobs * N + FR_THREADS - 1) / FR_THREADS), FR_THREADS, 0, st>>>(
+        (uint64_t)frames_bytes, (uint64_t)model_bytes, jobs, njobs, P, N, status, sad);
+    HIPCHK(hipGetLastError());
+    const uint32_t tiles_x = ((uint32_t)(W - 2 * R) + SH_TW - 1) / SH_TW, tiles_y = ((uint32_t)(H - 2 * R) + SH_TH - 1) / SH_TH;
+    const dim3 grid(tiles_x * tiles_y, (unsigned)(njobs < 65535 ? njobs : 65535)); // (at most 256 * 1024 tiles)
+    typedef void (*Launch)(dim3, hipStream_t, const uint8_t *, uint64_t, const uint8_t *, uint64_t, const abub_shift_job *, int, uint32_t,
+                           uint32_t, uint32_t, uint64_t *);
+    static const Launch launch[8] = {shift_launch<1>, shift_launch<2>, shift_launch<3>, shift_launch<4>,
+                                     shift_launch<5>, shift_launch<6>, shift_launch<7>, shift_launch<8>};
+    launch[R - 1](grid, st, frames, (uint64_t)frames_bytes, mu, (uint64_t)model_bytes, jobs, njobs, (uint32_t)W, (uint32_t)H, tiles_x, sad);
+    HIPCHK(hipGetLastError());
     return ABUB_OK;
 }

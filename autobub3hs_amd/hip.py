@@ -682,6 +682,33 @@ def frame_stats(frames, jobs, frame_bytes, mu=None, sigma6=None, frames_bytes=No
                           axis=1)
 
 
+SHIFT_E_RANGE = 1
+
+
+def frame_shift(frames, mu, jobs, W, H, R, frames_bytes=None, model_bytes=None, status=None, sad=None):
+    """abub_frame_shift_dev: frames / mu u8 device tensors (any shape), jobs: [n, 2] byte offsets (cur, model) of each job's
+    W x H frame in `frames` and of its model plane in `mu` (any alignment); R: the radius, 1 to 8; frames_bytes /
+    model_bytes: the sizes the kernel is told (default: the tensors'); status: int32 device tensor of at least n words, sad:
+    int64 device tensor of at least n * (2 R + 1)^2 words, both written in place (None: new ones)
+    -> (status int64 [n] on the host: 0 or SHIFT_E_RANGE; the surfaces, uint64 [n, 2 R + 1, 2 R + 1] on the host, entry
+    [dy + R, dx + R])."""
+    import numpy as np
+    _need_cuda(frames, mu, status, sad)
+    offs = np.array([[int(v) for v in row] for row in jobs], dtype=np.uint64).reshape(-1, 2)
+    n, D = len(offs), 2 * int(R) + 1
+    dev = frames.device
+    d_jobs = torch.from_numpy(np.concatenate([offs, np.zeros((1, 2), np.uint64)]).view(np.int64)).to(dev)
+    if status is None:
+        status = torch.full((max(n, 1),), 0x5A5A5A5A, dtype=torch.int32, device=dev)
+    if sad is None:
+        sad = torch.full((max(n, 1) * D * D,), -1, dtype=torch.int64, device=dev)
+    _lib.check(_lib.lib().abub_frame_shift_dev(_ptr(frames), frames.numel() if frames_bytes is None else int(frames_bytes), _ptr(mu),
+                                               mu.numel() if model_bytes is None else int(model_bytes), _ptr(d_jobs), n, int(W), int(H),
+                                               int(R), _ptr(status), _ptr(sad), _stream()), "abub_frame_shift_dev")
+    return (status.reshape(-1)[:n].cpu().numpy().astype(np.int64),
+            sad.reshape(-1)[:n * D * D].cpu().numpy().view(np.uint64).reshape(n, D, D))
+
+
 ACT_PLANES = ("n_zero", "n_sat", "n_out", "sum_out", "n_moved", "sum_moved")
 ACT_E_RANGE = 1
 ACT_PIXELS_PER_THREAD = 8  # AC_PX of csrc/abub_stats.hip: the run of pixels a thread owns

@@ -67,6 +67,10 @@ SIGNATURES = {
     "abh_run_survey_report": (_s, [_vp]),
     "abh_run_survey_planes": (_i, [_vp, _s, _s, _i, _i, _dp, _dp, C.c_char_p, _i]),
     "abh_run_survey_planes_dev": (_i, [_vp, _s, _s, _i, _i, _i, _dp, _dp, C.c_char_p, _i]),
+    "abh_run_survey_shift": (_i, [_vp, _s, _s, _s, _i, _i, _i, _dp, _dp, _dp, C.c_char_p, _i]),
+    "abh_run_survey_shift_dev": (_i, [_vp, _s, _s, _s, _i, _i, _i, _i, _dp, _dp, _dp, C.c_char_p, _i]),
+    "abh_frame_shift_host": (_i, [_u8p, _u8p, _i, _i, _i, _u64p]),
+    "abh_shift_best": (None, [_u64p, _i, C.POINTER(_i)]),
     "abh_activity_add_host": (None, [C.POINTER(C.c_uint32), _u8p, _u8p, _u8p, _u8p, C.c_uint64]),
     "abh_frame_stats_host": (None, [_u8p, _u8p, _u8p, _u8p, C.c_uint64, _u64p]),
     "abh_zip_write": (_i, [_s, _i, _u8p, _u32p, _u8p, _u64p]),
@@ -443,7 +447,7 @@ class Run:
                     "gpu_png_decoded", "gpu_unpacked", "gpu_bmp_decoded", "host_decoded", "reread", "frames_gpu_unzipped", "device",
                     "W", "H", "batches", "model_cams")
 
-    def survey(self, path=None, nthreads=16, ncams=4, device=None, planes=None):
+    def survey(self, path=None, nthreads=16, ncams=4, device=None, planes=None, shift=None, shift_radius=4):
         """abub3hs --survey of this run (opened from a directory or an archive): the run is listed and trained as for
         detect, then every frame of cameras 0 .. ncams-1 is measured without analysing any; the report (DESIGN section 3,
         "Surveying a run") is written to `path` (None: it is not written).  device=None: host threads (cv::imdecode and
@@ -455,14 +459,27 @@ class Run:
         planes (--survey-planes): the directory (the CLI's DIR/<run_ID>) that gets the per-pixel activity planes (DESIGN
         section 3, "Surveying a run per pixel"): cam<c>_activity.npy, cam<c>_moved.png, activity.txt, the same bytes on
         both routes; the stats then also have plane_rows_kernel / plane_rows_host and the legs activity_s, planes_copy_s,
-        planes_write_s.  The report does not change."""
+        planes_write_s.  The report does not change.
+        shift (--survey-shift): the file that gets the shift search ("Surveying a run for movement"): per
+        ok frame of a camera with a model its best displacement against mu within shift_radius (1 to 8), the same bytes on
+        both routes; the stats then also have shift_frames_kernel / shift_frames_host, shift_launches and the legs shift_s
+        (the device route's) and shift_host_s (the host threads', summed).  The report and the planes do not change."""
         L = lib()
         st = (C.c_double * 24)()
         pst = (C.c_double * 5)()
+        sst = (C.c_double * 5)()
         cap = 1 << 16
         buf = C.create_string_buffer(cap)
         to = None if path is None else str(path).encode()
-        if planes is not None:
+        if shift is not None:
+            pd = None if planes is None else str(planes).encode()
+            sp = str(shift).encode()
+            if device is None:
+                rc = L.abh_run_survey_shift(self._h, to, pd, sp, int(shift_radius), ncams, nthreads, st, pst, sst, buf, cap)
+            else:
+                rc = L.abh_run_survey_shift_dev(self._h, to, pd, sp, int(shift_radius), ncams, nthreads, int(device), st, pst, sst, buf,
+                                                cap)
+        elif planes is not None:
             pd = str(planes).encode()
             if device is None:
                 rc = L.abh_run_survey_planes(self._h, to, pd, ncams, nthreads, st, pst, buf, cap)
@@ -480,6 +497,9 @@ class Run:
         if planes is not None:
             res.update(plane_rows_kernel=int(pst[0]), plane_rows_host=int(pst[1]), activity_s=pst[2], planes_copy_s=pst[3],
                        planes_write_s=pst[4])
+        if shift is not None:
+            res.update(shift_frames_kernel=int(sst[0]), shift_frames_host=int(sst[1]), shift_launches=int(sst[2]), shift_s=sst[3],
+                       shift_host_s=sst[4])
         return res, text.decode()
 
     def analyze(self, event, cam, maskdir=""):
@@ -515,6 +535,26 @@ def activity_add_host(planes, cur, ref=None, mu=None, sigma6=None):
     assert planes.dtype == np.uint32 and planes.flags["C_CONTIGUOUS"] and planes.size == 6 * n
     lib().abh_activity_add_host(planes.ctypes.data_as(C.POINTER(C.c_uint32)),
                                 *[None if a is None else a.ctypes.data_as(_u8p) for a in arrs], n)
+
+
+def frame_shift_host(p, m, R):
+    """abub::frameShiftHost (host/survey.cpp), the definition of abub_frame_shift_dev: the frame p and the model plane m, u8
+    [H, W], at radius R -> the SAD surface, uint64 [2 R + 1, 2 R + 1], entry [dy + R, dx + R]."""
+    p, m = (np.ascontiguousarray(a, dtype=np.uint8) for a in (p, m))
+    assert p.ndim == 2 and p.shape == m.shape
+    sad = np.zeros((2 * R + 1, 2 * R + 1), np.uint64)
+    if lib().abh_frame_shift_host(p.ctypes.data_as(_u8p), m.ctypes.data_as(_u8p), p.shape[1], p.shape[0], int(R), sad.ctypes.data_as(_u64p)):
+        raise ValueError(f"abh_frame_shift_host refuses {p.shape[1]}x{p.shape[0]} at radius {R}")
+    return sad
+
+
+def shift_best(sad, R):
+    """abub::shiftBest (host/survey.cpp), the tie rule of both survey routes: a surface of radius R -> (dx, dy, at_edge)."""
+    sad = np.ascontiguousarray(sad, dtype=np.uint64).reshape(-1)
+    assert sad.size == (2 * R + 1) ** 2
+    out = (C.c_int * 3)()
+    lib().abh_shift_best(sad.ctypes.data_as(_u64p), int(R), out)
+    return out[0], out[1], bool(out[2])
 
 
 def zip_write(path, entries):

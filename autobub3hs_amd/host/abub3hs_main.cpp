@@ -34,6 +34,7 @@ static std::string usage()
            "       abub3hs [-z] [-D data_series] -d data_dir -r run_ID --unpack out_data_dir [--unpack-gpu] [--archive]\n"
            "       abub3hs [-z] [-D data_series] -d data_dir -r run_ID --verify-repack other_data_dir [--verify-gpu] [--archive]\n"
            "       abub3hs [-z] [-D data_series] -d data_dir -r run_ID --survey FILE [--survey-gpu] [--survey-planes DIR]\n"
+           "               [--survey-shift FILE [--survey-shift-radius R]]\n"
            "Run the AutoBub3hs bubble finding algorithm on a PICO run (MI355X hot path)\n\n"
            "Required arguments:\n"
            "  -d, --data_dir = Dir\t\tpath to the directory in which the run folder/file is stored\n"
@@ -100,6 +101,14 @@ static std::string usage()
            "\t\t\t\tcam<c>_moved.png (the share of frames in which the pixel moved, 255 = all) and activity.txt (the\n"
            "\t\t\t\tdenominators, dead / stuck / ever-moved pixel counts and the 16 hottest pixels); the same bytes\n"
            "\t\t\t\twith --survey-gpu; the report does not change\n"
+           "  --survey-shift = File\t\twith --survey: also search every ok frame of a camera with a model for its displacement\n"
+           "\t\t\t\tagainst the model's mean image (the sum of absolute differences over the interior at every integer\n"
+           "\t\t\t\tdx, dy within the radius) and write File: per frame the best dx, dy, whether it lies on the edge of\n"
+           "\t\t\t\tthe search, the sums at (0, 0) and at the best, and the gain; per camera and for the run how many\n"
+           "\t\t\t\tframes moved and from which event on; the same bytes with --survey-gpu; the report and the planes\n"
+           "\t\t\t\tdo not change\n"
+           "  --survey-shift-radius = R\twith --survey-shift: the radius of the search in pixels, 1 to 8 (4); the frames must be at\n"
+           "\t\t\t\tleast 2 R + 1 wide and high\n"
            "Environment: ABUB_TRAIN_ON_GPU=0 trains the runs of a campaign with the host Trainer\n"
            "             ABUB_REPACK_BATCH=n (a test knob) lowers the frames per batch of --repack-gpu and --unpack-gpu to n; the files\n"
            "             are the same\n"
@@ -275,6 +284,9 @@ int main(int argc, char **argv)
     bool haveSurvey = false, surveyGpu = false;
     std::string surveyPlanesDir; // --survey-planes DIR: the survey's per-pixel planes go to DIR/<run_ID>/
     bool haveSurveyPlanes = false;
+    std::string surveyShiftFile; // --survey-shift FILE: the survey's shift search, its answers go to FILE
+    bool haveSurveyShift = false, haveShiftRadius = false;
+    int surveyShiftRadius = 4;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i], v;
         auto value = [&](std::string &dst) {
@@ -375,6 +387,20 @@ int main(int argc, char **argv)
         } else if (a == "--survey-planes" || a.rfind("--survey-planes=", 0) == 0) {
             value(surveyPlanesDir);
             haveSurveyPlanes = true;
+        } else if (a == "--survey-shift-radius" || a.rfind("--survey-shift-radius=", 0) == 0) {
+            v.clear();
+            value(v);
+            haveShiftRadius = true;
+            char *end = nullptr;
+            const long radius = strtol(v.c_str(), &end, 10);
+            if (v.empty() || *end || radius < 1 || radius > 8) {
+                std::cerr << "--survey-shift-radius expects a radius from 1 to 8" << std::endl;
+                return -1;
+            }
+            surveyShiftRadius = (int)radius;
+        } else if (a == "--survey-shift" || a.rfind("--survey-shift=", 0) == 0) {
+            value(surveyShiftFile);
+            haveSurveyShift = true;
         } else if (a == "--per-event") {
             perEvent = true;
         } else if (a == "--peek" || a.rfind("--peek=", 0) == 0) {
@@ -410,6 +436,14 @@ int main(int argc, char **argv)
         std::cerr << "--survey-planes is valid only together with --survey" << std::endl;
         return -1;
     }
+    if (haveSurveyShift && !haveSurvey) {
+        std::cerr << "--survey-shift is valid only together with --survey" << std::endl;
+        return -1;
+    }
+    if (haveShiftRadius && !haveSurveyShift) {
+        std::cerr << "--survey-shift-radius is valid only together with --survey-shift" << std::endl;
+        return -1;
+    }
     if (haveSurvey) {
         const char *bad = haveUnpack ? "--unpack" : haveRepack ? "--repack" : haveVerify ? "--verify-repack" : mergeN > 0 ? "--merge"
                           : debug_mode ? "--debug" : perEvent ? "--per-event" : event_user >= 0 ? "-e/--event" : havePeek ? "--peek"
@@ -424,6 +458,10 @@ int main(int argc, char **argv)
         }
         if (haveSurveyPlanes && surveyPlanesDir.empty()) {
             std::cerr << "--survey-planes needs the directory to write to" << std::endl;
+            return -1;
+        }
+        if (haveSurveyShift && surveyShiftFile.empty()) {
+            std::cerr << "--survey-shift needs the file to write to" << std::endl;
             return -1;
         }
     }
@@ -600,6 +638,11 @@ int main(int argc, char **argv)
             planes.dir = surveyPlanesDir + "/" + run_number;
             planes.srcRunDir = zipped ? std::string() : sp.eventDir;
         }
+        abub::SurveyShift shift;
+        if (haveSurveyShift) {
+            shift.path = surveyShiftFile;
+            shift.radius = surveyShiftRadius;
+        }
         int rc = 1;
         try {
             abub::PreparedRun prep = abub::PrepareRun(sp, po, 0, nullptr, false);
@@ -608,9 +651,9 @@ int main(int argc, char **argv)
             if (prep.rc)
                 printf("survey: a camera did not train: the report has no model columns for it\n");
             rc = surveyGpu ? abub::SurveyRunDevice(prep.parser.get(), prep.trainers, sp.numCams, sp.imageFormat, surveyFile, poolThreads(), 0,
-                                                   &ss, nullptr, nullptr, planes)
+                                                   &ss, nullptr, nullptr, planes, shift)
                            : abub::SurveyRun(prep.parser.get(), prep.trainers, sp.numCams, sp.imageFormat, surveyFile, poolThreads(), &ss,
-                                             nullptr, nullptr, planes);
+                                             nullptr, nullptr, planes, shift);
         } catch (std::exception &e) {
             std::cerr << "survey failed: " << e.what() << std::endl;
             return -6;
@@ -638,6 +681,10 @@ int main(int argc, char **argv)
             printf("survey-planes: %s: %lld rows added on the GPU, %lld on the host; activity launches %.3f s, copy back %.3f s, files "
                    "%.3f s\n",
                    planes.dir.c_str(), ss.planeRowsKernel, ss.planeRowsHost, ss.activity_s, ss.planes_copy_s, ss.planes_write_s);
+        if (haveSurveyShift)
+            printf("survey-shift: %s: radius %d, %lld frames searched on the GPU in %d launches, %lld on the host; shift leg %.3f s, host "
+                   "threads %.3f s\n",
+                   shift.path.c_str(), shift.radius, ss.shiftFramesKernel, ss.shiftLaunches, ss.shiftFramesHost, ss.shift_s, ss.shiftHost_s);
         return rc;
     }
     if (haveList) {

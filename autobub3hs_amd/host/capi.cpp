@@ -401,8 +401,13 @@ const char *abh_run_verify_report(void *src)
 // abh_run_survey_planes[_dev]: the same with the per-pixel planes written to planes_dir (abub::SurveyPlanes::dir, the CLI's
 // DIR/<run_ID>; NULL or empty: none) and plane_stats (may be NULL, 5 values): [rows added to the planes by
 // abub_pixel_activity_dev, rows added by a host thread, seconds of the activity launches, of the copy back, of the files].
+// abh_run_survey_shift[_dev]: the same with the shift search (abub::SurveyShift; DESIGN section 3, "Surveying a run for
+// movement") written to shift_path (NULL or empty: none) at radius shift_radius (1 to 8), and shift_stats (may be NULL, 5
+// values): [frames searched by abub_frame_shift_dev, by a host thread, the kernel's calls, seconds of the device route's shift
+// leg, seconds the host threads spent in frameShiftHost].
 static int runSurvey(void *r, const char *path, int ncams, int nthreads, int device, bool onDevice, double *stats, char *report,
-                     int report_cap, const char *planes_dir = nullptr, double *plane_stats = nullptr)
+                     int report_cap, const char *planes_dir = nullptr, double *plane_stats = nullptr, const char *shift_path = nullptr,
+                     int shift_radius = 4, double *shift_stats = nullptr)
 {
     Run *run = (Run *)r;
     try {
@@ -428,10 +433,17 @@ static int runSurvey(void *r, const char *path, int ncams, int nthreads, int dev
         abub::SurveyPlanes planes;
         planes.dir = planes_dir ? planes_dir : "";
         planes.srcRunDir = run->kind == 0 ? run->runFolder : std::string();
+        abub::SurveyShift shift;
+        shift.path = shift_path ? shift_path : "";
+        shift.radius = shift_radius;
         const int rc = onDevice ? abub::SurveyRunDevice(pr.parser.get(), pr.trainers, ncams, sp.imageFormat, to, std::max(1, nthreads),
-                                                        device, &st, &rows, &models, planes)
+                                                        device, &st, &rows, &models, planes, shift)
                                 : abub::SurveyRun(pr.parser.get(), pr.trainers, ncams, sp.imageFormat, to, std::max(1, nthreads), &st,
-                                                  &rows, &models, planes);
+                                                  &rows, &models, planes, shift);
+        if (shift_stats) {
+            const double v[5] = {(double)st.shiftFramesKernel, (double)st.shiftFramesHost, (double)st.shiftLaunches, st.shift_s, st.shiftHost_s};
+            std::memcpy(shift_stats, v, sizeof v);
+        }
         if (plane_stats) {
             const double v[5] = {(double)st.planeRowsKernel, (double)st.planeRowsHost, st.activity_s, st.planes_copy_s, st.planes_write_s};
             std::memcpy(plane_stats, v, sizeof v);
@@ -478,6 +490,19 @@ int abh_run_survey_planes_dev(void *r, const char *path, const char *planes_dir,
 {
     return runSurvey(r, path, ncams, nthreads, device, true, stats, report, report_cap, planes_dir, plane_stats);
 }
+int abh_run_survey_shift(void *r, const char *path, const char *planes_dir, const char *shift_path, int shift_radius, int ncams,
+                         int nthreads, double *stats, double *plane_stats, double *shift_stats, char *report, int report_cap)
+{
+    return runSurvey(r, path, ncams, nthreads, -1, false, stats, report, report_cap, planes_dir, plane_stats, shift_path, shift_radius,
+                     shift_stats);
+}
+int abh_run_survey_shift_dev(void *r, const char *path, const char *planes_dir, const char *shift_path, int shift_radius, int ncams,
+                             int nthreads, int device, double *stats, double *plane_stats, double *shift_stats, char *report,
+                             int report_cap)
+{
+    return runSurvey(r, path, ncams, nthreads, device, true, stats, report, report_cap, planes_dir, plane_stats, shift_path, shift_radius,
+                     shift_stats);
+}
 // the whole report of the last abh_run_survey[_dev] on the run (valid until the next query on it)
 const char *abh_run_survey_report(void *r)
 {
@@ -496,6 +521,24 @@ void abh_frame_stats_host(const uint8_t *cur, const uint8_t *ref, const uint8_t 
 void abh_activity_add_host(uint32_t *planes, const uint8_t *cur, const uint8_t *ref, const uint8_t *mu, const uint8_t *sigma6, uint64_t n)
 {
     abub::activityAddHost(planes, cur, ref, mu, sigma6, (size_t)n);
+}
+
+// abub::frameShiftHost on raw buffers: the W x H frame p against the model plane m at radius R -> sad[(2 R + 1)^2]; returns 0,
+// or -1 (nothing written) for a null pointer, R outside [1, 8] or a side below 2 R + 1
+int abh_frame_shift_host(const uint8_t *p, const uint8_t *m, int W, int H, int R, uint64_t *sad)
+{
+    if (!p || !m || !sad || R < 1 || R > 8 || W < 2 * R + 1 || H < 2 * R + 1)
+        return -1;
+    abub::frameShiftHost(p, m, W, H, R, sad);
+    return 0;
+}
+// abub::shiftBest of a surface of radius R: out[3] = [dx, dy, at_edge]
+void abh_shift_best(const uint64_t *sad, int R, int *out)
+{
+    const abub::ShiftBest b = abub::shiftBest(sad, R);
+    out[0] = b.dx;
+    out[1] = b.dy;
+    out[2] = b.atEdge ? 1 : 0;
 }
 
 // bmpWalk (host/bmpwalk.hpp: what the reading threads learn about a BMP before the GPU decodes it): 1 = a file decodeBMP

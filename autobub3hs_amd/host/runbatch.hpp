@@ -217,6 +217,20 @@ FrameStats frameStatsHost(const unsigned char *cur, const unsigned char *ref, co
 // the host route, the device route's host share and the tests use it.
 void activityAddHost(uint32_t *planes, const unsigned char *cur, const unsigned char *ref, const unsigned char *mu,
                      const unsigned char *sigma6, size_t n);
+// The definition of abub_frame_shift_dev ("Surveying a run for movement"): the SAD between the W x H frame
+// p and the model plane m at every integer displacement within R, 1 <= R <= 8, W and H >= 2 R + 1.  Over the interior
+// I = [R, W - R) x [R, H - R): sad[(dy + R) * (2 R + 1) + (dx + R)] = sum over I of |p(x + dx, y + dy) - m(x, y)|; every
+// displacement sums the same |I| pixels.  Plain loops, the one copy: both survey routes and the tests use it.
+void frameShiftHost(const unsigned char *p, const unsigned char *m, int W, int H, int R, uint64_t *sad);
+// What a surface says: the displacement with the smallest sad; among equal ones the smaller dx^2 + dy^2, then the smaller
+// dy, then the smaller dx (an all-equal surface gives (0, 0)).  atEdge: |dx| == R or |dy| == R, the true shift may be
+// larger.  One host function for both routes: the kernel returns only the surface, so they cannot disagree on a tie.
+struct ShiftBest {
+    int dx = 0, dy = 0;
+    bool atEdge = false;
+    uint64_t sad0 = 0, sadBest = 0; // the surface at (0, 0) and at (dx, dy)
+};
+ShiftBest shiftBest(const uint64_t *sad, int R);
 
 // One row of a survey: a frame the run lists, or one it should list (missing)
 struct SurveyRow {
@@ -227,6 +241,8 @@ struct SurveyRow {
     int state = Ok, w = 0, h = 0; // w, h: of Ok and OtherSize rows
     FrameStats s;            // Ok: all of it, as far as its flags say; OtherSize: the raw columns
     bool onKernel = false;
+    bool hasShift = false, shiftOnKernel = false; // with a shift file: an ok row of a camera with a model has its surface's answer
+    ShiftBest shift;
     const char *stateName() const; // "ok", "undecodable", "missing", "other_size"
 };
 // What the report says of one camera's model
@@ -252,6 +268,12 @@ struct SurveyStats {
     // seconds of the activity launches, of the planes' copy back and of writing the files
     long long planeRowsKernel = 0, planeRowsHost = 0;
     double activity_s = 0, planes_copy_s = 0, planes_write_s = 0;
+    // With a shift file: the rows whose surface abub_frame_shift_dev made and those frameShiftHost made, the kernel's calls,
+    // the seconds of the device route's shift leg (upload of the jobs, launches, copy back) and the seconds the host threads
+    // spent in frameShiftHost, summed over the threads
+    long long shiftFramesKernel = 0, shiftFramesHost = 0;
+    int shiftLaunches = 0;
+    double shift_s = 0, shiftHost_s = 0;
 };
 // Where a survey writes its per-pixel activity planes (abub3hs --survey-planes; DESIGN section 3, "Surveying a run per
 // pixel"): the directory `dir` (the CLI's DIR/<run_ID>; empty: no planes) gets cam<c>_activity.npy (u32 [6, H, W]) for
@@ -260,6 +282,16 @@ struct SurveyStats {
 struct SurveyPlanes {
     std::string dir, srcRunDir;
 };
+// Where a survey writes its shift file (abub3hs --survey-shift; DESIGN section 3, "Surveying a run for movement"): per ok
+// row of a camera with a model the best displacement of the frame against mu within `radius` (path empty: no shift search).
+// A run narrower or lower than 2 radius + 1 is refused before its frames are measured.
+struct SurveyShift {
+    std::string path;
+    int radius = 4;
+};
+// The shift file's text: "# abub3hs shift 1", `radius R`, the table's header and one tab-separated row per survey row, one
+// `shift cam` line per camera, the `run` line.  Both routes write it through this one function.
+std::string ShiftReport(int radius, const std::vector<SurveyModel> &models, const std::vector<SurveyRow> &rows);
 // The report's text ("Surveying a run"): "# abub3hs survey 1", one `model` line per camera, the table's
 // header and one tab-separated row per frame, the `run` line.  Both routes write it through this one function.
 std::string SurveyReport(const std::vector<SurveyModel> &models, const std::vector<SurveyRow> &rows);
@@ -272,9 +304,13 @@ std::string SurveyReport(const std::vector<SurveyModel> &models, const std::vect
 // not ok.  The report goes to reportPath (empty: it is not written).  No GPU.  Returns 0, or 1 if any frame is not ok;
 // throws where the report cannot be written.
 // With planes.dir the rows are also summed per pixel and camera and the planes' files are written (both routes: the same bytes).
+// With shift.path every ok row of a camera with a model is also searched for its displacement against mu (frameShiftHost
+// here; on the device route abub_frame_shift_dev for the rows in place in the slab, one call per batch behind the statistics
+// launch) and the shift file is written (both routes: the same bytes).  The report and the planes do not change.
 int SurveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCams, const std::string &imageFormat,
               const std::string &reportPath, int nthreads, SurveyStats *stats, std::vector<SurveyRow> *rows,
-              std::vector<SurveyModel> *models = nullptr, const SurveyPlanes &planes = SurveyPlanes());
+              std::vector<SurveyModel> *models = nullptr, const SurveyPlanes &planes = SurveyPlanes(),
+              const SurveyShift &shift = SurveyShift());
 // abub3hs --survey FILE --survey-gpu: the same rows and the same report, byte for byte.  The frames are read through the
 // FileBatch protocol (framefiles.hpp) in batches of at most 4 frames per CU (ABUB_SURVEY_BATCH=n: of n), decoded into the
 // batch's slab, and measured by one abub_frame_stats_dev launch per batch.  A batch that begins inside a stack reads again
@@ -284,7 +320,8 @@ int SurveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCam
 // frame that decodes, goes the host route whole.  Throws, before anything else, when there is no such device.
 int SurveyRunDevice(Parser *parser, const std::vector<Trainer *> &trainers, int numCams, const std::string &imageFormat,
                     const std::string &reportPath, int nthreads, int device, SurveyStats *stats, std::vector<SurveyRow> *rows,
-                    std::vector<SurveyModel> *models = nullptr, const SurveyPlanes &planes = SurveyPlanes());
+                    std::vector<SurveyModel> *models = nullptr, const SurveyPlanes &planes = SurveyPlanes(),
+                    const SurveyShift &shift = SurveyShift());
 
 // A run listed and trained, ready for detect; rc = -5 (the run cannot be read) or -7 (a camera did not train)
 struct PreparedRun {

@@ -9,6 +9,10 @@
 // pixel and camera: activityAddHost is the definition, a host thread adds its row into the camera's one set of planes with
 // relaxed atomic adds, the device route adds the rows in place in the slab with abub_pixel_activity_dev and keeps its planes
 // on the device until the end; the result is their sum, and one writer puts the files on disk for both routes.
+// With a shift file (--survey-shift; DESIGN section 3, "Surveying a run for movement") the ok rows of a camera with a model
+// are also searched for their displacement against mu: frameShiftHost is the definition of the SAD surface, the device route
+// gets the surfaces of the rows in place in the slab from abub_frame_shift_dev, shiftBest reads every surface on the host,
+// and one writer (ShiftReport) makes the file for both routes.
 #include <algorithm>
 #include <cinttypes>
 #include <cmath>
@@ -88,6 +92,95 @@ void activityAddHost(uint32_t *planes, const unsigned char *cur, const unsigned 
         add(4, i, moved > 0);
         add(5, i, (uint32_t)moved);
     }
+}
+
+void frameShiftHost(const unsigned char *p, const unsigned char *m, int W, int H, int R, uint64_t *sad)
+{
+    const int D = 2 * R + 1;
+    for (int dy = -R; dy <= R; ++dy)
+        for (int dx = -R; dx <= R; ++dx) {
+            uint64_t s = 0;
+            for (int y = R; y < H - R; ++y) {
+                const unsigned char *pr = p + (size_t)(y + dy) * W + dx, *mr = m + (size_t)y * W;
+                uint32_t row = 0; // (at most 65535 * 255)
+                for (int x = R; x < W - R; ++x)
+                    row += (uint32_t)std::abs((int)pr[x] - (int)mr[x]);
+                s += row;
+            }
+            sad[(size_t)(dy + R) * D + (dx + R)] = s;
+        }
+}
+
+ShiftBest shiftBest(const uint64_t *sad, int R)
+{
+    const int D = 2 * R + 1;
+    ShiftBest b;
+    b.sad0 = b.sadBest = sad[(size_t)R * D + R];
+    for (int dy = -R; dy <= R; ++dy) // (in the tie rule's last two orders: a later equal one wins only when it is nearer)
+        for (int dx = -R; dx <= R; ++dx) {
+            const uint64_t v = sad[(size_t)(dy + R) * D + (dx + R)];
+            if (v < b.sadBest || (v == b.sadBest && dx * dx + dy * dy < b.dx * b.dx + b.dy * b.dy)) {
+                b.sadBest = v;
+                b.dx = dx;
+                b.dy = dy;
+            }
+        }
+    b.atEdge = std::abs(b.dx) == R || std::abs(b.dy) == R;
+    return b;
+}
+
+std::string ShiftReport(int radius, const std::vector<SurveyModel> &models, const std::vector<SurveyRow> &rows)
+{
+    std::string text = "# abub3hs shift 1\n";
+    char buf[512];
+    snprintf(buf, sizeof buf, "radius %d\n", radius);
+    text += buf;
+    text += "event\tcam\tframe\tname\tstate\tdx\tdy\tat_edge\tsad0\tsad_best\tgain\n";
+    struct Cam {
+        long long frames = 0, atZero = 0, shifted = 0, atEdge = 0;
+        int maxDx = 0, maxDy = 0;
+        const std::string *first = nullptr;
+    };
+    std::vector<Cam> cams(models.size());
+    for (const SurveyRow &r : rows) {
+        snprintf(buf, sizeof buf, "%s\t%d\t%d\t%s\t%s", r.event.c_str(), r.cam, r.frame, r.name.c_str(), r.stateName());
+        text += buf;
+        if (r.state != SurveyRow::Ok || !r.hasShift) {
+            text += "\t-\t-\t-\t-\t-\t-\n";
+            continue;
+        }
+        const ShiftBest &b = r.shift;
+        const double gain = b.sad0 ? 1.0 - (double)b.sadBest / (double)b.sad0 : 0.0;
+        snprintf(buf, sizeof buf, "\t%d\t%d\t%d\t%" PRIu64 "\t%" PRIu64 "\t%.6f\n", b.dx, b.dy, b.atEdge ? 1 : 0, b.sad0, b.sadBest, gain);
+        text += buf;
+        Cam &c = cams[(size_t)r.cam];
+        ++c.frames;
+        const bool moved = b.dx != 0 || b.dy != 0;
+        ++(moved ? c.shifted : c.atZero);
+        c.atEdge += b.atEdge;
+        c.maxDx = std::max(c.maxDx, std::abs(b.dx));
+        c.maxDy = std::max(c.maxDy, std::abs(b.dy));
+        if (moved && !c.first)
+            c.first = &r.event;
+    }
+    long long frames = 0, shifted = 0, atEdge = 0;
+    for (size_t c = 0; c < cams.size(); ++c) {
+        if (!models[c].trained) {
+            snprintf(buf, sizeof buf, "shift cam %zu none\n", c);
+            text += buf;
+            continue;
+        }
+        const Cam &k = cams[c];
+        snprintf(buf, sizeof buf, "shift cam %zu frames %lld at_zero %lld shifted %lld at_edge %lld max_abs_dx %d max_abs_dy %d first_shifted_event %s\n",
+                 c, k.frames, k.atZero, k.shifted, k.atEdge, k.maxDx, k.maxDy, k.first ? k.first->c_str() : "-");
+        text += buf;
+        frames += k.frames;
+        shifted += k.shifted;
+        atEdge += k.atEdge;
+    }
+    snprintf(buf, sizeof buf, "run frames %lld shifted %lld at_edge %lld\n", frames, shifted, atEdge);
+    text += buf;
+    return text;
 }
 
 const char *SurveyRow::stateName() const
@@ -184,6 +277,8 @@ struct HostPlanes {
 // The part of a survey that is not its frames' pixels
 struct Plan {
     HostPlanes *planes = nullptr;   // with a planes directory: where surveyFrame adds its ok rows
+    int shiftR = 0;                 // with a shift file: the radius surveyFrame searches its ok rows with a model in (0: none)
+    std::atomic<long long> *shiftHostUs = nullptr; // ... and where it adds the microseconds it spent in frameShiftHost
     std::vector<std::string> events;
     std::vector<SurveyRow> rows;    // in event, camera and frame order
     std::vector<size_t> ref;        // ref[i]: the row frame i is measured against (frame max(i - 2, 0) of its stack)
@@ -303,11 +398,26 @@ cv::Mat decodeRow(Parser &p, const Plan &pl, size_t i)
     return file.empty() ? cv::Mat() : cv::imdecode(file.data(), file.size(), 0);
 }
 
+// The shift search of an ok row of a camera with a model on this thread: the definition, then the one tie rule
+void shiftRowHost(const Plan &pl, const uint8_t *cur, const uint8_t *mu, SurveyRow &row)
+{
+    const double t0 = nowMs();
+    const size_t D = 2 * (size_t)pl.shiftR + 1;
+    std::vector<uint64_t> sad(D * D);
+    frameShiftHost(cur, mu, pl.W, pl.H, pl.shiftR, sad.data());
+    row.shift = shiftBest(sad.data(), pl.shiftR);
+    row.hasShift = true;
+    row.shiftOnKernel = false;
+    if (pl.shiftHostUs)
+        *pl.shiftHostUs += (long long)((nowMs() - t0) * 1e3);
+}
+
 // The host route's per-frame function: row i on this thread, its state and its record.  It asks nothing of the other rows:
 // the reference frame is decoded here as well, and is there iff its own row is ok
 void surveyFrame(Parser &p, const Plan &pl, size_t i, SurveyRow &row)
 {
     row.onKernel = false;
+    row.hasShift = row.shiftOnKernel = false;
     row.s = FrameStats();
     row.w = row.h = 0;
     if (row.state == SurveyRow::Missing)
@@ -338,6 +448,8 @@ void surveyFrame(Parser &p, const Plan &pl, size_t i, SurveyRow &row)
     row.s = frameStatsHost(cur.data, r, mu, mu ? pl.sigma6[row.cam].data() : nullptr, n);
     if (pl.planes)
         pl.planes->add(row.cam, cur.data, r, mu, mu ? pl.sigma6[row.cam].data() : nullptr);
+    if (pl.shiftR && mu)
+        shiftRowHost(pl, cur.data, mu, row);
 }
 
 void hostFrames(Parser *parser, Plan &pl, int nthreads)
@@ -370,6 +482,10 @@ FrameStats fromRecord(const abub_stat_result &r)
 // abub_pixel_activity_dev call per camera that has rows in place, its jobs behind the records in the same meta buffer; they
 // come back in one copy at the end, into devPlanes.  A row in place whose file no GPU decoder reads was decoded by a reading
 // thread; its pixels are on the host, and it is added to the host planes there, not by the kernel.
+// With pl.shiftR the rows in place that have a model are also searched for their displacement, behind the statistics launch
+// and on the same stream: one abub_frame_shift_dev call per batch over [jobs][status words][surfaces] in a buffer of its own
+// (mu is resident already), the surfaces back in one copy; shiftBest on the host says what each means.  Every row in place
+// is in the slab, whichever decoder or thread put it there, so all of them are the kernel's.
 void deviceFrames(Parser *parser, Plan &pl, int nthreads, int device, SurveyStats &st, std::vector<uint32_t> &devPlanes)
 {
     HIPOK(hipSetDevice(device));
@@ -381,8 +497,8 @@ void deviceFrames(Parser *parser, Plan &pl, int nthreads, int device, SurveyStat
     const size_t P = (size_t)W * H, stride = (P + 15) & ~(size_t)15, C = pl.mu.size();
     FileBatch B;
     B.sizer.reset(parser->clone());
-    PinnedBuffer h_meta;
-    DeviceBuffer d_meta, d_model; // d_model: [mu of every camera][sigma6 of every camera], camera c at c * stride
+    PinnedBuffer h_meta, h_shift;
+    DeviceBuffer d_meta, d_shift, d_model; // d_model: [mu of every camera][sigma6 of every camera], camera c at c * stride
     Stream stream;
     hipStream_t cs = stream.get();
     bool anyModel = false;
@@ -477,6 +593,43 @@ void deviceFrames(Parser *parser, Plan &pl, int nthreads, int device, SurveyStat
                   "abub_frame_stats_dev");
             HIPOK(hipMemcpyAsync(h_meta.get() + nj * sizeof(abub_stat_job), d_res, nj * sizeof(abub_stat_result), hipMemcpyDeviceToHost, cs));
             HIPOK(hipStreamSynchronize(cs));
+            if (pl.shiftR) {
+                st.stats_s += (nowMs() - t0) * 1e-3;
+                t0 = nowMs();
+                std::vector<size_t> with; // the jobs that have a model
+                for (size_t g = 0; g < nj; ++g)
+                    if (jobs[g].model != UINT64_MAX)
+                        with.push_back(g);
+                const size_t ns = with.size(), N = (2 * (size_t)pl.shiftR + 1) * (2 * (size_t)pl.shiftR + 1);
+                if (ns) {
+                    const size_t jobBytes = ns * sizeof(abub_shift_job), statusBytes = (ns * sizeof(uint32_t) + 7) & ~(size_t)7;
+                    const size_t bytes = jobBytes + statusBytes + ns * N * sizeof(uint64_t);
+                    h_shift.grow(bytes);
+                    d_shift.grow(bytes);
+                    abub_shift_job *sj = (abub_shift_job *)h_shift.get();
+                    for (size_t q = 0; q < ns; ++q)
+                        sj[q] = abub_shift_job{jobs[with[q]].cur, jobs[with[q]].model};
+                    HIPOK(hipMemcpyAsync(d_shift.get(), h_shift.get(), jobBytes, hipMemcpyHostToDevice, cs));
+                    check(abub_frame_shift_dev(B.slab.get(), slots * stride, d_model.get(), C * stride, (const abub_shift_job *)d_shift.get(),
+                                               (int)ns, W, H, pl.shiftR, (uint32_t *)(d_shift.get() + jobBytes),
+                                               (uint64_t *)(d_shift.get() + jobBytes + statusBytes), cs),
+                          "abub_frame_shift_dev");
+                    HIPOK(hipMemcpyAsync(h_shift.get() + jobBytes, d_shift.get() + jobBytes, bytes - jobBytes, hipMemcpyDeviceToHost, cs));
+                    HIPOK(hipStreamSynchronize(cs));
+                    const uint32_t *status = (const uint32_t *)(h_shift.get() + jobBytes);
+                    const uint64_t *sad = (const uint64_t *)(h_shift.get() + jobBytes + statusBytes);
+                    for (size_t q = 0; q < ns; ++q) {
+                        if (status[q] != 0)
+                            throw std::runtime_error("survey: abub_frame_shift_dev refused a frame of its own slab");
+                        SurveyRow &row = pl.rows[rowOf(slot[with[q]])];
+                        row.shift = shiftBest(sad + q * N, pl.shiftR);
+                        row.hasShift = row.shiftOnKernel = true;
+                    }
+                    ++st.shiftLaunches;
+                }
+                st.shift_s += (nowMs() - t0) * 1e-3;
+                t0 = nowMs();
+            }
             if (wantPlanes) {
                 st.stats_s += (nowMs() - t0) * 1e-3;
                 t0 = nowMs();
@@ -686,7 +839,7 @@ bool sameDirectory(const std::string &path, const std::string &other)
 
 int surveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCams, const std::string &format,
               const std::string &reportPath, int nthreads, int device, SurveyStats *stats, std::vector<SurveyRow> *rows,
-              std::vector<SurveyModel> *models, const SurveyPlanes &planes)
+              std::vector<SurveyModel> *models, const SurveyPlanes &planes, const SurveyShift &shift)
 {
     const double t0 = nowMs();
     SurveyStats st;
@@ -696,7 +849,19 @@ int surveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCam
     // (the planes' files have names of their own, but a run directory is not the place for what was derived from it)
     if (!planesDir.empty() && sameDirectory(trimSlashes(planes.srcRunDir), planesDir))
         throw std::runtime_error("survey: " + planesDir + " is the run that is being read");
+    if (!shift.path.empty() && (shift.radius < 1 || shift.radius > 8))
+        throw std::runtime_error("survey: the shift radius must be in [1, 8], not " + std::to_string(shift.radius));
     Plan pl = planRun(parser, trainers, numCams, format);
+    std::atomic<long long> shiftHostUs{0};
+    if (!shift.path.empty()) {
+        const int need = 2 * shift.radius + 1;
+        if (pl.W > 0 && (pl.W < need || pl.H < need))
+            throw std::runtime_error("survey: a shift search at radius " + std::to_string(shift.radius) + " needs frames of at least " +
+                                     std::to_string(need) + "x" + std::to_string(need) + ", the run's are " + std::to_string(pl.W) + "x" +
+                                     std::to_string(pl.H));
+        pl.shiftR = shift.radius;
+        pl.shiftHostUs = &shiftHostUs;
+    }
     std::unique_ptr<HostPlanes> hostPlanes;
     std::vector<uint32_t> devPlanes;
     if (!planesDir.empty()) {
@@ -712,7 +877,8 @@ int surveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCam
     st.H = pl.H;
     for (const SurveyModel &m : pl.models)
         st.modelCams += m.trained;
-    if (device >= 0 && pl.W > 0 && decodersTakeWidth(pl.W)) {
+    // (abub_frame_shift_dev takes sides of up to 65535: a larger run with a shift file is the host route's whole)
+    if (device >= 0 && pl.W > 0 && decodersTakeWidth(pl.W) && (!pl.shiftR || (pl.W <= 65535 && pl.H <= 65535))) {
         st.device = device;
         deviceFrames(parser, pl, nthreads, device, st, devPlanes);
     } else
@@ -722,11 +888,19 @@ int surveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCam
         ++*counter[r.state];
         ++st.frames;
         ++(r.onKernel ? st.framesKernel : st.framesHostRoute);
+        if (r.state == SurveyRow::Ok && r.hasShift)
+            ++(r.shiftOnKernel ? st.shiftFramesKernel : st.shiftFramesHost);
     }
+    st.shiftHost_s = (double)shiftHostUs * 1e-6;
     if (!reportPath.empty()) {
         const std::string text = SurveyReport(pl.models, pl.rows);
         if (!writeFile(reportPath, (const unsigned char *)text.data(), text.size()))
             throw std::runtime_error("survey: cannot write " + reportPath);
+    }
+    if (!shift.path.empty()) {
+        const std::string text = ShiftReport(shift.radius, pl.models, pl.rows);
+        if (!writeFile(shift.path, (const unsigned char *)text.data(), text.size()))
+            throw std::runtime_error("survey: cannot write " + shift.path);
     }
     if (hostPlanes) {
         const double t1 = nowMs();
@@ -749,18 +923,18 @@ int surveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCam
 
 int SurveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCams, const std::string &imageFormat,
               const std::string &reportPath, int nthreads, SurveyStats *stats, std::vector<SurveyRow> *rows,
-              std::vector<SurveyModel> *models, const SurveyPlanes &planes)
+              std::vector<SurveyModel> *models, const SurveyPlanes &planes, const SurveyShift &shift)
 {
-    return surveyRun(parser, trainers, numCams, imageFormat, reportPath, nthreads, -1, stats, rows, models, planes);
+    return surveyRun(parser, trainers, numCams, imageFormat, reportPath, nthreads, -1, stats, rows, models, planes, shift);
 }
 
 int SurveyRunDevice(Parser *parser, const std::vector<Trainer *> &trainers, int numCams, const std::string &imageFormat,
                     const std::string &reportPath, int nthreads, int device, SurveyStats *stats, std::vector<SurveyRow> *rows,
-                    std::vector<SurveyModel> *models, const SurveyPlanes &planes)
+                    std::vector<SurveyModel> *models, const SurveyPlanes &planes, const SurveyShift &shift)
 {
     if (device < 0)
         throw std::runtime_error("survey: no such HIP device: " + std::to_string(device));
-    return surveyRun(parser, trainers, numCams, imageFormat, reportPath, nthreads, device, stats, rows, models, planes);
+    return surveyRun(parser, trainers, numCams, imageFormat, reportPath, nthreads, device, stats, rows, models, planes, shift);
 }
 
 } // namespace abub

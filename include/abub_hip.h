@@ -829,6 +829,31 @@ int abub_pixel_activity_dev(const uint8_t *frames, size_t frames_bytes, const ui
                             const abub_act_job *jobs, int njobs, size_t frame_bytes, uint32_t *planes, size_t plane_stride,
                             uint32_t *status, void *stream);
 
+/* ---- per-frame shift search of resident frames (abub_stats.hip) -------------------------------------------------------
+ * Did the camera or the chamber image move against the trained model (abub3hs --survey --survey-shift; definition, report
+ * and measurements: DESIGN section 3, "Surveying a run for movement")?  For a batch of resident W x H frames, with p the
+ * frame at frames + jobs[j].cur, m the plane of `mu` at mu + jobs[j].model, a radius R and the interior
+ * I = { (x, y) : R <= x < W - R, R <= y < H - R }, for every -R <= dx, dy <= R
+ *   sad[j * (2R+1)^2 + (dy + R) * (2R+1) + (dx + R)] = sum over (x, y) in I of | p(x + dx, y + dy) - m(x, y) |     (u64).
+ * Every displacement sums over the same |I| pixels; there is no border rule and no sigma term.  Every value is an exact
+ * integer, bit-identical to the host definition (host/survey.cpp frameShiftHost) whatever the order of the jobs or the
+ * blocks: two launches on `stream` (status and a cleared surface, then jobs x tiles of 256 x 64 interior pixels, each
+ * block reading its tile and halo once into LDS, summing v_sad_u8 of byte-shifted dwords on chip and issuing one u64 atomic
+ * add per displacement, which commute), no host synchronisation, no allocation, no workgroup waiting for another.  Which
+ * displacement is the best one is the host's to say (abub::shiftBest, one tie rule for both routes). */
+typedef struct abub_shift_job { uint64_t cur, model; } abub_shift_job;   /* byte offsets into frames / mu */
+#define ABUB_SHIFT_E_RANGE 1
+/* Every pointer is a device pointer; jobs and sad are 8-byte aligned, status 4-byte aligned; R in [1, 8]; W and H in
+ * [2R+1, 65535].  No alignment rule on the offsets: a stream is read through aligned dwords wherever it lies.  status[j] (0
+ * or ABUB_SHIFT_E_RANGE) and all (2R+1)^2 values of sad[j] are written in full by every call with njobs > 0, whatever they
+ * held before, and nothing else is written.  A job whose frame runs past frames_bytes or whose model plane runs past
+ * model_bytes gets ABUB_SHIFT_E_RANGE and a zero surface; nothing of it is read.  Null pointers, njobs < 0, R, W or H out
+ * of range or a misaligned jobs / status / sad: ABUB_E_INVALID before anything touches the device.  njobs == 0: ABUB_OK,
+ * nothing is touched. */
+int abub_frame_shift_dev(const uint8_t *frames, size_t frames_bytes, const uint8_t *mu, size_t model_bytes,
+                         const abub_shift_job *jobs, int njobs, int W, int H, int R,
+                         uint32_t *status /*[njobs]*/, uint64_t *sad /*[njobs * (2R+1)^2]*/, void *stream);
+
 /* ---- the two DebugPeek planes of a batch of resident frames (abub_peek.hip) ------------------------------------------
  * What L3Localizer::CalculateInitialBubbleParams builds on the analyzer's thread for its debug write-out (reference
  * L3Localizer.cpp:252-257, 397, 448; DESIGN section 3, "The peek planes"), for a batch of items.  Per item two W x H u8
