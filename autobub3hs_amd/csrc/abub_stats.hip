@@ -1,6 +1,6 @@
 // abub_stats.hip -- per-frame statistics of resident frames: abub_frame_stats_dev (include/abub_hip.h, DESIGN section 3,
-// "Surveying a run"); below it the per-pixel planes (abub_pixel_activity_dev) and the shift search (abub_frame_shift_dev),
-// each under a header of its own.  What a byte loop over a decoded frame does on a host thread (host/survey.cpp frameStatsHost, the
+// "Surveying a run"); below it the per-pixel planes (abub_pixel_activity_dev), the shift search (abub_frame_shift_dev) and
+// the per-cell shift field (abub_frame_shift_cells_dev), each under a header of its own.  What a byte loop over a decoded frame does on a host thread (host/survey.cpp frameStatsHost, the
 // definition): per job the grey-level range, sum, sum of squares, black and saturated pixels of the frame, and against a
 // model (mu, sigma6) and a reference frame the count and sum of sat(|p - m| - s) and of sat(|p - r| - s).
 //
@@ -760,6 +760,183 @@ extern "C" int abub_frame_shift_dev(const uint8_t *frames, size_t frames_bytes, 
     static const Launch launch[8] = {shift_launch<1>, shift_launch<2>, shift_launch<3>, shift_launch<4>,
                                      shift_launch<5>, shift_launch<6>, shift_launch<7>, shift_launch<8>};
     launch[R - 1](grid, st, frames, (uint64_t)frames_bytes, mu, (uint64_t)model_bytes, jobs, njobs, (uint32_t)W, (uint32_t)H, tiles_x, sad);
+    HIPCHK(hipGetLastError());
+    return ABUB_OK;
+}
+
+// ---- per-cell shift field: abub_frame_shift_cells_dev ("Surveying a run for local movement") ------------
+// The same sums as above, kept apart per cell of FC_CELL x FC_CELL interior pixels (host/survey.cpp fieldCellsHost, the
+// definition): with (ncx, ncy, x0, y0) = abub_frame_cells_grid(W, H, R), for cell (cx, cy)
+//   sad[((j ncy + cy) ncx + cx) (2 R + 1)^2 + (dy + R) (2 R + 1) + (dx + R)] = sum of |p(x + dx, y + dy) - m(x, y)|
+// over x0 + 128 cx <= x < x0 + 128 (cx + 1), y0 + 128 cy <= y < y0 + 128 (cy + 1).  Only whole cells exist.
+//
+// The grid is cells x jobs; a block of four waves owns one cell of one job at a time and with it the (2 R + 1)^2 words of
+// its surface: it writes each of them once with a plain store, so there is no atomic, no clearing launch and no other
+// launch (the block of cell 0 writes the job's status word).  It reads the cell with its halo of R pixels on every side
+// once into LDS, 128 + 2 R rows of RS = 32 + ND - 1 dwords (row r, dword c: the four pixels from (xc - R + 4 c, yc - R + r)
+// on).  A cell is 32 dwords wide, so the 64 lanes of a wave span two cell rows: lane l owns dword l & 31 of the rows
+// 8 k + 2 w + (l >> 5), k < 16 (w: its wave), and holds their mu dwords in registers.  The two halves of a wave are the two
+// lane groups of a ds_read_b32 / ds_read2_b32 (banks mod 32), and within a half the lanes read 32 consecutive dwords of
+// one row: no bank conflict at any RS.  The arithmetic is sh_tile's full-tile path: per dy 2 R + 1 sums in registers, from
+// R = 2 on four dx at a time with v_qsad_pk_u16_u8 (a lane adds at most 16 rows * 4 * 255 = 16320 into a u16), the rest
+// with v_alignbyte_b32 and v_sad_u8; summed over the wave with shuffles, over the waves through LDS.  A surface entry sums
+// 16384 pixels: at most 16384 * 255 < 2^32.
+//
+// Bounds.  A job is read only if sh_job_ok holds; otherwise E_RANGE and a zero surface, found alike by every block of the
+// job.  A cell with its halo lies inside the frame (x0 >= R, x0 + 128 ncx + R <= W, and so in y), and the last dword of a
+// tile row ends at byte 4 RS >= 128 + 2 R of it, at most 3 bytes behind the halo: sh_load4 tests the index itself against
+// W * H, a byte beyond reads as 0, and no lane uses a byte behind the halo (its last is 4 * 31 + 2 R + 3).  LDS: row
+// < 128 + 2 R, dword < RS.  Stores: status[j] and sad[(j * cells + cell) * N + t], j < njobs, cell < cells, t < N.
+namespace {
+
+#define FC_CELL ((uint32_t)ABUB_FIELD_CELL)
+#define FC_ROWS (FC_CELL / (2u * (FR_THREADS / 64))) /* rows of a cell per lane: 16 */
+static_assert(FC_CELL == 128u && FC_ROWS == SH_ROWS, "a wave spans two rows of 32 dwords; the u16 bound is that of sh_tile");
+
+template <int R>
+__device__ __forceinline__ void fc_cell(const uint32_t *tile, const uint32_t (&m)[FC_ROWS], uint32_t (*part)[(2 * R + 1) * (2 * R + 1)])
+{
+    constexpr int D = 2 * R + 1, ND = (2 * R + 4 + 3) / 4, RS = FC_CELL / 4 + ND - 1;
+    constexpr int NQ = R >= 2 ? ND - 1 : 0; // (as k_shift chose: the quad form from R = 2 on)
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t first = 2u * wave + (lane >> 5), col = lane & 31u;
+#pragma unroll 1
+    for (int dy = 0; dy < D; ++dy) {
+        uint32_t acc[D];
+#pragma unroll
+        for (int o = 0; o < D; ++o)
+            acc[o] = 0;
+        uint64_t qacc[NQ ? NQ : 1] = {};
+#pragma unroll
+        for (uint32_t r = 0; r < FC_ROWS; ++r) {
+            const uint32_t *src = tile + (r * 8u + first + (uint32_t)dy) * RS + col;
+            uint32_t d[ND];
+#pragma unroll
+            for (int k = 0; k < ND; ++k)
+                d[k] = src[k];
+#pragma unroll
+            for (int g = 0; g < NQ; ++g)
+                qacc[g] = __builtin_amdgcn_qsad_pk_u16_u8((uint64_t)d[g] | (uint64_t)d[g + 1] << 32, m[r], qacc[g]);
+#pragma unroll
+            for (int o = 4 * NQ; o < D; ++o) {
+                uint32_t a = d[o >> 2]; // the four pixels at dx = o - R: bytes o .. o + 3 of what the lane read
+                if (o & 3)
+                    a = __builtin_amdgcn_alignbyte(d[(o + 3) >> 2], a, (uint32_t)(o & 3));
+                acc[o] = __builtin_amdgcn_sad_u8(a, m[r], acc[o]);
+            }
+        }
+#pragma unroll
+        for (int o = 0; o < 4 * NQ && o < D; ++o)
+            acc[o] = (uint32_t)(qacc[o >> 2] >> (16 * (o & 3))) & 0xffffu;
+#pragma unroll
+        for (int s = 32; s > 0; s >>= 1)
+#pragma unroll
+            for (int o = 0; o < D; ++o)
+                acc[o] += (uint32_t)__shfl_xor(acc[o], s);
+        if (lane == 0u) {
+#pragma unroll
+            for (int o = 0; o < D; ++o)
+                part[wave][dy * D + o] = acc[o];
+        }
+    }
+}
+
+template <int R>
+__global__ __launch_bounds__(FR_THREADS) void k_shift_cells(const uint8_t *frames, uint64_t frames_bytes, const uint8_t *mu,
+                                                            uint64_t model_bytes, const abub_shift_job *__restrict__ jobs, int njobs,
+                                                            uint32_t W, uint32_t H, uint32_t ncx, uint32_t x0, uint32_t y0,
+                                                            uint32_t *__restrict__ status, uint32_t *__restrict__ sad)
+{
+    constexpr int D = 2 * R + 1, N = D * D, ND = (2 * R + 4 + 3) / 4, RS = FC_CELL / 4 + ND - 1, TR = FC_CELL + 2 * R;
+    __shared__ uint32_t tile[TR * RS];
+    __shared__ uint32_t part[FR_THREADS / 64][N];
+    const uint64_t P = (uint64_t)W * H;
+    const uint32_t cell = blockIdx.x, cells = gridDim.x;
+    const uint32_t xc = x0 + (cell % ncx) * FC_CELL, yc = y0 + (cell / ncx) * FC_CELL; // the cell's first interior pixel
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t first = 2u * wave + (lane >> 5), col = lane & 31u;
+    for (uint32_t j = blockIdx.y; j < (uint32_t)njobs; j += gridDim.y) {
+        const abub_shift_job jb = jobs[j];
+        const bool ok = sh_job_ok(jb, frames_bytes, model_bytes, P); // (the same in every thread of every block of the job)
+        uint32_t *out = sad + ((uint64_t)j * cells + cell) * (uint32_t)N;
+        if (cell == 0u && threadIdx.x == 0u)
+            status[j] = ok ? 0u : (uint32_t)ABUB_SHIFT_E_RANGE;
+        if (!ok) {
+            for (uint32_t t = threadIdx.x; t < (uint32_t)N; t += FR_THREADS)
+                out[t] = 0u;
+            continue;
+        }
+        const uint8_t *p = frames + jb.cur, *q = mu + jb.model;
+        for (uint32_t i = threadIdx.x; i < (uint32_t)(TR * RS); i += FR_THREADS) {
+            const uint32_t r = i / (uint32_t)RS, c = i % (uint32_t)RS;
+            tile[i] = sh_load4(p, (uint64_t)(yc - R + r) * W + (xc - R) + 4u * c, P);
+        }
+        uint32_t m[FC_ROWS];
+#pragma unroll
+        for (uint32_t r = 0; r < FC_ROWS; ++r)
+            m[r] = sh_load4(q, (uint64_t)(yc + r * 8u + first) * W + xc + 4u * col, P);
+        __syncthreads();
+        fc_cell<R>(tile, m, part);
+        __syncthreads();
+        for (uint32_t t = threadIdx.x; t < (uint32_t)N; t += FR_THREADS) {
+            uint32_t v = part[0][t];
+#pragma unroll
+            for (int w = 1; w < FR_THREADS / 64; ++w)
+                v += part[w][t];
+            out[t] = v;
+        }
+        __syncthreads(); // (tile and part are written again for the block's next job)
+    }
+}
+
+template <int R>
+void cells_launch(dim3 grid, hipStream_t st, const uint8_t *frames, uint64_t frames_bytes, const uint8_t *mu, uint64_t model_bytes,
+                  const abub_shift_job *jobs, int njobs, uint32_t W, uint32_t H, uint32_t ncx, uint32_t x0, uint32_t y0, uint32_t *status,
+                  uint32_t *sad)
+{
+    k_shift_cells<R><<<grid, FR_THREADS, 0, st>>>(frames, frames_bytes, mu, model_bytes, jobs, njobs, W, H, ncx, x0, y0, status, sad);
+}
+
+} // namespace
+
+extern "C" int abub_frame_cells_grid(int W, int H, int R, int *ncx, int *ncy, int *x0, int *y0)
+{
+    if (!ncx || !ncy || !x0 || !y0)
+        return set_err(ABUB_E_INVALID, "abub_frame_cells_grid: null pointer");
+    if (R < 1 || R > 8 || W < 0 || H < 0)
+        return set_err(ABUB_E_INVALID, "abub_frame_cells_grid: R must be in [1, 8], W and H not negative");
+    const int C = ABUB_FIELD_CELL, iw = std::max(W - 2 * R, 0), ih = std::max(H - 2 * R, 0);
+    *ncx = iw / C;
+    *ncy = ih / C;
+    *x0 = R + (iw - C * *ncx) / 2;
+    *y0 = R + (ih - C * *ncy) / 2;
+    return ABUB_OK;
+}
+
+extern "C" int abub_frame_shift_cells_dev(const uint8_t *frames, size_t frames_bytes, const uint8_t *mu, size_t model_bytes,
+                                          const abub_shift_job *jobs, int njobs, int W, int H, int R, uint32_t *status, uint32_t *sad,
+                                          void *stream)
+{
+    if (!frames || !mu || !jobs || !status || !sad || njobs < 0)
+        return set_err(ABUB_E_INVALID, "abub_frame_shift_cells_dev: null pointer or negative count");
+    if (R < 1 || R > 8)
+        return set_err(ABUB_E_INVALID, "abub_frame_shift_cells_dev: R must be in [1, 8]");
+    if (W < 1 || W > 65535 || H < 1 || H > 65535)
+        return set_err(ABUB_E_INVALID, "abub_frame_shift_cells_dev: W and H must be in [1, 65535]");
+    int ncx = 0, ncy = 0, x0 = 0, y0 = 0;
+    if (abub_frame_cells_grid(W, H, R, &ncx, &ncy, &x0, &y0) != ABUB_OK || ncx == 0 || ncy == 0)
+        return set_err(ABUB_E_INVALID, "abub_frame_shift_cells_dev: W and H must be at least 128 + 2 R: the frame has no whole cell");
+    if (((uintptr_t)jobs & 7) || (((uintptr_t)status | (uintptr_t)sad) & 3))
+        return set_err(ABUB_E_INVALID, "abub_frame_shift_cells_dev: jobs must be 8-byte aligned, status and sad 4-byte aligned");
+    if (njobs == 0)
+        return ABUB_OK;
+    const dim3 grid((unsigned)(ncx * ncy), (unsigned)(njobs < 65535 ? njobs : 65535)); // (at most 511 * 511 cells)
+    typedef void (*Launch)(dim3, hipStream_t, const uint8_t *, uint64_t, const uint8_t *, uint64_t, const abub_shift_job *, int, uint32_t,
+                           uint32_t, uint32_t, uint32_t, uint32_t, uint32_t *, uint32_t *);
+    static const Launch launch[8] = {cells_launch<1>, cells_launch<2>, cells_launch<3>, cells_launch<4>,
+                                     cells_launch<5>, cells_launch<6>, cells_launch<7>, cells_launch<8>};
+    launch[R - 1](grid, (hipStream_t)stream, frames, (uint64_t)frames_bytes, mu, (uint64_t)model_bytes, jobs, njobs, (uint32_t)W,
+                  (uint32_t)H, (uint32_t)ncx, (uint32_t)x0, (uint32_t)y0, status, sad);
     HIPCHK(hipGetLastError());
     return ABUB_OK;
 }

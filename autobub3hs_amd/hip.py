@@ -709,7 +709,44 @@ def frame_shift(frames, mu, jobs, W, H, R, frames_bytes=None, model_bytes=None, 
             sad.reshape(-1)[:n * D * D].cpu().numpy().view(np.uint64).reshape(n, D, D))
 
 
-ACT_PLANES = ("n_zero", "n_sat", "n_out", "sum_out", "n_moved", "sum_moved")
+FIELD_CELL = 128  # ABUB_FIELD_CELL of include/abub_hip.h
+
+
+def field_grid(W, H, R):
+    """abub_frame_cells_grid, the one copy of the grid's rule (no device): -> (ncx, ncy, x0, y0), the whole 128 x 128 cells
+    of a W x H frame's interior at radius R and the first cell's first pixel; ncx * ncy == 0: the frame has no field."""
+    import ctypes
+    out = [ctypes.c_int() for _ in range(4)]
+    _lib.check(_lib.lib().abub_frame_cells_grid(int(W), int(H), int(R), *[ctypes.byref(v) for v in out]), "abub_frame_cells_grid")
+    return tuple(v.value for v in out)
+
+
+def frame_shift_cells(frames, mu, jobs, W, H, R, frames_bytes=None, model_bytes=None, status=None, sad=None):
+    """abub_frame_shift_cells_dev: the arguments of frame_shift; sad: int32 device tensor of at least
+    n * ncy * ncx * (2 R + 1)^2 words, written in place (None: a new one)
+    -> (status int64 [n] on the host: 0 or SHIFT_E_RANGE; the surfaces, uint32 [n, ncy, ncx, 2 R + 1, 2 R + 1] on the
+    host, entry [dy + R, dx + R] of cell (cx, cy))."""
+    import numpy as np
+    _need_cuda(frames, mu, status, sad)
+    offs = np.array([[int(v) for v in row] for row in jobs], dtype=np.uint64).reshape(-1, 2)
+    n, D = len(offs), 2 * int(R) + 1
+    ncx, ncy, _, _ = field_grid(W, H, R)
+    words = n * ncy * ncx * D * D
+    dev = frames.device
+    d_jobs = torch.from_numpy(np.concatenate([offs, np.zeros((1, 2), np.uint64)]).view(np.int64)).to(dev)
+    if status is None:
+        status = torch.full((max(n, 1),), 0x5A5A5A5A, dtype=torch.int32, device=dev)
+    if sad is None:
+        sad = torch.full((max(words, 1),), -1, dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().abub_frame_shift_cells_dev(_ptr(frames), frames.numel() if frames_bytes is None else int(frames_bytes),
+                                                     _ptr(mu), mu.numel() if model_bytes is None else int(model_bytes), _ptr(d_jobs), n,
+                                                     int(W), int(H), int(R), _ptr(status), _ptr(sad), _stream()),
+               "abub_frame_shift_cells_dev")
+    return (status.reshape(-1)[:n].cpu().numpy().astype(np.int64),
+            sad.reshape(-1)[:words].cpu().numpy().view(np.uint32).reshape(n, ncy, ncx, D, D))
+
+
+ACT_PLANES = ("n_zero","n_sat", "n_out", "sum_out", "n_moved", "sum_moved")
 ACT_E_RANGE = 1
 ACT_PIXELS_PER_THREAD = 8  # AC_PX of csrc/abub_stats.hip: the run of pixels a thread owns
 

@@ -71,6 +71,10 @@ SIGNATURES = {
     "abh_run_survey_shift_dev": (_i, [_vp, _s, _s, _s, _i, _i, _i, _i, _dp, _dp, _dp, C.c_char_p, _i]),
     "abh_frame_shift_host": (_i, [_u8p, _u8p, _i, _i, _i, _u64p]),
     "abh_shift_best": (None, [_u64p, _i, C.POINTER(_i)]),
+    "abh_run_survey_field": (_i, [_vp, _s, _s, _s, _i, _s, _i, _i, _i, _dp, _dp, _dp, _dp, C.c_char_p, _i]),
+    "abh_run_survey_field_dev": (_i, [_vp, _s, _s, _s, _i, _s, _i, _i, _i, _i, _dp, _dp, _dp, _dp, C.c_char_p, _i]),
+    "abh_field_grid": (_i, [_i, _i, _i, C.POINTER(_i)]),
+    "abh_field_cells_host": (_i, [_u8p, _u8p, _i, _i, _i, _u32p, C.POINTER(C.c_int32)]),
     "abh_activity_add_host": (None, [C.POINTER(C.c_uint32), _u8p, _u8p, _u8p, _u8p, C.c_uint64]),
     "abh_frame_stats_host": (None, [_u8p, _u8p, _u8p, _u8p, C.c_uint64, _u64p]),
     "abh_zip_write": (_i, [_s, _i, _u8p, _u32p, _u8p, _u64p]),
@@ -447,7 +451,8 @@ class Run:
                     "gpu_png_decoded", "gpu_unpacked", "gpu_bmp_decoded", "host_decoded", "reread", "frames_gpu_unzipped", "device",
                     "W", "H", "batches", "model_cams")
 
-    def survey(self, path=None, nthreads=16, ncams=4, device=None, planes=None, shift=None, shift_radius=4):
+    def survey(self, path=None, nthreads=16, ncams=4, device=None, planes=None, shift=None, shift_radius=4, field=None,
+               field_radius=4):
         """abub3hs --survey of this run (opened from a directory or an archive): the run is listed and trained as for
         detect, then every frame of cameras 0 .. ncams-1 is measured without analysing any; the report (DESIGN section 3,
         "Surveying a run") is written to `path` (None: it is not written).  device=None: host threads (cv::imdecode and
@@ -463,15 +468,30 @@ class Run:
         shift (--survey-shift): the file that gets the shift search ("Surveying a run for movement"): per
         ok frame of a camera with a model its best displacement against mu within shift_radius (1 to 8), the same bytes on
         both routes; the stats then also have shift_frames_kernel / shift_frames_host, shift_launches and the legs shift_s
-        (the device route's) and shift_host_s (the host threads', summed).  The report and the planes do not change."""
+        (the device route's) and shift_host_s (the host threads', summed).  The report and the planes do not change.
+        field (--survey-field): the directory (the CLI's DIR/<run_ID>) that gets the per-cell shift field (DESIGN section 3,
+        "Surveying a run for local movement"): cam<c>_field.npy and field.txt, the same rows searched per cell of 128 x 128
+        pixels within field_radius (1 to 8), the same bytes on both routes; the stats then also have field_frames_kernel /
+        field_frames_host, field_launches and the legs field_s and field_host_s.  Nothing else changes."""
         L = lib()
         st = (C.c_double * 24)()
         pst = (C.c_double * 5)()
         sst = (C.c_double * 5)()
+        fst = (C.c_double * 5)()
         cap = 1 << 16
         buf = C.create_string_buffer(cap)
         to = None if path is None else str(path).encode()
-        if shift is not None:
+        if field is not None:
+            pd = None if planes is None else str(planes).encode()
+            sp = None if shift is None else str(shift).encode()
+            fd = str(field).encode()
+            if device is None:
+                rc = L.abh_run_survey_field(self._h, to, pd, sp, int(shift_radius), fd, int(field_radius), ncams, nthreads, st, pst, sst,
+                                            fst, buf, cap)
+            else:
+                rc = L.abh_run_survey_field_dev(self._h, to, pd, sp, int(shift_radius), fd, int(field_radius), ncams, nthreads,
+                                                int(device), st, pst, sst, fst, buf, cap)
+        elif shift is not None:
             pd = None if planes is None else str(planes).encode()
             sp = str(shift).encode()
             if device is None:
@@ -500,6 +520,9 @@ class Run:
         if shift is not None:
             res.update(shift_frames_kernel=int(sst[0]), shift_frames_host=int(sst[1]), shift_launches=int(sst[2]), shift_s=sst[3],
                        shift_host_s=sst[4])
+        if field is not None:
+            res.update(field_frames_kernel=int(fst[0]), field_frames_host=int(fst[1]), field_launches=int(fst[2]), field_s=fst[3],
+                       field_host_s=fst[4])
         return res, text.decode()
 
     def analyze(self, event, cam, maskdir=""):
@@ -555,6 +578,33 @@ def shift_best(sad, R):
     out = (C.c_int * 3)()
     lib().abh_shift_best(sad.ctypes.data_as(_u64p), int(R), out)
     return out[0], out[1], bool(out[2])
+
+
+def field_grid(W, H, R):
+    """abub_frame_cells_grid (the GPU library's, the one copy of the rule) through the host library: the whole 128 x 128 cells
+    of a W x H frame's interior at radius R -> (ncx, ncy, x0, y0); ncx * ncy == 0: the frame has no field."""
+    out = (C.c_int * 4)()
+    if lib().abh_field_grid(int(W), int(H), int(R), out):
+        raise ValueError(f"abh_field_grid refuses {W}x{H} at radius {R}")
+    return tuple(out)
+
+
+def field_cells_host(p, m, R):
+    """abub::fieldCellsHost and abub::fieldCell (host/survey.cpp), the definition of abub_frame_shift_cells_dev and what a
+    surface says: the frame p and the model plane m, u8 [H, W], at radius R -> (the cells' surfaces, uint32
+    [ncy, ncx, 2 R + 1, 2 R + 1], entry [dy + R, dx + R]; their records, int32 [ncy, ncx, 5]: dx, dy, sad0, sad_best, sad_max)."""
+    p, m = (np.ascontiguousarray(a, dtype=np.uint8) for a in (p, m))
+    assert p.ndim == 2 and p.shape == m.shape
+    try:
+        ncx, ncy, _, _ = field_grid(p.shape[1], p.shape[0], R)
+    except ValueError:
+        ncx = ncy = 0
+    sad = np.zeros((ncy, ncx, 2 * R + 1, 2 * R + 1), np.uint32)
+    rec = np.zeros((ncy, ncx, 5), np.int32)
+    if ncx * ncy == 0 or lib().abh_field_cells_host(p.ctypes.data_as(_u8p), m.ctypes.data_as(_u8p), p.shape[1], p.shape[0], int(R),
+                                                    sad.ctypes.data_as(_u32p), rec.ctypes.data_as(C.POINTER(C.c_int32))) != ncx * ncy:
+        raise ValueError(f"abh_field_cells_host refuses {p.shape[1]}x{p.shape[0]} at radius {R}")
+    return sad, rec
 
 
 def zip_write(path, entries):

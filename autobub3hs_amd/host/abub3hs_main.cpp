@@ -35,6 +35,7 @@ static std::string usage()
            "       abub3hs [-z] [-D data_series] -d data_dir -r run_ID --verify-repack other_data_dir [--verify-gpu] [--archive]\n"
            "       abub3hs [-z] [-D data_series] -d data_dir -r run_ID --survey FILE [--survey-gpu] [--survey-planes DIR]\n"
            "               [--survey-shift FILE [--survey-shift-radius R]]\n"
+           "               [--survey-field DIR [--survey-field-radius R]]\n"
            "Run the AutoBub3hs bubble finding algorithm on a PICO run (MI355X hot path)\n\n"
            "Required arguments:\n"
            "  -d, --data_dir = Dir\t\tpath to the directory in which the run folder/file is stored\n"
@@ -109,6 +110,16 @@ static std::string usage()
            "\t\t\t\tdo not change\n"
            "  --survey-shift-radius = R\twith --survey-shift: the radius of the search in pixels, 1 to 8 (4); the frames must be at\n"
            "\t\t\t\tleast 2 R + 1 wide and high\n"
+           "  --survey-field = Dir\t\twith --survey: also search the same frames per cell of 128 x 128 pixels (whole cells, centred\n"
+           "\t\t\t\tin the interior) and write into Dir/<run_ID>/ cam<c>_field.npy (i32 [frames, cells down, cells\n"
+           "\t\t\t\tacross, 5]: per cell the best dx, dy, the sums at (0, 0), at the best and the largest) and\n"
+           "\t\t\t\tfield.txt: per frame how many cells are rated (the best sum at most half the largest) and how\n"
+           "\t\t\t\tmany of those moved, their most frequent displacement and its range, and the frame's kind (blind,\n"
+           "\t\t\t\tstill, rigid, warped, local); per camera and for the run the counts of each kind and per cell the\n"
+           "\t\t\t\tframes in which it moved; the same bytes with --survey-gpu; the report, the planes and the shift\n"
+           "\t\t\t\tfile do not change\n"
+           "  --survey-field-radius = R\twith --survey-field: the radius of the search in pixels, 1 to 8 (4); the frames must be at\n"
+           "\t\t\t\tleast 128 + 2 R wide and high\n"
            "Environment: ABUB_TRAIN_ON_GPU=0 trains the runs of a campaign with the host Trainer\n"
            "             ABUB_REPACK_BATCH=n (a test knob) lowers the frames per batch of --repack-gpu and --unpack-gpu to n; the files\n"
            "             are the same\n"
@@ -287,6 +298,9 @@ int main(int argc, char **argv)
     std::string surveyShiftFile; // --survey-shift FILE: the survey's shift search, its answers go to FILE
     bool haveSurveyShift = false, haveShiftRadius = false;
     int surveyShiftRadius = 4;
+    std::string surveyFieldDir; // --survey-field DIR: the survey's per-cell shift field goes to DIR/<run_ID>/
+    bool haveSurveyField = false, haveFieldRadius = false;
+    int surveyFieldRadius = 4;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i], v;
         auto value = [&](std::string &dst) {
@@ -401,6 +415,20 @@ int main(int argc, char **argv)
         } else if (a == "--survey-shift" || a.rfind("--survey-shift=", 0) == 0) {
             value(surveyShiftFile);
             haveSurveyShift = true;
+        } else if (a == "--survey-field-radius" || a.rfind("--survey-field-radius=", 0) == 0) {
+            v.clear();
+            value(v);
+            haveFieldRadius = true;
+            char *end = nullptr;
+            const long radius = strtol(v.c_str(), &end, 10);
+            if (v.empty() || *end || radius < 1 || radius > 8) {
+                std::cerr << "--survey-field-radius expects a radius from 1 to 8" << std::endl;
+                return -1;
+            }
+            surveyFieldRadius = (int)radius;
+        } else if (a == "--survey-field" || a.rfind("--survey-field=", 0) == 0) {
+            value(surveyFieldDir);
+            haveSurveyField = true;
         } else if (a == "--per-event") {
             perEvent = true;
         } else if (a == "--peek" || a.rfind("--peek=", 0) == 0) {
@@ -444,6 +472,14 @@ int main(int argc, char **argv)
         std::cerr << "--survey-shift-radius is valid only together with --survey-shift" << std::endl;
         return -1;
     }
+    if (haveSurveyField && !haveSurvey) {
+        std::cerr << "--survey-field is valid only together with --survey" << std::endl;
+        return -1;
+    }
+    if (haveFieldRadius && !haveSurveyField) {
+        std::cerr << "--survey-field-radius is valid only together with --survey-field" << std::endl;
+        return -1;
+    }
     if (haveSurvey) {
         const char *bad = haveUnpack ? "--unpack" : haveRepack ? "--repack" : haveVerify ? "--verify-repack" : mergeN > 0 ? "--merge"
                           : debug_mode ? "--debug" : perEvent ? "--per-event" : event_user >= 0 ? "-e/--event" : havePeek ? "--peek"
@@ -462,6 +498,10 @@ int main(int argc, char **argv)
         }
         if (haveSurveyShift && surveyShiftFile.empty()) {
             std::cerr << "--survey-shift needs the file to write to" << std::endl;
+            return -1;
+        }
+        if (haveSurveyField && surveyFieldDir.empty()) {
+            std::cerr << "--survey-field needs the directory to write to" << std::endl;
             return -1;
         }
     }
@@ -643,6 +683,12 @@ int main(int argc, char **argv)
             shift.path = surveyShiftFile;
             shift.radius = surveyShiftRadius;
         }
+        abub::SurveyField field;
+        if (haveSurveyField) {
+            field.dir = surveyFieldDir + "/" + run_number;
+            field.srcRunDir = zipped ? std::string() : sp.eventDir;
+            field.radius = surveyFieldRadius;
+        }
         int rc = 1;
         try {
             abub::PreparedRun prep = abub::PrepareRun(sp, po, 0, nullptr, false);
@@ -651,9 +697,9 @@ int main(int argc, char **argv)
             if (prep.rc)
                 printf("survey: a camera did not train: the report has no model columns for it\n");
             rc = surveyGpu ? abub::SurveyRunDevice(prep.parser.get(), prep.trainers, sp.numCams, sp.imageFormat, surveyFile, poolThreads(), 0,
-                                                   &ss, nullptr, nullptr, planes, shift)
+                                                   &ss, nullptr, nullptr, planes, shift, field)
                            : abub::SurveyRun(prep.parser.get(), prep.trainers, sp.numCams, sp.imageFormat, surveyFile, poolThreads(), &ss,
-                                             nullptr, nullptr, planes, shift);
+                                             nullptr, nullptr, planes, shift, field);
         } catch (std::exception &e) {
             std::cerr << "survey failed: " << e.what() << std::endl;
             return -6;
@@ -685,6 +731,10 @@ int main(int argc, char **argv)
             printf("survey-shift: %s: radius %d, %lld frames searched on the GPU in %d launches, %lld on the host; shift leg %.3f s, host "
                    "threads %.3f s\n",
                    shift.path.c_str(), shift.radius, ss.shiftFramesKernel, ss.shiftLaunches, ss.shiftFramesHost, ss.shift_s, ss.shiftHost_s);
+        if (haveSurveyField)
+            printf("survey-field: %s: radius %d, %lld frames searched on the GPU in %d launches, %lld on the host; field leg %.3f s, host "
+                   "threads %.3f s\n",
+                   field.dir.c_str(), field.radius, ss.fieldFramesKernel, ss.fieldLaunches, ss.fieldFramesHost, ss.field_s, ss.fieldHost_s);
         return rc;
     }
     if (haveList) {

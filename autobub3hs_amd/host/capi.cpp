@@ -405,9 +405,13 @@ const char *abh_run_verify_report(void *src)
 // movement") written to shift_path (NULL or empty: none) at radius shift_radius (1 to 8), and shift_stats (may be NULL, 5
 // values): [frames searched by abub_frame_shift_dev, by a host thread, the kernel's calls, seconds of the device route's shift
 // leg, seconds the host threads spent in frameShiftHost].
+// abh_run_survey_field[_dev]: the same with the per-cell shift field (abub::SurveyField; DESIGN section 3, "Surveying a run
+// for local movement") written to field_dir (the CLI's DIR/<run_ID>; NULL or empty: none) at radius field_radius (1 to 8),
+// and field_stats (may be NULL, 5 values): the shift's five for abub_frame_shift_cells_dev and fieldCellsHost.
 static int runSurvey(void *r, const char *path, int ncams, int nthreads, int device, bool onDevice, double *stats, char *report,
                      int report_cap, const char *planes_dir = nullptr, double *plane_stats = nullptr, const char *shift_path = nullptr,
-                     int shift_radius = 4, double *shift_stats = nullptr)
+                     int shift_radius = 4, double *shift_stats = nullptr, const char *field_dir = nullptr, int field_radius = 4,
+                     double *field_stats = nullptr)
 {
     Run *run = (Run *)r;
     try {
@@ -436,10 +440,18 @@ static int runSurvey(void *r, const char *path, int ncams, int nthreads, int dev
         abub::SurveyShift shift;
         shift.path = shift_path ? shift_path : "";
         shift.radius = shift_radius;
+        abub::SurveyField field;
+        field.dir = field_dir ? field_dir : "";
+        field.srcRunDir = planes.srcRunDir;
+        field.radius = field_radius;
         const int rc = onDevice ? abub::SurveyRunDevice(pr.parser.get(), pr.trainers, ncams, sp.imageFormat, to, std::max(1, nthreads),
-                                                        device, &st, &rows, &models, planes, shift)
+                                                        device, &st, &rows, &models, planes, shift, field)
                                 : abub::SurveyRun(pr.parser.get(), pr.trainers, ncams, sp.imageFormat, to, std::max(1, nthreads), &st,
-                                                  &rows, &models, planes, shift);
+                                                  &rows, &models, planes, shift, field);
+        if (field_stats) {
+            const double v[5] = {(double)st.fieldFramesKernel, (double)st.fieldFramesHost, (double)st.fieldLaunches, st.field_s, st.fieldHost_s};
+            std::memcpy(field_stats, v, sizeof v);
+        }
         if (shift_stats) {
             const double v[5] = {(double)st.shiftFramesKernel, (double)st.shiftFramesHost, (double)st.shiftLaunches, st.shift_s, st.shiftHost_s};
             std::memcpy(shift_stats, v, sizeof v);
@@ -503,6 +515,20 @@ int abh_run_survey_shift_dev(void *r, const char *path, const char *planes_dir, 
     return runSurvey(r, path, ncams, nthreads, device, true, stats, report, report_cap, planes_dir, plane_stats, shift_path, shift_radius,
                      shift_stats);
 }
+int abh_run_survey_field(void *r, const char *path, const char *planes_dir, const char *shift_path, int shift_radius, const char *field_dir,
+                         int field_radius, int ncams, int nthreads, double *stats, double *plane_stats, double *shift_stats,
+                         double *field_stats, char *report, int report_cap)
+{
+    return runSurvey(r, path, ncams, nthreads, -1, false, stats, report, report_cap, planes_dir, plane_stats, shift_path, shift_radius,
+                     shift_stats, field_dir, field_radius, field_stats);
+}
+int abh_run_survey_field_dev(void *r, const char *path, const char *planes_dir, const char *shift_path, int shift_radius,
+                             const char *field_dir, int field_radius, int ncams, int nthreads, int device, double *stats,
+                             double *plane_stats, double *shift_stats, double *field_stats, char *report, int report_cap)
+{
+    return runSurvey(r, path, ncams, nthreads, device, true, stats, report, report_cap, planes_dir, plane_stats, shift_path, shift_radius,
+                     shift_stats, field_dir, field_radius, field_stats);
+}
 // the whole report of the last abh_run_survey[_dev] on the run (valid until the next query on it)
 const char *abh_run_survey_report(void *r)
 {
@@ -539,6 +565,32 @@ void abh_shift_best(const uint64_t *sad, int R, int *out)
     out[0] = b.dx;
     out[1] = b.dy;
     out[2] = b.atEdge ? 1 : 0;
+}
+
+// abub_frame_cells_grid (the GPU library's, the one copy of the rule): out[4] = [ncx, ncy, x0, y0]; returns 0, or -1 (nothing
+// written) for a null pointer, R outside [1, 8] or a negative side
+int abh_field_grid(int W, int H, int R, int *out)
+{
+    if (!out)
+        return -1;
+    int v[4];
+    if (abub_frame_cells_grid(W, H, R, &v[0], &v[1], &v[2], &v[3]) != ABUB_OK)
+        return -1;
+    std::memcpy(out, v, sizeof v);
+    return 0;
+}
+// abub::fieldCellsHost and abub::fieldCell on raw buffers: the W x H frame p against the model plane m at radius R ->
+// sad[ncy * ncx * (2 R + 1)^2] and rec[ncy * ncx * 5]; returns the number of cells, or -1 (nothing written) for a null
+// pointer, R outside [1, 8] or a frame without a whole cell
+int abh_field_cells_host(const uint8_t *p, const uint8_t *m, int W, int H, int R, uint32_t *sad, int32_t *rec)
+{
+    int g[4];
+    if (!p || !m || !sad || !rec || abh_field_grid(W, H, R, g) || g[0] * g[1] == 0)
+        return -1;
+    const size_t cells = abub::fieldCellsHost(p, m, W, H, R, sad), N = (size_t)(2 * R + 1) * (2 * R + 1);
+    for (size_t k = 0; k < cells; ++k)
+        abub::fieldCell(sad + k * N, R, rec + k * abub::FieldRecordWords);
+    return (int)cells;
 }
 
 // bmpWalk (host/bmpwalk.hpp: what the reading threads learn about a BMP before the GPU decodes it): 1 = a file decodeBMP

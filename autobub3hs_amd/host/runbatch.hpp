@@ -231,6 +231,18 @@ struct ShiftBest {
     uint64_t sad0 = 0, sadBest = 0; // the surface at (0, 0) and at (dx, dy)
 };
 ShiftBest shiftBest(const uint64_t *sad, int R);
+ShiftBest shiftBest(const uint32_t *sad, int R); // the same rule (one template) on a cell's u32 surface
+// The definition of abub_frame_shift_cells_dev ("Surveying a run for local movement"): frameShiftHost's
+// sums kept apart per whole cell of 128 x 128 interior pixels, on the grid abub_frame_cells_grid gives (the one copy of that
+// rule, in the GPU library): sad[((cy * ncx + cx) * (2 R + 1) + (dy + R)) * (2 R + 1) + (dx + R)] = sum over the cell of
+// |p(x + dx, y + dy) - m(x, y)|, u32.  Plain loops.  Returns the number of cells, 0 (nothing written) where the frame has none.
+size_t fieldCellsHost(const unsigned char *p, const unsigned char *m, int W, int H, int R, uint32_t *sad);
+// What a cell's surface says, five i32: dx, dy, sad0, sad_best (shiftBest's answer), sad_max (the largest entry)
+enum { FieldRecordWords = 5 };
+void fieldCell(const uint32_t *sad, int R, int32_t *rec);
+// A cell is rated iff sad_max > 0 and 2 * sad_best <= sad_max: the best displacement explains at least half of the worst
+// mismatch.  A flat cell, where every displacement scores alike, is not.
+inline bool fieldRated(const int32_t *rec) { return rec[4] > 0 && 2 * (int64_t)rec[3] <= (int64_t)rec[4]; }
 
 // One row of a survey: a frame the run lists, or one it should list (missing)
 struct SurveyRow {
@@ -243,6 +255,8 @@ struct SurveyRow {
     bool onKernel = false;
     bool hasShift = false, shiftOnKernel = false; // with a shift file: an ok row of a camera with a model has its surface's answer
     ShiftBest shift;
+    bool hasField = false, fieldOnKernel = false; // with a field directory: the same rows have their cells' records
+    std::vector<int32_t> field;                   // [ncy][ncx][5]
     const char *stateName() const; // "ok", "undecodable", "missing", "other_size"
 };
 // What the report says of one camera's model
@@ -274,6 +288,10 @@ struct SurveyStats {
     long long shiftFramesKernel = 0, shiftFramesHost = 0;
     int shiftLaunches = 0;
     double shift_s = 0, shiftHost_s = 0;
+    // With a field directory: the same five for abub_frame_shift_cells_dev and fieldCellsHost
+    long long fieldFramesKernel = 0, fieldFramesHost = 0;
+    int fieldLaunches = 0;
+    double field_s = 0, fieldHost_s = 0;
 };
 // Where a survey writes its per-pixel activity planes (abub3hs --survey-planes; DESIGN section 3, "Surveying a run per
 // pixel"): the directory `dir` (the CLI's DIR/<run_ID>; empty: no planes) gets cam<c>_activity.npy (u32 [6, H, W]) for
@@ -289,6 +307,18 @@ struct SurveyShift {
     std::string path;
     int radius = 4;
 };
+// Where a survey writes its per-cell shift field (abub3hs --survey-field; DESIGN section 3, "Surveying a run for local
+// movement"): the directory `dir` (the CLI's DIR/<run_ID>; empty: no field) gets cam<c>_field.npy (i32 [N_c, ncy, ncx, 5]:
+// the records of camera c's rows that have a surface, in survey order) for every camera with a model, and field.txt.  A run
+// narrower or lower than 128 + 2 radius has no whole cell and is refused before its frames are measured.
+struct SurveyField {
+    std::string dir, srcRunDir;
+    int radius = 4;
+};
+// field.txt's text: "# abub3hs field 1", the grid's line, the table's header and one tab-separated row per survey row, one
+// `field cam` line per camera, the `moved` lines of every camera with a model, the `run` line.  Both routes write it through
+// this one function; W, H: the run's size.
+std::string FieldReport(int radius, int W, int H, const std::vector<SurveyModel> &models, const std::vector<SurveyRow> &rows);
 // The shift file's text: "# abub3hs shift 1", `radius R`, the table's header and one tab-separated row per survey row, one
 // `shift cam` line per camera, the `run` line.  Both routes write it through this one function.
 std::string ShiftReport(int radius, const std::vector<SurveyModel> &models, const std::vector<SurveyRow> &rows);
@@ -307,10 +337,13 @@ std::string SurveyReport(const std::vector<SurveyModel> &models, const std::vect
 // With shift.path every ok row of a camera with a model is also searched for its displacement against mu (frameShiftHost
 // here; on the device route abub_frame_shift_dev for the rows in place in the slab, one call per batch behind the statistics
 // launch) and the shift file is written (both routes: the same bytes).  The report and the planes do not change.
+// With field.dir the same rows also get their per-cell records (fieldCellsHost here; on the device route
+// abub_frame_shift_cells_dev behind the statistics and the shift launch) and the field's files are written (both routes: the
+// same bytes).  The report, the planes and the shift file do not change.
 int SurveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCams, const std::string &imageFormat,
               const std::string &reportPath, int nthreads, SurveyStats *stats, std::vector<SurveyRow> *rows,
               std::vector<SurveyModel> *models = nullptr, const SurveyPlanes &planes = SurveyPlanes(),
-              const SurveyShift &shift = SurveyShift());
+              const SurveyShift &shift = SurveyShift(), const SurveyField &field = SurveyField());
 // abub3hs --survey FILE --survey-gpu: the same rows and the same report, byte for byte.  The frames are read through the
 // FileBatch protocol (framefiles.hpp) in batches of at most 4 frames per CU (ABUB_SURVEY_BATCH=n: of n), decoded into the
 // batch's slab, and measured by one abub_frame_stats_dev launch per batch.  A batch that begins inside a stack reads again
@@ -321,7 +354,7 @@ int SurveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCam
 int SurveyRunDevice(Parser *parser, const std::vector<Trainer *> &trainers, int numCams, const std::string &imageFormat,
                     const std::string &reportPath, int nthreads, int device, SurveyStats *stats, std::vector<SurveyRow> *rows,
                     std::vector<SurveyModel> *models = nullptr, const SurveyPlanes &planes = SurveyPlanes(),
-                    const SurveyShift &shift = SurveyShift());
+                    const SurveyShift &shift = SurveyShift(), const SurveyField &field = SurveyField());
 
 // A run listed and trained, ready for detect; rc = -5 (the run cannot be read) or -7 (a camera did not train)
 struct PreparedRun {

@@ -13,6 +13,10 @@
 // are also searched for their displacement against mu: frameShiftHost is the definition of the SAD surface, the device route
 // gets the surfaces of the rows in place in the slab from abub_frame_shift_dev, shiftBest reads every surface on the host,
 // and one writer (ShiftReport) makes the file for both routes.
+// With a field directory (--survey-field; DESIGN section 3, "Surveying a run for local movement") the same rows are also
+// searched per cell of 128 x 128 pixels: fieldCellsHost is the definition of the cells' surfaces, the device route gets them
+// from abub_frame_shift_cells_dev, fieldCell reads every surface on the host into a record of five words, and one writer
+// (writeField, with FieldReport for the text) makes the files for both routes.
 #include <algorithm>
 #include <cinttypes>
 #include <cmath>
@@ -111,7 +115,7 @@ void frameShiftHost(const unsigned char *p, const unsigned char *m, int W, int H
         }
 }
 
-ShiftBest shiftBest(const uint64_t *sad, int R)
+template <class T> static ShiftBest shiftBestOf(const T *sad, int R)
 {
     const int D = 2 * R + 1;
     ShiftBest b;
@@ -127,6 +131,147 @@ ShiftBest shiftBest(const uint64_t *sad, int R)
         }
     b.atEdge = std::abs(b.dx) == R || std::abs(b.dy) == R;
     return b;
+}
+ShiftBest shiftBest(const uint64_t *sad, int R) { return shiftBestOf(sad, R); }
+ShiftBest shiftBest(const uint32_t *sad, int R) { return shiftBestOf(sad, R); }
+
+size_t fieldCellsHost(const unsigned char *p, const unsigned char *m, int W, int H, int R, uint32_t *sad)
+{
+    int ncx = 0, ncy = 0, x0 = 0, y0 = 0;
+    if (abub_frame_cells_grid(W, H, R, &ncx, &ncy, &x0, &y0) != ABUB_OK)
+        return 0;
+    const int C = ABUB_FIELD_CELL, D = 2 * R + 1;
+    for (int cy = 0; cy < ncy; ++cy)
+        for (int cx = 0; cx < ncx; ++cx) {
+            uint32_t *out = sad + ((size_t)cy * ncx + cx) * D * D;
+            const int xa = x0 + C * cx, ya = y0 + C * cy;
+            for (int dy = -R; dy <= R; ++dy)
+                for (int dx = -R; dx <= R; ++dx) {
+                    uint32_t s = 0; // (at most 16384 * 255)
+                    for (int y = ya; y < ya + C; ++y) {
+                        const unsigned char *pr = p + (size_t)(y + dy) * W + dx, *mr = m + (size_t)y * W;
+                        for (int x = xa; x < xa + C; ++x)
+                            s += (uint32_t)std::abs((int)pr[x] - (int)mr[x]);
+                    }
+                    out[(size_t)(dy + R) * D + (dx + R)] = s;
+                }
+        }
+    return (size_t)ncx * ncy;
+}
+
+void fieldCell(const uint32_t *sad, int R, int32_t *rec)
+{
+    const ShiftBest b = shiftBest(sad, R);
+    const size_t N = (size_t)(2 * R + 1) * (2 * R + 1);
+    rec[0] = b.dx;
+    rec[1] = b.dy;
+    rec[2] = (int32_t)b.sad0;
+    rec[3] = (int32_t)b.sadBest;
+    rec[4] = (int32_t)*std::max_element(sad, sad + N);
+}
+
+std::string FieldReport(int radius, int W, int H, const std::vector<SurveyModel> &models, const std::vector<SurveyRow> &rows)
+{
+    int ncx = 0, ncy = 0, x0 = 0, y0 = 0;
+    if (W > 0 && H > 0)
+        abub_frame_cells_grid(W, H, radius, &ncx, &ncy, &x0, &y0);
+    const size_t cells = (size_t)ncx * ncy;
+    std::string text = "# abub3hs field 1\n";
+    char buf[512];
+    snprintf(buf, sizeof buf, "radius %d cell %d grid %d %d origin %d %d\n", radius, (int)ABUB_FIELD_CELL, ncx, ncy, x0, y0);
+    text += buf;
+    text += "event\tcam\tframe\tname\tstate\tindex\trated\tmoved\tmodal_dx\tmodal_dy\tmodal_n\tdx_min\tdx_max\tdy_min\tdy_max\tkind\n";
+    enum { Blind, Still, Rigid, Warped, Local };
+    static const char *const kinds[] = {"blind", "still", "rigid", "warped", "local"};
+    struct Cam {
+        long long frames = 0, kind[5] = {0, 0, 0, 0, 0};
+        const std::string *first = nullptr;
+        std::vector<long long> moved; // per cell: the frames in which it was rated and off (0, 0)
+    };
+    std::vector<Cam> cams(models.size());
+    for (const SurveyRow &r : rows) {
+        snprintf(buf, sizeof buf, "%s\t%d\t%d\t%s\t%s", r.event.c_str(), r.cam, r.frame, r.name.c_str(), r.stateName());
+        text += buf;
+        if (r.state != SurveyRow::Ok || !r.hasField || r.field.size() != cells * FieldRecordWords) {
+            text += "\t-\t-\t-\t-\t-\t-\t-\t-\t-\t-\t-\n";
+            continue;
+        }
+        Cam &c = cams[(size_t)r.cam];
+        c.moved.resize(cells, 0);
+        int rated = 0, moved = 0, dxMin = 0, dxMax = 0, dyMin = 0, dyMax = 0;
+        std::map<std::pair<int, int>, int> seen; // (dy, dx) of the rated cells -> how many
+        for (size_t k = 0; k < cells; ++k) {
+            const int32_t *rec = r.field.data() + k * FieldRecordWords;
+            if (!fieldRated(rec))
+                continue;
+            const int dx = rec[0], dy = rec[1];
+            dxMin = rated ? std::min(dxMin, dx) : dx;
+            dxMax = rated ? std::max(dxMax, dx) : dx;
+            dyMin = rated ? std::min(dyMin, dy) : dy;
+            dyMax = rated ? std::max(dyMax, dy) : dy;
+            ++rated;
+            ++seen[{dy, dx}];
+            if (dx != 0 || dy != 0) {
+                ++moved;
+                ++c.moved[k];
+            }
+        }
+        // the most frequent displacement; among equally frequent ones shiftBest's order: the nearer, the smaller dy, the smaller dx
+        int mdx = 0, mdy = 0, mn = 0;
+        for (const auto &kv : seen) { // (in (dy, dx) order: a later equal one wins only when it is nearer)
+            const int dy = kv.first.first, dx = kv.first.second;
+            if (kv.second > mn || (kv.second == mn && dx * dx + dy * dy < mdx * mdx + mdy * mdy)) {
+                mn = kv.second;
+                mdx = dx;
+                mdy = dy;
+            }
+        }
+        const int kind = !rated ? Blind : !moved ? Still : moved < rated ? Local : seen.size() == 1 ? Rigid : Warped;
+        snprintf(buf, sizeof buf, "\t%lld\t%d\t%d", c.frames, rated, moved);
+        text += buf;
+        if (kind == Blind)
+            snprintf(buf, sizeof buf, "\t-\t-\t-\t-\t-\t-\t-\t%s\n", kinds[kind]);
+        else
+            snprintf(buf, sizeof buf, "\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%s\n", mdx, mdy, mn, dxMin, dxMax, dyMin, dyMax, kinds[kind]);
+        text += buf;
+        ++c.frames;
+        ++c.kind[kind];
+        if (moved && !c.first)
+            c.first = &r.event;
+    }
+    long long frames = 0, kind[5] = {0, 0, 0, 0, 0};
+    for (size_t c = 0; c < cams.size(); ++c) {
+        if (!models[c].trained) {
+            snprintf(buf, sizeof buf, "field cam %zu none\n", c);
+            text += buf;
+            continue;
+        }
+        const Cam &k = cams[c];
+        snprintf(buf, sizeof buf, "field cam %zu frames %lld blind %lld still %lld rigid %lld warped %lld local %lld first_moved_event %s\n", c,
+                 k.frames, k.kind[Blind], k.kind[Still], k.kind[Rigid], k.kind[Warped], k.kind[Local], k.first ? k.first->c_str() : "-");
+        text += buf;
+        frames += k.frames;
+        for (int q = 0; q < 5; ++q)
+            kind[q] += k.kind[q];
+    }
+    for (size_t c = 0; c < cams.size(); ++c) {
+        if (!models[c].trained)
+            continue;
+        for (int y = 0; y < ncy; ++y) {
+            snprintf(buf, sizeof buf, "moved cam %zu y %d", c, y);
+            text += buf;
+            for (int x = 0; x < ncx; ++x) {
+                const size_t k = (size_t)y * ncx + x;
+                snprintf(buf, sizeof buf, " %lld", k < cams[c].moved.size() ? cams[c].moved[k] : 0ll);
+                text += buf;
+            }
+            text += "\n";
+        }
+    }
+    snprintf(buf, sizeof buf, "run frames %lld blind %lld still %lld rigid %lld warped %lld local %lld\n", frames, kind[Blind], kind[Still],
+             kind[Rigid], kind[Warped], kind[Local]);
+    text += buf;
+    return text;
 }
 
 std::string ShiftReport(int radius, const std::vector<SurveyModel> &models, const std::vector<SurveyRow> &rows)
@@ -279,6 +424,9 @@ struct Plan {
     HostPlanes *planes = nullptr;   // with a planes directory: where surveyFrame adds its ok rows
     int shiftR = 0;                 // with a shift file: the radius surveyFrame searches its ok rows with a model in (0: none)
     std::atomic<long long> *shiftHostUs = nullptr; // ... and where it adds the microseconds it spent in frameShiftHost
+    int fieldR = 0;                 // with a field directory: the radius of the per-cell search (0: none) ...
+    size_t fieldCells = 0;          // ... the run's cells (abub_frame_cells_grid) ...
+    std::atomic<long long> *fieldHostUs = nullptr; // ... and where surveyFrame adds the microseconds it spent in fieldCellsHost
     std::vector<std::string> events;
     std::vector<SurveyRow> rows;    // in event, camera and frame order
     std::vector<size_t> ref;        // ref[i]: the row frame i is measured against (frame max(i - 2, 0) of its stack)
@@ -412,12 +560,36 @@ void shiftRowHost(const Plan &pl, const uint8_t *cur, const uint8_t *mu, SurveyR
         *pl.shiftHostUs += (long long)((nowMs() - t0) * 1e3);
 }
 
+// a row's records from its cells' surfaces ([cells][(2 R + 1)^2]), whichever route made them
+void fieldRecords(const Plan &pl, const uint32_t *sad, SurveyRow &row, bool onKernel)
+{
+    const size_t N = (2 * (size_t)pl.fieldR + 1) * (2 * (size_t)pl.fieldR + 1);
+    row.field.resize(pl.fieldCells * FieldRecordWords);
+    for (size_t k = 0; k < pl.fieldCells; ++k)
+        fieldCell(sad + k * N, pl.fieldR, row.field.data() + k * FieldRecordWords);
+    row.hasField = true;
+    row.fieldOnKernel = onKernel;
+}
+
+// The per-cell search of an ok row of a camera with a model on this thread: the definition, then the records
+void fieldRowHost(const Plan &pl, const uint8_t *cur, const uint8_t *mu, SurveyRow &row)
+{
+    const double t0 = nowMs();
+    const size_t N = (2 * (size_t)pl.fieldR + 1) * (2 * (size_t)pl.fieldR + 1);
+    std::vector<uint32_t> sad(pl.fieldCells * N);
+    fieldCellsHost(cur, mu, pl.W, pl.H, pl.fieldR, sad.data());
+    fieldRecords(pl, sad.data(), row, false);
+    if (pl.fieldHostUs)
+        *pl.fieldHostUs += (long long)((nowMs() - t0) * 1e3);
+}
+
 // The host route's per-frame function: row i on this thread, its state and its record.  It asks nothing of the other rows:
 // the reference frame is decoded here as well, and is there iff its own row is ok
 void surveyFrame(Parser &p, const Plan &pl, size_t i, SurveyRow &row)
 {
     row.onKernel = false;
     row.hasShift = row.shiftOnKernel = false;
+    row.hasField = row.fieldOnKernel = false;
     row.s = FrameStats();
     row.w = row.h = 0;
     if (row.state == SurveyRow::Missing)
@@ -450,6 +622,8 @@ void surveyFrame(Parser &p, const Plan &pl, size_t i, SurveyRow &row)
         pl.planes->add(row.cam, cur.data, r, mu, mu ? pl.sigma6[row.cam].data() : nullptr);
     if (pl.shiftR && mu)
         shiftRowHost(pl, cur.data, mu, row);
+    if (pl.fieldR && mu)
+        fieldRowHost(pl, cur.data, mu, row);
 }
 
 void hostFrames(Parser *parser, Plan &pl, int nthreads)
@@ -486,6 +660,10 @@ FrameStats fromRecord(const abub_stat_result &r)
 // and on the same stream: one abub_frame_shift_dev call per batch over [jobs][status words][surfaces] in a buffer of its own
 // (mu is resident already), the surfaces back in one copy; shiftBest on the host says what each means.  Every row in place
 // is in the slab, whichever decoder or thread put it there, so all of them are the kernel's.
+// With pl.fieldR the same rows are then searched per cell, behind the shift launch on the same stream, over
+// [jobs][status words][surfaces] in a buffer of its own: abub_frame_shift_cells_dev in calls of as many jobs as keep the
+// surfaces below 64 MiB (ABUB_FIELD_CHUNK=n, a test knob: of n jobs), each call's status words and surfaces back in one copy.
+// A job's surface depends on nothing but the job, so the split cannot show in the result.
 void deviceFrames(Parser *parser, Plan &pl, int nthreads, int device, SurveyStats &st, std::vector<uint32_t> &devPlanes)
 {
     HIPOK(hipSetDevice(device));
@@ -497,8 +675,8 @@ void deviceFrames(Parser *parser, Plan &pl, int nthreads, int device, SurveyStat
     const size_t P = (size_t)W * H, stride = (P + 15) & ~(size_t)15, C = pl.mu.size();
     FileBatch B;
     B.sizer.reset(parser->clone());
-    PinnedBuffer h_meta, h_shift;
-    DeviceBuffer d_meta, d_shift, d_model; // d_model: [mu of every camera][sigma6 of every camera], camera c at c * stride
+    PinnedBuffer h_meta, h_shift, h_field;
+    DeviceBuffer d_meta, d_shift, d_field, d_model; // d_model: [mu of every camera][sigma6 of every camera], camera c at c * stride
     Stream stream;
     hipStream_t cs = stream.get();
     bool anyModel = false;
@@ -630,6 +808,44 @@ void deviceFrames(Parser *parser, Plan &pl, int nthreads, int device, SurveyStat
                 st.shift_s += (nowMs() - t0) * 1e-3;
                 t0 = nowMs();
             }
+            if (pl.fieldR) {
+                st.stats_s += (nowMs() - t0) * 1e-3;
+                t0 = nowMs();
+                std::vector<size_t> with; // the jobs that have a model
+                for (size_t g = 0; g < nj; ++g)
+                    if (jobs[g].model != UINT64_MAX)
+                        with.push_back(g);
+                const size_t N = (2 * (size_t)pl.fieldR + 1) * (2 * (size_t)pl.fieldR + 1), words = pl.fieldCells * N;
+                size_t chunk = std::max<size_t>(1, ((size_t)64 << 20) / (words * sizeof(uint32_t)));
+                if (const char *e = getenv("ABUB_FIELD_CHUNK"))
+                    if (atoi(e) > 0)
+                        chunk = (size_t)atoi(e);
+                for (size_t q0 = 0; q0 < with.size(); q0 += chunk) {
+                    const size_t ns = std::min(chunk, with.size() - q0);
+                    const size_t jobBytes = ns * sizeof(abub_shift_job), bytes = jobBytes + ns * (1 + words) * sizeof(uint32_t);
+                    h_field.grow(bytes);
+                    d_field.grow(bytes);
+                    abub_shift_job *fj = (abub_shift_job *)h_field.get();
+                    for (size_t q = 0; q < ns; ++q)
+                        fj[q] = abub_shift_job{jobs[with[q0 + q]].cur, jobs[with[q0 + q]].model};
+                    HIPOK(hipMemcpyAsync(d_field.get(), h_field.get(), jobBytes, hipMemcpyHostToDevice, cs));
+                    uint32_t *d_status = (uint32_t *)(d_field.get() + jobBytes);
+                    check(abub_frame_shift_cells_dev(B.slab.get(), slots * stride, d_model.get(), C * stride,
+                                                     (const abub_shift_job *)d_field.get(), (int)ns, W, H, pl.fieldR, d_status, d_status + ns, cs),
+                          "abub_frame_shift_cells_dev");
+                    HIPOK(hipMemcpyAsync(h_field.get() + jobBytes, d_field.get() + jobBytes, bytes - jobBytes, hipMemcpyDeviceToHost, cs));
+                    HIPOK(hipStreamSynchronize(cs));
+                    const uint32_t *status = (const uint32_t *)(h_field.get() + jobBytes), *sad = status + ns;
+                    for (size_t q = 0; q < ns; ++q) {
+                        if (status[q] != 0)
+                            throw std::runtime_error("survey: abub_frame_shift_cells_dev refused a frame of its own slab");
+                        fieldRecords(pl, sad + q * words, pl.rows[rowOf(slot[with[q0 + q]])], true);
+                    }
+                    ++st.fieldLaunches;
+                }
+                st.field_s += (nowMs() - t0) * 1e-3;
+                t0 = nowMs();
+            }
             if (wantPlanes) {
                 st.stats_s += (nowMs() - t0) * 1e-3;
                 t0 = nowMs();
@@ -732,6 +948,51 @@ void deviceFrames(Parser *parser, Plan &pl, int nthreads, int device, SurveyStat
     }
 }
 
+// The head of a NumPy format 1.0 file of `descr` values in C order, `shape` as Python writes a tuple: the data that follows
+// it begins at a multiple of 64
+std::string npyHead(const char *descr, const std::string &shape)
+{
+    std::string head = std::string("{'descr': '") + descr + "', 'fortran_order': False, 'shape': " + shape + ", }";
+    head.resize((10 + head.size() + 1 + 63) / 64 * 64 - 10 - 1, ' ');
+    head += '\n';
+    std::string file("\x93NUMPY\x01\x00", 8);
+    file += (char)(head.size() & 0xff);
+    file += (char)(head.size() >> 8);
+    return file + head;
+}
+
+// The files of the per-cell shift field, one writer for both routes ("Surveying a run for local
+// movement"): per camera with a model cam<c>_field.npy, the records of its rows that have a surface in survey order (the
+// `index` column of field.txt), and field.txt
+void writeField(const std::string &dir, int radius, const Plan &pl)
+{
+    std::string failed;
+    if (!makeDirs(dir, &failed))
+        throw std::runtime_error("survey: cannot make the directory " + failed);
+    int ncx = 0, ncy = 0, x0 = 0, y0 = 0;
+    if (pl.W > 0)
+        abub_frame_cells_grid(pl.W, pl.H, radius, &ncx, &ncy, &x0, &y0);
+    for (size_t c = 0; c < pl.models.size(); ++c) {
+        if (!pl.models[c].trained)
+            continue;
+        std::string data;
+        size_t n = 0;
+        for (const SurveyRow &r : pl.rows)
+            if ((size_t)r.cam == c && r.state == SurveyRow::Ok && r.hasField && r.field.size() == pl.fieldCells * FieldRecordWords) {
+                data.append((const char *)r.field.data(), r.field.size() * sizeof(int32_t));
+                ++n;
+            }
+        char shape[96];
+        snprintf(shape, sizeof shape, "(%zu, %d, %d, %d)", n, ncy, ncx, (int)FieldRecordWords);
+        const std::string file = npyHead("<i4", shape) + data, path = dir + "/cam" + std::to_string(c) + "_field.npy";
+        if (!writeFile(path, (const unsigned char *)file.data(), file.size()))
+            throw std::runtime_error("survey: cannot write " + path);
+    }
+    const std::string text = FieldReport(radius, pl.W, pl.H, pl.models, pl.rows);
+    if (!writeFile(dir + "/field.txt", (const unsigned char *)text.data(), text.size()))
+        throw std::runtime_error("survey: cannot write " + dir + "/field.txt");
+}
+
 // The files of the per-pixel planes, one writer for both routes ("Surveying a run per pixel"): per camera
 // with a listed row the sum of the host's planes and the device's (dev: [camera][6][stride], or empty) as
 // cam<c>_activity.npy, with a model cam<c>_moved.png, and the cameras' lines of activity.txt
@@ -770,14 +1031,8 @@ void writePlanes(const std::string &dir, const Plan &pl, const HostPlanes &hp, c
                        *sumMoved = nMoved + P;
 
         // ---- cam<c>_activity.npy: NumPy format 1.0, the data at a multiple of 64 --------------------------------------------
-        snprintf(buf, sizeof buf, "{'descr': '<u4', 'fortran_order': False, 'shape': (6, %d, %d), }", pl.H, pl.W);
-        std::string head = buf;
-        head.resize((10 + head.size() + 1 + 63) / 64 * 64 - 10 - 1, ' ');
-        head += '\n';
-        std::string file("\x93NUMPY\x01\x00", 8);
-        file += (char)(head.size() & 0xff);
-        file += (char)(head.size() >> 8);
-        file += head;
+        snprintf(buf, sizeof buf, "(6, %d, %d)", pl.H, pl.W);
+        std::string file = npyHead("<u4", buf);
         file.append((const char *)v.data(), v.size() * sizeof(uint32_t));
         const std::string stem = dir + "/cam" + std::to_string(c);
         if (!writeFile(stem + "_activity.npy", (const unsigned char *)file.data(), file.size()))
@@ -839,7 +1094,7 @@ bool sameDirectory(const std::string &path, const std::string &other)
 
 int surveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCams, const std::string &format,
               const std::string &reportPath, int nthreads, int device, SurveyStats *stats, std::vector<SurveyRow> *rows,
-              std::vector<SurveyModel> *models, const SurveyPlanes &planes, const SurveyShift &shift)
+              std::vector<SurveyModel> *models, const SurveyPlanes &planes, const SurveyShift &shift, const SurveyField &field)
 {
     const double t0 = nowMs();
     SurveyStats st;
@@ -849,6 +1104,11 @@ int surveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCam
     // (the planes' files have names of their own, but a run directory is not the place for what was derived from it)
     if (!planesDir.empty() && sameDirectory(trimSlashes(planes.srcRunDir), planesDir))
         throw std::runtime_error("survey: " + planesDir + " is the run that is being read");
+    const std::string fieldDir = trimSlashes(field.dir);
+    if (!fieldDir.empty() && sameDirectory(trimSlashes(field.srcRunDir), fieldDir))
+        throw std::runtime_error("survey: " + fieldDir + " is the run that is being read");
+    if (!fieldDir.empty() && (field.radius < 1 || field.radius > 8))
+        throw std::runtime_error("survey: the field radius must be in [1, 8], not " + std::to_string(field.radius));
     if (!shift.path.empty() && (shift.radius < 1 || shift.radius > 8))
         throw std::runtime_error("survey: the shift radius must be in [1, 8], not " + std::to_string(shift.radius));
     Plan pl = planRun(parser, trainers, numCams, format);
@@ -861,6 +1121,21 @@ int surveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCam
                                      std::to_string(pl.H));
         pl.shiftR = shift.radius;
         pl.shiftHostUs = &shiftHostUs;
+    }
+    std::atomic<long long> fieldHostUs{0};
+    if (!fieldDir.empty()) {
+        const int need = ABUB_FIELD_CELL + 2 * field.radius;
+        int ncx = 0, ncy = 0, x0 = 0, y0 = 0;
+        if (pl.W > 0) {
+            abub_frame_cells_grid(pl.W, pl.H, field.radius, &ncx, &ncy, &x0, &y0);
+            if (ncx == 0 || ncy == 0)
+                throw std::runtime_error("survey: a shift field at radius " + std::to_string(field.radius) + " needs frames of at least " +
+                                         std::to_string(need) + "x" + std::to_string(need) + ", the run's are " + std::to_string(pl.W) + "x" +
+                                         std::to_string(pl.H));
+        }
+        pl.fieldR = field.radius;
+        pl.fieldCells = (size_t)ncx * ncy;
+        pl.fieldHostUs = &fieldHostUs;
     }
     std::unique_ptr<HostPlanes> hostPlanes;
     std::vector<uint32_t> devPlanes;
@@ -877,8 +1152,9 @@ int surveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCam
     st.H = pl.H;
     for (const SurveyModel &m : pl.models)
         st.modelCams += m.trained;
-    // (abub_frame_shift_dev takes sides of up to 65535: a larger run with a shift file is the host route's whole)
-    if (device >= 0 && pl.W > 0 && decodersTakeWidth(pl.W) && (!pl.shiftR || (pl.W <= 65535 && pl.H <= 65535))) {
+    // (abub_frame_shift_dev and abub_frame_shift_cells_dev take sides of up to 65535: a larger run with a shift file or a
+    // field is the host route's whole)
+    if (device >= 0 && pl.W > 0 && decodersTakeWidth(pl.W) && ((!pl.shiftR && !pl.fieldR) || (pl.W <= 65535 && pl.H <= 65535))) {
         st.device = device;
         deviceFrames(parser, pl, nthreads, device, st, devPlanes);
     } else
@@ -890,8 +1166,11 @@ int surveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCam
         ++(r.onKernel ? st.framesKernel : st.framesHostRoute);
         if (r.state == SurveyRow::Ok && r.hasShift)
             ++(r.shiftOnKernel ? st.shiftFramesKernel : st.shiftFramesHost);
+        if (r.state == SurveyRow::Ok && r.hasField)
+            ++(r.fieldOnKernel ? st.fieldFramesKernel : st.fieldFramesHost);
     }
     st.shiftHost_s = (double)shiftHostUs * 1e-6;
+    st.fieldHost_s = (double)fieldHostUs * 1e-6;
     if (!reportPath.empty()) {
         const std::string text = SurveyReport(pl.models, pl.rows);
         if (!writeFile(reportPath, (const unsigned char *)text.data(), text.size()))
@@ -902,6 +1181,8 @@ int surveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCam
         if (!writeFile(shift.path, (const unsigned char *)text.data(), text.size()))
             throw std::runtime_error("survey: cannot write " + shift.path);
     }
+    if (!fieldDir.empty())
+        writeField(fieldDir, field.radius, pl);
     if (hostPlanes) {
         const double t1 = nowMs();
         st.planeRowsHost = hostPlanes->rows;
@@ -923,18 +1204,18 @@ int surveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCam
 
 int SurveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCams, const std::string &imageFormat,
               const std::string &reportPath, int nthreads, SurveyStats *stats, std::vector<SurveyRow> *rows,
-              std::vector<SurveyModel> *models, const SurveyPlanes &planes, const SurveyShift &shift)
+              std::vector<SurveyModel> *models, const SurveyPlanes &planes, const SurveyShift &shift, const SurveyField &field)
 {
-    return surveyRun(parser, trainers, numCams, imageFormat, reportPath, nthreads, -1, stats, rows, models, planes, shift);
+    return surveyRun(parser, trainers, numCams, imageFormat, reportPath, nthreads, -1, stats, rows, models, planes, shift, field);
 }
 
 int SurveyRunDevice(Parser *parser, const std::vector<Trainer *> &trainers, int numCams, const std::string &imageFormat,
                     const std::string &reportPath, int nthreads, int device, SurveyStats *stats, std::vector<SurveyRow> *rows,
-                    std::vector<SurveyModel> *models, const SurveyPlanes &planes, const SurveyShift &shift)
+                    std::vector<SurveyModel> *models, const SurveyPlanes &planes, const SurveyShift &shift, const SurveyField &field)
 {
     if (device < 0)
         throw std::runtime_error("survey: no such HIP device: " + std::to_string(device));
-    return surveyRun(parser, trainers, numCams, imageFormat, reportPath, nthreads, device, stats, rows, models, planes, shift);
+    return surveyRun(parser, trainers, numCams, imageFormat, reportPath, nthreads, device, stats, rows, models, planes, shift, field);
 }
 
 } // namespace abub

@@ -854,6 +854,34 @@ int abub_frame_shift_dev(const uint8_t *frames, size_t frames_bytes, const uint8
                          const abub_shift_job *jobs, int njobs, int W, int H, int R,
                          uint32_t *status /*[njobs]*/, uint64_t *sad /*[njobs * (2R+1)^2]*/, void *stream);
 
+/* ---- per-cell shift field of resident frames (abub_stats.hip) ---------------------------------------------------------
+ * Did a part of the image move, or the whole of it other than rigidly (abub3hs --survey --survey-field; definition, files
+ * and measurements: DESIGN section 3, "Surveying a run for local movement")?  The sums of abub_frame_shift_dev kept apart
+ * per cell of ABUB_FIELD_CELL x ABUB_FIELD_CELL interior pixels.  Only whole cells exist, centred in the interior:
+ * abub_frame_cells_grid gives ncx = floor((W - 2R) / 128), ncy = floor((H - 2R) / 128), x0 = R + floor(((W - 2R) - 128 ncx) / 2)
+ * and y0 likewise; a frame with W or H < 128 + 2R has ncx * ncy = 0 and no field.  It is the one copy of the rule: the
+ * launcher, the host definition and the tests call it.  It touches no device; ABUB_E_INVALID for a null pointer, R outside
+ * [1, 8] or a negative side.  For cell (cx, cy) of job j and every -R <= dx, dy <= R
+ *   sad[((j * ncy + cy) * ncx + cx) * (2R+1)^2 + (dy + R) * (2R+1) + (dx + R)] = sum of | p(x + dx, y + dy) - m(x, y) |  (u32)
+ * over x0 + 128 cx <= x < x0 + 128 (cx + 1), y0 + 128 cy <= y < y0 + 128 (cy + 1): 16384 pixels, at most 16384 * 255 < 2^32.
+ * Every value is an exact integer, bit-identical to the host definition (host/survey.cpp fieldCellsHost) whatever the
+ * order of the jobs or the blocks: one launch on `stream` of cells x jobs blocks, each reading its cell and halo once into
+ * LDS, summing as abub_frame_shift_dev does and writing the words of its cell's surface with plain stores.  Every output
+ * word has one owning workgroup: no atomics, no clearing launch, no host synchronisation, no allocation, no workgroup
+ * waiting for another.  What a surface means (best displacement, rated or not) is the host's to say (abub::fieldCell). */
+#define ABUB_FIELD_CELL 128
+int abub_frame_cells_grid(int W, int H, int R, int *ncx, int *ncy, int *x0, int *y0);
+/* Every pointer is a device pointer; jobs is 8-byte aligned, status and sad 4-byte aligned; R in [1, 8]; W and H in
+ * [128 + 2R, 65535].  No alignment rule on the offsets.  status[j] (0 or ABUB_SHIFT_E_RANGE) and all ncx * ncy * (2R+1)^2
+ * values of sad[j] are written in full by every call with njobs > 0, whatever they held before, and nothing else is
+ * written.  A job whose frame runs past frames_bytes or whose model plane runs past model_bytes gets ABUB_SHIFT_E_RANGE and
+ * a zero surface; nothing of it is read.  Null pointers, njobs < 0, R, W or H out of range (a frame without a whole cell
+ * included) or a misaligned jobs / status / sad: ABUB_E_INVALID before anything touches the device.  njobs == 0: ABUB_OK,
+ * nothing is touched. */
+int abub_frame_shift_cells_dev(const uint8_t *frames, size_t frames_bytes, const uint8_t *mu, size_t model_bytes,
+                               const abub_shift_job *jobs, int njobs, int W, int H, int R,
+                               uint32_t *status /*[njobs]*/, uint32_t *sad /*[njobs * ncy * ncx * (2R+1)^2]*/, void *stream);
+
 /* ---- the two DebugPeek planes of a batch of resident frames (abub_peek.hip) ------------------------------------------
  * What L3Localizer::CalculateInitialBubbleParams builds on the analyzer's thread for its debug write-out (reference
  * L3Localizer.cpp:252-257, 397, 448; DESIGN section 3, "The peek planes"), for a batch of items.  Per item two W x H u8
