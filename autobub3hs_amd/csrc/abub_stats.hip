@@ -1,6 +1,7 @@
 // abub_stats.hip -- per-frame statistics of resident frames: abub_frame_stats_dev (include/abub_hip.h, DESIGN section 3,
 // "Surveying a run"); below it the per-pixel planes (abub_pixel_activity_dev), the shift search (abub_frame_shift_dev) and
-// the per-cell shift field (abub_frame_shift_cells_dev), each under a header of its own.  What a byte loop over a decoded frame does on a host thread (host/survey.cpp frameStatsHost, the
+// the per-cell shift field (abub_frame_shift_cells_dev) and the per-cell light record (abub_frame_light_cells_dev), each
+// under a header of its own.  What a byte loop over a decoded frame does on a host thread (host/survey.cpp frameStatsHost, the
 // definition): per job the grey-level range, sum, sum of squares, black and saturated pixels of the frame, and against a
 // model (mu, sigma6) and a reference frame the count and sum of sat(|p - m| - s) and of sat(|p - r| - s).
 //
@@ -937,6 +938,118 @@ extern "C" int abub_frame_shift_cells_dev(const uint8_t *frames, size_t frames_b
                                      cells_launch<5>, cells_launch<6>, cells_launch<7>, cells_launch<8>};
     launch[R - 1](grid, (hipStream_t)stream, frames, (uint64_t)frames_bytes, mu, (uint64_t)model_bytes, jobs, njobs, (uint32_t)W,
                   (uint32_t)H, (uint32_t)ncx, (uint32_t)x0, (uint32_t)y0, status, sad);
+    HIPCHK(hipGetLastError());
+    return ABUB_OK;
+}
+
+// ---- per-cell light record: abub_frame_light_cells_dev ("Surveying a run for lighting changes") ----------
+// Per cell of FC_CELL x FC_CELL pixels on a grid the caller gives (x0, y0, ncx, ncy: abub_frame_cells_grid's, or any other
+// that lies inside the frame) six u32 sums over the cell's pixels p of the frame and m of mu (host/survey.cpp
+// lightCellsHost, the definition):
+//   rec[((j ncy + cy) ncx + cx) 6 + 0 .. 5] = sum p, sum p^2, sum p m, sum |p - m|, the pixels with p == 0, with p == 255.
+//
+// The grid is cells x jobs; a block of four waves owns one cell of one job at a time and with it the cell's six words: it
+// writes each of them once with a plain store, so there is no atomic, no clearing launch and no other launch (the block of
+// cell 0 writes the job's status word).  There is no halo and so no LDS tile: fc_cell's lane mapping (lane l owns dword
+// l & 31 of the rows 8 k + 2 w + (l >> 5), k < 16), p and m straight into registers through sh_load4.  Per dword: sum p is
+// v_sad_u8 against 0, sum |p - m| v_sad_u8(p, m), sum p^2 and sum p m v_dot4_u32_u8; the two counts are the set top bits of
+// ((x & 0x7f7f7f7f) + 0x7f7f7f7f | x | 0x7f7f7f7f) inverted, x = p and ~p: 0x7f + 0x7f = 0xfe never carries into the next
+// byte, so the test is exact per byte.  A lane sums 64 pixels (at most 64 * 65025 < 2^32), a cell 16384 (at most
+// 16384 * 65025 = 1065369600 < 2^31).  Summed over the wave with shuffles, over the waves through 24 words of LDS.
+//
+// Bounds.  A job is read only if sh_job_ok holds; otherwise E_RANGE and a zero record, found alike by every block of the
+// job.  The launcher admits only grids with x0 + 128 ncx <= W and y0 + 128 ncy <= H, so every dword a lane loads lies
+// wholly inside the W * H bytes of its stream; sh_load4 tests the index against W * H besides.  Stores: status[j] and
+// rec[(j * cells + cell) * 6 + t], j < njobs, cell < cells, t < 6.
+namespace {
+
+#define LC_WORDS 6u
+
+// 0x80 in every byte of x that is 0, 0 in the others (no carry crosses a byte)
+__device__ __forceinline__ uint32_t lc_zero_bytes(uint32_t x)
+{
+    return ~(((x & 0x7f7f7f7fu) + 0x7f7f7f7fu) | x | 0x7f7f7f7fu);
+}
+
+__global__ __launch_bounds__(FR_THREADS) void k_light_cells(const uint8_t *frames, uint64_t frames_bytes, const uint8_t *mu,
+                                                            uint64_t model_bytes, const abub_shift_job *__restrict__ jobs, int njobs,
+                                                            uint32_t W, uint32_t H, uint32_t ncx, uint32_t x0, uint32_t y0,
+                                                            uint32_t *__restrict__ status, uint32_t *__restrict__ rec)
+{
+    __shared__ uint32_t part[FR_THREADS / 64][LC_WORDS];
+    const uint64_t P = (uint64_t)W * H;
+    const uint32_t cell = blockIdx.x, cells = gridDim.x;
+    const uint32_t xc = x0 + (cell % ncx) * FC_CELL, yc = y0 + (cell / ncx) * FC_CELL; // the cell's first pixel
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t first = 2u * wave + (lane >> 5), col = lane & 31u;
+    for (uint32_t j = blockIdx.y; j < (uint32_t)njobs; j += gridDim.y) {
+        const abub_shift_job jb = jobs[j];
+        const bool ok = sh_job_ok(jb, frames_bytes, model_bytes, P); // (the same in every thread of every block of the job)
+        uint32_t *out = rec + ((uint64_t)j * cells + cell) * LC_WORDS;
+        if (cell == 0u && threadIdx.x == 0u)
+            status[j] = ok ? 0u : (uint32_t)ABUB_SHIFT_E_RANGE;
+        if (!ok) {
+            if (threadIdx.x < LC_WORDS)
+                out[threadIdx.x] = 0u;
+            continue;
+        }
+        const uint8_t *p = frames + jb.cur, *q = mu + jb.model;
+        uint32_t acc[LC_WORDS] = {0u, 0u, 0u, 0u, 0u, 0u};
+#pragma unroll
+        for (uint32_t r = 0; r < FC_ROWS; ++r) {
+            const uint64_t i = (uint64_t)(yc + r * 8u + first) * W + xc + 4u * col;
+            const uint32_t a = sh_load4(p, i, P), b = sh_load4(q, i, P);
+            acc[0] = __builtin_amdgcn_sad_u8(a, 0u, acc[0]);
+            acc[1] = __builtin_amdgcn_udot4(a, a, acc[1], false);
+            acc[2] = __builtin_amdgcn_udot4(a, b, acc[2], false);
+            acc[3] = __builtin_amdgcn_sad_u8(a, b, acc[3]);
+            acc[4] += (uint32_t)__builtin_popcount(lc_zero_bytes(a));
+            acc[5] += (uint32_t)__builtin_popcount(lc_zero_bytes(~a));
+        }
+#pragma unroll
+        for (int s = 32; s > 0; s >>= 1)
+#pragma unroll
+            for (uint32_t o = 0; o < LC_WORDS; ++o)
+                acc[o] += (uint32_t)__shfl_xor(acc[o], s);
+        if (lane == 0u) {
+#pragma unroll
+            for (uint32_t o = 0; o < LC_WORDS; ++o)
+                part[wave][o] = acc[o];
+        }
+        __syncthreads();
+        if (threadIdx.x < LC_WORDS) {
+            uint32_t v = part[0][threadIdx.x];
+#pragma unroll
+            for (int w = 1; w < FR_THREADS / 64; ++w)
+                v += part[w][threadIdx.x];
+            out[threadIdx.x] = v;
+        }
+        __syncthreads(); // (part is written again for the block's next job)
+    }
+}
+
+} // namespace
+
+extern "C" int abub_frame_light_cells_dev(const uint8_t *frames, size_t frames_bytes, const uint8_t *mu, size_t model_bytes,
+                                          const abub_shift_job *jobs, int njobs, int W, int H, int x0, int y0, int ncx, int ncy,
+                                          uint32_t *status, uint32_t *rec, void *stream)
+{
+    if (!frames || !mu || !jobs || !status || !rec || njobs < 0)
+        return set_err(ABUB_E_INVALID, "abub_frame_light_cells_dev: null pointer or negative count");
+    if (W < ABUB_FIELD_CELL || W > 65535 || H < ABUB_FIELD_CELL || H > 65535)
+        return set_err(ABUB_E_INVALID, "abub_frame_light_cells_dev: W and H must be in [128, 65535]");
+    // (ncx, ncy <= 511 once the sides are bounded, so the sums below cannot overflow an int)
+    if (ncx < 1 || ncy < 1 || ncx > W / ABUB_FIELD_CELL || ncy > H / ABUB_FIELD_CELL || x0 < 0 || y0 < 0 ||
+        x0 > W - ABUB_FIELD_CELL * ncx || y0 > H - ABUB_FIELD_CELL * ncy)
+        return set_err(ABUB_E_INVALID, "abub_frame_light_cells_dev: the grid of whole cells must lie inside the frame");
+    if (((uintptr_t)jobs & 7) || (((uintptr_t)status | (uintptr_t)rec) & 3))
+        return set_err(ABUB_E_INVALID, "abub_frame_light_cells_dev: jobs must be 8-byte aligned, status and rec 4-byte aligned");
+    if (njobs == 0)
+        return ABUB_OK;
+    const dim3 grid((unsigned)(ncx * ncy), (unsigned)(njobs < 65535 ? njobs : 65535)); // (at most 511 * 511 cells)
+    k_light_cells<<<grid, FR_THREADS, 0, (hipStream_t)stream>>>(frames, (uint64_t)frames_bytes, mu, (uint64_t)model_bytes, jobs, njobs,
+                                                                (uint32_t)W, (uint32_t)H, (uint32_t)ncx, (uint32_t)x0, (uint32_t)y0, status,
+                                                                rec);
     HIPCHK(hipGetLastError());
     return ABUB_OK;
 }

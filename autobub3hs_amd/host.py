@@ -73,6 +73,11 @@ SIGNATURES = {
     "abh_shift_best": (None, [_u64p, _i, C.POINTER(_i)]),
     "abh_run_survey_field": (_i, [_vp, _s, _s, _s, _i, _s, _i, _i, _i, _dp, _dp, _dp, _dp, C.c_char_p, _i]),
     "abh_run_survey_field_dev": (_i, [_vp, _s, _s, _s, _i, _s, _i, _i, _i, _i, _dp, _dp, _dp, _dp, C.c_char_p, _i]),
+    "abh_run_survey_light": (_i, [_vp, _s, _s, _s, _i, _s, _i, _s, _i, _i, _dp, _dp, _dp, _dp, _dp, C.c_char_p, _i]),
+    "abh_run_survey_light_dev": (_i, [_vp, _s, _s, _s, _i, _s, _i, _s, _i, _i, _i, _dp, _dp, _dp, _dp, _dp, C.c_char_p, _i]),
+    "abh_light_cells_host": (_i, [_u8p, _u8p, _i, _i, _i, _i, _i, _i, _u32p]),
+    "abh_light_model_host": (_i, [_u8p, _u8p, _i, _i, _i, _i, _i, _i, _u32p]),
+    "abh_light_frame": (None, [_u32p, _u32p, _i, C.POINTER(C.c_longlong)]),
     "abh_field_grid": (_i, [_i, _i, _i, C.POINTER(_i)]),
     "abh_field_cells_host": (_i, [_u8p, _u8p, _i, _i, _i, _u32p, C.POINTER(C.c_int32)]),
     "abh_activity_add_host": (None, [C.POINTER(C.c_uint32), _u8p, _u8p, _u8p, _u8p, C.c_uint64]),
@@ -452,7 +457,7 @@ class Run:
                     "W", "H", "batches", "model_cams")
 
     def survey(self, path=None, nthreads=16, ncams=4, device=None, planes=None, shift=None, shift_radius=4, field=None,
-               field_radius=4):
+               field_radius=4, light=None):
         """abub3hs --survey of this run (opened from a directory or an archive): the run is listed and trained as for
         detect, then every frame of cameras 0 .. ncams-1 is measured without analysing any; the report (DESIGN section 3,
         "Surveying a run") is written to `path` (None: it is not written).  device=None: host threads (cv::imdecode and
@@ -472,16 +477,33 @@ class Run:
         field (--survey-field): the directory (the CLI's DIR/<run_ID>) that gets the per-cell shift field (DESIGN section 3,
         "Surveying a run for local movement"): cam<c>_field.npy and field.txt, the same rows searched per cell of 128 x 128
         pixels within field_radius (1 to 8), the same bytes on both routes; the stats then also have field_frames_kernel /
-        field_frames_host, field_launches and the legs field_s and field_host_s.  Nothing else changes."""
+        field_frames_host, field_launches and the legs field_s and field_host_s.  Nothing else changes.
+        light (--survey-light): the directory (the CLI's DIR/<run_ID>) that gets the per-cell light records (DESIGN section 3,
+        "Surveying a run for lighting changes"): cam<c>_light.npy, cam<c>_light_model.npy and light.txt, the same rows summed
+        per cell of the field's grid at field_radius (whether or not field is given), the same bytes on both routes; the
+        stats then also have light_frames_kernel / light_frames_host, light_launches and the legs light_s and light_host_s.
+        Nothing else changes."""
         L = lib()
         st = (C.c_double * 24)()
         pst = (C.c_double * 5)()
         sst = (C.c_double * 5)()
         fst = (C.c_double * 5)()
+        lst = (C.c_double * 5)()
         cap = 1 << 16
         buf = C.create_string_buffer(cap)
         to = None if path is None else str(path).encode()
-        if field is not None:
+        if light is not None:
+            pd = None if planes is None else str(planes).encode()
+            sp = None if shift is None else str(shift).encode()
+            fd = None if field is None else str(field).encode()
+            ld = str(light).encode()
+            if device is None:
+                rc = L.abh_run_survey_light(self._h, to, pd, sp, int(shift_radius), fd, int(field_radius), ld, ncams, nthreads, st, pst,
+                                            sst, fst, lst, buf, cap)
+            else:
+                rc = L.abh_run_survey_light_dev(self._h, to, pd, sp, int(shift_radius), fd, int(field_radius), ld, ncams, nthreads,
+                                                int(device), st, pst, sst, fst, lst, buf, cap)
+        elif field is not None:
             pd = None if planes is None else str(planes).encode()
             sp = None if shift is None else str(shift).encode()
             fd = str(field).encode()
@@ -523,6 +545,9 @@ class Run:
         if field is not None:
             res.update(field_frames_kernel=int(fst[0]), field_frames_host=int(fst[1]), field_launches=int(fst[2]), field_s=fst[3],
                        field_host_s=fst[4])
+        if light is not None:
+            res.update(light_frames_kernel=int(lst[0]), light_frames_host=int(lst[1]), light_launches=int(lst[2]), light_s=lst[3],
+                       light_host_s=lst[4])
         return res, text.decode()
 
     def analyze(self, event, cam, maskdir=""):
@@ -605,6 +630,48 @@ def field_cells_host(p, m, R):
                                                     sad.ctypes.data_as(_u32p), rec.ctypes.data_as(C.POINTER(C.c_int32))) != ncx * ncy:
         raise ValueError(f"abh_field_cells_host refuses {p.shape[1]}x{p.shape[0]} at radius {R}")
     return sad, rec
+
+
+LIGHT_KINDS = ("blind", "steady", "level", "uneven")
+
+
+def _light_call(fn, a, b, x0, y0, ncx, ncy, words):
+    a, b = (np.ascontiguousarray(v, dtype=np.uint8) for v in (a, b))
+    assert a.ndim == 2 and a.shape == b.shape
+    rec = np.zeros((max(ncy, 0), max(ncx, 0), words), np.uint32)
+    if fn(a.ctypes.data_as(_u8p), b.ctypes.data_as(_u8p), a.shape[1], a.shape[0], int(x0), int(y0), int(ncx), int(ncy),
+          rec.ctypes.data_as(_u32p)) != ncx * ncy or ncx * ncy <= 0:
+        raise ValueError(f"the grid {ncx}x{ncy} from ({x0}, {y0}) does not lie inside {a.shape[1]}x{a.shape[0]}")
+    return rec
+
+
+def light_cells_host(p, m, x0, y0, ncx, ncy):
+    """abub::lightCellsHost (host/survey.cpp), the definition of abub_frame_light_cells_dev: the frame p and the model
+    plane m, u8 [H, W], on the grid of ncx x ncy cells of 128 x 128 pixels from (x0, y0) -> uint32 [ncy, ncx, 6]: the
+    sums of p, p^2, p m and |p - m|, the pixels with p == 0 and with p == 255."""
+    return _light_call(lib().abh_light_cells_host, p, m, x0, y0, ncx, ncy, 6)
+
+
+def light_model_host(mu, sigma6, x0, y0, ncx, ncy):
+    """abub::lightModelHost: the model planes mu and sigma6, u8 [H, W], on the same grid -> uint32 [ncy, ncx, 3]: the sums
+    of mu, mu^2 and sigma6."""
+    return _light_call(lib().abh_light_model_host, mu, sigma6, x0, y0, ncx, ncy, 3)
+
+
+def light_frame(rec, model):
+    """abub::lightFrame: what a frame's records [..., 6] say against the model's [..., 3] -> dict: rated, clipped, changed,
+    up, down, kind (a word of LIGHT_KINDS), and level_milli, ratio_min, ratio_max, gain_milli, offset_milli (None where
+    light.txt has '-')."""
+    rec = np.ascontiguousarray(rec, dtype=np.uint32).reshape(-1, 6)
+    model = np.ascontiguousarray(model, dtype=np.uint32).reshape(-1, 3)
+    assert len(rec) == len(model)
+    out = (C.c_longlong * 12)()
+    lib().abh_light_frame(rec.ctypes.data_as(_u32p), model.ctypes.data_as(_u32p), len(rec), out)
+    v = list(out)
+    blind, gain = v[5] == 0, bool(v[6])
+    return {"rated": v[0], "clipped": v[1], "changed": v[2], "up": v[3], "down": v[4], "kind": LIGHT_KINDS[v[5]],
+            "level_milli": None if blind else v[7], "ratio_min": None if blind else v[8], "ratio_max": None if blind else v[9],
+            "gain_milli": v[10] if gain else None, "offset_milli": v[11] if gain else None}
 
 
 def zip_write(path, entries):

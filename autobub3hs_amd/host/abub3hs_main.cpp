@@ -36,6 +36,7 @@ static std::string usage()
            "       abub3hs [-z] [-D data_series] -d data_dir -r run_ID --survey FILE [--survey-gpu] [--survey-planes DIR]\n"
            "               [--survey-shift FILE [--survey-shift-radius R]]\n"
            "               [--survey-field DIR [--survey-field-radius R]]\n"
+           "               [--survey-light DIR [--survey-field-radius R]]\n"
            "Run the AutoBub3hs bubble finding algorithm on a PICO run (MI355X hot path)\n\n"
            "Required arguments:\n"
            "  -d, --data_dir = Dir\t\tpath to the directory in which the run folder/file is stored\n"
@@ -119,7 +120,19 @@ static std::string usage()
            "\t\t\t\tframes in which it moved; the same bytes with --survey-gpu; the report, the planes and the shift\n"
            "\t\t\t\tfile do not change\n"
            "  --survey-field-radius = R\twith --survey-field: the radius of the search in pixels, 1 to 8 (4); the frames must be at\n"
-           "\t\t\t\tleast 128 + 2 R wide and high\n"
+           "\t\t\t\tleast 128 + 2 R wide and high; with --survey-light, with or without --survey-field: the radius\n"
+           "\t\t\t\tthat places the cells\n"
+           "  --survey-light = Dir\t\twith --survey: also sum the same frames per cell of the field's grid (the cells of\n"
+           "\t\t\t\t--survey-field at --survey-field-radius, 4 unless given, whether or not the field is written) and\n"
+           "\t\t\t\twrite into Dir/<run_ID>/ cam<c>_light.npy (i32 [frames, cells down, cells across, 6]: per cell the\n"
+           "\t\t\t\tsums of p, p^2, p mu and |p - mu|, the black and the saturated pixels), cam<c>_light_model.npy\n"
+           "\t\t\t\t(i32 [cells down, cells across, 3]: the sums of mu, mu^2 and min(6 sigma, 255)) and light.txt: per\n"
+           "\t\t\t\tframe how many cells are rated, clipped and changed (the mean level moved by more than the mean\n"
+           "\t\t\t\t6 sigma), up or down, the level in thousandths of a grey level, the range of the cells' ratios in\n"
+           "\t\t\t\tthousandths, the pooled gain and offset in thousandths, and the frame's kind (blind, steady, level,\n"
+           "\t\t\t\tuneven); per camera and for the run the counts of each kind and per cell the frames in which it\n"
+           "\t\t\t\tchanged; the same bytes with --survey-gpu; the report, the planes, the shift file and the field do\n"
+           "\t\t\t\tnot change\n"
            "Environment: ABUB_TRAIN_ON_GPU=0 trains the runs of a campaign with the host Trainer\n"
            "             ABUB_REPACK_BATCH=n (a test knob) lowers the frames per batch of --repack-gpu and --unpack-gpu to n; the files\n"
            "             are the same\n"
@@ -301,6 +314,8 @@ int main(int argc, char **argv)
     std::string surveyFieldDir; // --survey-field DIR: the survey's per-cell shift field goes to DIR/<run_ID>/
     bool haveSurveyField = false, haveFieldRadius = false;
     int surveyFieldRadius = 4;
+    std::string surveyLightDir; // --survey-light DIR: the survey's per-cell light records go to DIR/<run_ID>/
+    bool haveSurveyLight = false;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i], v;
         auto value = [&](std::string &dst) {
@@ -429,6 +444,9 @@ int main(int argc, char **argv)
         } else if (a == "--survey-field" || a.rfind("--survey-field=", 0) == 0) {
             value(surveyFieldDir);
             haveSurveyField = true;
+        } else if (a == "--survey-light" || a.rfind("--survey-light=", 0) == 0) {
+            value(surveyLightDir);
+            haveSurveyLight = true;
         } else if (a == "--per-event") {
             perEvent = true;
         } else if (a == "--peek" || a.rfind("--peek=", 0) == 0) {
@@ -476,7 +494,11 @@ int main(int argc, char **argv)
         std::cerr << "--survey-field is valid only together with --survey" << std::endl;
         return -1;
     }
-    if (haveFieldRadius && !haveSurveyField) {
+    if (haveSurveyLight && !haveSurvey) {
+        std::cerr << "--survey-light is valid only together with --survey" << std::endl;
+        return -1;
+    }
+    if (haveFieldRadius && !haveSurveyField && !haveSurveyLight) { // (the light's cells are the field's)
         std::cerr << "--survey-field-radius is valid only together with --survey-field" << std::endl;
         return -1;
     }
@@ -502,6 +524,10 @@ int main(int argc, char **argv)
         }
         if (haveSurveyField && surveyFieldDir.empty()) {
             std::cerr << "--survey-field needs the directory to write to" << std::endl;
+            return -1;
+        }
+        if (haveSurveyLight && surveyLightDir.empty()) {
+            std::cerr << "--survey-light needs the directory to write to" << std::endl;
             return -1;
         }
     }
@@ -689,6 +715,12 @@ int main(int argc, char **argv)
             field.srcRunDir = zipped ? std::string() : sp.eventDir;
             field.radius = surveyFieldRadius;
         }
+        abub::SurveyLight light;
+        if (haveSurveyLight) {
+            light.dir = surveyLightDir + "/" + run_number;
+            light.srcRunDir = zipped ? std::string() : sp.eventDir;
+            field.radius = surveyFieldRadius; // (the grid's radius, whether or not the field is written)
+        }
         int rc = 1;
         try {
             abub::PreparedRun prep = abub::PrepareRun(sp, po, 0, nullptr, false);
@@ -697,9 +729,9 @@ int main(int argc, char **argv)
             if (prep.rc)
                 printf("survey: a camera did not train: the report has no model columns for it\n");
             rc = surveyGpu ? abub::SurveyRunDevice(prep.parser.get(), prep.trainers, sp.numCams, sp.imageFormat, surveyFile, poolThreads(), 0,
-                                                   &ss, nullptr, nullptr, planes, shift, field)
+                                                   &ss, nullptr, nullptr, planes, shift, field, light)
                            : abub::SurveyRun(prep.parser.get(), prep.trainers, sp.numCams, sp.imageFormat, surveyFile, poolThreads(), &ss,
-                                             nullptr, nullptr, planes, shift, field);
+                                             nullptr, nullptr, planes, shift, field, light);
         } catch (std::exception &e) {
             std::cerr << "survey failed: " << e.what() << std::endl;
             return -6;
@@ -735,6 +767,10 @@ int main(int argc, char **argv)
             printf("survey-field: %s: radius %d, %lld frames searched on the GPU in %d launches, %lld on the host; field leg %.3f s, host "
                    "threads %.3f s\n",
                    field.dir.c_str(), field.radius, ss.fieldFramesKernel, ss.fieldLaunches, ss.fieldFramesHost, ss.field_s, ss.fieldHost_s);
+        if (haveSurveyLight)
+            printf("survey-light: %s: radius %d, %lld frames summed on the GPU in %d launches, %lld on the host; light leg %.3f s, host "
+                   "threads %.3f s\n",
+                   light.dir.c_str(), field.radius, ss.lightFramesKernel, ss.lightLaunches, ss.lightFramesHost, ss.light_s, ss.lightHost_s);
         return rc;
     }
     if (haveList) {

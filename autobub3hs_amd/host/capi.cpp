@@ -408,10 +408,14 @@ const char *abh_run_verify_report(void *src)
 // abh_run_survey_field[_dev]: the same with the per-cell shift field (abub::SurveyField; DESIGN section 3, "Surveying a run
 // for local movement") written to field_dir (the CLI's DIR/<run_ID>; NULL or empty: none) at radius field_radius (1 to 8),
 // and field_stats (may be NULL, 5 values): the shift's five for abub_frame_shift_cells_dev and fieldCellsHost.
+// abh_run_survey_light[_dev]: the same with the per-cell light records (abub::SurveyLight; DESIGN section 3, "Surveying a run
+// for lighting changes") written to light_dir (the CLI's DIR/<run_ID>; NULL or empty: none) on the grid of field_radius,
+// whether or not field_dir is given, and light_stats (may be NULL, 5 values): the same five for abub_frame_light_cells_dev
+// and lightCellsHost.
 static int runSurvey(void *r, const char *path, int ncams, int nthreads, int device, bool onDevice, double *stats, char *report,
                      int report_cap, const char *planes_dir = nullptr, double *plane_stats = nullptr, const char *shift_path = nullptr,
                      int shift_radius = 4, double *shift_stats = nullptr, const char *field_dir = nullptr, int field_radius = 4,
-                     double *field_stats = nullptr)
+                     double *field_stats = nullptr, const char *light_dir = nullptr, double *light_stats = nullptr)
 {
     Run *run = (Run *)r;
     try {
@@ -444,10 +448,17 @@ static int runSurvey(void *r, const char *path, int ncams, int nthreads, int dev
         field.dir = field_dir ? field_dir : "";
         field.srcRunDir = planes.srcRunDir;
         field.radius = field_radius;
+        abub::SurveyLight light;
+        light.dir = light_dir ? light_dir : "";
+        light.srcRunDir = planes.srcRunDir;
         const int rc = onDevice ? abub::SurveyRunDevice(pr.parser.get(), pr.trainers, ncams, sp.imageFormat, to, std::max(1, nthreads),
-                                                        device, &st, &rows, &models, planes, shift, field)
+                                                        device, &st, &rows, &models, planes, shift, field, light)
                                 : abub::SurveyRun(pr.parser.get(), pr.trainers, ncams, sp.imageFormat, to, std::max(1, nthreads), &st,
-                                                  &rows, &models, planes, shift, field);
+                                                  &rows, &models, planes, shift, field, light);
+        if (light_stats) {
+            const double v[5] = {(double)st.lightFramesKernel, (double)st.lightFramesHost, (double)st.lightLaunches, st.light_s, st.lightHost_s};
+            std::memcpy(light_stats, v, sizeof v);
+        }
         if (field_stats) {
             const double v[5] = {(double)st.fieldFramesKernel, (double)st.fieldFramesHost, (double)st.fieldLaunches, st.field_s, st.fieldHost_s};
             std::memcpy(field_stats, v, sizeof v);
@@ -529,6 +540,21 @@ int abh_run_survey_field_dev(void *r, const char *path, const char *planes_dir, 
     return runSurvey(r, path, ncams, nthreads, device, true, stats, report, report_cap, planes_dir, plane_stats, shift_path, shift_radius,
                      shift_stats, field_dir, field_radius, field_stats);
 }
+int abh_run_survey_light(void *r, const char *path, const char *planes_dir, const char *shift_path, int shift_radius, const char *field_dir,
+                         int field_radius, const char *light_dir, int ncams, int nthreads, double *stats, double *plane_stats,
+                         double *shift_stats, double *field_stats, double *light_stats, char *report, int report_cap)
+{
+    return runSurvey(r, path, ncams, nthreads, -1, false, stats, report, report_cap, planes_dir, plane_stats, shift_path, shift_radius,
+                     shift_stats, field_dir, field_radius, field_stats, light_dir, light_stats);
+}
+int abh_run_survey_light_dev(void *r, const char *path, const char *planes_dir, const char *shift_path, int shift_radius,
+                             const char *field_dir, int field_radius, const char *light_dir, int ncams, int nthreads, int device,
+                             double *stats, double *plane_stats, double *shift_stats, double *field_stats, double *light_stats,
+                             char *report, int report_cap)
+{
+    return runSurvey(r, path, ncams, nthreads, device, true, stats, report, report_cap, planes_dir, plane_stats, shift_path, shift_radius,
+                     shift_stats, field_dir, field_radius, field_stats, light_dir, light_stats);
+}
 // the whole report of the last abh_run_survey[_dev] on the run (valid until the next query on it)
 const char *abh_run_survey_report(void *r)
 {
@@ -591,6 +617,40 @@ int abh_field_cells_host(const uint8_t *p, const uint8_t *m, int W, int H, int R
     for (size_t k = 0; k < cells; ++k)
         abub::fieldCell(sad + k * N, R, rec + k * abub::FieldRecordWords);
     return (int)cells;
+}
+
+// do ncx x ncy whole cells of 128 x 128 pixels from (x0, y0) lie inside a W x H frame?
+static bool lightGridInside(int W, int H, int x0, int y0, int ncx, int ncy)
+{
+    const int C = ABUB_FIELD_CELL;
+    return W >= C && H >= C && ncx >= 1 && ncy >= 1 && ncx <= W / C && ncy <= H / C && x0 >= 0 && y0 >= 0 && x0 <= W - C * ncx &&
+           y0 <= H - C * ncy;
+}
+// abub::lightCellsHost / abub::lightModelHost on raw buffers: the W x H frame p against the model plane m (mu, sigma6) on
+// the grid of ncx x ncy cells of 128 x 128 pixels from (x0, y0) -> rec[ncy * ncx * 6] / rec[ncy * ncx * 3]; returns the
+// number of cells, or -1 (nothing written) for a null pointer or a grid that does not lie inside the frame
+int abh_light_cells_host(const uint8_t *p, const uint8_t *m, int W, int H, int x0, int y0, int ncx, int ncy, uint32_t *rec)
+{
+    if (!p || !m || !rec || !lightGridInside(W, H, x0, y0, ncx, ncy))
+        return -1;
+    abub::lightCellsHost(p, m, W, H, x0, y0, ncx, ncy, rec);
+    return ncx * ncy;
+}
+int abh_light_model_host(const uint8_t *mu, const uint8_t *sigma6, int W, int H, int x0, int y0, int ncx, int ncy, uint32_t *rec)
+{
+    if (!mu || !sigma6 || !rec || !lightGridInside(W, H, x0, y0, ncx, ncy))
+        return -1;
+    abub::lightModelHost(mu, sigma6, W, H, x0, y0, ncx, ncy, rec);
+    return ncx * ncy;
+}
+// abub::lightFrame on raw buffers, what a frame's records say against the model's: out[12] = rated, clipped, changed, up,
+// down, kind (0 blind, 1 steady, 2 level, 3 uneven), has_gain, level_milli, ratio_min, ratio_max, gain_milli, offset_milli
+void abh_light_frame(const uint32_t *rec, const uint32_t *model, int cells, long long *out)
+{
+    const abub::LightFrame f = abub::lightFrame(rec, model, (size_t)std::max(cells, 0));
+    const long long v[12] = {f.rated, f.clipped, f.changed, f.up, f.down, f.kind, f.hasGain ? 1 : 0, f.levelMilli, f.ratioMin, f.ratioMax,
+                             f.gainMilli, f.offsetMilli};
+    std::memcpy(out, v, sizeof v);
 }
 
 // bmpWalk (host/bmpwalk.hpp: what the reading threads learn about a BMP before the GPU decodes it): 1 = a file decodeBMP

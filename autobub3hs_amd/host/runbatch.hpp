@@ -244,6 +244,36 @@ void fieldCell(const uint32_t *sad, int R, int32_t *rec);
 // mismatch.  A flat cell, where every displacement scores alike, is not.
 inline bool fieldRated(const int32_t *rec) { return rec[4] > 0 && 2 * (int64_t)rec[3] <= (int64_t)rec[4]; }
 
+// The definition of abub_frame_light_cells_dev ("Surveying a run for lighting changes"): per cell of
+// 128 x 128 pixels of the grid (ncx x ncy whole cells, the first at (x0, y0); the survey's is abub_frame_cells_grid's) six
+// u32 over the cell's pixels p of the frame and m of mu: rec[(cy * ncx + cx) * 6 + 0 .. 5] = sum p, sum p^2, sum p m,
+// sum |p - m|, pixels with p == 0, pixels with p == 255.  Plain loops; at most 16384 * 255^2 < 2^31.
+enum { LightRecordWords = 6, LightModelWords = 3 };
+void lightCellsHost(const unsigned char *p, const unsigned char *m, int W, int H, int x0, int y0, int ncx, int ncy, uint32_t *rec);
+// The model's share, which depends on the camera alone: rec[(cy * ncx + cx) * 3 + 0 .. 2] = sum m, sum m^2, sum sigma6
+void lightModelHost(const unsigned char *mu, const unsigned char *sigma6, int W, int H, int x0, int y0, int ncx, int ncy, uint32_t *rec);
+// rdiv(a, b) = floor((2 a + b) / (2 b)), b > 0, floor toward minus infinity: a / b rounded to the nearest, a half upward
+long long lightRdiv(__int128 a, __int128 b);
+// What a cell says, from its frame record and its model record (one function for both routes; integers only).  With
+// N = 16384: rated iff sm >= N and n_zero + n_sat <= N / 16; clipped iff sm >= N and not so; of a rated cell
+// ratio = rdiv(1000 sp, sm), changed iff |sp - sm| > ss6 (its mean level moved by more than its mean 6 sigma), up iff sp > sm
+struct LightCell {
+    bool rated = false, clipped = false, changed = false, up = false;
+    long long ratio = 0;
+};
+LightCell lightCell(const uint32_t *rec, const uint32_t *model);
+// What a frame says, from its rated cells (n = N * rated, S* pooled over them): level_milli = rdiv(1000 (Ssp - Ssm), n),
+// the range of the ratios, and the pooled fit p = gain * m + offset: var = n Ssmm - Ssm^2, cov = n Sspm - Ssp Ssm, with
+// var > 0 gain_milli = rdiv(1000 cov, var) and offset_milli = rdiv(1000 Ssp - gain_milli Ssm, n), else hasGain false.
+// kind: blind (no rated cell), steady (none of them changed), level (all changed, in one direction), uneven (the rest)
+struct LightFrame {
+    enum Kind { Blind = 0, Steady = 1, Level = 2, Uneven = 3 };
+    int rated = 0, clipped = 0, changed = 0, up = 0, down = 0, kind = Blind;
+    bool hasGain = false;
+    long long levelMilli = 0, ratioMin = 0, ratioMax = 0, gainMilli = 0, offsetMilli = 0;
+};
+LightFrame lightFrame(const uint32_t *rec, const uint32_t *model, size_t cells);
+
 // One row of a survey: a frame the run lists, or one it should list (missing)
 struct SurveyRow {
     enum State { Ok = 0, Undecodable = 1, Missing = 2, OtherSize = 3 };
@@ -257,6 +287,8 @@ struct SurveyRow {
     ShiftBest shift;
     bool hasField = false, fieldOnKernel = false; // with a field directory: the same rows have their cells' records
     std::vector<int32_t> field;                   // [ncy][ncx][5]
+    bool hasLight = false, lightOnKernel = false; // with a light directory: the same rows have their cells' light records
+    std::vector<uint32_t> light;                  // [ncy][ncx][6]
     const char *stateName() const; // "ok", "undecodable", "missing", "other_size"
 };
 // What the report says of one camera's model
@@ -265,6 +297,7 @@ struct SurveyModel {
     int trainingSetSize = 0, sigmaMax = 0;
     long long pixels = 0, sigmaZero = 0, sigma6Sat = 0; // pixels with sigma == 0; with 6 sigma >= 255
     double muMean = 0;
+    std::vector<uint32_t> light; // with a light directory, of a trained camera: lightModelHost's [ncy][ncx][3]
 };
 struct SurveyStats {
     int events = 0;
@@ -292,6 +325,10 @@ struct SurveyStats {
     long long fieldFramesKernel = 0, fieldFramesHost = 0;
     int fieldLaunches = 0;
     double field_s = 0, fieldHost_s = 0;
+    // With a light directory: the same five for abub_frame_light_cells_dev and lightCellsHost
+    long long lightFramesKernel = 0, lightFramesHost = 0;
+    int lightLaunches = 0;
+    double light_s = 0, lightHost_s = 0;
 };
 // Where a survey writes its per-pixel activity planes (abub3hs --survey-planes; DESIGN section 3, "Surveying a run per
 // pixel"): the directory `dir` (the CLI's DIR/<run_ID>; empty: no planes) gets cam<c>_activity.npy (u32 [6, H, W]) for
@@ -315,6 +352,18 @@ struct SurveyField {
     std::string dir, srcRunDir;
     int radius = 4;
 };
+// Where a survey writes its per-cell light records (abub3hs --survey-light; DESIGN section 3, "Surveying a run for lighting
+// changes"): the directory `dir` (the CLI's DIR/<run_ID>; empty: none) gets cam<c>_light.npy (i32 [N_c, ncy, ncx, 6]: the
+// records of camera c's rows that have one, in survey order) and cam<c>_light_model.npy (i32 [ncy, ncx, 3]) for every camera
+// with a model, and light.txt.  The cells are the field's: abub_frame_cells_grid at SurveyField::radius, whether or not the
+// field is written; a run without a whole cell is refused before its frames are measured.
+struct SurveyLight {
+    std::string dir, srcRunDir;
+};
+// light.txt's text: "# abub3hs light 1", the grid's line, the table's header and one tab-separated row per survey row, one
+// `light cam` line per camera, the `changed` lines of every camera with a model, the `run` line.  Both routes write it
+// through this one function; W, H: the run's size; models[c].light: the camera's model record.
+std::string LightReport(int radius, int W, int H, const std::vector<SurveyModel> &models, const std::vector<SurveyRow> &rows);
 // field.txt's text: "# abub3hs field 1", the grid's line, the table's header and one tab-separated row per survey row, one
 // `field cam` line per camera, the `moved` lines of every camera with a model, the `run` line.  Both routes write it through
 // this one function; W, H: the run's size.
@@ -340,10 +389,14 @@ std::string SurveyReport(const std::vector<SurveyModel> &models, const std::vect
 // With field.dir the same rows also get their per-cell records (fieldCellsHost here; on the device route
 // abub_frame_shift_cells_dev behind the statistics and the shift launch) and the field's files are written (both routes: the
 // same bytes).  The report, the planes and the shift file do not change.
+// With light.dir the same rows also get their per-cell light records (lightCellsHost here; on the device route
+// abub_frame_light_cells_dev behind the launches above) and the light's files are written (both routes: the same bytes).
+// Nothing else changes.
 int SurveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCams, const std::string &imageFormat,
               const std::string &reportPath, int nthreads, SurveyStats *stats, std::vector<SurveyRow> *rows,
               std::vector<SurveyModel> *models = nullptr, const SurveyPlanes &planes = SurveyPlanes(),
-              const SurveyShift &shift = SurveyShift(), const SurveyField &field = SurveyField());
+              const SurveyShift &shift = SurveyShift(), const SurveyField &field = SurveyField(),
+              const SurveyLight &light = SurveyLight());
 // abub3hs --survey FILE --survey-gpu: the same rows and the same report, byte for byte.  The frames are read through the
 // FileBatch protocol (framefiles.hpp) in batches of at most 4 frames per CU (ABUB_SURVEY_BATCH=n: of n), decoded into the
 // batch's slab, and measured by one abub_frame_stats_dev launch per batch.  A batch that begins inside a stack reads again
@@ -354,7 +407,8 @@ int SurveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCam
 int SurveyRunDevice(Parser *parser, const std::vector<Trainer *> &trainers, int numCams, const std::string &imageFormat,
                     const std::string &reportPath, int nthreads, int device, SurveyStats *stats, std::vector<SurveyRow> *rows,
                     std::vector<SurveyModel> *models = nullptr, const SurveyPlanes &planes = SurveyPlanes(),
-                    const SurveyShift &shift = SurveyShift(), const SurveyField &field = SurveyField());
+                    const SurveyShift &shift = SurveyShift(), const SurveyField &field = SurveyField(),
+              const SurveyLight &light = SurveyLight());
 
 // A run listed and trained, ready for detect; rc = -5 (the run cannot be read) or -7 (a camera did not train)
 struct PreparedRun {

@@ -17,6 +17,10 @@
 // searched per cell of 128 x 128 pixels: fieldCellsHost is the definition of the cells' surfaces, the device route gets them
 // from abub_frame_shift_cells_dev, fieldCell reads every surface on the host into a record of five words, and one writer
 // (writeField, with FieldReport for the text) makes the files for both routes.
+// With a light directory (--survey-light; DESIGN section 3, "Surveying a run for lighting changes") the same rows also get
+// six sums per cell of the field's grid: lightCellsHost is the definition, the device route gets the records from
+// abub_frame_light_cells_dev, lightModelHost sums the model once per camera on the host, lightCell and lightFrame say what
+// the sums mean, and one writer (writeLight, with LightReport for the text) makes the files for both routes.
 #include <algorithm>
 #include <cinttypes>
 #include <cmath>
@@ -168,6 +172,199 @@ void fieldCell(const uint32_t *sad, int R, int32_t *rec)
     rec[2] = (int32_t)b.sad0;
     rec[3] = (int32_t)b.sadBest;
     rec[4] = (int32_t)*std::max_element(sad, sad + N);
+}
+
+void lightCellsHost(const unsigned char *p, const unsigned char *m, int W, int H, int x0, int y0, int ncx, int ncy, uint32_t *rec)
+{
+    (void)H;
+    const int C = ABUB_FIELD_CELL;
+    for (int cy = 0; cy < ncy; ++cy)
+        for (int cx = 0; cx < ncx; ++cx) {
+            uint32_t sp = 0, spp = 0, spm = 0, sad = 0, nZero = 0, nSat = 0; // (at most 16384 * 255^2 < 2^31)
+            for (int y = y0 + C * cy; y < y0 + C * (cy + 1); ++y) {
+                const unsigned char *pr = p + (size_t)y * W, *mr = m + (size_t)y * W;
+                for (int x = x0 + C * cx; x < x0 + C * (cx + 1); ++x) {
+                    const uint32_t a = pr[x], b = mr[x];
+                    sp += a;
+                    spp += a * a;
+                    spm += a * b;
+                    sad += a > b ? a - b : b - a;
+                    nZero += a == 0;
+                    nSat += a == 255;
+                }
+            }
+            uint32_t *out = rec + ((size_t)cy * ncx + cx) * LightRecordWords;
+            out[0] = sp;
+            out[1] = spp;
+            out[2] = spm;
+            out[3] = sad;
+            out[4] = nZero;
+            out[5] = nSat;
+        }
+}
+
+void lightModelHost(const unsigned char *mu, const unsigned char *sigma6, int W, int H, int x0, int y0, int ncx, int ncy, uint32_t *rec)
+{
+    (void)H;
+    const int C = ABUB_FIELD_CELL;
+    for (int cy = 0; cy < ncy; ++cy)
+        for (int cx = 0; cx < ncx; ++cx) {
+            uint32_t sm = 0, smm = 0, ss6 = 0;
+            for (int y = y0 + C * cy; y < y0 + C * (cy + 1); ++y)
+                for (int x = x0 + C * cx; x < x0 + C * (cx + 1); ++x) {
+                    const uint32_t b = mu[(size_t)y * W + x];
+                    sm += b;
+                    smm += b * b;
+                    ss6 += sigma6[(size_t)y * W + x];
+                }
+            uint32_t *out = rec + ((size_t)cy * ncx + cx) * LightModelWords;
+            out[0] = sm;
+            out[1] = smm;
+            out[2] = ss6;
+        }
+}
+
+long long lightRdiv(__int128 a, __int128 b)
+{
+    const __int128 n = 2 * a + b, d = 2 * b;
+    __int128 q = n / d; // (truncates toward 0: one less where the remainder is negative)
+    if (n % d < 0)
+        --q;
+    return (long long)q;
+}
+
+LightCell lightCell(const uint32_t *rec, const uint32_t *model)
+{
+    const long long N = (long long)ABUB_FIELD_CELL * ABUB_FIELD_CELL, sp = rec[0], sm = model[0], ss6 = model[2];
+    LightCell c;
+    if (sm < N)
+        return c;
+    c.clipped = (long long)rec[4] + rec[5] > N / 16;
+    if (c.clipped)
+        return c;
+    c.rated = true;
+    c.ratio = lightRdiv((__int128)1000 * sp, sm);
+    c.changed = std::llabs(sp - sm) > ss6;
+    c.up = c.changed && sp > sm;
+    return c;
+}
+
+LightFrame lightFrame(const uint32_t *rec, const uint32_t *model, size_t cells)
+{
+    LightFrame f;
+    __int128 Ssp = 0, Sspm = 0, Ssm = 0, Ssmm = 0;
+    for (size_t k = 0; k < cells; ++k) {
+        const uint32_t *r = rec + k * LightRecordWords, *m = model + k * LightModelWords;
+        const LightCell c = lightCell(r, m);
+        f.clipped += c.clipped;
+        if (!c.rated)
+            continue;
+        f.ratioMin = f.rated ? std::min(f.ratioMin, c.ratio) : c.ratio;
+        f.ratioMax = f.rated ? std::max(f.ratioMax, c.ratio) : c.ratio;
+        ++f.rated;
+        f.changed += c.changed;
+        f.up += c.up;
+        f.down += c.changed && !c.up;
+        Ssp += r[0];
+        Sspm += r[2];
+        Ssm += m[0];
+        Ssmm += m[1];
+    }
+    if (!f.rated)
+        return f;
+    const __int128 n = (__int128)ABUB_FIELD_CELL * ABUB_FIELD_CELL * f.rated;
+    f.levelMilli = lightRdiv(1000 * (Ssp - Ssm), n);
+    const __int128 var = n * Ssmm - Ssm * Ssm, cov = n * Sspm - Ssp * Ssm;
+    if (var > 0) {
+        f.hasGain = true;
+        f.gainMilli = lightRdiv(1000 * cov, var);
+        f.offsetMilli = lightRdiv(1000 * Ssp - (__int128)f.gainMilli * Ssm, n);
+    }
+    f.kind = !f.changed ? LightFrame::Steady : f.changed == f.rated && (f.up == 0 || f.down == 0) ? LightFrame::Level : LightFrame::Uneven;
+    return f;
+}
+
+std::string LightReport(int radius, int W, int H, const std::vector<SurveyModel> &models, const std::vector<SurveyRow> &rows)
+{
+    int ncx = 0, ncy = 0, x0 = 0, y0 = 0;
+    if (W > 0 && H > 0)
+        abub_frame_cells_grid(W, H, radius, &ncx, &ncy, &x0, &y0);
+    const size_t cells = (size_t)ncx * ncy;
+    std::string text = "# abub3hs light 1\n";
+    char buf[512];
+    snprintf(buf, sizeof buf, "radius %d cell %d grid %d %d origin %d %d\n", radius, (int)ABUB_FIELD_CELL, ncx, ncy, x0, y0);
+    text += buf;
+    text += "event\tcam\tframe\tname\tstate\tindex\trated\tclipped\tchanged\tup\tdown\tlevel_milli\tratio_min\tratio_max\tgain_milli\toffset_milli\tkind\n";
+    static const char *const kinds[] = {"blind", "steady", "level", "uneven"};
+    struct Cam {
+        long long frames = 0, kind[4] = {0, 0, 0, 0};
+        const std::string *first = nullptr;
+        std::vector<long long> changed; // per cell: the frames in which it was rated and changed
+    };
+    std::vector<Cam> cams(models.size());
+    for (const SurveyRow &r : rows) {
+        snprintf(buf, sizeof buf, "%s\t%d\t%d\t%s\t%s", r.event.c_str(), r.cam, r.frame, r.name.c_str(), r.stateName());
+        text += buf;
+        const std::vector<uint32_t> *model = (size_t)r.cam < models.size() ? &models[(size_t)r.cam].light : nullptr;
+        if (r.state != SurveyRow::Ok || !r.hasLight || r.light.size() != cells * LightRecordWords || !model ||
+            model->size() != cells * LightModelWords) {
+            text += "\t-\t-\t-\t-\t-\t-\t-\t-\t-\t-\t-\t-\n";
+            continue;
+        }
+        Cam &c = cams[(size_t)r.cam];
+        c.changed.resize(cells, 0);
+        const LightFrame f = lightFrame(r.light.data(), model->data(), cells);
+        for (size_t k = 0; k < cells; ++k) {
+            const LightCell lc = lightCell(r.light.data() + k * LightRecordWords, model->data() + k * LightModelWords);
+            c.changed[k] += lc.rated && lc.changed;
+        }
+        snprintf(buf, sizeof buf, "\t%lld\t%d\t%d\t%d\t%d\t%d", c.frames, f.rated, f.clipped, f.changed, f.up, f.down);
+        text += buf;
+        if (f.kind == LightFrame::Blind)
+            snprintf(buf, sizeof buf, "\t-\t-\t-\t-\t-");
+        else if (f.hasGain)
+            snprintf(buf, sizeof buf, "\t%lld\t%lld\t%lld\t%lld\t%lld", f.levelMilli, f.ratioMin, f.ratioMax, f.gainMilli, f.offsetMilli);
+        else
+            snprintf(buf, sizeof buf, "\t%lld\t%lld\t%lld\t-\t-", f.levelMilli, f.ratioMin, f.ratioMax);
+        text += buf;
+        text += std::string("\t") + kinds[f.kind] + "\n";
+        ++c.frames;
+        ++c.kind[f.kind];
+        if (f.changed && !c.first)
+            c.first = &r.event;
+    }
+    long long frames = 0, kind[4] = {0, 0, 0, 0};
+    for (size_t c = 0; c < cams.size(); ++c) {
+        if (!models[c].trained) {
+            snprintf(buf, sizeof buf, "light cam %zu none\n", c);
+            text += buf;
+            continue;
+        }
+        const Cam &k = cams[c];
+        snprintf(buf, sizeof buf, "light cam %zu frames %lld blind %lld steady %lld level %lld uneven %lld first_changed_event %s\n", c, k.frames,
+                 k.kind[0], k.kind[1], k.kind[2], k.kind[3], k.first ? k.first->c_str() : "-");
+        text += buf;
+        frames += k.frames;
+        for (int q = 0; q < 4; ++q)
+            kind[q] += k.kind[q];
+    }
+    for (size_t c = 0; c < cams.size(); ++c) {
+        if (!models[c].trained)
+            continue;
+        for (int y = 0; y < ncy; ++y) {
+            snprintf(buf, sizeof buf, "changed cam %zu y %d", c, y);
+            text += buf;
+            for (int x = 0; x < ncx; ++x) {
+                const size_t k = (size_t)y * ncx + x;
+                snprintf(buf, sizeof buf, " %lld", k < cams[c].changed.size() ? cams[c].changed[k] : 0ll);
+                text += buf;
+            }
+            text += "\n";
+        }
+    }
+    snprintf(buf, sizeof buf, "run frames %lld blind %lld steady %lld level %lld uneven %lld\n", frames, kind[0], kind[1], kind[2], kind[3]);
+    text += buf;
+    return text;
 }
 
 std::string FieldReport(int radius, int W, int H, const std::vector<SurveyModel> &models, const std::vector<SurveyRow> &rows)
@@ -427,6 +624,9 @@ struct Plan {
     int fieldR = 0;                 // with a field directory: the radius of the per-cell search (0: none) ...
     size_t fieldCells = 0;          // ... the run's cells (abub_frame_cells_grid) ...
     std::atomic<long long> *fieldHostUs = nullptr; // ... and where surveyFrame adds the microseconds it spent in fieldCellsHost
+    bool light = false;             // with a light directory: surveyFrame gives its ok rows with a model their light records ...
+    int lightNcx = 0, lightNcy = 0, lightX0 = 0, lightY0 = 0; // ... on this grid (abub_frame_cells_grid at the field's radius) ...
+    std::atomic<long long> *lightHostUs = nullptr; // ... and adds the microseconds it spent in lightCellsHost here
     std::vector<std::string> events;
     std::vector<SurveyRow> rows;    // in event, camera and frame order
     std::vector<size_t> ref;        // ref[i]: the row frame i is measured against (frame max(i - 2, 0) of its stack)
@@ -583,6 +783,18 @@ void fieldRowHost(const Plan &pl, const uint8_t *cur, const uint8_t *mu, SurveyR
         *pl.fieldHostUs += (long long)((nowMs() - t0) * 1e3);
 }
 
+// The light records of an ok row of a camera with a model on this thread: the definition
+void lightRowHost(const Plan &pl, const uint8_t *cur, const uint8_t *mu, SurveyRow &row)
+{
+    const double t0 = nowMs();
+    row.light.resize((size_t)pl.lightNcx * pl.lightNcy * LightRecordWords);
+    lightCellsHost(cur, mu, pl.W, pl.H, pl.lightX0, pl.lightY0, pl.lightNcx, pl.lightNcy, row.light.data());
+    row.hasLight = true;
+    row.lightOnKernel = false;
+    if (pl.lightHostUs)
+        *pl.lightHostUs += (long long)((nowMs() - t0) * 1e3);
+}
+
 // The host route's per-frame function: row i on this thread, its state and its record.  It asks nothing of the other rows:
 // the reference frame is decoded here as well, and is there iff its own row is ok
 void surveyFrame(Parser &p, const Plan &pl, size_t i, SurveyRow &row)
@@ -590,6 +802,7 @@ void surveyFrame(Parser &p, const Plan &pl, size_t i, SurveyRow &row)
     row.onKernel = false;
     row.hasShift = row.shiftOnKernel = false;
     row.hasField = row.fieldOnKernel = false;
+    row.hasLight = row.lightOnKernel = false;
     row.s = FrameStats();
     row.w = row.h = 0;
     if (row.state == SurveyRow::Missing)
@@ -624,6 +837,8 @@ void surveyFrame(Parser &p, const Plan &pl, size_t i, SurveyRow &row)
         shiftRowHost(pl, cur.data, mu, row);
     if (pl.fieldR && mu)
         fieldRowHost(pl, cur.data, mu, row);
+    if (pl.light && mu)
+        lightRowHost(pl, cur.data, mu, row);
 }
 
 void hostFrames(Parser *parser, Plan &pl, int nthreads)
@@ -664,6 +879,9 @@ FrameStats fromRecord(const abub_stat_result &r)
 // [jobs][status words][surfaces] in a buffer of its own: abub_frame_shift_cells_dev in calls of as many jobs as keep the
 // surfaces below 64 MiB (ABUB_FIELD_CHUNK=n, a test knob: of n jobs), each call's status words and surfaces back in one copy.
 // A job's surface depends on nothing but the job, so the split cannot show in the result.
+// With pl.light the same rows then get their light records, behind the launches above on the same stream: one
+// abub_frame_light_cells_dev call per batch over [jobs][status words][records] in a buffer of its own, the status words and
+// the records (24 bytes per cell) back in one copy.
 void deviceFrames(Parser *parser, Plan &pl, int nthreads, int device, SurveyStats &st, std::vector<uint32_t> &devPlanes)
 {
     HIPOK(hipSetDevice(device));
@@ -675,8 +893,8 @@ void deviceFrames(Parser *parser, Plan &pl, int nthreads, int device, SurveyStat
     const size_t P = (size_t)W * H, stride = (P + 15) & ~(size_t)15, C = pl.mu.size();
     FileBatch B;
     B.sizer.reset(parser->clone());
-    PinnedBuffer h_meta, h_shift, h_field;
-    DeviceBuffer d_meta, d_shift, d_field, d_model; // d_model: [mu of every camera][sigma6 of every camera], camera c at c * stride
+    PinnedBuffer h_meta, h_shift, h_field, h_light;
+    DeviceBuffer d_meta, d_shift, d_field, d_light, d_model; // d_model: [mu of every camera][sigma6 of every camera], camera c at c * stride
     Stream stream;
     hipStream_t cs = stream.get();
     bool anyModel = false;
@@ -846,6 +1064,42 @@ void deviceFrames(Parser *parser, Plan &pl, int nthreads, int device, SurveyStat
                 st.field_s += (nowMs() - t0) * 1e-3;
                 t0 = nowMs();
             }
+            if (pl.light) {
+                st.stats_s += (nowMs() - t0) * 1e-3;
+                t0 = nowMs();
+                std::vector<size_t> with; // the jobs that have a model
+                for (size_t g = 0; g < nj; ++g)
+                    if (jobs[g].model != UINT64_MAX)
+                        with.push_back(g);
+                const size_t ns = with.size(), words = (size_t)pl.lightNcx * pl.lightNcy * LightRecordWords;
+                if (ns) {
+                    const size_t jobBytes = ns * sizeof(abub_shift_job), bytes = jobBytes + ns * (1 + words) * sizeof(uint32_t);
+                    h_light.grow(bytes);
+                    d_light.grow(bytes);
+                    abub_shift_job *lj = (abub_shift_job *)h_light.get();
+                    for (size_t q = 0; q < ns; ++q)
+                        lj[q] = abub_shift_job{jobs[with[q]].cur, jobs[with[q]].model};
+                    HIPOK(hipMemcpyAsync(d_light.get(), h_light.get(), jobBytes, hipMemcpyHostToDevice, cs));
+                    uint32_t *d_status = (uint32_t *)(d_light.get() + jobBytes);
+                    check(abub_frame_light_cells_dev(B.slab.get(), slots * stride, d_model.get(), C * stride,
+                                                     (const abub_shift_job *)d_light.get(), (int)ns, W, H, pl.lightX0, pl.lightY0, pl.lightNcx,
+                                                     pl.lightNcy, d_status, d_status + ns, cs),
+                          "abub_frame_light_cells_dev");
+                    HIPOK(hipMemcpyAsync(h_light.get() + jobBytes, d_light.get() + jobBytes, bytes - jobBytes, hipMemcpyDeviceToHost, cs));
+                    HIPOK(hipStreamSynchronize(cs));
+                    const uint32_t *status = (const uint32_t *)(h_light.get() + jobBytes), *rec = status + ns;
+                    for (size_t q = 0; q < ns; ++q) {
+                        if (status[q] != 0)
+                            throw std::runtime_error("survey: abub_frame_light_cells_dev refused a frame of its own slab");
+                        SurveyRow &row = pl.rows[rowOf(slot[with[q]])];
+                        row.light.assign(rec + q * words, rec + (q + 1) * words);
+                        row.hasLight = row.lightOnKernel = true;
+                    }
+                    ++st.lightLaunches;
+                }
+                st.light_s += (nowMs() - t0) * 1e-3;
+                t0 = nowMs();
+            }
             if (wantPlanes) {
                 st.stats_s += (nowMs() - t0) * 1e-3;
                 t0 = nowMs();
@@ -993,6 +1247,42 @@ void writeField(const std::string &dir, int radius, const Plan &pl)
         throw std::runtime_error("survey: cannot write " + dir + "/field.txt");
 }
 
+// The files of the light records, one writer for both routes ("Surveying a run for lighting changes"): per
+// camera with a model cam<c>_light.npy, the records of its rows that have one in survey order (the `index` column of
+// light.txt), cam<c>_light_model.npy, and light.txt
+void writeLight(const std::string &dir, int radius, const Plan &pl)
+{
+    std::string failed;
+    if (!makeDirs(dir, &failed))
+        throw std::runtime_error("survey: cannot make the directory " + failed);
+    const size_t cells = (size_t)pl.lightNcx * pl.lightNcy;
+    for (size_t c = 0; c < pl.models.size(); ++c) {
+        if (!pl.models[c].trained)
+            continue;
+        std::string data;
+        size_t n = 0;
+        for (const SurveyRow &r : pl.rows)
+            if ((size_t)r.cam == c && r.state == SurveyRow::Ok && r.hasLight && r.light.size() == cells * LightRecordWords) {
+                data.append((const char *)r.light.data(), r.light.size() * sizeof(uint32_t));
+                ++n;
+            }
+        char shape[96];
+        snprintf(shape, sizeof shape, "(%zu, %d, %d, %d)", n, pl.lightNcy, pl.lightNcx, (int)LightRecordWords);
+        const std::string stem = dir + "/cam" + std::to_string(c);
+        std::string file = npyHead("<i4", shape) + data;
+        if (!writeFile(stem + "_light.npy", (const unsigned char *)file.data(), file.size()))
+            throw std::runtime_error("survey: cannot write " + stem + "_light.npy");
+        snprintf(shape, sizeof shape, "(%d, %d, %d)", pl.lightNcy, pl.lightNcx, (int)LightModelWords);
+        const std::vector<uint32_t> &m = pl.models[c].light;
+        file = npyHead("<i4", shape) + std::string((const char *)m.data(), m.size() * sizeof(uint32_t));
+        if (!writeFile(stem + "_light_model.npy", (const unsigned char *)file.data(), file.size()))
+            throw std::runtime_error("survey: cannot write " + stem + "_light_model.npy");
+    }
+    const std::string text = LightReport(radius, pl.W, pl.H, pl.models, pl.rows);
+    if (!writeFile(dir + "/light.txt", (const unsigned char *)text.data(), text.size()))
+        throw std::runtime_error("survey: cannot write " + dir + "/light.txt");
+}
+
 // The files of the per-pixel planes, one writer for both routes ("Surveying a run per pixel"): per camera
 // with a listed row the sum of the host's planes and the device's (dev: [camera][6][stride], or empty) as
 // cam<c>_activity.npy, with a model cam<c>_moved.png, and the cameras' lines of activity.txt
@@ -1094,7 +1384,8 @@ bool sameDirectory(const std::string &path, const std::string &other)
 
 int surveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCams, const std::string &format,
               const std::string &reportPath, int nthreads, int device, SurveyStats *stats, std::vector<SurveyRow> *rows,
-              std::vector<SurveyModel> *models, const SurveyPlanes &planes, const SurveyShift &shift, const SurveyField &field)
+              std::vector<SurveyModel> *models, const SurveyPlanes &planes, const SurveyShift &shift, const SurveyField &field,
+              const SurveyLight &light)
 {
     const double t0 = nowMs();
     SurveyStats st;
@@ -1107,7 +1398,10 @@ int surveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCam
     const std::string fieldDir = trimSlashes(field.dir);
     if (!fieldDir.empty() && sameDirectory(trimSlashes(field.srcRunDir), fieldDir))
         throw std::runtime_error("survey: " + fieldDir + " is the run that is being read");
-    if (!fieldDir.empty() && (field.radius < 1 || field.radius > 8))
+    const std::string lightDir = trimSlashes(light.dir);
+    if (!lightDir.empty() && sameDirectory(trimSlashes(light.srcRunDir), lightDir))
+        throw std::runtime_error("survey: " + lightDir + " is the run that is being read");
+    if ((!fieldDir.empty() || !lightDir.empty()) && (field.radius < 1 || field.radius > 8))
         throw std::runtime_error("survey: the field radius must be in [1, 8], not " + std::to_string(field.radius));
     if (!shift.path.empty() && (shift.radius < 1 || shift.radius > 8))
         throw std::runtime_error("survey: the shift radius must be in [1, 8], not " + std::to_string(shift.radius));
@@ -1137,6 +1431,26 @@ int surveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCam
         pl.fieldCells = (size_t)ncx * ncy;
         pl.fieldHostUs = &fieldHostUs;
     }
+    std::atomic<long long> lightHostUs{0};
+    if (!lightDir.empty()) {
+        if (pl.W > 0) {
+            abub_frame_cells_grid(pl.W, pl.H, field.radius, &pl.lightNcx, &pl.lightNcy, &pl.lightX0, &pl.lightY0);
+            if (pl.lightNcx == 0 || pl.lightNcy == 0) {
+                const int need = ABUB_FIELD_CELL + 2 * field.radius;
+                throw std::runtime_error("survey: the light records at radius " + std::to_string(field.radius) + " need frames of at least " +
+                                         std::to_string(need) + "x" + std::to_string(need) + ", the run's are " + std::to_string(pl.W) + "x" +
+                                         std::to_string(pl.H));
+            }
+        }
+        pl.light = true;
+        pl.lightHostUs = &lightHostUs;
+        for (size_t c = 0; c < pl.models.size(); ++c) // (the model's sums depend on the camera alone: once, here, for both routes)
+            if (pl.models[c].trained) {
+                pl.models[c].light.resize((size_t)pl.lightNcx * pl.lightNcy * LightModelWords);
+                lightModelHost(pl.mu[c], pl.sigma6[c].data(), pl.W, pl.H, pl.lightX0, pl.lightY0, pl.lightNcx, pl.lightNcy,
+                               pl.models[c].light.data());
+            }
+    }
     std::unique_ptr<HostPlanes> hostPlanes;
     std::vector<uint32_t> devPlanes;
     if (!planesDir.empty()) {
@@ -1152,9 +1466,10 @@ int surveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCam
     st.H = pl.H;
     for (const SurveyModel &m : pl.models)
         st.modelCams += m.trained;
-    // (abub_frame_shift_dev and abub_frame_shift_cells_dev take sides of up to 65535: a larger run with a shift file or a
-    // field is the host route's whole)
-    if (device >= 0 && pl.W > 0 && decodersTakeWidth(pl.W) && ((!pl.shiftR && !pl.fieldR) || (pl.W <= 65535 && pl.H <= 65535))) {
+    // (abub_frame_shift_dev, abub_frame_shift_cells_dev and abub_frame_light_cells_dev take sides of up to 65535: a larger
+    // run with a shift file, a field or light records is the host route's whole)
+    if (device >= 0 && pl.W > 0 && decodersTakeWidth(pl.W) &&
+        ((!pl.shiftR && !pl.fieldR && !pl.light) || (pl.W <= 65535 && pl.H <= 65535))) {
         st.device = device;
         deviceFrames(parser, pl, nthreads, device, st, devPlanes);
     } else
@@ -1168,9 +1483,12 @@ int surveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCam
             ++(r.shiftOnKernel ? st.shiftFramesKernel : st.shiftFramesHost);
         if (r.state == SurveyRow::Ok && r.hasField)
             ++(r.fieldOnKernel ? st.fieldFramesKernel : st.fieldFramesHost);
+        if (r.state == SurveyRow::Ok && r.hasLight)
+            ++(r.lightOnKernel ? st.lightFramesKernel : st.lightFramesHost);
     }
     st.shiftHost_s = (double)shiftHostUs * 1e-6;
     st.fieldHost_s = (double)fieldHostUs * 1e-6;
+    st.lightHost_s = (double)lightHostUs * 1e-6;
     if (!reportPath.empty()) {
         const std::string text = SurveyReport(pl.models, pl.rows);
         if (!writeFile(reportPath, (const unsigned char *)text.data(), text.size()))
@@ -1183,6 +1501,8 @@ int surveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCam
     }
     if (!fieldDir.empty())
         writeField(fieldDir, field.radius, pl);
+    if (!lightDir.empty())
+        writeLight(lightDir, field.radius, pl);
     if (hostPlanes) {
         const double t1 = nowMs();
         st.planeRowsHost = hostPlanes->rows;
@@ -1204,18 +1524,21 @@ int surveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCam
 
 int SurveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCams, const std::string &imageFormat,
               const std::string &reportPath, int nthreads, SurveyStats *stats, std::vector<SurveyRow> *rows,
-              std::vector<SurveyModel> *models, const SurveyPlanes &planes, const SurveyShift &shift, const SurveyField &field)
+              std::vector<SurveyModel> *models, const SurveyPlanes &planes, const SurveyShift &shift, const SurveyField &field,
+              const SurveyLight &light)
 {
-    return surveyRun(parser, trainers, numCams, imageFormat, reportPath, nthreads, -1, stats, rows, models, planes, shift, field);
+    return surveyRun(parser, trainers, numCams, imageFormat, reportPath, nthreads, -1, stats, rows, models, planes, shift, field, light);
 }
 
 int SurveyRunDevice(Parser *parser, const std::vector<Trainer *> &trainers, int numCams, const std::string &imageFormat,
                     const std::string &reportPath, int nthreads, int device, SurveyStats *stats, std::vector<SurveyRow> *rows,
-                    std::vector<SurveyModel> *models, const SurveyPlanes &planes, const SurveyShift &shift, const SurveyField &field)
+                    std::vector<SurveyModel> *models, const SurveyPlanes &planes, const SurveyShift &shift, const SurveyField &field,
+                    const SurveyLight &light)
 {
     if (device < 0)
         throw std::runtime_error("survey: no such HIP device: " + std::to_string(device));
-    return surveyRun(parser, trainers, numCams, imageFormat, reportPath, nthreads, device, stats, rows, models, planes, shift, field);
+    return surveyRun(parser, trainers, numCams, imageFormat, reportPath, nthreads, device, stats, rows, models, planes, shift, field,
+                     light);
 }
 
 } // namespace abub

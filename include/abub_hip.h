@@ -882,6 +882,30 @@ int abub_frame_shift_cells_dev(const uint8_t *frames, size_t frames_bytes, const
                                const abub_shift_job *jobs, int njobs, int W, int H, int R,
                                uint32_t *status /*[njobs]*/, uint32_t *sad /*[njobs * ncy * ncx * (2R+1)^2]*/, void *stream);
 
+/* ---- per-cell light record of resident frames (abub_stats.hip) -------------------------------------------------------
+ * Did the light change, and where (abub3hs --survey --survey-light; definition, files and measurements: DESIGN section 3,
+ * "Surveying a run for lighting changes")?  Per cell of ABUB_FIELD_CELL x ABUB_FIELD_CELL pixels on the grid the caller
+ * gives (ncx x ncy whole cells, the first at (x0, y0); the survey passes abub_frame_cells_grid's) six u32 sums over the
+ * cell's pixels p of the frame at frames + jobs[j].cur and m of the plane at mu + jobs[j].model:
+ *   rec[((j * ncy + cy) * ncx + cx) * 6 + 0 .. 5] = sum p, sum p^2, sum p m, sum |p - m|, pixels with p == 0, with p == 255
+ * over x0 + 128 cx <= x < x0 + 128 (cx + 1), y0 + 128 cy <= y < y0 + 128 (cy + 1): 16384 pixels, at most
+ * 16384 * 255^2 = 1065369600 < 2^31.  Every value is an exact integer, bit-identical to the host definition
+ * (host/survey.cpp lightCellsHost) whatever the order of the jobs or the blocks: one launch on `stream` of cells x jobs
+ * blocks of four waves, each reading its cell once into registers and writing its six words with plain stores.  Every
+ * output word has one owning workgroup: no atomics, no clearing launch, no scratch buffer, no host synchronisation, no
+ * allocation, no workgroup waiting for another.  What a record means is the host's to say (abub::lightCell).
+ * Every pointer is a device pointer; jobs is 8-byte aligned, status and rec 4-byte aligned; W and H in [128, 65535];
+ * ncx, ncy >= 1, x0, y0 >= 0, x0 + 128 ncx <= W, y0 + 128 ncy <= H.  No alignment rule on the offsets or on x0.  status[j]
+ * (0 or ABUB_SHIFT_E_RANGE) and all ncx * ncy * 6 values of rec[j] are written in full by every call with njobs > 0,
+ * whatever they held before, and nothing else is written.  A job whose frame runs past frames_bytes or whose model plane
+ * runs past model_bytes gets ABUB_SHIFT_E_RANGE and a zero record; nothing of it is read.  Null pointers, njobs < 0, W, H
+ * or the grid out of range or a misaligned jobs / status / rec: ABUB_E_INVALID before anything touches the device.
+ * njobs == 0: ABUB_OK, nothing is touched.  njobs may exceed 65535. */
+#define ABUB_LIGHT_WORDS 6
+int abub_frame_light_cells_dev(const uint8_t *frames, size_t frames_bytes, const uint8_t *mu, size_t model_bytes,
+                               const abub_shift_job *jobs, int njobs, int W, int H, int x0, int y0, int ncx, int ncy,
+                               uint32_t *status /*[njobs]*/, uint32_t *rec /*[njobs * ncy * ncx * 6]*/, void *stream);
+
 /* ---- the two DebugPeek planes of a batch of resident frames (abub_peek.hip) ------------------------------------------
  * What L3Localizer::CalculateInitialBubbleParams builds on the analyzer's thread for its debug write-out (reference
  * L3Localizer.cpp:252-257, 397, 448; DESIGN section 3, "The peek planes"), for a batch of items.  Per item two W x H u8
