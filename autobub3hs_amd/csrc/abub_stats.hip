@@ -1,7 +1,7 @@
 // abub_stats.hip -- per-frame statistics of resident frames: abub_frame_stats_dev (include/abub_hip.h, DESIGN section 3,
 // "Surveying a run"); below it the per-pixel planes (abub_pixel_activity_dev), the shift search (abub_frame_shift_dev) and
-// the per-cell shift field (abub_frame_shift_cells_dev) and the per-cell light record (abub_frame_light_cells_dev), each
-// under a header of its own.  What a byte loop over a decoded frame does on a host thread (host/survey.cpp frameStatsHost, the
+// the per-cell shift field (abub_frame_shift_cells_dev), the per-cell light record (abub_frame_light_cells_dev) and the
+// per-cell edge agreement (abub_frame_focus_cells_dev), each under a header of its own.  What a byte loop over a decoded frame does on a host thread (host/survey.cpp frameStatsHost, the
 // definition): per job the grey-level range, sum, sum of squares, black and saturated pixels of the frame, and against a
 // model (mu, sigma6) and a reference frame the count and sum of sat(|p - m| - s) and of sat(|p - r| - s).
 //
@@ -1048,6 +1048,193 @@ extern "C" int abub_frame_light_cells_dev(const uint8_t *frames, size_t frames_b
         return ABUB_OK;
     const dim3 grid((unsigned)(ncx * ncy), (unsigned)(njobs < 65535 ? njobs : 65535)); // (at most 511 * 511 cells)
     k_light_cells<<<grid, FR_THREADS, 0, (hipStream_t)stream>>>(frames, (uint64_t)frames_bytes, mu, (uint64_t)model_bytes, jobs, njobs,
+                                                                (uint32_t)W, (uint32_t)H, (uint32_t)ncx, (uint32_t)x0, (uint32_t)y0, status,
+                                                                rec);
+    HIPCHK(hipGetLastError());
+    return ABUB_OK;
+}
+
+// ---- per-cell edge agreement: abub_frame_focus_cells_dev ("Surveying a run for lost focus") -------------
+// Per cell of FC_CELL x FC_CELL pixels on a grid the caller gives (x0, y0, ncx, ncy: abub_frame_cells_grid's, or any other
+// that lies inside the frame with a ring of one pixel around it) five i32 over the cell's pixels, with the central
+// differences gx = p(x + 1, y) - p(x - 1, y), gy = p(x, y + 1) - p(x, y - 1) of the frame and hx, hy of mu (host/survey.cpp
+// focusCellsHost, the definition):
+//   rec[((j ncy + cy) ncx + cx) 5 + 0 .. 4] = sum gx^2, sum gy^2, sum gx hx, sum gy hy, the pixels with p == 0 or p == 255.
+//
+// The grid is cells x jobs; a block of four waves owns one cell of one job at a time and with it the cell's five words: it
+// writes each of them once with a plain store, so there is no atomic, no clearing launch and no other launch (the block of
+// cell 0 writes the job's status word).  It reads the cell with its ring once into two LDS tiles, one of the frame and one
+// of mu, each FO_TR = 130 rows of FO_RS = 33 dwords (row r, dword c: the four pixels from (xc - 1 + 4 c, yc - 1 + r) on):
+// 2 * 130 * 33 * 4 = 34320 bytes.  fc_cell's lane mapping: lane l owns dword l & 31 of the cell rows 8 k + 2 w + (l >> 5),
+// k < 16 (w: its wave); the two halves of a wave are the two lane groups of a ds_read_b32 / ds_read2_b32 and within a half
+// the lanes read 32 consecutive dwords of one tile row, so there is no bank conflict.  Of a cell row y the lane reads dwords
+// col and col + 1 of the tile rows y, y + 1, y + 2 of both tiles.  With d0, d1 those of tile row y + 1, its four pixels are
+// bytes 1 .. 4 of the pair: their left neighbours are d0, their right neighbours v_alignbyte_b32(d1, d0, 2), the pixels
+// themselves v_alignbyte_b32(d1, d0, 1); the pixels above and below are the same alignment by one byte of the tile rows y and
+// y + 2.  No byte is unpacked: with l, r the neighbours in the frame and L, R those in mu (packed, four to a dword)
+//   sum (r - l)^2 = r.r + l.l - 2 r.l,   sum (r - l)(R - L) = r.R + l.L - r.L - l.R,
+// each product one v_dot4_u32_u8: seven per direction and dword.  The clipped pixels are the set top bits of
+// lc_zero_bytes(p) | lc_zero_bytes(~p).  A lane sums 64 pixels, so each of its eight u32 sums holds at most
+// 2 * 64 * 65025 < 2^24; the differences are formed per lane in i32, where the squares' are never negative and a product's
+// magnitude is at most 64 * 65025.  Summed over the wave with shuffles, over the waves through 20 words of LDS: a cell's
+// magnitude is at most 16384 * 65025 = 1065369600 < 2^31, and so is that of every partial sum.
+//
+// Bounds.  A job is read only if sh_job_ok holds; otherwise E_RANGE and a zero record, found alike by every block of the
+// job.  The launcher admits only grids with x0, y0 >= 1, x0 + 128 ncx + 1 <= W and y0 + 128 ncy + 1 <= H, so the tile's 130
+// rows yc - 1 .. yc + 128 lie inside the frame and so do the 130 pixels xc - 1 .. xc + 128 of each; a tile row's last dword
+// ends at byte 132 of it, two behind the ring: sh_load4 tests the index itself against W * H, a byte beyond reads as 0, and
+// no lane uses a byte behind the ring (its last is byte 4 * 31 + 5 = 129).  A block whose tile lies far enough inside the
+// stream, its first byte index lo >= 3 and the index of its last dword's first byte lo + 129 W + 128 <= W * H - 8, fills it
+// through fo_fill_inside instead: every load is one of the two aligned dwords around a tile dword's first byte, at stream
+// bytes >= lo - 3 >= 0 and < lo + 129 W + 128 + 8 <= W * H, so inside the job's frame or model plane, which sh_job_ok has
+// placed inside its buffer.  Every other block (the first and the last rows of cells of a frame with no margin) keeps sh_load4.  LDS: tile row first + 8 k + 2 <= 129 < FO_TR,
+// dword col + 1 <= 32 < FO_RS; part[wave][o], o < 5.  Stores: status[j] and rec[(j * cells + cell) * 5 + t], j < njobs,
+// cell < cells, t < 5.
+namespace {
+
+#define FO_WORDS 5u
+#define FO_RS (FC_CELL / 4u + 1u) /* dwords of a tile row: 128 + 2 pixels */
+#define FO_TR (FC_CELL + 2u)      /* rows of a tile */
+
+// the seven products of one direction: a, b the neighbours behind and ahead in the frame, A, B those in mu
+__device__ __forceinline__ void fo_dir(uint32_t a, uint32_t b, uint32_t A, uint32_t B, uint32_t &sq, uint32_t &cross, uint32_t &pos,
+                                       uint32_t &neg)
+{
+    sq = __builtin_amdgcn_udot4(b, b, sq, false);
+    sq = __builtin_amdgcn_udot4(a, a, sq, false);
+    cross = __builtin_amdgcn_udot4(b, a, cross, false);
+    pos = __builtin_amdgcn_udot4(b, B, pos, false);
+    pos = __builtin_amdgcn_udot4(a, A, pos, false);
+    neg = __builtin_amdgcn_udot4(b, A, neg, false);
+    neg = __builtin_amdgcn_udot4(a, B, neg, false);
+}
+
+// A tile filled without a test per load, for a tile whose every byte index i in the stream has 3 <= i and i + 8 <= P: the
+// two aligned dwords around s + i then lie in [i - 3, i + 8) of the stream whatever its address, and the four bytes from i on
+// are v_alignbyte_b32 of them.  A lane issues its loads six at a time before it uses the first (the loop with sh_load4's
+// tests waits for every load in turn)
+__device__ __forceinline__ void fo_fill_inside(uint32_t *tile, const uint8_t *s, uint64_t lo, uint32_t W)
+{
+    constexpr uint32_t STEPS = (FO_TR * FO_RS + FR_THREADS - 1u) / FR_THREADS, BATCH = 6u; // (17 loads in batches of 6: registers)
+#pragma unroll
+    for (uint32_t k0 = 0; k0 < STEPS; k0 += BATCH) {
+        uint32_t d0[BATCH], d1[BATCH], mis[BATCH];
+#pragma unroll
+        for (uint32_t k = 0; k < BATCH; ++k) {
+            // (the last step's spare lanes load the last dword again)
+            const uint32_t i = min((k0 + k) * FR_THREADS + threadIdx.x, FO_TR * FO_RS - 1u);
+            const uintptr_t a = (uintptr_t)(s + lo + (uint64_t)(i / FO_RS) * W + 4u * (i % FO_RS));
+            const uint32_t *d = reinterpret_cast<const uint32_t *>(a & ~(uintptr_t)3);
+            mis[k] = (uint32_t)(a & 3u);
+            d0[k] = d[0];
+            d1[k] = d[1];
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < BATCH; ++k) {
+            const uint32_t i = (k0 + k) * FR_THREADS + threadIdx.x;
+            if (i < FO_TR * FO_RS)
+                tile[i] = __builtin_amdgcn_alignbyte(d1[k], d0[k], mis[k]);
+        }
+        __builtin_amdgcn_sched_barrier(0); // (the next batch's loads stay behind this batch's stores)
+    }
+}
+
+__global__ __launch_bounds__(FR_THREADS, 4) void k_focus_cells(const uint8_t *frames, uint64_t frames_bytes, const uint8_t *mu,
+                                                            uint64_t model_bytes, const abub_shift_job *__restrict__ jobs, int njobs,
+                                                            uint32_t W, uint32_t H, uint32_t ncx, uint32_t x0, uint32_t y0,
+                                                            uint32_t *__restrict__ status, int32_t *__restrict__ rec)
+{
+    __shared__ uint32_t tp[FO_TR * FO_RS], tm[FO_TR * FO_RS];
+    __shared__ int32_t part[FR_THREADS / 64][FO_WORDS];
+    const uint64_t P = (uint64_t)W * H;
+    const uint32_t cell = blockIdx.x, cells = gridDim.x;
+    const uint32_t xc = x0 + (cell % ncx) * FC_CELL, yc = y0 + (cell / ncx) * FC_CELL; // the cell's first pixel
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t first = 2u * wave + (lane >> 5), col = lane & 31u;
+    // the tile's bytes are those at lo + r W + 0 .. 131 of a stream, r < 130: inside iff every one of them has the two aligned
+    // dwords around it within the stream wherever the stream begins (the same in every thread of the block, for every job)
+    const uint64_t lo = (uint64_t)(yc - 1u) * W + (xc - 1u);
+    const bool inside = lo >= 3u && lo + (uint64_t)(FO_TR - 1u) * W + 4u * FO_RS + 4u <= P;
+    for (uint32_t j = blockIdx.y; j < (uint32_t)njobs; j += gridDim.y) {
+        const abub_shift_job jb = jobs[j];
+        const bool ok = sh_job_ok(jb, frames_bytes, model_bytes, P); // (the same in every thread of every block of the job)
+        int32_t *out = rec + ((uint64_t)j * cells + cell) * FO_WORDS;
+        if (cell == 0u && threadIdx.x == 0u)
+            status[j] = ok ? 0u : (uint32_t)ABUB_SHIFT_E_RANGE;
+        if (!ok) {
+            if (threadIdx.x < FO_WORDS)
+                out[threadIdx.x] = 0;
+            continue;
+        }
+        const uint8_t *p = frames + jb.cur, *q = mu + jb.model;
+        if (inside) {
+            fo_fill_inside(tp, p, lo, W);
+            fo_fill_inside(tm, q, lo, W);
+        } else {
+            for (uint32_t i = threadIdx.x; i < FO_TR * FO_RS; i += FR_THREADS) {
+                const uint64_t at = lo + (uint64_t)(i / FO_RS) * W + 4u * (i % FO_RS);
+                tp[i] = sh_load4(p, at, P);
+                tm[i] = sh_load4(q, at, P);
+            }
+        }
+        __syncthreads();
+        uint32_t xs = 0, xc2 = 0, xp = 0, xn = 0, ys = 0, yc2 = 0, yp = 0, yn = 0, clip = 0;
+#pragma unroll
+        for (uint32_t r = 0; r < FC_ROWS; ++r) {
+            const uint32_t at = (r * 8u + first) * FO_RS + col; // tile row y: the pixels above cell row y
+            const uint32_t pu = __builtin_amdgcn_alignbyte(tp[at + 1u], tp[at], 1u), mu_ = __builtin_amdgcn_alignbyte(tm[at + 1u], tm[at], 1u);
+            const uint32_t p0 = tp[at + FO_RS], p1 = tp[at + FO_RS + 1u], m0 = tm[at + FO_RS], m1 = tm[at + FO_RS + 1u];
+            const uint32_t pd = __builtin_amdgcn_alignbyte(tp[at + 2u * FO_RS + 1u], tp[at + 2u * FO_RS], 1u);
+            const uint32_t md = __builtin_amdgcn_alignbyte(tm[at + 2u * FO_RS + 1u], tm[at + 2u * FO_RS], 1u);
+            fo_dir(p0, __builtin_amdgcn_alignbyte(p1, p0, 2u), m0, __builtin_amdgcn_alignbyte(m1, m0, 2u), xs, xc2, xp, xn);
+            fo_dir(pu, pd, mu_, md, ys, yc2, yp, yn);
+            const uint32_t c = __builtin_amdgcn_alignbyte(p1, p0, 1u);
+            clip += (uint32_t)__builtin_popcount(lc_zero_bytes(c) | lc_zero_bytes(~c));
+        }
+        int32_t acc[FO_WORDS] = {(int32_t)(xs - 2u * xc2), (int32_t)(ys - 2u * yc2), (int32_t)xp - (int32_t)xn, (int32_t)yp - (int32_t)yn,
+                                 (int32_t)clip};
+#pragma unroll
+        for (int s = 32; s > 0; s >>= 1)
+#pragma unroll
+            for (uint32_t o = 0; o < FO_WORDS; ++o)
+                acc[o] += __shfl_xor(acc[o], s);
+        if (lane == 0u) {
+#pragma unroll
+            for (uint32_t o = 0; o < FO_WORDS; ++o)
+                part[wave][o] = acc[o];
+        }
+        __syncthreads();
+        if (threadIdx.x < FO_WORDS) {
+            int32_t v = part[0][threadIdx.x];
+#pragma unroll
+            for (int w = 1; w < FR_THREADS / 64; ++w)
+                v += part[w][threadIdx.x];
+            out[threadIdx.x] = v;
+        }
+        __syncthreads(); // (the tiles and part are written again for the block's next job)
+    }
+}
+
+} // namespace
+
+extern "C" int abub_frame_focus_cells_dev(const uint8_t *frames, size_t frames_bytes, const uint8_t *mu, size_t model_bytes,
+                                          const abub_shift_job *jobs, int njobs, int W, int H, int x0, int y0, int ncx, int ncy,
+                                          uint32_t *status, int32_t *rec, void *stream)
+{
+    if (!frames || !mu || !jobs || !status || !rec || njobs < 0)
+        return set_err(ABUB_E_INVALID, "abub_frame_focus_cells_dev: null pointer or negative count");
+    if (W < ABUB_FIELD_CELL + 2 || W > 65535 || H < ABUB_FIELD_CELL + 2 || H > 65535)
+        return set_err(ABUB_E_INVALID, "abub_frame_focus_cells_dev: W and H must be in [130, 65535]");
+    // (ncx, ncy <= 511 once the sides are bounded, so the sums below cannot overflow an int)
+    if (ncx < 1 || ncy < 1 || ncx > (W - 2) / ABUB_FIELD_CELL || ncy > (H - 2) / ABUB_FIELD_CELL || x0 < 1 || y0 < 1 ||
+        x0 > W - 1 - ABUB_FIELD_CELL * ncx || y0 > H - 1 - ABUB_FIELD_CELL * ncy)
+        return set_err(ABUB_E_INVALID, "abub_frame_focus_cells_dev: the grid of whole cells and a ring of one pixel must lie inside the frame");
+    if (((uintptr_t)jobs & 7) || (((uintptr_t)status | (uintptr_t)rec) & 3))
+        return set_err(ABUB_E_INVALID, "abub_frame_focus_cells_dev: jobs must be 8-byte aligned, status and rec 4-byte aligned");
+    if (njobs == 0)
+        return ABUB_OK;
+    const dim3 grid((unsigned)(ncx * ncy), (unsigned)(njobs < 65535 ? njobs : 65535)); // (at most 511 * 511 cells)
+    k_focus_cells<<<grid, FR_THREADS, 0, (hipStream_t)stream>>>(frames, (uint64_t)frames_bytes, mu, (uint64_t)model_bytes, jobs, njobs,
                                                                 (uint32_t)W, (uint32_t)H, (uint32_t)ncx, (uint32_t)x0, (uint32_t)y0, status,
                                                                 rec);
     HIPCHK(hipGetLastError());

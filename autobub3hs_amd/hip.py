@@ -774,6 +774,34 @@ def frame_light_cells(frames, mu, jobs, W, H, x0, y0, ncx, ncy, frames_bytes=Non
             rec.reshape(-1)[:words].cpu().numpy().view(np.uint32).reshape(n, ncy, ncx, LIGHT_WORDS))
 
 
+FOCUS_WORDS = 5  # ABUB_FOCUS_WORDS of include/abub_hip.h
+
+
+def frame_focus_cells(frames, mu, jobs, W, H, x0, y0, ncx, ncy, frames_bytes=None, model_bytes=None, status=None, rec=None):
+    """abub_frame_focus_cells_dev: frames, mu and jobs as for frame_shift; the grid of ncx x ncy cells of 128 x 128 pixels
+    from (x0, y0), with a ring of one pixel inside the frame; rec: int32 device tensor of at least n * ncy * ncx * 5 words,
+    written in place (None: a new one) -> (status int64 [n] on the host: 0 or SHIFT_E_RANGE; the records, int32
+    [n, ncy, ncx, 5] on the host: the sums of gx^2, gy^2, gx hx and gy hy, the pixels with p == 0 or p == 255)."""
+    import numpy as np
+    _need_cuda(frames, mu, status, rec)
+    offs = np.array([[int(v) for v in row] for row in jobs], dtype=np.uint64).reshape(-1, 2)
+    n = len(offs)
+    words = n * max(int(ncy), 0) * max(int(ncx), 0) * FOCUS_WORDS
+    dev = frames.device
+    d_jobs = torch.from_numpy(np.concatenate([offs, np.zeros((1, 2), np.uint64)]).view(np.int64)).to(dev)
+    if status is None:
+        status = torch.full((max(n, 1),), 0x5A5A5A5A, dtype=torch.int32, device=dev)
+    if rec is None:
+        rec = torch.full((max(words, 1),), -1, dtype=torch.int32, device=dev)
+    _lib.check(_lib.lib().abub_frame_focus_cells_dev(_ptr(frames), frames.numel() if frames_bytes is None else int(frames_bytes),
+                                                     _ptr(mu), mu.numel() if model_bytes is None else int(model_bytes), _ptr(d_jobs), n,
+                                                     int(W), int(H), int(x0), int(y0), int(ncx), int(ncy), _ptr(status), _ptr(rec),
+                                                     _stream()),
+               "abub_frame_focus_cells_dev")
+    return (status.reshape(-1)[:n].cpu().numpy().astype(np.int64),
+            rec.reshape(-1)[:words].cpu().numpy().view(np.int32).reshape(n, ncy, ncx, FOCUS_WORDS))
+
+
 ACT_PLANES = ("n_zero","n_sat", "n_out", "sum_out", "n_moved", "sum_moved")
 ACT_E_RANGE = 1
 ACT_PIXELS_PER_THREAD = 8  # AC_PX of csrc/abub_stats.hip: the run of pixels a thread owns

@@ -78,6 +78,12 @@ SIGNATURES = {
     "abh_light_cells_host": (_i, [_u8p, _u8p, _i, _i, _i, _i, _i, _i, _u32p]),
     "abh_light_model_host": (_i, [_u8p, _u8p, _i, _i, _i, _i, _i, _i, _u32p]),
     "abh_light_frame": (None, [_u32p, _u32p, _i, C.POINTER(C.c_longlong)]),
+    "abh_run_survey_focus": (_i, [_vp, _s, _s, _s, _i, _s, _i, _s, _s, _i, _i, _dp, _dp, _dp, _dp, _dp, _dp, C.c_char_p, _i]),
+    "abh_run_survey_focus_dev": (_i, [_vp, _s, _s, _s, _i, _s, _i, _s, _s, _i, _i, _i, _dp, _dp, _dp, _dp, _dp, _dp, C.c_char_p, _i]),
+    "abh_focus_cells_host": (_i, [_u8p, _u8p, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_int32)]),
+    "abh_focus_model_host": (_i, [_u8p, _u8p, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_int64)]),
+    "abh_focus_cell": (None, [C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_longlong)]),
+    "abh_focus_frame": (None, [C.POINTER(C.c_int32), C.POINTER(C.c_int64), _i, C.POINTER(C.c_longlong)]),
     "abh_field_grid": (_i, [_i, _i, _i, C.POINTER(_i)]),
     "abh_field_cells_host": (_i, [_u8p, _u8p, _i, _i, _i, _u32p, C.POINTER(C.c_int32)]),
     "abh_activity_add_host": (None, [C.POINTER(C.c_uint32), _u8p, _u8p, _u8p, _u8p, C.c_uint64]),
@@ -457,7 +463,7 @@ class Run:
                     "W", "H", "batches", "model_cams")
 
     def survey(self, path=None, nthreads=16, ncams=4, device=None, planes=None, shift=None, shift_radius=4, field=None,
-               field_radius=4, light=None):
+               field_radius=4, light=None, focus=None):
         """abub3hs --survey of this run (opened from a directory or an archive): the run is listed and trained as for
         detect, then every frame of cameras 0 .. ncams-1 is measured without analysing any; the report (DESIGN section 3,
         "Surveying a run") is written to `path` (None: it is not written).  device=None: host threads (cv::imdecode and
@@ -482,17 +488,35 @@ class Run:
         "Surveying a run for lighting changes"): cam<c>_light.npy, cam<c>_light_model.npy and light.txt, the same rows summed
         per cell of the field's grid at field_radius (whether or not field is given), the same bytes on both routes; the
         stats then also have light_frames_kernel / light_frames_host, light_launches and the legs light_s and light_host_s.
-        Nothing else changes."""
+        Nothing else changes.
+        focus (--survey-focus): the directory (the CLI's DIR/<run_ID>) that gets the per-cell focus records (DESIGN section 3,
+        "Surveying a run for lost focus"): cam<c>_focus.npy, cam<c>_focus_model.npy and focus.txt, the same rows compared
+        per cell of the field's grid at field_radius (whether or not field or light is given), the same bytes on both routes;
+        the stats then also have focus_frames_kernel / focus_frames_host, focus_launches and the legs focus_s and
+        focus_host_s.  Nothing else changes."""
         L = lib()
         st = (C.c_double * 24)()
         pst = (C.c_double * 5)()
         sst = (C.c_double * 5)()
         fst = (C.c_double * 5)()
         lst = (C.c_double * 5)()
+        ost = (C.c_double * 5)()
         cap = 1 << 16
         buf = C.create_string_buffer(cap)
         to = None if path is None else str(path).encode()
-        if light is not None:
+        if focus is not None:
+            pd = None if planes is None else str(planes).encode()
+            sp = None if shift is None else str(shift).encode()
+            fd = None if field is None else str(field).encode()
+            ld = None if light is None else str(light).encode()
+            od = str(focus).encode()
+            if device is None:
+                rc = L.abh_run_survey_focus(self._h, to, pd, sp, int(shift_radius), fd, int(field_radius), ld, od, ncams, nthreads, st, pst,
+                                            sst, fst, lst, ost, buf, cap)
+            else:
+                rc = L.abh_run_survey_focus_dev(self._h, to, pd, sp, int(shift_radius), fd, int(field_radius), ld, od, ncams, nthreads,
+                                                int(device), st, pst, sst, fst, lst, ost, buf, cap)
+        elif light is not None:
             pd = None if planes is None else str(planes).encode()
             sp = None if shift is None else str(shift).encode()
             fd = None if field is None else str(field).encode()
@@ -548,6 +572,9 @@ class Run:
         if light is not None:
             res.update(light_frames_kernel=int(lst[0]), light_frames_host=int(lst[1]), light_launches=int(lst[2]), light_s=lst[3],
                        light_host_s=lst[4])
+        if focus is not None:
+            res.update(focus_frames_kernel=int(ost[0]), focus_frames_host=int(ost[1]), focus_launches=int(ost[2]), focus_s=ost[3],
+                       focus_host_s=ost[4])
         return res, text.decode()
 
     def analyze(self, event, cam, maskdir=""):
@@ -672,6 +699,61 @@ def light_frame(rec, model):
     return {"rated": v[0], "clipped": v[1], "changed": v[2], "up": v[3], "down": v[4], "kind": LIGHT_KINDS[v[5]],
             "level_milli": None if blind else v[7], "ratio_min": None if blind else v[8], "ratio_max": None if blind else v[9],
             "gain_milli": v[10] if gain else None, "offset_milli": v[11] if gain else None}
+
+
+FOCUS_KINDS = ("blind", "steady", "soft", "uneven")
+_i32p, _i64p = C.POINTER(C.c_int32), C.POINTER(C.c_int64)
+
+
+def _focus_call(fn, a, b, x0, y0, ncx, ncy, words, dtype, ptr):
+    a, b = (np.ascontiguousarray(v, dtype=np.uint8) for v in (a, b))
+    assert a.ndim == 2 and a.shape == b.shape
+    rec = np.zeros((max(ncy, 0), max(ncx, 0), words), dtype)
+    if fn(a.ctypes.data_as(_u8p), b.ctypes.data_as(_u8p), a.shape[1], a.shape[0], int(x0), int(y0), int(ncx), int(ncy),
+          rec.ctypes.data_as(ptr)) != ncx * ncy or ncx * ncy <= 0:
+        raise ValueError(f"the grid {ncx}x{ncy} from ({x0}, {y0}) and its ring do not lie inside {a.shape[1]}x{a.shape[0]}")
+    return rec
+
+
+def focus_cells_host(p, m, x0, y0, ncx, ncy):
+    """abub::focusCellsHost (host/survey.cpp), the definition of abub_frame_focus_cells_dev: the frame p and the model
+    plane m, u8 [H, W], on the grid of ncx x ncy cells of 128 x 128 pixels from (x0, y0) -> int32 [ncy, ncx, 5]: the sums of
+    gx^2, gy^2, gx hx and gy hy (central differences of p and of m), the pixels with p == 0 or p == 255."""
+    return _focus_call(lib().abh_focus_cells_host, p, m, x0, y0, ncx, ncy, 5, np.int32, _i32p)
+
+
+def focus_model_host(mu, sigma6, x0, y0, ncx, ncy):
+    """abub::focusModelHost: the model planes mu and sigma6, u8 [H, W], on the same grid -> int64 [ncy, ncx, 3]: the sums
+    of hx^2 and hy^2, and nv, the sum over the cell and its ring of (sigma6 c)^2."""
+    return _focus_call(lib().abh_focus_model_host, mu, sigma6, x0, y0, ncx, ncy, 3, np.int64, _i64p)
+
+
+def focus_cell(rec, model):
+    """abub::focusCell: what one cell's record [5] says against its model's [3] -> dict: rated, clipped, changed, softer
+    (bool), keep, energy (None where the cell is not rated)."""
+    rec = np.ascontiguousarray(rec, dtype=np.int32).reshape(5)
+    model = np.ascontiguousarray(model, dtype=np.int64).reshape(3)
+    out = (C.c_longlong * 6)()
+    lib().abh_focus_cell(rec.ctypes.data_as(_i32p), model.ctypes.data_as(_i64p), out)
+    v = list(out)
+    return {"rated": bool(v[0]), "clipped": bool(v[1]), "changed": bool(v[2]), "softer": bool(v[3]),
+            "keep": v[4] if v[0] else None, "energy": v[5] if v[0] else None}
+
+
+def focus_frame(rec, model):
+    """abub::focusFrame: what a frame's records [..., 5] say against the model's [..., 3] -> dict: rated, clipped, changed,
+    softer, harder, kind (a word of FOCUS_KINDS), and keep_milli, keep_min, keep_max, energy_milli (None where focus.txt has
+    '-')."""
+    rec = np.ascontiguousarray(rec, dtype=np.int32).reshape(-1, 5)
+    model = np.ascontiguousarray(model, dtype=np.int64).reshape(-1, 3)
+    assert len(rec) == len(model)
+    out = (C.c_longlong * 10)()
+    lib().abh_focus_frame(rec.ctypes.data_as(_i32p), model.ctypes.data_as(_i64p), len(rec), out)
+    v = list(out)
+    blind = v[5] == 0
+    return {"rated": v[0], "clipped": v[1], "changed": v[2], "softer": v[3], "harder": v[4], "kind": FOCUS_KINDS[v[5]],
+            "keep_milli": None if blind else v[6], "keep_min": None if blind else v[7], "keep_max": None if blind else v[8],
+            "energy_milli": None if blind else v[9]}
 
 
 def zip_write(path, entries):

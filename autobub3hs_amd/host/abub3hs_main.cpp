@@ -37,6 +37,7 @@ static std::string usage()
            "               [--survey-shift FILE [--survey-shift-radius R]]\n"
            "               [--survey-field DIR [--survey-field-radius R]]\n"
            "               [--survey-light DIR [--survey-field-radius R]]\n"
+           "               [--survey-focus DIR [--survey-field-radius R]]\n"
            "Run the AutoBub3hs bubble finding algorithm on a PICO run (MI355X hot path)\n\n"
            "Required arguments:\n"
            "  -d, --data_dir = Dir\t\tpath to the directory in which the run folder/file is stored\n"
@@ -120,8 +121,8 @@ static std::string usage()
            "\t\t\t\tframes in which it moved; the same bytes with --survey-gpu; the report, the planes and the shift\n"
            "\t\t\t\tfile do not change\n"
            "  --survey-field-radius = R\twith --survey-field: the radius of the search in pixels, 1 to 8 (4); the frames must be at\n"
-           "\t\t\t\tleast 128 + 2 R wide and high; with --survey-light, with or without --survey-field: the radius\n"
-           "\t\t\t\tthat places the cells\n"
+           "\t\t\t\tleast 128 + 2 R wide and high; with --survey-light or --survey-focus, with or without\n"
+           "\t\t\t\t--survey-field: the radius that places the cells\n"
            "  --survey-light = Dir\t\twith --survey: also sum the same frames per cell of the field's grid (the cells of\n"
            "\t\t\t\t--survey-field at --survey-field-radius, 4 unless given, whether or not the field is written) and\n"
            "\t\t\t\twrite into Dir/<run_ID>/ cam<c>_light.npy (i32 [frames, cells down, cells across, 6]: per cell the\n"
@@ -132,6 +133,18 @@ static std::string usage()
            "\t\t\t\tthousandths, the pooled gain and offset in thousandths, and the frame's kind (blind, steady, level,\n"
            "\t\t\t\tuneven); per camera and for the run the counts of each kind and per cell the frames in which it\n"
            "\t\t\t\tchanged; the same bytes with --survey-gpu; the report, the planes, the shift file and the field do\n"
+           "\t\t\t\tnot change\n"
+           "  --survey-focus = Dir\t\twith --survey: also compare the edges of the same frames with the model's per cell of the\n"
+           "\t\t\t\tfield's grid (at --survey-field-radius, 4 unless given, whether or not the field or the light is\n"
+           "\t\t\t\twritten) and write into Dir/<run_ID>/ cam<c>_focus.npy (i32 [frames, cells down, cells across, 5]:\n"
+           "\t\t\t\tper cell the sums of gx^2, gy^2, gx hx and gy hy, g and h the central differences of the frame and\n"
+           "\t\t\t\tof mu, and the pixels at 0 or 255), cam<c>_focus_model.npy (i64 [cells down, cells across, 3]: the\n"
+           "\t\t\t\tsums of hx^2 and hy^2 and the square of six standard deviations of the agreement under the trained\n"
+           "\t\t\t\tnoise) and focus.txt: per frame how many cells are rated, clipped and changed (the agreement moved\n"
+           "\t\t\t\tby more than that), softer or harder, the pooled agreement and edge energy in thousandths of the\n"
+           "\t\t\t\tmodel's, the range of the cells' agreement, and the frame's kind (blind, steady, soft, uneven); per\n"
+           "\t\t\t\tcamera and for the run the counts of each kind and per cell the frames in which it changed; the\n"
+           "\t\t\t\tsame bytes with --survey-gpu; the report, the planes, the shift file, the field and the light do\n"
            "\t\t\t\tnot change\n"
            "Environment: ABUB_TRAIN_ON_GPU=0 trains the runs of a campaign with the host Trainer\n"
            "             ABUB_REPACK_BATCH=n (a test knob) lowers the frames per batch of --repack-gpu and --unpack-gpu to n; the files\n"
@@ -316,6 +329,8 @@ int main(int argc, char **argv)
     int surveyFieldRadius = 4;
     std::string surveyLightDir; // --survey-light DIR: the survey's per-cell light records go to DIR/<run_ID>/
     bool haveSurveyLight = false;
+    std::string surveyFocusDir; // --survey-focus DIR: the survey's per-cell focus records go to DIR/<run_ID>/
+    bool haveSurveyFocus = false;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i], v;
         auto value = [&](std::string &dst) {
@@ -447,6 +462,9 @@ int main(int argc, char **argv)
         } else if (a == "--survey-light" || a.rfind("--survey-light=", 0) == 0) {
             value(surveyLightDir);
             haveSurveyLight = true;
+        } else if (a == "--survey-focus" || a.rfind("--survey-focus=", 0) == 0) {
+            value(surveyFocusDir);
+            haveSurveyFocus = true;
         } else if (a == "--per-event") {
             perEvent = true;
         } else if (a == "--peek" || a.rfind("--peek=", 0) == 0) {
@@ -498,7 +516,11 @@ int main(int argc, char **argv)
         std::cerr << "--survey-light is valid only together with --survey" << std::endl;
         return -1;
     }
-    if (haveFieldRadius && !haveSurveyField && !haveSurveyLight) { // (the light's cells are the field's)
+    if (haveSurveyFocus && !haveSurvey) {
+        std::cerr << "--survey-focus is valid only together with --survey" << std::endl;
+        return -1;
+    }
+    if (haveFieldRadius && !haveSurveyField && !haveSurveyLight && !haveSurveyFocus) { // (the light's and the focus' cells are the field's)
         std::cerr << "--survey-field-radius is valid only together with --survey-field" << std::endl;
         return -1;
     }
@@ -528,6 +550,10 @@ int main(int argc, char **argv)
         }
         if (haveSurveyLight && surveyLightDir.empty()) {
             std::cerr << "--survey-light needs the directory to write to" << std::endl;
+            return -1;
+        }
+        if (haveSurveyFocus && surveyFocusDir.empty()) {
+            std::cerr << "--survey-focus needs the directory to write to" << std::endl;
             return -1;
         }
     }
@@ -721,6 +747,12 @@ int main(int argc, char **argv)
             light.srcRunDir = zipped ? std::string() : sp.eventDir;
             field.radius = surveyFieldRadius; // (the grid's radius, whether or not the field is written)
         }
+        abub::SurveyFocus focus;
+        if (haveSurveyFocus) {
+            focus.dir = surveyFocusDir + "/" + run_number;
+            focus.srcRunDir = zipped ? std::string() : sp.eventDir;
+            field.radius = surveyFieldRadius; // (the grid's radius, whether or not the field is written)
+        }
         int rc = 1;
         try {
             abub::PreparedRun prep = abub::PrepareRun(sp, po, 0, nullptr, false);
@@ -729,9 +761,9 @@ int main(int argc, char **argv)
             if (prep.rc)
                 printf("survey: a camera did not train: the report has no model columns for it\n");
             rc = surveyGpu ? abub::SurveyRunDevice(prep.parser.get(), prep.trainers, sp.numCams, sp.imageFormat, surveyFile, poolThreads(), 0,
-                                                   &ss, nullptr, nullptr, planes, shift, field, light)
+                                                   &ss, nullptr, nullptr, planes, shift, field, light, focus)
                            : abub::SurveyRun(prep.parser.get(), prep.trainers, sp.numCams, sp.imageFormat, surveyFile, poolThreads(), &ss,
-                                             nullptr, nullptr, planes, shift, field, light);
+                                             nullptr, nullptr, planes, shift, field, light, focus);
         } catch (std::exception &e) {
             std::cerr << "survey failed: " << e.what() << std::endl;
             return -6;
@@ -771,6 +803,10 @@ int main(int argc, char **argv)
             printf("survey-light: %s: radius %d, %lld frames summed on the GPU in %d launches, %lld on the host; light leg %.3f s, host "
                    "threads %.3f s\n",
                    light.dir.c_str(), field.radius, ss.lightFramesKernel, ss.lightLaunches, ss.lightFramesHost, ss.light_s, ss.lightHost_s);
+        if (haveSurveyFocus)
+            printf("survey-focus: %s: radius %d, %lld frames summed on the GPU in %d launches, %lld on the host; focus leg %.3f s, host "
+                   "threads %.3f s\n",
+                   focus.dir.c_str(), field.radius, ss.focusFramesKernel, ss.focusLaunches, ss.focusFramesHost, ss.focus_s, ss.focusHost_s);
         return rc;
     }
     if (haveList) {

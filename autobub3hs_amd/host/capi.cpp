@@ -412,10 +412,15 @@ const char *abh_run_verify_report(void *src)
 // for lighting changes") written to light_dir (the CLI's DIR/<run_ID>; NULL or empty: none) on the grid of field_radius,
 // whether or not field_dir is given, and light_stats (may be NULL, 5 values): the same five for abub_frame_light_cells_dev
 // and lightCellsHost.
+// abh_run_survey_focus[_dev]: the same with the per-cell focus records (abub::SurveyFocus; DESIGN section 3, "Surveying a run
+// for lost focus") written to focus_dir (the CLI's DIR/<run_ID>; NULL or empty: none) on the grid of field_radius, whether
+// or not field_dir or light_dir is given, and focus_stats (may be NULL, 5 values): the same five for
+// abub_frame_focus_cells_dev and focusCellsHost.
 static int runSurvey(void *r, const char *path, int ncams, int nthreads, int device, bool onDevice, double *stats, char *report,
                      int report_cap, const char *planes_dir = nullptr, double *plane_stats = nullptr, const char *shift_path = nullptr,
                      int shift_radius = 4, double *shift_stats = nullptr, const char *field_dir = nullptr, int field_radius = 4,
-                     double *field_stats = nullptr, const char *light_dir = nullptr, double *light_stats = nullptr)
+                     double *field_stats = nullptr, const char *light_dir = nullptr, double *light_stats = nullptr,
+                     const char *focus_dir = nullptr, double *focus_stats = nullptr)
 {
     Run *run = (Run *)r;
     try {
@@ -451,10 +456,17 @@ static int runSurvey(void *r, const char *path, int ncams, int nthreads, int dev
         abub::SurveyLight light;
         light.dir = light_dir ? light_dir : "";
         light.srcRunDir = planes.srcRunDir;
+        abub::SurveyFocus focus;
+        focus.dir = focus_dir ? focus_dir : "";
+        focus.srcRunDir = planes.srcRunDir;
         const int rc = onDevice ? abub::SurveyRunDevice(pr.parser.get(), pr.trainers, ncams, sp.imageFormat, to, std::max(1, nthreads),
-                                                        device, &st, &rows, &models, planes, shift, field, light)
+                                                        device, &st, &rows, &models, planes, shift, field, light, focus)
                                 : abub::SurveyRun(pr.parser.get(), pr.trainers, ncams, sp.imageFormat, to, std::max(1, nthreads), &st,
-                                                  &rows, &models, planes, shift, field, light);
+                                                  &rows, &models, planes, shift, field, light, focus);
+        if (focus_stats) {
+            const double v[5] = {(double)st.focusFramesKernel, (double)st.focusFramesHost, (double)st.focusLaunches, st.focus_s, st.focusHost_s};
+            std::memcpy(focus_stats, v, sizeof v);
+        }
         if (light_stats) {
             const double v[5] = {(double)st.lightFramesKernel, (double)st.lightFramesHost, (double)st.lightLaunches, st.light_s, st.lightHost_s};
             std::memcpy(light_stats, v, sizeof v);
@@ -555,6 +567,22 @@ int abh_run_survey_light_dev(void *r, const char *path, const char *planes_dir, 
     return runSurvey(r, path, ncams, nthreads, device, true, stats, report, report_cap, planes_dir, plane_stats, shift_path, shift_radius,
                      shift_stats, field_dir, field_radius, field_stats, light_dir, light_stats);
 }
+int abh_run_survey_focus(void *r, const char *path, const char *planes_dir, const char *shift_path, int shift_radius, const char *field_dir,
+                         int field_radius, const char *light_dir, const char *focus_dir, int ncams, int nthreads, double *stats,
+                         double *plane_stats, double *shift_stats, double *field_stats, double *light_stats, double *focus_stats,
+                         char *report, int report_cap)
+{
+    return runSurvey(r, path, ncams, nthreads, -1, false, stats, report, report_cap, planes_dir, plane_stats, shift_path, shift_radius,
+                     shift_stats, field_dir, field_radius, field_stats, light_dir, light_stats, focus_dir, focus_stats);
+}
+int abh_run_survey_focus_dev(void *r, const char *path, const char *planes_dir, const char *shift_path, int shift_radius,
+                             const char *field_dir, int field_radius, const char *light_dir, const char *focus_dir, int ncams,
+                             int nthreads, int device, double *stats, double *plane_stats, double *shift_stats, double *field_stats,
+                             double *light_stats, double *focus_stats, char *report, int report_cap)
+{
+    return runSurvey(r, path, ncams, nthreads, device, true, stats, report, report_cap, planes_dir, plane_stats, shift_path, shift_radius,
+                     shift_stats, field_dir, field_radius, field_stats, light_dir, light_stats, focus_dir, focus_stats);
+}
 // the whole report of the last abh_run_survey[_dev] on the run (valid until the next query on it)
 const char *abh_run_survey_report(void *r)
 {
@@ -650,6 +678,48 @@ void abh_light_frame(const uint32_t *rec, const uint32_t *model, int cells, long
     const abub::LightFrame f = abub::lightFrame(rec, model, (size_t)std::max(cells, 0));
     const long long v[12] = {f.rated, f.clipped, f.changed, f.up, f.down, f.kind, f.hasGain ? 1 : 0, f.levelMilli, f.ratioMin, f.ratioMax,
                              f.gainMilli, f.offsetMilli};
+    std::memcpy(out, v, sizeof v);
+}
+
+// do ncx x ncy whole cells of 128 x 128 pixels from (x0, y0) and a ring of one pixel around them lie inside a W x H frame?
+static bool focusGridInside(int W, int H, int x0, int y0, int ncx, int ncy)
+{
+    const int C = ABUB_FIELD_CELL;
+    return W >= C + 2 && H >= C + 2 && ncx >= 1 && ncy >= 1 && ncx <= (W - 2) / C && ncy <= (H - 2) / C && x0 >= 1 && y0 >= 1 &&
+           x0 <= W - 1 - C * ncx && y0 <= H - 1 - C * ncy;
+}
+// abub::focusCellsHost / abub::focusModelHost on raw buffers: the W x H frame p against the model plane m / the planes mu and
+// sigma6 on the grid of ncx x ncy cells of 128 x 128 pixels from (x0, y0) -> rec[ncy * ncx * 5] (i32) / rec[ncy * ncx * 3]
+// (i64); returns the number of cells, or -1 (nothing written) for a null pointer or a grid that does not lie inside the
+// frame with its ring
+int abh_focus_cells_host(const uint8_t *p, const uint8_t *m, int W, int H, int x0, int y0, int ncx, int ncy, int32_t *rec)
+{
+    if (!p || !m || !rec || !focusGridInside(W, H, x0, y0, ncx, ncy))
+        return -1;
+    abub::focusCellsHost(p, m, W, H, x0, y0, ncx, ncy, rec);
+    return ncx * ncy;
+}
+int abh_focus_model_host(const uint8_t *mu, const uint8_t *sigma6, int W, int H, int x0, int y0, int ncx, int ncy, int64_t *rec)
+{
+    if (!mu || !sigma6 || !rec || !focusGridInside(W, H, x0, y0, ncx, ncy))
+        return -1;
+    abub::focusModelHost(mu, sigma6, W, H, x0, y0, ncx, ncy, rec);
+    return ncx * ncy;
+}
+// abub::focusCell on raw buffers, what a cell's record says against its model's: out[6] = rated, clipped, changed, softer,
+// keep, energy
+void abh_focus_cell(const int32_t *rec, const int64_t *model, long long *out)
+{
+    const abub::FocusCell c = abub::focusCell(rec, model);
+    const long long v[6] = {c.rated, c.clipped, c.changed, c.softer, c.keep, c.energy};
+    std::memcpy(out, v, sizeof v);
+}
+// abub::focusFrame on raw buffers, what a frame's records say against the model's: out[10] = rated, clipped, changed, softer,
+// harder, kind (0 blind, 1 steady, 2 soft, 3 uneven), keep_milli, keep_min, keep_max, energy_milli
+void abh_focus_frame(const int32_t *rec, const int64_t *model, int cells, long long *out)
+{
+    const abub::FocusFrame f = abub::focusFrame(rec, model, (size_t)std::max(cells, 0));
+    const long long v[10] = {f.rated, f.clipped, f.changed, f.softer, f.harder, f.kind, f.keepMilli, f.keepMin, f.keepMax, f.energyMilli};
     std::memcpy(out, v, sizeof v);
 }
 

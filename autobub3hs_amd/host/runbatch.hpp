@@ -274,6 +274,39 @@ struct LightFrame {
 };
 LightFrame lightFrame(const uint32_t *rec, const uint32_t *model, size_t cells);
 
+// The definition of abub_frame_focus_cells_dev ("Surveying a run for lost focus"): per cell of 128 x 128
+// pixels of the grid (ncx x ncy whole cells, the first at (x0, y0) with x0, y0 >= 1, x0 + 128 ncx + 1 <= W and so in y; the
+// survey's is abub_frame_cells_grid's) five i32 over the cell's pixels, with the central differences
+// gx = p(x + 1, y) - p(x - 1, y), gy = p(x, y + 1) - p(x, y - 1) of the frame and hx, hy of m = mu:
+// rec[(cy * ncx + cx) * 5 + 0 .. 4] = sum gx^2, sum gy^2, sum gx hx, sum gy hy, pixels with p == 0 or p == 255.  Plain
+// loops; a magnitude of at most 16384 * 255^2 < 2^31.
+enum { FocusRecordWords = 5, FocusModelWords = 3 };
+void focusCellsHost(const unsigned char *p, const unsigned char *m, int W, int H, int x0, int y0, int ncx, int ncy, int32_t *rec);
+// The model's share, which depends on the camera alone: rec[(cy * ncx + cx) * 3 + 0 .. 2] = mxx = sum hx^2, myy = sum hy^2
+// and nv = the sum over the cell K and its ring of one pixel of (s6(u) c(u))^2, where c(u) is the coefficient of p(u) in
+// G = sum gx hx + sum gy hy: c(u) = [u - ex in K] hx(u - ex) - [u + ex in K] hx(u + ex) + [u - ey in K] hy(u - ey)
+// - [u + ey in K] hy(u + ey).  With M = mxx + myy, G - M = sum (p - m)(u) c(u) exactly, so sqrt(nv) is six standard
+// deviations of what independent pixel noise of the trained sigma does to G.  nv <= 16900 * (255 * 1020)^2 < 2^63.
+void focusModelHost(const unsigned char *mu, const unsigned char *sigma6, int W, int H, int x0, int y0, int ncx, int ncy, int64_t *rec);
+// What a cell says, from its frame record and its model record (one function for both routes; integers only, __int128).
+// With N = 16384, G = gxm + gym and M = mxx + myy: clipped iff n_clip > N / 16; rated iff not clipped and M^2 > nv (a total
+// loss of agreement could be told from noise); of a rated cell keep = rdiv(1000 G, M), energy = rdiv(1000 (gxx + gyy), M)
+// (lightRdiv), changed iff (M - G)^2 > nv, and of a changed cell softer iff G < M, else harder
+struct FocusCell {
+    bool rated = false, clipped = false, changed = false, softer = false;
+    long long keep = 0, energy = 0;
+};
+FocusCell focusCell(const int32_t *rec, const int64_t *model);
+// What a frame says, from its rated cells: keep_milli = rdiv(1000 sum G, sum M) and energy_milli =
+// rdiv(1000 sum (gxx + gyy), sum M) pooled over them, the range of their keep, and the kind: blind (no rated cell), steady
+// (none of them changed), soft (all of them changed, every one softer), uneven (the rest)
+struct FocusFrame {
+    enum Kind { Blind = 0, Steady = 1, Soft = 2, Uneven = 3 };
+    int rated = 0, clipped = 0, changed = 0, softer = 0, harder = 0, kind = Blind;
+    long long keepMilli = 0, keepMin = 0, keepMax = 0, energyMilli = 0;
+};
+FocusFrame focusFrame(const int32_t *rec, const int64_t *model, size_t cells);
+
 // One row of a survey: a frame the run lists, or one it should list (missing)
 struct SurveyRow {
     enum State { Ok = 0, Undecodable = 1, Missing = 2, OtherSize = 3 };
@@ -289,6 +322,8 @@ struct SurveyRow {
     std::vector<int32_t> field;                   // [ncy][ncx][5]
     bool hasLight = false, lightOnKernel = false; // with a light directory: the same rows have their cells' light records
     std::vector<uint32_t> light;                  // [ncy][ncx][6]
+    bool hasFocus = false, focusOnKernel = false; // with a focus directory: the same rows have their cells' focus records
+    std::vector<int32_t> focus;                   // [ncy][ncx][5]
     const char *stateName() const; // "ok", "undecodable", "missing", "other_size"
 };
 // What the report says of one camera's model
@@ -298,6 +333,7 @@ struct SurveyModel {
     long long pixels = 0, sigmaZero = 0, sigma6Sat = 0; // pixels with sigma == 0; with 6 sigma >= 255
     double muMean = 0;
     std::vector<uint32_t> light; // with a light directory, of a trained camera: lightModelHost's [ncy][ncx][3]
+    std::vector<int64_t> focus;  // with a focus directory, of a trained camera: focusModelHost's [ncy][ncx][3]
 };
 struct SurveyStats {
     int events = 0;
@@ -329,6 +365,10 @@ struct SurveyStats {
     long long lightFramesKernel = 0, lightFramesHost = 0;
     int lightLaunches = 0;
     double light_s = 0, lightHost_s = 0;
+    // With a focus directory: the same five for abub_frame_focus_cells_dev and focusCellsHost
+    long long focusFramesKernel = 0, focusFramesHost = 0;
+    int focusLaunches = 0;
+    double focus_s = 0, focusHost_s = 0;
 };
 // Where a survey writes its per-pixel activity planes (abub3hs --survey-planes; DESIGN section 3, "Surveying a run per
 // pixel"): the directory `dir` (the CLI's DIR/<run_ID>; empty: no planes) gets cam<c>_activity.npy (u32 [6, H, W]) for
@@ -364,6 +404,18 @@ struct SurveyLight {
 // `light cam` line per camera, the `changed` lines of every camera with a model, the `run` line.  Both routes write it
 // through this one function; W, H: the run's size; models[c].light: the camera's model record.
 std::string LightReport(int radius, int W, int H, const std::vector<SurveyModel> &models, const std::vector<SurveyRow> &rows);
+// Where a survey writes its per-cell focus records (abub3hs --survey-focus; DESIGN section 3, "Surveying a run for lost
+// focus"): the directory `dir` (the CLI's DIR/<run_ID>; empty: none) gets cam<c>_focus.npy (i32 [N_c, ncy, ncx, 5]: the
+// records of camera c's rows that have one, in survey order) and cam<c>_focus_model.npy (i64 [ncy, ncx, 3]) for every camera
+// with a model, and focus.txt.  The cells are the field's: abub_frame_cells_grid at SurveyField::radius, whether or not the
+// field or the light is written; a run without a whole cell is refused before its frames are measured.
+struct SurveyFocus {
+    std::string dir, srcRunDir;
+};
+// focus.txt's text: "# abub3hs focus 1", the grid's line, the table's header and one tab-separated row per survey row, one
+// `focus cam` line per camera, the `changed` lines of every camera with a model, the `run` line.  Both routes write it
+// through this one function; W, H: the run's size; models[c].focus: the camera's model record.
+std::string FocusReport(int radius, int W, int H, const std::vector<SurveyModel> &models, const std::vector<SurveyRow> &rows);
 // field.txt's text: "# abub3hs field 1", the grid's line, the table's header and one tab-separated row per survey row, one
 // `field cam` line per camera, the `moved` lines of every camera with a model, the `run` line.  Both routes write it through
 // this one function; W, H: the run's size.
@@ -392,11 +444,14 @@ std::string SurveyReport(const std::vector<SurveyModel> &models, const std::vect
 // With light.dir the same rows also get their per-cell light records (lightCellsHost here; on the device route
 // abub_frame_light_cells_dev behind the launches above) and the light's files are written (both routes: the same bytes).
 // Nothing else changes.
+// With focus.dir the same rows also get their per-cell focus records (focusCellsHost here; on the device route
+// abub_frame_focus_cells_dev behind the launches above) and the focus files are written (both routes: the same bytes).
+// Nothing else changes.
 int SurveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCams, const std::string &imageFormat,
               const std::string &reportPath, int nthreads, SurveyStats *stats, std::vector<SurveyRow> *rows,
               std::vector<SurveyModel> *models = nullptr, const SurveyPlanes &planes = SurveyPlanes(),
               const SurveyShift &shift = SurveyShift(), const SurveyField &field = SurveyField(),
-              const SurveyLight &light = SurveyLight());
+              const SurveyLight &light = SurveyLight(), const SurveyFocus &focus = SurveyFocus());
 // abub3hs --survey FILE --survey-gpu: the same rows and the same report, byte for byte.  The frames are read through the
 // FileBatch protocol (framefiles.hpp) in batches of at most 4 frames per CU (ABUB_SURVEY_BATCH=n: of n), decoded into the
 // batch's slab, and measured by one abub_frame_stats_dev launch per batch.  A batch that begins inside a stack reads again
@@ -408,7 +463,7 @@ int SurveyRunDevice(Parser *parser, const std::vector<Trainer *> &trainers, int 
                     const std::string &reportPath, int nthreads, int device, SurveyStats *stats, std::vector<SurveyRow> *rows,
                     std::vector<SurveyModel> *models = nullptr, const SurveyPlanes &planes = SurveyPlanes(),
                     const SurveyShift &shift = SurveyShift(), const SurveyField &field = SurveyField(),
-              const SurveyLight &light = SurveyLight());
+              const SurveyLight &light = SurveyLight(), const SurveyFocus &focus = SurveyFocus());
 
 // A run listed and trained, ready for detect; rc = -5 (the run cannot be read) or -7 (a camera did not train)
 struct PreparedRun {

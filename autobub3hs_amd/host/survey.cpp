@@ -21,6 +21,10 @@
 // six sums per cell of the field's grid: lightCellsHost is the definition, the device route gets the records from
 // abub_frame_light_cells_dev, lightModelHost sums the model once per camera on the host, lightCell and lightFrame say what
 // the sums mean, and one writer (writeLight, with LightReport for the text) makes the files for both routes.
+// With a focus directory (--survey-focus; DESIGN section 3, "Surveying a run for lost focus") the same rows also get five
+// sums of gradient products per cell of the same grid: focusCellsHost is the definition, the device route gets the records
+// from abub_frame_focus_cells_dev, focusModelHost sums the model once per camera on the host, focusCell and focusFrame say
+// what the sums mean, and one writer (writeFocus, with FocusReport for the text) makes the files for both routes.
 #include <algorithm>
 #include <cinttypes>
 #include <cmath>
@@ -367,6 +371,196 @@ std::string LightReport(int radius, int W, int H, const std::vector<SurveyModel>
     return text;
 }
 
+void focusCellsHost(const unsigned char *p, const unsigned char *m, int W, int H, int x0, int y0, int ncx, int ncy, int32_t *rec)
+{
+    (void)H;
+    const int C = ABUB_FIELD_CELL;
+    for (int cy = 0; cy < ncy; ++cy)
+        for (int cx = 0; cx < ncx; ++cx) {
+            int32_t gxx = 0, gyy = 0, gxm = 0, gym = 0, nClip = 0; // (a magnitude of at most 16384 * 255^2 < 2^31)
+            for (int y = y0 + C * cy; y < y0 + C * (cy + 1); ++y) {
+                const unsigned char *pr = p + (size_t)y * W, *mr = m + (size_t)y * W;
+                for (int x = x0 + C * cx; x < x0 + C * (cx + 1); ++x) {
+                    const int32_t gx = (int32_t)pr[x + 1] - pr[x - 1], gy = (int32_t)pr[x + W] - pr[x - W];
+                    const int32_t hx = (int32_t)mr[x + 1] - mr[x - 1], hy = (int32_t)mr[x + W] - mr[x - W];
+                    gxx += gx * gx;
+                    gyy += gy * gy;
+                    gxm += gx * hx;
+                    gym += gy * hy;
+                    nClip += pr[x] == 0 || pr[x] == 255;
+                }
+            }
+            int32_t *out = rec + ((size_t)cy * ncx + cx) * FocusRecordWords;
+            out[0] = gxx;
+            out[1] = gyy;
+            out[2] = gxm;
+            out[3] = gym;
+            out[4] = nClip;
+        }
+}
+
+void focusModelHost(const unsigned char *mu, const unsigned char *sigma6, int W, int H, int x0, int y0, int ncx, int ncy, int64_t *rec)
+{
+    (void)H;
+    const int C = ABUB_FIELD_CELL;
+    for (int cy = 0; cy < ncy; ++cy)
+        for (int cx = 0; cx < ncx; ++cx) {
+            const int xa = x0 + C * cx, xb = xa + C, ya = y0 + C * cy, yb = ya + C; // K = [xa, xb) x [ya, yb)
+            auto inK = [&](int x, int y) { return x >= xa && x < xb && y >= ya && y < yb; };
+            auto hx = [&](int x, int y) { return (int64_t)mu[(size_t)y * W + x + 1] - mu[(size_t)y * W + x - 1]; };
+            auto hy = [&](int x, int y) { return (int64_t)mu[(size_t)(y + 1) * W + x] - mu[(size_t)(y - 1) * W + x]; };
+            int64_t mxx = 0, myy = 0, nv = 0; // (nv <= 16900 * (255 * 1020)^2 < 2^63)
+            for (int y = ya - 1; y <= yb; ++y)
+                for (int x = xa - 1; x <= xb; ++x) {
+                    if (inK(x, y)) {
+                        mxx += hx(x, y) * hx(x, y);
+                        myy += hy(x, y) * hy(x, y);
+                    }
+                    int64_t c = 0; // the coefficient of p(x, y) in G
+                    if (inK(x - 1, y))
+                        c += hx(x - 1, y);
+                    if (inK(x + 1, y))
+                        c -= hx(x + 1, y);
+                    if (inK(x, y - 1))
+                        c += hy(x, y - 1);
+                    if (inK(x, y + 1))
+                        c -= hy(x, y + 1);
+                    const int64_t t = (int64_t)sigma6[(size_t)y * W + x] * c;
+                    nv += t * t;
+                }
+            int64_t *out = rec + ((size_t)cy * ncx + cx) * FocusModelWords;
+            out[0] = mxx;
+            out[1] = myy;
+            out[2] = nv;
+        }
+}
+
+FocusCell focusCell(const int32_t *rec, const int64_t *model)
+{
+    const long long N = (long long)ABUB_FIELD_CELL * ABUB_FIELD_CELL;
+    const __int128 G = (__int128)rec[2] + rec[3], M = (__int128)model[0] + model[1], nv = model[2];
+    FocusCell c;
+    c.clipped = rec[4] > N / 16;
+    if (c.clipped || !(M * M > nv))
+        return c;
+    c.rated = true;
+    c.keep = lightRdiv(1000 * G, M);
+    c.energy = lightRdiv(1000 * ((__int128)rec[0] + rec[1]), M);
+    c.changed = (M - G) * (M - G) > nv;
+    c.softer = c.changed && G < M;
+    return c;
+}
+
+FocusFrame focusFrame(const int32_t *rec, const int64_t *model, size_t cells)
+{
+    FocusFrame f;
+    __int128 SG = 0, SM = 0, SE = 0;
+    for (size_t k = 0; k < cells; ++k) {
+        const int32_t *r = rec + k * FocusRecordWords;
+        const int64_t *m = model + k * FocusModelWords;
+        const FocusCell c = focusCell(r, m);
+        f.clipped += c.clipped;
+        if (!c.rated)
+            continue;
+        f.keepMin = f.rated ? std::min(f.keepMin, c.keep) : c.keep;
+        f.keepMax = f.rated ? std::max(f.keepMax, c.keep) : c.keep;
+        ++f.rated;
+        f.changed += c.changed;
+        f.softer += c.softer;
+        f.harder += c.changed && !c.softer;
+        SG += (__int128)r[2] + r[3];
+        SE += (__int128)r[0] + r[1];
+        SM += (__int128)m[0] + m[1];
+    }
+    if (!f.rated)
+        return f;
+    f.keepMilli = lightRdiv(1000 * SG, SM); // (SM > 0: every rated cell has M^2 > nv >= 0)
+    f.energyMilli = lightRdiv(1000 * SE, SM);
+    f.kind = !f.changed ? FocusFrame::Steady : f.changed == f.rated && f.harder == 0 ? FocusFrame::Soft : FocusFrame::Uneven;
+    return f;
+}
+
+std::string FocusReport(int radius, int W, int H, const std::vector<SurveyModel> &models, const std::vector<SurveyRow> &rows)
+{
+    int ncx = 0, ncy = 0, x0 = 0, y0 = 0;
+    if (W > 0 && H > 0)
+        abub_frame_cells_grid(W, H, radius, &ncx, &ncy, &x0, &y0);
+    const size_t cells = (size_t)ncx * ncy;
+    std::string text = "# abub3hs focus 1\n";
+    char buf[512];
+    snprintf(buf, sizeof buf, "radius %d cell %d grid %d %d origin %d %d\n", radius, (int)ABUB_FIELD_CELL, ncx, ncy, x0, y0);
+    text += buf;
+    text += "event\tcam\tframe\tname\tstate\tindex\trated\tclipped\tchanged\tsofter\tharder\tkeep_milli\tkeep_min\tkeep_max\tenergy_milli\tkind\n";
+    static const char *const kinds[] = {"blind", "steady", "soft", "uneven"};
+    struct Cam {
+        long long frames = 0, kind[4] = {0, 0, 0, 0};
+        const std::string *first = nullptr;
+        std::vector<long long> changed; // per cell: the frames in which it was rated and changed
+    };
+    std::vector<Cam> cams(models.size());
+    for (const SurveyRow &r : rows) {
+        snprintf(buf, sizeof buf, "%s\t%d\t%d\t%s\t%s", r.event.c_str(), r.cam, r.frame, r.name.c_str(), r.stateName());
+        text += buf;
+        const std::vector<int64_t> *model = (size_t)r.cam < models.size() ? &models[(size_t)r.cam].focus : nullptr;
+        if (r.state != SurveyRow::Ok || !r.hasFocus || r.focus.size() != cells * FocusRecordWords || !model ||
+            model->size() != cells * FocusModelWords) {
+            text += "\t-\t-\t-\t-\t-\t-\t-\t-\t-\t-\t-\n";
+            continue;
+        }
+        Cam &c = cams[(size_t)r.cam];
+        c.changed.resize(cells, 0);
+        const FocusFrame f = focusFrame(r.focus.data(), model->data(), cells);
+        for (size_t k = 0; k < cells; ++k) {
+            const FocusCell fc = focusCell(r.focus.data() + k * FocusRecordWords, model->data() + k * FocusModelWords);
+            c.changed[k] += fc.rated && fc.changed;
+        }
+        snprintf(buf, sizeof buf, "\t%lld\t%d\t%d\t%d\t%d\t%d", c.frames, f.rated, f.clipped, f.changed, f.softer, f.harder);
+        text += buf;
+        if (f.kind == FocusFrame::Blind)
+            snprintf(buf, sizeof buf, "\t-\t-\t-\t-");
+        else
+            snprintf(buf, sizeof buf, "\t%lld\t%lld\t%lld\t%lld", f.keepMilli, f.keepMin, f.keepMax, f.energyMilli);
+        text += buf;
+        text += std::string("\t") + kinds[f.kind] + "\n";
+        ++c.frames;
+        ++c.kind[f.kind];
+        if (f.changed && !c.first)
+            c.first = &r.event;
+    }
+    long long frames = 0, kind[4] = {0, 0, 0, 0};
+    for (size_t c = 0; c < cams.size(); ++c) {
+        if (!models[c].trained) {
+            snprintf(buf, sizeof buf, "focus cam %zu none\n", c);
+            text += buf;
+            continue;
+        }
+        const Cam &k = cams[c];
+        snprintf(buf, sizeof buf, "focus cam %zu frames %lld blind %lld steady %lld soft %lld uneven %lld first_changed_event %s\n", c, k.frames,
+                 k.kind[0], k.kind[1], k.kind[2], k.kind[3], k.first ? k.first->c_str() : "-");
+        text += buf;
+        frames += k.frames;
+        for (int q = 0; q < 4; ++q)
+            kind[q] += k.kind[q];
+    }
+    for (size_t c = 0; c < cams.size(); ++c) {
+        if (!models[c].trained)
+            continue;
+        for (int y = 0; y < ncy; ++y) {
+            snprintf(buf, sizeof buf, "changed cam %zu y %d", c, y);
+            text += buf;
+            for (int x = 0; x < ncx; ++x) {
+                const size_t k = (size_t)y * ncx + x;
+                snprintf(buf, sizeof buf, " %lld", k < cams[c].changed.size() ? cams[c].changed[k] : 0ll);
+                text += buf;
+            }
+            text += "\n";
+        }
+    }
+    snprintf(buf, sizeof buf, "run frames %lld blind %lld steady %lld soft %lld uneven %lld\n", frames, kind[0], kind[1], kind[2], kind[3]);
+    text += buf;
+    return text;
+}
+
 std::string FieldReport(int radius, int W, int H, const std::vector<SurveyModel> &models, const std::vector<SurveyRow> &rows)
 {
     int ncx = 0, ncy = 0, x0 = 0, y0 = 0;
@@ -627,6 +821,9 @@ struct Plan {
     bool light = false;             // with a light directory: surveyFrame gives its ok rows with a model their light records ...
     int lightNcx = 0, lightNcy = 0, lightX0 = 0, lightY0 = 0; // ... on this grid (abub_frame_cells_grid at the field's radius) ...
     std::atomic<long long> *lightHostUs = nullptr; // ... and adds the microseconds it spent in lightCellsHost here
+    bool focus = false;             // with a focus directory: surveyFrame gives its ok rows with a model their focus records ...
+    int focusNcx = 0, focusNcy = 0, focusX0 = 0, focusY0 = 0; // ... on this grid (the same rule) ...
+    std::atomic<long long> *focusHostUs = nullptr; // ... and adds the microseconds it spent in focusCellsHost here
     std::vector<std::string> events;
     std::vector<SurveyRow> rows;    // in event, camera and frame order
     std::vector<size_t> ref;        // ref[i]: the row frame i is measured against (frame max(i - 2, 0) of its stack)
@@ -795,6 +992,18 @@ void lightRowHost(const Plan &pl, const uint8_t *cur, const uint8_t *mu, SurveyR
         *pl.lightHostUs += (long long)((nowMs() - t0) * 1e3);
 }
 
+// The focus records of an ok row of a camera with a model on this thread: the definition
+void focusRowHost(const Plan &pl, const uint8_t *cur, const uint8_t *mu, SurveyRow &row)
+{
+    const double t0 = nowMs();
+    row.focus.resize((size_t)pl.focusNcx * pl.focusNcy * FocusRecordWords);
+    focusCellsHost(cur, mu, pl.W, pl.H, pl.focusX0, pl.focusY0, pl.focusNcx, pl.focusNcy, row.focus.data());
+    row.hasFocus = true;
+    row.focusOnKernel = false;
+    if (pl.focusHostUs)
+        *pl.focusHostUs += (long long)((nowMs() - t0) * 1e3);
+}
+
 // The host route's per-frame function: row i on this thread, its state and its record.  It asks nothing of the other rows:
 // the reference frame is decoded here as well, and is there iff its own row is ok
 void surveyFrame(Parser &p, const Plan &pl, size_t i, SurveyRow &row)
@@ -803,6 +1012,7 @@ void surveyFrame(Parser &p, const Plan &pl, size_t i, SurveyRow &row)
     row.hasShift = row.shiftOnKernel = false;
     row.hasField = row.fieldOnKernel = false;
     row.hasLight = row.lightOnKernel = false;
+    row.hasFocus = row.focusOnKernel = false;
     row.s = FrameStats();
     row.w = row.h = 0;
     if (row.state == SurveyRow::Missing)
@@ -839,6 +1049,8 @@ void surveyFrame(Parser &p, const Plan &pl, size_t i, SurveyRow &row)
         fieldRowHost(pl, cur.data, mu, row);
     if (pl.light && mu)
         lightRowHost(pl, cur.data, mu, row);
+    if (pl.focus && mu)
+        focusRowHost(pl, cur.data, mu, row);
 }
 
 void hostFrames(Parser *parser, Plan &pl, int nthreads)
@@ -882,6 +1094,9 @@ FrameStats fromRecord(const abub_stat_result &r)
 // With pl.light the same rows then get their light records, behind the launches above on the same stream: one
 // abub_frame_light_cells_dev call per batch over [jobs][status words][records] in a buffer of its own, the status words and
 // the records (24 bytes per cell) back in one copy.
+// With pl.focus the same rows then get their focus records in the same way, behind the light's launch on the same stream: one
+// abub_frame_focus_cells_dev call per batch over [jobs][status words][records] in a buffer of its own, the status words and
+// the records (20 bytes per cell) back in one copy.
 void deviceFrames(Parser *parser, Plan &pl, int nthreads, int device, SurveyStats &st, std::vector<uint32_t> &devPlanes)
 {
     HIPOK(hipSetDevice(device));
@@ -893,8 +1108,8 @@ void deviceFrames(Parser *parser, Plan &pl, int nthreads, int device, SurveyStat
     const size_t P = (size_t)W * H, stride = (P + 15) & ~(size_t)15, C = pl.mu.size();
     FileBatch B;
     B.sizer.reset(parser->clone());
-    PinnedBuffer h_meta, h_shift, h_field, h_light;
-    DeviceBuffer d_meta, d_shift, d_field, d_light, d_model; // d_model: [mu of every camera][sigma6 of every camera], camera c at c * stride
+    PinnedBuffer h_meta, h_shift, h_field, h_light, h_focus;
+    DeviceBuffer d_meta, d_shift, d_field, d_light, d_focus, d_model; // d_model: [mu of every camera][sigma6 of every camera], camera c at c * stride
     Stream stream;
     hipStream_t cs = stream.get();
     bool anyModel = false;
@@ -1100,6 +1315,43 @@ void deviceFrames(Parser *parser, Plan &pl, int nthreads, int device, SurveyStat
                 st.light_s += (nowMs() - t0) * 1e-3;
                 t0 = nowMs();
             }
+            if (pl.focus) {
+                st.stats_s += (nowMs() - t0) * 1e-3;
+                t0 = nowMs();
+                std::vector<size_t> with; // the jobs that have a model
+                for (size_t g = 0; g < nj; ++g)
+                    if (jobs[g].model != UINT64_MAX)
+                        with.push_back(g);
+                const size_t ns = with.size(), words = (size_t)pl.focusNcx * pl.focusNcy * FocusRecordWords;
+                if (ns) {
+                    const size_t jobBytes = ns * sizeof(abub_shift_job), bytes = jobBytes + ns * (1 + words) * sizeof(uint32_t);
+                    h_focus.grow(bytes);
+                    d_focus.grow(bytes);
+                    abub_shift_job *fj = (abub_shift_job *)h_focus.get();
+                    for (size_t q = 0; q < ns; ++q)
+                        fj[q] = abub_shift_job{jobs[with[q]].cur, jobs[with[q]].model};
+                    HIPOK(hipMemcpyAsync(d_focus.get(), h_focus.get(), jobBytes, hipMemcpyHostToDevice, cs));
+                    uint32_t *d_status = (uint32_t *)(d_focus.get() + jobBytes);
+                    check(abub_frame_focus_cells_dev(B.slab.get(), slots * stride, d_model.get(), C * stride,
+                                                     (const abub_shift_job *)d_focus.get(), (int)ns, W, H, pl.focusX0, pl.focusY0, pl.focusNcx,
+                                                     pl.focusNcy, d_status, (int32_t *)(d_status + ns), cs),
+                          "abub_frame_focus_cells_dev");
+                    HIPOK(hipMemcpyAsync(h_focus.get() + jobBytes, d_focus.get() + jobBytes, bytes - jobBytes, hipMemcpyDeviceToHost, cs));
+                    HIPOK(hipStreamSynchronize(cs));
+                    const uint32_t *status = (const uint32_t *)(h_focus.get() + jobBytes);
+                    const int32_t *rec = (const int32_t *)(status + ns);
+                    for (size_t q = 0; q < ns; ++q) {
+                        if (status[q] != 0)
+                            throw std::runtime_error("survey: abub_frame_focus_cells_dev refused a frame of its own slab");
+                        SurveyRow &row = pl.rows[rowOf(slot[with[q]])];
+                        row.focus.assign(rec + q * words, rec + (q + 1) * words);
+                        row.hasFocus = row.focusOnKernel = true;
+                    }
+                    ++st.focusLaunches;
+                }
+                st.focus_s += (nowMs() - t0) * 1e-3;
+                t0 = nowMs();
+            }
             if (wantPlanes) {
                 st.stats_s += (nowMs() - t0) * 1e-3;
                 t0 = nowMs();
@@ -1283,6 +1535,42 @@ void writeLight(const std::string &dir, int radius, const Plan &pl)
         throw std::runtime_error("survey: cannot write " + dir + "/light.txt");
 }
 
+// The files of the focus records, one writer for both routes ("Surveying a run for lost focus"): per
+// camera with a model cam<c>_focus.npy, the records of its rows that have one in survey order (the `index` column of
+// focus.txt), cam<c>_focus_model.npy, and focus.txt
+void writeFocus(const std::string &dir, int radius, const Plan &pl)
+{
+    std::string failed;
+    if (!makeDirs(dir, &failed))
+        throw std::runtime_error("survey: cannot make the directory " + failed);
+    const size_t cells = (size_t)pl.focusNcx * pl.focusNcy;
+    for (size_t c = 0; c < pl.models.size(); ++c) {
+        if (!pl.models[c].trained)
+            continue;
+        std::string data;
+        size_t n = 0;
+        for (const SurveyRow &r : pl.rows)
+            if ((size_t)r.cam == c && r.state == SurveyRow::Ok && r.hasFocus && r.focus.size() == cells * FocusRecordWords) {
+                data.append((const char *)r.focus.data(), r.focus.size() * sizeof(int32_t));
+                ++n;
+            }
+        char shape[96];
+        snprintf(shape, sizeof shape, "(%zu, %d, %d, %d)", n, pl.focusNcy, pl.focusNcx, (int)FocusRecordWords);
+        const std::string stem = dir + "/cam" + std::to_string(c);
+        std::string file = npyHead("<i4", shape) + data;
+        if (!writeFile(stem + "_focus.npy", (const unsigned char *)file.data(), file.size()))
+            throw std::runtime_error("survey: cannot write " + stem + "_focus.npy");
+        snprintf(shape, sizeof shape, "(%d, %d, %d)", pl.focusNcy, pl.focusNcx, (int)FocusModelWords);
+        const std::vector<int64_t> &m = pl.models[c].focus;
+        file = npyHead("<i8", shape) + std::string((const char *)m.data(), m.size() * sizeof(int64_t));
+        if (!writeFile(stem + "_focus_model.npy", (const unsigned char *)file.data(), file.size()))
+            throw std::runtime_error("survey: cannot write " + stem + "_focus_model.npy");
+    }
+    const std::string text = FocusReport(radius, pl.W, pl.H, pl.models, pl.rows);
+    if (!writeFile(dir + "/focus.txt", (const unsigned char *)text.data(), text.size()))
+        throw std::runtime_error("survey: cannot write " + dir + "/focus.txt");
+}
+
 // The files of the per-pixel planes, one writer for both routes ("Surveying a run per pixel"): per camera
 // with a listed row the sum of the host's planes and the device's (dev: [camera][6][stride], or empty) as
 // cam<c>_activity.npy, with a model cam<c>_moved.png, and the cameras' lines of activity.txt
@@ -1385,7 +1673,7 @@ bool sameDirectory(const std::string &path, const std::string &other)
 int surveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCams, const std::string &format,
               const std::string &reportPath, int nthreads, int device, SurveyStats *stats, std::vector<SurveyRow> *rows,
               std::vector<SurveyModel> *models, const SurveyPlanes &planes, const SurveyShift &shift, const SurveyField &field,
-              const SurveyLight &light)
+              const SurveyLight &light, const SurveyFocus &focus)
 {
     const double t0 = nowMs();
     SurveyStats st;
@@ -1401,7 +1689,10 @@ int surveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCam
     const std::string lightDir = trimSlashes(light.dir);
     if (!lightDir.empty() && sameDirectory(trimSlashes(light.srcRunDir), lightDir))
         throw std::runtime_error("survey: " + lightDir + " is the run that is being read");
-    if ((!fieldDir.empty() || !lightDir.empty()) && (field.radius < 1 || field.radius > 8))
+    const std::string focusDir = trimSlashes(focus.dir);
+    if (!focusDir.empty() && sameDirectory(trimSlashes(focus.srcRunDir), focusDir))
+        throw std::runtime_error("survey: " + focusDir + " is the run that is being read");
+    if ((!fieldDir.empty() || !lightDir.empty() || !focusDir.empty()) && (field.radius < 1 || field.radius > 8))
         throw std::runtime_error("survey: the field radius must be in [1, 8], not " + std::to_string(field.radius));
     if (!shift.path.empty() && (shift.radius < 1 || shift.radius > 8))
         throw std::runtime_error("survey: the shift radius must be in [1, 8], not " + std::to_string(shift.radius));
@@ -1451,6 +1742,26 @@ int surveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCam
                                pl.models[c].light.data());
             }
     }
+    std::atomic<long long> focusHostUs{0};
+    if (!focusDir.empty()) {
+        if (pl.W > 0) {
+            abub_frame_cells_grid(pl.W, pl.H, field.radius, &pl.focusNcx, &pl.focusNcy, &pl.focusX0, &pl.focusY0);
+            if (pl.focusNcx == 0 || pl.focusNcy == 0) {
+                const int need = ABUB_FIELD_CELL + 2 * field.radius;
+                throw std::runtime_error("survey: the focus records at radius " + std::to_string(field.radius) + " need frames of at least " +
+                                         std::to_string(need) + "x" + std::to_string(need) + ", the run's are " + std::to_string(pl.W) + "x" +
+                                         std::to_string(pl.H));
+            }
+        }
+        pl.focus = true;
+        pl.focusHostUs = &focusHostUs;
+        for (size_t c = 0; c < pl.models.size(); ++c) // (the model's sums depend on the camera alone: once, here, for both routes)
+            if (pl.models[c].trained) {
+                pl.models[c].focus.resize((size_t)pl.focusNcx * pl.focusNcy * FocusModelWords);
+                focusModelHost(pl.mu[c], pl.sigma6[c].data(), pl.W, pl.H, pl.focusX0, pl.focusY0, pl.focusNcx, pl.focusNcy,
+                               pl.models[c].focus.data());
+            }
+    }
     std::unique_ptr<HostPlanes> hostPlanes;
     std::vector<uint32_t> devPlanes;
     if (!planesDir.empty()) {
@@ -1466,10 +1777,10 @@ int surveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCam
     st.H = pl.H;
     for (const SurveyModel &m : pl.models)
         st.modelCams += m.trained;
-    // (abub_frame_shift_dev, abub_frame_shift_cells_dev and abub_frame_light_cells_dev take sides of up to 65535: a larger
-    // run with a shift file, a field or light records is the host route's whole)
+    // (abub_frame_shift_dev, abub_frame_shift_cells_dev, abub_frame_light_cells_dev and abub_frame_focus_cells_dev take sides
+    // of up to 65535: a larger run with a shift file, a field, light or focus records is the host route's whole)
     if (device >= 0 && pl.W > 0 && decodersTakeWidth(pl.W) &&
-        ((!pl.shiftR && !pl.fieldR && !pl.light) || (pl.W <= 65535 && pl.H <= 65535))) {
+        ((!pl.shiftR && !pl.fieldR && !pl.light && !pl.focus) || (pl.W <= 65535 && pl.H <= 65535))) {
         st.device = device;
         deviceFrames(parser, pl, nthreads, device, st, devPlanes);
     } else
@@ -1485,10 +1796,13 @@ int surveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCam
             ++(r.fieldOnKernel ? st.fieldFramesKernel : st.fieldFramesHost);
         if (r.state == SurveyRow::Ok && r.hasLight)
             ++(r.lightOnKernel ? st.lightFramesKernel : st.lightFramesHost);
+        if (r.state == SurveyRow::Ok && r.hasFocus)
+            ++(r.focusOnKernel ? st.focusFramesKernel : st.focusFramesHost);
     }
     st.shiftHost_s = (double)shiftHostUs * 1e-6;
     st.fieldHost_s = (double)fieldHostUs * 1e-6;
     st.lightHost_s = (double)lightHostUs * 1e-6;
+    st.focusHost_s = (double)focusHostUs * 1e-6;
     if (!reportPath.empty()) {
         const std::string text = SurveyReport(pl.models, pl.rows);
         if (!writeFile(reportPath, (const unsigned char *)text.data(), text.size()))
@@ -1503,6 +1817,8 @@ int surveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCam
         writeField(fieldDir, field.radius, pl);
     if (!lightDir.empty())
         writeLight(lightDir, field.radius, pl);
+    if (!focusDir.empty())
+        writeFocus(focusDir, field.radius, pl);
     if (hostPlanes) {
         const double t1 = nowMs();
         st.planeRowsHost = hostPlanes->rows;
@@ -1525,20 +1841,21 @@ int surveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCam
 int SurveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCams, const std::string &imageFormat,
               const std::string &reportPath, int nthreads, SurveyStats *stats, std::vector<SurveyRow> *rows,
               std::vector<SurveyModel> *models, const SurveyPlanes &planes, const SurveyShift &shift, const SurveyField &field,
-              const SurveyLight &light)
+              const SurveyLight &light, const SurveyFocus &focus)
 {
-    return surveyRun(parser, trainers, numCams, imageFormat, reportPath, nthreads, -1, stats, rows, models, planes, shift, field, light);
+    return surveyRun(parser, trainers, numCams, imageFormat, reportPath, nthreads, -1, stats, rows, models, planes, shift, field, light,
+                     focus);
 }
 
 int SurveyRunDevice(Parser *parser, const std::vector<Trainer *> &trainers, int numCams, const std::string &imageFormat,
                     const std::string &reportPath, int nthreads, int device, SurveyStats *stats, std::vector<SurveyRow> *rows,
                     std::vector<SurveyModel> *models, const SurveyPlanes &planes, const SurveyShift &shift, const SurveyField &field,
-                    const SurveyLight &light)
+                    const SurveyLight &light, const SurveyFocus &focus)
 {
     if (device < 0)
         throw std::runtime_error("survey: no such HIP device: " + std::to_string(device));
     return surveyRun(parser, trainers, numCams, imageFormat, reportPath, nthreads, device, stats, rows, models, planes, shift, field,
-                     light);
+                     light, focus);
 }
 
 } // namespace abub

@@ -906,6 +906,32 @@ int abub_frame_light_cells_dev(const uint8_t *frames, size_t frames_bytes, const
                                const abub_shift_job *jobs, int njobs, int W, int H, int x0, int y0, int ncx, int ncy,
                                uint32_t *status /*[njobs]*/, uint32_t *rec /*[njobs * ncy * ncx * 6]*/, void *stream);
 
+/* ---- per-cell edge agreement of resident frames (abub_stats.hip) ------------------------------------------------------
+ * Do the frame's edges still agree with the model's, and where (abub3hs --survey --survey-focus; definition, files and
+ * measurements: DESIGN section 3, "Surveying a run for lost focus")?  Per cell of ABUB_FIELD_CELL x ABUB_FIELD_CELL pixels
+ * on the grid the caller gives (ncx x ncy whole cells, the first at (x0, y0); the survey passes abub_frame_cells_grid's)
+ * five i32 over the cell's pixels, with gx = p(x + 1, y) - p(x - 1, y) and gy = p(x, y + 1) - p(x, y - 1) of the frame at
+ * frames + jobs[j].cur and hx, hy the same differences of the plane at mu + jobs[j].model:
+ *   rec[((j * ncy + cy) * ncx + cx) * 5 + 0 .. 4] = sum gx^2, sum gy^2, sum gx hx, sum gy hy, pixels with p == 0 or p == 255
+ * over x0 + 128 cx <= x < x0 + 128 (cx + 1), y0 + 128 cy <= y < y0 + 128 (cy + 1): 16384 pixels, a magnitude of at most
+ * 16384 * 255^2 = 1065369600 < 2^31.  Every value is an exact integer, bit-identical to the host definition
+ * (host/survey.cpp focusCellsHost) whatever the order of the jobs or the blocks: one launch on `stream` of cells x jobs
+ * blocks of four waves, each reading its cell and the ring of one pixel around it once into two LDS tiles (the frame's and
+ * mu's, 34320 bytes) and writing its five words with plain stores.  Every output word has one owning workgroup: no atomics,
+ * no clearing launch, no scratch buffer, no host synchronisation, no allocation, no workgroup waiting for another.  What a
+ * record means is the host's to say (abub::focusCell).
+ * Every pointer is a device pointer; jobs is 8-byte aligned, status and rec 4-byte aligned; W and H in [130, 65535];
+ * ncx, ncy >= 1, x0, y0 >= 1, x0 + 128 ncx + 1 <= W, y0 + 128 ncy + 1 <= H.  No alignment rule on the offsets or on x0.
+ * status[j] (0 or ABUB_SHIFT_E_RANGE) and all ncx * ncy * 5 values of rec[j] are written in full by every call with
+ * njobs > 0, whatever they held before, and nothing else is written.  A job whose frame runs past frames_bytes or whose
+ * model plane runs past model_bytes gets ABUB_SHIFT_E_RANGE and a zero record; nothing of it is read.  Null pointers,
+ * njobs < 0, W, H or the grid out of range or a misaligned jobs / status / rec: ABUB_E_INVALID before anything touches the
+ * device.  njobs == 0: ABUB_OK, nothing is touched.  njobs may exceed 65535. */
+#define ABUB_FOCUS_WORDS 5
+int abub_frame_focus_cells_dev(const uint8_t *frames, size_t frames_bytes, const uint8_t *mu, size_t model_bytes,
+                               const abub_shift_job *jobs, int njobs, int W, int H, int x0, int y0, int ncx, int ncy,
+                               uint32_t *status /*[njobs]*/, int32_t *rec /*[njobs * ncy * ncx * 5]*/, void *stream);
+
 /* ---- the two DebugPeek planes of a batch of resident frames (abub_peek.hip) ------------------------------------------
  * What L3Localizer::CalculateInitialBubbleParams builds on the analyzer's thread for its debug write-out (reference
  * L3Localizer.cpp:252-257, 397, 448; DESIGN section 3, "The peek planes"), for a batch of items.  Per item two W x H u8
