@@ -685,6 +685,29 @@ def frame_stats(frames, jobs, frame_bytes, mu=None, sigma6=None, frames_bytes=No
 SHIFT_E_RANGE = 1
 
 
+def _model_jobs(entry, frames, mu, jobs, args, frames_bytes, model_bytes, status, out, shape, dtype, view):
+    """The shared body of frame_shift, frame_shift_cells, frame_light_cells and frame_focus_cells, whose entries take
+    (frames, frames_bytes, mu, model_bytes, jobs, n, *args, status, out, stream): the [n, 2] jobs tensor with a spare row
+    behind it, a new status tensor preset to 0x5A5A5A5A and a new `out` of `dtype` preset to -1 where none is given, the
+    call checked -> (status int64 [n] on the host, out as `view` [n, *shape] on the host)."""
+    import numpy as np
+    _need_cuda(frames, mu, status, out)
+    offs = np.array([[int(v) for v in row] for row in jobs], dtype=np.uint64).reshape(-1, 2)
+    n = len(offs)
+    words = n * int(np.prod([max(s, 0) for s in shape]))
+    dev = frames.device
+    d_jobs = torch.from_numpy(np.concatenate([offs, np.zeros((1, 2), np.uint64)]).view(np.int64)).to(dev)
+    if status is None:
+        status = torch.full((max(n, 1),), 0x5A5A5A5A, dtype=torch.int32, device=dev)
+    if out is None:
+        out = torch.full((max(words, 1),), -1, dtype=dtype, device=dev)
+    _lib.check(getattr(_lib.lib(), entry)(_ptr(frames), frames.numel() if frames_bytes is None else int(frames_bytes), _ptr(mu),
+                                          mu.numel() if model_bytes is None else int(model_bytes), _ptr(d_jobs), n, *args, _ptr(status),
+                                          _ptr(out), _stream()), entry)
+    return (status.reshape(-1)[:n].cpu().numpy().astype(np.int64),
+            out.reshape(-1)[:words].cpu().numpy().view(view).reshape(n, *shape))
+
+
 def frame_shift(frames, mu, jobs, W, H, R, frames_bytes=None, model_bytes=None, status=None, sad=None):
     """abub_frame_shift_dev: frames / mu u8 device tensors (any shape), jobs: [n, 2] byte offsets (cur, model) of each job's
     W x H frame in `frames` and of its model plane in `mu` (any alignment); R: the radius, 1 to 8; frames_bytes /
@@ -692,21 +715,9 @@ def frame_shift(frames, mu, jobs, W, H, R, frames_bytes=None, model_bytes=None, 
     int64 device tensor of at least n * (2 R + 1)^2 words, both written in place (None: new ones)
     -> (status int64 [n] on the host: 0 or SHIFT_E_RANGE; the surfaces, uint64 [n, 2 R + 1, 2 R + 1] on the host, entry
     [dy + R, dx + R])."""
-    import numpy as np
-    _need_cuda(frames, mu, status, sad)
-    offs = np.array([[int(v) for v in row] for row in jobs], dtype=np.uint64).reshape(-1, 2)
-    n, D = len(offs), 2 * int(R) + 1
-    dev = frames.device
-    d_jobs = torch.from_numpy(np.concatenate([offs, np.zeros((1, 2), np.uint64)]).view(np.int64)).to(dev)
-    if status is None:
-        status = torch.full((max(n, 1),), 0x5A5A5A5A, dtype=torch.int32, device=dev)
-    if sad is None:
-        sad = torch.full((max(n, 1) * D * D,), -1, dtype=torch.int64, device=dev)
-    _lib.check(_lib.lib().abub_frame_shift_dev(_ptr(frames), frames.numel() if frames_bytes is None else int(frames_bytes), _ptr(mu),
-                                               mu.numel() if model_bytes is None else int(model_bytes), _ptr(d_jobs), n, int(W), int(H),
-                                               int(R), _ptr(status), _ptr(sad), _stream()), "abub_frame_shift_dev")
-    return (status.reshape(-1)[:n].cpu().numpy().astype(np.int64),
-            sad.reshape(-1)[:n * D * D].cpu().numpy().view(np.uint64).reshape(n, D, D))
+    D = 2 * int(R) + 1
+    return _model_jobs("abub_frame_shift_dev", frames, mu, jobs, (int(W), int(H), int(R)), frames_bytes, model_bytes, status, sad,
+                       (D, D), torch.int64, "uint64")
 
 
 FIELD_CELL = 128  # ABUB_FIELD_CELL of include/abub_hip.h
@@ -726,24 +737,10 @@ def frame_shift_cells(frames, mu, jobs, W, H, R, frames_bytes=None, model_bytes=
     n * ncy * ncx * (2 R + 1)^2 words, written in place (None: a new one)
     -> (status int64 [n] on the host: 0 or SHIFT_E_RANGE; the surfaces, uint32 [n, ncy, ncx, 2 R + 1, 2 R + 1] on the
     host, entry [dy + R, dx + R] of cell (cx, cy))."""
-    import numpy as np
-    _need_cuda(frames, mu, status, sad)
-    offs = np.array([[int(v) for v in row] for row in jobs], dtype=np.uint64).reshape(-1, 2)
-    n, D = len(offs), 2 * int(R) + 1
+    D = 2 * int(R) + 1
     ncx, ncy, _, _ = field_grid(W, H, R)
-    words = n * ncy * ncx * D * D
-    dev = frames.device
-    d_jobs = torch.from_numpy(np.concatenate([offs, np.zeros((1, 2), np.uint64)]).view(np.int64)).to(dev)
-    if status is None:
-        status = torch.full((max(n, 1),), 0x5A5A5A5A, dtype=torch.int32, device=dev)
-    if sad is None:
-        sad = torch.full((max(words, 1),), -1, dtype=torch.int32, device=dev)
-    _lib.check(_lib.lib().abub_frame_shift_cells_dev(_ptr(frames), frames.numel() if frames_bytes is None else int(frames_bytes),
-                                                     _ptr(mu), mu.numel() if model_bytes is None else int(model_bytes), _ptr(d_jobs), n,
-                                                     int(W), int(H), int(R), _ptr(status), _ptr(sad), _stream()),
-               "abub_frame_shift_cells_dev")
-    return (status.reshape(-1)[:n].cpu().numpy().astype(np.int64),
-            sad.reshape(-1)[:words].cpu().numpy().view(np.uint32).reshape(n, ncy, ncx, D, D))
+    return _model_jobs("abub_frame_shift_cells_dev", frames, mu, jobs, (int(W), int(H), int(R)), frames_bytes, model_bytes, status, sad,
+                       (ncy, ncx, D, D), torch.int32, "uint32")
 
 
 LIGHT_WORDS = 6  # ABUB_LIGHT_WORDS of include/abub_hip.h
@@ -754,24 +751,8 @@ def frame_light_cells(frames, mu, jobs, W, H, x0, y0, ncx, ncy, frames_bytes=Non
     from (x0, y0); rec: int32 device tensor of at least n * ncy * ncx * 6 words, written in place (None: a new one)
     -> (status int64 [n] on the host: 0 or SHIFT_E_RANGE; the records, uint32 [n, ncy, ncx, 6] on the host: the sums of p,
     p^2, p m and |p - m|, the pixels with p == 0 and with p == 255)."""
-    import numpy as np
-    _need_cuda(frames, mu, status, rec)
-    offs = np.array([[int(v) for v in row] for row in jobs], dtype=np.uint64).reshape(-1, 2)
-    n = len(offs)
-    words = n * max(int(ncy), 0) * max(int(ncx), 0) * LIGHT_WORDS
-    dev = frames.device
-    d_jobs = torch.from_numpy(np.concatenate([offs, np.zeros((1, 2), np.uint64)]).view(np.int64)).to(dev)
-    if status is None:
-        status = torch.full((max(n, 1),), 0x5A5A5A5A, dtype=torch.int32, device=dev)
-    if rec is None:
-        rec = torch.full((max(words, 1),), -1, dtype=torch.int32, device=dev)
-    _lib.check(_lib.lib().abub_frame_light_cells_dev(_ptr(frames), frames.numel() if frames_bytes is None else int(frames_bytes),
-                                                     _ptr(mu), mu.numel() if model_bytes is None else int(model_bytes), _ptr(d_jobs), n,
-                                                     int(W), int(H), int(x0), int(y0), int(ncx), int(ncy), _ptr(status), _ptr(rec),
-                                                     _stream()),
-               "abub_frame_light_cells_dev")
-    return (status.reshape(-1)[:n].cpu().numpy().astype(np.int64),
-            rec.reshape(-1)[:words].cpu().numpy().view(np.uint32).reshape(n, ncy, ncx, LIGHT_WORDS))
+    return _model_jobs("abub_frame_light_cells_dev", frames, mu, jobs, (int(W), int(H), int(x0), int(y0), int(ncx), int(ncy)),
+                       frames_bytes, model_bytes, status, rec, (int(ncy), int(ncx), LIGHT_WORDS), torch.int32, "uint32")
 
 
 FOCUS_WORDS = 5  # ABUB_FOCUS_WORDS of include/abub_hip.h
@@ -782,24 +763,8 @@ def frame_focus_cells(frames, mu, jobs, W, H, x0, y0, ncx, ncy, frames_bytes=Non
     from (x0, y0), with a ring of one pixel inside the frame; rec: int32 device tensor of at least n * ncy * ncx * 5 words,
     written in place (None: a new one) -> (status int64 [n] on the host: 0 or SHIFT_E_RANGE; the records, int32
     [n, ncy, ncx, 5] on the host: the sums of gx^2, gy^2, gx hx and gy hy, the pixels with p == 0 or p == 255)."""
-    import numpy as np
-    _need_cuda(frames, mu, status, rec)
-    offs = np.array([[int(v) for v in row] for row in jobs], dtype=np.uint64).reshape(-1, 2)
-    n = len(offs)
-    words = n * max(int(ncy), 0) * max(int(ncx), 0) * FOCUS_WORDS
-    dev = frames.device
-    d_jobs = torch.from_numpy(np.concatenate([offs, np.zeros((1, 2), np.uint64)]).view(np.int64)).to(dev)
-    if status is None:
-        status = torch.full((max(n, 1),), 0x5A5A5A5A, dtype=torch.int32, device=dev)
-    if rec is None:
-        rec = torch.full((max(words, 1),), -1, dtype=torch.int32, device=dev)
-    _lib.check(_lib.lib().abub_frame_focus_cells_dev(_ptr(frames), frames.numel() if frames_bytes is None else int(frames_bytes),
-                                                     _ptr(mu), mu.numel() if model_bytes is None else int(model_bytes), _ptr(d_jobs), n,
-                                                     int(W), int(H), int(x0), int(y0), int(ncx), int(ncy), _ptr(status), _ptr(rec),
-                                                     _stream()),
-               "abub_frame_focus_cells_dev")
-    return (status.reshape(-1)[:n].cpu().numpy().astype(np.int64),
-            rec.reshape(-1)[:words].cpu().numpy().view(np.int32).reshape(n, ncy, ncx, FOCUS_WORDS))
+    return _model_jobs("abub_frame_focus_cells_dev", frames, mu, jobs, (int(W), int(H), int(x0), int(y0), int(ncx), int(ncy)),
+                       frames_bytes, model_bytes, status, rec, (int(ncy), int(ncx), FOCUS_WORDS), torch.int32, "int32")
 
 
 ACT_PLANES = ("n_zero","n_sat", "n_out", "sum_out", "n_moved", "sum_moved")

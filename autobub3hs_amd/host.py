@@ -495,66 +495,18 @@ class Run:
         the stats then also have focus_frames_kernel / focus_frames_host, focus_launches and the legs focus_s and
         focus_host_s.  Nothing else changes."""
         L = lib()
-        st = (C.c_double * 24)()
-        pst = (C.c_double * 5)()
-        sst = (C.c_double * 5)()
-        fst = (C.c_double * 5)()
-        lst = (C.c_double * 5)()
-        ost = (C.c_double * 5)()
+        st, pst = (C.c_double * 24)(), (C.c_double * 5)()
+        products = [(v, (C.c_double * 5)(), k) for v, k in ((shift, "shift"), (field, "field"), (light, "light"), (focus, "focus"))]
         cap = 1 << 16
         buf = C.create_string_buffer(cap)
-        to = None if path is None else str(path).encode()
-        if focus is not None:
-            pd = None if planes is None else str(planes).encode()
-            sp = None if shift is None else str(shift).encode()
-            fd = None if field is None else str(field).encode()
-            ld = None if light is None else str(light).encode()
-            od = str(focus).encode()
-            if device is None:
-                rc = L.abh_run_survey_focus(self._h, to, pd, sp, int(shift_radius), fd, int(field_radius), ld, od, ncams, nthreads, st, pst,
-                                            sst, fst, lst, ost, buf, cap)
-            else:
-                rc = L.abh_run_survey_focus_dev(self._h, to, pd, sp, int(shift_radius), fd, int(field_radius), ld, od, ncams, nthreads,
-                                                int(device), st, pst, sst, fst, lst, ost, buf, cap)
-        elif light is not None:
-            pd = None if planes is None else str(planes).encode()
-            sp = None if shift is None else str(shift).encode()
-            fd = None if field is None else str(field).encode()
-            ld = str(light).encode()
-            if device is None:
-                rc = L.abh_run_survey_light(self._h, to, pd, sp, int(shift_radius), fd, int(field_radius), ld, ncams, nthreads, st, pst,
-                                            sst, fst, lst, buf, cap)
-            else:
-                rc = L.abh_run_survey_light_dev(self._h, to, pd, sp, int(shift_radius), fd, int(field_radius), ld, ncams, nthreads,
-                                                int(device), st, pst, sst, fst, lst, buf, cap)
-        elif field is not None:
-            pd = None if planes is None else str(planes).encode()
-            sp = None if shift is None else str(shift).encode()
-            fd = str(field).encode()
-            if device is None:
-                rc = L.abh_run_survey_field(self._h, to, pd, sp, int(shift_radius), fd, int(field_radius), ncams, nthreads, st, pst, sst,
-                                            fst, buf, cap)
-            else:
-                rc = L.abh_run_survey_field_dev(self._h, to, pd, sp, int(shift_radius), fd, int(field_radius), ncams, nthreads,
-                                                int(device), st, pst, sst, fst, buf, cap)
-        elif shift is not None:
-            pd = None if planes is None else str(planes).encode()
-            sp = str(shift).encode()
-            if device is None:
-                rc = L.abh_run_survey_shift(self._h, to, pd, sp, int(shift_radius), ncams, nthreads, st, pst, sst, buf, cap)
-            else:
-                rc = L.abh_run_survey_shift_dev(self._h, to, pd, sp, int(shift_radius), ncams, nthreads, int(device), st, pst, sst, buf,
-                                                cap)
-        elif planes is not None:
-            pd = str(planes).encode()
-            if device is None:
-                rc = L.abh_run_survey_planes(self._h, to, pd, ncams, nthreads, st, pst, buf, cap)
-            else:
-                rc = L.abh_run_survey_planes_dev(self._h, to, pd, ncams, nthreads, int(device), st, pst, buf, cap)
-        elif device is None:
-            rc = L.abh_run_survey(self._h, to, ncams, nthreads, st, buf, cap)
+        # the widest entry takes every product; a NULL path: that product is not made
+        to, pd, sp, fd, ld, od = (None if p is None else str(p).encode() for p in (path, planes, shift, field, light, focus))
+        args = (self._h, to, pd, sp, int(shift_radius), fd, int(field_radius), ld, od, ncams, nthreads)
+        out = (st, pst, *(a for _, a, _ in products), buf, cap)
+        if device is None:
+            rc = L.abh_run_survey_focus(*args, *out)
         else:
-            rc = L.abh_run_survey_dev(self._h, to, ncams, nthreads, int(device), st, buf, cap)
+            rc = L.abh_run_survey_focus_dev(*args, int(device), *out)
         if rc not in (0, 1):
             raise RuntimeError(f"abh_run_survey rc={rc}: " + L.abh_last_error(self._h).decode())
         text = buf.value if st[23] < cap else L.abh_run_survey_report(self._h)
@@ -563,18 +515,10 @@ class Run:
         if planes is not None:
             res.update(plane_rows_kernel=int(pst[0]), plane_rows_host=int(pst[1]), activity_s=pst[2], planes_copy_s=pst[3],
                        planes_write_s=pst[4])
-        if shift is not None:
-            res.update(shift_frames_kernel=int(sst[0]), shift_frames_host=int(sst[1]), shift_launches=int(sst[2]), shift_s=sst[3],
-                       shift_host_s=sst[4])
-        if field is not None:
-            res.update(field_frames_kernel=int(fst[0]), field_frames_host=int(fst[1]), field_launches=int(fst[2]), field_s=fst[3],
-                       field_host_s=fst[4])
-        if light is not None:
-            res.update(light_frames_kernel=int(lst[0]), light_frames_host=int(lst[1]), light_launches=int(lst[2]), light_s=lst[3],
-                       light_host_s=lst[4])
-        if focus is not None:
-            res.update(focus_frames_kernel=int(ost[0]), focus_frames_host=int(ost[1]), focus_launches=int(ost[2]), focus_s=ost[3],
-                       focus_host_s=ost[4])
+        for want, a, k in products:
+            if want is not None:
+                res.update({f"{k}_frames_kernel": int(a[0]), f"{k}_frames_host": int(a[1]), f"{k}_launches": int(a[2]), f"{k}_s": a[3],
+                            f"{k}_host_s": a[4]})
         return res, text.decode()
 
     def analyze(self, event, cam, maskdir=""):

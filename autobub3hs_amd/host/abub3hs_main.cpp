@@ -492,38 +492,31 @@ int main(int argc, char **argv)
             return -1;
         }
     }
-    if (surveyGpu && !haveSurvey) {
-        std::cerr << "--survey-gpu is valid only together with --survey" << std::endl;
-        return -1;
-    }
-    if (haveSurveyPlanes && !haveSurvey) {
-        std::cerr << "--survey-planes is valid only together with --survey" << std::endl;
-        return -1;
-    }
-    if (haveSurveyShift && !haveSurvey) {
-        std::cerr << "--survey-shift is valid only together with --survey" << std::endl;
-        return -1;
-    }
-    if (haveShiftRadius && !haveSurveyShift) {
-        std::cerr << "--survey-shift-radius is valid only together with --survey-shift" << std::endl;
-        return -1;
-    }
-    if (haveSurveyField && !haveSurvey) {
-        std::cerr << "--survey-field is valid only together with --survey" << std::endl;
-        return -1;
-    }
-    if (haveSurveyLight && !haveSurvey) {
-        std::cerr << "--survey-light is valid only together with --survey" << std::endl;
-        return -1;
-    }
-    if (haveSurveyFocus && !haveSurvey) {
-        std::cerr << "--survey-focus is valid only together with --survey" << std::endl;
-        return -1;
-    }
-    if (haveFieldRadius && !haveSurveyField && !haveSurveyLight && !haveSurveyFocus) { // (the light's and the focus' cells are the field's)
-        std::cerr << "--survey-field-radius is valid only together with --survey-field" << std::endl;
-        return -1;
-    }
+    // the --survey-* flags, in the order they are checked: the flag it is valid only together with, and of those that take
+    // a place to write to that place and what it is
+    const struct {
+        const char *flag;
+        bool have;
+        const char *with;
+        bool haveWith;
+        const std::string *value;
+        const char *noun;
+    } surveyFlags[] = {
+        {"--survey-gpu", surveyGpu, "--survey", haveSurvey, nullptr, nullptr},
+        {"--survey-planes", haveSurveyPlanes, "--survey", haveSurvey, &surveyPlanesDir, "directory"},
+        {"--survey-shift", haveSurveyShift, "--survey", haveSurvey, &surveyShiftFile, "file"},
+        {"--survey-shift-radius", haveShiftRadius, "--survey-shift", haveSurveyShift, nullptr, nullptr},
+        {"--survey-field", haveSurveyField, "--survey", haveSurvey, &surveyFieldDir, "directory"},
+        {"--survey-light", haveSurveyLight, "--survey", haveSurvey, &surveyLightDir, "directory"},
+        {"--survey-focus", haveSurveyFocus, "--survey", haveSurvey, &surveyFocusDir, "directory"},
+        // (the light's and the focus' cells are the field's)
+        {"--survey-field-radius", haveFieldRadius, "--survey-field", haveSurveyField || haveSurveyLight || haveSurveyFocus, nullptr, nullptr},
+    };
+    for (const auto &f : surveyFlags)
+        if (f.have && !f.haveWith) {
+            std::cerr << f.flag << " is valid only together with " << f.with << std::endl;
+            return -1;
+        }
     if (haveSurvey) {
         const char *bad = haveUnpack ? "--unpack" : haveRepack ? "--repack" : haveVerify ? "--verify-repack" : mergeN > 0 ? "--merge"
                           : debug_mode ? "--debug" : perEvent ? "--per-event" : event_user >= 0 ? "-e/--event" : havePeek ? "--peek"
@@ -536,26 +529,11 @@ int main(int argc, char **argv)
             std::cerr << "--survey needs --data_dir, --run_id and the file to write the report to" << std::endl;
             return -1;
         }
-        if (haveSurveyPlanes && surveyPlanesDir.empty()) {
-            std::cerr << "--survey-planes needs the directory to write to" << std::endl;
-            return -1;
-        }
-        if (haveSurveyShift && surveyShiftFile.empty()) {
-            std::cerr << "--survey-shift needs the file to write to" << std::endl;
-            return -1;
-        }
-        if (haveSurveyField && surveyFieldDir.empty()) {
-            std::cerr << "--survey-field needs the directory to write to" << std::endl;
-            return -1;
-        }
-        if (haveSurveyLight && surveyLightDir.empty()) {
-            std::cerr << "--survey-light needs the directory to write to" << std::endl;
-            return -1;
-        }
-        if (haveSurveyFocus && surveyFocusDir.empty()) {
-            std::cerr << "--survey-focus needs the directory to write to" << std::endl;
-            return -1;
-        }
+        for (const auto &f : surveyFlags)
+            if (f.have && f.value && f.value->empty()) {
+                std::cerr << f.flag << " needs the " << f.noun << " to write to" << std::endl;
+                return -1;
+            }
     }
     if (unpackGpu && !haveUnpack) {
         std::cerr << "--unpack-gpu is valid only together with --unpack" << std::endl;
@@ -725,34 +703,17 @@ int main(int argc, char **argv)
         abub::BatchedRunOptions po;
         po.trainOnGpu = 0; // (a single run trains through the host Trainer, as the reference does)
         abub::SurveyStats ss;
-        abub::SurveyPlanes planes;
-        if (haveSurveyPlanes) {
-            planes.dir = surveyPlanesDir + "/" + run_number;
-            planes.srcRunDir = zipped ? std::string() : sp.eventDir;
-        }
-        abub::SurveyShift shift;
-        if (haveSurveyShift) {
-            shift.path = surveyShiftFile;
-            shift.radius = surveyShiftRadius;
-        }
-        abub::SurveyField field;
-        if (haveSurveyField) {
-            field.dir = surveyFieldDir + "/" + run_number;
-            field.srcRunDir = zipped ? std::string() : sp.eventDir;
-            field.radius = surveyFieldRadius;
-        }
-        abub::SurveyLight light;
-        if (haveSurveyLight) {
-            light.dir = surveyLightDir + "/" + run_number;
-            light.srcRunDir = zipped ? std::string() : sp.eventDir;
-            field.radius = surveyFieldRadius; // (the grid's radius, whether or not the field is written)
-        }
-        abub::SurveyFocus focus;
-        if (haveSurveyFocus) {
-            focus.dir = surveyFocusDir + "/" + run_number;
-            focus.srcRunDir = zipped ? std::string() : sp.eventDir;
-            field.radius = surveyFieldRadius; // (the grid's radius, whether or not the field is written)
-        }
+        abub::SurveyRequest rq;
+        rq.reportPath = surveyFile;
+        rq.srcRunDir = zipped ? std::string() : sp.eventDir;
+        const auto under = [&](bool have, const std::string &dir) { return have ? dir + "/" + run_number : std::string(); };
+        rq.planesDir = under(haveSurveyPlanes, surveyPlanesDir);
+        rq.shiftPath = surveyShiftFile;
+        rq.shiftRadius = surveyShiftRadius;
+        rq.fieldDir = under(haveSurveyField, surveyFieldDir);
+        rq.cellRadius = surveyFieldRadius;
+        rq.lightDir = under(haveSurveyLight, surveyLightDir);
+        rq.focusDir = under(haveSurveyFocus, surveyFocusDir);
         int rc = 1;
         try {
             abub::PreparedRun prep = abub::PrepareRun(sp, po, 0, nullptr, false);
@@ -760,10 +721,8 @@ int main(int argc, char **argv)
                 return -5;
             if (prep.rc)
                 printf("survey: a camera did not train: the report has no model columns for it\n");
-            rc = surveyGpu ? abub::SurveyRunDevice(prep.parser.get(), prep.trainers, sp.numCams, sp.imageFormat, surveyFile, poolThreads(), 0,
-                                                   &ss, nullptr, nullptr, planes, shift, field, light, focus)
-                           : abub::SurveyRun(prep.parser.get(), prep.trainers, sp.numCams, sp.imageFormat, surveyFile, poolThreads(), &ss,
-                                             nullptr, nullptr, planes, shift, field, light, focus);
+            // (--survey-gpu is GPU 0, so "no such HIP device" for a negative one cannot arise here; SurveyRun refuses a missing GPU 0)
+            rc = abub::SurveyRun(prep.parser.get(), prep.trainers, sp.numCams, sp.imageFormat, rq, poolThreads(), surveyGpu ? 0 : -1, &ss);
         } catch (std::exception &e) {
             std::cerr << "survey failed: " << e.what() << std::endl;
             return -6;
@@ -790,23 +749,21 @@ int main(int argc, char **argv)
         if (haveSurveyPlanes)
             printf("survey-planes: %s: %lld rows added on the GPU, %lld on the host; activity launches %.3f s, copy back %.3f s, files "
                    "%.3f s\n",
-                   planes.dir.c_str(), ss.planeRowsKernel, ss.planeRowsHost, ss.activity_s, ss.planes_copy_s, ss.planes_write_s);
-        if (haveSurveyShift)
-            printf("survey-shift: %s: radius %d, %lld frames searched on the GPU in %d launches, %lld on the host; shift leg %.3f s, host "
-                   "threads %.3f s\n",
-                   shift.path.c_str(), shift.radius, ss.shiftFramesKernel, ss.shiftLaunches, ss.shiftFramesHost, ss.shift_s, ss.shiftHost_s);
-        if (haveSurveyField)
-            printf("survey-field: %s: radius %d, %lld frames searched on the GPU in %d launches, %lld on the host; field leg %.3f s, host "
-                   "threads %.3f s\n",
-                   field.dir.c_str(), field.radius, ss.fieldFramesKernel, ss.fieldLaunches, ss.fieldFramesHost, ss.field_s, ss.fieldHost_s);
-        if (haveSurveyLight)
-            printf("survey-light: %s: radius %d, %lld frames summed on the GPU in %d launches, %lld on the host; light leg %.3f s, host "
-                   "threads %.3f s\n",
-                   light.dir.c_str(), field.radius, ss.lightFramesKernel, ss.lightLaunches, ss.lightFramesHost, ss.light_s, ss.lightHost_s);
-        if (haveSurveyFocus)
-            printf("survey-focus: %s: radius %d, %lld frames summed on the GPU in %d launches, %lld on the host; focus leg %.3f s, host "
-                   "threads %.3f s\n",
-                   focus.dir.c_str(), field.radius, ss.focusFramesKernel, ss.focusLaunches, ss.focusFramesHost, ss.focus_s, ss.focusHost_s);
+                   rq.planesDir.c_str(), ss.planeRowsKernel, ss.planeRowsHost, ss.activity_s, ss.planes_copy_s, ss.planes_write_s);
+        const struct {
+            bool have;
+            const char *name, *to, *verb;
+            int radius;
+        } products[abub::SurveyProducts] = {{haveSurveyShift, "shift", rq.shiftPath.c_str(), "searched", rq.shiftRadius},
+                                            {haveSurveyField, "field", rq.fieldDir.c_str(), "searched", rq.cellRadius},
+                                            {haveSurveyLight, "light", rq.lightDir.c_str(), "summed", rq.cellRadius},
+                                            {haveSurveyFocus, "focus", rq.focusDir.c_str(), "summed", rq.cellRadius}};
+        for (int p = 0; p < abub::SurveyProducts; ++p)
+            if (products[p].have)
+                printf("survey-%s: %s: radius %d, %lld frames %s on the GPU in %d launches, %lld on the host; %s leg %.3f s, host "
+                       "threads %.3f s\n",
+                       products[p].name, products[p].to, products[p].radius, ss.product[p].framesKernel, products[p].verb,
+                       ss.product[p].launches, ss.product[p].framesHost, products[p].name, ss.product[p].leg_s, ss.product[p].host_s);
         return rc;
     }
     if (haveList) {

@@ -396,31 +396,46 @@ const char *abh_run_verify_report(void *src)
 // the GPU, the device (-1: its route was not taken), W, H, batches, cameras with a model, seconds of the legs read, upload +
 // decode, measure, seconds in all, the report's length].  report (may be NULL): the report's text, cut at report_cap - 1
 // characters; the whole text stays with the run for abh_run_survey_report.  Returns SurveyRun's code (0, or 1 if a frame is
-// not ok), -5 if the run cannot be read, -1 on errors.  abh_run_survey_dev: abub::SurveyRunDevice on `device`, no fall-back
+// not ok), -5 if the run cannot be read, -1 on errors.  abh_run_survey_dev: the device route on `device`, no fall-back
 // when there is no such device.
-// abh_run_survey_planes[_dev]: the same with the per-pixel planes written to planes_dir (abub::SurveyPlanes::dir, the CLI's
+// abh_run_survey_planes[_dev]: the same with the per-pixel planes written to planes_dir (abub::SurveyRequest::planesDir, the CLI's
 // DIR/<run_ID>; NULL or empty: none) and plane_stats (may be NULL, 5 values): [rows added to the planes by
 // abub_pixel_activity_dev, rows added by a host thread, seconds of the activity launches, of the copy back, of the files].
-// abh_run_survey_shift[_dev]: the same with the shift search (abub::SurveyShift; DESIGN section 3, "Surveying a run for
+// abh_run_survey_shift[_dev]: the same with the shift search (SurveyRequest::shiftPath; DESIGN section 3, "Surveying a run for
 // movement") written to shift_path (NULL or empty: none) at radius shift_radius (1 to 8), and shift_stats (may be NULL, 5
 // values): [frames searched by abub_frame_shift_dev, by a host thread, the kernel's calls, seconds of the device route's shift
 // leg, seconds the host threads spent in frameShiftHost].
-// abh_run_survey_field[_dev]: the same with the per-cell shift field (abub::SurveyField; DESIGN section 3, "Surveying a run
+// abh_run_survey_field[_dev]: the same with the per-cell shift field (SurveyRequest::fieldDir; DESIGN section 3, "Surveying a run
 // for local movement") written to field_dir (the CLI's DIR/<run_ID>; NULL or empty: none) at radius field_radius (1 to 8),
 // and field_stats (may be NULL, 5 values): the shift's five for abub_frame_shift_cells_dev and fieldCellsHost.
-// abh_run_survey_light[_dev]: the same with the per-cell light records (abub::SurveyLight; DESIGN section 3, "Surveying a run
+// abh_run_survey_light[_dev]: the same with the per-cell light records (SurveyRequest::lightDir; DESIGN section 3, "Surveying a run
 // for lighting changes") written to light_dir (the CLI's DIR/<run_ID>; NULL or empty: none) on the grid of field_radius,
 // whether or not field_dir is given, and light_stats (may be NULL, 5 values): the same five for abub_frame_light_cells_dev
 // and lightCellsHost.
-// abh_run_survey_focus[_dev]: the same with the per-cell focus records (abub::SurveyFocus; DESIGN section 3, "Surveying a run
+// abh_run_survey_focus[_dev]: the same with the per-cell focus records (SurveyRequest::focusDir; DESIGN section 3, "Surveying a run
 // for lost focus") written to focus_dir (the CLI's DIR/<run_ID>; NULL or empty: none) on the grid of field_radius, whether
 // or not field_dir or light_dir is given, and focus_stats (may be NULL, 5 values): the same five for
 // abub_frame_focus_cells_dev and focusCellsHost.
-static int runSurvey(void *r, const char *path, int ncams, int nthreads, int device, bool onDevice, double *stats, char *report,
-                     int report_cap, const char *planes_dir = nullptr, double *plane_stats = nullptr, const char *shift_path = nullptr,
-                     int shift_radius = 4, double *shift_stats = nullptr, const char *field_dir = nullptr, int field_radius = 4,
-                     double *field_stats = nullptr, const char *light_dir = nullptr, double *light_stats = nullptr,
-                     const char *focus_dir = nullptr, double *focus_stats = nullptr)
+// what an entry's arguments ask for (a NULL path: none; the directory the run is read from is runSurvey's to fill in)
+static abub::SurveyRequest surveyRequest(const char *path, const char *planes_dir = nullptr, const char *shift_path = nullptr,
+                                         int shift_radius = 4, const char *field_dir = nullptr, int field_radius = 4,
+                                         const char *light_dir = nullptr, const char *focus_dir = nullptr)
+{
+    const auto str = [](const char *s) { return std::string(s ? s : ""); };
+    abub::SurveyRequest rq;
+    rq.reportPath = str(path);
+    rq.planesDir = str(planes_dir);
+    rq.shiftPath = str(shift_path);
+    rq.shiftRadius = shift_radius;
+    rq.fieldDir = str(field_dir);
+    rq.cellRadius = field_radius;
+    rq.lightDir = str(light_dir);
+    rq.focusDir = str(focus_dir);
+    return rq;
+}
+static int runSurvey(void *r, abub::SurveyRequest rq, int ncams, int nthreads, int device, bool onDevice, char *report, int report_cap,
+                     double *stats, double *plane_stats = nullptr, double *shift_stats = nullptr, double *field_stats = nullptr,
+                     double *light_stats = nullptr, double *focus_stats = nullptr)
 {
     Run *run = (Run *)r;
     try {
@@ -442,43 +457,18 @@ static int runSurvey(void *r, const char *path, int ncams, int nthreads, int dev
         abub::SurveyStats st;
         std::vector<abub::SurveyRow> rows;
         std::vector<abub::SurveyModel> models;
-        const std::string to = path ? path : "";
-        abub::SurveyPlanes planes;
-        planes.dir = planes_dir ? planes_dir : "";
-        planes.srcRunDir = run->kind == 0 ? run->runFolder : std::string();
-        abub::SurveyShift shift;
-        shift.path = shift_path ? shift_path : "";
-        shift.radius = shift_radius;
-        abub::SurveyField field;
-        field.dir = field_dir ? field_dir : "";
-        field.srcRunDir = planes.srcRunDir;
-        field.radius = field_radius;
-        abub::SurveyLight light;
-        light.dir = light_dir ? light_dir : "";
-        light.srcRunDir = planes.srcRunDir;
-        abub::SurveyFocus focus;
-        focus.dir = focus_dir ? focus_dir : "";
-        focus.srcRunDir = planes.srcRunDir;
-        const int rc = onDevice ? abub::SurveyRunDevice(pr.parser.get(), pr.trainers, ncams, sp.imageFormat, to, std::max(1, nthreads),
-                                                        device, &st, &rows, &models, planes, shift, field, light, focus)
-                                : abub::SurveyRun(pr.parser.get(), pr.trainers, ncams, sp.imageFormat, to, std::max(1, nthreads), &st,
-                                                  &rows, &models, planes, shift, field, light, focus);
-        if (focus_stats) {
-            const double v[5] = {(double)st.focusFramesKernel, (double)st.focusFramesHost, (double)st.focusLaunches, st.focus_s, st.focusHost_s};
-            std::memcpy(focus_stats, v, sizeof v);
-        }
-        if (light_stats) {
-            const double v[5] = {(double)st.lightFramesKernel, (double)st.lightFramesHost, (double)st.lightLaunches, st.light_s, st.lightHost_s};
-            std::memcpy(light_stats, v, sizeof v);
-        }
-        if (field_stats) {
-            const double v[5] = {(double)st.fieldFramesKernel, (double)st.fieldFramesHost, (double)st.fieldLaunches, st.field_s, st.fieldHost_s};
-            std::memcpy(field_stats, v, sizeof v);
-        }
-        if (shift_stats) {
-            const double v[5] = {(double)st.shiftFramesKernel, (double)st.shiftFramesHost, (double)st.shiftLaunches, st.shift_s, st.shiftHost_s};
-            std::memcpy(shift_stats, v, sizeof v);
-        }
+        rq.srcRunDir = run->kind == 0 ? run->runFolder : std::string();
+        if (onDevice && device < 0) // (a _dev entry chose the device route: there is no falling back to the host's)
+            throw std::runtime_error("survey: no such HIP device: " + std::to_string(device));
+        const int rc = abub::SurveyRun(pr.parser.get(), pr.trainers, ncams, sp.imageFormat, rq, std::max(1, nthreads), onDevice ? device : -1,
+                                       &st, &rows, &models);
+        double *const product_stats[abub::SurveyProducts] = {shift_stats, field_stats, light_stats, focus_stats};
+        for (int p = 0; p < abub::SurveyProducts; ++p)
+            if (product_stats[p]) {
+                const abub::ProductStats &ps = st.product[p];
+                const double v[5] = {(double)ps.framesKernel, (double)ps.framesHost, (double)ps.launches, ps.leg_s, ps.host_s};
+                std::memcpy(product_stats[p], v, sizeof v);
+            }
         if (plane_stats) {
             const double v[5] = {(double)st.planeRowsKernel, (double)st.planeRowsHost, st.activity_s, st.planes_copy_s, st.planes_write_s};
             std::memcpy(plane_stats, v, sizeof v);
@@ -509,79 +499,79 @@ static int runSurvey(void *r, const char *path, int ncams, int nthreads, int dev
 }
 int abh_run_survey(void *r, const char *path, int ncams, int nthreads, double *stats, char *report, int report_cap)
 {
-    return runSurvey(r, path, ncams, nthreads, -1, false, stats, report, report_cap);
+    return runSurvey(r, surveyRequest(path), ncams, nthreads, -1, false, report, report_cap, stats);
 }
 int abh_run_survey_dev(void *r, const char *path, int ncams, int nthreads, int device, double *stats, char *report, int report_cap)
 {
-    return runSurvey(r, path, ncams, nthreads, device, true, stats, report, report_cap);
+    return runSurvey(r, surveyRequest(path), ncams, nthreads, device, true, report, report_cap, stats);
 }
 int abh_run_survey_planes(void *r, const char *path, const char *planes_dir, int ncams, int nthreads, double *stats, double *plane_stats,
                           char *report, int report_cap)
 {
-    return runSurvey(r, path, ncams, nthreads, -1, false, stats, report, report_cap, planes_dir, plane_stats);
+    return runSurvey(r, surveyRequest(path, planes_dir), ncams, nthreads, -1, false, report, report_cap, stats, plane_stats);
 }
 int abh_run_survey_planes_dev(void *r, const char *path, const char *planes_dir, int ncams, int nthreads, int device, double *stats,
                               double *plane_stats, char *report, int report_cap)
 {
-    return runSurvey(r, path, ncams, nthreads, device, true, stats, report, report_cap, planes_dir, plane_stats);
+    return runSurvey(r, surveyRequest(path, planes_dir), ncams, nthreads, device, true, report, report_cap, stats, plane_stats);
 }
 int abh_run_survey_shift(void *r, const char *path, const char *planes_dir, const char *shift_path, int shift_radius, int ncams,
                          int nthreads, double *stats, double *plane_stats, double *shift_stats, char *report, int report_cap)
 {
-    return runSurvey(r, path, ncams, nthreads, -1, false, stats, report, report_cap, planes_dir, plane_stats, shift_path, shift_radius,
-                     shift_stats);
+    return runSurvey(r, surveyRequest(path, planes_dir, shift_path, shift_radius), ncams, nthreads, -1, false, report, report_cap, stats,
+                     plane_stats, shift_stats);
 }
 int abh_run_survey_shift_dev(void *r, const char *path, const char *planes_dir, const char *shift_path, int shift_radius, int ncams,
                              int nthreads, int device, double *stats, double *plane_stats, double *shift_stats, char *report,
                              int report_cap)
 {
-    return runSurvey(r, path, ncams, nthreads, device, true, stats, report, report_cap, planes_dir, plane_stats, shift_path, shift_radius,
-                     shift_stats);
+    return runSurvey(r, surveyRequest(path, planes_dir, shift_path, shift_radius), ncams, nthreads, device, true, report, report_cap, stats,
+                     plane_stats, shift_stats);
 }
 int abh_run_survey_field(void *r, const char *path, const char *planes_dir, const char *shift_path, int shift_radius, const char *field_dir,
                          int field_radius, int ncams, int nthreads, double *stats, double *plane_stats, double *shift_stats,
                          double *field_stats, char *report, int report_cap)
 {
-    return runSurvey(r, path, ncams, nthreads, -1, false, stats, report, report_cap, planes_dir, plane_stats, shift_path, shift_radius,
-                     shift_stats, field_dir, field_radius, field_stats);
+    return runSurvey(r, surveyRequest(path, planes_dir, shift_path, shift_radius, field_dir, field_radius), ncams, nthreads, -1, false,
+                     report, report_cap, stats, plane_stats, shift_stats, field_stats);
 }
 int abh_run_survey_field_dev(void *r, const char *path, const char *planes_dir, const char *shift_path, int shift_radius,
                              const char *field_dir, int field_radius, int ncams, int nthreads, int device, double *stats,
                              double *plane_stats, double *shift_stats, double *field_stats, char *report, int report_cap)
 {
-    return runSurvey(r, path, ncams, nthreads, device, true, stats, report, report_cap, planes_dir, plane_stats, shift_path, shift_radius,
-                     shift_stats, field_dir, field_radius, field_stats);
+    return runSurvey(r, surveyRequest(path, planes_dir, shift_path, shift_radius, field_dir, field_radius), ncams, nthreads, device, true,
+                     report, report_cap, stats, plane_stats, shift_stats, field_stats);
 }
 int abh_run_survey_light(void *r, const char *path, const char *planes_dir, const char *shift_path, int shift_radius, const char *field_dir,
                          int field_radius, const char *light_dir, int ncams, int nthreads, double *stats, double *plane_stats,
                          double *shift_stats, double *field_stats, double *light_stats, char *report, int report_cap)
 {
-    return runSurvey(r, path, ncams, nthreads, -1, false, stats, report, report_cap, planes_dir, plane_stats, shift_path, shift_radius,
-                     shift_stats, field_dir, field_radius, field_stats, light_dir, light_stats);
+    return runSurvey(r, surveyRequest(path, planes_dir, shift_path, shift_radius, field_dir, field_radius, light_dir), ncams, nthreads, -1,
+                     false, report, report_cap, stats, plane_stats, shift_stats, field_stats, light_stats);
 }
 int abh_run_survey_light_dev(void *r, const char *path, const char *planes_dir, const char *shift_path, int shift_radius,
                              const char *field_dir, int field_radius, const char *light_dir, int ncams, int nthreads, int device,
                              double *stats, double *plane_stats, double *shift_stats, double *field_stats, double *light_stats,
                              char *report, int report_cap)
 {
-    return runSurvey(r, path, ncams, nthreads, device, true, stats, report, report_cap, planes_dir, plane_stats, shift_path, shift_radius,
-                     shift_stats, field_dir, field_radius, field_stats, light_dir, light_stats);
+    return runSurvey(r, surveyRequest(path, planes_dir, shift_path, shift_radius, field_dir, field_radius, light_dir), ncams, nthreads,
+                     device, true, report, report_cap, stats, plane_stats, shift_stats, field_stats, light_stats);
 }
 int abh_run_survey_focus(void *r, const char *path, const char *planes_dir, const char *shift_path, int shift_radius, const char *field_dir,
                          int field_radius, const char *light_dir, const char *focus_dir, int ncams, int nthreads, double *stats,
                          double *plane_stats, double *shift_stats, double *field_stats, double *light_stats, double *focus_stats,
                          char *report, int report_cap)
 {
-    return runSurvey(r, path, ncams, nthreads, -1, false, stats, report, report_cap, planes_dir, plane_stats, shift_path, shift_radius,
-                     shift_stats, field_dir, field_radius, field_stats, light_dir, light_stats, focus_dir, focus_stats);
+    return runSurvey(r, surveyRequest(path, planes_dir, shift_path, shift_radius, field_dir, field_radius, light_dir, focus_dir), ncams,
+                     nthreads, -1, false, report, report_cap, stats, plane_stats, shift_stats, field_stats, light_stats, focus_stats);
 }
 int abh_run_survey_focus_dev(void *r, const char *path, const char *planes_dir, const char *shift_path, int shift_radius,
                              const char *field_dir, int field_radius, const char *light_dir, const char *focus_dir, int ncams,
                              int nthreads, int device, double *stats, double *plane_stats, double *shift_stats, double *field_stats,
                              double *light_stats, double *focus_stats, char *report, int report_cap)
 {
-    return runSurvey(r, path, ncams, nthreads, device, true, stats, report, report_cap, planes_dir, plane_stats, shift_path, shift_radius,
-                     shift_stats, field_dir, field_radius, field_stats, light_dir, light_stats, focus_dir, focus_stats);
+    return runSurvey(r, surveyRequest(path, planes_dir, shift_path, shift_radius, field_dir, field_radius, light_dir, focus_dir), ncams,
+                     nthreads, device, true, report, report_cap, stats, plane_stats, shift_stats, field_stats, light_stats, focus_stats);
 }
 // the whole report of the last abh_run_survey[_dev] on the run (valid until the next query on it)
 const char *abh_run_survey_report(void *r)

@@ -307,23 +307,26 @@ struct FocusFrame {
 };
 FocusFrame focusFrame(const int32_t *rec, const int64_t *model, size_t cells);
 
+// What a survey makes of every ok row of a camera with a model, beyond its record: the index of the row's state, of the
+// product's counters and of the host threads' clocks
+enum SurveyProduct { SurveyShiftProduct = 0, SurveyFieldProduct = 1, SurveyLightProduct = 2, SurveyFocusProduct = 3, SurveyProducts = 4 };
 // One row of a survey: a frame the run lists, or one it should list (missing)
 struct SurveyRow {
     enum State { Ok = 0, Undecodable = 1, Missing = 2, OtherSize = 3 };
+    enum Made { None = 0, Host = 1, Kernel = 2 }; // who made a product of the row: nobody, a host thread, the product's kernel
     size_t ev = 0;           // index into the run's sorted event list
     std::string event, name;
     int cam = 0, frame = 0;  // frame: its place in its (event, camera) stack, missing frames counted
     int state = Ok, w = 0, h = 0; // w, h: of Ok and OtherSize rows
     FrameStats s;            // Ok: all of it, as far as its flags say; OtherSize: the raw columns
     bool onKernel = false;
-    bool hasShift = false, shiftOnKernel = false; // with a shift file: an ok row of a camera with a model has its surface's answer
-    ShiftBest shift;
-    bool hasField = false, fieldOnKernel = false; // with a field directory: the same rows have their cells' records
-    std::vector<int32_t> field;                   // [ncy][ncx][5]
-    bool hasLight = false, lightOnKernel = false; // with a light directory: the same rows have their cells' light records
-    std::vector<uint32_t> light;                  // [ncy][ncx][6]
-    bool hasFocus = false, focusOnKernel = false; // with a focus directory: the same rows have their cells' focus records
-    std::vector<int32_t> focus;                   // [ncy][ncx][5]
+    uint8_t made = 0;        // two bits per SurveyProduct: an ok row of a camera with a model has every product that was asked for
+    Made has(SurveyProduct p) const { return (Made)(made >> (2 * p) & 3); }
+    void set(SurveyProduct p, Made m) { made = (uint8_t)((made & ~(3 << (2 * p))) | (m << (2 * p))); }
+    ShiftBest shift;             // with a shift file: its surface's answer
+    std::vector<int32_t> field;  // with a field directory: its cells' records, [ncy][ncx][5]
+    std::vector<uint32_t> light; // with a light directory: its cells' light records, [ncy][ncx][6]
+    std::vector<int32_t> focus;  // with a focus directory: its cells' focus records, [ncy][ncx][5]
     const char *stateName() const; // "ok", "undecodable", "missing", "other_size"
 };
 // What the report says of one camera's model
@@ -334,6 +337,15 @@ struct SurveyModel {
     double muMean = 0;
     std::vector<uint32_t> light; // with a light directory, of a trained camera: lightModelHost's [ncy][ncx][3]
     std::vector<int64_t> focus;  // with a focus directory, of a trained camera: focusModelHost's [ncy][ncx][3]
+};
+// The counters of one product: the rows whose product its kernel made (abub_frame_shift_dev, abub_frame_shift_cells_dev,
+// abub_frame_light_cells_dev, abub_frame_focus_cells_dev) and those a host thread made from the definition, the kernel's
+// calls, the seconds of the device route's leg (launches, copy back) and the seconds the host threads spent in the
+// definition, summed over the threads
+struct ProductStats {
+    long long framesKernel = 0, framesHost = 0;
+    int launches = 0;
+    double leg_s = 0, host_s = 0;
 };
 struct SurveyStats {
     int events = 0;
@@ -351,75 +363,37 @@ struct SurveyStats {
     // seconds of the activity launches, of the planes' copy back and of writing the files
     long long planeRowsKernel = 0, planeRowsHost = 0;
     double activity_s = 0, planes_copy_s = 0, planes_write_s = 0;
-    // With a shift file: the rows whose surface abub_frame_shift_dev made and those frameShiftHost made, the kernel's calls,
-    // the seconds of the device route's shift leg (upload of the jobs, launches, copy back) and the seconds the host threads
-    // spent in frameShiftHost, summed over the threads
-    long long shiftFramesKernel = 0, shiftFramesHost = 0;
-    int shiftLaunches = 0;
-    double shift_s = 0, shiftHost_s = 0;
-    // With a field directory: the same five for abub_frame_shift_cells_dev and fieldCellsHost
-    long long fieldFramesKernel = 0, fieldFramesHost = 0;
-    int fieldLaunches = 0;
-    double field_s = 0, fieldHost_s = 0;
-    // With a light directory: the same five for abub_frame_light_cells_dev and lightCellsHost
-    long long lightFramesKernel = 0, lightFramesHost = 0;
-    int lightLaunches = 0;
-    double light_s = 0, lightHost_s = 0;
-    // With a focus directory: the same five for abub_frame_focus_cells_dev and focusCellsHost
-    long long focusFramesKernel = 0, focusFramesHost = 0;
-    int focusLaunches = 0;
-    double focus_s = 0, focusHost_s = 0;
+    ProductStats product[SurveyProducts]; // of the products that were asked for
 };
-// Where a survey writes its per-pixel activity planes (abub3hs --survey-planes; DESIGN section 3, "Surveying a run per
-// pixel"): the directory `dir` (the CLI's DIR/<run_ID>; empty: no planes) gets cam<c>_activity.npy (u32 [6, H, W]) for
-// every camera with a listed row, cam<c>_moved.png for those with a model, and activity.txt.  srcRunDir (empty: an
-// archive) is the directory the run is read from; it is refused as `dir`.
-struct SurveyPlanes {
-    std::string dir, srcRunDir;
+// What a survey writes and where (abub3hs --survey and its --survey-* flags); an empty path: that product is not made.
+// srcRunDir (empty: an archive) is the directory the run is read from; it is refused as any of the directories below: a run
+// directory is not the place for what was derived from it.
+struct SurveyRequest {
+    std::string reportPath, srcRunDir;
+    // DESIGN section 3, "Surveying a run per pixel": planesDir (the CLI's DIR/<run_ID>) gets cam<c>_activity.npy (u32
+    // [6, H, W]) for every camera with a listed row, cam<c>_moved.png for those with a model, and activity.txt
+    std::string planesDir;
+    // "Surveying a run for movement": per ok row of a camera with a model the best displacement of the frame against mu within
+    // shiftRadius.  A run narrower or lower than 2 shiftRadius + 1 is refused before its frames are measured
+    std::string shiftPath;
+    int shiftRadius = 4;
+    // The per-cell products, each into its directory (the CLI's DIR/<run_ID>), for every camera with a model, of its rows
+    // that have the product, in survey order.  All three share one grid: abub_frame_cells_grid at cellRadius; a run narrower or
+    // lower than 128 + 2 cellRadius has no whole cell and is refused before its frames are measured.
+    // "... for local movement": cam<c>_field.npy (i32 [N_c, ncy, ncx, 5]) and field.txt;
+    // "... for lighting changes": cam<c>_light.npy (i32 [N_c, ncy, ncx, 6]), cam<c>_light_model.npy (i32 [ncy, ncx, 3]), light.txt;
+    // "... for lost focus": cam<c>_focus.npy (i32 [N_c, ncy, ncx, 5]), cam<c>_focus_model.npy (i64 [ncy, ncx, 3]), focus.txt
+    std::string fieldDir;
+    int cellRadius = 4;
+    std::string lightDir, focusDir;
 };
-// Where a survey writes its shift file (abub3hs --survey-shift; DESIGN section 3, "Surveying a run for movement"): per ok
-// row of a camera with a model the best displacement of the frame against mu within `radius` (path empty: no shift search).
-// A run narrower or lower than 2 radius + 1 is refused before its frames are measured.
-struct SurveyShift {
-    std::string path;
-    int radius = 4;
-};
-// Where a survey writes its per-cell shift field (abub3hs --survey-field; DESIGN section 3, "Surveying a run for local
-// movement"): the directory `dir` (the CLI's DIR/<run_ID>; empty: no field) gets cam<c>_field.npy (i32 [N_c, ncy, ncx, 5]:
-// the records of camera c's rows that have a surface, in survey order) for every camera with a model, and field.txt.  A run
-// narrower or lower than 128 + 2 radius has no whole cell and is refused before its frames are measured.
-struct SurveyField {
-    std::string dir, srcRunDir;
-    int radius = 4;
-};
-// Where a survey writes its per-cell light records (abub3hs --survey-light; DESIGN section 3, "Surveying a run for lighting
-// changes"): the directory `dir` (the CLI's DIR/<run_ID>; empty: none) gets cam<c>_light.npy (i32 [N_c, ncy, ncx, 6]: the
-// records of camera c's rows that have one, in survey order) and cam<c>_light_model.npy (i32 [ncy, ncx, 3]) for every camera
-// with a model, and light.txt.  The cells are the field's: abub_frame_cells_grid at SurveyField::radius, whether or not the
-// field is written; a run without a whole cell is refused before its frames are measured.
-struct SurveyLight {
-    std::string dir, srcRunDir;
-};
-// light.txt's text: "# abub3hs light 1", the grid's line, the table's header and one tab-separated row per survey row, one
-// `light cam` line per camera, the `changed` lines of every camera with a model, the `run` line.  Both routes write it
-// through this one function; W, H: the run's size; models[c].light: the camera's model record.
-std::string LightReport(int radius, int W, int H, const std::vector<SurveyModel> &models, const std::vector<SurveyRow> &rows);
-// Where a survey writes its per-cell focus records (abub3hs --survey-focus; DESIGN section 3, "Surveying a run for lost
-// focus"): the directory `dir` (the CLI's DIR/<run_ID>; empty: none) gets cam<c>_focus.npy (i32 [N_c, ncy, ncx, 5]: the
-// records of camera c's rows that have one, in survey order) and cam<c>_focus_model.npy (i64 [ncy, ncx, 3]) for every camera
-// with a model, and focus.txt.  The cells are the field's: abub_frame_cells_grid at SurveyField::radius, whether or not the
-// field or the light is written; a run without a whole cell is refused before its frames are measured.
-struct SurveyFocus {
-    std::string dir, srcRunDir;
-};
-// focus.txt's text: "# abub3hs focus 1", the grid's line, the table's header and one tab-separated row per survey row, one
-// `focus cam` line per camera, the `changed` lines of every camera with a model, the `run` line.  Both routes write it
-// through this one function; W, H: the run's size; models[c].focus: the camera's model record.
-std::string FocusReport(int radius, int W, int H, const std::vector<SurveyModel> &models, const std::vector<SurveyRow> &rows);
-// field.txt's text: "# abub3hs field 1", the grid's line, the table's header and one tab-separated row per survey row, one
-// `field cam` line per camera, the `moved` lines of every camera with a model, the `run` line.  Both routes write it through
-// this one function; W, H: the run's size.
+// The texts of field.txt, light.txt and focus.txt: "# abub3hs <tag> 1", the grid's line, the table's header and one
+// tab-separated row per survey row, one `<tag> cam` line per camera, the `moved` (field) or `changed` lines of every camera
+// with a model, the `run` line.  Both routes write them through these functions; W, H: the run's size; models[c].light and
+// models[c].focus: the camera's model record.
 std::string FieldReport(int radius, int W, int H, const std::vector<SurveyModel> &models, const std::vector<SurveyRow> &rows);
+std::string LightReport(int radius, int W, int H, const std::vector<SurveyModel> &models, const std::vector<SurveyRow> &rows);
+std::string FocusReport(int radius, int W, int H, const std::vector<SurveyModel> &models, const std::vector<SurveyRow> &rows);
 // The shift file's text: "# abub3hs shift 1", `radius R`, the table's header and one tab-separated row per survey row, one
 // `shift cam` line per camera, the `run` line.  Both routes write it through this one function.
 std::string ShiftReport(int radius, const std::vector<SurveyModel> &models, const std::vector<SurveyRow> &rows);
@@ -427,43 +401,26 @@ std::string ShiftReport(int radius, const std::vector<SurveyModel> &models, cons
 // header and one tab-separated row per frame, the `run` line.  Both routes write it through this one function.
 std::string SurveyReport(const std::vector<SurveyModel> &models, const std::vector<SurveyRow> &rows);
 // abub3hs --survey FILE: every frame that `parser` lists for cameras 0 .. numCams-1 measured, no analysis: one row per
-// frame in event, camera and frame order, cv::imdecode and frameStatsHost on `nthreads` threads.  A frame number (read
-// from the name through imageFormat) that some stack of the run has and a stack with frames lacks is a `missing` row of
-// that stack.  Frame i of a stack is measured against frame max(i - 2, 0) of it (the trigger search's pairing) and against
-// the model of its camera: trainers[cam] where it is there, trained (StatusCode 0) and of the run's size (that of the first
-// frame that decodes); without it the model columns are invalid, and the moved columns also where the reference frame is
-// not ok.  The report goes to reportPath (empty: it is not written).  No GPU.  Returns 0, or 1 if any frame is not ok;
-// throws where the report cannot be written.
-// With planes.dir the rows are also summed per pixel and camera and the planes' files are written (both routes: the same bytes).
-// With shift.path every ok row of a camera with a model is also searched for its displacement against mu (frameShiftHost
-// here; on the device route abub_frame_shift_dev for the rows in place in the slab, one call per batch behind the statistics
-// launch) and the shift file is written (both routes: the same bytes).  The report and the planes do not change.
-// With field.dir the same rows also get their per-cell records (fieldCellsHost here; on the device route
-// abub_frame_shift_cells_dev behind the statistics and the shift launch) and the field's files are written (both routes: the
-// same bytes).  The report, the planes and the shift file do not change.
-// With light.dir the same rows also get their per-cell light records (lightCellsHost here; on the device route
-// abub_frame_light_cells_dev behind the launches above) and the light's files are written (both routes: the same bytes).
-// Nothing else changes.
-// With focus.dir the same rows also get their per-cell focus records (focusCellsHost here; on the device route
-// abub_frame_focus_cells_dev behind the launches above) and the focus files are written (both routes: the same bytes).
-// Nothing else changes.
+// frame in event, camera and frame order.  A frame number (read from the name through imageFormat) that some stack of the
+// run has and a stack with frames lacks is a `missing` row of that stack.  Frame i of a stack is measured against frame
+// max(i - 2, 0) of it (the trigger search's pairing) and against the model of its camera: trainers[cam] where it is there,
+// trained (StatusCode 0) and of the run's size (that of the first frame that decodes); without it the model columns are
+// invalid, and the moved columns also where the reference frame is not ok.  The report goes to request.reportPath (empty: it
+// is not written), every other product of `request` to its place; a product changes nothing in the others.  Returns 0, or 1
+// if any frame is not ok; throws where a file cannot be written.
+// device < 0, the host route: cv::imdecode and the definitions (frameStatsHost, activityAddHost, frameShiftHost,
+// fieldCellsHost, lightCellsHost, focusCellsHost) on `nthreads` threads.  No GPU.
+// device >= 0 (--survey-gpu): the same rows and the same files, byte for byte.  The frames are read through the FileBatch
+// protocol (framefiles.hpp) in batches of at most 4 frames per CU (ABUB_SURVEY_BATCH=n: of n), decoded into the batch's
+// slab, and measured by one abub_frame_stats_dev launch per batch, with the products' kernels behind it.  A batch that
+// begins inside a stack reads again the at most two frames of the batch before that its first jobs refer to (they take
+// slots of their own: the number of batches is ceil(rows / batch size) exactly).  A frame that is not in place in the slab
+// (no decoder reads it, another size) gets its row from the host route's per-frame function.  A run whose width the
+// decoders do not take, or without a frame that decodes, goes the host route whole.  Throws, before anything else, when
+// there is no such device.
 int SurveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCams, const std::string &imageFormat,
-              const std::string &reportPath, int nthreads, SurveyStats *stats, std::vector<SurveyRow> *rows,
-              std::vector<SurveyModel> *models = nullptr, const SurveyPlanes &planes = SurveyPlanes(),
-              const SurveyShift &shift = SurveyShift(), const SurveyField &field = SurveyField(),
-              const SurveyLight &light = SurveyLight(), const SurveyFocus &focus = SurveyFocus());
-// abub3hs --survey FILE --survey-gpu: the same rows and the same report, byte for byte.  The frames are read through the
-// FileBatch protocol (framefiles.hpp) in batches of at most 4 frames per CU (ABUB_SURVEY_BATCH=n: of n), decoded into the
-// batch's slab, and measured by one abub_frame_stats_dev launch per batch.  A batch that begins inside a stack reads again
-// the at most two frames of the batch before that its first jobs refer to (they take slots of their own: the number of
-// batches is ceil(rows / batch size) exactly).  A frame that is not in place in the slab (no decoder reads it, another
-// size) gets its row from the host route's per-frame function.  A run whose width the decoders do not take, or without a
-// frame that decodes, goes the host route whole.  Throws, before anything else, when there is no such device.
-int SurveyRunDevice(Parser *parser, const std::vector<Trainer *> &trainers, int numCams, const std::string &imageFormat,
-                    const std::string &reportPath, int nthreads, int device, SurveyStats *stats, std::vector<SurveyRow> *rows,
-                    std::vector<SurveyModel> *models = nullptr, const SurveyPlanes &planes = SurveyPlanes(),
-                    const SurveyShift &shift = SurveyShift(), const SurveyField &field = SurveyField(),
-              const SurveyLight &light = SurveyLight(), const SurveyFocus &focus = SurveyFocus());
+              const SurveyRequest &request, int nthreads, int device, SurveyStats *stats, std::vector<SurveyRow> *rows = nullptr,
+              std::vector<SurveyModel> *models = nullptr);
 
 // A run listed and trained, ready for detect; rc = -5 (the run cannot be read) or -7 (a camera did not train)
 struct PreparedRun {

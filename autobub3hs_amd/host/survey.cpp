@@ -1,30 +1,20 @@
 // survey.cpp -- a run measured frame by frame ("Surveying a run"): abub3hs --survey.  No analysis.
-// frameStatsHost is the definition of the per-frame record, plain byte loops.  SurveyRun is host only: per frame
-// cv::imdecode of the frame and of its reference frame, then frameStatsHost.  SurveyRunDevice (--survey-gpu) reads the
-// frames of the run's size through the FileBatch protocol into a resident slab and fills the same records with one
-// abub_frame_stats_dev launch per batch; what is not in place in the slab gets its row from the host route's per-frame
-// function, of which there is one copy.  Both routes fill one row per frame and share everything behind that: the list of
-// the rows, the models, the counters, the report's text, the exit status.
-// With a planes directory (--survey-planes; DESIGN section 3, "Surveying a run per pixel") the ok rows are also summed per
-// pixel and camera: activityAddHost is the definition, a host thread adds its row into the camera's one set of planes with
-// relaxed atomic adds, the device route adds the rows in place in the slab with abub_pixel_activity_dev and keeps its planes
-// on the device until the end; the result is their sum, and one writer puts the files on disk for both routes.
-// With a shift file (--survey-shift; DESIGN section 3, "Surveying a run for movement") the ok rows of a camera with a model
-// are also searched for their displacement against mu: frameShiftHost is the definition of the SAD surface, the device route
-// gets the surfaces of the rows in place in the slab from abub_frame_shift_dev, shiftBest reads every surface on the host,
-// and one writer (ShiftReport) makes the file for both routes.
-// With a field directory (--survey-field; DESIGN section 3, "Surveying a run for local movement") the same rows are also
-// searched per cell of 128 x 128 pixels: fieldCellsHost is the definition of the cells' surfaces, the device route gets them
-// from abub_frame_shift_cells_dev, fieldCell reads every surface on the host into a record of five words, and one writer
-// (writeField, with FieldReport for the text) makes the files for both routes.
-// With a light directory (--survey-light; DESIGN section 3, "Surveying a run for lighting changes") the same rows also get
-// six sums per cell of the field's grid: lightCellsHost is the definition, the device route gets the records from
-// abub_frame_light_cells_dev, lightModelHost sums the model once per camera on the host, lightCell and lightFrame say what
-// the sums mean, and one writer (writeLight, with LightReport for the text) makes the files for both routes.
-// With a focus directory (--survey-focus; DESIGN section 3, "Surveying a run for lost focus") the same rows also get five
-// sums of gradient products per cell of the same grid: focusCellsHost is the definition, the device route gets the records
-// from abub_frame_focus_cells_dev, focusModelHost sums the model once per camera on the host, focusCell and focusFrame say
-// what the sums mean, and one writer (writeFocus, with FocusReport for the text) makes the files for both routes.
+// One path: SurveyRun plans the run (one row per frame, the models, one grid of cells), fills every row on one of two
+// routes, and writes what the request asks for through one writer per kind of file, the same for both routes.  The host
+// route (device < 0) is the definition: per frame cv::imdecode of the frame and of its reference frame, then the plain loops
+// of this file.  The device route (--survey-gpu) reads the frames of the run's size through the FileBatch protocol into a
+// resident slab and runs one launch per batch and product; what is not in place in the slab gets its row from the host
+// route's per-frame function, of which there is one copy.
+// What each product adds to that path is its definition, its kernel entry and what its numbers mean:
+//   the record      frameStatsHost     abub_frame_stats_dev          SurveyReport
+//   planes          activityAddHost    abub_pixel_activity_dev       writePlanes; summed per pixel and camera, not kept per row
+//   shift           frameShiftHost     abub_frame_shift_dev          shiftBest reads a surface; ShiftReport
+//   field           fieldCellsHost     abub_frame_shift_cells_dev    fieldCell reads a cell's surface; FieldReport
+//   light           lightCellsHost     abub_frame_light_cells_dev    lightModelHost once per camera; lightCell, lightFrame; LightReport
+//   focus           focusCellsHost     abub_frame_focus_cells_dev    focusModelHost once per camera; focusCell, focusFrame; FocusReport
+// Shift, field, light and focus are made of the ok rows of a camera with a model and share the rest: one two-bit state per
+// row, one ProductStats, one timing wrapper on the host, one device leg over one job list (deviceFrames), and for the three
+// per-cell products one grid, one report skeleton (cellReport) and one writer (writeCells).
 #include <algorithm>
 #include <cinttypes>
 #include <cmath>
@@ -32,6 +22,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <atomic>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -288,89 +279,6 @@ LightFrame lightFrame(const uint32_t *rec, const uint32_t *model, size_t cells)
     return f;
 }
 
-std::string LightReport(int radius, int W, int H, const std::vector<SurveyModel> &models, const std::vector<SurveyRow> &rows)
-{
-    int ncx = 0, ncy = 0, x0 = 0, y0 = 0;
-    if (W > 0 && H > 0)
-        abub_frame_cells_grid(W, H, radius, &ncx, &ncy, &x0, &y0);
-    const size_t cells = (size_t)ncx * ncy;
-    std::string text = "# abub3hs light 1\n";
-    char buf[512];
-    snprintf(buf, sizeof buf, "radius %d cell %d grid %d %d origin %d %d\n", radius, (int)ABUB_FIELD_CELL, ncx, ncy, x0, y0);
-    text += buf;
-    text += "event\tcam\tframe\tname\tstate\tindex\trated\tclipped\tchanged\tup\tdown\tlevel_milli\tratio_min\tratio_max\tgain_milli\toffset_milli\tkind\n";
-    static const char *const kinds[] = {"blind", "steady", "level", "uneven"};
-    struct Cam {
-        long long frames = 0, kind[4] = {0, 0, 0, 0};
-        const std::string *first = nullptr;
-        std::vector<long long> changed; // per cell: the frames in which it was rated and changed
-    };
-    std::vector<Cam> cams(models.size());
-    for (const SurveyRow &r : rows) {
-        snprintf(buf, sizeof buf, "%s\t%d\t%d\t%s\t%s", r.event.c_str(), r.cam, r.frame, r.name.c_str(), r.stateName());
-        text += buf;
-        const std::vector<uint32_t> *model = (size_t)r.cam < models.size() ? &models[(size_t)r.cam].light : nullptr;
-        if (r.state != SurveyRow::Ok || !r.hasLight || r.light.size() != cells * LightRecordWords || !model ||
-            model->size() != cells * LightModelWords) {
-            text += "\t-\t-\t-\t-\t-\t-\t-\t-\t-\t-\t-\t-\n";
-            continue;
-        }
-        Cam &c = cams[(size_t)r.cam];
-        c.changed.resize(cells, 0);
-        const LightFrame f = lightFrame(r.light.data(), model->data(), cells);
-        for (size_t k = 0; k < cells; ++k) {
-            const LightCell lc = lightCell(r.light.data() + k * LightRecordWords, model->data() + k * LightModelWords);
-            c.changed[k] += lc.rated && lc.changed;
-        }
-        snprintf(buf, sizeof buf, "\t%lld\t%d\t%d\t%d\t%d\t%d", c.frames, f.rated, f.clipped, f.changed, f.up, f.down);
-        text += buf;
-        if (f.kind == LightFrame::Blind)
-            snprintf(buf, sizeof buf, "\t-\t-\t-\t-\t-");
-        else if (f.hasGain)
-            snprintf(buf, sizeof buf, "\t%lld\t%lld\t%lld\t%lld\t%lld", f.levelMilli, f.ratioMin, f.ratioMax, f.gainMilli, f.offsetMilli);
-        else
-            snprintf(buf, sizeof buf, "\t%lld\t%lld\t%lld\t-\t-", f.levelMilli, f.ratioMin, f.ratioMax);
-        text += buf;
-        text += std::string("\t") + kinds[f.kind] + "\n";
-        ++c.frames;
-        ++c.kind[f.kind];
-        if (f.changed && !c.first)
-            c.first = &r.event;
-    }
-    long long frames = 0, kind[4] = {0, 0, 0, 0};
-    for (size_t c = 0; c < cams.size(); ++c) {
-        if (!models[c].trained) {
-            snprintf(buf, sizeof buf, "light cam %zu none\n", c);
-            text += buf;
-            continue;
-        }
-        const Cam &k = cams[c];
-        snprintf(buf, sizeof buf, "light cam %zu frames %lld blind %lld steady %lld level %lld uneven %lld first_changed_event %s\n", c, k.frames,
-                 k.kind[0], k.kind[1], k.kind[2], k.kind[3], k.first ? k.first->c_str() : "-");
-        text += buf;
-        frames += k.frames;
-        for (int q = 0; q < 4; ++q)
-            kind[q] += k.kind[q];
-    }
-    for (size_t c = 0; c < cams.size(); ++c) {
-        if (!models[c].trained)
-            continue;
-        for (int y = 0; y < ncy; ++y) {
-            snprintf(buf, sizeof buf, "changed cam %zu y %d", c, y);
-            text += buf;
-            for (int x = 0; x < ncx; ++x) {
-                const size_t k = (size_t)y * ncx + x;
-                snprintf(buf, sizeof buf, " %lld", k < cams[c].changed.size() ? cams[c].changed[k] : 0ll);
-                text += buf;
-            }
-            text += "\n";
-        }
-    }
-    snprintf(buf, sizeof buf, "run frames %lld blind %lld steady %lld level %lld uneven %lld\n", frames, kind[0], kind[1], kind[2], kind[3]);
-    text += buf;
-    return text;
-}
-
 void focusCellsHost(const unsigned char *p, const unsigned char *m, int W, int H, int x0, int y0, int ncx, int ncy, int32_t *rec)
 {
     (void)H;
@@ -480,115 +388,125 @@ FocusFrame focusFrame(const int32_t *rec, const int64_t *model, size_t cells)
     return f;
 }
 
-std::string FocusReport(int radius, int W, int H, const std::vector<SurveyModel> &models, const std::vector<SurveyRow> &rows)
+// the columns every table of a survey begins with
+static void rowPrefix(std::string &text, const SurveyRow &r)
+{
+    char buf[512];
+    snprintf(buf, sizeof buf, "%s\t%d\t%d\t%s\t%s", r.event.c_str(), r.cam, r.frame, r.name.c_str(), r.stateName());
+    text += buf;
+}
+
+namespace {
+
+// What differs between field.txt, light.txt and focus.txt; cellReport is the rest
+struct CellReport {
+    const char *tag;                 // of "# abub3hs <tag> 1" and of the `<tag> cam` lines
+    const char *columns;             // the table's column names between `index` and `kind`; a row without a record has a dash in each
+    std::vector<const char *> kinds; // the kinds' names, blind first
+    const char *mapWord;             // `moved` or `changed`: what the per-cell map's lines count the frames of
+    const char *firstLabel;          // of the `<tag> cam` lines: first_..._event
+    // One row: -1 if it has no record.  Else its columns are appended to `cols`, `first` says whether the row counts as its
+    // camera's first event, hit[k] is raised for every cell that counts in the map; returns the row's kind
+    std::function<int(const SurveyRow &r, size_t cells, std::string &cols, bool &first, std::vector<long long> &hit)> row;
+};
+
+std::string cellReport(const CellReport &d, int radius, int W, int H, const std::vector<SurveyModel> &models,
+                       const std::vector<SurveyRow> &rows)
 {
     int ncx = 0, ncy = 0, x0 = 0, y0 = 0;
     if (W > 0 && H > 0)
         abub_frame_cells_grid(W, H, radius, &ncx, &ncy, &x0, &y0);
-    const size_t cells = (size_t)ncx * ncy;
-    std::string text = "# abub3hs focus 1\n";
+    const size_t cells = (size_t)ncx * ncy, K = d.kinds.size();
+    std::string text = std::string("# abub3hs ") + d.tag + " 1\n";
     char buf[512];
     snprintf(buf, sizeof buf, "radius %d cell %d grid %d %d origin %d %d\n", radius, (int)ABUB_FIELD_CELL, ncx, ncy, x0, y0);
     text += buf;
-    text += "event\tcam\tframe\tname\tstate\tindex\trated\tclipped\tchanged\tsofter\tharder\tkeep_milli\tkeep_min\tkeep_max\tenergy_milli\tkind\n";
-    static const char *const kinds[] = {"blind", "steady", "soft", "uneven"};
+    text += std::string("event\tcam\tframe\tname\tstate\tindex\t") + d.columns + "\tkind\n";
+    std::string dashes = "\t-\t-\t-"; // index, the first column, kind; one more per further column
+    for (const char *c = d.columns; *c; ++c)
+        if (*c == '\t')
+            dashes += "\t-";
     struct Cam {
-        long long frames = 0, kind[4] = {0, 0, 0, 0};
+        long long frames = 0;
+        std::vector<long long> kind;
         const std::string *first = nullptr;
-        std::vector<long long> changed; // per cell: the frames in which it was rated and changed
+        std::vector<long long> perCell; // per cell: the frames in which it counted in the map
     };
     std::vector<Cam> cams(models.size());
+    std::vector<long long> hit;
     for (const SurveyRow &r : rows) {
-        snprintf(buf, sizeof buf, "%s\t%d\t%d\t%s\t%s", r.event.c_str(), r.cam, r.frame, r.name.c_str(), r.stateName());
-        text += buf;
-        const std::vector<int64_t> *model = (size_t)r.cam < models.size() ? &models[(size_t)r.cam].focus : nullptr;
-        if (r.state != SurveyRow::Ok || !r.hasFocus || r.focus.size() != cells * FocusRecordWords || !model ||
-            model->size() != cells * FocusModelWords) {
-            text += "\t-\t-\t-\t-\t-\t-\t-\t-\t-\t-\t-\n";
+        rowPrefix(text, r);
+        std::string cols;
+        bool first = false;
+        hit.assign(cells, 0);
+        const int kind = d.row(r, cells, cols, first, hit);
+        if (kind < 0) {
+            text += dashes + "\n";
             continue;
         }
         Cam &c = cams[(size_t)r.cam];
-        c.changed.resize(cells, 0);
-        const FocusFrame f = focusFrame(r.focus.data(), model->data(), cells);
-        for (size_t k = 0; k < cells; ++k) {
-            const FocusCell fc = focusCell(r.focus.data() + k * FocusRecordWords, model->data() + k * FocusModelWords);
-            c.changed[k] += fc.rated && fc.changed;
-        }
-        snprintf(buf, sizeof buf, "\t%lld\t%d\t%d\t%d\t%d\t%d", c.frames, f.rated, f.clipped, f.changed, f.softer, f.harder);
-        text += buf;
-        if (f.kind == FocusFrame::Blind)
-            snprintf(buf, sizeof buf, "\t-\t-\t-\t-");
-        else
-            snprintf(buf, sizeof buf, "\t%lld\t%lld\t%lld\t%lld", f.keepMilli, f.keepMin, f.keepMax, f.energyMilli);
-        text += buf;
-        text += std::string("\t") + kinds[f.kind] + "\n";
+        c.kind.resize(K, 0);
+        c.perCell.resize(cells, 0);
+        for (size_t k = 0; k < cells; ++k)
+            c.perCell[k] += hit[k];
+        snprintf(buf, sizeof buf, "\t%lld", c.frames);
+        text += buf + cols + "\t" + d.kinds[(size_t)kind] + "\n";
         ++c.frames;
-        ++c.kind[f.kind];
-        if (f.changed && !c.first)
+        ++c.kind[(size_t)kind];
+        if (first && !c.first)
             c.first = &r.event;
     }
-    long long frames = 0, kind[4] = {0, 0, 0, 0};
+    long long frames = 0;
+    std::vector<long long> kind(K, 0);
     for (size_t c = 0; c < cams.size(); ++c) {
         if (!models[c].trained) {
-            snprintf(buf, sizeof buf, "focus cam %zu none\n", c);
+            snprintf(buf, sizeof buf, "%s cam %zu none\n", d.tag, c);
             text += buf;
             continue;
         }
-        const Cam &k = cams[c];
-        snprintf(buf, sizeof buf, "focus cam %zu frames %lld blind %lld steady %lld soft %lld uneven %lld first_changed_event %s\n", c, k.frames,
-                 k.kind[0], k.kind[1], k.kind[2], k.kind[3], k.first ? k.first->c_str() : "-");
+        Cam &k = cams[c];
+        k.kind.resize(K, 0);
+        snprintf(buf, sizeof buf, "%s cam %zu frames %lld", d.tag, c, k.frames);
         text += buf;
-        frames += k.frames;
-        for (int q = 0; q < 4; ++q)
+        for (size_t q = 0; q < K; ++q) {
+            snprintf(buf, sizeof buf, " %s %lld", d.kinds[q], k.kind[q]);
+            text += buf;
             kind[q] += k.kind[q];
+        }
+        text += std::string(" ") + d.firstLabel + " " + (k.first ? *k.first : std::string("-")) + "\n";
+        frames += k.frames;
     }
     for (size_t c = 0; c < cams.size(); ++c) {
         if (!models[c].trained)
             continue;
         for (int y = 0; y < ncy; ++y) {
-            snprintf(buf, sizeof buf, "changed cam %zu y %d", c, y);
+            snprintf(buf, sizeof buf, "%s cam %zu y %d", d.mapWord, c, y);
             text += buf;
             for (int x = 0; x < ncx; ++x) {
                 const size_t k = (size_t)y * ncx + x;
-                snprintf(buf, sizeof buf, " %lld", k < cams[c].changed.size() ? cams[c].changed[k] : 0ll);
+                snprintf(buf, sizeof buf, " %lld", k < cams[c].perCell.size() ? cams[c].perCell[k] : 0ll);
                 text += buf;
             }
             text += "\n";
         }
     }
-    snprintf(buf, sizeof buf, "run frames %lld blind %lld steady %lld soft %lld uneven %lld\n", frames, kind[0], kind[1], kind[2], kind[3]);
+    snprintf(buf, sizeof buf, "run frames %lld", frames);
     text += buf;
-    return text;
+    for (size_t q = 0; q < K; ++q) {
+        snprintf(buf, sizeof buf, " %s %lld", d.kinds[q], kind[q]);
+        text += buf;
+    }
+    return text + "\n";
 }
+
+} // namespace
 
 std::string FieldReport(int radius, int W, int H, const std::vector<SurveyModel> &models, const std::vector<SurveyRow> &rows)
 {
-    int ncx = 0, ncy = 0, x0 = 0, y0 = 0;
-    if (W > 0 && H > 0)
-        abub_frame_cells_grid(W, H, radius, &ncx, &ncy, &x0, &y0);
-    const size_t cells = (size_t)ncx * ncy;
-    std::string text = "# abub3hs field 1\n";
-    char buf[512];
-    snprintf(buf, sizeof buf, "radius %d cell %d grid %d %d origin %d %d\n", radius, (int)ABUB_FIELD_CELL, ncx, ncy, x0, y0);
-    text += buf;
-    text += "event\tcam\tframe\tname\tstate\tindex\trated\tmoved\tmodal_dx\tmodal_dy\tmodal_n\tdx_min\tdx_max\tdy_min\tdy_max\tkind\n";
     enum { Blind, Still, Rigid, Warped, Local };
-    static const char *const kinds[] = {"blind", "still", "rigid", "warped", "local"};
-    struct Cam {
-        long long frames = 0, kind[5] = {0, 0, 0, 0, 0};
-        const std::string *first = nullptr;
-        std::vector<long long> moved; // per cell: the frames in which it was rated and off (0, 0)
-    };
-    std::vector<Cam> cams(models.size());
-    for (const SurveyRow &r : rows) {
-        snprintf(buf, sizeof buf, "%s\t%d\t%d\t%s\t%s", r.event.c_str(), r.cam, r.frame, r.name.c_str(), r.stateName());
-        text += buf;
-        if (r.state != SurveyRow::Ok || !r.hasField || r.field.size() != cells * FieldRecordWords) {
-            text += "\t-\t-\t-\t-\t-\t-\t-\t-\t-\t-\t-\n";
-            continue;
-        }
-        Cam &c = cams[(size_t)r.cam];
-        c.moved.resize(cells, 0);
+    const auto row = [](const SurveyRow &r, size_t cells, std::string &cols, bool &first, std::vector<long long> &hit) -> int {
+        if (r.state != SurveyRow::Ok || !r.has(SurveyFieldProduct) || r.field.size() != cells * FieldRecordWords)
+            return -1;
         int rated = 0, moved = 0, dxMin = 0, dxMax = 0, dyMin = 0, dyMax = 0;
         std::map<std::pair<int, int>, int> seen; // (dy, dx) of the rated cells -> how many
         for (size_t k = 0; k < cells; ++k) {
@@ -604,7 +522,7 @@ std::string FieldReport(int radius, int W, int H, const std::vector<SurveyModel>
             ++seen[{dy, dx}];
             if (dx != 0 || dy != 0) {
                 ++moved;
-                ++c.moved[k];
+                ++hit[k];
             }
         }
         // the most frequent displacement; among equally frequent ones shiftBest's order: the nearer, the smaller dy, the smaller dx
@@ -618,51 +536,76 @@ std::string FieldReport(int radius, int W, int H, const std::vector<SurveyModel>
             }
         }
         const int kind = !rated ? Blind : !moved ? Still : moved < rated ? Local : seen.size() == 1 ? Rigid : Warped;
-        snprintf(buf, sizeof buf, "\t%lld\t%d\t%d", c.frames, rated, moved);
-        text += buf;
+        char buf[512];
         if (kind == Blind)
-            snprintf(buf, sizeof buf, "\t-\t-\t-\t-\t-\t-\t-\t%s\n", kinds[kind]);
+            snprintf(buf, sizeof buf, "\t%d\t%d\t-\t-\t-\t-\t-\t-\t-", rated, moved);
         else
-            snprintf(buf, sizeof buf, "\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%s\n", mdx, mdy, mn, dxMin, dxMax, dyMin, dyMax, kinds[kind]);
-        text += buf;
-        ++c.frames;
-        ++c.kind[kind];
-        if (moved && !c.first)
-            c.first = &r.event;
-    }
-    long long frames = 0, kind[5] = {0, 0, 0, 0, 0};
-    for (size_t c = 0; c < cams.size(); ++c) {
-        if (!models[c].trained) {
-            snprintf(buf, sizeof buf, "field cam %zu none\n", c);
-            text += buf;
-            continue;
+            snprintf(buf, sizeof buf, "\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d", rated, moved, mdx, mdy, mn, dxMin, dxMax, dyMin, dyMax);
+        cols += buf;
+        first = moved != 0;
+        return kind;
+    };
+    return cellReport({"field", "rated\tmoved\tmodal_dx\tmodal_dy\tmodal_n\tdx_min\tdx_max\tdy_min\tdy_max",
+                       {"blind", "still", "rigid", "warped", "local"}, "moved", "first_moved_event", row},
+                      radius, W, H, models, rows);
+}
+
+std::string LightReport(int radius, int W, int H, const std::vector<SurveyModel> &models, const std::vector<SurveyRow> &rows)
+{
+    const auto row = [&](const SurveyRow &r, size_t cells, std::string &cols, bool &first, std::vector<long long> &hit) -> int {
+        const std::vector<uint32_t> *model = (size_t)r.cam < models.size() ? &models[(size_t)r.cam].light : nullptr;
+        if (r.state != SurveyRow::Ok || !r.has(SurveyLightProduct) || r.light.size() != cells * LightRecordWords || !model ||
+            model->size() != cells * LightModelWords)
+            return -1;
+        const LightFrame f = lightFrame(r.light.data(), model->data(), cells);
+        for (size_t k = 0; k < cells; ++k) {
+            const LightCell lc = lightCell(r.light.data() + k * LightRecordWords, model->data() + k * LightModelWords);
+            hit[k] += lc.rated && lc.changed;
         }
-        const Cam &k = cams[c];
-        snprintf(buf, sizeof buf, "field cam %zu frames %lld blind %lld still %lld rigid %lld warped %lld local %lld first_moved_event %s\n", c,
-                 k.frames, k.kind[Blind], k.kind[Still], k.kind[Rigid], k.kind[Warped], k.kind[Local], k.first ? k.first->c_str() : "-");
-        text += buf;
-        frames += k.frames;
-        for (int q = 0; q < 5; ++q)
-            kind[q] += k.kind[q];
-    }
-    for (size_t c = 0; c < cams.size(); ++c) {
-        if (!models[c].trained)
-            continue;
-        for (int y = 0; y < ncy; ++y) {
-            snprintf(buf, sizeof buf, "moved cam %zu y %d", c, y);
-            text += buf;
-            for (int x = 0; x < ncx; ++x) {
-                const size_t k = (size_t)y * ncx + x;
-                snprintf(buf, sizeof buf, " %lld", k < cams[c].moved.size() ? cams[c].moved[k] : 0ll);
-                text += buf;
-            }
-            text += "\n";
+        char buf[512];
+        snprintf(buf, sizeof buf, "\t%d\t%d\t%d\t%d\t%d", f.rated, f.clipped, f.changed, f.up, f.down);
+        cols += buf;
+        if (f.kind == LightFrame::Blind)
+            snprintf(buf, sizeof buf, "\t-\t-\t-\t-\t-");
+        else if (f.hasGain)
+            snprintf(buf, sizeof buf, "\t%lld\t%lld\t%lld\t%lld\t%lld", f.levelMilli, f.ratioMin, f.ratioMax, f.gainMilli, f.offsetMilli);
+        else
+            snprintf(buf, sizeof buf, "\t%lld\t%lld\t%lld\t-\t-", f.levelMilli, f.ratioMin, f.ratioMax);
+        cols += buf;
+        first = f.changed != 0;
+        return f.kind;
+    };
+    return cellReport({"light", "rated\tclipped\tchanged\tup\tdown\tlevel_milli\tratio_min\tratio_max\tgain_milli\toffset_milli",
+                       {"blind", "steady", "level", "uneven"}, "changed", "first_changed_event", row},
+                      radius, W, H, models, rows);
+}
+
+std::string FocusReport(int radius, int W, int H, const std::vector<SurveyModel> &models, const std::vector<SurveyRow> &rows)
+{
+    const auto row = [&](const SurveyRow &r, size_t cells, std::string &cols, bool &first, std::vector<long long> &hit) -> int {
+        const std::vector<int64_t> *model = (size_t)r.cam < models.size() ? &models[(size_t)r.cam].focus : nullptr;
+        if (r.state != SurveyRow::Ok || !r.has(SurveyFocusProduct) || r.focus.size() != cells * FocusRecordWords || !model ||
+            model->size() != cells * FocusModelWords)
+            return -1;
+        const FocusFrame f = focusFrame(r.focus.data(), model->data(), cells);
+        for (size_t k = 0; k < cells; ++k) {
+            const FocusCell fc = focusCell(r.focus.data() + k * FocusRecordWords, model->data() + k * FocusModelWords);
+            hit[k] += fc.rated && fc.changed;
         }
-    }
-    snprintf(buf, sizeof buf, "run frames %lld blind %lld still %lld rigid %lld warped %lld local %lld\n", frames, kind[Blind], kind[Still],
-             kind[Rigid], kind[Warped], kind[Local]);
-    text += buf;
-    return text;
+        char buf[512];
+        snprintf(buf, sizeof buf, "\t%d\t%d\t%d\t%d\t%d", f.rated, f.clipped, f.changed, f.softer, f.harder);
+        cols += buf;
+        if (f.kind == FocusFrame::Blind)
+            snprintf(buf, sizeof buf, "\t-\t-\t-\t-");
+        else
+            snprintf(buf, sizeof buf, "\t%lld\t%lld\t%lld\t%lld", f.keepMilli, f.keepMin, f.keepMax, f.energyMilli);
+        cols += buf;
+        first = f.changed != 0;
+        return f.kind;
+    };
+    return cellReport({"focus", "rated\tclipped\tchanged\tsofter\tharder\tkeep_milli\tkeep_min\tkeep_max\tenergy_milli",
+                       {"blind", "steady", "soft", "uneven"}, "changed", "first_changed_event", row},
+                      radius, W, H, models, rows);
 }
 
 std::string ShiftReport(int radius, const std::vector<SurveyModel> &models, const std::vector<SurveyRow> &rows)
@@ -679,9 +622,8 @@ std::string ShiftReport(int radius, const std::vector<SurveyModel> &models, cons
     };
     std::vector<Cam> cams(models.size());
     for (const SurveyRow &r : rows) {
-        snprintf(buf, sizeof buf, "%s\t%d\t%d\t%s\t%s", r.event.c_str(), r.cam, r.frame, r.name.c_str(), r.stateName());
-        text += buf;
-        if (r.state != SurveyRow::Ok || !r.hasShift) {
+        rowPrefix(text, r);
+        if (r.state != SurveyRow::Ok || !r.has(SurveyShiftProduct)) {
             text += "\t-\t-\t-\t-\t-\t-\n";
             continue;
         }
@@ -748,8 +690,7 @@ std::string SurveyReport(const std::vector<SurveyModel> &models, const std::vect
     std::vector<double> movedShare;
     for (const SurveyRow &r : rows) {
         ++perState[r.state];
-        snprintf(buf, sizeof buf, "%s\t%d\t%d\t%s\t%s", r.event.c_str(), r.cam, r.frame, r.name.c_str(), r.stateName());
-        text += buf;
+        rowPrefix(text, r);
         if (r.state != SurveyRow::Ok && r.state != SurveyRow::OtherSize) {
             text += "\t-\t-\t-\t-\t-\t-\t-\t-\t-\t-\t-\t-\t-\t-\n";
             continue;
@@ -811,19 +752,16 @@ struct HostPlanes {
 };
 
 // The part of a survey that is not its frames' pixels
+struct CellGrid { // abub_frame_cells_grid's answer
+    int ncx = 0, ncy = 0, x0 = 0, y0 = 0;
+    size_t cells() const { return (size_t)ncx * ncy; }
+};
 struct Plan {
     HostPlanes *planes = nullptr;   // with a planes directory: where surveyFrame adds its ok rows
-    int shiftR = 0;                 // with a shift file: the radius surveyFrame searches its ok rows with a model in (0: none)
-    std::atomic<long long> *shiftHostUs = nullptr; // ... and where it adds the microseconds it spent in frameShiftHost
-    int fieldR = 0;                 // with a field directory: the radius of the per-cell search (0: none) ...
-    size_t fieldCells = 0;          // ... the run's cells (abub_frame_cells_grid) ...
-    std::atomic<long long> *fieldHostUs = nullptr; // ... and where surveyFrame adds the microseconds it spent in fieldCellsHost
-    bool light = false;             // with a light directory: surveyFrame gives its ok rows with a model their light records ...
-    int lightNcx = 0, lightNcy = 0, lightX0 = 0, lightY0 = 0; // ... on this grid (abub_frame_cells_grid at the field's radius) ...
-    std::atomic<long long> *lightHostUs = nullptr; // ... and adds the microseconds it spent in lightCellsHost here
-    bool focus = false;             // with a focus directory: surveyFrame gives its ok rows with a model their focus records ...
-    int focusNcx = 0, focusNcy = 0, focusX0 = 0, focusY0 = 0; // ... on this grid (the same rule) ...
-    std::atomic<long long> *focusHostUs = nullptr; // ... and adds the microseconds it spent in focusCellsHost here
+    bool want[SurveyProducts] = {false, false, false, false}; // the products surveyFrame makes of its ok rows with a model
+    int shiftR = 0, cellR = 0;      // the shift search's radius; the radius of the grid and of the field's per-cell search
+    CellGrid grid;                  // the one grid of the field, the light and the focus (all zero: none asked for, or no size)
+    std::atomic<long long> *hostUs = nullptr; // [SurveyProducts]: where surveyFrame adds the microseconds it spent in a definition
     std::vector<std::string> events;
     std::vector<SurveyRow> rows;    // in event, camera and frame order
     std::vector<size_t> ref;        // ref[i]: the row frame i is measured against (frame max(i - 2, 0) of its stack)
@@ -943,65 +881,48 @@ cv::Mat decodeRow(Parser &p, const Plan &pl, size_t i)
     return file.empty() ? cv::Mat() : cv::imdecode(file.data(), file.size(), 0);
 }
 
-// The shift search of an ok row of a camera with a model on this thread: the definition, then the one tie rule
-void shiftRowHost(const Plan &pl, const uint8_t *cur, const uint8_t *mu, SurveyRow &row)
-{
-    const double t0 = nowMs();
-    const size_t D = 2 * (size_t)pl.shiftR + 1;
-    std::vector<uint64_t> sad(D * D);
-    frameShiftHost(cur, mu, pl.W, pl.H, pl.shiftR, sad.data());
-    row.shift = shiftBest(sad.data(), pl.shiftR);
-    row.hasShift = true;
-    row.shiftOnKernel = false;
-    if (pl.shiftHostUs)
-        *pl.shiftHostUs += (long long)((nowMs() - t0) * 1e3);
-}
-
 // a row's records from its cells' surfaces ([cells][(2 R + 1)^2]), whichever route made them
-void fieldRecords(const Plan &pl, const uint32_t *sad, SurveyRow &row, bool onKernel)
+void fieldRecords(const Plan &pl, const uint32_t *sad, SurveyRow &row)
 {
-    const size_t N = (2 * (size_t)pl.fieldR + 1) * (2 * (size_t)pl.fieldR + 1);
-    row.field.resize(pl.fieldCells * FieldRecordWords);
-    for (size_t k = 0; k < pl.fieldCells; ++k)
-        fieldCell(sad + k * N, pl.fieldR, row.field.data() + k * FieldRecordWords);
-    row.hasField = true;
-    row.fieldOnKernel = onKernel;
+    const size_t N = (2 * (size_t)pl.cellR + 1) * (2 * (size_t)pl.cellR + 1);
+    row.field.resize(pl.grid.cells() * FieldRecordWords);
+    for (size_t k = 0; k < pl.grid.cells(); ++k)
+        fieldCell(sad + k * N, pl.cellR, row.field.data() + k * FieldRecordWords);
 }
 
-// The per-cell search of an ok row of a camera with a model on this thread: the definition, then the records
-void fieldRowHost(const Plan &pl, const uint8_t *cur, const uint8_t *mu, SurveyRow &row)
+// The products of an ok row of a camera with a model on this thread: each one's definition and where its result goes, under
+// one clock
+void productsHost(const Plan &pl, const uint8_t *cur, const uint8_t *mu, SurveyRow &row)
 {
-    const double t0 = nowMs();
-    const size_t N = (2 * (size_t)pl.fieldR + 1) * (2 * (size_t)pl.fieldR + 1);
-    std::vector<uint32_t> sad(pl.fieldCells * N);
-    fieldCellsHost(cur, mu, pl.W, pl.H, pl.fieldR, sad.data());
-    fieldRecords(pl, sad.data(), row, false);
-    if (pl.fieldHostUs)
-        *pl.fieldHostUs += (long long)((nowMs() - t0) * 1e3);
-}
-
-// The light records of an ok row of a camera with a model on this thread: the definition
-void lightRowHost(const Plan &pl, const uint8_t *cur, const uint8_t *mu, SurveyRow &row)
-{
-    const double t0 = nowMs();
-    row.light.resize((size_t)pl.lightNcx * pl.lightNcy * LightRecordWords);
-    lightCellsHost(cur, mu, pl.W, pl.H, pl.lightX0, pl.lightY0, pl.lightNcx, pl.lightNcy, row.light.data());
-    row.hasLight = true;
-    row.lightOnKernel = false;
-    if (pl.lightHostUs)
-        *pl.lightHostUs += (long long)((nowMs() - t0) * 1e3);
-}
-
-// The focus records of an ok row of a camera with a model on this thread: the definition
-void focusRowHost(const Plan &pl, const uint8_t *cur, const uint8_t *mu, SurveyRow &row)
-{
-    const double t0 = nowMs();
-    row.focus.resize((size_t)pl.focusNcx * pl.focusNcy * FocusRecordWords);
-    focusCellsHost(cur, mu, pl.W, pl.H, pl.focusX0, pl.focusY0, pl.focusNcx, pl.focusNcy, row.focus.data());
-    row.hasFocus = true;
-    row.focusOnKernel = false;
-    if (pl.focusHostUs)
-        *pl.focusHostUs += (long long)((nowMs() - t0) * 1e3);
+    const auto timed = [&](SurveyProduct p, auto make) {
+        if (!pl.want[p])
+            return;
+        const double t0 = nowMs();
+        make();
+        row.set(p, SurveyRow::Host);
+        pl.hostUs[p] += (long long)((nowMs() - t0) * 1e3);
+    };
+    const CellGrid &g = pl.grid;
+    timed(SurveyShiftProduct, [&] {
+        const size_t D = 2 * (size_t)pl.shiftR + 1;
+        std::vector<uint64_t> sad(D * D);
+        frameShiftHost(cur, mu, pl.W, pl.H, pl.shiftR, sad.data());
+        row.shift = shiftBest(sad.data(), pl.shiftR); // (the one tie rule)
+    });
+    timed(SurveyFieldProduct, [&] {
+        const size_t N = (2 * (size_t)pl.cellR + 1) * (2 * (size_t)pl.cellR + 1);
+        std::vector<uint32_t> sad(g.cells() * N);
+        fieldCellsHost(cur, mu, pl.W, pl.H, pl.cellR, sad.data());
+        fieldRecords(pl, sad.data(), row);
+    });
+    timed(SurveyLightProduct, [&] {
+        row.light.resize(g.cells() * LightRecordWords);
+        lightCellsHost(cur, mu, pl.W, pl.H, g.x0, g.y0, g.ncx, g.ncy, row.light.data());
+    });
+    timed(SurveyFocusProduct, [&] {
+        row.focus.resize(g.cells() * FocusRecordWords);
+        focusCellsHost(cur, mu, pl.W, pl.H, g.x0, g.y0, g.ncx, g.ncy, row.focus.data());
+    });
 }
 
 // The host route's per-frame function: row i on this thread, its state and its record.  It asks nothing of the other rows:
@@ -1009,10 +930,7 @@ void focusRowHost(const Plan &pl, const uint8_t *cur, const uint8_t *mu, SurveyR
 void surveyFrame(Parser &p, const Plan &pl, size_t i, SurveyRow &row)
 {
     row.onKernel = false;
-    row.hasShift = row.shiftOnKernel = false;
-    row.hasField = row.fieldOnKernel = false;
-    row.hasLight = row.lightOnKernel = false;
-    row.hasFocus = row.focusOnKernel = false;
+    row.made = 0;
     row.s = FrameStats();
     row.w = row.h = 0;
     if (row.state == SurveyRow::Missing)
@@ -1043,14 +961,8 @@ void surveyFrame(Parser &p, const Plan &pl, size_t i, SurveyRow &row)
     row.s = frameStatsHost(cur.data, r, mu, mu ? pl.sigma6[row.cam].data() : nullptr, n);
     if (pl.planes)
         pl.planes->add(row.cam, cur.data, r, mu, mu ? pl.sigma6[row.cam].data() : nullptr);
-    if (pl.shiftR && mu)
-        shiftRowHost(pl, cur.data, mu, row);
-    if (pl.fieldR && mu)
-        fieldRowHost(pl, cur.data, mu, row);
-    if (pl.light && mu)
-        lightRowHost(pl, cur.data, mu, row);
-    if (pl.focus && mu)
-        focusRowHost(pl, cur.data, mu, row);
+    if (mu)
+        productsHost(pl, cur.data, mu, row);
 }
 
 void hostFrames(Parser *parser, Plan &pl, int nthreads)
@@ -1075,28 +987,23 @@ FrameStats fromRecord(const abub_stat_result &r)
     return s;
 }
 
-// The device route: the rows in batches.  Per batch: the reference frames of its first rows that lie in front of it take
-// the first slots (they are read again), then the rows; the pool reads the files into a pinned buffer; upload; the decoders
-// into the slab, slot s at s * align16(W * H); one abub_frame_stats_dev launch over the rows that are in place, and the
-// records back in one copy.  A row that is not in place goes to surveyFrame.  With pl.planes the rows in place are also
-// added to the per-pixel planes on the device, [camera][6][stride] u32 cleared once: behind the batch's statistics launch one
-// abub_pixel_activity_dev call per camera that has rows in place, its jobs behind the records in the same meta buffer; they
-// come back in one copy at the end, into devPlanes.  A row in place whose file no GPU decoder reads was decoded by a reading
-// thread; its pixels are on the host, and it is added to the host planes there, not by the kernel.
-// With pl.shiftR the rows in place that have a model are also searched for their displacement, behind the statistics launch
-// and on the same stream: one abub_frame_shift_dev call per batch over [jobs][status words][surfaces] in a buffer of its own
-// (mu is resident already), the surfaces back in one copy; shiftBest on the host says what each means.  Every row in place
-// is in the slab, whichever decoder or thread put it there, so all of them are the kernel's.
-// With pl.fieldR the same rows are then searched per cell, behind the shift launch on the same stream, over
-// [jobs][status words][surfaces] in a buffer of its own: abub_frame_shift_cells_dev in calls of as many jobs as keep the
-// surfaces below 64 MiB (ABUB_FIELD_CHUNK=n, a test knob: of n jobs), each call's status words and surfaces back in one copy.
-// A job's surface depends on nothing but the job, so the split cannot show in the result.
-// With pl.light the same rows then get their light records, behind the launches above on the same stream: one
-// abub_frame_light_cells_dev call per batch over [jobs][status words][records] in a buffer of its own, the status words and
-// the records (24 bytes per cell) back in one copy.
-// With pl.focus the same rows then get their focus records in the same way, behind the light's launch on the same stream: one
-// abub_frame_focus_cells_dev call per batch over [jobs][status words][records] in a buffer of its own, the status words and
-// the records (20 bytes per cell) back in one copy.
+// The device route: the rows in batches, every leg on the one stream and synchronised before the next.  Per batch: the
+// reference frames of its first rows that lie in front of it take the first slots (they are read again), then the rows; the
+// pool reads the files into a pinned buffer; upload; the decoders into the slab, slot s at s * align16(W * H).  A row that is
+// not in place goes to surveyFrame.  Every row in place is in the slab, whichever decoder or thread put it there, so the
+// legs below take all of them.  In order:
+// * stats: one abub_frame_stats_dev launch over the rows in place, [jobs][records] in the meta buffer, the records back in
+//   one copy.  The list of the jobs that have a model is made from them once, as one abub_shift_job array, and uploaded once
+//   (mu is resident already); the four product legs read it.
+// * shift, field, light, focus, each only if asked for: one helper (`leg`) launches the product's entry over that list,
+//   copies [status words][payloads] back from the one buffer pair the legs share, checks the status words and hands every
+//   row its payload.  The shift's payload is a u64 surface, read by shiftBest; the field's are the cells' u32 surfaces, read
+//   by fieldRecords, in calls of as many jobs as keep them below 64 MiB (ABUB_FIELD_CHUNK=n: of n jobs), a call reading the
+//   list from its first job on; the light's and the focus' are the cells' records as they are (24 and 20 bytes per cell).
+// * activity, with pl.planes: the rows in place are added to the per-pixel planes on the device, [camera][6][stride] u32
+//   cleared once: one abub_pixel_activity_dev call per camera that has rows in place, its jobs behind the records in the
+//   meta buffer; the planes come back in one copy at the end, into devPlanes.  A row in place whose file no GPU decoder reads
+//   was decoded by a reading thread; its pixels are on the host, and it is added to the host planes there, not by the kernel.
 void deviceFrames(Parser *parser, Plan &pl, int nthreads, int device, SurveyStats &st, std::vector<uint32_t> &devPlanes)
 {
     HIPOK(hipSetDevice(device));
@@ -1108,8 +1015,8 @@ void deviceFrames(Parser *parser, Plan &pl, int nthreads, int device, SurveyStat
     const size_t P = (size_t)W * H, stride = (P + 15) & ~(size_t)15, C = pl.mu.size();
     FileBatch B;
     B.sizer.reset(parser->clone());
-    PinnedBuffer h_meta, h_shift, h_field, h_light, h_focus;
-    DeviceBuffer d_meta, d_shift, d_field, d_light, d_focus, d_model; // d_model: [mu of every camera][sigma6 of every camera], camera c at c * stride
+    PinnedBuffer h_meta, h_jobs, h_leg;
+    DeviceBuffer d_meta, d_jobsBuf, d_leg, d_model; // d_model: [mu of every camera][sigma6 of every camera], camera c at c * stride
     Stream stream;
     hipStream_t cs = stream.get();
     bool anyModel = false;
@@ -1204,154 +1111,86 @@ void deviceFrames(Parser *parser, Plan &pl, int nthreads, int device, SurveyStat
                   "abub_frame_stats_dev");
             HIPOK(hipMemcpyAsync(h_meta.get() + nj * sizeof(abub_stat_job), d_res, nj * sizeof(abub_stat_result), hipMemcpyDeviceToHost, cs));
             HIPOK(hipStreamSynchronize(cs));
-            if (pl.shiftR) {
+            // ---- the products of the jobs that have a model: one job list, one leg per product ------------------------------
+            std::vector<size_t> with; // the jobs that have a model
+            for (size_t g = 0; g < nj; ++g)
+                if (jobs[g].model != UINT64_MAX)
+                    with.push_back(g);
+            const size_t ns = with.size();
+            const abub_shift_job *d_jobs = nullptr;
+            if (ns && (pl.want[SurveyShiftProduct] || pl.want[SurveyFieldProduct] || pl.want[SurveyLightProduct] || pl.want[SurveyFocusProduct])) {
+                h_jobs.grow(ns * sizeof(abub_shift_job));
+                d_jobsBuf.grow(ns * sizeof(abub_shift_job));
+                abub_shift_job *sj = (abub_shift_job *)h_jobs.get();
+                for (size_t q = 0; q < ns; ++q)
+                    sj[q] = abub_shift_job{jobs[with[q]].cur, jobs[with[q]].model};
+                HIPOK(hipMemcpyAsync(d_jobsBuf.get(), sj, ns * sizeof(abub_shift_job), hipMemcpyHostToDevice, cs));
+                d_jobs = (const abub_shift_job *)d_jobsBuf.get();
+            }
+            const auto rowWith = [&](size_t q) -> SurveyRow & { return pl.rows[rowOf(slot[with[q]])]; };
+            // One leg: `entry` over the jobs in calls of `chunk` (0: all of them in one; no job: no call), each call's status
+            // words and payloads ([status, padded to 8 bytes][payloadBytes per job], the one buffer pair of all legs, which
+            // synchronise one after another) back in one copy; take(q, payload) gets what job q's row is given
+            const auto leg = [&](SurveyProduct p, const char *entry, size_t payloadBytes, size_t chunk, auto launch, auto take) {
+                if (!pl.want[p])
+                    return;
                 st.stats_s += (nowMs() - t0) * 1e-3;
                 t0 = nowMs();
-                std::vector<size_t> with; // the jobs that have a model
-                for (size_t g = 0; g < nj; ++g)
-                    if (jobs[g].model != UINT64_MAX)
-                        with.push_back(g);
-                const size_t ns = with.size(), N = (2 * (size_t)pl.shiftR + 1) * (2 * (size_t)pl.shiftR + 1);
-                if (ns) {
-                    const size_t jobBytes = ns * sizeof(abub_shift_job), statusBytes = (ns * sizeof(uint32_t) + 7) & ~(size_t)7;
-                    const size_t bytes = jobBytes + statusBytes + ns * N * sizeof(uint64_t);
-                    h_shift.grow(bytes);
-                    d_shift.grow(bytes);
-                    abub_shift_job *sj = (abub_shift_job *)h_shift.get();
-                    for (size_t q = 0; q < ns; ++q)
-                        sj[q] = abub_shift_job{jobs[with[q]].cur, jobs[with[q]].model};
-                    HIPOK(hipMemcpyAsync(d_shift.get(), h_shift.get(), jobBytes, hipMemcpyHostToDevice, cs));
-                    check(abub_frame_shift_dev(B.slab.get(), slots * stride, d_model.get(), C * stride, (const abub_shift_job *)d_shift.get(),
-                                               (int)ns, W, H, pl.shiftR, (uint32_t *)(d_shift.get() + jobBytes),
-                                               (uint64_t *)(d_shift.get() + jobBytes + statusBytes), cs),
-                          "abub_frame_shift_dev");
-                    HIPOK(hipMemcpyAsync(h_shift.get() + jobBytes, d_shift.get() + jobBytes, bytes - jobBytes, hipMemcpyDeviceToHost, cs));
+                for (size_t q0 = 0; q0 < ns; q0 += chunk ? chunk : ns) {
+                    const size_t n = std::min(chunk ? chunk : ns, ns - q0);
+                    const size_t statusBytes = (n * sizeof(uint32_t) + 7) & ~(size_t)7, bytes = statusBytes + n * payloadBytes;
+                    h_leg.grow(bytes);
+                    d_leg.grow(bytes);
+                    check(launch(d_jobs + q0, (int)n, (uint32_t *)d_leg.get(), d_leg.get() + statusBytes), entry);
+                    HIPOK(hipMemcpyAsync(h_leg.get(), d_leg.get(), bytes, hipMemcpyDeviceToHost, cs));
                     HIPOK(hipStreamSynchronize(cs));
-                    const uint32_t *status = (const uint32_t *)(h_shift.get() + jobBytes);
-                    const uint64_t *sad = (const uint64_t *)(h_shift.get() + jobBytes + statusBytes);
-                    for (size_t q = 0; q < ns; ++q) {
-                        if (status[q] != 0)
-                            throw std::runtime_error("survey: abub_frame_shift_dev refused a frame of its own slab");
-                        SurveyRow &row = pl.rows[rowOf(slot[with[q]])];
-                        row.shift = shiftBest(sad + q * N, pl.shiftR);
-                        row.hasShift = row.shiftOnKernel = true;
+                    for (size_t q = 0; q < n; ++q) {
+                        if (((const uint32_t *)h_leg.get())[q] != 0)
+                            throw std::runtime_error(std::string("survey: ") + entry + " refused a frame of its own slab");
+                        take(q0 + q, h_leg.get() + statusBytes + q * payloadBytes);
+                        rowWith(q0 + q).set(p, SurveyRow::Kernel);
                     }
-                    ++st.shiftLaunches;
+                    ++st.product[p].launches;
                 }
-                st.shift_s += (nowMs() - t0) * 1e-3;
+                st.product[p].leg_s += (nowMs() - t0) * 1e-3;
                 t0 = nowMs();
-            }
-            if (pl.fieldR) {
-                st.stats_s += (nowMs() - t0) * 1e-3;
-                t0 = nowMs();
-                std::vector<size_t> with; // the jobs that have a model
-                for (size_t g = 0; g < nj; ++g)
-                    if (jobs[g].model != UINT64_MAX)
-                        with.push_back(g);
-                const size_t N = (2 * (size_t)pl.fieldR + 1) * (2 * (size_t)pl.fieldR + 1), words = pl.fieldCells * N;
-                size_t chunk = std::max<size_t>(1, ((size_t)64 << 20) / (words * sizeof(uint32_t)));
-                if (const char *e = getenv("ABUB_FIELD_CHUNK"))
-                    if (atoi(e) > 0)
-                        chunk = (size_t)atoi(e);
-                for (size_t q0 = 0; q0 < with.size(); q0 += chunk) {
-                    const size_t ns = std::min(chunk, with.size() - q0);
-                    const size_t jobBytes = ns * sizeof(abub_shift_job), bytes = jobBytes + ns * (1 + words) * sizeof(uint32_t);
-                    h_field.grow(bytes);
-                    d_field.grow(bytes);
-                    abub_shift_job *fj = (abub_shift_job *)h_field.get();
-                    for (size_t q = 0; q < ns; ++q)
-                        fj[q] = abub_shift_job{jobs[with[q0 + q]].cur, jobs[with[q0 + q]].model};
-                    HIPOK(hipMemcpyAsync(d_field.get(), h_field.get(), jobBytes, hipMemcpyHostToDevice, cs));
-                    uint32_t *d_status = (uint32_t *)(d_field.get() + jobBytes);
-                    check(abub_frame_shift_cells_dev(B.slab.get(), slots * stride, d_model.get(), C * stride,
-                                                     (const abub_shift_job *)d_field.get(), (int)ns, W, H, pl.fieldR, d_status, d_status + ns, cs),
-                          "abub_frame_shift_cells_dev");
-                    HIPOK(hipMemcpyAsync(h_field.get() + jobBytes, d_field.get() + jobBytes, bytes - jobBytes, hipMemcpyDeviceToHost, cs));
-                    HIPOK(hipStreamSynchronize(cs));
-                    const uint32_t *status = (const uint32_t *)(h_field.get() + jobBytes), *sad = status + ns;
-                    for (size_t q = 0; q < ns; ++q) {
-                        if (status[q] != 0)
-                            throw std::runtime_error("survey: abub_frame_shift_cells_dev refused a frame of its own slab");
-                        fieldRecords(pl, sad + q * words, pl.rows[rowOf(slot[with[q0 + q]])], true);
-                    }
-                    ++st.fieldLaunches;
-                }
-                st.field_s += (nowMs() - t0) * 1e-3;
-                t0 = nowMs();
-            }
-            if (pl.light) {
-                st.stats_s += (nowMs() - t0) * 1e-3;
-                t0 = nowMs();
-                std::vector<size_t> with; // the jobs that have a model
-                for (size_t g = 0; g < nj; ++g)
-                    if (jobs[g].model != UINT64_MAX)
-                        with.push_back(g);
-                const size_t ns = with.size(), words = (size_t)pl.lightNcx * pl.lightNcy * LightRecordWords;
-                if (ns) {
-                    const size_t jobBytes = ns * sizeof(abub_shift_job), bytes = jobBytes + ns * (1 + words) * sizeof(uint32_t);
-                    h_light.grow(bytes);
-                    d_light.grow(bytes);
-                    abub_shift_job *lj = (abub_shift_job *)h_light.get();
-                    for (size_t q = 0; q < ns; ++q)
-                        lj[q] = abub_shift_job{jobs[with[q]].cur, jobs[with[q]].model};
-                    HIPOK(hipMemcpyAsync(d_light.get(), h_light.get(), jobBytes, hipMemcpyHostToDevice, cs));
-                    uint32_t *d_status = (uint32_t *)(d_light.get() + jobBytes);
-                    check(abub_frame_light_cells_dev(B.slab.get(), slots * stride, d_model.get(), C * stride,
-                                                     (const abub_shift_job *)d_light.get(), (int)ns, W, H, pl.lightX0, pl.lightY0, pl.lightNcx,
-                                                     pl.lightNcy, d_status, d_status + ns, cs),
-                          "abub_frame_light_cells_dev");
-                    HIPOK(hipMemcpyAsync(h_light.get() + jobBytes, d_light.get() + jobBytes, bytes - jobBytes, hipMemcpyDeviceToHost, cs));
-                    HIPOK(hipStreamSynchronize(cs));
-                    const uint32_t *status = (const uint32_t *)(h_light.get() + jobBytes), *rec = status + ns;
-                    for (size_t q = 0; q < ns; ++q) {
-                        if (status[q] != 0)
-                            throw std::runtime_error("survey: abub_frame_light_cells_dev refused a frame of its own slab");
-                        SurveyRow &row = pl.rows[rowOf(slot[with[q]])];
-                        row.light.assign(rec + q * words, rec + (q + 1) * words);
-                        row.hasLight = row.lightOnKernel = true;
-                    }
-                    ++st.lightLaunches;
-                }
-                st.light_s += (nowMs() - t0) * 1e-3;
-                t0 = nowMs();
-            }
-            if (pl.focus) {
-                st.stats_s += (nowMs() - t0) * 1e-3;
-                t0 = nowMs();
-                std::vector<size_t> with; // the jobs that have a model
-                for (size_t g = 0; g < nj; ++g)
-                    if (jobs[g].model != UINT64_MAX)
-                        with.push_back(g);
-                const size_t ns = with.size(), words = (size_t)pl.focusNcx * pl.focusNcy * FocusRecordWords;
-                if (ns) {
-                    const size_t jobBytes = ns * sizeof(abub_shift_job), bytes = jobBytes + ns * (1 + words) * sizeof(uint32_t);
-                    h_focus.grow(bytes);
-                    d_focus.grow(bytes);
-                    abub_shift_job *fj = (abub_shift_job *)h_focus.get();
-                    for (size_t q = 0; q < ns; ++q)
-                        fj[q] = abub_shift_job{jobs[with[q]].cur, jobs[with[q]].model};
-                    HIPOK(hipMemcpyAsync(d_focus.get(), h_focus.get(), jobBytes, hipMemcpyHostToDevice, cs));
-                    uint32_t *d_status = (uint32_t *)(d_focus.get() + jobBytes);
-                    check(abub_frame_focus_cells_dev(B.slab.get(), slots * stride, d_model.get(), C * stride,
-                                                     (const abub_shift_job *)d_focus.get(), (int)ns, W, H, pl.focusX0, pl.focusY0, pl.focusNcx,
-                                                     pl.focusNcy, d_status, (int32_t *)(d_status + ns), cs),
-                          "abub_frame_focus_cells_dev");
-                    HIPOK(hipMemcpyAsync(h_focus.get() + jobBytes, d_focus.get() + jobBytes, bytes - jobBytes, hipMemcpyDeviceToHost, cs));
-                    HIPOK(hipStreamSynchronize(cs));
-                    const uint32_t *status = (const uint32_t *)(h_focus.get() + jobBytes);
-                    const int32_t *rec = (const int32_t *)(status + ns);
-                    for (size_t q = 0; q < ns; ++q) {
-                        if (status[q] != 0)
-                            throw std::runtime_error("survey: abub_frame_focus_cells_dev refused a frame of its own slab");
-                        SurveyRow &row = pl.rows[rowOf(slot[with[q]])];
-                        row.focus.assign(rec + q * words, rec + (q + 1) * words);
-                        row.hasFocus = row.focusOnKernel = true;
-                    }
-                    ++st.focusLaunches;
-                }
-                st.focus_s += (nowMs() - t0) * 1e-3;
-                t0 = nowMs();
-            }
+            };
+            const uint8_t *slab = B.slab.get(), *d_mu = d_model.get();
+            const size_t slabBytes = slots * stride, muBytes = C * stride;
+            const CellGrid &cg = pl.grid;
+            const size_t shiftN = (2 * (size_t)pl.shiftR + 1) * (2 * (size_t)pl.shiftR + 1);
+            leg(SurveyShiftProduct, "abub_frame_shift_dev", shiftN * sizeof(uint64_t), 0,
+                [&](const abub_shift_job *j, int n, uint32_t *status, uint8_t *sad) {
+                    return abub_frame_shift_dev(slab, slabBytes, d_mu, muBytes, j, n, W, H, pl.shiftR, status, (uint64_t *)sad, cs);
+                },
+                [&](size_t q, const uint8_t *sad) { rowWith(q).shift = shiftBest((const uint64_t *)sad, pl.shiftR); });
+            // (a job's surfaces depend on nothing but the job, so the split cannot show in the result)
+            const size_t fieldWords = cg.cells() * (2 * (size_t)pl.cellR + 1) * (2 * (size_t)pl.cellR + 1);
+            size_t fieldChunk = std::max<size_t>(1, ((size_t)64 << 20) / std::max<size_t>(1, fieldWords * sizeof(uint32_t)));
+            if (const char *e = getenv("ABUB_FIELD_CHUNK")) // (a test knob)
+                if (atoi(e) > 0)
+                    fieldChunk = (size_t)atoi(e);
+            leg(SurveyFieldProduct, "abub_frame_shift_cells_dev", fieldWords * sizeof(uint32_t), fieldChunk,
+                [&](const abub_shift_job *j, int n, uint32_t *status, uint8_t *sad) {
+                    return abub_frame_shift_cells_dev(slab, slabBytes, d_mu, muBytes, j, n, W, H, pl.cellR, status, (uint32_t *)sad, cs);
+                },
+                [&](size_t q, const uint8_t *sad) { fieldRecords(pl, (const uint32_t *)sad, rowWith(q)); });
+            leg(SurveyLightProduct, "abub_frame_light_cells_dev", cg.cells() * LightRecordWords * sizeof(uint32_t), 0,
+                [&](const abub_shift_job *j, int n, uint32_t *status, uint8_t *rec) {
+                    return abub_frame_light_cells_dev(slab, slabBytes, d_mu, muBytes, j, n, W, H, cg.x0, cg.y0, cg.ncx, cg.ncy, status,
+                                                      (uint32_t *)rec, cs);
+                },
+                [&](size_t q, const uint8_t *rec) {
+                    rowWith(q).light.assign((const uint32_t *)rec, (const uint32_t *)rec + cg.cells() * LightRecordWords);
+                });
+            leg(SurveyFocusProduct, "abub_frame_focus_cells_dev", cg.cells() * FocusRecordWords * sizeof(int32_t), 0,
+                [&](const abub_shift_job *j, int n, uint32_t *status, uint8_t *rec) {
+                    return abub_frame_focus_cells_dev(slab, slabBytes, d_mu, muBytes, j, n, W, H, cg.x0, cg.y0, cg.ncx, cg.ncy, status,
+                                                      (int32_t *)rec, cs);
+                },
+                [&](size_t q, const uint8_t *rec) {
+                    rowWith(q).focus.assign((const int32_t *)rec, (const int32_t *)rec + cg.cells() * FocusRecordWords);
+                });
             if (wantPlanes) {
                 st.stats_s += (nowMs() - t0) * 1e-3;
                 t0 = nowMs();
@@ -1467,108 +1306,44 @@ std::string npyHead(const char *descr, const std::string &shape)
     return file + head;
 }
 
-// The files of the per-cell shift field, one writer for both routes ("Surveying a run for local
-// movement"): per camera with a model cam<c>_field.npy, the records of its rows that have a surface in survey order (the
-// `index` column of field.txt), and field.txt
-void writeField(const std::string &dir, int radius, const Plan &pl)
+// The files of a per-cell product, one writer for both routes: the directory; per camera with a model cam<c>_<tag>.npy, the
+// records (`words` 4-byte values per cell, the row's `rec`) of its rows that have the product in survey order (the `index`
+// column of the text), and with modelDescr cam<c>_<tag>_model.npy, the camera's `model` ([ncy][ncx][modelWords]); then
+// <tag>.txt.  The records' descr is <i4, for the light's u32 too (none reaches 2^31).
+template <class T, class M>
+void writeCells(const std::string &dir, const char *tag, SurveyProduct p, const Plan &pl, size_t words, std::vector<T> SurveyRow::*rec,
+                const char *modelDescr, size_t modelWords, std::vector<M> SurveyModel::*model, const std::string &text)
 {
+    static_assert(sizeof(T) == 4, "the records are <i4");
     std::string failed;
     if (!makeDirs(dir, &failed))
         throw std::runtime_error("survey: cannot make the directory " + failed);
-    int ncx = 0, ncy = 0, x0 = 0, y0 = 0;
-    if (pl.W > 0)
-        abub_frame_cells_grid(pl.W, pl.H, radius, &ncx, &ncy, &x0, &y0);
-    for (size_t c = 0; c < pl.models.size(); ++c) {
-        if (!pl.models[c].trained)
-            continue;
-        std::string data;
-        size_t n = 0;
-        for (const SurveyRow &r : pl.rows)
-            if ((size_t)r.cam == c && r.state == SurveyRow::Ok && r.hasField && r.field.size() == pl.fieldCells * FieldRecordWords) {
-                data.append((const char *)r.field.data(), r.field.size() * sizeof(int32_t));
-                ++n;
-            }
-        char shape[96];
-        snprintf(shape, sizeof shape, "(%zu, %d, %d, %d)", n, ncy, ncx, (int)FieldRecordWords);
-        const std::string file = npyHead("<i4", shape) + data, path = dir + "/cam" + std::to_string(c) + "_field.npy";
-        if (!writeFile(path, (const unsigned char *)file.data(), file.size()))
+    const auto write = [](const std::string &path, const std::string &bytes) {
+        if (!writeFile(path, (const unsigned char *)bytes.data(), bytes.size()))
             throw std::runtime_error("survey: cannot write " + path);
-    }
-    const std::string text = FieldReport(radius, pl.W, pl.H, pl.models, pl.rows);
-    if (!writeFile(dir + "/field.txt", (const unsigned char *)text.data(), text.size()))
-        throw std::runtime_error("survey: cannot write " + dir + "/field.txt");
-}
-
-// The files of the light records, one writer for both routes ("Surveying a run for lighting changes"): per
-// camera with a model cam<c>_light.npy, the records of its rows that have one in survey order (the `index` column of
-// light.txt), cam<c>_light_model.npy, and light.txt
-void writeLight(const std::string &dir, int radius, const Plan &pl)
-{
-    std::string failed;
-    if (!makeDirs(dir, &failed))
-        throw std::runtime_error("survey: cannot make the directory " + failed);
-    const size_t cells = (size_t)pl.lightNcx * pl.lightNcy;
+    };
+    const CellGrid &g = pl.grid;
     for (size_t c = 0; c < pl.models.size(); ++c) {
         if (!pl.models[c].trained)
             continue;
         std::string data;
         size_t n = 0;
         for (const SurveyRow &r : pl.rows)
-            if ((size_t)r.cam == c && r.state == SurveyRow::Ok && r.hasLight && r.light.size() == cells * LightRecordWords) {
-                data.append((const char *)r.light.data(), r.light.size() * sizeof(uint32_t));
+            if ((size_t)r.cam == c && r.state == SurveyRow::Ok && r.has(p) && (r.*rec).size() == g.cells() * words) {
+                data.append((const char *)(r.*rec).data(), (r.*rec).size() * sizeof(T));
                 ++n;
             }
         char shape[96];
-        snprintf(shape, sizeof shape, "(%zu, %d, %d, %d)", n, pl.lightNcy, pl.lightNcx, (int)LightRecordWords);
-        const std::string stem = dir + "/cam" + std::to_string(c);
-        std::string file = npyHead("<i4", shape) + data;
-        if (!writeFile(stem + "_light.npy", (const unsigned char *)file.data(), file.size()))
-            throw std::runtime_error("survey: cannot write " + stem + "_light.npy");
-        snprintf(shape, sizeof shape, "(%d, %d, %d)", pl.lightNcy, pl.lightNcx, (int)LightModelWords);
-        const std::vector<uint32_t> &m = pl.models[c].light;
-        file = npyHead("<i4", shape) + std::string((const char *)m.data(), m.size() * sizeof(uint32_t));
-        if (!writeFile(stem + "_light_model.npy", (const unsigned char *)file.data(), file.size()))
-            throw std::runtime_error("survey: cannot write " + stem + "_light_model.npy");
-    }
-    const std::string text = LightReport(radius, pl.W, pl.H, pl.models, pl.rows);
-    if (!writeFile(dir + "/light.txt", (const unsigned char *)text.data(), text.size()))
-        throw std::runtime_error("survey: cannot write " + dir + "/light.txt");
-}
-
-// The files of the focus records, one writer for both routes ("Surveying a run for lost focus"): per
-// camera with a model cam<c>_focus.npy, the records of its rows that have one in survey order (the `index` column of
-// focus.txt), cam<c>_focus_model.npy, and focus.txt
-void writeFocus(const std::string &dir, int radius, const Plan &pl)
-{
-    std::string failed;
-    if (!makeDirs(dir, &failed))
-        throw std::runtime_error("survey: cannot make the directory " + failed);
-    const size_t cells = (size_t)pl.focusNcx * pl.focusNcy;
-    for (size_t c = 0; c < pl.models.size(); ++c) {
-        if (!pl.models[c].trained)
+        snprintf(shape, sizeof shape, "(%zu, %d, %d, %zu)", n, g.ncy, g.ncx, words);
+        const std::string stem = dir + "/cam" + std::to_string(c) + "_" + tag;
+        write(stem + ".npy", npyHead("<i4", shape) + data);
+        if (!modelDescr)
             continue;
-        std::string data;
-        size_t n = 0;
-        for (const SurveyRow &r : pl.rows)
-            if ((size_t)r.cam == c && r.state == SurveyRow::Ok && r.hasFocus && r.focus.size() == cells * FocusRecordWords) {
-                data.append((const char *)r.focus.data(), r.focus.size() * sizeof(int32_t));
-                ++n;
-            }
-        char shape[96];
-        snprintf(shape, sizeof shape, "(%zu, %d, %d, %d)", n, pl.focusNcy, pl.focusNcx, (int)FocusRecordWords);
-        const std::string stem = dir + "/cam" + std::to_string(c);
-        std::string file = npyHead("<i4", shape) + data;
-        if (!writeFile(stem + "_focus.npy", (const unsigned char *)file.data(), file.size()))
-            throw std::runtime_error("survey: cannot write " + stem + "_focus.npy");
-        snprintf(shape, sizeof shape, "(%d, %d, %d)", pl.focusNcy, pl.focusNcx, (int)FocusModelWords);
-        const std::vector<int64_t> &m = pl.models[c].focus;
-        file = npyHead("<i8", shape) + std::string((const char *)m.data(), m.size() * sizeof(int64_t));
-        if (!writeFile(stem + "_focus_model.npy", (const unsigned char *)file.data(), file.size()))
-            throw std::runtime_error("survey: cannot write " + stem + "_focus_model.npy");
+        snprintf(shape, sizeof shape, "(%d, %d, %zu)", g.ncy, g.ncx, modelWords);
+        const std::vector<M> &m = pl.models[c].*model;
+        write(stem + "_model.npy", npyHead(modelDescr, shape) + std::string((const char *)m.data(), m.size() * sizeof(M)));
     }
-    const std::string text = FocusReport(radius, pl.W, pl.H, pl.models, pl.rows);
-    if (!writeFile(dir + "/focus.txt", (const unsigned char *)text.data(), text.size()))
-        throw std::runtime_error("survey: cannot write " + dir + "/focus.txt");
+    write(dir + "/" + tag + ".txt", text);
 }
 
 // The files of the per-pixel planes, one writer for both routes ("Surveying a run per pixel"): per camera
@@ -1670,97 +1445,77 @@ bool sameDirectory(const std::string &path, const std::string &other)
            a.st_ino == b.st_ino;
 }
 
-int surveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCams, const std::string &format,
-              const std::string &reportPath, int nthreads, int device, SurveyStats *stats, std::vector<SurveyRow> *rows,
-              std::vector<SurveyModel> *models, const SurveyPlanes &planes, const SurveyShift &shift, const SurveyField &field,
-              const SurveyLight &light, const SurveyFocus &focus)
+// a directory to write to, trimmed; refused where it is the run that is being read
+// (the files have names of their own, but a run directory is not the place for what was derived from it)
+std::string outputDir(const std::string &dir, const std::string &srcRunDir)
+{
+    const std::string d = trimSlashes(dir);
+    if (!d.empty() && sameDirectory(trimSlashes(srcRunDir), d))
+        throw std::runtime_error("survey: " + d + " is the run that is being read");
+    return d;
+}
+
+// refuses a run whose frames are too small for `what` ("a shift field", "needs") at `radius`, which takes sides of `need`; a
+// run of which no frame decodes has no size to refuse
+void needFrames(const Plan &pl, bool enough, const char *what, const char *needs, int radius, int need)
+{
+    if (pl.W > 0 && !enough)
+        throw std::runtime_error(std::string("survey: ") + what + " at radius " + std::to_string(radius) + " " + needs +
+                                 " frames of at least " + std::to_string(need) + "x" + std::to_string(need) + ", the run's are " +
+                                 std::to_string(pl.W) + "x" + std::to_string(pl.H));
+}
+
+} // namespace
+
+int SurveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCams, const std::string &format, const SurveyRequest &rq,
+              int nthreads, int device, SurveyStats *stats, std::vector<SurveyRow> *rows, std::vector<SurveyModel> *models)
 {
     const double t0 = nowMs();
     SurveyStats st;
     if (device >= 0) // (before anything else)
         requireDevice(device, "survey", "; without --survey-gpu the run is surveyed on the host");
-    const std::string planesDir = trimSlashes(planes.dir);
-    // (the planes' files have names of their own, but a run directory is not the place for what was derived from it)
-    if (!planesDir.empty() && sameDirectory(trimSlashes(planes.srcRunDir), planesDir))
-        throw std::runtime_error("survey: " + planesDir + " is the run that is being read");
-    const std::string fieldDir = trimSlashes(field.dir);
-    if (!fieldDir.empty() && sameDirectory(trimSlashes(field.srcRunDir), fieldDir))
-        throw std::runtime_error("survey: " + fieldDir + " is the run that is being read");
-    const std::string lightDir = trimSlashes(light.dir);
-    if (!lightDir.empty() && sameDirectory(trimSlashes(light.srcRunDir), lightDir))
-        throw std::runtime_error("survey: " + lightDir + " is the run that is being read");
-    const std::string focusDir = trimSlashes(focus.dir);
-    if (!focusDir.empty() && sameDirectory(trimSlashes(focus.srcRunDir), focusDir))
-        throw std::runtime_error("survey: " + focusDir + " is the run that is being read");
-    if ((!fieldDir.empty() || !lightDir.empty() || !focusDir.empty()) && (field.radius < 1 || field.radius > 8))
-        throw std::runtime_error("survey: the field radius must be in [1, 8], not " + std::to_string(field.radius));
-    if (!shift.path.empty() && (shift.radius < 1 || shift.radius > 8))
-        throw std::runtime_error("survey: the shift radius must be in [1, 8], not " + std::to_string(shift.radius));
+    const std::string planesDir = outputDir(rq.planesDir, rq.srcRunDir), fieldDir = outputDir(rq.fieldDir, rq.srcRunDir),
+                      lightDir = outputDir(rq.lightDir, rq.srcRunDir), focusDir = outputDir(rq.focusDir, rq.srcRunDir);
+    const bool want[SurveyProducts] = {!rq.shiftPath.empty(), !fieldDir.empty(), !lightDir.empty(), !focusDir.empty()};
+    const bool wantCells = want[SurveyFieldProduct] || want[SurveyLightProduct] || want[SurveyFocusProduct];
+    if (wantCells && (rq.cellRadius < 1 || rq.cellRadius > 8))
+        throw std::runtime_error("survey: the field radius must be in [1, 8], not " + std::to_string(rq.cellRadius));
+    if (want[SurveyShiftProduct] && (rq.shiftRadius < 1 || rq.shiftRadius > 8))
+        throw std::runtime_error("survey: the shift radius must be in [1, 8], not " + std::to_string(rq.shiftRadius));
     Plan pl = planRun(parser, trainers, numCams, format);
-    std::atomic<long long> shiftHostUs{0};
-    if (!shift.path.empty()) {
-        const int need = 2 * shift.radius + 1;
-        if (pl.W > 0 && (pl.W < need || pl.H < need))
-            throw std::runtime_error("survey: a shift search at radius " + std::to_string(shift.radius) + " needs frames of at least " +
-                                     std::to_string(need) + "x" + std::to_string(need) + ", the run's are " + std::to_string(pl.W) + "x" +
-                                     std::to_string(pl.H));
-        pl.shiftR = shift.radius;
-        pl.shiftHostUs = &shiftHostUs;
+    std::atomic<long long> hostUs[SurveyProducts];
+    for (int p = 0; p < SurveyProducts; ++p) {
+        hostUs[p] = 0;
+        pl.want[p] = want[p];
     }
-    std::atomic<long long> fieldHostUs{0};
-    if (!fieldDir.empty()) {
-        const int need = ABUB_FIELD_CELL + 2 * field.radius;
-        int ncx = 0, ncy = 0, x0 = 0, y0 = 0;
-        if (pl.W > 0) {
-            abub_frame_cells_grid(pl.W, pl.H, field.radius, &ncx, &ncy, &x0, &y0);
-            if (ncx == 0 || ncy == 0)
-                throw std::runtime_error("survey: a shift field at radius " + std::to_string(field.radius) + " needs frames of at least " +
-                                         std::to_string(need) + "x" + std::to_string(need) + ", the run's are " + std::to_string(pl.W) + "x" +
-                                         std::to_string(pl.H));
-        }
-        pl.fieldR = field.radius;
-        pl.fieldCells = (size_t)ncx * ncy;
-        pl.fieldHostUs = &fieldHostUs;
+    pl.hostUs = hostUs;
+    if (want[SurveyShiftProduct]) {
+        const int need = 2 * rq.shiftRadius + 1;
+        needFrames(pl, pl.W >= need && pl.H >= need, "a shift search", "needs", rq.shiftRadius, need);
+        pl.shiftR = rq.shiftRadius;
     }
-    std::atomic<long long> lightHostUs{0};
-    if (!lightDir.empty()) {
-        if (pl.W > 0) {
-            abub_frame_cells_grid(pl.W, pl.H, field.radius, &pl.lightNcx, &pl.lightNcy, &pl.lightX0, &pl.lightY0);
-            if (pl.lightNcx == 0 || pl.lightNcy == 0) {
-                const int need = ABUB_FIELD_CELL + 2 * field.radius;
-                throw std::runtime_error("survey: the light records at radius " + std::to_string(field.radius) + " need frames of at least " +
-                                         std::to_string(need) + "x" + std::to_string(need) + ", the run's are " + std::to_string(pl.W) + "x" +
-                                         std::to_string(pl.H));
+    if (wantCells) {
+        pl.cellR = rq.cellRadius;
+        CellGrid &g = pl.grid;
+        if (pl.W > 0)
+            abub_frame_cells_grid(pl.W, pl.H, pl.cellR, &g.ncx, &g.ncy, &g.x0, &g.y0);
+        static const char *const what[SurveyProducts][2] = {
+            {nullptr, nullptr}, {"a shift field", "needs"}, {"the light records", "need"}, {"the focus records", "need"}};
+        for (int p = SurveyFieldProduct; p < SurveyProducts; ++p)
+            if (want[p]) // (a frame without a whole cell)
+                needFrames(pl, g.cells() > 0, what[p][0], what[p][1], pl.cellR, ABUB_FIELD_CELL + 2 * pl.cellR);
+        // (the model's sums depend on the camera alone: once, here, for both routes)
+        for (size_t c = 0; c < pl.models.size(); ++c) {
+            SurveyModel &m = pl.models[c];
+            if (m.trained && want[SurveyLightProduct]) {
+                m.light.resize(g.cells() * LightModelWords);
+                lightModelHost(pl.mu[c], pl.sigma6[c].data(), pl.W, pl.H, g.x0, g.y0, g.ncx, g.ncy, m.light.data());
+            }
+            if (m.trained && want[SurveyFocusProduct]) {
+                m.focus.resize(g.cells() * FocusModelWords);
+                focusModelHost(pl.mu[c], pl.sigma6[c].data(), pl.W, pl.H, g.x0, g.y0, g.ncx, g.ncy, m.focus.data());
             }
         }
-        pl.light = true;
-        pl.lightHostUs = &lightHostUs;
-        for (size_t c = 0; c < pl.models.size(); ++c) // (the model's sums depend on the camera alone: once, here, for both routes)
-            if (pl.models[c].trained) {
-                pl.models[c].light.resize((size_t)pl.lightNcx * pl.lightNcy * LightModelWords);
-                lightModelHost(pl.mu[c], pl.sigma6[c].data(), pl.W, pl.H, pl.lightX0, pl.lightY0, pl.lightNcx, pl.lightNcy,
-                               pl.models[c].light.data());
-            }
-    }
-    std::atomic<long long> focusHostUs{0};
-    if (!focusDir.empty()) {
-        if (pl.W > 0) {
-            abub_frame_cells_grid(pl.W, pl.H, field.radius, &pl.focusNcx, &pl.focusNcy, &pl.focusX0, &pl.focusY0);
-            if (pl.focusNcx == 0 || pl.focusNcy == 0) {
-                const int need = ABUB_FIELD_CELL + 2 * field.radius;
-                throw std::runtime_error("survey: the focus records at radius " + std::to_string(field.radius) + " need frames of at least " +
-                                         std::to_string(need) + "x" + std::to_string(need) + ", the run's are " + std::to_string(pl.W) + "x" +
-                                         std::to_string(pl.H));
-            }
-        }
-        pl.focus = true;
-        pl.focusHostUs = &focusHostUs;
-        for (size_t c = 0; c < pl.models.size(); ++c) // (the model's sums depend on the camera alone: once, here, for both routes)
-            if (pl.models[c].trained) {
-                pl.models[c].focus.resize((size_t)pl.focusNcx * pl.focusNcy * FocusModelWords);
-                focusModelHost(pl.mu[c], pl.sigma6[c].data(), pl.W, pl.H, pl.focusX0, pl.focusY0, pl.focusNcx, pl.focusNcy,
-                               pl.models[c].focus.data());
-            }
     }
     std::unique_ptr<HostPlanes> hostPlanes;
     std::vector<uint32_t> devPlanes;
@@ -1777,10 +1532,8 @@ int surveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCam
     st.H = pl.H;
     for (const SurveyModel &m : pl.models)
         st.modelCams += m.trained;
-    // (abub_frame_shift_dev, abub_frame_shift_cells_dev, abub_frame_light_cells_dev and abub_frame_focus_cells_dev take sides
-    // of up to 65535: a larger run with a shift file, a field, light or focus records is the host route's whole)
-    if (device >= 0 && pl.W > 0 && decodersTakeWidth(pl.W) &&
-        ((!pl.shiftR && !pl.fieldR && !pl.light && !pl.focus) || (pl.W <= 65535 && pl.H <= 65535))) {
+    // (the products' kernels take sides of up to 65535: a larger run with one of them is the host route's whole)
+    if (device >= 0 && pl.W > 0 && decodersTakeWidth(pl.W) && ((!want[SurveyShiftProduct] && !wantCells) || (pl.W <= 65535 && pl.H <= 65535))) {
         st.device = device;
         deviceFrames(parser, pl, nthreads, device, st, devPlanes);
     } else
@@ -1790,35 +1543,29 @@ int surveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCam
         ++*counter[r.state];
         ++st.frames;
         ++(r.onKernel ? st.framesKernel : st.framesHostRoute);
-        if (r.state == SurveyRow::Ok && r.hasShift)
-            ++(r.shiftOnKernel ? st.shiftFramesKernel : st.shiftFramesHost);
-        if (r.state == SurveyRow::Ok && r.hasField)
-            ++(r.fieldOnKernel ? st.fieldFramesKernel : st.fieldFramesHost);
-        if (r.state == SurveyRow::Ok && r.hasLight)
-            ++(r.lightOnKernel ? st.lightFramesKernel : st.lightFramesHost);
-        if (r.state == SurveyRow::Ok && r.hasFocus)
-            ++(r.focusOnKernel ? st.focusFramesKernel : st.focusFramesHost);
+        for (int p = 0; p < SurveyProducts; ++p)
+            if (r.state == SurveyRow::Ok && r.has((SurveyProduct)p))
+                ++(r.has((SurveyProduct)p) == SurveyRow::Kernel ? st.product[p].framesKernel : st.product[p].framesHost);
     }
-    st.shiftHost_s = (double)shiftHostUs * 1e-6;
-    st.fieldHost_s = (double)fieldHostUs * 1e-6;
-    st.lightHost_s = (double)lightHostUs * 1e-6;
-    st.focusHost_s = (double)focusHostUs * 1e-6;
-    if (!reportPath.empty()) {
-        const std::string text = SurveyReport(pl.models, pl.rows);
-        if (!writeFile(reportPath, (const unsigned char *)text.data(), text.size()))
-            throw std::runtime_error("survey: cannot write " + reportPath);
-    }
-    if (!shift.path.empty()) {
-        const std::string text = ShiftReport(shift.radius, pl.models, pl.rows);
-        if (!writeFile(shift.path, (const unsigned char *)text.data(), text.size()))
-            throw std::runtime_error("survey: cannot write " + shift.path);
-    }
-    if (!fieldDir.empty())
-        writeField(fieldDir, field.radius, pl);
-    if (!lightDir.empty())
-        writeLight(lightDir, field.radius, pl);
-    if (!focusDir.empty())
-        writeFocus(focusDir, field.radius, pl);
+    for (int p = 0; p < SurveyProducts; ++p)
+        st.product[p].host_s = (double)hostUs[p] * 1e-6;
+    const auto writeText = [](const std::string &path, const std::string &text) {
+        if (!writeFile(path, (const unsigned char *)text.data(), text.size()))
+            throw std::runtime_error("survey: cannot write " + path);
+    };
+    if (!rq.reportPath.empty())
+        writeText(rq.reportPath, SurveyReport(pl.models, pl.rows));
+    if (want[SurveyShiftProduct])
+        writeText(rq.shiftPath, ShiftReport(rq.shiftRadius, pl.models, pl.rows));
+    if (want[SurveyFieldProduct]) // (no model file)
+        writeCells(fieldDir, "field", SurveyFieldProduct, pl, FieldRecordWords, &SurveyRow::field, nullptr, 0, &SurveyModel::light,
+                   FieldReport(pl.cellR, pl.W, pl.H, pl.models, pl.rows));
+    if (want[SurveyLightProduct])
+        writeCells(lightDir, "light", SurveyLightProduct, pl, LightRecordWords, &SurveyRow::light, "<i4", LightModelWords, &SurveyModel::light,
+                   LightReport(pl.cellR, pl.W, pl.H, pl.models, pl.rows));
+    if (want[SurveyFocusProduct])
+        writeCells(focusDir, "focus", SurveyFocusProduct, pl, FocusRecordWords, &SurveyRow::focus, "<i8", FocusModelWords, &SurveyModel::focus,
+                   FocusReport(pl.cellR, pl.W, pl.H, pl.models, pl.rows));
     if (hostPlanes) {
         const double t1 = nowMs();
         st.planeRowsHost = hostPlanes->rows;
@@ -1834,28 +1581,6 @@ int surveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCam
     if (rows)
         *rows = std::move(pl.rows);
     return rc;
-}
-
-} // namespace
-
-int SurveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCams, const std::string &imageFormat,
-              const std::string &reportPath, int nthreads, SurveyStats *stats, std::vector<SurveyRow> *rows,
-              std::vector<SurveyModel> *models, const SurveyPlanes &planes, const SurveyShift &shift, const SurveyField &field,
-              const SurveyLight &light, const SurveyFocus &focus)
-{
-    return surveyRun(parser, trainers, numCams, imageFormat, reportPath, nthreads, -1, stats, rows, models, planes, shift, field, light,
-                     focus);
-}
-
-int SurveyRunDevice(Parser *parser, const std::vector<Trainer *> &trainers, int numCams, const std::string &imageFormat,
-                    const std::string &reportPath, int nthreads, int device, SurveyStats *stats, std::vector<SurveyRow> *rows,
-                    std::vector<SurveyModel> *models, const SurveyPlanes &planes, const SurveyShift &shift, const SurveyField &field,
-                    const SurveyLight &light, const SurveyFocus &focus)
-{
-    if (device < 0)
-        throw std::runtime_error("survey: no such HIP device: " + std::to_string(device));
-    return surveyRun(parser, trainers, numCams, imageFormat, reportPath, nthreads, device, stats, rows, models, planes, shift, field,
-                     light, focus);
 }
 
 } // namespace abub

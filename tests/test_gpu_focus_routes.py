@@ -8,9 +8,9 @@ import os
 import pytest
 
 from autobub3hs_amd import host
-from test_focus_abi import (F, NEV, SOFT, TOTAL, UNEVEN, W, expected_focus, focus_cli, half_trained, make_focus_run, read_focus,  # noqa: F401
+from test_focus_abi import (F, H, NEV, SOFT, TOTAL, UNEVEN, W, expected_focus, focus_cli, half_trained, make_focus_run, read_focus,  # noqa: F401
                             same_focus, soft)
-from test_survey_abi import NCAMS, RUN_ID, Sources, survey_cli
+from test_survey_abi import NCAMS, RUN_ID, Sources, survey_cli, trained_models
 
 pytestmark = pytest.mark.gpu
 
@@ -130,6 +130,50 @@ def test_the_kernel_sums_every_frame_with_a_model(half_trained, tmp_path, monkey
         assert same(got, exp) and sorted(got[3]) == ["cam1_focus.npy", "cam1_focus_model.npy", "focus.txt"]
         assert got[0]["focus_frames_kernel" if device == 0 else "focus_frames_host"] == F * NEV - 1
         assert got[0]["focus_frames_host" if device == 0 else "focus_frames_kernel"] == 0
+
+
+def test_all_five_products_on_one_job_list(half_trained, tmp_path, monkeypatch):  # noqa: F811
+    """All five products at once where camera 0 has no model, so that the list of the jobs with a model is shorter than the
+    batch's: in batches of one row (a batch of camera 0 has no such job and makes no launch), then in batches of 7 with the
+    field's leg split job by job.  Every file is the host route's, byte for byte; each product's kernel made camera 1's ok
+    rows, and the field counts one launch per chunk."""
+    rd, frames = half_trained
+    models = trained_models(rd, W, H)
+    assert models[0] is None and models[1] is not None
+    keys = sorted(frames)  # (survey order: event, camera, name)
+    has_job = [frames[k] is not None and models[k[1]] is not None for k in keys]
+    assert sum(has_job) == F * NEV - 1
+    products = ("shift", "field", "light", "focus")
+
+    def all_five(tag, device):
+        out = {k: str(tmp_path / f"{k}_{tag}") for k in ("planes", "field", "light", "focus")}
+        run = host.Run("raw", rd + "/", "Images")
+        try:
+            res, text = run.survey(str(tmp_path / f"report_{tag}.txt"), nthreads=4, ncams=NCAMS, device=device,
+                                   shift=str(tmp_path / f"shift_{tag}.txt"), **out)
+        finally:
+            run.close()
+        files = {f"{k}/{f}": open(os.path.join(d, f), "rb").read() for k, d in out.items() for f in sorted(os.listdir(d))}
+        for k in ("report", "shift"):
+            files[k] = open(str(tmp_path / f"{k}_{tag}.txt"), "rb").read()
+        return res, text, files
+
+    set_env(monkeypatch, {})
+    cpu = all_five("cpu", None)
+    assert all(cpu[0][f"{k}_frames_host"] == sum(has_job) and cpu[0][f"{k}_launches"] == 0 for k in products)
+    assert {"field/field.txt", "light/cam1_light_model.npy", "focus/cam1_focus.npy", "planes/activity.txt"} <= set(cpu[2])
+    for tag, env, batch, chunk in (("b1", {"ABUB_SURVEY_BATCH": "1"}, 1, None),
+                                   ("b7", {"ABUB_SURVEY_BATCH": "7", "ABUB_FIELD_CHUNK": "1"}, 7, 1)):
+        set_env(monkeypatch, env)
+        res, text, files = all_five(tag, 0)
+        assert text == cpu[1] and sorted(files) == sorted(cpu[2]), tag
+        assert all(files[f] == cpu[2][f] for f in files), [f for f in files if files[f] != cpu[2][f]]
+        per_batch = [sum(has_job[i:i + batch]) for i in range(0, TOTAL, batch)]
+        assert res["device"] == 0 and res["batches"] == len(per_batch), tag
+        for k in products:
+            assert res[f"{k}_frames_kernel"] == sum(has_job) and res[f"{k}_frames_host"] == 0, (tag, k)
+        assert res["shift_launches"] == res["light_launches"] == res["focus_launches"] == sum(n > 0 for n in per_batch), tag
+        assert res["field_launches"] == (sum(per_batch) if chunk else sum(n > 0 for n in per_batch)), tag
 
 
 def test_each_decoder_knob_gives_the_same_bytes(soft, want, tmp_path, monkeypatch):  # noqa: F811
