@@ -1,7 +1,7 @@
 // abub_stats.hip -- per-frame statistics of resident frames: abub_frame_stats_dev (include/abub_hip.h, DESIGN section 3,
 // "Surveying a run"); below it the per-pixel planes (abub_pixel_activity_dev), the shift search (abub_frame_shift_dev) and
-// the per-cell shift field (abub_frame_shift_cells_dev), the per-cell light record (abub_frame_light_cells_dev) and the
-// per-cell edge agreement (abub_frame_focus_cells_dev), each under a header of its own.  What a byte loop over a decoded frame does on a host thread (host/survey.cpp frameStatsHost, the
+// the per-cell shift field (abub_frame_shift_cells_dev), the per-cell light record (abub_frame_light_cells_dev), the
+// per-cell edge agreement (abub_frame_focus_cells_dev) and the per-cell noise record (abub_frame_noise_cells_dev), each under a header of its own.  What a byte loop over a decoded frame does on a host thread (host/survey.cpp frameStatsHost, the
 // definition): per job the grey-level range, sum, sum of squares, black and saturated pixels of the frame, and against a
 // model (mu, sigma6) and a reference frame the count and sum of sat(|p - m| - s) and of sat(|p - r| - s).
 //
@@ -1237,6 +1237,134 @@ extern "C" int abub_frame_focus_cells_dev(const uint8_t *frames, size_t frames_b
     k_focus_cells<<<grid, FR_THREADS, 0, (hipStream_t)stream>>>(frames, (uint64_t)frames_bytes, mu, (uint64_t)model_bytes, jobs, njobs,
                                                                 (uint32_t)W, (uint32_t)H, (uint32_t)ncx, (uint32_t)x0, (uint32_t)y0, status,
                                                                 rec);
+    HIPCHK(hipGetLastError());
+    return ABUB_OK;
+}
+
+// ---- per-cell frame-pair noise record: abub_frame_noise_cells_dev ("Surveying a run for noise changes") --
+// Per cell of FC_CELL x FC_CELL pixels on a grid the caller gives (x0, y0, ncx, ncy: abub_frame_cells_grid's, or any other
+// that lies inside the frame) six i32 over the cell's pixels p of the frame, r of its reference frame and s of sigma6, with
+// d = p - r (host/survey.cpp noiseCellsHost, the definition):
+//   rec[((j ncy + cy) ncx + cx) 6 + 0 .. 5] = the pixels with |d| > s, the pixels where p or r is 0 or 255, sum d and sum d^2
+//   over the pixels with |d| <= s (the inside ones), sum |d| and sum d^2 over all.
+//
+// k_light_cells' structure with a third stream: the grid is cells x jobs, a block of four waves owns one cell of one job at
+// a time and writes its six words once with plain stores (the block of cell 0 writes the job's status word); lane l owns
+// dword l & 31 of the rows 8 k + 2 w + (l >> 5), k < 16; p, r and s come straight into registers through sh_load4.  Per
+// dword: sum |d| is v_sad_u8(p, r); sum d^2 = p.p + r.r - 2 p.r from three v_dot4_u32_u8, exact mod 2^32.  sat(|d| - s) of
+// the four bytes comes as u16 pairs (widen, pk_absdiff, pk_subsat); pk_min1 makes each 1 where the pixel is over, v_perm
+// packs the four into the bytes of a dword `over`, and (over ^ 0x01010101) * 0xff is 0xff in the bytes of the inside pixels
+// (a byte is 0 or 1 times 255: no carry).  With P = p & mask and R = r & mask an outside pixel contributes 0 - 0, so the
+// inside sum of d is sad(P, 0) - sad(R, 0) and that of d^2 P.P + R.R - 2 P.R.  The clipped pixels are the set bits of
+// lc_zero_bytes of p, ~p, r and ~r, OR-ed.
+// A lane sums 64 pixels: each of its nine partial sums is at most 64 * 2 * 65025 < 2^24.  A cell has 16384: the sums of
+// squares and of |d| at most 16384 * 255^2 = 1065369600 < 2^31, sum d a magnitude of at most 16384 * 255, the counts at most
+// 16384.  The differences (sum d, the two p.p + r.r - 2 p.r) are taken per lane in u32, where they are exact mod 2^32, and
+// the true value of every word fits i32; summed over the wave with shuffles, over the waves through 24 words of LDS.
+//
+// Bounds.  A job is read only if all three of its streams lie inside their buffers (nc_job_ok); otherwise E_RANGE and a
+// zero record, found alike by every block of the job.  The launcher admits only grids with x0 + 128 ncx <= W and
+// y0 + 128 ncy <= H, so every dword a lane loads lies wholly inside the W * H bytes of its stream; sh_load4 tests the index
+// against W * H besides.  Stores: status[j] and rec[(j * cells + cell) * 6 + t], j < njobs, cell < cells, t < 6.
+namespace {
+
+#define NC_WORDS 6u
+
+__device__ __forceinline__ bool nc_job_ok(const abub_stat_job &jb, uint64_t frames_bytes, uint64_t model_bytes, uint64_t P)
+{
+    return frame_in_range(jb.cur, frames_bytes, P) && frame_in_range(jb.ref, frames_bytes, P) && frame_in_range(jb.model, model_bytes, P);
+}
+
+__global__ __launch_bounds__(FR_THREADS) void k_noise_cells(const uint8_t *frames, uint64_t frames_bytes, const uint8_t *sigma6,
+                                                            uint64_t model_bytes, const abub_stat_job *__restrict__ jobs, int njobs,
+                                                            uint32_t W, uint32_t H, uint32_t ncx, uint32_t x0, uint32_t y0,
+                                                            uint32_t *__restrict__ status, uint32_t *__restrict__ rec)
+{
+    __shared__ uint32_t part[FR_THREADS / 64][NC_WORDS];
+    const uint64_t P = (uint64_t)W * H;
+    const uint32_t cell = blockIdx.x, cells = gridDim.x;
+    const uint32_t xc = x0 + (cell % ncx) * FC_CELL, yc = y0 + (cell / ncx) * FC_CELL; // the cell's first pixel
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t first = 2u * wave + (lane >> 5), col = lane & 31u;
+    for (uint32_t j = blockIdx.y; j < (uint32_t)njobs; j += gridDim.y) {
+        const abub_stat_job jb = jobs[j];
+        const bool ok = nc_job_ok(jb, frames_bytes, model_bytes, P); // (the same in every thread of every block of the job)
+        uint32_t *out = rec + ((uint64_t)j * cells + cell) * NC_WORDS;
+        if (cell == 0u && threadIdx.x == 0u)
+            status[j] = ok ? 0u : (uint32_t)ABUB_SHIFT_E_RANGE;
+        if (!ok) {
+            if (threadIdx.x < NC_WORDS)
+                out[threadIdx.x] = 0u;
+            continue;
+        }
+        const uint8_t *p = frames + jb.cur, *q = frames + jb.ref, *sg = sigma6 + jb.model;
+        uint32_t nOver = 0, nClip = 0, inP = 0, inR = 0, inSq = 0, inPr = 0, sad = 0, allSq = 0, allPr = 0;
+#pragma unroll
+        for (uint32_t r = 0; r < FC_ROWS; ++r) {
+            const uint64_t i = (uint64_t)(yc + r * 8u + first) * W + xc + 4u * col;
+            const uint32_t a = sh_load4(p, i, P), b = sh_load4(q, i, P), s = sh_load4(sg, i, P);
+            sad = __builtin_amdgcn_sad_u8(a, b, sad);
+            allSq = __builtin_amdgcn_udot4(a, a, allSq, false);
+            allSq = __builtin_amdgcn_udot4(b, b, allSq, false);
+            allPr = __builtin_amdgcn_udot4(a, b, allPr, false);
+            const uint32_t lo = pk_min1(pk_subsat(pk_absdiff(widen_lo(a), widen_lo(b)), widen_lo(s)));
+            const uint32_t hi = pk_min1(pk_subsat(pk_absdiff(widen_hi(a), widen_hi(b)), widen_hi(s)));
+            const uint32_t over = __builtin_amdgcn_perm(hi, lo, 0x06040200u); // 1 in the byte of every pixel with |d| > s
+            const uint32_t mask = (over ^ 0x01010101u) * 0xffu;
+            const uint32_t am = a & mask, bm = b & mask;
+            nOver += (uint32_t)__builtin_popcount(over);
+            inP = __builtin_amdgcn_sad_u8(am, 0u, inP);
+            inR = __builtin_amdgcn_sad_u8(bm, 0u, inR);
+            inSq = __builtin_amdgcn_udot4(am, am, inSq, false);
+            inSq = __builtin_amdgcn_udot4(bm, bm, inSq, false);
+            inPr = __builtin_amdgcn_udot4(am, bm, inPr, false);
+            nClip += (uint32_t)__builtin_popcount(lc_zero_bytes(a) | lc_zero_bytes(~a) | lc_zero_bytes(b) | lc_zero_bytes(~b));
+        }
+        uint32_t acc[NC_WORDS] = {nOver, nClip, inP - inR, inSq - 2u * inPr, sad, allSq - 2u * allPr};
+#pragma unroll
+        for (int s = 32; s > 0; s >>= 1)
+#pragma unroll
+            for (uint32_t o = 0; o < NC_WORDS; ++o)
+                acc[o] += (uint32_t)__shfl_xor(acc[o], s);
+        if (lane == 0u) {
+#pragma unroll
+            for (uint32_t o = 0; o < NC_WORDS; ++o)
+                part[wave][o] = acc[o];
+        }
+        __syncthreads();
+        if (threadIdx.x < NC_WORDS) {
+            uint32_t v = part[0][threadIdx.x];
+#pragma unroll
+            for (int w = 1; w < FR_THREADS / 64; ++w)
+                v += part[w][threadIdx.x];
+            out[threadIdx.x] = v;
+        }
+        __syncthreads(); // (part is written again for the block's next job)
+    }
+}
+
+} // namespace
+
+extern "C" int abub_frame_noise_cells_dev(const uint8_t *frames, size_t frames_bytes, const uint8_t *sigma6, size_t model_bytes,
+                                          const abub_stat_job *jobs, int njobs, int W, int H, int x0, int y0, int ncx, int ncy,
+                                          uint32_t *status, int32_t *rec, void *stream)
+{
+    if (!frames || !sigma6 || !jobs || !status || !rec || njobs < 0)
+        return set_err(ABUB_E_INVALID, "abub_frame_noise_cells_dev: null pointer or negative count");
+    if (W < ABUB_FIELD_CELL || W > 65535 || H < ABUB_FIELD_CELL || H > 65535)
+        return set_err(ABUB_E_INVALID, "abub_frame_noise_cells_dev: W and H must be in [128, 65535]");
+    // (ncx, ncy <= 511 once the sides are bounded, so the sums below cannot overflow an int)
+    if (ncx < 1 || ncy < 1 || ncx > W / ABUB_FIELD_CELL || ncy > H / ABUB_FIELD_CELL || x0 < 0 || y0 < 0 ||
+        x0 > W - ABUB_FIELD_CELL * ncx || y0 > H - ABUB_FIELD_CELL * ncy)
+        return set_err(ABUB_E_INVALID, "abub_frame_noise_cells_dev: the grid of whole cells must lie inside the frame");
+    if (((uintptr_t)jobs & 7) || (((uintptr_t)status | (uintptr_t)rec) & 3))
+        return set_err(ABUB_E_INVALID, "abub_frame_noise_cells_dev: jobs must be 8-byte aligned, status and rec 4-byte aligned");
+    if (njobs == 0)
+        return ABUB_OK;
+    const dim3 grid((unsigned)(ncx * ncy), (unsigned)(njobs < 65535 ? njobs : 65535)); // (at most 511 * 511 cells)
+    k_noise_cells<<<grid, FR_THREADS, 0, (hipStream_t)stream>>>(frames, (uint64_t)frames_bytes, sigma6, (uint64_t)model_bytes, jobs, njobs,
+                                                                (uint32_t)W, (uint32_t)H, (uint32_t)ncx, (uint32_t)x0, (uint32_t)y0, status,
+                                                                (uint32_t *)rec);
     HIPCHK(hipGetLastError());
     return ABUB_OK;
 }

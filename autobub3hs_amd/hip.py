@@ -685,18 +685,18 @@ def frame_stats(frames, jobs, frame_bytes, mu=None, sigma6=None, frames_bytes=No
 SHIFT_E_RANGE = 1
 
 
-def _model_jobs(entry, frames, mu, jobs, args, frames_bytes, model_bytes, status, out, shape, dtype, view):
-    """The shared body of frame_shift, frame_shift_cells, frame_light_cells and frame_focus_cells, whose entries take
-    (frames, frames_bytes, mu, model_bytes, jobs, n, *args, status, out, stream): the [n, 2] jobs tensor with a spare row
-    behind it, a new status tensor preset to 0x5A5A5A5A and a new `out` of `dtype` preset to -1 where none is given, the
+def _model_jobs(entry, frames, mu, jobs, args, frames_bytes, model_bytes, status, out, shape, dtype, view, job_words=2):
+    """The shared body of frame_shift, frame_shift_cells, frame_light_cells, frame_focus_cells and frame_noise_cells, whose
+    entries take (frames, frames_bytes, mu, model_bytes, jobs, n, *args, status, out, stream): the [n, job_words] jobs tensor
+    (a negative offset: UINT64_MAX) with a spare row behind it, a new status tensor preset to 0x5A5A5A5A and a new `out` of `dtype` preset to -1 where none is given, the
     call checked -> (status int64 [n] on the host, out as `view` [n, *shape] on the host)."""
     import numpy as np
     _need_cuda(frames, mu, status, out)
-    offs = np.array([[int(v) for v in row] for row in jobs], dtype=np.uint64).reshape(-1, 2)
+    offs = np.array([[int(v) & STAT_NONE for v in row] for row in jobs], dtype=np.uint64).reshape(-1, job_words)
     n = len(offs)
     words = n * int(np.prod([max(s, 0) for s in shape]))
     dev = frames.device
-    d_jobs = torch.from_numpy(np.concatenate([offs, np.zeros((1, 2), np.uint64)]).view(np.int64)).to(dev)
+    d_jobs = torch.from_numpy(np.concatenate([offs, np.zeros((1, job_words), np.uint64)]).view(np.int64)).to(dev)
     if status is None:
         status = torch.full((max(n, 1),), 0x5A5A5A5A, dtype=torch.int32, device=dev)
     if out is None:
@@ -765,6 +765,20 @@ def frame_focus_cells(frames, mu, jobs, W, H, x0, y0, ncx, ncy, frames_bytes=Non
     [n, ncy, ncx, 5] on the host: the sums of gx^2, gy^2, gx hx and gy hy, the pixels with p == 0 or p == 255)."""
     return _model_jobs("abub_frame_focus_cells_dev", frames, mu, jobs, (int(W), int(H), int(x0), int(y0), int(ncx), int(ncy)),
                        frames_bytes, model_bytes, status, rec, (int(ncy), int(ncx), FOCUS_WORDS), torch.int32, "int32")
+
+
+NOISE_WORDS = 6  # ABUB_NOISE_WORDS of include/abub_hip.h
+
+
+def frame_noise_cells(frames, sigma6, jobs, W, H, x0, y0, ncx, ncy, frames_bytes=None, model_bytes=None, status=None, rec=None):
+    """abub_frame_noise_cells_dev: frames and sigma6 u8 device tensors (any shape), jobs: [n, 3] byte offsets (cur, ref,
+    model) of each job's W x H frame and reference frame in `frames` and of its plane in `sigma6` (any alignment; STAT_NONE
+    or a negative number is out of range like any other offset past the buffer); the grid of ncx x ncy cells of 128 x 128
+    pixels from (x0, y0); rec: int32 device tensor of at least n * ncy * ncx * 6 words, written in place (None: a new one)
+    -> (status int64 [n] on the host: 0 or SHIFT_E_RANGE; the records, int32 [n, ncy, ncx, 6] on the host: n_over, n_clip,
+    s1_in, s2_in, sad, s2_all)."""
+    return _model_jobs("abub_frame_noise_cells_dev", frames, sigma6, jobs, (int(W), int(H), int(x0), int(y0), int(ncx), int(ncy)),
+                       frames_bytes, model_bytes, status, rec, (int(ncy), int(ncx), NOISE_WORDS), torch.int32, "int32", job_words=3)
 
 
 ACT_PLANES = ("n_zero","n_sat", "n_out", "sum_out", "n_moved", "sum_moved")

@@ -84,6 +84,13 @@ SIGNATURES = {
     "abh_focus_model_host": (_i, [_u8p, _u8p, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_int64)]),
     "abh_focus_cell": (None, [C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_longlong)]),
     "abh_focus_frame": (None, [C.POINTER(C.c_int32), C.POINTER(C.c_int64), _i, C.POINTER(C.c_longlong)]),
+    "abh_run_survey_noise": (_i, [_vp, _s, _s, _s, _i, _s, _i, _s, _s, _s, _i, _i, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.c_char_p, _i]),
+    "abh_run_survey_noise_dev": (_i, [_vp, _s, _s, _s, _i, _s, _i, _s, _s, _s, _i, _i, _i, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.c_char_p,
+                                      _i]),
+    "abh_noise_cells_host": (_i, [_u8p, _u8p, _u8p, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_int32)]),
+    "abh_noise_model_host": (_i, [_u8p, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_int32), _i, C.POINTER(C.c_int64)]),
+    "abh_noise_cell": (None, [C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_longlong)]),
+    "abh_noise_frame": (None, [C.POINTER(C.c_int32), C.POINTER(C.c_int64), _i, C.POINTER(C.c_longlong)]),
     "abh_field_grid": (_i, [_i, _i, _i, C.POINTER(_i)]),
     "abh_field_cells_host": (_i, [_u8p, _u8p, _i, _i, _i, _u32p, C.POINTER(C.c_int32)]),
     "abh_activity_add_host": (None, [C.POINTER(C.c_uint32), _u8p, _u8p, _u8p, _u8p, C.c_uint64]),
@@ -463,7 +470,7 @@ class Run:
                     "W", "H", "batches", "model_cams")
 
     def survey(self, path=None, nthreads=16, ncams=4, device=None, planes=None, shift=None, shift_radius=4, field=None,
-               field_radius=4, light=None, focus=None):
+               field_radius=4, light=None, focus=None, noise=None):
         """abub3hs --survey of this run (opened from a directory or an archive): the run is listed and trained as for
         detect, then every frame of cameras 0 .. ncams-1 is measured without analysing any; the report (DESIGN section 3,
         "Surveying a run") is written to `path` (None: it is not written).  device=None: host threads (cv::imdecode and
@@ -493,20 +500,26 @@ class Run:
         "Surveying a run for lost focus"): cam<c>_focus.npy, cam<c>_focus_model.npy and focus.txt, the same rows compared
         per cell of the field's grid at field_radius (whether or not field or light is given), the same bytes on both routes;
         the stats then also have focus_frames_kernel / focus_frames_host, focus_launches and the legs focus_s and
-        focus_host_s.  Nothing else changes."""
+        focus_host_s.  Nothing else changes.
+        noise (--survey-noise): the directory (the CLI's DIR/<run_ID>) that gets the per-cell noise records (DESIGN section 3,
+        "Surveying a run for noise changes"): cam<c>_noise.npy, cam<c>_noise_model.npy and noise.txt, of the same rows those
+        whose reference frame (the frame two before) is another ok frame, each against that frame per cell of the field's
+        grid at field_radius, the same bytes on both routes; the stats then also have noise_frames_kernel /
+        noise_frames_host, noise_launches and the legs noise_s and noise_host_s.  Nothing else changes."""
         L = lib()
         st, pst = (C.c_double * 24)(), (C.c_double * 5)()
-        products = [(v, (C.c_double * 5)(), k) for v, k in ((shift, "shift"), (field, "field"), (light, "light"), (focus, "focus"))]
+        products = [(v, (C.c_double * 5)(), k) for v, k in ((shift, "shift"), (field, "field"), (light, "light"), (focus, "focus"),
+                                                                 (noise, "noise"))]
         cap = 1 << 16
         buf = C.create_string_buffer(cap)
         # the widest entry takes every product; a NULL path: that product is not made
-        to, pd, sp, fd, ld, od = (None if p is None else str(p).encode() for p in (path, planes, shift, field, light, focus))
-        args = (self._h, to, pd, sp, int(shift_radius), fd, int(field_radius), ld, od, ncams, nthreads)
+        to, pd, sp, fd, ld, od, nd = (None if p is None else str(p).encode() for p in (path, planes, shift, field, light, focus, noise))
+        args = (self._h, to, pd, sp, int(shift_radius), fd, int(field_radius), ld, od, nd, ncams, nthreads)
         out = (st, pst, *(a for _, a, _ in products), buf, cap)
         if device is None:
-            rc = L.abh_run_survey_focus(*args, *out)
+            rc = L.abh_run_survey_noise(*args, *out)
         else:
-            rc = L.abh_run_survey_focus_dev(*args, int(device), *out)
+            rc = L.abh_run_survey_noise_dev(*args, int(device), *out)
         if rc not in (0, 1):
             raise RuntimeError(f"abh_run_survey rc={rc}: " + L.abh_last_error(self._h).decode())
         text = buf.value if st[23] < cap else L.abh_run_survey_report(self._h)
@@ -698,6 +711,63 @@ def focus_frame(rec, model):
     return {"rated": v[0], "clipped": v[1], "changed": v[2], "softer": v[3], "harder": v[4], "kind": FOCUS_KINDS[v[5]],
             "keep_milli": None if blind else v[6], "keep_min": None if blind else v[7], "keep_max": None if blind else v[8],
             "energy_milli": None if blind else v[9]}
+
+
+NOISE_STATES = ("clipped", "busy", "nobase", "noisy", "quiet", "same")
+NOISE_KINDS = ("blind", "busy", "steady", "noisy", "quiet", "uneven")
+
+
+def noise_cells_host(p, r, sigma6, x0, y0, ncx, ncy):
+    """abub::noiseCellsHost (host/survey.cpp), the definition of abub_frame_noise_cells_dev: the frame p, its reference
+    frame r and the plane sigma6, u8 [H, W], on the grid of ncx x ncy cells of 128 x 128 pixels from (x0, y0) -> int32
+    [ncy, ncx, 6]: n_over, n_clip, s1_in, s2_in, sad, s2_all of d = p - r."""
+    p, r, sigma6 = (np.ascontiguousarray(v, dtype=np.uint8) for v in (p, r, sigma6))
+    assert p.ndim == 2 and p.shape == r.shape == sigma6.shape
+    rec = np.zeros((max(ncy, 0), max(ncx, 0), 6), np.int32)
+    if lib().abh_noise_cells_host(p.ctypes.data_as(_u8p), r.ctypes.data_as(_u8p), sigma6.ctypes.data_as(_u8p), p.shape[1], p.shape[0],
+                                  int(x0), int(y0), int(ncx), int(ncy), rec.ctypes.data_as(_i32p)) != ncx * ncy or ncx * ncy <= 0:
+        raise ValueError(f"the grid {ncx}x{ncy} from ({x0}, {y0}) does not lie inside {p.shape[1]}x{p.shape[0]}")
+    return rec
+
+
+def noise_model_host(sigma6, recs, x0, y0, ncx, ncy):
+    """abub::noiseModelHost: the plane sigma6, u8 [H, W], and the records [n, ncy, ncx, 6] (n may be 0) of the camera's
+    rows at stack position 1 on the same grid -> int64 [ncy, ncx, 5]: BE, BN, B, the sum of sigma6^2, the pixels with
+    sigma6 == 0."""
+    sigma6 = np.ascontiguousarray(sigma6, dtype=np.uint8)
+    recs = np.ascontiguousarray(recs, dtype=np.int32).reshape(-1, max(ncy, 0), max(ncx, 0), 6)
+    assert sigma6.ndim == 2
+    rec = np.zeros((max(ncy, 0), max(ncx, 0), 5), np.int64)
+    if lib().abh_noise_model_host(sigma6.ctypes.data_as(_u8p), sigma6.shape[1], sigma6.shape[0], int(x0), int(y0), int(ncx), int(ncy),
+                                  recs.ctypes.data_as(_i32p) if len(recs) else None, len(recs),
+                                  rec.ctypes.data_as(_i64p)) != ncx * ncy or ncx * ncy <= 0:
+        raise ValueError(f"the grid {ncx}x{ncy} from ({x0}, {y0}) does not lie inside {sigma6.shape[1]}x{sigma6.shape[0]}")
+    return rec
+
+
+def noise_cell(rec, model):
+    """abub::noiseCell: what one cell's record [6] says against its model's [5] -> dict: state (a word of NOISE_STATES),
+    q_milli (None where the cell is not rated), all_milli, model_milli."""
+    rec = np.ascontiguousarray(rec, dtype=np.int32).reshape(6)
+    model = np.ascontiguousarray(model, dtype=np.int64).reshape(5)
+    out = (C.c_longlong * 4)()
+    lib().abh_noise_cell(rec.ctypes.data_as(_i32p), model.ctypes.data_as(_i64p), out)
+    v = list(out)
+    return {"state": NOISE_STATES[v[0]], "q_milli": v[1] if v[0] >= 3 else None, "all_milli": v[2], "model_milli": v[3]}
+
+
+def noise_frame(rec, model):
+    """abub::noiseFrame: what a frame's records [..., 6] say against the model's [..., 5] -> dict: rated, clipped, busy,
+    noisy, quiet, kind (a word of NOISE_KINDS), q_milli, q_min, q_max (None where noise.txt has '-') and all_milli."""
+    rec = np.ascontiguousarray(rec, dtype=np.int32).reshape(-1, 6)
+    model = np.ascontiguousarray(model, dtype=np.int64).reshape(-1, 5)
+    assert len(rec) == len(model)
+    out = (C.c_longlong * 10)()
+    lib().abh_noise_frame(rec.ctypes.data_as(_i32p), model.ctypes.data_as(_i64p), len(rec), out)
+    v = list(out)
+    none = v[0] == 0
+    return {"rated": v[0], "clipped": v[1], "busy": v[2], "noisy": v[3], "quiet": v[4], "kind": NOISE_KINDS[v[5]],
+            "q_milli": None if none else v[6], "q_min": None if none else v[7], "q_max": None if none else v[8], "all_milli": v[9]}
 
 
 def zip_write(path, entries):

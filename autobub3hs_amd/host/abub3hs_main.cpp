@@ -38,6 +38,7 @@ static std::string usage()
            "               [--survey-field DIR [--survey-field-radius R]]\n"
            "               [--survey-light DIR [--survey-field-radius R]]\n"
            "               [--survey-focus DIR [--survey-field-radius R]]\n"
+           "               [--survey-noise DIR [--survey-field-radius R]]\n"
            "Run the AutoBub3hs bubble finding algorithm on a PICO run (MI355X hot path)\n\n"
            "Required arguments:\n"
            "  -d, --data_dir = Dir\t\tpath to the directory in which the run folder/file is stored\n"
@@ -121,7 +122,7 @@ static std::string usage()
            "\t\t\t\tframes in which it moved; the same bytes with --survey-gpu; the report, the planes and the shift\n"
            "\t\t\t\tfile do not change\n"
            "  --survey-field-radius = R\twith --survey-field: the radius of the search in pixels, 1 to 8 (4); the frames must be at\n"
-           "\t\t\t\tleast 128 + 2 R wide and high; with --survey-light or --survey-focus, with or without\n"
+           "\t\t\t\tleast 128 + 2 R wide and high; with --survey-light, --survey-focus or --survey-noise, with or without\n"
            "\t\t\t\t--survey-field: the radius that places the cells\n"
            "  --survey-light = Dir\t\twith --survey: also sum the same frames per cell of the field's grid (the cells of\n"
            "\t\t\t\t--survey-field at --survey-field-radius, 4 unless given, whether or not the field is written) and\n"
@@ -146,6 +147,20 @@ static std::string usage()
            "\t\t\t\tcamera and for the run the counts of each kind and per cell the frames in which it changed; the\n"
            "\t\t\t\tsame bytes with --survey-gpu; the report, the planes, the shift file, the field and the light do\n"
            "\t\t\t\tnot change\n"
+           "  --survey-noise = Dir\t\twith --survey: also compare every such frame whose reference frame (the frame two before in\n"
+           "\t\t\t\tits stack) is another ok frame with that frame, per cell of the field's grid (at\n"
+           "\t\t\t\t--survey-field-radius, 4 unless given, whatever else is written), and write into Dir/<run_ID>/\n"
+           "\t\t\t\tcam<c>_noise.npy (i32 [frames, cells down, cells across, 6]: per cell, with d the difference of\n"
+           "\t\t\t\tthe two frames, the pixels with |d| over min(6 sigma, 255), the pixels at 0 or 255 in either\n"
+           "\t\t\t\tframe, the sums of d and d^2 over the other pixels, the sums of |d| and d^2 over all),\n"
+           "\t\t\t\tcam<c>_noise_model.npy (i64 [cells down, cells across, 5]: the baseline measured from the run's\n"
+           "\t\t\t\town second frames, its pixels and frames, the sum of min(6 sigma, 255)^2 and the pixels with sigma\n"
+           "\t\t\t\t0) and noise.txt: per frame how many cells are rated, clipped, busy (more than a quarter of the\n"
+           "\t\t\t\tpixels over), noisy (the variance over 1.5 times the baseline's) and quiet (under 0.667 times),\n"
+           "\t\t\t\tthe pooled variance ratio in thousandths and its range, the ratio of all pixels, and the frame's\n"
+           "\t\t\t\tkind (blind, busy, steady, noisy, quiet, uneven); per camera and for the run the counts of each\n"
+           "\t\t\t\tkind and per cell the frames in which it changed; the same bytes with --survey-gpu; nothing else\n"
+           "\t\t\t\tchanges\n"
            "Environment: ABUB_TRAIN_ON_GPU=0 trains the runs of a campaign with the host Trainer\n"
            "             ABUB_REPACK_BATCH=n (a test knob) lowers the frames per batch of --repack-gpu and --unpack-gpu to n; the files\n"
            "             are the same\n"
@@ -331,6 +346,8 @@ int main(int argc, char **argv)
     bool haveSurveyLight = false;
     std::string surveyFocusDir; // --survey-focus DIR: the survey's per-cell focus records go to DIR/<run_ID>/
     bool haveSurveyFocus = false;
+    std::string surveyNoiseDir; // --survey-noise DIR: the survey's per-cell noise records go to DIR/<run_ID>/
+    bool haveSurveyNoise = false;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i], v;
         auto value = [&](std::string &dst) {
@@ -465,6 +482,9 @@ int main(int argc, char **argv)
         } else if (a == "--survey-focus" || a.rfind("--survey-focus=", 0) == 0) {
             value(surveyFocusDir);
             haveSurveyFocus = true;
+        } else if (a == "--survey-noise" || a.rfind("--survey-noise=", 0) == 0) {
+            value(surveyNoiseDir);
+            haveSurveyNoise = true;
         } else if (a == "--per-event") {
             perEvent = true;
         } else if (a == "--peek" || a.rfind("--peek=", 0) == 0) {
@@ -509,8 +529,10 @@ int main(int argc, char **argv)
         {"--survey-field", haveSurveyField, "--survey", haveSurvey, &surveyFieldDir, "directory"},
         {"--survey-light", haveSurveyLight, "--survey", haveSurvey, &surveyLightDir, "directory"},
         {"--survey-focus", haveSurveyFocus, "--survey", haveSurvey, &surveyFocusDir, "directory"},
-        // (the light's and the focus' cells are the field's)
-        {"--survey-field-radius", haveFieldRadius, "--survey-field", haveSurveyField || haveSurveyLight || haveSurveyFocus, nullptr, nullptr},
+        {"--survey-noise", haveSurveyNoise, "--survey", haveSurvey, &surveyNoiseDir, "directory"},
+        // (the light's, the focus' and the noise's cells are the field's)
+        {"--survey-field-radius", haveFieldRadius, "--survey-field", haveSurveyField || haveSurveyLight || haveSurveyFocus || haveSurveyNoise,
+         nullptr, nullptr},
     };
     for (const auto &f : surveyFlags)
         if (f.have && !f.haveWith) {
@@ -714,6 +736,7 @@ int main(int argc, char **argv)
         rq.cellRadius = surveyFieldRadius;
         rq.lightDir = under(haveSurveyLight, surveyLightDir);
         rq.focusDir = under(haveSurveyFocus, surveyFocusDir);
+        rq.noiseDir = under(haveSurveyNoise, surveyNoiseDir);
         int rc = 1;
         try {
             abub::PreparedRun prep = abub::PrepareRun(sp, po, 0, nullptr, false);
@@ -757,7 +780,8 @@ int main(int argc, char **argv)
         } products[abub::SurveyProducts] = {{haveSurveyShift, "shift", rq.shiftPath.c_str(), "searched", rq.shiftRadius},
                                             {haveSurveyField, "field", rq.fieldDir.c_str(), "searched", rq.cellRadius},
                                             {haveSurveyLight, "light", rq.lightDir.c_str(), "summed", rq.cellRadius},
-                                            {haveSurveyFocus, "focus", rq.focusDir.c_str(), "summed", rq.cellRadius}};
+                                            {haveSurveyFocus, "focus", rq.focusDir.c_str(), "summed", rq.cellRadius},
+                                            {haveSurveyNoise, "noise", rq.noiseDir.c_str(), "summed", rq.cellRadius}};
         for (int p = 0; p < abub::SurveyProducts; ++p)
             if (products[p].have)
                 printf("survey-%s: %s: radius %d, %lld frames %s on the GPU in %d launches, %lld on the host; %s leg %.3f s, host "

@@ -416,10 +416,14 @@ const char *abh_run_verify_report(void *src)
 // for lost focus") written to focus_dir (the CLI's DIR/<run_ID>; NULL or empty: none) on the grid of field_radius, whether
 // or not field_dir or light_dir is given, and focus_stats (may be NULL, 5 values): the same five for
 // abub_frame_focus_cells_dev and focusCellsHost.
+// abh_run_survey_noise[_dev]: the same with the per-cell noise records (SurveyRequest::noiseDir; DESIGN section 3, "Surveying a run
+// for noise changes") written to noise_dir (the CLI's DIR/<run_ID>; NULL or empty: none) on the grid of field_radius, whether
+// or not any of the other three is given, and noise_stats (may be NULL, 5 values): the same five for
+// abub_frame_noise_cells_dev and noiseCellsHost.
 // what an entry's arguments ask for (a NULL path: none; the directory the run is read from is runSurvey's to fill in)
 static abub::SurveyRequest surveyRequest(const char *path, const char *planes_dir = nullptr, const char *shift_path = nullptr,
                                          int shift_radius = 4, const char *field_dir = nullptr, int field_radius = 4,
-                                         const char *light_dir = nullptr, const char *focus_dir = nullptr)
+                                         const char *light_dir = nullptr, const char *focus_dir = nullptr, const char *noise_dir = nullptr)
 {
     const auto str = [](const char *s) { return std::string(s ? s : ""); };
     abub::SurveyRequest rq;
@@ -431,11 +435,12 @@ static abub::SurveyRequest surveyRequest(const char *path, const char *planes_di
     rq.cellRadius = field_radius;
     rq.lightDir = str(light_dir);
     rq.focusDir = str(focus_dir);
+    rq.noiseDir = str(noise_dir);
     return rq;
 }
 static int runSurvey(void *r, abub::SurveyRequest rq, int ncams, int nthreads, int device, bool onDevice, char *report, int report_cap,
                      double *stats, double *plane_stats = nullptr, double *shift_stats = nullptr, double *field_stats = nullptr,
-                     double *light_stats = nullptr, double *focus_stats = nullptr)
+                     double *light_stats = nullptr, double *focus_stats = nullptr, double *noise_stats = nullptr)
 {
     Run *run = (Run *)r;
     try {
@@ -462,7 +467,7 @@ static int runSurvey(void *r, abub::SurveyRequest rq, int ncams, int nthreads, i
             throw std::runtime_error("survey: no such HIP device: " + std::to_string(device));
         const int rc = abub::SurveyRun(pr.parser.get(), pr.trainers, ncams, sp.imageFormat, rq, std::max(1, nthreads), onDevice ? device : -1,
                                        &st, &rows, &models);
-        double *const product_stats[abub::SurveyProducts] = {shift_stats, field_stats, light_stats, focus_stats};
+        double *const product_stats[abub::SurveyProducts] = {shift_stats, field_stats, light_stats, focus_stats, noise_stats};
         for (int p = 0; p < abub::SurveyProducts; ++p)
             if (product_stats[p]) {
                 const abub::ProductStats &ps = st.product[p];
@@ -572,6 +577,25 @@ int abh_run_survey_focus_dev(void *r, const char *path, const char *planes_dir, 
 {
     return runSurvey(r, surveyRequest(path, planes_dir, shift_path, shift_radius, field_dir, field_radius, light_dir, focus_dir), ncams,
                      nthreads, device, true, report, report_cap, stats, plane_stats, shift_stats, field_stats, light_stats, focus_stats);
+}
+int abh_run_survey_noise(void *r, const char *path, const char *planes_dir, const char *shift_path, int shift_radius, const char *field_dir,
+                         int field_radius, const char *light_dir, const char *focus_dir, const char *noise_dir, int ncams, int nthreads,
+                         double *stats, double *plane_stats, double *shift_stats, double *field_stats, double *light_stats,
+                         double *focus_stats, double *noise_stats, char *report, int report_cap)
+{
+    return runSurvey(r, surveyRequest(path, planes_dir, shift_path, shift_radius, field_dir, field_radius, light_dir, focus_dir, noise_dir),
+                     ncams, nthreads, -1, false, report, report_cap, stats, plane_stats, shift_stats, field_stats, light_stats, focus_stats,
+                     noise_stats);
+}
+int abh_run_survey_noise_dev(void *r, const char *path, const char *planes_dir, const char *shift_path, int shift_radius,
+                             const char *field_dir, int field_radius, const char *light_dir, const char *focus_dir, const char *noise_dir,
+                             int ncams, int nthreads, int device, double *stats, double *plane_stats, double *shift_stats,
+                             double *field_stats, double *light_stats, double *focus_stats, double *noise_stats, char *report,
+                             int report_cap)
+{
+    return runSurvey(r, surveyRequest(path, planes_dir, shift_path, shift_radius, field_dir, field_radius, light_dir, focus_dir, noise_dir),
+                     ncams, nthreads, device, true, report, report_cap, stats, plane_stats, shift_stats, field_stats, light_stats,
+                     focus_stats, noise_stats);
 }
 // the whole report of the last abh_run_survey[_dev] on the run (valid until the next query on it)
 const char *abh_run_survey_report(void *r)
@@ -710,6 +734,46 @@ void abh_focus_frame(const int32_t *rec, const int64_t *model, int cells, long l
 {
     const abub::FocusFrame f = abub::focusFrame(rec, model, (size_t)std::max(cells, 0));
     const long long v[10] = {f.rated, f.clipped, f.changed, f.softer, f.harder, f.kind, f.keepMilli, f.keepMin, f.keepMax, f.energyMilli};
+    std::memcpy(out, v, sizeof v);
+}
+
+// abub::noiseCellsHost on raw buffers: the W x H frame p against its reference frame r and the plane sigma6 on the grid of
+// ncx x ncy cells of 128 x 128 pixels from (x0, y0) -> rec[ncy * ncx * 6] (i32); returns the number of cells, or -1 (nothing
+// written) for a null pointer or a grid that does not lie inside the frame
+int abh_noise_cells_host(const uint8_t *p, const uint8_t *r, const uint8_t *sigma6, int W, int H, int x0, int y0, int ncx, int ncy,
+                         int32_t *rec)
+{
+    if (!p || !r || !sigma6 || !rec || !lightGridInside(W, H, x0, y0, ncx, ncy))
+        return -1;
+    abub::noiseCellsHost(p, r, sigma6, W, H, x0, y0, ncx, ncy, rec);
+    return ncx * ncy;
+}
+// abub::noiseModelHost on raw buffers: recs[nrecs * ncy * ncx * 6], the records of the camera's rows at stack position 1, one
+// after another (nrecs may be 0, recs then NULL) -> rec[ncy * ncx * 5] (i64); returns as above
+int abh_noise_model_host(const uint8_t *sigma6, int W, int H, int x0, int y0, int ncx, int ncy, const int32_t *recs, int nrecs, int64_t *rec)
+{
+    if (!sigma6 || !rec || nrecs < 0 || (nrecs > 0 && !recs) || !lightGridInside(W, H, x0, y0, ncx, ncy))
+        return -1;
+    std::vector<const int32_t *> each((size_t)nrecs);
+    for (int q = 0; q < nrecs; ++q)
+        each[(size_t)q] = recs + (size_t)q * ncx * ncy * abub::NoiseRecordWords;
+    abub::noiseModelHost(sigma6, W, H, x0, y0, ncx, ncy, each.data(), each.size(), rec);
+    return ncx * ncy;
+}
+// abub::noiseCell on raw buffers, what a cell's record says against its model's: out[4] = state (0 clipped, 1 busy, 2 nobase,
+// 3 noisy, 4 quiet, 5 same), q_milli, all_milli, model_milli
+void abh_noise_cell(const int32_t *rec, const int64_t *model, long long *out)
+{
+    const abub::NoiseCell c = abub::noiseCell(rec, model);
+    const long long v[4] = {c.state, c.qMilli, c.allMilli, abub::noiseModelMilli(model)};
+    std::memcpy(out, v, sizeof v);
+}
+// abub::noiseFrame on raw buffers, what a frame's records say against the model's: out[10] = rated, clipped, busy, noisy,
+// quiet, kind (0 blind, 1 busy, 2 steady, 3 noisy, 4 quiet, 5 uneven), q_milli, q_min, q_max, all_milli
+void abh_noise_frame(const int32_t *rec, const int64_t *model, int cells, long long *out)
+{
+    const abub::NoiseFrame f = abub::noiseFrame(rec, model, (size_t)std::max(cells, 0));
+    const long long v[10] = {f.rated, f.clipped, f.busy, f.noisy, f.quiet, f.kind, f.qMilli, f.qMin, f.qMax, f.allMilli};
     std::memcpy(out, v, sizeof v);
 }
 

@@ -307,9 +307,67 @@ struct FocusFrame {
 };
 FocusFrame focusFrame(const int32_t *rec, const int64_t *model, size_t cells);
 
+// The definition of abub_frame_noise_cells_dev ("Surveying a run for noise changes"): per cell of 128 x 128
+// pixels of the grid (ncx x ncy whole cells, the first at (x0, y0); the survey's is abub_frame_cells_grid's) six i32 over the
+// cell's pixels p of the frame, r of its reference frame (the frame two before) and s of sigma6, with d = p - r:
+// rec[(cy * ncx + cx) * 6 + 0 .. 5] = n_over (pixels with |d| > s), n_clip (pixels where p or r is 0 or 255), s1_in = sum d
+// and s2_in = sum d^2 over the pixels with |d| <= s (the inside ones; with s = 0 only d = 0 is inside), sad = sum |d| and
+// s2_all = sum d^2 over all.  mu is not read.  Plain loops; a magnitude of at most 16384 * 255^2 < 2^31.
+enum { NoiseRecordWords = 6, NoiseModelWords = 5, NoiseCellPixels = 128 * 128 /* ABUB_FIELD_CELL^2 */ };
+void noiseCellsHost(const unsigned char *p, const unsigned char *r, const unsigned char *sigma6, int W, int H, int x0, int y0, int ncx,
+                    int ncy, int32_t *rec);
+// The rule's constants.  A cell is clipped if more than 1 / NoiseClipShare of its pixels are, busy if more than
+// 1 / NoiseBusyShare of them lie outside 6 sigma; a rated cell is noisy above NoiseNoisyMilli, quiet below NoiseQuietMilli.
+// The two ratios are the rule, not measurements: the sampling spread of a variance over 16384 pixels is sqrt(2 / N), about
+// 1.1 %, and a factor 1.5 in variance (1.22 in sigma) is far outside it and well inside a doubling.
+enum { NoiseClipShare = 8, NoiseBusyShare = 4, NoiseNoisyMilli = 1500, NoiseQuietMilli = 667 };
+// Of a record with N = 16384: n_in = N - n_over and E = s2_in - floor(s1_in^2 / n_in) (0 where n_in = 0), the inside sum of
+// squares about the inside mean: a level step between the two frames does not count as noise
+inline long long noiseNIn(const int32_t *rec) { return (long long)NoiseCellPixels - rec[0]; }
+inline long long noiseE(const int32_t *rec)
+{
+    const long long n = noiseNIn(rec), s1 = rec[2];
+    return n > 0 ? (long long)rec[3] - s1 * s1 / n : 0; // (s1^2 >= 0: the division floors)
+}
+inline bool noiseClipped(const int32_t *rec) { return (long long)rec[1] * NoiseClipShare > (long long)NoiseCellPixels; }
+inline bool noiseBusy(const int32_t *rec) { return (long long)rec[0] * NoiseBusyShare > (long long)NoiseCellPixels; }
+// The camera's share, measured from the run itself: rec[(cy * ncx + cx) * 5 + 0 .. 4] = BE, BN, B, sum s^2 over the cell, the
+// cell's pixels with s = 0.  recs[0 .. nrecs): the records ([ncy][ncx][6]) of the camera's rows at stack position 1 that have
+// one (their reference is frame 0: the two frames the Trainer reads); per cell, over those of them that are neither clipped
+// nor busy in that cell, BE = sum E, BN = sum n_in and B their number.  The u8 sigma is truncated, so a rule against sigma
+// itself would call every steady run noisy: the baseline is the run's own.
+void noiseModelHost(const unsigned char *sigma6, int W, int H, int x0, int y0, int ncx, int ncy, const int32_t *const *recs, size_t nrecs,
+                    int64_t *rec);
+// What a cell says, from its frame record and its model record (one function for both routes; integers only, unsigned
+// __int128).  The states in this order: clipped; busy (too much of the cell lies outside 6 sigma for the inside sums to mean
+// noise; all_milli says which); nobase (BE = 0 or B = 0); else rated by q_milli = floor(1000 E BN / (n_in BE)): noisy above
+// 1500, quiet below 667, else same.  all_milli = floor(1000 s2_all BN / (N BE)), 0 without a baseline, whatever the state.
+// model_milli = floor(1000 * 18 BE N / (BN sum s^2)) (0 where BN or sum s^2 is 0): how far the u8 sigma plane is from the
+// noise it was trained on (E[d^2] = 2 sigma^2 and s = 6 sigma give the 18); reported, never used to rate.
+struct NoiseCell {
+    enum State { Clipped = 0, Busy = 1, NoBase = 2, Noisy = 3, Quiet = 4, Same = 5 };
+    int state = NoBase;
+    bool rated() const { return state >= Noisy; }
+    long long qMilli = 0, allMilli = 0; // qMilli: of a rated cell
+};
+NoiseCell noiseCell(const int32_t *rec, const int64_t *model);
+long long noiseModelMilli(const int64_t *model);
+// What a frame says, from its cells.  Pooled over the rated cells q_milli = floor(1000 sum(E BN) / sum(n_in BE)) and the range
+// of their q_milli; pooled over the cells with a baseline that are not clipped all_milli = floor(1000 sum(s2_all BN) /
+// sum(N BE)) (0 where there is none).  kind, with U the cells that are not clipped: blind (rated + busy < a quarter of all
+// cells), else busy (busy * 2 > U), else steady (no noisy and no quiet cell), else noisy (no quiet cell and noisy * 2 >=
+// rated), else quiet (no noisy cell and quiet * 2 >= rated), else uneven
+struct NoiseFrame {
+    enum Kind { Blind = 0, Busy = 1, Steady = 2, Noisy = 3, Quiet = 4, Uneven = 5 };
+    int rated = 0, clipped = 0, busy = 0, noisy = 0, quiet = 0, kind = Blind;
+    long long qMilli = 0, qMin = 0, qMax = 0, allMilli = 0;
+};
+NoiseFrame noiseFrame(const int32_t *rec, const int64_t *model, size_t cells);
+
 // What a survey makes of every ok row of a camera with a model, beyond its record: the index of the row's state, of the
 // product's counters and of the host threads' clocks
-enum SurveyProduct { SurveyShiftProduct = 0, SurveyFieldProduct = 1, SurveyLightProduct = 2, SurveyFocusProduct = 3, SurveyProducts = 4 };
+enum SurveyProduct { SurveyShiftProduct = 0, SurveyFieldProduct = 1, SurveyLightProduct = 2, SurveyFocusProduct = 3, SurveyNoiseProduct = 4,
+                     SurveyProducts = 5 };
 // One row of a survey: a frame the run lists, or one it should list (missing)
 struct SurveyRow {
     enum State { Ok = 0, Undecodable = 1, Missing = 2, OtherSize = 3 };
@@ -320,13 +378,15 @@ struct SurveyRow {
     int state = Ok, w = 0, h = 0; // w, h: of Ok and OtherSize rows
     FrameStats s;            // Ok: all of it, as far as its flags say; OtherSize: the raw columns
     bool onKernel = false;
-    uint8_t made = 0;        // two bits per SurveyProduct: an ok row of a camera with a model has every product that was asked for
+    uint16_t made = 0;       // two bits per SurveyProduct: an ok row of a camera with a model has every product that was asked for
+                             // (the noise only where its reference row is another row, ok and of the run's size)
     Made has(SurveyProduct p) const { return (Made)(made >> (2 * p) & 3); }
-    void set(SurveyProduct p, Made m) { made = (uint8_t)((made & ~(3 << (2 * p))) | (m << (2 * p))); }
+    void set(SurveyProduct p, Made m) { made = (uint16_t)((made & ~(3 << (2 * p))) | (m << (2 * p))); }
     ShiftBest shift;             // with a shift file: its surface's answer
     std::vector<int32_t> field;  // with a field directory: its cells' records, [ncy][ncx][5]
     std::vector<uint32_t> light; // with a light directory: its cells' light records, [ncy][ncx][6]
     std::vector<int32_t> focus;  // with a focus directory: its cells' focus records, [ncy][ncx][5]
+    std::vector<int32_t> noise;  // with a noise directory: its cells' noise records, [ncy][ncx][6]
     const char *stateName() const; // "ok", "undecodable", "missing", "other_size"
 };
 // What the report says of one camera's model
@@ -337,9 +397,10 @@ struct SurveyModel {
     double muMean = 0;
     std::vector<uint32_t> light; // with a light directory, of a trained camera: lightModelHost's [ncy][ncx][3]
     std::vector<int64_t> focus;  // with a focus directory, of a trained camera: focusModelHost's [ncy][ncx][3]
+    std::vector<int64_t> noise;  // with a noise directory, of a trained camera: noiseModelHost's [ncy][ncx][5]
 };
 // The counters of one product: the rows whose product its kernel made (abub_frame_shift_dev, abub_frame_shift_cells_dev,
-// abub_frame_light_cells_dev, abub_frame_focus_cells_dev) and those a host thread made from the definition, the kernel's
+// abub_frame_light_cells_dev, abub_frame_focus_cells_dev, abub_frame_noise_cells_dev) and those a host thread made from the definition, the kernel's
 // calls, the seconds of the device route's leg (launches, copy back) and the seconds the host threads spent in the
 // definition, summed over the threads
 struct ProductStats {
@@ -382,18 +443,20 @@ struct SurveyRequest {
     // lower than 128 + 2 cellRadius has no whole cell and is refused before its frames are measured.
     // "... for local movement": cam<c>_field.npy (i32 [N_c, ncy, ncx, 5]) and field.txt;
     // "... for lighting changes": cam<c>_light.npy (i32 [N_c, ncy, ncx, 6]), cam<c>_light_model.npy (i32 [ncy, ncx, 3]), light.txt;
-    // "... for lost focus": cam<c>_focus.npy (i32 [N_c, ncy, ncx, 5]), cam<c>_focus_model.npy (i64 [ncy, ncx, 3]), focus.txt
+    // "... for lost focus": cam<c>_focus.npy (i32 [N_c, ncy, ncx, 5]), cam<c>_focus_model.npy (i64 [ncy, ncx, 3]), focus.txt;
+    // "... for noise changes": cam<c>_noise.npy (i32 [N_c, ncy, ncx, 6]), cam<c>_noise_model.npy (i64 [ncy, ncx, 5]), noise.txt
     std::string fieldDir;
     int cellRadius = 4;
-    std::string lightDir, focusDir;
+    std::string lightDir, focusDir, noiseDir;
 };
-// The texts of field.txt, light.txt and focus.txt: "# abub3hs <tag> 1", the grid's line, the table's header and one
+// The texts of field.txt, light.txt, focus.txt and noise.txt: "# abub3hs <tag> 1", the grid's line, the table's header and one
 // tab-separated row per survey row, one `<tag> cam` line per camera, the `moved` (field) or `changed` lines of every camera
-// with a model, the `run` line.  Both routes write them through these functions; W, H: the run's size; models[c].light and
-// models[c].focus: the camera's model record.
+// with a model, the `run` line.  Both routes write them through these functions; W, H: the run's size; models[c].light,
+// models[c].focus and models[c].noise: the camera's model record.  A `noise cam` line ends with the cells' model_milli.
 std::string FieldReport(int radius, int W, int H, const std::vector<SurveyModel> &models, const std::vector<SurveyRow> &rows);
 std::string LightReport(int radius, int W, int H, const std::vector<SurveyModel> &models, const std::vector<SurveyRow> &rows);
 std::string FocusReport(int radius, int W, int H, const std::vector<SurveyModel> &models, const std::vector<SurveyRow> &rows);
+std::string NoiseReport(int radius, int W, int H, const std::vector<SurveyModel> &models, const std::vector<SurveyRow> &rows);
 // The shift file's text: "# abub3hs shift 1", `radius R`, the table's header and one tab-separated row per survey row, one
 // `shift cam` line per camera, the `run` line.  Both routes write it through this one function.
 std::string ShiftReport(int radius, const std::vector<SurveyModel> &models, const std::vector<SurveyRow> &rows);
@@ -409,7 +472,7 @@ std::string SurveyReport(const std::vector<SurveyModel> &models, const std::vect
 // is not written), every other product of `request` to its place; a product changes nothing in the others.  Returns 0, or 1
 // if any frame is not ok; throws where a file cannot be written.
 // device < 0, the host route: cv::imdecode and the definitions (frameStatsHost, activityAddHost, frameShiftHost,
-// fieldCellsHost, lightCellsHost, focusCellsHost) on `nthreads` threads.  No GPU.
+// fieldCellsHost, lightCellsHost, focusCellsHost, noiseCellsHost) on `nthreads` threads.  No GPU.
 // device >= 0 (--survey-gpu): the same rows and the same files, byte for byte.  The frames are read through the FileBatch
 // protocol (framefiles.hpp) in batches of at most 4 frames per CU (ABUB_SURVEY_BATCH=n: of n), decoded into the batch's
 // slab, and measured by one abub_frame_stats_dev launch per batch, with the products' kernels behind it.  A batch that

@@ -12,7 +12,9 @@
 //   field           fieldCellsHost     abub_frame_shift_cells_dev    fieldCell reads a cell's surface; FieldReport
 //   light           lightCellsHost     abub_frame_light_cells_dev    lightModelHost once per camera; lightCell, lightFrame; LightReport
 //   focus           focusCellsHost     abub_frame_focus_cells_dev    focusModelHost once per camera; focusCell, focusFrame; FocusReport
-// Shift, field, light and focus are made of the ok rows of a camera with a model and share the rest: one two-bit state per
+//   noise           noiseCellsHost     abub_frame_noise_cells_dev    the row against its reference frame, not mu; noiseModelHost once
+//                                                                    per camera after the rows; noiseCell, noiseFrame; NoiseReport
+// Shift, field, light, focus and noise are made of the ok rows of a camera with a model and share the rest: one two-bit state per
 // row, one ProductStats, one timing wrapper on the host, one device leg over one job list (deviceFrames), and for the three
 // per-cell products one grid, one report skeleton (cellReport) and one writer (writeCells).
 #include <algorithm>
@@ -388,6 +390,139 @@ FocusFrame focusFrame(const int32_t *rec, const int64_t *model, size_t cells)
     return f;
 }
 
+void noiseCellsHost(const unsigned char *p, const unsigned char *r, const unsigned char *sigma6, int W, int H, int x0, int y0, int ncx,
+                    int ncy, int32_t *rec)
+{
+    (void)H;
+    const int C = ABUB_FIELD_CELL;
+    for (int cy = 0; cy < ncy; ++cy)
+        for (int cx = 0; cx < ncx; ++cx) {
+            int32_t nOver = 0, nClip = 0, s1In = 0, s2In = 0, sad = 0, s2All = 0; // (a magnitude of at most 16384 * 255^2 < 2^31)
+            for (int y = y0 + C * cy; y < y0 + C * (cy + 1); ++y) {
+                const unsigned char *pr = p + (size_t)y * W, *rr = r + (size_t)y * W, *sr = sigma6 + (size_t)y * W;
+                for (int x = x0 + C * cx; x < x0 + C * (cx + 1); ++x) {
+                    const int32_t d = (int32_t)pr[x] - rr[x], a = std::abs(d);
+                    nClip += pr[x] == 0 || pr[x] == 255 || rr[x] == 0 || rr[x] == 255;
+                    sad += a;
+                    s2All += d * d;
+                    if (a > sr[x]) {
+                        ++nOver;
+                        continue;
+                    }
+                    s1In += d;
+                    s2In += d * d;
+                }
+            }
+            int32_t *out = rec + ((size_t)cy * ncx + cx) * NoiseRecordWords;
+            out[0] = nOver;
+            out[1] = nClip;
+            out[2] = s1In;
+            out[3] = s2In;
+            out[4] = sad;
+            out[5] = s2All;
+        }
+}
+
+void noiseModelHost(const unsigned char *sigma6, int W, int H, int x0, int y0, int ncx, int ncy, const int32_t *const *recs, size_t nrecs,
+                    int64_t *rec)
+{
+    (void)H;
+    const int C = ABUB_FIELD_CELL;
+    for (int cy = 0; cy < ncy; ++cy)
+        for (int cx = 0; cx < ncx; ++cx) {
+            const size_t k = (size_t)cy * ncx + cx;
+            int64_t BE = 0, BN = 0, B = 0, ss = 0, zero = 0; // (ss <= 16384 * 255^2)
+            for (size_t q = 0; q < nrecs; ++q) {
+                const int32_t *r = recs[q] + k * NoiseRecordWords;
+                if (noiseClipped(r) || noiseBusy(r))
+                    continue;
+                BE += noiseE(r);
+                BN += noiseNIn(r);
+                ++B;
+            }
+            for (int y = y0 + C * cy; y < y0 + C * (cy + 1); ++y)
+                for (int x = x0 + C * cx; x < x0 + C * (cx + 1); ++x) {
+                    const int64_t s = sigma6[(size_t)y * W + x];
+                    ss += s * s;
+                    zero += s == 0;
+                }
+            int64_t *out = rec + k * NoiseModelWords;
+            out[0] = BE;
+            out[1] = BN;
+            out[2] = B;
+            out[3] = ss;
+            out[4] = zero;
+        }
+}
+
+NoiseCell noiseCell(const int32_t *rec, const int64_t *model)
+{
+    typedef unsigned __int128 u128;
+    const long long N = NoiseCellPixels, BE = model[0], BN = model[1], B = model[2];
+    const bool base = BE > 0 && B > 0;
+    NoiseCell c;
+    if (base)
+        c.allMilli = (long long)((u128)1000 * (u128)rec[5] * (u128)BN / ((u128)N * (u128)BE));
+    if (noiseClipped(rec))
+        c.state = NoiseCell::Clipped;
+    else if (noiseBusy(rec))
+        c.state = NoiseCell::Busy;
+    else if (!base)
+        c.state = NoiseCell::NoBase;
+    else { // (n_in >= 3 N / 4 > 0: the cell is not busy)
+        c.qMilli = (long long)((u128)1000 * (u128)noiseE(rec) * (u128)BN / ((u128)noiseNIn(rec) * (u128)BE));
+        c.state = c.qMilli > NoiseNoisyMilli ? NoiseCell::Noisy : c.qMilli < NoiseQuietMilli ? NoiseCell::Quiet : NoiseCell::Same;
+    }
+    return c;
+}
+
+long long noiseModelMilli(const int64_t *model)
+{
+    typedef unsigned __int128 u128;
+    if (model[1] <= 0 || model[3] <= 0)
+        return 0;
+    return (long long)((u128)(1000 * 18) * (u128)model[0] * (u128)NoiseCellPixels / ((u128)model[1] * (u128)model[3]));
+}
+
+NoiseFrame noiseFrame(const int32_t *rec, const int64_t *model, size_t cells)
+{
+    typedef unsigned __int128 u128;
+    NoiseFrame f;
+    u128 qNum = 0, qDen = 0, aNum = 0, aDen = 0;
+    for (size_t k = 0; k < cells; ++k) {
+        const int32_t *r = rec + k * NoiseRecordWords;
+        const int64_t *m = model + k * NoiseModelWords;
+        const NoiseCell c = noiseCell(r, m);
+        f.clipped += c.state == NoiseCell::Clipped;
+        f.busy += c.state == NoiseCell::Busy;
+        if (c.state != NoiseCell::Clipped && m[0] > 0 && m[2] > 0) {
+            aNum += (u128)r[5] * (u128)m[1];
+            aDen += (u128)NoiseCellPixels * (u128)m[0];
+        }
+        if (!c.rated())
+            continue;
+        f.qMin = f.rated ? std::min(f.qMin, c.qMilli) : c.qMilli;
+        f.qMax = f.rated ? std::max(f.qMax, c.qMilli) : c.qMilli;
+        ++f.rated;
+        f.noisy += c.state == NoiseCell::Noisy;
+        f.quiet += c.state == NoiseCell::Quiet;
+        qNum += (u128)noiseE(r) * (u128)m[1];
+        qDen += (u128)noiseNIn(r) * (u128)m[0];
+    }
+    if (f.rated)
+        f.qMilli = (long long)((u128)1000 * qNum / qDen);
+    if (aDen)
+        f.allMilli = (long long)((u128)1000 * aNum / aDen);
+    const long long U = (long long)cells - f.clipped;
+    f.kind = (long long)(f.rated + f.busy) * 4 < (long long)cells ? NoiseFrame::Blind
+             : f.busy * 2 > U                                      ? NoiseFrame::Busy
+             : !f.noisy && !f.quiet                                ? NoiseFrame::Steady
+             : !f.quiet && f.noisy * 2 >= f.rated                  ? NoiseFrame::Noisy
+             : !f.noisy && f.quiet * 2 >= f.rated                  ? NoiseFrame::Quiet
+                                                                   : NoiseFrame::Uneven;
+    return f;
+}
+
 // the columns every table of a survey begins with
 static void rowPrefix(std::string &text, const SurveyRow &r)
 {
@@ -408,6 +543,7 @@ struct CellReport {
     // One row: -1 if it has no record.  Else its columns are appended to `cols`, `first` says whether the row counts as its
     // camera's first event, hit[k] is raised for every cell that counts in the map; returns the row's kind
     std::function<int(const SurveyRow &r, size_t cells, std::string &cols, bool &first, std::vector<long long> &hit)> row;
+    std::function<std::string(size_t cam, size_t cells)> camTail; // (may be empty) what a trained camera's `<tag> cam` line ends with
 };
 
 std::string cellReport(const CellReport &d, int radius, int W, int H, const std::vector<SurveyModel> &models,
@@ -473,7 +609,7 @@ std::string cellReport(const CellReport &d, int radius, int W, int H, const std:
             text += buf;
             kind[q] += k.kind[q];
         }
-        text += std::string(" ") + d.firstLabel + " " + (k.first ? *k.first : std::string("-")) + "\n";
+        text += std::string(" ") + d.firstLabel + " " + (k.first ? *k.first : std::string("-")) + (d.camTail ? d.camTail(c, cells) : "") + "\n";
         frames += k.frames;
     }
     for (size_t c = 0; c < cams.size(); ++c) {
@@ -546,7 +682,7 @@ std::string FieldReport(int radius, int W, int H, const std::vector<SurveyModel>
         return kind;
     };
     return cellReport({"field", "rated\tmoved\tmodal_dx\tmodal_dy\tmodal_n\tdx_min\tdx_max\tdy_min\tdy_max",
-                       {"blind", "still", "rigid", "warped", "local"}, "moved", "first_moved_event", row},
+                       {"blind", "still", "rigid", "warped", "local"}, "moved", "first_moved_event", row, nullptr},
                       radius, W, H, models, rows);
 }
 
@@ -576,7 +712,7 @@ std::string LightReport(int radius, int W, int H, const std::vector<SurveyModel>
         return f.kind;
     };
     return cellReport({"light", "rated\tclipped\tchanged\tup\tdown\tlevel_milli\tratio_min\tratio_max\tgain_milli\toffset_milli",
-                       {"blind", "steady", "level", "uneven"}, "changed", "first_changed_event", row},
+                       {"blind", "steady", "level", "uneven"}, "changed", "first_changed_event", row, nullptr},
                       radius, W, H, models, rows);
 }
 
@@ -604,7 +740,44 @@ std::string FocusReport(int radius, int W, int H, const std::vector<SurveyModel>
         return f.kind;
     };
     return cellReport({"focus", "rated\tclipped\tchanged\tsofter\tharder\tkeep_milli\tkeep_min\tkeep_max\tenergy_milli",
-                       {"blind", "steady", "soft", "uneven"}, "changed", "first_changed_event", row},
+                       {"blind", "steady", "soft", "uneven"}, "changed", "first_changed_event", row, nullptr},
+                      radius, W, H, models, rows);
+}
+
+std::string NoiseReport(int radius, int W, int H, const std::vector<SurveyModel> &models, const std::vector<SurveyRow> &rows)
+{
+    const auto modelOf = [&](size_t cam, size_t cells) -> const std::vector<int64_t> * {
+        return cam < models.size() && models[cam].noise.size() == cells * NoiseModelWords ? &models[cam].noise : nullptr;
+    };
+    const auto row = [&](const SurveyRow &r, size_t cells, std::string &cols, bool &first, std::vector<long long> &hit) -> int {
+        const std::vector<int64_t> *model = modelOf((size_t)r.cam, cells);
+        if (r.state != SurveyRow::Ok || !r.has(SurveyNoiseProduct) || r.noise.size() != cells * NoiseRecordWords || !model)
+            return -1;
+        const NoiseFrame f = noiseFrame(r.noise.data(), model->data(), cells);
+        for (size_t k = 0; k < cells; ++k) {
+            const NoiseCell nc = noiseCell(r.noise.data() + k * NoiseRecordWords, model->data() + k * NoiseModelWords);
+            hit[k] += nc.state == NoiseCell::Noisy || nc.state == NoiseCell::Quiet;
+        }
+        char buf[512];
+        snprintf(buf, sizeof buf, "\t%d\t%d\t%d\t%d\t%d", f.rated, f.clipped, f.busy, f.noisy, f.quiet);
+        cols += buf;
+        if (f.rated)
+            snprintf(buf, sizeof buf, "\t%lld\t%lld\t%lld\t%lld", f.qMilli, f.qMin, f.qMax, f.allMilli);
+        else
+            snprintf(buf, sizeof buf, "\t-\t-\t-\t%lld", f.allMilli);
+        cols += buf;
+        first = f.noisy + f.quiet != 0;
+        return f.kind;
+    };
+    const auto camTail = [&](size_t cam, size_t cells) {
+        std::string tail = " model_milli";
+        const std::vector<int64_t> *model = modelOf(cam, cells);
+        for (size_t k = 0; k < cells; ++k)
+            tail += " " + std::to_string(model ? noiseModelMilli(model->data() + k * NoiseModelWords) : 0ll);
+        return tail;
+    };
+    return cellReport({"noise", "rated\tclipped\tbusy\tnoisy\tquiet\tq_milli\tq_min\tq_max\tall_milli",
+                       {"blind", "busy", "steady", "noisy", "quiet", "uneven"}, "changed", "first_changed_event", row, camTail},
                       radius, W, H, models, rows);
 }
 
@@ -758,9 +931,9 @@ struct CellGrid { // abub_frame_cells_grid's answer
 };
 struct Plan {
     HostPlanes *planes = nullptr;   // with a planes directory: where surveyFrame adds its ok rows
-    bool want[SurveyProducts] = {false, false, false, false}; // the products surveyFrame makes of its ok rows with a model
+    bool want[SurveyProducts] = {false, false, false, false, false}; // the products surveyFrame makes of its ok rows with a model
     int shiftR = 0, cellR = 0;      // the shift search's radius; the radius of the grid and of the field's per-cell search
-    CellGrid grid;                  // the one grid of the field, the light and the focus (all zero: none asked for, or no size)
+    CellGrid grid;                  // the one grid of the field, the light, the focus and the noise (all zero: none asked for, or no size)
     std::atomic<long long> *hostUs = nullptr; // [SurveyProducts]: where surveyFrame adds the microseconds it spent in a definition
     std::vector<std::string> events;
     std::vector<SurveyRow> rows;    // in event, camera and frame order
@@ -892,7 +1065,8 @@ void fieldRecords(const Plan &pl, const uint32_t *sad, SurveyRow &row)
 
 // The products of an ok row of a camera with a model on this thread: each one's definition and where its result goes, under
 // one clock
-void productsHost(const Plan &pl, const uint8_t *cur, const uint8_t *mu, SurveyRow &row)
+// (other: the row's decoded reference frame where that is another row, ok and of the run's size, else null: no noise record)
+void productsHost(const Plan &pl, const uint8_t *cur, const uint8_t *other, const uint8_t *mu, SurveyRow &row)
 {
     const auto timed = [&](SurveyProduct p, auto make) {
         if (!pl.want[p])
@@ -923,6 +1097,11 @@ void productsHost(const Plan &pl, const uint8_t *cur, const uint8_t *mu, SurveyR
         row.focus.resize(g.cells() * FocusRecordWords);
         focusCellsHost(cur, mu, pl.W, pl.H, g.x0, g.y0, g.ncx, g.ncy, row.focus.data());
     });
+    if (other)
+        timed(SurveyNoiseProduct, [&] {
+            row.noise.resize(g.cells() * NoiseRecordWords);
+            noiseCellsHost(cur, other, pl.sigma6[row.cam].data(), pl.W, pl.H, g.x0, g.y0, g.ncx, g.ncy, row.noise.data());
+        });
 }
 
 // The host route's per-frame function: row i on this thread, its state and its record.  It asks nothing of the other rows:
@@ -962,7 +1141,7 @@ void surveyFrame(Parser &p, const Plan &pl, size_t i, SurveyRow &row)
     if (pl.planes)
         pl.planes->add(row.cam, cur.data, r, mu, mu ? pl.sigma6[row.cam].data() : nullptr);
     if (mu)
-        productsHost(pl, cur.data, mu, row);
+        productsHost(pl, cur.data, ri != i && !ref.empty() ? ref.data : nullptr, mu, row);
 }
 
 void hostFrames(Parser *parser, Plan &pl, int nthreads)
@@ -995,7 +1174,8 @@ FrameStats fromRecord(const abub_stat_result &r)
 // * stats: one abub_frame_stats_dev launch over the rows in place, [jobs][records] in the meta buffer, the records back in
 //   one copy.  The list of the jobs that have a model is made from them once, as one abub_shift_job array, and uploaded once
 //   (mu is resident already); the four product legs read it.
-// * shift, field, light, focus, each only if asked for: one helper (`leg`) launches the product's entry over that list,
+// * shift, field, light, focus, each only if asked for: one helper (`leg`) launches the product's entry over that list
+//   (the noise's over a list of its own, the stats jobs as they are of the rows whose reference frame is another frame in place),
 //   copies [status words][payloads] back from the one buffer pair the legs share, checks the status words and hands every
 //   row its payload.  The shift's payload is a u64 surface, read by shiftBest; the field's are the cells' u32 surfaces, read
 //   by fieldRecords, in calls of as many jobs as keep them below 64 MiB (ABUB_FIELD_CHUNK=n: of n jobs), a call reading the
@@ -1116,24 +1296,41 @@ void deviceFrames(Parser *parser, Plan &pl, int nthreads, int device, SurveyStat
             for (size_t g = 0; g < nj; ++g)
                 if (jobs[g].model != UINT64_MAX)
                     with.push_back(g);
-            const size_t ns = with.size();
+            // (the noise pairs a row with its reference frame: of those, the jobs whose reference is another frame, in place; the
+            // offsets are the stats jobs' own, the reference among the batch's rows or among the frames read again)
+            std::vector<size_t> paired;
+            if (pl.want[SurveyNoiseProduct])
+                for (size_t g : with)
+                    if (jobs[g].ref != UINT64_MAX && jobs[g].ref != jobs[g].cur)
+                        paired.push_back(g);
+            const size_t ns = with.size(), nn = paired.size();
             const abub_shift_job *d_jobs = nullptr;
-            if (ns && (pl.want[SurveyShiftProduct] || pl.want[SurveyFieldProduct] || pl.want[SurveyLightProduct] || pl.want[SurveyFocusProduct])) {
-                h_jobs.grow(ns * sizeof(abub_shift_job));
-                d_jobsBuf.grow(ns * sizeof(abub_shift_job));
+            const abub_stat_job *d_pairs = nullptr; // behind the with-model list in the same buffer
+            if (ns && (pl.want[SurveyShiftProduct] || pl.want[SurveyFieldProduct] || pl.want[SurveyLightProduct] || pl.want[SurveyFocusProduct] ||
+                       nn)) {
+                const size_t bytes = ns * sizeof(abub_shift_job) + nn * sizeof(abub_stat_job);
+                h_jobs.grow(bytes);
+                d_jobsBuf.grow(bytes);
                 abub_shift_job *sj = (abub_shift_job *)h_jobs.get();
                 for (size_t q = 0; q < ns; ++q)
                     sj[q] = abub_shift_job{jobs[with[q]].cur, jobs[with[q]].model};
-                HIPOK(hipMemcpyAsync(d_jobsBuf.get(), sj, ns * sizeof(abub_shift_job), hipMemcpyHostToDevice, cs));
+                abub_stat_job *nj3 = (abub_stat_job *)(h_jobs.get() + ns * sizeof(abub_shift_job));
+                for (size_t q = 0; q < nn; ++q)
+                    nj3[q] = jobs[paired[q]];
+                HIPOK(hipMemcpyAsync(d_jobsBuf.get(), h_jobs.get(), bytes, hipMemcpyHostToDevice, cs));
                 d_jobs = (const abub_shift_job *)d_jobsBuf.get();
+                d_pairs = (const abub_stat_job *)(d_jobsBuf.get() + ns * sizeof(abub_shift_job));
             }
             const auto rowWith = [&](size_t q) -> SurveyRow & { return pl.rows[rowOf(slot[with[q]])]; };
-            // One leg: `entry` over the jobs in calls of `chunk` (0: all of them in one; no job: no call), each call's status
-            // words and payloads ([status, padded to 8 bytes][payloadBytes per job], the one buffer pair of all legs, which
-            // synchronise one after another) back in one copy; take(q, payload) gets what job q's row is given
-            const auto leg = [&](SurveyProduct p, const char *entry, size_t payloadBytes, size_t chunk, auto launch, auto take) {
+            // One leg: `entry` over the `ns` jobs of `list` (indices into the stats jobs) in calls of `chunk` (0: all of them in
+            // one; no job: no call), each call's status words and payloads ([status, padded to 8 bytes][payloadBytes per job], the
+            // one buffer pair of all legs, which synchronise one after another) back in one copy; launch(q0, n, ...) runs the
+            // entry over the list's jobs from q0 on, take(q, payload) gets what job q's row is given
+            const auto leg = [&](SurveyProduct p, const char *entry, const std::vector<size_t> &list, size_t payloadBytes, size_t chunk,
+                                 auto launch, auto take) {
                 if (!pl.want[p])
                     return;
+                const size_t ns = list.size();
                 st.stats_s += (nowMs() - t0) * 1e-3;
                 t0 = nowMs();
                 for (size_t q0 = 0; q0 < ns; q0 += chunk ? chunk : ns) {
@@ -1141,14 +1338,14 @@ void deviceFrames(Parser *parser, Plan &pl, int nthreads, int device, SurveyStat
                     const size_t statusBytes = (n * sizeof(uint32_t) + 7) & ~(size_t)7, bytes = statusBytes + n * payloadBytes;
                     h_leg.grow(bytes);
                     d_leg.grow(bytes);
-                    check(launch(d_jobs + q0, (int)n, (uint32_t *)d_leg.get(), d_leg.get() + statusBytes), entry);
+                    check(launch(q0, (int)n, (uint32_t *)d_leg.get(), d_leg.get() + statusBytes), entry);
                     HIPOK(hipMemcpyAsync(h_leg.get(), d_leg.get(), bytes, hipMemcpyDeviceToHost, cs));
                     HIPOK(hipStreamSynchronize(cs));
                     for (size_t q = 0; q < n; ++q) {
                         if (((const uint32_t *)h_leg.get())[q] != 0)
                             throw std::runtime_error(std::string("survey: ") + entry + " refused a frame of its own slab");
                         take(q0 + q, h_leg.get() + statusBytes + q * payloadBytes);
-                        rowWith(q0 + q).set(p, SurveyRow::Kernel);
+                        pl.rows[rowOf(slot[list[q0 + q]])].set(p, SurveyRow::Kernel);
                     }
                     ++st.product[p].launches;
                 }
@@ -1159,9 +1356,9 @@ void deviceFrames(Parser *parser, Plan &pl, int nthreads, int device, SurveyStat
             const size_t slabBytes = slots * stride, muBytes = C * stride;
             const CellGrid &cg = pl.grid;
             const size_t shiftN = (2 * (size_t)pl.shiftR + 1) * (2 * (size_t)pl.shiftR + 1);
-            leg(SurveyShiftProduct, "abub_frame_shift_dev", shiftN * sizeof(uint64_t), 0,
-                [&](const abub_shift_job *j, int n, uint32_t *status, uint8_t *sad) {
-                    return abub_frame_shift_dev(slab, slabBytes, d_mu, muBytes, j, n, W, H, pl.shiftR, status, (uint64_t *)sad, cs);
+            leg(SurveyShiftProduct, "abub_frame_shift_dev", with, shiftN * sizeof(uint64_t), 0,
+                [&](size_t q0, int n, uint32_t *status, uint8_t *sad) {
+                    return abub_frame_shift_dev(slab, slabBytes, d_mu, muBytes, d_jobs + q0, n, W, H, pl.shiftR, status, (uint64_t *)sad, cs);
                 },
                 [&](size_t q, const uint8_t *sad) { rowWith(q).shift = shiftBest((const uint64_t *)sad, pl.shiftR); });
             // (a job's surfaces depend on nothing but the job, so the split cannot show in the result)
@@ -1170,26 +1367,35 @@ void deviceFrames(Parser *parser, Plan &pl, int nthreads, int device, SurveyStat
             if (const char *e = getenv("ABUB_FIELD_CHUNK")) // (a test knob)
                 if (atoi(e) > 0)
                     fieldChunk = (size_t)atoi(e);
-            leg(SurveyFieldProduct, "abub_frame_shift_cells_dev", fieldWords * sizeof(uint32_t), fieldChunk,
-                [&](const abub_shift_job *j, int n, uint32_t *status, uint8_t *sad) {
-                    return abub_frame_shift_cells_dev(slab, slabBytes, d_mu, muBytes, j, n, W, H, pl.cellR, status, (uint32_t *)sad, cs);
+            leg(SurveyFieldProduct, "abub_frame_shift_cells_dev", with, fieldWords * sizeof(uint32_t), fieldChunk,
+                [&](size_t q0, int n, uint32_t *status, uint8_t *sad) {
+                    return abub_frame_shift_cells_dev(slab, slabBytes, d_mu, muBytes, d_jobs + q0, n, W, H, pl.cellR, status, (uint32_t *)sad,
+                                                      cs);
                 },
                 [&](size_t q, const uint8_t *sad) { fieldRecords(pl, (const uint32_t *)sad, rowWith(q)); });
-            leg(SurveyLightProduct, "abub_frame_light_cells_dev", cg.cells() * LightRecordWords * sizeof(uint32_t), 0,
-                [&](const abub_shift_job *j, int n, uint32_t *status, uint8_t *rec) {
-                    return abub_frame_light_cells_dev(slab, slabBytes, d_mu, muBytes, j, n, W, H, cg.x0, cg.y0, cg.ncx, cg.ncy, status,
-                                                      (uint32_t *)rec, cs);
+            leg(SurveyLightProduct, "abub_frame_light_cells_dev", with, cg.cells() * LightRecordWords * sizeof(uint32_t), 0,
+                [&](size_t q0, int n, uint32_t *status, uint8_t *rec) {
+                    return abub_frame_light_cells_dev(slab, slabBytes, d_mu, muBytes, d_jobs + q0, n, W, H, cg.x0, cg.y0, cg.ncx, cg.ncy,
+                                                      status, (uint32_t *)rec, cs);
                 },
                 [&](size_t q, const uint8_t *rec) {
                     rowWith(q).light.assign((const uint32_t *)rec, (const uint32_t *)rec + cg.cells() * LightRecordWords);
                 });
-            leg(SurveyFocusProduct, "abub_frame_focus_cells_dev", cg.cells() * FocusRecordWords * sizeof(int32_t), 0,
-                [&](const abub_shift_job *j, int n, uint32_t *status, uint8_t *rec) {
-                    return abub_frame_focus_cells_dev(slab, slabBytes, d_mu, muBytes, j, n, W, H, cg.x0, cg.y0, cg.ncx, cg.ncy, status,
-                                                      (int32_t *)rec, cs);
+            leg(SurveyFocusProduct, "abub_frame_focus_cells_dev", with, cg.cells() * FocusRecordWords * sizeof(int32_t), 0,
+                [&](size_t q0, int n, uint32_t *status, uint8_t *rec) {
+                    return abub_frame_focus_cells_dev(slab, slabBytes, d_mu, muBytes, d_jobs + q0, n, W, H, cg.x0, cg.y0, cg.ncx, cg.ncy,
+                                                      status, (int32_t *)rec, cs);
                 },
                 [&](size_t q, const uint8_t *rec) {
                     rowWith(q).focus.assign((const int32_t *)rec, (const int32_t *)rec + cg.cells() * FocusRecordWords);
+                });
+            leg(SurveyNoiseProduct, "abub_frame_noise_cells_dev", paired, cg.cells() * NoiseRecordWords * sizeof(int32_t), 0,
+                [&](size_t q0, int n, uint32_t *status, uint8_t *rec) { // (sigma6 lies behind mu: camera c at (C + c) * stride)
+                    return abub_frame_noise_cells_dev(slab, slabBytes, d_mu + C * stride, muBytes, d_pairs + q0, n, W, H, cg.x0, cg.y0, cg.ncx,
+                                                      cg.ncy, status, (int32_t *)rec, cs);
+                },
+                [&](size_t q, const uint8_t *rec) {
+                    pl.rows[rowOf(slot[paired[q]])].noise.assign((const int32_t *)rec, (const int32_t *)rec + cg.cells() * NoiseRecordWords);
                 });
             if (wantPlanes) {
                 st.stats_s += (nowMs() - t0) * 1e-3;
@@ -1475,9 +1681,10 @@ int SurveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCam
     if (device >= 0) // (before anything else)
         requireDevice(device, "survey", "; without --survey-gpu the run is surveyed on the host");
     const std::string planesDir = outputDir(rq.planesDir, rq.srcRunDir), fieldDir = outputDir(rq.fieldDir, rq.srcRunDir),
-                      lightDir = outputDir(rq.lightDir, rq.srcRunDir), focusDir = outputDir(rq.focusDir, rq.srcRunDir);
-    const bool want[SurveyProducts] = {!rq.shiftPath.empty(), !fieldDir.empty(), !lightDir.empty(), !focusDir.empty()};
-    const bool wantCells = want[SurveyFieldProduct] || want[SurveyLightProduct] || want[SurveyFocusProduct];
+                      lightDir = outputDir(rq.lightDir, rq.srcRunDir), focusDir = outputDir(rq.focusDir, rq.srcRunDir),
+                      noiseDir = outputDir(rq.noiseDir, rq.srcRunDir);
+    const bool want[SurveyProducts] = {!rq.shiftPath.empty(), !fieldDir.empty(), !lightDir.empty(), !focusDir.empty(), !noiseDir.empty()};
+    const bool wantCells = want[SurveyFieldProduct] || want[SurveyLightProduct] || want[SurveyFocusProduct] || want[SurveyNoiseProduct];
     if (wantCells && (rq.cellRadius < 1 || rq.cellRadius > 8))
         throw std::runtime_error("survey: the field radius must be in [1, 8], not " + std::to_string(rq.cellRadius));
     if (want[SurveyShiftProduct] && (rq.shiftRadius < 1 || rq.shiftRadius > 8))
@@ -1500,7 +1707,8 @@ int SurveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCam
         if (pl.W > 0)
             abub_frame_cells_grid(pl.W, pl.H, pl.cellR, &g.ncx, &g.ncy, &g.x0, &g.y0);
         static const char *const what[SurveyProducts][2] = {
-            {nullptr, nullptr}, {"a shift field", "needs"}, {"the light records", "need"}, {"the focus records", "need"}};
+            {nullptr, nullptr}, {"a shift field", "needs"}, {"the light records", "need"}, {"the focus records", "need"},
+            {"the noise records", "need"}};
         for (int p = SurveyFieldProduct; p < SurveyProducts; ++p)
             if (want[p]) // (a frame without a whole cell)
                 needFrames(pl, g.cells() > 0, what[p][0], what[p][1], pl.cellR, ABUB_FIELD_CELL + 2 * pl.cellR);
@@ -1538,6 +1746,21 @@ int SurveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCam
         deviceFrames(parser, pl, nthreads, device, st, devPlanes);
     } else
         hostFrames(parser, pl, nthreads);
+    // (the noise's baseline is the run's own: per camera, once every row is there, from its rows at stack position 1)
+    if (want[SurveyNoiseProduct])
+        for (size_t c = 0; c < pl.models.size(); ++c) {
+            SurveyModel &m = pl.models[c];
+            if (!m.trained)
+                continue;
+            const CellGrid &g = pl.grid;
+            std::vector<const int32_t *> base;
+            for (const SurveyRow &r : pl.rows)
+                if ((size_t)r.cam == c && r.frame == 1 && r.state == SurveyRow::Ok && r.has(SurveyNoiseProduct) &&
+                    r.noise.size() == g.cells() * NoiseRecordWords)
+                    base.push_back(r.noise.data());
+            m.noise.resize(g.cells() * NoiseModelWords);
+            noiseModelHost(pl.sigma6[c].data(), pl.W, pl.H, g.x0, g.y0, g.ncx, g.ncy, base.data(), base.size(), m.noise.data());
+        }
     for (const SurveyRow &r : pl.rows) {
         long long *const counter[] = {&st.ok, &st.undecodable, &st.missing, &st.otherSize};
         ++*counter[r.state];
@@ -1566,6 +1789,9 @@ int SurveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCam
     if (want[SurveyFocusProduct])
         writeCells(focusDir, "focus", SurveyFocusProduct, pl, FocusRecordWords, &SurveyRow::focus, "<i8", FocusModelWords, &SurveyModel::focus,
                    FocusReport(pl.cellR, pl.W, pl.H, pl.models, pl.rows));
+    if (want[SurveyNoiseProduct])
+        writeCells(noiseDir, "noise", SurveyNoiseProduct, pl, NoiseRecordWords, &SurveyRow::noise, "<i8", NoiseModelWords, &SurveyModel::noise,
+                   NoiseReport(pl.cellR, pl.W, pl.H, pl.models, pl.rows));
     if (hostPlanes) {
         const double t1 = nowMs();
         st.planeRowsHost = hostPlanes->rows;

@@ -932,6 +932,33 @@ int abub_frame_focus_cells_dev(const uint8_t *frames, size_t frames_bytes, const
                                const abub_shift_job *jobs, int njobs, int W, int H, int x0, int y0, int ncx, int ncy,
                                uint32_t *status /*[njobs]*/, int32_t *rec /*[njobs * ncy * ncx * 5]*/, void *stream);
 
+/* ---- per-cell frame-pair noise record of resident frames (abub_stats.hip) ----------------------------------------------
+ * Is the noise of the run still the noise the model was trained on, and where (abub3hs --survey --survey-noise;
+ * definition, files and measurements: DESIGN section 3, "Surveying a run for noise changes")?  Per cell of
+ * ABUB_FIELD_CELL x ABUB_FIELD_CELL pixels on the grid the caller gives (ncx x ncy whole cells, the first at (x0, y0); the
+ * survey passes abub_frame_cells_grid's) six i32 over the cell's pixels p of the frame at frames + jobs[j].cur, r of the
+ * reference frame at frames + jobs[j].ref and s of the plane at sigma6 + jobs[j].model (min(6 sigma, 255)), with d = p - r:
+ *   rec[((j * ncy + cy) * ncx + cx) * 6 + 0 .. 5] = n_over, the pixels with |d| > s; n_clip, the pixels where p or r is 0 or
+ *   255; s1_in = sum d and s2_in = sum d^2 over the pixels with |d| <= s; sad = sum |d| and s2_all = sum d^2 over all
+ * 16384 pixels: a magnitude of at most 16384 * 255^2 = 1065369600 < 2^31.  mu is not read.  Every value is an exact
+ * integer, bit-identical to the host definition (host/survey.cpp noiseCellsHost) whatever the order of the jobs or the
+ * blocks: one launch on `stream` of cells x jobs blocks of four waves, each reading its cell once into registers and
+ * writing its six words with plain stores.  Every output word has one owning workgroup: no atomics, no clearing launch, no
+ * scratch buffer, no host synchronisation, no allocation, no workgroup waiting for another.  What a record means is the
+ * host's to say (abub::noiseCell).
+ * Every pointer is a device pointer; jobs is 8-byte aligned, status and rec 4-byte aligned; W and H in [128, 65535];
+ * ncx, ncy >= 1, x0, y0 >= 0, x0 + 128 ncx <= W, y0 + 128 ncy <= H.  No alignment rule on the three offsets or on x0.
+ * status[j] (0 or ABUB_SHIFT_E_RANGE) and all ncx * ncy * 6 values of rec[j] are written in full by every call with
+ * njobs > 0, whatever they held before, and nothing else is written.  A job of which the frame or the reference frame runs
+ * past frames_bytes or the sigma6 plane past model_bytes (an offset of UINT64_MAX included) gets ABUB_SHIFT_E_RANGE and a
+ * zero record; nothing of it is read.  ref == cur is legal: a record with d = 0.  Null pointers, njobs < 0, W, H or the
+ * grid out of range or a misaligned jobs / status / rec: ABUB_E_INVALID before anything touches the device.  njobs == 0:
+ * ABUB_OK, nothing is touched.  njobs may exceed 65535. */
+#define ABUB_NOISE_WORDS 6
+int abub_frame_noise_cells_dev(const uint8_t *frames, size_t frames_bytes, const uint8_t *sigma6, size_t model_bytes,
+                               const abub_stat_job *jobs, int njobs, int W, int H, int x0, int y0, int ncx, int ncy,
+                               uint32_t *status /*[njobs]*/, int32_t *rec /*[njobs * ncy * ncx * 6]*/, void *stream);
+
 /* ---- the two DebugPeek planes of a batch of resident frames (abub_peek.hip) ------------------------------------------
  * What L3Localizer::CalculateInitialBubbleParams builds on the analyzer's thread for its debug write-out (reference
  * L3Localizer.cpp:252-257, 397, 448; DESIGN section 3, "The peek planes"), for a batch of items.  Per item two W x H u8
