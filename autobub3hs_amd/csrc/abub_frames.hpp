@@ -119,6 +119,16 @@ __device__ __forceinline__ void wave_reduce(V &...v)
         ((v = Op::op(v, (uint32_t)__shfl_xor(v, o))), ...);
 }
 __device__ __forceinline__ uint32_t wave_sum(uint32_t v) { return wave_reduce<WaveSum>(v), v; }
+// the same butterfly for an array of uint32_t or int32_t under one operation (an int32_t sum wraps as the uint32_t sum does)
+template <class Op, class T, size_t N>
+__device__ __forceinline__ void wave_reduce_all(T (&v)[N])
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1)
+#pragma unroll
+        for (size_t k = 0; k < N; ++k)
+            v[k] = (T)Op::op((uint32_t)v[k], (uint32_t)__shfl_xor(v[k], o));
+}
 
 // the entries' side: what a frame size and a job list must satisfy, and the grid of a walk over n jobs
 inline bool frame_bytes_ok(size_t frame_bytes) { return frame_bytes >= 1 && frame_bytes <= (size_t)0xfffffffeu; }

@@ -765,34 +765,138 @@ extern "C" int abub_frame_shift_dev(const uint8_t *frames, size_t frames_bytes, 
     return ABUB_OK;
 }
 
+// ---- per-cell products: what the field, light, focus and noise kernels share ----------------------------------------------
+// Each gives WORDS words per job and cell of FC_CELL x FC_CELL pixels, on a grid of ncx x ncy whole cells from (x0, y0)
+// that lies inside the frame with a ring of `ring` pixels around it: rec[((j ncy + cy) ncx + cx) WORDS + t].
+//
+// The grid is cells x jobs; a block of four waves owns one cell of one job at a time and with it the cell's WORDS words: it
+// writes each of them once with a plain store, so there is no atomic, no clearing launch and no other launch (the block of
+// cell 0 writes the job's status word).  A cell is 32 dwords wide, so the 64 lanes of a wave span two cell rows: lane l
+// owns dword col = l & 31 of the cell rows 8 k + first, first = 2 w + (l >> 5), k < FC_ROWS = 16 (w: its wave); in a stream
+// that is the dword at byte Cell::at(k).  A kernel is
+//     c = cells_here(..); for (j = blockIdx.y; j < njobs; j += gridDim.y) {
+//         ok = its range test; out = cells_open(j, ok, ..); if (!ok) { cells_zero(out); continue; }
+//         its sums; cells_close(c, sums, part, out); }
+// cells_close adds a lane's sums over its wave with shuffles, over the four waves through `part`, and stores the record.
+// The loop and the branch stay in the kernel, which keeps the code of the four what it was when each had a copy of all this
+// (profiles/r28): behind a functor of a shared loop a product's arithmetic is compiled on its own before the loop around it
+// is seen, and k_noise_cells went from 112 to 129 VGPRs, from 4 waves per SIMD to 3; with the branch inside cells_open
+// k_light_cells ran 2.5 % and k_focus_cells 1.4 % slower.
+//
+// A refused job.  A job is read only if the product's range test holds (sh_job_ok, nc_job_ok); otherwise its status is
+// E_RANGE and its record zero.  The test depends on the job and the launch alone, so it comes out the same in every thread
+// of every block of the job: a block leaves the job as one, before the job's first barrier.
+//
+// Bounds.  Stores: status[j] and rec[(j * cells + cell) * WORDS + t] with j < njobs, cell < cells = gridDim.x and t < WORDS,
+// inside the njobs and njobs * cells * WORDS words the caller gives.  LDS: part[wave][t], wave < 4, t < WORDS; the barrier
+// that ends cells_close stands between a job's last read of `part` and of the product's tiles and the next job's first
+// write.  cells_check admits only grids with ring <= x0, x0 + 128 ncx + ring <= W and so in y: a cell's pixels and the ring
+// around them lie inside the W * H bytes of a frame or model plane, which the range test has placed inside its buffer.
+namespace {
+
+#define FC_CELL ((uint32_t)ABUB_FIELD_CELL)
+#define FC_ROWS (FC_CELL / (2u * (FR_THREADS / 64))) /* rows of a cell per lane: 16 */
+static_assert(FC_CELL == 128u && FC_ROWS == SH_ROWS, "a wave spans two rows of 32 dwords; the u16 bound is that of sh_tile");
+
+struct Cell {
+    uint64_t P;                      // bytes of a frame or model plane
+    uint32_t W, xc, yc;              // the cell's first pixel
+    uint32_t lane, wave, first, col; // the lane's rows and dword (above)
+    __device__ __forceinline__ uint64_t at(uint32_t k) const { return (uint64_t)(yc + k * 8u + first) * W + xc + 4u * col; }
+};
+__device__ __forceinline__ Cell cells_here(uint32_t W, uint32_t H, uint32_t ncx, uint32_t x0, uint32_t y0)
+{
+    const uint32_t cell = blockIdx.x, lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    return {(uint64_t)W * H, W, x0 + (cell % ncx) * FC_CELL, y0 + (cell / ncx) * FC_CELL, lane, wave, 2u * wave + (lane >> 5), lane & 31u};
+}
+
+// A job begins: its status word.  -> the block's record
+template <uint32_t WORDS, class T>
+__device__ __forceinline__ T *cells_open(uint32_t j, bool good, uint32_t *status, T *rec)
+{
+    T *out = rec + ((uint64_t)j * gridDim.x + blockIdx.x) * WORDS;
+    if (blockIdx.x == 0u && threadIdx.x == 0u)
+        status[j] = good ? 0u : (uint32_t)ABUB_SHIFT_E_RANGE;
+    return out;
+}
+// the record of a refused job
+template <uint32_t WORDS, class T>
+__device__ __forceinline__ void cells_zero(T *out)
+{
+    for (uint32_t t = threadIdx.x; t < WORDS; t += FR_THREADS)
+        out[t] = 0;
+}
+// A job ends: word t of its record is the sum of part[wave][t] over the waves
+template <uint32_t WORDS, class T>
+__device__ __forceinline__ void cells_close(const T (*part)[WORDS], T *out)
+{
+    __syncthreads();
+    for (uint32_t t = threadIdx.x; t < WORDS; t += FR_THREADS) {
+        T v = part[0][t];
+#pragma unroll
+        for (int w = 1; w < FR_THREADS / 64; ++w)
+            v += part[w][t];
+        out[t] = v;
+    }
+    __syncthreads();
+}
+// the same from the lanes' sums
+template <uint32_t WORDS, class T>
+__device__ __forceinline__ void cells_close(const Cell &c, T (&acc)[WORDS], T (*part)[WORDS], T *out)
+{
+    wave_reduce_all<WaveSum>(acc);
+    if (c.lane == 0u) {
+#pragma unroll
+        for (uint32_t o = 0; o < WORDS; ++o)
+            part[c.wave][o] = acc[o];
+    }
+    cells_close(part, out);
+}
+
+// The entries' side.  CELLS_LAUNCH, or what the entry returns: its error, or ABUB_OK for an empty job list
+#define CELLS_LAUNCH 1
+int cells_check(const char *entry, bool pointers, const void *jobs, const void *status, const void *rec, int njobs, int W, int H, int x0,
+                int y0, int ncx, int ncy, int ring)
+{
+    const int C = ABUB_FIELD_CELL;
+    char msg[192];
+    if (!pointers || njobs < 0)
+        snprintf(msg, sizeof msg, "%s: null pointer or negative count", entry);
+    else if (W < C + 2 * ring || W > 65535 || H < C + 2 * ring || H > 65535)
+        snprintf(msg, sizeof msg, "%s: W and H must be in [%d, 65535]", entry, C + 2 * ring);
+    // (ncx, ncy <= 511 once the sides are bounded, so the sums below cannot overflow an int)
+    else if (ncx < 1 || ncy < 1 || ncx > (W - 2 * ring) / C || ncy > (H - 2 * ring) / C || x0 < ring || y0 < ring ||
+             x0 > W - ring - C * ncx || y0 > H - ring - C * ncy)
+        snprintf(msg, sizeof msg, "%s: the grid of whole cells and a ring of %d pixels around it must lie inside the frame", entry, ring);
+    else if (((uintptr_t)jobs & 7) || (((uintptr_t)status | (uintptr_t)rec) & 3))
+        snprintf(msg, sizeof msg, "%s: jobs must be 8-byte aligned, status and the records 4-byte aligned", entry);
+    else
+        return njobs == 0 ? ABUB_OK : CELLS_LAUNCH;
+    return set_err(ABUB_E_INVALID, msg);
+}
+inline dim3 cells_grid(int ncx, int ncy, int njobs) { return dim3((unsigned)(ncx * ncy), (unsigned)(njobs < 65535 ? njobs : 65535)); } // (at most 511 * 511 cells)
+
+} // namespace
+
 // ---- per-cell shift field: abub_frame_shift_cells_dev ("Surveying a run for local movement") ------------
 // The same sums as above, kept apart per cell of FC_CELL x FC_CELL interior pixels (host/survey.cpp fieldCellsHost, the
 // definition): with (ncx, ncy, x0, y0) = abub_frame_cells_grid(W, H, R), for cell (cx, cy)
 //   sad[((j ncy + cy) ncx + cx) (2 R + 1)^2 + (dy + R) (2 R + 1) + (dx + R)] = sum of |p(x + dx, y + dy) - m(x, y)|
 // over x0 + 128 cx <= x < x0 + 128 (cx + 1), y0 + 128 cy <= y < y0 + 128 (cy + 1).  Only whole cells exist.
 //
-// The grid is cells x jobs; a block of four waves owns one cell of one job at a time and with it the (2 R + 1)^2 words of
-// its surface: it writes each of them once with a plain store, so there is no atomic, no clearing launch and no other
-// launch (the block of cell 0 writes the job's status word).  It reads the cell with its halo of R pixels on every side
-// once into LDS, 128 + 2 R rows of RS = 32 + ND - 1 dwords (row r, dword c: the four pixels from (xc - R + 4 c, yc - R + r)
-// on).  A cell is 32 dwords wide, so the 64 lanes of a wave span two cell rows: lane l owns dword l & 31 of the rows
-// 8 k + 2 w + (l >> 5), k < 16 (w: its wave), and holds their mu dwords in registers.  The two halves of a wave are the two
-// lane groups of a ds_read_b32 / ds_read2_b32 (banks mod 32), and within a half the lanes read 32 consecutive dwords of
-// one row: no bank conflict at any RS.  The arithmetic is sh_tile's full-tile path: per dy 2 R + 1 sums in registers, from
-// R = 2 on four dx at a time with v_qsad_pk_u16_u8 (a lane adds at most 16 rows * 4 * 255 = 16320 into a u16), the rest
-// with v_alignbyte_b32 and v_sad_u8; summed over the wave with shuffles, over the waves through LDS.  A surface entry sums
-// 16384 pixels: at most 16384 * 255 < 2^32.
+// A block reads the cell with its halo of R pixels on every side once into LDS, 128 + 2 R rows of RS = 32 + ND - 1 dwords
+// (row r, dword c: the four pixels from (xc - R + 4 c, yc - R + r) on), and a lane holds the mu dwords of its rows in
+// registers.  The two halves of a wave are the two lane groups of a ds_read_b32 / ds_read2_b32 (banks mod 32), and within a
+// half the lanes read 32 consecutive dwords of one row: no bank conflict at any RS.  The arithmetic is sh_tile's full-tile
+// path: per dy 2 R + 1 sums in registers, from R = 2 on four dx at a time with v_qsad_pk_u16_u8 (a lane adds at most
+// 16 rows * 4 * 255 = 16320 into a u16), the rest with v_alignbyte_b32 and v_sad_u8.  fc_cell adds the lanes of a wave
+// itself, a dy at a time, and leaves the (2 R + 1)^2 sums in `part`: the field closes a job with cells_close(part, out).  A surface
+// entry sums 16384 pixels: at most 16384 * 255 < 2^32.
 //
-// Bounds.  A job is read only if sh_job_ok holds; otherwise E_RANGE and a zero surface, found alike by every block of the
-// job.  A cell with its halo lies inside the frame (x0 >= R, x0 + 128 ncx + R <= W, and so in y), and the last dword of a
-// tile row ends at byte 4 RS >= 128 + 2 R of it, at most 3 bytes behind the halo: sh_load4 tests the index itself against
-// W * H, a byte beyond reads as 0, and no lane uses a byte behind the halo (its last is 4 * 31 + 2 R + 3).  LDS: row
-// < 128 + 2 R, dword < RS.  Stores: status[j] and sad[(j * cells + cell) * N + t], j < njobs, cell < cells, t < N.
+// Bounds.  The ring is the halo, R.  The last dword of a tile row ends at byte 4 RS >= 128 + 2 R of it, at most 3 bytes
+// behind the halo: sh_load4 tests the index itself against W * H, a byte beyond reads as 0, and no lane uses a byte behind
+// the halo (its last is 4 * 31 + 2 R + 3).  LDS: row < 128 + 2 R, dword < RS.
 namespace {
-
-#define FC_CELL ((uint32_t)ABUB_FIELD_CELL)
-#define FC_ROWS (FC_CELL / (2u * (FR_THREADS / 64))) /* rows of a cell per lane: 16 */
-static_assert(FC_CELL == 128u && FC_ROWS == SH_ROWS, "a wave spans two rows of 32 dwords; the u16 bound is that of sh_tile");
 
 template <int R>
 __device__ __forceinline__ void fc_cell(const uint32_t *tile, const uint32_t (&m)[FC_ROWS], uint32_t (*part)[(2 * R + 1) * (2 * R + 1)])
@@ -850,43 +954,28 @@ __global__ __launch_bounds__(FR_THREADS) void k_shift_cells(const uint8_t *frame
 {
     constexpr int D = 2 * R + 1, N = D * D, ND = (2 * R + 4 + 3) / 4, RS = FC_CELL / 4 + ND - 1, TR = FC_CELL + 2 * R;
     __shared__ uint32_t tile[TR * RS];
-    __shared__ uint32_t part[FR_THREADS / 64][N];
-    const uint64_t P = (uint64_t)W * H;
-    const uint32_t cell = blockIdx.x, cells = gridDim.x;
-    const uint32_t xc = x0 + (cell % ncx) * FC_CELL, yc = y0 + (cell / ncx) * FC_CELL; // the cell's first interior pixel
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t first = 2u * wave + (lane >> 5), col = lane & 31u;
+    __shared__ uint32_t part[FR_THREADS / 64][(uint32_t)N];
+    const Cell c = cells_here(W, H, ncx, x0, y0);
     for (uint32_t j = blockIdx.y; j < (uint32_t)njobs; j += gridDim.y) {
         const abub_shift_job jb = jobs[j];
-        const bool ok = sh_job_ok(jb, frames_bytes, model_bytes, P); // (the same in every thread of every block of the job)
-        uint32_t *out = sad + ((uint64_t)j * cells + cell) * (uint32_t)N;
-        if (cell == 0u && threadIdx.x == 0u)
-            status[j] = ok ? 0u : (uint32_t)ABUB_SHIFT_E_RANGE;
+        const bool ok = sh_job_ok(jb, frames_bytes, model_bytes, c.P);
+        uint32_t *out = cells_open<(uint32_t)N>(j, ok, status, sad);
         if (!ok) {
-            for (uint32_t t = threadIdx.x; t < (uint32_t)N; t += FR_THREADS)
-                out[t] = 0u;
+            cells_zero<(uint32_t)N>(out);
             continue;
         }
         const uint8_t *p = frames + jb.cur, *q = mu + jb.model;
         for (uint32_t i = threadIdx.x; i < (uint32_t)(TR * RS); i += FR_THREADS) {
-            const uint32_t r = i / (uint32_t)RS, c = i % (uint32_t)RS;
-            tile[i] = sh_load4(p, (uint64_t)(yc - R + r) * W + (xc - R) + 4u * c, P);
+            const uint32_t r = i / (uint32_t)RS, d = i % (uint32_t)RS;
+            tile[i] = sh_load4(p, (uint64_t)(c.yc - R + r) * W + (c.xc - R) + 4u * d, c.P);
         }
         uint32_t m[FC_ROWS];
 #pragma unroll
         for (uint32_t r = 0; r < FC_ROWS; ++r)
-            m[r] = sh_load4(q, (uint64_t)(yc + r * 8u + first) * W + xc + 4u * col, P);
+            m[r] = sh_load4(q, c.at(r), c.P);
         __syncthreads();
         fc_cell<R>(tile, m, part);
-        __syncthreads();
-        for (uint32_t t = threadIdx.x; t < (uint32_t)N; t += FR_THREADS) {
-            uint32_t v = part[0][t];
-#pragma unroll
-            for (int w = 1; w < FR_THREADS / 64; ++w)
-                v += part[w][t];
-            out[t] = v;
-        }
-        __syncthreads(); // (tile and part are written again for the block's next job)
+        cells_close(part, out);
     }
 }
 
@@ -918,20 +1007,15 @@ extern "C" int abub_frame_shift_cells_dev(const uint8_t *frames, size_t frames_b
                                           const abub_shift_job *jobs, int njobs, int W, int H, int R, uint32_t *status, uint32_t *sad,
                                           void *stream)
 {
-    if (!frames || !mu || !jobs || !status || !sad || njobs < 0)
-        return set_err(ABUB_E_INVALID, "abub_frame_shift_cells_dev: null pointer or negative count");
     if (R < 1 || R > 8)
         return set_err(ABUB_E_INVALID, "abub_frame_shift_cells_dev: R must be in [1, 8]");
-    if (W < 1 || W > 65535 || H < 1 || H > 65535)
-        return set_err(ABUB_E_INVALID, "abub_frame_shift_cells_dev: W and H must be in [1, 65535]");
     int ncx = 0, ncy = 0, x0 = 0, y0 = 0;
-    if (abub_frame_cells_grid(W, H, R, &ncx, &ncy, &x0, &y0) != ABUB_OK || ncx == 0 || ncy == 0)
-        return set_err(ABUB_E_INVALID, "abub_frame_shift_cells_dev: W and H must be at least 128 + 2 R: the frame has no whole cell");
-    if (((uintptr_t)jobs & 7) || (((uintptr_t)status | (uintptr_t)sad) & 3))
-        return set_err(ABUB_E_INVALID, "abub_frame_shift_cells_dev: jobs must be 8-byte aligned, status and sad 4-byte aligned");
-    if (njobs == 0)
-        return ABUB_OK;
-    const dim3 grid((unsigned)(ncx * ncy), (unsigned)(njobs < 65535 ? njobs : 65535)); // (at most 511 * 511 cells)
+    abub_frame_cells_grid(W, H, R, &ncx, &ncy, &x0, &y0); // (a side it refuses or that has no whole cell is below 128 + 2 R)
+    const int chk = cells_check("abub_frame_shift_cells_dev", frames && mu && jobs && status && sad, jobs, status, sad, njobs, W, H, x0,
+                                y0, ncx, ncy, R);
+    if (chk != CELLS_LAUNCH)
+        return chk;
+    const dim3 grid = cells_grid(ncx, ncy, njobs);
     typedef void (*Launch)(dim3, hipStream_t, const uint8_t *, uint64_t, const uint8_t *, uint64_t, const abub_shift_job *, int, uint32_t,
                            uint32_t, uint32_t, uint32_t, uint32_t, uint32_t *, uint32_t *);
     static const Launch launch[8] = {cells_launch<1>, cells_launch<2>, cells_launch<3>, cells_launch<4>,
@@ -948,19 +1032,14 @@ extern "C" int abub_frame_shift_cells_dev(const uint8_t *frames, size_t frames_b
 // lightCellsHost, the definition):
 //   rec[((j ncy + cy) ncx + cx) 6 + 0 .. 5] = sum p, sum p^2, sum p m, sum |p - m|, the pixels with p == 0, with p == 255.
 //
-// The grid is cells x jobs; a block of four waves owns one cell of one job at a time and with it the cell's six words: it
-// writes each of them once with a plain store, so there is no atomic, no clearing launch and no other launch (the block of
-// cell 0 writes the job's status word).  There is no halo and so no LDS tile: fc_cell's lane mapping (lane l owns dword
-// l & 31 of the rows 8 k + 2 w + (l >> 5), k < 16), p and m straight into registers through sh_load4.  Per dword: sum p is
+// There is no halo and so no LDS tile: p and m come straight into registers through sh_load4.  Per dword: sum p is
 // v_sad_u8 against 0, sum |p - m| v_sad_u8(p, m), sum p^2 and sum p m v_dot4_u32_u8; the two counts are the set top bits of
 // ((x & 0x7f7f7f7f) + 0x7f7f7f7f | x | 0x7f7f7f7f) inverted, x = p and ~p: 0x7f + 0x7f = 0xfe never carries into the next
 // byte, so the test is exact per byte.  A lane sums 64 pixels (at most 64 * 65025 < 2^32), a cell 16384 (at most
-// 16384 * 65025 = 1065369600 < 2^31).  Summed over the wave with shuffles, over the waves through 24 words of LDS.
+// 16384 * 65025 = 1065369600 < 2^31).
 //
-// Bounds.  A job is read only if sh_job_ok holds; otherwise E_RANGE and a zero record, found alike by every block of the
-// job.  The launcher admits only grids with x0 + 128 ncx <= W and y0 + 128 ncy <= H, so every dword a lane loads lies
-// wholly inside the W * H bytes of its stream; sh_load4 tests the index against W * H besides.  Stores: status[j] and
-// rec[(j * cells + cell) * 6 + t], j < njobs, cell < cells, t < 6.
+// Bounds.  No ring: every dword a lane loads lies wholly inside the W * H bytes of its stream; sh_load4 tests the index
+// against W * H besides.
 namespace {
 
 #define LC_WORDS 6u
@@ -977,28 +1056,21 @@ __global__ __launch_bounds__(FR_THREADS) void k_light_cells(const uint8_t *frame
                                                             uint32_t *__restrict__ status, uint32_t *__restrict__ rec)
 {
     __shared__ uint32_t part[FR_THREADS / 64][LC_WORDS];
-    const uint64_t P = (uint64_t)W * H;
-    const uint32_t cell = blockIdx.x, cells = gridDim.x;
-    const uint32_t xc = x0 + (cell % ncx) * FC_CELL, yc = y0 + (cell / ncx) * FC_CELL; // the cell's first pixel
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t first = 2u * wave + (lane >> 5), col = lane & 31u;
+    const Cell c = cells_here(W, H, ncx, x0, y0);
     for (uint32_t j = blockIdx.y; j < (uint32_t)njobs; j += gridDim.y) {
         const abub_shift_job jb = jobs[j];
-        const bool ok = sh_job_ok(jb, frames_bytes, model_bytes, P); // (the same in every thread of every block of the job)
-        uint32_t *out = rec + ((uint64_t)j * cells + cell) * LC_WORDS;
-        if (cell == 0u && threadIdx.x == 0u)
-            status[j] = ok ? 0u : (uint32_t)ABUB_SHIFT_E_RANGE;
+        const bool ok = sh_job_ok(jb, frames_bytes, model_bytes, c.P);
+        uint32_t *out = cells_open<LC_WORDS>(j, ok, status, rec);
         if (!ok) {
-            if (threadIdx.x < LC_WORDS)
-                out[threadIdx.x] = 0u;
+            cells_zero<LC_WORDS>(out);
             continue;
         }
         const uint8_t *p = frames + jb.cur, *q = mu + jb.model;
-        uint32_t acc[LC_WORDS] = {0u, 0u, 0u, 0u, 0u, 0u};
+        uint32_t acc[LC_WORDS] = {};
 #pragma unroll
         for (uint32_t r = 0; r < FC_ROWS; ++r) {
-            const uint64_t i = (uint64_t)(yc + r * 8u + first) * W + xc + 4u * col;
-            const uint32_t a = sh_load4(p, i, P), b = sh_load4(q, i, P);
+            const uint64_t i = c.at(r);
+            const uint32_t a = sh_load4(p, i, c.P), b = sh_load4(q, i, c.P);
             acc[0] = __builtin_amdgcn_sad_u8(a, 0u, acc[0]);
             acc[1] = __builtin_amdgcn_udot4(a, a, acc[1], false);
             acc[2] = __builtin_amdgcn_udot4(a, b, acc[2], false);
@@ -1006,25 +1078,7 @@ __global__ __launch_bounds__(FR_THREADS) void k_light_cells(const uint8_t *frame
             acc[4] += (uint32_t)__builtin_popcount(lc_zero_bytes(a));
             acc[5] += (uint32_t)__builtin_popcount(lc_zero_bytes(~a));
         }
-#pragma unroll
-        for (int s = 32; s > 0; s >>= 1)
-#pragma unroll
-            for (uint32_t o = 0; o < LC_WORDS; ++o)
-                acc[o] += (uint32_t)__shfl_xor(acc[o], s);
-        if (lane == 0u) {
-#pragma unroll
-            for (uint32_t o = 0; o < LC_WORDS; ++o)
-                part[wave][o] = acc[o];
-        }
-        __syncthreads();
-        if (threadIdx.x < LC_WORDS) {
-            uint32_t v = part[0][threadIdx.x];
-#pragma unroll
-            for (int w = 1; w < FR_THREADS / 64; ++w)
-                v += part[w][threadIdx.x];
-            out[threadIdx.x] = v;
-        }
-        __syncthreads(); // (part is written again for the block's next job)
+        cells_close(c, acc, part, out);
     }
 }
 
@@ -1034,22 +1088,13 @@ extern "C" int abub_frame_light_cells_dev(const uint8_t *frames, size_t frames_b
                                           const abub_shift_job *jobs, int njobs, int W, int H, int x0, int y0, int ncx, int ncy,
                                           uint32_t *status, uint32_t *rec, void *stream)
 {
-    if (!frames || !mu || !jobs || !status || !rec || njobs < 0)
-        return set_err(ABUB_E_INVALID, "abub_frame_light_cells_dev: null pointer or negative count");
-    if (W < ABUB_FIELD_CELL || W > 65535 || H < ABUB_FIELD_CELL || H > 65535)
-        return set_err(ABUB_E_INVALID, "abub_frame_light_cells_dev: W and H must be in [128, 65535]");
-    // (ncx, ncy <= 511 once the sides are bounded, so the sums below cannot overflow an int)
-    if (ncx < 1 || ncy < 1 || ncx > W / ABUB_FIELD_CELL || ncy > H / ABUB_FIELD_CELL || x0 < 0 || y0 < 0 ||
-        x0 > W - ABUB_FIELD_CELL * ncx || y0 > H - ABUB_FIELD_CELL * ncy)
-        return set_err(ABUB_E_INVALID, "abub_frame_light_cells_dev: the grid of whole cells must lie inside the frame");
-    if (((uintptr_t)jobs & 7) || (((uintptr_t)status | (uintptr_t)rec) & 3))
-        return set_err(ABUB_E_INVALID, "abub_frame_light_cells_dev: jobs must be 8-byte aligned, status and rec 4-byte aligned");
-    if (njobs == 0)
-        return ABUB_OK;
-    const dim3 grid((unsigned)(ncx * ncy), (unsigned)(njobs < 65535 ? njobs : 65535)); // (at most 511 * 511 cells)
-    k_light_cells<<<grid, FR_THREADS, 0, (hipStream_t)stream>>>(frames, (uint64_t)frames_bytes, mu, (uint64_t)model_bytes, jobs, njobs,
-                                                                (uint32_t)W, (uint32_t)H, (uint32_t)ncx, (uint32_t)x0, (uint32_t)y0, status,
-                                                                rec);
+    const int chk = cells_check("abub_frame_light_cells_dev", frames && mu && jobs && status && rec, jobs, status, rec, njobs, W, H, x0,
+                                y0, ncx, ncy, 0);
+    if (chk != CELLS_LAUNCH)
+        return chk;
+    k_light_cells<<<cells_grid(ncx, ncy, njobs), FR_THREADS, 0, (hipStream_t)stream>>>(
+        frames, (uint64_t)frames_bytes, mu, (uint64_t)model_bytes, jobs, njobs, (uint32_t)W, (uint32_t)H, (uint32_t)ncx, (uint32_t)x0,
+        (uint32_t)y0, status, rec);
     HIPCHK(hipGetLastError());
     return ABUB_OK;
 }
@@ -1061,13 +1106,10 @@ extern "C" int abub_frame_light_cells_dev(const uint8_t *frames, size_t frames_b
 // focusCellsHost, the definition):
 //   rec[((j ncy + cy) ncx + cx) 5 + 0 .. 4] = sum gx^2, sum gy^2, sum gx hx, sum gy hy, the pixels with p == 0 or p == 255.
 //
-// The grid is cells x jobs; a block of four waves owns one cell of one job at a time and with it the cell's five words: it
-// writes each of them once with a plain store, so there is no atomic, no clearing launch and no other launch (the block of
-// cell 0 writes the job's status word).  It reads the cell with its ring once into two LDS tiles, one of the frame and one
-// of mu, each FO_TR = 130 rows of FO_RS = 33 dwords (row r, dword c: the four pixels from (xc - 1 + 4 c, yc - 1 + r) on):
-// 2 * 130 * 33 * 4 = 34320 bytes.  fc_cell's lane mapping: lane l owns dword l & 31 of the cell rows 8 k + 2 w + (l >> 5),
-// k < 16 (w: its wave); the two halves of a wave are the two lane groups of a ds_read_b32 / ds_read2_b32 and within a half
-// the lanes read 32 consecutive dwords of one tile row, so there is no bank conflict.  Of a cell row y the lane reads dwords
+// A block reads the cell with its ring once into two LDS tiles, one of the frame and one of mu, each FO_TR = 130 rows of
+// FO_RS = 33 dwords (row r, dword c: the four pixels from (xc - 1 + 4 c, yc - 1 + r) on): 2 * 130 * 33 * 4 = 34320 bytes.
+// The two halves of a wave are the two lane groups of a ds_read_b32 / ds_read2_b32 and within a half the lanes read 32
+// consecutive dwords of one tile row, so there is no bank conflict.  Of a cell row y the lane reads dwords
 // col and col + 1 of the tile rows y, y + 1, y + 2 of both tiles.  With d0, d1 those of tile row y + 1, its four pixels are
 // bytes 1 .. 4 of the pair: their left neighbours are d0, their right neighbours v_alignbyte_b32(d1, d0, 2), the pixels
 // themselves v_alignbyte_b32(d1, d0, 1); the pixels above and below are the same alignment by one byte of the tile rows y and
@@ -1076,20 +1118,18 @@ extern "C" int abub_frame_light_cells_dev(const uint8_t *frames, size_t frames_b
 // each product one v_dot4_u32_u8: seven per direction and dword.  The clipped pixels are the set top bits of
 // lc_zero_bytes(p) | lc_zero_bytes(~p).  A lane sums 64 pixels, so each of its eight u32 sums holds at most
 // 2 * 64 * 65025 < 2^24; the differences are formed per lane in i32, where the squares' are never negative and a product's
-// magnitude is at most 64 * 65025.  Summed over the wave with shuffles, over the waves through 20 words of LDS: a cell's
-// magnitude is at most 16384 * 65025 = 1065369600 < 2^31, and so is that of every partial sum.
+// magnitude is at most 64 * 65025.  A cell's magnitude is at most 16384 * 65025 = 1065369600 < 2^31, and so is that of
+// every partial sum.
 //
-// Bounds.  A job is read only if sh_job_ok holds; otherwise E_RANGE and a zero record, found alike by every block of the
-// job.  The launcher admits only grids with x0, y0 >= 1, x0 + 128 ncx + 1 <= W and y0 + 128 ncy + 1 <= H, so the tile's 130
-// rows yc - 1 .. yc + 128 lie inside the frame and so do the 130 pixels xc - 1 .. xc + 128 of each; a tile row's last dword
+// Bounds.  The ring is 1, so the tile's 130 rows yc - 1 .. yc + 128 lie inside the frame and so do the 130 pixels
+// xc - 1 .. xc + 128 of each; a tile row's last dword
 // ends at byte 132 of it, two behind the ring: sh_load4 tests the index itself against W * H, a byte beyond reads as 0, and
 // no lane uses a byte behind the ring (its last is byte 4 * 31 + 5 = 129).  A block whose tile lies far enough inside the
 // stream, its first byte index lo >= 3 and the index of its last dword's first byte lo + 129 W + 128 <= W * H - 8, fills it
 // through fo_fill_inside instead: every load is one of the two aligned dwords around a tile dword's first byte, at stream
 // bytes >= lo - 3 >= 0 and < lo + 129 W + 128 + 8 <= W * H, so inside the job's frame or model plane, which sh_job_ok has
 // placed inside its buffer.  Every other block (the first and the last rows of cells of a frame with no margin) keeps sh_load4.  LDS: tile row first + 8 k + 2 <= 129 < FO_TR,
-// dword col + 1 <= 32 < FO_RS; part[wave][o], o < 5.  Stores: status[j] and rec[(j * cells + cell) * 5 + t], j < njobs,
-// cell < cells, t < 5.
+// dword col + 1 <= 32 < FO_RS.
 namespace {
 
 #define FO_WORDS 5u
@@ -1146,24 +1186,17 @@ __global__ __launch_bounds__(FR_THREADS, 4) void k_focus_cells(const uint8_t *fr
 {
     __shared__ uint32_t tp[FO_TR * FO_RS], tm[FO_TR * FO_RS];
     __shared__ int32_t part[FR_THREADS / 64][FO_WORDS];
-    const uint64_t P = (uint64_t)W * H;
-    const uint32_t cell = blockIdx.x, cells = gridDim.x;
-    const uint32_t xc = x0 + (cell % ncx) * FC_CELL, yc = y0 + (cell / ncx) * FC_CELL; // the cell's first pixel
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t first = 2u * wave + (lane >> 5), col = lane & 31u;
+    const Cell c = cells_here(W, H, ncx, x0, y0);
     // the tile's bytes are those at lo + r W + 0 .. 131 of a stream, r < 130: inside iff every one of them has the two aligned
     // dwords around it within the stream wherever the stream begins (the same in every thread of the block, for every job)
-    const uint64_t lo = (uint64_t)(yc - 1u) * W + (xc - 1u);
-    const bool inside = lo >= 3u && lo + (uint64_t)(FO_TR - 1u) * W + 4u * FO_RS + 4u <= P;
+    const uint64_t lo = (uint64_t)(c.yc - 1u) * W + (c.xc - 1u);
+    const bool inside = lo >= 3u && lo + (uint64_t)(FO_TR - 1u) * W + 4u * FO_RS + 4u <= c.P;
     for (uint32_t j = blockIdx.y; j < (uint32_t)njobs; j += gridDim.y) {
         const abub_shift_job jb = jobs[j];
-        const bool ok = sh_job_ok(jb, frames_bytes, model_bytes, P); // (the same in every thread of every block of the job)
-        int32_t *out = rec + ((uint64_t)j * cells + cell) * FO_WORDS;
-        if (cell == 0u && threadIdx.x == 0u)
-            status[j] = ok ? 0u : (uint32_t)ABUB_SHIFT_E_RANGE;
+        const bool ok = sh_job_ok(jb, frames_bytes, model_bytes, c.P);
+        int32_t *out = cells_open<FO_WORDS>(j, ok, status, rec);
         if (!ok) {
-            if (threadIdx.x < FO_WORDS)
-                out[threadIdx.x] = 0;
+            cells_zero<FO_WORDS>(out);
             continue;
         }
         const uint8_t *p = frames + jb.cur, *q = mu + jb.model;
@@ -1173,45 +1206,27 @@ __global__ __launch_bounds__(FR_THREADS, 4) void k_focus_cells(const uint8_t *fr
         } else {
             for (uint32_t i = threadIdx.x; i < FO_TR * FO_RS; i += FR_THREADS) {
                 const uint64_t at = lo + (uint64_t)(i / FO_RS) * W + 4u * (i % FO_RS);
-                tp[i] = sh_load4(p, at, P);
-                tm[i] = sh_load4(q, at, P);
+                tp[i] = sh_load4(p, at, c.P);
+                tm[i] = sh_load4(q, at, c.P);
             }
         }
         __syncthreads();
         uint32_t xs = 0, xc2 = 0, xp = 0, xn = 0, ys = 0, yc2 = 0, yp = 0, yn = 0, clip = 0;
 #pragma unroll
         for (uint32_t r = 0; r < FC_ROWS; ++r) {
-            const uint32_t at = (r * 8u + first) * FO_RS + col; // tile row y: the pixels above cell row y
+            const uint32_t at = (r * 8u + c.first) * FO_RS + c.col; // tile row y: the pixels above cell row y
             const uint32_t pu = __builtin_amdgcn_alignbyte(tp[at + 1u], tp[at], 1u), mu_ = __builtin_amdgcn_alignbyte(tm[at + 1u], tm[at], 1u);
             const uint32_t p0 = tp[at + FO_RS], p1 = tp[at + FO_RS + 1u], m0 = tm[at + FO_RS], m1 = tm[at + FO_RS + 1u];
             const uint32_t pd = __builtin_amdgcn_alignbyte(tp[at + 2u * FO_RS + 1u], tp[at + 2u * FO_RS], 1u);
             const uint32_t md = __builtin_amdgcn_alignbyte(tm[at + 2u * FO_RS + 1u], tm[at + 2u * FO_RS], 1u);
             fo_dir(p0, __builtin_amdgcn_alignbyte(p1, p0, 2u), m0, __builtin_amdgcn_alignbyte(m1, m0, 2u), xs, xc2, xp, xn);
             fo_dir(pu, pd, mu_, md, ys, yc2, yp, yn);
-            const uint32_t c = __builtin_amdgcn_alignbyte(p1, p0, 1u);
-            clip += (uint32_t)__builtin_popcount(lc_zero_bytes(c) | lc_zero_bytes(~c));
+            const uint32_t x = __builtin_amdgcn_alignbyte(p1, p0, 1u);
+            clip += (uint32_t)__builtin_popcount(lc_zero_bytes(x) | lc_zero_bytes(~x));
         }
         int32_t acc[FO_WORDS] = {(int32_t)(xs - 2u * xc2), (int32_t)(ys - 2u * yc2), (int32_t)xp - (int32_t)xn, (int32_t)yp - (int32_t)yn,
                                  (int32_t)clip};
-#pragma unroll
-        for (int s = 32; s > 0; s >>= 1)
-#pragma unroll
-            for (uint32_t o = 0; o < FO_WORDS; ++o)
-                acc[o] += __shfl_xor(acc[o], s);
-        if (lane == 0u) {
-#pragma unroll
-            for (uint32_t o = 0; o < FO_WORDS; ++o)
-                part[wave][o] = acc[o];
-        }
-        __syncthreads();
-        if (threadIdx.x < FO_WORDS) {
-            int32_t v = part[0][threadIdx.x];
-#pragma unroll
-            for (int w = 1; w < FR_THREADS / 64; ++w)
-                v += part[w][threadIdx.x];
-            out[threadIdx.x] = v;
-        }
-        __syncthreads(); // (the tiles and part are written again for the block's next job)
+        cells_close(c, acc, part, out);
     }
 }
 
@@ -1221,22 +1236,13 @@ extern "C" int abub_frame_focus_cells_dev(const uint8_t *frames, size_t frames_b
                                           const abub_shift_job *jobs, int njobs, int W, int H, int x0, int y0, int ncx, int ncy,
                                           uint32_t *status, int32_t *rec, void *stream)
 {
-    if (!frames || !mu || !jobs || !status || !rec || njobs < 0)
-        return set_err(ABUB_E_INVALID, "abub_frame_focus_cells_dev: null pointer or negative count");
-    if (W < ABUB_FIELD_CELL + 2 || W > 65535 || H < ABUB_FIELD_CELL + 2 || H > 65535)
-        return set_err(ABUB_E_INVALID, "abub_frame_focus_cells_dev: W and H must be in [130, 65535]");
-    // (ncx, ncy <= 511 once the sides are bounded, so the sums below cannot overflow an int)
-    if (ncx < 1 || ncy < 1 || ncx > (W - 2) / ABUB_FIELD_CELL || ncy > (H - 2) / ABUB_FIELD_CELL || x0 < 1 || y0 < 1 ||
-        x0 > W - 1 - ABUB_FIELD_CELL * ncx || y0 > H - 1 - ABUB_FIELD_CELL * ncy)
-        return set_err(ABUB_E_INVALID, "abub_frame_focus_cells_dev: the grid of whole cells and a ring of one pixel must lie inside the frame");
-    if (((uintptr_t)jobs & 7) || (((uintptr_t)status | (uintptr_t)rec) & 3))
-        return set_err(ABUB_E_INVALID, "abub_frame_focus_cells_dev: jobs must be 8-byte aligned, status and rec 4-byte aligned");
-    if (njobs == 0)
-        return ABUB_OK;
-    const dim3 grid((unsigned)(ncx * ncy), (unsigned)(njobs < 65535 ? njobs : 65535)); // (at most 511 * 511 cells)
-    k_focus_cells<<<grid, FR_THREADS, 0, (hipStream_t)stream>>>(frames, (uint64_t)frames_bytes, mu, (uint64_t)model_bytes, jobs, njobs,
-                                                                (uint32_t)W, (uint32_t)H, (uint32_t)ncx, (uint32_t)x0, (uint32_t)y0, status,
-                                                                rec);
+    const int chk = cells_check("abub_frame_focus_cells_dev", frames && mu && jobs && status && rec, jobs, status, rec, njobs, W, H, x0,
+                                y0, ncx, ncy, 1);
+    if (chk != CELLS_LAUNCH)
+        return chk;
+    k_focus_cells<<<cells_grid(ncx, ncy, njobs), FR_THREADS, 0, (hipStream_t)stream>>>(
+        frames, (uint64_t)frames_bytes, mu, (uint64_t)model_bytes, jobs, njobs, (uint32_t)W, (uint32_t)H, (uint32_t)ncx, (uint32_t)x0,
+        (uint32_t)y0, status, rec);
     HIPCHK(hipGetLastError());
     return ABUB_OK;
 }
@@ -1248,10 +1254,8 @@ extern "C" int abub_frame_focus_cells_dev(const uint8_t *frames, size_t frames_b
 //   rec[((j ncy + cy) ncx + cx) 6 + 0 .. 5] = the pixels with |d| > s, the pixels where p or r is 0 or 255, sum d and sum d^2
 //   over the pixels with |d| <= s (the inside ones), sum |d| and sum d^2 over all.
 //
-// k_light_cells' structure with a third stream: the grid is cells x jobs, a block of four waves owns one cell of one job at
-// a time and writes its six words once with plain stores (the block of cell 0 writes the job's status word); lane l owns
-// dword l & 31 of the rows 8 k + 2 w + (l >> 5), k < 16; p, r and s come straight into registers through sh_load4.  Per
-// dword: sum |d| is v_sad_u8(p, r); sum d^2 = p.p + r.r - 2 p.r from three v_dot4_u32_u8, exact mod 2^32.  sat(|d| - s) of
+// No LDS tile: p, r and s come straight into registers through sh_load4.  Per dword: sum |d| is v_sad_u8(p, r);
+// sum d^2 = p.p + r.r - 2 p.r from three v_dot4_u32_u8, exact mod 2^32.  sat(|d| - s) of
 // the four bytes comes as u16 pairs (widen, pk_absdiff, pk_subsat); pk_min1 makes each 1 where the pixel is over, v_perm
 // packs the four into the bytes of a dword `over`, and (over ^ 0x01010101) * 0xff is 0xff in the bytes of the inside pixels
 // (a byte is 0 or 1 times 255: no carry).  With P = p & mask and R = r & mask an outside pixel contributes 0 - 0, so the
@@ -1260,12 +1264,10 @@ extern "C" int abub_frame_focus_cells_dev(const uint8_t *frames, size_t frames_b
 // A lane sums 64 pixels: each of its nine partial sums is at most 64 * 2 * 65025 < 2^24.  A cell has 16384: the sums of
 // squares and of |d| at most 16384 * 255^2 = 1065369600 < 2^31, sum d a magnitude of at most 16384 * 255, the counts at most
 // 16384.  The differences (sum d, the two p.p + r.r - 2 p.r) are taken per lane in u32, where they are exact mod 2^32, and
-// the true value of every word fits i32; summed over the wave with shuffles, over the waves through 24 words of LDS.
+// the true value of every word fits i32, and the sums over lanes and waves are exact mod 2^32 as well.
 //
-// Bounds.  A job is read only if all three of its streams lie inside their buffers (nc_job_ok); otherwise E_RANGE and a
-// zero record, found alike by every block of the job.  The launcher admits only grids with x0 + 128 ncx <= W and
-// y0 + 128 ncy <= H, so every dword a lane loads lies wholly inside the W * H bytes of its stream; sh_load4 tests the index
-// against W * H besides.  Stores: status[j] and rec[(j * cells + cell) * 6 + t], j < njobs, cell < cells, t < 6.
+// Bounds.  A job is read only if all three of its streams lie inside their buffers (nc_job_ok).  No ring: every dword a
+// lane loads lies wholly inside the W * H bytes of its stream; sh_load4 tests the index against W * H besides.
 namespace {
 
 #define NC_WORDS 6u
@@ -1281,28 +1283,21 @@ __global__ __launch_bounds__(FR_THREADS) void k_noise_cells(const uint8_t *frame
                                                             uint32_t *__restrict__ status, uint32_t *__restrict__ rec)
 {
     __shared__ uint32_t part[FR_THREADS / 64][NC_WORDS];
-    const uint64_t P = (uint64_t)W * H;
-    const uint32_t cell = blockIdx.x, cells = gridDim.x;
-    const uint32_t xc = x0 + (cell % ncx) * FC_CELL, yc = y0 + (cell / ncx) * FC_CELL; // the cell's first pixel
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    const uint32_t first = 2u * wave + (lane >> 5), col = lane & 31u;
+    const Cell c = cells_here(W, H, ncx, x0, y0);
     for (uint32_t j = blockIdx.y; j < (uint32_t)njobs; j += gridDim.y) {
         const abub_stat_job jb = jobs[j];
-        const bool ok = nc_job_ok(jb, frames_bytes, model_bytes, P); // (the same in every thread of every block of the job)
-        uint32_t *out = rec + ((uint64_t)j * cells + cell) * NC_WORDS;
-        if (cell == 0u && threadIdx.x == 0u)
-            status[j] = ok ? 0u : (uint32_t)ABUB_SHIFT_E_RANGE;
+        const bool ok = nc_job_ok(jb, frames_bytes, model_bytes, c.P);
+        uint32_t *out = cells_open<NC_WORDS>(j, ok, status, rec);
         if (!ok) {
-            if (threadIdx.x < NC_WORDS)
-                out[threadIdx.x] = 0u;
+            cells_zero<NC_WORDS>(out);
             continue;
         }
         const uint8_t *p = frames + jb.cur, *q = frames + jb.ref, *sg = sigma6 + jb.model;
         uint32_t nOver = 0, nClip = 0, inP = 0, inR = 0, inSq = 0, inPr = 0, sad = 0, allSq = 0, allPr = 0;
 #pragma unroll
         for (uint32_t r = 0; r < FC_ROWS; ++r) {
-            const uint64_t i = (uint64_t)(yc + r * 8u + first) * W + xc + 4u * col;
-            const uint32_t a = sh_load4(p, i, P), b = sh_load4(q, i, P), s = sh_load4(sg, i, P);
+            const uint64_t i = c.at(r);
+            const uint32_t a = sh_load4(p, i, c.P), b = sh_load4(q, i, c.P), s = sh_load4(sg, i, c.P);
             sad = __builtin_amdgcn_sad_u8(a, b, sad);
             allSq = __builtin_amdgcn_udot4(a, a, allSq, false);
             allSq = __builtin_amdgcn_udot4(b, b, allSq, false);
@@ -1321,25 +1316,7 @@ __global__ __launch_bounds__(FR_THREADS) void k_noise_cells(const uint8_t *frame
             nClip += (uint32_t)__builtin_popcount(lc_zero_bytes(a) | lc_zero_bytes(~a) | lc_zero_bytes(b) | lc_zero_bytes(~b));
         }
         uint32_t acc[NC_WORDS] = {nOver, nClip, inP - inR, inSq - 2u * inPr, sad, allSq - 2u * allPr};
-#pragma unroll
-        for (int s = 32; s > 0; s >>= 1)
-#pragma unroll
-            for (uint32_t o = 0; o < NC_WORDS; ++o)
-                acc[o] += (uint32_t)__shfl_xor(acc[o], s);
-        if (lane == 0u) {
-#pragma unroll
-            for (uint32_t o = 0; o < NC_WORDS; ++o)
-                part[wave][o] = acc[o];
-        }
-        __syncthreads();
-        if (threadIdx.x < NC_WORDS) {
-            uint32_t v = part[0][threadIdx.x];
-#pragma unroll
-            for (int w = 1; w < FR_THREADS / 64; ++w)
-                v += part[w][threadIdx.x];
-            out[threadIdx.x] = v;
-        }
-        __syncthreads(); // (part is written again for the block's next job)
+        cells_close(c, acc, part, out);
     }
 }
 
@@ -1349,22 +1326,13 @@ extern "C" int abub_frame_noise_cells_dev(const uint8_t *frames, size_t frames_b
                                           const abub_stat_job *jobs, int njobs, int W, int H, int x0, int y0, int ncx, int ncy,
                                           uint32_t *status, int32_t *rec, void *stream)
 {
-    if (!frames || !sigma6 || !jobs || !status || !rec || njobs < 0)
-        return set_err(ABUB_E_INVALID, "abub_frame_noise_cells_dev: null pointer or negative count");
-    if (W < ABUB_FIELD_CELL || W > 65535 || H < ABUB_FIELD_CELL || H > 65535)
-        return set_err(ABUB_E_INVALID, "abub_frame_noise_cells_dev: W and H must be in [128, 65535]");
-    // (ncx, ncy <= 511 once the sides are bounded, so the sums below cannot overflow an int)
-    if (ncx < 1 || ncy < 1 || ncx > W / ABUB_FIELD_CELL || ncy > H / ABUB_FIELD_CELL || x0 < 0 || y0 < 0 ||
-        x0 > W - ABUB_FIELD_CELL * ncx || y0 > H - ABUB_FIELD_CELL * ncy)
-        return set_err(ABUB_E_INVALID, "abub_frame_noise_cells_dev: the grid of whole cells must lie inside the frame");
-    if (((uintptr_t)jobs & 7) || (((uintptr_t)status | (uintptr_t)rec) & 3))
-        return set_err(ABUB_E_INVALID, "abub_frame_noise_cells_dev: jobs must be 8-byte aligned, status and rec 4-byte aligned");
-    if (njobs == 0)
-        return ABUB_OK;
-    const dim3 grid((unsigned)(ncx * ncy), (unsigned)(njobs < 65535 ? njobs : 65535)); // (at most 511 * 511 cells)
-    k_noise_cells<<<grid, FR_THREADS, 0, (hipStream_t)stream>>>(frames, (uint64_t)frames_bytes, sigma6, (uint64_t)model_bytes, jobs, njobs,
-                                                                (uint32_t)W, (uint32_t)H, (uint32_t)ncx, (uint32_t)x0, (uint32_t)y0, status,
-                                                                (uint32_t *)rec);
+    const int chk = cells_check("abub_frame_noise_cells_dev", frames && sigma6 && jobs && status && rec, jobs, status, rec, njobs, W, H,
+                                x0, y0, ncx, ncy, 0);
+    if (chk != CELLS_LAUNCH)
+        return chk;
+    k_noise_cells<<<cells_grid(ncx, ncy, njobs), FR_THREADS, 0, (hipStream_t)stream>>>(
+        frames, (uint64_t)frames_bytes, sigma6, (uint64_t)model_bytes, jobs, njobs, (uint32_t)W, (uint32_t)H, (uint32_t)ncx, (uint32_t)x0,
+        (uint32_t)y0, status, (uint32_t *)rec);
     HIPCHK(hipGetLastError());
     return ABUB_OK;
 }
