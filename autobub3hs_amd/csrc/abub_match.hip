@@ -23,6 +23,7 @@ constexpr int MWAVES = 4;            // waves per workgroup (stacked vertically,
 constexpr int MTPL = 16384 / 16;     // uint4 entries of the LDS template chunk (16 KiB)
 constexpr int WS_ROWS = 8;           // output rows per workgroup of k_match_wsum2
 constexpr int WS_MAXW = 4096;        // widest frame k_match_wsum2 keeps in LDS
+constexpr int WS_MAXTH = 66051;      // tallest template its u32 column sums hold: 66051 * 255 * 255 < 2^32
 
 struct MatchGeom {
     int rw, rh, nc, ybl, nsplit, rsplit, flushEvery;
@@ -179,7 +180,7 @@ __global__ __launch_bounds__(256) void k_match_num(const uint8_t *__restrict__ f
 }
 
 // wsum2[job][y][x] = sum over the th x tw window of I^2: column window sums cs[x] (u32: th * 65025 < 2^32 for
-// th <= 66051) slid down the rows, then per row an exclusive prefix sum P (u64) and P[x + tw] - P[x]
+// th <= WS_MAXTH) slid down the rows, then per row an exclusive prefix sum P (u64) and P[x + tw] - P[x]
 __global__ __launch_bounds__(256) void k_match_wsum2(const uint8_t *__restrict__ frames, int W, int H,
                                                      const uint32_t *__restrict__ fidx, int tw, int th, int rw, int rh,
                                                      unsigned long long *__restrict__ wsum2)
@@ -374,11 +375,19 @@ __global__ __launch_bounds__(64) void k_match_sub(const float *__restrict__ res,
     out[job] = make_float2(sx * inv, sy * inv);
 }
 
+// the shapes every entry admits: k_match_wsum2 keeps a frame row and u32 column sums in LDS, k_match_num one template row
+// of nc words, k_match_first a u32 placement index with 0xffffffff for "none"
+static bool match_shape_ok(int W, int H, int tw, int th, int njobs)
+{
+    return W > 0 && H > 0 && tw > 0 && th > 0 && tw <= W && th <= H && njobs > 0 && njobs <= 65535 && W <= WS_MAXW &&
+           (tw + 2) / 4 + 1 <= MTPL && th <= WS_MAXTH && (H - th + 1) <= 65535 * MR * MWAVES &&
+           (size_t)(W - tw + 1) * (size_t)(H - th + 1) < 0xffffffffull;
+}
+
 static bool match_args_ok(const uint8_t *frames, int W, int H, const uint32_t *fidx, int njobs, const uint8_t *tmpl,
                           int tw, int th)
 {
-    return frames && fidx && tmpl && W > 0 && H > 0 && tw > 0 && th > 0 && tw <= W && th <= H && njobs > 0 &&
-           njobs <= 65535 && W <= WS_MAXW && (tw + 2) / 4 + 1 <= MTPL && (H - th + 1) <= 65535 * MR * MWAVES;
+    return frames && fidx && tmpl && match_shape_ok(W, H, tw, th, njobs);
 }
 
 static int launch_terms(const uint8_t *frames, int W, int H, const uint32_t *fidx, int njobs, const uint8_t *tmpl,
@@ -413,7 +422,7 @@ extern "C" int abub_match_ccorr_batch_dev(const uint8_t *frames, int W, int H, c
 
 extern "C" size_t abub_match_best_scratch_bytes(int W, int H, int tw, int th, int njobs)
 {
-    if (W <= 0 || H <= 0 || tw <= 0 || th <= 0 || tw > W || th > H || njobs <= 0)
+    if (!match_shape_ok(W, H, tw, th, njobs))
         return 0;
     const size_t n = (size_t)(W - tw + 1) * (H - th + 1) * njobs;
     return 2 * align256(n * 8) + align256(n * 4) + 3 * align256((size_t)njobs * 4) + 256;
@@ -424,7 +433,7 @@ extern "C" int abub_match_best_batch_dev(const uint8_t *frames, int W, int H, co
                                          size_t scratch_bytes, void *stream)
 {
     if (!match_args_ok(frames, W, H, frame_idx, njobs, tmpl, tw, th) || !best_xy || !scratch ||
-        scratch_bytes < abub_match_best_scratch_bytes(W, H, tw, th, njobs))
+        ((uintptr_t)scratch & 255) || scratch_bytes < abub_match_best_scratch_bytes(W, H, tw, th, njobs))
         return set_err(ABUB_E_INVALID, "abub_match_best_batch_dev: bad arguments");
     hipStream_t st = (hipStream_t)stream;
     const int rw = W - tw + 1, rh = H - th + 1;

@@ -845,22 +845,31 @@ def peek_planes(diff, frames, items, rects, W, H, out, diff_bytes=None, frames_b
     return status[:n].cpu().numpy()
 
 
-def match_terms(frames, frame_idx, tmpl):
+def match_terms(frames, frame_idx, tmpl, out=None):
     """Exact CCORR terms (abub_match_ccorr_batch_dev): frames u8 [N,H,W] (any slab of frames), frame_idx int32 [njobs]
-    (frame of each job), tmpl u8 [th,tw] -> (num, wsum2), each int64 [njobs, H-th+1, W-tw+1] holding the u64 sums."""
+    (frame of each job), tmpl u8 [th,tw] -> (num, wsum2), each int64 [njobs, H-th+1, W-tw+1] holding the u64 sums.
+    out: (num, wsum2) of that shape and type to write in place (default: fresh tensors)."""
     _need_cuda(frames, frame_idx, tmpl)
     H, W = frames.shape[-2:]
     th, tw = tmpl.shape
     n = frame_idx.numel()
-    num = torch.empty((n, H - th + 1, W - tw + 1), dtype=torch.int64, device=frames.device)
-    w2 = torch.empty_like(num)
+    shape = (n, H - th + 1, W - tw + 1)
+    if out is None:
+        num = torch.empty(shape, dtype=torch.int64, device=frames.device)
+        w2 = torch.empty_like(num)
+    else:
+        num, w2 = out
+        _need_cuda(num, w2)
+        assert num.dtype == w2.dtype == torch.int64 and tuple(num.shape) == tuple(w2.shape) == shape
     _lib.check(_lib.lib().abub_match_ccorr_batch_dev(_ptr(frames), W, H, _ptr(frame_idx), n, _ptr(tmpl), tw, th,
                                                      _ptr(num), _ptr(w2), _stream()), "abub_match_ccorr_batch_dev")
     return num, w2
 
 
-def match_best(frames, frame_idx, tmpl, scratch=None):
-    """Best template position per job, computed on the device (abub_match_best_batch_dev) -> float32 [njobs, 2] (x, y)."""
+def match_best(frames, frame_idx, tmpl, scratch=None, out=None):
+    """Best template position per job, computed on the device (abub_match_best_batch_dev) -> float32 [njobs, 2] (x, y).
+    scratch: u8, contiguous, 256-byte aligned, at least abub_match_best_scratch_bytes; out: float32, contiguous, at least
+    2 * njobs elements, written in place and returned (both default to fresh tensors)."""
     _need_cuda(frames, frame_idx, tmpl)
     H, W = frames.shape[-2:]
     th, tw = tmpl.shape
@@ -868,7 +877,11 @@ def match_best(frames, frame_idx, tmpl, scratch=None):
     need = _lib.lib().abub_match_best_scratch_bytes(W, H, tw, th, n)
     if scratch is None:
         scratch = torch.empty(max(need, 1), dtype=torch.uint8, device=frames.device)
-    out = torch.empty((n, 2), dtype=torch.float32, device=frames.device)
+    if out is None:
+        out = torch.empty((n, 2), dtype=torch.float32, device=frames.device)
+    else:
+        _need_cuda(out)
+        assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() >= 2 * n
     _lib.check(_lib.lib().abub_match_best_batch_dev(_ptr(frames), W, H, _ptr(frame_idx), n, _ptr(tmpl), tw, th,
                                                     _ptr(out), _ptr(scratch), scratch.numel(), _stream()),
                "abub_match_best_batch_dev")

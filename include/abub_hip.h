@@ -406,18 +406,21 @@ int abub_match_ccorr_dev(const uint8_t *img, int W, int H, const uint8_t *tmpl, 
 /* Batched form of abub_match_ccorr_dev (same integers) for the bellows veto of many stacks at once
  * (L3Localizer.cpp:292-390, TrackAFeature :473-510, whose matchTemplate searches the whole frame, :485): job k
  * matches the template against frame frame_idx[k] of the slab `frames` ([..][H][W]); frame_idx: njobs u32 (device).
- * num / wsum2: [njobs][H-th+1][W-tw+1].  W <= 4096, tw <= 4090; tw > W, th > H or njobs <= 0 -> ABUB_E_INVALID. */
+ * num / wsum2: [njobs][H-th+1][W-tw+1].  Limits: W <= 4096, tw <= 4093, th <= 66051 (the u32 column sums of the
+ * window energy), njobs <= 65535, (W-tw+1) * (H-th+1) < 2^32 - 1 (placement indices are u32); beyond them, or with
+ * tw > W, th > H or njobs <= 0 -> ABUB_E_INVALID before anything is launched. */
 int abub_match_ccorr_batch_dev(const uint8_t *frames, int W, int H, const uint32_t *frame_idx, int njobs,
                                const uint8_t *tmpl, int tw, int th, unsigned long long *num, unsigned long long *wsum2,
                                void *stream);
 /* The whole of TrackAFeature on the device (L3Localizer.cpp:499-510: CCORR_NORMED, normalize(NORM_MINMAX), minMaxLoc,
  * 3x3 sub-pixel centre of mass), bit for bit what the host's bestMatchFromTerms makes of the terms above:
  * best_xy[2k], best_xy[2k+1] = best match of job k (float x, y).  scratch: device memory of at least
- * abub_match_best_scratch_bytes(W, H, tw, th, njobs) bytes, 256-byte aligned (ABUB_E_INVALID if smaller). */
+ * abub_match_best_scratch_bytes(W, H, tw, th, njobs) bytes, 256-byte aligned (ABUB_E_INVALID if smaller or
+ * misaligned).  The limits of abub_match_ccorr_batch_dev hold here too. */
 int abub_match_best_batch_dev(const uint8_t *frames, int W, int H, const uint32_t *frame_idx, int njobs,
                               const uint8_t *tmpl, int tw, int th, float *best_xy, void *scratch, size_t scratch_bytes,
                               void *stream);
-/* 0 for impossible shapes */
+/* 0 for every shape the two entries above refuse */
 size_t abub_match_best_scratch_bytes(int W, int H, int tw, int th, int njobs);
 /* img = saturate(img - sub) in place + its 256-bin histogram (`overTheSigma -= diff_frame`, L3Localizer.cpp:362). */
 int abub_subsat_hist_dev(uint8_t *img, const uint8_t *sub, int W, int H, uint32_t *hist, void *stream);

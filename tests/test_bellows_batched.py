@@ -11,6 +11,8 @@ import numpy as np
 import pytest
 from PIL import Image
 
+from matchref import match_geometry, same_xy
+
 from autobub3hs_amd import _lib, host, synth
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -140,16 +142,6 @@ def test_batch_terms_equal_per_event_kernel_at_full_size():
         assert torch.equal(num[k], on) and torch.equal(w2[k], ow), k
 
 
-def match_geometry(W, H, tw, th, njobs):
-    """(nsplit, template rows per workgroup, flush interval in image rows) of k_match_num (match_geom, abub_match.hip)"""
-    rw, rh = W - tw + 1, H - th + 1
-    ybl = (rh + 31) // 32
-    base = ((rw + 255) // 256) * ybl * njobs
-    nsplit = 1 if base >= 1024 else min((1024 + base - 1) // base, max(1, th // 32))
-    rsplit = (th + nsplit - 1) // nsplit
-    return (th + rsplit - 1) // rsplit, rsplit, 0xffffffff // (65025 * tw)
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("W,H,tw,th,njobs", [(1680, 1050, 178, 557, 12), (4096, 60, 4000, 40, 2)])
 def test_batch_terms_u64_flush(W, H, tw, th, njobs):
@@ -178,12 +170,6 @@ def test_batch_terms_u64_flush(W, H, tw, th, njobs):
             j = 1 - k
             assert torch.equal(num[j], on) and torch.equal(w2[j], ow), k
             assert torch.equal(num[j + 2 * (njobs // 2 - 1)], on), k
-
-
-def same_xy(a, b):
-    """Bit-identical float32 pairs; a flat plane has zero mass and gives NaN on every route (any NaN matches)."""
-    a, b = np.asarray(a, np.float32), np.asarray(b, np.float32)
-    return all((np.isnan(u) and np.isnan(v)) or u.view(np.uint32) == v.view(np.uint32) for u, v in zip(a, b))
 
 
 def _device_best(frames_np, idx, tmpl):
