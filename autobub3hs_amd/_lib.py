@@ -111,6 +111,7 @@ SIGNATURES = {
     "abub_frame_light_cells_dev": (_i, [_vp, _sz, _vp, _sz, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "abub_frame_focus_cells_dev": (_i, [_vp, _sz, _vp, _sz, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "abub_frame_noise_cells_dev": (_i, [_vp, _sz, _vp, _sz, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "abub_frame_lines_dev": (_i, [_vp, _sz, _vp, _sz, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "abub_peek_planes_dev": (_i, [_vp, _sz, _vp, _sz, _vp, _i, _vp, _i, _i, _i, _vp, _sz, _vp, _vp]),
     "abub_diff_hist_chained_deferred_dev": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _i, _i, _vp, C.c_uint32, _vp, _vp, _vp]),
     "abub_diff_hist_pieces_dev": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),

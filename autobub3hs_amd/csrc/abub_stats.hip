@@ -1,7 +1,8 @@
 // abub_stats.hip -- per-frame statistics of resident frames: abub_frame_stats_dev (include/abub_hip.h, DESIGN section 3,
 // "Surveying a run"); below it the per-pixel planes (abub_pixel_activity_dev), the shift search (abub_frame_shift_dev) and
 // the per-cell shift field (abub_frame_shift_cells_dev), the per-cell light record (abub_frame_light_cells_dev), the
-// per-cell edge agreement (abub_frame_focus_cells_dev) and the per-cell noise record (abub_frame_noise_cells_dev), each under a header of its own.  What a byte loop over a decoded frame does on a host thread (host/survey.cpp frameStatsHost, the
+// per-cell edge agreement (abub_frame_focus_cells_dev), the per-cell noise record (abub_frame_noise_cells_dev) and the per-line sums
+// (abub_frame_lines_dev), each under a header of its own.  What a byte loop over a decoded frame does on a host thread (host/survey.cpp frameStatsHost, the
 // definition): per job the grey-level range, sum, sum of squares, black and saturated pixels of the frame, and against a
 // model (mu, sigma6) and a reference frame the count and sum of sat(|p - m| - s) and of sat(|p - r| - s).
 //
@@ -1333,6 +1334,225 @@ extern "C" int abub_frame_noise_cells_dev(const uint8_t *frames, size_t frames_b
     k_noise_cells<<<cells_grid(ncx, ncy, njobs), FR_THREADS, 0, (hipStream_t)stream>>>(
         frames, (uint64_t)frames_bytes, sigma6, (uint64_t)model_bytes, jobs, njobs, (uint32_t)W, (uint32_t)H, (uint32_t)ncx, (uint32_t)x0,
         (uint32_t)y0, status, (uint32_t *)rec);
+    HIPCHK(hipGetLastError());
+    return ABUB_OK;
+}
+
+// ---- per-line sums of whole frames: abub_frame_lines_dev ("Surveying a run for torn, repeated and banded
+// frames") ----------------------------------------------------------------------------------------------------------------
+// Per job and image row y five u32 over the row's W pixels p of the frame, m of mu and r of the reference frame (host/survey.cpp
+// linesHost, the definition): sum p, sum |p - m|, the pixels at 0 or 255, sum |p - r|, the pixels with p == r (the last two 0
+// for a job without a reference, ref == UINT64_MAX); per image column x the first three over the column's H pixels.
+//
+// One block of four waves owns one job at a time and with it every output word of the job: plain stores, no atomics on
+// memory, no clearing launch.  The frame is walked in bands of LN_BAND rows and, inside a band, in strips of LN_STRIP pixels
+// across; in a strip lane l owns the 16 pixels from 16 l on, down the band, and wave w takes the band's rows w, w + 4, ...
+// (48 bytes of a lane in flight per row, 16 waves on a CU: no unrolling over rows).  A lane keeps its 16 columns' three sums in 48 registers through the strip; at the strip's end the
+// four waves add them into 48 x 64 words of LDS (ds_add, integers: any order gives the same bits), and thread t hands columns
+// t, t + 256, ... to cols[]: stored in the frame's first band, added to its own word in the later ones (the same thread every
+// time, so program order is enough).  A row's five sums are packed into three words (sum p < 2^18 and n_clip <= 1024 in one,
+// sum |p - m| and n_same in the next, sum |p - r|), summed over the wave by the butterfly, and lane 0 keeps the row's five
+// words in LDS: stored in the band's first strip, added to in the others, by that one thread; after the band's last strip
+// the block writes the band's rows out in one contiguous run.
+// Loads: a lane's 16 bytes of a stream come in one 16-byte load where the row's address in the strip is a multiple of 16 and
+// the bytes end inside the stream, else as five aligned dwords and v_alignbyte (single bytes at the stream's two ends).
+// Bytes past the row's end belong to the next row (or are zeros past the stream): the row sums mask them out, and the column
+// sums of columns >= W are never stored.
+// Bounds.  A job is read only if its frame and its plane lie inside their buffers and its reference is absent or inside
+// (ln_job_ok); otherwise E_RANGE and zero records.  Every load is at an index below P = W * H of its stream (ln_load16 tests
+// every one of its three forms).  Stores: status[j], rows[(j H + y) 5 + k] with y < H, cols[(j W + x) 3 + k] with
+// x < W, j < njobs.  Sums: a lane's column sums over at most 256 rows, the LDS words over at most 1024 rows, a word of the
+// result at most 65535 * 255 < 2^24.
+namespace {
+
+#define LN_ROW_WORDS ((uint32_t)ABUB_LINES_ROW_WORDS)
+#define LN_COL_WORDS ((uint32_t)ABUB_LINES_COL_WORDS)
+#define LN_WAVES (FR_THREADS / 64u)
+#define LN_STRIP 1024u /* pixels of a strip across: 64 lanes of 16 */
+#define LN_BAND 1024u  /* rows of a band: 20 KiB of row words in LDS */
+#define LN_PAD 65u     /* words of a row of the column sums in LDS (64 lanes and one: the readers spread over the banks) */
+static_assert(LN_ROW_WORDS == 5u && LN_COL_WORDS == 3u, "the packing below is of five and three words");
+
+__device__ __forceinline__ bool ln_job_ok(const abub_stat_job &jb, uint64_t frames_bytes, uint64_t model_bytes, uint64_t P)
+{
+    return frame_in_range(jb.cur, frames_bytes, P) && frame_in_range(jb.model, model_bytes, P) &&
+           (jb.ref == ST_NONE || frame_in_range(jb.ref, frames_bytes, P));
+}
+
+// the 16 bytes from index i on of a stream of P bytes, in memory order (wide: the address is a multiple of 16); bytes at P
+// and beyond read as 0; zeros where `on` is false.  Nothing outside [s, s + P) is touched: the five aligned dwords around
+// the bytes only where they lie inside, else byte by byte (the stream's first and last bytes)
+// (P = W * H <= 65535^2 and i < P + 1040: 32 bits hold every index and every sum below)
+__device__ __forceinline__ u32x4 ln_load16(const uint8_t *s, uint32_t i, uint32_t P, bool wide, bool on)
+{
+    u32x4 v = {0u, 0u, 0u, 0u};
+    if (!on)
+        return v;
+    if (wide && i + 16u <= P)
+        return *reinterpret_cast<const u32x4 *>(s + i);
+    const uint32_t mis = (uint32_t)((uintptr_t)(s + i) & 3u);
+    if (i >= mis && i - mis + 20u <= P) {
+        const uint32_t *a = reinterpret_cast<const uint32_t *>(s + (i - mis));
+        const uint32_t a0 = a[0], a1 = a[1], a2 = a[2], a3 = a[3], a4 = a[4];
+        v.x = __builtin_amdgcn_alignbyte(a1, a0, mis);
+        v.y = __builtin_amdgcn_alignbyte(a2, a1, mis);
+        v.z = __builtin_amdgcn_alignbyte(a3, a2, mis);
+        v.w = __builtin_amdgcn_alignbyte(a4, a3, mis);
+        return v;
+    }
+#pragma unroll 1
+    for (uint32_t k = 0; k < 16u; ++k) { // (a 16-byte shift register: byte k ends at place k)
+        const uint32_t byte = i + k < P ? (uint32_t)s[i + k] : 0u;
+        v.x = (v.x >> 8) | (v.y << 24);
+        v.y = (v.y >> 8) | (v.z << 24);
+        v.z = (v.z >> 8) | (v.w << 24);
+        v.w = (v.w >> 8) | (byte << 24);
+    }
+    return v;
+}
+
+struct LnRow { // what a lane holds of one row
+    u32x4 p, m, r;
+};
+
+struct LnCols { // a lane's 16 columns
+    uint32_t sum[16], dev[16], clip[16];
+};
+
+// one dword of a row: its four columns, and the row's sums under the mask of the bytes that lie in the row
+template <int D>
+__device__ __forceinline__ void ln_dword(uint32_t p, uint32_t m, uint32_t r, bool ref, uint32_t vm, LnCols &c, uint32_t &sp, uint32_t &sm,
+                                         uint32_t &sr, uint32_t &nclip, uint32_t &nsame)
+{
+    const uint32_t clip = lc_zero_bytes(p) | lc_zero_bytes(~p); // 0x80 in the bytes at 0 or 255
+    const uint32_t pv = p & vm;
+    sp = __builtin_amdgcn_sad_u8(pv, 0u, sp);
+    sm = __builtin_amdgcn_sad_u8(pv, m & vm, sm);
+    nclip += (uint32_t)__builtin_popcount(clip & vm);
+    if (ref) {
+        sr = __builtin_amdgcn_sad_u8(pv, r & vm, sr);
+        nsame += (uint32_t)__builtin_popcount(lc_zero_bytes(p ^ r) & vm);
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const uint32_t byte = 0xffu << (8 * k), pk = p & byte;
+        c.sum[4 * D + k] = __builtin_amdgcn_sad_u8(pk, 0u, c.sum[4 * D + k]);
+        c.dev[4 * D + k] = __builtin_amdgcn_sad_u8(pk, m & byte, c.dev[4 * D + k]);
+        c.clip[4 * D + k] += (clip >> (8 * k + 7)) & 1u;
+    }
+}
+
+__global__ __launch_bounds__(FR_THREADS) void k_lines(const uint8_t *frames, uint64_t frames_bytes, const uint8_t *mu, uint64_t model_bytes,
+                                                      const abub_stat_job *__restrict__ jobs, int njobs, uint32_t W, uint32_t H,
+                                                      uint32_t *__restrict__ status, uint32_t *__restrict__ rows,
+                                                      uint32_t *__restrict__ cols)
+{
+    __shared__ uint32_t rowpart[LN_BAND][LN_ROW_WORDS];
+    __shared__ uint32_t colsum[LN_COL_WORDS][16][LN_PAD];
+    const uint32_t P = W * H; // (at most 65535^2 < 2^32)
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+#pragma unroll 1
+    for (uint32_t t = threadIdx.x; t < LN_COL_WORDS * 16u * LN_PAD; t += FR_THREADS)
+        (&colsum[0][0][0])[t] = 0u;
+    __syncthreads();
+    for (uint32_t j = blockIdx.x; j < (uint32_t)njobs; j += gridDim.x) {
+        const abub_stat_job jb = jobs[j];
+        const bool ok = ln_job_ok(jb, frames_bytes, model_bytes, (uint64_t)P); // (the same in every thread of the block)
+        uint32_t *jrows = rows + (uint64_t)j * H * LN_ROW_WORDS, *jcols = cols + (uint64_t)j * W * LN_COL_WORDS;
+        if (threadIdx.x == 0u)
+            status[j] = ok ? 0u : (uint32_t)ABUB_SHIFT_E_RANGE;
+        if (!ok) {
+#pragma unroll 1
+            for (uint32_t t = threadIdx.x; t < H * LN_ROW_WORDS; t += FR_THREADS)
+                jrows[t] = 0u;
+#pragma unroll 1
+            for (uint32_t t = threadIdx.x; t < W * LN_COL_WORDS; t += FR_THREADS)
+                jcols[t] = 0u;
+            continue;
+        }
+        const bool ref = jb.ref != ST_NONE;
+        const uint8_t *p = frames + jb.cur, *m = mu + jb.model, *q = frames + (ref ? jb.ref : jb.cur);
+        const uint32_t lowP = (uint32_t)(uintptr_t)p, lowM = (uint32_t)(uintptr_t)m, lowQ = (uint32_t)(uintptr_t)q;
+        for (uint32_t yb = 0; yb < H; yb += LN_BAND) {
+            const uint32_t yEnd = min(H, yb + LN_BAND);
+            for (uint32_t xs = 0; xs < W; xs += LN_STRIP) {
+                const uint32_t x = xs + 16u * lane;
+                const bool on = x < W;
+                const uint32_t left = on ? min(W - x, 16u) : 0u; // the lane's bytes that lie in the row
+                uint32_t vm[4];
+#pragma unroll
+                for (uint32_t d = 0; d < 4u; ++d)
+                    vm[d] = left >= 4u * d + 4u ? 0xffffffffu : left > 4u * d ? (1u << (8u * (left - 4u * d))) - 1u : 0u;
+                LnCols c = {};
+#pragma unroll 1
+                for (uint32_t y = yb + wave; y < yEnd; y += LN_WAVES) {
+                    const uint32_t low = y * W + xs, i = low + 16u * lane; // (mod 16 the row's address in the strip is the stream's plus `low`)
+                    LnRow row;
+                    row.p = ln_load16(p, i, P, ((lowP + low) & 15u) == 0u, on);
+                    row.m = ln_load16(m, i, P, ((lowM + low) & 15u) == 0u, on);
+                    row.r = ln_load16(q, i, P, ((lowQ + low) & 15u) == 0u, on && ref);
+                    uint32_t sp = 0, sm = 0, sr = 0, nclip = 0, nsame = 0;
+                    ln_dword<0>(row.p.x, row.m.x, row.r.x, ref, vm[0], c, sp, sm, sr, nclip, nsame);
+                    ln_dword<1>(row.p.y, row.m.y, row.r.y, ref, vm[1], c, sp, sm, sr, nclip, nsame);
+                    ln_dword<2>(row.p.z, row.m.z, row.r.z, ref, vm[2], c, sp, sm, sr, nclip, nsame);
+                    ln_dword<3>(row.p.w, row.m.w, row.r.w, ref, vm[3], c, sp, sm, sr, nclip, nsame);
+                    // (over the wave: sums of at most 1024 * 255 < 2^18, counts of at most 1024 < 2^11)
+                    uint32_t a = sp | (nclip << 18), b = sm | (nsame << 18), d = sr;
+                    wave_reduce<WaveSum, WaveSum, WaveSum>(a, b, d);
+                    if (lane == 0u) {
+                        uint32_t *rp = rowpart[y - yb];
+                        const uint32_t v[LN_ROW_WORDS] = {a & 0x3ffffu, b & 0x3ffffu, a >> 18, d, b >> 18};
+#pragma unroll
+                        for (uint32_t k = 0; k < LN_ROW_WORDS; ++k)
+                            rp[k] = xs == 0u ? v[k] : rp[k] + v[k];
+                    }
+                }
+                // (a lane of a strip's columns >= W holds what the next row's bytes gave it: it is never stored)
+#pragma unroll
+                for (uint32_t k = 0; k < 16u; ++k) {
+                    atomicAdd(&colsum[0][k][lane], c.sum[k]);
+                    atomicAdd(&colsum[1][k][lane], c.dev[k]);
+                    atomicAdd(&colsum[2][k][lane], c.clip[k]);
+                }
+                __syncthreads();
+#pragma unroll 1
+                for (uint32_t cx = threadIdx.x; cx < LN_STRIP; cx += FR_THREADS) {
+#pragma unroll
+                    for (uint32_t k = 0; k < LN_COL_WORDS; ++k) {
+                        const uint32_t v = colsum[k][cx & 15u][cx >> 4];
+                        colsum[k][cx & 15u][cx >> 4] = 0u;
+                        if (xs + cx < W) {
+                            uint32_t *out = jcols + (uint64_t)(xs + cx) * LN_COL_WORDS + k;
+                            *out = yb == 0u ? v : *out + v;
+                        }
+                    }
+                }
+                __syncthreads(); // (the column sums are zero again, and every row word of the strip is in LDS)
+            }
+#pragma unroll 1
+            for (uint32_t t = threadIdx.x; t < (yEnd - yb) * LN_ROW_WORDS; t += FR_THREADS)
+                jrows[(uint64_t)yb * LN_ROW_WORDS + t] = (&rowpart[0][0])[t];
+            __syncthreads(); // (rowpart is written again in the next band, or job)
+        }
+    }
+}
+
+} // namespace
+
+extern "C" int abub_frame_lines_dev(const uint8_t *frames, size_t frames_bytes, const uint8_t *mu, size_t model_bytes,
+                                    const abub_stat_job *jobs, int njobs, int W, int H, uint32_t *status, uint32_t *rows, uint32_t *cols,
+                                    void *stream)
+{
+    if (!frames || !mu || !jobs || !status || !rows || !cols || njobs < 0)
+        return set_err(ABUB_E_INVALID, "abub_frame_lines_dev: null pointer or negative count");
+    if (W < 1 || W > 65535 || H < 1 || H > 65535)
+        return set_err(ABUB_E_INVALID, "abub_frame_lines_dev: W and H must be in [1, 65535]");
+    if (((uintptr_t)jobs & 7) || (((uintptr_t)status | (uintptr_t)rows | (uintptr_t)cols) & 3))
+        return set_err(ABUB_E_INVALID, "abub_frame_lines_dev: jobs must be 8-byte aligned, status, rows and cols 4-byte aligned");
+    if (njobs == 0)
+        return ABUB_OK;
+    k_lines<<<dim3((unsigned)(njobs < 65535 ? njobs : 65535)), FR_THREADS, 0, (hipStream_t)stream>>>(
+        frames, (uint64_t)frames_bytes, mu, (uint64_t)model_bytes, jobs, njobs, (uint32_t)W, (uint32_t)H, status, rows, cols);
     HIPCHK(hipGetLastError());
     return ABUB_OK;
 }

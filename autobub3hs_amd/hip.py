@@ -781,6 +781,37 @@ def frame_noise_cells(frames, sigma6, jobs, W, H, x0, y0, ncx, ncy, frames_bytes
                        frames_bytes, model_bytes, status, rec, (int(ncy), int(ncx), NOISE_WORDS), torch.int32, "int32", job_words=3)
 
 
+LINES_ROW_WORDS = 5  # ABUB_LINES_ROW_WORDS of include/abub_hip.h
+LINES_COL_WORDS = 3  # ABUB_LINES_COL_WORDS
+
+
+def frame_lines(frames, mu, jobs, W, H, frames_bytes=None, model_bytes=None, status=None, rows=None, cols=None):
+    """abub_frame_lines_dev: frames and mu u8 device tensors (any shape), jobs: [n, 3] byte offsets (cur, ref, model) of each
+    job's W x H frame and reference frame in `frames` and of its plane in `mu` (any alignment; ref STAT_NONE or negative: no
+    reference frame); rows / cols: int32 device tensors of at least n * H * 5 and n * W * 3 words, written in place (None:
+    new ones) -> (status int64 [n] on the host: 0 or SHIFT_E_RANGE; rows uint32 [n, H, 5] on the host: sum p, sum |p - mu|,
+    n_clip, sum |p - r|, n_same; cols uint32 [n, W, 3]: the first three per column)."""
+    import numpy as np
+    _need_cuda(frames, mu, status, rows, cols)
+    offs = np.array([[int(v) & STAT_NONE for v in row] for row in jobs], dtype=np.uint64).reshape(-1, 3)
+    n, W, H = len(offs), int(W), int(H)
+    dev = frames.device
+    d_jobs = torch.from_numpy(np.concatenate([offs, np.zeros((1, 3), np.uint64)]).view(np.int64)).to(dev)
+    if status is None:
+        status = torch.full((max(n, 1),), 0x5A5A5A5A, dtype=torch.int32, device=dev)
+    if rows is None:
+        rows = torch.full((max(n * H * LINES_ROW_WORDS, 1),), -1, dtype=torch.int32, device=dev)
+    if cols is None:
+        cols = torch.full((max(n * W * LINES_COL_WORDS, 1),), -1, dtype=torch.int32, device=dev)
+    assert rows.numel() >= n * H * LINES_ROW_WORDS and cols.numel() >= n * W * LINES_COL_WORDS and status.numel() >= n
+    _lib.check(_lib.lib().abub_frame_lines_dev(_ptr(frames), frames.numel() if frames_bytes is None else int(frames_bytes), _ptr(mu),
+                                               mu.numel() if model_bytes is None else int(model_bytes), _ptr(d_jobs), n, W, H,
+                                               _ptr(status), _ptr(rows), _ptr(cols), _stream()), "abub_frame_lines_dev")
+    return (status.reshape(-1)[:n].cpu().numpy().astype(np.int64),
+            rows.reshape(-1)[:n * H * LINES_ROW_WORDS].cpu().numpy().view(np.uint32).reshape(n, H, LINES_ROW_WORDS),
+            cols.reshape(-1)[:n * W * LINES_COL_WORDS].cpu().numpy().view(np.uint32).reshape(n, W, LINES_COL_WORDS))
+
+
 ACT_PLANES = ("n_zero","n_sat", "n_out", "sum_out", "n_moved", "sum_moved")
 ACT_E_RANGE = 1
 ACT_PIXELS_PER_THREAD = 8  # AC_PX of csrc/abub_stats.hip: the run of pixels a thread owns

@@ -91,6 +91,14 @@ SIGNATURES = {
     "abh_noise_model_host": (_i, [_u8p, _i, _i, _i, _i, _i, _i, C.POINTER(C.c_int32), _i, C.POINTER(C.c_int64)]),
     "abh_noise_cell": (None, [C.POINTER(C.c_int32), C.POINTER(C.c_int64), C.POINTER(C.c_longlong)]),
     "abh_noise_frame": (None, [C.POINTER(C.c_int32), C.POINTER(C.c_int64), _i, C.POINTER(C.c_longlong)]),
+    "abh_run_survey_lines": (_i, [_vp, _s, _s, _s, _i, _s, _i, _s, _s, _s, _s, _i, _i, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.c_char_p,
+                                  _i]),
+    "abh_run_survey_lines_dev": (_i, [_vp, _s, _s, _s, _i, _s, _i, _s, _s, _s, _s, _i, _i, _i, _dp, _dp, _dp, _dp, _dp, _dp, _dp, _dp,
+                                      C.c_char_p, _i]),
+    "abh_lines_host": (_i, [_u8p, _u8p, _u8p, _i, _i, _u32p, _u32p]),
+    "abh_lines_model_host": (_i, [_u8p, _u8p, _i, _i, _u32p, _u32p]),
+    "abh_lines_rate": (_i, [_u32p, _u32p, C.c_longlong, C.c_longlong, C.c_longlong, C.POINTER(C.c_ulonglong)]),
+    "abh_lines_frame": (None, [_u32p, _u32p, _u32p, _u32p, _i, _i, _i, C.POINTER(C.c_longlong), _u8p, _u8p]),
     "abh_field_grid": (_i, [_i, _i, _i, C.POINTER(_i)]),
     "abh_field_cells_host": (_i, [_u8p, _u8p, _i, _i, _i, _u32p, C.POINTER(C.c_int32)]),
     "abh_activity_add_host": (None, [C.POINTER(C.c_uint32), _u8p, _u8p, _u8p, _u8p, C.c_uint64]),
@@ -470,7 +478,7 @@ class Run:
                     "W", "H", "batches", "model_cams")
 
     def survey(self, path=None, nthreads=16, ncams=4, device=None, planes=None, shift=None, shift_radius=4, field=None,
-               field_radius=4, light=None, focus=None, noise=None):
+               field_radius=4, light=None, focus=None, noise=None, lines=None):
         """abub3hs --survey of this run (opened from a directory or an archive): the run is listed and trained as for
         detect, then every frame of cameras 0 .. ncams-1 is measured without analysing any; the report (DESIGN section 3,
         "Surveying a run") is written to `path` (None: it is not written).  device=None: host threads (cv::imdecode and
@@ -505,21 +513,28 @@ class Run:
         "Surveying a run for noise changes"): cam<c>_noise.npy, cam<c>_noise_model.npy and noise.txt, of the same rows those
         whose reference frame (the frame two before) is another ok frame, each against that frame per cell of the field's
         grid at field_radius, the same bytes on both routes; the stats then also have noise_frames_kernel /
-        noise_frames_host, noise_launches and the legs noise_s and noise_host_s.  Nothing else changes."""
+        noise_frames_host, noise_launches and the legs noise_s and noise_host_s.  Nothing else changes.
+        lines (--survey-lines): the directory (the CLI's DIR/<run_ID>) that gets the per-line records (DESIGN section 3,
+        "Surveying a run for torn, repeated and banded frames"): cam<c>_lines_rows.npy, cam<c>_lines_cols.npy, the two model
+        files and lines.txt, the same rows summed along every image row and column (no grid, any size), against the frame
+        two before where that is another ok frame, the same bytes on both routes; the stats then also have
+        lines_frames_kernel / lines_frames_host, lines_launches and the legs lines_s and lines_host_s.  Nothing else
+        changes."""
         L = lib()
         st, pst = (C.c_double * 24)(), (C.c_double * 5)()
         products = [(v, (C.c_double * 5)(), k) for v, k in ((shift, "shift"), (field, "field"), (light, "light"), (focus, "focus"),
-                                                                 (noise, "noise"))]
+                                                                 (noise, "noise"), (lines, "lines"))]
         cap = 1 << 16
         buf = C.create_string_buffer(cap)
         # the widest entry takes every product; a NULL path: that product is not made
-        to, pd, sp, fd, ld, od, nd = (None if p is None else str(p).encode() for p in (path, planes, shift, field, light, focus, noise))
-        args = (self._h, to, pd, sp, int(shift_radius), fd, int(field_radius), ld, od, nd, ncams, nthreads)
+        to, pd, sp, fd, ld, od, nd, nl = (None if p is None else str(p).encode()
+                                          for p in (path, planes, shift, field, light, focus, noise, lines))
+        args = (self._h, to, pd, sp, int(shift_radius), fd, int(field_radius), ld, od, nd, nl, ncams, nthreads)
         out = (st, pst, *(a for _, a, _ in products), buf, cap)
         if device is None:
-            rc = L.abh_run_survey_noise(*args, *out)
+            rc = L.abh_run_survey_lines(*args, *out)
         else:
-            rc = L.abh_run_survey_noise_dev(*args, int(device), *out)
+            rc = L.abh_run_survey_lines_dev(*args, int(device), *out)
         if rc not in (0, 1):
             raise RuntimeError(f"abh_run_survey rc={rc}: " + L.abh_last_error(self._h).decode())
         text = buf.value if st[23] < cap else L.abh_run_survey_report(self._h)
@@ -768,6 +783,71 @@ def noise_frame(rec, model):
     none = v[0] == 0
     return {"rated": v[0], "clipped": v[1], "busy": v[2], "noisy": v[3], "quiet": v[4], "kind": NOISE_KINDS[v[5]],
             "q_milli": None if none else v[6], "q_min": None if none else v[7], "q_max": None if none else v[8], "all_milli": v[9]}
+
+
+LINE_STATES = ("unrated", "rated", "off")
+LINES_KINDS = ("blind", "repeated", "torn", "banded", "striped", "steady")
+
+
+def lines_host(p, mu, r=None):
+    """abub::linesHost (host/survey.cpp), the definition of abub_frame_lines_dev: the frame p, the plane mu and the
+    reference frame r (None: none), u8 [H, W] -> (rows uint32 [H, 5]: sum p, sum |p - mu|, n_clip, sum |p - r|, n_same;
+    cols uint32 [W, 3]: the first three per column)."""
+    p, mu = (np.ascontiguousarray(v, dtype=np.uint8) for v in (p, mu))
+    r = None if r is None else np.ascontiguousarray(r, dtype=np.uint8)
+    assert p.ndim == 2 and p.shape == mu.shape and (r is None or r.shape == p.shape)
+    H, W = p.shape
+    rows, cols = np.zeros((H, 5), np.uint32), np.zeros((W, 3), np.uint32)
+    if lib().abh_lines_host(p.ctypes.data_as(_u8p), None if r is None else r.ctypes.data_as(_u8p), mu.ctypes.data_as(_u8p), W, H,
+                            rows.ctypes.data_as(_u32p), cols.ctypes.data_as(_u32p)) != H:
+        raise ValueError(f"a frame of {W}x{H} has a side outside [1, 65535]")
+    return rows, cols
+
+
+def lines_model_host(mu, sigma6):
+    """abub::linesModelHost: the planes mu and sigma6, u8 [H, W] -> (rows uint32 [H, 3], cols uint32 [W, 3]): sum mu, T = sum
+    sigma6, the pixels with sigma6 == 0."""
+    mu, sigma6 = (np.ascontiguousarray(v, dtype=np.uint8) for v in (mu, sigma6))
+    assert mu.ndim == 2 and mu.shape == sigma6.shape
+    H, W = mu.shape
+    rows, cols = np.zeros((H, 3), np.uint32), np.zeros((W, 3), np.uint32)
+    if lib().abh_lines_model_host(mu.ctypes.data_as(_u8p), sigma6.ctypes.data_as(_u8p), W, H, rows.ctypes.data_as(_u32p),
+                                  cols.ctypes.data_as(_u32p)) != H:
+        raise ValueError(f"a plane of {W}x{H} has a side outside [1, 65535]")
+    return rows, cols
+
+
+def line_rate(rec, model, N, n, S):
+    """abub::lineRate: what one line of N pixels says, from its record (the first three words are read), its model record
+    [3], the number n of the frame's rated lines and the sum S of their D -> dict: state (a word of LINE_STATES), num and den
+    (e^2 N and (n T)^2 as Python ints; None where the line is unrated).  The line is off when num > 4 den."""
+    rec = np.ascontiguousarray(rec, dtype=np.uint32).reshape(-1)
+    model = np.ascontiguousarray(model, dtype=np.uint32).reshape(3)
+    assert rec.size >= 3
+    out = (C.c_ulonglong * 4)()
+    state = lib().abh_lines_rate(rec.ctypes.data_as(_u32p), model.ctypes.data_as(_u32p), int(N), int(n), int(S), out)
+    return {"state": LINE_STATES[state], "num": (out[0] | out[1] << 64) if state else None,
+            "den": (out[2] | out[3] << 64) if state else None}
+
+
+def lines_frame(rows, cols, model_rows, model_cols, has_ref):
+    """abub::linesFrame: what a frame's records (rows [H, 5], cols [W, 3]) say against the model's ([H, 3], [W, 3]) -> dict:
+    rated_rows, off_rows, stale_rows, first_stale, last_stale, rated_cols, off_cols, first_off_row, last_off_row,
+    first_off_col, last_off_col (None where lines.txt has '-'), level_milli, kind (a word of LINES_KINDS), row_state [H] and
+    col_state [W] (uint8: 0 unrated, 1 rated, 2 off, 3 stale)."""
+    rows, cols, model_rows, model_cols = (np.ascontiguousarray(v, dtype=np.uint32) for v in (rows, cols, model_rows, model_cols))
+    H, W = rows.shape[0], cols.shape[0]
+    assert rows.shape == (H, 5) and cols.shape == (W, 3) and model_rows.shape == (H, 3) and model_cols.shape == (W, 3)
+    out = (C.c_longlong * 13)()
+    rs, cs = np.zeros(H, np.uint8), np.zeros(W, np.uint8)
+    lib().abh_lines_frame(rows.ctypes.data_as(_u32p), cols.ctypes.data_as(_u32p), model_rows.ctypes.data_as(_u32p),
+                          model_cols.ctypes.data_as(_u32p), W, H, int(bool(has_ref)), out, rs.ctypes.data_as(_u8p), cs.ctypes.data_as(_u8p))
+    v = list(out)
+    keys = ("rated_rows", "off_rows", "stale_rows", "first_stale", "last_stale", "rated_cols", "off_cols", "first_off_row",
+            "last_off_row", "first_off_col", "last_off_col")
+    res = {k: (None if k.startswith(("first", "last")) and x < 0 else x) for k, x in zip(keys, v)}
+    res.update(level_milli=v[11], kind=LINES_KINDS[v[12]], row_state=rs, col_state=cs)
+    return res
 
 
 def zip_write(path, entries):

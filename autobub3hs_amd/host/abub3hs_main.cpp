@@ -39,6 +39,7 @@ static std::string usage()
            "               [--survey-light DIR [--survey-field-radius R]]\n"
            "               [--survey-focus DIR [--survey-field-radius R]]\n"
            "               [--survey-noise DIR [--survey-field-radius R]]\n"
+           "               [--survey-lines DIR]\n"
            "Run the AutoBub3hs bubble finding algorithm on a PICO run (MI355X hot path)\n\n"
            "Required arguments:\n"
            "  -d, --data_dir = Dir\t\tpath to the directory in which the run folder/file is stored\n"
@@ -161,6 +162,18 @@ static std::string usage()
            "\t\t\t\tkind (blind, busy, steady, noisy, quiet, uneven); per camera and for the run the counts of each\n"
            "\t\t\t\tkind and per cell the frames in which it changed; the same bytes with --survey-gpu; nothing else\n"
            "\t\t\t\tchanges\n"
+           "  --survey-lines = Dir\t\twith --survey: also sum every such frame along its image rows and columns (any size, no grid)\n"
+           "\t\t\t\tagainst mu and against the frame two before in its stack where that is another ok frame, and\n"
+           "\t\t\t\twrite into Dir/<run_ID>/ cam<c>_lines_rows.npy (i32 [frames, H, 5]: per row the sums of p and of\n"
+           "\t\t\t\t|p - mu|, the pixels at 0 or 255, the sum of |p - r| and the pixels with p == r),\n"
+           "\t\t\t\tcam<c>_lines_cols.npy (i32 [frames, W, 3]: the first three per column),\n"
+           "\t\t\t\tcam<c>_lines_model_rows.npy and cam<c>_lines_model_cols.npy (i32 [H, 3] and [W, 3]: the sums of mu\n"
+           "\t\t\t\tand of min(6 sigma, 255), the pixels with sigma 0) and lines.txt: per frame the rated, off and\n"
+           "\t\t\t\tstale rows (stale: equal to the reference frame's row pixel for pixel), the first and last stale\n"
+           "\t\t\t\trow, the rated and off columns, the first and last off row and column, the level in thousandths\n"
+           "\t\t\t\tand the frame's kind (blind, repeated, torn, banded, striped, steady); per camera and for the run\n"
+           "\t\t\t\tthe counts of each kind and per row and column the frames in which it was off or stale; the\n"
+           "\t\t\t\tsame bytes with --survey-gpu; nothing else changes\n"
            "Environment: ABUB_TRAIN_ON_GPU=0 trains the runs of a campaign with the host Trainer\n"
            "             ABUB_REPACK_BATCH=n (a test knob) lowers the frames per batch of --repack-gpu and --unpack-gpu to n; the files\n"
            "             are the same\n"
@@ -348,6 +361,8 @@ int main(int argc, char **argv)
     bool haveSurveyFocus = false;
     std::string surveyNoiseDir; // --survey-noise DIR: the survey's per-cell noise records go to DIR/<run_ID>/
     bool haveSurveyNoise = false;
+    std::string surveyLinesDir; // --survey-lines DIR: the survey's per-line records go to DIR/<run_ID>/
+    bool haveSurveyLines = false;
     for (int i = 1; i < argc; ++i) {
         std::string a = argv[i], v;
         auto value = [&](std::string &dst) {
@@ -485,6 +500,9 @@ int main(int argc, char **argv)
         } else if (a == "--survey-noise" || a.rfind("--survey-noise=", 0) == 0) {
             value(surveyNoiseDir);
             haveSurveyNoise = true;
+        } else if (a == "--survey-lines" || a.rfind("--survey-lines=", 0) == 0) {
+            value(surveyLinesDir);
+            haveSurveyLines = true;
         } else if (a == "--per-event") {
             perEvent = true;
         } else if (a == "--peek" || a.rfind("--peek=", 0) == 0) {
@@ -530,6 +548,7 @@ int main(int argc, char **argv)
         {"--survey-light", haveSurveyLight, "--survey", haveSurvey, &surveyLightDir, "directory"},
         {"--survey-focus", haveSurveyFocus, "--survey", haveSurvey, &surveyFocusDir, "directory"},
         {"--survey-noise", haveSurveyNoise, "--survey", haveSurvey, &surveyNoiseDir, "directory"},
+        {"--survey-lines", haveSurveyLines, "--survey", haveSurvey, &surveyLinesDir, "directory"},
         // (the light's, the focus' and the noise's cells are the field's)
         {"--survey-field-radius", haveFieldRadius, "--survey-field", haveSurveyField || haveSurveyLight || haveSurveyFocus || haveSurveyNoise,
          nullptr, nullptr},
@@ -737,6 +756,7 @@ int main(int argc, char **argv)
         rq.lightDir = under(haveSurveyLight, surveyLightDir);
         rq.focusDir = under(haveSurveyFocus, surveyFocusDir);
         rq.noiseDir = under(haveSurveyNoise, surveyNoiseDir);
+        rq.linesDir = under(haveSurveyLines, surveyLinesDir);
         int rc = 1;
         try {
             abub::PreparedRun prep = abub::PrepareRun(sp, po, 0, nullptr, false);
@@ -781,7 +801,8 @@ int main(int argc, char **argv)
                                             {haveSurveyField, "field", rq.fieldDir.c_str(), "searched", rq.cellRadius},
                                             {haveSurveyLight, "light", rq.lightDir.c_str(), "summed", rq.cellRadius},
                                             {haveSurveyFocus, "focus", rq.focusDir.c_str(), "summed", rq.cellRadius},
-                                            {haveSurveyNoise, "noise", rq.noiseDir.c_str(), "summed", rq.cellRadius}};
+                                            {haveSurveyNoise, "noise", rq.noiseDir.c_str(), "summed", rq.cellRadius},
+                                            {haveSurveyLines, "lines", rq.linesDir.c_str(), "summed", 0}};
         for (int p = 0; p < abub::SurveyProducts; ++p)
             if (products[p].have)
                 printf("survey-%s: %s: radius %d, %lld frames %s on the GPU in %d launches, %lld on the host; %s leg %.3f s, host "

@@ -420,10 +420,14 @@ const char *abh_run_verify_report(void *src)
 // for noise changes") written to noise_dir (the CLI's DIR/<run_ID>; NULL or empty: none) on the grid of field_radius, whether
 // or not any of the other three is given, and noise_stats (may be NULL, 5 values): the same five for
 // abub_frame_noise_cells_dev and noiseCellsHost.
+// abh_run_survey_lines[_dev]: the same with the per-line records (SurveyRequest::linesDir; DESIGN section 3, "Surveying a run
+// for torn, repeated and banded frames") written to lines_dir (the CLI's DIR/<run_ID>; NULL or empty: none), whatever else is
+// given, and lines_stats (may be NULL, 5 values): the same five for abub_frame_lines_dev and linesHost.
 // what an entry's arguments ask for (a NULL path: none; the directory the run is read from is runSurvey's to fill in)
 static abub::SurveyRequest surveyRequest(const char *path, const char *planes_dir = nullptr, const char *shift_path = nullptr,
                                          int shift_radius = 4, const char *field_dir = nullptr, int field_radius = 4,
-                                         const char *light_dir = nullptr, const char *focus_dir = nullptr, const char *noise_dir = nullptr)
+                                         const char *light_dir = nullptr, const char *focus_dir = nullptr, const char *noise_dir = nullptr,
+                                         const char *lines_dir = nullptr)
 {
     const auto str = [](const char *s) { return std::string(s ? s : ""); };
     abub::SurveyRequest rq;
@@ -436,11 +440,13 @@ static abub::SurveyRequest surveyRequest(const char *path, const char *planes_di
     rq.lightDir = str(light_dir);
     rq.focusDir = str(focus_dir);
     rq.noiseDir = str(noise_dir);
+    rq.linesDir = str(lines_dir);
     return rq;
 }
 static int runSurvey(void *r, abub::SurveyRequest rq, int ncams, int nthreads, int device, bool onDevice, char *report, int report_cap,
                      double *stats, double *plane_stats = nullptr, double *shift_stats = nullptr, double *field_stats = nullptr,
-                     double *light_stats = nullptr, double *focus_stats = nullptr, double *noise_stats = nullptr)
+                     double *light_stats = nullptr, double *focus_stats = nullptr, double *noise_stats = nullptr,
+                     double *lines_stats = nullptr)
 {
     Run *run = (Run *)r;
     try {
@@ -467,7 +473,7 @@ static int runSurvey(void *r, abub::SurveyRequest rq, int ncams, int nthreads, i
             throw std::runtime_error("survey: no such HIP device: " + std::to_string(device));
         const int rc = abub::SurveyRun(pr.parser.get(), pr.trainers, ncams, sp.imageFormat, rq, std::max(1, nthreads), onDevice ? device : -1,
                                        &st, &rows, &models);
-        double *const product_stats[abub::SurveyProducts] = {shift_stats, field_stats, light_stats, focus_stats, noise_stats};
+        double *const product_stats[abub::SurveyProducts] = {shift_stats, field_stats, light_stats, focus_stats, noise_stats, lines_stats};
         for (int p = 0; p < abub::SurveyProducts; ++p)
             if (product_stats[p]) {
                 const abub::ProductStats &ps = st.product[p];
@@ -596,6 +602,27 @@ int abh_run_survey_noise_dev(void *r, const char *path, const char *planes_dir, 
     return runSurvey(r, surveyRequest(path, planes_dir, shift_path, shift_radius, field_dir, field_radius, light_dir, focus_dir, noise_dir),
                      ncams, nthreads, device, true, report, report_cap, stats, plane_stats, shift_stats, field_stats, light_stats,
                      focus_stats, noise_stats);
+}
+int abh_run_survey_lines(void *r, const char *path, const char *planes_dir, const char *shift_path, int shift_radius, const char *field_dir,
+                         int field_radius, const char *light_dir, const char *focus_dir, const char *noise_dir, const char *lines_dir,
+                         int ncams, int nthreads, double *stats, double *plane_stats, double *shift_stats, double *field_stats,
+                         double *light_stats, double *focus_stats, double *noise_stats, double *lines_stats, char *report, int report_cap)
+{
+    return runSurvey(r, surveyRequest(path, planes_dir, shift_path, shift_radius, field_dir, field_radius, light_dir, focus_dir, noise_dir,
+                                      lines_dir),
+                     ncams, nthreads, -1, false, report, report_cap, stats, plane_stats, shift_stats, field_stats, light_stats, focus_stats,
+                     noise_stats, lines_stats);
+}
+int abh_run_survey_lines_dev(void *r, const char *path, const char *planes_dir, const char *shift_path, int shift_radius,
+                             const char *field_dir, int field_radius, const char *light_dir, const char *focus_dir, const char *noise_dir,
+                             const char *lines_dir, int ncams, int nthreads, int device, double *stats, double *plane_stats,
+                             double *shift_stats, double *field_stats, double *light_stats, double *focus_stats, double *noise_stats,
+                             double *lines_stats, char *report, int report_cap)
+{
+    return runSurvey(r, surveyRequest(path, planes_dir, shift_path, shift_radius, field_dir, field_radius, light_dir, focus_dir, noise_dir,
+                                      lines_dir),
+                     ncams, nthreads, device, true, report, report_cap, stats, plane_stats, shift_stats, field_stats, light_stats,
+                     focus_stats, noise_stats, lines_stats);
 }
 // the whole report of the last abh_run_survey[_dev] on the run (valid until the next query on it)
 const char *abh_run_survey_report(void *r)
@@ -774,6 +801,51 @@ void abh_noise_frame(const int32_t *rec, const int64_t *model, int cells, long l
 {
     const abub::NoiseFrame f = abub::noiseFrame(rec, model, (size_t)std::max(cells, 0));
     const long long v[10] = {f.rated, f.clipped, f.busy, f.noisy, f.quiet, f.kind, f.qMilli, f.qMin, f.qMax, f.allMilli};
+    std::memcpy(out, v, sizeof v);
+}
+
+// abub::linesHost on raw buffers: the W x H frame p against the plane mu and the reference frame r (NULL: none) -> rows[H * 5]
+// and cols[W * 3] (u32); returns H, or -1 (nothing written) for a null pointer or a side outside [1, 65535]
+int abh_lines_host(const uint8_t *p, const uint8_t *r, const uint8_t *mu, int W, int H, uint32_t *rows, uint32_t *cols)
+{
+    if (!p || !mu || !rows || !cols || W < 1 || W > 65535 || H < 1 || H > 65535)
+        return -1;
+    abub::linesHost(p, r, mu, W, H, rows, cols);
+    return H;
+}
+// abub::linesModelHost on raw buffers -> rows[H * 3] and cols[W * 3] (u32): sum mu, sum sigma6, pixels with sigma6 == 0;
+// returns as above
+int abh_lines_model_host(const uint8_t *mu, const uint8_t *sigma6, int W, int H, uint32_t *rows, uint32_t *cols)
+{
+    if (!mu || !sigma6 || !rows || !cols || W < 1 || W > 65535 || H < 1 || H > 65535)
+        return -1;
+    abub::linesModelHost(mu, sigma6, W, H, rows, cols);
+    return H;
+}
+// abub::lineRate on raw buffers, what a line of N pixels says: rec[3] and model[3], n the frame's rated lines and S their sum
+// of D; returns 0 unrated, 1 rated and not off, 2 off; out[4] (may be NULL) = e^2 N and (n T)^2 of a rated line, each as its
+// low and its high 64 bits
+int abh_lines_rate(const uint32_t *rec, const uint32_t *model, long long N, long long n, long long S, unsigned long long *out)
+{
+    unsigned __int128 num = 0, den = 0;
+    const int state = abub::lineRate(rec, model, N, n, S, &num, &den);
+    if (out) {
+        const unsigned long long v[4] = {(unsigned long long)num, (unsigned long long)(num >> 64), (unsigned long long)den,
+                                         (unsigned long long)(den >> 64)};
+        std::memcpy(out, v, sizeof v);
+    }
+    return state;
+}
+// abub::linesFrame on raw buffers, what a frame's records say against the model's: out[13] = rated_rows, off_rows, stale_rows,
+// first_stale, last_stale, rated_cols, off_cols, first_off_row, last_off_row, first_off_col, last_off_col (-1: none),
+// level_milli, kind (0 blind, 1 repeated, 2 torn, 3 banded, 4 striped, 5 steady); row_state[H] and col_state[W] (may be NULL):
+// per line 0 unrated, 1 rated, 2 off, 3 stale
+void abh_lines_frame(const uint32_t *rows, const uint32_t *cols, const uint32_t *model_rows, const uint32_t *model_cols, int W, int H,
+                     int has_ref, long long *out, uint8_t *row_state, uint8_t *col_state)
+{
+    const abub::LinesFrame f = abub::linesFrame(rows, cols, model_rows, model_cols, W, H, has_ref != 0, row_state, col_state);
+    const long long v[13] = {f.ratedRows, f.offRows, f.staleRows, f.firstStale, f.lastStale, f.ratedCols, f.offCols, f.firstOffRow,
+                             f.lastOffRow, f.firstOffCol, f.lastOffCol, f.levelMilli, f.kind};
     std::memcpy(out, v, sizeof v);
 }
 

@@ -364,10 +364,49 @@ struct NoiseFrame {
 };
 NoiseFrame noiseFrame(const int32_t *rec, const int64_t *model, size_t cells);
 
+// The definition of abub_frame_lines_dev ("Surveying a run for torn, repeated and banded frames"): per image
+// row y of the W x H frame p five u32 over the row's W pixels, against m of mu and r of the reference frame (the frame two
+// before; null: none, words 3 and 4 are 0): rows[y * 5 + 0 .. 4] = sum p, sum |p - m|, n_clip (pixels with p == 0 or
+// p == 255), sum |p - r|, n_same (pixels with p == r); per image column x the first three over the column's H pixels:
+// cols[x * 3 + 0 .. 2].  Plain loops; with W, H <= 65535 a value of at most 65535 * 255 < 2^24.
+enum { LinesRowWords = 5, LinesColWords = 3, LinesModelWords = 3 };
+void linesHost(const unsigned char *p, const unsigned char *r, const unsigned char *mu, int W, int H, uint32_t *rows, uint32_t *cols);
+// The camera's share, once per camera: per row (rows[y * 3 + 0 .. 2]) and per column (cols[x * 3 + 0 .. 2]) sum m, T = the
+// sum of sigma6 (min(6 sigma, 255)) and n_s0, the pixels with sigma6 == 0
+void linesModelHost(const unsigned char *mu, const unsigned char *sigma6, int W, int H, uint32_t *rows, uint32_t *cols);
+// The rule's constants.  A line of N pixels is unrated if more than 1 / LinesShare of them are clipped or have sigma6 == 0.
+// A rated line is off when e^2 N > LinesFactor (n T)^2, with n the frame's rated lines of its direction, D = word 0 - sum m,
+// S the sum of D over them and e = n D - S: n times the line's excess over the frame's own level, against two times T in
+// amplitude (the line's noise is about T / (6 sqrt N); DESIGN has the simulation the factor comes from and the measured
+// margin).  A frame is torn from LinesTornRun consecutive stale rows on, banded or striped from LinesOffLines off lines on.
+enum { LinesShare = 4, LinesFactor = 4, LinesTornRun = 8, LinesOffLines = 4 };
+// What one line says (one function for rows and columns and for both routes; integers only, the products in unsigned
+// __int128: e^2 N reaches 10^29): rec, its record (the first three words are read); model, its model record; N, its pixels;
+// n and S as above, over the rated lines of the frame -> LineUnrated, LineRated (and not off) or LineOff.  *num and *den (may
+// be null) get e^2 N and (n T)^2 of a rated line
+enum LineState { LineUnrated = 0, LineRated = 1, LineOff = 2, LineStale = 3 }; // (stale: of a row, in linesFrame's states only)
+bool lineRated(const uint32_t *rec, const uint32_t *model, long long N);
+int lineRate(const uint32_t *rec, const uint32_t *model, long long N, long long n, long long S, unsigned __int128 *num = nullptr,
+             unsigned __int128 *den = nullptr);
+// What a frame says, from its records and its camera's model.  A rated row is stale when the frame has a reference and its
+// n_same == W.  kind, the first that applies: blind (the rated rows are fewer than a quarter of H), repeated (a reference,
+// and every rated row is stale), torn (a run of at least 8 consecutive stale rows), banded (at least 4 off rows), striped (at
+// least 4 off columns), steady.  levelMilli = floor(1000 S / (n W)) over the rated rows (0 without one): the frame's level
+// above the model's; first / last: -1 where there is none
+struct LinesFrame {
+    enum Kind { Blind = 0, Repeated = 1, Torn = 2, Banded = 3, Striped = 4, Steady = 5 };
+    int ratedRows = 0, offRows = 0, staleRows = 0, firstStale = -1, lastStale = -1, ratedCols = 0, offCols = 0;
+    int firstOffRow = -1, lastOffRow = -1, firstOffCol = -1, lastOffCol = -1, kind = Blind;
+    long long levelMilli = 0;
+};
+// rowState[H] and colState[W] (may be null): per line its LineState (a row that is off and stale: LineStale)
+LinesFrame linesFrame(const uint32_t *rows, const uint32_t *cols, const uint32_t *modelRows, const uint32_t *modelCols, int W, int H,
+                      bool hasRef, uint8_t *rowState = nullptr, uint8_t *colState = nullptr);
+
 // What a survey makes of every ok row of a camera with a model, beyond its record: the index of the row's state, of the
 // product's counters and of the host threads' clocks
 enum SurveyProduct { SurveyShiftProduct = 0, SurveyFieldProduct = 1, SurveyLightProduct = 2, SurveyFocusProduct = 3, SurveyNoiseProduct = 4,
-                     SurveyProducts = 5 };
+                     SurveyLinesProduct = 5, SurveyProducts = 6 };
 // One row of a survey: a frame the run lists, or one it should list (missing)
 struct SurveyRow {
     enum State { Ok = 0, Undecodable = 1, Missing = 2, OtherSize = 3 };
@@ -387,6 +426,8 @@ struct SurveyRow {
     std::vector<uint32_t> light; // with a light directory: its cells' light records, [ncy][ncx][6]
     std::vector<int32_t> focus;  // with a focus directory: its cells' focus records, [ncy][ncx][5]
     std::vector<int32_t> noise;  // with a noise directory: its cells' noise records, [ncy][ncx][6]
+    std::vector<uint32_t> linesRows, linesCols; // with a lines directory: linesHost's [H][5] and [W][3]
+    bool linesRef = false;       // those were made against a reference frame (another row, ok and of the run's size)
     const char *stateName() const; // "ok", "undecodable", "missing", "other_size"
 };
 // What the report says of one camera's model
@@ -398,9 +439,10 @@ struct SurveyModel {
     std::vector<uint32_t> light; // with a light directory, of a trained camera: lightModelHost's [ncy][ncx][3]
     std::vector<int64_t> focus;  // with a focus directory, of a trained camera: focusModelHost's [ncy][ncx][3]
     std::vector<int64_t> noise;  // with a noise directory, of a trained camera: noiseModelHost's [ncy][ncx][5]
+    std::vector<uint32_t> linesRows, linesCols; // with a lines directory, of a trained camera: linesModelHost's [H][3] and [W][3]
 };
 // The counters of one product: the rows whose product its kernel made (abub_frame_shift_dev, abub_frame_shift_cells_dev,
-// abub_frame_light_cells_dev, abub_frame_focus_cells_dev, abub_frame_noise_cells_dev) and those a host thread made from the definition, the kernel's
+// abub_frame_light_cells_dev, abub_frame_focus_cells_dev, abub_frame_noise_cells_dev, abub_frame_lines_dev) and those a host thread made from the definition, the kernel's
 // calls, the seconds of the device route's leg (launches, copy back) and the seconds the host threads spent in the
 // definition, summed over the threads
 struct ProductStats {
@@ -448,6 +490,10 @@ struct SurveyRequest {
     std::string fieldDir;
     int cellRadius = 4;
     std::string lightDir, focusDir, noiseDir;
+    // "Surveying a run for torn, repeated and banded frames": linesDir (the CLI's DIR/<run_ID>) gets, for every camera with a
+    // model, of its ok rows cam<c>_lines_rows.npy (i32 [N_c, H, 5]) and cam<c>_lines_cols.npy (i32 [N_c, W, 3]), the model's
+    // cam<c>_lines_model_rows.npy (i32 [H, 3]) and cam<c>_lines_model_cols.npy (i32 [W, 3]), and lines.txt.  No grid: any size
+    std::string linesDir;
 };
 // The texts of field.txt, light.txt, focus.txt and noise.txt: "# abub3hs <tag> 1", the grid's line, the table's header and one
 // tab-separated row per survey row, one `<tag> cam` line per camera, the `moved` (field) or `changed` lines of every camera
@@ -457,6 +503,11 @@ std::string FieldReport(int radius, int W, int H, const std::vector<SurveyModel>
 std::string LightReport(int radius, int W, int H, const std::vector<SurveyModel> &models, const std::vector<SurveyRow> &rows);
 std::string FocusReport(int radius, int W, int H, const std::vector<SurveyModel> &models, const std::vector<SurveyRow> &rows);
 std::string NoiseReport(int radius, int W, int H, const std::vector<SurveyModel> &models, const std::vector<SurveyRow> &rows);
+// The text of lines.txt: "# abub3hs lines 1", `size W H`, the table's header and one tab-separated row per survey row (the
+// rated, off and stale rows, the first and last stale row, the rated and off columns, the first and last off row and off
+// column, the level in thousandths, the kind), one `lines cam` line per camera, per camera with a model one `changed` line
+// for every row and every column that was off or stale in a frame, with the number of such frames, the `run` line
+std::string LinesReport(int W, int H, const std::vector<SurveyModel> &models, const std::vector<SurveyRow> &rows);
 // The shift file's text: "# abub3hs shift 1", `radius R`, the table's header and one tab-separated row per survey row, one
 // `shift cam` line per camera, the `run` line.  Both routes write it through this one function.
 std::string ShiftReport(int radius, const std::vector<SurveyModel> &models, const std::vector<SurveyRow> &rows);
@@ -472,7 +523,7 @@ std::string SurveyReport(const std::vector<SurveyModel> &models, const std::vect
 // is not written), every other product of `request` to its place; a product changes nothing in the others.  Returns 0, or 1
 // if any frame is not ok; throws where a file cannot be written.
 // device < 0, the host route: cv::imdecode and the definitions (frameStatsHost, activityAddHost, frameShiftHost,
-// fieldCellsHost, lightCellsHost, focusCellsHost, noiseCellsHost) on `nthreads` threads.  No GPU.
+// fieldCellsHost, lightCellsHost, focusCellsHost, noiseCellsHost, linesHost) on `nthreads` threads.  No GPU.
 // device >= 0 (--survey-gpu): the same rows and the same files, byte for byte.  The frames are read through the FileBatch
 // protocol (framefiles.hpp) in batches of at most 4 frames per CU (ABUB_SURVEY_BATCH=n: of n), decoded into the batch's
 // slab, and measured by one abub_frame_stats_dev launch per batch, with the products' kernels behind it.  A batch that

@@ -14,10 +14,13 @@
 //   focus           focusCellsHost     abub_frame_focus_cells_dev    focusModelHost once per camera; focusCell, focusFrame; FocusReport
 //   noise           noiseCellsHost     abub_frame_noise_cells_dev    the row against its reference frame, not mu; noiseModelHost once
 //                                                                    per camera after the rows; noiseCell, noiseFrame; NoiseReport
+//   lines           linesHost          abub_frame_lines_dev          per image row and column, no grid; linesModelHost once per
+//                                                                    camera; lineRate, linesFrame; LinesReport, writeLines
 // Shift, field, light, focus and noise are made of the ok rows of a camera with a model and share the rest: one two-bit state per
 // row, one ProductStats, one timing wrapper on the host, one device leg over one job list (deviceFrames), and for the three
 // per-cell products one grid, one report skeleton (cellReport) and one writer (writeCells).
 #include <algorithm>
+#include <type_traits>
 #include <cinttypes>
 #include <cmath>
 #include <cstdio>
@@ -523,6 +526,123 @@ NoiseFrame noiseFrame(const int32_t *rec, const int64_t *model, size_t cells)
     return f;
 }
 
+void linesHost(const unsigned char *p, const unsigned char *r, const unsigned char *mu, int W, int H, uint32_t *rows, uint32_t *cols)
+{
+    std::fill(rows, rows + (size_t)H * LinesRowWords, 0u);
+    std::fill(cols, cols + (size_t)W * LinesColWords, 0u);
+    for (int y = 0; y < H; ++y) {
+        const unsigned char *pr = p + (size_t)y * W, *mr = mu + (size_t)y * W, *rr = r ? r + (size_t)y * W : nullptr;
+        uint32_t *row = rows + (size_t)y * LinesRowWords;
+        for (int x = 0; x < W; ++x) {
+            const uint32_t v = pr[x], dev = (uint32_t)std::abs((int)pr[x] - (int)mr[x]), clip = v == 0 || v == 255;
+            uint32_t *col = cols + (size_t)x * LinesColWords;
+            row[0] += v;
+            row[1] += dev;
+            row[2] += clip;
+            col[0] += v;
+            col[1] += dev;
+            col[2] += clip;
+            if (rr) {
+                row[3] += (uint32_t)std::abs((int)pr[x] - (int)rr[x]);
+                row[4] += pr[x] == rr[x];
+            }
+        }
+    }
+}
+
+void linesModelHost(const unsigned char *mu, const unsigned char *sigma6, int W, int H, uint32_t *rows, uint32_t *cols)
+{
+    std::fill(rows, rows + (size_t)H * LinesModelWords, 0u);
+    std::fill(cols, cols + (size_t)W * LinesModelWords, 0u);
+    for (int y = 0; y < H; ++y)
+        for (int x = 0; x < W; ++x) {
+            const uint32_t m = mu[(size_t)y * W + x], s = sigma6[(size_t)y * W + x];
+            uint32_t *row = rows + (size_t)y * LinesModelWords, *col = cols + (size_t)x * LinesModelWords;
+            row[0] += m;
+            row[1] += s;
+            row[2] += s == 0;
+            col[0] += m;
+            col[1] += s;
+            col[2] += s == 0;
+        }
+}
+
+bool lineRated(const uint32_t *rec, const uint32_t *model, long long N)
+{
+    return (long long)LinesShare * rec[2] <= N && (long long)LinesShare * model[2] <= N;
+}
+
+int lineRate(const uint32_t *rec, const uint32_t *model, long long N, long long n, long long S, unsigned __int128 *num, unsigned __int128 *den)
+{
+    typedef unsigned __int128 u128;
+    if (!lineRated(rec, model, N))
+        return LineUnrated;
+    const __int128 e = (__int128)n * ((long long)rec[0] - (long long)model[0]) - (__int128)S;
+    const u128 a = (u128)(e < 0 ? -e : e), nT = (u128)n * (u128)model[1]; // (a < 2^41 and nT < 2^40 with sides of at most 65535)
+    const u128 lhs = a * a * (u128)N, rhs = nT * nT;
+    if (num)
+        *num = lhs;
+    if (den)
+        *den = rhs;
+    return lhs > (u128)LinesFactor * rhs ? LineOff : LineRated;
+}
+
+LinesFrame linesFrame(const uint32_t *rows, const uint32_t *cols, const uint32_t *modelRows, const uint32_t *modelCols, int W, int H,
+                      bool hasRef, uint8_t *rowState, uint8_t *colState)
+{
+    LinesFrame f;
+    // one direction: the rated lines, their number and their sum of D first, then every rated line against them
+    const auto direction = [](const uint32_t *rec, size_t words, const uint32_t *model, int lines, long long N, int &rated, int &off,
+                              int &firstOff, int &lastOff, long long &S, uint8_t *state) {
+        long long n = 0;
+        S = 0;
+        for (int k = 0; k < lines; ++k)
+            if (lineRated(rec + (size_t)k * words, model + (size_t)k * LinesModelWords, N)) {
+                ++n;
+                S += (long long)rec[(size_t)k * words] - (long long)model[(size_t)k * LinesModelWords];
+            }
+        rated = (int)n;
+        for (int k = 0; k < lines; ++k) {
+            const int s = lineRate(rec + (size_t)k * words, model + (size_t)k * LinesModelWords, N, n, S);
+            if (state)
+                state[k] = (uint8_t)s;
+            if (s != LineOff)
+                continue;
+            ++off;
+            firstOff = firstOff < 0 ? k : firstOff;
+            lastOff = k;
+        }
+    };
+    long long S = 0, Sc = 0;
+    direction(rows, LinesRowWords, modelRows, H, W, f.ratedRows, f.offRows, f.firstOffRow, f.lastOffRow, S, rowState);
+    direction(cols, LinesColWords, modelCols, W, H, f.ratedCols, f.offCols, f.firstOffCol, f.lastOffCol, Sc, colState);
+    if (f.ratedRows) {
+        const long long num = 1000 * S, den = (long long)f.ratedRows * W; // (|S| < 2^40)
+        f.levelMilli = num >= 0 ? num / den : -((-num + den - 1) / den);   // (the floor)
+    }
+    int run = 0, longest = 0;
+    for (int y = 0; y < H; ++y) {
+        const uint32_t *row = rows + (size_t)y * LinesRowWords;
+        const bool stale = hasRef && row[4] == (uint32_t)W && lineRated(row, modelRows + (size_t)y * LinesModelWords, W);
+        run = stale ? run + 1 : 0;
+        longest = std::max(longest, run);
+        if (!stale)
+            continue;
+        ++f.staleRows;
+        f.firstStale = f.firstStale < 0 ? y : f.firstStale;
+        f.lastStale = y;
+        if (rowState)
+            rowState[y] = LineStale;
+    }
+    f.kind = 4ll * f.ratedRows < H                   ? LinesFrame::Blind
+             : hasRef && f.staleRows == f.ratedRows  ? LinesFrame::Repeated
+             : longest >= LinesTornRun               ? LinesFrame::Torn
+             : f.offRows >= LinesOffLines            ? LinesFrame::Banded
+             : f.offCols >= LinesOffLines            ? LinesFrame::Striped
+                                                     : LinesFrame::Steady;
+    return f;
+}
+
 // the columns every table of a survey begins with
 static void rowPrefix(std::string &text, const SurveyRow &r)
 {
@@ -781,6 +901,90 @@ std::string NoiseReport(int radius, int W, int H, const std::vector<SurveyModel>
                       radius, W, H, models, rows);
 }
 
+std::string LinesReport(int W, int H, const std::vector<SurveyModel> &models, const std::vector<SurveyRow> &rows)
+{
+    static const char *const kinds[] = {"blind", "repeated", "torn", "banded", "striped", "steady"};
+    enum : size_t { K = sizeof kinds / sizeof *kinds };
+    std::string text = "# abub3hs lines 1\n";
+    char buf[512];
+    snprintf(buf, sizeof buf, "size %d %d\n", W, H);
+    text += buf;
+    text += "event\tcam\tframe\tname\tstate\tindex\trated_rows\toff_rows\tstale_rows\tfirst_stale\tlast_stale\trated_cols\toff_cols\t"
+            "first_off_row\tlast_off_row\tfirst_off_col\tlast_off_col\tlevel_milli\tkind\n";
+    struct Cam {
+        long long frames = 0, kind[K] = {};
+        const std::string *first = nullptr;
+        std::vector<long long> perRow, perCol; // the frames in which the line was off or stale
+    };
+    std::vector<Cam> cams(models.size());
+    std::vector<uint8_t> rowState((size_t)std::max(H, 0)), colState((size_t)std::max(W, 0));
+    const auto orDash = [](int v) { return v < 0 ? std::string("-") : std::to_string(v); };
+    for (const SurveyRow &r : rows) {
+        rowPrefix(text, r);
+        const SurveyModel *m = (size_t)r.cam < models.size() ? &models[(size_t)r.cam] : nullptr;
+        if (r.state != SurveyRow::Ok || !r.has(SurveyLinesProduct) || !m || r.linesRows.size() != (size_t)H * LinesRowWords ||
+            r.linesCols.size() != (size_t)W * LinesColWords || m->linesRows.size() != (size_t)H * LinesModelWords ||
+            m->linesCols.size() != (size_t)W * LinesModelWords) {
+            text += "\t-\t-\t-\t-\t-\t-\t-\t-\t-\t-\t-\t-\t-\t-\n";
+            continue;
+        }
+        const LinesFrame f = linesFrame(r.linesRows.data(), r.linesCols.data(), m->linesRows.data(), m->linesCols.data(), W, H, r.linesRef,
+                                        rowState.data(), colState.data());
+        Cam &c = cams[(size_t)r.cam];
+        c.perRow.resize((size_t)H, 0);
+        c.perCol.resize((size_t)W, 0);
+        for (int y = 0; y < H; ++y)
+            c.perRow[(size_t)y] += rowState[(size_t)y] >= LineOff;
+        for (int x = 0; x < W; ++x)
+            c.perCol[(size_t)x] += colState[(size_t)x] >= LineOff;
+        snprintf(buf, sizeof buf, "\t%lld\t%d\t%d\t%d\t%s\t%s\t%d\t%d\t%s\t%s\t%s\t%s\t%lld\t%s\n", c.frames, f.ratedRows, f.offRows, f.staleRows,
+                 orDash(f.firstStale).c_str(), orDash(f.lastStale).c_str(), f.ratedCols, f.offCols, orDash(f.firstOffRow).c_str(),
+                 orDash(f.lastOffRow).c_str(), orDash(f.firstOffCol).c_str(), orDash(f.lastOffCol).c_str(), f.levelMilli, kinds[f.kind]);
+        text += buf;
+        ++c.frames;
+        ++c.kind[f.kind];
+        if (f.kind != LinesFrame::Steady && f.kind != LinesFrame::Blind && !c.first)
+            c.first = &r.event;
+    }
+    long long frames = 0, kind[K] = {};
+    for (size_t c = 0; c < cams.size(); ++c) {
+        if (!models[c].trained) {
+            snprintf(buf, sizeof buf, "lines cam %zu none\n", c);
+            text += buf;
+            continue;
+        }
+        snprintf(buf, sizeof buf, "lines cam %zu frames %lld", c, cams[c].frames);
+        text += buf;
+        for (size_t q = 0; q < K; ++q) {
+            snprintf(buf, sizeof buf, " %s %lld", kinds[q], cams[c].kind[q]);
+            text += buf;
+            kind[q] += cams[c].kind[q];
+        }
+        text += std::string(" first_changed_event ") + (cams[c].first ? *cams[c].first : std::string("-")) + "\n";
+        frames += cams[c].frames;
+    }
+    for (size_t c = 0; c < cams.size(); ++c) {
+        if (!models[c].trained)
+            continue;
+        const auto changed = [&](const char *word, const std::vector<long long> &per) {
+            for (size_t k = 0; k < per.size(); ++k)
+                if (per[k]) {
+                    snprintf(buf, sizeof buf, "changed cam %zu %s %zu frames %lld\n", c, word, k, per[k]);
+                    text += buf;
+                }
+        };
+        changed("row", cams[c].perRow);
+        changed("col", cams[c].perCol);
+    }
+    snprintf(buf, sizeof buf, "run frames %lld", frames);
+    text += buf;
+    for (size_t q = 0; q < K; ++q) {
+        snprintf(buf, sizeof buf, " %s %lld", kinds[q], kind[q]);
+        text += buf;
+    }
+    return text + "\n";
+}
+
 std::string ShiftReport(int radius, const std::vector<SurveyModel> &models, const std::vector<SurveyRow> &rows)
 {
     std::string text = "# abub3hs shift 1\n";
@@ -931,7 +1135,7 @@ struct CellGrid { // abub_frame_cells_grid's answer
 };
 struct Plan {
     HostPlanes *planes = nullptr;   // with a planes directory: where surveyFrame adds its ok rows
-    bool want[SurveyProducts] = {false, false, false, false, false}; // the products surveyFrame makes of its ok rows with a model
+    bool want[SurveyProducts] = {false, false, false, false, false, false}; // the products surveyFrame makes of its ok rows with a model
     int shiftR = 0, cellR = 0;      // the shift search's radius; the radius of the grid and of the field's per-cell search
     CellGrid grid;                  // the one grid of the field, the light, the focus and the noise (all zero: none asked for, or no size)
     std::atomic<long long> *hostUs = nullptr; // [SurveyProducts]: where surveyFrame adds the microseconds it spent in a definition
@@ -1102,6 +1306,12 @@ void productsHost(const Plan &pl, const uint8_t *cur, const uint8_t *other, cons
             row.noise.resize(g.cells() * NoiseRecordWords);
             noiseCellsHost(cur, other, pl.sigma6[row.cam].data(), pl.W, pl.H, g.x0, g.y0, g.ncx, g.ncy, row.noise.data());
         });
+    timed(SurveyLinesProduct, [&] { // (without the other frame: no reference, words 3 and 4 are 0)
+        row.linesRows.resize((size_t)pl.H * LinesRowWords);
+        row.linesCols.resize((size_t)pl.W * LinesColWords);
+        row.linesRef = other != nullptr;
+        linesHost(cur, other, mu, pl.W, pl.H, row.linesRows.data(), row.linesCols.data());
+    });
 }
 
 // The host route's per-frame function: row i on this thread, its state and its record.  It asks nothing of the other rows:
@@ -1303,12 +1513,14 @@ void deviceFrames(Parser *parser, Plan &pl, int nthreads, int device, SurveyStat
                 for (size_t g : with)
                     if (jobs[g].ref != UINT64_MAX && jobs[g].ref != jobs[g].cur)
                         paired.push_back(g);
-            const size_t ns = with.size(), nn = paired.size();
+            // (the lines take every job that has a model, its reference where that is another frame in place, else none)
+            const size_t ns = with.size(), nn = paired.size(), nl = pl.want[SurveyLinesProduct] ? ns : 0;
             const abub_shift_job *d_jobs = nullptr;
             const abub_stat_job *d_pairs = nullptr; // behind the with-model list in the same buffer
+            const abub_stat_job *d_lines = nullptr; // behind the pairs
             if (ns && (pl.want[SurveyShiftProduct] || pl.want[SurveyFieldProduct] || pl.want[SurveyLightProduct] || pl.want[SurveyFocusProduct] ||
-                       nn)) {
-                const size_t bytes = ns * sizeof(abub_shift_job) + nn * sizeof(abub_stat_job);
+                       nn || nl)) {
+                const size_t bytes = ns * sizeof(abub_shift_job) + (nn + nl) * sizeof(abub_stat_job);
                 h_jobs.grow(bytes);
                 d_jobsBuf.grow(bytes);
                 abub_shift_job *sj = (abub_shift_job *)h_jobs.get();
@@ -1317,15 +1529,22 @@ void deviceFrames(Parser *parser, Plan &pl, int nthreads, int device, SurveyStat
                 abub_stat_job *nj3 = (abub_stat_job *)(h_jobs.get() + ns * sizeof(abub_shift_job));
                 for (size_t q = 0; q < nn; ++q)
                     nj3[q] = jobs[paired[q]];
+                for (size_t q = 0; q < nl; ++q) {
+                    nj3[nn + q] = jobs[with[q]];
+                    if (nj3[nn + q].ref == nj3[nn + q].cur)
+                        nj3[nn + q].ref = UINT64_MAX;
+                }
                 HIPOK(hipMemcpyAsync(d_jobsBuf.get(), h_jobs.get(), bytes, hipMemcpyHostToDevice, cs));
                 d_jobs = (const abub_shift_job *)d_jobsBuf.get();
                 d_pairs = (const abub_stat_job *)(d_jobsBuf.get() + ns * sizeof(abub_shift_job));
+                d_lines = d_pairs + nn;
             }
             const auto rowWith = [&](size_t q) -> SurveyRow & { return pl.rows[rowOf(slot[with[q]])]; };
             // One leg: `entry` over the `ns` jobs of `list` (indices into the stats jobs) in calls of `chunk` (0: all of them in
             // one; no job: no call), each call's status words and payloads ([status, padded to 8 bytes][payloadBytes per job], the
             // one buffer pair of all legs, which synchronise one after another) back in one copy; launch(q0, n, ...) runs the
-            // entry over the list's jobs from q0 on, take(q, payload) gets what job q's row is given
+            // entry over the list's jobs from q0 on, take(q, payload) gets what job q's row is given (a take of four arguments:
+            // (q, the call's payloads, the job's place in the call, the call's jobs), for an entry whose payloads are not one run per job)
             const auto leg = [&](SurveyProduct p, const char *entry, const std::vector<size_t> &list, size_t payloadBytes, size_t chunk,
                                  auto launch, auto take) {
                 if (!pl.want[p])
@@ -1344,7 +1563,11 @@ void deviceFrames(Parser *parser, Plan &pl, int nthreads, int device, SurveyStat
                     for (size_t q = 0; q < n; ++q) {
                         if (((const uint32_t *)h_leg.get())[q] != 0)
                             throw std::runtime_error(std::string("survey: ") + entry + " refused a frame of its own slab");
-                        take(q0 + q, h_leg.get() + statusBytes + q * payloadBytes);
+                        // (a take of four arguments gets the call's payloads whole, the job's place in the call and the call's size)
+                        if constexpr (std::is_invocable_v<decltype(take), size_t, const uint8_t *, size_t, size_t>)
+                            take(q0 + q, (const uint8_t *)h_leg.get() + statusBytes, q, n);
+                        else
+                            take(q0 + q, h_leg.get() + statusBytes + q * payloadBytes);
                         pl.rows[rowOf(slot[list[q0 + q]])].set(p, SurveyRow::Kernel);
                     }
                     ++st.product[p].launches;
@@ -1396,6 +1619,25 @@ void deviceFrames(Parser *parser, Plan &pl, int nthreads, int device, SurveyStat
                 },
                 [&](size_t q, const uint8_t *rec) {
                     pl.rows[rowOf(slot[paired[q]])].noise.assign((const int32_t *)rec, (const int32_t *)rec + cg.cells() * NoiseRecordWords);
+                });
+            // (as the field: in calls of as many jobs as keep the payloads below 64 MiB, or of the field's knob)
+            const size_t linesBytes = ((size_t)H * LinesRowWords + (size_t)W * LinesColWords) * sizeof(uint32_t);
+            size_t linesChunk = std::max<size_t>(1, ((size_t)64 << 20) / linesBytes);
+            if (const char *e = getenv("ABUB_FIELD_CHUNK"))
+                if (atoi(e) > 0)
+                    linesChunk = (size_t)atoi(e);
+            leg(SurveyLinesProduct, "abub_frame_lines_dev", with, linesBytes, linesChunk,
+                [&](size_t q0, int n, uint32_t *status, uint8_t *rec) { // ([rows of all n jobs][cols of all n jobs] behind the status words)
+                    return abub_frame_lines_dev(slab, slabBytes, d_mu, muBytes, d_lines + q0, n, W, H, status, (uint32_t *)rec,
+                                                (uint32_t *)rec + (size_t)n * H * LinesRowWords, cs);
+                },
+                [&](size_t q, const uint8_t *call, size_t in, size_t n) { // (job `in` of a call of n: the rows of all, then the columns)
+                    const uint32_t *all = (const uint32_t *)call;
+                    const uint32_t *rws = all + in * H * LinesRowWords, *cls = all + n * H * LinesRowWords + in * W * LinesColWords;
+                    SurveyRow &row = rowWith(q);
+                    row.linesRows.assign(rws, rws + (size_t)H * LinesRowWords);
+                    row.linesCols.assign(cls, cls + (size_t)W * LinesColWords);
+                    row.linesRef = jobs[with[q]].ref != UINT64_MAX && jobs[with[q]].ref != jobs[with[q]].cur;
                 });
             if (wantPlanes) {
                 st.stats_s += (nowMs() - t0) * 1e-3;
@@ -1552,6 +1794,46 @@ void writeCells(const std::string &dir, const char *tag, SurveyProduct p, const 
     write(dir + "/" + tag + ".txt", text);
 }
 
+// The files of the per-line product, one writer for both routes: per camera with a model cam<c>_lines_rows.npy and
+// cam<c>_lines_cols.npy, the records of its rows that have the product in survey order (the `index` column of the text),
+// cam<c>_lines_model_rows.npy and cam<c>_lines_model_cols.npy; then lines.txt.  All <i4 (no value reaches 2^31)
+void writeLines(const std::string &dir, const Plan &pl, const std::string &text)
+{
+    std::string failed;
+    if (!makeDirs(dir, &failed))
+        throw std::runtime_error("survey: cannot make the directory " + failed);
+    const auto write = [](const std::string &path, const std::string &bytes) {
+        if (!writeFile(path, (const unsigned char *)bytes.data(), bytes.size()))
+            throw std::runtime_error("survey: cannot write " + path);
+    };
+    const auto bytesOf = [](const std::vector<uint32_t> &v) { return std::string((const char *)v.data(), v.size() * sizeof(uint32_t)); };
+    for (size_t c = 0; c < pl.models.size(); ++c) {
+        const SurveyModel &m = pl.models[c];
+        if (!m.trained)
+            continue;
+        std::string rowData, colData;
+        size_t n = 0;
+        for (const SurveyRow &r : pl.rows)
+            if ((size_t)r.cam == c && r.state == SurveyRow::Ok && r.has(SurveyLinesProduct) &&
+                r.linesRows.size() == (size_t)pl.H * LinesRowWords && r.linesCols.size() == (size_t)pl.W * LinesColWords) {
+                rowData += bytesOf(r.linesRows);
+                colData += bytesOf(r.linesCols);
+                ++n;
+            }
+        char shape[96];
+        const std::string stem = dir + "/cam" + std::to_string(c) + "_lines_";
+        snprintf(shape, sizeof shape, "(%zu, %d, %d)", n, pl.H, (int)LinesRowWords);
+        write(stem + "rows.npy", npyHead("<i4", shape) + rowData);
+        snprintf(shape, sizeof shape, "(%zu, %d, %d)", n, pl.W, (int)LinesColWords);
+        write(stem + "cols.npy", npyHead("<i4", shape) + colData);
+        snprintf(shape, sizeof shape, "(%d, %d)", pl.H, (int)LinesModelWords);
+        write(stem + "model_rows.npy", npyHead("<i4", shape) + bytesOf(m.linesRows));
+        snprintf(shape, sizeof shape, "(%d, %d)", pl.W, (int)LinesModelWords);
+        write(stem + "model_cols.npy", npyHead("<i4", shape) + bytesOf(m.linesCols));
+    }
+    write(dir + "/lines.txt", text);
+}
+
 // The files of the per-pixel planes, one writer for both routes ("Surveying a run per pixel"): per camera
 // with a listed row the sum of the host's planes and the device's (dev: [camera][6][stride], or empty) as
 // cam<c>_activity.npy, with a model cam<c>_moved.png, and the cameras' lines of activity.txt
@@ -1682,8 +1964,9 @@ int SurveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCam
         requireDevice(device, "survey", "; without --survey-gpu the run is surveyed on the host");
     const std::string planesDir = outputDir(rq.planesDir, rq.srcRunDir), fieldDir = outputDir(rq.fieldDir, rq.srcRunDir),
                       lightDir = outputDir(rq.lightDir, rq.srcRunDir), focusDir = outputDir(rq.focusDir, rq.srcRunDir),
-                      noiseDir = outputDir(rq.noiseDir, rq.srcRunDir);
-    const bool want[SurveyProducts] = {!rq.shiftPath.empty(), !fieldDir.empty(), !lightDir.empty(), !focusDir.empty(), !noiseDir.empty()};
+                      noiseDir = outputDir(rq.noiseDir, rq.srcRunDir), linesDir = outputDir(rq.linesDir, rq.srcRunDir);
+    const bool want[SurveyProducts] = {!rq.shiftPath.empty(), !fieldDir.empty(), !lightDir.empty(), !focusDir.empty(), !noiseDir.empty(),
+                                       !linesDir.empty()};
     const bool wantCells = want[SurveyFieldProduct] || want[SurveyLightProduct] || want[SurveyFocusProduct] || want[SurveyNoiseProduct];
     if (wantCells && (rq.cellRadius < 1 || rq.cellRadius > 8))
         throw std::runtime_error("survey: the field radius must be in [1, 8], not " + std::to_string(rq.cellRadius));
@@ -1708,8 +1991,8 @@ int SurveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCam
             abub_frame_cells_grid(pl.W, pl.H, pl.cellR, &g.ncx, &g.ncy, &g.x0, &g.y0);
         static const char *const what[SurveyProducts][2] = {
             {nullptr, nullptr}, {"a shift field", "needs"}, {"the light records", "need"}, {"the focus records", "need"},
-            {"the noise records", "need"}};
-        for (int p = SurveyFieldProduct; p < SurveyProducts; ++p)
+            {"the noise records", "need"}, {nullptr, nullptr}};
+        for (int p = SurveyFieldProduct; p <= SurveyNoiseProduct; ++p) // (the per-cell products)
             if (want[p]) // (a frame without a whole cell)
                 needFrames(pl, g.cells() > 0, what[p][0], what[p][1], pl.cellR, ABUB_FIELD_CELL + 2 * pl.cellR);
         // (the model's sums depend on the camera alone: once, here, for both routes)
@@ -1725,6 +2008,15 @@ int SurveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCam
             }
         }
     }
+    if (want[SurveyLinesProduct] && pl.W > 0) // (the model's line sums: once per camera, here, for both routes)
+        for (size_t c = 0; c < pl.models.size(); ++c) {
+            SurveyModel &m = pl.models[c];
+            if (!m.trained)
+                continue;
+            m.linesRows.resize((size_t)pl.H * LinesModelWords);
+            m.linesCols.resize((size_t)pl.W * LinesModelWords);
+            linesModelHost(pl.mu[c], pl.sigma6[c].data(), pl.W, pl.H, m.linesRows.data(), m.linesCols.data());
+        }
     std::unique_ptr<HostPlanes> hostPlanes;
     std::vector<uint32_t> devPlanes;
     if (!planesDir.empty()) {
@@ -1741,7 +2033,7 @@ int SurveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCam
     for (const SurveyModel &m : pl.models)
         st.modelCams += m.trained;
     // (the products' kernels take sides of up to 65535: a larger run with one of them is the host route's whole)
-    if (device >= 0 && pl.W > 0 && decodersTakeWidth(pl.W) && ((!want[SurveyShiftProduct] && !wantCells) || (pl.W <= 65535 && pl.H <= 65535))) {
+    if (device >= 0 && pl.W > 0 && decodersTakeWidth(pl.W) && ((!want[SurveyShiftProduct] && !wantCells && !want[SurveyLinesProduct]) || (pl.W <= 65535 && pl.H <= 65535))) {
         st.device = device;
         deviceFrames(parser, pl, nthreads, device, st, devPlanes);
     } else
@@ -1792,6 +2084,8 @@ int SurveyRun(Parser *parser, const std::vector<Trainer *> &trainers, int numCam
     if (want[SurveyNoiseProduct])
         writeCells(noiseDir, "noise", SurveyNoiseProduct, pl, NoiseRecordWords, &SurveyRow::noise, "<i8", NoiseModelWords, &SurveyModel::noise,
                    NoiseReport(pl.cellR, pl.W, pl.H, pl.models, pl.rows));
+    if (want[SurveyLinesProduct])
+        writeLines(linesDir, pl, LinesReport(pl.W, pl.H, pl.models, pl.rows));
     if (hostPlanes) {
         const double t1 = nowMs();
         st.planeRowsHost = hostPlanes->rows;

@@ -962,6 +962,36 @@ int abub_frame_noise_cells_dev(const uint8_t *frames, size_t frames_bytes, const
                                const abub_stat_job *jobs, int njobs, int W, int H, int x0, int y0, int ncx, int ncy,
                                uint32_t *status /*[njobs]*/, int32_t *rec /*[njobs * ncy * ncx * 6]*/, void *stream);
 
+/* ---- per-line sums of whole resident frames (abub_stats.hip) -----------------------------------------------------------
+ * Is a frame torn, repeated or banded: does a run of its rows equal the rows of the frame two before it, do single rows or
+ * columns stand above the model (abub3hs --survey --survey-lines; definition, rule, files and measurements: DESIGN section
+ * 3, "Surveying a run for torn, repeated and banded frames")?  Per image row y of the W x H frame p at frames + jobs[j].cur,
+ * against the plane m at mu + jobs[j].model and the reference frame r at frames + jobs[j].ref, five u32 over the row's W
+ * pixels:
+ *   rows[(j * H + y) * 5 + 0 .. 4] = sum p; sum |p - m|; n_clip, the pixels with p == 0 or p == 255; sum |p - r|; n_same,
+ *   the pixels with p == r
+ * and per image column x the first three of them over the column's H pixels: cols[(j * W + x) * 3 + 0 .. 2].  A job with
+ * ref == UINT64_MAX has no reference frame: its words 3 and 4 are 0.  ref == cur is legal: n_same = W and word 3 = 0.  Every
+ * value is an exact integer of at most 65535 * 255 = 16711425, bit-identical to the host definition (host/survey.cpp
+ * linesHost) whatever the order of the jobs or the blocks: one launch on `stream`, a block of four waves per job, which
+ * reads the job's three streams once (16-byte loads where the address allows, aligned dwords elsewhere) and owns every
+ * output word of the job: plain stores, no atomics on memory, no clearing launch, no scratch buffer, no host
+ * synchronisation, no allocation, no workgroup waiting for another.  What the sums mean is the host's to say
+ * (abub::lineRate, abub::linesFrame).
+ * Every pointer is a device pointer; jobs is 8-byte aligned, status, rows and cols 4-byte aligned; W and H in [1, 65535].
+ * No alignment rule on the three offsets.  status[j] (0 or ABUB_SHIFT_E_RANGE) and all H * 5 values of rows[j] and W * 3 of
+ * cols[j] are written in full by every call with njobs > 0, whatever they held before, and nothing else is written.  A job
+ * of which the frame or a reference frame that is there runs past frames_bytes or the plane past model_bytes gets
+ * ABUB_SHIFT_E_RANGE and zero records; nothing of it is read.  Null pointers, njobs < 0, W or H out of range or a
+ * misaligned jobs / status / rows / cols: ABUB_E_INVALID before anything touches the device.  njobs == 0: ABUB_OK, nothing
+ * is touched.  njobs may exceed 65535. */
+#define ABUB_LINES_ROW_WORDS 5
+#define ABUB_LINES_COL_WORDS 3
+int abub_frame_lines_dev(const uint8_t *frames, size_t frames_bytes, const uint8_t *mu, size_t model_bytes,
+                         const abub_stat_job *jobs, int njobs, int W, int H,
+                         uint32_t *status /*[njobs]*/, uint32_t *rows /*[njobs * H * 5]*/,
+                         uint32_t *cols /*[njobs * W * 3]*/, void *stream);
+
 /* ---- the two DebugPeek planes of a batch of resident frames (abub_peek.hip) ------------------------------------------
  * What L3Localizer::CalculateInitialBubbleParams builds on the analyzer's thread for its debug write-out (reference
  * L3Localizer.cpp:252-257, 397, 448; DESIGN section 3, "The peek planes"), for a batch of items.  Per item two W x H u8
