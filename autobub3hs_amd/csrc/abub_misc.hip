@@ -207,7 +207,7 @@ __global__ __launch_bounds__(256) void k1_welford(const uint8_t *__restrict__ fr
     mu[px] = (uint8_t)(int)mean;
 }
 
-// 4 pixels per thread (dword loads) when P % 4 == 0
+// 4 pixels per thread (dword loads and stores): P % 4 == 0 and frames, mu, sigma 4-byte aligned (abub_train_dev)
 __global__ __launch_bounds__(256) void k1_welford4(const uint8_t *__restrict__ frames,
                                                    const uint32_t *__restrict__ idx, int N, size_t P,
                                                    uint8_t *__restrict__ mu,
@@ -249,7 +249,10 @@ extern "C" int abub_train_dev(const uint8_t *frames, const uint32_t *idx, int N,
         return set_err(ABUB_E_INVALID, "abub_train_dev: bad arguments");
     size_t P = (size_t)W * H;
     hipStream_t st = (hipStream_t)stream;
-    if ((P & 3) == 0) {
+    // the dword kernel is a choice of the launcher: every frame starts at frames + f * P, so with P % 4 == 0 the
+    // alignment of `frames` is that of every row it reads
+    const bool wide = (P & 3) == 0 && (((uintptr_t)frames | (uintptr_t)mu | (uintptr_t)sigma) & 3) == 0;
+    if (wide) {
         size_t nq = P / 4;
         hipLaunchKernelGGL(k1_welford4, dim3((unsigned)((nq + 255) / 256)), dim3(256), 0, st, frames,
                            idx, N, P, mu, sigma);
@@ -309,13 +312,15 @@ extern "C" int abub_pair_hist_dev(const uint8_t *frames, const abub_job *pairs, 
 }
 
 // ------------------------------------------------------------------------------------------------
-// K4: binarize + foreground compaction.  grid (blocks, nimg); 16 pixels per thread per step when
-// the image size allows it.
+// K4: binarize + foreground compaction.  grid (blocks, nimg); 16 pixels per thread per step (`wide`) when
+// the launcher finds P % 16 == 0 and img 16-byte aligned, so that every image img + k * P is.
 // ------------------------------------------------------------------------------------------------
+static int k4_wide(const uint8_t *img, size_t P) { return (P & 15) == 0 && ((uintptr_t)img & 15) == 0; }
+
 __global__ __launch_bounds__(256) void k4_compact(const uint8_t *__restrict__ img, size_t P,
                                                   const int32_t *__restrict__ thr,
                                                   uint32_t *__restrict__ idx, int cap,
-                                                  uint32_t *__restrict__ count)
+                                                  uint32_t *__restrict__ count, int wide)
 {
     const int k = blockIdx.y;
     const uint8_t *im = img + (size_t)k * P;
@@ -323,7 +328,7 @@ __global__ __launch_bounds__(256) void k4_compact(const uint8_t *__restrict__ im
     uint32_t *cnt = count + k;
     uint32_t *out = idx + (size_t)k * cap;
     size_t stride = (size_t)gridDim.x * blockDim.x;
-    if ((P & 15) == 0) {
+    if (wide) {
         size_t nv = P / 16;
         for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < nv; q += stride) {
             uint4 w = reinterpret_cast<const uint4 *>(im)[q];
@@ -372,7 +377,7 @@ extern "C" int abub_fg_compact_dev(const uint8_t *img, int nimg, int W, int H, c
         bx = 1;
     if (bx > 512)
         bx = 512;
-    hipLaunchKernelGGL(k4_compact, dim3(bx, nimg), dim3(256), 0, st, img, P, thr, idx, cap, count);
+    hipLaunchKernelGGL(k4_compact, dim3(bx, nimg), dim3(256), 0, st, img, P, thr, idx, cap, count, k4_wide(img, P));
     HIPCHK(hipGetLastError());
     return ABUB_OK;
 }
@@ -381,13 +386,13 @@ extern "C" int abub_fg_compact_dev(const uint8_t *img, int nimg, int W, int H, c
 __global__ __launch_bounds__(256) void k4_compact_pairs(const uint8_t *__restrict__ img, size_t P,
                                                         const int32_t *__restrict__ thr,
                                                         uint32_t *__restrict__ pairs, uint32_t cap,
-                                                        uint32_t *__restrict__ count)
+                                                        uint32_t *__restrict__ count, int wide)
 {
     const uint32_t k = blockIdx.y;
     const uint8_t *im = img + (size_t)k * P;
     const int t = thr[k];
     size_t stride = (size_t)gridDim.x * blockDim.x;
-    if ((P & 15) == 0) {
+    if (wide) {
         size_t nv = P / 16;
         for (size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x; q < nv; q += stride) {
             uint4 w = reinterpret_cast<const uint4 *>(im)[q];
@@ -441,7 +446,8 @@ extern "C" int abub_fg_compact_pairs_dev(const uint8_t *img, int nimg, int W, in
         int n = nimg - base < 65535 ? nimg - base : 65535;
         if (base != 0)
             return set_err(ABUB_E_INVALID, "abub_fg_compact_pairs_dev: nimg > 65535");
-        hipLaunchKernelGGL(k4_compact_pairs, dim3(bx, n), dim3(256), 0, st, img, P, thr, pairs, cap, count);
+        hipLaunchKernelGGL(k4_compact_pairs, dim3(bx, n), dim3(256), 0, st, img, P, thr, pairs, cap, count,
+                           k4_wide(img, P));
     }
     HIPCHK(hipGetLastError());
     return ABUB_OK;

@@ -83,7 +83,9 @@ int abub_diff_roi_dev(const uint8_t *cur, const uint8_t *ref, const uint8_t *sig
                       int rx, int ry, int rw, int rh, uint8_t *diff, uint32_t *hist, void *stream);
 
 /* K1: Trainer::CalculateMeanSigmaImageVector (Trainer.cpp:144-216): float32 Welford over the
- * N frames `idx[0..N)` (device array of frame indices, NULL = 0..N-1) of `frames`. */
+ * N frames `idx[0..N)` (device array of frame indices, NULL = 0..N-1) of `frames`.  Any byte address will do for
+ * frames, mu and sigma: four pixels per thread with 4-byte loads and stores when W*H % 4 == 0 and all three are
+ * 4-byte aligned, one pixel per thread otherwise, with the same bytes. */
 int abub_train_dev(const uint8_t *frames, const uint32_t *idx, int N, int W, int H, uint8_t *mu,
                    uint8_t *sigma, void *stream);
 
@@ -103,7 +105,9 @@ int abub_posttrig_dev(const uint8_t *frames, const uint8_t *mu, const uint8_t *s
  * img[k] (the TOZERO + BINARY|OTSU mask of L3Localizer.cpp:252-254,786-787 with
  * thr = max(loc_thres, otsu)).  idx: [nimg][cap] u32 raster indices (unordered); count: [nimg]
  * (true counts, may exceed cap -> caller falls back to abub_fetch; nothing is written past cap).
- * Any thr: a negative one lists value-0 pixels too. */
+ * Any thr: a negative one lists value-0 pixels too.  Any byte address will do for img: it is read 16 bytes at a time
+ * when W*H % 16 == 0 and img is 16-byte aligned (so that every image is), a byte at a time otherwise, with the same
+ * lists. */
 int abub_fg_compact_dev(const uint8_t *img, int nimg, int W, int H, const int32_t *thr,
                         uint32_t *idx, int cap, uint32_t *count, void *stream);
 
@@ -218,7 +222,7 @@ int abub_pairs_group_hist_dev(const uint32_t *pairs, const uint32_t *count, uint
 
 /* K4, batched form: one shared output list for all nimg images, pairs[2*k] = image | value << 24,
  * pairs[2*k+1] = y*W+x (unordered); *count = true total (may exceed cap; nothing is written past cap).
- * Any thr, as abub_fg_compact_dev. */
+ * Any thr and any address of img, as abub_fg_compact_dev. */
 int abub_fg_compact_pairs_dev(const uint8_t *img, int nimg, int W, int H, const int32_t *thr,
                               uint32_t *pairs, uint32_t cap, uint32_t *count, void *stream);
 
