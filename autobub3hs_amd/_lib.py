@@ -25,6 +25,9 @@ class TrigStack(C.Structure):
                 ("first_bad", C.c_int32)]
 
 
+TRIG_MAX_PIXELS = 2147483583  # ABUB_TRIG_MAX_PIXELS (2^31 - 65): abub_trigger_search_dev refuses a larger W * H
+
+
 class ContourDesc(C.Structure):
     _fields_ = [("x", C.c_int32), ("y", C.c_int32), ("w", C.c_int32), ("h", C.c_int32), ("area", C.c_double),
                 ("radius", C.c_double), ("m00", C.c_double), ("m10", C.c_double), ("m01", C.c_double), ("cx", C.c_float),

@@ -340,6 +340,12 @@ extern "C" int abub_trigger_search_dev(const abub_trig_stack *stacks, const abub
     if (!stacks || !out || !desc || nstacks < 0 || nsegs < 0 || (nsegs > 0 && !segs) || W <= 0 || H <= 0 ||
         (size_t)W * H > 0x7fffffffu || (sig_main && sig_pitch <= 0))
         return set_err(ABUB_E_INVALID, "abub_trigger_search_dev: bad arguments");
+    // (int)count and (int)((float)rem - count) are defined only while the float is below 2^31.  A bin holds at most W * H
+    // pixels and `rem` never rises, so both floats are at most (float)(W * H): 2^31 - 128 up to W * H = 2^31 - 65, and
+    // 2^31 from 2^31 - 64 on (the tie goes to the even mantissa) -- undefined on the host, saturating on the device.
+    static_assert(ABUB_TRIG_MAX_PIXELS == 0x7fffffff - 64, "the largest int whose float is below 2^31");
+    if ((size_t)W * H > (size_t)ABUB_TRIG_MAX_PIXELS)
+        return set_err(ABUB_E_INVALID, "abub_trigger_search_dev: W * H above ABUB_TRIG_MAX_PIXELS (a float count would leave the int range)");
     if (nstacks == 0)
         return ABUB_OK;
     if (((uintptr_t)desc & 255) || desc_bytes < abub_trigger_search_desc_bytes(nstacks, nsegs))

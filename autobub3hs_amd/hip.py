@@ -260,7 +260,9 @@ def trigger_search(stacks, W, H, sig_main=True):
     """K6 (abub_trigger_search_dev): one trigger search per stack in one launch.  stacks: a list of dicts with F, tss and
     segs = [(first, hist, pending)] (hist: int32 device tensor [count, 256], pending: uint8 device tensor [count] or
     None), optionally start (1) and first_bad (F).  -> (list of result dicts with the fields of abub_trig_result,
-    sig_main: float64 tensor [nstacks, max F] filled with NaN where the search evaluated no main-loop frame, or None)."""
+    sig_main: float64 tensor [nstacks, max F] filled with NaN where the search evaluated no main-loop frame, or None).
+    W * H <= 2^31 - 65 (ABUB_TRIG_MAX_PIXELS), the largest pixel count whose float stays below 2^31: the search converts
+    float counts and its float pixel counter to int.  A larger one is refused."""
     import ctypes as C
     import struct
     n = len(stacks)

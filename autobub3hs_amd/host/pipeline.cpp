@@ -1313,7 +1313,7 @@ public:
     int stackFrames(int s) const { return meta.empty() ? F : (int)meta[s].names.size(); }
     // trigger knob: is stack s searched on the device in this run (decided before the first search, from the kernel's static
     // limits; the host search stays for the others), and the stacks of a list that are
-    bool devRoute(int s) const { return trigOn && stackFrames(s) <= trigMaxF; }
+    bool devRoute(int s) const { return trigOn && stackFrames(s) <= trigMaxF && P <= (size_t)ABUB_TRIG_MAX_PIXELS; }
     std::vector<int> devRoute(std::vector<int> list) const
     {
         list.erase(std::remove_if(list.begin(), list.end(), [this](int s) { return !devRoute(s); }), list.end());

@@ -308,6 +308,7 @@ typedef struct abub_trig_result {
     float sig;                      /* singleEntropy of the last main-loop frame */
     int32_t reserved;
 } abub_trig_result;
+#define ABUB_TRIG_MAX_PIXELS 2147483583 /* 2^31 - 65: the largest W * H abub_trigger_search_dev takes (see there) */
 /* One search per stack (AnalyzerUnit.cpp:119-324, 435-504, 514-532), all in one launch.  stacks[nstacks] and segs[nsegs] are HOST arrays: they are checked here, before
  * anything is launched (a stack beyond abub_trigger_search_limits, overlapping segments: ABUB_E_INVALID), then copied to
  * `desc` on the stream -- device memory of abub_trigger_search_desc_bytes(nstacks, nsegs) bytes, 256-byte aligned; keep the
@@ -317,7 +318,10 @@ typedef struct abub_trig_result {
  * loc_thres -1, evaluated 0, sig 0).  A frame behind a missing one never influences anything.  n < 5 gives DONE, -9.
  * sig_main: NULL, or device [nstacks][sig_pitch] doubles (sig_pitch >= every F): entry [s][i] receives the significance
  * of every main-loop frame i the search of stack s evaluated, when its state is DONE or BAD_LOOKAHEAD; other entries,
- * and the whole row of a search that needs frames, are left alone. */
+ * and the whole row of a search that needs frames, are left alone.
+ * W * H <= ABUB_TRIG_MAX_PIXELS, else ABUB_E_INVALID: the search converts a float bin count and the float pixel counter
+ * (`pix_rem -= binEntry`, AnalyzerUnit.cpp:493) to int, which is defined only below 2^31; no histogram bin of a W x H frame
+ * and no value of the counter exceeds W * H, and (float)(W * H) is 2^31 - 128 up to 2^31 - 65 and 2^31 from 2^31 - 64 on. */
 int abub_trigger_search_dev(const abub_trig_stack *stacks, const abub_trig_seg *segs, int nstacks, int nsegs, int W, int H,
                             void *desc, size_t desc_bytes, abub_trig_result *out, double *sig_main, int sig_pitch,
                             void *stream);

@@ -21,12 +21,17 @@ def process_frame(cur, ref, sigma):
 
 
 class Sig:
-    """AnalyzerUnit::calculateSignificanceFrame (AnalyzerUnit.cpp:435-504) on histograms."""
+    """AnalyzerUnit::calculateSignificanceFrame (AnalyzerUnit.cpp:435-504) on histograms.
+
+    pix[i] (the pushed counts of bin i) and sq[i] (their squares as the reference's int product wraps them) are re-summed
+    from the start for every bin of every evaluation, as CalcMean / CalcStdDev do; both sums are of integers far below
+    2^53, so summing them as Python ints and converting once gives the double the reference's running double sum holds."""
 
     def __init__(self, P, training_set_size):
         self.P = P
         self.tss = training_set_size
         self.pix = [[] for _ in range(256)]
+        self.sq = [[] for _ in range(256)]
         self.loc_thres = 3
 
     def __call__(self, h, store):
@@ -38,16 +43,14 @@ class Sig:
                 break
             b = float(np.float32(h[i]))
             if store:
-                self.pix[i].append(int(b))
+                v = int(b)
+                sq = (v * v) & 0xFFFFFFFF
+                self.pix[i].append(v)
+                self.sq[i].append(sq - 2 ** 32 if sq >= 2 ** 31 else sq)
             if i > 1:
                 n0 = len(self.pix[0])
                 mean = float(sum(self.pix[i])) / n0
-                ss = 0.0
-                for v in self.pix[i]:
-                    sq = (v * v) & 0xFFFFFFFF
-                    if sq >= 2 ** 31:
-                        sq -= 2 ** 32
-                    ss += sq
+                ss = float(sum(self.sq[i]))
                 var = ss / n0 - mean * mean
                 sd = math.sqrt(var) if var >= 0 else float("nan")
                 if b != mean or sd > 0:
@@ -69,7 +72,7 @@ class Sig:
                 if lt > 3 or self.tss < 6:
                     lt = 3
                 self.loc_thres = lt
-            rem -= int(b)
+            rem = int(np.float32(rem) - np.float32(h[i]))  # `pix_rem -= binEntry`, an int -= float (:493)
         return sig
 
 

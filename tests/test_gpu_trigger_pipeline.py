@@ -253,3 +253,69 @@ def test_run_batched_text_is_the_same_with_the_knob(tmp_path, monkeypatch):
     assert n1[0] >= nev * ncams and n1[1] == 0, n1
     assert txt == ref
     assert "  -9  " in ref and len(ref.splitlines()) >= nev * ncams
+
+
+def _triggers_where_built(oracle, slab, models, tss, specs):
+    """the oracle alone, before any device result is looked at: every designed bubble triggers at its t0"""
+    E, C_ = slab.shape[:2]
+    for e in range(E):
+        for c in range(C_):
+            a = oracle.Analyzer(slab[e, c], models[c][0], models[c][1], tss[c])
+            st = a.find_trigger(1)
+            a.close()
+            t0 = specs[e * C_ + c].t0
+            assert (st["status"], st["trig"] if t0 is not None else None) == ((0, t0) if t0 is not None else (-3, None)), (e, c, t0, st)
+
+
+def test_pipeline_trigger_across_a_tile_seam(oracle, monkeypatch):
+    """70 frames: K6 walks a stack in tiles of 64 frames from frame 1, and the bubbles start at 62 .. 65, around its first
+    seam (64 | 65); block 0 ends at frame 60 and the lazy blocks have 4 frames, so the searches stop and go on around it"""
+    W, H, F, E, C_ = 1280, 96, 70, 4, 2
+    B = [(600, 48, 40)]
+    specs = [synth.EventSpec(F, 62, B), synth.EventSpec(F, 63, B), synth.EventSpec(F, 64, B), synth.EventSpec(F, 64, [(200, 30, 40)]),
+             synth.EventSpec(F, 65, B), synth.EventSpec(F, flicker=63, flicker_adu=12), synth.EventSpec(F, 63, [(900, 50, -40)]),
+             synth.EventSpec(F)]
+    slab = np.stack([synth.render_event(W, H, sp, 300 + k // C_, k % C_) for k, sp in enumerate(specs)]).reshape(E, C_, F, H, W)
+    tr0, tr1 = synth.training_pairs(W, H, 10, 0, F), synth.training_pairs(W, H, 2, 1, F)
+    models = [oracle.welford(tr0), oracle.welford(tr1)]
+    tss = [len(tr0), len(tr1)]
+    _triggers_where_built(oracle, slab, models, tss, specs)
+    d_slab, d_mu, d_s6 = _device(slab, models)
+    env = {"ABUB_PIPE_BLOCK0": "60", "ABUB_PIPE_BLOCK": "4"}
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    pipe = host.Pipeline(0, W, H, F, E, C_, tss, nthreads=4)
+    for k in env:
+        monkeypatch.delenv(k)
+    st_ = torch.cuda.current_stream().cuda_stream
+    res, st = _both_settings(pipe, lambda: pipe.run(d_slab, d_mu, d_s6, st_), E * C_)
+    _against_oracle(oracle, res, slab, models, tss, "seam")
+    assert st["need_frames"] > 0, st
+    pipe.close()
+
+
+@pytest.mark.parametrize("over", [0, 1])
+def test_pipeline_trigger_at_and_above_the_frame_limit(oracle, over):
+    """a stack of exactly abub_trigger_search_limits() frames is searched on the device (its last tile is partial), one
+    frame more keeps the host search; a bubble in the last tile, both against the oracle"""
+    F0, _ = hip.trigger_search_limits()
+    W, H, F, E, C_ = 320, 64, F0 + over, 1, 2
+    specs = [synth.EventSpec(F, 450, [(160, 32, 40)]), synth.EventSpec(F, 450, [(100, 30, 40)])]
+    slab = np.stack([synth.render_event(W, H, sp, 300, c) for c, sp in enumerate(specs)]).reshape(E, C_, F, H, W)
+    tr0, tr1 = synth.training_pairs(W, H, 10, 0, F), synth.training_pairs(W, H, 2, 1, F)
+    models = [oracle.welford(tr0), oracle.welford(tr1)]
+    tss = [len(tr0), len(tr1)]
+    _triggers_where_built(oracle, slab, models, tss, specs)
+    d_slab, d_mu, d_s6 = _device(slab, models)
+    pipe = host.Pipeline(0, W, H, F, E, C_, tss, nthreads=4)
+    st_ = torch.cuda.current_stream().cuda_stream
+    res = []
+    for v in (0, 1):
+        pipe.set_option("trigger", v)
+        pipe.run(d_slab, d_mu, d_s6, st_)
+        res.append([pipe.result(s) for s in range(E * C_)])
+    st = pipe.trigger_stats()
+    assert (st["device"], st["host_route"]) == ((0, 2) if over else (2, 0)), st
+    assert repr(res[0]) == repr(res[1])
+    _against_oracle(oracle, res[1], slab, models, tss, "limit + %d" % over)
+    pipe.close()

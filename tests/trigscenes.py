@@ -160,25 +160,52 @@ def random_cases(seed, n, frame_counts, P):
     return cases
 
 
-def step_stack(seed, F, t0, P, flicker=None):
-    """a quiet stack with a bubble that starts at t0 and grows (and optionally a one-frame flicker before it)"""
+def step_stack(seed, F, t0, P, flicker=None, flicker_len=1):
+    """a quiet stack with a bubble that starts at t0 and grows (t0 = F: none), and optionally a flicker of one frame, or
+    of flicker_len frames, from frame `flicker` on"""
     rng = np.random.RandomState(seed)
     h = _noise(rng, F, 0.5)
     for i in range(t0, F):
         h[i, 2:30] += 60 + 30 * (i - t0)
     if flicker is not None:
-        h[flicker, 2:7] += 400
+        h[flicker:flicker + flicker_len, 2:7] += 400
     h[:, 0] = 0
     h[:, 0] = P - h.sum(1)
     h[0] = 0
     return h.astype(np.uint32)
 
 
+def spike_stack(seed, F, t0, P):
+    """a small bubble from t0 on (bins 2 .. 6 only) with one very bright frame at t0 + 1.  The search triggers at t0 on
+    its second look-ahead, frame t0 + 2, whose history is frames 1 .. t0: were frame t0 + 1 left in that history, its
+    standard deviations would be some hundred times larger and the look-ahead would fail."""
+    rng = np.random.RandomState(seed)
+    h = _noise(rng, F, 0.5)
+    h[t0:, 2:7] += 30
+    h[t0 + 1, 2:7] += 4000
+    h[:, 0] = 0
+    h[:, 0] = P - h.sum(1)
+    h[0] = 0
+    return h.astype(np.uint32)
+
+
+def seams_of(F):
+    """the kernel's tile seams of an F-frame stack: s with frames s | s + 1 in different 64-frame tiles (tiles start at 1)"""
+    return range(64, F - 1, 64)
+
+
 def edge_cases(P=512 * 512, F=12):
     """Arithmetic edges: wrapped squares (negative variance -> NaN), constant columns (sd = 0, term skipped), a constant
-    history with a different look-ahead count (+-inf, then inf - inf), and frames that stop below earlier frames' bins."""
+    history with a different look-ahead count (+-inf, then inf - inf), and frames that stop below earlier frames' bins.
+    With F > 64 (70, 131) the jumps and the changes of the constant columns sit at s - 1 .. s + 2 of a tile seam s (64, 128)
+    of the kernel, so NaN, +-inf and a negative sum of squares are history carried from one tile into the next."""
     rng = np.random.RandomState(11)
     cases = []
+    seams = list(seams_of(F))
+
+    def at(k, short):
+        """where family member k's event starts: as ever in a short stack, else at s - 1 .. s + 2 of the seams in turn"""
+        return short if not seams else seams[k % len(seams)] - 1 + (k // len(seams)) % 4
 
     def fin(h, tss):
         h[:, 0] = 0
@@ -199,7 +226,7 @@ def edge_cases(P=512 * 512, F=12):
         h[:, 3] = 100
         h[:, 4] = 50
         h[:, 6:13] = 10 + rng.randint(0, 3, (F, 7))
-        tj = 3 + k % 5
+        tj = at(k, 3 + k % 5)
         h[tj:, 6:13] += 3000
         if k < 5:
             h[tj + 1:, 3] = 200 + k      # only upwards: +inf and stays there
@@ -211,8 +238,198 @@ def edge_cases(P=512 * 512, F=12):
         h = np.zeros((F, 256), np.int64)
         h[1:4, 2:200] = rng.randint(0, 40, (3, 198))
         h[4:, 2:6] = rng.randint(0, 40, (F - 4, 4))
-        h[6 + k % 3:, 2:5] += 900
+        h[at(k, 6 + k % 3):, 2:5] += 900
         fin(h, (2, 10)[k % 2])
+    return cases
+
+
+def walk(h, P):
+    """one evaluation's way through the bins of histogram h with the reference's counter (`pix_rem -= binEntry`, an int
+    -= float, AnalyzerUnit.cpp:493) -> (last bin walked, the counter behind it, the exact counter behind it)"""
+    rem = ex = int(P)
+    last = 0
+    for i in range(256):
+        if rem <= 0:
+            break
+        last = i
+        rem = int(np.float32(rem) - np.float32(h[i]))
+        ex -= int(h[i])
+    return last, rem, ex
+
+
+def _fin(h, P):
+    h[:, 0] = 0
+    h[:, 0] = P - h.sum(1)
+    assert (h[:, 0] >= 0).all()
+    h[0] = 0
+    return h.astype(np.uint32)
+
+
+def _case(h, P, tss, what, **kw):
+    c = dict(hists=h, P=P, tss=tss, start=1, first_bad=len(h), cuts=[], what=what)
+    c.update(kw)
+    return c
+
+
+def seam_sets(limit=512):
+    """(F, s): the frame counts of the designed scenes and the tile seam the scene is built around"""
+    assert limit > 130
+    return (67, 64), (70, 64), (131, 64), (131, 128), (limit, max(seams_of(limit)))
+
+
+# step stacks whose first seed has a noise frame just below t0 that passes both look-aheads and triggers in its place
+_SEAM_RESEED = {(131, 128, 128): 1, (512, 448, 449): 1}
+_SPIKE_RESEED = {(67, 64, 64): 4, (512, 448, 448): 1}
+
+
+def seam_cases(P=1280 * 96, limit=512):
+    """Decisions placed at a tile seam s of the kernel (frames s | s + 1 lie in different 64-frame tiles).  Per (F, s) of
+    seam_sets(): a growing step (step_stack: it triggers at t0) and a one- and a two-frame flicker (a look-ahead that
+    fails) at each of s - 2 .. s + 2, a spike_stack at s - 2 .. s (its second look-ahead decides by the history alone), and on the step stacks retries from s .. s + 2 and from behind the trigger,
+    first_bad, the end of the coverage and a pending frame at s .. s + 2, a hole in the history of a retry, and segment
+    cuts at the seam and every 16 frames.  Each case says in `what`, `seam` and `t0` what it was built as."""
+    cases = []
+    for n, (F, s) in enumerate(seam_sets(limit)):
+        steps = {}
+        for k, t0 in enumerate(range(s - 2, s + 3)):
+            tss = (2, 10)[(k + n) % 2]
+            h = step_stack(7000 + 100 * n + t0 + 1000 * _SEAM_RESEED.get((F, s, t0), 0), F, t0, P)
+            steps[t0] = (h, tss)
+            cases.append(_case(h, P, tss, "step", seam=s, t0=t0))
+            for fl in (1, 2):  # the flicker at t0, and (where there is room) a bubble some frames behind it
+                hf = step_stack(7050 + 100 * n + 10 * fl + t0, F, t0 + 8 if t0 + 12 < F else F, P, t0, fl)
+                cases.append(_case(hf, P, (10, 2)[(k + n) % 2], "flicker%d" % fl, seam=s, t0=t0))
+        for k, t0 in enumerate((s - 2, s - 1, s)):  # the second look-ahead is frame s, s + 1 (lane 0 of the next tile), s + 2
+            cases.append(_case(spike_stack(7090 + 100 * n + t0 + 1000 * _SPIKE_RESEED.get((F, s, t0), 0), F, t0, P), P, (10, 2)[(k + n) % 2], "spike", seam=s, t0=t0))
+        for t0 in (s - 1, s, s + 1, s + 2):
+            h, tss = steps[t0]
+            kw = dict(seam=s, t0=t0)
+            if t0 in (s, s + 2):
+                for st in (s, s + 1, s + 2):
+                    cases.append(_case(h, P, tss, "retry", start=st, **kw))
+            if t0 <= s + 1:
+                cases.append(_case(h, P, tss, "retry behind the trigger", start=t0 + 1, **kw))
+                for fb in (s, s + 1, s + 2):
+                    cases.append(_case(h, P, tss, "first_bad", first_bad=fb, **kw))
+            if t0 in (s, s + 2):  # NEED_* from the look-aheads of main frame s, and from the main loop
+                for e in (s - 1, s, s + 1):
+                    cov = np.zeros(F, bool)
+                    cov[1:e + 1] = True
+                    cases.append(_case(h, P, tss, "covered", covered=cov, pending=np.zeros(F, bool), end=e, **kw))
+                    pend = np.zeros(F, bool)
+                    pend[e + 1] = True
+                    cases.append(_case(h, P, tss, "pending", covered=np.ones(F, bool), pending=pend, **kw))
+        h, tss = steps[s + 1]
+        cov = np.ones(F, bool)
+        cov[10] = False  # a frame of the history of a retry, one tile (or more) below it
+        cases.append(_case(h, P, tss, "hole below start", start=s + 2, covered=cov, pending=np.zeros(F, bool), seam=s, t0=s + 1))
+        cases.append(_case(h, P, tss, "cuts at the seam", cuts=[s, s + 1], seam=s, t0=s + 1))
+        h, tss = steps[s]
+        cases.append(_case(h, P, tss, "cuts every 16", cuts=list(range(16, F, 16)), seam=s, t0=s))
+    return cases
+
+
+CHUNK_TOPS = (63, 64, 65, 127, 128, 129, 191, 192, 255)
+
+
+def _chunk_stack(rng, F, P, tops, change=None):
+    """counts up to bin tops[i] in frame i: a level per bin plus a unit that alternates along the bins and the frames, so a
+    frame's terms cancel in pairs and only what `change` adds (or a frame that pushes bins others did not) is significant"""
+    level = rng.randint(3, 40, 256)
+    i, b = np.meshgrid(np.arange(F), np.arange(256), indexing="ij")
+    h = (level[None, :] + ((i + b) & 1)).astype(np.int64)
+    if change is not None:
+        change(h)
+    h[:, :2] = 0
+    h[b > np.asarray(tops)[:, None]] = 0
+    return _fin(h, P)
+
+
+def chunk_cases(P=1280 * 96, limit=512):
+    """Stacks longer than a tile whose frames push counts beyond the first 64-bin chunk the kernel stages, up to bin 255:
+    the prefix sums of bins >= 64 are carried over a seam, a tile that ends in chunk 0 lies between two that reach bin
+    220, frame s (lane 63 of its tile) stops 130 bins below or above its neighbours, and steps and flickers in the high
+    bins at s - 1 .. s + 1 make the look-aheads run over those bins across the seam."""
+    rng = np.random.RandomState(23)
+    cases = []
+
+    def step(t0, lo, hi, grow=15):
+        def f(h):
+            for i in range(t0, len(h)):
+                h[i, lo:hi + 1] += 40 + grow * (i - t0)
+        return f
+
+    def flicker(t0, n, lo, hi):
+        def f(h):
+            h[t0:t0 + n, lo:hi + 1] += 150
+        return f
+
+    sets = [(70, 64), (131, 64), (131, 128), (limit, max(seams_of(limit)))]
+    for n, (F, s) in enumerate(sets):
+        tss = (10, 2)[n % 2]
+        tops = [255] * F  # every CHUNK_TOPS value as a frame's last bin, at s - 6 .. s + 2
+        tops[s - 6:s + 3] = CHUNK_TOPS if n % 2 == 0 else CHUNK_TOPS[::-1]
+        cases.append(_case(_chunk_stack(rng, F, P, tops), P, tss, "tops", seam=s))
+        if F == limit:
+            break  # (one case at the limit)
+        tops = [230] * F
+        tops[s] = 100
+        cases.append(_case(_chunk_stack(rng, F, P, tops, step(s - 1, 150, 200)), P, tss, "lane 63 low", seam=s))
+        tops = [100] * F
+        tops[s] = 230
+        cases.append(_case(_chunk_stack(rng, F, P, tops, flicker(s - 1, 2, 60, 100)), P, 12 - tss, "lane 63 high", seam=s))
+        for t0 in (s, s + 1):
+            cases.append(_case(_chunk_stack(rng, F, P, [255] * F, step(t0, 192, 255)), P, (2, 10)[t0 % 2], "high step", seam=s, t0=t0))
+        cases.append(_case(_chunk_stack(rng, F, P, [255] * F, flicker(s, 1, 100, 255)), P, tss, "high flicker", seam=s))
+        if F == 131 and s == 64:
+            tops = [220] * 65 + [8] * 64 + [220] * 2  # tile 1 never leaves chunk 0: every chunk after the first is skipped
+            cases.append(_case(_chunk_stack(rng, F, P, tops), P, tss, "low tile between high ones", seam=s))
+            # The same, with a second look-ahead that decides by what tile 1's last frame pushed in the high bins: nothing.
+            # Frame 64 (the last of tile 0) holds 30000 in bin 200; a flicker at 127, 128 passes its first look-ahead; the
+            # second one, frame 129 against history 127, has 3000 in bin 200 and zeros below it.  With frame 64 in that
+            # history its term is about 1 and the look-ahead fails; a history that has lost frame 64 (its count taken off
+            # once more as "frame 128's") makes it some hundreds, a trigger at 127.
+            def stale(h):
+                h[64, 200] = 30000
+                h[127:129, 2:7] += 400
+                h[129:, 7:200] = 0
+                h[129:, 200] = 3000
+            tops = [220] * 65 + [8] * 64 + [200] * 2
+            for t in (10, 2):
+                cases.append(_case(_chunk_stack(rng, F, P, tops, stale), P, t, "previous tile's last frame pushed nothing", seam=128))
+    return cases
+
+
+LARGE_P = ((16777217, 1), (4097, 4097), (8388609, 2), (2147483583, 1))  # 2^24 + 1, 4097^2, 2^24 + 2, the entry's bound
+
+
+def large_p_cases():
+    """P = W * H above 2^24, where the reference's float counter rounds: it ends one short of the exact one (the last
+    non-zero bin, one pixel, is neither pushed nor summed) or one over (the walk runs to bin 255), and a bin count above
+    2^24 is pushed rounded.  Each stack has a step, at F = 70 at the tile seam.  The cases carry their own W and H."""
+    rng = np.random.RandomState(29)
+    cases = []
+    for n, (W, H) in enumerate(LARGE_P):
+        P = W * H
+        for F in (12, 70):
+            t0 = F - 6  # 6, and 64: the seam
+            for variant in ("odd rest", "one pixel", "big bin 1", "big bin 2"):
+                h = np.zeros((F, 256), np.int64)
+                if variant == "one pixel":
+                    h[:, 5] = 1
+                else:
+                    h[:, 3:9] = rng.randint(5, 30, (F, 6))
+                    h[:, 40] = rng.randint(1, 3, F)  # the last bin holds one pixel, or two: dropped, or pushed
+                if variant.startswith("big bin"):  # in bin 1, which no term reads, or in bin 2 (NaN from there on)
+                    if P < (1 << 24) + 8000:
+                        continue  # (no bin but bin 0 can hold more than 2^24 there)
+                    big = (1 << 24) + 1 if P < (1 << 30) + 8000 else (1 << 30) + 1
+                    h[:, int(variant[-1])] = big + 2 * rng.randint(0, 2000, F)
+                for i in range(t0, F):
+                    h[i, 4:21] += 60 + 30 * (i - t0)
+                h[:, 3] += 1 - h.sum(1) % 2  # an odd number of pixels outside bin 0
+                tss = (2, 10)[(n + (F == 70)) % 2]
+                cases.append(_case(_fin(h, P), P, tss, variant, W=W, H=H, t0=t0))
     return cases
 
 
